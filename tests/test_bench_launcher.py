@@ -6,7 +6,10 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
+
+from oracle import ref_stats
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -48,6 +51,41 @@ def test_parent_makes_no_gpu_call():
     assert "import torch" not in body and "hip" not in body.lower() and "cuda" not in body
 
 
+def load_dump(d):
+    return {f[:-len(".npy")]: np.load(os.path.join(d, f)) for f in sorted(os.listdir(d))}
+
+
+def check_dump(d, stats_line, n_paths, rel=1e-12):
+    """The files --dump-outputs wrote: float32 / float64 only, 64 MB at most, the statistics records are those of the
+    terminal values beside them and the ones the JSON line reports."""
+    files = [os.path.join(d, f) for f in os.listdir(d)]
+    assert sum(os.path.getsize(f) for f in files) <= 64_000_000
+    got = load_dump(d)
+    assert all(a.dtype in (np.float32, np.float64) for a in got.values()), {k: a.dtype for k, a in got.items()}
+    term = got["terminal"]
+    assert term.dtype == np.float32 and term.shape == (1, n_paths)
+    want = ref_stats.path_stats(term[0])
+    assert got["stats_n"][0] == want["n"] == stats_line["n"] and got["stats_n_tail"][0] == want["n_tail"] == stats_line["n_tail"]
+    assert got["stats_var"][0] == want["var"] == stats_line["var95"]
+    for key in ("mean", "std", "sharpe", "cvar"):
+        assert got["stats_" + key][0] == pytest.approx(want[key], rel=rel, abs=1e-15), key
+    return got
+
+
+def test_dump_outputs_are_the_last_step_and_repeat(tmp_path):
+    """--dump-outputs after the timed steps (CPU rehearsal: the same PathEngine, the test double behind it): what the last
+    step hands its caller, and the same files from a second run with the same arguments."""
+    runs = []
+    for d in (tmp_path / "a", tmp_path / "b"):
+        r = run_bench("--gpus", "1", "--steps", "2", "--warmup", "0", "--backend", "gloo-fake", "--dump-outputs", str(d))
+        assert r.returncode == 0, r.stderr[-2000:]
+        runs.append(check_dump(d, last_json(r.stdout)["stats"], 2000))
+    a, b = runs
+    assert a.keys() == b.keys()
+    for k in a:
+        assert np.array_equal(a[k], b[k]), k
+
+
 def test_world_size_mismatch_is_an_error():
     r = run_bench("--gpus", "2", "--backend", "gloo-fake", env={"WORLD_SIZE": "1", "RANK": "0"}, timeout=120)
     assert r.returncode != 0 and "WORLD_SIZE" in r.stderr
@@ -55,13 +93,26 @@ def test_world_size_mismatch_is_an_error():
 
 @pytest.mark.gpu
 def test_gpu_bench_through_the_spawning_parent():
-    r = run_bench("--gpus", "1", "--spawn", "--steps", "3", "--warmup", "1", "--no-cpu-baseline")
+    r = run_bench("--gpus", "1", "--spawn", "--steps", "3", "--warmup", "1", "--full", "--no-cpu-baseline")
     assert r.returncode == 0, r.stderr[-3000:]
     out = last_json(r.stdout)
     assert out["n_gpus"] == 1 and out["unit"] == "paths/s" and out["value"] > 1e7
     assert out["stats"]["n"] == 1_000_000 and out["stats"]["n_tail"] == 50_000
     rf = out["roofline"]
     assert rf["peak"] == 157.3 and abs(rf["frac"] - rf["achieved"] / rf["peak"]) < 1e-12 and 0 < rf["frac"] < 1
+
+
+@pytest.mark.gpu
+def test_gpu_plain_bench_times_the_steps_only_and_dumps_its_outputs(tmp_path):
+    """A plain run: the headline line, nothing of --full, and the last timed step's outputs on disk."""
+    r = run_bench("--gpus", "1", "--steps", "3", "--warmup", "1", "--dump-outputs", str(tmp_path))
+    assert r.returncode == 0, r.stderr[-3000:]
+    out = last_json(r.stdout)
+    assert out["unit"] == "paths/s" and out["higher_is_better"] is True and out["dtype"] == "f32" and out["steps"] == 3
+    assert out["metric"].startswith("simulated paths/sec") and out["value"] > 1e7
+    assert out["value"] == pytest.approx(1_000_000 * 1e3 / out["ms_per_step"], rel=1e-9)
+    assert not {"roofline", "host_call", "cpu_baseline", "historical_sweep", "sustained"} & out.keys()
+    check_dump(str(tmp_path), out["stats"], 1_000_000)
 
 
 @pytest.mark.gpu
