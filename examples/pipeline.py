@@ -41,9 +41,12 @@ def main(paths, resample_rule="M", user_rf=3.0, investment=10000.0, seed=12345, 
 
     w = res["Monte Carlo"]["weights"]
     mu_step, cov_step = returns_df.mean().values, returns_df.cov().values  # per period, before annualising
-    sim = mcp.simulate_paths(mu_step, cov_step, w, n_steps=af, n_paths=n_paths, seed=seed, v0=investment, rf=user_rf / 100)
+    sim = mcp.simulate_paths(mu_step, cov_step, w, n_steps=af, n_paths=n_paths, seed=seed, v0=investment, rf=user_rf / 100,
+                             drawdown=True)
     print(f"max-Sharpe weights on {n_paths:,} simulated {af}-period paths: mean {sim['mean']:+.4f}  std {sim['std']:.4f}  "
           f"VaR95 {sim['var']:+.4f}  CVaR95 {sim['cvar']:+.4f}  Sharpe {sim['sharpe']:.4f}")
+    dd = sim["drawdown"]                  # max drawdown of every path before the horizon (SPEC.md 4.2 / 5.1)
+    print(f"  max drawdown: mean {dd['mean']:+.4f}  DaR95 {dd['dar']:+.4f}  CDaR95 {dd['cdar']:+.4f}  worst {dd['worst']:+.4f}")
     return res, sim
 
 

@@ -79,9 +79,11 @@ with tab_sweep:                                               # app.py:655-783
     w = results["Monte Carlo"]["weights"]
     mu_step, cov_step = returns_df.mean().values, returns_df.cov().values          # per period (app.py:679-680 before annualising)
     sim = mcp.simulate_paths(mu_step, cov_step, w, n_steps=annual_factor, n_paths=n_paths, seed=12345,
-                             v0=state["investment_amount"], rf=user_rf / 100.0)
+                             v0=state["investment_amount"], rf=user_rf / 100.0, drawdown=True)
     st.subheader("max-Sharpe weights on simulated one-year paths (MI355X path engine)")
     st.write({k: sim[k] for k in ("n", "mean", "std", "sharpe", "var", "cvar", "min", "max")})
+    st.write({"max drawdown: mean": sim["drawdown"]["mean"], "DaR": sim["drawdown"]["dar"], "CDaR": sim["drawdown"]["cdar"],
+              "worst": sim["drawdown"]["worst"]})
 
 with tab_forecast:                                            # app.py:785-809
     st.info("ARIMA/GARCH forecasting is outside the scope of this package (SURVEY.md section 2, component 11).")

@@ -23,7 +23,7 @@
 extern "C" {
 #endif
 
-#define MCP_ABI_VERSION 3
+#define MCP_ABI_VERSION 4        /* 4: + mcp_simulate_drawdown, mcp_launch_paths_drawdown (additive) */
 #define MCP_MAX_ASSETS 64        /* thread-per-path kernels are instantiated for N4 = 4..64 */
 #define MCP_SELECT_BINS 2048     /* radix-select digit: 11 + 11 + 10 bits */
 
@@ -142,6 +142,22 @@ int mcp_simulate(mcp_ctx *ctx, const mcp_params *prm,
                  float *terminal_out,  /* NULL or host [K*n_paths] */
                  mcp_stats *stats_out  /* [K] */);
 
+/* mcp_simulate plus the max drawdown of every path (SPEC.md 4.2) reduced per portfolio as the reference's VaR / CVaR reduce
+ * a sample (SPEC.md 5.1): dd_stats_out[k] is an mcp_stats over mdd (var = DaR, cvar = CDaR, n_tail, mean, std, min = worst,
+ * max = best, x_lo / x_hi; sharpe = 0).  mdd_out: NULL or host [K*n_paths] floats, the kernels' raw per-path q (simple
+ * compounding: mdd = q - 1) or d (log: mdd = expm1(d)).  terminal_out / stats_out are what mcp_simulate returns, with the
+ * same V_T; for K >= 17 the moments (mean, m2, std, sharpe) agree with mcp_simulate's to fp64 association only, everything
+ * else exactly.  Costs: the path kernels keep the running peak in registers (one IEEE division per step and portfolio),
+ * K >= 17 runs as passes of the 8-portfolio kernel instead of the MFMA sweep kernels, a second select pipeline reduces the
+ * drawdowns, and the terminal budget counts 8 B per path and portfolio.  MCP_FLAG_FOLD / MCP_FLAG_NATIVE_MATH:
+ * MCP_E_UNSUPPORTED. */
+int mcp_simulate_drawdown(mcp_ctx *ctx, const mcp_params *prm, const float *mu, const float *chol, const float *W,
+                          uint64_t seed, uint64_t path_begin, uint64_t n_paths,
+                          float *terminal_out,     /* NULL or host [K*n_paths] */
+                          mcp_stats *stats_out,    /* [K] */
+                          float *mdd_out,          /* NULL or host [K*n_paths]: q or d */
+                          mcp_stats *dd_stats_out  /* [K] */);
+
 /* The reference's own sweep (app.py:699-717) over HISTORICAL returns, loop body app.py:708-713 for P weight
  * vectors at once, binary64 like the reference.  returns: [R*N] row-major (returns_df.values, app.py:667),
  * mean/cov: the annualised mean_returns / cov_matrix of app.py:679-680, W: [P*N] (rows as drawn at
@@ -199,6 +215,14 @@ int mcp_pivots(const mcp_params *prm, const float *mu, const float *chol, const 
 int mcp_launch_paths(const mcp_params *prm, const float *d_packed, const double *d_pivot, uint64_t seed, uint64_t path_begin,
                      uint64_t n_paths, float *d_terminal, uint64_t terminal_stride, void *d_partials, void *d_hist,
                      void *stream);
+/* mcp_launch_paths that also stores the per-path drawdown state of SPEC.md 4.2 into d_mdd ([K][mdd_stride] floats, q or d;
+ * mdd_stride >= n_paths).  Always the one-lane-per-path kernels (K >= 17: passes of 8 portfolios, whose moment partials keep
+ * the mcp_moment_slots(K, n) layout).  To reduce the drawdowns: mcp_launch_pass0 over d_mdd with a copy of the parameters
+ * with v0 = 1, rf = 0 and d_pivot NULL, then the usual scan / hist / final steps (x = q - 1 or expm1(d) is then exactly the
+ * drawdown).  MCP_FLAG_FOLD / MCP_FLAG_NATIVE_MATH: MCP_E_UNSUPPORTED. */
+int mcp_launch_paths_drawdown(const mcp_params *prm, const float *d_packed, const double *d_pivot, uint64_t seed,
+                              uint64_t path_begin, uint64_t n_paths, float *d_terminal, uint64_t terminal_stride,
+                              float *d_mdd, uint64_t mdd_stride, void *d_partials, void *d_hist, void *stream);
 
 /* np.percentile(x, (1-alpha)*100) bookkeeping (numpy 2.2 `_compute_virtual_index`/`_get_indexes`,
  * method 'linear'; the q of app.py:259): ranks of the two order statistics and the weight. */

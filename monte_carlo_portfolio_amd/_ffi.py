@@ -17,7 +17,7 @@ _PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MCP_LIB_PATH") or os.path.join(_PKG, "libmcport.so")     # MCP_LIB_PATH: a lab build (tools/kernel_lab.py)
 CSRC = os.path.join(_PKG, "csrc")
 
-MCP_ABI_VERSION = 3
+MCP_ABI_VERSION = 4
 MCP_MAX_ASSETS = 64
 MCP_SELECT_BINS = 2048
 MCP_COMPOUND = {"simple": 0, "log": 1}
@@ -95,6 +95,8 @@ SIGNATURES = {
     "mcp_packed_len": (ctypes.c_size_t, [_int, _int]),
     "mcp_pack_params": (_int, [_int, _int, _f32p, _f32p, _f32p, _f32p, ctypes.c_size_t]),
     "mcp_launch_paths": (_int, [_PP, _vp, _vp, _u64, _u64, _u64, _vp, _u64, _vp, _vp, _vp]),
+    "mcp_simulate_drawdown": (_int, [_vp, _PP, _f32p, _f32p, _f32p, _u64, _u64, _u64, _vp, _vp, _vp, _vp]),
+    "mcp_launch_paths_drawdown": (_int, [_PP, _vp, _vp, _u64, _u64, _u64, _vp, _u64, _vp, _u64, _vp, _vp, _vp]),
     "mcp_percentile_rank": (_int, [_u64, ctypes.c_double, ctypes.POINTER(_u64), ctypes.POINTER(_u64),
                                    ctypes.POINTER(ctypes.c_double)]),
     "mcp_launch_pass0": (_int, [_PP, _vp, _u64, _u64, _vp, _vp, _vp, _vp]),

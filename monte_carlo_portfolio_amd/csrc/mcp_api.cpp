@@ -108,6 +108,11 @@ const mcp::launch_paths_fn k_launch[16] = {
     mcp::launch_paths_nb5,  mcp::launch_paths_nb6,  mcp::launch_paths_nb7,  mcp::launch_paths_nb8,
     mcp::launch_paths_nb9,  mcp::launch_paths_nb10, mcp::launch_paths_nb11, mcp::launch_paths_nb12,
     mcp::launch_paths_nb13, mcp::launch_paths_nb14, mcp::launch_paths_nb15, mcp::launch_paths_nb16};
+const mcp::launch_paths_dd_fn k_launch_dd[16] = {
+    mcp::launch_paths_dd_nb1,  mcp::launch_paths_dd_nb2,  mcp::launch_paths_dd_nb3,  mcp::launch_paths_dd_nb4,
+    mcp::launch_paths_dd_nb5,  mcp::launch_paths_dd_nb6,  mcp::launch_paths_dd_nb7,  mcp::launch_paths_dd_nb8,
+    mcp::launch_paths_dd_nb9,  mcp::launch_paths_dd_nb10, mcp::launch_paths_dd_nb11, mcp::launch_paths_dd_nb12,
+    mcp::launch_paths_dd_nb13, mcp::launch_paths_dd_nb14, mcp::launch_paths_dd_nb15, mcp::launch_paths_dd_nb16};
 
 // Inverse-CDF coefficient table (SPEC.md section 3; DATA of the spec, generated by tools/fit_icdf_table.py): one
 // device-resident copy per device, uploaded on first use on the caller's stream.  The first call on a device
@@ -176,6 +181,11 @@ struct Shard {
   size_t h_pivot_cap = 0;
   mcp_stats* h_stats = nullptr;            // pinned AND mapped: ws[MCP_WS_STATS] is its device address, so the last kernel
   size_t h_stats_cap = 0;                  // of a pass writes the [K] records straight into host memory (no copy-back)
+  float* d_mdd = nullptr;                  // drawdown calls: [K tile][paths] q / d of SPEC.md 4.2
+  size_t mdd_cap = 0;
+  mcp_stats* h_dd_stats = nullptr;         // drawdown calls: the drawdown statistics, pinned and mapped like h_stats
+  size_t h_dd_stats_cap = 0;
+  void* d_dd_stats = nullptr;              // device address of h_dd_stats
 };
 
 // RCCL entry points, resolved at run time (no link-time dependency: a single-device user never loads librccl).
@@ -331,10 +341,22 @@ int mcp_pivots(const mcp_params* prm, const float* mu, const float* chol, const 
   return MCP_OK;
 }
 
-int mcp_launch_paths(const mcp_params* prm, const float* d_packed, const double* d_pivot, uint64_t seed, uint64_t path_begin,
-                     uint64_t n_paths, float* d_terminal, uint64_t stride, void* d_partials, void* d_hist, void* stream) {
+}  // extern "C"
+
+// mcp_launch_paths (d_mdd NULL) and mcp_launch_paths_drawdown.  A drawdown launch always runs mc_paths_dd_kernel, K >= 17 as
+// passes of the 8-portfolio kernel: the MFMA sweep kernels do not track the path's peak.  Its moment partials keep the layout
+// mcp_moment_slots(K, n) gives (what mcp_launch_scan reads): where that is one slot per 64-path tile (K >= 17), an empty pass 0
+// first pads every slot, and the path kernel's workgroups overwrite the first path_grid(n) of them.
+static int launch_paths_impl(const mcp_params* prm, const float* d_packed, const double* d_pivot, uint64_t seed, uint64_t path_begin,
+                             uint64_t n_paths, float* d_terminal, uint64_t stride, float* d_mdd, uint64_t mdd_stride, void* d_partials,
+                             void* d_hist, void* stream) {
+  const bool dd = d_mdd != nullptr;
   if (int rc = check_params(prm)) return rc;
   if (!d_packed || !d_terminal) return fail(MCP_E_ARG, "NULL device pointer");
+  if (dd && (prm->flags & (MCP_FLAG_FOLD | MCP_FLAG_NATIVE_MATH)))
+    return fail(MCP_E_UNSUPPORTED, "the drawdown runs on the spec's normals and the unfolded recurrence (no MCP_FLAG_FOLD / MCP_FLAG_NATIVE_MATH)");
+  if (dd && mdd_stride < n_paths) return fail(MCP_E_ARG, "mdd_stride %llu < n_paths %llu", (unsigned long long)mdd_stride,
+                                              (unsigned long long)n_paths);
   if ((d_partials == nullptr) != (d_hist == nullptr)) return fail(MCP_E_ARG, "d_partials and d_hist go together (both or neither)");
   if (n_paths < 1) return fail(MCP_E_ARG, "n_paths must be >= 1");
   if (stride < n_paths) return fail(MCP_E_ARG, "terminal_stride %llu < n_paths %llu",
@@ -359,14 +381,14 @@ int mcp_launch_paths(const mcp_params* prm, const float* d_packed, const double*
   DeviceGuard guard(dev);                 // the stream may belong to another device than the thread's current one
   if (guard.err != hipSuccess) return fail(MCP_E_HIP, "hipSetDevice(%d): %s", dev, hipGetErrorString(guard.err));
   if (int rc = device_tables(dev, (hipStream_t)stream, &tables)) return rc;
-  const bool sweep = uses_sweep(K);
+  const bool sweep = !dd && uses_sweep(K);
   a.tables = tables;
   a.packed = d_packed;
   a.terminal = d_terminal;
   a.pivot = d_pivot;
   a.partials = (mcp::MomentPartial*)d_partials;
   a.hist = sweep ? nullptr : (unsigned long long*)d_hist;     // the sweep kernels leave digit 0 to hist(0) below
-  a.slots = mcp::moment_slots(sweep, n_paths);
+  a.slots = dd ? mcp_moment_slots(K, n_paths) : mcp::moment_slots(sweep, n_paths);
   a.v0d = (double)(float)prm->v0;
   a.inv_v0d = 1.0 / a.v0d;
   { int e = 0; a.v0_pow2 = std::frexp(a.v0d, &e) == 0.5; }
@@ -398,12 +420,42 @@ int mcp_launch_paths(const mcp_params* prm, const float* d_packed, const double*
     }
     return MCP_OK;
   }
+  if (dd) {
+    if (d_partials && a.slots > (uint64_t)grid)
+      HIP_TRY(mcp::launch_pass0(*prm, K, d_terminal, stride, 0, nullptr, a.slots, (mcp::MomentPartial*)d_partials,
+                                (unsigned long long*)d_hist, (hipStream_t)stream));
+    mcp::PathArgsDD ad;
+    static_cast<mcp::PathArgs&>(ad) = a;
+    ad.mdd = d_mdd;
+    ad.mdd_stride = mdd_stride;
+    for (int kb = 0; kb < K; kb += kt) {
+      ad.k_begin = kb;
+      hipError_t e = k_launch_dd[nb - 1](variant, ad, grid, (hipStream_t)stream);
+      if (e != hipSuccess) return fail(MCP_E_HIP, "mc_paths_dd_kernel launch: %s", hipGetErrorString(e));
+    }
+    return MCP_OK;
+  }
   for (int kb = 0; kb < K; kb += kt) {
     a.k_begin = kb;
     hipError_t e = k_launch[nb - 1](variant, a, grid, (hipStream_t)stream);
     if (e != hipSuccess) return fail(MCP_E_HIP, "mc_paths_kernel launch: %s", hipGetErrorString(e));
   }
   return MCP_OK;
+}
+
+extern "C" {
+
+int mcp_launch_paths(const mcp_params* prm, const float* d_packed, const double* d_pivot, uint64_t seed, uint64_t path_begin,
+                     uint64_t n_paths, float* d_terminal, uint64_t stride, void* d_partials, void* d_hist, void* stream) {
+  return launch_paths_impl(prm, d_packed, d_pivot, seed, path_begin, n_paths, d_terminal, stride, nullptr, 0, d_partials, d_hist, stream);
+}
+
+int mcp_launch_paths_drawdown(const mcp_params* prm, const float* d_packed, const double* d_pivot, uint64_t seed, uint64_t path_begin,
+                              uint64_t n_paths, float* d_terminal, uint64_t terminal_stride, float* d_mdd, uint64_t mdd_stride,
+                              void* d_partials, void* d_hist, void* stream) {
+  if (!d_mdd) return fail(MCP_E_ARG, "d_mdd is NULL");
+  return launch_paths_impl(prm, d_packed, d_pivot, seed, path_begin, n_paths, d_terminal, terminal_stride, d_mdd, mdd_stride,
+                           d_partials, d_hist, stream);
 }
 
 // Launches below go to the device that owns the stream.
@@ -559,6 +611,8 @@ static void free_shard(Shard& sh) {
   if (sh.h_packed) (void)hipHostFree(sh.h_packed);
   if (sh.h_pivot) (void)hipHostFree(sh.h_pivot);
   if (sh.h_stats) (void)hipHostFree(sh.h_stats);
+  if (sh.d_mdd) (void)hipFree(sh.d_mdd);
+  if (sh.h_dd_stats) (void)hipHostFree(sh.h_dd_stats);
 }
 
 int mcp_ctx_create_multi(const int* devices, int ndev, mcp_ctx** out) {
@@ -759,12 +813,57 @@ int exchange_records(mcp_ctx* c, int kt) {
   return MCP_OK;
 }
 
+// The select / exchange / record phase of one tile, over the [kt][pn] array of every active shard whose moment partials and
+// digit-0 histogram are in the shard's work buffers: three descents of the radix select, exchanges between the steps when the
+// tile is path-sharded (`exchange`), and the [kt] statistics into each shard's mapped host buffer (merged on shard 0 when
+// path-sharded).  `dd`: the drawdown array (SPEC.md 5.1; tp carries v0 = 1, rf = 0, no pivot) instead of the terminal values.
+// When it runs a second time, on the drawdown, the histogram exchange that opens it also orders every shard's work after
+// shard 0's copies of the first phase's records (same-device exchange).
+int run_select(mcp_ctx* c, const std::vector<mcp_params>& tp, const std::vector<Job>& jobs, bool exchange, uint64_t lo, uint64_t hi,
+               double gamma, bool dd) {
+  const size_t S = c->sh.size();
+  int rc;
+  const int kt_x = jobs[0].kt;                 // path-sharded tiles: the same portfolios on every shard
+  for (int pass = 0; pass < 3; pass++) {
+    if (exchange && (rc = exchange_hist(c, kt_x))) return rc;
+    for (size_t s = 0; s < S; s++) {
+      const Job& j = jobs[s];
+      if (!j.active) continue;
+      Shard& sh = c->sh[s];
+      HIP_TRY(hipSetDevice(sh.device));
+      const uint64_t stride = j.pn ? j.pn : 1;
+      const double* piv = dd ? nullptr : (const double*)sh.ws[MCP_WS_PIVOT];
+      const float* src = dd ? sh.d_mdd : sh.d_terminal;
+      if (pass < 2) {
+        if ((rc = mcp_launch_scan(&tp[s], pass, j.pn, lo, hi, sh.ws[MCP_WS_PARTIALS], sh.ws[MCP_WS_BELOW], piv, sh.ws[MCP_WS_HIST],
+                                  sh.ws[MCP_WS_STATE], sh.ws[MCP_WS_RECORD], sh.stream))) return rc;
+        if ((rc = mcp_launch_hist(&tp[s], pass + 1, src, stride, j.pn, sh.ws[MCP_WS_STATE], piv, sh.ws[MCP_WS_BELOW],
+                                  sh.ws[MCP_WS_HIST], sh.stream))) return rc;
+      } else {
+        void* stats = exchange ? nullptr : (dd ? sh.d_dd_stats : sh.ws[MCP_WS_STATS]);
+        if ((rc = mcp_launch_final(&tp[s], j.pn, gamma, lo, hi, sh.ws[MCP_WS_BELOW], sh.ws[MCP_WS_HIST], sh.ws[MCP_WS_STATE],
+                                   sh.ws[MCP_WS_RECORD], sh.ws[MCP_WS_QUANT], stats, sh.stream)))
+          return rc;
+      }
+    }
+  }
+  // finish: merged records on shard 0 (path-sharded) or each shard's own records (portfolio-sharded / one shard)
+  if (exchange) {
+    if ((rc = exchange_records(c, kt_x))) return rc;
+    Shard& s0 = c->sh[0];
+    HIP_TRY(hipSetDevice(s0.device));
+    if ((rc = mcp_launch_stats(&tp[0], (int)S, s0.d_gather, s0.ws[MCP_WS_QUANT], dd ? s0.d_dd_stats : s0.ws[MCP_WS_STATS], s0.stream)))
+      return rc;
+  }
+  return MCP_OK;
+}
+
 // One tile: every active shard simulates its (portfolios x paths) block -- the kernels' epilogue leaves the moment partials
-// and the digit-0 histogram -- and the rest of the statistics pipeline runs, with the exchanges between the steps when the
-// tile is path-sharded (`exchange`).
+// and the digit-0 histogram -- and the rest of the statistics pipeline runs (run_select).  `dd`: the path kernels also leave
+// the drawdown array, and after the terminal values a pass 0 over it and a second run_select reduce it to dd_stats_out.
 int run_tile(mcp_ctx* c, const mcp_params* prm, const float* mu, const float* chol, const float* W, uint64_t seed,
              uint64_t path_begin, uint64_t n_total, const std::vector<Job>& jobs, bool exchange, float* terminal_out,
-             mcp_stats* stats_out) {
+             mcp_stats* stats_out, bool dd, float* mdd_out, mcp_stats* dd_stats_out) {
   const size_t S = c->sh.size();
   uint64_t lo, hi;
   double gamma;
@@ -791,6 +890,13 @@ int run_tile(mcp_ctx* c, const mcp_params* prm, const float* mu, const float* ch
       if ((rc = grow_host((void**)&sh.h_stats, &sh.h_stats_cap, (size_t)j.kt * sizeof(mcp_stats), true))) return rc;
       HIP_TRY(hipHostGetDevicePointer(&sh.ws[MCP_WS_STATS], sh.h_stats, 0));
     }
+    if (dd) {
+      if ((rc = grow_dev((void**)&sh.d_mdd, &sh.mdd_cap, (size_t)j.kt * (j.pn ? j.pn : 1) * sizeof(float)))) return rc;
+      if ((size_t)j.kt * sizeof(mcp_stats) > sh.h_dd_stats_cap) {
+        if ((rc = grow_host((void**)&sh.h_dd_stats, &sh.h_dd_stats_cap, (size_t)j.kt * sizeof(mcp_stats), true))) return rc;
+        HIP_TRY(hipHostGetDevicePointer(&sh.d_dd_stats, sh.h_dd_stats, 0));
+      }
+    }
   }
   // 1b. parameters up and the path kernels out, device after device with nothing else in between: every GPU should be
   //     simulating as early as possible.  Shards of a path-sharded tile share one packed block and one pivot vector
@@ -816,43 +922,30 @@ int run_tile(mcp_ctx* c, const mcp_params* prm, const float* mu, const float* ch
     HIP_TRY(hipMemcpyAsync(sh.d_packed, src, plen * sizeof(float), hipMemcpyHostToDevice, sh.stream));
     HIP_TRY(hipMemcpyAsync(sh.ws[MCP_WS_PIVOT], psrc, (size_t)j.kt * sizeof(double), hipMemcpyHostToDevice, sh.stream));
     if (j.pn) {
-      if ((rc = mcp_launch_paths(&tp[s], sh.d_packed, (const double*)sh.ws[MCP_WS_PIVOT], seed, path_begin + j.p0, j.pn, sh.d_terminal,
-                                 j.pn, sh.ws[MCP_WS_PARTIALS], sh.ws[MCP_WS_HIST], sh.stream))) return rc;
+      if ((rc = launch_paths_impl(&tp[s], sh.d_packed, (const double*)sh.ws[MCP_WS_PIVOT], seed, path_begin + j.p0, j.pn, sh.d_terminal,
+                                  j.pn, dd ? sh.d_mdd : nullptr, j.pn, sh.ws[MCP_WS_PARTIALS], sh.ws[MCP_WS_HIST], sh.stream))) return rc;
     } else {
       // a shard without paths (fewer paths than shards): empty moment partials, nothing in the histogram
       if ((rc = mcp_launch_pass0(&tp[s], sh.d_terminal, 1, 0, (const double*)sh.ws[MCP_WS_PIVOT], sh.ws[MCP_WS_PARTIALS],
                                  sh.ws[MCP_WS_HIST], sh.stream))) return rc;
     }
   }
-  // 2. three descents of the radix select, exchanges between the steps
-  const int kt_x = jobs[0].kt;                 // path-sharded tiles: the same portfolios on every shard
-  for (int pass = 0; pass < 3; pass++) {
-    if (exchange && (rc = exchange_hist(c, kt_x))) return rc;
+  // 2. the terminal values' select, exchanges and records
+  if ((rc = run_select(c, tp, jobs, exchange, lo, hi, gamma, false))) return rc;
+  // 3. drawdown (SPEC.md 5.1): the same pipeline over q / d -- x = q - 1 (simple, v0 = 1) or expm1(d) (log), no pivot, no rf
+  std::vector<mcp_params> tpd(tp);
+  if (dd) {
     for (size_t s = 0; s < S; s++) {
+      tpd[s].v0 = 1.0;
+      tpd[s].rf = 0.0;
       const Job& j = jobs[s];
       if (!j.active) continue;
       Shard& sh = c->sh[s];
       HIP_TRY(hipSetDevice(sh.device));
-      const uint64_t stride = j.pn ? j.pn : 1;
-      const double* piv = (const double*)sh.ws[MCP_WS_PIVOT];
-      if (pass < 2) {
-        if ((rc = mcp_launch_scan(&tp[s], pass, j.pn, lo, hi, sh.ws[MCP_WS_PARTIALS], sh.ws[MCP_WS_BELOW], piv, sh.ws[MCP_WS_HIST],
-                                  sh.ws[MCP_WS_STATE], sh.ws[MCP_WS_RECORD], sh.stream))) return rc;
-        if ((rc = mcp_launch_hist(&tp[s], pass + 1, sh.d_terminal, stride, j.pn, sh.ws[MCP_WS_STATE], piv, sh.ws[MCP_WS_BELOW],
-                                  sh.ws[MCP_WS_HIST], sh.stream))) return rc;
-      } else {
-        if ((rc = mcp_launch_final(&tp[s], j.pn, gamma, lo, hi, sh.ws[MCP_WS_BELOW], sh.ws[MCP_WS_HIST], sh.ws[MCP_WS_STATE],
-                                   sh.ws[MCP_WS_RECORD], sh.ws[MCP_WS_QUANT], exchange ? nullptr : sh.ws[MCP_WS_STATS], sh.stream)))
-          return rc;
-      }
+      if ((rc = mcp_launch_pass0(&tpd[s], sh.d_mdd, j.pn ? j.pn : 1, j.pn, nullptr, sh.ws[MCP_WS_PARTIALS], sh.ws[MCP_WS_HIST], sh.stream)))
+        return rc;
     }
-  }
-  // 3. finish: merged records on shard 0 (path-sharded) or each shard's own records (portfolio-sharded / one shard)
-  if (exchange) {
-    if ((rc = exchange_records(c, kt_x))) return rc;
-    Shard& s0 = c->sh[0];
-    HIP_TRY(hipSetDevice(s0.device));
-    if ((rc = mcp_launch_stats(&tp[0], (int)S, s0.d_gather, s0.ws[MCP_WS_QUANT], s0.ws[MCP_WS_STATS], s0.stream))) return rc;
+    if ((rc = run_select(c, tpd, jobs, exchange, lo, hi, gamma, true))) return rc;
   }
   for (size_t s = 0; s < S; s++) {
     const Job& j = jobs[s];
@@ -863,32 +956,42 @@ int run_tile(mcp_ctx* c, const mcp_params* prm, const float* mu, const float* ch
     if (terminal_out && j.pn)
       HIP_TRY(hipMemcpy2DAsync(terminal_out + (size_t)j.k0 * n_total + j.p0, n_total * sizeof(float), sh.d_terminal,
                                j.pn * sizeof(float), j.pn * sizeof(float), (size_t)j.kt, hipMemcpyDeviceToHost, sh.stream));
+    if (dd && mdd_out && j.pn)
+      HIP_TRY(hipMemcpy2DAsync(mdd_out + (size_t)j.k0 * n_total + j.p0, n_total * sizeof(float), sh.d_mdd,
+                               j.pn * sizeof(float), j.pn * sizeof(float), (size_t)j.kt, hipMemcpyDeviceToHost, sh.stream));
   }
   for (size_t s = 0; s < S; s++)
     if (jobs[s].active) { HIP_TRY(hipSetDevice(c->sh[s].device)); HIP_TRY(hipStreamSynchronize(c->sh[s].stream)); }
   for (size_t s = 0; s < S; s++)
-    if (jobs[s].active && (!exchange || s == 0))
+    if (jobs[s].active && (!exchange || s == 0)) {
       memcpy(stats_out + jobs[s].k0, c->sh[s].h_stats, (size_t)jobs[s].kt * sizeof(mcp_stats));
+      if (dd) {
+        memcpy(dd_stats_out + jobs[s].k0, c->sh[s].h_dd_stats, (size_t)jobs[s].kt * sizeof(mcp_stats));
+        for (int k = 0; k < jobs[s].kt; k++) dd_stats_out[jobs[s].k0 + k].sharpe = 0.0;
+      }
+    }
   return MCP_OK;
 }
 
-// Portfolios per tile so that kt * n_paths * 4 B fits the budget: whole 512-portfolio workgroups of the MFMA sweep
-// kernel when K is tiled at all.
-int tile_portfolios(size_t budget, uint64_t n_paths, int K) {
-  const uint64_t fit = budget / (sizeof(float) * (n_paths ? n_paths : 1));
+// Portfolios per tile so that kt * n_paths * bytes_per_path fits the budget (4 B of V_T, 8 B with the drawdown array): whole
+// 512-portfolio workgroups of the MFMA sweep kernel when K is tiled at all.
+int tile_portfolios(size_t budget, uint64_t n_paths, int K, size_t bytes_per_path = sizeof(float)) {
+  const uint64_t fit = budget / (bytes_per_path * (n_paths ? n_paths : 1));
   if (fit >= (uint64_t)K) return K;
   if (fit >= (uint64_t)K_PAD) return (int)(fit / K_PAD) * K_PAD;
   return fit >= 1 ? (int)fit : 1;
 }
 
-}  // namespace
-
-int mcp_simulate(mcp_ctx* c, const mcp_params* prm, const float* mu, const float* chol, const float* W,
-                 uint64_t seed, uint64_t path_begin, uint64_t n_paths, float* terminal_out, mcp_stats* stats_out) {
+int simulate_impl(mcp_ctx* c, const mcp_params* prm, const float* mu, const float* chol, const float* W, uint64_t seed,
+                  uint64_t path_begin, uint64_t n_paths, float* terminal_out, mcp_stats* stats_out, bool dd, float* mdd_out,
+                  mcp_stats* dd_stats_out) {
   if (!c) return fail(MCP_E_ARG, "ctx is NULL");
   if (int rc = check_params(prm)) return rc;
-  if (!mu || !chol || !W || !stats_out) return fail(MCP_E_ARG, "NULL pointer");
+  if (!mu || !chol || !W || !stats_out || (dd && !dd_stats_out)) return fail(MCP_E_ARG, "NULL pointer");
   if (n_paths < 1) return fail(MCP_E_ARG, "n_paths must be >= 1");
+  if (dd && (prm->flags & (MCP_FLAG_FOLD | MCP_FLAG_NATIVE_MATH)))
+    return fail(MCP_E_UNSUPPORTED, "the drawdown runs on the spec's normals and the unfolded recurrence (no MCP_FLAG_FOLD / MCP_FLAG_NATIVE_MATH)");
+  const size_t bytes_per_path = dd ? 2 * sizeof(float) : sizeof(float);
   std::lock_guard<std::mutex> lock(c->mu);
   const size_t S = c->sh.size();
   const int K = prm->n_portfolios;
@@ -907,12 +1010,12 @@ int mcp_simulate(mcp_ctx* c, const mcp_params* prm, const float* mu, const float
         const int left = kb[s + 1] - kb[s] - done[s];
         jobs[s] = Job();
         if (left <= 0) continue;
-        const int kt = std::min(left, tile_portfolios(c->terminal_budget, n_paths, left));
+        const int kt = std::min(left, tile_portfolios(c->terminal_budget, n_paths, left, bytes_per_path));
         jobs[s].k0 = kb[s] + done[s]; jobs[s].kt = kt; jobs[s].p0 = 0; jobs[s].pn = n_paths; jobs[s].active = true;
         done[s] += kt;
         more = true;
       }
-      if (more) rc = run_tile(c, prm, mu, chol, W, seed, path_begin, n_paths, jobs, false, terminal_out, stats_out);
+      if (more) rc = run_tile(c, prm, mu, chol, W, seed, path_begin, n_paths, jobs, false, terminal_out, stats_out, dd, mdd_out, dd_stats_out);
     }
   } else {
     // the path range is sharded; all shards see the same tile of portfolios
@@ -923,16 +1026,18 @@ int mcp_simulate(mcp_ctx* c, const mcp_params* prm, const float* mu, const float
       jobs[s].active = true;
       pn_max = std::max(pn_max, jobs[s].pn);
     }
-    const int kt_max = tile_portfolios(c->terminal_budget, pn_max, K);
+    const int kt_max = tile_portfolios(c->terminal_budget, pn_max, K, bytes_per_path);
     rc = ensure_exchange(c);
     for (int k0 = 0; k0 < K && rc == MCP_OK; k0 += kt_max) {
       for (size_t s = 0; s < S; s++) { jobs[s].k0 = k0; jobs[s].kt = std::min(kt_max, K - k0); }
-      rc = run_tile(c, prm, mu, chol, W, seed, path_begin, n_paths, jobs, S > 1 || c->exchange_always, terminal_out, stats_out);
+      rc = run_tile(c, prm, mu, chol, W, seed, path_begin, n_paths, jobs, S > 1 || c->exchange_always, terminal_out, stats_out, dd,
+                    mdd_out, dd_stats_out);
     }
   }
   if (rc != MCP_OK) {
     // Leave no work in flight behind a failed call, and restore the invariant of the read-and-clear protocol: a pass that
-    // stopped half way may have left counts in the histograms, and the next call would add to them.
+    // stopped half way may have left counts in the histograms, and the next call would add to them.  (Both selects of a
+    // drawdown call -- terminal values and drawdowns -- share these buffers.)
     const std::string why = g_err;
     for (Shard& sh : c->sh) { (void)hipSetDevice(sh.device); (void)hipStreamSynchronize(sh.stream); }
     for (Shard& sh : c->sh) {
@@ -946,6 +1051,19 @@ int mcp_simulate(mcp_ctx* c, const mcp_params* prm, const float* mu, const float
   }
   (void)hipSetDevice(prev_dev);
   return rc;
+}
+
+}  // namespace
+
+int mcp_simulate(mcp_ctx* c, const mcp_params* prm, const float* mu, const float* chol, const float* W,
+                 uint64_t seed, uint64_t path_begin, uint64_t n_paths, float* terminal_out, mcp_stats* stats_out) {
+  return simulate_impl(c, prm, mu, chol, W, seed, path_begin, n_paths, terminal_out, stats_out, false, nullptr, nullptr);
+}
+
+int mcp_simulate_drawdown(mcp_ctx* c, const mcp_params* prm, const float* mu, const float* chol, const float* W, uint64_t seed,
+                          uint64_t path_begin, uint64_t n_paths, float* terminal_out, mcp_stats* stats_out, float* mdd_out,
+                          mcp_stats* dd_stats_out) {
+  return simulate_impl(c, prm, mu, chol, W, seed, path_begin, n_paths, terminal_out, stats_out, true, mdd_out, dd_stats_out);
 }
 
 int mcp_sweep_historical(mcp_ctx* c, int N, int R, int P, const double* returns, const double* mean, const double* cov,

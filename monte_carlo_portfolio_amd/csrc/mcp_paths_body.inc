@@ -1,0 +1,244 @@
+// mcp_paths_body.inc -- the body of the path kernels of mcp_paths.h, included textually by mc_paths_kernel (DD = false) and
+// mc_paths_dd_kernel (DD = true).  As a shared __device__ function the plain kernel's registers came out allocated differently;
+// included, the DD = false kernel compiles to the same instructions as before the drawdown existed.  In scope: the template
+// parameters NB, KT, PPT, NATIVE, FOLD, LOGC, DD and the kernel argument `a` (PathArgs, or PathArgsDD which starts with one).
+  constexpr int N4 = 4 * NB;
+  // wave-uniform parameters through the constant address space -> s_load_dword* into SGPRs
+  typedef const __attribute__((address_space(4))) float* cfloat_p;
+  cfloat_p mu = (cfloat_p)a.packed;
+  cfloat_p Lp = mu + N4;
+  cfloat_p Wk = mu + N4 + N4 * (N4 / 2 + 1) + (size_t)a.k_begin * N4;
+  const int kt = min(KT, a.n_portfolios - a.k_begin);   // live portfolios in this pass (uniform)
+  // inverse-CDF table: 16.5 KiB of LDS per block, filled once from the device-resident copy
+  __shared__ float4 s_tab[ICDF_LDS_ENTRIES];
+  if constexpr (!NATIVE) {
+    for (int i = threadIdx.x; i < ICDF_ENTRIES; i += PATH_BLOCK) s_tab[ICDF_PAD + i] = a.tables[i];
+  }
+  // The 512 B of padding in front of the table hold the drift (and, for one portfolio, the weights): read from LDS they
+  // land in VGPRs without a VALU instruction (a v_mov from an SGPR costs an issue slot, an SGPR operand halves the
+  // issue rate of the weight-dot FMAs).
+  constexpr bool LDS_MU = MCP_EXP_LDSPAR >= 1 && !NATIVE && !FOLD;
+  constexpr bool LDS_W = MCP_EXP_LDSPAR >= 2 && !NATIVE && !FOLD && KT == 1;
+  float* const s_par0 = (float*)&s_tab[0];
+  if constexpr (LDS_MU) {
+    if (threadIdx.x < N4) { s_par0[threadIdx.x] = mu[threadIdx.x]; if (LDS_W) s_par0[N4 + threadIdx.x] = Wk[threadIdx.x]; }
+  }
+  // statistics epilogue (N3): per-wave moment accumulators and the digit-0 histogram of one portfolio at a time
+  __shared__ uint32_t s_hist[MCP_SELECT_BINS];
+  __shared__ double s_mom[PATH_BLOCK / 64][KT][2];
+  __shared__ float s_ext[PATH_BLOCK / 64][KT][2];
+  __shared__ unsigned long long s_cnt[PATH_BLOCK / 64];
+  // The epilogue's own arguments (pivot, partials, hist, slots, v0d: 13 dwords) are read from the kernel-argument segment
+  // AFTER the step loop, through a pointer the compiler cannot see through: loaded up front they would sit in SGPRs for the
+  // whole walk, and the kernel has none to spare (the Cholesky factor is fed from SGPRs): they spilled into VGPR lanes.
+  typedef const __attribute__((address_space(4))) PathArgs* cargs_p;
+  cargs_p kargs = (cargs_p)__builtin_amdgcn_kernarg_segment_ptr();
+  for (int i = threadIdx.x; i < MCP_SELECT_BINS; i += PATH_BLOCK) s_hist[i] = 0u;
+  if (threadIdx.x < (PATH_BLOCK / 64) * KT) {
+    (&s_mom[0][0][0])[2 * threadIdx.x] = 0.0; (&s_mom[0][0][0])[2 * threadIdx.x + 1] = 0.0;
+    (&s_ext[0][0][0])[2 * threadIdx.x] = __builtin_inff(); (&s_ext[0][0][0])[2 * threadIdx.x + 1] = -__builtin_inff();
+  }
+  if (threadIdx.x < PATH_BLOCK / 64) s_cnt[threadIdx.x] = 0ull;
+  __syncthreads();
+  const IcdfConsts kc = icdf_consts();
+  PhiloxKeys ks = philox_keys((uint32_t)a.seed, (uint32_t)(a.seed >> 32));
+#if MCP_EXP_VKEYS
+  // pin the 20 round keys in VGPRs: an SGPR operand halves the issue rate of the xor (profiles/r01_valu_rates.txt)
+#pragma unroll
+  for (int r = 0; r < 10; r++) { asm volatile("" : "+v"(ks.k0[r])); asm volatile("" : "+v"(ks.k1[r])); }
+#endif
+  const int T = a.n_steps;
+  constexpr bool logc = LOGC;
+
+  const uint64_t tile = (uint64_t)PATH_BLOCK * PPT;
+  const uint64_t n_tiles = (a.n_paths + tile - 1) / tile;
+#ifdef MCP_DIAG_CLOCK
+  const unsigned long long diag_t0 = __builtin_amdgcn_s_memtime(), diag_r0 = __builtin_amdgcn_s_memrealtime();
+#endif
+  for (uint64_t tl = blockIdx.x; tl < n_tiles; tl += gridDim.x) {
+    uint64_t p[PPT];
+    bool live[PPT];
+    uint32_t plo[PPT], phi[PPT];
+    float V[PPT][KT];
+    float Pk[PPT][KT], Qk[PPT][KT];                       // DD: running peak P and q (simple) / d (log)
+#pragma unroll
+    for (int e = 0; e < PPT; e++) {
+      p[e] = tl * tile + (uint64_t)e * PATH_BLOCK + threadIdx.x;
+      live[e] = p[e] < a.n_paths;
+      const uint64_t g = a.path_begin + p[e];
+      plo[e] = (uint32_t)g; phi[e] = (uint32_t)(g >> 32);
+#pragma unroll
+      for (int k = 0; k < KT; k++) V[e][k] = logc ? 0.0f : a.v0;
+      if constexpr (DD) {
+#pragma unroll
+        for (int k = 0; k < KT; k++) { Pk[e][k] = -__builtin_inff(); Qk[e][k] = logc ? 0.0f : 1.0f; }
+      }
+    }
+
+    for (int t = 0; t < T; t++) {
+      // keep the (loop-invariant) parameter loads inside the step: hoisted, they would pin ~170 registers
+      asm volatile("" : "+s"(mu), "+s"(Lp), "+s"(Wk));
+      uint32_t par_off = 0;                                        // opaque zero: keeps the LDS reads inside the step too
+      if constexpr (LDS_MU) asm volatile("" : "+v"(par_off));
+      const float* s_par = s_par0 + par_off;
+      float z[PPT][N4];
+#pragma unroll
+      for (int q = 0; q < NB; q++) {
+        const uint32_t blk = (uint32_t)t * NB + q;     // counter.x; counter.y = 0 (T*NB < 2^32)
+#pragma unroll
+        for (int e = 0; e < PPT; e++) {
+          uint32_t x[4];
+          philox4x32_10(blk, 0u, plo[e], phi[e], ks, x);
+          block_normals<NATIVE>(x, s_tab, kc, z[e][0 * NB + q], z[e][1 * NB + q], z[e][2 * NB + q], z[e][3 * NB + q]);
+        }
+      }
+      float rho[PPT][KT];
+      if constexpr (FOLD) {
+        cfloat_p fv = mu + a.fold_offset;
+        asm volatile("" : "+s"(fv));
+#pragma unroll
+        for (int e = 0; e < PPT; e++) {
+          float acc = fv[0];
+#pragma unroll
+          for (int j = 0; j < N4; j++) acc = fma32(fv[1 + j], z[e][j], acc);
+          rho[e][0] = acc;
+        }
+      } else {
+      // r = mu + L z (row i: acc = mu_i, then j ascending), rho_k = sum_i w_ki r_i (i ascending)
+#pragma unroll
+      for (int e = 0; e < PPT; e++)
+#pragma unroll
+        for (int k = 0; k < KT; k++) rho[e][k] = 0.0f;
+      // Rows are processed in pairs (2m, 2m+1): one v_pk_fma_f32 per column does both rows, its L operand
+      // an SGPR pair straight from the row-pair-interleaved parameter block, z_j broadcast by op_sel.
+#pragma unroll
+      for (int m = 0; m < N4 / 2; m++) {
+        f32x2 acc[PPT];
+        f32x2 mu2;
+        if constexpr (LDS_MU) mu2 = *(const f32x2*)&s_par[2 * m];
+        else mu2 = f32x2{mu[2 * m], mu[2 * m + 1]};
+#pragma unroll
+        for (int e = 0; e < PPT; e++) acc[e] = mu2;
+#pragma unroll
+        for (int j = 0; j <= 2 * m + 1; j++) {
+          const f32x2 l2 = {Lp[2 * m * (m + 1) + 2 * j], Lp[2 * m * (m + 1) + 2 * j + 1]};   // (L[2m][j], L[2m+1][j])
+#pragma unroll
+          for (int e = 0; e < PPT; e++) acc[e] = __builtin_elementwise_fma(l2, (f32x2){z[e][j], z[e][j]}, acc[e]);
+        }
+#pragma unroll
+        for (int h = 0; h < 2; h++) {
+          const int i = 2 * m + h;
+#pragma unroll
+          for (int k = 0; k < KT; k++) {
+            const float wki = LDS_W ? s_par[N4 + i] : Wk[k * N4 + i];   // rows >= kt are zero-padded by pack_params
+#pragma unroll
+            for (int e = 0; e < PPT; e++) rho[e][k] = fma32(wki, h ? acc[e].y : acc[e].x, rho[e][k]);
+          }
+        }
+      }
+      }  // !FOLD
+#pragma unroll
+      for (int e = 0; e < PPT; e++)
+#pragma unroll
+        for (int k = 0; k < KT; k++)
+          V[e][k] = logc ? (V[e][k] + rho[e][k]) : fma32(V[e][k], rho[e][k], V[e][k]);
+      if constexpr (DD) {
+        // SPEC.md 4.2: P = fmax(P, V_t); q = fminf(q, V_t / P) (IEEE division) or d = fminf(d, S_t - P).  fminf is IEEE
+        // minNum: the 0/0 of a zero peak is ignored.
+#pragma unroll
+        for (int e = 0; e < PPT; e++)
+#pragma unroll
+          for (int k = 0; k < KT; k++) {
+            Pk[e][k] = fmaxf(Pk[e][k], V[e][k]);
+            Qk[e][k] = fminf(Qk[e][k], logc ? V[e][k] - Pk[e][k] : V[e][k] / Pk[e][k]);
+          }
+      }
+    }
+
+#pragma unroll
+    for (int e = 0; e < PPT; e++) {
+      if (live[e]) {
+#pragma unroll
+        for (int k = 0; k < KT; k++)
+          if (k < kt) a.terminal[(size_t)(a.k_begin + k) * a.stride + p[e]] = V[e][k];
+        if constexpr (DD) {                                // the drawdown output, read from the kernel arguments here only
+          typedef const __attribute__((address_space(4))) PathArgsDD* cdd_p;
+          cdd_p dk = (cdd_p)__builtin_amdgcn_kernarg_segment_ptr();
+          asm volatile("" : "+s"(dk));
+#pragma unroll
+          for (int k = 0; k < KT; k++)
+            if (k < kt) dk->mdd[(size_t)(a.k_begin + k) * dk->mdd_stride + p[e]] = Qk[e][k];
+        }
+      }
+    }
+
+    // ---- fused statistics epilogue: V is still in registers ----
+    asm volatile("" : "+s"(kargs));
+    if (kargs->partials != nullptr) {                      // wave-uniform (kernel argument)
+      const double* __restrict__ e_pivot = kargs->pivot;
+      unsigned long long* __restrict__ e_hist = kargs->hist;
+      const double e_v0d = kargs->v0d;
+      int tid = threadIdx.x;
+      asm volatile("" : "+v"(tid));                        // nothing derived from it (LDS addresses) is hoisted above the step loop
+      const int lane = tid & 63, wv = tid >> 6;
+      unsigned long long cnt = 0;
+#pragma unroll
+      for (int e = 0; e < PPT; e++) cnt += (unsigned long long)__popcll(__ballot(live[e]));
+      if (lane == 0) s_cnt[wv] += cnt;
+#pragma unroll 1
+      for (int k = 0; k < kt; k++) {
+        const double c = e_pivot ? e_pivot[a.k_begin + k] : 0.0;
+        double d1 = 0.0, d2 = 0.0;
+        float mn = __builtin_inff(), mx = -__builtin_inff();
+#pragma unroll
+        for (int e = 0; e < PPT; e++) {
+          float v = V[e][0];
+#pragma unroll
+          for (int kk = 1; kk < KT; kk++) v = (kk == k) ? V[e][kk] : v;      // register select (k is a run-time index)
+          if (live[e]) {
+            const double d = terminal_to_x(v, e_v0d, logc ? MCP_COMPOUND_LOG : MCP_COMPOUND_SIMPLE) - c;
+            d1 += d;
+            d2 = __builtin_fma(d, d, d2);
+            mn = fminf(mn, v);
+            mx = fmaxf(mx, v);
+          }
+          if (e_hist) lds_hist_add(s_hist, float_to_key(v) >> 21, live[e]);
+        }
+        d1 = wave_sum(d1); d2 = wave_sum(d2); mn = wave_minf(mn); mx = wave_maxf(mx);
+        if (lane == 0) {                                   // this wave's own slot: no race, fixed order over the tiles
+          s_mom[wv][k][0] += d1; s_mom[wv][k][1] += d2;
+          s_ext[wv][k][0] = fminf(s_ext[wv][k][0], mn); s_ext[wv][k][1] = fmaxf(s_ext[wv][k][1], mx);
+        }
+        if (e_hist) {                                      // flush portfolio k's digit-0 counts (read-and-clear)
+          __syncthreads();
+          unsigned long long* out = e_hist + (size_t)(a.k_begin + k) * 2 * MCP_SELECT_BINS;
+          for (int i = tid; i < MCP_SELECT_BINS; i += PATH_BLOCK) {
+            const uint32_t h = s_hist[i];
+            if (h) { atomicAdd(&out[i], (unsigned long long)h); s_hist[i] = 0u; }
+          }
+          __syncthreads();
+        }
+      }
+    }
+  }
+
+#ifdef MCP_DIAG_CLOCK
+  if (threadIdx.x == 0 && blockIdx.x < 8192) {
+    mcp_diag_stamps[2 * blockIdx.x] = __builtin_amdgcn_s_memtime() - diag_t0;
+    mcp_diag_stamps[2 * blockIdx.x + 1] = __builtin_amdgcn_s_memrealtime() - diag_r0;
+  }
+#endif
+  asm volatile("" : "+s"(kargs));
+  if (kargs->partials != nullptr) {
+    __syncthreads();
+    if ((int)threadIdx.x < kt) {                           // one partial per workgroup and portfolio, waves in order
+      const int k = threadIdx.x;
+      MomentPartial o;
+      o.s1 = (s_mom[0][k][0] + s_mom[1][k][0]) + (s_mom[2][k][0] + s_mom[3][k][0]);
+      o.s2 = (s_mom[0][k][1] + s_mom[1][k][1]) + (s_mom[2][k][1] + s_mom[3][k][1]);
+      o.vmin = fminf(fminf(s_ext[0][k][0], s_ext[1][k][0]), fminf(s_ext[2][k][0], s_ext[3][k][0]));
+      o.vmax = fmaxf(fmaxf(s_ext[0][k][1], s_ext[1][k][1]), fmaxf(s_ext[2][k][1], s_ext[3][k][1]));
+      o.n = (s_cnt[0] + s_cnt[1]) + (s_cnt[2] + s_cnt[3]);
+      kargs->partials[(size_t)(a.k_begin + k) * kargs->slots + blockIdx.x] = o;
+    }
+  }

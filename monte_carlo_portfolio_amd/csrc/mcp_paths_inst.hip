@@ -46,4 +46,21 @@ hipError_t MCP_CAT(launch_paths_nb, MCP_NB)(int variant, const PathArgs& args, i
   }
 }
 
+// The drawdown kernel (mcp_launch_paths_drawdown): one portfolio or KT = 8 passes, both compounding modes.
+hipError_t MCP_CAT(launch_paths_dd_nb, MCP_NB)(int variant, const PathArgsDD& args, int grid, hipStream_t stream) {
+  const bool lg = args.compounding == MCP_COMPOUND_LOG;
+  switch (variant) {
+    case 0:
+      if (lg) mc_paths_dd_kernel<MCP_NB, 1, 1, true><<<grid, PATH_BLOCK, lds_pad(), stream>>>(args);
+      else mc_paths_dd_kernel<MCP_NB, 1, 1, false><<<grid, PATH_BLOCK, lds_pad(), stream>>>(args);
+      break;
+    case VAR_KT8:
+      if (lg) mc_paths_dd_kernel<MCP_NB, 8, 1, true><<<grid, PATH_BLOCK, lds_pad(), stream>>>(args);
+      else mc_paths_dd_kernel<MCP_NB, 8, 1, false><<<grid, PATH_BLOCK, lds_pad(), stream>>>(args);
+      break;
+    default: return hipErrorInvalidValue;
+  }
+  return hipGetLastError();
+}
+
 }  // namespace mcp

@@ -65,6 +65,13 @@ typedef hipError_t (*launch_paths_fn)(int variant, const PathArgs& args, int gri
 MCP_DECL_NB(1) MCP_DECL_NB(2) MCP_DECL_NB(3) MCP_DECL_NB(4) MCP_DECL_NB(5) MCP_DECL_NB(6) MCP_DECL_NB(7) MCP_DECL_NB(8)
 MCP_DECL_NB(9) MCP_DECL_NB(10) MCP_DECL_NB(11) MCP_DECL_NB(12) MCP_DECL_NB(13) MCP_DECL_NB(14) MCP_DECL_NB(15) MCP_DECL_NB(16)
 #undef MCP_DECL_NB
+// the drawdown kernel (SPEC.md 4.2), variants 0 and VAR_KT8 only
+struct PathArgsDD;
+typedef hipError_t (*launch_paths_dd_fn)(int variant, const PathArgsDD& args, int grid, hipStream_t stream);
+#define MCP_DECL_NB(n) hipError_t launch_paths_dd_nb##n(int variant, const PathArgsDD& args, int grid, hipStream_t stream);
+MCP_DECL_NB(1) MCP_DECL_NB(2) MCP_DECL_NB(3) MCP_DECL_NB(4) MCP_DECL_NB(5) MCP_DECL_NB(6) MCP_DECL_NB(7) MCP_DECL_NB(8)
+MCP_DECL_NB(9) MCP_DECL_NB(10) MCP_DECL_NB(11) MCP_DECL_NB(12) MCP_DECL_NB(13) MCP_DECL_NB(14) MCP_DECL_NB(15) MCP_DECL_NB(16)
+#undef MCP_DECL_NB
 
 // mcp_sweep_paths.hip: MFMA K-portfolio kernels; mt = 32-portfolio tiles per wave (1, 2 or 4)
 hipError_t launch_sweep_shared(int nb, int mt, bool native, const PathArgs& args, hipStream_t stream);   // mt: 4|2 (N <= 16), 2|1 (N > 16)

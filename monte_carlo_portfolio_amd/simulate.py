@@ -72,6 +72,29 @@ class Context:
             stats.ctypes.data_as(ctypes.c_void_p)))
         return stats, term
 
+    def simulate_drawdown(self, prm: _ffi.McpParams, mu, chol, W, seed: int, path_begin: int, n_paths: int, store: bool):
+        """simulate() plus the max drawdown of every path (SPEC.md 4.2 / 5.1; include/mcport.h, mcp_simulate_drawdown) ->
+        (stats, dd_stats, terminal, qd): dd_stats is a [K] mcp_stats record array over the per-path drawdowns; with `store`,
+        qd is the kernels' binary32 [K, n_paths] q (simple: mdd = q - 1) or d (log: mdd = expm1(d)), see mdd_from_raw."""
+        K = prm.n_portfolios
+        stats = np.zeros(K, _ffi.STATS_DTYPE)
+        dd_stats = np.zeros(K, _ffi.STATS_DTYPE)
+        term = np.empty((K, n_paths), np.float32) if store else None
+        raw = np.empty((K, n_paths), np.float32) if store else None
+        _ffi.check(_ffi.lib().mcp_simulate_drawdown(
+            self._h, ctypes.byref(prm), mu, chol, W, seed, path_begin, n_paths,
+            term.ctypes.data_as(ctypes.c_void_p) if store else None,
+            stats.ctypes.data_as(ctypes.c_void_p),
+            raw.ctypes.data_as(ctypes.c_void_p) if store else None,
+            dd_stats.ctypes.data_as(ctypes.c_void_p)))
+        return stats, dd_stats, term, raw
+
+
+def mdd_from_raw(qd, compounding="simple") -> np.ndarray:
+    """SPEC.md 4.2: the per-path max drawdown in binary64 from the kernel's binary32 q (simple: q - 1) or d (log: expm1(d))."""
+    qd = np.asarray(qd, np.float32).astype(np.float64)
+    return np.expm1(qd) if compounding == "log" else qd - 1.0
+
 
 def _close_default_contexts() -> None:
     """Interpreter exit: destroy the cached contexts (streams, device buffers, RCCL communicators) while the HIP runtime
@@ -128,9 +151,17 @@ def stats_to_dict(rec) -> dict:
     return {name: (int(rec[name]) if name in ("n", "n_tail") else float(rec[name])) for name in rec.dtype.names}
 
 
+def drawdown_to_dict(rec) -> dict:
+    """The drawdown fields of one mcp_stats record of mcp_simulate_drawdown (SPEC.md 5.1): DaR / CDaR are its var / cvar,
+    the worst / best drawdown its min / max."""
+    return {"mean": float(rec["mean"]), "std": float(rec["std"]), "dar": float(rec["var"]), "cdar": float(rec["cvar"]),
+            "n_tail": int(rec["n_tail"]), "worst": float(rec["min"]), "best": float(rec["max"]),
+            "x_lo": float(rec["x_lo"]), "x_hi": float(rec["x_hi"])}
+
+
 def simulate_paths(mu, cov, weights, n_steps=252, n_paths=10_000, seed=0, v0=1.0, compounding="simple",
                    rf=0.0, alpha=0.95, devices=None, store=False, path_begin=0, chol=None,
-                   native_math=False, as_array=False, fold=False, shard="auto", context=None):
+                   native_math=False, as_array=False, fold=False, shard="auto", context=None, drawdown=False):
     """Simulate `n_paths` correlated return paths and reduce them to risk statistics.
 
     mu [N], cov [N,N] are per-step mean and covariance (the reference's `mean_returns`, `cov_matrix`
@@ -142,7 +173,14 @@ def simulate_paths(mu, cov, weights, n_steps=252, n_paths=10_000, seed=0, v0=1.0
     all-reduce of the radix-select histograms, one all-gather of the moment records).
     shard="portfolios" (or "auto" with K >= 512 per device) shards the weight matrix instead: every GPU walks all
     paths for its slice of the portfolios, no collective at all (BASELINE configs[4]).
+
+    drawdown=True: also the max drawdown of every path (SPEC.md 4.2), tracked inside the path kernel, reduced per portfolio
+    (SPEC.md 5.1): every dict gains 'drawdown' {mean, std, dar, cdar, n_tail, worst, best, x_lo, x_hi} and, with store=True,
+    'max_drawdown' (float64 per-path drawdowns).  as_array=True returns (stats, dd_stats) [+ (terminal, max_drawdown) with
+    store].  Not with fold or native_math (ValueError).
     """
+    if drawdown and (fold or native_math):
+        raise ValueError("drawdown=True needs the spec's normals and the unfolded recurrence: not with fold or native_math")
     single = np.asarray(weights).ndim == 1
     mu32, L, W = prepare_inputs(mu, cov, weights, chol)
     devs = (0,) if not devices else tuple(int(d) for d in devices)
@@ -151,13 +189,23 @@ def simulate_paths(mu, cov, weights, n_steps=252, n_paths=10_000, seed=0, v0=1.0
     by_portfolio = len(devs) > 1 and (shard == "portfolios" or (shard == "auto" and W.shape[0] >= 512 * len(devs)))
     prm = _ffi.make_params(mu32.shape[0], n_steps, W.shape[0], compounding, v0, alpha, rf, native_math, fold, by_portfolio)
     ctx = context if context is not None else default_context(devs)
-    stats, term = ctx.simulate(prm, mu32, L, W, int(seed), int(path_begin), int(n_paths), store)
-    if as_array:                      # [K] structured array (fields of mcp_stats), for large sweeps
-        return (stats, term) if store else stats
+    if drawdown:
+        stats, dd_stats, term, raw = ctx.simulate_drawdown(prm, mu32, L, W, int(seed), int(path_begin), int(n_paths), store)
+        mdd = mdd_from_raw(raw, compounding) if store else None
+        if as_array:
+            return (stats, dd_stats, term, mdd) if store else (stats, dd_stats)
+    else:
+        stats, term = ctx.simulate(prm, mu32, L, W, int(seed), int(path_begin), int(n_paths), store)
+        if as_array:                      # [K] structured array (fields of mcp_stats), for large sweeps
+            return (stats, term) if store else stats
     out = [stats_to_dict(stats[k]) for k in range(W.shape[0])]
-    if store:
-        for k, d in enumerate(out):
+    for k, d in enumerate(out):
+        if drawdown:
+            d["drawdown"] = drawdown_to_dict(dd_stats[k])
+        if store:
             d["terminal"] = term[k]
+            if drawdown:
+                d["max_drawdown"] = mdd[k]
     return out[0] if single else out
 
 
@@ -166,14 +214,22 @@ def simulate_sweep(mu, cov, weights=None, n_portfolios=2500, min_weights=None, m
     """The reference's sweep (app.py:682-722) scored on SIMULATED terminal values instead of historical rows:
     weights drawn exactly as app.py:699-707 (host, NumPy legacy RNG; pass `weights` to supply them), all
     portfolios on common random numbers in one launch (MFMA kernel for K >= 17), metric and optimum as at
-    app.py:672-676 / 717 / 747.  -> dict(all_weights, stats [K] record array, all_metrics, opt_idx)."""
+    app.py:672-676 / 717 / 747.  -> dict(all_weights, stats [K] record array, all_metrics, opt_idx); drawdown=True adds
+    'drawdown_stats', the [K] record array of the per-path max drawdowns (simulate_paths)."""
     from .sweep import _METRIC, draw_weights, select_optimum
     if weights is None:
         if np_seed is not None:
             np.random.seed(np_seed)
         weights = draw_weights(len(np.atleast_1d(mu)), n_portfolios, min_weights, max_weights)
     W = np.atleast_2d(np.asarray(weights, np.float64))
+    drawdown = bool(kw.get("drawdown", False))
     stats = simulate_paths(mu, cov, W, n_steps=n_steps, n_paths=n_paths, seed=seed, rf=rf, alpha=alpha, as_array=True, **kw)
+    dd_stats = None
+    if drawdown:
+        stats, dd_stats = stats[0], stats[1]
     metric = {"sharpe": stats["sharpe"], "var_95": -stats["var"], "cvar_95": -stats["cvar"]}[_METRIC[method]]
-    return {"all_weights": W, "stats": stats, "all_metrics": metric, "opt_idx": select_optimum(method, metric),
-            "all_risks": stats["std"], "all_returns": stats["mean"]}
+    out = {"all_weights": W, "stats": stats, "all_metrics": metric, "opt_idx": select_optimum(method, metric),
+           "all_risks": stats["std"], "all_returns": stats["mean"]}
+    if drawdown:
+        out["drawdown_stats"] = dd_stats
+    return out
