@@ -47,6 +47,11 @@ def main(paths, resample_rule="M", user_rf=3.0, investment=10000.0, seed=12345, 
           f"VaR95 {sim['var']:+.4f}  CVaR95 {sim['cvar']:+.4f}  Sharpe {sim['sharpe']:.4f}")
     dd = sim["drawdown"]                  # max drawdown of every path before the horizon (SPEC.md 4.2 / 5.1)
     print(f"  max drawdown: mean {dd['mean']:+.4f}  DaR95 {dd['dar']:+.4f}  CDaR95 {dd['cdar']:+.4f}  worst {dd['worst']:+.4f}")
+    fan = mcp.simulate_paths(mu_step, cov_step, w, n_steps=6, n_paths=n_paths, seed=seed, v0=investment, horizons=[1, 3, 6],
+                             bands=(2.5, 50.0, 97.5))["horizons"]        # values at intermediate horizons (SPEC.md 4.3 / 5.2)
+    for h, b in zip(fan["steps"], fan["bands"]):
+        lo, mid, hi = investment * (1.0 + b)
+        print(f"  forecast fan after {h} period(s): 2.5 % {lo:,.2f}  median {mid:,.2f}  97.5 % {hi:,.2f}")
     return res, sim
 
 

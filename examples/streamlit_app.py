@@ -7,7 +7,8 @@ surface the package exposes under the reference's names.
 
 Tabs (reference lines they stand for): per-asset statistics (app.py:463-497), option strategy and P/L curve
 (app.py:499-653), the five-method random-weight sweep on historical rows plus the optimum re-scored on simulated paths
-(app.py:655-783 + the MI355X path engine), forecast (app.py:785-809: ARIMA/GARCH, out of scope -- the tab says so).
+(app.py:655-783 + the MI355X path engine), forecast (app.py:785-809: there ARIMA/GARCH; here a Monte Carlo fan from the
+path engine's values at intermediate horizons -- the tab says so).
 Streamlit is not part of the test image; tests/test_gpu_shim.py runs this file under a recording stand-in module.
 """
 import os
@@ -86,4 +87,19 @@ with tab_sweep:                                               # app.py:655-783
               "worst": sim["drawdown"]["worst"]})
 
 with tab_forecast:                                            # app.py:785-809
-    st.info("ARIMA/GARCH forecasting is outside the scope of this package (SURVEY.md section 2, component 11).")
+    # The reference forecasts 1, 3 and 6 periods ahead with a 95 % interval.  Here: a Monte Carlo fan from the path engine
+    # (values at intermediate horizons, SPEC.md 4.3 / 5.2) -- each asset on its own (one-hot weight rows, from its last
+    # price) and the Monte Carlo optimum (from the capital).
+    st.info("Monte Carlo forecast on simulated paths (MI355X path engine), not the reference's ARIMA/GARCH models.")
+    horizons, levels = [1, 3, 6], (2.5, 50.0, 97.5)
+    _, _, asset_bands = mcp.simulate_paths(mu_step, cov_step, np.eye(len(names)), n_steps=horizons[-1], n_paths=n_paths, seed=12345,
+                                           horizons=horizons, bands=levels, as_array=True)
+    opt_fan = mcp.simulate_paths(mu_step, cov_step, w, n_steps=horizons[-1], n_paths=n_paths, seed=12345,
+                                 v0=state["investment_amount"], horizons=horizons, bands=levels)["horizons"]["bands"]
+    fans = [(n, float(resampled[n].iloc[-1]), asset_bands[:, a, :]) for a, n in enumerate(names)]
+    fans.append(("Monte Carlo optimum", float(state["investment_amount"]), opt_fan))
+    for name, v0, b in fans:
+        st.subheader(f"{name}: forecast fan")
+        fan = {"horizon": horizons, **{f"{q} %": (v0 * (1.0 + b[:, j])).tolist() for j, q in enumerate(levels)}}
+        st.line_chart(fan, x="horizon")
+        st.write({"asset": name, **fan})

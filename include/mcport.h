@@ -23,9 +23,12 @@
 extern "C" {
 #endif
 
-#define MCP_ABI_VERSION 4        /* 4: + mcp_simulate_drawdown, mcp_launch_paths_drawdown (additive) */
+#define MCP_ABI_VERSION 4        /* 4: + mcp_simulate_drawdown, mcp_launch_paths_drawdown (additive); + mcp_simulate_horizons,
+                                    mcp_launch_paths_horizons, mcp_percentile_rank_q (additive, detected by symbol) */
 #define MCP_MAX_ASSETS 64        /* thread-per-path kernels are instantiated for N4 = 4..64 */
 #define MCP_SELECT_BINS 2048     /* radix-select digit: 11 + 11 + 10 bits */
+#define MCP_MAX_HORIZONS 64      /* mcp_simulate_horizons: horizon steps per call */
+#define MCP_MAX_LEVELS 16        /* mcp_simulate_horizons: band levels per call */
 
 enum {
     MCP_OK = 0,
@@ -158,6 +161,27 @@ int mcp_simulate_drawdown(mcp_ctx *ctx, const mcp_params *prm, const float *mu, 
                           float *mdd_out,          /* NULL or host [K*n_paths]: q or d */
                           mcp_stats *dd_stats_out  /* [K] */);
 
+/* mcp_simulate plus the values at intermediate horizons (SPEC.md 4.3) and their statistics and bands (SPEC.md 5.2).
+ * horizons: n_horizons in [1, MCP_MAX_HORIZONS] strictly increasing steps in [1, n_steps] (n_steps itself allowed); the
+ * value after step h of this walk is bit for bit the terminal value of the same call with n_steps = h.  levels: n_levels in
+ * [0, MCP_MAX_LEVELS] percentages in [0, 100].  Per (horizon h, portfolio k), over x_h = V_h/v0 - 1 (simple) or expm1(S_h)
+ * (log): hz_stats_out[h*K + k] is an mcp_stats record at the call's alpha (pivot of n_steps = h, sharpe = 0), and
+ * bands_out[(h*K + k)*L + l] = np.percentile(x_h, levels[l]) bit for bit.  horizon_out: NULL or host [H*K*n_paths] floats,
+ * row h*K + k, the raw V_h / S_h.  terminal_out / stats_out are what mcp_simulate returns, with the same V_T; for K >= 17 the
+ * moments agree with mcp_simulate's to fp64 association only, everything else exactly.  Costs: one 4 B store per path,
+ * portfolio and horizon; K >= 17 runs as passes of the 8-portfolio kernel; 1 + L selects over the H*K rows; the terminal
+ * budget counts 4 (1 + H) B per path and portfolio.  Argument errors (MCP_E_ARG) are found before any device is touched;
+ * MCP_FLAG_FOLD / MCP_FLAG_NATIVE_MATH: MCP_E_UNSUPPORTED. */
+int mcp_simulate_horizons(mcp_ctx *ctx, const mcp_params *prm, const float *mu, const float *chol, const float *W,
+                          uint64_t seed, uint64_t path_begin, uint64_t n_paths,
+                          int n_horizons, const int32_t *horizons,
+                          int n_levels, const double *levels,
+                          float *terminal_out,        /* NULL or host [K*n_paths] */
+                          mcp_stats *stats_out,       /* [K] */
+                          float *horizon_out,         /* NULL or host [H*K*n_paths], row h*K + k */
+                          mcp_stats *hz_stats_out,    /* [H*K] */
+                          double *bands_out);         /* [H*K*L], NULL iff n_levels == 0 */
+
 /* The reference's own sweep (app.py:699-717) over HISTORICAL returns, loop body app.py:708-713 for P weight
  * vectors at once, binary64 like the reference.  returns: [R*N] row-major (returns_df.values, app.py:667),
  * mean/cov: the annualised mean_returns / cov_matrix of app.py:679-680, W: [P*N] (rows as drawn at
@@ -223,10 +247,21 @@ int mcp_launch_paths(const mcp_params *prm, const float *d_packed, const double 
 int mcp_launch_paths_drawdown(const mcp_params *prm, const float *d_packed, const double *d_pivot, uint64_t seed,
                               uint64_t path_begin, uint64_t n_paths, float *d_terminal, uint64_t terminal_stride,
                               float *d_mdd, uint64_t mdd_stride, void *d_partials, void *d_hist, void *stream);
+/* mcp_launch_paths that also stores the values after the steps horizons[0..n_horizons) (host array, SPEC.md 4.3) into
+ * d_horizon ([n_horizons][K][horizon_stride] floats, row h*K + k; horizon_stride >= n_paths).  Kernels and moment partials
+ * as in mcp_launch_paths_drawdown.  To reduce one horizon row set: mcp_launch_pass0 over d_horizon with n_portfolios =
+ * H*K and the [H*K] pivots of mcp_pivots at n_steps = h, then the usual scan / hist / final steps.
+ * MCP_FLAG_FOLD / MCP_FLAG_NATIVE_MATH: MCP_E_UNSUPPORTED. */
+int mcp_launch_paths_horizons(const mcp_params *prm, const float *d_packed, const double *d_pivot, uint64_t seed,
+                              uint64_t path_begin, uint64_t n_paths, float *d_terminal, uint64_t terminal_stride,
+                              int n_horizons, const int32_t *horizons, float *d_horizon, uint64_t horizon_stride,
+                              void *d_partials, void *d_hist, void *stream);
 
 /* np.percentile(x, (1-alpha)*100) bookkeeping (numpy 2.2 `_compute_virtual_index`/`_get_indexes`,
  * method 'linear'; the q of app.py:259): ranks of the two order statistics and the weight. */
 int mcp_percentile_rank(uint64_t n_total, double alpha, uint64_t *rank_lo, uint64_t *rank_hi, double *gamma);
+/* The same bookkeeping for np.percentile(x, q) itself, q in percent in [0, 100]: q/100, vi = (n-1)*(q/100), the same clamps. */
+int mcp_percentile_rank_q(uint64_t n_total, double q, uint64_t *rank_lo, uint64_t *rank_hi, double *gamma);
 
 /* Standalone pass 0 over CALLER-SUPPLIED terminal values (n per portfolio): the same moment partials and digit-0
  * histogram the fused epilogue of mcp_launch_paths leaves.  d_pivot: [K] doubles or NULL (= 0: raw sums). */

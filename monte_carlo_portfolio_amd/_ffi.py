@@ -20,6 +20,8 @@ CSRC = os.path.join(_PKG, "csrc")
 MCP_ABI_VERSION = 4
 MCP_MAX_ASSETS = 64
 MCP_SELECT_BINS = 2048
+MCP_MAX_HORIZONS = 64
+MCP_MAX_LEVELS = 16
 MCP_COMPOUND = {"simple": 0, "log": 1}
 MCP_FLAG_NATIVE_MATH = 1
 MCP_FLAG_FOLD = 2
@@ -97,6 +99,11 @@ SIGNATURES = {
     "mcp_launch_paths": (_int, [_PP, _vp, _vp, _u64, _u64, _u64, _vp, _u64, _vp, _vp, _vp]),
     "mcp_simulate_drawdown": (_int, [_vp, _PP, _f32p, _f32p, _f32p, _u64, _u64, _u64, _vp, _vp, _vp, _vp]),
     "mcp_launch_paths_drawdown": (_int, [_PP, _vp, _vp, _u64, _u64, _u64, _vp, _u64, _vp, _u64, _vp, _vp, _vp]),
+    "mcp_simulate_horizons": (_int, [_vp, _PP, _f32p, _f32p, _f32p, _u64, _u64, _u64, _int, _vp, _int, _vp, _vp, _vp, _vp, _vp,
+                                     _vp]),
+    "mcp_launch_paths_horizons": (_int, [_PP, _vp, _vp, _u64, _u64, _u64, _vp, _u64, _int, _vp, _vp, _u64, _vp, _vp, _vp]),
+    "mcp_percentile_rank_q": (_int, [_u64, ctypes.c_double, ctypes.POINTER(_u64), ctypes.POINTER(_u64),
+                                     ctypes.POINTER(ctypes.c_double)]),
     "mcp_percentile_rank": (_int, [_u64, ctypes.c_double, ctypes.POINTER(_u64), ctypes.POINTER(_u64),
                                    ctypes.POINTER(ctypes.c_double)]),
     "mcp_launch_pass0": (_int, [_PP, _vp, _u64, _u64, _vp, _vp, _vp, _vp]),
@@ -214,6 +221,13 @@ def pivots(prm: McpParams, mu: np.ndarray, chol: np.ndarray, W: np.ndarray) -> n
     out = np.zeros(W.shape[0], np.float64)
     check(lib().mcp_pivots(ctypes.byref(prm), mu, chol, W, out))
     return out
+
+
+def percentile_rank_q(n_total: int, q: float):
+    """(rank_lo, rank_hi, gamma) of np.percentile(x, q) over n_total values, q in percent (include/mcport.h)."""
+    lo, hi, g = _u64(), _u64(), ctypes.c_double()
+    check(lib().mcp_percentile_rank_q(n_total, q, ctypes.byref(lo), ctypes.byref(hi), ctypes.byref(g)))
+    return lo.value, hi.value, g.value
 
 
 def percentile_rank(n_total: int, alpha: float):

@@ -113,6 +113,31 @@ const mcp::launch_paths_dd_fn k_launch_dd[16] = {
     mcp::launch_paths_dd_nb5,  mcp::launch_paths_dd_nb6,  mcp::launch_paths_dd_nb7,  mcp::launch_paths_dd_nb8,
     mcp::launch_paths_dd_nb9,  mcp::launch_paths_dd_nb10, mcp::launch_paths_dd_nb11, mcp::launch_paths_dd_nb12,
     mcp::launch_paths_dd_nb13, mcp::launch_paths_dd_nb14, mcp::launch_paths_dd_nb15, mcp::launch_paths_dd_nb16};
+const mcp::launch_paths_hz_fn k_launch_hz[16] = {
+    mcp::launch_paths_hz_nb1,  mcp::launch_paths_hz_nb2,  mcp::launch_paths_hz_nb3,  mcp::launch_paths_hz_nb4,
+    mcp::launch_paths_hz_nb5,  mcp::launch_paths_hz_nb6,  mcp::launch_paths_hz_nb7,  mcp::launch_paths_hz_nb8,
+    mcp::launch_paths_hz_nb9,  mcp::launch_paths_hz_nb10, mcp::launch_paths_hz_nb11, mcp::launch_paths_hz_nb12,
+    mcp::launch_paths_hz_nb13, mcp::launch_paths_hz_nb14, mcp::launch_paths_hz_nb15, mcp::launch_paths_hz_nb16};
+
+// SPEC.md 4.3: 1..MCP_MAX_HORIZONS strictly increasing steps in [1, n_steps]
+int check_horizons(int n_steps, int H, const int32_t* steps) {
+  if (H < 1 || H > MCP_MAX_HORIZONS) return fail(MCP_E_ARG, "n_horizons=%d outside [1,%d]", H, MCP_MAX_HORIZONS);
+  if (!steps) return fail(MCP_E_ARG, "horizons is NULL");
+  for (int i = 0; i < H; i++) {
+    if (steps[i] < 1 || steps[i] > n_steps) return fail(MCP_E_ARG, "horizon %d = %d outside [1, n_steps=%d]", i, steps[i], n_steps);
+    if (i && steps[i] <= steps[i - 1]) return fail(MCP_E_ARG, "horizons must be strictly increasing (%d after %d)", steps[i], steps[i - 1]);
+  }
+  return MCP_OK;
+}
+
+// SPEC.md 5.2: 0..MCP_MAX_LEVELS percentages in [0, 100]
+int check_levels(int L, const double* levels) {
+  if (L < 0 || L > MCP_MAX_LEVELS) return fail(MCP_E_ARG, "n_levels=%d outside [0,%d]", L, MCP_MAX_LEVELS);
+  if (L && !levels) return fail(MCP_E_ARG, "levels is NULL");
+  for (int i = 0; i < L; i++)
+    if (!(levels[i] >= 0.0 && levels[i] <= 100.0)) return fail(MCP_E_ARG, "level %d = %g outside [0, 100]", i, levels[i]);
+  return MCP_OK;
+}
 
 // Inverse-CDF coefficient table (SPEC.md section 3; DATA of the spec, generated by tools/fit_icdf_table.py): one
 // device-resident copy per device, uploaded on first use on the caller's stream.  The first call on a device
@@ -186,6 +211,15 @@ struct Shard {
   mcp_stats* h_dd_stats = nullptr;         // drawdown calls: the drawdown statistics, pinned and mapped like h_stats
   size_t h_dd_stats_cap = 0;
   void* d_dd_stats = nullptr;              // device address of h_dd_stats
+  float* d_hz = nullptr;                   // horizon calls: [H][K tile][paths] V_h / S_h of SPEC.md 4.3
+  size_t hz_cap = 0;
+  double* d_hz_pivot = nullptr;            // horizon calls: [H][K tile] pivots (mcp_pivots at n_steps = h)
+  size_t hz_pivot_cap = 0;
+  double* h_hz_pivot = nullptr;            // pinned staging of d_hz_pivot
+  size_t h_hz_pivot_cap = 0;
+  mcp_stats* h_hz_stats = nullptr;         // horizon calls: [1 + L][H][K tile] records of the alpha select and of every level's
+  size_t h_hz_stats_cap = 0;               // select, pinned and mapped like h_stats
+  void* d_hz_stats = nullptr;              // device address of h_hz_stats
 };
 
 // RCCL entry points, resolved at run time (no link-time dependency: a single-device user never loads librccl).
@@ -343,13 +377,22 @@ int mcp_pivots(const mcp_params* prm, const float* mu, const float* chol, const 
 
 }  // extern "C"
 
-// mcp_launch_paths (d_mdd NULL) and mcp_launch_paths_drawdown.  A drawdown launch always runs mc_paths_dd_kernel, K >= 17 as
-// passes of the 8-portfolio kernel: the MFMA sweep kernels do not track the path's peak.  Its moment partials keep the layout
-// mcp_moment_slots(K, n) gives (what mcp_launch_scan reads): where that is one slot per 64-path tile (K >= 17), an empty pass 0
-// first pads every slot, and the path kernel's workgroups overwrite the first path_grid(n) of them.
+// The horizon output of a launch (SPEC.md 4.3): n horizon steps (host), the [n][K][stride] array.
+struct HzOut {
+  int n = 0;
+  const int32_t* steps = nullptr;
+  float* d_out = nullptr;
+  uint64_t stride = 0;
+};
+
+// mcp_launch_paths (d_mdd and hz NULL), mcp_launch_paths_drawdown and mcp_launch_paths_horizons.  A drawdown or horizon launch
+// always runs mc_paths_dd_kernel / mc_paths_hz_kernel, K >= 17 as passes of the 8-portfolio kernel: the MFMA sweep kernels
+// track neither the path's peak nor its intermediate values.  Its moment partials keep the layout mcp_moment_slots(K, n) gives
+// (what mcp_launch_scan reads): where that is one slot per 64-path tile (K >= 17), an empty pass 0 first pads every slot, and
+// the path kernel's workgroups overwrite the first path_grid(n) of them.
 static int launch_paths_impl(const mcp_params* prm, const float* d_packed, const double* d_pivot, uint64_t seed, uint64_t path_begin,
                              uint64_t n_paths, float* d_terminal, uint64_t stride, float* d_mdd, uint64_t mdd_stride, void* d_partials,
-                             void* d_hist, void* stream) {
+                             void* d_hist, void* stream, const HzOut* hz = nullptr) {
   const bool dd = d_mdd != nullptr;
   if (int rc = check_params(prm)) return rc;
   if (!d_packed || !d_terminal) return fail(MCP_E_ARG, "NULL device pointer");
@@ -357,6 +400,15 @@ static int launch_paths_impl(const mcp_params* prm, const float* d_packed, const
     return fail(MCP_E_UNSUPPORTED, "the drawdown runs on the spec's normals and the unfolded recurrence (no MCP_FLAG_FOLD / MCP_FLAG_NATIVE_MATH)");
   if (dd && mdd_stride < n_paths) return fail(MCP_E_ARG, "mdd_stride %llu < n_paths %llu", (unsigned long long)mdd_stride,
                                               (unsigned long long)n_paths);
+  if (hz) {
+    if (dd) return fail(MCP_E_UNSUPPORTED, "horizons and the drawdown are not tracked in one walk");
+    if (prm->flags & (MCP_FLAG_FOLD | MCP_FLAG_NATIVE_MATH))
+      return fail(MCP_E_UNSUPPORTED, "the horizons run on the spec's normals and the unfolded recurrence (no MCP_FLAG_FOLD / MCP_FLAG_NATIVE_MATH)");
+    if (int rc = check_horizons(prm->n_steps, hz->n, hz->steps)) return rc;
+    if (!hz->d_out) return fail(MCP_E_ARG, "d_horizon is NULL");
+    if (hz->stride < n_paths) return fail(MCP_E_ARG, "horizon_stride %llu < n_paths %llu", (unsigned long long)hz->stride,
+                                          (unsigned long long)n_paths);
+  }
   if ((d_partials == nullptr) != (d_hist == nullptr)) return fail(MCP_E_ARG, "d_partials and d_hist go together (both or neither)");
   if (n_paths < 1) return fail(MCP_E_ARG, "n_paths must be >= 1");
   if (stride < n_paths) return fail(MCP_E_ARG, "terminal_stride %llu < n_paths %llu",
@@ -381,14 +433,14 @@ static int launch_paths_impl(const mcp_params* prm, const float* d_packed, const
   DeviceGuard guard(dev);                 // the stream may belong to another device than the thread's current one
   if (guard.err != hipSuccess) return fail(MCP_E_HIP, "hipSetDevice(%d): %s", dev, hipGetErrorString(guard.err));
   if (int rc = device_tables(dev, (hipStream_t)stream, &tables)) return rc;
-  const bool sweep = !dd && uses_sweep(K);
+  const bool sweep = !dd && !hz && uses_sweep(K);
   a.tables = tables;
   a.packed = d_packed;
   a.terminal = d_terminal;
   a.pivot = d_pivot;
   a.partials = (mcp::MomentPartial*)d_partials;
   a.hist = sweep ? nullptr : (unsigned long long*)d_hist;     // the sweep kernels leave digit 0 to hist(0) below
-  a.slots = dd ? mcp_moment_slots(K, n_paths) : mcp::moment_slots(sweep, n_paths);
+  a.slots = (dd || hz) ? mcp_moment_slots(K, n_paths) : mcp::moment_slots(sweep, n_paths);
   a.v0d = (double)(float)prm->v0;
   a.inv_v0d = 1.0 / a.v0d;
   { int e = 0; a.v0_pow2 = std::frexp(a.v0d, &e) == 0.5; }
@@ -420,10 +472,24 @@ static int launch_paths_impl(const mcp_params* prm, const float* d_packed, const
     }
     return MCP_OK;
   }
+  if ((dd || hz) && d_partials && a.slots > (uint64_t)grid)
+    HIP_TRY(mcp::launch_pass0(*prm, K, d_terminal, stride, 0, nullptr, a.slots, (mcp::MomentPartial*)d_partials,
+                              (unsigned long long*)d_hist, (hipStream_t)stream));
+  if (hz) {
+    mcp::PathArgsHZ ah;
+    static_cast<mcp::PathArgs&>(ah) = a;
+    ah.hz = hz->d_out;
+    ah.hz_stride = hz->stride;
+    ah.n_horizons = hz->n;
+    for (int i = 0; i < MCP_MAX_HORIZONS; i++) ah.steps[i] = i < hz->n ? hz->steps[i] : 0;
+    for (int kb = 0; kb < K; kb += kt) {
+      ah.k_begin = kb;
+      hipError_t e = k_launch_hz[nb - 1](variant, ah, grid, (hipStream_t)stream);
+      if (e != hipSuccess) return fail(MCP_E_HIP, "mc_paths_hz_kernel launch: %s", hipGetErrorString(e));
+    }
+    return MCP_OK;
+  }
   if (dd) {
-    if (d_partials && a.slots > (uint64_t)grid)
-      HIP_TRY(mcp::launch_pass0(*prm, K, d_terminal, stride, 0, nullptr, a.slots, (mcp::MomentPartial*)d_partials,
-                                (unsigned long long*)d_hist, (hipStream_t)stream));
     mcp::PathArgsDD ad;
     static_cast<mcp::PathArgs&>(ad) = a;
     ad.mdd = d_mdd;
@@ -458,6 +524,18 @@ int mcp_launch_paths_drawdown(const mcp_params* prm, const float* d_packed, cons
                            d_partials, d_hist, stream);
 }
 
+int mcp_launch_paths_horizons(const mcp_params* prm, const float* d_packed, const double* d_pivot, uint64_t seed, uint64_t path_begin,
+                              uint64_t n_paths, float* d_terminal, uint64_t terminal_stride, int n_horizons, const int32_t* horizons,
+                              float* d_horizon, uint64_t horizon_stride, void* d_partials, void* d_hist, void* stream) {
+  HzOut hz;
+  hz.n = n_horizons;
+  hz.steps = horizons;
+  hz.d_out = d_horizon;
+  hz.stride = horizon_stride;
+  return launch_paths_impl(prm, d_packed, d_pivot, seed, path_begin, n_paths, d_terminal, terminal_stride, nullptr, 0, d_partials,
+                           d_hist, stream, &hz);
+}
+
 // Launches below go to the device that owns the stream.
 #define MCP_ON_STREAM_DEVICE(stream)                                                                     \
   int dev_ = 0;                                                                                          \
@@ -472,6 +550,20 @@ int mcp_percentile_rank(uint64_t n, double alpha, uint64_t* rank_lo, uint64_t* r
   const double pct = (1.0 - alpha) * 100.0;
   const double q = pct / 100.0;
   const double vi = (double)(n - 1) * q;
+  if (vi >= (double)(n - 1)) { *rank_lo = *rank_hi = n - 1; *gamma = 0.0; return MCP_OK; }
+  if (vi < 0.0) { *rank_lo = *rank_hi = 0; *gamma = 0.0; return MCP_OK; }
+  const double fl = std::floor(vi);
+  *rank_lo = (uint64_t)fl;
+  *rank_hi = *rank_lo + 1;
+  *gamma = vi - fl;
+  return MCP_OK;
+}
+
+int mcp_percentile_rank_q(uint64_t n, double q, uint64_t* rank_lo, uint64_t* rank_hi, double* gamma) {
+  if (n < 1 || !rank_lo || !rank_hi || !gamma || !(q >= 0.0 && q <= 100.0)) return fail(MCP_E_ARG, "bad argument");
+  // np.percentile(x, q): numpy divides q by 100, then method 'linear' as in mcp_percentile_rank
+  const double qq = q / 100.0;
+  const double vi = (double)(n - 1) * qq;
   if (vi >= (double)(n - 1)) { *rank_lo = *rank_hi = n - 1; *gamma = 0.0; return MCP_OK; }
   if (vi < 0.0) { *rank_lo = *rank_hi = 0; *gamma = 0.0; return MCP_OK; }
   const double fl = std::floor(vi);
@@ -613,6 +705,10 @@ static void free_shard(Shard& sh) {
   if (sh.h_stats) (void)hipHostFree(sh.h_stats);
   if (sh.d_mdd) (void)hipFree(sh.d_mdd);
   if (sh.h_dd_stats) (void)hipHostFree(sh.h_dd_stats);
+  if (sh.d_hz) (void)hipFree(sh.d_hz);
+  if (sh.d_hz_pivot) (void)hipFree(sh.d_hz_pivot);
+  if (sh.h_hz_pivot) (void)hipHostFree(sh.h_hz_pivot);
+  if (sh.h_hz_stats) (void)hipHostFree(sh.h_hz_stats);
 }
 
 int mcp_ctx_create_multi(const int* devices, int ndev, mcp_ctx** out) {
@@ -813,17 +909,26 @@ int exchange_records(mcp_ctx* c, int kt) {
   return MCP_OK;
 }
 
-// The select / exchange / record phase of one tile, over the [kt][pn] array of every active shard whose moment partials and
-// digit-0 histogram are in the shard's work buffers: three descents of the radix select, exchanges between the steps when the
-// tile is path-sharded (`exchange`), and the [kt] statistics into each shard's mapped host buffer (merged on shard 0 when
-// path-sharded).  `dd`: the drawdown array (SPEC.md 5.1; tp carries v0 = 1, rf = 0, no pivot) instead of the terminal values.
-// When it runs a second time, on the drawdown, the histogram exchange that opens it also orders every shard's work after
-// shard 0's copies of the first phase's records (same-device exchange).
+// What a select phase reduces: the terminal values, the drawdown array (SPEC.md 5.1; tp carries v0 = 1, rf = 0, no pivot) or
+// the horizon array (SPEC.md 5.2; tp carries n_portfolios = H * kt rows, one pivot per row).
+enum SelectOf { SEL_TERMINAL, SEL_DRAWDOWN, SEL_HORIZON };
+
+// The select / exchange / record phase of one tile, over the [rows][pn] array of every active shard (rows = tp[s].n_portfolios)
+// whose moment partials and digit-0 histogram are in the shard's work buffers: three descents of the radix select, exchanges
+// between the steps when the tile is path-sharded (`exchange`), and the [rows] statistics into each shard's mapped host buffer
+// (merged on shard 0 when path-sharded); SEL_HORIZON writes them to slot `slot` of h_hz_stats.  When it runs again, on the
+// drawdown or the horizons, the histogram exchange that opens it also orders every shard's work after shard 0's copies of the
+// previous phase's records (same-device exchange).
 int run_select(mcp_ctx* c, const std::vector<mcp_params>& tp, const std::vector<Job>& jobs, bool exchange, uint64_t lo, uint64_t hi,
-               double gamma, bool dd) {
+               double gamma, SelectOf what, int slot = 0) {
   const size_t S = c->sh.size();
   int rc;
-  const int kt_x = jobs[0].kt;                 // path-sharded tiles: the same portfolios on every shard
+  const int kt_x = tp[0].n_portfolios;         // path-sharded tiles: the same rows on every shard
+  const auto stats_of = [&](Shard& sh, int rows) -> void* {
+    if (what == SEL_DRAWDOWN) return sh.d_dd_stats;
+    if (what == SEL_HORIZON) return (mcp_stats*)sh.d_hz_stats + (size_t)slot * rows;
+    return sh.ws[MCP_WS_STATS];
+  };
   for (int pass = 0; pass < 3; pass++) {
     if (exchange && (rc = exchange_hist(c, kt_x))) return rc;
     for (size_t s = 0; s < S; s++) {
@@ -832,15 +937,15 @@ int run_select(mcp_ctx* c, const std::vector<mcp_params>& tp, const std::vector<
       Shard& sh = c->sh[s];
       HIP_TRY(hipSetDevice(sh.device));
       const uint64_t stride = j.pn ? j.pn : 1;
-      const double* piv = dd ? nullptr : (const double*)sh.ws[MCP_WS_PIVOT];
-      const float* src = dd ? sh.d_mdd : sh.d_terminal;
+      const double* piv = what == SEL_DRAWDOWN ? nullptr : what == SEL_HORIZON ? sh.d_hz_pivot : (const double*)sh.ws[MCP_WS_PIVOT];
+      const float* src = what == SEL_DRAWDOWN ? sh.d_mdd : what == SEL_HORIZON ? sh.d_hz : sh.d_terminal;
       if (pass < 2) {
         if ((rc = mcp_launch_scan(&tp[s], pass, j.pn, lo, hi, sh.ws[MCP_WS_PARTIALS], sh.ws[MCP_WS_BELOW], piv, sh.ws[MCP_WS_HIST],
                                   sh.ws[MCP_WS_STATE], sh.ws[MCP_WS_RECORD], sh.stream))) return rc;
         if ((rc = mcp_launch_hist(&tp[s], pass + 1, src, stride, j.pn, sh.ws[MCP_WS_STATE], piv, sh.ws[MCP_WS_BELOW],
                                   sh.ws[MCP_WS_HIST], sh.stream))) return rc;
       } else {
-        void* stats = exchange ? nullptr : (dd ? sh.d_dd_stats : sh.ws[MCP_WS_STATS]);
+        void* stats = exchange ? nullptr : stats_of(sh, tp[s].n_portfolios);
         if ((rc = mcp_launch_final(&tp[s], j.pn, gamma, lo, hi, sh.ws[MCP_WS_BELOW], sh.ws[MCP_WS_HIST], sh.ws[MCP_WS_STATE],
                                    sh.ws[MCP_WS_RECORD], sh.ws[MCP_WS_QUANT], stats, sh.stream)))
           return rc;
@@ -852,18 +957,30 @@ int run_select(mcp_ctx* c, const std::vector<mcp_params>& tp, const std::vector<
     if ((rc = exchange_records(c, kt_x))) return rc;
     Shard& s0 = c->sh[0];
     HIP_TRY(hipSetDevice(s0.device));
-    if ((rc = mcp_launch_stats(&tp[0], (int)S, s0.d_gather, s0.ws[MCP_WS_QUANT], dd ? s0.d_dd_stats : s0.ws[MCP_WS_STATS], s0.stream)))
+    if ((rc = mcp_launch_stats(&tp[0], (int)S, s0.d_gather, s0.ws[MCP_WS_QUANT], stats_of(s0, kt_x), s0.stream)))
       return rc;
   }
   return MCP_OK;
 }
 
+// The horizon request of mcp_simulate_horizons (SPEC.md 4.3 / 5.2).
+struct HzReq {
+  int H = 0, L = 0;
+  const int32_t* steps = nullptr;
+  const double* levels = nullptr;
+  float* out = nullptr;              // NULL or [H*K*n], row h*K + k
+  mcp_stats* stats_out = nullptr;    // [H*K]
+  double* bands_out = nullptr;       // [H*K*L]
+};
+
 // One tile: every active shard simulates its (portfolios x paths) block -- the kernels' epilogue leaves the moment partials
 // and the digit-0 histogram -- and the rest of the statistics pipeline runs (run_select).  `dd`: the path kernels also leave
 // the drawdown array, and after the terminal values a pass 0 over it and a second run_select reduce it to dd_stats_out.
+// `hz`: the path kernels also leave the [H][kt][pn] horizon array; after the terminal values it is reduced as H*kt rows, once
+// at alpha (pass 0 + run_select) and once per level at that level's rank, whose records contribute only their `var`.
 int run_tile(mcp_ctx* c, const mcp_params* prm, const float* mu, const float* chol, const float* W, uint64_t seed,
              uint64_t path_begin, uint64_t n_total, const std::vector<Job>& jobs, bool exchange, float* terminal_out,
-             mcp_stats* stats_out, bool dd, float* mdd_out, mcp_stats* dd_stats_out) {
+             mcp_stats* stats_out, bool dd, float* mdd_out, mcp_stats* dd_stats_out, const HzReq* hz) {
   const size_t S = c->sh.size();
   uint64_t lo, hi;
   double gamma;
@@ -878,12 +995,26 @@ int run_tile(mcp_ctx* c, const mcp_params* prm, const float* mu, const float* ch
     HIP_TRY(hipSetDevice(sh.device));
     tp[s].n_portfolios = j.kt;
     const size_t plen = mcp_packed_len(prm->n_assets, j.kt);
-    for (int w = 0; w < MCP_WS_COUNT; w++)      // only the histogram and the select state must start zeroed
-      if (w != MCP_WS_STATS && (rc = grow_dev(&sh.ws[w], &sh.ws_cap[w], mcp_ws_bytes(w, j.kt, j.pn ? j.pn : 1), sh.stream,
-                                              w == MCP_WS_HIST || w == MCP_WS_STATE))) return rc;
+    const int rows = hz ? hz->H * j.kt : j.kt;  // horizon calls: the work buffers also serve the H*kt rows of the horizon selects
+    for (int w = 0; w < MCP_WS_COUNT; w++) {    // only the histogram and the select state must start zeroed
+      const size_t need = std::max(mcp_ws_bytes(w, j.kt, j.pn ? j.pn : 1), mcp_ws_bytes(w, rows, j.pn ? j.pn : 1));
+      if (w != MCP_WS_STATS && (rc = grow_dev(&sh.ws[w], &sh.ws_cap[w], need, sh.stream, w == MCP_WS_HIST || w == MCP_WS_STATE)))
+        return rc;
+    }
     if ((rc = grow_dev((void**)&sh.d_packed, &sh.packed_cap, plen * sizeof(float)))) return rc;
     if ((rc = grow_dev((void**)&sh.d_terminal, &sh.terminal_cap, (size_t)j.kt * (j.pn ? j.pn : 1) * sizeof(float)))) return rc;
-    if (exchange && (rc = grow_dev((void**)&sh.d_gather, &sh.gather_cap, S * (size_t)j.kt * sizeof(mcp_record)))) return rc;
+    if (exchange && (rc = grow_dev((void**)&sh.d_gather, &sh.gather_cap, S * (size_t)std::max(j.kt, rows) * sizeof(mcp_record))))
+      return rc;
+    if (hz) {
+      const size_t hz_stats_bytes = (size_t)(1 + hz->L) * rows * sizeof(mcp_stats);
+      if ((rc = grow_dev((void**)&sh.d_hz, &sh.hz_cap, (size_t)rows * (j.pn ? j.pn : 1) * sizeof(float)))) return rc;
+      if ((rc = grow_dev((void**)&sh.d_hz_pivot, &sh.hz_pivot_cap, (size_t)rows * sizeof(double)))) return rc;
+      if ((rc = grow_host((void**)&sh.h_hz_pivot, &sh.h_hz_pivot_cap, (size_t)rows * sizeof(double)))) return rc;
+      if (hz_stats_bytes > sh.h_hz_stats_cap) {
+        if ((rc = grow_host((void**)&sh.h_hz_stats, &sh.h_hz_stats_cap, hz_stats_bytes, true))) return rc;
+        HIP_TRY(hipHostGetDevicePointer(&sh.d_hz_stats, sh.h_hz_stats, 0));
+      }
+    }
     if ((rc = grow_host((void**)&sh.h_packed, &sh.h_packed_cap, plen * sizeof(float)))) return rc;
     if ((rc = grow_host((void**)&sh.h_pivot, &sh.h_pivot_cap, (size_t)j.kt * sizeof(double)))) return rc;
     if ((size_t)j.kt * sizeof(mcp_stats) > sh.h_stats_cap) {
@@ -921,9 +1052,23 @@ int run_tile(mcp_ctx* c, const mcp_params* prm, const float* mu, const float* ch
     }
     HIP_TRY(hipMemcpyAsync(sh.d_packed, src, plen * sizeof(float), hipMemcpyHostToDevice, sh.stream));
     HIP_TRY(hipMemcpyAsync(sh.ws[MCP_WS_PIVOT], psrc, (size_t)j.kt * sizeof(double), hipMemcpyHostToDevice, sh.stream));
+    HzOut hzo;
+    if (hz) {                                                // SPEC.md 5.2: row h*kt + k is pivoted with n_steps = h
+      mcp_params ph = tp[s];
+      for (int h = 0; h < hz->H; h++) {
+        ph.n_steps = hz->steps[h];
+        if ((rc = mcp_pivots(&ph, mu, chol, W + (size_t)j.k0 * prm->n_assets, sh.h_hz_pivot + (size_t)h * j.kt))) return rc;
+      }
+      HIP_TRY(hipMemcpyAsync(sh.d_hz_pivot, sh.h_hz_pivot, (size_t)hz->H * j.kt * sizeof(double), hipMemcpyHostToDevice, sh.stream));
+      hzo.n = hz->H;
+      hzo.steps = hz->steps;
+      hzo.d_out = sh.d_hz;
+      hzo.stride = j.pn;
+    }
     if (j.pn) {
       if ((rc = launch_paths_impl(&tp[s], sh.d_packed, (const double*)sh.ws[MCP_WS_PIVOT], seed, path_begin + j.p0, j.pn, sh.d_terminal,
-                                  j.pn, dd ? sh.d_mdd : nullptr, j.pn, sh.ws[MCP_WS_PARTIALS], sh.ws[MCP_WS_HIST], sh.stream))) return rc;
+                                  j.pn, dd ? sh.d_mdd : nullptr, j.pn, sh.ws[MCP_WS_PARTIALS], sh.ws[MCP_WS_HIST], sh.stream,
+                                  hz ? &hzo : nullptr))) return rc;
     } else {
       // a shard without paths (fewer paths than shards): empty moment partials, nothing in the histogram
       if ((rc = mcp_launch_pass0(&tp[s], sh.d_terminal, 1, 0, (const double*)sh.ws[MCP_WS_PIVOT], sh.ws[MCP_WS_PARTIALS],
@@ -931,7 +1076,7 @@ int run_tile(mcp_ctx* c, const mcp_params* prm, const float* mu, const float* ch
     }
   }
   // 2. the terminal values' select, exchanges and records
-  if ((rc = run_select(c, tp, jobs, exchange, lo, hi, gamma, false))) return rc;
+  if ((rc = run_select(c, tp, jobs, exchange, lo, hi, gamma, SEL_TERMINAL))) return rc;
   // 3. drawdown (SPEC.md 5.1): the same pipeline over q / d -- x = q - 1 (simple, v0 = 1) or expm1(d) (log), no pivot, no rf
   std::vector<mcp_params> tpd(tp);
   if (dd) {
@@ -945,7 +1090,27 @@ int run_tile(mcp_ctx* c, const mcp_params* prm, const float* mu, const float* ch
       if ((rc = mcp_launch_pass0(&tpd[s], sh.d_mdd, j.pn ? j.pn : 1, j.pn, nullptr, sh.ws[MCP_WS_PARTIALS], sh.ws[MCP_WS_HIST], sh.stream)))
         return rc;
     }
-    if ((rc = run_select(c, tpd, jobs, exchange, lo, hi, gamma, true))) return rc;
+    if ((rc = run_select(c, tpd, jobs, exchange, lo, hi, gamma, SEL_DRAWDOWN))) return rc;
+  }
+  // 4. horizons (SPEC.md 5.2): the H*kt rows of the horizon array, at alpha and at every level's rank
+  if (hz) {
+    std::vector<mcp_params> tph(tp);
+    for (size_t s = 0; s < S; s++)
+      if (jobs[s].active) tph[s].n_portfolios = hz->H * jobs[s].kt;
+    for (int l = -1; l < hz->L; l++) {
+      uint64_t qlo = lo, qhi = hi;
+      double qg = gamma;
+      if (l >= 0 && (rc = mcp_percentile_rank_q(n_total, hz->levels[l], &qlo, &qhi, &qg))) return rc;
+      for (size_t s = 0; s < S; s++) {
+        const Job& j = jobs[s];
+        if (!j.active) continue;
+        Shard& sh = c->sh[s];
+        HIP_TRY(hipSetDevice(sh.device));
+        if ((rc = mcp_launch_pass0(&tph[s], sh.d_hz, j.pn ? j.pn : 1, j.pn, sh.d_hz_pivot, sh.ws[MCP_WS_PARTIALS], sh.ws[MCP_WS_HIST],
+                                   sh.stream))) return rc;
+      }
+      if ((rc = run_select(c, tph, jobs, exchange, qlo, qhi, qg, SEL_HORIZON, l + 1))) return rc;
+    }
   }
   for (size_t s = 0; s < S; s++) {
     const Job& j = jobs[s];
@@ -959,6 +1124,11 @@ int run_tile(mcp_ctx* c, const mcp_params* prm, const float* mu, const float* ch
     if (dd && mdd_out && j.pn)
       HIP_TRY(hipMemcpy2DAsync(mdd_out + (size_t)j.k0 * n_total + j.p0, n_total * sizeof(float), sh.d_mdd,
                                j.pn * sizeof(float), j.pn * sizeof(float), (size_t)j.kt, hipMemcpyDeviceToHost, sh.stream));
+    if (hz && hz->out && j.pn)
+      for (int h = 0; h < hz->H; h++)
+        HIP_TRY(hipMemcpy2DAsync(hz->out + ((size_t)h * prm->n_portfolios + j.k0) * n_total + j.p0, n_total * sizeof(float),
+                                 sh.d_hz + (size_t)h * j.kt * j.pn, j.pn * sizeof(float), j.pn * sizeof(float), (size_t)j.kt,
+                                 hipMemcpyDeviceToHost, sh.stream));
   }
   for (size_t s = 0; s < S; s++)
     if (jobs[s].active) { HIP_TRY(hipSetDevice(c->sh[s].device)); HIP_TRY(hipStreamSynchronize(c->sh[s].stream)); }
@@ -969,11 +1139,23 @@ int run_tile(mcp_ctx* c, const mcp_params* prm, const float* mu, const float* ch
         memcpy(dd_stats_out + jobs[s].k0, c->sh[s].h_dd_stats, (size_t)jobs[s].kt * sizeof(mcp_stats));
         for (int k = 0; k < jobs[s].kt; k++) dd_stats_out[jobs[s].k0 + k].sharpe = 0.0;
       }
+      if (hz) {                                        // slot 0: the records at alpha; slot 1 + l: level l's quantile (var)
+        const int kt = jobs[s].kt, rows = hz->H * kt;
+        const mcp_stats* hs = c->sh[s].h_hz_stats;
+        for (int h = 0; h < hz->H; h++)
+          for (int k = 0; k < kt; k++) {
+            const size_t o = (size_t)h * prm->n_portfolios + jobs[s].k0 + k, r = (size_t)h * kt + k;
+            hz->stats_out[o] = hs[r];
+            hz->stats_out[o].sharpe = 0.0;
+            for (int l = 0; l < hz->L; l++) hz->bands_out[o * hz->L + l] = hs[(size_t)(1 + l) * rows + r].var;
+          }
+      }
     }
   return MCP_OK;
 }
 
-// Portfolios per tile so that kt * n_paths * bytes_per_path fits the budget (4 B of V_T, 8 B with the drawdown array): whole
+// Portfolios per tile so that kt * n_paths * bytes_per_path fits the budget (4 B of V_T, 8 B with the drawdown array,
+// 4 (1 + H) B with H horizons): whole
 // 512-portfolio workgroups of the MFMA sweep kernel when K is tiled at all.
 int tile_portfolios(size_t budget, uint64_t n_paths, int K, size_t bytes_per_path = sizeof(float)) {
   const uint64_t fit = budget / (bytes_per_path * (n_paths ? n_paths : 1));
@@ -984,14 +1166,16 @@ int tile_portfolios(size_t budget, uint64_t n_paths, int K, size_t bytes_per_pat
 
 int simulate_impl(mcp_ctx* c, const mcp_params* prm, const float* mu, const float* chol, const float* W, uint64_t seed,
                   uint64_t path_begin, uint64_t n_paths, float* terminal_out, mcp_stats* stats_out, bool dd, float* mdd_out,
-                  mcp_stats* dd_stats_out) {
+                  mcp_stats* dd_stats_out, const HzReq* hz = nullptr) {
   if (!c) return fail(MCP_E_ARG, "ctx is NULL");
   if (int rc = check_params(prm)) return rc;
   if (!mu || !chol || !W || !stats_out || (dd && !dd_stats_out)) return fail(MCP_E_ARG, "NULL pointer");
   if (n_paths < 1) return fail(MCP_E_ARG, "n_paths must be >= 1");
   if (dd && (prm->flags & (MCP_FLAG_FOLD | MCP_FLAG_NATIVE_MATH)))
     return fail(MCP_E_UNSUPPORTED, "the drawdown runs on the spec's normals and the unfolded recurrence (no MCP_FLAG_FOLD / MCP_FLAG_NATIVE_MATH)");
-  const size_t bytes_per_path = dd ? 2 * sizeof(float) : sizeof(float);
+  if (hz && (prm->flags & (MCP_FLAG_FOLD | MCP_FLAG_NATIVE_MATH)))
+    return fail(MCP_E_UNSUPPORTED, "the horizons run on the spec's normals and the unfolded recurrence (no MCP_FLAG_FOLD / MCP_FLAG_NATIVE_MATH)");
+  const size_t bytes_per_path = hz ? (1 + (size_t)hz->H) * sizeof(float) : dd ? 2 * sizeof(float) : sizeof(float);
   std::lock_guard<std::mutex> lock(c->mu);
   const size_t S = c->sh.size();
   const int K = prm->n_portfolios;
@@ -1015,7 +1199,8 @@ int simulate_impl(mcp_ctx* c, const mcp_params* prm, const float* mu, const floa
         done[s] += kt;
         more = true;
       }
-      if (more) rc = run_tile(c, prm, mu, chol, W, seed, path_begin, n_paths, jobs, false, terminal_out, stats_out, dd, mdd_out, dd_stats_out);
+      if (more)
+        rc = run_tile(c, prm, mu, chol, W, seed, path_begin, n_paths, jobs, false, terminal_out, stats_out, dd, mdd_out, dd_stats_out, hz);
     }
   } else {
     // the path range is sharded; all shards see the same tile of portfolios
@@ -1031,13 +1216,13 @@ int simulate_impl(mcp_ctx* c, const mcp_params* prm, const float* mu, const floa
     for (int k0 = 0; k0 < K && rc == MCP_OK; k0 += kt_max) {
       for (size_t s = 0; s < S; s++) { jobs[s].k0 = k0; jobs[s].kt = std::min(kt_max, K - k0); }
       rc = run_tile(c, prm, mu, chol, W, seed, path_begin, n_paths, jobs, S > 1 || c->exchange_always, terminal_out, stats_out, dd,
-                    mdd_out, dd_stats_out);
+                    mdd_out, dd_stats_out, hz);
     }
   }
   if (rc != MCP_OK) {
     // Leave no work in flight behind a failed call, and restore the invariant of the read-and-clear protocol: a pass that
-    // stopped half way may have left counts in the histograms, and the next call would add to them.  (Both selects of a
-    // drawdown call -- terminal values and drawdowns -- share these buffers.)
+    // stopped half way may have left counts in the histograms, and the next call would add to them.  (Every select of a
+    // drawdown or horizon call -- terminal values, drawdowns, horizon rows -- shares these buffers.)
     const std::string why = g_err;
     for (Shard& sh : c->sh) { (void)hipSetDevice(sh.device); (void)hipStreamSynchronize(sh.stream); }
     for (Shard& sh : c->sh) {
@@ -1064,6 +1249,27 @@ int mcp_simulate_drawdown(mcp_ctx* c, const mcp_params* prm, const float* mu, co
                           uint64_t path_begin, uint64_t n_paths, float* terminal_out, mcp_stats* stats_out, float* mdd_out,
                           mcp_stats* dd_stats_out) {
   return simulate_impl(c, prm, mu, chol, W, seed, path_begin, n_paths, terminal_out, stats_out, true, mdd_out, dd_stats_out);
+}
+
+int mcp_simulate_horizons(mcp_ctx* c, const mcp_params* prm, const float* mu, const float* chol, const float* W, uint64_t seed,
+                          uint64_t path_begin, uint64_t n_paths, int n_horizons, const int32_t* horizons, int n_levels,
+                          const double* levels, float* terminal_out, mcp_stats* stats_out, float* horizon_out,
+                          mcp_stats* hz_stats_out, double* bands_out) {
+  // the arguments first, so that each error is found (and named) before any device is touched, a NULL ctx included
+  if (int rc = check_params(prm)) return rc;
+  if (int rc = check_horizons(prm->n_steps, n_horizons, horizons)) return rc;
+  if (int rc = check_levels(n_levels, levels)) return rc;
+  if (!hz_stats_out) return fail(MCP_E_ARG, "hz_stats_out is NULL");
+  if ((bands_out == nullptr) != (n_levels == 0)) return fail(MCP_E_ARG, "bands_out must be NULL exactly when n_levels == 0");
+  HzReq hz;
+  hz.H = n_horizons;
+  hz.L = n_levels;
+  hz.steps = horizons;
+  hz.levels = levels;
+  hz.out = horizon_out;
+  hz.stats_out = hz_stats_out;
+  hz.bands_out = bands_out;
+  return simulate_impl(c, prm, mu, chol, W, seed, path_begin, n_paths, terminal_out, stats_out, false, nullptr, nullptr, &hz);
 }
 
 int mcp_sweep_historical(mcp_ctx* c, int N, int R, int P, const double* returns, const double* mean, const double* cov,

@@ -73,6 +73,14 @@ struct PathArgsDD : PathArgs {
   uint64_t mdd_stride;
 };
 
+// Arguments of mc_paths_hz_kernel: PathArgs and the values at the horizons of SPEC.md 4.3.
+struct PathArgsHZ : PathArgs {
+  float* __restrict__ hz;             // [H][K][hz_stride]: V_h (simple) / S_h (log), row h*K + k
+  uint64_t hz_stride;
+  int32_t n_horizons;                 // H in [1, MCP_MAX_HORIZONS]
+  int32_t steps[MCP_MAX_HORIZONS];    // strictly increasing, in [1, n_steps]
+};
+
 __device__ __forceinline__ double wave_sum(double v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
@@ -130,13 +138,14 @@ constexpr int PATH_BLOCK = 256;
 // v = L^T w precomputed on the host (SPEC.md 4.1, one portfolio) instead of the triangular GEMV.
 // LOGC: compounding mode at compile time (as a run-time flag the compiler if-converts the step into fma + add + select).
 // DD: also track the running peak and the max drawdown of every (path, portfolio) through the step loop (SPEC.md 4.2) and
-// store q (simple: min V_t/P_t) or d (log: min S_t - P_t) next to V_T.  Both kernels are the body in mcp_paths_body.inc.
+// store q (simple: min V_t/P_t) or d (log: min S_t - P_t) next to V_T.  HZ: also store V_h at the horizons (SPEC.md 4.3).
+// All three kernels are the body in mcp_paths_body.inc.
 #define MCP_PATHS_BOUNDS(NB, KT, PPT) \
   __launch_bounds__(PATH_BLOCK, (NB <= 4 && KT == 1 && PPT == 1) ? MCP_MIN_WAVES : ((KT == 1 && PPT == 1) ? MCP_MIN_WAVES_BIG : 1))
 
 template <int NB, int KT, int PPT, bool NATIVE, bool FOLD = false, bool LOGC = false>
 __global__ void MCP_PATHS_BOUNDS(NB, KT, PPT) mc_paths_kernel(const PathArgs a) {
-  constexpr bool DD = false;
+  constexpr bool DD = false, HZ = false;
 #include "mcp_paths_body.inc"
 }
 
@@ -144,7 +153,15 @@ __global__ void MCP_PATHS_BOUNDS(NB, KT, PPT) mc_paths_kernel(const PathArgs a) 
 // array: appended to PathArgs itself they would move the hidden kernel arguments (grid size) of every plain kernel.
 template <int NB, int KT, int PPT, bool LOGC>
 __global__ void MCP_PATHS_BOUNDS(NB, KT, PPT) mc_paths_dd_kernel(const PathArgsDD a) {
-  constexpr bool DD = true, NATIVE = false, FOLD = false;
+  constexpr bool DD = true, HZ = false, NATIVE = false, FOLD = false;
+#include "mcp_paths_body.inc"
+}
+
+// The horizon kernel (SPEC.md 4.3; spec normals, unfolded recurrence only): the walk of mc_paths_kernel in segments that end
+// at the horizons, V_h stored after each; V_T and the fused epilogue as in mc_paths_kernel.
+template <int NB, int KT, int PPT, bool LOGC>
+__global__ void MCP_PATHS_BOUNDS(NB, KT, PPT) mc_paths_hz_kernel(const PathArgsHZ a) {
+  constexpr bool DD = false, HZ = true, NATIVE = false, FOLD = false;
 #include "mcp_paths_body.inc"
 }
 #undef MCP_PATHS_BOUNDS

@@ -63,4 +63,21 @@ hipError_t MCP_CAT(launch_paths_dd_nb, MCP_NB)(int variant, const PathArgsDD& ar
   return hipGetLastError();
 }
 
+// The horizon kernel (mcp_launch_paths_horizons): one portfolio or KT = 8 passes, both compounding modes.
+hipError_t MCP_CAT(launch_paths_hz_nb, MCP_NB)(int variant, const PathArgsHZ& args, int grid, hipStream_t stream) {
+  const bool lg = args.compounding == MCP_COMPOUND_LOG;
+  switch (variant) {
+    case 0:
+      if (lg) mc_paths_hz_kernel<MCP_NB, 1, 1, true><<<grid, PATH_BLOCK, lds_pad(), stream>>>(args);
+      else mc_paths_hz_kernel<MCP_NB, 1, 1, false><<<grid, PATH_BLOCK, lds_pad(), stream>>>(args);
+      break;
+    case VAR_KT8:
+      if (lg) mc_paths_hz_kernel<MCP_NB, 8, 1, true><<<grid, PATH_BLOCK, lds_pad(), stream>>>(args);
+      else mc_paths_hz_kernel<MCP_NB, 8, 1, false><<<grid, PATH_BLOCK, lds_pad(), stream>>>(args);
+      break;
+    default: return hipErrorInvalidValue;
+  }
+  return hipGetLastError();
+}
+
 }  // namespace mcp

@@ -1,0 +1,80 @@
+// mcp_paths_step.inc -- one step t of the path kernels' walk (mcp_paths_body.inc, included in its step loops): the normals of
+// step t, r = mu + L z, rho = w.r, the update of V (and, DD, of the running peak and drawdown state).  In scope: everything
+// mcp_paths_body.inc declares before its step loops, and t.
+      // keep the (loop-invariant) parameter loads inside the step: hoisted, they would pin ~170 registers
+      asm volatile("" : "+s"(mu), "+s"(Lp), "+s"(Wk));
+      uint32_t par_off = 0;                                        // opaque zero: keeps the LDS reads inside the step too
+      if constexpr (LDS_MU) asm volatile("" : "+v"(par_off));
+      const float* s_par = s_par0 + par_off;
+      float z[PPT][N4];
+#pragma unroll
+      for (int q = 0; q < NB; q++) {
+        const uint32_t blk = (uint32_t)t * NB + q;     // counter.x; counter.y = 0 (T*NB < 2^32)
+#pragma unroll
+        for (int e = 0; e < PPT; e++) {
+          uint32_t x[4];
+          philox4x32_10(blk, 0u, plo[e], phi[e], ks, x);
+          block_normals<NATIVE>(x, s_tab, kc, z[e][0 * NB + q], z[e][1 * NB + q], z[e][2 * NB + q], z[e][3 * NB + q]);
+        }
+      }
+      float rho[PPT][KT];
+      if constexpr (FOLD) {
+        cfloat_p fv = mu + a.fold_offset;
+        asm volatile("" : "+s"(fv));
+#pragma unroll
+        for (int e = 0; e < PPT; e++) {
+          float acc = fv[0];
+#pragma unroll
+          for (int j = 0; j < N4; j++) acc = fma32(fv[1 + j], z[e][j], acc);
+          rho[e][0] = acc;
+        }
+      } else {
+      // r = mu + L z (row i: acc = mu_i, then j ascending), rho_k = sum_i w_ki r_i (i ascending)
+#pragma unroll
+      for (int e = 0; e < PPT; e++)
+#pragma unroll
+        for (int k = 0; k < KT; k++) rho[e][k] = 0.0f;
+      // Rows are processed in pairs (2m, 2m+1): one v_pk_fma_f32 per column does both rows, its L operand
+      // an SGPR pair straight from the row-pair-interleaved parameter block, z_j broadcast by op_sel.
+#pragma unroll
+      for (int m = 0; m < N4 / 2; m++) {
+        f32x2 acc[PPT];
+        f32x2 mu2;
+        if constexpr (LDS_MU) mu2 = *(const f32x2*)&s_par[2 * m];
+        else mu2 = f32x2{mu[2 * m], mu[2 * m + 1]};
+#pragma unroll
+        for (int e = 0; e < PPT; e++) acc[e] = mu2;
+#pragma unroll
+        for (int j = 0; j <= 2 * m + 1; j++) {
+          const f32x2 l2 = {Lp[2 * m * (m + 1) + 2 * j], Lp[2 * m * (m + 1) + 2 * j + 1]};   // (L[2m][j], L[2m+1][j])
+#pragma unroll
+          for (int e = 0; e < PPT; e++) acc[e] = __builtin_elementwise_fma(l2, (f32x2){z[e][j], z[e][j]}, acc[e]);
+        }
+#pragma unroll
+        for (int h = 0; h < 2; h++) {
+          const int i = 2 * m + h;
+#pragma unroll
+          for (int k = 0; k < KT; k++) {
+            const float wki = LDS_W ? s_par[N4 + i] : Wk[k * N4 + i];   // rows >= kt are zero-padded by pack_params
+#pragma unroll
+            for (int e = 0; e < PPT; e++) rho[e][k] = fma32(wki, h ? acc[e].y : acc[e].x, rho[e][k]);
+          }
+        }
+      }
+      }  // !FOLD
+#pragma unroll
+      for (int e = 0; e < PPT; e++)
+#pragma unroll
+        for (int k = 0; k < KT; k++)
+          V[e][k] = logc ? (V[e][k] + rho[e][k]) : fma32(V[e][k], rho[e][k], V[e][k]);
+      if constexpr (DD) {
+        // SPEC.md 4.2: P = fmax(P, V_t); q = fminf(q, V_t / P) (IEEE division) or d = fminf(d, S_t - P).  fminf is IEEE
+        // minNum: the 0/0 of a zero peak is ignored.
+#pragma unroll
+        for (int e = 0; e < PPT; e++)
+#pragma unroll
+          for (int k = 0; k < KT; k++) {
+            Pk[e][k] = fmaxf(Pk[e][k], V[e][k]);
+            Qk[e][k] = fminf(Qk[e][k], logc ? V[e][k] - Pk[e][k] : V[e][k] / Pk[e][k]);
+          }
+      }

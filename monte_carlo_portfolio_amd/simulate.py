@@ -89,6 +89,44 @@ class Context:
             dd_stats.ctypes.data_as(ctypes.c_void_p)))
         return stats, dd_stats, term, raw
 
+    def simulate_horizons(self, prm: _ffi.McpParams, mu, chol, W, seed: int, path_begin: int, n_paths: int, horizons, levels,
+                          store: bool):
+        """simulate() plus the values after the steps `horizons` (SPEC.md 4.3 / 5.2; include/mcport.h, mcp_simulate_horizons)
+        -> (stats [K], hz_stats [H, K] mcp_stats records, bands [H, K, L] float64 np.percentile(x_h, levels), terminal,
+        horizon_terminal): with `store`, terminal is [K, n_paths] and horizon_terminal the binary32 [H, K, n_paths] V_h / S_h."""
+        K = prm.n_portfolios
+        steps = np.ascontiguousarray(horizons, np.int32).ravel()
+        lv = np.ascontiguousarray(levels, np.float64).ravel()
+        H, L = steps.size, lv.size
+        stats = np.zeros(K, _ffi.STATS_DTYPE)
+        hz_stats = np.zeros((H, K), _ffi.STATS_DTYPE)
+        bands = np.zeros((H, K, L), np.float64)
+        term = np.empty((K, n_paths), np.float32) if store else None
+        hz_term = np.empty((H, K, n_paths), np.float32) if store else None
+        ptr = lambda a: a.ctypes.data_as(ctypes.c_void_p) if a is not None else None   # noqa: E731
+        _ffi.check(_ffi.lib().mcp_simulate_horizons(
+            self._h, ctypes.byref(prm), mu, chol, W, seed, path_begin, n_paths, H, ptr(steps), L, ptr(lv) if L else None,
+            ptr(term), ptr(stats), ptr(hz_term), ptr(hz_stats), ptr(bands) if L else None))
+        return stats, hz_stats, bands, term, hz_term
+
+
+def check_horizons(horizons, bands, n_steps):
+    """SPEC.md 4.3 / 5.2 argument rules -> (steps int32 [H], levels float64 [L]); ValueError otherwise."""
+    h = np.asarray(horizons)
+    if h.ndim != 1 or h.size < 1 or h.size > _ffi.MCP_MAX_HORIZONS:
+        raise ValueError(f"horizons must be a list of 1..{_ffi.MCP_MAX_HORIZONS} steps, got shape {h.shape}")
+    if not np.issubdtype(h.dtype, np.integer) and not (np.issubdtype(h.dtype, np.floating) and np.all(h == np.round(h))):
+        raise ValueError(f"horizons must be whole steps, got {horizons!r}")
+    steps = h.astype(np.int64)
+    if steps[0] < 1 or steps[-1] > n_steps or np.any(np.diff(steps) <= 0):
+        raise ValueError(f"horizons must be strictly increasing steps in [1, n_steps={n_steps}], got {steps.tolist()}")
+    levels = np.asarray(bands, np.float64).ravel()
+    if levels.size > _ffi.MCP_MAX_LEVELS:
+        raise ValueError(f"at most {_ffi.MCP_MAX_LEVELS} band levels, got {levels.size}")
+    if not np.all((levels >= 0.0) & (levels <= 100.0)):
+        raise ValueError(f"band levels are percentages in [0, 100], got {levels.tolist()}")
+    return steps.astype(np.int32), levels
+
 
 def mdd_from_raw(qd, compounding="simple") -> np.ndarray:
     """SPEC.md 4.2: the per-path max drawdown in binary64 from the kernel's binary32 q (simple: q - 1) or d (log: expm1(d))."""
@@ -161,7 +199,8 @@ def drawdown_to_dict(rec) -> dict:
 
 def simulate_paths(mu, cov, weights, n_steps=252, n_paths=10_000, seed=0, v0=1.0, compounding="simple",
                    rf=0.0, alpha=0.95, devices=None, store=False, path_begin=0, chol=None,
-                   native_math=False, as_array=False, fold=False, shard="auto", context=None, drawdown=False):
+                   native_math=False, as_array=False, fold=False, shard="auto", context=None, drawdown=False,
+                   horizons=None, bands=()):
     """Simulate `n_paths` correlated return paths and reduce them to risk statistics.
 
     mu [N], cov [N,N] are per-step mean and covariance (the reference's `mean_returns`, `cov_matrix`
@@ -178,9 +217,22 @@ def simulate_paths(mu, cov, weights, n_steps=252, n_paths=10_000, seed=0, v0=1.0
     (SPEC.md 5.1): every dict gains 'drawdown' {mean, std, dar, cdar, n_tail, worst, best, x_lo, x_hi} and, with store=True,
     'max_drawdown' (float64 per-path drawdowns).  as_array=True returns (stats, dd_stats) [+ (terminal, max_drawdown) with
     store].  Not with fold or native_math (ValueError).
+
+    horizons=[h_1 < ... < h_H] (steps in [1, n_steps], at most 64), bands=(q_1, ...) (percentages, at most 16): also the value of
+    every path after step h (SPEC.md 4.3: bit for bit the terminal value of the same call with n_steps = h) and, per horizon,
+    the statistics of x_h = V_h/v0 - 1 (log: expm1(S_h)) at alpha and np.percentile(x_h, q) for every level (SPEC.md 5.2).
+    Every dict gains 'horizons' {steps, levels, bands [H, L], mean, std, var, cvar, min, max, n_tail [H]} and, with store=True,
+    'horizon_terminal' (float32 [H, n_paths], raw V_h / S_h).  as_array=True returns (stats, hz_stats [H, K], bands [H, K, L])
+    [+ (terminal, horizon_terminal [H, K, n_paths]) with store].  Not with drawdown, fold or native_math (ValueError).
     """
     if drawdown and (fold or native_math):
         raise ValueError("drawdown=True needs the spec's normals and the unfolded recurrence: not with fold or native_math")
+    if horizons is not None:
+        if drawdown or fold or native_math:
+            raise ValueError("horizons need the spec's normals and the unfolded recurrence: not with drawdown, fold or native_math")
+        steps, levels = check_horizons(horizons, bands, n_steps)
+    elif len(np.atleast_1d(np.asarray(bands, np.float64))):
+        raise ValueError("bands need horizons")
     single = np.asarray(weights).ndim == 1
     mu32, L, W = prepare_inputs(mu, cov, weights, chol)
     devs = (0,) if not devices else tuple(int(d) for d in devices)
@@ -189,7 +241,12 @@ def simulate_paths(mu, cov, weights, n_steps=252, n_paths=10_000, seed=0, v0=1.0
     by_portfolio = len(devs) > 1 and (shard == "portfolios" or (shard == "auto" and W.shape[0] >= 512 * len(devs)))
     prm = _ffi.make_params(mu32.shape[0], n_steps, W.shape[0], compounding, v0, alpha, rf, native_math, fold, by_portfolio)
     ctx = context if context is not None else default_context(devs)
-    if drawdown:
+    if horizons is not None:
+        stats, hz_stats, hz_bands, term, hz_term = ctx.simulate_horizons(prm, mu32, L, W, int(seed), int(path_begin), int(n_paths),
+                                                                        steps, levels, store)
+        if as_array:
+            return (stats, hz_stats, hz_bands, term, hz_term) if store else (stats, hz_stats, hz_bands)
+    elif drawdown:
         stats, dd_stats, term, raw = ctx.simulate_drawdown(prm, mu32, L, W, int(seed), int(path_begin), int(n_paths), store)
         mdd = mdd_from_raw(raw, compounding) if store else None
         if as_array:
@@ -202,10 +259,16 @@ def simulate_paths(mu, cov, weights, n_steps=252, n_paths=10_000, seed=0, v0=1.0
     for k, d in enumerate(out):
         if drawdown:
             d["drawdown"] = drawdown_to_dict(dd_stats[k])
+        if horizons is not None:
+            d["horizons"] = dict({"steps": steps.astype(np.int64), "levels": levels.copy(), "bands": hz_bands[:, k, :]},
+                                 **{f: hz_stats[f][:, k].astype(np.int64 if f == "n_tail" else np.float64)
+                                    for f in ("mean", "std", "var", "cvar", "min", "max", "n_tail")})
         if store:
             d["terminal"] = term[k]
             if drawdown:
                 d["max_drawdown"] = mdd[k]
+            if horizons is not None:
+                d["horizon_terminal"] = hz_term[:, k, :]
     return out[0] if single else out
 
 
@@ -222,6 +285,8 @@ def simulate_sweep(mu, cov, weights=None, n_portfolios=2500, min_weights=None, m
             np.random.seed(np_seed)
         weights = draw_weights(len(np.atleast_1d(mu)), n_portfolios, min_weights, max_weights)
     W = np.atleast_2d(np.asarray(weights, np.float64))
+    if kw.get("horizons") is not None or len(np.atleast_1d(np.asarray(kw.get("bands", ()), np.float64))):
+        raise ValueError("simulate_sweep does not take horizons or bands: call simulate_paths for the optimum")
     drawdown = bool(kw.get("drawdown", False))
     stats = simulate_paths(mu, cov, W, n_steps=n_steps, n_paths=n_paths, seed=seed, rf=rf, alpha=alpha, as_array=True, **kw)
     dd_stats = None
