@@ -85,6 +85,13 @@ with tab_sweep:                                               # app.py:655-783
     st.write({k: sim[k] for k in ("n", "mean", "std", "sharpe", "var", "cvar", "min", "max")})
     st.write({"max drawdown: mean": sim["drawdown"]["mean"], "DaR": sim["drawdown"]["dar"], "CDaR": sim["drawdown"]["cdar"],
               "worst": sim["drawdown"]["worst"]})
+    # the same weights on paths resampled from the observed rows (stationary bootstrap, SPEC.md 2.1 / 4.4), next to the normal
+    # model: hedged (option-overlay) rows keep their floor and cap here
+    boot = mcp.simulate_bootstrap(returns_df, w, n_steps=annual_factor, n_paths=n_paths, block=3.0, seed=12345,
+                                  v0=state["investment_amount"], rf=user_rf / 100.0)
+    keys = ("mean", "std", "sharpe", "var", "cvar", "min", "max")
+    st.subheader("normal model vs. bootstrap of the observed rows (mean block 3)")
+    st.write({"normal model (mean / cov)": {k: sim[k] for k in keys}, "bootstrap of the observed rows": {k: boot[k] for k in keys}})
 
 with tab_forecast:                                            # app.py:785-809
     # The reference forecasts 1, 3 and 6 periods ahead with a 95 % interval.  Here: a Monte Carlo fan from the path engine

@@ -24,11 +24,13 @@ extern "C" {
 #endif
 
 #define MCP_ABI_VERSION 4        /* 4: + mcp_simulate_drawdown, mcp_launch_paths_drawdown (additive); + mcp_simulate_horizons,
-                                    mcp_launch_paths_horizons, mcp_percentile_rank_q (additive, detected by symbol) */
+                                    mcp_launch_paths_horizons, mcp_percentile_rank_q (additive, detected by symbol);
+                                    + mcp_simulate_bootstrap[_horizons], mcp_bootstrap_pivots (additive, detected by symbol) */
 #define MCP_MAX_ASSETS 64        /* thread-per-path kernels are instantiated for N4 = 4..64 */
 #define MCP_SELECT_BINS 2048     /* radix-select digit: 11 + 11 + 10 bits */
 #define MCP_MAX_HORIZONS 64      /* mcp_simulate_horizons: horizon steps per call */
 #define MCP_MAX_LEVELS 16        /* mcp_simulate_horizons: band levels per call */
+#define MCP_MAX_BOOT_ROWS (1 << 20) /* mcp_simulate_bootstrap: observed return rows per call */
 
 enum {
     MCP_OK = 0,
@@ -181,6 +183,42 @@ int mcp_simulate_horizons(mcp_ctx *ctx, const mcp_params *prm, const float *mu, 
                           float *horizon_out,         /* NULL or host [H*K*n_paths], row h*K + k */
                           mcp_stats *hz_stats_out,    /* [H*K] */
                           double *bands_out);         /* [H*K*L], NULL iff n_levels == 0 */
+
+/* Stationary block bootstrap of observed return rows (Politis & Romano 1994; SPEC.md 2.1 / 4.4 / 5.3).  rows: [n_rows * N]
+ * row-major binary32 (returns_df.values, app.py:667, rounded to nearest by the caller), every entry finite, 1 <= n_rows <=
+ * MCP_MAX_BOOT_ROWS.  mean_block: the mean block length b in [1, +inf]: b = 1 draws every step's row independently, b = +inf
+ * walks consecutive rows (circularly) from one random start. */
+typedef struct {
+    const float *rows;      /* [n_rows * N] */
+    int32_t n_rows;
+    int32_t reserved;
+    double mean_block;
+} mcp_bootstrap;
+
+/* mcp_simulate on bootstrap paths: step t of path p uses row j_t of the table (SPEC.md 2.1, one Philox block per step on a
+ * counter stream of its own), rho_k = w_k . row, and V or S is updated as in SPEC.md 4 (SPEC.md 4.4).  All K portfolios see
+ * the same rows.  stats_out / terminal_out as mcp_simulate, with the moments pivoted at SPEC.md 5.3.  The n_assets of prm is the
+ * row width.  Argument errors (MCP_E_ARG) are found before any device is touched; MCP_FLAG_FOLD / MCP_FLAG_NATIVE_MATH:
+ * MCP_E_UNSUPPORTED.  Costs: the row table is uploaded once per device and call (4 N4 B per row); it is read from LDS when
+ * n_rows * ceil(N/4) <= 1088 (N = 16: 272 rows), else from global memory; K >= 17 runs as passes of 8 portfolios. */
+int mcp_simulate_bootstrap(mcp_ctx *ctx, const mcp_params *prm, const mcp_bootstrap *boot, const float *W, uint64_t seed,
+                           uint64_t path_begin, uint64_t n_paths, float *terminal_out, mcp_stats *stats_out);
+/* mcp_simulate_horizons on bootstrap paths: the horizons, records and bands of SPEC.md 4.3 / 5.2 over the walk of
+ * mcp_simulate_bootstrap (the value after step h is bit for bit the terminal value of the same call with n_steps = h). */
+int mcp_simulate_bootstrap_horizons(mcp_ctx *ctx, const mcp_params *prm, const mcp_bootstrap *boot, const float *W,
+                                    uint64_t seed, uint64_t path_begin, uint64_t n_paths,
+                                    int n_horizons, const int32_t *horizons,
+                                    int n_levels, const double *levels,
+                                    float *terminal_out,        /* NULL or host [K*n_paths] */
+                                    mcp_stats *stats_out,       /* [K] */
+                                    float *horizon_out,         /* NULL or host [H*K*n_paths], row h*K + k */
+                                    mcp_stats *hz_stats_out,    /* [H*K] */
+                                    double *bands_out);         /* [H*K*L], NULL iff n_levels == 0 */
+/* The shift of the moments of bootstrap paths (SPEC.md 5.3; host side, binary64): with rho_jk = sum_i W[k,i] rows[j,i],
+ * m_k = sum_j rho_jk / R and s2_k = sum_j (rho_jk - m_k)^2 / R,
+ *   simple: c_k = (1 + m_k)^T - 1 (as expm1(T log1p(m_k)), 0 if m_k <= -1)     log: c_k = expm1(T (m_k + s2_k / 2)).
+ * 0 where it is not finite. */
+int mcp_bootstrap_pivots(const mcp_params *prm, const mcp_bootstrap *boot, const float *W, double *pivots_out /* [K] */);
 
 /* The reference's own sweep (app.py:699-717) over HISTORICAL returns, loop body app.py:708-713 for P weight
  * vectors at once, binary64 like the reference.  returns: [R*N] row-major (returns_df.values, app.py:667),

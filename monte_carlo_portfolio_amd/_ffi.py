@@ -22,6 +22,7 @@ MCP_MAX_ASSETS = 64
 MCP_SELECT_BINS = 2048
 MCP_MAX_HORIZONS = 64
 MCP_MAX_LEVELS = 16
+MCP_MAX_BOOT_ROWS = 1 << 20
 MCP_COMPOUND = {"simple": 0, "log": 1}
 MCP_FLAG_NATIVE_MATH = 1
 MCP_FLAG_FOLD = 2
@@ -51,6 +52,11 @@ class McpStats(ctypes.Structure):
         ("min", ctypes.c_double), ("max", ctypes.c_double), ("sum_tail", ctypes.c_double),
         ("x_lo", ctypes.c_double), ("x_hi", ctypes.c_double),
     ]
+
+
+class McpBootstrap(ctypes.Structure):
+    """mcp_bootstrap: the observed return rows of a bootstrap call (SPEC.md 2.1)."""
+    _fields_ = [("rows", ctypes.c_void_p), ("n_rows", ctypes.c_int32), ("reserved", ctypes.c_int32), ("mean_block", ctypes.c_double)]
 
 
 STATS_DTYPE = np.dtype([
@@ -102,6 +108,10 @@ SIGNATURES = {
     "mcp_simulate_horizons": (_int, [_vp, _PP, _f32p, _f32p, _f32p, _u64, _u64, _u64, _int, _vp, _int, _vp, _vp, _vp, _vp, _vp,
                                      _vp]),
     "mcp_launch_paths_horizons": (_int, [_PP, _vp, _vp, _u64, _u64, _u64, _vp, _u64, _int, _vp, _vp, _u64, _vp, _vp, _vp]),
+    "mcp_simulate_bootstrap": (_int, [_vp, _PP, ctypes.POINTER(McpBootstrap), _f32p, _u64, _u64, _u64, _vp, _vp]),
+    "mcp_simulate_bootstrap_horizons": (_int, [_vp, _PP, ctypes.POINTER(McpBootstrap), _f32p, _u64, _u64, _u64, _int, _vp, _int, _vp,
+                                               _vp, _vp, _vp, _vp, _vp]),
+    "mcp_bootstrap_pivots": (_int, [_PP, ctypes.POINTER(McpBootstrap), _f32p, _f64p]),
     "mcp_percentile_rank_q": (_int, [_u64, ctypes.c_double, ctypes.POINTER(_u64), ctypes.POINTER(_u64),
                                      ctypes.POINTER(ctypes.c_double)]),
     "mcp_percentile_rank": (_int, [_u64, ctypes.c_double, ctypes.POINTER(_u64), ctypes.POINTER(_u64),
@@ -220,6 +230,22 @@ def pivots(prm: McpParams, mu: np.ndarray, chol: np.ndarray, W: np.ndarray) -> n
     """[K] shifts of the moments (include/mcport.h: mcp_pivots): the analytic mean of x per portfolio, pure host arithmetic."""
     out = np.zeros(W.shape[0], np.float64)
     check(lib().mcp_pivots(ctypes.byref(prm), mu, chol, W, out))
+    return out
+
+
+def make_bootstrap(rows: np.ndarray, block: float) -> McpBootstrap:
+    """mcp_bootstrap over a C-contiguous binary32 [R, N] array (the caller keeps `rows` alive for the call)."""
+    if rows.dtype != np.float32 or rows.ndim != 2 or not rows.flags.c_contiguous:
+        raise ValueError("bootstrap rows must be a C-contiguous float32 [R, N] array")
+    return McpBootstrap(rows.ctypes.data_as(ctypes.c_void_p), int(rows.shape[0]), 0, float(block))
+
+
+def bootstrap_pivots(prm: McpParams, rows: np.ndarray, W: np.ndarray, block: float = 1.0) -> np.ndarray:
+    """[K] shifts of the moments of bootstrap paths (SPEC.md 5.3; include/mcport.h, mcp_bootstrap_pivots), pure host arithmetic."""
+    out = np.zeros(W.shape[0], np.float64)
+    rows = np.ascontiguousarray(rows, np.float32)
+    bt = make_bootstrap(rows, block)
+    check(lib().mcp_bootstrap_pivots(ctypes.byref(prm), ctypes.byref(bt), W, out))
     return out
 
 

@@ -118,6 +118,16 @@ const mcp::launch_paths_hz_fn k_launch_hz[16] = {
     mcp::launch_paths_hz_nb5,  mcp::launch_paths_hz_nb6,  mcp::launch_paths_hz_nb7,  mcp::launch_paths_hz_nb8,
     mcp::launch_paths_hz_nb9,  mcp::launch_paths_hz_nb10, mcp::launch_paths_hz_nb11, mcp::launch_paths_hz_nb12,
     mcp::launch_paths_hz_nb13, mcp::launch_paths_hz_nb14, mcp::launch_paths_hz_nb15, mcp::launch_paths_hz_nb16};
+const mcp::launch_paths_bt_fn k_launch_bt[16] = {
+    mcp::launch_paths_bt_nb1,  mcp::launch_paths_bt_nb2,  mcp::launch_paths_bt_nb3,  mcp::launch_paths_bt_nb4,
+    mcp::launch_paths_bt_nb5,  mcp::launch_paths_bt_nb6,  mcp::launch_paths_bt_nb7,  mcp::launch_paths_bt_nb8,
+    mcp::launch_paths_bt_nb9,  mcp::launch_paths_bt_nb10, mcp::launch_paths_bt_nb11, mcp::launch_paths_bt_nb12,
+    mcp::launch_paths_bt_nb13, mcp::launch_paths_bt_nb14, mcp::launch_paths_bt_nb15, mcp::launch_paths_bt_nb16};
+const mcp::launch_paths_bthz_fn k_launch_bthz[16] = {
+    mcp::launch_paths_bthz_nb1,  mcp::launch_paths_bthz_nb2,  mcp::launch_paths_bthz_nb3,  mcp::launch_paths_bthz_nb4,
+    mcp::launch_paths_bthz_nb5,  mcp::launch_paths_bthz_nb6,  mcp::launch_paths_bthz_nb7,  mcp::launch_paths_bthz_nb8,
+    mcp::launch_paths_bthz_nb9,  mcp::launch_paths_bthz_nb10, mcp::launch_paths_bthz_nb11, mcp::launch_paths_bthz_nb12,
+    mcp::launch_paths_bthz_nb13, mcp::launch_paths_bthz_nb14, mcp::launch_paths_bthz_nb15, mcp::launch_paths_bthz_nb16};
 
 // SPEC.md 4.3: 1..MCP_MAX_HORIZONS strictly increasing steps in [1, n_steps]
 int check_horizons(int n_steps, int H, const int32_t* steps) {
@@ -137,6 +147,55 @@ int check_levels(int L, const double* levels) {
   for (int i = 0; i < L; i++)
     if (!(levels[i] >= 0.0 && levels[i] <= 100.0)) return fail(MCP_E_ARG, "level %d = %g outside [0, 100]", i, levels[i]);
   return MCP_OK;
+}
+
+// SPEC.md 2.1: the bootstrap request -- 1..MCP_MAX_BOOT_ROWS rows of n_assets finite binary32 values, 1 <= b <= +inf -- and
+// its restart threshold thr = b == +inf ? 0 : min(2^32, floor(fl64(2^32 / b))).
+int check_boot(const mcp_params* prm, const mcp_bootstrap* boot, uint64_t* thr) {
+  if (!boot) return fail(MCP_E_ARG, "bootstrap is NULL");
+  if (!boot->rows) return fail(MCP_E_ARG, "bootstrap rows is NULL");
+  if (boot->n_rows < 1 || boot->n_rows > MCP_MAX_BOOT_ROWS)
+    return fail(MCP_E_ARG, "n_rows=%d outside [1,%d]", boot->n_rows, MCP_MAX_BOOT_ROWS);
+  const double b = boot->mean_block;
+  if (!(b >= 1.0)) return fail(MCP_E_ARG, "mean_block=%g must be >= 1 (or +inf)", b);
+  const size_t n = (size_t)boot->n_rows * (size_t)prm->n_assets;
+  for (size_t i = 0; i < n; i++)
+    if (!std::isfinite(boot->rows[i]))
+      return fail(MCP_E_ARG, "bootstrap row %zu, asset %zu is not finite", i / (size_t)prm->n_assets, i % (size_t)prm->n_assets);
+  if (thr) {
+    const double q = 4294967296.0 / b;                 // fl64(2^32 / b); 0 for b = +inf
+    *thr = q >= 4294967296.0 ? (uint64_t)1 << 32 : (uint64_t)q;
+  }
+  return MCP_OK;
+}
+
+// SPEC.md 5.3: per portfolio the mean m and variance s2 (population) of rho_j = sum_i w_i rows[j,i] over the R rows, binary64.
+void boot_moments(int N, const mcp_bootstrap* boot, const float* W, int K, double* m_out, double* s2_out) {
+  const int R = boot->n_rows;
+  std::vector<double> rho((size_t)R);
+  for (int k = 0; k < K; k++) {
+    const float* w = W + (size_t)k * N;
+    double sum = 0.0;
+    for (int j = 0; j < R; j++) {
+      const float* r = boot->rows + (size_t)j * N;
+      double v = 0.0;
+      for (int i = 0; i < N; i++) v += (double)w[i] * (double)r[i];
+      rho[(size_t)j] = v;
+      sum += v;
+    }
+    const double m = sum / (double)R;
+    double ss = 0.0;
+    for (int j = 0; j < R; j++) { const double d = rho[(size_t)j] - m; ss += d * d; }
+    m_out[k] = m;
+    s2_out[k] = ss / (double)R;
+  }
+}
+
+// SPEC.md 5.3: the pivot at T steps from the row moments
+double boot_pivot(int compounding, int T, double m, double s2) {
+  const double c = compounding == MCP_COMPOUND_LOG ? std::expm1((double)T * (m + 0.5 * s2))
+                                                   : (m > -1.0 ? std::expm1((double)T * std::log1p(m)) : 0.0);
+  return std::isfinite(c) ? c : 0.0;
 }
 
 // Inverse-CDF coefficient table (SPEC.md section 3; DATA of the spec, generated by tools/fit_icdf_table.py): one
@@ -220,6 +279,8 @@ struct Shard {
   mcp_stats* h_hz_stats = nullptr;         // horizon calls: [1 + L][H][K tile] records of the alpha select and of every level's
   size_t h_hz_stats_cap = 0;               // select, pinned and mapped like h_stats
   void* d_hz_stats = nullptr;              // device address of h_hz_stats
+  float* d_boot = nullptr;                 // bootstrap calls: [R][N4] observed rows, zero-padded (SPEC.md 2.1)
+  size_t boot_cap = 0;
 };
 
 // RCCL entry points, resolved at run time (no link-time dependency: a single-device user never loads librccl).
@@ -280,6 +341,8 @@ struct mcp_ctx {
   size_t terminal_budget = (size_t)8 << 30;
   double* d_sweep = nullptr;         // inputs then outputs of mcp_sweep_historical (shard 0)
   size_t sweep_cap = 0;
+  float* h_boot = nullptr;           // bootstrap calls: pinned, portable [R][N4] padded rows, uploaded to every shard's d_boot
+  size_t h_boot_cap = 0;
 };
 
 
@@ -375,6 +438,17 @@ int mcp_pivots(const mcp_params* prm, const float* mu, const float* chol, const 
   return MCP_OK;
 }
 
+int mcp_bootstrap_pivots(const mcp_params* prm, const mcp_bootstrap* boot, const float* W, double* out) {
+  if (int rc = check_params(prm)) return rc;
+  if (int rc = check_boot(prm, boot, nullptr)) return rc;
+  if (!W || !out) return fail(MCP_E_ARG, "NULL pointer");
+  const int K = prm->n_portfolios;
+  std::vector<double> m((size_t)K), s2((size_t)K);
+  boot_moments(prm->n_assets, boot, W, K, m.data(), s2.data());
+  for (int k = 0; k < K; k++) out[k] = boot_pivot(prm->compounding, prm->n_steps, m[(size_t)k], s2[(size_t)k]);
+  return MCP_OK;
+}
+
 }  // extern "C"
 
 // The horizon output of a launch (SPEC.md 4.3): n horizon steps (host), the [n][K][stride] array.
@@ -385,6 +459,13 @@ struct HzOut {
   uint64_t stride = 0;
 };
 
+// The row table of a bootstrap launch (SPEC.md 2.1): the device copy [n_rows][N4], zero-padded, and the restart threshold.
+struct BootIn {
+  const float* d_rows = nullptr;
+  uint32_t n_rows = 0;
+  uint64_t thr = 0;
+};
+
 // mcp_launch_paths (d_mdd and hz NULL), mcp_launch_paths_drawdown and mcp_launch_paths_horizons.  A drawdown or horizon launch
 // always runs mc_paths_dd_kernel / mc_paths_hz_kernel, K >= 17 as passes of the 8-portfolio kernel: the MFMA sweep kernels
 // track neither the path's peak nor its intermediate values.  Its moment partials keep the layout mcp_moment_slots(K, n) gives
@@ -392,7 +473,7 @@ struct HzOut {
 // the path kernel's workgroups overwrite the first path_grid(n) of them.
 static int launch_paths_impl(const mcp_params* prm, const float* d_packed, const double* d_pivot, uint64_t seed, uint64_t path_begin,
                              uint64_t n_paths, float* d_terminal, uint64_t stride, float* d_mdd, uint64_t mdd_stride, void* d_partials,
-                             void* d_hist, void* stream, const HzOut* hz = nullptr) {
+                             void* d_hist, void* stream, const HzOut* hz = nullptr, const BootIn* boot = nullptr) {
   const bool dd = d_mdd != nullptr;
   if (int rc = check_params(prm)) return rc;
   if (!d_packed || !d_terminal) return fail(MCP_E_ARG, "NULL device pointer");
@@ -409,12 +490,18 @@ static int launch_paths_impl(const mcp_params* prm, const float* d_packed, const
     if (hz->stride < n_paths) return fail(MCP_E_ARG, "horizon_stride %llu < n_paths %llu", (unsigned long long)hz->stride,
                                           (unsigned long long)n_paths);
   }
+  if (boot) {
+    if (dd) return fail(MCP_E_UNSUPPORTED, "the drawdown is not tracked on bootstrap paths");
+    if (prm->flags & (MCP_FLAG_FOLD | MCP_FLAG_NATIVE_MATH))
+      return fail(MCP_E_UNSUPPORTED, "bootstrap paths draw no normals (no MCP_FLAG_FOLD / MCP_FLAG_NATIVE_MATH)");
+    if (!boot->d_rows || boot->n_rows < 1 || boot->n_rows > (uint32_t)MCP_MAX_BOOT_ROWS) return fail(MCP_E_ARG, "bad bootstrap table");
+  }
   if ((d_partials == nullptr) != (d_hist == nullptr)) return fail(MCP_E_ARG, "d_partials and d_hist go together (both or neither)");
   if (n_paths < 1) return fail(MCP_E_ARG, "n_paths must be >= 1");
   if (stride < n_paths) return fail(MCP_E_ARG, "terminal_stride %llu < n_paths %llu",
                                     (unsigned long long)stride, (unsigned long long)n_paths);
   const int grid = mcp::path_grid(n_paths);
-  if ((uint64_t)prm->n_steps * (uint64_t)((prm->n_assets + 3) / 4) > 0xFFFFFFFFull)
+  if (!boot && (uint64_t)prm->n_steps * (uint64_t)((prm->n_assets + 3) / 4) > 0xFFFFFFFFull)
     return fail(MCP_E_UNSUPPORTED, "n_steps * ceil(N/4) exceeds the 32-bit Philox block counter");
   const int nb = (prm->n_assets + 3) / 4;
   const int K = prm->n_portfolios;
@@ -433,14 +520,14 @@ static int launch_paths_impl(const mcp_params* prm, const float* d_packed, const
   DeviceGuard guard(dev);                 // the stream may belong to another device than the thread's current one
   if (guard.err != hipSuccess) return fail(MCP_E_HIP, "hipSetDevice(%d): %s", dev, hipGetErrorString(guard.err));
   if (int rc = device_tables(dev, (hipStream_t)stream, &tables)) return rc;
-  const bool sweep = !dd && !hz && uses_sweep(K);
+  const bool sweep = !dd && !hz && !boot && uses_sweep(K);
   a.tables = tables;
   a.packed = d_packed;
   a.terminal = d_terminal;
   a.pivot = d_pivot;
   a.partials = (mcp::MomentPartial*)d_partials;
   a.hist = sweep ? nullptr : (unsigned long long*)d_hist;     // the sweep kernels leave digit 0 to hist(0) below
-  a.slots = (dd || hz) ? mcp_moment_slots(K, n_paths) : mcp::moment_slots(sweep, n_paths);
+  a.slots = (dd || hz || boot) ? mcp_moment_slots(K, n_paths) : mcp::moment_slots(sweep, n_paths);
   a.v0d = (double)(float)prm->v0;
   a.inv_v0d = 1.0 / a.v0d;
   { int e = 0; a.v0_pow2 = std::frexp(a.v0d, &e) == 0.5; }
@@ -472,9 +559,41 @@ static int launch_paths_impl(const mcp_params* prm, const float* d_packed, const
     }
     return MCP_OK;
   }
-  if ((dd || hz) && d_partials && a.slots > (uint64_t)grid)
+  if ((dd || hz || boot) && d_partials && a.slots > (uint64_t)grid)
     HIP_TRY(mcp::launch_pass0(*prm, K, d_terminal, stride, 0, nullptr, a.slots, (mcp::MomentPartial*)d_partials,
                               (unsigned long long*)d_hist, (hipStream_t)stream));
+  if (boot) {
+    mcp::BootArgs bt;
+    bt.rows = (const float4*)boot->d_rows;
+    bt.thr = boot->thr;
+    bt.n_rows = boot->n_rows;
+    bt.pad = 0;
+    const bool lds = mcp::boot_fits_lds(boot->n_rows, nb);
+    if (hz) {
+      mcp::PathArgsBTHZ ab;
+      static_cast<mcp::PathArgs&>(ab) = a;
+      ab.hz = hz->d_out;
+      ab.hz_stride = hz->stride;
+      ab.n_horizons = hz->n;
+      for (int i = 0; i < MCP_MAX_HORIZONS; i++) ab.steps[i] = i < hz->n ? hz->steps[i] : 0;
+      ab.bt = bt;
+      for (int kb = 0; kb < K; kb += kt) {
+        ab.k_begin = kb;
+        hipError_t e = k_launch_bthz[nb - 1](variant, lds, ab, grid, (hipStream_t)stream);
+        if (e != hipSuccess) return fail(MCP_E_HIP, "mc_paths_boot_hz_kernel launch: %s", hipGetErrorString(e));
+      }
+    } else {
+      mcp::PathArgsBT ab;
+      static_cast<mcp::PathArgs&>(ab) = a;
+      ab.bt = bt;
+      for (int kb = 0; kb < K; kb += kt) {
+        ab.k_begin = kb;
+        hipError_t e = k_launch_bt[nb - 1](variant, lds, ab, grid, (hipStream_t)stream);
+        if (e != hipSuccess) return fail(MCP_E_HIP, "mc_paths_boot_kernel launch: %s", hipGetErrorString(e));
+      }
+    }
+    return MCP_OK;
+  }
   if (hz) {
     mcp::PathArgsHZ ah;
     static_cast<mcp::PathArgs&>(ah) = a;
@@ -709,6 +828,7 @@ static void free_shard(Shard& sh) {
   if (sh.d_hz_pivot) (void)hipFree(sh.d_hz_pivot);
   if (sh.h_hz_pivot) (void)hipHostFree(sh.h_hz_pivot);
   if (sh.h_hz_stats) (void)hipHostFree(sh.h_hz_stats);
+  if (sh.d_boot) (void)hipFree(sh.d_boot);
 }
 
 int mcp_ctx_create_multi(const int* devices, int ndev, mcp_ctx** out) {
@@ -817,6 +937,7 @@ void mcp_ctx_destroy(mcp_ctx* c) {
       if (comm) (void)c->rccl->CommDestroy(comm);
   for (Shard& sh : c->sh) free_shard(sh);
   if (c->d_sweep && !c->sh.empty()) { (void)hipSetDevice(c->sh[0].device); (void)hipFree(c->d_sweep); }
+  if (c->h_boot) (void)hipHostFree(c->h_boot);
   if (have_prev) (void)hipSetDevice(prev_dev);
   delete c;
 }
@@ -973,6 +1094,14 @@ struct HzReq {
   double* bands_out = nullptr;       // [H*K*L]
 };
 
+// The bootstrap request of mcp_simulate_bootstrap[_horizons] (SPEC.md 2.1 / 5.3): the caller's rows (for the pivots; the padded
+// copy is already in every working shard's d_boot when a tile runs), R and the restart threshold.
+struct BootReq {
+  const mcp_bootstrap* boot = nullptr;
+  uint32_t n_rows = 0;
+  uint64_t thr = 0;
+};
+
 // One tile: every active shard simulates its (portfolios x paths) block -- the kernels' epilogue leaves the moment partials
 // and the digit-0 histogram -- and the rest of the statistics pipeline runs (run_select).  `dd`: the path kernels also leave
 // the drawdown array, and after the terminal values a pass 0 over it and a second run_select reduce it to dd_stats_out.
@@ -980,7 +1109,7 @@ struct HzReq {
 // at alpha (pass 0 + run_select) and once per level at that level's rank, whose records contribute only their `var`.
 int run_tile(mcp_ctx* c, const mcp_params* prm, const float* mu, const float* chol, const float* W, uint64_t seed,
              uint64_t path_begin, uint64_t n_total, const std::vector<Job>& jobs, bool exchange, float* terminal_out,
-             mcp_stats* stats_out, bool dd, float* mdd_out, mcp_stats* dd_stats_out, const HzReq* hz) {
+             mcp_stats* stats_out, bool dd, float* mdd_out, mcp_stats* dd_stats_out, const HzReq* hz, const BootReq* boot) {
   const size_t S = c->sh.size();
   uint64_t lo, hi;
   double gamma;
@@ -1034,6 +1163,17 @@ int run_tile(mcp_ctx* c, const mcp_params* prm, const float* mu, const float* ch
   //     (packed once; the pivot is a function of the inputs, identical on every shard by construction).
   const float* shared_packed = nullptr;
   const double* shared_pivot = nullptr;
+  const double* shared_hz_pivot = nullptr;
+  // bootstrap: no drift and no Cholesky factor in the packed block (only W is read), the pivots of SPEC.md 5.3 from the row
+  // moments (computed once per tile)
+  std::vector<float> zmu, zchol;
+  std::vector<double> bm, bs2;
+  if (boot) {
+    zmu.assign((size_t)prm->n_assets, 0.0f);
+    zchol.assign((size_t)prm->n_assets * prm->n_assets, 0.0f);
+    mu = zmu.data();
+    chol = zchol.data();
+  }
   for (size_t s = 0; s < S; s++) {
     const Job& j = jobs[s];
     if (!j.active) continue;
@@ -1042,33 +1182,55 @@ int run_tile(mcp_ctx* c, const mcp_params* prm, const float* mu, const float* ch
     const size_t plen = mcp_packed_len(prm->n_assets, j.kt);
     const float* src = sh.h_packed;
     const double* psrc = sh.h_pivot;
+    const double* hpsrc = sh.h_hz_pivot;
     if (exchange && shared_packed) {
       src = shared_packed;                                   // same portfolios on every shard: pinned + portable
       psrc = shared_pivot;
+      hpsrc = shared_hz_pivot;
     } else {
       if ((rc = mcp_pack_params(prm->n_assets, j.kt, mu, chol, W + (size_t)j.k0 * prm->n_assets, sh.h_packed, plen))) return rc;
-      if ((rc = mcp_pivots(&tp[s], mu, chol, W + (size_t)j.k0 * prm->n_assets, sh.h_pivot))) return rc;
-      if (exchange) { shared_packed = sh.h_packed; shared_pivot = sh.h_pivot; }
+      if (boot) {
+        bm.resize((size_t)j.kt);
+        bs2.resize((size_t)j.kt);
+        boot_moments(prm->n_assets, boot->boot, W + (size_t)j.k0 * prm->n_assets, j.kt, bm.data(), bs2.data());
+        for (int k = 0; k < j.kt; k++) sh.h_pivot[k] = boot_pivot(prm->compounding, prm->n_steps, bm[(size_t)k], bs2[(size_t)k]);
+      } else if ((rc = mcp_pivots(&tp[s], mu, chol, W + (size_t)j.k0 * prm->n_assets, sh.h_pivot))) {
+        return rc;
+      }
+      if (hz) {                                              // SPEC.md 5.2 / 5.3: row h*kt + k is pivoted with n_steps = h
+        mcp_params ph = tp[s];
+        for (int h = 0; h < hz->H; h++) {
+          ph.n_steps = hz->steps[h];
+          double* hp = sh.h_hz_pivot + (size_t)h * j.kt;
+          if (boot) {
+            for (int k = 0; k < j.kt; k++) hp[k] = boot_pivot(prm->compounding, ph.n_steps, bm[(size_t)k], bs2[(size_t)k]);
+          } else if ((rc = mcp_pivots(&ph, mu, chol, W + (size_t)j.k0 * prm->n_assets, hp))) {
+            return rc;
+          }
+        }
+      }
+      if (exchange) { shared_packed = sh.h_packed; shared_pivot = sh.h_pivot; shared_hz_pivot = sh.h_hz_pivot; }
     }
     HIP_TRY(hipMemcpyAsync(sh.d_packed, src, plen * sizeof(float), hipMemcpyHostToDevice, sh.stream));
     HIP_TRY(hipMemcpyAsync(sh.ws[MCP_WS_PIVOT], psrc, (size_t)j.kt * sizeof(double), hipMemcpyHostToDevice, sh.stream));
     HzOut hzo;
-    if (hz) {                                                // SPEC.md 5.2: row h*kt + k is pivoted with n_steps = h
-      mcp_params ph = tp[s];
-      for (int h = 0; h < hz->H; h++) {
-        ph.n_steps = hz->steps[h];
-        if ((rc = mcp_pivots(&ph, mu, chol, W + (size_t)j.k0 * prm->n_assets, sh.h_hz_pivot + (size_t)h * j.kt))) return rc;
-      }
-      HIP_TRY(hipMemcpyAsync(sh.d_hz_pivot, sh.h_hz_pivot, (size_t)hz->H * j.kt * sizeof(double), hipMemcpyHostToDevice, sh.stream));
+    if (hz) {
+      HIP_TRY(hipMemcpyAsync(sh.d_hz_pivot, hpsrc, (size_t)hz->H * j.kt * sizeof(double), hipMemcpyHostToDevice, sh.stream));
       hzo.n = hz->H;
       hzo.steps = hz->steps;
       hzo.d_out = sh.d_hz;
       hzo.stride = j.pn;
     }
+    BootIn bti;
+    if (boot) {
+      bti.d_rows = sh.d_boot;
+      bti.n_rows = boot->n_rows;
+      bti.thr = boot->thr;
+    }
     if (j.pn) {
       if ((rc = launch_paths_impl(&tp[s], sh.d_packed, (const double*)sh.ws[MCP_WS_PIVOT], seed, path_begin + j.p0, j.pn, sh.d_terminal,
                                   j.pn, dd ? sh.d_mdd : nullptr, j.pn, sh.ws[MCP_WS_PARTIALS], sh.ws[MCP_WS_HIST], sh.stream,
-                                  hz ? &hzo : nullptr))) return rc;
+                                  hz ? &hzo : nullptr, boot ? &bti : nullptr))) return rc;
     } else {
       // a shard without paths (fewer paths than shards): empty moment partials, nothing in the histogram
       if ((rc = mcp_launch_pass0(&tp[s], sh.d_terminal, 1, 0, (const double*)sh.ws[MCP_WS_PIVOT], sh.ws[MCP_WS_PARTIALS],
@@ -1166,10 +1328,10 @@ int tile_portfolios(size_t budget, uint64_t n_paths, int K, size_t bytes_per_pat
 
 int simulate_impl(mcp_ctx* c, const mcp_params* prm, const float* mu, const float* chol, const float* W, uint64_t seed,
                   uint64_t path_begin, uint64_t n_paths, float* terminal_out, mcp_stats* stats_out, bool dd, float* mdd_out,
-                  mcp_stats* dd_stats_out, const HzReq* hz = nullptr) {
+                  mcp_stats* dd_stats_out, const HzReq* hz = nullptr, const BootReq* boot = nullptr) {
   if (!c) return fail(MCP_E_ARG, "ctx is NULL");
   if (int rc = check_params(prm)) return rc;
-  if (!mu || !chol || !W || !stats_out || (dd && !dd_stats_out)) return fail(MCP_E_ARG, "NULL pointer");
+  if ((!boot && (!mu || !chol)) || !W || !stats_out || (dd && !dd_stats_out)) return fail(MCP_E_ARG, "NULL pointer");
   if (n_paths < 1) return fail(MCP_E_ARG, "n_paths must be >= 1");
   if (dd && (prm->flags & (MCP_FLAG_FOLD | MCP_FLAG_NATIVE_MATH)))
     return fail(MCP_E_UNSUPPORTED, "the drawdown runs on the spec's normals and the unfolded recurrence (no MCP_FLAG_FOLD / MCP_FLAG_NATIVE_MATH)");
@@ -1183,7 +1345,29 @@ int simulate_impl(mcp_ctx* c, const mcp_params* prm, const float* mu, const floa
   (void)hipGetDevice(&prev_dev);
   int rc = MCP_OK;
   std::vector<Job> jobs(S);
-  if (S > 1 && (prm->flags & MCP_FLAG_SHARD_PORTFOLIOS)) {
+  const bool by_portfolio = S > 1 && (prm->flags & MCP_FLAG_SHARD_PORTFOLIOS);
+  if (boot) {
+    // SPEC.md 2.1: the rows, zero-padded to N4, into one pinned staging copy and from there once into the d_boot of every shard
+    // that walks paths in this call (the tiles of the call share it)
+    const int N = prm->n_assets, n4 = n4_of(N);
+    const size_t R = boot->n_rows, bytes = R * (size_t)n4 * sizeof(float);
+    rc = grow_host((void**)&c->h_boot, &c->h_boot_cap, bytes);
+    if (rc == MCP_OK) {
+      memset(c->h_boot, 0, bytes);
+      for (size_t j = 0; j < R; j++) memcpy(c->h_boot + j * n4, boot->boot->rows + j * N, (size_t)N * sizeof(float));
+    }
+    for (size_t s = 0; s < S && rc == MCP_OK; s++) {
+      const bool works = by_portfolio ? (int64_t)K * (int64_t)(s + 1) / (int64_t)S > (int64_t)K * (int64_t)s / (int64_t)S
+                                      : n_paths / S + (s < n_paths % S ? 1 : 0) > 0;
+      if (!works) continue;
+      Shard& sh = c->sh[s];
+      if (hipSetDevice(sh.device) != hipSuccess) { rc = fail(MCP_E_HIP, "hipSetDevice(%d)", sh.device); break; }
+      if ((rc = grow_dev((void**)&sh.d_boot, &sh.boot_cap, bytes))) break;
+      const hipError_t e = hipMemcpyAsync(sh.d_boot, c->h_boot, bytes, hipMemcpyHostToDevice, sh.stream);
+      if (e != hipSuccess) rc = fail(MCP_E_HIP, "bootstrap rows upload: %s", hipGetErrorString(e));
+    }
+  }
+  if (rc == MCP_OK && by_portfolio) {
     // every shard walks all paths for its slice of W; slices are tiled independently; no exchange
     std::vector<int> kb(S + 1);
     for (size_t s = 0; s <= S; s++) kb[s] = (int)((int64_t)K * (int64_t)s / (int64_t)S);
@@ -1200,9 +1384,10 @@ int simulate_impl(mcp_ctx* c, const mcp_params* prm, const float* mu, const floa
         more = true;
       }
       if (more)
-        rc = run_tile(c, prm, mu, chol, W, seed, path_begin, n_paths, jobs, false, terminal_out, stats_out, dd, mdd_out, dd_stats_out, hz);
+        rc = run_tile(c, prm, mu, chol, W, seed, path_begin, n_paths, jobs, false, terminal_out, stats_out, dd, mdd_out, dd_stats_out, hz,
+                      boot);
     }
-  } else {
+  } else if (rc == MCP_OK) {
     // the path range is sharded; all shards see the same tile of portfolios
     uint64_t pn_max = 0;
     for (size_t s = 0; s < S; s++) {
@@ -1216,7 +1401,7 @@ int simulate_impl(mcp_ctx* c, const mcp_params* prm, const float* mu, const floa
     for (int k0 = 0; k0 < K && rc == MCP_OK; k0 += kt_max) {
       for (size_t s = 0; s < S; s++) { jobs[s].k0 = k0; jobs[s].kt = std::min(kt_max, K - k0); }
       rc = run_tile(c, prm, mu, chol, W, seed, path_begin, n_paths, jobs, S > 1 || c->exchange_always, terminal_out, stats_out, dd,
-                    mdd_out, dd_stats_out, hz);
+                    mdd_out, dd_stats_out, hz, boot);
     }
   }
   if (rc != MCP_OK) {
@@ -1270,6 +1455,50 @@ int mcp_simulate_horizons(mcp_ctx* c, const mcp_params* prm, const float* mu, co
   hz.stats_out = hz_stats_out;
   hz.bands_out = bands_out;
   return simulate_impl(c, prm, mu, chol, W, seed, path_begin, n_paths, terminal_out, stats_out, false, nullptr, nullptr, &hz);
+}
+
+int mcp_simulate_bootstrap(mcp_ctx* c, const mcp_params* prm, const mcp_bootstrap* boot, const float* W, uint64_t seed,
+                           uint64_t path_begin, uint64_t n_paths, float* terminal_out, mcp_stats* stats_out) {
+  // the arguments first, so that each error is found (and named) before any device is touched, a NULL ctx included
+  if (int rc = check_params(prm)) return rc;
+  BootReq br;
+  if (int rc = check_boot(prm, boot, &br.thr)) return rc;
+  if (prm->flags & (MCP_FLAG_FOLD | MCP_FLAG_NATIVE_MATH))
+    return fail(MCP_E_UNSUPPORTED, "bootstrap paths draw no normals (no MCP_FLAG_FOLD / MCP_FLAG_NATIVE_MATH)");
+  if (!W || !stats_out) return fail(MCP_E_ARG, "NULL pointer");
+  if (n_paths < 1) return fail(MCP_E_ARG, "n_paths must be >= 1");
+  br.boot = boot;
+  br.n_rows = (uint32_t)boot->n_rows;
+  return simulate_impl(c, prm, nullptr, nullptr, W, seed, path_begin, n_paths, terminal_out, stats_out, false, nullptr, nullptr, nullptr,
+                       &br);
+}
+
+int mcp_simulate_bootstrap_horizons(mcp_ctx* c, const mcp_params* prm, const mcp_bootstrap* boot, const float* W, uint64_t seed,
+                                    uint64_t path_begin, uint64_t n_paths, int n_horizons, const int32_t* horizons, int n_levels,
+                                    const double* levels, float* terminal_out, mcp_stats* stats_out, float* horizon_out,
+                                    mcp_stats* hz_stats_out, double* bands_out) {
+  if (int rc = check_params(prm)) return rc;
+  BootReq br;
+  if (int rc = check_boot(prm, boot, &br.thr)) return rc;
+  if (prm->flags & (MCP_FLAG_FOLD | MCP_FLAG_NATIVE_MATH))
+    return fail(MCP_E_UNSUPPORTED, "bootstrap paths draw no normals (no MCP_FLAG_FOLD / MCP_FLAG_NATIVE_MATH)");
+  if (int rc = check_horizons(prm->n_steps, n_horizons, horizons)) return rc;
+  if (int rc = check_levels(n_levels, levels)) return rc;
+  if (!W || !stats_out || !hz_stats_out) return fail(MCP_E_ARG, "NULL pointer");
+  if ((bands_out == nullptr) != (n_levels == 0)) return fail(MCP_E_ARG, "bands_out must be NULL exactly when n_levels == 0");
+  if (n_paths < 1) return fail(MCP_E_ARG, "n_paths must be >= 1");
+  br.boot = boot;
+  br.n_rows = (uint32_t)boot->n_rows;
+  HzReq hz;
+  hz.H = n_horizons;
+  hz.L = n_levels;
+  hz.steps = horizons;
+  hz.levels = levels;
+  hz.out = horizon_out;
+  hz.stats_out = hz_stats_out;
+  hz.bands_out = bands_out;
+  return simulate_impl(c, prm, nullptr, nullptr, W, seed, path_begin, n_paths, terminal_out, stats_out, false, nullptr, nullptr, &hz,
+                       &br);
 }
 
 int mcp_sweep_historical(mcp_ctx* c, int N, int R, int P, const double* returns, const double* mean, const double* cov,

@@ -32,6 +32,9 @@
 #ifndef MCP_EXP_VKEYS
 #define MCP_EXP_VKEYS 1
 #endif
+#ifndef MCP_EXP_BOOT_SWIZZLE  // 1: the bootstrap's LDS row table is XOR-swizzled (BootSwizzle); 0: plain layout (lab builds)
+#define MCP_EXP_BOOT_SWIZZLE 1
+#endif
 #ifndef MCP_EXP_LDSPAR      // 1: drift from LDS (default); 2: drift and (one portfolio) weights from LDS; 0: both from SGPRs
 #define MCP_EXP_LDSPAR 1
 #endif
@@ -79,6 +82,36 @@ struct PathArgsHZ : PathArgs {
   uint64_t hz_stride;
   int32_t n_horizons;                 // H in [1, MCP_MAX_HORIZONS]
   int32_t steps[MCP_MAX_HORIZONS];    // strictly increasing, in [1, n_steps]
+};
+
+// The observed return rows of the bootstrap kernels (SPEC.md 2.1 / 4.4).
+struct BootArgs {
+  const float4* __restrict__ rows;    // [R][NB] float4: row j zero-padded to N4 floats (device copy, not swizzled)
+  uint64_t thr;                       // restart when (uint64)x1 < thr; in [0, 2^32] (SPEC.md 2.1)
+  uint32_t n_rows;                    // R in [1, MCP_MAX_BOOT_ROWS]
+  uint32_t pad;
+};
+// Arguments of mc_paths_boot_kernel / mc_paths_boot_hz_kernel: PathArgs (PathArgsHZ) first, as for the drawdown kernel.
+struct PathArgsBT : PathArgs { BootArgs bt; };
+struct PathArgsBTHZ : PathArgsHZ { BootArgs bt; };
+__device__ __forceinline__ BootArgs boot_args(const PathArgs&) { return BootArgs{}; }
+__device__ __forceinline__ BootArgs boot_args(const PathArgsBT& a) { return a.bt; }
+__device__ __forceinline__ BootArgs boot_args(const PathArgsBTHZ& a) { return a.bt; }
+
+// The LDS copy of the row table takes the slot of the inverse-CDF table (ICDF_LDS_ENTRIES float4: the bootstrap needs neither
+// that table nor the drift copy in its padding): R rows of NB float4 fit when R * NB <= ICDF_LDS_ENTRIES (N = 16: 272 rows).
+__host__ __device__ constexpr bool boot_fits_lds(uint64_t n_rows, int nb) { return n_rows * (uint64_t)nb <= (uint64_t)ICDF_LDS_ENTRIES; }
+// LDS banking of the gather (ds_read_b128: 16 slots of 16 B, bank slot = float4 index mod 16).  Row j starts at slot
+// (j NB) mod 16, a multiple of G = the largest power of two dividing NB, so a fixed chunk q of random rows would fall on only
+// 16 / G slots.  Chunk q of row j is stored at j NB + (q ^ s(j)), s(j) = (j >> log2(16 / G)) & (G - 1): the bits of j that
+// the row start does not already spread, XORed into the chunk index inside its aligned group of G (which stays inside the
+// row since G divides NB).  A fixed q then spreads over all 16 slots.  No padding: the slot would outgrow the table's.
+template <int NB>
+struct BootSwizzle {
+  static constexpr int G = (NB & -NB) > 16 ? 16 : (NB & -NB);
+  static constexpr int SHIFT = G == 16 ? 0 : G == 8 ? 1 : G == 4 ? 2 : G == 2 ? 3 : 4;
+  static constexpr uint32_t MASK = (uint32_t)G - 1u;
+  __device__ static __forceinline__ uint32_t of(uint32_t j) { return MCP_EXP_BOOT_SWIZZLE ? (j >> SHIFT) & MASK : 0u; }
 };
 
 __device__ __forceinline__ double wave_sum(double v) {
@@ -139,13 +172,14 @@ constexpr int PATH_BLOCK = 256;
 // LOGC: compounding mode at compile time (as a run-time flag the compiler if-converts the step into fma + add + select).
 // DD: also track the running peak and the max drawdown of every (path, portfolio) through the step loop (SPEC.md 4.2) and
 // store q (simple: min V_t/P_t) or d (log: min S_t - P_t) next to V_T.  HZ: also store V_h at the horizons (SPEC.md 4.3).
-// All three kernels are the body in mcp_paths_body.inc.
+// BOOT: r is row j_t of the observed returns (SPEC.md 2.1 / 4.4) instead of mu + L z; BLDS: that table is read from LDS.
+// All five kernels are the body in mcp_paths_body.inc.
 #define MCP_PATHS_BOUNDS(NB, KT, PPT) \
   __launch_bounds__(PATH_BLOCK, (NB <= 4 && KT == 1 && PPT == 1) ? MCP_MIN_WAVES : ((KT == 1 && PPT == 1) ? MCP_MIN_WAVES_BIG : 1))
 
 template <int NB, int KT, int PPT, bool NATIVE, bool FOLD = false, bool LOGC = false>
 __global__ void MCP_PATHS_BOUNDS(NB, KT, PPT) mc_paths_kernel(const PathArgs a) {
-  constexpr bool DD = false, HZ = false;
+  constexpr bool DD = false, HZ = false, BOOT = false, BLDS = false;
 #include "mcp_paths_body.inc"
 }
 
@@ -153,7 +187,7 @@ __global__ void MCP_PATHS_BOUNDS(NB, KT, PPT) mc_paths_kernel(const PathArgs a) 
 // array: appended to PathArgs itself they would move the hidden kernel arguments (grid size) of every plain kernel.
 template <int NB, int KT, int PPT, bool LOGC>
 __global__ void MCP_PATHS_BOUNDS(NB, KT, PPT) mc_paths_dd_kernel(const PathArgsDD a) {
-  constexpr bool DD = true, HZ = false, NATIVE = false, FOLD = false;
+  constexpr bool DD = true, HZ = false, NATIVE = false, FOLD = false, BOOT = false, BLDS = false;
 #include "mcp_paths_body.inc"
 }
 
@@ -161,7 +195,22 @@ __global__ void MCP_PATHS_BOUNDS(NB, KT, PPT) mc_paths_dd_kernel(const PathArgsD
 // at the horizons, V_h stored after each; V_T and the fused epilogue as in mc_paths_kernel.
 template <int NB, int KT, int PPT, bool LOGC>
 __global__ void MCP_PATHS_BOUNDS(NB, KT, PPT) mc_paths_hz_kernel(const PathArgsHZ a) {
-  constexpr bool DD = false, HZ = true, NATIVE = false, FOLD = false;
+  constexpr bool DD = false, HZ = true, NATIVE = false, FOLD = false, BOOT = false, BLDS = false;
+#include "mcp_paths_body.inc"
+}
+
+// The bootstrap kernel (SPEC.md 2.1 / 4.4): the walk of mc_paths_kernel on resampled rows of observed returns, one Philox
+// block per path-step for the row index, no normals, no Cholesky GEMV.  V_T and the fused epilogue as in mc_paths_kernel.
+template <int NB, int KT, int PPT, bool LOGC, bool BLDS>
+__global__ void MCP_PATHS_BOUNDS(NB, KT, PPT) mc_paths_boot_kernel(const PathArgsBT a) {
+  constexpr bool DD = false, HZ = false, NATIVE = false, FOLD = false, BOOT = true;
+#include "mcp_paths_body.inc"
+}
+
+// The bootstrap kernel with the horizons of SPEC.md 4.3 (the segmented walk of mc_paths_hz_kernel).
+template <int NB, int KT, int PPT, bool LOGC, bool BLDS>
+__global__ void MCP_PATHS_BOUNDS(NB, KT, PPT) mc_paths_boot_hz_kernel(const PathArgsBTHZ a) {
+  constexpr bool DD = false, HZ = true, NATIVE = false, FOLD = false, BOOT = true;
 #include "mcp_paths_body.inc"
 }
 #undef MCP_PATHS_BOUNDS

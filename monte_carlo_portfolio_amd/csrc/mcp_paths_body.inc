@@ -1,8 +1,9 @@
 // mcp_paths_body.inc -- the body of the path kernels of mcp_paths.h, included textually by mc_paths_kernel (DD = HZ = false),
-// mc_paths_dd_kernel (DD = true) and mc_paths_hz_kernel (HZ = true); the step itself is mcp_paths_step.inc.  As a shared __device__ function the plain kernel's registers came out allocated differently;
+// mc_paths_dd_kernel (DD = true), mc_paths_hz_kernel (HZ = true) and the bootstrap kernels mc_paths_boot_kernel (BOOT = true)
+// and mc_paths_boot_hz_kernel (BOOT = HZ = true); the step itself is mcp_paths_step.inc.  As a shared __device__ function the plain kernel's registers came out allocated differently;
 // included, the DD = false kernel compiles to the same instructions as before the drawdown existed.  In scope: the template
-// parameters NB, KT, PPT, NATIVE, FOLD, LOGC, DD, HZ and the kernel argument `a` (PathArgs, or PathArgsDD / PathArgsHZ which
-// start with one).  Without HZ the walk is the one loop it always was, so the plain and drawdown kernels keep their code.
+// parameters NB, KT, PPT, NATIVE, FOLD, LOGC, DD, HZ, BOOT, BLDS and the kernel argument `a` (PathArgs, or PathArgsDD /
+// PathArgsHZ / PathArgsBT / PathArgsBTHZ which start with one).  Without HZ the walk is the one loop it always was, so the plain and drawdown kernels keep their code.
   constexpr int N4 = 4 * NB;
   // wave-uniform parameters through the constant address space -> s_load_dword* into SGPRs
   typedef const __attribute__((address_space(4))) float* cfloat_p;
@@ -12,14 +13,24 @@
   const int kt = min(KT, a.n_portfolios - a.k_begin);   // live portfolios in this pass (uniform)
   // inverse-CDF table: 16.5 KiB of LDS per block, filled once from the device-resident copy
   __shared__ float4 s_tab[ICDF_LDS_ENTRIES];
-  if constexpr (!NATIVE) {
+  if constexpr (!NATIVE && !BOOT) {
     for (int i = threadIdx.x; i < ICDF_ENTRIES; i += PATH_BLOCK) s_tab[ICDF_PAD + i] = a.tables[i];
+  }
+  // BOOT: the observed rows (SPEC.md 2.1); BLDS: copied into the table's slot, chunk q of row j at j NB + (q ^ s(j))
+  // (BootSwizzle), with ordinary vector LDS writes
+  BootArgs bt{};
+  if constexpr (BOOT) bt = boot_args(a);
+  if constexpr (BOOT && BLDS) {
+    for (uint32_t i = threadIdx.x; i < bt.n_rows * (uint32_t)NB; i += PATH_BLOCK) {
+      const uint32_t j = i / NB, q = i % NB;
+      s_tab[j * NB + (q ^ BootSwizzle<NB>::of(j))] = bt.rows[i];
+    }
   }
   // The 512 B of padding in front of the table hold the drift (and, for one portfolio, the weights): read from LDS they
   // land in VGPRs without a VALU instruction (a v_mov from an SGPR costs an issue slot, an SGPR operand halves the
   // issue rate of the weight-dot FMAs).
-  constexpr bool LDS_MU = MCP_EXP_LDSPAR >= 1 && !NATIVE && !FOLD;
-  constexpr bool LDS_W = MCP_EXP_LDSPAR >= 2 && !NATIVE && !FOLD && KT == 1;
+  constexpr bool LDS_MU = MCP_EXP_LDSPAR >= 1 && !NATIVE && !FOLD && !BOOT;
+  constexpr bool LDS_W = MCP_EXP_LDSPAR >= 2 && !NATIVE && !FOLD && !BOOT && KT == 1;
   float* const s_par0 = (float*)&s_tab[0];
   if constexpr (LDS_MU) {
     if (threadIdx.x < N4) { s_par0[threadIdx.x] = mu[threadIdx.x]; if (LDS_W) s_par0[N4 + threadIdx.x] = Wk[threadIdx.x]; }
@@ -62,6 +73,7 @@
     uint32_t plo[PPT], phi[PPT];
     float V[PPT][KT];
     float Pk[PPT][KT], Qk[PPT][KT];                       // DD: running peak P and q (simple) / d (log)
+    uint32_t jrow[PPT];                                   // BOOT: the row index j_t of SPEC.md 2.1
 #pragma unroll
     for (int e = 0; e < PPT; e++) {
       p[e] = tl * tile + (uint64_t)e * PATH_BLOCK + threadIdx.x;
@@ -70,6 +82,7 @@
       plo[e] = (uint32_t)g; phi[e] = (uint32_t)(g >> 32);
 #pragma unroll
       for (int k = 0; k < KT; k++) V[e][k] = logc ? 0.0f : a.v0;
+      if constexpr (BOOT) jrow[e] = 0u;                   // replaced at t = 0 (a restart)
       if constexpr (DD) {
 #pragma unroll
         for (int k = 0; k < KT; k++) { Pk[e][k] = -__builtin_inff(); Qk[e][k] = logc ? 0.0f : 1.0f; }

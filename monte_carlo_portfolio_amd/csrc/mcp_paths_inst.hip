@@ -80,4 +80,37 @@ hipError_t MCP_CAT(launch_paths_hz_nb, MCP_NB)(int variant, const PathArgsHZ& ar
   return hipGetLastError();
 }
 
+// The bootstrap kernels (mcp_simulate_bootstrap[_horizons]): one portfolio or KT = 8 passes, both compounding modes, the row
+// table in LDS or in global memory.
+template <int KT, bool LG, bool LDS>
+static void go_bt(const PathArgsBT& args, int grid, hipStream_t stream) {
+  mc_paths_boot_kernel<MCP_NB, KT, 1, LG, LDS><<<grid, PATH_BLOCK, lds_pad(), stream>>>(args);
+}
+template <int KT, bool LG, bool LDS>
+static void go_bt(const PathArgsBTHZ& args, int grid, hipStream_t stream) {
+  mc_paths_boot_hz_kernel<MCP_NB, KT, 1, LG, LDS><<<grid, PATH_BLOCK, lds_pad(), stream>>>(args);
+}
+template <class A>
+static hipError_t go_bt_any(int variant, bool lds, const A& args, int grid, hipStream_t stream) {
+  const bool lg = args.compounding == MCP_COMPOUND_LOG;
+  if (variant != 0 && variant != VAR_KT8) return hipErrorInvalidValue;
+  const bool kt8 = variant == VAR_KT8;
+  if (kt8) {
+    if (lg) lds ? go_bt<8, true, true>(args, grid, stream) : go_bt<8, true, false>(args, grid, stream);
+    else lds ? go_bt<8, false, true>(args, grid, stream) : go_bt<8, false, false>(args, grid, stream);
+  } else {
+    if (lg) lds ? go_bt<1, true, true>(args, grid, stream) : go_bt<1, true, false>(args, grid, stream);
+    else lds ? go_bt<1, false, true>(args, grid, stream) : go_bt<1, false, false>(args, grid, stream);
+  }
+  return hipGetLastError();
+}
+
+hipError_t MCP_CAT(launch_paths_bt_nb, MCP_NB)(int variant, bool lds, const PathArgsBT& args, int grid, hipStream_t stream) {
+  return go_bt_any(variant, lds, args, grid, stream);
+}
+
+hipError_t MCP_CAT(launch_paths_bthz_nb, MCP_NB)(int variant, bool lds, const PathArgsBTHZ& args, int grid, hipStream_t stream) {
+  return go_bt_any(variant, lds, args, grid, stream);
+}
+
 }  // namespace mcp

@@ -1,6 +1,43 @@
 // mcp_paths_step.inc -- one step t of the path kernels' walk (mcp_paths_body.inc, included in its step loops): the normals of
-// step t, r = mu + L z, rho = w.r, the update of V (and, DD, of the running peak and drawdown state).  In scope: everything
-// mcp_paths_body.inc declares before its step loops, and t.
+// step t, r = mu + L z (BOOT: r = row j_t of the observed returns), rho = w.r, the update of V (and, DD, of the running peak
+// and drawdown state).  In scope: everything mcp_paths_body.inc declares before its step loops, and t.
+      float rho[PPT][KT];
+      if constexpr (BOOT) {
+        // SPEC.md 2.1 / 4.4: one Philox block on counter (t, 1, p_lo, p_hi); j_t = mulhi(x0, R) on a restart (t = 0 or
+        // x1 < thr), else the next row, circularly; rho_k = sum_i w_ki r_i, i ascending over N4 (zero-padded rows)
+        asm volatile("" : "+s"(Wk));
+#pragma unroll
+        for (int e = 0; e < PPT; e++) {
+          uint32_t x[4];
+          philox4x32_10((uint32_t)t, 1u, plo[e], phi[e], ks, x);
+          const uint32_t start = __umulhi(x[0], bt.n_rows);
+          const uint32_t next = jrow[e] + 1u;
+          jrow[e] = (t == 0 || (uint64_t)x[1] < bt.thr) ? start : (next == bt.n_rows ? 0u : next);
+          const uint32_t j = jrow[e];
+          float4 r4[NB];
+          if constexpr (BLDS) {
+            const uint32_t sw = BootSwizzle<NB>::of(j);
+#pragma unroll
+            for (int q = 0; q < NB; q++) r4[q] = s_tab[j * NB + ((uint32_t)q ^ sw)];
+          } else {
+            const float4* src = bt.rows + (size_t)j * NB;
+#pragma unroll
+            for (int q = 0; q < NB; q++) r4[q] = src[q];
+          }
+#pragma unroll
+          for (int k = 0; k < KT; k++) {
+            float acc = 0.0f;
+#pragma unroll
+            for (int q = 0; q < NB; q++) {
+              acc = fma32(Wk[k * N4 + 4 * q + 0], r4[q].x, acc);
+              acc = fma32(Wk[k * N4 + 4 * q + 1], r4[q].y, acc);
+              acc = fma32(Wk[k * N4 + 4 * q + 2], r4[q].z, acc);
+              acc = fma32(Wk[k * N4 + 4 * q + 3], r4[q].w, acc);
+            }
+            rho[e][k] = acc;
+          }
+        }
+      } else {
       // keep the (loop-invariant) parameter loads inside the step: hoisted, they would pin ~170 registers
       asm volatile("" : "+s"(mu), "+s"(Lp), "+s"(Wk));
       uint32_t par_off = 0;                                        // opaque zero: keeps the LDS reads inside the step too
@@ -17,7 +54,6 @@
           block_normals<NATIVE>(x, s_tab, kc, z[e][0 * NB + q], z[e][1 * NB + q], z[e][2 * NB + q], z[e][3 * NB + q]);
         }
       }
-      float rho[PPT][KT];
       if constexpr (FOLD) {
         cfloat_p fv = mu + a.fold_offset;
         asm volatile("" : "+s"(fv));
@@ -62,6 +98,7 @@
         }
       }
       }  // !FOLD
+      }  // !BOOT
 #pragma unroll
       for (int e = 0; e < PPT; e++)
 #pragma unroll

@@ -110,6 +110,40 @@ class Context:
         return stats, hz_stats, bands, term, hz_term
 
 
+    def simulate_bootstrap(self, prm: _ffi.McpParams, rows, W, block: float, seed: int, path_begin: int, n_paths: int,
+                           store: bool):
+        """simulate() on bootstrap paths (SPEC.md 2.1 / 4.4; include/mcport.h, mcp_simulate_bootstrap): rows is the binary32
+        [R, N] table of observed returns, block the mean block length -> (stats [K], terminal [K, n_paths] or None)."""
+        K = prm.n_portfolios
+        stats = np.zeros(K, _ffi.STATS_DTYPE)
+        term = np.empty((K, n_paths), np.float32) if store else None
+        bt = _ffi.make_bootstrap(rows, block)
+        _ffi.check(_ffi.lib().mcp_simulate_bootstrap(
+            self._h, ctypes.byref(prm), ctypes.byref(bt), W, seed, path_begin, n_paths,
+            term.ctypes.data_as(ctypes.c_void_p) if store else None, stats.ctypes.data_as(ctypes.c_void_p)))
+        return stats, term
+
+    def simulate_bootstrap_horizons(self, prm: _ffi.McpParams, rows, W, block: float, seed: int, path_begin: int, n_paths: int,
+                                    horizons, levels, store: bool):
+        """simulate_horizons() on bootstrap paths (include/mcport.h, mcp_simulate_bootstrap_horizons) -> (stats, hz_stats,
+        bands, terminal, horizon_terminal) as simulate_horizons."""
+        K = prm.n_portfolios
+        steps = np.ascontiguousarray(horizons, np.int32).ravel()
+        lv = np.ascontiguousarray(levels, np.float64).ravel()
+        H, L = steps.size, lv.size
+        stats = np.zeros(K, _ffi.STATS_DTYPE)
+        hz_stats = np.zeros((H, K), _ffi.STATS_DTYPE)
+        bands = np.zeros((H, K, L), np.float64)
+        term = np.empty((K, n_paths), np.float32) if store else None
+        hz_term = np.empty((H, K, n_paths), np.float32) if store else None
+        ptr = lambda a: a.ctypes.data_as(ctypes.c_void_p) if a is not None else None   # noqa: E731
+        bt = _ffi.make_bootstrap(rows, block)
+        _ffi.check(_ffi.lib().mcp_simulate_bootstrap_horizons(
+            self._h, ctypes.byref(prm), ctypes.byref(bt), W, seed, path_begin, n_paths, H, ptr(steps), L, ptr(lv) if L else None,
+            ptr(term), ptr(stats), ptr(hz_term), ptr(hz_stats), ptr(bands) if L else None))
+        return stats, hz_stats, bands, term, hz_term
+
+
 def check_horizons(horizons, bands, n_steps):
     """SPEC.md 4.3 / 5.2 argument rules -> (steps int32 [H], levels float64 [L]); ValueError otherwise."""
     h = np.asarray(horizons)
@@ -267,6 +301,84 @@ def simulate_paths(mu, cov, weights, n_steps=252, n_paths=10_000, seed=0, v0=1.0
             d["terminal"] = term[k]
             if drawdown:
                 d["max_drawdown"] = mdd[k]
+            if horizons is not None:
+                d["horizon_terminal"] = hz_term[:, k, :]
+    return out[0] if single else out
+
+
+def bootstrap_inputs(returns, weights):
+    """SPEC.md 2.1 argument rules -> (rows binary32 [R, N] C-contiguous, W binary32 [K, N]); ValueError otherwise.  `returns`
+    is a DataFrame (returns_matrix(...), app.py:667) or an [R, N] array; its values are rounded to binary32 to nearest."""
+    vals = returns.to_numpy() if hasattr(returns, "to_numpy") else returns
+    rows64 = np.asarray(vals, np.float64)
+    if rows64.ndim == 1:
+        rows64 = rows64[:, None]
+    if rows64.ndim != 2 or rows64.shape[0] < 1:
+        raise ValueError(f"returns must be an [R, N] matrix with R >= 1, got shape {rows64.shape}")
+    R, N = rows64.shape
+    if R > _ffi.MCP_MAX_BOOT_ROWS:
+        raise ValueError(f"at most {_ffi.MCP_MAX_BOOT_ROWS} return rows, got {R}")
+    if not 1 <= N <= _ffi.MCP_MAX_ASSETS:
+        raise ValueError(f"n_assets={N} outside [1, {_ffi.MCP_MAX_ASSETS}]")
+    rows = np.ascontiguousarray(rows64.astype(np.float32))
+    bad = ~np.isfinite(rows).all(axis=1)
+    if bad.any():
+        raise ValueError(f"returns hold NaN or infinite values in {int(bad.sum())} rows (first: row {int(np.argmax(bad))}); drop them first")
+    W = np.ascontiguousarray(np.atleast_2d(np.asarray(weights, np.float32)))
+    if W.ndim != 2 or W.shape[1] != N:
+        raise ValueError(f"weights have {W.shape[-1]} columns, the returns {N}")
+    return rows, W
+
+
+def simulate_bootstrap(returns, weights, n_steps=252, n_paths=10_000, block=1.0, seed=0, v0=1.0, compounding="simple",
+                       rf=0.0, alpha=0.95, devices=None, store=False, path_begin=0, as_array=False, shard="auto", context=None,
+                       horizons=None, bands=(), **unsupported):
+    """simulate_paths on paths resampled from the observed return rows instead of a normal model: the stationary block
+    bootstrap of Politis & Romano (SPEC.md 2.1 / 4.4).  Every step of a path uses one whole row of `returns` (all assets of one
+    date together), so fat tails, skew, the co-movement within a row and -- with a mean block length `block` > 1 -- short-range
+    serial dependence survive.  block = 1: every row drawn independently; block = inf: one random start, then consecutive
+    rows (circularly).  All portfolios see the same rows.
+
+    returns: DataFrame (returns_matrix(...), app.py:667) or [R, N] array of per-step returns, finite, R <= 2^20; weights [N]
+    or [K, N].  Returns exactly what simulate_paths returns for the same arguments, 'horizons' block included (pivots of
+    SPEC.md 5.3).  ValueError for NaN rows, a width that does not match the weights, block < 1, or the simulate_paths keywords
+    that have no meaning here (fold, native_math, drawdown, chol).
+    """
+    if unsupported:
+        raise ValueError(f"simulate_bootstrap does not take {sorted(unsupported)} (no normals: no fold / native_math; "
+                         "drawdown on bootstrap paths is not supported)")
+    b = float(block)
+    if not b >= 1.0:
+        raise ValueError(f"block (mean block length) must be >= 1 or inf, got {block!r}")
+    if horizons is not None:
+        steps, levels = check_horizons(horizons, bands, n_steps)
+    elif len(np.atleast_1d(np.asarray(bands, np.float64))):
+        raise ValueError("bands need horizons")
+    single = np.asarray(weights).ndim == 1
+    rows, W = bootstrap_inputs(returns, weights)
+    devs = (0,) if not devices else tuple(int(d) for d in devices)
+    if shard not in ("auto", "paths", "portfolios"):
+        raise ValueError("shard must be 'auto', 'paths' or 'portfolios'")
+    by_portfolio = len(devs) > 1 and (shard == "portfolios" or (shard == "auto" and W.shape[0] >= 512 * len(devs)))
+    prm = _ffi.make_params(rows.shape[1], n_steps, W.shape[0], compounding, v0, alpha, rf, False, False, by_portfolio)
+    ctx = context if context is not None else default_context(devs)
+    if horizons is not None:
+        stats, hz_stats, hz_bands, term, hz_term = ctx.simulate_bootstrap_horizons(
+            prm, rows, W, b, int(seed), int(path_begin), int(n_paths), steps, levels, store)
+        if as_array:
+            return (stats, hz_stats, hz_bands, term, hz_term) if store else (stats, hz_stats, hz_bands)
+    else:
+        stats, term = ctx.simulate_bootstrap(prm, rows, W, b, int(seed), int(path_begin), int(n_paths), store)
+        if as_array:
+            return (stats, term) if store else stats
+    out = [stats_to_dict(stats[k]) for k in range(W.shape[0])]
+    for k, d in enumerate(out):
+        if horizons is not None:
+            d["horizons"] = dict({"steps": steps.astype(np.int64), "levels": levels.copy(), "bands": hz_bands[:, k, :]},
+                                 **{f: hz_stats[f][:, k].astype(np.int64 if f == "n_tail" else np.float64)
+                                    for f in ("mean", "std", "var", "cvar", "min", "max", "n_tail")})
+        if store:
+            d["terminal"] = term[k]
             if horizons is not None:
                 d["horizon_terminal"] = hz_term[:, k, :]
     return out[0] if single else out
