@@ -92,6 +92,15 @@ with tab_sweep:                                               # app.py:655-783
     keys = ("mean", "std", "sharpe", "var", "cvar", "min", "max")
     st.subheader("normal model vs. bootstrap of the observed rows (mean block 3)")
     st.write({"normal model (mean / cov)": {k: sim[k] for k in keys}, "bootstrap of the observed rows": {k: boot[k] for k in keys}})
+    # the same allocation as a purchase: bought and held, or traded back to the weights every few periods at a proportional cost
+    # of the amount traded (SPEC.md 4.5), instead of the free rebalance after every period of the paths above
+    choices = ["never (buy and hold)", "every period", "every 3 periods", "every 6 periods"]
+    held_choice = st.selectbox("rebalancing of the allocation", choices, 0)
+    cost_bp = float(st.number_input("trading cost (basis points of the amount traded)", value=10.0))
+    held = mcp.simulate_paths(mu_step, cov_step, w, n_steps=annual_factor, n_paths=n_paths, seed=12345,
+                              v0=state["investment_amount"], rf=user_rf / 100.0,
+                              rebalance=dict(zip(choices, ["never", 1, 3, 6]))[held_choice], rebalance_cost=cost_bp / 1e4)
+    st.write({"allocation held": {"rebalancing": held_choice, "cost (bp)": cost_bp, **{k: held[k] for k in keys}}})
 
 with tab_forecast:                                            # app.py:785-809
     # The reference forecasts 1, 3 and 6 periods ahead with a 95 % interval.  Here: a Monte Carlo fan from the path engine

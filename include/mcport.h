@@ -25,7 +25,8 @@ extern "C" {
 
 #define MCP_ABI_VERSION 4        /* 4: + mcp_simulate_drawdown, mcp_launch_paths_drawdown (additive); + mcp_simulate_horizons,
                                     mcp_launch_paths_horizons, mcp_percentile_rank_q (additive, detected by symbol);
-                                    + mcp_simulate_bootstrap[_horizons], mcp_bootstrap_pivots (additive, detected by symbol) */
+                                    + mcp_simulate_bootstrap[_horizons], mcp_bootstrap_pivots (additive, detected by symbol);
+                                    + mcp_simulate_rebalanced, mcp_rebalance_pivots (additive, detected by symbol) */
 #define MCP_MAX_ASSETS 64        /* thread-per-path kernels are instantiated for N4 = 4..64 */
 #define MCP_SELECT_BINS 2048     /* radix-select digit: 11 + 11 + 10 bits */
 #define MCP_MAX_HORIZONS 64      /* mcp_simulate_horizons: horizon steps per call */
@@ -219,6 +220,40 @@ int mcp_simulate_bootstrap_horizons(mcp_ctx *ctx, const mcp_params *prm, const m
  *   simple: c_k = (1 + m_k)^T - 1 (as expm1(T log1p(m_k)), 0 if m_k <= -1)     log: c_k = expm1(T (m_k + s2_k / 2)).
  * 0 where it is not finite. */
 int mcp_bootstrap_pivots(const mcp_params *prm, const mcp_bootstrap *boot, const float *W, double *pivots_out /* [K] */);
+
+/* Buy-and-hold and periodic rebalancing (SPEC.md 4.5 / 5.4).  period m >= 0: the portfolio is traded back to its weights after
+ * every step s with s mod m == 0 and s < T; m = 0 (or m >= T) is buy-and-hold.  cost: the proportional cost kappa in [0, 1) of
+ * the fraction traded, paid out of the portfolio.  reserved must be 0. */
+typedef struct {
+    int32_t period;
+    int32_t reserved;
+    double cost;
+} mcp_rebalance;
+
+/* mcp_simulate / mcp_simulate_horizons / mcp_simulate_bootstrap[_horizons] with the weights held between rebalance dates
+ * instead of kept constant (SPEC.md 4.5; simple compounding only).  Draws: exactly one source -- mu and chol (SPEC.md 2-4,
+ * boot NULL) or boot (SPEC.md 2.1 / 4.4, mu and chol NULL).  n_horizons = 0: no horizons (horizons ignored, n_levels = 0,
+ * horizon_out, hz_stats_out and bands_out NULL); otherwise the horizons, records and bands of mcp_simulate_horizons, V_h taken
+ * before any trade of step h.  Period 1 without cost is bit for bit the constant-weight call.  The moments are pivoted at
+ * SPEC.md 5.4.  Argument errors (MCP_E_ARG) are found before any device is touched; log compounding, MCP_FLAG_FOLD,
+ * MCP_FLAG_NATIVE_MATH: MCP_E_UNSUPPORTED.  K >= 17 runs as passes of 8 portfolios. */
+int mcp_simulate_rebalanced(mcp_ctx *ctx, const mcp_params *prm, const mcp_rebalance *reb,
+                            const float *mu, const float *chol,   /* Gaussian draws ...                       */
+                            const mcp_bootstrap *boot,             /* ... or bootstrap draws: exactly one        */
+                            const float *W, uint64_t seed, uint64_t path_begin, uint64_t n_paths,
+                            int n_horizons, const int32_t *horizons,
+                            int n_levels, const double *levels,
+                            float *terminal_out,        /* NULL or host [K*n_paths] */
+                            mcp_stats *stats_out,       /* [K] */
+                            float *horizon_out,         /* NULL or host [H*K*n_paths], row h*K + k */
+                            mcp_stats *hz_stats_out,    /* [H*K], NULL iff n_horizons == 0 */
+                            double *bands_out);         /* [H*K*L], NULL iff n_levels == 0 */
+/* The shift of the moments of rebalanced paths at prm->n_steps (SPEC.md 5.4; host side, binary64): with the segments l_1..l_S
+ * between the rebalance dates, mu_i = mu[i] (Gaussian) or the mean of column i of the rows (bootstrap; exactly one of mu and boot),
+ * a_i(l) = expm1(l log1p(mu_i)), g_s = sum_i W[k,i] a_i(l_s):  c_k = expm1(sum_s log1p(g_s)), 0 where it is not finite.  The cost
+ * is ignored. */
+int mcp_rebalance_pivots(const mcp_params *prm, const mcp_rebalance *reb, const float *mu, const mcp_bootstrap *boot,
+                         const float *W, double *pivots_out /* [K] */);
 
 /* The reference's own sweep (app.py:699-717) over HISTORICAL returns, loop body app.py:708-713 for P weight
  * vectors at once, binary64 like the reference.  returns: [R*N] row-major (returns_df.values, app.py:667),

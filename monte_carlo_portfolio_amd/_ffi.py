@@ -59,6 +59,11 @@ class McpBootstrap(ctypes.Structure):
     _fields_ = [("rows", ctypes.c_void_p), ("n_rows", ctypes.c_int32), ("reserved", ctypes.c_int32), ("mean_block", ctypes.c_double)]
 
 
+class McpRebalance(ctypes.Structure):
+    """mcp_rebalance: the rebalancing rule of SPEC.md 4.5 (period 0: never, buy-and-hold; cost: proportional, in [0, 1))."""
+    _fields_ = [("period", ctypes.c_int32), ("reserved", ctypes.c_int32), ("cost", ctypes.c_double)]
+
+
 STATS_DTYPE = np.dtype([
     ("n", np.uint64), ("n_tail", np.uint64), ("mean", np.float64), ("m2", np.float64), ("std", np.float64),
     ("sharpe", np.float64), ("var", np.float64), ("cvar", np.float64), ("min", np.float64), ("max", np.float64),
@@ -112,6 +117,9 @@ SIGNATURES = {
     "mcp_simulate_bootstrap_horizons": (_int, [_vp, _PP, ctypes.POINTER(McpBootstrap), _f32p, _u64, _u64, _u64, _int, _vp, _int, _vp,
                                                _vp, _vp, _vp, _vp, _vp]),
     "mcp_bootstrap_pivots": (_int, [_PP, ctypes.POINTER(McpBootstrap), _f32p, _f64p]),
+    "mcp_simulate_rebalanced": (_int, [_vp, _PP, ctypes.POINTER(McpRebalance), _vp, _vp, ctypes.POINTER(McpBootstrap), _f32p, _u64, _u64,
+                                       _u64, _int, _vp, _int, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "mcp_rebalance_pivots": (_int, [_PP, ctypes.POINTER(McpRebalance), _vp, ctypes.POINTER(McpBootstrap), _f32p, _f64p]),
     "mcp_percentile_rank_q": (_int, [_u64, ctypes.c_double, ctypes.POINTER(_u64), ctypes.POINTER(_u64),
                                      ctypes.POINTER(ctypes.c_double)]),
     "mcp_percentile_rank": (_int, [_u64, ctypes.c_double, ctypes.POINTER(_u64), ctypes.POINTER(_u64),
@@ -246,6 +254,19 @@ def bootstrap_pivots(prm: McpParams, rows: np.ndarray, W: np.ndarray, block: flo
     rows = np.ascontiguousarray(rows, np.float32)
     bt = make_bootstrap(rows, block)
     check(lib().mcp_bootstrap_pivots(ctypes.byref(prm), ctypes.byref(bt), W, out))
+    return out
+
+
+def rebalance_pivots(prm: McpParams, period: int, W: np.ndarray, mu: np.ndarray | None = None, rows: np.ndarray | None = None,
+                     cost: float = 0.0) -> np.ndarray:
+    """[K] shifts of the moments of rebalanced paths (SPEC.md 5.4; include/mcport.h, mcp_rebalance_pivots), pure host arithmetic:
+    pass the drift `mu` (Gaussian draws) or the binary32 [R, N] `rows` (bootstrap draws)."""
+    out = np.zeros(W.shape[0], np.float64)
+    rb = McpRebalance(int(period), 0, float(cost))
+    mu_p = np.ascontiguousarray(mu, np.float32) if mu is not None else None
+    bt = make_bootstrap(np.ascontiguousarray(rows, np.float32), 1.0) if rows is not None else None
+    check(lib().mcp_rebalance_pivots(ctypes.byref(prm), ctypes.byref(rb), mu_p.ctypes.data_as(_vp) if mu_p is not None else None,
+                                     ctypes.byref(bt) if bt is not None else None, W, out))
     return out
 
 

@@ -128,6 +128,11 @@ const mcp::launch_paths_bthz_fn k_launch_bthz[16] = {
     mcp::launch_paths_bthz_nb5,  mcp::launch_paths_bthz_nb6,  mcp::launch_paths_bthz_nb7,  mcp::launch_paths_bthz_nb8,
     mcp::launch_paths_bthz_nb9,  mcp::launch_paths_bthz_nb10, mcp::launch_paths_bthz_nb11, mcp::launch_paths_bthz_nb12,
     mcp::launch_paths_bthz_nb13, mcp::launch_paths_bthz_nb14, mcp::launch_paths_bthz_nb15, mcp::launch_paths_bthz_nb16};
+const mcp::launch_paths_rb_fn k_launch_rb[16] = {
+    mcp::launch_paths_rb_nb1,  mcp::launch_paths_rb_nb2,  mcp::launch_paths_rb_nb3,  mcp::launch_paths_rb_nb4,
+    mcp::launch_paths_rb_nb5,  mcp::launch_paths_rb_nb6,  mcp::launch_paths_rb_nb7,  mcp::launch_paths_rb_nb8,
+    mcp::launch_paths_rb_nb9,  mcp::launch_paths_rb_nb10, mcp::launch_paths_rb_nb11, mcp::launch_paths_rb_nb12,
+    mcp::launch_paths_rb_nb13, mcp::launch_paths_rb_nb14, mcp::launch_paths_rb_nb15, mcp::launch_paths_rb_nb16};
 
 // SPEC.md 4.3: 1..MCP_MAX_HORIZONS strictly increasing steps in [1, n_steps]
 int check_horizons(int n_steps, int H, const int32_t* steps) {
@@ -196,6 +201,70 @@ double boot_pivot(int compounding, int T, double m, double s2) {
   const double c = compounding == MCP_COMPOUND_LOG ? std::expm1((double)T * (m + 0.5 * s2))
                                                    : (m > -1.0 ? std::expm1((double)T * std::log1p(m)) : 0.0);
   return std::isfinite(c) ? c : 0.0;
+}
+
+// The rebalancing rule of a launch (SPEC.md 4.5): the period m >= 0 and kappa32 = fl32(kappa).
+struct RebReq {
+  int32_t period = 0;
+  float cost = 0.0f;
+};
+
+// SPEC.md 4.5: period >= 0, reserved == 0, cost in [0, 1) (not NaN)
+int check_reb(const mcp_rebalance* reb, RebReq* out) {
+  if (!reb) return fail(MCP_E_ARG, "rebalance is NULL");
+  if (reb->period < 0) return fail(MCP_E_ARG, "rebalance period=%d < 0", reb->period);
+  if (reb->reserved != 0) return fail(MCP_E_ARG, "rebalance reserved=%d must be 0", reb->reserved);
+  if (!(reb->cost >= 0.0 && reb->cost < 1.0)) return fail(MCP_E_ARG, "rebalance cost=%g outside [0, 1)", reb->cost);
+  if (out) {
+    out->period = reb->period;
+    out->cost = (float)reb->cost;
+  }
+  return MCP_OK;
+}
+
+// SPEC.md 5.4: mu_i of the pivot of rebalanced paths, binary64 -- the drift (Gaussian) or the mean of column i of the rows
+// (bootstrap, j ascending)
+void reb_means(int N, const float* mu, const mcp_bootstrap* boot, double* out) {
+  for (int i = 0; i < N; i++) {
+    if (boot) {
+      double sum = 0.0;
+      for (int j = 0; j < boot->n_rows; j++) sum += (double)boot->rows[(size_t)j * N + i];
+      out[i] = sum / (double)boot->n_rows;
+    } else {
+      out[i] = (double)mu[i];
+    }
+  }
+}
+
+// SPEC.md 5.4: the pivots at T steps of period m for K portfolios.  The dates m, 2m, .. < T cut [0, T] into F = floor((T-1)/m)
+// segments of length m and a last one of length T - F m (m = 0 or m >= T: one segment of length T); with
+// a_i(l) = expm1(l log1p(mu_i)) and g(l) = sum_i W[k,i] a_i(l) (i ascending), c = expm1(F log1p(g(m)) + log1p(g(l_last))),
+// 0 where it is not finite (0 for T = 0).
+void reb_pivots(int N, int K, int T, int m, const double* mu, const float* W, double* out) {
+  if (T <= 0) {
+    for (int k = 0; k < K; k++) out[k] = 0.0;
+    return;
+  }
+  const int64_t F = (m >= 1 && m < T) ? (int64_t)(T - 1) / m : 0;
+  const double l_last = (double)((int64_t)T - F * m);
+  std::vector<double> af((size_t)N), al((size_t)N);
+  for (int i = 0; i < N; i++) {
+    const double lp = std::log1p(mu[i]);
+    al[(size_t)i] = std::expm1(l_last * lp);
+    af[(size_t)i] = F ? std::expm1((double)m * lp) : 0.0;
+  }
+  for (int k = 0; k < K; k++) {
+    const float* w = W + (size_t)k * N;
+    double gf = 0.0, gl = 0.0;
+    for (int i = 0; i < N; i++) {
+      gf += (double)w[i] * af[(size_t)i];
+      gl += (double)w[i] * al[(size_t)i];
+    }
+    double e = std::log1p(gl);
+    if (F) e = (double)F * std::log1p(gf) + e;
+    const double c = std::expm1(e);
+    out[k] = std::isfinite(c) ? c : 0.0;
+  }
 }
 
 // Inverse-CDF coefficient table (SPEC.md section 3; DATA of the spec, generated by tools/fit_icdf_table.py): one
@@ -438,6 +507,21 @@ int mcp_pivots(const mcp_params* prm, const float* mu, const float* chol, const 
   return MCP_OK;
 }
 
+int mcp_rebalance_pivots(const mcp_params* prm, const mcp_rebalance* reb, const float* mu, const mcp_bootstrap* boot, const float* W,
+                         double* out) {
+  if (int rc = check_params(prm)) return rc;
+  if (int rc = check_reb(reb, nullptr)) return rc;
+  if ((mu == nullptr) == (boot == nullptr)) return fail(MCP_E_ARG, "exactly one of mu and boot");
+  if (boot)
+    if (int rc = check_boot(prm, boot, nullptr)) return rc;
+  if (!W || !out) return fail(MCP_E_ARG, "NULL pointer");
+  if (prm->compounding != MCP_COMPOUND_SIMPLE) return fail(MCP_E_UNSUPPORTED, "rebalanced paths compound simply (no log compounding)");
+  std::vector<double> m((size_t)prm->n_assets);
+  reb_means(prm->n_assets, mu, boot, m.data());
+  reb_pivots(prm->n_assets, prm->n_portfolios, prm->n_steps, reb->period, m.data(), W, out);
+  return MCP_OK;
+}
+
 int mcp_bootstrap_pivots(const mcp_params* prm, const mcp_bootstrap* boot, const float* W, double* out) {
   if (int rc = check_params(prm)) return rc;
   if (int rc = check_boot(prm, boot, nullptr)) return rc;
@@ -473,7 +557,8 @@ struct BootIn {
 // the path kernel's workgroups overwrite the first path_grid(n) of them.
 static int launch_paths_impl(const mcp_params* prm, const float* d_packed, const double* d_pivot, uint64_t seed, uint64_t path_begin,
                              uint64_t n_paths, float* d_terminal, uint64_t stride, float* d_mdd, uint64_t mdd_stride, void* d_partials,
-                             void* d_hist, void* stream, const HzOut* hz = nullptr, const BootIn* boot = nullptr) {
+                             void* d_hist, void* stream, const HzOut* hz = nullptr, const BootIn* boot = nullptr,
+                             const RebReq* reb = nullptr) {
   const bool dd = d_mdd != nullptr;
   if (int rc = check_params(prm)) return rc;
   if (!d_packed || !d_terminal) return fail(MCP_E_ARG, "NULL device pointer");
@@ -495,6 +580,13 @@ static int launch_paths_impl(const mcp_params* prm, const float* d_packed, const
     if (prm->flags & (MCP_FLAG_FOLD | MCP_FLAG_NATIVE_MATH))
       return fail(MCP_E_UNSUPPORTED, "bootstrap paths draw no normals (no MCP_FLAG_FOLD / MCP_FLAG_NATIVE_MATH)");
     if (!boot->d_rows || boot->n_rows < 1 || boot->n_rows > (uint32_t)MCP_MAX_BOOT_ROWS) return fail(MCP_E_ARG, "bad bootstrap table");
+  }
+  if (reb) {
+    if (dd) return fail(MCP_E_UNSUPPORTED, "the drawdown is not tracked on rebalanced paths");
+    if (prm->compounding != MCP_COMPOUND_SIMPLE) return fail(MCP_E_UNSUPPORTED, "rebalanced paths compound simply (no log compounding)");
+    if (prm->flags & (MCP_FLAG_FOLD | MCP_FLAG_NATIVE_MATH))
+      return fail(MCP_E_UNSUPPORTED, "rebalanced paths run on the unfolded recurrence and the spec's normals (no MCP_FLAG_FOLD / MCP_FLAG_NATIVE_MATH)");
+    if (reb->period < 0 || !(reb->cost >= 0.0f && reb->cost <= 1.0f)) return fail(MCP_E_ARG, "bad rebalancing rule");
   }
   if ((d_partials == nullptr) != (d_hist == nullptr)) return fail(MCP_E_ARG, "d_partials and d_hist go together (both or neither)");
   if (n_paths < 1) return fail(MCP_E_ARG, "n_paths must be >= 1");
@@ -520,14 +612,14 @@ static int launch_paths_impl(const mcp_params* prm, const float* d_packed, const
   DeviceGuard guard(dev);                 // the stream may belong to another device than the thread's current one
   if (guard.err != hipSuccess) return fail(MCP_E_HIP, "hipSetDevice(%d): %s", dev, hipGetErrorString(guard.err));
   if (int rc = device_tables(dev, (hipStream_t)stream, &tables)) return rc;
-  const bool sweep = !dd && !hz && !boot && uses_sweep(K);
+  const bool sweep = !dd && !hz && !boot && !reb && uses_sweep(K);
   a.tables = tables;
   a.packed = d_packed;
   a.terminal = d_terminal;
   a.pivot = d_pivot;
   a.partials = (mcp::MomentPartial*)d_partials;
   a.hist = sweep ? nullptr : (unsigned long long*)d_hist;     // the sweep kernels leave digit 0 to hist(0) below
-  a.slots = (dd || hz || boot) ? mcp_moment_slots(K, n_paths) : mcp::moment_slots(sweep, n_paths);
+  a.slots = (dd || hz || boot || reb) ? mcp_moment_slots(K, n_paths) : mcp::moment_slots(sweep, n_paths);
   a.v0d = (double)(float)prm->v0;
   a.inv_v0d = 1.0 / a.v0d;
   { int e = 0; a.v0_pow2 = std::frexp(a.v0d, &e) == 0.5; }
@@ -559,9 +651,30 @@ static int launch_paths_impl(const mcp_params* prm, const float* d_packed, const
     }
     return MCP_OK;
   }
-  if ((dd || hz || boot) && d_partials && a.slots > (uint64_t)grid)
+  if ((dd || hz || boot || reb) && d_partials && a.slots > (uint64_t)grid)
     HIP_TRY(mcp::launch_pass0(*prm, K, d_terminal, stride, 0, nullptr, a.slots, (mcp::MomentPartial*)d_partials,
                               (unsigned long long*)d_hist, (hipStream_t)stream));
+  if (reb) {                              // SPEC.md 4.5: one kernel for every draw source, with or without horizons
+    mcp::PathArgsRB ar;
+    static_cast<mcp::PathArgs&>(ar) = a;
+    ar.hz = hz ? hz->d_out : nullptr;
+    ar.hz_stride = hz ? hz->stride : 0;
+    ar.n_horizons = hz ? hz->n : 0;
+    for (int i = 0; i < MCP_MAX_HORIZONS; i++) ar.steps[i] = hz && i < hz->n ? hz->steps[i] : 0;
+    ar.bt.rows = boot ? (const float4*)boot->d_rows : nullptr;
+    ar.bt.thr = boot ? boot->thr : 0;
+    ar.bt.n_rows = boot ? boot->n_rows : 0;
+    ar.bt.pad = 0;
+    ar.period = reb->period;
+    ar.cost = reb->cost;
+    const bool lds = boot && mcp::boot_fits_lds(boot->n_rows, nb);
+    for (int kb = 0; kb < K; kb += kt) {
+      ar.k_begin = kb;
+      hipError_t e = k_launch_rb[nb - 1](variant, boot != nullptr, lds, ar, grid, (hipStream_t)stream);
+      if (e != hipSuccess) return fail(MCP_E_HIP, "mc_paths_reb_kernel launch: %s", hipGetErrorString(e));
+    }
+    return MCP_OK;
+  }
   if (boot) {
     mcp::BootArgs bt;
     bt.rows = (const float4*)boot->d_rows;
@@ -1109,7 +1222,8 @@ struct BootReq {
 // at alpha (pass 0 + run_select) and once per level at that level's rank, whose records contribute only their `var`.
 int run_tile(mcp_ctx* c, const mcp_params* prm, const float* mu, const float* chol, const float* W, uint64_t seed,
              uint64_t path_begin, uint64_t n_total, const std::vector<Job>& jobs, bool exchange, float* terminal_out,
-             mcp_stats* stats_out, bool dd, float* mdd_out, mcp_stats* dd_stats_out, const HzReq* hz, const BootReq* boot) {
+             mcp_stats* stats_out, bool dd, float* mdd_out, mcp_stats* dd_stats_out, const HzReq* hz, const BootReq* boot,
+             const RebReq* reb) {
   const size_t S = c->sh.size();
   uint64_t lo, hi;
   double gamma;
@@ -1167,7 +1281,11 @@ int run_tile(mcp_ctx* c, const mcp_params* prm, const float* mu, const float* ch
   // bootstrap: no drift and no Cholesky factor in the packed block (only W is read), the pivots of SPEC.md 5.3 from the row
   // moments (computed once per tile)
   std::vector<float> zmu, zchol;
-  std::vector<double> bm, bs2;
+  std::vector<double> bm, bs2, rmu;
+  if (reb) {                              // SPEC.md 5.4: the per-asset means of the draws, once per tile
+    rmu.resize((size_t)prm->n_assets);
+    reb_means(prm->n_assets, boot ? nullptr : mu, boot ? boot->boot : nullptr, rmu.data());
+  }
   if (boot) {
     zmu.assign((size_t)prm->n_assets, 0.0f);
     zchol.assign((size_t)prm->n_assets * prm->n_assets, 0.0f);
@@ -1189,7 +1307,9 @@ int run_tile(mcp_ctx* c, const mcp_params* prm, const float* mu, const float* ch
       hpsrc = shared_hz_pivot;
     } else {
       if ((rc = mcp_pack_params(prm->n_assets, j.kt, mu, chol, W + (size_t)j.k0 * prm->n_assets, sh.h_packed, plen))) return rc;
-      if (boot) {
+      if (reb) {
+        reb_pivots(prm->n_assets, j.kt, prm->n_steps, reb->period, rmu.data(), W + (size_t)j.k0 * prm->n_assets, sh.h_pivot);
+      } else if (boot) {
         bm.resize((size_t)j.kt);
         bs2.resize((size_t)j.kt);
         boot_moments(prm->n_assets, boot->boot, W + (size_t)j.k0 * prm->n_assets, j.kt, bm.data(), bs2.data());
@@ -1202,7 +1322,9 @@ int run_tile(mcp_ctx* c, const mcp_params* prm, const float* mu, const float* ch
         for (int h = 0; h < hz->H; h++) {
           ph.n_steps = hz->steps[h];
           double* hp = sh.h_hz_pivot + (size_t)h * j.kt;
-          if (boot) {
+          if (reb) {
+            reb_pivots(prm->n_assets, j.kt, ph.n_steps, reb->period, rmu.data(), W + (size_t)j.k0 * prm->n_assets, hp);
+          } else if (boot) {
             for (int k = 0; k < j.kt; k++) hp[k] = boot_pivot(prm->compounding, ph.n_steps, bm[(size_t)k], bs2[(size_t)k]);
           } else if ((rc = mcp_pivots(&ph, mu, chol, W + (size_t)j.k0 * prm->n_assets, hp))) {
             return rc;
@@ -1230,7 +1352,7 @@ int run_tile(mcp_ctx* c, const mcp_params* prm, const float* mu, const float* ch
     if (j.pn) {
       if ((rc = launch_paths_impl(&tp[s], sh.d_packed, (const double*)sh.ws[MCP_WS_PIVOT], seed, path_begin + j.p0, j.pn, sh.d_terminal,
                                   j.pn, dd ? sh.d_mdd : nullptr, j.pn, sh.ws[MCP_WS_PARTIALS], sh.ws[MCP_WS_HIST], sh.stream,
-                                  hz ? &hzo : nullptr, boot ? &bti : nullptr))) return rc;
+                                  hz ? &hzo : nullptr, boot ? &bti : nullptr, reb))) return rc;
     } else {
       // a shard without paths (fewer paths than shards): empty moment partials, nothing in the histogram
       if ((rc = mcp_launch_pass0(&tp[s], sh.d_terminal, 1, 0, (const double*)sh.ws[MCP_WS_PIVOT], sh.ws[MCP_WS_PARTIALS],
@@ -1328,7 +1450,7 @@ int tile_portfolios(size_t budget, uint64_t n_paths, int K, size_t bytes_per_pat
 
 int simulate_impl(mcp_ctx* c, const mcp_params* prm, const float* mu, const float* chol, const float* W, uint64_t seed,
                   uint64_t path_begin, uint64_t n_paths, float* terminal_out, mcp_stats* stats_out, bool dd, float* mdd_out,
-                  mcp_stats* dd_stats_out, const HzReq* hz = nullptr, const BootReq* boot = nullptr) {
+                  mcp_stats* dd_stats_out, const HzReq* hz = nullptr, const BootReq* boot = nullptr, const RebReq* reb = nullptr) {
   if (!c) return fail(MCP_E_ARG, "ctx is NULL");
   if (int rc = check_params(prm)) return rc;
   if ((!boot && (!mu || !chol)) || !W || !stats_out || (dd && !dd_stats_out)) return fail(MCP_E_ARG, "NULL pointer");
@@ -1385,7 +1507,7 @@ int simulate_impl(mcp_ctx* c, const mcp_params* prm, const float* mu, const floa
       }
       if (more)
         rc = run_tile(c, prm, mu, chol, W, seed, path_begin, n_paths, jobs, false, terminal_out, stats_out, dd, mdd_out, dd_stats_out, hz,
-                      boot);
+                      boot, reb);
     }
   } else if (rc == MCP_OK) {
     // the path range is sharded; all shards see the same tile of portfolios
@@ -1401,7 +1523,7 @@ int simulate_impl(mcp_ctx* c, const mcp_params* prm, const float* mu, const floa
     for (int k0 = 0; k0 < K && rc == MCP_OK; k0 += kt_max) {
       for (size_t s = 0; s < S; s++) { jobs[s].k0 = k0; jobs[s].kt = std::min(kt_max, K - k0); }
       rc = run_tile(c, prm, mu, chol, W, seed, path_begin, n_paths, jobs, S > 1 || c->exchange_always, terminal_out, stats_out, dd,
-                    mdd_out, dd_stats_out, hz, boot);
+                    mdd_out, dd_stats_out, hz, boot, reb);
     }
   }
   if (rc != MCP_OK) {
@@ -1499,6 +1621,48 @@ int mcp_simulate_bootstrap_horizons(mcp_ctx* c, const mcp_params* prm, const mcp
   hz.bands_out = bands_out;
   return simulate_impl(c, prm, nullptr, nullptr, W, seed, path_begin, n_paths, terminal_out, stats_out, false, nullptr, nullptr, &hz,
                        &br);
+}
+
+int mcp_simulate_rebalanced(mcp_ctx* c, const mcp_params* prm, const mcp_rebalance* reb, const float* mu, const float* chol,
+                            const mcp_bootstrap* boot, const float* W, uint64_t seed, uint64_t path_begin, uint64_t n_paths,
+                            int n_horizons, const int32_t* horizons, int n_levels, const double* levels, float* terminal_out,
+                            mcp_stats* stats_out, float* horizon_out, mcp_stats* hz_stats_out, double* bands_out) {
+  // the arguments first, so that each error is found (and named) before any device is touched, a NULL ctx included
+  if (int rc = check_params(prm)) return rc;
+  RebReq rr;
+  if (int rc = check_reb(reb, &rr)) return rc;
+  const bool gauss = mu && chol && !boot, resample = boot && !mu && !chol;
+  if (!gauss && !resample) return fail(MCP_E_ARG, "exactly one draw source: mu and chol, or boot");
+  BootReq br;
+  if (boot) {
+    if (int rc = check_boot(prm, boot, &br.thr)) return rc;
+    br.boot = boot;
+    br.n_rows = (uint32_t)boot->n_rows;
+  }
+  if (prm->compounding != MCP_COMPOUND_SIMPLE) return fail(MCP_E_UNSUPPORTED, "rebalanced paths compound simply (no log compounding)");
+  if (prm->flags & (MCP_FLAG_FOLD | MCP_FLAG_NATIVE_MATH))
+    return fail(MCP_E_UNSUPPORTED, "rebalanced paths run on the unfolded recurrence and the spec's normals (no MCP_FLAG_FOLD / MCP_FLAG_NATIVE_MATH)");
+  HzReq hz;
+  if (n_horizons == 0) {
+    if (n_levels != 0 || horizon_out || hz_stats_out || bands_out)
+      return fail(MCP_E_ARG, "n_horizons = 0: n_levels must be 0 and horizon_out, hz_stats_out, bands_out NULL");
+  } else {
+    if (int rc = check_horizons(prm->n_steps, n_horizons, horizons)) return rc;
+    if (int rc = check_levels(n_levels, levels)) return rc;
+    if (!hz_stats_out) return fail(MCP_E_ARG, "hz_stats_out is NULL");
+    if ((bands_out == nullptr) != (n_levels == 0)) return fail(MCP_E_ARG, "bands_out must be NULL exactly when n_levels == 0");
+    hz.H = n_horizons;
+    hz.L = n_levels;
+    hz.steps = horizons;
+    hz.levels = levels;
+    hz.out = horizon_out;
+    hz.stats_out = hz_stats_out;
+    hz.bands_out = bands_out;
+  }
+  if (!W || !stats_out) return fail(MCP_E_ARG, "NULL pointer");
+  if (n_paths < 1) return fail(MCP_E_ARG, "n_paths must be >= 1");
+  return simulate_impl(c, prm, mu, chol, W, seed, path_begin, n_paths, terminal_out, stats_out, false, nullptr, nullptr,
+                       n_horizons ? &hz : nullptr, boot ? &br : nullptr, &rr);
 }
 
 int mcp_sweep_historical(mcp_ctx* c, int N, int R, int P, const double* returns, const double* mean, const double* cov,

@@ -29,6 +29,13 @@
 #define MCP_MIN_WAVES_BIG 1 // the same for 16 < N <= 64, one portfolio.  4 (<= 128 VGPRs) was measured: the 64 live normals plus the
                             // Philox / transform state do not fit, 108-148 B per lane spill into the step loop, -10 % (profiles/r03_lab_n64.txt)
 #endif
+#ifndef MCP_MIN_WAVES_REB
+#define MCP_MIN_WAVES_REB 5 // the rebalancing kernel (N <= 16, one portfolio) holds the N4 returns B since the last rebalance on top: at
+                            // 6 waves (80 VGPRs) it spilled 20 dwords into its step loop; at 5 it gets 96, no scratch in the loop
+#endif
+#ifndef MCP_MIN_WAVES_REB8
+#define MCP_MIN_WAVES_REB8 4 // the same for 8 portfolios, N <= 16: unbounded it took 137 VGPRs (3 waves); at 4 it gets 128, no scratch in the loop
+#endif
 #ifndef MCP_EXP_VKEYS
 #define MCP_EXP_VKEYS 1
 #endif
@@ -97,6 +104,14 @@ struct PathArgsBTHZ : PathArgsHZ { BootArgs bt; };
 __device__ __forceinline__ BootArgs boot_args(const PathArgs&) { return BootArgs{}; }
 __device__ __forceinline__ BootArgs boot_args(const PathArgsBT& a) { return a.bt; }
 __device__ __forceinline__ BootArgs boot_args(const PathArgsBTHZ& a) { return a.bt; }
+// Arguments of mc_paths_reb_kernel (SPEC.md 4.5): the horizons of PathArgsHZ (n_horizons = 0: none), the row table of the
+// bootstrap (read only when BOOT) and the rebalancing rule.
+struct PathArgsRB : PathArgsHZ {
+  BootArgs bt;
+  int32_t period;                     // m >= 0: a rebalance after every step s with s mod m == 0 and s < T (0: never)
+  float cost;                         // kappa32 = fl32(kappa), in [0, 1)
+};
+__device__ __forceinline__ BootArgs boot_args(const PathArgsRB& a) { return a.bt; }
 
 // The LDS copy of the row table takes the slot of the inverse-CDF table (ICDF_LDS_ENTRIES float4: the bootstrap needs neither
 // that table nor the drift copy in its padding): R rows of NB float4 fit when R * NB <= ICDF_LDS_ENTRIES (N = 16: 272 rows).
@@ -173,13 +188,17 @@ constexpr int PATH_BLOCK = 256;
 // DD: also track the running peak and the max drawdown of every (path, portfolio) through the step loop (SPEC.md 4.2) and
 // store q (simple: min V_t/P_t) or d (log: min S_t - P_t) next to V_T.  HZ: also store V_h at the horizons (SPEC.md 4.3).
 // BOOT: r is row j_t of the observed returns (SPEC.md 2.1 / 4.4) instead of mu + L z; BLDS: that table is read from LDS.
-// All five kernels are the body in mcp_paths_body.inc.
+// REB: the step updates the assets' returns since the last rebalance B instead of V; V moves at the rebalance dates only
+// (SPEC.md 4.5).  All six kernels are the body in mcp_paths_body.inc.
 #define MCP_PATHS_BOUNDS(NB, KT, PPT) \
   __launch_bounds__(PATH_BLOCK, (NB <= 4 && KT == 1 && PPT == 1) ? MCP_MIN_WAVES : ((KT == 1 && PPT == 1) ? MCP_MIN_WAVES_BIG : 1))
+#define MCP_REB_BOUNDS(NB, KT, PPT) \
+  __launch_bounds__(PATH_BLOCK, (NB <= 4 && PPT == 1) ? (KT == 1 ? MCP_MIN_WAVES_REB : MCP_MIN_WAVES_REB8) \
+                                                     : ((KT == 1 && PPT == 1) ? MCP_MIN_WAVES_BIG : 1))
 
 template <int NB, int KT, int PPT, bool NATIVE, bool FOLD = false, bool LOGC = false>
 __global__ void MCP_PATHS_BOUNDS(NB, KT, PPT) mc_paths_kernel(const PathArgs a) {
-  constexpr bool DD = false, HZ = false, BOOT = false, BLDS = false;
+  constexpr bool DD = false, HZ = false, BOOT = false, BLDS = false, REB = false;
 #include "mcp_paths_body.inc"
 }
 
@@ -187,7 +206,7 @@ __global__ void MCP_PATHS_BOUNDS(NB, KT, PPT) mc_paths_kernel(const PathArgs a) 
 // array: appended to PathArgs itself they would move the hidden kernel arguments (grid size) of every plain kernel.
 template <int NB, int KT, int PPT, bool LOGC>
 __global__ void MCP_PATHS_BOUNDS(NB, KT, PPT) mc_paths_dd_kernel(const PathArgsDD a) {
-  constexpr bool DD = true, HZ = false, NATIVE = false, FOLD = false, BOOT = false, BLDS = false;
+  constexpr bool DD = true, HZ = false, NATIVE = false, FOLD = false, BOOT = false, BLDS = false, REB = false;
 #include "mcp_paths_body.inc"
 }
 
@@ -195,7 +214,7 @@ __global__ void MCP_PATHS_BOUNDS(NB, KT, PPT) mc_paths_dd_kernel(const PathArgsD
 // at the horizons, V_h stored after each; V_T and the fused epilogue as in mc_paths_kernel.
 template <int NB, int KT, int PPT, bool LOGC>
 __global__ void MCP_PATHS_BOUNDS(NB, KT, PPT) mc_paths_hz_kernel(const PathArgsHZ a) {
-  constexpr bool DD = false, HZ = true, NATIVE = false, FOLD = false, BOOT = false, BLDS = false;
+  constexpr bool DD = false, HZ = true, NATIVE = false, FOLD = false, BOOT = false, BLDS = false, REB = false;
 #include "mcp_paths_body.inc"
 }
 
@@ -203,16 +222,25 @@ __global__ void MCP_PATHS_BOUNDS(NB, KT, PPT) mc_paths_hz_kernel(const PathArgsH
 // block per path-step for the row index, no normals, no Cholesky GEMV.  V_T and the fused epilogue as in mc_paths_kernel.
 template <int NB, int KT, int PPT, bool LOGC, bool BLDS>
 __global__ void MCP_PATHS_BOUNDS(NB, KT, PPT) mc_paths_boot_kernel(const PathArgsBT a) {
-  constexpr bool DD = false, HZ = false, NATIVE = false, FOLD = false, BOOT = true;
+  constexpr bool DD = false, HZ = false, NATIVE = false, FOLD = false, BOOT = true, REB = false;
 #include "mcp_paths_body.inc"
 }
 
 // The bootstrap kernel with the horizons of SPEC.md 4.3 (the segmented walk of mc_paths_hz_kernel).
 template <int NB, int KT, int PPT, bool LOGC, bool BLDS>
 __global__ void MCP_PATHS_BOUNDS(NB, KT, PPT) mc_paths_boot_hz_kernel(const PathArgsBTHZ a) {
-  constexpr bool DD = false, HZ = true, NATIVE = false, FOLD = false, BOOT = true;
+  constexpr bool DD = false, HZ = true, NATIVE = false, FOLD = false, BOOT = true, REB = false;
+#include "mcp_paths_body.inc"
+}
+// The rebalancing kernel (SPEC.md 4.5; simple compounding, Gaussian draws or, BOOT, the bootstrap's rows): the walk in segments
+// that end at the events -- rebalance dates, horizons, T -- where V^ = V (1 + W.B) is marked.  H = 0 is one segment, so one
+// kernel serves terminal-only and horizon calls.  V_T and the fused epilogue as in mc_paths_kernel.
+template <int NB, int KT, int PPT, bool BOOT, bool BLDS>
+__global__ void MCP_REB_BOUNDS(NB, KT, PPT) mc_paths_reb_kernel(const PathArgsRB a) {
+  constexpr bool DD = false, HZ = false, NATIVE = false, FOLD = false, LOGC = false, REB = true;
 #include "mcp_paths_body.inc"
 }
 #undef MCP_PATHS_BOUNDS
+#undef MCP_REB_BOUNDS
 
 }  // namespace mcp

@@ -1,9 +1,10 @@
 // mcp_paths_body.inc -- the body of the path kernels of mcp_paths.h, included textually by mc_paths_kernel (DD = HZ = false),
-// mc_paths_dd_kernel (DD = true), mc_paths_hz_kernel (HZ = true) and the bootstrap kernels mc_paths_boot_kernel (BOOT = true)
-// and mc_paths_boot_hz_kernel (BOOT = HZ = true); the step itself is mcp_paths_step.inc.  As a shared __device__ function the plain kernel's registers came out allocated differently;
+// mc_paths_dd_kernel (DD = true), mc_paths_hz_kernel (HZ = true), the bootstrap kernels mc_paths_boot_kernel (BOOT = true)
+// and mc_paths_boot_hz_kernel (BOOT = HZ = true) and the rebalancing kernel mc_paths_reb_kernel (REB = true, BOOT either);
+// the step itself is mcp_paths_step.inc.  As a shared __device__ function the plain kernel's registers came out allocated differently;
 // included, the DD = false kernel compiles to the same instructions as before the drawdown existed.  In scope: the template
-// parameters NB, KT, PPT, NATIVE, FOLD, LOGC, DD, HZ, BOOT, BLDS and the kernel argument `a` (PathArgs, or PathArgsDD /
-// PathArgsHZ / PathArgsBT / PathArgsBTHZ which start with one).  Without HZ the walk is the one loop it always was, so the plain and drawdown kernels keep their code.
+// parameters NB, KT, PPT, NATIVE, FOLD, LOGC, DD, HZ, BOOT, BLDS, REB and the kernel argument `a` (PathArgs, or PathArgsDD /
+// PathArgsHZ / PathArgsBT / PathArgsBTHZ / PathArgsRB which start with one).  Without HZ the walk is the one loop it always was, so the plain and drawdown kernels keep their code.
   constexpr int N4 = 4 * NB;
   // wave-uniform parameters through the constant address space -> s_load_dword* into SGPRs
   typedef const __attribute__((address_space(4))) float* cfloat_p;
@@ -74,6 +75,7 @@
     float V[PPT][KT];
     float Pk[PPT][KT], Qk[PPT][KT];                       // DD: running peak P and q (simple) / d (log)
     uint32_t jrow[PPT];                                   // BOOT: the row index j_t of SPEC.md 2.1
+    f32x2 Bs[PPT][N4 / 2];                                // REB: the assets' returns since the last rebalance (SPEC.md 4.5)
 #pragma unroll
     for (int e = 0; e < PPT; e++) {
       p[e] = tl * tile + (uint64_t)e * PATH_BLOCK + threadIdx.x;
@@ -83,13 +85,107 @@
 #pragma unroll
       for (int k = 0; k < KT; k++) V[e][k] = logc ? 0.0f : a.v0;
       if constexpr (BOOT) jrow[e] = 0u;                   // replaced at t = 0 (a restart)
+      if constexpr (REB) {
+#pragma unroll
+        for (int m = 0; m < N4 / 2; m++) Bs[e][m] = f32x2{0.0f, 0.0f};
+      }
       if constexpr (DD) {
 #pragma unroll
         for (int k = 0; k < KT; k++) { Pk[e][k] = -__builtin_inff(); Qk[e][k] = logc ? 0.0f : 1.0f; }
       }
     }
 
-    if constexpr (HZ) {
+    if constexpr (REB) {
+      // SPEC.md 4.5: the walk in segments that end at the events -- the next rebalance date nd, the next horizon, T.  Between
+      // events the step updates B only.  At an event: the mark rho^_k = W_k.B (i ascending) and V^_k = fma(V_k, rho^_k, V_k),
+      // the horizon store of V^, and at a date the trade (V_k = fma(V_k, rho'_k, V_k), B = +0) or, at T, V = V^.  The period,
+      // cost and horizons are read through the kernel-argument pointer where they are needed, wave-uniform (nothing held in
+      // SGPRs across the walk: the Cholesky factor lives there); every branch below is on wave-uniform values.
+      typedef const __attribute__((address_space(4))) PathArgsRB* crb_p;
+      const crb_p rk = (crb_p)__builtin_amdgcn_kernarg_segment_ptr();
+      int nd;                                              // the next rebalance date (s mod m == 0, s < T), T if none is left
+      {
+        crb_p rs = rk;
+        asm volatile("" : "+s"(rs));
+        const int per = rs->period;
+        nd = (per >= 1 && per < T) ? per : T;
+      }
+      int t = 0, hi = 0;
+      while (t < T) {
+        crb_p rs = rk;
+        asm volatile("" : "+s"(rs));
+        const int t_hz = hi < rs->n_horizons ? rs->steps[hi] : T;
+        const int t_end = min(nd, t_hz);
+        for (; t < t_end; t++) {
+#include "mcp_paths_step.inc"
+        }
+        float rh[PPT][KT], vh[PPT][KT];                    // rho^ and V^ at s = t
+        asm volatile("" : "+s"(Wk));
+#pragma unroll
+        for (int e = 0; e < PPT; e++)
+#pragma unroll
+          for (int k = 0; k < KT; k++) {
+            float acc = 0.0f;
+#pragma unroll
+            for (int m = 0; m < N4 / 2; m++) {
+              acc = fma32(Wk[k * N4 + 2 * m], Bs[e][m].x, acc);
+              acc = fma32(Wk[k * N4 + 2 * m + 1], Bs[e][m].y, acc);
+            }
+            rh[e][k] = acc;
+            vh[e][k] = fma32(V[e][k], acc, V[e][k]);
+          }
+        crb_p hs = rk;
+        asm volatile("" : "+s"(hs));
+        if (hi < hs->n_horizons && hs->steps[hi] == t) {   // V_h of SPEC.md 4.3, before any trade of step h (t_hz may be T with no
+                                                           // horizon left: the list is read again, nothing is stored then)
+          float* const row = hs->hz + (size_t)(hi * a.n_portfolios + a.k_begin) * hs->hz_stride;
+#pragma unroll
+          for (int e = 0; e < PPT; e++)
+            if (live[e]) {
+#pragma unroll
+              for (int k = 0; k < KT; k++)
+                if (k < kt) row[(size_t)k * hs->hz_stride + p[e]] = vh[e][k];
+            }
+          hi++;
+        }
+        if (t == T) {
+#pragma unroll
+          for (int e = 0; e < PPT; e++)
+#pragma unroll
+            for (int k = 0; k < KT; k++) V[e][k] = vh[e][k];
+        } else if (t == nd) {                              // a rebalance date: the trade back to W
+          crb_p cs = rk;
+          asm volatile("" : "+s"(cs));
+          const float kap = cs->cost;
+          if (kap > 0.0f) {                                // rho' = rho^ - kappa tau, tau = sum_i |W_ki| |B_i - rho^_k|
+            asm volatile("" : "+s"(Wk));
+#pragma unroll
+            for (int e = 0; e < PPT; e++)
+#pragma unroll
+              for (int k = 0; k < KT; k++) {
+                float tau = 0.0f;
+#pragma unroll
+                for (int m = 0; m < N4 / 2; m++) {
+                  tau = fma32(fabsf(Wk[k * N4 + 2 * m]), fabsf(Bs[e][m].x - rh[e][k]), tau);
+                  tau = fma32(fabsf(Wk[k * N4 + 2 * m + 1]), fabsf(Bs[e][m].y - rh[e][k]), tau);
+                }
+                V[e][k] = fma32(V[e][k], fma32(-kap, tau, rh[e][k]), V[e][k]);
+              }
+          } else {
+#pragma unroll
+            for (int e = 0; e < PPT; e++)
+#pragma unroll
+              for (int k = 0; k < KT; k++) V[e][k] = vh[e][k];
+          }
+#pragma unroll
+          for (int e = 0; e < PPT; e++)
+#pragma unroll
+            for (int m = 0; m < N4 / 2; m++) Bs[e][m] = f32x2{0.0f, 0.0f};
+          const int per = cs->period;
+          nd = per < T - t ? t + per : T;
+        }
+      }
+    } else if constexpr (HZ) {
       // SPEC.md 4.3: segment i runs the steps [h_{i-1}, h_i) with the unchanged step body and ends in one coalesced store
       // per live path and portfolio into row i*K + k of the horizon array; the last segment runs on to T.  The horizon
       // count, the steps and the array are read through the kernel-argument pointer, wave-uniform, where they are needed

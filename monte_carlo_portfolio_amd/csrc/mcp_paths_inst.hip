@@ -113,4 +113,20 @@ hipError_t MCP_CAT(launch_paths_bthz_nb, MCP_NB)(int variant, bool lds, const Pa
   return go_bt_any(variant, lds, args, grid, stream);
 }
 
+// The rebalancing kernel (mcp_simulate_rebalanced, SPEC.md 4.5): one portfolio or KT = 8 passes, simple compounding, Gaussian
+// draws or the bootstrap's row table in LDS or in global memory.
+template <int KT>
+static void go_rb(bool boot, bool lds, const PathArgsRB& args, int grid, hipStream_t stream) {
+  if (!boot) mc_paths_reb_kernel<MCP_NB, KT, 1, false, false><<<grid, PATH_BLOCK, lds_pad(), stream>>>(args);
+  else if (lds) mc_paths_reb_kernel<MCP_NB, KT, 1, true, true><<<grid, PATH_BLOCK, lds_pad(), stream>>>(args);
+  else mc_paths_reb_kernel<MCP_NB, KT, 1, true, false><<<grid, PATH_BLOCK, lds_pad(), stream>>>(args);
+}
+
+hipError_t MCP_CAT(launch_paths_rb_nb, MCP_NB)(int variant, bool boot, bool lds, const PathArgsRB& args, int grid, hipStream_t stream) {
+  if (variant != 0 && variant != VAR_KT8) return hipErrorInvalidValue;
+  if (variant == VAR_KT8) go_rb<8>(boot, lds, args, grid, stream);
+  else go_rb<1>(boot, lds, args, grid, stream);
+  return hipGetLastError();
+}
+
 }  // namespace mcp

@@ -1,6 +1,8 @@
 // mcp_paths_step.inc -- one step t of the path kernels' walk (mcp_paths_body.inc, included in its step loops): the normals of
 // step t, r = mu + L z (BOOT: r = row j_t of the observed returns), rho = w.r, the update of V (and, DD, of the running peak
-// and drawdown state).  In scope: everything mcp_paths_body.inc declares before its step loops, and t.
+// and drawdown state).  REB: no rho and no V; the returns since the last rebalance B_i = B_i + r_i + B_i r_i instead
+// (SPEC.md 4.5), a = B + r then B = fma(B, r, a), one v_pk_add_f32 and one v_pk_fma_f32 per pair of assets.  In scope:
+// everything mcp_paths_body.inc declares before its step loops, and t.
       float rho[PPT][KT];
       if constexpr (BOOT) {
         // SPEC.md 2.1 / 4.4: one Philox block on counter (t, 1, p_lo, p_hi); j_t = mulhi(x0, R) on a restart (t = 0 or
@@ -24,6 +26,15 @@
 #pragma unroll
             for (int q = 0; q < NB; q++) r4[q] = src[q];
           }
+          if constexpr (REB) {
+#pragma unroll
+            for (int q = 0; q < NB; q++) {
+              const f32x2 r0 = {r4[q].x, r4[q].y}, r1 = {r4[q].z, r4[q].w};
+              const f32x2 a0 = Bs[e][2 * q] + r0, a1 = Bs[e][2 * q + 1] + r1;
+              Bs[e][2 * q] = __builtin_elementwise_fma(Bs[e][2 * q], r0, a0);
+              Bs[e][2 * q + 1] = __builtin_elementwise_fma(Bs[e][2 * q + 1], r1, a1);
+            }
+          } else {
 #pragma unroll
           for (int k = 0; k < KT; k++) {
             float acc = 0.0f;
@@ -36,6 +47,7 @@
             }
             rho[e][k] = acc;
           }
+          }  // !REB
         }
       } else {
       // keep the (loop-invariant) parameter loads inside the step: hoisted, they would pin ~170 registers
@@ -86,6 +98,13 @@
 #pragma unroll
           for (int e = 0; e < PPT; e++) acc[e] = __builtin_elementwise_fma(l2, (f32x2){z[e][j], z[e][j]}, acc[e]);
         }
+        if constexpr (REB) {
+#pragma unroll
+          for (int e = 0; e < PPT; e++) {
+            const f32x2 a2 = Bs[e][m] + acc[e];
+            Bs[e][m] = __builtin_elementwise_fma(Bs[e][m], acc[e], a2);
+          }
+        } else {
 #pragma unroll
         for (int h = 0; h < 2; h++) {
           const int i = 2 * m + h;
@@ -96,14 +115,17 @@
             for (int e = 0; e < PPT; e++) rho[e][k] = fma32(wki, h ? acc[e].y : acc[e].x, rho[e][k]);
           }
         }
+        }  // !REB
       }
       }  // !FOLD
       }  // !BOOT
+      if constexpr (!REB) {
 #pragma unroll
       for (int e = 0; e < PPT; e++)
 #pragma unroll
         for (int k = 0; k < KT; k++)
           V[e][k] = logc ? (V[e][k] + rho[e][k]) : fma32(V[e][k], rho[e][k], V[e][k]);
+      }
       if constexpr (DD) {
         // SPEC.md 4.2: P = fmax(P, V_t); q = fminf(q, V_t / P) (IEEE division) or d = fminf(d, S_t - P).  fminf is IEEE
         // minNum: the 0/0 of a zero peak is ignored.

@@ -144,6 +144,53 @@ class Context:
         return stats, hz_stats, bands, term, hz_term
 
 
+    def simulate_rebalanced(self, prm: _ffi.McpParams, period: int, cost: float, W, seed: int, path_begin: int, n_paths: int,
+                            store: bool, mu=None, chol=None, rows=None, block: float = 1.0, horizons=None, levels=()):
+        """simulate() / simulate_horizons() / simulate_bootstrap[_horizons]() with the weights rebalanced every `period` steps
+        (0: bought and held) at the proportional cost `cost` (SPEC.md 4.5 / 5.4; include/mcport.h, mcp_simulate_rebalanced).
+        Draws: `mu` and `chol` (Gaussian) or `rows` and `block` (bootstrap).  -> (stats [K], hz_stats [H, K], bands [H, K, L],
+        terminal, horizon_terminal) as simulate_horizons; the horizon entries are None without horizons."""
+        K = prm.n_portfolios
+        stats = np.zeros(K, _ffi.STATS_DTYPE)
+        term = np.empty((K, n_paths), np.float32) if store else None
+        ptr = lambda a: a.ctypes.data_as(ctypes.c_void_p) if a is not None else None   # noqa: E731
+        hz_stats = bands = hz_term = steps = lv = None
+        H = L = 0
+        if horizons is not None:
+            steps = np.ascontiguousarray(horizons, np.int32).ravel()
+            lv = np.ascontiguousarray(levels, np.float64).ravel()
+            H, L = steps.size, lv.size
+            hz_stats = np.zeros((H, K), _ffi.STATS_DTYPE)
+            bands = np.zeros((H, K, L), np.float64)
+            hz_term = np.empty((H, K, n_paths), np.float32) if store else None
+        rb = _ffi.McpRebalance(int(period), 0, float(cost))
+        bt = _ffi.make_bootstrap(rows, block) if rows is not None else None
+        _ffi.check(_ffi.lib().mcp_simulate_rebalanced(
+            self._h, ctypes.byref(prm), ctypes.byref(rb), ptr(mu), ptr(chol), ctypes.byref(bt) if bt is not None else None, W, seed,
+            path_begin, n_paths, H, ptr(steps) if H else None, L, ptr(lv) if L else None, ptr(term), ptr(stats), ptr(hz_term),
+            ptr(hz_stats), ptr(bands) if L else None))
+        return stats, hz_stats, bands, term, hz_term
+
+
+def check_rebalance(rebalance, rebalance_cost):
+    """SPEC.md 4.5 argument rules -> (period, cost): period None (constant weights, no rebalancing), 0 (rebalance="never": bought
+    and held) or the int k >= 1 of rebalance=k (traded back to the weights every k steps); cost in [0, 1).  ValueError otherwise."""
+    if isinstance(rebalance_cost, (bool, np.bool_)) or not isinstance(rebalance_cost, (int, float, np.integer, np.floating)):
+        raise ValueError(f"rebalance_cost must be a number in [0, 1), got {rebalance_cost!r}")
+    cost = float(rebalance_cost)
+    if not 0.0 <= cost < 1.0:
+        raise ValueError(f"rebalance_cost must be in [0, 1), got {rebalance_cost!r}")
+    if rebalance is None:
+        if cost != 0.0:
+            raise ValueError("rebalance_cost needs rebalance (an int period >= 1 or 'never'): constant weights trade for free")
+        return None, 0.0
+    if isinstance(rebalance, str) and rebalance == "never":
+        return 0, cost
+    if isinstance(rebalance, (bool, np.bool_)) or not isinstance(rebalance, (int, np.integer)) or not 1 <= rebalance <= 2**31 - 1:
+        raise ValueError(f"rebalance must be a whole number of steps >= 1 or 'never', got {rebalance!r}")
+    return int(rebalance), cost
+
+
 def check_horizons(horizons, bands, n_steps):
     """SPEC.md 4.3 / 5.2 argument rules -> (steps int32 [H], levels float64 [L]); ValueError otherwise."""
     h = np.asarray(horizons)
@@ -234,7 +281,7 @@ def drawdown_to_dict(rec) -> dict:
 def simulate_paths(mu, cov, weights, n_steps=252, n_paths=10_000, seed=0, v0=1.0, compounding="simple",
                    rf=0.0, alpha=0.95, devices=None, store=False, path_begin=0, chol=None,
                    native_math=False, as_array=False, fold=False, shard="auto", context=None, drawdown=False,
-                   horizons=None, bands=()):
+                   horizons=None, bands=(), rebalance=None, rebalance_cost=0.0):
     """Simulate `n_paths` correlated return paths and reduce them to risk statistics.
 
     mu [N], cov [N,N] are per-step mean and covariance (the reference's `mean_returns`, `cov_matrix`
@@ -258,7 +305,18 @@ def simulate_paths(mu, cov, weights, n_steps=252, n_paths=10_000, seed=0, v0=1.0
     Every dict gains 'horizons' {steps, levels, bands [H, L], mean, std, var, cvar, min, max, n_tail [H]} and, with store=True,
     'horizon_terminal' (float32 [H, n_paths], raw V_h / S_h).  as_array=True returns (stats, hz_stats [H, K], bands [H, K, L])
     [+ (terminal, horizon_terminal [H, K, n_paths]) with store].  Not with drawdown, fold or native_math (ValueError).
+
+    rebalance=None (default): constant weights, the portfolio traded back to `weights` after every step for free (SPEC.md 4).
+    rebalance=k (int >= 1): the holdings drift with the prices and are traded back to `weights` every k steps; rebalance="never":
+    bought and held; rebalance_cost: the proportional cost in [0, 1) of the fraction traded, paid out of the portfolio (SPEC.md
+    4.5, simple compounding only).  The result has the shape of the same call without it, horizons and bands included (pivots of
+    SPEC.md 5.4); rebalance=1 with no cost gives the constant-weight values bit for bit, on the rebalancing kernel.  Not with
+    drawdown, fold, native_math or compounding="log" (ValueError).
     """
+    period, cost = check_rebalance(rebalance, rebalance_cost)
+    if period is not None and (drawdown or fold or native_math or compounding == "log"):
+        raise ValueError("rebalance needs simple compounding, the spec's normals and the unfolded recurrence: not with drawdown, fold, "
+                         "native_math or compounding='log'")
     if drawdown and (fold or native_math):
         raise ValueError("drawdown=True needs the spec's normals and the unfolded recurrence: not with fold or native_math")
     if horizons is not None:
@@ -275,7 +333,15 @@ def simulate_paths(mu, cov, weights, n_steps=252, n_paths=10_000, seed=0, v0=1.0
     by_portfolio = len(devs) > 1 and (shard == "portfolios" or (shard == "auto" and W.shape[0] >= 512 * len(devs)))
     prm = _ffi.make_params(mu32.shape[0], n_steps, W.shape[0], compounding, v0, alpha, rf, native_math, fold, by_portfolio)
     ctx = context if context is not None else default_context(devs)
-    if horizons is not None:
+    if period is not None:
+        stats, hz_stats, hz_bands, term, hz_term = ctx.simulate_rebalanced(
+            prm, period, cost, W, int(seed), int(path_begin), int(n_paths), store, mu=mu32, chol=L,
+            horizons=steps if horizons is not None else None, levels=levels if horizons is not None else ())
+        if as_array:
+            if horizons is not None:
+                return (stats, hz_stats, hz_bands, term, hz_term) if store else (stats, hz_stats, hz_bands)
+            return (stats, term) if store else stats
+    elif horizons is not None:
         stats, hz_stats, hz_bands, term, hz_term = ctx.simulate_horizons(prm, mu32, L, W, int(seed), int(path_begin), int(n_paths),
                                                                         steps, levels, store)
         if as_array:
@@ -332,7 +398,7 @@ def bootstrap_inputs(returns, weights):
 
 def simulate_bootstrap(returns, weights, n_steps=252, n_paths=10_000, block=1.0, seed=0, v0=1.0, compounding="simple",
                        rf=0.0, alpha=0.95, devices=None, store=False, path_begin=0, as_array=False, shard="auto", context=None,
-                       horizons=None, bands=(), **unsupported):
+                       horizons=None, bands=(), rebalance=None, rebalance_cost=0.0, **unsupported):
     """simulate_paths on paths resampled from the observed return rows instead of a normal model: the stationary block
     bootstrap of Politis & Romano (SPEC.md 2.1 / 4.4).  Every step of a path uses one whole row of `returns` (all assets of one
     date together), so fat tails, skew, the co-movement within a row and -- with a mean block length `block` > 1 -- short-range
@@ -342,11 +408,15 @@ def simulate_bootstrap(returns, weights, n_steps=252, n_paths=10_000, block=1.0,
     returns: DataFrame (returns_matrix(...), app.py:667) or [R, N] array of per-step returns, finite, R <= 2^20; weights [N]
     or [K, N].  Returns exactly what simulate_paths returns for the same arguments, 'horizons' block included (pivots of
     SPEC.md 5.3).  ValueError for NaN rows, a width that does not match the weights, block < 1, or the simulate_paths keywords
-    that have no meaning here (fold, native_math, drawdown, chol).
+    that have no meaning here (fold, native_math, drawdown, chol).  rebalance / rebalance_cost as in simulate_paths (SPEC.md 4.5,
+    pivots of SPEC.md 5.4; not with compounding="log").
     """
     if unsupported:
         raise ValueError(f"simulate_bootstrap does not take {sorted(unsupported)} (no normals: no fold / native_math; "
                          "drawdown on bootstrap paths is not supported)")
+    period, cost = check_rebalance(rebalance, rebalance_cost)
+    if period is not None and compounding == "log":
+        raise ValueError("rebalance needs simple compounding: not with compounding='log'")
     b = float(block)
     if not b >= 1.0:
         raise ValueError(f"block (mean block length) must be >= 1 or inf, got {block!r}")
@@ -362,7 +432,15 @@ def simulate_bootstrap(returns, weights, n_steps=252, n_paths=10_000, block=1.0,
     by_portfolio = len(devs) > 1 and (shard == "portfolios" or (shard == "auto" and W.shape[0] >= 512 * len(devs)))
     prm = _ffi.make_params(rows.shape[1], n_steps, W.shape[0], compounding, v0, alpha, rf, False, False, by_portfolio)
     ctx = context if context is not None else default_context(devs)
-    if horizons is not None:
+    if period is not None:
+        stats, hz_stats, hz_bands, term, hz_term = ctx.simulate_rebalanced(
+            prm, period, cost, W, int(seed), int(path_begin), int(n_paths), store, rows=rows, block=b,
+            horizons=steps if horizons is not None else None, levels=levels if horizons is not None else ())
+        if as_array:
+            if horizons is not None:
+                return (stats, hz_stats, hz_bands, term, hz_term) if store else (stats, hz_stats, hz_bands)
+            return (stats, term) if store else stats
+    elif horizons is not None:
         stats, hz_stats, hz_bands, term, hz_term = ctx.simulate_bootstrap_horizons(
             prm, rows, W, b, int(seed), int(path_begin), int(n_paths), steps, levels, store)
         if as_array:
