@@ -89,9 +89,14 @@ with tab_sweep:                                               # app.py:655-783
     # model: hedged (option-overlay) rows keep their floor and cap here
     boot = mcp.simulate_bootstrap(returns_df, w, n_steps=annual_factor, n_paths=n_paths, block=3.0, seed=12345,
                                   v0=state["investment_amount"], rf=user_rf / 100.0)
+    # and on fat-tailed Student-t steps with the normal model's mean and covariance, nu fitted to the rows (SPEC.md 2.2 / 4.6)
+    nu = mcp.fit_student_t_dof(returns_df)
+    tsim = mcp.simulate_paths(mu_step, cov_step, w, n_steps=annual_factor, n_paths=n_paths, seed=12345,
+                              v0=state["investment_amount"], rf=user_rf / 100.0, dof=nu)
     keys = ("mean", "std", "sharpe", "var", "cvar", "min", "max")
-    st.subheader("normal model vs. bootstrap of the observed rows (mean block 3)")
-    st.write({"normal model (mean / cov)": {k: sim[k] for k in keys}, "bootstrap of the observed rows": {k: boot[k] for k in keys}})
+    st.subheader("normal model vs. bootstrap of the observed rows (mean block 3) vs. Student-t")
+    st.write({"normal model (mean / cov)": {k: sim[k] for k in keys}, "bootstrap of the observed rows": {k: boot[k] for k in keys},
+              f"Student-t (ν = {nu}, fitted)": {k: tsim[k] for k in keys}})
     # the same allocation as a purchase: bought and held, or traded back to the weights every few periods at a proportional cost
     # of the amount traded (SPEC.md 4.5), instead of the free rebalance after every period of the paths above
     choices = ["never (buy and hold)", "every period", "every 3 periods", "every 6 periods"]

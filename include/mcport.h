@@ -26,12 +26,14 @@ extern "C" {
 #define MCP_ABI_VERSION 4        /* 4: + mcp_simulate_drawdown, mcp_launch_paths_drawdown (additive); + mcp_simulate_horizons,
                                     mcp_launch_paths_horizons, mcp_percentile_rank_q (additive, detected by symbol);
                                     + mcp_simulate_bootstrap[_horizons], mcp_bootstrap_pivots (additive, detected by symbol);
-                                    + mcp_simulate_rebalanced, mcp_rebalance_pivots (additive, detected by symbol) */
+                                    + mcp_simulate_rebalanced, mcp_rebalance_pivots (additive, detected by symbol);
+                                    + mcp_simulate_student_t (additive, detected by symbol) */
 #define MCP_MAX_ASSETS 64        /* thread-per-path kernels are instantiated for N4 = 4..64 */
 #define MCP_SELECT_BINS 2048     /* radix-select digit: 11 + 11 + 10 bits */
 #define MCP_MAX_HORIZONS 64      /* mcp_simulate_horizons: horizon steps per call */
 #define MCP_MAX_LEVELS 16        /* mcp_simulate_horizons: band levels per call */
 #define MCP_MAX_BOOT_ROWS (1 << 20) /* mcp_simulate_bootstrap: observed return rows per call */
+#define MCP_MAX_T_DOF 32         /* mcp_simulate_student_t: degrees of freedom in [3, MCP_MAX_T_DOF] */
 
 enum {
     MCP_OK = 0,
@@ -254,6 +256,35 @@ int mcp_simulate_rebalanced(mcp_ctx *ctx, const mcp_params *prm, const mcp_rebal
  * is ignored. */
 int mcp_rebalance_pivots(const mcp_params *prm, const mcp_rebalance *reb, const float *mu, const mcp_bootstrap *boot,
                          const float *W, double *pivots_out /* [K] */);
+
+/* Fat-tailed draws: the multivariate Student-t with nu degrees of freedom, a normal variance mixture (SPEC.md 2.2 / 4.6).  dof:
+ * an integer nu in [3, MCP_MAX_T_DOF]; reserved must be 0. */
+typedef struct {
+    int32_t dof;
+    int32_t reserved;
+} mcp_student_t;
+
+/* mcp_simulate / mcp_simulate_drawdown / mcp_simulate_horizons with every step's normals z scaled by s = sqrt((nu - 2) / chi),
+ * chi the sum of nu squared normals of a counter stream of its own (SPEC.md 2.2 / 4.6; simple compounding only): r = mu + L s z
+ * has the mean mu and the covariance L L^T of the Gaussian call, fat tails (excess kurtosis 6 / (nu - 4) for nu > 4) and
+ * assets that crash together.  The asset normals are the Gaussian call's own (common random numbers with the same seed).
+ * dd_stats_out non-NULL: the drawdown of mcp_simulate_drawdown (mdd_out NULL or host [K*n_paths] q); n_horizons > 0: the
+ * horizons, records and bands of mcp_simulate_horizons (n_horizons = 0: horizons ignored, n_levels = 0, horizon_out,
+ * hz_stats_out and bands_out NULL); not both (MCP_E_UNSUPPORTED).  The moments are pivoted as mcp_pivots (SPEC.md 5).
+ * Argument errors (MCP_E_ARG: nu out of range, reserved != 0, n_steps * ceil(nu/4) >= 2^32, NULL pointers) are found before
+ * any device is touched; log compounding, MCP_FLAG_FOLD, MCP_FLAG_NATIVE_MATH: MCP_E_UNSUPPORTED.  Costs: ceil(nu/4) more
+ * Philox blocks and normals per step; K >= 17 runs as passes of 8 portfolios. */
+int mcp_simulate_student_t(mcp_ctx *ctx, const mcp_params *prm, const mcp_student_t *st,
+                           const float *mu, const float *chol, const float *W,
+                           uint64_t seed, uint64_t path_begin, uint64_t n_paths,
+                           int n_horizons, const int32_t *horizons, int n_levels, const double *levels,
+                           float *terminal_out,        /* NULL or host [K*n_paths] */
+                           mcp_stats *stats_out,       /* [K] */
+                           float *mdd_out,             /* NULL or host [K*n_paths]; needs dd_stats_out */
+                           mcp_stats *dd_stats_out,    /* [K], or NULL: no drawdown */
+                           float *horizon_out,         /* NULL or host [H*K*n_paths], row h*K + k */
+                           mcp_stats *hz_stats_out,    /* [H*K], NULL iff n_horizons == 0 */
+                           double *bands_out);         /* [H*K*L], NULL iff n_levels == 0 */
 
 /* The reference's own sweep (app.py:699-717) over HISTORICAL returns, loop body app.py:708-713 for P weight
  * vectors at once, binary64 like the reference.  returns: [R*N] row-major (returns_df.values, app.py:667),

@@ -23,6 +23,7 @@ MCP_SELECT_BINS = 2048
 MCP_MAX_HORIZONS = 64
 MCP_MAX_LEVELS = 16
 MCP_MAX_BOOT_ROWS = 1 << 20
+MCP_MAX_T_DOF = 32
 MCP_COMPOUND = {"simple": 0, "log": 1}
 MCP_FLAG_NATIVE_MATH = 1
 MCP_FLAG_FOLD = 2
@@ -62,6 +63,11 @@ class McpBootstrap(ctypes.Structure):
 class McpRebalance(ctypes.Structure):
     """mcp_rebalance: the rebalancing rule of SPEC.md 4.5 (period 0: never, buy-and-hold; cost: proportional, in [0, 1))."""
     _fields_ = [("period", ctypes.c_int32), ("reserved", ctypes.c_int32), ("cost", ctypes.c_double)]
+
+
+class McpStudentT(ctypes.Structure):
+    """mcp_student_t: the degrees of freedom nu in [3, MCP_MAX_T_DOF] of Student-t draws (SPEC.md 2.2)."""
+    _fields_ = [("dof", ctypes.c_int32), ("reserved", ctypes.c_int32)]
 
 
 STATS_DTYPE = np.dtype([
@@ -120,6 +126,8 @@ SIGNATURES = {
     "mcp_simulate_rebalanced": (_int, [_vp, _PP, ctypes.POINTER(McpRebalance), _vp, _vp, ctypes.POINTER(McpBootstrap), _f32p, _u64, _u64,
                                        _u64, _int, _vp, _int, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mcp_rebalance_pivots": (_int, [_PP, ctypes.POINTER(McpRebalance), _vp, ctypes.POINTER(McpBootstrap), _f32p, _f64p]),
+    "mcp_simulate_student_t": (_int, [_vp, _PP, ctypes.POINTER(McpStudentT), _vp, _vp, _vp, _u64, _u64, _u64, _int, _vp, _int, _vp, _vp,
+                                      _vp, _vp, _vp, _vp, _vp, _vp]),
     "mcp_percentile_rank_q": (_int, [_u64, ctypes.c_double, ctypes.POINTER(_u64), ctypes.POINTER(_u64),
                                      ctypes.POINTER(ctypes.c_double)]),
     "mcp_percentile_rank": (_int, [_u64, ctypes.c_double, ctypes.POINTER(_u64), ctypes.POINTER(_u64),

@@ -133,6 +133,11 @@ const mcp::launch_paths_rb_fn k_launch_rb[16] = {
     mcp::launch_paths_rb_nb5,  mcp::launch_paths_rb_nb6,  mcp::launch_paths_rb_nb7,  mcp::launch_paths_rb_nb8,
     mcp::launch_paths_rb_nb9,  mcp::launch_paths_rb_nb10, mcp::launch_paths_rb_nb11, mcp::launch_paths_rb_nb12,
     mcp::launch_paths_rb_nb13, mcp::launch_paths_rb_nb14, mcp::launch_paths_rb_nb15, mcp::launch_paths_rb_nb16};
+const mcp::launch_paths_t_fn k_launch_t[16] = {
+    mcp::launch_paths_t_nb1,  mcp::launch_paths_t_nb2,  mcp::launch_paths_t_nb3,  mcp::launch_paths_t_nb4,
+    mcp::launch_paths_t_nb5,  mcp::launch_paths_t_nb6,  mcp::launch_paths_t_nb7,  mcp::launch_paths_t_nb8,
+    mcp::launch_paths_t_nb9,  mcp::launch_paths_t_nb10, mcp::launch_paths_t_nb11, mcp::launch_paths_t_nb12,
+    mcp::launch_paths_t_nb13, mcp::launch_paths_t_nb14, mcp::launch_paths_t_nb15, mcp::launch_paths_t_nb16};
 
 // SPEC.md 4.3: 1..MCP_MAX_HORIZONS strictly increasing steps in [1, n_steps]
 int check_horizons(int n_steps, int H, const int32_t* steps) {
@@ -219,6 +224,23 @@ int check_reb(const mcp_rebalance* reb, RebReq* out) {
     out->period = reb->period;
     out->cost = (float)reb->cost;
   }
+  return MCP_OK;
+}
+
+// The Student-t draws of a launch (SPEC.md 2.2): nu in [3, MCP_MAX_T_DOF].
+struct StReq {
+  int32_t dof = 0;
+};
+
+// SPEC.md 2.2: 3 <= nu <= MCP_MAX_T_DOF, reserved == 0, (uint64)T ceil(nu/4) < 2^32 (the counter of stream 2)
+int check_student_t(const mcp_params* prm, const mcp_student_t* st, StReq* out) {
+  if (!st) return fail(MCP_E_ARG, "student_t is NULL");
+  if (st->dof < 3 || st->dof > MCP_MAX_T_DOF) return fail(MCP_E_ARG, "dof=%d outside [3,%d]", st->dof, MCP_MAX_T_DOF);
+  if (st->reserved != 0) return fail(MCP_E_ARG, "student_t reserved=%d must be 0", st->reserved);
+  if ((uint64_t)prm->n_steps * (uint64_t)((st->dof + 3) / 4) > 0xFFFFFFFFull)
+    return fail(MCP_E_ARG, "n_steps * ceil(dof/4) = %llu exceeds the 32-bit Philox block counter of stream 2",
+                (unsigned long long)((uint64_t)prm->n_steps * (uint64_t)((st->dof + 3) / 4)));
+  if (out) out->dof = st->dof;
   return MCP_OK;
 }
 
@@ -558,7 +580,7 @@ struct BootIn {
 static int launch_paths_impl(const mcp_params* prm, const float* d_packed, const double* d_pivot, uint64_t seed, uint64_t path_begin,
                              uint64_t n_paths, float* d_terminal, uint64_t stride, float* d_mdd, uint64_t mdd_stride, void* d_partials,
                              void* d_hist, void* stream, const HzOut* hz = nullptr, const BootIn* boot = nullptr,
-                             const RebReq* reb = nullptr) {
+                             const RebReq* reb = nullptr, const StReq* st = nullptr) {
   const bool dd = d_mdd != nullptr;
   if (int rc = check_params(prm)) return rc;
   if (!d_packed || !d_terminal) return fail(MCP_E_ARG, "NULL device pointer");
@@ -588,6 +610,14 @@ static int launch_paths_impl(const mcp_params* prm, const float* d_packed, const
       return fail(MCP_E_UNSUPPORTED, "rebalanced paths run on the unfolded recurrence and the spec's normals (no MCP_FLAG_FOLD / MCP_FLAG_NATIVE_MATH)");
     if (reb->period < 0 || !(reb->cost >= 0.0f && reb->cost <= 1.0f)) return fail(MCP_E_ARG, "bad rebalancing rule");
   }
+  if (st) {
+    if (boot || reb) return fail(MCP_E_UNSUPPORTED, "Student-t draws are not combined with the bootstrap or rebalancing");
+    if (prm->compounding != MCP_COMPOUND_SIMPLE) return fail(MCP_E_UNSUPPORTED, "Student-t paths compound simply (no log compounding)");
+    if (prm->flags & (MCP_FLAG_FOLD | MCP_FLAG_NATIVE_MATH))
+      return fail(MCP_E_UNSUPPORTED, "Student-t paths run on the spec's normals and the unfolded recurrence (no MCP_FLAG_FOLD / MCP_FLAG_NATIVE_MATH)");
+    if (st->dof < 3 || st->dof > MCP_MAX_T_DOF || (uint64_t)prm->n_steps * (uint64_t)((st->dof + 3) / 4) > 0xFFFFFFFFull)
+      return fail(MCP_E_ARG, "bad Student-t request");
+  }
   if ((d_partials == nullptr) != (d_hist == nullptr)) return fail(MCP_E_ARG, "d_partials and d_hist go together (both or neither)");
   if (n_paths < 1) return fail(MCP_E_ARG, "n_paths must be >= 1");
   if (stride < n_paths) return fail(MCP_E_ARG, "terminal_stride %llu < n_paths %llu",
@@ -612,14 +642,14 @@ static int launch_paths_impl(const mcp_params* prm, const float* d_packed, const
   DeviceGuard guard(dev);                 // the stream may belong to another device than the thread's current one
   if (guard.err != hipSuccess) return fail(MCP_E_HIP, "hipSetDevice(%d): %s", dev, hipGetErrorString(guard.err));
   if (int rc = device_tables(dev, (hipStream_t)stream, &tables)) return rc;
-  const bool sweep = !dd && !hz && !boot && !reb && uses_sweep(K);
+  const bool sweep = !dd && !hz && !boot && !reb && !st && uses_sweep(K);
   a.tables = tables;
   a.packed = d_packed;
   a.terminal = d_terminal;
   a.pivot = d_pivot;
   a.partials = (mcp::MomentPartial*)d_partials;
   a.hist = sweep ? nullptr : (unsigned long long*)d_hist;     // the sweep kernels leave digit 0 to hist(0) below
-  a.slots = (dd || hz || boot || reb) ? mcp_moment_slots(K, n_paths) : mcp::moment_slots(sweep, n_paths);
+  a.slots = (dd || hz || boot || reb || st) ? mcp_moment_slots(K, n_paths) : mcp::moment_slots(sweep, n_paths);
   a.v0d = (double)(float)prm->v0;
   a.inv_v0d = 1.0 / a.v0d;
   { int e = 0; a.v0_pow2 = std::frexp(a.v0d, &e) == 0.5; }
@@ -651,9 +681,40 @@ static int launch_paths_impl(const mcp_params* prm, const float* d_packed, const
     }
     return MCP_OK;
   }
-  if ((dd || hz || boot || reb) && d_partials && a.slots > (uint64_t)grid)
+  if ((dd || hz || boot || reb || st) && d_partials && a.slots > (uint64_t)grid)
     HIP_TRY(mcp::launch_pass0(*prm, K, d_terminal, stride, 0, nullptr, a.slots, (mcp::MomentPartial*)d_partials,
                               (unsigned long long*)d_hist, (hipStream_t)stream));
+  if (st) {                               // SPEC.md 2.2 / 4.6: the t twin of the plain, drawdown or horizon kernel
+    mcp::StudentArgs sa;
+    sa.dof = st->dof;
+    sa.pad = 0;
+    mcp::PathArgsT at;
+    mcp::PathArgsTDD ad;
+    mcp::PathArgsTHZ ah;
+    if (hz) {
+      static_cast<mcp::PathArgs&>(ah) = a;
+      ah.hz = hz->d_out;
+      ah.hz_stride = hz->stride;
+      ah.n_horizons = hz->n;
+      for (int i = 0; i < MCP_MAX_HORIZONS; i++) ah.steps[i] = i < hz->n ? hz->steps[i] : 0;
+      ah.st = sa;
+    } else if (dd) {
+      static_cast<mcp::PathArgs&>(ad) = a;
+      ad.mdd = d_mdd;
+      ad.mdd_stride = mdd_stride;
+      ad.st = sa;
+    } else {
+      static_cast<mcp::PathArgs&>(at) = a;
+      at.st = sa;
+    }
+    for (int kb = 0; kb < K; kb += kt) {
+      at.k_begin = ad.k_begin = ah.k_begin = kb;
+      hipError_t e = k_launch_t[nb - 1](variant, hz || dd ? nullptr : &at, dd ? &ad : nullptr, hz ? &ah : nullptr, grid,
+                                        (hipStream_t)stream);
+      if (e != hipSuccess) return fail(MCP_E_HIP, "mc_paths_t_kernel launch: %s", hipGetErrorString(e));
+    }
+    return MCP_OK;
+  }
   if (reb) {                              // SPEC.md 4.5: one kernel for every draw source, with or without horizons
     mcp::PathArgsRB ar;
     static_cast<mcp::PathArgs&>(ar) = a;
@@ -1223,7 +1284,7 @@ struct BootReq {
 int run_tile(mcp_ctx* c, const mcp_params* prm, const float* mu, const float* chol, const float* W, uint64_t seed,
              uint64_t path_begin, uint64_t n_total, const std::vector<Job>& jobs, bool exchange, float* terminal_out,
              mcp_stats* stats_out, bool dd, float* mdd_out, mcp_stats* dd_stats_out, const HzReq* hz, const BootReq* boot,
-             const RebReq* reb) {
+             const RebReq* reb, const StReq* st) {
   const size_t S = c->sh.size();
   uint64_t lo, hi;
   double gamma;
@@ -1352,7 +1413,7 @@ int run_tile(mcp_ctx* c, const mcp_params* prm, const float* mu, const float* ch
     if (j.pn) {
       if ((rc = launch_paths_impl(&tp[s], sh.d_packed, (const double*)sh.ws[MCP_WS_PIVOT], seed, path_begin + j.p0, j.pn, sh.d_terminal,
                                   j.pn, dd ? sh.d_mdd : nullptr, j.pn, sh.ws[MCP_WS_PARTIALS], sh.ws[MCP_WS_HIST], sh.stream,
-                                  hz ? &hzo : nullptr, boot ? &bti : nullptr, reb))) return rc;
+                                  hz ? &hzo : nullptr, boot ? &bti : nullptr, reb, st))) return rc;
     } else {
       // a shard without paths (fewer paths than shards): empty moment partials, nothing in the histogram
       if ((rc = mcp_launch_pass0(&tp[s], sh.d_terminal, 1, 0, (const double*)sh.ws[MCP_WS_PIVOT], sh.ws[MCP_WS_PARTIALS],
@@ -1450,7 +1511,8 @@ int tile_portfolios(size_t budget, uint64_t n_paths, int K, size_t bytes_per_pat
 
 int simulate_impl(mcp_ctx* c, const mcp_params* prm, const float* mu, const float* chol, const float* W, uint64_t seed,
                   uint64_t path_begin, uint64_t n_paths, float* terminal_out, mcp_stats* stats_out, bool dd, float* mdd_out,
-                  mcp_stats* dd_stats_out, const HzReq* hz = nullptr, const BootReq* boot = nullptr, const RebReq* reb = nullptr) {
+                  mcp_stats* dd_stats_out, const HzReq* hz = nullptr, const BootReq* boot = nullptr, const RebReq* reb = nullptr,
+                  const StReq* st = nullptr) {
   if (!c) return fail(MCP_E_ARG, "ctx is NULL");
   if (int rc = check_params(prm)) return rc;
   if ((!boot && (!mu || !chol)) || !W || !stats_out || (dd && !dd_stats_out)) return fail(MCP_E_ARG, "NULL pointer");
@@ -1507,7 +1569,7 @@ int simulate_impl(mcp_ctx* c, const mcp_params* prm, const float* mu, const floa
       }
       if (more)
         rc = run_tile(c, prm, mu, chol, W, seed, path_begin, n_paths, jobs, false, terminal_out, stats_out, dd, mdd_out, dd_stats_out, hz,
-                      boot, reb);
+                      boot, reb, st);
     }
   } else if (rc == MCP_OK) {
     // the path range is sharded; all shards see the same tile of portfolios
@@ -1523,7 +1585,7 @@ int simulate_impl(mcp_ctx* c, const mcp_params* prm, const float* mu, const floa
     for (int k0 = 0; k0 < K && rc == MCP_OK; k0 += kt_max) {
       for (size_t s = 0; s < S; s++) { jobs[s].k0 = k0; jobs[s].kt = std::min(kt_max, K - k0); }
       rc = run_tile(c, prm, mu, chol, W, seed, path_begin, n_paths, jobs, S > 1 || c->exchange_always, terminal_out, stats_out, dd,
-                    mdd_out, dd_stats_out, hz, boot, reb);
+                    mdd_out, dd_stats_out, hz, boot, reb, st);
     }
   }
   if (rc != MCP_OK) {
@@ -1663,6 +1725,44 @@ int mcp_simulate_rebalanced(mcp_ctx* c, const mcp_params* prm, const mcp_rebalan
   if (n_paths < 1) return fail(MCP_E_ARG, "n_paths must be >= 1");
   return simulate_impl(c, prm, mu, chol, W, seed, path_begin, n_paths, terminal_out, stats_out, false, nullptr, nullptr,
                        n_horizons ? &hz : nullptr, boot ? &br : nullptr, &rr);
+}
+
+int mcp_simulate_student_t(mcp_ctx* c, const mcp_params* prm, const mcp_student_t* st, const float* mu, const float* chol,
+                           const float* W, uint64_t seed, uint64_t path_begin, uint64_t n_paths, int n_horizons, const int32_t* horizons,
+                           int n_levels, const double* levels, float* terminal_out, mcp_stats* stats_out, float* mdd_out,
+                           mcp_stats* dd_stats_out, float* horizon_out, mcp_stats* hz_stats_out, double* bands_out) {
+  // the arguments first, so that each error is found (and named) before any device is touched, a NULL ctx included
+  if (int rc = check_params(prm)) return rc;
+  StReq sr;
+  if (int rc = check_student_t(prm, st, &sr)) return rc;
+  if (prm->compounding != MCP_COMPOUND_SIMPLE)
+    return fail(MCP_E_UNSUPPORTED, "Student-t paths compound simply (log compounding: expm1(S) has no finite mean under t steps)");
+  if (prm->flags & (MCP_FLAG_FOLD | MCP_FLAG_NATIVE_MATH))
+    return fail(MCP_E_UNSUPPORTED, "Student-t paths run on the spec's normals and the unfolded recurrence (no MCP_FLAG_FOLD / MCP_FLAG_NATIVE_MATH)");
+  const bool dd = dd_stats_out != nullptr;
+  if (dd && n_horizons != 0) return fail(MCP_E_UNSUPPORTED, "horizons and the drawdown are not tracked in one walk");
+  if (!dd && mdd_out) return fail(MCP_E_ARG, "mdd_out needs dd_stats_out");
+  HzReq hz;
+  if (n_horizons == 0) {
+    if (n_levels != 0 || horizon_out || hz_stats_out || bands_out)
+      return fail(MCP_E_ARG, "n_horizons = 0: n_levels must be 0 and horizon_out, hz_stats_out, bands_out NULL");
+  } else {
+    if (int rc = check_horizons(prm->n_steps, n_horizons, horizons)) return rc;
+    if (int rc = check_levels(n_levels, levels)) return rc;
+    if (!hz_stats_out) return fail(MCP_E_ARG, "hz_stats_out is NULL");
+    if ((bands_out == nullptr) != (n_levels == 0)) return fail(MCP_E_ARG, "bands_out must be NULL exactly when n_levels == 0");
+    hz.H = n_horizons;
+    hz.L = n_levels;
+    hz.steps = horizons;
+    hz.levels = levels;
+    hz.out = horizon_out;
+    hz.stats_out = hz_stats_out;
+    hz.bands_out = bands_out;
+  }
+  if (!mu || !chol || !W || !stats_out) return fail(MCP_E_ARG, "NULL pointer");
+  if (n_paths < 1) return fail(MCP_E_ARG, "n_paths must be >= 1");
+  return simulate_impl(c, prm, mu, chol, W, seed, path_begin, n_paths, terminal_out, stats_out, dd, mdd_out, dd_stats_out,
+                       n_horizons ? &hz : nullptr, nullptr, nullptr, &sr);
 }
 
 int mcp_sweep_historical(mcp_ctx* c, int N, int R, int P, const double* returns, const double* mean, const double* cov,

@@ -112,6 +112,28 @@ struct PathArgsRB : PathArgsHZ {
   float cost;                         // kappa32 = fl32(kappa), in [0, 1)
 };
 __device__ __forceinline__ BootArgs boot_args(const PathArgsRB& a) { return a.bt; }
+// The Student-t draws of SPEC.md 2.2 / 4.6: the degrees of freedom nu in [3, MCP_MAX_T_DOF], wave-uniform.  Appended to the
+// arguments of the plain, drawdown and horizon kernels (mc_paths_t_kernel, mc_paths_t_dd_kernel, mc_paths_t_hz_kernel).
+struct StudentArgs {
+  int32_t dof;
+  int32_t pad;
+};
+struct PathArgsT : PathArgs { StudentArgs st; };
+struct PathArgsTDD : PathArgsDD { StudentArgs st; };
+struct PathArgsTHZ : PathArgsHZ { StudentArgs st; };
+// nu of a t kernel's launch, read through the kernel-argument pointer where it is needed (nothing held in SGPRs across the walk:
+// the Cholesky factor lives there); the argument only selects the kernel's argument type.
+template <class A>
+__device__ __forceinline__ int32_t kernarg_dof() {
+  typedef const __attribute__((address_space(4))) A* cst_p;
+  cst_p k = (cst_p)__builtin_amdgcn_kernarg_segment_ptr();
+  asm volatile("" : "+s"(k));
+  return k->st.dof;
+}
+__device__ __forceinline__ int32_t student_dof(const PathArgs&) { return 0; }
+__device__ __forceinline__ int32_t student_dof(const PathArgsT&) { return kernarg_dof<PathArgsT>(); }
+__device__ __forceinline__ int32_t student_dof(const PathArgsTDD&) { return kernarg_dof<PathArgsTDD>(); }
+__device__ __forceinline__ int32_t student_dof(const PathArgsTHZ&) { return kernarg_dof<PathArgsTHZ>(); }
 
 // The LDS copy of the row table takes the slot of the inverse-CDF table (ICDF_LDS_ENTRIES float4: the bootstrap needs neither
 // that table nor the drift copy in its padding): R rows of NB float4 fit when R * NB <= ICDF_LDS_ENTRIES (N = 16: 272 rows).
@@ -189,7 +211,8 @@ constexpr int PATH_BLOCK = 256;
 // store q (simple: min V_t/P_t) or d (log: min S_t - P_t) next to V_T.  HZ: also store V_h at the horizons (SPEC.md 4.3).
 // BOOT: r is row j_t of the observed returns (SPEC.md 2.1 / 4.4) instead of mu + L z; BLDS: that table is read from LDS.
 // REB: the step updates the assets' returns since the last rebalance B instead of V; V moves at the rebalance dates only
-// (SPEC.md 4.5).  All six kernels are the body in mcp_paths_body.inc.
+// (SPEC.md 4.5).  STT: every normal of the step is scaled by s = sqrt((nu - 2) / chi), chi the sum of nu squared normals of
+// counter stream 2 (SPEC.md 2.2 / 4.6).  All nine kernels are the body in mcp_paths_body.inc.
 #define MCP_PATHS_BOUNDS(NB, KT, PPT) \
   __launch_bounds__(PATH_BLOCK, (NB <= 4 && KT == 1 && PPT == 1) ? MCP_MIN_WAVES : ((KT == 1 && PPT == 1) ? MCP_MIN_WAVES_BIG : 1))
 #define MCP_REB_BOUNDS(NB, KT, PPT) \
@@ -198,7 +221,7 @@ constexpr int PATH_BLOCK = 256;
 
 template <int NB, int KT, int PPT, bool NATIVE, bool FOLD = false, bool LOGC = false>
 __global__ void MCP_PATHS_BOUNDS(NB, KT, PPT) mc_paths_kernel(const PathArgs a) {
-  constexpr bool DD = false, HZ = false, BOOT = false, BLDS = false, REB = false;
+  constexpr bool DD = false, HZ = false, BOOT = false, BLDS = false, REB = false, STT = false;
 #include "mcp_paths_body.inc"
 }
 
@@ -206,7 +229,7 @@ __global__ void MCP_PATHS_BOUNDS(NB, KT, PPT) mc_paths_kernel(const PathArgs a) 
 // array: appended to PathArgs itself they would move the hidden kernel arguments (grid size) of every plain kernel.
 template <int NB, int KT, int PPT, bool LOGC>
 __global__ void MCP_PATHS_BOUNDS(NB, KT, PPT) mc_paths_dd_kernel(const PathArgsDD a) {
-  constexpr bool DD = true, HZ = false, NATIVE = false, FOLD = false, BOOT = false, BLDS = false, REB = false;
+  constexpr bool DD = true, HZ = false, NATIVE = false, FOLD = false, BOOT = false, BLDS = false, REB = false, STT = false;
 #include "mcp_paths_body.inc"
 }
 
@@ -214,7 +237,7 @@ __global__ void MCP_PATHS_BOUNDS(NB, KT, PPT) mc_paths_dd_kernel(const PathArgsD
 // at the horizons, V_h stored after each; V_T and the fused epilogue as in mc_paths_kernel.
 template <int NB, int KT, int PPT, bool LOGC>
 __global__ void MCP_PATHS_BOUNDS(NB, KT, PPT) mc_paths_hz_kernel(const PathArgsHZ a) {
-  constexpr bool DD = false, HZ = true, NATIVE = false, FOLD = false, BOOT = false, BLDS = false, REB = false;
+  constexpr bool DD = false, HZ = true, NATIVE = false, FOLD = false, BOOT = false, BLDS = false, REB = false, STT = false;
 #include "mcp_paths_body.inc"
 }
 
@@ -222,14 +245,14 @@ __global__ void MCP_PATHS_BOUNDS(NB, KT, PPT) mc_paths_hz_kernel(const PathArgsH
 // block per path-step for the row index, no normals, no Cholesky GEMV.  V_T and the fused epilogue as in mc_paths_kernel.
 template <int NB, int KT, int PPT, bool LOGC, bool BLDS>
 __global__ void MCP_PATHS_BOUNDS(NB, KT, PPT) mc_paths_boot_kernel(const PathArgsBT a) {
-  constexpr bool DD = false, HZ = false, NATIVE = false, FOLD = false, BOOT = true, REB = false;
+  constexpr bool DD = false, HZ = false, NATIVE = false, FOLD = false, BOOT = true, REB = false, STT = false;
 #include "mcp_paths_body.inc"
 }
 
 // The bootstrap kernel with the horizons of SPEC.md 4.3 (the segmented walk of mc_paths_hz_kernel).
 template <int NB, int KT, int PPT, bool LOGC, bool BLDS>
 __global__ void MCP_PATHS_BOUNDS(NB, KT, PPT) mc_paths_boot_hz_kernel(const PathArgsBTHZ a) {
-  constexpr bool DD = false, HZ = true, NATIVE = false, FOLD = false, BOOT = true, REB = false;
+  constexpr bool DD = false, HZ = true, NATIVE = false, FOLD = false, BOOT = true, REB = false, STT = false;
 #include "mcp_paths_body.inc"
 }
 // The rebalancing kernel (SPEC.md 4.5; simple compounding, Gaussian draws or, BOOT, the bootstrap's rows): the walk in segments
@@ -237,7 +260,26 @@ __global__ void MCP_PATHS_BOUNDS(NB, KT, PPT) mc_paths_boot_hz_kernel(const Path
 // kernel serves terminal-only and horizon calls.  V_T and the fused epilogue as in mc_paths_kernel.
 template <int NB, int KT, int PPT, bool BOOT, bool BLDS>
 __global__ void MCP_REB_BOUNDS(NB, KT, PPT) mc_paths_reb_kernel(const PathArgsRB a) {
-  constexpr bool DD = false, HZ = false, NATIVE = false, FOLD = false, LOGC = false, REB = true;
+  constexpr bool DD = false, HZ = false, NATIVE = false, FOLD = false, LOGC = false, REB = true, STT = false;
+#include "mcp_paths_body.inc"
+}
+
+// The Student-t kernels (SPEC.md 2.2 / 4.6; simple compounding, unfolded recurrence): mc_paths_kernel, mc_paths_dd_kernel and
+// mc_paths_hz_kernel with every step's normals scaled by the step's s.  V_T, the drawdown, the horizons and the fused epilogue as
+// there.
+template <int NB, int KT, int PPT>
+__global__ void MCP_PATHS_BOUNDS(NB, KT, PPT) mc_paths_t_kernel(const PathArgsT a) {
+  constexpr bool DD = false, HZ = false, NATIVE = false, FOLD = false, LOGC = false, BOOT = false, BLDS = false, REB = false, STT = true;
+#include "mcp_paths_body.inc"
+}
+template <int NB, int KT, int PPT>
+__global__ void MCP_PATHS_BOUNDS(NB, KT, PPT) mc_paths_t_dd_kernel(const PathArgsTDD a) {
+  constexpr bool DD = true, HZ = false, NATIVE = false, FOLD = false, LOGC = false, BOOT = false, BLDS = false, REB = false, STT = true;
+#include "mcp_paths_body.inc"
+}
+template <int NB, int KT, int PPT>
+__global__ void MCP_PATHS_BOUNDS(NB, KT, PPT) mc_paths_t_hz_kernel(const PathArgsTHZ a) {
+  constexpr bool DD = false, HZ = true, NATIVE = false, FOLD = false, LOGC = false, BOOT = false, BLDS = false, REB = false, STT = true;
 #include "mcp_paths_body.inc"
 }
 #undef MCP_PATHS_BOUNDS

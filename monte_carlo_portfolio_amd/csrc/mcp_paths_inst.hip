@@ -129,4 +129,22 @@ hipError_t MCP_CAT(launch_paths_rb_nb, MCP_NB)(int variant, bool boot, bool lds,
   return hipGetLastError();
 }
 
+// The Student-t kernels (mcp_simulate_student_t, SPEC.md 2.2 / 4.6): one portfolio or KT = 8 passes, simple compounding; exactly
+// one of the three argument blocks is given (terminal values only, with the drawdown, with horizons).
+template <int KT>
+static void go_t(const PathArgsT* at, const PathArgsTDD* ad, const PathArgsTHZ* ah, int grid, hipStream_t stream) {
+  if (ad) mc_paths_t_dd_kernel<MCP_NB, KT, 1><<<grid, PATH_BLOCK, lds_pad(), stream>>>(*ad);
+  else if (ah) mc_paths_t_hz_kernel<MCP_NB, KT, 1><<<grid, PATH_BLOCK, lds_pad(), stream>>>(*ah);
+  else mc_paths_t_kernel<MCP_NB, KT, 1><<<grid, PATH_BLOCK, lds_pad(), stream>>>(*at);
+}
+
+hipError_t MCP_CAT(launch_paths_t_nb, MCP_NB)(int variant, const PathArgsT* at, const PathArgsTDD* ad, const PathArgsTHZ* ah, int grid,
+                                              hipStream_t stream) {
+  if (variant != 0 && variant != VAR_KT8) return hipErrorInvalidValue;
+  if ((at != nullptr) + (ad != nullptr) + (ah != nullptr) != 1) return hipErrorInvalidValue;
+  if (variant == VAR_KT8) go_t<8>(at, ad, ah, grid, stream);
+  else go_t<1>(at, ad, ah, grid, stream);
+  return hipGetLastError();
+}
+
 }  // namespace mcp

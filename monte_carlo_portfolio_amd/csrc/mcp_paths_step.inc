@@ -1,8 +1,9 @@
 // mcp_paths_step.inc -- one step t of the path kernels' walk (mcp_paths_body.inc, included in its step loops): the normals of
 // step t, r = mu + L z (BOOT: r = row j_t of the observed returns), rho = w.r, the update of V (and, DD, of the running peak
 // and drawdown state).  REB: no rho and no V; the returns since the last rebalance B_i = B_i + r_i + B_i r_i instead
-// (SPEC.md 4.5), a = B + r then B = fma(B, r, a), one v_pk_add_f32 and one v_pk_fma_f32 per pair of assets.  In scope:
-// everything mcp_paths_body.inc declares before its step loops, and t.
+// (SPEC.md 4.5), a = B + r then B = fma(B, r, a), one v_pk_add_f32 and one v_pk_fma_f32 per pair of assets.  STT: the step's
+// chi blocks first (only s stays live while the asset normals are formed), then every asset normal scaled by s as it leaves
+// block_normals (SPEC.md 2.2 / 4.6).  In scope: everything mcp_paths_body.inc declares before its step loops, and t.
       float rho[PPT][KT];
       if constexpr (BOOT) {
         // SPEC.md 2.1 / 4.4: one Philox block on counter (t, 1, p_lo, p_hi); j_t = mulhi(x0, R) on a restart (t = 0 or
@@ -56,6 +57,37 @@
       if constexpr (LDS_MU) asm volatile("" : "+v"(par_off));
       const float* s_par = s_par0 + par_off;
       float z[PPT][N4];
+      float st_s[PPT];                                 // STT: the step's scale s of SPEC.md 2.2
+      if constexpr (STT) {
+        // SPEC.md 2.2: chi = sum_k g_k^2 (fma, k = 4q + m ascending) over nt = ceil(nu/4) blocks on counter (t nt + q, 2, p_lo,
+        // p_hi); the surplus words of the last block are masked to +0, which leaves chi unchanged.  nu is wave-uniform.
+        const int dof = student_dof(a);
+        const int nt = (dof + 3) >> 2;
+        float chi[PPT];
+#pragma unroll
+        for (int e = 0; e < PPT; e++) chi[e] = 0.0f;
+#pragma unroll 1
+        for (int q = 0; q < nt; q++) {
+          const uint32_t blk = (uint32_t)t * (uint32_t)nt + (uint32_t)q;   // T*nt < 2^32 (checked on the host)
+          const int left = dof - 4 * q;                                   // words of this block that count (uniform)
+#pragma unroll
+          for (int e = 0; e < PPT; e++) {
+            uint32_t x[4];
+            float g[4];
+            philox4x32_10(blk, 2u, plo[e], phi[e], ks, x);
+            block_normals<false>(x, s_tab, kc, g[0], g[1], g[2], g[3]);
+#pragma unroll
+            for (int m = 0; m < 4; m++) {
+              const float gm = m < left ? g[m] : 0.0f;
+              chi[e] = fma32(gm, gm, chi[e]);
+            }
+          }
+        }
+        // s = sqrt(fl32(nu - 2) / max(chi, 2^-126)): IEEE division and square root, each correctly rounded
+        const float num = (float)(dof - 2);
+#pragma unroll
+        for (int e = 0; e < PPT; e++) st_s[e] = sqrtf(num / fmaxf(chi[e], 0x1p-126f));
+      }
 #pragma unroll
       for (int q = 0; q < NB; q++) {
         const uint32_t blk = (uint32_t)t * NB + q;     // counter.x; counter.y = 0 (T*NB < 2^32)
@@ -64,6 +96,10 @@
           uint32_t x[4];
           philox4x32_10(blk, 0u, plo[e], phi[e], ks, x);
           block_normals<NATIVE>(x, s_tab, kc, z[e][0 * NB + q], z[e][1 * NB + q], z[e][2 * NB + q], z[e][3 * NB + q]);
+          if constexpr (STT) {                         // SPEC.md 4.6: z' = fl32(s z)
+#pragma unroll
+            for (int m = 0; m < 4; m++) z[e][m * NB + q] = st_s[e] * z[e][m * NB + q];
+          }
         }
       }
       if constexpr (FOLD) {

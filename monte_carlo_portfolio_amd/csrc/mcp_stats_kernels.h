@@ -103,6 +103,20 @@ MCP_DECL_NB(1) MCP_DECL_NB(2) MCP_DECL_NB(3) MCP_DECL_NB(4) MCP_DECL_NB(5) MCP_D
 MCP_DECL_NB(9) MCP_DECL_NB(10) MCP_DECL_NB(11) MCP_DECL_NB(12) MCP_DECL_NB(13) MCP_DECL_NB(14) MCP_DECL_NB(15) MCP_DECL_NB(16)
 #undef MCP_DECL_NB
 
+// the Student-t kernels (SPEC.md 2.2 / 4.6), variants 0 and VAR_KT8 only; exactly one of at (terminal values), ad (drawdown),
+// ah (horizons)
+struct PathArgsT;
+struct PathArgsTDD;
+struct PathArgsTHZ;
+typedef hipError_t (*launch_paths_t_fn)(int variant, const PathArgsT* at, const PathArgsTDD* ad, const PathArgsTHZ* ah, int grid,
+                                        hipStream_t stream);
+#define MCP_DECL_NB(n)                                                                                                    \
+  hipError_t launch_paths_t_nb##n(int variant, const PathArgsT* at, const PathArgsTDD* ad, const PathArgsTHZ* ah, int grid, \
+                                  hipStream_t stream);
+MCP_DECL_NB(1) MCP_DECL_NB(2) MCP_DECL_NB(3) MCP_DECL_NB(4) MCP_DECL_NB(5) MCP_DECL_NB(6) MCP_DECL_NB(7) MCP_DECL_NB(8)
+MCP_DECL_NB(9) MCP_DECL_NB(10) MCP_DECL_NB(11) MCP_DECL_NB(12) MCP_DECL_NB(13) MCP_DECL_NB(14) MCP_DECL_NB(15) MCP_DECL_NB(16)
+#undef MCP_DECL_NB
+
 // mcp_sweep_paths.hip: MFMA K-portfolio kernels; mt = 32-portfolio tiles per wave (1, 2 or 4)
 hipError_t launch_sweep_shared(int nb, int mt, bool native, const PathArgs& args, hipStream_t stream);   // mt: 4|2 (N <= 16), 2|1 (N > 16)
 hipError_t launch_sweep_shared_p0(int nb, int mt, bool native, const PathArgs& args, hipStream_t stream);

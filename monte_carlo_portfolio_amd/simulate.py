@@ -171,6 +171,47 @@ class Context:
             ptr(hz_stats), ptr(bands) if L else None))
         return stats, hz_stats, bands, term, hz_term
 
+    def simulate_student_t(self, prm: _ffi.McpParams, dof: int, mu, chol, W, seed: int, path_begin: int, n_paths: int, store: bool,
+                           drawdown: bool = False, horizons=None, levels=()):
+        """simulate() / simulate_drawdown() / simulate_horizons() on Student-t draws with `dof` degrees of freedom (SPEC.md 2.2 /
+        4.6; include/mcport.h, mcp_simulate_student_t; simple compounding only) -> (stats [K], dd_stats [K] or None, hz_stats
+        [H, K], bands [H, K, L], terminal, qd, horizon_terminal): the entries of the blocks not asked for are None; with `store`,
+        terminal is [K, n_paths], qd the binary32 drawdown q [K, n_paths], horizon_terminal [H, K, n_paths]."""
+        K = prm.n_portfolios
+        stats = np.zeros(K, _ffi.STATS_DTYPE)
+        term = np.empty((K, n_paths), np.float32) if store else None
+        ptr = lambda a: a.ctypes.data_as(ctypes.c_void_p) if a is not None else None   # noqa: E731
+        dd_stats = raw = hz_stats = bands = hz_term = steps = lv = None
+        H = L = 0
+        if drawdown:
+            dd_stats = np.zeros(K, _ffi.STATS_DTYPE)
+            raw = np.empty((K, n_paths), np.float32) if store else None
+        if horizons is not None:
+            steps = np.ascontiguousarray(horizons, np.int32).ravel()
+            lv = np.ascontiguousarray(levels, np.float64).ravel()
+            H, L = steps.size, lv.size
+            hz_stats = np.zeros((H, K), _ffi.STATS_DTYPE)
+            bands = np.zeros((H, K, L), np.float64)
+            hz_term = np.empty((H, K, n_paths), np.float32) if store else None
+        st = _ffi.McpStudentT(int(dof), 0)
+        _ffi.check(_ffi.lib().mcp_simulate_student_t(
+            self._h, ctypes.byref(prm), ctypes.byref(st), ptr(mu), ptr(chol), ptr(W), seed, path_begin, n_paths, H,
+            ptr(steps) if H else None, L, ptr(lv) if L else None, ptr(term), ptr(stats), ptr(raw), ptr(dd_stats), ptr(hz_term),
+            ptr(hz_stats), ptr(bands) if L else None))
+        return stats, dd_stats, hz_stats, bands, term, raw, hz_term
+
+
+def check_dof(dof):
+    """SPEC.md 2.2 argument rule -> None (Gaussian draws) or the int nu in [3, MCP_MAX_T_DOF]; ValueError otherwise (a bool,
+    a non-integral value, a value out of range)."""
+    if dof is None:
+        return None
+    if isinstance(dof, (bool, np.bool_)) or not isinstance(dof, (int, float, np.integer, np.floating)):
+        raise ValueError(f"dof must be an integer in [3, {_ffi.MCP_MAX_T_DOF}], got {dof!r}")
+    if not float(dof).is_integer() or not 3 <= dof <= _ffi.MCP_MAX_T_DOF:
+        raise ValueError(f"dof must be an integer in [3, {_ffi.MCP_MAX_T_DOF}], got {dof!r}")
+    return int(dof)
+
 
 def check_rebalance(rebalance, rebalance_cost):
     """SPEC.md 4.5 argument rules -> (period, cost): period None (constant weights, no rebalancing), 0 (rebalance="never": bought
@@ -281,7 +322,7 @@ def drawdown_to_dict(rec) -> dict:
 def simulate_paths(mu, cov, weights, n_steps=252, n_paths=10_000, seed=0, v0=1.0, compounding="simple",
                    rf=0.0, alpha=0.95, devices=None, store=False, path_begin=0, chol=None,
                    native_math=False, as_array=False, fold=False, shard="auto", context=None, drawdown=False,
-                   horizons=None, bands=(), rebalance=None, rebalance_cost=0.0):
+                   horizons=None, bands=(), rebalance=None, rebalance_cost=0.0, dof=None):
     """Simulate `n_paths` correlated return paths and reduce them to risk statistics.
 
     mu [N], cov [N,N] are per-step mean and covariance (the reference's `mean_returns`, `cov_matrix`
@@ -312,7 +353,18 @@ def simulate_paths(mu, cov, weights, n_steps=252, n_paths=10_000, seed=0, v0=1.0
     4.5, simple compounding only).  The result has the shape of the same call without it, horizons and bands included (pivots of
     SPEC.md 5.4); rebalance=1 with no cost gives the constant-weight values bit for bit, on the rebalancing kernel.  Not with
     drawdown, fold, native_math or compounding="log" (ValueError).
+
+    dof=None (default): Gaussian steps r = mu + L z.  dof=nu (an int in [3, 32]): multivariate Student-t steps with nu degrees
+    of freedom, r = mu + L s z with one s = sqrt((nu - 2) / chi2_nu) per path and step shared by all assets (SPEC.md 2.2 / 4.6):
+    the same mean and covariance as the Gaussian call, fat tails, assets that crash together, and the Gaussian call's own z
+    (common random numbers with the same seed).  The result has the shape of the same call without it, drawdown and horizons
+    blocks included (pivots of SPEC.md 5).  fit_student_t_dof(returns) estimates nu from return rows.  Not with fold,
+    native_math, rebalance or compounding="log" (ValueError).
     """
+    dof = check_dof(dof)
+    if dof is not None and (fold or native_math or compounding == "log" or rebalance is not None):
+        raise ValueError("dof needs simple compounding, the spec's normals, the unfolded recurrence and constant weights: not with "
+                         "fold, native_math, rebalance or compounding='log'")
     period, cost = check_rebalance(rebalance, rebalance_cost)
     if period is not None and (drawdown or fold or native_math or compounding == "log"):
         raise ValueError("rebalance needs simple compounding, the spec's normals and the unfolded recurrence: not with drawdown, fold, "
@@ -333,7 +385,18 @@ def simulate_paths(mu, cov, weights, n_steps=252, n_paths=10_000, seed=0, v0=1.0
     by_portfolio = len(devs) > 1 and (shard == "portfolios" or (shard == "auto" and W.shape[0] >= 512 * len(devs)))
     prm = _ffi.make_params(mu32.shape[0], n_steps, W.shape[0], compounding, v0, alpha, rf, native_math, fold, by_portfolio)
     ctx = context if context is not None else default_context(devs)
-    if period is not None:
+    if dof is not None:
+        stats, dd_stats, hz_stats, hz_bands, term, raw, hz_term = ctx.simulate_student_t(
+            prm, dof, mu32, L, W, int(seed), int(path_begin), int(n_paths), store, drawdown=drawdown,
+            horizons=steps if horizons is not None else None, levels=levels if horizons is not None else ())
+        mdd = mdd_from_raw(raw, compounding) if drawdown and store else None
+        if as_array:
+            if horizons is not None:
+                return (stats, hz_stats, hz_bands, term, hz_term) if store else (stats, hz_stats, hz_bands)
+            if drawdown:
+                return (stats, dd_stats, term, mdd) if store else (stats, dd_stats)
+            return (stats, term) if store else stats
+    elif period is not None:
         stats, hz_stats, hz_bands, term, hz_term = ctx.simulate_rebalanced(
             prm, period, cost, W, int(seed), int(path_begin), int(n_paths), store, mu=mu32, chol=L,
             horizons=steps if horizons is not None else None, levels=levels if horizons is not None else ())
@@ -412,8 +475,9 @@ def simulate_bootstrap(returns, weights, n_steps=252, n_paths=10_000, block=1.0,
     pivots of SPEC.md 5.4; not with compounding="log").
     """
     if unsupported:
-        raise ValueError(f"simulate_bootstrap does not take {sorted(unsupported)} (no normals: no fold / native_math; "
-                         "drawdown on bootstrap paths is not supported)")
+        raise ValueError(f"simulate_bootstrap does not take {sorted(unsupported)} (no normals: no fold / native_math / dof -- "
+                         "Student-t draws are a parametric model, call simulate_paths(dof=...); drawdown on bootstrap paths is "
+                         "not supported)")
     period, cost = check_rebalance(rebalance, rebalance_cost)
     if period is not None and compounding == "log":
         raise ValueError("rebalance needs simple compounding: not with compounding='log'")
