@@ -108,36 +108,6 @@ const mcp::launch_paths_fn k_launch[16] = {
     mcp::launch_paths_nb5,  mcp::launch_paths_nb6,  mcp::launch_paths_nb7,  mcp::launch_paths_nb8,
     mcp::launch_paths_nb9,  mcp::launch_paths_nb10, mcp::launch_paths_nb11, mcp::launch_paths_nb12,
     mcp::launch_paths_nb13, mcp::launch_paths_nb14, mcp::launch_paths_nb15, mcp::launch_paths_nb16};
-const mcp::launch_paths_dd_fn k_launch_dd[16] = {
-    mcp::launch_paths_dd_nb1,  mcp::launch_paths_dd_nb2,  mcp::launch_paths_dd_nb3,  mcp::launch_paths_dd_nb4,
-    mcp::launch_paths_dd_nb5,  mcp::launch_paths_dd_nb6,  mcp::launch_paths_dd_nb7,  mcp::launch_paths_dd_nb8,
-    mcp::launch_paths_dd_nb9,  mcp::launch_paths_dd_nb10, mcp::launch_paths_dd_nb11, mcp::launch_paths_dd_nb12,
-    mcp::launch_paths_dd_nb13, mcp::launch_paths_dd_nb14, mcp::launch_paths_dd_nb15, mcp::launch_paths_dd_nb16};
-const mcp::launch_paths_hz_fn k_launch_hz[16] = {
-    mcp::launch_paths_hz_nb1,  mcp::launch_paths_hz_nb2,  mcp::launch_paths_hz_nb3,  mcp::launch_paths_hz_nb4,
-    mcp::launch_paths_hz_nb5,  mcp::launch_paths_hz_nb6,  mcp::launch_paths_hz_nb7,  mcp::launch_paths_hz_nb8,
-    mcp::launch_paths_hz_nb9,  mcp::launch_paths_hz_nb10, mcp::launch_paths_hz_nb11, mcp::launch_paths_hz_nb12,
-    mcp::launch_paths_hz_nb13, mcp::launch_paths_hz_nb14, mcp::launch_paths_hz_nb15, mcp::launch_paths_hz_nb16};
-const mcp::launch_paths_bt_fn k_launch_bt[16] = {
-    mcp::launch_paths_bt_nb1,  mcp::launch_paths_bt_nb2,  mcp::launch_paths_bt_nb3,  mcp::launch_paths_bt_nb4,
-    mcp::launch_paths_bt_nb5,  mcp::launch_paths_bt_nb6,  mcp::launch_paths_bt_nb7,  mcp::launch_paths_bt_nb8,
-    mcp::launch_paths_bt_nb9,  mcp::launch_paths_bt_nb10, mcp::launch_paths_bt_nb11, mcp::launch_paths_bt_nb12,
-    mcp::launch_paths_bt_nb13, mcp::launch_paths_bt_nb14, mcp::launch_paths_bt_nb15, mcp::launch_paths_bt_nb16};
-const mcp::launch_paths_bthz_fn k_launch_bthz[16] = {
-    mcp::launch_paths_bthz_nb1,  mcp::launch_paths_bthz_nb2,  mcp::launch_paths_bthz_nb3,  mcp::launch_paths_bthz_nb4,
-    mcp::launch_paths_bthz_nb5,  mcp::launch_paths_bthz_nb6,  mcp::launch_paths_bthz_nb7,  mcp::launch_paths_bthz_nb8,
-    mcp::launch_paths_bthz_nb9,  mcp::launch_paths_bthz_nb10, mcp::launch_paths_bthz_nb11, mcp::launch_paths_bthz_nb12,
-    mcp::launch_paths_bthz_nb13, mcp::launch_paths_bthz_nb14, mcp::launch_paths_bthz_nb15, mcp::launch_paths_bthz_nb16};
-const mcp::launch_paths_rb_fn k_launch_rb[16] = {
-    mcp::launch_paths_rb_nb1,  mcp::launch_paths_rb_nb2,  mcp::launch_paths_rb_nb3,  mcp::launch_paths_rb_nb4,
-    mcp::launch_paths_rb_nb5,  mcp::launch_paths_rb_nb6,  mcp::launch_paths_rb_nb7,  mcp::launch_paths_rb_nb8,
-    mcp::launch_paths_rb_nb9,  mcp::launch_paths_rb_nb10, mcp::launch_paths_rb_nb11, mcp::launch_paths_rb_nb12,
-    mcp::launch_paths_rb_nb13, mcp::launch_paths_rb_nb14, mcp::launch_paths_rb_nb15, mcp::launch_paths_rb_nb16};
-const mcp::launch_paths_t_fn k_launch_t[16] = {
-    mcp::launch_paths_t_nb1,  mcp::launch_paths_t_nb2,  mcp::launch_paths_t_nb3,  mcp::launch_paths_t_nb4,
-    mcp::launch_paths_t_nb5,  mcp::launch_paths_t_nb6,  mcp::launch_paths_t_nb7,  mcp::launch_paths_t_nb8,
-    mcp::launch_paths_t_nb9,  mcp::launch_paths_t_nb10, mcp::launch_paths_t_nb11, mcp::launch_paths_t_nb12,
-    mcp::launch_paths_t_nb13, mcp::launch_paths_t_nb14, mcp::launch_paths_t_nb15, mcp::launch_paths_t_nb16};
 
 // SPEC.md 4.3: 1..MCP_MAX_HORIZONS strictly increasing steps in [1, n_steps]
 int check_horizons(int n_steps, int H, const int32_t* steps) {
@@ -159,9 +129,8 @@ int check_levels(int L, const double* levels) {
   return MCP_OK;
 }
 
-// SPEC.md 2.1: the bootstrap request -- 1..MCP_MAX_BOOT_ROWS rows of n_assets finite binary32 values, 1 <= b <= +inf -- and
-// its restart threshold thr = b == +inf ? 0 : min(2^32, floor(fl64(2^32 / b))).
-int check_boot(const mcp_params* prm, const mcp_bootstrap* boot, uint64_t* thr) {
+// SPEC.md 2.1: the bootstrap request -- 1..MCP_MAX_BOOT_ROWS rows of n_assets finite binary32 values, 1 <= b <= +inf
+int check_boot(const mcp_params* prm, const mcp_bootstrap* boot) {
   if (!boot) return fail(MCP_E_ARG, "bootstrap is NULL");
   if (!boot->rows) return fail(MCP_E_ARG, "bootstrap rows is NULL");
   if (boot->n_rows < 1 || boot->n_rows > MCP_MAX_BOOT_ROWS)
@@ -172,11 +141,13 @@ int check_boot(const mcp_params* prm, const mcp_bootstrap* boot, uint64_t* thr) 
   for (size_t i = 0; i < n; i++)
     if (!std::isfinite(boot->rows[i]))
       return fail(MCP_E_ARG, "bootstrap row %zu, asset %zu is not finite", i / (size_t)prm->n_assets, i % (size_t)prm->n_assets);
-  if (thr) {
-    const double q = 4294967296.0 / b;                 // fl64(2^32 / b); 0 for b = +inf
-    *thr = q >= 4294967296.0 ? (uint64_t)1 << 32 : (uint64_t)q;
-  }
   return MCP_OK;
+}
+
+// SPEC.md 2.1: the restart threshold thr = b == +inf ? 0 : min(2^32, floor(fl64(2^32 / b)))
+uint64_t boot_threshold(double b) {
+  const double q = 4294967296.0 / b;                   // fl64(2^32 / b); 0 for b = +inf
+  return q >= 4294967296.0 ? (uint64_t)1 << 32 : (uint64_t)q;
 }
 
 // SPEC.md 5.3: per portfolio the mean m and variance s2 (population) of rho_j = sum_i w_i rows[j,i] over the R rows, binary64.
@@ -208,39 +179,151 @@ double boot_pivot(int compounding, int T, double m, double s2) {
   return std::isfinite(c) ? c : 0.0;
 }
 
-// The rebalancing rule of a launch (SPEC.md 4.5): the period m >= 0 and kappa32 = fl32(kappa).
-struct RebReq {
-  int32_t period = 0;
-  float cost = 0.0f;
-};
-
 // SPEC.md 4.5: period >= 0, reserved == 0, cost in [0, 1) (not NaN)
-int check_reb(const mcp_rebalance* reb, RebReq* out) {
+int check_reb(const mcp_rebalance* reb) {
   if (!reb) return fail(MCP_E_ARG, "rebalance is NULL");
   if (reb->period < 0) return fail(MCP_E_ARG, "rebalance period=%d < 0", reb->period);
   if (reb->reserved != 0) return fail(MCP_E_ARG, "rebalance reserved=%d must be 0", reb->reserved);
   if (!(reb->cost >= 0.0 && reb->cost < 1.0)) return fail(MCP_E_ARG, "rebalance cost=%g outside [0, 1)", reb->cost);
-  if (out) {
-    out->period = reb->period;
-    out->cost = (float)reb->cost;
-  }
   return MCP_OK;
 }
 
-// The Student-t draws of a launch (SPEC.md 2.2): nu in [3, MCP_MAX_T_DOF].
-struct StReq {
-  int32_t dof = 0;
-};
-
 // SPEC.md 2.2: 3 <= nu <= MCP_MAX_T_DOF, reserved == 0, (uint64)T ceil(nu/4) < 2^32 (the counter of stream 2)
-int check_student_t(const mcp_params* prm, const mcp_student_t* st, StReq* out) {
+int check_student_t(const mcp_params* prm, const mcp_student_t* st) {
   if (!st) return fail(MCP_E_ARG, "student_t is NULL");
   if (st->dof < 3 || st->dof > MCP_MAX_T_DOF) return fail(MCP_E_ARG, "dof=%d outside [3,%d]", st->dof, MCP_MAX_T_DOF);
   if (st->reserved != 0) return fail(MCP_E_ARG, "student_t reserved=%d must be 0", st->reserved);
   if ((uint64_t)prm->n_steps * (uint64_t)((st->dof + 3) / 4) > 0xFFFFFFFFull)
     return fail(MCP_E_ARG, "n_steps * ceil(dof/4) = %llu exceeds the 32-bit Philox block counter of stream 2",
                 (unsigned long long)((uint64_t)prm->n_steps * (uint64_t)((st->dof + 3) / 4)));
-  if (out) out->dof = st->dof;
+  return MCP_OK;
+}
+
+// The draws of a walk (SPEC.md 2): Gaussian steps mu + L z, rows of the bootstrap, or Student-t steps mu + L s z.
+enum Source { SRC_GAUSS, SRC_BOOT, SRC_T };
+
+// What one call asks of the walk: the draw source, optionally a rebalancing rule, the drawdown or horizons, and the host arrays
+// of an mcp_simulate* call (an mcp_launch_paths* call gives its device arrays in a Launch instead).
+struct Request {
+  Source src = SRC_GAUSS;
+  const float* mu = nullptr;            // SRC_GAUSS, SRC_T: the drift and the Cholesky factor
+  const float* chol = nullptr;
+  const mcp_bootstrap* boot = nullptr;  // SRC_BOOT (SPEC.md 2.1)
+  const mcp_student_t* st = nullptr;    // SRC_T (SPEC.md 2.2)
+  bool rebalanced = false;              // SPEC.md 4.5: the rule `reb`
+  const mcp_rebalance* reb = nullptr;
+  bool dd = false;                      // SPEC.md 4.2 / 5.1: the drawdown of every path
+  bool hz = false;                      // SPEC.md 4.3 / 5.2: the values after H steps, statistics at alpha and at L levels
+  int H = 0, L = 0;
+  const int32_t* steps = nullptr;
+  const double* levels = nullptr;
+  const float* W = nullptr;             // [K][N]
+  float* terminal_out = nullptr;        // outputs; the optional ones NULL when not asked for
+  mcp_stats* stats_out = nullptr;
+  float* mdd_out = nullptr;
+  mcp_stats* dd_stats_out = nullptr;
+  float* hz_out = nullptr;              // [H*K*n], row h*K + k
+  mcp_stats* hz_stats_out = nullptr;    // [H*K]
+  double* bands_out = nullptr;          // [H*K*L]
+};
+
+Request host_request(Source src, const float* mu, const float* chol, const float* W, float* terminal_out, mcp_stats* stats_out) {
+  Request rq;
+  rq.src = src;
+  rq.mu = mu;
+  rq.chol = chol;
+  rq.W = W;
+  rq.terminal_out = terminal_out;
+  rq.stats_out = stats_out;
+  return rq;
+}
+
+void ask_horizons(Request& rq, bool on, int H, const int32_t* steps, int L, const double* levels, float* out, mcp_stats* stats,
+                  double* bands) {
+  rq.hz = on;
+  rq.H = H;
+  rq.steps = steps;
+  rq.L = L;
+  rq.levels = levels;
+  rq.hz_out = out;
+  rq.hz_stats_out = stats;
+  rq.bands_out = bands;
+}
+
+// One launch of the path kernels for a request: the device arrays of an mcp_launch_paths* call or of one shard's part of a tile.
+struct Launch {
+  const float* d_packed = nullptr;
+  const double* d_pivot = nullptr;
+  uint64_t seed = 0, path_begin = 0, n_paths = 0;
+  float* d_terminal = nullptr;
+  uint64_t stride = 0;
+  float* d_mdd = nullptr;               // drawdown: [K][mdd_stride]
+  uint64_t mdd_stride = 0;
+  float* d_hz = nullptr;                // horizons: [H][K][hz_stride]
+  uint64_t hz_stride = 0;
+  const float* d_rows = nullptr;        // bootstrap: [R][N4], zero-padded
+  void* d_partials = nullptr;
+  void* d_hist = nullptr;
+  hipStream_t stream = nullptr;
+};
+
+// Every rule a request meets: each feature's own arguments, then which features combine (MCP_E_UNSUPPORTED), then the outputs.
+// `ln`: an mcp_launch_paths* call, whose device arrays are checked instead of the host arrays of an mcp_simulate* call.
+int check_request(const mcp_params* prm, const Request& rq, uint64_t n_paths, const Launch* ln = nullptr) {
+  int rc;
+  if ((rc = check_params(prm))) return rc;
+  if (rq.rebalanced) {
+    if ((rc = check_reb(rq.reb))) return rc;
+    if (rq.src == SRC_BOOT ? rq.mu || rq.chol : !rq.mu || !rq.chol) return fail(MCP_E_ARG, "exactly one draw source: mu and chol, or boot");
+  }
+  if (rq.src == SRC_BOOT && (rc = check_boot(prm, rq.boot))) return rc;
+  if (rq.src == SRC_T && (rc = check_student_t(prm, rq.st))) return rc;
+  const bool logc = prm->compounding != MCP_COMPOUND_SIMPLE;
+  if (rq.rebalanced && logc) return fail(MCP_E_UNSUPPORTED, "rebalanced paths compound simply (no log compounding)");
+  if (rq.src == SRC_T && logc)
+    return fail(MCP_E_UNSUPPORTED, "Student-t paths compound simply (log compounding: expm1(S) has no finite mean under t steps)");
+  if (prm->flags & (MCP_FLAG_FOLD | MCP_FLAG_NATIVE_MATH)) {   // the fast steps exist for plain Gaussian walks only
+    const char* who = rq.rebalanced        ? "rebalanced paths run on the unfolded recurrence and the spec's normals"
+                      : rq.src == SRC_T    ? "Student-t paths run on the spec's normals and the unfolded recurrence"
+                      : rq.src == SRC_BOOT ? "bootstrap paths draw no normals"
+                      : rq.dd              ? "the drawdown runs on the spec's normals and the unfolded recurrence"
+                      : rq.hz              ? "the horizons run on the spec's normals and the unfolded recurrence"
+                                           : nullptr;
+    if (who) return fail(MCP_E_UNSUPPORTED, "%s (no MCP_FLAG_FOLD / MCP_FLAG_NATIVE_MATH)", who);
+    if ((prm->flags & MCP_FLAG_FOLD) && (prm->n_portfolios != 1 || (prm->flags & MCP_FLAG_NATIVE_MATH)))
+      return fail(MCP_E_UNSUPPORTED, "MCP_FLAG_FOLD needs one portfolio and the spec's normals");
+  }
+  if (rq.dd && rq.hz) return fail(MCP_E_UNSUPPORTED, "horizons and the drawdown are not tracked in one walk");
+  if (rq.dd && (rq.src == SRC_BOOT || rq.rebalanced))
+    return fail(MCP_E_UNSUPPORTED, "the drawdown is not tracked on bootstrap or rebalanced paths");
+  if (rq.src == SRC_T && rq.rebalanced) return fail(MCP_E_UNSUPPORTED, "Student-t draws are not combined with rebalancing");
+  if (rq.src != SRC_BOOT && (uint64_t)prm->n_steps * (uint64_t)((prm->n_assets + 3) / 4) > 0xFFFFFFFFull)
+    return fail(MCP_E_UNSUPPORTED, "n_steps * ceil(N/4) exceeds the 32-bit Philox block counter");
+  if (!rq.dd && rq.mdd_out) return fail(MCP_E_ARG, "mdd_out needs dd_stats_out");
+  if (!rq.hz) {
+    if (rq.L != 0 || rq.hz_out || rq.hz_stats_out || rq.bands_out)
+      return fail(MCP_E_ARG, "n_horizons = 0: n_levels must be 0 and horizon_out, hz_stats_out, bands_out NULL");
+  } else {
+    if ((rc = check_horizons(prm->n_steps, rq.H, rq.steps))) return rc;
+    if ((rc = check_levels(rq.L, rq.levels))) return rc;
+    if (!ln && !rq.hz_stats_out) return fail(MCP_E_ARG, "hz_stats_out is NULL");
+    if ((rq.bands_out == nullptr) != (rq.L == 0)) return fail(MCP_E_ARG, "bands_out must be NULL exactly when n_levels == 0");
+  }
+  if (!ln) {
+    if ((rq.src != SRC_BOOT && (!rq.mu || !rq.chol)) || !rq.W || !rq.stats_out || (rq.dd && !rq.dd_stats_out))
+      return fail(MCP_E_ARG, "NULL pointer");
+    if (n_paths < 1) return fail(MCP_E_ARG, "n_paths must be >= 1");
+    return MCP_OK;
+  }
+  if (!ln->d_packed || !ln->d_terminal) return fail(MCP_E_ARG, "NULL device pointer");
+  if (rq.dd && !ln->d_mdd) return fail(MCP_E_ARG, "d_mdd is NULL");
+  if (rq.hz && !ln->d_hz) return fail(MCP_E_ARG, "d_horizon is NULL");
+  if ((ln->d_partials == nullptr) != (ln->d_hist == nullptr)) return fail(MCP_E_ARG, "d_partials and d_hist go together (both or neither)");
+  if (n_paths < 1) return fail(MCP_E_ARG, "n_paths must be >= 1");
+  const uint64_t need[3] = {ln->stride, rq.dd ? ln->mdd_stride : n_paths, rq.hz ? ln->hz_stride : n_paths};
+  const char* name[3] = {"terminal_stride", "mdd_stride", "horizon_stride"};
+  for (int i = 0; i < 3; i++)
+    if (need[i] < n_paths) return fail(MCP_E_ARG, "%s %llu < n_paths %llu", name[i], (unsigned long long)need[i], (unsigned long long)n_paths);
   return MCP_OK;
 }
 
@@ -337,42 +420,72 @@ int device_tables(int dev, hipStream_t stream, const float4** out) {
   return MCP_OK;
 }
 
+// Device memory (hipMalloc) and pinned host memory (hipHostMalloc, portable; `dev` is the device address of a mapped one), grown
+// by grow() / grow_mapped() and released by release().
+template <class T> struct DevBuf { T* p = nullptr; size_t cap = 0; };
+template <class T> struct HostBuf { T* p = nullptr; size_t cap = 0; void* dev = nullptr; };
+
 // One shard of a context: a device, its stream and every buffer a pass needs there.
 struct Shard {
   int device = 0;
   hipStream_t stream = nullptr;
   hipEvent_t ev = nullptr;                 // same-device exchange: "my step is enqueued"
-  void* ws[MCP_WS_COUNT] = {nullptr};
+  void* ws[MCP_WS_COUNT] = {nullptr};      // ws[MCP_WS_STATS] is stats.dev
   size_t ws_cap[MCP_WS_COUNT] = {0};
-  float* d_packed = nullptr;
-  size_t packed_cap = 0;
-  float* d_terminal = nullptr;
-  size_t terminal_cap = 0;
-  mcp_record* d_gather = nullptr;          // [shards][K tile] records of all shards (shard 0 finishes the statistics)
-  size_t gather_cap = 0;
-  float* h_packed = nullptr;               // pinned staging
-  size_t h_packed_cap = 0;
-  double* h_pivot = nullptr;               // pinned staging of the [K tile] pivots
-  size_t h_pivot_cap = 0;
-  mcp_stats* h_stats = nullptr;            // pinned AND mapped: ws[MCP_WS_STATS] is its device address, so the last kernel
-  size_t h_stats_cap = 0;                  // of a pass writes the [K] records straight into host memory (no copy-back)
-  float* d_mdd = nullptr;                  // drawdown calls: [K tile][paths] q / d of SPEC.md 4.2
-  size_t mdd_cap = 0;
-  mcp_stats* h_dd_stats = nullptr;         // drawdown calls: the drawdown statistics, pinned and mapped like h_stats
-  size_t h_dd_stats_cap = 0;
-  void* d_dd_stats = nullptr;              // device address of h_dd_stats
-  float* d_hz = nullptr;                   // horizon calls: [H][K tile][paths] V_h / S_h of SPEC.md 4.3
-  size_t hz_cap = 0;
-  double* d_hz_pivot = nullptr;            // horizon calls: [H][K tile] pivots (mcp_pivots at n_steps = h)
-  size_t hz_pivot_cap = 0;
-  double* h_hz_pivot = nullptr;            // pinned staging of d_hz_pivot
-  size_t h_hz_pivot_cap = 0;
-  mcp_stats* h_hz_stats = nullptr;         // horizon calls: [1 + L][H][K tile] records of the alpha select and of every level's
-  size_t h_hz_stats_cap = 0;               // select, pinned and mapped like h_stats
-  void* d_hz_stats = nullptr;              // device address of h_hz_stats
-  float* d_boot = nullptr;                 // bootstrap calls: [R][N4] observed rows, zero-padded (SPEC.md 2.1)
-  size_t boot_cap = 0;
+  DevBuf<float> packed;
+  DevBuf<float> terminal;
+  DevBuf<mcp_record> gather;               // [shards][K tile] records of all shards (shard 0 finishes the statistics)
+  HostBuf<float> h_packed;                 // pinned staging
+  HostBuf<double> h_pivot;                 // pinned staging of the [K tile] pivots
+  HostBuf<mcp_stats> stats;                // mapped: the last kernel of a pass writes the [K] records straight into host memory
+  struct {                                 // drawdown calls
+    DevBuf<float> mdd;                     // [K tile][paths] q / d of SPEC.md 4.2
+    HostBuf<mcp_stats> stats;              // the drawdown statistics, mapped
+  } dd;
+  struct {                                 // horizon calls
+    DevBuf<float> values;                  // [H][K tile][paths] V_h / S_h of SPEC.md 4.3
+    DevBuf<double> pivot;                  // [H][K tile] pivots (mcp_pivots at n_steps = h)
+    HostBuf<double> h_pivot;               // pinned staging of pivot
+    HostBuf<mcp_stats> stats;              // [1 + L][H][K tile] records of the alpha select and of every level's select, mapped
+  } hz;
+  DevBuf<float> boot;                      // bootstrap calls: [R][N4] observed rows, zero-padded (SPEC.md 2.1)
 };
+
+int grow_dev(void** p, size_t* cap, size_t need, hipStream_t zero_on = nullptr, bool zero = false) {
+  if (need <= *cap) return MCP_OK;
+  if (*p) (void)hipFree(*p);
+  *p = nullptr;
+  *cap = 0;
+  const size_t bytes = (need + 7) & ~(size_t)7;
+  if (hipMalloc(p, bytes) != hipSuccess) return fail(MCP_E_NOMEM, "hipMalloc(%zu) failed", bytes);
+  *cap = need;
+  if (zero) HIP_TRY(mcp::launch_zero(*p, bytes, zero_on));
+  return MCP_OK;
+}
+
+int grow_host(void** p, size_t* cap, size_t need, bool mapped = false) {
+  if (need <= *cap) return MCP_OK;
+  if (*p) (void)hipHostFree(*p);
+  *p = nullptr;
+  *cap = 0;
+  if (hipHostMalloc(p, need, mapped ? (hipHostMallocMapped | hipHostMallocPortable) : hipHostMallocPortable) != hipSuccess)   // portable: every device of a multi-device context copies from / writes to it
+    return fail(MCP_E_NOMEM, "hipHostMalloc(%zu) failed", need);
+  *cap = need;
+  return MCP_OK;
+}
+
+// `count` elements of T
+template <class T> int grow(DevBuf<T>& b, size_t count) { return grow_dev((void**)&b.p, &b.cap, count * sizeof(T)); }
+template <class T> int grow(HostBuf<T>& b, size_t count) { return grow_host((void**)&b.p, &b.cap, count * sizeof(T)); }
+template <class T> int grow_mapped(HostBuf<T>& b, size_t count) {
+  if (count * sizeof(T) <= b.cap) return MCP_OK;
+  if (int rc = grow_host((void**)&b.p, &b.cap, count * sizeof(T), true)) return rc;
+  HIP_TRY(hipHostGetDevicePointer(&b.dev, b.p, 0));
+  return MCP_OK;
+}
+
+template <class T> void release(DevBuf<T>& b) { if (b.p) (void)hipFree(b.p); }
+template <class T> void release(HostBuf<T>& b) { if (b.p) (void)hipHostFree(b.p); }
 
 // RCCL entry points, resolved at run time (no link-time dependency: a single-device user never loads librccl).
 // Prototypes as in /opt/rocm/include/rccl/rccl.h:236 (ncclCommInitAll), :260 (ncclCommDestroy), :339
@@ -432,7 +545,7 @@ struct mcp_ctx {
   size_t terminal_budget = (size_t)8 << 30;
   double* d_sweep = nullptr;         // inputs then outputs of mcp_sweep_historical (shard 0)
   size_t sweep_cap = 0;
-  float* h_boot = nullptr;           // bootstrap calls: pinned, portable [R][N4] padded rows, uploaded to every shard's d_boot
+  float* h_boot = nullptr;           // bootstrap calls: pinned, portable [R][N4] padded rows, uploaded to every shard's boot buffer
   size_t h_boot_cap = 0;
 };
 
@@ -532,10 +645,10 @@ int mcp_pivots(const mcp_params* prm, const float* mu, const float* chol, const 
 int mcp_rebalance_pivots(const mcp_params* prm, const mcp_rebalance* reb, const float* mu, const mcp_bootstrap* boot, const float* W,
                          double* out) {
   if (int rc = check_params(prm)) return rc;
-  if (int rc = check_reb(reb, nullptr)) return rc;
+  if (int rc = check_reb(reb)) return rc;
   if ((mu == nullptr) == (boot == nullptr)) return fail(MCP_E_ARG, "exactly one of mu and boot");
   if (boot)
-    if (int rc = check_boot(prm, boot, nullptr)) return rc;
+    if (int rc = check_boot(prm, boot)) return rc;
   if (!W || !out) return fail(MCP_E_ARG, "NULL pointer");
   if (prm->compounding != MCP_COMPOUND_SIMPLE) return fail(MCP_E_UNSUPPORTED, "rebalanced paths compound simply (no log compounding)");
   std::vector<double> m((size_t)prm->n_assets);
@@ -546,7 +659,7 @@ int mcp_rebalance_pivots(const mcp_params* prm, const mcp_rebalance* reb, const 
 
 int mcp_bootstrap_pivots(const mcp_params* prm, const mcp_bootstrap* boot, const float* W, double* out) {
   if (int rc = check_params(prm)) return rc;
-  if (int rc = check_boot(prm, boot, nullptr)) return rc;
+  if (int rc = check_boot(prm, boot)) return rc;
   if (!W || !out) return fail(MCP_E_ARG, "NULL pointer");
   const int K = prm->n_portfolios;
   std::vector<double> m((size_t)K), s2((size_t)K);
@@ -557,106 +670,93 @@ int mcp_bootstrap_pivots(const mcp_params* prm, const mcp_bootstrap* boot, const
 
 }  // extern "C"
 
-// The horizon output of a launch (SPEC.md 4.3): n horizon steps (host), the [n][K][stride] array.
-struct HzOut {
-  int n = 0;
-  const int32_t* steps = nullptr;
-  float* d_out = nullptr;
-  uint64_t stride = 0;
-};
+// The blocks that the family kernels add to PathArgs (mcp_paths.h), filled from the request and its launch.
+static void fill_hz(mcp::PathArgsHZ& x, const Request& rq, const Launch& ln) {
+  x.hz = rq.hz ? ln.d_hz : nullptr;
+  x.hz_stride = rq.hz ? ln.hz_stride : 0;
+  x.n_horizons = rq.hz ? rq.H : 0;
+  for (int i = 0; i < MCP_MAX_HORIZONS; i++) x.steps[i] = i < x.n_horizons ? rq.steps[i] : 0;
+}
+static mcp::BootArgs boot_block(const Request& rq, const Launch& ln) {
+  mcp::BootArgs bt;
+  const bool on = rq.src == SRC_BOOT;
+  bt.rows = on ? (const float4*)ln.d_rows : nullptr;
+  bt.thr = on ? boot_threshold(rq.boot->mean_block) : 0;
+  bt.n_rows = on ? (uint32_t)rq.boot->n_rows : 0;
+  bt.pad = 0;
+  return bt;
+}
+static mcp::StudentArgs student_block(const Request& rq) {
+  mcp::StudentArgs st;
+  st.dof = rq.st->dof;
+  st.pad = 0;
+  return st;
+}
+static void fill(mcp::PathArgs&, const Request&, const Launch&) {}
+static void fill(mcp::PathArgsDD& x, const Request&, const Launch& ln) { x.mdd = ln.d_mdd; x.mdd_stride = ln.mdd_stride; }
+static void fill(mcp::PathArgsHZ& x, const Request& rq, const Launch& ln) { fill_hz(x, rq, ln); }
+static void fill(mcp::PathArgsBT& x, const Request& rq, const Launch& ln) { x.bt = boot_block(rq, ln); }
+static void fill(mcp::PathArgsBTHZ& x, const Request& rq, const Launch& ln) { fill_hz(x, rq, ln); x.bt = boot_block(rq, ln); }
+static void fill(mcp::PathArgsT& x, const Request& rq, const Launch&) { x.st = student_block(rq); }
+static void fill(mcp::PathArgsTDD& x, const Request& rq, const Launch& ln) { fill((mcp::PathArgsDD&)x, rq, ln); x.st = student_block(rq); }
+static void fill(mcp::PathArgsTHZ& x, const Request& rq, const Launch& ln) { fill_hz(x, rq, ln); x.st = student_block(rq); }
+static void fill(mcp::PathArgsRB& x, const Request& rq, const Launch& ln) {
+  fill_hz(x, rq, ln);
+  x.bt = boot_block(rq, ln);
+  x.period = rq.reb->period;
+  x.cost = (float)rq.reb->cost;
+}
 
-// The row table of a bootstrap launch (SPEC.md 2.1): the device copy [n_rows][N4], zero-padded, and the restart threshold.
-struct BootIn {
-  const float* d_rows = nullptr;
-  uint32_t n_rows = 0;
-  uint64_t thr = 0;
-};
+// The passes of KT portfolios of kernel `k`, whose argument struct is A: PathArgs `a`, then the blocks of A.
+template <class A>
+static int launch_passes(const mcp::PathArgs& a, const Request& rq, const Launch& ln, int variant, const mcp::PathKernel& k, int nb) {
+  A x;
+  static_cast<mcp::PathArgs&>(x) = a;
+  fill(x, rq, ln);
+  const int kt = (variant & mcp::VAR_KT8) ? KT_WIDE : 1;
+  for (int kb = 0; kb < a.n_portfolios; kb += kt) {
+    x.k_begin = kb;
+    const hipError_t e = k_launch[nb - 1](variant, k, x, mcp::path_grid(ln.n_paths), ln.stream);
+    if (e != hipSuccess) return fail(MCP_E_HIP, "path kernel launch (family %d): %s", k.family, hipGetErrorString(e));
+  }
+  return MCP_OK;
+}
 
-// mcp_launch_paths (d_mdd and hz NULL), mcp_launch_paths_drawdown and mcp_launch_paths_horizons.  A drawdown or horizon launch
-// always runs mc_paths_dd_kernel / mc_paths_hz_kernel, K >= 17 as passes of the 8-portfolio kernel: the MFMA sweep kernels
-// track neither the path's peak nor its intermediate values.  Its moment partials keep the layout mcp_moment_slots(K, n) gives
-// (what mcp_launch_scan reads): where that is one slot per 64-path tile (K >= 17), an empty pass 0 first pads every slot, and
-// the path kernel's workgroups overwrite the first path_grid(n) of them.
-static int launch_paths_impl(const mcp_params* prm, const float* d_packed, const double* d_pivot, uint64_t seed, uint64_t path_begin,
-                             uint64_t n_paths, float* d_terminal, uint64_t stride, float* d_mdd, uint64_t mdd_stride, void* d_partials,
-                             void* d_hist, void* stream, const HzOut* hz = nullptr, const BootIn* boot = nullptr,
-                             const RebReq* reb = nullptr, const StReq* st = nullptr) {
-  const bool dd = d_mdd != nullptr;
-  if (int rc = check_params(prm)) return rc;
-  if (!d_packed || !d_terminal) return fail(MCP_E_ARG, "NULL device pointer");
-  if (dd && (prm->flags & (MCP_FLAG_FOLD | MCP_FLAG_NATIVE_MATH)))
-    return fail(MCP_E_UNSUPPORTED, "the drawdown runs on the spec's normals and the unfolded recurrence (no MCP_FLAG_FOLD / MCP_FLAG_NATIVE_MATH)");
-  if (dd && mdd_stride < n_paths) return fail(MCP_E_ARG, "mdd_stride %llu < n_paths %llu", (unsigned long long)mdd_stride,
-                                              (unsigned long long)n_paths);
-  if (hz) {
-    if (dd) return fail(MCP_E_UNSUPPORTED, "horizons and the drawdown are not tracked in one walk");
-    if (prm->flags & (MCP_FLAG_FOLD | MCP_FLAG_NATIVE_MATH))
-      return fail(MCP_E_UNSUPPORTED, "the horizons run on the spec's normals and the unfolded recurrence (no MCP_FLAG_FOLD / MCP_FLAG_NATIVE_MATH)");
-    if (int rc = check_horizons(prm->n_steps, hz->n, hz->steps)) return rc;
-    if (!hz->d_out) return fail(MCP_E_ARG, "d_horizon is NULL");
-    if (hz->stride < n_paths) return fail(MCP_E_ARG, "horizon_stride %llu < n_paths %llu", (unsigned long long)hz->stride,
-                                          (unsigned long long)n_paths);
-  }
-  if (boot) {
-    if (dd) return fail(MCP_E_UNSUPPORTED, "the drawdown is not tracked on bootstrap paths");
-    if (prm->flags & (MCP_FLAG_FOLD | MCP_FLAG_NATIVE_MATH))
-      return fail(MCP_E_UNSUPPORTED, "bootstrap paths draw no normals (no MCP_FLAG_FOLD / MCP_FLAG_NATIVE_MATH)");
-    if (!boot->d_rows || boot->n_rows < 1 || boot->n_rows > (uint32_t)MCP_MAX_BOOT_ROWS) return fail(MCP_E_ARG, "bad bootstrap table");
-  }
-  if (reb) {
-    if (dd) return fail(MCP_E_UNSUPPORTED, "the drawdown is not tracked on rebalanced paths");
-    if (prm->compounding != MCP_COMPOUND_SIMPLE) return fail(MCP_E_UNSUPPORTED, "rebalanced paths compound simply (no log compounding)");
-    if (prm->flags & (MCP_FLAG_FOLD | MCP_FLAG_NATIVE_MATH))
-      return fail(MCP_E_UNSUPPORTED, "rebalanced paths run on the unfolded recurrence and the spec's normals (no MCP_FLAG_FOLD / MCP_FLAG_NATIVE_MATH)");
-    if (reb->period < 0 || !(reb->cost >= 0.0f && reb->cost <= 1.0f)) return fail(MCP_E_ARG, "bad rebalancing rule");
-  }
-  if (st) {
-    if (boot || reb) return fail(MCP_E_UNSUPPORTED, "Student-t draws are not combined with the bootstrap or rebalancing");
-    if (prm->compounding != MCP_COMPOUND_SIMPLE) return fail(MCP_E_UNSUPPORTED, "Student-t paths compound simply (no log compounding)");
-    if (prm->flags & (MCP_FLAG_FOLD | MCP_FLAG_NATIVE_MATH))
-      return fail(MCP_E_UNSUPPORTED, "Student-t paths run on the spec's normals and the unfolded recurrence (no MCP_FLAG_FOLD / MCP_FLAG_NATIVE_MATH)");
-    if (st->dof < 3 || st->dof > MCP_MAX_T_DOF || (uint64_t)prm->n_steps * (uint64_t)((st->dof + 3) / 4) > 0xFFFFFFFFull)
-      return fail(MCP_E_ARG, "bad Student-t request");
-  }
-  if ((d_partials == nullptr) != (d_hist == nullptr)) return fail(MCP_E_ARG, "d_partials and d_hist go together (both or neither)");
-  if (n_paths < 1) return fail(MCP_E_ARG, "n_paths must be >= 1");
-  if (stride < n_paths) return fail(MCP_E_ARG, "terminal_stride %llu < n_paths %llu",
-                                    (unsigned long long)stride, (unsigned long long)n_paths);
-  const int grid = mcp::path_grid(n_paths);
-  if (!boot && (uint64_t)prm->n_steps * (uint64_t)((prm->n_assets + 3) / 4) > 0xFFFFFFFFull)
-    return fail(MCP_E_UNSUPPORTED, "n_steps * ceil(N/4) exceeds the 32-bit Philox block counter");
+// Enqueues the path kernels of a checked request (check_request).  Plain Gaussian walks with K >= 17 run on the MFMA sweep
+// kernels; every other request runs its family's kernel, K >= 17 as passes of the 8-portfolio kernel (the sweep kernels track
+// neither the path's peak, its intermediate values, rows nor t draws).  Its moment partials keep the layout mcp_moment_slots(K, n)
+// gives (what mcp_launch_scan reads): where that is one slot per 64-path tile (K >= 17), an empty pass 0 first pads every slot,
+// and the path kernel's workgroups overwrite the first path_grid(n) of them.
+static int launch_paths_impl(const mcp_params* prm, const Request& rq, const Launch& ln) {
   const int nb = (prm->n_assets + 3) / 4;
   const int K = prm->n_portfolios;
+  const bool plain = rq.src == SRC_GAUSS && !rq.dd && !rq.hz && !rq.rebalanced;
   int variant = 0;
-  if (prm->flags & MCP_FLAG_FOLD) {
-    if (K != 1 || (prm->flags & MCP_FLAG_NATIVE_MATH)) return fail(MCP_E_UNSUPPORTED, "MCP_FLAG_FOLD needs one portfolio and the spec's normals");
-    variant |= mcp::VAR_FOLD;
-  }
+  if (prm->flags & MCP_FLAG_FOLD) variant |= mcp::VAR_FOLD;
   if (K > 1) variant |= mcp::VAR_KT8;
   if (prm->flags & MCP_FLAG_NATIVE_MATH) variant |= mcp::VAR_NATIVE;
-  const int kt = (variant & mcp::VAR_KT8) ? KT_WIDE : 1;
   mcp::PathArgs a;
   const float4* tables = nullptr;
   int dev = 0;
-  if (int rc = stream_device((hipStream_t)stream, &dev)) return rc;
+  if (int rc = stream_device(ln.stream, &dev)) return rc;
   DeviceGuard guard(dev);                 // the stream may belong to another device than the thread's current one
   if (guard.err != hipSuccess) return fail(MCP_E_HIP, "hipSetDevice(%d): %s", dev, hipGetErrorString(guard.err));
-  if (int rc = device_tables(dev, (hipStream_t)stream, &tables)) return rc;
-  const bool sweep = !dd && !hz && !boot && !reb && !st && uses_sweep(K);
+  if (int rc = device_tables(dev, ln.stream, &tables)) return rc;
+  const bool sweep = plain && uses_sweep(K);
   a.tables = tables;
-  a.packed = d_packed;
-  a.terminal = d_terminal;
-  a.pivot = d_pivot;
-  a.partials = (mcp::MomentPartial*)d_partials;
-  a.hist = sweep ? nullptr : (unsigned long long*)d_hist;     // the sweep kernels leave digit 0 to hist(0) below
-  a.slots = (dd || hz || boot || reb || st) ? mcp_moment_slots(K, n_paths) : mcp::moment_slots(sweep, n_paths);
+  a.packed = ln.d_packed;
+  a.terminal = ln.d_terminal;
+  a.pivot = ln.d_pivot;
+  a.partials = (mcp::MomentPartial*)ln.d_partials;
+  a.hist = sweep ? nullptr : (unsigned long long*)ln.d_hist;     // the sweep kernels leave digit 0 to hist(0) below
+  a.slots = mcp_moment_slots(K, ln.n_paths);
   a.v0d = (double)(float)prm->v0;
   a.inv_v0d = 1.0 / a.v0d;
   { int e = 0; a.v0_pow2 = std::frexp(a.v0d, &e) == 0.5; }
-  a.seed = seed;
-  a.path_begin = path_begin;
-  a.n_paths = n_paths;
-  a.stride = stride;
+  a.seed = ln.seed;
+  a.path_begin = ln.path_begin;
+  a.n_paths = ln.n_paths;
+  a.stride = ln.stride;
   a.n_steps = prm->n_steps;
   a.n_portfolios = K;
   a.compounding = prm->compounding;
@@ -671,162 +771,87 @@ static int launch_paths_impl(const mcp_params* prm, const float* d_packed, const
     for (int i = 0; i < n_seg && e == hipSuccess; i++) {
       a.k_begin = segs[i].k_begin;
       a.k_count = segs[i].k_count;
-      e = segs[i].shared ? mcp::launch_sweep_shared(nb, segs[i].mt, native, a, (hipStream_t)stream)
-                         : mcp::launch_sweep_paths(nb, segs[i].mt, native, a, (hipStream_t)stream);
+      e = segs[i].shared ? mcp::launch_sweep_shared(nb, segs[i].mt, native, a, ln.stream)
+                         : mcp::launch_sweep_paths(nb, segs[i].mt, native, a, ln.stream);
     }
     if (e != hipSuccess) return fail(MCP_E_HIP, "mc_sweep_kernel launch: %s", hipGetErrorString(e));
-    if (d_hist) {                              // digit 0 of the select: one lean read of the terminal values just written
-      e = mcp::launch_hist(*prm, K, 0, d_terminal, stride, n_paths, nullptr, d_pivot, nullptr, (unsigned long long*)d_hist, (hipStream_t)stream);
+    if (ln.d_hist) {                           // digit 0 of the select: one lean read of the terminal values just written
+      e = mcp::launch_hist(*prm, K, 0, ln.d_terminal, ln.stride, ln.n_paths, nullptr, ln.d_pivot, nullptr, (unsigned long long*)ln.d_hist,
+                           ln.stream);
       if (e != hipSuccess) return fail(MCP_E_HIP, "hist_kernel<0> launch: %s", hipGetErrorString(e));
     }
     return MCP_OK;
   }
-  if ((dd || hz || boot || reb || st) && d_partials && a.slots > (uint64_t)grid)
-    HIP_TRY(mcp::launch_pass0(*prm, K, d_terminal, stride, 0, nullptr, a.slots, (mcp::MomentPartial*)d_partials,
-                              (unsigned long long*)d_hist, (hipStream_t)stream));
-  if (st) {                               // SPEC.md 2.2 / 4.6: the t twin of the plain, drawdown or horizon kernel
-    mcp::StudentArgs sa;
-    sa.dof = st->dof;
-    sa.pad = 0;
-    mcp::PathArgsT at;
-    mcp::PathArgsTDD ad;
-    mcp::PathArgsTHZ ah;
-    if (hz) {
-      static_cast<mcp::PathArgs&>(ah) = a;
-      ah.hz = hz->d_out;
-      ah.hz_stride = hz->stride;
-      ah.n_horizons = hz->n;
-      for (int i = 0; i < MCP_MAX_HORIZONS; i++) ah.steps[i] = i < hz->n ? hz->steps[i] : 0;
-      ah.st = sa;
-    } else if (dd) {
-      static_cast<mcp::PathArgs&>(ad) = a;
-      ad.mdd = d_mdd;
-      ad.mdd_stride = mdd_stride;
-      ad.st = sa;
-    } else {
-      static_cast<mcp::PathArgs&>(at) = a;
-      at.st = sa;
-    }
-    for (int kb = 0; kb < K; kb += kt) {
-      at.k_begin = ad.k_begin = ah.k_begin = kb;
-      hipError_t e = k_launch_t[nb - 1](variant, hz || dd ? nullptr : &at, dd ? &ad : nullptr, hz ? &ah : nullptr, grid,
-                                        (hipStream_t)stream);
-      if (e != hipSuccess) return fail(MCP_E_HIP, "mc_paths_t_kernel launch: %s", hipGetErrorString(e));
-    }
-    return MCP_OK;
+  if (!plain && ln.d_partials && a.slots > (uint64_t)mcp::path_grid(ln.n_paths))
+    HIP_TRY(mcp::launch_pass0(*prm, K, ln.d_terminal, ln.stride, 0, nullptr, a.slots, (mcp::MomentPartial*)ln.d_partials,
+                              (unsigned long long*)ln.d_hist, ln.stream));
+  mcp::PathKernel k;
+  k.family = rq.rebalanced ? mcp::FAM_REB : rq.dd ? mcp::FAM_DD : rq.hz ? mcp::FAM_HZ : mcp::FAM_PLAIN;
+  k.logc = prm->compounding == MCP_COMPOUND_LOG;
+  k.boot = rq.src == SRC_BOOT;
+  k.blds = k.boot && mcp::boot_fits_lds((uint64_t)rq.boot->n_rows, nb);
+  k.stt = rq.src == SRC_T;
+  switch (k.family) {
+    case mcp::FAM_REB: return launch_passes<mcp::PathArgsRB>(a, rq, ln, variant, k, nb);
+    case mcp::FAM_DD: return k.stt ? launch_passes<mcp::PathArgsTDD>(a, rq, ln, variant, k, nb)
+                                   : launch_passes<mcp::PathArgsDD>(a, rq, ln, variant, k, nb);
+    case mcp::FAM_HZ: return k.stt ? launch_passes<mcp::PathArgsTHZ>(a, rq, ln, variant, k, nb)
+                           : k.boot ? launch_passes<mcp::PathArgsBTHZ>(a, rq, ln, variant, k, nb)
+                                    : launch_passes<mcp::PathArgsHZ>(a, rq, ln, variant, k, nb);
+    default: return k.stt ? launch_passes<mcp::PathArgsT>(a, rq, ln, variant, k, nb)
+                  : k.boot ? launch_passes<mcp::PathArgsBT>(a, rq, ln, variant, k, nb)
+                           : launch_passes<mcp::PathArgs>(a, rq, ln, variant, k, nb);
   }
-  if (reb) {                              // SPEC.md 4.5: one kernel for every draw source, with or without horizons
-    mcp::PathArgsRB ar;
-    static_cast<mcp::PathArgs&>(ar) = a;
-    ar.hz = hz ? hz->d_out : nullptr;
-    ar.hz_stride = hz ? hz->stride : 0;
-    ar.n_horizons = hz ? hz->n : 0;
-    for (int i = 0; i < MCP_MAX_HORIZONS; i++) ar.steps[i] = hz && i < hz->n ? hz->steps[i] : 0;
-    ar.bt.rows = boot ? (const float4*)boot->d_rows : nullptr;
-    ar.bt.thr = boot ? boot->thr : 0;
-    ar.bt.n_rows = boot ? boot->n_rows : 0;
-    ar.bt.pad = 0;
-    ar.period = reb->period;
-    ar.cost = reb->cost;
-    const bool lds = boot && mcp::boot_fits_lds(boot->n_rows, nb);
-    for (int kb = 0; kb < K; kb += kt) {
-      ar.k_begin = kb;
-      hipError_t e = k_launch_rb[nb - 1](variant, boot != nullptr, lds, ar, grid, (hipStream_t)stream);
-      if (e != hipSuccess) return fail(MCP_E_HIP, "mc_paths_reb_kernel launch: %s", hipGetErrorString(e));
-    }
-    return MCP_OK;
-  }
-  if (boot) {
-    mcp::BootArgs bt;
-    bt.rows = (const float4*)boot->d_rows;
-    bt.thr = boot->thr;
-    bt.n_rows = boot->n_rows;
-    bt.pad = 0;
-    const bool lds = mcp::boot_fits_lds(boot->n_rows, nb);
-    if (hz) {
-      mcp::PathArgsBTHZ ab;
-      static_cast<mcp::PathArgs&>(ab) = a;
-      ab.hz = hz->d_out;
-      ab.hz_stride = hz->stride;
-      ab.n_horizons = hz->n;
-      for (int i = 0; i < MCP_MAX_HORIZONS; i++) ab.steps[i] = i < hz->n ? hz->steps[i] : 0;
-      ab.bt = bt;
-      for (int kb = 0; kb < K; kb += kt) {
-        ab.k_begin = kb;
-        hipError_t e = k_launch_bthz[nb - 1](variant, lds, ab, grid, (hipStream_t)stream);
-        if (e != hipSuccess) return fail(MCP_E_HIP, "mc_paths_boot_hz_kernel launch: %s", hipGetErrorString(e));
-      }
-    } else {
-      mcp::PathArgsBT ab;
-      static_cast<mcp::PathArgs&>(ab) = a;
-      ab.bt = bt;
-      for (int kb = 0; kb < K; kb += kt) {
-        ab.k_begin = kb;
-        hipError_t e = k_launch_bt[nb - 1](variant, lds, ab, grid, (hipStream_t)stream);
-        if (e != hipSuccess) return fail(MCP_E_HIP, "mc_paths_boot_kernel launch: %s", hipGetErrorString(e));
-      }
-    }
-    return MCP_OK;
-  }
-  if (hz) {
-    mcp::PathArgsHZ ah;
-    static_cast<mcp::PathArgs&>(ah) = a;
-    ah.hz = hz->d_out;
-    ah.hz_stride = hz->stride;
-    ah.n_horizons = hz->n;
-    for (int i = 0; i < MCP_MAX_HORIZONS; i++) ah.steps[i] = i < hz->n ? hz->steps[i] : 0;
-    for (int kb = 0; kb < K; kb += kt) {
-      ah.k_begin = kb;
-      hipError_t e = k_launch_hz[nb - 1](variant, ah, grid, (hipStream_t)stream);
-      if (e != hipSuccess) return fail(MCP_E_HIP, "mc_paths_hz_kernel launch: %s", hipGetErrorString(e));
-    }
-    return MCP_OK;
-  }
-  if (dd) {
-    mcp::PathArgsDD ad;
-    static_cast<mcp::PathArgs&>(ad) = a;
-    ad.mdd = d_mdd;
-    ad.mdd_stride = mdd_stride;
-    for (int kb = 0; kb < K; kb += kt) {
-      ad.k_begin = kb;
-      hipError_t e = k_launch_dd[nb - 1](variant, ad, grid, (hipStream_t)stream);
-      if (e != hipSuccess) return fail(MCP_E_HIP, "mc_paths_dd_kernel launch: %s", hipGetErrorString(e));
-    }
-    return MCP_OK;
-  }
-  for (int kb = 0; kb < K; kb += kt) {
-    a.k_begin = kb;
-    hipError_t e = k_launch[nb - 1](variant, a, grid, (hipStream_t)stream);
-    if (e != hipSuccess) return fail(MCP_E_HIP, "mc_paths_kernel launch: %s", hipGetErrorString(e));
-  }
-  return MCP_OK;
+}
+
+static Launch make_launch(const float* d_packed, const double* d_pivot, uint64_t seed, uint64_t path_begin, uint64_t n_paths,
+                          float* d_terminal, uint64_t stride, void* d_partials, void* d_hist, void* stream) {
+  Launch ln;
+  ln.d_packed = d_packed;
+  ln.d_pivot = d_pivot;
+  ln.seed = seed;
+  ln.path_begin = path_begin;
+  ln.n_paths = n_paths;
+  ln.d_terminal = d_terminal;
+  ln.stride = stride;
+  ln.d_partials = d_partials;
+  ln.d_hist = d_hist;
+  ln.stream = (hipStream_t)stream;
+  return ln;
+}
+
+static int launch_checked(const mcp_params* prm, const Request& rq, const Launch& ln) {
+  if (int rc = check_request(prm, rq, ln.n_paths, &ln)) return rc;
+  return launch_paths_impl(prm, rq, ln);
 }
 
 extern "C" {
 
 int mcp_launch_paths(const mcp_params* prm, const float* d_packed, const double* d_pivot, uint64_t seed, uint64_t path_begin,
                      uint64_t n_paths, float* d_terminal, uint64_t stride, void* d_partials, void* d_hist, void* stream) {
-  return launch_paths_impl(prm, d_packed, d_pivot, seed, path_begin, n_paths, d_terminal, stride, nullptr, 0, d_partials, d_hist, stream);
+  return launch_checked(prm, Request(), make_launch(d_packed, d_pivot, seed, path_begin, n_paths, d_terminal, stride, d_partials, d_hist, stream));
 }
 
 int mcp_launch_paths_drawdown(const mcp_params* prm, const float* d_packed, const double* d_pivot, uint64_t seed, uint64_t path_begin,
                               uint64_t n_paths, float* d_terminal, uint64_t terminal_stride, float* d_mdd, uint64_t mdd_stride,
                               void* d_partials, void* d_hist, void* stream) {
-  if (!d_mdd) return fail(MCP_E_ARG, "d_mdd is NULL");
-  return launch_paths_impl(prm, d_packed, d_pivot, seed, path_begin, n_paths, d_terminal, terminal_stride, d_mdd, mdd_stride,
-                           d_partials, d_hist, stream);
+  Request rq;
+  rq.dd = true;
+  Launch ln = make_launch(d_packed, d_pivot, seed, path_begin, n_paths, d_terminal, terminal_stride, d_partials, d_hist, stream);
+  ln.d_mdd = d_mdd;
+  ln.mdd_stride = mdd_stride;
+  return launch_checked(prm, rq, ln);
 }
 
 int mcp_launch_paths_horizons(const mcp_params* prm, const float* d_packed, const double* d_pivot, uint64_t seed, uint64_t path_begin,
                               uint64_t n_paths, float* d_terminal, uint64_t terminal_stride, int n_horizons, const int32_t* horizons,
                               float* d_horizon, uint64_t horizon_stride, void* d_partials, void* d_hist, void* stream) {
-  HzOut hz;
-  hz.n = n_horizons;
-  hz.steps = horizons;
-  hz.d_out = d_horizon;
-  hz.stride = horizon_stride;
-  return launch_paths_impl(prm, d_packed, d_pivot, seed, path_begin, n_paths, d_terminal, terminal_stride, nullptr, 0, d_partials,
-                           d_hist, stream, &hz);
+  Request rq;
+  ask_horizons(rq, true, n_horizons, horizons, 0, nullptr, nullptr, nullptr, nullptr);
+  Launch ln = make_launch(d_packed, d_pivot, seed, path_begin, n_paths, d_terminal, terminal_stride, d_partials, d_hist, stream);
+  ln.d_hz = d_horizon;
+  ln.hz_stride = horizon_stride;
+  return launch_checked(prm, rq, ln);
 }
 
 // Launches below go to the device that owns the stream.
@@ -990,19 +1015,19 @@ static void free_shard(Shard& sh) {
   if (sh.ev) (void)hipEventDestroy(sh.ev);
   for (int i = 0; i < MCP_WS_COUNT; i++)
     if (sh.ws[i] && i != MCP_WS_STATS) (void)hipFree(sh.ws[i]);
-  if (sh.d_packed) (void)hipFree(sh.d_packed);
-  if (sh.d_terminal) (void)hipFree(sh.d_terminal);
-  if (sh.d_gather) (void)hipFree(sh.d_gather);
-  if (sh.h_packed) (void)hipHostFree(sh.h_packed);
-  if (sh.h_pivot) (void)hipHostFree(sh.h_pivot);
-  if (sh.h_stats) (void)hipHostFree(sh.h_stats);
-  if (sh.d_mdd) (void)hipFree(sh.d_mdd);
-  if (sh.h_dd_stats) (void)hipHostFree(sh.h_dd_stats);
-  if (sh.d_hz) (void)hipFree(sh.d_hz);
-  if (sh.d_hz_pivot) (void)hipFree(sh.d_hz_pivot);
-  if (sh.h_hz_pivot) (void)hipHostFree(sh.h_hz_pivot);
-  if (sh.h_hz_stats) (void)hipHostFree(sh.h_hz_stats);
-  if (sh.d_boot) (void)hipFree(sh.d_boot);
+  release(sh.packed);
+  release(sh.terminal);
+  release(sh.gather);
+  release(sh.h_packed);
+  release(sh.h_pivot);
+  release(sh.stats);
+  release(sh.dd.mdd);
+  release(sh.dd.stats);
+  release(sh.hz.values);
+  release(sh.hz.pivot);
+  release(sh.hz.h_pivot);
+  release(sh.hz.stats);
+  release(sh.boot);
 }
 
 int mcp_ctx_create_multi(const int* devices, int ndev, mcp_ctx** out) {
@@ -1116,29 +1141,6 @@ void mcp_ctx_destroy(mcp_ctx* c) {
   delete c;
 }
 
-static int grow_dev(void** p, size_t* cap, size_t need, hipStream_t zero_on = nullptr, bool zero = false) {
-  if (need <= *cap) return MCP_OK;
-  if (*p) (void)hipFree(*p);
-  *p = nullptr;
-  *cap = 0;
-  const size_t bytes = (need + 7) & ~(size_t)7;
-  if (hipMalloc(p, bytes) != hipSuccess) return fail(MCP_E_NOMEM, "hipMalloc(%zu) failed", bytes);
-  *cap = need;
-  if (zero) HIP_TRY(mcp::launch_zero(*p, bytes, zero_on));
-  return MCP_OK;
-}
-
-static int grow_host(void** p, size_t* cap, size_t need, bool mapped = false) {
-  if (need <= *cap) return MCP_OK;
-  if (*p) (void)hipHostFree(*p);
-  *p = nullptr;
-  *cap = 0;
-  if (hipHostMalloc(p, need, mapped ? (hipHostMallocMapped | hipHostMallocPortable) : hipHostMallocPortable) != hipSuccess)   // portable: every device of a multi-device context copies from / writes to it
-    return fail(MCP_E_NOMEM, "hipHostMalloc(%zu) failed", need);
-  *cap = need;
-  return MCP_OK;
-}
-
 namespace {
 
 // What one shard does in one tile of portfolios.
@@ -1190,13 +1192,13 @@ int exchange_records(mcp_ctx* c, int kt) {
     HIP_TRY(hipSetDevice(s0.device));
     for (size_t s = 0; s < S; s++) {
       if (s) { HIP_TRY(hipEventRecord(c->sh[s].ev, c->sh[s].stream)); HIP_TRY(hipStreamWaitEvent(s0.stream, c->sh[s].ev, 0)); }
-      HIP_TRY(hipMemcpyAsync((char*)s0.d_gather + s * bytes, c->sh[s].ws[MCP_WS_RECORD], bytes, hipMemcpyDeviceToDevice, s0.stream));
+      HIP_TRY(hipMemcpyAsync((char*)s0.gather.p + s * bytes, c->sh[s].ws[MCP_WS_RECORD], bytes, hipMemcpyDeviceToDevice, s0.stream));
     }
     return MCP_OK;
   }
   RCCL_TRY(c, c->rccl->GroupStart());
   for (size_t s = 0; s < S; s++) {
-    const int r = c->rccl->AllGather(c->sh[s].ws[MCP_WS_RECORD], c->sh[s].d_gather, (size_t)kt * (sizeof(mcp_record) / sizeof(double)),
+    const int r = c->rccl->AllGather(c->sh[s].ws[MCP_WS_RECORD], c->sh[s].gather.p, (size_t)kt * (sizeof(mcp_record) / sizeof(double)),
                                      NCCL_FLOAT64, c->comms[s], c->sh[s].stream);
     if (r != 0) { (void)c->rccl->GroupEnd(); return fail(MCP_E_COMM, "ncclAllGather (shard %zu): %s", s, c->rccl->GetErrorString(r)); }
   }
@@ -1220,8 +1222,8 @@ int run_select(mcp_ctx* c, const std::vector<mcp_params>& tp, const std::vector<
   int rc;
   const int kt_x = tp[0].n_portfolios;         // path-sharded tiles: the same rows on every shard
   const auto stats_of = [&](Shard& sh, int rows) -> void* {
-    if (what == SEL_DRAWDOWN) return sh.d_dd_stats;
-    if (what == SEL_HORIZON) return (mcp_stats*)sh.d_hz_stats + (size_t)slot * rows;
+    if (what == SEL_DRAWDOWN) return sh.dd.stats.dev;
+    if (what == SEL_HORIZON) return (mcp_stats*)sh.hz.stats.dev + (size_t)slot * rows;
     return sh.ws[MCP_WS_STATS];
   };
   for (int pass = 0; pass < 3; pass++) {
@@ -1232,8 +1234,8 @@ int run_select(mcp_ctx* c, const std::vector<mcp_params>& tp, const std::vector<
       Shard& sh = c->sh[s];
       HIP_TRY(hipSetDevice(sh.device));
       const uint64_t stride = j.pn ? j.pn : 1;
-      const double* piv = what == SEL_DRAWDOWN ? nullptr : what == SEL_HORIZON ? sh.d_hz_pivot : (const double*)sh.ws[MCP_WS_PIVOT];
-      const float* src = what == SEL_DRAWDOWN ? sh.d_mdd : what == SEL_HORIZON ? sh.d_hz : sh.d_terminal;
+      const double* piv = what == SEL_DRAWDOWN ? nullptr : what == SEL_HORIZON ? sh.hz.pivot.p : (const double*)sh.ws[MCP_WS_PIVOT];
+      const float* src = what == SEL_DRAWDOWN ? sh.dd.mdd.p : what == SEL_HORIZON ? sh.hz.values.p : sh.terminal.p;
       if (pass < 2) {
         if ((rc = mcp_launch_scan(&tp[s], pass, j.pn, lo, hi, sh.ws[MCP_WS_PARTIALS], sh.ws[MCP_WS_BELOW], piv, sh.ws[MCP_WS_HIST],
                                   sh.ws[MCP_WS_STATE], sh.ws[MCP_WS_RECORD], sh.stream))) return rc;
@@ -1252,40 +1254,38 @@ int run_select(mcp_ctx* c, const std::vector<mcp_params>& tp, const std::vector<
     if ((rc = exchange_records(c, kt_x))) return rc;
     Shard& s0 = c->sh[0];
     HIP_TRY(hipSetDevice(s0.device));
-    if ((rc = mcp_launch_stats(&tp[0], (int)S, s0.d_gather, s0.ws[MCP_WS_QUANT], stats_of(s0, kt_x), s0.stream)))
+    if ((rc = mcp_launch_stats(&tp[0], (int)S, s0.gather.p, s0.ws[MCP_WS_QUANT], stats_of(s0, kt_x), s0.stream)))
       return rc;
   }
   return MCP_OK;
 }
 
-// The horizon request of mcp_simulate_horizons (SPEC.md 4.3 / 5.2).
-struct HzReq {
-  int H = 0, L = 0;
-  const int32_t* steps = nullptr;
-  const double* levels = nullptr;
-  float* out = nullptr;              // NULL or [H*K*n], row h*K + k
-  mcp_stats* stats_out = nullptr;    // [H*K]
-  double* bands_out = nullptr;       // [H*K*L]
-};
-
-// The bootstrap request of mcp_simulate_bootstrap[_horizons] (SPEC.md 2.1 / 5.3): the caller's rows (for the pivots; the padded
-// copy is already in every working shard's d_boot when a tile runs), R and the restart threshold.
-struct BootReq {
-  const mcp_bootstrap* boot = nullptr;
-  uint32_t n_rows = 0;
-  uint64_t thr = 0;
-};
+// The [kt] pivots of the portfolios W[0, kt) of a tile (tp.n_portfolios = kt) at T steps (SPEC.md 5): of rebalanced paths from
+// the draws' per-asset means rmu (5.4), of bootstrap paths from the row moments bm, bs2 (5.3), else mcp_pivots.
+int tile_pivots(const mcp_params& tp, const Request& rq, int T, const float* W, const double* rmu, const double* bm, const double* bs2,
+                double* out) {
+  if (rq.rebalanced) {
+    reb_pivots(tp.n_assets, tp.n_portfolios, T, rq.reb->period, rmu, W, out);
+    return MCP_OK;
+  }
+  if (rq.src == SRC_BOOT) {
+    for (int k = 0; k < tp.n_portfolios; k++) out[k] = boot_pivot(tp.compounding, T, bm[k], bs2[k]);
+    return MCP_OK;
+  }
+  mcp_params p = tp;
+  p.n_steps = T;
+  return mcp_pivots(&p, rq.mu, rq.chol, W, out);
+}
 
 // One tile: every active shard simulates its (portfolios x paths) block -- the kernels' epilogue leaves the moment partials
-// and the digit-0 histogram -- and the rest of the statistics pipeline runs (run_select).  `dd`: the path kernels also leave
+// and the digit-0 histogram -- and the rest of the statistics pipeline runs (run_select).  Drawdown: the path kernels also leave
 // the drawdown array, and after the terminal values a pass 0 over it and a second run_select reduce it to dd_stats_out.
-// `hz`: the path kernels also leave the [H][kt][pn] horizon array; after the terminal values it is reduced as H*kt rows, once
+// Horizons: the path kernels also leave the [H][kt][pn] horizon array; after the terminal values it is reduced as H*kt rows, once
 // at alpha (pass 0 + run_select) and once per level at that level's rank, whose records contribute only their `var`.
-int run_tile(mcp_ctx* c, const mcp_params* prm, const float* mu, const float* chol, const float* W, uint64_t seed,
-             uint64_t path_begin, uint64_t n_total, const std::vector<Job>& jobs, bool exchange, float* terminal_out,
-             mcp_stats* stats_out, bool dd, float* mdd_out, mcp_stats* dd_stats_out, const HzReq* hz, const BootReq* boot,
-             const RebReq* reb, const StReq* st) {
+int run_tile(mcp_ctx* c, const mcp_params* prm, const Request& rq, uint64_t seed, uint64_t path_begin, uint64_t n_total,
+             const std::vector<Job>& jobs, bool exchange) {
   const size_t S = c->sh.size();
+  const int N = prm->n_assets;
   uint64_t lo, hi;
   double gamma;
   if (int rc = mcp_percentile_rank(n_total, prm->alpha, &lo, &hi, &gamma)) return rc;
@@ -1298,40 +1298,21 @@ int run_tile(mcp_ctx* c, const mcp_params* prm, const float* mu, const float* ch
     Shard& sh = c->sh[s];
     HIP_TRY(hipSetDevice(sh.device));
     tp[s].n_portfolios = j.kt;
-    const size_t plen = mcp_packed_len(prm->n_assets, j.kt);
-    const int rows = hz ? hz->H * j.kt : j.kt;  // horizon calls: the work buffers also serve the H*kt rows of the horizon selects
-    for (int w = 0; w < MCP_WS_COUNT; w++) {    // only the histogram and the select state must start zeroed
-      const size_t need = std::max(mcp_ws_bytes(w, j.kt, j.pn ? j.pn : 1), mcp_ws_bytes(w, rows, j.pn ? j.pn : 1));
+    const size_t plen = mcp_packed_len(N, j.kt), pn = j.pn ? j.pn : 1;
+    const int rows = rq.hz ? rq.H * j.kt : j.kt;  // horizon calls: the work buffers also serve the H*kt rows of the horizon selects
+    for (int w = 0; w < MCP_WS_COUNT; w++) {      // only the histogram and the select state must start zeroed
+      const size_t need = std::max(mcp_ws_bytes(w, j.kt, pn), mcp_ws_bytes(w, rows, pn));
       if (w != MCP_WS_STATS && (rc = grow_dev(&sh.ws[w], &sh.ws_cap[w], need, sh.stream, w == MCP_WS_HIST || w == MCP_WS_STATE)))
         return rc;
     }
-    if ((rc = grow_dev((void**)&sh.d_packed, &sh.packed_cap, plen * sizeof(float)))) return rc;
-    if ((rc = grow_dev((void**)&sh.d_terminal, &sh.terminal_cap, (size_t)j.kt * (j.pn ? j.pn : 1) * sizeof(float)))) return rc;
-    if (exchange && (rc = grow_dev((void**)&sh.d_gather, &sh.gather_cap, S * (size_t)std::max(j.kt, rows) * sizeof(mcp_record))))
+    if ((rc = grow(sh.packed, plen)) || (rc = grow(sh.terminal, (size_t)j.kt * pn))) return rc;
+    if (exchange && (rc = grow(sh.gather, S * (size_t)std::max(j.kt, rows)))) return rc;
+    if ((rc = grow(sh.h_packed, plen)) || (rc = grow(sh.h_pivot, (size_t)j.kt)) || (rc = grow_mapped(sh.stats, (size_t)j.kt))) return rc;
+    sh.ws[MCP_WS_STATS] = sh.stats.dev;
+    if (rq.dd && ((rc = grow(sh.dd.mdd, (size_t)j.kt * pn)) || (rc = grow_mapped(sh.dd.stats, (size_t)j.kt)))) return rc;
+    if (rq.hz && ((rc = grow(sh.hz.values, (size_t)rows * pn)) || (rc = grow(sh.hz.pivot, (size_t)rows)) ||
+                  (rc = grow(sh.hz.h_pivot, (size_t)rows)) || (rc = grow_mapped(sh.hz.stats, (size_t)(1 + rq.L) * rows))))
       return rc;
-    if (hz) {
-      const size_t hz_stats_bytes = (size_t)(1 + hz->L) * rows * sizeof(mcp_stats);
-      if ((rc = grow_dev((void**)&sh.d_hz, &sh.hz_cap, (size_t)rows * (j.pn ? j.pn : 1) * sizeof(float)))) return rc;
-      if ((rc = grow_dev((void**)&sh.d_hz_pivot, &sh.hz_pivot_cap, (size_t)rows * sizeof(double)))) return rc;
-      if ((rc = grow_host((void**)&sh.h_hz_pivot, &sh.h_hz_pivot_cap, (size_t)rows * sizeof(double)))) return rc;
-      if (hz_stats_bytes > sh.h_hz_stats_cap) {
-        if ((rc = grow_host((void**)&sh.h_hz_stats, &sh.h_hz_stats_cap, hz_stats_bytes, true))) return rc;
-        HIP_TRY(hipHostGetDevicePointer(&sh.d_hz_stats, sh.h_hz_stats, 0));
-      }
-    }
-    if ((rc = grow_host((void**)&sh.h_packed, &sh.h_packed_cap, plen * sizeof(float)))) return rc;
-    if ((rc = grow_host((void**)&sh.h_pivot, &sh.h_pivot_cap, (size_t)j.kt * sizeof(double)))) return rc;
-    if ((size_t)j.kt * sizeof(mcp_stats) > sh.h_stats_cap) {
-      if ((rc = grow_host((void**)&sh.h_stats, &sh.h_stats_cap, (size_t)j.kt * sizeof(mcp_stats), true))) return rc;
-      HIP_TRY(hipHostGetDevicePointer(&sh.ws[MCP_WS_STATS], sh.h_stats, 0));
-    }
-    if (dd) {
-      if ((rc = grow_dev((void**)&sh.d_mdd, &sh.mdd_cap, (size_t)j.kt * (j.pn ? j.pn : 1) * sizeof(float)))) return rc;
-      if ((size_t)j.kt * sizeof(mcp_stats) > sh.h_dd_stats_cap) {
-        if ((rc = grow_host((void**)&sh.h_dd_stats, &sh.h_dd_stats_cap, (size_t)j.kt * sizeof(mcp_stats), true))) return rc;
-        HIP_TRY(hipHostGetDevicePointer(&sh.d_dd_stats, sh.h_dd_stats, 0));
-      }
-    }
   }
   // 1b. parameters up and the path kernels out, device after device with nothing else in between: every GPU should be
   //     simulating as early as possible.  Shards of a path-sharded tile share one packed block and one pivot vector
@@ -1340,91 +1321,63 @@ int run_tile(mcp_ctx* c, const mcp_params* prm, const float* mu, const float* ch
   const double* shared_pivot = nullptr;
   const double* shared_hz_pivot = nullptr;
   // bootstrap: no drift and no Cholesky factor in the packed block (only W is read), the pivots of SPEC.md 5.3 from the row
-  // moments (computed once per tile)
-  std::vector<float> zmu, zchol;
-  std::vector<double> bm, bs2, rmu;
-  if (reb) {                              // SPEC.md 5.4: the per-asset means of the draws, once per tile
-    rmu.resize((size_t)prm->n_assets);
-    reb_means(prm->n_assets, boot ? nullptr : mu, boot ? boot->boot : nullptr, rmu.data());
-  }
-  if (boot) {
-    zmu.assign((size_t)prm->n_assets, 0.0f);
-    zchol.assign((size_t)prm->n_assets * prm->n_assets, 0.0f);
-    mu = zmu.data();
-    chol = zchol.data();
-  }
+  // moments (computed once per tile); rebalancing: the per-asset means of the draws (SPEC.md 5.4), once per tile
+  const bool boot = rq.src == SRC_BOOT;
+  const std::vector<float> zmu(boot ? N : 0, 0.0f), zchol(boot ? (size_t)N * N : 0, 0.0f);
+  const float* mu = boot ? zmu.data() : rq.mu;
+  const float* chol = boot ? zchol.data() : rq.chol;
+  std::vector<double> bm, bs2, rmu(rq.rebalanced ? N : 0);
+  if (rq.rebalanced) reb_means(N, rq.mu, boot ? rq.boot : nullptr, rmu.data());
   for (size_t s = 0; s < S; s++) {
     const Job& j = jobs[s];
     if (!j.active) continue;
     Shard& sh = c->sh[s];
     HIP_TRY(hipSetDevice(sh.device));
-    const size_t plen = mcp_packed_len(prm->n_assets, j.kt);
-    const float* src = sh.h_packed;
-    const double* psrc = sh.h_pivot;
-    const double* hpsrc = sh.h_hz_pivot;
+    const size_t plen = mcp_packed_len(N, j.kt);
+    const float* src = sh.h_packed.p;
+    const double* psrc = sh.h_pivot.p;
+    const double* hpsrc = sh.hz.h_pivot.p;
     if (exchange && shared_packed) {
       src = shared_packed;                                   // same portfolios on every shard: pinned + portable
       psrc = shared_pivot;
       hpsrc = shared_hz_pivot;
     } else {
-      if ((rc = mcp_pack_params(prm->n_assets, j.kt, mu, chol, W + (size_t)j.k0 * prm->n_assets, sh.h_packed, plen))) return rc;
-      if (reb) {
-        reb_pivots(prm->n_assets, j.kt, prm->n_steps, reb->period, rmu.data(), W + (size_t)j.k0 * prm->n_assets, sh.h_pivot);
-      } else if (boot) {
+      const float* Wt = rq.W + (size_t)j.k0 * N;
+      if ((rc = mcp_pack_params(N, j.kt, mu, chol, Wt, sh.h_packed.p, plen))) return rc;
+      if (boot && !rq.rebalanced) {
         bm.resize((size_t)j.kt);
         bs2.resize((size_t)j.kt);
-        boot_moments(prm->n_assets, boot->boot, W + (size_t)j.k0 * prm->n_assets, j.kt, bm.data(), bs2.data());
-        for (int k = 0; k < j.kt; k++) sh.h_pivot[k] = boot_pivot(prm->compounding, prm->n_steps, bm[(size_t)k], bs2[(size_t)k]);
-      } else if ((rc = mcp_pivots(&tp[s], mu, chol, W + (size_t)j.k0 * prm->n_assets, sh.h_pivot))) {
-        return rc;
+        boot_moments(N, rq.boot, Wt, j.kt, bm.data(), bs2.data());
       }
-      if (hz) {                                              // SPEC.md 5.2 / 5.3: row h*kt + k is pivoted with n_steps = h
-        mcp_params ph = tp[s];
-        for (int h = 0; h < hz->H; h++) {
-          ph.n_steps = hz->steps[h];
-          double* hp = sh.h_hz_pivot + (size_t)h * j.kt;
-          if (reb) {
-            reb_pivots(prm->n_assets, j.kt, ph.n_steps, reb->period, rmu.data(), W + (size_t)j.k0 * prm->n_assets, hp);
-          } else if (boot) {
-            for (int k = 0; k < j.kt; k++) hp[k] = boot_pivot(prm->compounding, ph.n_steps, bm[(size_t)k], bs2[(size_t)k]);
-          } else if ((rc = mcp_pivots(&ph, mu, chol, W + (size_t)j.k0 * prm->n_assets, hp))) {
-            return rc;
-          }
-        }
-      }
-      if (exchange) { shared_packed = sh.h_packed; shared_pivot = sh.h_pivot; shared_hz_pivot = sh.h_hz_pivot; }
+      if ((rc = tile_pivots(tp[s], rq, prm->n_steps, Wt, rmu.data(), bm.data(), bs2.data(), sh.h_pivot.p))) return rc;
+      for (int h = 0; rq.hz && h < rq.H; h++)                // SPEC.md 5.2 / 5.3: row h*kt + k is pivoted with n_steps = h
+        if ((rc = tile_pivots(tp[s], rq, rq.steps[h], Wt, rmu.data(), bm.data(), bs2.data(), sh.hz.h_pivot.p + (size_t)h * j.kt)))
+          return rc;
+      if (exchange) { shared_packed = sh.h_packed.p; shared_pivot = sh.h_pivot.p; shared_hz_pivot = sh.hz.h_pivot.p; }
     }
-    HIP_TRY(hipMemcpyAsync(sh.d_packed, src, plen * sizeof(float), hipMemcpyHostToDevice, sh.stream));
+    HIP_TRY(hipMemcpyAsync(sh.packed.p, src, plen * sizeof(float), hipMemcpyHostToDevice, sh.stream));
     HIP_TRY(hipMemcpyAsync(sh.ws[MCP_WS_PIVOT], psrc, (size_t)j.kt * sizeof(double), hipMemcpyHostToDevice, sh.stream));
-    HzOut hzo;
-    if (hz) {
-      HIP_TRY(hipMemcpyAsync(sh.d_hz_pivot, hpsrc, (size_t)hz->H * j.kt * sizeof(double), hipMemcpyHostToDevice, sh.stream));
-      hzo.n = hz->H;
-      hzo.steps = hz->steps;
-      hzo.d_out = sh.d_hz;
-      hzo.stride = j.pn;
-    }
-    BootIn bti;
-    if (boot) {
-      bti.d_rows = sh.d_boot;
-      bti.n_rows = boot->n_rows;
-      bti.thr = boot->thr;
-    }
+    if (rq.hz) HIP_TRY(hipMemcpyAsync(sh.hz.pivot.p, hpsrc, (size_t)rq.H * j.kt * sizeof(double), hipMemcpyHostToDevice, sh.stream));
     if (j.pn) {
-      if ((rc = launch_paths_impl(&tp[s], sh.d_packed, (const double*)sh.ws[MCP_WS_PIVOT], seed, path_begin + j.p0, j.pn, sh.d_terminal,
-                                  j.pn, dd ? sh.d_mdd : nullptr, j.pn, sh.ws[MCP_WS_PARTIALS], sh.ws[MCP_WS_HIST], sh.stream,
-                                  hz ? &hzo : nullptr, boot ? &bti : nullptr, reb, st))) return rc;
+      Launch ln = make_launch(sh.packed.p, (const double*)sh.ws[MCP_WS_PIVOT], seed, path_begin + j.p0, j.pn, sh.terminal.p, j.pn,
+                              sh.ws[MCP_WS_PARTIALS], sh.ws[MCP_WS_HIST], sh.stream);
+      ln.d_mdd = sh.dd.mdd.p;
+      ln.mdd_stride = j.pn;
+      ln.d_hz = sh.hz.values.p;
+      ln.hz_stride = j.pn;
+      ln.d_rows = sh.boot.p;
+      if ((rc = launch_paths_impl(&tp[s], rq, ln))) return rc;
     } else {
       // a shard without paths (fewer paths than shards): empty moment partials, nothing in the histogram
-      if ((rc = mcp_launch_pass0(&tp[s], sh.d_terminal, 1, 0, (const double*)sh.ws[MCP_WS_PIVOT], sh.ws[MCP_WS_PARTIALS],
+      if ((rc = mcp_launch_pass0(&tp[s], sh.terminal.p, 1, 0, (const double*)sh.ws[MCP_WS_PIVOT], sh.ws[MCP_WS_PARTIALS],
                                  sh.ws[MCP_WS_HIST], sh.stream))) return rc;
     }
   }
   // 2. the terminal values' select, exchanges and records
   if ((rc = run_select(c, tp, jobs, exchange, lo, hi, gamma, SEL_TERMINAL))) return rc;
   // 3. drawdown (SPEC.md 5.1): the same pipeline over q / d -- x = q - 1 (simple, v0 = 1) or expm1(d) (log), no pivot, no rf
-  std::vector<mcp_params> tpd(tp);
-  if (dd) {
+  if (rq.dd) {
+    std::vector<mcp_params> tpd(tp);
     for (size_t s = 0; s < S; s++) {
       tpd[s].v0 = 1.0;
       tpd[s].rf = 0.0;
@@ -1432,70 +1385,70 @@ int run_tile(mcp_ctx* c, const mcp_params* prm, const float* mu, const float* ch
       if (!j.active) continue;
       Shard& sh = c->sh[s];
       HIP_TRY(hipSetDevice(sh.device));
-      if ((rc = mcp_launch_pass0(&tpd[s], sh.d_mdd, j.pn ? j.pn : 1, j.pn, nullptr, sh.ws[MCP_WS_PARTIALS], sh.ws[MCP_WS_HIST], sh.stream)))
+      if ((rc = mcp_launch_pass0(&tpd[s], sh.dd.mdd.p, j.pn ? j.pn : 1, j.pn, nullptr, sh.ws[MCP_WS_PARTIALS], sh.ws[MCP_WS_HIST],
+                                 sh.stream)))
         return rc;
     }
     if ((rc = run_select(c, tpd, jobs, exchange, lo, hi, gamma, SEL_DRAWDOWN))) return rc;
   }
   // 4. horizons (SPEC.md 5.2): the H*kt rows of the horizon array, at alpha and at every level's rank
-  if (hz) {
+  if (rq.hz) {
     std::vector<mcp_params> tph(tp);
     for (size_t s = 0; s < S; s++)
-      if (jobs[s].active) tph[s].n_portfolios = hz->H * jobs[s].kt;
-    for (int l = -1; l < hz->L; l++) {
+      if (jobs[s].active) tph[s].n_portfolios = rq.H * jobs[s].kt;
+    for (int l = -1; l < rq.L; l++) {
       uint64_t qlo = lo, qhi = hi;
       double qg = gamma;
-      if (l >= 0 && (rc = mcp_percentile_rank_q(n_total, hz->levels[l], &qlo, &qhi, &qg))) return rc;
+      if (l >= 0 && (rc = mcp_percentile_rank_q(n_total, rq.levels[l], &qlo, &qhi, &qg))) return rc;
       for (size_t s = 0; s < S; s++) {
         const Job& j = jobs[s];
         if (!j.active) continue;
         Shard& sh = c->sh[s];
         HIP_TRY(hipSetDevice(sh.device));
-        if ((rc = mcp_launch_pass0(&tph[s], sh.d_hz, j.pn ? j.pn : 1, j.pn, sh.d_hz_pivot, sh.ws[MCP_WS_PARTIALS], sh.ws[MCP_WS_HIST],
-                                   sh.stream))) return rc;
+        if ((rc = mcp_launch_pass0(&tph[s], sh.hz.values.p, j.pn ? j.pn : 1, j.pn, sh.hz.pivot.p, sh.ws[MCP_WS_PARTIALS],
+                                   sh.ws[MCP_WS_HIST], sh.stream))) return rc;
       }
       if ((rc = run_select(c, tph, jobs, exchange, qlo, qhi, qg, SEL_HORIZON, l + 1))) return rc;
     }
   }
   for (size_t s = 0; s < S; s++) {
     const Job& j = jobs[s];
-    if (!j.active) continue;
+    if (!j.active || !j.pn) continue;
     Shard& sh = c->sh[s];
     HIP_TRY(hipSetDevice(sh.device));
-    // the records are already in host memory when the stream drains: ws[MCP_WS_STATS] is the mapped h_stats
-    if (terminal_out && j.pn)
-      HIP_TRY(hipMemcpy2DAsync(terminal_out + (size_t)j.k0 * n_total + j.p0, n_total * sizeof(float), sh.d_terminal,
-                               j.pn * sizeof(float), j.pn * sizeof(float), (size_t)j.kt, hipMemcpyDeviceToHost, sh.stream));
-    if (dd && mdd_out && j.pn)
-      HIP_TRY(hipMemcpy2DAsync(mdd_out + (size_t)j.k0 * n_total + j.p0, n_total * sizeof(float), sh.d_mdd,
-                               j.pn * sizeof(float), j.pn * sizeof(float), (size_t)j.kt, hipMemcpyDeviceToHost, sh.stream));
-    if (hz && hz->out && j.pn)
-      for (int h = 0; h < hz->H; h++)
-        HIP_TRY(hipMemcpy2DAsync(hz->out + ((size_t)h * prm->n_portfolios + j.k0) * n_total + j.p0, n_total * sizeof(float),
-                                 sh.d_hz + (size_t)h * j.kt * j.pn, j.pn * sizeof(float), j.pn * sizeof(float), (size_t)j.kt,
-                                 hipMemcpyDeviceToHost, sh.stream));
+    // the records are already in host memory when the stream drains: ws[MCP_WS_STATS] is the mapped sh.stats
+    const auto copy_out = [&](float* out, const float* d) {   // [kt][pn] block -> rows k0.. of the [K][n_total] array at column p0
+      return hipMemcpy2DAsync(out + (size_t)j.k0 * n_total + j.p0, n_total * sizeof(float), d, j.pn * sizeof(float),
+                              j.pn * sizeof(float), (size_t)j.kt, hipMemcpyDeviceToHost, sh.stream);
+    };
+    if (rq.terminal_out) HIP_TRY(copy_out(rq.terminal_out, sh.terminal.p));
+    if (rq.dd && rq.mdd_out) HIP_TRY(copy_out(rq.mdd_out, sh.dd.mdd.p));
+    if (rq.hz && rq.hz_out)
+      for (int h = 0; h < rq.H; h++)
+        HIP_TRY(copy_out(rq.hz_out + (size_t)h * prm->n_portfolios * n_total, sh.hz.values.p + (size_t)h * j.kt * j.pn));
   }
   for (size_t s = 0; s < S; s++)
     if (jobs[s].active) { HIP_TRY(hipSetDevice(c->sh[s].device)); HIP_TRY(hipStreamSynchronize(c->sh[s].stream)); }
-  for (size_t s = 0; s < S; s++)
-    if (jobs[s].active && (!exchange || s == 0)) {
-      memcpy(stats_out + jobs[s].k0, c->sh[s].h_stats, (size_t)jobs[s].kt * sizeof(mcp_stats));
-      if (dd) {
-        memcpy(dd_stats_out + jobs[s].k0, c->sh[s].h_dd_stats, (size_t)jobs[s].kt * sizeof(mcp_stats));
-        for (int k = 0; k < jobs[s].kt; k++) dd_stats_out[jobs[s].k0 + k].sharpe = 0.0;
-      }
-      if (hz) {                                        // slot 0: the records at alpha; slot 1 + l: level l's quantile (var)
-        const int kt = jobs[s].kt, rows = hz->H * kt;
-        const mcp_stats* hs = c->sh[s].h_hz_stats;
-        for (int h = 0; h < hz->H; h++)
-          for (int k = 0; k < kt; k++) {
-            const size_t o = (size_t)h * prm->n_portfolios + jobs[s].k0 + k, r = (size_t)h * kt + k;
-            hz->stats_out[o] = hs[r];
-            hz->stats_out[o].sharpe = 0.0;
-            for (int l = 0; l < hz->L; l++) hz->bands_out[o * hz->L + l] = hs[(size_t)(1 + l) * rows + r].var;
-          }
-      }
+  for (size_t s = 0; s < S; s++) {
+    const Job& j = jobs[s];
+    if (!j.active || (exchange && s != 0)) continue;
+    const Shard& sh = c->sh[s];
+    memcpy(rq.stats_out + j.k0, sh.stats.p, (size_t)j.kt * sizeof(mcp_stats));
+    if (rq.dd) {
+      memcpy(rq.dd_stats_out + j.k0, sh.dd.stats.p, (size_t)j.kt * sizeof(mcp_stats));
+      for (int k = 0; k < j.kt; k++) rq.dd_stats_out[j.k0 + k].sharpe = 0.0;
     }
+    if (rq.hz) {                                         // slot 0: the records at alpha; slot 1 + l: level l's quantile (var)
+      const int rows = rq.H * j.kt;
+      for (int h = 0; h < rq.H; h++)
+        for (int k = 0; k < j.kt; k++) {
+          const size_t o = (size_t)h * prm->n_portfolios + j.k0 + k, r = (size_t)h * j.kt + k;
+          rq.hz_stats_out[o] = sh.hz.stats.p[r];
+          rq.hz_stats_out[o].sharpe = 0.0;
+          for (int l = 0; l < rq.L; l++) rq.bands_out[o * rq.L + l] = sh.hz.stats.p[(size_t)(1 + l) * rows + r].var;
+        }
+    }
+  }
   return MCP_OK;
 }
 
@@ -1509,19 +1462,10 @@ int tile_portfolios(size_t budget, uint64_t n_paths, int K, size_t bytes_per_pat
   return fit >= 1 ? (int)fit : 1;
 }
 
-int simulate_impl(mcp_ctx* c, const mcp_params* prm, const float* mu, const float* chol, const float* W, uint64_t seed,
-                  uint64_t path_begin, uint64_t n_paths, float* terminal_out, mcp_stats* stats_out, bool dd, float* mdd_out,
-                  mcp_stats* dd_stats_out, const HzReq* hz = nullptr, const BootReq* boot = nullptr, const RebReq* reb = nullptr,
-                  const StReq* st = nullptr) {
+// A checked request (check_request) on the shards of a context.
+int simulate_impl(mcp_ctx* c, const mcp_params* prm, const Request& rq, uint64_t seed, uint64_t path_begin, uint64_t n_paths) {
   if (!c) return fail(MCP_E_ARG, "ctx is NULL");
-  if (int rc = check_params(prm)) return rc;
-  if ((!boot && (!mu || !chol)) || !W || !stats_out || (dd && !dd_stats_out)) return fail(MCP_E_ARG, "NULL pointer");
-  if (n_paths < 1) return fail(MCP_E_ARG, "n_paths must be >= 1");
-  if (dd && (prm->flags & (MCP_FLAG_FOLD | MCP_FLAG_NATIVE_MATH)))
-    return fail(MCP_E_UNSUPPORTED, "the drawdown runs on the spec's normals and the unfolded recurrence (no MCP_FLAG_FOLD / MCP_FLAG_NATIVE_MATH)");
-  if (hz && (prm->flags & (MCP_FLAG_FOLD | MCP_FLAG_NATIVE_MATH)))
-    return fail(MCP_E_UNSUPPORTED, "the horizons run on the spec's normals and the unfolded recurrence (no MCP_FLAG_FOLD / MCP_FLAG_NATIVE_MATH)");
-  const size_t bytes_per_path = hz ? (1 + (size_t)hz->H) * sizeof(float) : dd ? 2 * sizeof(float) : sizeof(float);
+  const size_t bytes_per_path = rq.hz ? (1 + (size_t)rq.H) * sizeof(float) : rq.dd ? 2 * sizeof(float) : sizeof(float);
   std::lock_guard<std::mutex> lock(c->mu);
   const size_t S = c->sh.size();
   const int K = prm->n_portfolios;
@@ -1530,15 +1474,15 @@ int simulate_impl(mcp_ctx* c, const mcp_params* prm, const float* mu, const floa
   int rc = MCP_OK;
   std::vector<Job> jobs(S);
   const bool by_portfolio = S > 1 && (prm->flags & MCP_FLAG_SHARD_PORTFOLIOS);
-  if (boot) {
-    // SPEC.md 2.1: the rows, zero-padded to N4, into one pinned staging copy and from there once into the d_boot of every shard
-    // that walks paths in this call (the tiles of the call share it)
+  if (rq.src == SRC_BOOT) {
+    // SPEC.md 2.1: the rows, zero-padded to N4, into one pinned staging copy and from there once into the boot buffer of every
+    // shard that walks paths in this call (the tiles of the call share it)
     const int N = prm->n_assets, n4 = n4_of(N);
-    const size_t R = boot->n_rows, bytes = R * (size_t)n4 * sizeof(float);
+    const size_t R = rq.boot->n_rows, bytes = R * (size_t)n4 * sizeof(float);
     rc = grow_host((void**)&c->h_boot, &c->h_boot_cap, bytes);
     if (rc == MCP_OK) {
       memset(c->h_boot, 0, bytes);
-      for (size_t j = 0; j < R; j++) memcpy(c->h_boot + j * n4, boot->boot->rows + j * N, (size_t)N * sizeof(float));
+      for (size_t j = 0; j < R; j++) memcpy(c->h_boot + j * n4, rq.boot->rows + j * N, (size_t)N * sizeof(float));
     }
     for (size_t s = 0; s < S && rc == MCP_OK; s++) {
       const bool works = by_portfolio ? (int64_t)K * (int64_t)(s + 1) / (int64_t)S > (int64_t)K * (int64_t)s / (int64_t)S
@@ -1546,8 +1490,8 @@ int simulate_impl(mcp_ctx* c, const mcp_params* prm, const float* mu, const floa
       if (!works) continue;
       Shard& sh = c->sh[s];
       if (hipSetDevice(sh.device) != hipSuccess) { rc = fail(MCP_E_HIP, "hipSetDevice(%d)", sh.device); break; }
-      if ((rc = grow_dev((void**)&sh.d_boot, &sh.boot_cap, bytes))) break;
-      const hipError_t e = hipMemcpyAsync(sh.d_boot, c->h_boot, bytes, hipMemcpyHostToDevice, sh.stream);
+      if ((rc = grow(sh.boot, R * (size_t)n4))) break;
+      const hipError_t e = hipMemcpyAsync(sh.boot.p, c->h_boot, bytes, hipMemcpyHostToDevice, sh.stream);
       if (e != hipSuccess) rc = fail(MCP_E_HIP, "bootstrap rows upload: %s", hipGetErrorString(e));
     }
   }
@@ -1567,9 +1511,7 @@ int simulate_impl(mcp_ctx* c, const mcp_params* prm, const float* mu, const floa
         done[s] += kt;
         more = true;
       }
-      if (more)
-        rc = run_tile(c, prm, mu, chol, W, seed, path_begin, n_paths, jobs, false, terminal_out, stats_out, dd, mdd_out, dd_stats_out, hz,
-                      boot, reb, st);
+      if (more) rc = run_tile(c, prm, rq, seed, path_begin, n_paths, jobs, false);
     }
   } else if (rc == MCP_OK) {
     // the path range is sharded; all shards see the same tile of portfolios
@@ -1584,8 +1526,7 @@ int simulate_impl(mcp_ctx* c, const mcp_params* prm, const float* mu, const floa
     rc = ensure_exchange(c);
     for (int k0 = 0; k0 < K && rc == MCP_OK; k0 += kt_max) {
       for (size_t s = 0; s < S; s++) { jobs[s].k0 = k0; jobs[s].kt = std::min(kt_max, K - k0); }
-      rc = run_tile(c, prm, mu, chol, W, seed, path_begin, n_paths, jobs, S > 1 || c->exchange_always, terminal_out, stats_out, dd,
-                    mdd_out, dd_stats_out, hz, boot, reb, st);
+      rc = run_tile(c, prm, rq, seed, path_begin, n_paths, jobs, S > 1 || c->exchange_always);
     }
   }
   if (rc != MCP_OK) {
@@ -1607,162 +1548,80 @@ int simulate_impl(mcp_ctx* c, const mcp_params* prm, const float* mu, const floa
   return rc;
 }
 
+// Every public simulate entry point: the request is checked in full before the context is looked at.
+int simulate_checked(mcp_ctx* c, const mcp_params* prm, const Request& rq, uint64_t seed, uint64_t path_begin, uint64_t n_paths) {
+  if (int rc = check_request(prm, rq, n_paths)) return rc;
+  return simulate_impl(c, prm, rq, seed, path_begin, n_paths);
+}
+
 }  // namespace
 
 int mcp_simulate(mcp_ctx* c, const mcp_params* prm, const float* mu, const float* chol, const float* W,
                  uint64_t seed, uint64_t path_begin, uint64_t n_paths, float* terminal_out, mcp_stats* stats_out) {
-  return simulate_impl(c, prm, mu, chol, W, seed, path_begin, n_paths, terminal_out, stats_out, false, nullptr, nullptr);
+  if (!c) return fail(MCP_E_ARG, "ctx is NULL");   // mcp_simulate and mcp_simulate_drawdown look at the context first (ABI 1)
+  return simulate_checked(c, prm, host_request(SRC_GAUSS, mu, chol, W, terminal_out, stats_out), seed, path_begin, n_paths);
 }
 
 int mcp_simulate_drawdown(mcp_ctx* c, const mcp_params* prm, const float* mu, const float* chol, const float* W, uint64_t seed,
                           uint64_t path_begin, uint64_t n_paths, float* terminal_out, mcp_stats* stats_out, float* mdd_out,
                           mcp_stats* dd_stats_out) {
-  return simulate_impl(c, prm, mu, chol, W, seed, path_begin, n_paths, terminal_out, stats_out, true, mdd_out, dd_stats_out);
+  if (!c) return fail(MCP_E_ARG, "ctx is NULL");
+  Request rq = host_request(SRC_GAUSS, mu, chol, W, terminal_out, stats_out);
+  rq.dd = true;
+  rq.mdd_out = mdd_out;
+  rq.dd_stats_out = dd_stats_out;
+  return simulate_checked(c, prm, rq, seed, path_begin, n_paths);
 }
 
 int mcp_simulate_horizons(mcp_ctx* c, const mcp_params* prm, const float* mu, const float* chol, const float* W, uint64_t seed,
                           uint64_t path_begin, uint64_t n_paths, int n_horizons, const int32_t* horizons, int n_levels,
                           const double* levels, float* terminal_out, mcp_stats* stats_out, float* horizon_out,
                           mcp_stats* hz_stats_out, double* bands_out) {
-  // the arguments first, so that each error is found (and named) before any device is touched, a NULL ctx included
-  if (int rc = check_params(prm)) return rc;
-  if (int rc = check_horizons(prm->n_steps, n_horizons, horizons)) return rc;
-  if (int rc = check_levels(n_levels, levels)) return rc;
-  if (!hz_stats_out) return fail(MCP_E_ARG, "hz_stats_out is NULL");
-  if ((bands_out == nullptr) != (n_levels == 0)) return fail(MCP_E_ARG, "bands_out must be NULL exactly when n_levels == 0");
-  HzReq hz;
-  hz.H = n_horizons;
-  hz.L = n_levels;
-  hz.steps = horizons;
-  hz.levels = levels;
-  hz.out = horizon_out;
-  hz.stats_out = hz_stats_out;
-  hz.bands_out = bands_out;
-  return simulate_impl(c, prm, mu, chol, W, seed, path_begin, n_paths, terminal_out, stats_out, false, nullptr, nullptr, &hz);
+  Request rq = host_request(SRC_GAUSS, mu, chol, W, terminal_out, stats_out);
+  ask_horizons(rq, true, n_horizons, horizons, n_levels, levels, horizon_out, hz_stats_out, bands_out);
+  return simulate_checked(c, prm, rq, seed, path_begin, n_paths);
 }
 
 int mcp_simulate_bootstrap(mcp_ctx* c, const mcp_params* prm, const mcp_bootstrap* boot, const float* W, uint64_t seed,
                            uint64_t path_begin, uint64_t n_paths, float* terminal_out, mcp_stats* stats_out) {
-  // the arguments first, so that each error is found (and named) before any device is touched, a NULL ctx included
-  if (int rc = check_params(prm)) return rc;
-  BootReq br;
-  if (int rc = check_boot(prm, boot, &br.thr)) return rc;
-  if (prm->flags & (MCP_FLAG_FOLD | MCP_FLAG_NATIVE_MATH))
-    return fail(MCP_E_UNSUPPORTED, "bootstrap paths draw no normals (no MCP_FLAG_FOLD / MCP_FLAG_NATIVE_MATH)");
-  if (!W || !stats_out) return fail(MCP_E_ARG, "NULL pointer");
-  if (n_paths < 1) return fail(MCP_E_ARG, "n_paths must be >= 1");
-  br.boot = boot;
-  br.n_rows = (uint32_t)boot->n_rows;
-  return simulate_impl(c, prm, nullptr, nullptr, W, seed, path_begin, n_paths, terminal_out, stats_out, false, nullptr, nullptr, nullptr,
-                       &br);
+  Request rq = host_request(SRC_BOOT, nullptr, nullptr, W, terminal_out, stats_out);
+  rq.boot = boot;
+  return simulate_checked(c, prm, rq, seed, path_begin, n_paths);
 }
 
 int mcp_simulate_bootstrap_horizons(mcp_ctx* c, const mcp_params* prm, const mcp_bootstrap* boot, const float* W, uint64_t seed,
                                     uint64_t path_begin, uint64_t n_paths, int n_horizons, const int32_t* horizons, int n_levels,
                                     const double* levels, float* terminal_out, mcp_stats* stats_out, float* horizon_out,
                                     mcp_stats* hz_stats_out, double* bands_out) {
-  if (int rc = check_params(prm)) return rc;
-  BootReq br;
-  if (int rc = check_boot(prm, boot, &br.thr)) return rc;
-  if (prm->flags & (MCP_FLAG_FOLD | MCP_FLAG_NATIVE_MATH))
-    return fail(MCP_E_UNSUPPORTED, "bootstrap paths draw no normals (no MCP_FLAG_FOLD / MCP_FLAG_NATIVE_MATH)");
-  if (int rc = check_horizons(prm->n_steps, n_horizons, horizons)) return rc;
-  if (int rc = check_levels(n_levels, levels)) return rc;
-  if (!W || !stats_out || !hz_stats_out) return fail(MCP_E_ARG, "NULL pointer");
-  if ((bands_out == nullptr) != (n_levels == 0)) return fail(MCP_E_ARG, "bands_out must be NULL exactly when n_levels == 0");
-  if (n_paths < 1) return fail(MCP_E_ARG, "n_paths must be >= 1");
-  br.boot = boot;
-  br.n_rows = (uint32_t)boot->n_rows;
-  HzReq hz;
-  hz.H = n_horizons;
-  hz.L = n_levels;
-  hz.steps = horizons;
-  hz.levels = levels;
-  hz.out = horizon_out;
-  hz.stats_out = hz_stats_out;
-  hz.bands_out = bands_out;
-  return simulate_impl(c, prm, nullptr, nullptr, W, seed, path_begin, n_paths, terminal_out, stats_out, false, nullptr, nullptr, &hz,
-                       &br);
+  Request rq = host_request(SRC_BOOT, nullptr, nullptr, W, terminal_out, stats_out);
+  rq.boot = boot;
+  ask_horizons(rq, true, n_horizons, horizons, n_levels, levels, horizon_out, hz_stats_out, bands_out);
+  return simulate_checked(c, prm, rq, seed, path_begin, n_paths);
 }
 
 int mcp_simulate_rebalanced(mcp_ctx* c, const mcp_params* prm, const mcp_rebalance* reb, const float* mu, const float* chol,
                             const mcp_bootstrap* boot, const float* W, uint64_t seed, uint64_t path_begin, uint64_t n_paths,
                             int n_horizons, const int32_t* horizons, int n_levels, const double* levels, float* terminal_out,
                             mcp_stats* stats_out, float* horizon_out, mcp_stats* hz_stats_out, double* bands_out) {
-  // the arguments first, so that each error is found (and named) before any device is touched, a NULL ctx included
-  if (int rc = check_params(prm)) return rc;
-  RebReq rr;
-  if (int rc = check_reb(reb, &rr)) return rc;
-  const bool gauss = mu && chol && !boot, resample = boot && !mu && !chol;
-  if (!gauss && !resample) return fail(MCP_E_ARG, "exactly one draw source: mu and chol, or boot");
-  BootReq br;
-  if (boot) {
-    if (int rc = check_boot(prm, boot, &br.thr)) return rc;
-    br.boot = boot;
-    br.n_rows = (uint32_t)boot->n_rows;
-  }
-  if (prm->compounding != MCP_COMPOUND_SIMPLE) return fail(MCP_E_UNSUPPORTED, "rebalanced paths compound simply (no log compounding)");
-  if (prm->flags & (MCP_FLAG_FOLD | MCP_FLAG_NATIVE_MATH))
-    return fail(MCP_E_UNSUPPORTED, "rebalanced paths run on the unfolded recurrence and the spec's normals (no MCP_FLAG_FOLD / MCP_FLAG_NATIVE_MATH)");
-  HzReq hz;
-  if (n_horizons == 0) {
-    if (n_levels != 0 || horizon_out || hz_stats_out || bands_out)
-      return fail(MCP_E_ARG, "n_horizons = 0: n_levels must be 0 and horizon_out, hz_stats_out, bands_out NULL");
-  } else {
-    if (int rc = check_horizons(prm->n_steps, n_horizons, horizons)) return rc;
-    if (int rc = check_levels(n_levels, levels)) return rc;
-    if (!hz_stats_out) return fail(MCP_E_ARG, "hz_stats_out is NULL");
-    if ((bands_out == nullptr) != (n_levels == 0)) return fail(MCP_E_ARG, "bands_out must be NULL exactly when n_levels == 0");
-    hz.H = n_horizons;
-    hz.L = n_levels;
-    hz.steps = horizons;
-    hz.levels = levels;
-    hz.out = horizon_out;
-    hz.stats_out = hz_stats_out;
-    hz.bands_out = bands_out;
-  }
-  if (!W || !stats_out) return fail(MCP_E_ARG, "NULL pointer");
-  if (n_paths < 1) return fail(MCP_E_ARG, "n_paths must be >= 1");
-  return simulate_impl(c, prm, mu, chol, W, seed, path_begin, n_paths, terminal_out, stats_out, false, nullptr, nullptr,
-                       n_horizons ? &hz : nullptr, boot ? &br : nullptr, &rr);
+  Request rq = host_request(boot ? SRC_BOOT : SRC_GAUSS, mu, chol, W, terminal_out, stats_out);
+  rq.boot = boot;
+  rq.rebalanced = true;
+  rq.reb = reb;
+  ask_horizons(rq, n_horizons != 0, n_horizons, horizons, n_levels, levels, horizon_out, hz_stats_out, bands_out);
+  return simulate_checked(c, prm, rq, seed, path_begin, n_paths);
 }
 
 int mcp_simulate_student_t(mcp_ctx* c, const mcp_params* prm, const mcp_student_t* st, const float* mu, const float* chol,
                            const float* W, uint64_t seed, uint64_t path_begin, uint64_t n_paths, int n_horizons, const int32_t* horizons,
                            int n_levels, const double* levels, float* terminal_out, mcp_stats* stats_out, float* mdd_out,
                            mcp_stats* dd_stats_out, float* horizon_out, mcp_stats* hz_stats_out, double* bands_out) {
-  // the arguments first, so that each error is found (and named) before any device is touched, a NULL ctx included
-  if (int rc = check_params(prm)) return rc;
-  StReq sr;
-  if (int rc = check_student_t(prm, st, &sr)) return rc;
-  if (prm->compounding != MCP_COMPOUND_SIMPLE)
-    return fail(MCP_E_UNSUPPORTED, "Student-t paths compound simply (log compounding: expm1(S) has no finite mean under t steps)");
-  if (prm->flags & (MCP_FLAG_FOLD | MCP_FLAG_NATIVE_MATH))
-    return fail(MCP_E_UNSUPPORTED, "Student-t paths run on the spec's normals and the unfolded recurrence (no MCP_FLAG_FOLD / MCP_FLAG_NATIVE_MATH)");
-  const bool dd = dd_stats_out != nullptr;
-  if (dd && n_horizons != 0) return fail(MCP_E_UNSUPPORTED, "horizons and the drawdown are not tracked in one walk");
-  if (!dd && mdd_out) return fail(MCP_E_ARG, "mdd_out needs dd_stats_out");
-  HzReq hz;
-  if (n_horizons == 0) {
-    if (n_levels != 0 || horizon_out || hz_stats_out || bands_out)
-      return fail(MCP_E_ARG, "n_horizons = 0: n_levels must be 0 and horizon_out, hz_stats_out, bands_out NULL");
-  } else {
-    if (int rc = check_horizons(prm->n_steps, n_horizons, horizons)) return rc;
-    if (int rc = check_levels(n_levels, levels)) return rc;
-    if (!hz_stats_out) return fail(MCP_E_ARG, "hz_stats_out is NULL");
-    if ((bands_out == nullptr) != (n_levels == 0)) return fail(MCP_E_ARG, "bands_out must be NULL exactly when n_levels == 0");
-    hz.H = n_horizons;
-    hz.L = n_levels;
-    hz.steps = horizons;
-    hz.levels = levels;
-    hz.out = horizon_out;
-    hz.stats_out = hz_stats_out;
-    hz.bands_out = bands_out;
-  }
-  if (!mu || !chol || !W || !stats_out) return fail(MCP_E_ARG, "NULL pointer");
-  if (n_paths < 1) return fail(MCP_E_ARG, "n_paths must be >= 1");
-  return simulate_impl(c, prm, mu, chol, W, seed, path_begin, n_paths, terminal_out, stats_out, dd, mdd_out, dd_stats_out,
-                       n_horizons ? &hz : nullptr, nullptr, nullptr, &sr);
+  Request rq = host_request(SRC_T, mu, chol, W, terminal_out, stats_out);
+  rq.st = st;
+  rq.dd = dd_stats_out != nullptr;
+  rq.mdd_out = mdd_out;
+  rq.dd_stats_out = dd_stats_out;
+  ask_horizons(rq, n_horizons != 0, n_horizons, horizons, n_levels, levels, horizon_out, hz_stats_out, bands_out);
+  return simulate_checked(c, prm, rq, seed, path_begin, n_paths);
 }
 
 int mcp_sweep_historical(mcp_ctx* c, int N, int R, int P, const double* returns, const double* mean, const double* cov,

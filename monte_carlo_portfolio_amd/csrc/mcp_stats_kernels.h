@@ -58,61 +58,21 @@ struct PathArgs;
 // variant bits for launch_paths
 enum { VAR_KT8 = 1, VAR_NATIVE = 4, VAR_FOLD = 8 };
 
-// mcp_paths_inst.hip (one translation unit per NB): returns hipErrorInvalidValue for a variant that
-// is not instantiated.
-typedef hipError_t (*launch_paths_fn)(int variant, const PathArgs& args, int grid, hipStream_t stream);
-#define MCP_DECL_NB(n) hipError_t launch_paths_nb##n(int variant, const PathArgs& args, int grid, hipStream_t stream);
-MCP_DECL_NB(1) MCP_DECL_NB(2) MCP_DECL_NB(3) MCP_DECL_NB(4) MCP_DECL_NB(5) MCP_DECL_NB(6) MCP_DECL_NB(7) MCP_DECL_NB(8)
-MCP_DECL_NB(9) MCP_DECL_NB(10) MCP_DECL_NB(11) MCP_DECL_NB(12) MCP_DECL_NB(13) MCP_DECL_NB(14) MCP_DECL_NB(15) MCP_DECL_NB(16)
-#undef MCP_DECL_NB
-// the drawdown kernel (SPEC.md 4.2), variants 0 and VAR_KT8 only
-struct PathArgsDD;
-typedef hipError_t (*launch_paths_dd_fn)(int variant, const PathArgsDD& args, int grid, hipStream_t stream);
-#define MCP_DECL_NB(n) hipError_t launch_paths_dd_nb##n(int variant, const PathArgsDD& args, int grid, hipStream_t stream);
-MCP_DECL_NB(1) MCP_DECL_NB(2) MCP_DECL_NB(3) MCP_DECL_NB(4) MCP_DECL_NB(5) MCP_DECL_NB(6) MCP_DECL_NB(7) MCP_DECL_NB(8)
-MCP_DECL_NB(9) MCP_DECL_NB(10) MCP_DECL_NB(11) MCP_DECL_NB(12) MCP_DECL_NB(13) MCP_DECL_NB(14) MCP_DECL_NB(15) MCP_DECL_NB(16)
-#undef MCP_DECL_NB
+// Which path kernel a launch runs (mcp_paths.h): the family, the compounding mode and the draw source.  `args` of launch_paths
+// is the PathArgs base of the kernel's argument struct:
+//   FAM_PLAIN  PathArgs, PathArgsBT (boot), PathArgsT (stt)        FAM_DD   PathArgsDD, PathArgsTDD (stt)
+//   FAM_HZ     PathArgsHZ, PathArgsBTHZ (boot), PathArgsTHZ (stt)  FAM_REB  PathArgsRB (boot: its rows instead of normals)
+// `blds`: the bootstrap's row table is copied into LDS (it fits boot_fits_lds) instead of being read from global memory.
+// VAR_NATIVE and VAR_FOLD exist for the plain Gaussian kernel only.
+enum PathFamily { FAM_PLAIN, FAM_DD, FAM_HZ, FAM_REB };
+struct PathKernel {
+  int family;
+  bool logc, boot, blds, stt;
+};
 
-// the horizon kernel (SPEC.md 4.3), variants 0 and VAR_KT8 only
-struct PathArgsHZ;
-typedef hipError_t (*launch_paths_hz_fn)(int variant, const PathArgsHZ& args, int grid, hipStream_t stream);
-#define MCP_DECL_NB(n) hipError_t launch_paths_hz_nb##n(int variant, const PathArgsHZ& args, int grid, hipStream_t stream);
-MCP_DECL_NB(1) MCP_DECL_NB(2) MCP_DECL_NB(3) MCP_DECL_NB(4) MCP_DECL_NB(5) MCP_DECL_NB(6) MCP_DECL_NB(7) MCP_DECL_NB(8)
-MCP_DECL_NB(9) MCP_DECL_NB(10) MCP_DECL_NB(11) MCP_DECL_NB(12) MCP_DECL_NB(13) MCP_DECL_NB(14) MCP_DECL_NB(15) MCP_DECL_NB(16)
-#undef MCP_DECL_NB
-
-// the bootstrap kernels (SPEC.md 2.1 / 4.4), variants 0 and VAR_KT8 only; `lds`: the row table is copied into LDS (it fits
-// boot_fits_lds) instead of being read from global memory
-struct PathArgsBT;
-struct PathArgsBTHZ;
-typedef hipError_t (*launch_paths_bt_fn)(int variant, bool lds, const PathArgsBT& args, int grid, hipStream_t stream);
-typedef hipError_t (*launch_paths_bthz_fn)(int variant, bool lds, const PathArgsBTHZ& args, int grid, hipStream_t stream);
-#define MCP_DECL_NB(n)                                                                                                    \
-  hipError_t launch_paths_bt_nb##n(int variant, bool lds, const PathArgsBT& args, int grid, hipStream_t stream);          \
-  hipError_t launch_paths_bthz_nb##n(int variant, bool lds, const PathArgsBTHZ& args, int grid, hipStream_t stream);
-MCP_DECL_NB(1) MCP_DECL_NB(2) MCP_DECL_NB(3) MCP_DECL_NB(4) MCP_DECL_NB(5) MCP_DECL_NB(6) MCP_DECL_NB(7) MCP_DECL_NB(8)
-MCP_DECL_NB(9) MCP_DECL_NB(10) MCP_DECL_NB(11) MCP_DECL_NB(12) MCP_DECL_NB(13) MCP_DECL_NB(14) MCP_DECL_NB(15) MCP_DECL_NB(16)
-#undef MCP_DECL_NB
-
-// the rebalancing kernel (SPEC.md 4.5), variants 0 and VAR_KT8 only; `boot`: bootstrap rows instead of Gaussian draws, `lds`:
-// their table is copied into LDS (boot_fits_lds)
-struct PathArgsRB;
-typedef hipError_t (*launch_paths_rb_fn)(int variant, bool boot, bool lds, const PathArgsRB& args, int grid, hipStream_t stream);
-#define MCP_DECL_NB(n) hipError_t launch_paths_rb_nb##n(int variant, bool boot, bool lds, const PathArgsRB& args, int grid, hipStream_t stream);
-MCP_DECL_NB(1) MCP_DECL_NB(2) MCP_DECL_NB(3) MCP_DECL_NB(4) MCP_DECL_NB(5) MCP_DECL_NB(6) MCP_DECL_NB(7) MCP_DECL_NB(8)
-MCP_DECL_NB(9) MCP_DECL_NB(10) MCP_DECL_NB(11) MCP_DECL_NB(12) MCP_DECL_NB(13) MCP_DECL_NB(14) MCP_DECL_NB(15) MCP_DECL_NB(16)
-#undef MCP_DECL_NB
-
-// the Student-t kernels (SPEC.md 2.2 / 4.6), variants 0 and VAR_KT8 only; exactly one of at (terminal values), ad (drawdown),
-// ah (horizons)
-struct PathArgsT;
-struct PathArgsTDD;
-struct PathArgsTHZ;
-typedef hipError_t (*launch_paths_t_fn)(int variant, const PathArgsT* at, const PathArgsTDD* ad, const PathArgsTHZ* ah, int grid,
-                                        hipStream_t stream);
-#define MCP_DECL_NB(n)                                                                                                    \
-  hipError_t launch_paths_t_nb##n(int variant, const PathArgsT* at, const PathArgsTDD* ad, const PathArgsTHZ* ah, int grid, \
-                                  hipStream_t stream);
+// mcp_paths_inst.hip (one translation unit per NB): returns hipErrorInvalidValue for a kernel that is not instantiated.
+typedef hipError_t (*launch_paths_fn)(int variant, const PathKernel& k, const PathArgs& args, int grid, hipStream_t stream);
+#define MCP_DECL_NB(n) hipError_t launch_paths_nb##n(int variant, const PathKernel& k, const PathArgs& args, int grid, hipStream_t stream);
 MCP_DECL_NB(1) MCP_DECL_NB(2) MCP_DECL_NB(3) MCP_DECL_NB(4) MCP_DECL_NB(5) MCP_DECL_NB(6) MCP_DECL_NB(7) MCP_DECL_NB(8)
 MCP_DECL_NB(9) MCP_DECL_NB(10) MCP_DECL_NB(11) MCP_DECL_NB(12) MCP_DECL_NB(13) MCP_DECL_NB(14) MCP_DECL_NB(15) MCP_DECL_NB(16)
 #undef MCP_DECL_NB

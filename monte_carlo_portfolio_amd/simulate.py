@@ -9,6 +9,7 @@ validates, factors Sigma (float64 Cholesky on the host, cast to fp32) and marsha
 from __future__ import annotations
 
 import atexit
+import collections
 import ctypes
 import threading
 
@@ -62,125 +63,15 @@ class Context:
         except Exception:
             pass
 
-    def simulate(self, prm: _ffi.McpParams, mu, chol, W, seed: int, path_begin: int, n_paths: int, store: bool):
+    def _call(self, prm: _ffi.McpParams, W, seed: int, path_begin: int, n_paths: int, store: bool, mu=None, chol=None, rows=None,
+              block: float = 1.0, dof=None, period=None, cost: float = 0.0, drawdown: bool = False, horizons=None, levels=()):
+        """The one library call behind every simulate_* method: Student-t draws (dof), rebalancing (period, cost), bootstrap rows
+        (rows, block) or Gaussian draws (mu, chol), with the drawdown or horizons.  Allocates the outputs that were asked for and
+        passes NULL for the rest -> _Outputs, None where not asked for (terminal, qd, horizon_terminal: with `store` only)."""
         K = prm.n_portfolios
-        stats = np.zeros(K, _ffi.STATS_DTYPE)
-        term = np.empty((K, n_paths), np.float32) if store else None
-        _ffi.check(_ffi.lib().mcp_simulate(
-            self._h, ctypes.byref(prm), mu, chol, W, seed, path_begin, n_paths,
-            term.ctypes.data_as(ctypes.c_void_p) if store else None,
-            stats.ctypes.data_as(ctypes.c_void_p)))
-        return stats, term
-
-    def simulate_drawdown(self, prm: _ffi.McpParams, mu, chol, W, seed: int, path_begin: int, n_paths: int, store: bool):
-        """simulate() plus the max drawdown of every path (SPEC.md 4.2 / 5.1; include/mcport.h, mcp_simulate_drawdown) ->
-        (stats, dd_stats, terminal, qd): dd_stats is a [K] mcp_stats record array over the per-path drawdowns; with `store`,
-        qd is the kernels' binary32 [K, n_paths] q (simple: mdd = q - 1) or d (log: mdd = expm1(d)), see mdd_from_raw."""
-        K = prm.n_portfolios
-        stats = np.zeros(K, _ffi.STATS_DTYPE)
-        dd_stats = np.zeros(K, _ffi.STATS_DTYPE)
-        term = np.empty((K, n_paths), np.float32) if store else None
-        raw = np.empty((K, n_paths), np.float32) if store else None
-        _ffi.check(_ffi.lib().mcp_simulate_drawdown(
-            self._h, ctypes.byref(prm), mu, chol, W, seed, path_begin, n_paths,
-            term.ctypes.data_as(ctypes.c_void_p) if store else None,
-            stats.ctypes.data_as(ctypes.c_void_p),
-            raw.ctypes.data_as(ctypes.c_void_p) if store else None,
-            dd_stats.ctypes.data_as(ctypes.c_void_p)))
-        return stats, dd_stats, term, raw
-
-    def simulate_horizons(self, prm: _ffi.McpParams, mu, chol, W, seed: int, path_begin: int, n_paths: int, horizons, levels,
-                          store: bool):
-        """simulate() plus the values after the steps `horizons` (SPEC.md 4.3 / 5.2; include/mcport.h, mcp_simulate_horizons)
-        -> (stats [K], hz_stats [H, K] mcp_stats records, bands [H, K, L] float64 np.percentile(x_h, levels), terminal,
-        horizon_terminal): with `store`, terminal is [K, n_paths] and horizon_terminal the binary32 [H, K, n_paths] V_h / S_h."""
-        K = prm.n_portfolios
-        steps = np.ascontiguousarray(horizons, np.int32).ravel()
-        lv = np.ascontiguousarray(levels, np.float64).ravel()
-        H, L = steps.size, lv.size
-        stats = np.zeros(K, _ffi.STATS_DTYPE)
-        hz_stats = np.zeros((H, K), _ffi.STATS_DTYPE)
-        bands = np.zeros((H, K, L), np.float64)
-        term = np.empty((K, n_paths), np.float32) if store else None
-        hz_term = np.empty((H, K, n_paths), np.float32) if store else None
         ptr = lambda a: a.ctypes.data_as(ctypes.c_void_p) if a is not None else None   # noqa: E731
-        _ffi.check(_ffi.lib().mcp_simulate_horizons(
-            self._h, ctypes.byref(prm), mu, chol, W, seed, path_begin, n_paths, H, ptr(steps), L, ptr(lv) if L else None,
-            ptr(term), ptr(stats), ptr(hz_term), ptr(hz_stats), ptr(bands) if L else None))
-        return stats, hz_stats, bands, term, hz_term
-
-
-    def simulate_bootstrap(self, prm: _ffi.McpParams, rows, W, block: float, seed: int, path_begin: int, n_paths: int,
-                           store: bool):
-        """simulate() on bootstrap paths (SPEC.md 2.1 / 4.4; include/mcport.h, mcp_simulate_bootstrap): rows is the binary32
-        [R, N] table of observed returns, block the mean block length -> (stats [K], terminal [K, n_paths] or None)."""
-        K = prm.n_portfolios
         stats = np.zeros(K, _ffi.STATS_DTYPE)
         term = np.empty((K, n_paths), np.float32) if store else None
-        bt = _ffi.make_bootstrap(rows, block)
-        _ffi.check(_ffi.lib().mcp_simulate_bootstrap(
-            self._h, ctypes.byref(prm), ctypes.byref(bt), W, seed, path_begin, n_paths,
-            term.ctypes.data_as(ctypes.c_void_p) if store else None, stats.ctypes.data_as(ctypes.c_void_p)))
-        return stats, term
-
-    def simulate_bootstrap_horizons(self, prm: _ffi.McpParams, rows, W, block: float, seed: int, path_begin: int, n_paths: int,
-                                    horizons, levels, store: bool):
-        """simulate_horizons() on bootstrap paths (include/mcport.h, mcp_simulate_bootstrap_horizons) -> (stats, hz_stats,
-        bands, terminal, horizon_terminal) as simulate_horizons."""
-        K = prm.n_portfolios
-        steps = np.ascontiguousarray(horizons, np.int32).ravel()
-        lv = np.ascontiguousarray(levels, np.float64).ravel()
-        H, L = steps.size, lv.size
-        stats = np.zeros(K, _ffi.STATS_DTYPE)
-        hz_stats = np.zeros((H, K), _ffi.STATS_DTYPE)
-        bands = np.zeros((H, K, L), np.float64)
-        term = np.empty((K, n_paths), np.float32) if store else None
-        hz_term = np.empty((H, K, n_paths), np.float32) if store else None
-        ptr = lambda a: a.ctypes.data_as(ctypes.c_void_p) if a is not None else None   # noqa: E731
-        bt = _ffi.make_bootstrap(rows, block)
-        _ffi.check(_ffi.lib().mcp_simulate_bootstrap_horizons(
-            self._h, ctypes.byref(prm), ctypes.byref(bt), W, seed, path_begin, n_paths, H, ptr(steps), L, ptr(lv) if L else None,
-            ptr(term), ptr(stats), ptr(hz_term), ptr(hz_stats), ptr(bands) if L else None))
-        return stats, hz_stats, bands, term, hz_term
-
-
-    def simulate_rebalanced(self, prm: _ffi.McpParams, period: int, cost: float, W, seed: int, path_begin: int, n_paths: int,
-                            store: bool, mu=None, chol=None, rows=None, block: float = 1.0, horizons=None, levels=()):
-        """simulate() / simulate_horizons() / simulate_bootstrap[_horizons]() with the weights rebalanced every `period` steps
-        (0: bought and held) at the proportional cost `cost` (SPEC.md 4.5 / 5.4; include/mcport.h, mcp_simulate_rebalanced).
-        Draws: `mu` and `chol` (Gaussian) or `rows` and `block` (bootstrap).  -> (stats [K], hz_stats [H, K], bands [H, K, L],
-        terminal, horizon_terminal) as simulate_horizons; the horizon entries are None without horizons."""
-        K = prm.n_portfolios
-        stats = np.zeros(K, _ffi.STATS_DTYPE)
-        term = np.empty((K, n_paths), np.float32) if store else None
-        ptr = lambda a: a.ctypes.data_as(ctypes.c_void_p) if a is not None else None   # noqa: E731
-        hz_stats = bands = hz_term = steps = lv = None
-        H = L = 0
-        if horizons is not None:
-            steps = np.ascontiguousarray(horizons, np.int32).ravel()
-            lv = np.ascontiguousarray(levels, np.float64).ravel()
-            H, L = steps.size, lv.size
-            hz_stats = np.zeros((H, K), _ffi.STATS_DTYPE)
-            bands = np.zeros((H, K, L), np.float64)
-            hz_term = np.empty((H, K, n_paths), np.float32) if store else None
-        rb = _ffi.McpRebalance(int(period), 0, float(cost))
-        bt = _ffi.make_bootstrap(rows, block) if rows is not None else None
-        _ffi.check(_ffi.lib().mcp_simulate_rebalanced(
-            self._h, ctypes.byref(prm), ctypes.byref(rb), ptr(mu), ptr(chol), ctypes.byref(bt) if bt is not None else None, W, seed,
-            path_begin, n_paths, H, ptr(steps) if H else None, L, ptr(lv) if L else None, ptr(term), ptr(stats), ptr(hz_term),
-            ptr(hz_stats), ptr(bands) if L else None))
-        return stats, hz_stats, bands, term, hz_term
-
-    def simulate_student_t(self, prm: _ffi.McpParams, dof: int, mu, chol, W, seed: int, path_begin: int, n_paths: int, store: bool,
-                           drawdown: bool = False, horizons=None, levels=()):
-        """simulate() / simulate_drawdown() / simulate_horizons() on Student-t draws with `dof` degrees of freedom (SPEC.md 2.2 /
-        4.6; include/mcport.h, mcp_simulate_student_t; simple compounding only) -> (stats [K], dd_stats [K] or None, hz_stats
-        [H, K], bands [H, K, L], terminal, qd, horizon_terminal): the entries of the blocks not asked for are None; with `store`,
-        terminal is [K, n_paths], qd the binary32 drawdown q [K, n_paths], horizon_terminal [H, K, n_paths]."""
-        K = prm.n_portfolios
-        stats = np.zeros(K, _ffi.STATS_DTYPE)
-        term = np.empty((K, n_paths), np.float32) if store else None
-        ptr = lambda a: a.ctypes.data_as(ctypes.c_void_p) if a is not None else None   # noqa: E731
         dd_stats = raw = hz_stats = bands = hz_term = steps = lv = None
         H = L = 0
         if drawdown:
@@ -193,12 +84,86 @@ class Context:
             hz_stats = np.zeros((H, K), _ffi.STATS_DTYPE)
             bands = np.zeros((H, K, L), np.float64)
             hz_term = np.empty((H, K, n_paths), np.float32) if store else None
-        st = _ffi.McpStudentT(int(dof), 0)
-        _ffi.check(_ffi.lib().mcp_simulate_student_t(
-            self._h, ctypes.byref(prm), ctypes.byref(st), ptr(mu), ptr(chol), ptr(W), seed, path_begin, n_paths, H,
-            ptr(steps) if H else None, L, ptr(lv) if L else None, ptr(term), ptr(stats), ptr(raw), ptr(dd_stats), ptr(hz_term),
-            ptr(hz_stats), ptr(bands) if L else None))
-        return stats, dd_stats, hz_stats, bands, term, raw, hz_term
+        lib, prm_p, walk = _ffi.lib(), ctypes.byref(prm), (seed, path_begin, n_paths)
+        hz_in = (H, ptr(steps) if H else None, L, ptr(lv) if L else None)
+        hz_out = (ptr(hz_term), ptr(hz_stats), ptr(bands) if L else None)
+        bt = _ffi.make_bootstrap(rows, block) if rows is not None else None
+        if dof is not None:
+            rc = lib.mcp_simulate_student_t(self._h, prm_p, ctypes.byref(_ffi.McpStudentT(int(dof), 0)), ptr(mu), ptr(chol), ptr(W), *walk,
+                                            *hz_in, ptr(term), ptr(stats), ptr(raw), ptr(dd_stats), *hz_out)
+        elif period is not None:
+            rc = lib.mcp_simulate_rebalanced(self._h, prm_p, ctypes.byref(_ffi.McpRebalance(int(period), 0, float(cost))), ptr(mu),
+                                             ptr(chol), ctypes.byref(bt) if bt is not None else None, W, *walk, *hz_in, ptr(term),
+                                             ptr(stats), *hz_out)
+        elif bt is not None and horizons is not None:
+            rc = lib.mcp_simulate_bootstrap_horizons(self._h, prm_p, ctypes.byref(bt), W, *walk, *hz_in, ptr(term), ptr(stats), *hz_out)
+        elif bt is not None:
+            rc = lib.mcp_simulate_bootstrap(self._h, prm_p, ctypes.byref(bt), W, *walk, ptr(term), ptr(stats))
+        elif horizons is not None:
+            rc = lib.mcp_simulate_horizons(self._h, prm_p, mu, chol, W, *walk, *hz_in, ptr(term), ptr(stats), *hz_out)
+        elif drawdown:
+            rc = lib.mcp_simulate_drawdown(self._h, prm_p, mu, chol, W, *walk, ptr(term), ptr(stats), ptr(raw), ptr(dd_stats))
+        else:
+            rc = lib.mcp_simulate(self._h, prm_p, mu, chol, W, *walk, ptr(term), ptr(stats))
+        _ffi.check(rc)
+        return _Outputs(stats, dd_stats, hz_stats, bands, term, raw, hz_term)
+
+    def simulate(self, prm: _ffi.McpParams, mu, chol, W, seed: int, path_begin: int, n_paths: int, store: bool):
+        o = self._call(prm, W, seed, path_begin, n_paths, store, mu=mu, chol=chol)
+        return o.stats, o.terminal
+
+    def simulate_drawdown(self, prm: _ffi.McpParams, mu, chol, W, seed: int, path_begin: int, n_paths: int, store: bool):
+        """simulate() plus the max drawdown of every path (SPEC.md 4.2 / 5.1; include/mcport.h, mcp_simulate_drawdown) ->
+        (stats, dd_stats, terminal, qd): dd_stats is a [K] mcp_stats record array over the per-path drawdowns; with `store`,
+        qd is the kernels' binary32 [K, n_paths] q (simple: mdd = q - 1) or d (log: mdd = expm1(d)), see mdd_from_raw."""
+        o = self._call(prm, W, seed, path_begin, n_paths, store, mu=mu, chol=chol, drawdown=True)
+        return o.stats, o.dd_stats, o.terminal, o.qd
+
+    def simulate_horizons(self, prm: _ffi.McpParams, mu, chol, W, seed: int, path_begin: int, n_paths: int, horizons, levels,
+                          store: bool):
+        """simulate() plus the values after the steps `horizons` (SPEC.md 4.3 / 5.2; include/mcport.h, mcp_simulate_horizons)
+        -> (stats [K], hz_stats [H, K] mcp_stats records, bands [H, K, L] float64 np.percentile(x_h, levels), terminal,
+        horizon_terminal): with `store`, terminal is [K, n_paths] and horizon_terminal the binary32 [H, K, n_paths] V_h / S_h."""
+        o = self._call(prm, W, seed, path_begin, n_paths, store, mu=mu, chol=chol, horizons=horizons, levels=levels)
+        return o.stats, o.hz_stats, o.bands, o.terminal, o.horizon_terminal
+
+    def simulate_bootstrap(self, prm: _ffi.McpParams, rows, W, block: float, seed: int, path_begin: int, n_paths: int,
+                           store: bool):
+        """simulate() on bootstrap paths (SPEC.md 2.1 / 4.4; include/mcport.h, mcp_simulate_bootstrap): rows is the binary32
+        [R, N] table of observed returns, block the mean block length -> (stats [K], terminal [K, n_paths] or None)."""
+        o = self._call(prm, W, seed, path_begin, n_paths, store, rows=rows, block=block)
+        return o.stats, o.terminal
+
+    def simulate_bootstrap_horizons(self, prm: _ffi.McpParams, rows, W, block: float, seed: int, path_begin: int, n_paths: int,
+                                    horizons, levels, store: bool):
+        """simulate_horizons() on bootstrap paths (include/mcport.h, mcp_simulate_bootstrap_horizons) -> (stats, hz_stats,
+        bands, terminal, horizon_terminal) as simulate_horizons."""
+        o = self._call(prm, W, seed, path_begin, n_paths, store, rows=rows, block=block, horizons=horizons, levels=levels)
+        return o.stats, o.hz_stats, o.bands, o.terminal, o.horizon_terminal
+
+    def simulate_rebalanced(self, prm: _ffi.McpParams, period: int, cost: float, W, seed: int, path_begin: int, n_paths: int,
+                            store: bool, mu=None, chol=None, rows=None, block: float = 1.0, horizons=None, levels=()):
+        """simulate() / simulate_horizons() / simulate_bootstrap[_horizons]() with the weights rebalanced every `period` steps
+        (0: bought and held) at the proportional cost `cost` (SPEC.md 4.5 / 5.4; include/mcport.h, mcp_simulate_rebalanced).
+        Draws: `mu` and `chol` (Gaussian) or `rows` and `block` (bootstrap).  -> (stats [K], hz_stats [H, K], bands [H, K, L],
+        terminal, horizon_terminal) as simulate_horizons; the horizon entries are None without horizons."""
+        o = self._call(prm, W, seed, path_begin, n_paths, store, mu=mu, chol=chol, rows=rows, block=block, period=period, cost=cost,
+                       horizons=horizons, levels=levels)
+        return o.stats, o.hz_stats, o.bands, o.terminal, o.horizon_terminal
+
+    def simulate_student_t(self, prm: _ffi.McpParams, dof: int, mu, chol, W, seed: int, path_begin: int, n_paths: int, store: bool,
+                           drawdown: bool = False, horizons=None, levels=()):
+        """simulate() / simulate_drawdown() / simulate_horizons() on Student-t draws with `dof` degrees of freedom (SPEC.md 2.2 /
+        4.6; include/mcport.h, mcp_simulate_student_t; simple compounding only) -> (stats [K], dd_stats [K] or None, hz_stats
+        [H, K], bands [H, K, L], terminal, qd, horizon_terminal): the entries of the blocks not asked for are None; with `store`,
+        terminal is [K, n_paths], qd the binary32 drawdown q [K, n_paths], horizon_terminal [H, K, n_paths]."""
+        return tuple(self._call(prm, W, seed, path_begin, n_paths, store, mu=mu, chol=chol, dof=dof, drawdown=drawdown,
+                                horizons=horizons, levels=levels))
+
+
+# What Context._call returns: mcp_stats record arrays (stats [K], dd_stats [K], hz_stats [H, K]), bands [H, K, L] and the stored
+# binary32 arrays (terminal [K, n], qd [K, n], horizon_terminal [H, K, n]).
+_Outputs = collections.namedtuple("_Outputs", "stats dd_stats hz_stats bands terminal qd horizon_terminal")
 
 
 def check_dof(dof):
@@ -366,73 +331,71 @@ def simulate_paths(mu, cov, weights, n_steps=252, n_paths=10_000, seed=0, v0=1.0
         raise ValueError("dof needs simple compounding, the spec's normals, the unfolded recurrence and constant weights: not with "
                          "fold, native_math, rebalance or compounding='log'")
     period, cost = check_rebalance(rebalance, rebalance_cost)
-    if period is not None and (drawdown or fold or native_math or compounding == "log"):
-        raise ValueError("rebalance needs simple compounding, the spec's normals and the unfolded recurrence: not with drawdown, fold, "
-                         "native_math or compounding='log'")
+    if period is not None and (drawdown or fold or native_math):
+        raise ValueError("rebalance needs the spec's normals and the unfolded recurrence: not with drawdown, fold or native_math")
     if drawdown and (fold or native_math):
         raise ValueError("drawdown=True needs the spec's normals and the unfolded recurrence: not with fold or native_math")
+    if horizons is not None and (drawdown or fold or native_math):
+        raise ValueError("horizons need the spec's normals and the unfolded recurrence: not with drawdown, fold or native_math")
+    steps, levels = _check_walk(n_steps, horizons, bands, period, compounding, shard)
+    mu32, L, W = prepare_inputs(mu, cov, weights, chol)
+    prm, ctx = _setup(mu32.shape[0], n_steps, W.shape[0], compounding, v0, alpha, rf, native_math, fold, devices, shard, context)
+    out = ctx._call(prm, W, int(seed), int(path_begin), int(n_paths), store, mu=mu32, chol=L, dof=dof, period=period, cost=cost,
+                    drawdown=drawdown, horizons=steps, levels=levels)
+    return _result(out, np.asarray(weights).ndim == 1, store, as_array, steps, levels, compounding)
+
+
+def _check_walk(n_steps, horizons, bands, period, compounding, shard):
+    """The argument rules of simulate_paths and simulate_bootstrap alike: rebalancing compounds simply, bands need horizons, and
+    `shard` -> (steps, levels) of check_horizons, or (None, ()) without horizons."""
+    if period is not None and compounding == "log":
+        raise ValueError("rebalance needs simple compounding: not with compounding='log'")
     if horizons is not None:
-        if drawdown or fold or native_math:
-            raise ValueError("horizons need the spec's normals and the unfolded recurrence: not with drawdown, fold or native_math")
         steps, levels = check_horizons(horizons, bands, n_steps)
     elif len(np.atleast_1d(np.asarray(bands, np.float64))):
         raise ValueError("bands need horizons")
-    single = np.asarray(weights).ndim == 1
-    mu32, L, W = prepare_inputs(mu, cov, weights, chol)
-    devs = (0,) if not devices else tuple(int(d) for d in devices)
+    else:
+        steps, levels = None, ()
     if shard not in ("auto", "paths", "portfolios"):
         raise ValueError("shard must be 'auto', 'paths' or 'portfolios'")
-    by_portfolio = len(devs) > 1 and (shard == "portfolios" or (shard == "auto" and W.shape[0] >= 512 * len(devs)))
-    prm = _ffi.make_params(mu32.shape[0], n_steps, W.shape[0], compounding, v0, alpha, rf, native_math, fold, by_portfolio)
-    ctx = context if context is not None else default_context(devs)
-    if dof is not None:
-        stats, dd_stats, hz_stats, hz_bands, term, raw, hz_term = ctx.simulate_student_t(
-            prm, dof, mu32, L, W, int(seed), int(path_begin), int(n_paths), store, drawdown=drawdown,
-            horizons=steps if horizons is not None else None, levels=levels if horizons is not None else ())
-        mdd = mdd_from_raw(raw, compounding) if drawdown and store else None
-        if as_array:
-            if horizons is not None:
-                return (stats, hz_stats, hz_bands, term, hz_term) if store else (stats, hz_stats, hz_bands)
-            if drawdown:
-                return (stats, dd_stats, term, mdd) if store else (stats, dd_stats)
-            return (stats, term) if store else stats
-    elif period is not None:
-        stats, hz_stats, hz_bands, term, hz_term = ctx.simulate_rebalanced(
-            prm, period, cost, W, int(seed), int(path_begin), int(n_paths), store, mu=mu32, chol=L,
-            horizons=steps if horizons is not None else None, levels=levels if horizons is not None else ())
-        if as_array:
-            if horizons is not None:
-                return (stats, hz_stats, hz_bands, term, hz_term) if store else (stats, hz_stats, hz_bands)
-            return (stats, term) if store else stats
-    elif horizons is not None:
-        stats, hz_stats, hz_bands, term, hz_term = ctx.simulate_horizons(prm, mu32, L, W, int(seed), int(path_begin), int(n_paths),
-                                                                        steps, levels, store)
-        if as_array:
+    return steps, levels
+
+
+def _setup(n_assets, n_steps, K, compounding, v0, alpha, rf, native_math, fold, devices, shard, context):
+    """-> (mcp_params, Context) of a call: shard="portfolios" (or "auto" with K >= 512 per device) shards the weight matrix."""
+    devs = (0,) if not devices else tuple(int(d) for d in devices)
+    by_portfolio = len(devs) > 1 and (shard == "portfolios" or (shard == "auto" and K >= 512 * len(devs)))
+    prm = _ffi.make_params(n_assets, n_steps, K, compounding, v0, alpha, rf, native_math, fold, by_portfolio)
+    return prm, context if context is not None else default_context(devs)
+
+
+def _result(out, single, store, as_array, steps, levels, compounding):
+    """What simulate_paths / simulate_bootstrap return for Context._call's outputs `out`: with as_array the record arrays (stats,
+    then (hz_stats, bands) or dd_stats, then with `store` terminal and horizon_terminal or max_drawdown); else one dict per
+    portfolio (one dict for a single weight vector) with its 'drawdown' / 'horizons' blocks and, with `store`, the stored arrays."""
+    stats, dd_stats, hz_stats, hz_bands, term, qd, hz_term = out
+    mdd = mdd_from_raw(qd, compounding) if dd_stats is not None and store else None
+    if as_array:                          # [K] structured arrays (fields of mcp_stats), for large sweeps
+        if hz_stats is not None:
             return (stats, hz_stats, hz_bands, term, hz_term) if store else (stats, hz_stats, hz_bands)
-    elif drawdown:
-        stats, dd_stats, term, raw = ctx.simulate_drawdown(prm, mu32, L, W, int(seed), int(path_begin), int(n_paths), store)
-        mdd = mdd_from_raw(raw, compounding) if store else None
-        if as_array:
+        if dd_stats is not None:
             return (stats, dd_stats, term, mdd) if store else (stats, dd_stats)
-    else:
-        stats, term = ctx.simulate(prm, mu32, L, W, int(seed), int(path_begin), int(n_paths), store)
-        if as_array:                      # [K] structured array (fields of mcp_stats), for large sweeps
-            return (stats, term) if store else stats
-    out = [stats_to_dict(stats[k]) for k in range(W.shape[0])]
-    for k, d in enumerate(out):
-        if drawdown:
+        return (stats, term) if store else stats
+    res = [stats_to_dict(stats[k]) for k in range(stats.shape[0])]
+    for k, d in enumerate(res):
+        if dd_stats is not None:
             d["drawdown"] = drawdown_to_dict(dd_stats[k])
-        if horizons is not None:
+        if hz_stats is not None:
             d["horizons"] = dict({"steps": steps.astype(np.int64), "levels": levels.copy(), "bands": hz_bands[:, k, :]},
                                  **{f: hz_stats[f][:, k].astype(np.int64 if f == "n_tail" else np.float64)
                                     for f in ("mean", "std", "var", "cvar", "min", "max", "n_tail")})
         if store:
             d["terminal"] = term[k]
-            if drawdown:
+            if dd_stats is not None:
                 d["max_drawdown"] = mdd[k]
-            if horizons is not None:
+            if hz_stats is not None:
                 d["horizon_terminal"] = hz_term[:, k, :]
-    return out[0] if single else out
+    return res[0] if single else res
 
 
 def bootstrap_inputs(returns, weights):
@@ -479,51 +442,15 @@ def simulate_bootstrap(returns, weights, n_steps=252, n_paths=10_000, block=1.0,
                          "Student-t draws are a parametric model, call simulate_paths(dof=...); drawdown on bootstrap paths is "
                          "not supported)")
     period, cost = check_rebalance(rebalance, rebalance_cost)
-    if period is not None and compounding == "log":
-        raise ValueError("rebalance needs simple compounding: not with compounding='log'")
     b = float(block)
     if not b >= 1.0:
         raise ValueError(f"block (mean block length) must be >= 1 or inf, got {block!r}")
-    if horizons is not None:
-        steps, levels = check_horizons(horizons, bands, n_steps)
-    elif len(np.atleast_1d(np.asarray(bands, np.float64))):
-        raise ValueError("bands need horizons")
-    single = np.asarray(weights).ndim == 1
+    steps, levels = _check_walk(n_steps, horizons, bands, period, compounding, shard)
     rows, W = bootstrap_inputs(returns, weights)
-    devs = (0,) if not devices else tuple(int(d) for d in devices)
-    if shard not in ("auto", "paths", "portfolios"):
-        raise ValueError("shard must be 'auto', 'paths' or 'portfolios'")
-    by_portfolio = len(devs) > 1 and (shard == "portfolios" or (shard == "auto" and W.shape[0] >= 512 * len(devs)))
-    prm = _ffi.make_params(rows.shape[1], n_steps, W.shape[0], compounding, v0, alpha, rf, False, False, by_portfolio)
-    ctx = context if context is not None else default_context(devs)
-    if period is not None:
-        stats, hz_stats, hz_bands, term, hz_term = ctx.simulate_rebalanced(
-            prm, period, cost, W, int(seed), int(path_begin), int(n_paths), store, rows=rows, block=b,
-            horizons=steps if horizons is not None else None, levels=levels if horizons is not None else ())
-        if as_array:
-            if horizons is not None:
-                return (stats, hz_stats, hz_bands, term, hz_term) if store else (stats, hz_stats, hz_bands)
-            return (stats, term) if store else stats
-    elif horizons is not None:
-        stats, hz_stats, hz_bands, term, hz_term = ctx.simulate_bootstrap_horizons(
-            prm, rows, W, b, int(seed), int(path_begin), int(n_paths), steps, levels, store)
-        if as_array:
-            return (stats, hz_stats, hz_bands, term, hz_term) if store else (stats, hz_stats, hz_bands)
-    else:
-        stats, term = ctx.simulate_bootstrap(prm, rows, W, b, int(seed), int(path_begin), int(n_paths), store)
-        if as_array:
-            return (stats, term) if store else stats
-    out = [stats_to_dict(stats[k]) for k in range(W.shape[0])]
-    for k, d in enumerate(out):
-        if horizons is not None:
-            d["horizons"] = dict({"steps": steps.astype(np.int64), "levels": levels.copy(), "bands": hz_bands[:, k, :]},
-                                 **{f: hz_stats[f][:, k].astype(np.int64 if f == "n_tail" else np.float64)
-                                    for f in ("mean", "std", "var", "cvar", "min", "max", "n_tail")})
-        if store:
-            d["terminal"] = term[k]
-            if horizons is not None:
-                d["horizon_terminal"] = hz_term[:, k, :]
-    return out[0] if single else out
+    prm, ctx = _setup(rows.shape[1], n_steps, W.shape[0], compounding, v0, alpha, rf, False, False, devices, shard, context)
+    out = ctx._call(prm, W, int(seed), int(path_begin), int(n_paths), store, rows=rows, block=b, period=period, cost=cost,
+                    horizons=steps, levels=levels)
+    return _result(out, np.asarray(weights).ndim == 1, store, as_array, steps, levels, compounding)
 
 
 def simulate_sweep(mu, cov, weights=None, n_portfolios=2500, min_weights=None, max_weights=None, n_steps=252,
