@@ -74,6 +74,16 @@ def main(paths, resample_rule="M", user_rf=3.0, investment=10000.0, seed=12345, 
     for h, b in zip(tfan["steps"], tfan["bands"]):
         lo, mid, hi = investment * (1.0 + b)
         print(f"  Student-t fan after {h} period(s): 2.5 % {lo:,.2f}  median {mid:,.2f}  97.5 % {hi:,.2f}")
+    # a withdrawal plan on the same weights (SPEC.md 4.7 / 5.6): 1.5 % of the capital taken out after every period for 6 years;
+    # a path whose value is used up is ruined and stays so -- the share of ruined paths per horizon is the survival curve
+    T, take = 6 * af, 0.015 * investment
+    plan = mcp.simulate_paths(mu_step, cov_step, w, n_steps=T, n_paths=n_paths, seed=seed, v0=investment, cashflow=-take,
+                              target=investment, horizons=[2 * af, 4 * af, 6 * af], bands=(50.0,))
+    cash = plan["cashflow"]
+    print(f"withdrawal plan ({take:,.2f} per period over {T} periods, {-cash['contributed']:,.2f} in all): ruin probability at the end "
+          f"{cash['ruin_probability']:.4f}  below the initial capital {cash['shortfall_probability']:.4f}")
+    for h, p, b in zip(plan["horizons"]["steps"], plan["horizons"]["ruin_probability"], plan["horizons"]["bands"]):
+        print(f"  ruined after {h} periods: {p:.4f}  median value {investment * (1.0 + b[0]):,.2f}")
     # the same allocation bought and held, and traded back to the weights every 3 periods at 10 bp of the amount traded
     # (SPEC.md 4.5): a dollar allocation drifts with the prices instead of being rebalanced after every period for free
     for label, kw in (("bought and held", {"rebalance": "never"}),

@@ -124,3 +124,16 @@ with tab_forecast:                                            # app.py:785-809
         fan = {"horizon": horizons, **{f"{q} %": (v0 * (1.0 + b[:, j])).tolist() for j, q in enumerate(levels)}}
         st.line_chart(fan, x="horizon")
         st.write({"asset": name, **fan})
+    # contributions or withdrawals on the optimum (SPEC.md 4.7 / 5.6): the flow arrives after every period, a path whose value is
+    # used up is ruined and stays so; the ruined share per horizon stands next to the fan
+    flow = st.number_input("contribution (+) or withdrawal (-) per period", value=-0.05 * float(state["investment_amount"]))
+    goal = st.number_input("target value at the end", value=float(state["investment_amount"]))
+    plan = mcp.simulate_paths(mu_step, cov_step, w, n_steps=horizons[-1], n_paths=n_paths, seed=12345, v0=state["investment_amount"],
+                              cashflow=float(flow), target=float(goal), horizons=horizons, bands=levels)
+    pb = plan["horizons"]["bands"]
+    st.subheader("Monte Carlo optimum with the cash flow: forecast fan and ruin probability")
+    st.line_chart({"period": horizons, **{f"{q} %": (state["investment_amount"] * (1.0 + pb[:, j])).tolist()
+                                          for j, q in enumerate(levels)}}, x="period")
+    st.write({"cash flow per period": float(flow), "paid in (+) / taken out (-) in all": plan["cashflow"]["contributed"],
+              "ruin probability per horizon": {int(h): float(p) for h, p in zip(horizons, plan["horizons"]["ruin_probability"])},
+              "shortfall probability at the end": plan["cashflow"]["shortfall_probability"]})

@@ -286,6 +286,48 @@ int mcp_simulate_student_t(mcp_ctx *ctx, const mcp_params *prm, const mcp_studen
                            mcp_stats *hz_stats_out,    /* [H*K], NULL iff n_horizons == 0 */
                            double *bands_out);         /* [H*K*L], NULL iff n_levels == 0 */
 
+/* Contributions, withdrawals and ruin (SPEC.md 4.7 / 5.6).  flows: the schedule c_1 .. c_T, n_flows == prm->n_steps finite
+ * binary32 values in the units of v0 (positive: paid in, negative: taken out), the same for every portfolio; flow c_s arrives
+ * at the end of step s.  has_target (0 or 1): also count the paths whose value is below fl32(target) (finite). */
+typedef struct {
+    const float *flows;
+    int32_t n_flows;
+    int32_t has_target;
+    double target;
+} mcp_cashflow;
+
+/* mcp_simulate / mcp_simulate_horizons / mcp_simulate_bootstrap[_horizons] / mcp_simulate_student_t with the schedule applied
+ * inside the walk (simple compounding only): per step U = fma(V, rho, V), U = U + c_s, V = (V > 0 and U > 0) ? U : +0 -- ruin is
+ * absorbing, a ruined path is stored as +0 and every other stored value is > 0.  Draws: exactly one source -- mu and chol (st
+ * NULL: Gaussian; st: Student-t, SPEC.md 2.2) or boot (mu, chol and st NULL).  n_horizons = 0: no horizons (horizons ignored,
+ * n_levels = 0, horizon_out, hz_stats_out, bands_out and hz_counts_out NULL); otherwise the horizons, records and bands of
+ * mcp_simulate_horizons, V_h taken after the flow c_h.  The records are those of x = V/fl32(v0) - 1: terminal wealth over the
+ * INITIAL value, not a return on the capital paid in.  The moments are pivoted at SPEC.md 5.6 (mcp_cashflow_pivots).
+ * counts_out[k] = {#(V_T == +0), has_target ? #(V_T < fl32(target)) : 0}, hz_counts_out the same per horizon row h*K + k:
+ * integers summed over the shards, exact.  Argument errors (MCP_E_ARG: a NULL struct, NULL flows with n_steps > 0, n_flows !=
+ * n_steps, a flow or target that is not finite, has_target not 0 / 1, fl32(v0) == 0, NULL counts_out) are found before any
+ * device is touched; log compounding, MCP_FLAG_FOLD, MCP_FLAG_NATIVE_MATH: MCP_E_UNSUPPORTED.  K >= 17 runs as passes of 8
+ * portfolios. */
+int mcp_simulate_cashflow(mcp_ctx *ctx, const mcp_params *prm, const mcp_cashflow *cf,
+                          const float *mu, const float *chol,   /* Gaussian or Student-t draws ...                */
+                          const mcp_bootstrap *boot,             /* ... or bootstrap rows: exactly one             */
+                          const mcp_student_t *st,               /* NULL: Gaussian; needs mu and chol              */
+                          const float *W, uint64_t seed, uint64_t path_begin, uint64_t n_paths,
+                          int n_horizons, const int32_t *horizons, int n_levels, const double *levels,
+                          float *terminal_out,        /* NULL or host [K*n_paths] */
+                          mcp_stats *stats_out,       /* [K] */
+                          uint64_t *counts_out,       /* [K][2] {n_ruined, n_short} */
+                          float *horizon_out,         /* NULL or host [H*K*n_paths], row h*K + k */
+                          mcp_stats *hz_stats_out,    /* [H*K], NULL iff n_horizons == 0 */
+                          double *bands_out,          /* [H*K*L], NULL iff n_levels == 0 */
+                          uint64_t *hz_counts_out);   /* [H*K][2], NULL iff n_horizons == 0 */
+/* The shift of the moments of paths with cash flows at prm->n_steps (SPEC.md 5.6; host side, binary64 from the binary32 inputs):
+ * with m_k the per-step mean of mcp_pivots (mu) or of mcp_bootstrap_pivots (boot; exactly one of mu and boot), A_0 = fl32(v0),
+ * A_s = A_{s-1} (1 + m_k) + c_s (a product, then a sum):  c_k = max(A_T, 0) / fl32(v0) - 1, 0 where it is not finite.  The
+ * exact mean of x while no path is ruined. */
+int mcp_cashflow_pivots(const mcp_params *prm, const mcp_cashflow *cf, const float *mu, const mcp_bootstrap *boot,
+                        const float *W, double *pivots_out /* [K] */);
+
 /* The reference's own sweep (app.py:699-717) over HISTORICAL returns, loop body app.py:708-713 for P weight
  * vectors at once, binary64 like the reference.  returns: [R*N] row-major (returns_df.values, app.py:667),
  * mean/cov: the annualised mean_returns / cov_matrix of app.py:679-680, W: [P*N] (rows as drawn at

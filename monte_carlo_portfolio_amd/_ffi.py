@@ -70,6 +70,11 @@ class McpStudentT(ctypes.Structure):
     _fields_ = [("dof", ctypes.c_int32), ("reserved", ctypes.c_int32)]
 
 
+class McpCashflow(ctypes.Structure):
+    """mcp_cashflow: the schedule c_1 .. c_T (binary32, n_flows == n_steps) and the optional target of SPEC.md 4.7 / 5.6."""
+    _fields_ = [("flows", ctypes.c_void_p), ("n_flows", ctypes.c_int32), ("has_target", ctypes.c_int32), ("target", ctypes.c_double)]
+
+
 STATS_DTYPE = np.dtype([
     ("n", np.uint64), ("n_tail", np.uint64), ("mean", np.float64), ("m2", np.float64), ("std", np.float64),
     ("sharpe", np.float64), ("var", np.float64), ("cvar", np.float64), ("min", np.float64), ("max", np.float64),
@@ -128,6 +133,10 @@ SIGNATURES = {
     "mcp_rebalance_pivots": (_int, [_PP, ctypes.POINTER(McpRebalance), _vp, ctypes.POINTER(McpBootstrap), _f32p, _f64p]),
     "mcp_simulate_student_t": (_int, [_vp, _PP, ctypes.POINTER(McpStudentT), _vp, _vp, _vp, _u64, _u64, _u64, _int, _vp, _int, _vp, _vp,
                                       _vp, _vp, _vp, _vp, _vp, _vp]),
+    "mcp_simulate_cashflow": (_int, [_vp, _PP, ctypes.POINTER(McpCashflow), _vp, _vp, ctypes.POINTER(McpBootstrap),
+                                     ctypes.POINTER(McpStudentT), _vp, _u64, _u64, _u64, _int, _vp, _int, _vp, _vp, _vp, _vp, _vp, _vp,
+                                     _vp, _vp]),
+    "mcp_cashflow_pivots": (_int, [_PP, ctypes.POINTER(McpCashflow), _vp, ctypes.POINTER(McpBootstrap), _f32p, _f64p]),
     "mcp_percentile_rank_q": (_int, [_u64, ctypes.c_double, ctypes.POINTER(_u64), ctypes.POINTER(_u64),
                                      ctypes.POINTER(ctypes.c_double)]),
     "mcp_percentile_rank": (_int, [_u64, ctypes.c_double, ctypes.POINTER(_u64), ctypes.POINTER(_u64),
@@ -275,6 +284,28 @@ def rebalance_pivots(prm: McpParams, period: int, W: np.ndarray, mu: np.ndarray 
     bt = make_bootstrap(np.ascontiguousarray(rows, np.float32), 1.0) if rows is not None else None
     check(lib().mcp_rebalance_pivots(ctypes.byref(prm), ctypes.byref(rb), mu_p.ctypes.data_as(_vp) if mu_p is not None else None,
                                      ctypes.byref(bt) if bt is not None else None, W, out))
+    return out
+
+
+def make_cashflow(flows: np.ndarray, target=None) -> McpCashflow:
+    """mcp_cashflow over a C-contiguous binary32 [T] array (the caller keeps `flows` alive for the call)."""
+    if flows.dtype != np.float32 or flows.ndim != 1 or not flows.flags.c_contiguous:
+        raise ValueError("cash flows must be a C-contiguous float32 [n_steps] array")
+    return McpCashflow(flows.ctypes.data_as(ctypes.c_void_p) if flows.size else None, int(flows.size), 0 if target is None else 1,
+                       0.0 if target is None else float(target))
+
+
+def cashflow_pivots(prm: McpParams, flows: np.ndarray, W: np.ndarray, mu: np.ndarray | None = None,
+                    rows: np.ndarray | None = None) -> np.ndarray:
+    """[K] shifts of the moments of paths with cash flows (SPEC.md 5.6; include/mcport.h, mcp_cashflow_pivots), pure host
+    arithmetic: pass the drift `mu` (Gaussian and Student-t draws) or the binary32 [R, N] `rows` (bootstrap draws)."""
+    out = np.zeros(W.shape[0], np.float64)
+    flows = np.ascontiguousarray(flows, np.float32)
+    cf = make_cashflow(flows)
+    mu_p = np.ascontiguousarray(mu, np.float32) if mu is not None else None
+    bt = make_bootstrap(np.ascontiguousarray(rows, np.float32), 1.0) if rows is not None else None
+    check(lib().mcp_cashflow_pivots(ctypes.byref(prm), ctypes.byref(cf), mu_p.ctypes.data_as(_vp) if mu_p is not None else None,
+                                    ctypes.byref(bt) if bt is not None else None, W, out))
     return out
 
 

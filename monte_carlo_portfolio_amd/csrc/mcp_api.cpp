@@ -199,6 +199,19 @@ int check_student_t(const mcp_params* prm, const mcp_student_t* st) {
   return MCP_OK;
 }
 
+// SPEC.md 4.7: n_flows == n_steps finite flows, has_target 0 / 1 with a finite target, fl32(v0) > 0
+int check_cashflow(const mcp_params* prm, const mcp_cashflow* cf) {
+  if (!cf) return fail(MCP_E_ARG, "cashflow is NULL");
+  if (cf->n_flows != prm->n_steps) return fail(MCP_E_ARG, "n_flows=%d must equal n_steps=%d", cf->n_flows, prm->n_steps);
+  if (prm->n_steps > 0 && !cf->flows) return fail(MCP_E_ARG, "cashflow flows is NULL");
+  for (int s = 0; s < cf->n_flows; s++)
+    if (!std::isfinite(cf->flows[s])) return fail(MCP_E_ARG, "cash flow %d is not finite", s + 1);
+  if (cf->has_target != 0 && cf->has_target != 1) return fail(MCP_E_ARG, "has_target=%d must be 0 or 1", cf->has_target);
+  if (cf->has_target && !std::isfinite(cf->target)) return fail(MCP_E_ARG, "target=%g is not finite", cf->target);
+  if (!((float)prm->v0 > 0.0f)) return fail(MCP_E_ARG, "v0=%g rounds to zero in binary32", prm->v0);
+  return MCP_OK;
+}
+
 // The draws of a walk (SPEC.md 2): Gaussian steps mu + L z, rows of the bootstrap, or Student-t steps mu + L s z.
 enum Source { SRC_GAUSS, SRC_BOOT, SRC_T };
 
@@ -212,6 +225,8 @@ struct Request {
   const mcp_student_t* st = nullptr;    // SRC_T (SPEC.md 2.2)
   bool rebalanced = false;              // SPEC.md 4.5: the rule `reb`
   const mcp_rebalance* reb = nullptr;
+  bool cash = false;                    // SPEC.md 4.7: the schedule `cf`
+  const mcp_cashflow* cf = nullptr;
   bool dd = false;                      // SPEC.md 4.2 / 5.1: the drawdown of every path
   bool hz = false;                      // SPEC.md 4.3 / 5.2: the values after H steps, statistics at alpha and at L levels
   int H = 0, L = 0;
@@ -225,6 +240,8 @@ struct Request {
   float* hz_out = nullptr;              // [H*K*n], row h*K + k
   mcp_stats* hz_stats_out = nullptr;    // [H*K]
   double* bands_out = nullptr;          // [H*K*L]
+  uint64_t* counts_out = nullptr;       // cash flows: [K][2] {n_ruined, n_short} (SPEC.md 5.6)
+  uint64_t* hz_counts_out = nullptr;    // [H*K][2]
 };
 
 Request host_request(Source src, const float* mu, const float* chol, const float* W, float* terminal_out, mcp_stats* stats_out) {
@@ -262,6 +279,7 @@ struct Launch {
   float* d_hz = nullptr;                // horizons: [H][K][hz_stride]
   uint64_t hz_stride = 0;
   const float* d_rows = nullptr;        // bootstrap: [R][N4], zero-padded
+  const float* d_flows = nullptr;       // cash flows: [n_steps]
   void* d_partials = nullptr;
   void* d_hist = nullptr;
   hipStream_t stream = nullptr;
@@ -278,12 +296,21 @@ int check_request(const mcp_params* prm, const Request& rq, uint64_t n_paths, co
   }
   if (rq.src == SRC_BOOT && (rc = check_boot(prm, rq.boot))) return rc;
   if (rq.src == SRC_T && (rc = check_student_t(prm, rq.st))) return rc;
+  if (rq.cash) {
+    if ((rc = check_cashflow(prm, rq.cf))) return rc;
+    if (rq.src == SRC_BOOT ? rq.mu || rq.chol : !rq.mu || !rq.chol)
+      return fail(MCP_E_ARG, "exactly one draw source: mu and chol (with or without student_t), or boot");
+    if (!rq.counts_out) return fail(MCP_E_ARG, "counts_out is NULL");
+    if ((rq.hz_counts_out == nullptr) != !rq.hz) return fail(MCP_E_ARG, "hz_counts_out must be NULL exactly when n_horizons == 0");
+  }
   const bool logc = prm->compounding != MCP_COMPOUND_SIMPLE;
   if (rq.rebalanced && logc) return fail(MCP_E_UNSUPPORTED, "rebalanced paths compound simply (no log compounding)");
+  if (rq.cash && logc) return fail(MCP_E_UNSUPPORTED, "paths with cash flows compound simply (no log compounding)");
   if (rq.src == SRC_T && logc)
     return fail(MCP_E_UNSUPPORTED, "Student-t paths compound simply (log compounding: expm1(S) has no finite mean under t steps)");
   if (prm->flags & (MCP_FLAG_FOLD | MCP_FLAG_NATIVE_MATH)) {   // the fast steps exist for plain Gaussian walks only
-    const char* who = rq.rebalanced        ? "rebalanced paths run on the unfolded recurrence and the spec's normals"
+    const char* who = rq.cash              ? "paths with cash flows run on the unfolded recurrence and the spec's normals"
+                      : rq.rebalanced      ? "rebalanced paths run on the unfolded recurrence and the spec's normals"
                       : rq.src == SRC_T    ? "Student-t paths run on the spec's normals and the unfolded recurrence"
                       : rq.src == SRC_BOOT ? "bootstrap paths draw no normals"
                       : rq.dd              ? "the drawdown runs on the spec's normals and the unfolded recurrence"
@@ -297,6 +324,8 @@ int check_request(const mcp_params* prm, const Request& rq, uint64_t n_paths, co
   if (rq.dd && (rq.src == SRC_BOOT || rq.rebalanced))
     return fail(MCP_E_UNSUPPORTED, "the drawdown is not tracked on bootstrap or rebalanced paths");
   if (rq.src == SRC_T && rq.rebalanced) return fail(MCP_E_UNSUPPORTED, "Student-t draws are not combined with rebalancing");
+  if (rq.cash && (rq.dd || rq.rebalanced))
+    return fail(MCP_E_UNSUPPORTED, "cash flows are not combined with the drawdown or with rebalancing");
   if (rq.src != SRC_BOOT && (uint64_t)prm->n_steps * (uint64_t)((prm->n_assets + 3) / 4) > 0xFFFFFFFFull)
     return fail(MCP_E_UNSUPPORTED, "n_steps * ceil(N/4) exceeds the 32-bit Philox block counter");
   if (!rq.dd && rq.mdd_out) return fail(MCP_E_ARG, "mdd_out needs dd_stats_out");
@@ -369,6 +398,41 @@ void reb_pivots(int N, int K, int T, int m, const double* mu, const float* W, do
     if (F) e = (double)F * std::log1p(gf) + e;
     const double c = std::expm1(e);
     out[k] = std::isfinite(c) ? c : 0.0;
+  }
+}
+
+// SPEC.md 5.6: the per-step mean m_k of the draws, binary64 -- sum_i W[k,i] mu_i (i ascending) or the row mean of SPEC.md 5.3
+void cash_means(int N, int K, const float* mu, const mcp_bootstrap* boot, const float* W, double* out) {
+  if (boot) {
+    std::vector<double> s2((size_t)K);
+    boot_moments(N, boot, W, K, out, s2.data());
+    return;
+  }
+  for (int k = 0; k < K; k++) {
+    const float* w = W + (size_t)k * N;
+    double m = 0.0;
+    for (int i = 0; i < N; i++) m += (double)w[i] * (double)(mu[i] + 0.0f);
+    out[k] = m;
+  }
+}
+
+// SPEC.md 5.6: one Horner walk A_s = A_{s-1} (1 + m) + c_s from A_0 = fl32(v0) per portfolio; the pivot max(A, 0) / fl32(v0) - 1
+// (0 where not finite) after step T into out_T[k] and after the steps of the H horizons into out_hz[h*K + k].
+void cash_pivots(int K, int T, const double* m, const float* flows, double v0, int H, const int32_t* steps, double* out_T, double* out_hz) {
+  const auto pivot = [v0](double A) {
+    const double c = (A > 0.0 ? A : 0.0) / v0 - 1.0;
+    return std::isfinite(A) && std::isfinite(c) ? c : 0.0;
+  };
+  for (int k = 0; k < K; k++) {
+    const double g = 1.0 + m[k];
+    double A = v0;
+    int hi = 0;
+    for (int s = 1; s <= T; s++) {
+      A = A * g;
+      A = A + (double)flows[s - 1];
+      if (hi < H && steps[hi] == s) out_hz[(size_t)(hi++) * K + k] = pivot(A);
+    }
+    out_T[k] = pivot(A);
   }
 }
 
@@ -449,6 +513,11 @@ struct Shard {
     HostBuf<mcp_stats> stats;              // [1 + L][H][K tile] records of the alpha select and of every level's select, mapped
   } hz;
   DevBuf<float> boot;                      // bootstrap calls: [R][N4] observed rows, zero-padded (SPEC.md 2.1)
+  struct {                                 // cash-flow calls (SPEC.md 4.7 / 5.6)
+    DevBuf<float> flows;                   // [n_steps] the schedule
+    DevBuf<unsigned long long> counts;     // [(1 + H) K tile][2] {n_ruined, n_short}: the terminal rows, then the horizon rows
+    HostBuf<unsigned long long> h_counts;  // pinned copy of counts
+  } cf;
 };
 
 int grow_dev(void** p, size_t* cap, size_t need, hipStream_t zero_on = nullptr, bool zero = false) {
@@ -547,6 +616,8 @@ struct mcp_ctx {
   size_t sweep_cap = 0;
   float* h_boot = nullptr;           // bootstrap calls: pinned, portable [R][N4] padded rows, uploaded to every shard's boot buffer
   size_t h_boot_cap = 0;
+  float* h_flows = nullptr;          // cash-flow calls: pinned, portable [n_steps] schedule, uploaded to every shard's flows buffer
+  size_t h_flows_cap = 0;
 };
 
 
@@ -700,6 +771,13 @@ static void fill(mcp::PathArgsBTHZ& x, const Request& rq, const Launch& ln) { fi
 static void fill(mcp::PathArgsT& x, const Request& rq, const Launch&) { x.st = student_block(rq); }
 static void fill(mcp::PathArgsTDD& x, const Request& rq, const Launch& ln) { fill((mcp::PathArgsDD&)x, rq, ln); x.st = student_block(rq); }
 static void fill(mcp::PathArgsTHZ& x, const Request& rq, const Launch& ln) { fill_hz(x, rq, ln); x.st = student_block(rq); }
+static void fill(mcp::PathArgsCF& x, const Request& rq, const Launch& ln) {
+  fill_hz(x, rq, ln);
+  x.bt = boot_block(rq, ln);
+  x.st.dof = rq.src == SRC_T ? rq.st->dof : 0;
+  x.st.pad = 0;
+  x.cf.flows = ln.d_flows;
+}
 static void fill(mcp::PathArgsRB& x, const Request& rq, const Launch& ln) {
   fill_hz(x, rq, ln);
   x.bt = boot_block(rq, ln);
@@ -730,7 +808,7 @@ static int launch_passes(const mcp::PathArgs& a, const Request& rq, const Launch
 static int launch_paths_impl(const mcp_params* prm, const Request& rq, const Launch& ln) {
   const int nb = (prm->n_assets + 3) / 4;
   const int K = prm->n_portfolios;
-  const bool plain = rq.src == SRC_GAUSS && !rq.dd && !rq.hz && !rq.rebalanced;
+  const bool plain = rq.src == SRC_GAUSS && !rq.dd && !rq.hz && !rq.rebalanced && !rq.cash;
   int variant = 0;
   if (prm->flags & MCP_FLAG_FOLD) variant |= mcp::VAR_FOLD;
   if (K > 1) variant |= mcp::VAR_KT8;
@@ -786,12 +864,13 @@ static int launch_paths_impl(const mcp_params* prm, const Request& rq, const Lau
     HIP_TRY(mcp::launch_pass0(*prm, K, ln.d_terminal, ln.stride, 0, nullptr, a.slots, (mcp::MomentPartial*)ln.d_partials,
                               (unsigned long long*)ln.d_hist, ln.stream));
   mcp::PathKernel k;
-  k.family = rq.rebalanced ? mcp::FAM_REB : rq.dd ? mcp::FAM_DD : rq.hz ? mcp::FAM_HZ : mcp::FAM_PLAIN;
+  k.family = rq.cash ? mcp::FAM_CF : rq.rebalanced ? mcp::FAM_REB : rq.dd ? mcp::FAM_DD : rq.hz ? mcp::FAM_HZ : mcp::FAM_PLAIN;
   k.logc = prm->compounding == MCP_COMPOUND_LOG;
   k.boot = rq.src == SRC_BOOT;
   k.blds = k.boot && mcp::boot_fits_lds((uint64_t)rq.boot->n_rows, nb);
   k.stt = rq.src == SRC_T;
   switch (k.family) {
+    case mcp::FAM_CF: return launch_passes<mcp::PathArgsCF>(a, rq, ln, variant, k, nb);
     case mcp::FAM_REB: return launch_passes<mcp::PathArgsRB>(a, rq, ln, variant, k, nb);
     case mcp::FAM_DD: return k.stt ? launch_passes<mcp::PathArgsTDD>(a, rq, ln, variant, k, nb)
                                    : launch_passes<mcp::PathArgsDD>(a, rq, ln, variant, k, nb);
@@ -1028,6 +1107,9 @@ static void free_shard(Shard& sh) {
   release(sh.hz.h_pivot);
   release(sh.hz.stats);
   release(sh.boot);
+  release(sh.cf.flows);
+  release(sh.cf.counts);
+  release(sh.cf.h_counts);
 }
 
 int mcp_ctx_create_multi(const int* devices, int ndev, mcp_ctx** out) {
@@ -1137,6 +1219,7 @@ void mcp_ctx_destroy(mcp_ctx* c) {
   for (Shard& sh : c->sh) free_shard(sh);
   if (c->d_sweep && !c->sh.empty()) { (void)hipSetDevice(c->sh[0].device); (void)hipFree(c->d_sweep); }
   if (c->h_boot) (void)hipHostFree(c->h_boot);
+  if (c->h_flows) (void)hipHostFree(c->h_flows);
   if (have_prev) (void)hipSetDevice(prev_dev);
   delete c;
 }
@@ -1313,6 +1396,7 @@ int run_tile(mcp_ctx* c, const mcp_params* prm, const Request& rq, uint64_t seed
     if (rq.hz && ((rc = grow(sh.hz.values, (size_t)rows * pn)) || (rc = grow(sh.hz.pivot, (size_t)rows)) ||
                   (rc = grow(sh.hz.h_pivot, (size_t)rows)) || (rc = grow_mapped(sh.hz.stats, (size_t)(1 + rq.L) * rows))))
       return rc;
+    if (rq.cash && ((rc = grow(sh.cf.counts, 2 * (size_t)(j.kt + rows))) || (rc = grow(sh.cf.h_counts, 2 * (size_t)(j.kt + rows))))) return rc;
   }
   // 1b. parameters up and the path kernels out, device after device with nothing else in between: every GPU should be
   //     simulating as early as possible.  Shards of a path-sharded tile share one packed block and one pivot vector
@@ -1326,7 +1410,7 @@ int run_tile(mcp_ctx* c, const mcp_params* prm, const Request& rq, uint64_t seed
   const std::vector<float> zmu(boot ? N : 0, 0.0f), zchol(boot ? (size_t)N * N : 0, 0.0f);
   const float* mu = boot ? zmu.data() : rq.mu;
   const float* chol = boot ? zchol.data() : rq.chol;
-  std::vector<double> bm, bs2, rmu(rq.rebalanced ? N : 0);
+  std::vector<double> bm, bs2, rmu(rq.rebalanced ? N : 0), cm;
   if (rq.rebalanced) reb_means(N, rq.mu, boot ? rq.boot : nullptr, rmu.data());
   for (size_t s = 0; s < S; s++) {
     const Job& j = jobs[s];
@@ -1349,8 +1433,13 @@ int run_tile(mcp_ctx* c, const mcp_params* prm, const Request& rq, uint64_t seed
         bs2.resize((size_t)j.kt);
         boot_moments(N, rq.boot, Wt, j.kt, bm.data(), bs2.data());
       }
-      if ((rc = tile_pivots(tp[s], rq, prm->n_steps, Wt, rmu.data(), bm.data(), bs2.data(), sh.h_pivot.p))) return rc;
-      for (int h = 0; rq.hz && h < rq.H; h++)                // SPEC.md 5.2 / 5.3: row h*kt + k is pivoted with n_steps = h
+      if (rq.cash) {                                         // SPEC.md 5.6: one Horner walk gives T and every horizon
+        cm.resize((size_t)j.kt);
+        cash_means(N, j.kt, rq.mu, boot ? rq.boot : nullptr, Wt, cm.data());
+        cash_pivots(j.kt, prm->n_steps, cm.data(), rq.cf->flows, (double)(float)prm->v0, rq.hz ? rq.H : 0, rq.steps, sh.h_pivot.p,
+                    sh.hz.h_pivot.p);
+      } else if ((rc = tile_pivots(tp[s], rq, prm->n_steps, Wt, rmu.data(), bm.data(), bs2.data(), sh.h_pivot.p))) return rc;
+      for (int h = 0; rq.hz && !rq.cash && h < rq.H; h++)                // SPEC.md 5.2 / 5.3: row h*kt + k is pivoted with n_steps = h
         if ((rc = tile_pivots(tp[s], rq, rq.steps[h], Wt, rmu.data(), bm.data(), bs2.data(), sh.hz.h_pivot.p + (size_t)h * j.kt)))
           return rc;
       if (exchange) { shared_packed = sh.h_packed.p; shared_pivot = sh.h_pivot.p; shared_hz_pivot = sh.hz.h_pivot.p; }
@@ -1366,7 +1455,17 @@ int run_tile(mcp_ctx* c, const mcp_params* prm, const Request& rq, uint64_t seed
       ln.d_hz = sh.hz.values.p;
       ln.hz_stride = j.pn;
       ln.d_rows = sh.boot.p;
+      ln.d_flows = sh.cf.flows.p;
       if ((rc = launch_paths_impl(&tp[s], rq, ln))) return rc;
+      if (rq.cash) {                                         // SPEC.md 5.6: the ruined and the short paths of every stored row
+        const size_t rows_hz = rq.hz ? (size_t)rq.H * j.kt : 0;
+        const bool tg = rq.cf->has_target != 0;
+        const float g32 = tg ? (float)rq.cf->target : 0.0f;
+        HIP_TRY(mcp::launch_zero(sh.cf.counts.p, 2 * ((size_t)j.kt + rows_hz) * sizeof(unsigned long long), sh.stream));
+        HIP_TRY(mcp::launch_count_rows(sh.terminal.p, j.pn, j.pn, j.kt, tg, g32, sh.cf.counts.p, sh.stream));
+        if (rows_hz)
+          HIP_TRY(mcp::launch_count_rows(sh.hz.values.p, j.pn, j.pn, (int)rows_hz, tg, g32, sh.cf.counts.p + 2 * (size_t)j.kt, sh.stream));
+      }
     } else {
       // a shard without paths (fewer paths than shards): empty moment partials, nothing in the histogram
       if ((rc = mcp_launch_pass0(&tp[s], sh.terminal.p, 1, 0, (const double*)sh.ws[MCP_WS_PIVOT], sh.ws[MCP_WS_PARTIALS],
@@ -1426,9 +1525,23 @@ int run_tile(mcp_ctx* c, const mcp_params* prm, const Request& rq, uint64_t seed
     if (rq.hz && rq.hz_out)
       for (int h = 0; h < rq.H; h++)
         HIP_TRY(copy_out(rq.hz_out + (size_t)h * prm->n_portfolios * n_total, sh.hz.values.p + (size_t)h * j.kt * j.pn));
+    if (rq.cash)
+      HIP_TRY(hipMemcpyAsync(sh.cf.h_counts.p, sh.cf.counts.p, 2 * (size_t)((rq.hz ? 1 + rq.H : 1) * j.kt) * sizeof(unsigned long long),
+                             hipMemcpyDeviceToHost, sh.stream));
   }
   for (size_t s = 0; s < S; s++)
     if (jobs[s].active) { HIP_TRY(hipSetDevice(c->sh[s].device)); HIP_TRY(hipStreamSynchronize(c->sh[s].stream)); }
+  for (size_t s = 0; rq.cash && s < S; s++) {              // the counts of every shard that walked paths add up (zeroed per call)
+    const Job& j = jobs[s];
+    if (!j.active || !j.pn) continue;
+    const unsigned long long* hc = c->sh[s].cf.h_counts.p;
+    for (int k = 0; k < j.kt; k++)
+      for (int i = 0; i < 2; i++) {
+        rq.counts_out[2 * (size_t)(j.k0 + k) + i] += hc[2 * (size_t)k + i];
+        for (int h = 0; rq.hz && h < rq.H; h++)
+          rq.hz_counts_out[2 * ((size_t)h * prm->n_portfolios + j.k0 + k) + i] += hc[2 * ((size_t)j.kt + (size_t)h * j.kt + k) + i];
+      }
+  }
   for (size_t s = 0; s < S; s++) {
     const Job& j = jobs[s];
     if (!j.active || (exchange && s != 0)) continue;
@@ -1493,6 +1606,22 @@ int simulate_impl(mcp_ctx* c, const mcp_params* prm, const Request& rq, uint64_t
       if ((rc = grow(sh.boot, R * (size_t)n4))) break;
       const hipError_t e = hipMemcpyAsync(sh.boot.p, c->h_boot, bytes, hipMemcpyHostToDevice, sh.stream);
       if (e != hipSuccess) rc = fail(MCP_E_HIP, "bootstrap rows upload: %s", hipGetErrorString(e));
+    }
+  }
+  if (rc == MCP_OK && rq.cash) {
+    // SPEC.md 4.7: the schedule into one pinned staging copy and from there once into the flows buffer of every shard (the tiles
+    // of the call share it); the counts of the call start at zero, every tile and shard adds its own
+    const size_t T = (size_t)prm->n_steps, bytes = T * sizeof(float);
+    memset(rq.counts_out, 0, 2 * (size_t)K * sizeof(uint64_t));
+    if (rq.hz) memset(rq.hz_counts_out, 0, 2 * (size_t)rq.H * K * sizeof(uint64_t));
+    rc = grow_host((void**)&c->h_flows, &c->h_flows_cap, bytes ? bytes : sizeof(float));
+    if (rc == MCP_OK && bytes) memcpy(c->h_flows, rq.cf->flows, bytes);
+    for (size_t s = 0; s < S && rc == MCP_OK; s++) {
+      Shard& sh = c->sh[s];
+      if (hipSetDevice(sh.device) != hipSuccess) { rc = fail(MCP_E_HIP, "hipSetDevice(%d)", sh.device); break; }
+      if ((rc = grow(sh.cf.flows, T ? T : 1)) || !bytes) continue;
+      const hipError_t e = hipMemcpyAsync(sh.cf.flows.p, c->h_flows, bytes, hipMemcpyHostToDevice, sh.stream);
+      if (e != hipSuccess) rc = fail(MCP_E_HIP, "cash-flow schedule upload: %s", hipGetErrorString(e));
     }
   }
   if (rc == MCP_OK && by_portfolio) {
@@ -1622,6 +1751,38 @@ int mcp_simulate_student_t(mcp_ctx* c, const mcp_params* prm, const mcp_student_
   rq.dd_stats_out = dd_stats_out;
   ask_horizons(rq, n_horizons != 0, n_horizons, horizons, n_levels, levels, horizon_out, hz_stats_out, bands_out);
   return simulate_checked(c, prm, rq, seed, path_begin, n_paths);
+}
+
+int mcp_simulate_cashflow(mcp_ctx* c, const mcp_params* prm, const mcp_cashflow* cf, const float* mu, const float* chol,
+                          const mcp_bootstrap* boot, const mcp_student_t* st, const float* W, uint64_t seed, uint64_t path_begin,
+                          uint64_t n_paths, int n_horizons, const int32_t* horizons, int n_levels, const double* levels,
+                          float* terminal_out, mcp_stats* stats_out, uint64_t* counts_out, float* horizon_out, mcp_stats* hz_stats_out,
+                          double* bands_out, uint64_t* hz_counts_out) {
+  if (boot && st) return fail(MCP_E_ARG, "exactly one draw source: mu and chol (with or without student_t), or boot");
+  Request rq = host_request(boot ? SRC_BOOT : st ? SRC_T : SRC_GAUSS, mu, chol, W, terminal_out, stats_out);
+  rq.boot = boot;
+  rq.st = st;
+  rq.cash = true;
+  rq.cf = cf;
+  rq.counts_out = counts_out;
+  rq.hz_counts_out = hz_counts_out;
+  ask_horizons(rq, n_horizons != 0, n_horizons, horizons, n_levels, levels, horizon_out, hz_stats_out, bands_out);
+  return simulate_checked(c, prm, rq, seed, path_begin, n_paths);
+}
+
+int mcp_cashflow_pivots(const mcp_params* prm, const mcp_cashflow* cf, const float* mu, const mcp_bootstrap* boot, const float* W,
+                        double* out) {
+  if (int rc = check_params(prm)) return rc;
+  if (int rc = check_cashflow(prm, cf)) return rc;
+  if ((mu == nullptr) == (boot == nullptr)) return fail(MCP_E_ARG, "exactly one of mu and boot");
+  if (boot)
+    if (int rc = check_boot(prm, boot)) return rc;
+  if (!W || !out) return fail(MCP_E_ARG, "NULL pointer");
+  if (prm->compounding != MCP_COMPOUND_SIMPLE) return fail(MCP_E_UNSUPPORTED, "paths with cash flows compound simply (no log compounding)");
+  std::vector<double> m((size_t)prm->n_portfolios);
+  cash_means(prm->n_assets, prm->n_portfolios, mu, boot, W, m.data());
+  cash_pivots(prm->n_portfolios, prm->n_steps, m.data(), cf->flows, (double)(float)prm->v0, 0, nullptr, out, nullptr);
+  return MCP_OK;
 }
 
 int mcp_sweep_historical(mcp_ctx* c, int N, int R, int P, const double* returns, const double* mean, const double* cov,

@@ -36,6 +36,10 @@
 #ifndef MCP_MIN_WAVES_REB8
 #define MCP_MIN_WAVES_REB8 4 // the same for 8 portfolios, N <= 16: unbounded it took 137 VGPRs (3 waves); at 4 it gets 128, no scratch in the loop
 #endif
+#ifndef MCP_MIN_WAVES_CF8
+#define MCP_MIN_WAVES_CF8 5 // the cash-flow kernel for 8 portfolios, N <= 16: unbounded it took 102 VGPRs (4 waves) where its twin without cash
+                            // flows runs 5; at 5 it gets 93, no scratch, and measured 1.10x the twin instead of 1.12x
+#endif
 #ifndef MCP_EXP_VKEYS
 #define MCP_EXP_VKEYS 1
 #endif
@@ -135,6 +139,30 @@ __device__ __forceinline__ int32_t student_dof(const PathArgsT&) { return kernar
 __device__ __forceinline__ int32_t student_dof(const PathArgsTDD&) { return kernarg_dof<PathArgsTDD>(); }
 __device__ __forceinline__ int32_t student_dof(const PathArgsTHZ&) { return kernarg_dof<PathArgsTHZ>(); }
 
+// Cash flows and ruin (SPEC.md 4.7): the schedule c_1 .. c_T, one binary32 flow per step, the same for every portfolio.
+struct CashArgs {
+  const float* __restrict__ flows;    // [n_steps] device copy; flows[t] = c_{t+1} arrives at the end of step t
+};
+// Arguments of mc_paths_cf_kernel: the horizons of PathArgsHZ (n_horizons = 0: none), the row table of the bootstrap (read only
+// when BOOT), nu (read only when STT) and the schedule.
+struct PathArgsCF : PathArgsHZ {
+  BootArgs bt;
+  StudentArgs st;
+  CashArgs cf;
+};
+__device__ __forceinline__ BootArgs boot_args(const PathArgsCF& a) { return a.bt; }
+__device__ __forceinline__ int32_t student_dof(const PathArgsCF&) { return kernarg_dof<PathArgsCF>(); }
+// c_{t+1} of a cash-flow kernel's launch: wave-uniform, read where it is used through the kernel-argument pointer and the constant
+// address space (two scalar loads per step; nothing held in SGPRs across the walk: the Cholesky factor lives there).
+__device__ __forceinline__ float cash_flow(const PathArgs&, int) { return 0.0f; }
+__device__ __forceinline__ float cash_flow(const PathArgsCF&, int t) {
+  typedef const __attribute__((address_space(4))) PathArgsCF* ccf_p;
+  typedef const __attribute__((address_space(4))) float* cflow_p;
+  ccf_p k = (ccf_p)__builtin_amdgcn_kernarg_segment_ptr();
+  asm volatile("" : "+s"(k));
+  return ((cflow_p)k->cf.flows)[t];
+}
+
 // The LDS copy of the row table takes the slot of the inverse-CDF table (ICDF_LDS_ENTRIES float4: the bootstrap needs neither
 // that table nor the drift copy in its padding): R rows of NB float4 fit when R * NB <= ICDF_LDS_ENTRIES (N = 16: 272 rows).
 __host__ __device__ constexpr bool boot_fits_lds(uint64_t n_rows, int nb) { return n_rows * (uint64_t)nb <= (uint64_t)ICDF_LDS_ENTRIES; }
@@ -212,7 +240,8 @@ constexpr int PATH_BLOCK = 256;
 // BOOT: r is row j_t of the observed returns (SPEC.md 2.1 / 4.4) instead of mu + L z; BLDS: that table is read from LDS.
 // REB: the step updates the assets' returns since the last rebalance B instead of V; V moves at the rebalance dates only
 // (SPEC.md 4.5).  STT: every normal of the step is scaled by s = sqrt((nu - 2) / chi), chi the sum of nu squared normals of
-// counter stream 2 (SPEC.md 2.2 / 4.6).  All nine kernels are the body in mcp_paths_body.inc.
+// counter stream 2 (SPEC.md 2.2 / 4.6).  CF: the step's cash flow c_s is added to V after the update and ruin (V <= 0) is absorbing
+// (SPEC.md 4.7).  All ten kernels are the body in mcp_paths_body.inc.
 #define MCP_PATHS_BOUNDS(NB, KT, PPT) \
   __launch_bounds__(PATH_BLOCK, (NB <= 4 && KT == 1 && PPT == 1) ? MCP_MIN_WAVES : ((KT == 1 && PPT == 1) ? MCP_MIN_WAVES_BIG : 1))
 #define MCP_REB_BOUNDS(NB, KT, PPT) \
@@ -221,7 +250,7 @@ constexpr int PATH_BLOCK = 256;
 
 template <int NB, int KT, int PPT, bool NATIVE, bool FOLD = false, bool LOGC = false>
 __global__ void MCP_PATHS_BOUNDS(NB, KT, PPT) mc_paths_kernel(const PathArgs a) {
-  constexpr bool DD = false, HZ = false, BOOT = false, BLDS = false, REB = false, STT = false;
+  constexpr bool DD = false, HZ = false, BOOT = false, BLDS = false, REB = false, STT = false, CF = false;
 #include "mcp_paths_body.inc"
 }
 
@@ -229,7 +258,7 @@ __global__ void MCP_PATHS_BOUNDS(NB, KT, PPT) mc_paths_kernel(const PathArgs a) 
 // array: appended to PathArgs itself they would move the hidden kernel arguments (grid size) of every plain kernel.
 template <int NB, int KT, int PPT, bool LOGC>
 __global__ void MCP_PATHS_BOUNDS(NB, KT, PPT) mc_paths_dd_kernel(const PathArgsDD a) {
-  constexpr bool DD = true, HZ = false, NATIVE = false, FOLD = false, BOOT = false, BLDS = false, REB = false, STT = false;
+  constexpr bool DD = true, HZ = false, NATIVE = false, FOLD = false, BOOT = false, BLDS = false, REB = false, STT = false, CF = false;
 #include "mcp_paths_body.inc"
 }
 
@@ -237,7 +266,7 @@ __global__ void MCP_PATHS_BOUNDS(NB, KT, PPT) mc_paths_dd_kernel(const PathArgsD
 // at the horizons, V_h stored after each; V_T and the fused epilogue as in mc_paths_kernel.
 template <int NB, int KT, int PPT, bool LOGC>
 __global__ void MCP_PATHS_BOUNDS(NB, KT, PPT) mc_paths_hz_kernel(const PathArgsHZ a) {
-  constexpr bool DD = false, HZ = true, NATIVE = false, FOLD = false, BOOT = false, BLDS = false, REB = false, STT = false;
+  constexpr bool DD = false, HZ = true, NATIVE = false, FOLD = false, BOOT = false, BLDS = false, REB = false, STT = false, CF = false;
 #include "mcp_paths_body.inc"
 }
 
@@ -245,14 +274,14 @@ __global__ void MCP_PATHS_BOUNDS(NB, KT, PPT) mc_paths_hz_kernel(const PathArgsH
 // block per path-step for the row index, no normals, no Cholesky GEMV.  V_T and the fused epilogue as in mc_paths_kernel.
 template <int NB, int KT, int PPT, bool LOGC, bool BLDS>
 __global__ void MCP_PATHS_BOUNDS(NB, KT, PPT) mc_paths_boot_kernel(const PathArgsBT a) {
-  constexpr bool DD = false, HZ = false, NATIVE = false, FOLD = false, BOOT = true, REB = false, STT = false;
+  constexpr bool DD = false, HZ = false, NATIVE = false, FOLD = false, BOOT = true, REB = false, STT = false, CF = false;
 #include "mcp_paths_body.inc"
 }
 
 // The bootstrap kernel with the horizons of SPEC.md 4.3 (the segmented walk of mc_paths_hz_kernel).
 template <int NB, int KT, int PPT, bool LOGC, bool BLDS>
 __global__ void MCP_PATHS_BOUNDS(NB, KT, PPT) mc_paths_boot_hz_kernel(const PathArgsBTHZ a) {
-  constexpr bool DD = false, HZ = true, NATIVE = false, FOLD = false, BOOT = true, REB = false, STT = false;
+  constexpr bool DD = false, HZ = true, NATIVE = false, FOLD = false, BOOT = true, REB = false, STT = false, CF = false;
 #include "mcp_paths_body.inc"
 }
 // The rebalancing kernel (SPEC.md 4.5; simple compounding, Gaussian draws or, BOOT, the bootstrap's rows): the walk in segments
@@ -260,7 +289,7 @@ __global__ void MCP_PATHS_BOUNDS(NB, KT, PPT) mc_paths_boot_hz_kernel(const Path
 // kernel serves terminal-only and horizon calls.  V_T and the fused epilogue as in mc_paths_kernel.
 template <int NB, int KT, int PPT, bool BOOT, bool BLDS>
 __global__ void MCP_REB_BOUNDS(NB, KT, PPT) mc_paths_reb_kernel(const PathArgsRB a) {
-  constexpr bool DD = false, HZ = false, NATIVE = false, FOLD = false, LOGC = false, REB = true, STT = false;
+  constexpr bool DD = false, HZ = false, NATIVE = false, FOLD = false, LOGC = false, REB = true, STT = false, CF = false;
 #include "mcp_paths_body.inc"
 }
 
@@ -269,20 +298,34 @@ __global__ void MCP_REB_BOUNDS(NB, KT, PPT) mc_paths_reb_kernel(const PathArgsRB
 // there.
 template <int NB, int KT, int PPT>
 __global__ void MCP_PATHS_BOUNDS(NB, KT, PPT) mc_paths_t_kernel(const PathArgsT a) {
-  constexpr bool DD = false, HZ = false, NATIVE = false, FOLD = false, LOGC = false, BOOT = false, BLDS = false, REB = false, STT = true;
+  constexpr bool DD = false, HZ = false, NATIVE = false, FOLD = false, LOGC = false, BOOT = false, BLDS = false, REB = false, STT = true, CF = false;
 #include "mcp_paths_body.inc"
 }
 template <int NB, int KT, int PPT>
 __global__ void MCP_PATHS_BOUNDS(NB, KT, PPT) mc_paths_t_dd_kernel(const PathArgsTDD a) {
-  constexpr bool DD = true, HZ = false, NATIVE = false, FOLD = false, LOGC = false, BOOT = false, BLDS = false, REB = false, STT = true;
+  constexpr bool DD = true, HZ = false, NATIVE = false, FOLD = false, LOGC = false, BOOT = false, BLDS = false, REB = false, STT = true, CF = false;
 #include "mcp_paths_body.inc"
 }
 template <int NB, int KT, int PPT>
 __global__ void MCP_PATHS_BOUNDS(NB, KT, PPT) mc_paths_t_hz_kernel(const PathArgsTHZ a) {
-  constexpr bool DD = false, HZ = true, NATIVE = false, FOLD = false, LOGC = false, BOOT = false, BLDS = false, REB = false, STT = true;
+  constexpr bool DD = false, HZ = true, NATIVE = false, FOLD = false, LOGC = false, BOOT = false, BLDS = false, REB = false, STT = true, CF = false;
+#include "mcp_paths_body.inc"
+}
+
+// The cash-flow kernel (SPEC.md 4.7; simple compounding, unfolded recurrence; Gaussian draws, BOOT: the bootstrap's rows, STT:
+// Student-t draws): the segmented walk of mc_paths_hz_kernel with U = fma(V, rho, V) + c_s after every step and V = U while both
+// V and U are positive, +0 from then on.  H = 0 is one segment, so one kernel serves terminal-only and horizon calls.  V_T, the
+// horizons and the fused epilogue as in mc_paths_hz_kernel.
+#define MCP_CF_BOUNDS(NB, KT, PPT) \
+  __launch_bounds__(PATH_BLOCK, (NB <= 4 && PPT == 1) ? (KT == 1 ? MCP_MIN_WAVES : MCP_MIN_WAVES_CF8) \
+                                                     : ((KT == 1 && PPT == 1) ? MCP_MIN_WAVES_BIG : 1))
+template <int NB, int KT, int PPT, bool BOOT, bool BLDS, bool STT>
+__global__ void MCP_CF_BOUNDS(NB, KT, PPT) mc_paths_cf_kernel(const PathArgsCF a) {
+  constexpr bool DD = false, HZ = true, NATIVE = false, FOLD = false, LOGC = false, REB = false, CF = true;
 #include "mcp_paths_body.inc"
 }
 #undef MCP_PATHS_BOUNDS
 #undef MCP_REB_BOUNDS
+#undef MCP_CF_BOUNDS
 
 }  // namespace mcp

@@ -2,10 +2,10 @@
 // mc_paths_dd_kernel (DD = true), mc_paths_hz_kernel (HZ = true), the bootstrap kernels mc_paths_boot_kernel (BOOT = true)
 // and mc_paths_boot_hz_kernel (BOOT = HZ = true), the rebalancing kernel mc_paths_reb_kernel (REB = true, BOOT either) and the
 // Student-t kernels mc_paths_t_kernel / mc_paths_t_dd_kernel / mc_paths_t_hz_kernel (STT = true, DD or HZ as their twins);
-// the step itself is mcp_paths_step.inc.  As a shared __device__ function the plain kernel's registers came out allocated differently;
+// and the cash-flow kernel mc_paths_cf_kernel (CF = HZ = true, BOOT or STT either); the step itself is mcp_paths_step.inc.  As a shared __device__ function the plain kernel's registers came out allocated differently;
 // included, the DD = false kernel compiles to the same instructions as before the drawdown existed.  In scope: the template
-// parameters NB, KT, PPT, NATIVE, FOLD, LOGC, DD, HZ, BOOT, BLDS, REB, STT and the kernel argument `a` (PathArgs, or PathArgsDD /
-// PathArgsHZ / PathArgsBT / PathArgsBTHZ / PathArgsRB / PathArgsT / PathArgsTDD / PathArgsTHZ which start with one).  Without HZ the walk is the one loop it always was, so the plain and drawdown kernels keep their code.
+// parameters NB, KT, PPT, NATIVE, FOLD, LOGC, DD, HZ, BOOT, BLDS, REB, STT, CF and the kernel argument `a` (PathArgs, or PathArgsDD /
+// PathArgsHZ / PathArgsBT / PathArgsBTHZ / PathArgsRB / PathArgsT / PathArgsTDD / PathArgsTHZ / PathArgsCF which start with one).  Without HZ the walk is the one loop it always was, so the plain and drawdown kernels keep their code.
   constexpr int N4 = 4 * NB;
   // wave-uniform parameters through the constant address space -> s_load_dword* into SGPRs
   typedef const __attribute__((address_space(4))) float* cfloat_p;

@@ -3,7 +3,7 @@
 // and drawdown state).  REB: no rho and no V; the returns since the last rebalance B_i = B_i + r_i + B_i r_i instead
 // (SPEC.md 4.5), a = B + r then B = fma(B, r, a), one v_pk_add_f32 and one v_pk_fma_f32 per pair of assets.  STT: the step's
 // chi blocks first (only s stays live while the asset normals are formed), then every asset normal scaled by s as it leaves
-// block_normals (SPEC.md 2.2 / 4.6).  In scope: everything mcp_paths_body.inc declares before its step loops, and t.
+// block_normals (SPEC.md 2.2 / 4.6).  CF: the flow c_s after the update, ruin absorbing (SPEC.md 4.7).  In scope: everything mcp_paths_body.inc declares before its step loops, and t.
       float rho[PPT][KT];
       if constexpr (BOOT) {
         // SPEC.md 2.1 / 4.4: one Philox block on counter (t, 1, p_lo, p_hi); j_t = mulhi(x0, R) on a restart (t = 0 or
@@ -155,7 +155,17 @@
       }
       }  // !FOLD
       }  // !BOOT
-      if constexpr (!REB) {
+      if constexpr (CF) {
+        // SPEC.md 4.7: U = fma(V, rho, V), U = U + c_s (two roundings), V = (V > 0 and U > 0) ? U : +0 -- a NaN U is ruin too
+        const float cs = cash_flow(a, t);
+#pragma unroll
+        for (int e = 0; e < PPT; e++)
+#pragma unroll
+          for (int k = 0; k < KT; k++) {
+            const float u = fma32(V[e][k], rho[e][k], V[e][k]) + cs;
+            V[e][k] = (V[e][k] > 0.0f && u > 0.0f) ? u : 0.0f;
+          }
+      } else if constexpr (!REB) {
 #pragma unroll
       for (int e = 0; e < PPT; e++)
 #pragma unroll

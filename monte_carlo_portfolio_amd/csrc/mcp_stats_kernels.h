@@ -62,9 +62,10 @@ enum { VAR_KT8 = 1, VAR_NATIVE = 4, VAR_FOLD = 8 };
 // is the PathArgs base of the kernel's argument struct:
 //   FAM_PLAIN  PathArgs, PathArgsBT (boot), PathArgsT (stt)        FAM_DD   PathArgsDD, PathArgsTDD (stt)
 //   FAM_HZ     PathArgsHZ, PathArgsBTHZ (boot), PathArgsTHZ (stt)  FAM_REB  PathArgsRB (boot: its rows instead of normals)
+//   FAM_CF     PathArgsCF (boot: its rows; stt: t draws; the horizons optional)
 // `blds`: the bootstrap's row table is copied into LDS (it fits boot_fits_lds) instead of being read from global memory.
 // VAR_NATIVE and VAR_FOLD exist for the plain Gaussian kernel only.
-enum PathFamily { FAM_PLAIN, FAM_DD, FAM_HZ, FAM_REB };
+enum PathFamily { FAM_PLAIN, FAM_DD, FAM_HZ, FAM_REB, FAM_CF };
 struct PathKernel {
   int family;
   bool logc, boot, blds, stt;
@@ -103,6 +104,10 @@ hipError_t launch_final(const mcp_params& prm, int K, uint64_t n, double gamma, 
 hipError_t launch_stats(const mcp_params& prm, int K, int world, const mcp_record* gathered, const Quantile* quant,
                         mcp_stats* out, hipStream_t s);
 hipError_t launch_zero(void* p, size_t bytes, hipStream_t s);
+// counts[r] += {#(v == 0), target ? #(v < *target) : 0} over the n live values of each of the `rows` rows of a [rows][stride]
+// binary32 array (SPEC.md 5.6); `counts` is [rows][2] and zeroed by the caller
+hipError_t launch_count_rows(const float* values, uint64_t stride, uint64_t n, int rows, bool has_target, float target,
+                             unsigned long long* counts, hipStream_t s);
 // every buffer <- element-wise sum of the `nsrc` buffers (u64 words): the exchange between logical shards of ONE device
 // (or of devices with peer access)
 hipError_t launch_sum_u64(unsigned long long* const* bufs, int nsrc, size_t words, hipStream_t s);

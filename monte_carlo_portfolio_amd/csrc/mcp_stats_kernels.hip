@@ -570,6 +570,45 @@ hipError_t launch_zero(void* p, size_t bytes, hipStream_t s) {
   return hipGetLastError();
 }
 
+// SPEC.md 5.6: the ruined (V == +0) and the short (V < g32) paths of every row.  One workgroup column per row (blockIdx.y); a
+// wave counts its 64 values by ballot and population count in wave-uniform registers; the four waves meet in LDS and the
+// workgroup adds once per counter (every adder of a row lands on one address: the fewer the better).
+__global__ void __launch_bounds__(SB) count_rows_kernel(const float* __restrict__ values, uint64_t stride, uint64_t n, int has_target,
+                                                        float target, unsigned long long* __restrict__ counts) {
+  __shared__ unsigned long long s_n[2];
+  if (threadIdx.x < 2) s_n[threadIdx.x] = 0ull;
+  __syncthreads();
+  const float* __restrict__ row = values + (size_t)blockIdx.y * stride;
+  unsigned long long nr = 0, ns = 0;
+  for (uint64_t base = (uint64_t)blockIdx.x * SB; base < n; base += (uint64_t)gridDim.x * SB) {   // block-uniform trip count
+    const uint64_t i = base + threadIdx.x;
+    const bool live = i < n;
+    const float v = live ? row[i] : 1.0f;
+    nr += (unsigned long long)__popcll(__ballot(live && v == 0.0f));
+    ns += (unsigned long long)__popcll(__ballot(live && has_target && v < target));
+  }
+  if ((threadIdx.x & 63) == 0) {
+    if (nr) atomicAdd(&s_n[0], nr);
+    if (ns) atomicAdd(&s_n[1], ns);
+  }
+  __syncthreads();
+  if (threadIdx.x < 2 && s_n[threadIdx.x]) atomicAdd(&counts[2 * (size_t)blockIdx.y + threadIdx.x], s_n[threadIdx.x]);
+}
+
+hipError_t launch_count_rows(const float* values, uint64_t stride, uint64_t n, int rows, bool has_target, float target,
+                             unsigned long long* counts, hipStream_t s) {
+  if (rows < 1) return hipErrorInvalidValue;
+  uint64_t g = (n + SB - 1) / SB;
+  if (g < 1) g = 1;
+  if (g > 256) g = 256;
+  for (int r0 = 0; r0 < rows; r0 += 65535) {             // gridDim.y holds at most 65535 rows
+    const int nr = rows - r0 < 65535 ? rows - r0 : 65535;
+    count_rows_kernel<<<dim3((unsigned)g, (unsigned)nr), SB, 0, s>>>(values + (size_t)r0 * stride, stride, n, has_target ? 1 : 0, target,
+                                                                    counts + 2 * (size_t)r0);
+  }
+  return hipGetLastError();
+}
+
 hipError_t launch_sum_u64(unsigned long long* const* bufs, int nsrc, size_t words, hipStream_t s) {
   if (nsrc < 1 || nsrc > 8) return hipErrorInvalidValue;
   PtrList l;

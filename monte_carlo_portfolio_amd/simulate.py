@@ -64,15 +64,17 @@ class Context:
             pass
 
     def _call(self, prm: _ffi.McpParams, W, seed: int, path_begin: int, n_paths: int, store: bool, mu=None, chol=None, rows=None,
-              block: float = 1.0, dof=None, period=None, cost: float = 0.0, drawdown: bool = False, horizons=None, levels=()):
-        """The one library call behind every simulate_* method: Student-t draws (dof), rebalancing (period, cost), bootstrap rows
-        (rows, block) or Gaussian draws (mu, chol), with the drawdown or horizons.  Allocates the outputs that were asked for and
-        passes NULL for the rest -> _Outputs, None where not asked for (terminal, qd, horizon_terminal: with `store` only)."""
+              block: float = 1.0, dof=None, period=None, cost: float = 0.0, drawdown: bool = False, horizons=None, levels=(),
+              flows=None, target=None):
+        """The one library call behind every simulate_* method: cash flows (flows, target), Student-t draws (dof), rebalancing
+        (period, cost), bootstrap rows (rows, block) or Gaussian draws (mu, chol), with the drawdown or horizons.  Allocates the
+        outputs that were asked for and passes NULL for the rest -> _Outputs, None where not asked for (terminal, qd,
+        horizon_terminal: with `store` only; counts, hz_counts: with `flows` only)."""
         K = prm.n_portfolios
         ptr = lambda a: a.ctypes.data_as(ctypes.c_void_p) if a is not None else None   # noqa: E731
         stats = np.zeros(K, _ffi.STATS_DTYPE)
         term = np.empty((K, n_paths), np.float32) if store else None
-        dd_stats = raw = hz_stats = bands = hz_term = steps = lv = None
+        dd_stats = raw = hz_stats = bands = hz_term = steps = lv = counts = hz_counts = None
         H = L = 0
         if drawdown:
             dd_stats = np.zeros(K, _ffi.STATS_DTYPE)
@@ -88,7 +90,14 @@ class Context:
         hz_in = (H, ptr(steps) if H else None, L, ptr(lv) if L else None)
         hz_out = (ptr(hz_term), ptr(hz_stats), ptr(bands) if L else None)
         bt = _ffi.make_bootstrap(rows, block) if rows is not None else None
-        if dof is not None:
+        if flows is not None:
+            counts = np.zeros((K, 2), np.uint64)
+            hz_counts = np.zeros((H, K, 2), np.uint64) if horizons is not None else None
+            st = _ffi.McpStudentT(int(dof), 0) if dof is not None else None
+            rc = lib.mcp_simulate_cashflow(self._h, prm_p, ctypes.byref(_ffi.make_cashflow(flows, target)), ptr(mu), ptr(chol),
+                                           ctypes.byref(bt) if bt is not None else None, ctypes.byref(st) if st is not None else None,
+                                           ptr(W), *walk, *hz_in, ptr(term), ptr(stats), ptr(counts), *hz_out, ptr(hz_counts))
+        elif dof is not None:
             rc = lib.mcp_simulate_student_t(self._h, prm_p, ctypes.byref(_ffi.McpStudentT(int(dof), 0)), ptr(mu), ptr(chol), ptr(W), *walk,
                                             *hz_in, ptr(term), ptr(stats), ptr(raw), ptr(dd_stats), *hz_out)
         elif period is not None:
@@ -106,7 +115,7 @@ class Context:
         else:
             rc = lib.mcp_simulate(self._h, prm_p, mu, chol, W, *walk, ptr(term), ptr(stats))
         _ffi.check(rc)
-        return _Outputs(stats, dd_stats, hz_stats, bands, term, raw, hz_term)
+        return _Outputs(stats, dd_stats, hz_stats, bands, term, raw, hz_term, counts, hz_counts)
 
     def simulate(self, prm: _ffi.McpParams, mu, chol, W, seed: int, path_begin: int, n_paths: int, store: bool):
         o = self._call(prm, W, seed, path_begin, n_paths, store, mu=mu, chol=chol)
@@ -158,12 +167,56 @@ class Context:
         [H, K], bands [H, K, L], terminal, qd, horizon_terminal): the entries of the blocks not asked for are None; with `store`,
         terminal is [K, n_paths], qd the binary32 drawdown q [K, n_paths], horizon_terminal [H, K, n_paths]."""
         return tuple(self._call(prm, W, seed, path_begin, n_paths, store, mu=mu, chol=chol, dof=dof, drawdown=drawdown,
-                                horizons=horizons, levels=levels))
+                                horizons=horizons, levels=levels))[:7]
+
+    def simulate_cashflow(self, prm: _ffi.McpParams, flows, W, seed: int, path_begin: int, n_paths: int, store: bool, mu=None,
+                          chol=None, rows=None, block: float = 1.0, dof=None, target=None, horizons=None, levels=()):
+        """simulate() / simulate_horizons() / simulate_bootstrap[_horizons]() / simulate_student_t() with the schedule `flows`
+        (binary32 [n_steps]; positive: paid in, negative: taken out) applied at the end of every step and ruin absorbing (SPEC.md
+        4.7 / 5.6; include/mcport.h, mcp_simulate_cashflow; simple compounding only).  Draws: `mu` and `chol` (Gaussian, or
+        Student-t with `dof`) or `rows` and `block` (bootstrap).  -> _Outputs (stats [K], hz_stats [H, K], bands [H, K, L], terminal,
+        horizon_terminal, counts [K, 2] uint64 {n_ruined, n_short}, hz_counts [H, K, 2]); the horizon entries are None without
+        horizons, n_short is 0 without `target`."""
+        return self._call(prm, W, seed, path_begin, n_paths, store, mu=mu, chol=chol, rows=rows, block=block, dof=dof,
+                          horizons=horizons, levels=levels, flows=np.ascontiguousarray(flows, np.float32), target=target)
 
 
 # What Context._call returns: mcp_stats record arrays (stats [K], dd_stats [K], hz_stats [H, K]), bands [H, K, L] and the stored
-# binary32 arrays (terminal [K, n], qd [K, n], horizon_terminal [H, K, n]).
-_Outputs = collections.namedtuple("_Outputs", "stats dd_stats hz_stats bands terminal qd horizon_terminal")
+# binary32 arrays (terminal [K, n], qd [K, n], horizon_terminal [H, K, n]); with cash flows the counts {n_ruined, n_short} of
+# SPEC.md 5.6 (counts [K, 2], hz_counts [H, K, 2], uint64).
+_Outputs = collections.namedtuple("_Outputs", "stats dd_stats hz_stats bands terminal qd horizon_terminal counts hz_counts",
+                                  defaults=(None, None))
+
+
+def check_cashflow(cashflow, target, n_steps):
+    """SPEC.md 4.7 argument rules -> (flows, target): flows None (no cash flows) or the binary32 [n_steps] schedule -- a number is
+    that amount after every step, a sequence must hold exactly n_steps numbers --, target None or a finite float.  ValueError for
+    a bool, another length, an entry that is not finite (also after rounding to binary32), or a target without cashflow."""
+    def number(v):
+        return isinstance(v, (int, float, np.integer, np.floating)) and not isinstance(v, (bool, np.bool_))
+    if target is not None:
+        if cashflow is None:
+            raise ValueError("target needs cashflow (a goal without flows: cashflow=0)")
+        if not number(target) or not np.isfinite(float(target)):
+            raise ValueError(f"target must be a finite number, got {target!r}")
+        target = float(target)
+    if cashflow is None:
+        return None, None
+    if isinstance(cashflow, (bool, np.bool_)):
+        raise ValueError(f"cashflow must be a number or a sequence of n_steps numbers, got {cashflow!r}")
+    if number(cashflow):
+        vals = np.full(int(n_steps), float(cashflow), np.float64)
+    else:
+        if isinstance(cashflow, (str, bytes)) or any(not number(v) for v in np.asarray(cashflow, object).ravel().tolist()):
+            raise ValueError("cashflow must be a number or a sequence of n_steps numbers (no bools, no strings)")
+        vals = np.asarray(cashflow, np.float64)
+        if vals.ndim != 1 or vals.size != int(n_steps):
+            raise ValueError(f"cashflow must hold exactly n_steps={n_steps} numbers, got shape {vals.shape}")
+    with np.errstate(over="ignore"):
+        flows = np.ascontiguousarray(vals.astype(np.float32))
+    if not np.all(np.isfinite(flows)):
+        raise ValueError("cashflow entries must be finite (in binary32)")
+    return flows, target
 
 
 def check_dof(dof):
@@ -287,7 +340,7 @@ def drawdown_to_dict(rec) -> dict:
 def simulate_paths(mu, cov, weights, n_steps=252, n_paths=10_000, seed=0, v0=1.0, compounding="simple",
                    rf=0.0, alpha=0.95, devices=None, store=False, path_begin=0, chol=None,
                    native_math=False, as_array=False, fold=False, shard="auto", context=None, drawdown=False,
-                   horizons=None, bands=(), rebalance=None, rebalance_cost=0.0, dof=None):
+                   horizons=None, bands=(), rebalance=None, rebalance_cost=0.0, dof=None, cashflow=None, target=None):
     """Simulate `n_paths` correlated return paths and reduce them to risk statistics.
 
     mu [N], cov [N,N] are per-step mean and covariance (the reference's `mean_returns`, `cov_matrix`
@@ -325,7 +378,22 @@ def simulate_paths(mu, cov, weights, n_steps=252, n_paths=10_000, seed=0, v0=1.0
     (common random numbers with the same seed).  The result has the shape of the same call without it, drawdown and horizons
     blocks included (pivots of SPEC.md 5).  fit_student_t_dof(returns) estimates nu from return rows.  Not with fold,
     native_math, rebalance or compounding="log" (ValueError).
+
+    cashflow=None (default): the paths are left alone.  cashflow=c (a number): c is paid in (c > 0) or taken out (c < 0), in the
+    units of v0, at the end of every step; cashflow=[c_1, ..., c_T]: a schedule of exactly n_steps amounts (rounded to binary32).
+    A path whose value is not positive after a flow is ruined: it is stored as 0 and stays there (SPEC.md 4.7).  target=g: also
+    count the paths below g.  Every dict gains 'cashflow' {contributed (the binary64 sum of the flows), n_ruined,
+    ruin_probability} plus n_short, shortfall_probability with a target, and the 'horizons' block n_ruined, ruin_probability [H]
+    (the survival curve; plus the two shortfall arrays with a target).  The statistics are those of x = V_T/v0 - 1, terminal
+    wealth over the INITIAL value: with flows this is not a return on the capital paid in -- form one from 'contributed'.
+    as_array=True returns the tuple of the same call without cash flows with counts [K, 2] uint64 {n_ruined, n_short} (and
+    hz_counts [H, K, 2] with horizons) appended.  Combines with dof and horizons / bands; not with drawdown, rebalance, fold,
+    native_math or compounding="log", and target needs cashflow (ValueError).
     """
+    flows, target = check_cashflow(cashflow, target, n_steps)
+    if flows is not None and (drawdown or rebalance is not None or fold or native_math or compounding == "log"):
+        raise ValueError("cashflow needs simple compounding, the spec's normals, the unfolded recurrence and constant weights: not "
+                         "with drawdown, rebalance, fold, native_math or compounding='log'")
     dof = check_dof(dof)
     if dof is not None and (fold or native_math or compounding == "log" or rebalance is not None):
         raise ValueError("dof needs simple compounding, the spec's normals, the unfolded recurrence and constant weights: not with "
@@ -341,8 +409,8 @@ def simulate_paths(mu, cov, weights, n_steps=252, n_paths=10_000, seed=0, v0=1.0
     mu32, L, W = prepare_inputs(mu, cov, weights, chol)
     prm, ctx = _setup(mu32.shape[0], n_steps, W.shape[0], compounding, v0, alpha, rf, native_math, fold, devices, shard, context)
     out = ctx._call(prm, W, int(seed), int(path_begin), int(n_paths), store, mu=mu32, chol=L, dof=dof, period=period, cost=cost,
-                    drawdown=drawdown, horizons=steps, levels=levels)
-    return _result(out, np.asarray(weights).ndim == 1, store, as_array, steps, levels, compounding)
+                    drawdown=drawdown, horizons=steps, levels=levels, flows=flows, target=target)
+    return _result(out, np.asarray(weights).ndim == 1, store, as_array, steps, levels, compounding, flows, target)
 
 
 def _check_walk(n_steps, horizons, bands, period, compounding, shard):
@@ -369,17 +437,33 @@ def _setup(n_assets, n_steps, K, compounding, v0, alpha, rf, native_math, fold, 
     return prm, context if context is not None else default_context(devs)
 
 
-def _result(out, single, store, as_array, steps, levels, compounding):
+def _cash_block(counts, n, target, contributed=None):
+    """The counts {n_ruined, n_short} [..., 2] of SPEC.md 5.6 over n paths as the fields of a result dict."""
+    c = np.asarray(counts)
+    scalar = c.ndim == 1
+    cast = (lambda a: int(a)) if scalar else (lambda a: a.astype(np.int64))            # noqa: E731
+    prob = (lambda a: float(a) / n) if scalar else (lambda a: a.astype(np.float64) / n)   # noqa: E731
+    d = {} if contributed is None else {"contributed": contributed}
+    d.update(n_ruined=cast(c[..., 0]), ruin_probability=prob(c[..., 0]))
+    if target is not None:
+        d.update(n_short=cast(c[..., 1]), shortfall_probability=prob(c[..., 1]))
+    return d
+
+
+def _result(out, single, store, as_array, steps, levels, compounding, flows=None, target=None):
     """What simulate_paths / simulate_bootstrap return for Context._call's outputs `out`: with as_array the record arrays (stats,
     then (hz_stats, bands) or dd_stats, then with `store` terminal and horizon_terminal or max_drawdown); else one dict per
     portfolio (one dict for a single weight vector) with its 'drawdown' / 'horizons' blocks and, with `store`, the stored arrays."""
-    stats, dd_stats, hz_stats, hz_bands, term, qd, hz_term = out
+    stats, dd_stats, hz_stats, hz_bands, term, qd, hz_term, counts, hz_counts = out
     mdd = mdd_from_raw(qd, compounding) if dd_stats is not None and store else None
     if as_array:                          # [K] structured arrays (fields of mcp_stats), for large sweeps
+        cash = () if counts is None else (counts,) if hz_counts is None else (counts, hz_counts)
         if hz_stats is not None:
-            return (stats, hz_stats, hz_bands, term, hz_term) if store else (stats, hz_stats, hz_bands)
+            return ((stats, hz_stats, hz_bands, term, hz_term) if store else (stats, hz_stats, hz_bands)) + cash
         if dd_stats is not None:
             return (stats, dd_stats, term, mdd) if store else (stats, dd_stats)
+        if cash:
+            return ((stats, term) if store else (stats,)) + cash
         return (stats, term) if store else stats
     res = [stats_to_dict(stats[k]) for k in range(stats.shape[0])]
     for k, d in enumerate(res):
@@ -389,6 +473,10 @@ def _result(out, single, store, as_array, steps, levels, compounding):
             d["horizons"] = dict({"steps": steps.astype(np.int64), "levels": levels.copy(), "bands": hz_bands[:, k, :]},
                                  **{f: hz_stats[f][:, k].astype(np.int64 if f == "n_tail" else np.float64)
                                     for f in ("mean", "std", "var", "cvar", "min", "max", "n_tail")})
+            if hz_counts is not None:
+                d["horizons"].update(_cash_block(hz_counts[:, k, :], int(stats[k]["n"]), target))
+        if counts is not None:            # SPEC.md 5.6; contributed: the binary64 sum of the binary32 flows
+            d["cashflow"] = _cash_block(counts[k], int(stats[k]["n"]), target, float(np.sum(flows.astype(np.float64))))
         if store:
             d["terminal"] = term[k]
             if dd_stats is not None:
@@ -424,7 +512,7 @@ def bootstrap_inputs(returns, weights):
 
 def simulate_bootstrap(returns, weights, n_steps=252, n_paths=10_000, block=1.0, seed=0, v0=1.0, compounding="simple",
                        rf=0.0, alpha=0.95, devices=None, store=False, path_begin=0, as_array=False, shard="auto", context=None,
-                       horizons=None, bands=(), rebalance=None, rebalance_cost=0.0, **unsupported):
+                       horizons=None, bands=(), rebalance=None, rebalance_cost=0.0, cashflow=None, target=None, **unsupported):
     """simulate_paths on paths resampled from the observed return rows instead of a normal model: the stationary block
     bootstrap of Politis & Romano (SPEC.md 2.1 / 4.4).  Every step of a path uses one whole row of `returns` (all assets of one
     date together), so fat tails, skew, the co-movement within a row and -- with a mean block length `block` > 1 -- short-range
@@ -435,12 +523,16 @@ def simulate_bootstrap(returns, weights, n_steps=252, n_paths=10_000, block=1.0,
     or [K, N].  Returns exactly what simulate_paths returns for the same arguments, 'horizons' block included (pivots of
     SPEC.md 5.3).  ValueError for NaN rows, a width that does not match the weights, block < 1, or the simulate_paths keywords
     that have no meaning here (fold, native_math, drawdown, chol).  rebalance / rebalance_cost as in simulate_paths (SPEC.md 4.5,
-    pivots of SPEC.md 5.4; not with compounding="log").
+    pivots of SPEC.md 5.4; not with compounding="log").  cashflow / target as in simulate_paths (SPEC.md 4.7, pivots of SPEC.md
+    5.6; not with rebalance or compounding="log").
     """
     if unsupported:
         raise ValueError(f"simulate_bootstrap does not take {sorted(unsupported)} (no normals: no fold / native_math / dof -- "
                          "Student-t draws are a parametric model, call simulate_paths(dof=...); drawdown on bootstrap paths is "
                          "not supported)")
+    flows, target = check_cashflow(cashflow, target, n_steps)
+    if flows is not None and (rebalance is not None or compounding == "log"):
+        raise ValueError("cashflow needs simple compounding and constant weights: not with rebalance or compounding='log'")
     period, cost = check_rebalance(rebalance, rebalance_cost)
     b = float(block)
     if not b >= 1.0:
@@ -449,8 +541,8 @@ def simulate_bootstrap(returns, weights, n_steps=252, n_paths=10_000, block=1.0,
     rows, W = bootstrap_inputs(returns, weights)
     prm, ctx = _setup(rows.shape[1], n_steps, W.shape[0], compounding, v0, alpha, rf, False, False, devices, shard, context)
     out = ctx._call(prm, W, int(seed), int(path_begin), int(n_paths), store, rows=rows, block=b, period=period, cost=cost,
-                    horizons=steps, levels=levels)
-    return _result(out, np.asarray(weights).ndim == 1, store, as_array, steps, levels, compounding)
+                    horizons=steps, levels=levels, flows=flows, target=target)
+    return _result(out, np.asarray(weights).ndim == 1, store, as_array, steps, levels, compounding, flows, target)
 
 
 def simulate_sweep(mu, cov, weights=None, n_portfolios=2500, min_weights=None, max_weights=None, n_steps=252,
@@ -468,6 +560,8 @@ def simulate_sweep(mu, cov, weights=None, n_portfolios=2500, min_weights=None, m
     W = np.atleast_2d(np.asarray(weights, np.float64))
     if kw.get("horizons") is not None or len(np.atleast_1d(np.asarray(kw.get("bands", ()), np.float64))):
         raise ValueError("simulate_sweep does not take horizons or bands: call simulate_paths for the optimum")
+    if kw.get("cashflow") is not None or kw.get("target") is not None:
+        raise ValueError("simulate_sweep does not take cashflow or target: call simulate_paths for the optimum")
     drawdown = bool(kw.get("drawdown", False))
     stats = simulate_paths(mu, cov, W, n_steps=n_steps, n_paths=n_paths, seed=seed, rf=rf, alpha=alpha, as_array=True, **kw)
     dd_stats = None
