@@ -66,6 +66,16 @@ with tab_options:                                             # app.py:499-653
         grid = options.payoff_grid(spot)
         st.line_chart({"price": grid, "P/L": mcp.calculate_payoff(rows, spot, spot, grid)})
         st.write({"breakeven": mcp.calculate_breakeven(rows, spot)})
+        # next to the payoff curve: the asset alone on simulated one-year paths, unhedged and held through the strategy inside
+        # the path kernel (SPEC.md 4.8; the premiums, fractions of the price above, in price units here)
+        r1 = mcp.returns_matrix(resampled, {})[asset]
+        held = [(t, k, p * spot, q) for t, k, p, q in rows]
+        hedge = {}
+        for side, kw in (("unhedged", {}), ("hedged", {"overlay": {0: held}, "spot": [spot]})):
+            o = mcp.simulate_paths([r1.mean()], [[r1.var()]], [1.0], n_steps=annual_factor, n_paths=n_paths, seed=12345, alpha=0.95,
+                                   drawdown=True, **kw)
+            hedge[side] = {"VaR 5%": o["var"], "CVaR 5%": o["cvar"], "mean max drawdown": o["drawdown"]["mean"]}
+        st.write({"simulated hedge": hedge})
 
 with tab_sweep:                                               # app.py:655-783
     returns_df = mcp.returns_matrix(resampled, option_rows)

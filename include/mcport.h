@@ -27,12 +27,14 @@ extern "C" {
                                     mcp_launch_paths_horizons, mcp_percentile_rank_q (additive, detected by symbol);
                                     + mcp_simulate_bootstrap[_horizons], mcp_bootstrap_pivots (additive, detected by symbol);
                                     + mcp_simulate_rebalanced, mcp_rebalance_pivots (additive, detected by symbol);
-                                    + mcp_simulate_student_t (additive, detected by symbol) */
+                                    + mcp_simulate_student_t (additive, detected by symbol);
+                                    + mcp_simulate_overlay, mcp_overlay_pivots (additive, detected by symbol) */
 #define MCP_MAX_ASSETS 64        /* thread-per-path kernels are instantiated for N4 = 4..64 */
 #define MCP_SELECT_BINS 2048     /* radix-select digit: 11 + 11 + 10 bits */
 #define MCP_MAX_HORIZONS 64      /* mcp_simulate_horizons: horizon steps per call */
 #define MCP_MAX_LEVELS 16        /* mcp_simulate_horizons: band levels per call */
 #define MCP_MAX_BOOT_ROWS (1 << 20) /* mcp_simulate_bootstrap: observed return rows per call */
+#define MCP_MAX_OVERLAY_ROWS 8   /* mcp_simulate_overlay: option rows per asset */
 #define MCP_MAX_T_DOF 32         /* mcp_simulate_student_t: degrees of freedom in [3, MCP_MAX_T_DOF] */
 
 enum {
@@ -327,6 +329,53 @@ int mcp_simulate_cashflow(mcp_ctx *ctx, const mcp_params *prm, const mcp_cashflo
  * exact mean of x while no path is ruined. */
 int mcp_cashflow_pivots(const mcp_params *prm, const mcp_cashflow *cf, const float *mu, const mcp_bootstrap *boot,
                         const float *W, double *pivots_out /* [K] */);
+
+/* Option and hedging overlays (SPEC.md 4.8 / 5.7).  Asset i owns the rows [row_begin[i], row_begin[i+1]) of `rows`, applied in that
+ * order; kind LINEAR: leg = price - prev, CALL: leg = max(price - strike, 0) - premium, PUT: leg = max(strike - price, 0) -
+ * premium (strike and premium in price units, the sign of a short row folded into qty).  spot: the assets' current prices, > 0 on
+ * every asset that owns rows; reserved must be 0.  n_rows = 0: every asset passes through. */
+#define MCP_OVERLAY_LINEAR 0
+#define MCP_OVERLAY_CALL 1
+#define MCP_OVERLAY_PUT 2
+typedef struct {
+    int32_t kind;
+    float strike, premium, qty;
+} mcp_overlay_row;
+typedef struct {
+    const mcp_overlay_row *rows;   /* [n_rows], NULL when n_rows == 0 */
+    const int32_t *row_begin;      /* [n_assets + 1], ascending from 0 to n_rows */
+    const float *spot;             /* [n_assets] */
+    int32_t n_rows;
+    int32_t reserved;
+} mcp_overlay;
+
+/* mcp_simulate / mcp_simulate_drawdown / mcp_simulate_horizons / mcp_simulate_student_t with the overlay applied inside the walk
+ * (simple compounding only): the kernel carries the price P_i of every asset that owns rows (from fl32(spot_i), price = fma(P_i,
+ * r_i, P_i) with the RAW return r_i of the step) and replaces r_i by r'_i = sum_rows qty * leg / P_i (one fma per row from +0, one
+ * IEEE division; +0 where P_i == 0) before rho_k = sum_i W[k,i] r'_i.  st NULL: Gaussian draws; st: Student-t draws (SPEC.md
+ * 2.2).  dd_stats_out non-NULL: the drawdown of mcp_simulate_drawdown; n_horizons > 0: the horizons, records and bands of
+ * mcp_simulate_horizons (n_horizons = 0: horizons ignored, n_levels = 0, horizon_out, hz_stats_out, bands_out NULL); not both
+ * (MCP_E_UNSUPPORTED).  The moments are pivoted at SPEC.md 5.7 (mcp_overlay_pivots).  Argument errors (MCP_E_ARG: a NULL struct,
+ * row_begin not ascending from 0 to n_rows, more than MCP_MAX_OVERLAY_ROWS rows on an asset, a kind outside 0..2, a strike,
+ * premium, qty or spot that is not finite, spot <= 0 on an asset with rows, reserved != 0) are found before any device is touched;
+ * log compounding, MCP_FLAG_FOLD, MCP_FLAG_NATIVE_MATH: MCP_E_UNSUPPORTED.  K >= 17 runs as passes of 8 portfolios. */
+int mcp_simulate_overlay(mcp_ctx *ctx, const mcp_params *prm, const mcp_overlay *ov,
+                         const float *mu, const float *chol,
+                         const mcp_student_t *st,            /* NULL: Gaussian draws */
+                         const float *W, uint64_t seed, uint64_t path_begin, uint64_t n_paths,
+                         int n_horizons, const int32_t *horizons, int n_levels, const double *levels,
+                         float *terminal_out,        /* NULL or host [K*n_paths] */
+                         mcp_stats *stats_out,       /* [K] */
+                         float *mdd_out,             /* NULL or host [K*n_paths]; needs dd_stats_out */
+                         mcp_stats *dd_stats_out,    /* [K], or NULL: no drawdown */
+                         float *horizon_out,         /* NULL or host [H*K*n_paths], row h*K + k */
+                         mcp_stats *hz_stats_out,    /* [H*K], NULL iff n_horizons == 0 */
+                         double *bands_out);         /* [H*K*L], NULL iff n_levels == 0 */
+/* The shift of the moments of overlaid paths at prm->n_steps (SPEC.md 5.7; host side, binary64 from the binary32 inputs): the
+ * rule of SPEC.md 4.8 on the deterministic prices P_i,t = P_i,t-1 (1 + mu_i) from P_i,0 = spot_i, rho_k,t = sum_i W[k,i] r'_i,t
+ * (i ascending), A_k,t = A_k,t-1 (1 + rho_k,t) from 1:  c_k = A_k,T - 1, 0 where it is not finite.  n_rows = 0: mcp_pivots. */
+int mcp_overlay_pivots(const mcp_params *prm, const mcp_overlay *ov, const float *mu, const float *W,
+                       double *pivots_out /* [K] */);
 
 /* The reference's own sweep (app.py:699-717) over HISTORICAL returns, loop body app.py:708-713 for P weight
  * vectors at once, binary64 like the reference.  returns: [R*N] row-major (returns_df.values, app.py:667),

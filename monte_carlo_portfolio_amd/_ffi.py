@@ -24,6 +24,8 @@ MCP_MAX_HORIZONS = 64
 MCP_MAX_LEVELS = 16
 MCP_MAX_BOOT_ROWS = 1 << 20
 MCP_MAX_T_DOF = 32
+MCP_MAX_OVERLAY_ROWS = 8
+MCP_OVERLAY_LINEAR, MCP_OVERLAY_CALL, MCP_OVERLAY_PUT = 0, 1, 2
 MCP_COMPOUND = {"simple": 0, "log": 1}
 MCP_FLAG_NATIVE_MATH = 1
 MCP_FLAG_FOLD = 2
@@ -74,6 +76,16 @@ class McpCashflow(ctypes.Structure):
     """mcp_cashflow: the schedule c_1 .. c_T (binary32, n_flows == n_steps) and the optional target of SPEC.md 4.7 / 5.6."""
     _fields_ = [("flows", ctypes.c_void_p), ("n_flows", ctypes.c_int32), ("has_target", ctypes.c_int32), ("target", ctypes.c_double)]
 
+
+class McpOverlay(ctypes.Structure):
+    """mcp_overlay: the option rows of SPEC.md 4.8 -- rows [n_rows] of OVERLAY_ROW_DTYPE, row_begin int32 [N + 1], spot binary32 [N]."""
+    _fields_ = [("rows", ctypes.c_void_p), ("row_begin", ctypes.c_void_p), ("spot", ctypes.c_void_p), ("n_rows", ctypes.c_int32),
+                ("reserved", ctypes.c_int32)]
+
+
+# one mcp_overlay_row: kind 0 LINEAR, 1 CALL, 2 PUT; the sign of a short row is folded into qty
+OVERLAY_ROW_DTYPE = np.dtype([("kind", np.int32), ("strike", np.float32), ("premium", np.float32), ("qty", np.float32)])
+assert OVERLAY_ROW_DTYPE.itemsize == 16
 
 STATS_DTYPE = np.dtype([
     ("n", np.uint64), ("n_tail", np.uint64), ("mean", np.float64), ("m2", np.float64), ("std", np.float64),
@@ -137,6 +149,9 @@ SIGNATURES = {
                                      ctypes.POINTER(McpStudentT), _vp, _u64, _u64, _u64, _int, _vp, _int, _vp, _vp, _vp, _vp, _vp, _vp,
                                      _vp, _vp]),
     "mcp_cashflow_pivots": (_int, [_PP, ctypes.POINTER(McpCashflow), _vp, ctypes.POINTER(McpBootstrap), _f32p, _f64p]),
+    "mcp_simulate_overlay": (_int, [_vp, _PP, ctypes.POINTER(McpOverlay), _vp, _vp, ctypes.POINTER(McpStudentT), _vp, _u64, _u64, _u64,
+                                    _int, _vp, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "mcp_overlay_pivots": (_int, [_PP, ctypes.POINTER(McpOverlay), _f32p, _f32p, _f64p]),
     "mcp_percentile_rank_q": (_int, [_u64, ctypes.c_double, ctypes.POINTER(_u64), ctypes.POINTER(_u64),
                                      ctypes.POINTER(ctypes.c_double)]),
     "mcp_percentile_rank": (_int, [_u64, ctypes.c_double, ctypes.POINTER(_u64), ctypes.POINTER(_u64),
@@ -306,6 +321,26 @@ def cashflow_pivots(prm: McpParams, flows: np.ndarray, W: np.ndarray, mu: np.nda
     bt = make_bootstrap(np.ascontiguousarray(rows, np.float32), 1.0) if rows is not None else None
     check(lib().mcp_cashflow_pivots(ctypes.byref(prm), ctypes.byref(cf), mu_p.ctypes.data_as(_vp) if mu_p is not None else None,
                                     ctypes.byref(bt) if bt is not None else None, W, out))
+    return out
+
+
+def make_overlay(rows: np.ndarray, row_begin: np.ndarray, spot: np.ndarray) -> McpOverlay:
+    """mcp_overlay over C-contiguous arrays (rows of OVERLAY_ROW_DTYPE, row_begin int32 [N + 1], spot float32 [N]; the caller keeps
+    them alive for the call)."""
+    if rows.dtype != OVERLAY_ROW_DTYPE or rows.ndim != 1 or not rows.flags.c_contiguous:
+        raise ValueError("overlay rows must be a C-contiguous [n_rows] array of OVERLAY_ROW_DTYPE")
+    if row_begin.dtype != np.int32 or spot.dtype != np.float32 or row_begin.ndim != 1 or spot.ndim != 1 or row_begin.size != spot.size + 1:
+        raise ValueError("overlay row_begin must be int32 [N + 1] and spot float32 [N]")
+    return McpOverlay(rows.ctypes.data_as(ctypes.c_void_p) if rows.size else None, row_begin.ctypes.data_as(ctypes.c_void_p),
+                      spot.ctypes.data_as(ctypes.c_void_p), int(rows.size), 0)
+
+
+def overlay_pivots(prm: McpParams, overlay, mu: np.ndarray, W: np.ndarray) -> np.ndarray:
+    """[K] shifts of the moments of overlaid paths (SPEC.md 5.7; include/mcport.h, mcp_overlay_pivots), pure host arithmetic:
+    `overlay` is the (rows, row_begin, spot) triple of simulate.check_overlay."""
+    out = np.zeros(W.shape[0], np.float64)
+    ov = make_overlay(*overlay)
+    check(lib().mcp_overlay_pivots(ctypes.byref(prm), ctypes.byref(ov), np.ascontiguousarray(mu, np.float32), W, out))
     return out
 
 

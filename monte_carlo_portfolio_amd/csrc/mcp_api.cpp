@@ -212,6 +212,94 @@ int check_cashflow(const mcp_params* prm, const mcp_cashflow* cf) {
   return MCP_OK;
 }
 
+// SPEC.md 4.8: row_begin ascending from 0 to n_rows, at most MCP_MAX_OVERLAY_ROWS rows per asset, kinds 0..2, finite numbers, a
+// positive spot on every asset that owns rows, reserved == 0
+int check_overlay(const mcp_params* prm, const mcp_overlay* ov) {
+  if (!ov) return fail(MCP_E_ARG, "overlay is NULL");
+  if (ov->reserved != 0) return fail(MCP_E_ARG, "overlay reserved=%d must be 0", ov->reserved);
+  const int N = prm->n_assets;
+  if (ov->n_rows < 0 || ov->n_rows > N * MCP_MAX_OVERLAY_ROWS)
+    return fail(MCP_E_ARG, "overlay n_rows=%d outside [0,%d]", ov->n_rows, N * MCP_MAX_OVERLAY_ROWS);
+  if (!ov->row_begin || !ov->spot || (ov->n_rows > 0 && !ov->rows)) return fail(MCP_E_ARG, "overlay rows, row_begin or spot is NULL");
+  if (ov->row_begin[0] != 0 || ov->row_begin[N] != ov->n_rows)
+    return fail(MCP_E_ARG, "overlay row_begin must run from 0 to n_rows=%d (got %d .. %d)", ov->n_rows, ov->row_begin[0], ov->row_begin[N]);
+  for (int i = 0; i < N; i++) {
+    const int cnt = ov->row_begin[i + 1] - ov->row_begin[i];
+    if (cnt < 0) return fail(MCP_E_ARG, "overlay row_begin is not ascending at asset %d", i);
+    if (cnt > MCP_MAX_OVERLAY_ROWS) return fail(MCP_E_ARG, "asset %d owns %d overlay rows, at most %d", i, cnt, MCP_MAX_OVERLAY_ROWS);
+    if (!std::isfinite(ov->spot[i])) return fail(MCP_E_ARG, "spot of asset %d is not finite", i);
+    if (cnt > 0 && !(ov->spot[i] > 0.0f)) return fail(MCP_E_ARG, "spot of asset %d = %g must be positive (it owns overlay rows)", i, ov->spot[i]);
+  }
+  for (int j = 0; j < ov->n_rows; j++) {
+    const mcp_overlay_row& r = ov->rows[j];
+    if (r.kind < MCP_OVERLAY_LINEAR || r.kind > MCP_OVERLAY_PUT) return fail(MCP_E_ARG, "overlay row %d: kind=%d outside 0..2", j, r.kind);
+    if (!std::isfinite(r.strike) || !std::isfinite(r.premium) || !std::isfinite(r.qty))
+      return fail(MCP_E_ARG, "overlay row %d: strike, premium or qty is not finite", j);
+  }
+  return MCP_OK;
+}
+
+// SPEC.md 5.7: the rule of SPEC.md 4.8 in binary64 on the deterministic prices P_i,t = P_i,t-1 (1 + mu_i) from spot_i; the return of
+// an asset without rows is mu_i.  rho_k,t = sum_i W[k,i] r'_i,t (i ascending), A_k,t = A_k,t-1 (1 + rho_k,t) from 1; the pivot
+// A - 1 (0 where not finite) after step T into out_T[k] and after the steps of the H horizons into out_hz[h*K + k].
+void overlay_pivots(int N, int K, int T, const mcp_overlay* ov, const float* mu, const float* W, int H, const int32_t* steps,
+                    double* out_T, double* out_hz) {
+  const auto pivot = [](double A) {
+    const double c = A - 1.0;
+    return std::isfinite(c) ? c : 0.0;
+  };
+  std::vector<double> P((size_t)N), g((size_t)N), r((size_t)N), A((size_t)K, 1.0);
+  for (int i = 0; i < N; i++) {
+    P[(size_t)i] = (double)ov->spot[i];
+    r[(size_t)i] = (double)(mu[i] + 0.0f);
+    g[(size_t)i] = 1.0 + r[(size_t)i];
+  }
+  int hi = 0;
+  for (int t = 1; t <= T; t++) {
+    for (int i = 0; i < N; i++) {
+      const int rb = ov->row_begin[i], re = ov->row_begin[i + 1];
+      if (rb == re) continue;
+      const double prev = P[(size_t)i], price = prev * g[(size_t)i];
+      double num = 0.0;
+      for (int j = rb; j < re; j++) {
+        const mcp_overlay_row& row = ov->rows[j];
+        double leg;
+        if (row.kind == MCP_OVERLAY_LINEAR) {
+          leg = price - prev;
+        } else {
+          const double d = row.kind == MCP_OVERLAY_CALL ? price - (double)row.strike : (double)row.strike - price;
+          leg = (d > 0.0 ? d : 0.0) - (double)row.premium;
+        }
+        num = num + (double)row.qty * leg;
+      }
+      r[(size_t)i] = prev != 0.0 ? num / prev : 0.0;
+      P[(size_t)i] = price;
+    }
+    for (int k = 0; k < K; k++) {
+      const float* w = W + (size_t)k * N;
+      double rho = 0.0;
+      for (int i = 0; i < N; i++) rho += (double)w[i] * r[(size_t)i];
+      A[(size_t)k] = A[(size_t)k] * (1.0 + rho);
+    }
+    if (hi < H && steps[hi] == t) {
+      for (int k = 0; k < K; k++) out_hz[(size_t)hi * K + k] = pivot(A[(size_t)k]);
+      hi++;
+    }
+  }
+  for (int k = 0; k < K; k++) out_T[k] = pivot(A[(size_t)k]);
+}
+
+// SPEC.md 4.8: the device copy of an overlay -- [rows n_rows][row_begin N4 + 1][spot N4]; the assets >= N own no rows
+size_t overlay_bytes(int N, int n_rows) { return (size_t)n_rows * sizeof(mcp_overlay_row) + (size_t)(2 * n4_of(N) + 1) * 4; }
+void overlay_pack(int N, const mcp_overlay* ov, char* out) {
+  const int n4 = n4_of(N);
+  if (ov->n_rows) memcpy(out, ov->rows, (size_t)ov->n_rows * sizeof(mcp_overlay_row));
+  int32_t* rb = (int32_t*)(out + (size_t)ov->n_rows * sizeof(mcp_overlay_row));
+  float* sp = (float*)(rb + n4 + 1);
+  for (int i = 0; i <= n4; i++) rb[i] = i <= N ? ov->row_begin[i] : ov->n_rows;
+  for (int i = 0; i < n4; i++) sp[i] = i < N ? ov->spot[i] : 1.0f;
+}
+
 // The draws of a walk (SPEC.md 2): Gaussian steps mu + L z, rows of the bootstrap, or Student-t steps mu + L s z.
 enum Source { SRC_GAUSS, SRC_BOOT, SRC_T };
 
@@ -227,6 +315,8 @@ struct Request {
   const mcp_rebalance* reb = nullptr;
   bool cash = false;                    // SPEC.md 4.7: the schedule `cf`
   const mcp_cashflow* cf = nullptr;
+  bool overlay = false;                 // SPEC.md 4.8: the option rows `ov`
+  const mcp_overlay* ov = nullptr;
   bool dd = false;                      // SPEC.md 4.2 / 5.1: the drawdown of every path
   bool hz = false;                      // SPEC.md 4.3 / 5.2: the values after H steps, statistics at alpha and at L levels
   int H = 0, L = 0;
@@ -280,6 +370,8 @@ struct Launch {
   uint64_t hz_stride = 0;
   const float* d_rows = nullptr;        // bootstrap: [R][N4], zero-padded
   const float* d_flows = nullptr;       // cash flows: [n_steps]
+  const char* d_overlay = nullptr;      // overlay: [rows][row_begin N4 + 1][spot N4] (overlay_pack)
+  int ov_n = 0, ov_n4 = 0;              // overlay: N and N4 of that table
   void* d_partials = nullptr;
   void* d_hist = nullptr;
   hipStream_t stream = nullptr;
@@ -303,13 +395,18 @@ int check_request(const mcp_params* prm, const Request& rq, uint64_t n_paths, co
     if (!rq.counts_out) return fail(MCP_E_ARG, "counts_out is NULL");
     if ((rq.hz_counts_out == nullptr) != !rq.hz) return fail(MCP_E_ARG, "hz_counts_out must be NULL exactly when n_horizons == 0");
   }
+  if (rq.overlay && (rc = check_overlay(prm, rq.ov))) return rc;
   const bool logc = prm->compounding != MCP_COMPOUND_SIMPLE;
+  if (rq.overlay && logc) return fail(MCP_E_UNSUPPORTED, "overlaid paths compound simply (no log compounding)");
+  if (rq.overlay && (rq.src == SRC_BOOT || rq.rebalanced || rq.cash))
+    return fail(MCP_E_UNSUPPORTED, "the overlay is not combined with bootstrap rows, rebalancing or cash flows");
   if (rq.rebalanced && logc) return fail(MCP_E_UNSUPPORTED, "rebalanced paths compound simply (no log compounding)");
   if (rq.cash && logc) return fail(MCP_E_UNSUPPORTED, "paths with cash flows compound simply (no log compounding)");
   if (rq.src == SRC_T && logc)
     return fail(MCP_E_UNSUPPORTED, "Student-t paths compound simply (log compounding: expm1(S) has no finite mean under t steps)");
   if (prm->flags & (MCP_FLAG_FOLD | MCP_FLAG_NATIVE_MATH)) {   // the fast steps exist for plain Gaussian walks only
-    const char* who = rq.cash              ? "paths with cash flows run on the unfolded recurrence and the spec's normals"
+    const char* who = rq.overlay           ? "overlaid paths run on the unfolded recurrence and the spec's normals"
+                      : rq.cash            ? "paths with cash flows run on the unfolded recurrence and the spec's normals"
                       : rq.rebalanced      ? "rebalanced paths run on the unfolded recurrence and the spec's normals"
                       : rq.src == SRC_T    ? "Student-t paths run on the spec's normals and the unfolded recurrence"
                       : rq.src == SRC_BOOT ? "bootstrap paths draw no normals"
@@ -513,6 +610,7 @@ struct Shard {
     HostBuf<mcp_stats> stats;              // [1 + L][H][K tile] records of the alpha select and of every level's select, mapped
   } hz;
   DevBuf<float> boot;                      // bootstrap calls: [R][N4] observed rows, zero-padded (SPEC.md 2.1)
+  DevBuf<char> overlay;                    // overlay calls: the table of overlay_pack (SPEC.md 4.8)
   struct {                                 // cash-flow calls (SPEC.md 4.7 / 5.6)
     DevBuf<float> flows;                   // [n_steps] the schedule
     DevBuf<unsigned long long> counts;     // [(1 + H) K tile][2] {n_ruined, n_short}: the terminal rows, then the horizon rows
@@ -618,6 +716,8 @@ struct mcp_ctx {
   size_t h_boot_cap = 0;
   float* h_flows = nullptr;          // cash-flow calls: pinned, portable [n_steps] schedule, uploaded to every shard's flows buffer
   size_t h_flows_cap = 0;
+  char* h_overlay = nullptr;         // overlay calls: pinned, portable table of overlay_pack, uploaded to every shard's overlay buffer
+  size_t h_overlay_cap = 0;
 };
 
 
@@ -778,6 +878,20 @@ static void fill(mcp::PathArgsCF& x, const Request& rq, const Launch& ln) {
   x.st.pad = 0;
   x.cf.flows = ln.d_flows;
 }
+static void fill(mcp::PathArgsOV& x, const Request& rq, const Launch& ln) {
+  fill_hz(x, rq, ln);
+  x.mdd = rq.dd ? ln.d_mdd : nullptr;
+  x.mdd_stride = rq.dd ? ln.mdd_stride : 0;
+  x.st.dof = rq.src == SRC_T ? rq.st->dof : 0;
+  x.st.pad = 0;
+  const size_t row_bytes = (size_t)rq.ov->n_rows * sizeof(mcp_overlay_row);
+  x.ov.rows = (const mcp_overlay_row*)ln.d_overlay;
+  x.ov.row_begin = (const int32_t*)(ln.d_overlay + row_bytes);
+  x.ov.spot = (const float*)(ln.d_overlay + row_bytes) + ln.ov_n4 + 1;
+  x.ov.mask = 0;
+  for (int i = 0; i < ln.ov_n; i++)                            // the padding assets >= N own no rows
+    if (rq.ov->row_begin[i + 1] > rq.ov->row_begin[i]) x.ov.mask |= (uint64_t)1 << i;
+}
 static void fill(mcp::PathArgsRB& x, const Request& rq, const Launch& ln) {
   fill_hz(x, rq, ln);
   x.bt = boot_block(rq, ln);
@@ -808,7 +922,7 @@ static int launch_passes(const mcp::PathArgs& a, const Request& rq, const Launch
 static int launch_paths_impl(const mcp_params* prm, const Request& rq, const Launch& ln) {
   const int nb = (prm->n_assets + 3) / 4;
   const int K = prm->n_portfolios;
-  const bool plain = rq.src == SRC_GAUSS && !rq.dd && !rq.hz && !rq.rebalanced && !rq.cash;
+  const bool plain = rq.src == SRC_GAUSS && !rq.dd && !rq.hz && !rq.rebalanced && !rq.cash && !rq.overlay;
   int variant = 0;
   if (prm->flags & MCP_FLAG_FOLD) variant |= mcp::VAR_FOLD;
   if (K > 1) variant |= mcp::VAR_KT8;
@@ -864,12 +978,14 @@ static int launch_paths_impl(const mcp_params* prm, const Request& rq, const Lau
     HIP_TRY(mcp::launch_pass0(*prm, K, ln.d_terminal, ln.stride, 0, nullptr, a.slots, (mcp::MomentPartial*)ln.d_partials,
                               (unsigned long long*)ln.d_hist, ln.stream));
   mcp::PathKernel k;
-  k.family = rq.cash ? mcp::FAM_CF : rq.rebalanced ? mcp::FAM_REB : rq.dd ? mcp::FAM_DD : rq.hz ? mcp::FAM_HZ : mcp::FAM_PLAIN;
+  k.family = rq.overlay ? mcp::FAM_OV : rq.cash ? mcp::FAM_CF : rq.rebalanced ? mcp::FAM_REB : rq.dd ? mcp::FAM_DD : rq.hz ? mcp::FAM_HZ : mcp::FAM_PLAIN;
   k.logc = prm->compounding == MCP_COMPOUND_LOG;
   k.boot = rq.src == SRC_BOOT;
   k.blds = k.boot && mcp::boot_fits_lds((uint64_t)rq.boot->n_rows, nb);
   k.stt = rq.src == SRC_T;
+  k.dd = rq.overlay && rq.dd;
   switch (k.family) {
+    case mcp::FAM_OV: return launch_passes<mcp::PathArgsOV>(a, rq, ln, variant, k, nb);
     case mcp::FAM_CF: return launch_passes<mcp::PathArgsCF>(a, rq, ln, variant, k, nb);
     case mcp::FAM_REB: return launch_passes<mcp::PathArgsRB>(a, rq, ln, variant, k, nb);
     case mcp::FAM_DD: return k.stt ? launch_passes<mcp::PathArgsTDD>(a, rq, ln, variant, k, nb)
@@ -1108,6 +1224,7 @@ static void free_shard(Shard& sh) {
   release(sh.hz.stats);
   release(sh.boot);
   release(sh.cf.flows);
+  release(sh.overlay);
   release(sh.cf.counts);
   release(sh.cf.h_counts);
 }
@@ -1220,6 +1337,7 @@ void mcp_ctx_destroy(mcp_ctx* c) {
   if (c->d_sweep && !c->sh.empty()) { (void)hipSetDevice(c->sh[0].device); (void)hipFree(c->d_sweep); }
   if (c->h_boot) (void)hipHostFree(c->h_boot);
   if (c->h_flows) (void)hipHostFree(c->h_flows);
+  if (c->h_overlay) (void)hipHostFree(c->h_overlay);
   if (have_prev) (void)hipSetDevice(prev_dev);
   delete c;
 }
@@ -1412,6 +1530,7 @@ int run_tile(mcp_ctx* c, const mcp_params* prm, const Request& rq, uint64_t seed
   const float* chol = boot ? zchol.data() : rq.chol;
   std::vector<double> bm, bs2, rmu(rq.rebalanced ? N : 0), cm;
   if (rq.rebalanced) reb_means(N, rq.mu, boot ? rq.boot : nullptr, rmu.data());
+  const bool ov_walk = rq.overlay && rq.ov->n_rows > 0;    // no rows: the pivots of the plain call (SPEC.md 5.7)
   for (size_t s = 0; s < S; s++) {
     const Job& j = jobs[s];
     if (!j.active) continue;
@@ -1438,8 +1557,10 @@ int run_tile(mcp_ctx* c, const mcp_params* prm, const Request& rq, uint64_t seed
         cash_means(N, j.kt, rq.mu, boot ? rq.boot : nullptr, Wt, cm.data());
         cash_pivots(j.kt, prm->n_steps, cm.data(), rq.cf->flows, (double)(float)prm->v0, rq.hz ? rq.H : 0, rq.steps, sh.h_pivot.p,
                     sh.hz.h_pivot.p);
+      } else if (ov_walk) {                                  // SPEC.md 5.7: one walk gives T and every horizon
+        overlay_pivots(N, j.kt, prm->n_steps, rq.ov, rq.mu, Wt, rq.hz ? rq.H : 0, rq.steps, sh.h_pivot.p, sh.hz.h_pivot.p);
       } else if ((rc = tile_pivots(tp[s], rq, prm->n_steps, Wt, rmu.data(), bm.data(), bs2.data(), sh.h_pivot.p))) return rc;
-      for (int h = 0; rq.hz && !rq.cash && h < rq.H; h++)                // SPEC.md 5.2 / 5.3: row h*kt + k is pivoted with n_steps = h
+      for (int h = 0; rq.hz && !rq.cash && !ov_walk && h < rq.H; h++)                // SPEC.md 5.2 / 5.3: row h*kt + k is pivoted with n_steps = h
         if ((rc = tile_pivots(tp[s], rq, rq.steps[h], Wt, rmu.data(), bm.data(), bs2.data(), sh.hz.h_pivot.p + (size_t)h * j.kt)))
           return rc;
       if (exchange) { shared_packed = sh.h_packed.p; shared_pivot = sh.h_pivot.p; shared_hz_pivot = sh.hz.h_pivot.p; }
@@ -1456,6 +1577,9 @@ int run_tile(mcp_ctx* c, const mcp_params* prm, const Request& rq, uint64_t seed
       ln.hz_stride = j.pn;
       ln.d_rows = sh.boot.p;
       ln.d_flows = sh.cf.flows.p;
+      ln.d_overlay = sh.overlay.p;
+      ln.ov_n = N;
+      ln.ov_n4 = n4_of(N);
       if ((rc = launch_paths_impl(&tp[s], rq, ln))) return rc;
       if (rq.cash) {                                         // SPEC.md 5.6: the ruined and the short paths of every stored row
         const size_t rows_hz = rq.hz ? (size_t)rq.H * j.kt : 0;
@@ -1624,6 +1748,20 @@ int simulate_impl(mcp_ctx* c, const mcp_params* prm, const Request& rq, uint64_t
       if (e != hipSuccess) rc = fail(MCP_E_HIP, "cash-flow schedule upload: %s", hipGetErrorString(e));
     }
   }
+  if (rc == MCP_OK && rq.overlay) {
+    // SPEC.md 4.8: the table into one pinned staging copy and from there once into the overlay buffer of every shard (the tiles
+    // of the call share it)
+    const size_t bytes = overlay_bytes(prm->n_assets, rq.ov->n_rows);
+    rc = grow_host((void**)&c->h_overlay, &c->h_overlay_cap, bytes);
+    if (rc == MCP_OK) overlay_pack(prm->n_assets, rq.ov, c->h_overlay);
+    for (size_t s = 0; s < S && rc == MCP_OK; s++) {
+      Shard& sh = c->sh[s];
+      if (hipSetDevice(sh.device) != hipSuccess) { rc = fail(MCP_E_HIP, "hipSetDevice(%d)", sh.device); break; }
+      if ((rc = grow(sh.overlay, bytes))) break;
+      const hipError_t e = hipMemcpyAsync(sh.overlay.p, c->h_overlay, bytes, hipMemcpyHostToDevice, sh.stream);
+      if (e != hipSuccess) rc = fail(MCP_E_HIP, "overlay table upload: %s", hipGetErrorString(e));
+    }
+  }
   if (rc == MCP_OK && by_portfolio) {
     // every shard walks all paths for its slice of W; slices are tiled independently; no exchange
     std::vector<int> kb(S + 1);
@@ -1782,6 +1920,34 @@ int mcp_cashflow_pivots(const mcp_params* prm, const mcp_cashflow* cf, const flo
   std::vector<double> m((size_t)prm->n_portfolios);
   cash_means(prm->n_assets, prm->n_portfolios, mu, boot, W, m.data());
   cash_pivots(prm->n_portfolios, prm->n_steps, m.data(), cf->flows, (double)(float)prm->v0, 0, nullptr, out, nullptr);
+  return MCP_OK;
+}
+
+int mcp_simulate_overlay(mcp_ctx* c, const mcp_params* prm, const mcp_overlay* ov, const float* mu, const float* chol,
+                         const mcp_student_t* st, const float* W, uint64_t seed, uint64_t path_begin, uint64_t n_paths, int n_horizons,
+                         const int32_t* horizons, int n_levels, const double* levels, float* terminal_out, mcp_stats* stats_out,
+                         float* mdd_out, mcp_stats* dd_stats_out, float* horizon_out, mcp_stats* hz_stats_out, double* bands_out) {
+  Request rq = host_request(st ? SRC_T : SRC_GAUSS, mu, chol, W, terminal_out, stats_out);
+  rq.st = st;
+  rq.overlay = true;
+  rq.ov = ov;
+  rq.dd = dd_stats_out != nullptr;
+  rq.mdd_out = mdd_out;
+  rq.dd_stats_out = dd_stats_out;
+  ask_horizons(rq, n_horizons != 0, n_horizons, horizons, n_levels, levels, horizon_out, hz_stats_out, bands_out);
+  return simulate_checked(c, prm, rq, seed, path_begin, n_paths);
+}
+
+int mcp_overlay_pivots(const mcp_params* prm, const mcp_overlay* ov, const float* mu, const float* W, double* out) {
+  if (int rc = check_params(prm)) return rc;
+  if (int rc = check_overlay(prm, ov)) return rc;
+  if (!mu || !W || !out) return fail(MCP_E_ARG, "NULL pointer");
+  if (prm->compounding != MCP_COMPOUND_SIMPLE) return fail(MCP_E_UNSUPPORTED, "overlaid paths compound simply (no log compounding)");
+  if (ov->n_rows == 0) {                                   // every asset passes through: the plain pivots, which read no factor
+    const std::vector<float> eye((size_t)prm->n_assets * prm->n_assets, 0.0f);
+    return mcp_pivots(prm, mu, eye.data(), W, out);
+  }
+  overlay_pivots(prm->n_assets, prm->n_portfolios, prm->n_steps, ov, mu, W, 0, nullptr, out, nullptr);
   return MCP_OK;
 }
 

@@ -40,6 +40,13 @@
 #define MCP_MIN_WAVES_CF8 5 // the cash-flow kernel for 8 portfolios, N <= 16: unbounded it took 102 VGPRs (4 waves) where its twin without cash
                             // flows runs 5; at 5 it gets 93, no scratch, and measured 1.10x the twin instead of 1.12x
 #endif
+#ifndef MCP_MIN_WAVES_OV
+#define MCP_MIN_WAVES_OV 4  // the overlay kernel (N <= 16, one portfolio) holds the N4 prices P on top, as the rebalancing kernel holds B: at
+                            // 5 waves (96 VGPRs) the N = 16 kernels spilled 2 to 15 dwords to scratch outside the walk; at 4 none does
+#endif
+#ifndef MCP_MIN_WAVES_OV8
+#define MCP_MIN_WAVES_OV8 4 // the same for 8 portfolios, N <= 16
+#endif
 #ifndef MCP_EXP_VKEYS
 #define MCP_EXP_VKEYS 1
 #endif
@@ -163,6 +170,58 @@ __device__ __forceinline__ float cash_flow(const PathArgsCF&, int t) {
   return ((cflow_p)k->cf.flows)[t];
 }
 
+// The option overlay of SPEC.md 4.8: per asset a run of rows (kind, strike, premium, qty) that turns the raw return r_i of a step
+// into the strategy's return r'_i at the asset's price level P_i.  rows, row_begin [N4 + 1] (assets >= N own no rows) and spot [N4]
+// are device copies; bit i of `mask` is set when asset i owns rows.
+struct OverlayArgs {
+  const mcp_overlay_row* __restrict__ rows;
+  const int32_t* __restrict__ row_begin;
+  const float* __restrict__ spot;
+  uint64_t mask;
+};
+// Arguments of mc_paths_ov_kernel: the horizons of PathArgsHZ (n_horizons = 0: none), the drawdown output (written only when DD),
+// nu (read only when STT) and the overlay.
+struct PathArgsOV : PathArgsHZ {
+  float* __restrict__ mdd;
+  uint64_t mdd_stride;
+  StudentArgs st;
+  OverlayArgs ov;
+};
+__device__ __forceinline__ int32_t student_dof(const PathArgsOV&) { return kernarg_dof<PathArgsOV>(); }
+// The overlay of an overlay kernel's launch: wave-uniform and read-only, read where it is used through the kernel-argument pointer
+// and the constant address space (scalar loads; nothing held in SGPRs across the walk: the Cholesky factor lives there).
+typedef const __attribute__((address_space(4))) PathArgsOV* cov_p;
+__device__ __forceinline__ cov_p overlay_kernarg() {
+  cov_p k = (cov_p)__builtin_amdgcn_kernarg_segment_ptr();
+  asm volatile("" : "+s"(k));
+  return k;
+}
+// r'_i of SPEC.md 4.8 for an asset that owns the rows [rb, re): price = fma(prev, r, prev); num = fma(q_j, leg_j, num) over the
+// rows in order from +0; r' = prev != 0 ? num / prev : +0 (IEEE division); P_i = price.  The loop over the rows is a run-time loop
+// on wave-uniform bounds; every row is four scalar loads.
+__device__ __forceinline__ float overlay_return(float r, float& P, int rb, int re) {
+  typedef const __attribute__((address_space(4))) mcp_overlay_row* crow_p;
+  const float prev = P;
+  const float price = fma32(prev, r, prev);
+  float num = 0.0f;
+#pragma unroll 1
+  for (int j = rb; j < re; j++) {
+    const crow_p row = (crow_p)overlay_kernarg()->ov.rows + j;
+    const int32_t kind = row->kind;
+    const float strike = row->strike, premium = row->premium, qty = row->qty;
+    float leg;
+    if (kind == MCP_OVERLAY_LINEAR) {
+      leg = price - prev;
+    } else {
+      const float d = kind == MCP_OVERLAY_CALL ? price - strike : strike - price;
+      leg = (d > 0.0f ? d : 0.0f) - premium;
+    }
+    num = fma32(qty, leg, num);
+  }
+  P = price;
+  return prev != 0.0f ? num / prev : 0.0f;
+}
+
 // The LDS copy of the row table takes the slot of the inverse-CDF table (ICDF_LDS_ENTRIES float4: the bootstrap needs neither
 // that table nor the drift copy in its padding): R rows of NB float4 fit when R * NB <= ICDF_LDS_ENTRIES (N = 16: 272 rows).
 __host__ __device__ constexpr bool boot_fits_lds(uint64_t n_rows, int nb) { return n_rows * (uint64_t)nb <= (uint64_t)ICDF_LDS_ENTRIES; }
@@ -241,7 +300,8 @@ constexpr int PATH_BLOCK = 256;
 // REB: the step updates the assets' returns since the last rebalance B instead of V; V moves at the rebalance dates only
 // (SPEC.md 4.5).  STT: every normal of the step is scaled by s = sqrt((nu - 2) / chi), chi the sum of nu squared normals of
 // counter stream 2 (SPEC.md 2.2 / 4.6).  CF: the step's cash flow c_s is added to V after the update and ruin (V <= 0) is absorbing
-// (SPEC.md 4.7).  All ten kernels are the body in mcp_paths_body.inc.
+// (SPEC.md 4.7).  OV: the step carries the price P_i of every asset and replaces r_i by the return r'_i of the asset's option rows before
+// the weight dot (SPEC.md 4.8).  All eleven kernels are the body in mcp_paths_body.inc.
 #define MCP_PATHS_BOUNDS(NB, KT, PPT) \
   __launch_bounds__(PATH_BLOCK, (NB <= 4 && KT == 1 && PPT == 1) ? MCP_MIN_WAVES : ((KT == 1 && PPT == 1) ? MCP_MIN_WAVES_BIG : 1))
 #define MCP_REB_BOUNDS(NB, KT, PPT) \
@@ -250,7 +310,7 @@ constexpr int PATH_BLOCK = 256;
 
 template <int NB, int KT, int PPT, bool NATIVE, bool FOLD = false, bool LOGC = false>
 __global__ void MCP_PATHS_BOUNDS(NB, KT, PPT) mc_paths_kernel(const PathArgs a) {
-  constexpr bool DD = false, HZ = false, BOOT = false, BLDS = false, REB = false, STT = false, CF = false;
+  constexpr bool DD = false, HZ = false, BOOT = false, BLDS = false, REB = false, STT = false, CF = false, OV = false;
 #include "mcp_paths_body.inc"
 }
 
@@ -258,7 +318,7 @@ __global__ void MCP_PATHS_BOUNDS(NB, KT, PPT) mc_paths_kernel(const PathArgs a) 
 // array: appended to PathArgs itself they would move the hidden kernel arguments (grid size) of every plain kernel.
 template <int NB, int KT, int PPT, bool LOGC>
 __global__ void MCP_PATHS_BOUNDS(NB, KT, PPT) mc_paths_dd_kernel(const PathArgsDD a) {
-  constexpr bool DD = true, HZ = false, NATIVE = false, FOLD = false, BOOT = false, BLDS = false, REB = false, STT = false, CF = false;
+  constexpr bool DD = true, HZ = false, NATIVE = false, FOLD = false, BOOT = false, BLDS = false, REB = false, STT = false, CF = false, OV = false;
 #include "mcp_paths_body.inc"
 }
 
@@ -266,7 +326,7 @@ __global__ void MCP_PATHS_BOUNDS(NB, KT, PPT) mc_paths_dd_kernel(const PathArgsD
 // at the horizons, V_h stored after each; V_T and the fused epilogue as in mc_paths_kernel.
 template <int NB, int KT, int PPT, bool LOGC>
 __global__ void MCP_PATHS_BOUNDS(NB, KT, PPT) mc_paths_hz_kernel(const PathArgsHZ a) {
-  constexpr bool DD = false, HZ = true, NATIVE = false, FOLD = false, BOOT = false, BLDS = false, REB = false, STT = false, CF = false;
+  constexpr bool DD = false, HZ = true, NATIVE = false, FOLD = false, BOOT = false, BLDS = false, REB = false, STT = false, CF = false, OV = false;
 #include "mcp_paths_body.inc"
 }
 
@@ -274,14 +334,14 @@ __global__ void MCP_PATHS_BOUNDS(NB, KT, PPT) mc_paths_hz_kernel(const PathArgsH
 // block per path-step for the row index, no normals, no Cholesky GEMV.  V_T and the fused epilogue as in mc_paths_kernel.
 template <int NB, int KT, int PPT, bool LOGC, bool BLDS>
 __global__ void MCP_PATHS_BOUNDS(NB, KT, PPT) mc_paths_boot_kernel(const PathArgsBT a) {
-  constexpr bool DD = false, HZ = false, NATIVE = false, FOLD = false, BOOT = true, REB = false, STT = false, CF = false;
+  constexpr bool DD = false, HZ = false, NATIVE = false, FOLD = false, BOOT = true, REB = false, STT = false, CF = false, OV = false;
 #include "mcp_paths_body.inc"
 }
 
 // The bootstrap kernel with the horizons of SPEC.md 4.3 (the segmented walk of mc_paths_hz_kernel).
 template <int NB, int KT, int PPT, bool LOGC, bool BLDS>
 __global__ void MCP_PATHS_BOUNDS(NB, KT, PPT) mc_paths_boot_hz_kernel(const PathArgsBTHZ a) {
-  constexpr bool DD = false, HZ = true, NATIVE = false, FOLD = false, BOOT = true, REB = false, STT = false, CF = false;
+  constexpr bool DD = false, HZ = true, NATIVE = false, FOLD = false, BOOT = true, REB = false, STT = false, CF = false, OV = false;
 #include "mcp_paths_body.inc"
 }
 // The rebalancing kernel (SPEC.md 4.5; simple compounding, Gaussian draws or, BOOT, the bootstrap's rows): the walk in segments
@@ -289,7 +349,7 @@ __global__ void MCP_PATHS_BOUNDS(NB, KT, PPT) mc_paths_boot_hz_kernel(const Path
 // kernel serves terminal-only and horizon calls.  V_T and the fused epilogue as in mc_paths_kernel.
 template <int NB, int KT, int PPT, bool BOOT, bool BLDS>
 __global__ void MCP_REB_BOUNDS(NB, KT, PPT) mc_paths_reb_kernel(const PathArgsRB a) {
-  constexpr bool DD = false, HZ = false, NATIVE = false, FOLD = false, LOGC = false, REB = true, STT = false, CF = false;
+  constexpr bool DD = false, HZ = false, NATIVE = false, FOLD = false, LOGC = false, REB = true, STT = false, CF = false, OV = false;
 #include "mcp_paths_body.inc"
 }
 
@@ -298,17 +358,17 @@ __global__ void MCP_REB_BOUNDS(NB, KT, PPT) mc_paths_reb_kernel(const PathArgsRB
 // there.
 template <int NB, int KT, int PPT>
 __global__ void MCP_PATHS_BOUNDS(NB, KT, PPT) mc_paths_t_kernel(const PathArgsT a) {
-  constexpr bool DD = false, HZ = false, NATIVE = false, FOLD = false, LOGC = false, BOOT = false, BLDS = false, REB = false, STT = true, CF = false;
+  constexpr bool DD = false, HZ = false, NATIVE = false, FOLD = false, LOGC = false, BOOT = false, BLDS = false, REB = false, STT = true, CF = false, OV = false;
 #include "mcp_paths_body.inc"
 }
 template <int NB, int KT, int PPT>
 __global__ void MCP_PATHS_BOUNDS(NB, KT, PPT) mc_paths_t_dd_kernel(const PathArgsTDD a) {
-  constexpr bool DD = true, HZ = false, NATIVE = false, FOLD = false, LOGC = false, BOOT = false, BLDS = false, REB = false, STT = true, CF = false;
+  constexpr bool DD = true, HZ = false, NATIVE = false, FOLD = false, LOGC = false, BOOT = false, BLDS = false, REB = false, STT = true, CF = false, OV = false;
 #include "mcp_paths_body.inc"
 }
 template <int NB, int KT, int PPT>
 __global__ void MCP_PATHS_BOUNDS(NB, KT, PPT) mc_paths_t_hz_kernel(const PathArgsTHZ a) {
-  constexpr bool DD = false, HZ = true, NATIVE = false, FOLD = false, LOGC = false, BOOT = false, BLDS = false, REB = false, STT = true, CF = false;
+  constexpr bool DD = false, HZ = true, NATIVE = false, FOLD = false, LOGC = false, BOOT = false, BLDS = false, REB = false, STT = true, CF = false, OV = false;
 #include "mcp_paths_body.inc"
 }
 
@@ -321,9 +381,23 @@ __global__ void MCP_PATHS_BOUNDS(NB, KT, PPT) mc_paths_t_hz_kernel(const PathArg
                                                      : ((KT == 1 && PPT == 1) ? MCP_MIN_WAVES_BIG : 1))
 template <int NB, int KT, int PPT, bool BOOT, bool BLDS, bool STT>
 __global__ void MCP_CF_BOUNDS(NB, KT, PPT) mc_paths_cf_kernel(const PathArgsCF a) {
-  constexpr bool DD = false, HZ = true, NATIVE = false, FOLD = false, LOGC = false, REB = false, CF = true;
+  constexpr bool DD = false, HZ = true, NATIVE = false, FOLD = false, LOGC = false, REB = false, CF = true, OV = false;
 #include "mcp_paths_body.inc"
 }
+
+// The overlay kernel (SPEC.md 4.8; simple compounding, unfolded recurrence; Gaussian draws, STT: Student-t draws): the segmented
+// walk of mc_paths_hz_kernel with every asset's return replaced by its option rows' return at the price level the kernel carries.
+// H = 0 is one segment, so one kernel serves terminal-only and horizon calls; DD adds the drawdown state of mc_paths_dd_kernel.
+// V_T, the horizons, the drawdown and the fused epilogue as in those kernels.
+#define MCP_OV_BOUNDS(NB, KT, PPT) \
+  __launch_bounds__(PATH_BLOCK, (NB <= 4 && PPT == 1) ? (KT == 1 ? MCP_MIN_WAVES_OV : MCP_MIN_WAVES_OV8) \
+                                                     : ((KT == 1 && PPT == 1) ? MCP_MIN_WAVES_BIG : 1))
+template <int NB, int KT, int PPT, bool STT, bool DD>
+__global__ void MCP_OV_BOUNDS(NB, KT, PPT) mc_paths_ov_kernel(const PathArgsOV a) {
+  constexpr bool HZ = true, NATIVE = false, FOLD = false, LOGC = false, BOOT = false, BLDS = false, REB = false, CF = false, OV = true;
+#include "mcp_paths_body.inc"
+}
+#undef MCP_OV_BOUNDS
 #undef MCP_PATHS_BOUNDS
 #undef MCP_REB_BOUNDS
 #undef MCP_CF_BOUNDS

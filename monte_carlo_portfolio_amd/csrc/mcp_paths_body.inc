@@ -2,10 +2,11 @@
 // mc_paths_dd_kernel (DD = true), mc_paths_hz_kernel (HZ = true), the bootstrap kernels mc_paths_boot_kernel (BOOT = true)
 // and mc_paths_boot_hz_kernel (BOOT = HZ = true), the rebalancing kernel mc_paths_reb_kernel (REB = true, BOOT either) and the
 // Student-t kernels mc_paths_t_kernel / mc_paths_t_dd_kernel / mc_paths_t_hz_kernel (STT = true, DD or HZ as their twins);
-// and the cash-flow kernel mc_paths_cf_kernel (CF = HZ = true, BOOT or STT either); the step itself is mcp_paths_step.inc.  As a shared __device__ function the plain kernel's registers came out allocated differently;
+// and the cash-flow kernel mc_paths_cf_kernel (CF = HZ = true, BOOT or STT either) and the overlay kernel mc_paths_ov_kernel
+// (OV = HZ = true, STT or DD either); the step itself is mcp_paths_step.inc.  As a shared __device__ function the plain kernel's registers came out allocated differently;
 // included, the DD = false kernel compiles to the same instructions as before the drawdown existed.  In scope: the template
-// parameters NB, KT, PPT, NATIVE, FOLD, LOGC, DD, HZ, BOOT, BLDS, REB, STT, CF and the kernel argument `a` (PathArgs, or PathArgsDD /
-// PathArgsHZ / PathArgsBT / PathArgsBTHZ / PathArgsRB / PathArgsT / PathArgsTDD / PathArgsTHZ / PathArgsCF which start with one).  Without HZ the walk is the one loop it always was, so the plain and drawdown kernels keep their code.
+// parameters NB, KT, PPT, NATIVE, FOLD, LOGC, DD, HZ, BOOT, BLDS, REB, STT, CF, OV and the kernel argument `a` (PathArgs, or PathArgsDD /
+// PathArgsHZ / PathArgsBT / PathArgsBTHZ / PathArgsRB / PathArgsT / PathArgsTDD / PathArgsTHZ / PathArgsCF / PathArgsOV which start with one).  Without HZ the walk is the one loop it always was, so the plain and drawdown kernels keep their code.
   constexpr int N4 = 4 * NB;
   // wave-uniform parameters through the constant address space -> s_load_dword* into SGPRs
   typedef const __attribute__((address_space(4))) float* cfloat_p;
@@ -77,6 +78,7 @@
     float Pk[PPT][KT], Qk[PPT][KT];                       // DD: running peak P and q (simple) / d (log)
     uint32_t jrow[PPT];                                   // BOOT: the row index j_t of SPEC.md 2.1
     f32x2 Bs[PPT][N4 / 2];                                // REB: the assets' returns since the last rebalance (SPEC.md 4.5)
+    float Ps[PPT][N4];                                    // OV: the assets' price levels P_i (SPEC.md 4.8)
 #pragma unroll
     for (int e = 0; e < PPT; e++) {
       p[e] = tl * tile + (uint64_t)e * PATH_BLOCK + threadIdx.x;
@@ -93,6 +95,12 @@
       if constexpr (DD) {
 #pragma unroll
         for (int k = 0; k < KT; k++) { Pk[e][k] = -__builtin_inff(); Qk[e][k] = logc ? 0.0f : 1.0f; }
+      }
+      if constexpr (OV) {                                 // P_i = fl32(spot_i), scalar loads once per tile
+        typedef const __attribute__((address_space(4))) float* cspot_p;
+        const cspot_p sp = (cspot_p)overlay_kernarg()->ov.spot;
+#pragma unroll
+        for (int i = 0; i < N4; i++) Ps[e][i] = sp[i];
       }
     }
 
@@ -225,7 +233,12 @@
 #pragma unroll
         for (int k = 0; k < KT; k++)
           if (k < kt) a.terminal[(size_t)(a.k_begin + k) * a.stride + p[e]] = V[e][k];
-        if constexpr (DD) {                                // the drawdown output, read from the kernel arguments here only
+        if constexpr (DD && OV) {                          // the drawdown output of the overlay kernel's arguments
+          const cov_p dk = overlay_kernarg();
+#pragma unroll
+          for (int k = 0; k < KT; k++)
+            if (k < kt) dk->mdd[(size_t)(a.k_begin + k) * dk->mdd_stride + p[e]] = Qk[e][k];
+        } else if constexpr (DD) {                         // the drawdown output, read from the kernel arguments here only
           typedef const __attribute__((address_space(4))) PathArgsDD* cdd_p;
           cdd_p dk = (cdd_p)__builtin_amdgcn_kernarg_segment_ptr();
           asm volatile("" : "+s"(dk));

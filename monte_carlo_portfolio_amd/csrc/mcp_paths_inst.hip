@@ -32,7 +32,7 @@ static void go_plain(bool lg, const PathArgs& a, int grid, hipStream_t stream) {
 }
 
 // Every family on the spec's normals and the unfolded recurrence (or no normals: the bootstrap), KT = 1 or 8, compounding LG
-// (the rebalancing, Student-t and cash-flow kernels compound simply and take no LG).
+// (the rebalancing, Student-t, cash-flow and overlay kernels compound simply and take no LG).
 template <int KT, bool LG>
 static void go(const PathKernel& k, const PathArgs& a, int grid, hipStream_t stream) {
   switch (k.family) {
@@ -63,12 +63,18 @@ static void go(const PathKernel& k, const PathArgs& a, int grid, hipStream_t str
       else if (k.boot) MCP_GO((mc_paths_cf_kernel<MCP_NB, KT, 1, true, false, false>), PathArgsCF);
       else MCP_GO((mc_paths_cf_kernel<MCP_NB, KT, 1, false, false, false>), PathArgsCF);
       break;
+    case FAM_OV:
+      if (k.stt && k.dd) MCP_GO((mc_paths_ov_kernel<MCP_NB, KT, 1, true, true>), PathArgsOV);
+      else if (k.stt) MCP_GO((mc_paths_ov_kernel<MCP_NB, KT, 1, true, false>), PathArgsOV);
+      else if (k.dd) MCP_GO((mc_paths_ov_kernel<MCP_NB, KT, 1, false, true>), PathArgsOV);
+      else MCP_GO((mc_paths_ov_kernel<MCP_NB, KT, 1, false, false>), PathArgsOV);
+      break;
   }
 }
 
 hipError_t MCP_CAT(launch_paths_nb, MCP_NB)(int variant, const PathKernel& k, const PathArgs& a, int grid, hipStream_t stream) {
   const bool plain = k.family == FAM_PLAIN && !k.boot && !k.stt;
-  if (k.family < FAM_PLAIN || k.family > FAM_CF || (!plain && variant != 0 && variant != VAR_KT8)) return hipErrorInvalidValue;
+  if (k.family < FAM_PLAIN || k.family > FAM_OV || (!plain && variant != 0 && variant != VAR_KT8)) return hipErrorInvalidValue;
   switch (variant) {
     case 0: k.logc ? go<1, true>(k, a, grid, stream) : go<1, false>(k, a, grid, stream); break;
     case VAR_KT8: k.logc ? go<8, true>(k, a, grid, stream) : go<8, false>(k, a, grid, stream); break;

@@ -3,7 +3,9 @@
 // and drawdown state).  REB: no rho and no V; the returns since the last rebalance B_i = B_i + r_i + B_i r_i instead
 // (SPEC.md 4.5), a = B + r then B = fma(B, r, a), one v_pk_add_f32 and one v_pk_fma_f32 per pair of assets.  STT: the step's
 // chi blocks first (only s stays live while the asset normals are formed), then every asset normal scaled by s as it leaves
-// block_normals (SPEC.md 2.2 / 4.6).  CF: the flow c_s after the update, ruin absorbing (SPEC.md 4.7).  In scope: everything mcp_paths_body.inc declares before its step loops, and t.
+// block_normals (SPEC.md 2.2 / 4.6).  CF: the flow c_s after the update, ruin absorbing (SPEC.md 4.7).  OV: between the row pair's
+// returns and the weight dot, the return of every asset that owns option rows is replaced by its rows' return at the asset's price
+// level (SPEC.md 4.8); whether an asset owns rows is wave-uniform, a scalar branch.  In scope: everything mcp_paths_body.inc declares before its step loops, and t.
       float rho[PPT][KT];
       if constexpr (BOOT) {
         // SPEC.md 2.1 / 4.4: one Philox block on counter (t, 1, p_lo, p_hi); j_t = mulhi(x0, R) on a restart (t = 0 or
@@ -141,6 +143,23 @@
             Bs[e][m] = __builtin_elementwise_fma(Bs[e][m], acc[e], a2);
           }
         } else {
+        if constexpr (OV) {
+          const cov_p ok = overlay_kernarg();
+          const uint32_t has = (uint32_t)(ok->ov.mask >> (2 * m)) & 3u;     // do the assets 2m, 2m+1 own rows?
+          if (has) {
+            typedef const __attribute__((address_space(4))) int32_t* cbeg_p;
+            const cbeg_p rb = (cbeg_p)ok->ov.row_begin + 2 * m;
+            const int b0 = rb[0], b1 = rb[1], b2 = rb[2];
+            if (has & 1u) {
+#pragma unroll
+              for (int e = 0; e < PPT; e++) acc[e].x = overlay_return(acc[e].x, Ps[e][2 * m], b0, b1);
+            }
+            if (has & 2u) {
+#pragma unroll
+              for (int e = 0; e < PPT; e++) acc[e].y = overlay_return(acc[e].y, Ps[e][2 * m + 1], b1, b2);
+            }
+          }
+        }
 #pragma unroll
         for (int h = 0; h < 2; h++) {
           const int i = 2 * m + h;

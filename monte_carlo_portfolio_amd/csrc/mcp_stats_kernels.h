@@ -63,12 +63,14 @@ enum { VAR_KT8 = 1, VAR_NATIVE = 4, VAR_FOLD = 8 };
 //   FAM_PLAIN  PathArgs, PathArgsBT (boot), PathArgsT (stt)        FAM_DD   PathArgsDD, PathArgsTDD (stt)
 //   FAM_HZ     PathArgsHZ, PathArgsBTHZ (boot), PathArgsTHZ (stt)  FAM_REB  PathArgsRB (boot: its rows instead of normals)
 //   FAM_CF     PathArgsCF (boot: its rows; stt: t draws; the horizons optional)
+//   FAM_OV     PathArgsOV (stt: t draws; dd: the drawdown state; the horizons optional)
 // `blds`: the bootstrap's row table is copied into LDS (it fits boot_fits_lds) instead of being read from global memory.
 // VAR_NATIVE and VAR_FOLD exist for the plain Gaussian kernel only.
-enum PathFamily { FAM_PLAIN, FAM_DD, FAM_HZ, FAM_REB, FAM_CF };
+enum PathFamily { FAM_PLAIN, FAM_DD, FAM_HZ, FAM_REB, FAM_CF, FAM_OV };
 struct PathKernel {
   int family;
   bool logc, boot, blds, stt;
+  bool dd = false;                      // FAM_OV only: the overlay kernel that also tracks the drawdown
 };
 
 // mcp_paths_inst.hip (one translation unit per NB): returns hipErrorInvalidValue for a kernel that is not instantiated.

@@ -65,8 +65,8 @@ class Context:
 
     def _call(self, prm: _ffi.McpParams, W, seed: int, path_begin: int, n_paths: int, store: bool, mu=None, chol=None, rows=None,
               block: float = 1.0, dof=None, period=None, cost: float = 0.0, drawdown: bool = False, horizons=None, levels=(),
-              flows=None, target=None):
-        """The one library call behind every simulate_* method: cash flows (flows, target), Student-t draws (dof), rebalancing
+              flows=None, target=None, overlay=None):
+        """The one library call behind every simulate_* method: an option overlay (overlay: the triple of check_overlay), cash flows (flows, target), Student-t draws (dof), rebalancing
         (period, cost), bootstrap rows (rows, block) or Gaussian draws (mu, chol), with the drawdown or horizons.  Allocates the
         outputs that were asked for and passes NULL for the rest -> _Outputs, None where not asked for (terminal, qd,
         horizon_terminal: with `store` only; counts, hz_counts: with `flows` only)."""
@@ -90,7 +90,12 @@ class Context:
         hz_in = (H, ptr(steps) if H else None, L, ptr(lv) if L else None)
         hz_out = (ptr(hz_term), ptr(hz_stats), ptr(bands) if L else None)
         bt = _ffi.make_bootstrap(rows, block) if rows is not None else None
-        if flows is not None:
+        if overlay is not None:
+            st = _ffi.McpStudentT(int(dof), 0) if dof is not None else None
+            rc = lib.mcp_simulate_overlay(self._h, prm_p, ctypes.byref(_ffi.make_overlay(*overlay)), ptr(mu), ptr(chol),
+                                          ctypes.byref(st) if st is not None else None, ptr(W), *walk, *hz_in, ptr(term), ptr(stats),
+                                          ptr(raw), ptr(dd_stats), *hz_out)
+        elif flows is not None:
             counts = np.zeros((K, 2), np.uint64)
             hz_counts = np.zeros((H, K, 2), np.uint64) if horizons is not None else None
             st = _ffi.McpStudentT(int(dof), 0) if dof is not None else None
@@ -181,6 +186,16 @@ class Context:
                           horizons=horizons, levels=levels, flows=np.ascontiguousarray(flows, np.float32), target=target)
 
 
+    def simulate_overlay(self, prm: _ffi.McpParams, overlay, mu, chol, W, seed: int, path_begin: int, n_paths: int, store: bool,
+                         dof=None, drawdown: bool = False, horizons=None, levels=()):
+        """simulate() / simulate_drawdown() / simulate_horizons() / simulate_student_t() with the option rows `overlay` (the (rows,
+        row_begin, spot) triple of check_overlay) applied to every asset's return inside the walk (SPEC.md 4.8 / 5.7;
+        include/mcport.h, mcp_simulate_overlay; simple compounding only) -> _Outputs; the entries of the blocks not asked for are
+        None."""
+        return self._call(prm, W, seed, path_begin, n_paths, store, mu=mu, chol=chol, dof=dof, drawdown=drawdown, horizons=horizons,
+                          levels=levels, overlay=overlay)
+
+
 # What Context._call returns: mcp_stats record arrays (stats [K], dd_stats [K], hz_stats [H, K]), bands [H, K, L] and the stored
 # binary32 arrays (terminal [K, n], qd [K, n], horizon_terminal [H, K, n]); with cash flows the counts {n_ruined, n_short} of
 # SPEC.md 5.6 (counts [K, 2], hz_counts [H, K, 2], uint64).
@@ -217,6 +232,74 @@ def check_cashflow(cashflow, target, n_steps):
     if not np.all(np.isfinite(flows)):
         raise ValueError("cashflow entries must be finite (in binary32)")
     return flows, target
+
+
+def check_overlay(overlay, spot, n_assets):
+    """SPEC.md 4.8 argument rules -> None (no overlay) or (rows [n_rows] of _ffi.OVERLAY_ROW_DTYPE, row_begin int32 [N + 1], spot
+    binary32 [N]).  `overlay` is a dict {asset index: rows} or a length-N list of row lists, rows being the tuples (row_type,
+    strike, premium, qty) of options.strategy_rows with the seven row types of options.ROW_TYPES; strike and premium in price
+    units.  The sign of a selling row is folded into qty (negation is exact) and the numbers are rounded to binary32.  `spot`: the
+    assets' current prices [N] (a number for one asset), needed as soon as one asset owns rows; assets without rows may carry any
+    finite value.  ValueError for an unknown row type, a bool, a number that is not finite (also after rounding), a missing or
+    non-positive spot, an index out of range or more than MCP_MAX_OVERLAY_ROWS rows on an asset."""
+    from .options import BUY_ASSET, LONG_CALL, LONG_PUT, SELL_ASSET, SHORT_CALL, SHORT_FUTURES, SHORT_PUT
+    kinds = {BUY_ASSET: (_ffi.MCP_OVERLAY_LINEAR, 1.0), SELL_ASSET: (_ffi.MCP_OVERLAY_LINEAR, -1.0),
+             SHORT_FUTURES: (_ffi.MCP_OVERLAY_LINEAR, -1.0), LONG_CALL: (_ffi.MCP_OVERLAY_CALL, 1.0),
+             SHORT_CALL: (_ffi.MCP_OVERLAY_CALL, -1.0), LONG_PUT: (_ffi.MCP_OVERLAY_PUT, 1.0), SHORT_PUT: (_ffi.MCP_OVERLAY_PUT, -1.0)}
+
+    def number(v):
+        return isinstance(v, (int, float, np.integer, np.floating)) and not isinstance(v, (bool, np.bool_))
+    if overlay is None:
+        if spot is not None:
+            raise ValueError("spot needs overlay (prices matter to option rows only)")
+        return None
+    N = int(n_assets)
+    per_asset = [[] for _ in range(N)]
+    if isinstance(overlay, dict):
+        for key, rows in overlay.items():
+            if not isinstance(key, (int, np.integer)) or isinstance(key, (bool, np.bool_)) or not 0 <= key < N:
+                raise ValueError(f"overlay asset index {key!r} outside [0, {N})")
+            per_asset[int(key)] = list(rows)
+    else:
+        if isinstance(overlay, (str, bytes)) or not hasattr(overlay, "__len__") or len(overlay) != N:
+            raise ValueError(f"overlay must be a dict {{asset index: rows}} or a list of {N} row lists")
+        per_asset = [list(rows) if rows is not None else [] for rows in overlay]
+    out, begin = [], [0]
+    for i, rows in enumerate(per_asset):
+        if len(rows) > _ffi.MCP_MAX_OVERLAY_ROWS:
+            raise ValueError(f"asset {i} owns {len(rows)} overlay rows, at most {_ffi.MCP_MAX_OVERLAY_ROWS}")
+        for row in rows:
+            if not isinstance(row, (tuple, list)) or len(row) != 4:
+                raise ValueError(f"an overlay row is (row_type, strike, premium, qty), got {row!r}")
+            row_type, strike, premium, qty = row
+            if not isinstance(row_type, str) or row_type not in kinds:
+                raise ValueError(f"unknown overlay row type {row_type!r} (options.ROW_TYPES)")
+            if not all(number(v) for v in (strike, premium, qty)):
+                raise ValueError(f"overlay strike, premium and qty must be numbers (no bools), got {row!r}")
+            kind, sign = kinds[row_type]
+            with np.errstate(over="ignore"):
+                vals = np.array([strike, premium, sign * float(qty)], np.float64).astype(np.float32)
+            if not np.all(np.isfinite(vals)):
+                raise ValueError(f"overlay strike, premium and qty must be finite (in binary32), got {row!r}")
+            out.append((kind, vals[0], vals[1], vals[2]))
+        begin.append(len(out))
+    table = np.array(out, _ffi.OVERLAY_ROW_DTYPE) if out else np.zeros(0, _ffi.OVERLAY_ROW_DTYPE)
+    if spot is None:
+        if out:
+            raise ValueError("overlay rows need spot, the assets' current prices [N]")
+        spot32 = np.ones(N, np.float32)
+    else:
+        vals = np.atleast_1d(np.asarray(spot, object)).ravel().tolist()
+        if len(vals) != N or not all(number(v) for v in vals):
+            raise ValueError(f"spot must hold {N} numbers (no bools)")
+        with np.errstate(over="ignore"):
+            spot32 = np.asarray(vals, np.float64).astype(np.float32)
+        if not np.all(np.isfinite(spot32)):
+            raise ValueError("spot must be finite (in binary32)")
+        for i in range(N):
+            if begin[i + 1] > begin[i] and not spot32[i] > 0:
+                raise ValueError(f"spot of asset {i} must be positive (it owns overlay rows), got {vals[i]!r}")
+    return np.ascontiguousarray(table), np.asarray(begin, np.int32), np.ascontiguousarray(spot32)
 
 
 def check_dof(dof):
@@ -340,7 +423,8 @@ def drawdown_to_dict(rec) -> dict:
 def simulate_paths(mu, cov, weights, n_steps=252, n_paths=10_000, seed=0, v0=1.0, compounding="simple",
                    rf=0.0, alpha=0.95, devices=None, store=False, path_begin=0, chol=None,
                    native_math=False, as_array=False, fold=False, shard="auto", context=None, drawdown=False,
-                   horizons=None, bands=(), rebalance=None, rebalance_cost=0.0, dof=None, cashflow=None, target=None):
+                   horizons=None, bands=(), rebalance=None, rebalance_cost=0.0, dof=None, cashflow=None, target=None,
+                   overlay=None, spot=None):
     """Simulate `n_paths` correlated return paths and reduce them to risk statistics.
 
     mu [N], cov [N,N] are per-step mean and covariance (the reference's `mean_returns`, `cov_matrix`
@@ -389,7 +473,20 @@ def simulate_paths(mu, cov, weights, n_steps=252, n_paths=10_000, seed=0, v0=1.0
     as_array=True returns the tuple of the same call without cash flows with counts [K, 2] uint64 {n_ruined, n_short} (and
     hz_counts [H, K, 2] with horizons) appended.  Combines with dof and horizons / bands; not with drawdown, rebalance, fold,
     native_math or compounding="log", and target needs cashflow (ValueError).
+
+    overlay=None (default): every asset contributes its own return.  overlay={i: rows} (or a list of N row lists), spot=[N current
+    prices]: asset i is held through the option strategy `rows` -- the tuples (row_type, strike, premium, qty) of
+    options.strategy_rows, strike and premium in price units -- exactly as the reference replaces an asset's return series by
+    options.calc_options_series before anything else is computed: inside the path kernel every step's return of asset i becomes
+    sum_rows qty * leg(price, prev) / prev at the price level of that path (SPEC.md 4.8), the options struck again every step as
+    in the reference.  The result has the shape of the same call without it (drawdown, horizons / bands, dof, store and as_array
+    all combine; pivots of SPEC.md 5.7); an overlay without rows gives the plain call's values bit for bit.  Not with rebalance,
+    cashflow, fold, native_math or compounding="log" (ValueError).
     """
+    ov = check_overlay(overlay, spot, len(np.atleast_1d(np.asarray(mu))))
+    if ov is not None and (rebalance is not None or cashflow is not None or fold or native_math or compounding == "log"):
+        raise ValueError("overlay needs simple compounding, the spec's normals, the unfolded recurrence and constant weights: not "
+                         "with rebalance, cashflow, fold, native_math or compounding='log'")
     flows, target = check_cashflow(cashflow, target, n_steps)
     if flows is not None and (drawdown or rebalance is not None or fold or native_math or compounding == "log"):
         raise ValueError("cashflow needs simple compounding, the spec's normals, the unfolded recurrence and constant weights: not "
@@ -409,7 +506,7 @@ def simulate_paths(mu, cov, weights, n_steps=252, n_paths=10_000, seed=0, v0=1.0
     mu32, L, W = prepare_inputs(mu, cov, weights, chol)
     prm, ctx = _setup(mu32.shape[0], n_steps, W.shape[0], compounding, v0, alpha, rf, native_math, fold, devices, shard, context)
     out = ctx._call(prm, W, int(seed), int(path_begin), int(n_paths), store, mu=mu32, chol=L, dof=dof, period=period, cost=cost,
-                    drawdown=drawdown, horizons=steps, levels=levels, flows=flows, target=target)
+                    drawdown=drawdown, horizons=steps, levels=levels, flows=flows, target=target, overlay=ov)
     return _result(out, np.asarray(weights).ndim == 1, store, as_array, steps, levels, compounding, flows, target)
 
 
@@ -526,6 +623,10 @@ def simulate_bootstrap(returns, weights, n_steps=252, n_paths=10_000, block=1.0,
     pivots of SPEC.md 5.4; not with compounding="log").  cashflow / target as in simulate_paths (SPEC.md 4.7, pivots of SPEC.md
     5.6; not with rebalance or compounding="log").
     """
+    if unsupported.get("overlay") is not None or unsupported.get("spot") is not None:
+        raise ValueError("simulate_bootstrap does not take overlay: the rows are observed returns with no price level to strike an "
+                         "option at -- apply the strategy to the returns matrix first (options.calc_options_series per asset, as "
+                         "the reference does), or call simulate_paths(overlay=...)")
     if unsupported:
         raise ValueError(f"simulate_bootstrap does not take {sorted(unsupported)} (no normals: no fold / native_math / dof -- "
                          "Student-t draws are a parametric model, call simulate_paths(dof=...); drawdown on bootstrap paths is "
