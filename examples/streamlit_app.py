@@ -8,7 +8,8 @@ surface the package exposes under the reference's names.
 Tabs (reference lines they stand for): per-asset statistics (app.py:463-497), option strategy and P/L curve
 (app.py:499-653), the five-method random-weight sweep on historical rows plus the optimum re-scored on simulated paths
 (app.py:655-783 + the MI355X path engine), forecast (app.py:785-809: there ARIMA/GARCH; here a Monte Carlo fan from the
-path engine's values at intermediate horizons -- the tab says so).
+path engine's values at intermediate horizons, and for the selected asset a second fan with GARCH(1,1) volatility fitted to its
+rows -- the tab says so).
 Streamlit is not part of the test image; tests/test_gpu_shim.py runs this file under a recording stand-in module.
 """
 import os
@@ -134,6 +135,19 @@ with tab_forecast:                                            # app.py:785-809
         fan = {"horizon": horizons, **{f"{q} %": (v0 * (1.0 + b[:, j])).tolist() for j, q in enumerate(levels)}}
         st.line_chart(fan, x="horizon")
         st.write({"asset": name, **fan})
+    # the reference's forecast fits a GARCH(1,1) to the selected asset's returns and builds its interval from the summed variance
+    # forecast; here the same asset with the variance ratio fitted to its rows (fit_garch, N = 1) and the paths started from the
+    # fitted h0, today's regime (SPEC.md 4.9), beside the constant-variance fan above
+    r_sel = mcp.returns_matrix(resampled, {})[asset]
+    gfit = mcp.fit_garch(r_sel)
+    gfan = mcp.simulate_paths([r_sel.mean()], [[r_sel.var()]], [1.0], n_steps=horizons[-1], n_paths=n_paths, seed=12345,
+                              garch=gfit[:3], horizons=horizons, bands=levels)["horizons"]["bands"]
+    last = float(resampled[asset].iloc[-1])
+    st.subheader(f"{asset}: forecast fan with GARCH(1,1) volatility, started from today's regime")
+    gchart = {"step": horizons, **{f"{q} %": (last * (1.0 + gfan[:, j])).tolist() for j, q in enumerate(levels)}}
+    st.line_chart(gchart, x="step")
+    st.write({"GARCH(1,1)": {"asset": asset, "alpha": gfit.alpha, "beta": gfit.beta, "h0": gfit.h0,
+                             "log-likelihood gain over constant variance": gfit.loglik - gfit.loglik_iid}, **gchart})
     # contributions or withdrawals on the optimum (SPEC.md 4.7 / 5.6): the flow arrives after every period, a path whose value is
     # used up is ruined and stays so; the ruined share per horizon stands next to the fan
     flow = st.number_input("contribution (+) or withdrawal (-) per period", value=-0.05 * float(state["investment_amount"]))

@@ -28,7 +28,8 @@ extern "C" {
                                     + mcp_simulate_bootstrap[_horizons], mcp_bootstrap_pivots (additive, detected by symbol);
                                     + mcp_simulate_rebalanced, mcp_rebalance_pivots (additive, detected by symbol);
                                     + mcp_simulate_student_t (additive, detected by symbol);
-                                    + mcp_simulate_overlay, mcp_overlay_pivots (additive, detected by symbol) */
+                                    + mcp_simulate_overlay, mcp_overlay_pivots (additive, detected by symbol);
+                                    + mcp_simulate_garch (additive, detected by symbol) */
 #define MCP_MAX_ASSETS 64        /* thread-per-path kernels are instantiated for N4 = 4..64 */
 #define MCP_SELECT_BINS 2048     /* radix-select digit: 11 + 11 + 10 bits */
 #define MCP_MAX_HORIZONS 64      /* mcp_simulate_horizons: horizon steps per call */
@@ -287,6 +288,36 @@ int mcp_simulate_student_t(mcp_ctx *ctx, const mcp_params *prm, const mcp_studen
                            float *horizon_out,         /* NULL or host [H*K*n_paths], row h*K + k */
                            mcp_stats *hz_stats_out,    /* [H*K], NULL iff n_horizons == 0 */
                            double *bands_out);         /* [H*K*L], NULL iff n_levels == 0 */
+
+/* Volatility clustering: a scalar GARCH(1,1) on the covariance, Sigma_t = h_t Sigma (SPEC.md 4.9 / 5.8).  One variance ratio h per
+ * path, shared by all assets and portfolios: h_{t+1} = (1 - alpha - beta) + alpha (eps_t' Sigma^-1 eps_t / N) + beta h_t from h0, in
+ * units of the unconditional variance.  alpha, beta, h0: finite, rounded to binary32 (a, b, g) with a >= 0, b >= 0, a + b < 1 and
+ * g > 0; reserved must be 0. */
+typedef struct {
+    double alpha, beta, h0;
+    uint64_t reserved;
+} mcp_garch;
+
+/* mcp_simulate / mcp_simulate_drawdown / mcp_simulate_horizons / mcp_simulate_student_t with every step's normals scaled by
+ * u = sqrt(h) (st: u = s sqrt(h), s of SPEC.md 2.2) and h updated from the step's scaled normals (SPEC.md 4.9; simple compounding
+ * only): the conditional mean of every step is mu, so the moments are pivoted as mcp_pivots; with h0 = 1 the per-step covariance is
+ * the Gaussian call's, with h0 != 1 it reverts to it as 1 + (alpha + beta)^t (h0 - 1).  alpha = 0 and h0 = 1 is the call without
+ * GARCH bit for bit.  st NULL: Gaussian draws.  The horizon inputs and the outputs are those of mcp_simulate_student_t (the
+ * drawdown or the horizons, not both: MCP_E_UNSUPPORTED).  Argument errors (MCP_E_ARG: the rules above, those of st, NULL pointers)
+ * are found before any device is touched; log compounding, MCP_FLAG_FOLD, MCP_FLAG_NATIVE_MATH: MCP_E_UNSUPPORTED.  Costs: one
+ * square root, N + 2 fused multiply-adds and N multiplies per path-step; K >= 17 runs as passes of 8 portfolios. */
+int mcp_simulate_garch(mcp_ctx *ctx, const mcp_params *prm, const mcp_garch *g,
+                       const mcp_student_t *st,            /* NULL: Gaussian draws */
+                       const float *mu, const float *chol, const float *W,
+                       uint64_t seed, uint64_t path_begin, uint64_t n_paths,
+                       int n_horizons, const int32_t *horizons, int n_levels, const double *levels,
+                       float *terminal_out,        /* NULL or host [K*n_paths] */
+                       mcp_stats *stats_out,       /* [K] */
+                       float *mdd_out,             /* NULL or host [K*n_paths]; needs dd_stats_out */
+                       mcp_stats *dd_stats_out,    /* [K], or NULL: no drawdown */
+                       float *horizon_out,         /* NULL or host [H*K*n_paths], row h*K + k */
+                       mcp_stats *hz_stats_out,    /* [H*K], NULL iff n_horizons == 0 */
+                       double *bands_out);         /* [H*K*L], NULL iff n_levels == 0 */
 
 /* Contributions, withdrawals and ruin (SPEC.md 4.7 / 5.6).  flows: the schedule c_1 .. c_T, n_flows == prm->n_steps finite
  * binary32 values in the units of v0 (positive: paid in, negative: taken out), the same for every portfolio; flow c_s arrives

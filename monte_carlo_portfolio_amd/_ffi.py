@@ -72,6 +72,11 @@ class McpStudentT(ctypes.Structure):
     _fields_ = [("dof", ctypes.c_int32), ("reserved", ctypes.c_int32)]
 
 
+class McpGarch(ctypes.Structure):
+    """mcp_garch: alpha, beta and the starting variance ratio h0 of the GARCH(1,1) recurrence of SPEC.md 4.9."""
+    _fields_ = [("alpha", ctypes.c_double), ("beta", ctypes.c_double), ("h0", ctypes.c_double), ("reserved", ctypes.c_uint64)]
+
+
 class McpCashflow(ctypes.Structure):
     """mcp_cashflow: the schedule c_1 .. c_T (binary32, n_flows == n_steps) and the optional target of SPEC.md 4.7 / 5.6."""
     _fields_ = [("flows", ctypes.c_void_p), ("n_flows", ctypes.c_int32), ("has_target", ctypes.c_int32), ("target", ctypes.c_double)]
@@ -145,6 +150,8 @@ SIGNATURES = {
     "mcp_rebalance_pivots": (_int, [_PP, ctypes.POINTER(McpRebalance), _vp, ctypes.POINTER(McpBootstrap), _f32p, _f64p]),
     "mcp_simulate_student_t": (_int, [_vp, _PP, ctypes.POINTER(McpStudentT), _vp, _vp, _vp, _u64, _u64, _u64, _int, _vp, _int, _vp, _vp,
                                       _vp, _vp, _vp, _vp, _vp, _vp]),
+    "mcp_simulate_garch": (_int, [_vp, _PP, ctypes.POINTER(McpGarch), ctypes.POINTER(McpStudentT), _vp, _vp, _vp, _u64, _u64, _u64, _int,
+                                  _vp, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mcp_simulate_cashflow": (_int, [_vp, _PP, ctypes.POINTER(McpCashflow), _vp, _vp, ctypes.POINTER(McpBootstrap),
                                      ctypes.POINTER(McpStudentT), _vp, _u64, _u64, _u64, _int, _vp, _int, _vp, _vp, _vp, _vp, _vp, _vp,
                                      _vp, _vp]),

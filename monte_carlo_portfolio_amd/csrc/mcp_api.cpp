@@ -199,6 +199,35 @@ int check_student_t(const mcp_params* prm, const mcp_student_t* st) {
   return MCP_OK;
 }
 
+// SPEC.md 4.9: the binary32 constants of a GARCH request -- a = fl32(alpha), b = fl32(beta), g = fl32(h0), omega = fl32(1 - a - b)
+// and a_N = fl32(a / N), the last two from binary64 arithmetic on a and b
+struct GarchConsts { float a, b, g, omega, a_n; };
+GarchConsts garch_consts(const mcp_garch* g, int N) {
+  GarchConsts c;
+  c.a = (float)g->alpha;
+  c.b = (float)g->beta;
+  c.g = (float)g->h0;
+  c.omega = (float)(1.0 - (double)c.a - (double)c.b);
+  c.a_n = (float)((double)c.a / (double)N);
+  return c;
+}
+
+// SPEC.md 4.9: alpha, beta, h0 finite; a >= 0, b >= 0, a + b < 1 (binary64 sum of the rounded values), omega > 0, g > 0; reserved == 0
+int check_garch(const mcp_params* prm, const mcp_garch* g) {
+  if (!g) return fail(MCP_E_ARG, "garch is NULL");
+  if (g->reserved != 0) return fail(MCP_E_ARG, "garch reserved=%llu must be 0", (unsigned long long)g->reserved);
+  if (!std::isfinite(g->alpha) || !std::isfinite(g->beta) || !std::isfinite(g->h0))
+    return fail(MCP_E_ARG, "garch alpha=%g, beta=%g, h0=%g must be finite", g->alpha, g->beta, g->h0);
+  const GarchConsts c = garch_consts(g, prm->n_assets);
+  if (!std::isfinite(c.a) || !std::isfinite(c.b) || !std::isfinite(c.g))
+    return fail(MCP_E_ARG, "garch alpha=%g, beta=%g, h0=%g must be finite in binary32", g->alpha, g->beta, g->h0);
+  if (!(c.a >= 0.0f) || !(c.b >= 0.0f)) return fail(MCP_E_ARG, "garch alpha=%g and beta=%g must be >= 0", g->alpha, g->beta);
+  if (!((double)c.a + (double)c.b < 1.0) || !(c.omega > 0.0f))
+    return fail(MCP_E_ARG, "garch alpha + beta = %.9g must be < 1 in binary32", (double)c.a + (double)c.b);
+  if (!(c.g > 0.0f)) return fail(MCP_E_ARG, "garch h0=%g must be > 0 in binary32", g->h0);
+  return MCP_OK;
+}
+
 // SPEC.md 4.7: n_flows == n_steps finite flows, has_target 0 / 1 with a finite target, fl32(v0) > 0
 int check_cashflow(const mcp_params* prm, const mcp_cashflow* cf) {
   if (!cf) return fail(MCP_E_ARG, "cashflow is NULL");
@@ -317,6 +346,8 @@ struct Request {
   const mcp_cashflow* cf = nullptr;
   bool overlay = false;                 // SPEC.md 4.8: the option rows `ov`
   const mcp_overlay* ov = nullptr;
+  bool garch = false;                   // SPEC.md 4.9: the variance recurrence `gv` (SRC_GAUSS or SRC_T)
+  const mcp_garch* gv = nullptr;
   bool dd = false;                      // SPEC.md 4.2 / 5.1: the drawdown of every path
   bool hz = false;                      // SPEC.md 4.3 / 5.2: the values after H steps, statistics at alpha and at L levels
   int H = 0, L = 0;
@@ -372,6 +403,7 @@ struct Launch {
   const float* d_flows = nullptr;       // cash flows: [n_steps]
   const char* d_overlay = nullptr;      // overlay: [rows][row_begin N4 + 1][spot N4] (overlay_pack)
   int ov_n = 0, ov_n4 = 0;              // overlay: N and N4 of that table
+  int n_assets = 0;                     // GARCH: N (set by launch_paths_impl)
   void* d_partials = nullptr;
   void* d_hist = nullptr;
   hipStream_t stream = nullptr;
@@ -396,7 +428,12 @@ int check_request(const mcp_params* prm, const Request& rq, uint64_t n_paths, co
     if ((rq.hz_counts_out == nullptr) != !rq.hz) return fail(MCP_E_ARG, "hz_counts_out must be NULL exactly when n_horizons == 0");
   }
   if (rq.overlay && (rc = check_overlay(prm, rq.ov))) return rc;
+  if (rq.garch && (rc = check_garch(prm, rq.gv))) return rc;
   const bool logc = prm->compounding != MCP_COMPOUND_SIMPLE;
+  if (rq.garch && logc)
+    return fail(MCP_E_UNSUPPORTED, "GARCH paths compound simply (log compounding: expm1(S) has no finite mean under GARCH tails)");
+  if (rq.garch && (rq.src == SRC_BOOT || rq.rebalanced || rq.cash || rq.overlay))
+    return fail(MCP_E_UNSUPPORTED, "GARCH is not combined with bootstrap rows, rebalancing, cash flows or the overlay");
   if (rq.overlay && logc) return fail(MCP_E_UNSUPPORTED, "overlaid paths compound simply (no log compounding)");
   if (rq.overlay && (rq.src == SRC_BOOT || rq.rebalanced || rq.cash))
     return fail(MCP_E_UNSUPPORTED, "the overlay is not combined with bootstrap rows, rebalancing or cash flows");
@@ -405,7 +442,8 @@ int check_request(const mcp_params* prm, const Request& rq, uint64_t n_paths, co
   if (rq.src == SRC_T && logc)
     return fail(MCP_E_UNSUPPORTED, "Student-t paths compound simply (log compounding: expm1(S) has no finite mean under t steps)");
   if (prm->flags & (MCP_FLAG_FOLD | MCP_FLAG_NATIVE_MATH)) {   // the fast steps exist for plain Gaussian walks only
-    const char* who = rq.overlay           ? "overlaid paths run on the unfolded recurrence and the spec's normals"
+    const char* who = rq.garch             ? "GARCH paths run on the spec's normals and the unfolded recurrence"
+                      : rq.overlay         ? "overlaid paths run on the unfolded recurrence and the spec's normals"
                       : rq.cash            ? "paths with cash flows run on the unfolded recurrence and the spec's normals"
                       : rq.rebalanced      ? "rebalanced paths run on the unfolded recurrence and the spec's normals"
                       : rq.src == SRC_T    ? "Student-t paths run on the spec's normals and the unfolded recurrence"
@@ -871,6 +909,20 @@ static void fill(mcp::PathArgsBTHZ& x, const Request& rq, const Launch& ln) { fi
 static void fill(mcp::PathArgsT& x, const Request& rq, const Launch&) { x.st = student_block(rq); }
 static void fill(mcp::PathArgsTDD& x, const Request& rq, const Launch& ln) { fill((mcp::PathArgsDD&)x, rq, ln); x.st = student_block(rq); }
 static void fill(mcp::PathArgsTHZ& x, const Request& rq, const Launch& ln) { fill_hz(x, rq, ln); x.st = student_block(rq); }
+static void garch_block(mcp::StudentArgs& st, mcp::GarchArgs& gv, const Request& rq, int n_assets) {
+  const GarchConsts c = garch_consts(rq.gv, n_assets);
+  st.dof = rq.src == SRC_T ? rq.st->dof : 0;                   // 0: Gaussian draws
+  st.pad = 0;
+  gv.a_n = c.a_n;
+  gv.b = c.b;
+  gv.omega = c.omega;
+  gv.h0 = c.g;
+  gv.n_assets = n_assets;
+  gv.pad = 0;
+}
+static void fill(mcp::PathArgsG& x, const Request& rq, const Launch& ln) { garch_block(x.st, x.gv, rq, ln.n_assets); }
+static void fill(mcp::PathArgsGDD& x, const Request& rq, const Launch& ln) { fill((mcp::PathArgsDD&)x, rq, ln); garch_block(x.st, x.gv, rq, ln.n_assets); }
+static void fill(mcp::PathArgsGHZ& x, const Request& rq, const Launch& ln) { fill_hz(x, rq, ln); garch_block(x.st, x.gv, rq, ln.n_assets); }
 static void fill(mcp::PathArgsCF& x, const Request& rq, const Launch& ln) {
   fill_hz(x, rq, ln);
   x.bt = boot_block(rq, ln);
@@ -922,7 +974,7 @@ static int launch_passes(const mcp::PathArgs& a, const Request& rq, const Launch
 static int launch_paths_impl(const mcp_params* prm, const Request& rq, const Launch& ln) {
   const int nb = (prm->n_assets + 3) / 4;
   const int K = prm->n_portfolios;
-  const bool plain = rq.src == SRC_GAUSS && !rq.dd && !rq.hz && !rq.rebalanced && !rq.cash && !rq.overlay;
+  const bool plain = rq.src == SRC_GAUSS && !rq.dd && !rq.hz && !rq.rebalanced && !rq.cash && !rq.overlay && !rq.garch;
   int variant = 0;
   if (prm->flags & MCP_FLAG_FOLD) variant |= mcp::VAR_FOLD;
   if (K > 1) variant |= mcp::VAR_KT8;
@@ -984,6 +1036,16 @@ static int launch_paths_impl(const mcp_params* prm, const Request& rq, const Lau
   k.blds = k.boot && mcp::boot_fits_lds((uint64_t)rq.boot->n_rows, nb);
   k.stt = rq.src == SRC_T;
   k.dd = rq.overlay && rq.dd;
+  k.gv = rq.garch;
+  if (k.gv) {
+    Launch lg = ln;
+    lg.n_assets = prm->n_assets;
+    switch (k.family) {
+      case mcp::FAM_DD: return launch_passes<mcp::PathArgsGDD>(a, rq, lg, variant, k, nb);
+      case mcp::FAM_HZ: return launch_passes<mcp::PathArgsGHZ>(a, rq, lg, variant, k, nb);
+      default: return launch_passes<mcp::PathArgsG>(a, rq, lg, variant, k, nb);
+    }
+  }
   switch (k.family) {
     case mcp::FAM_OV: return launch_passes<mcp::PathArgsOV>(a, rq, ln, variant, k, nb);
     case mcp::FAM_CF: return launch_passes<mcp::PathArgsCF>(a, rq, ln, variant, k, nb);
@@ -1884,6 +1946,21 @@ int mcp_simulate_student_t(mcp_ctx* c, const mcp_params* prm, const mcp_student_
                            mcp_stats* dd_stats_out, float* horizon_out, mcp_stats* hz_stats_out, double* bands_out) {
   Request rq = host_request(SRC_T, mu, chol, W, terminal_out, stats_out);
   rq.st = st;
+  rq.dd = dd_stats_out != nullptr;
+  rq.mdd_out = mdd_out;
+  rq.dd_stats_out = dd_stats_out;
+  ask_horizons(rq, n_horizons != 0, n_horizons, horizons, n_levels, levels, horizon_out, hz_stats_out, bands_out);
+  return simulate_checked(c, prm, rq, seed, path_begin, n_paths);
+}
+
+int mcp_simulate_garch(mcp_ctx* c, const mcp_params* prm, const mcp_garch* g, const mcp_student_t* st, const float* mu,
+                       const float* chol, const float* W, uint64_t seed, uint64_t path_begin, uint64_t n_paths, int n_horizons,
+                       const int32_t* horizons, int n_levels, const double* levels, float* terminal_out, mcp_stats* stats_out,
+                       float* mdd_out, mcp_stats* dd_stats_out, float* horizon_out, mcp_stats* hz_stats_out, double* bands_out) {
+  Request rq = host_request(st ? SRC_T : SRC_GAUSS, mu, chol, W, terminal_out, stats_out);
+  rq.st = st;
+  rq.garch = true;
+  rq.gv = g;
   rq.dd = dd_stats_out != nullptr;
   rq.mdd_out = mdd_out;
   rq.dd_stats_out = dd_stats_out;

@@ -146,6 +146,36 @@ __device__ __forceinline__ int32_t student_dof(const PathArgsT&) { return kernar
 __device__ __forceinline__ int32_t student_dof(const PathArgsTDD&) { return kernarg_dof<PathArgsTDD>(); }
 __device__ __forceinline__ int32_t student_dof(const PathArgsTHZ&) { return kernarg_dof<PathArgsTHZ>(); }
 
+// GARCH(1,1) on the covariance (SPEC.md 4.9): the host constants a_N = fl32(a / N), b, omega = fl32(1 - a - b), the start h0 of the
+// per-path variance ratio h, and N (the padding normals j >= N stay out of the step's shock q).  Appended, after the degrees of
+// freedom (0: Gaussian draws), to the arguments of the plain, drawdown and horizon kernels (mc_paths_g_kernel,
+// mc_paths_g_dd_kernel, mc_paths_g_hz_kernel).
+struct GarchArgs {
+  float a_n, b, omega, h0;
+  int32_t n_assets;
+  int32_t pad;
+};
+struct PathArgsG : PathArgs { StudentArgs st; GarchArgs gv; };
+struct PathArgsGDD : PathArgsDD { StudentArgs st; GarchArgs gv; };
+struct PathArgsGHZ : PathArgsHZ { StudentArgs st; GarchArgs gv; };
+__device__ __forceinline__ int32_t student_dof(const PathArgsG&) { return kernarg_dof<PathArgsG>(); }
+__device__ __forceinline__ int32_t student_dof(const PathArgsGDD&) { return kernarg_dof<PathArgsGDD>(); }
+__device__ __forceinline__ int32_t student_dof(const PathArgsGHZ&) { return kernarg_dof<PathArgsGHZ>(); }
+// The GARCH block of a g kernel's launch: wave-uniform and read-only, read where it is used through the kernel-argument pointer
+// and the constant address space (scalar loads; nothing held in SGPRs across the walk: the Cholesky factor lives there).
+typedef const __attribute__((address_space(4))) GarchArgs* cgarch_p;
+template <class A>
+__device__ __forceinline__ cgarch_p kernarg_garch() {
+  typedef const __attribute__((address_space(4))) A* cg_p;
+  cg_p k = (cg_p)__builtin_amdgcn_kernarg_segment_ptr();
+  asm volatile("" : "+s"(k));
+  return &k->gv;
+}
+__device__ __forceinline__ cgarch_p garch_args(const PathArgs&) { return nullptr; }
+__device__ __forceinline__ cgarch_p garch_args(const PathArgsG&) { return kernarg_garch<PathArgsG>(); }
+__device__ __forceinline__ cgarch_p garch_args(const PathArgsGDD&) { return kernarg_garch<PathArgsGDD>(); }
+__device__ __forceinline__ cgarch_p garch_args(const PathArgsGHZ&) { return kernarg_garch<PathArgsGHZ>(); }
+
 // Cash flows and ruin (SPEC.md 4.7): the schedule c_1 .. c_T, one binary32 flow per step, the same for every portfolio.
 struct CashArgs {
   const float* __restrict__ flows;    // [n_steps] device copy; flows[t] = c_{t+1} arrives at the end of step t
@@ -301,7 +331,9 @@ constexpr int PATH_BLOCK = 256;
 // (SPEC.md 4.5).  STT: every normal of the step is scaled by s = sqrt((nu - 2) / chi), chi the sum of nu squared normals of
 // counter stream 2 (SPEC.md 2.2 / 4.6).  CF: the step's cash flow c_s is added to V after the update and ruin (V <= 0) is absorbing
 // (SPEC.md 4.7).  OV: the step carries the price P_i of every asset and replaces r_i by the return r'_i of the asset's option rows before
-// the weight dot (SPEC.md 4.8).  All eleven kernels are the body in mcp_paths_body.inc.
+// the weight dot (SPEC.md 4.8).  GV: the step's normals are scaled by u = sqrt(h) (STT: times s), h the path's GARCH(1,1) variance
+// ratio, and h is updated from the scaled normals (SPEC.md 4.9); in a GV kernel STT is set and nu = 0 at run time means Gaussian
+// draws.  All fourteen kernels are the body in mcp_paths_body.inc.
 #define MCP_PATHS_BOUNDS(NB, KT, PPT) \
   __launch_bounds__(PATH_BLOCK, (NB <= 4 && KT == 1 && PPT == 1) ? MCP_MIN_WAVES : ((KT == 1 && PPT == 1) ? MCP_MIN_WAVES_BIG : 1))
 #define MCP_REB_BOUNDS(NB, KT, PPT) \
@@ -310,7 +342,7 @@ constexpr int PATH_BLOCK = 256;
 
 template <int NB, int KT, int PPT, bool NATIVE, bool FOLD = false, bool LOGC = false>
 __global__ void MCP_PATHS_BOUNDS(NB, KT, PPT) mc_paths_kernel(const PathArgs a) {
-  constexpr bool DD = false, HZ = false, BOOT = false, BLDS = false, REB = false, STT = false, CF = false, OV = false;
+  constexpr bool DD = false, HZ = false, BOOT = false, BLDS = false, REB = false, STT = false, CF = false, OV = false, GV = false;
 #include "mcp_paths_body.inc"
 }
 
@@ -318,7 +350,7 @@ __global__ void MCP_PATHS_BOUNDS(NB, KT, PPT) mc_paths_kernel(const PathArgs a) 
 // array: appended to PathArgs itself they would move the hidden kernel arguments (grid size) of every plain kernel.
 template <int NB, int KT, int PPT, bool LOGC>
 __global__ void MCP_PATHS_BOUNDS(NB, KT, PPT) mc_paths_dd_kernel(const PathArgsDD a) {
-  constexpr bool DD = true, HZ = false, NATIVE = false, FOLD = false, BOOT = false, BLDS = false, REB = false, STT = false, CF = false, OV = false;
+  constexpr bool DD = true, HZ = false, NATIVE = false, FOLD = false, BOOT = false, BLDS = false, REB = false, STT = false, CF = false, OV = false, GV = false;
 #include "mcp_paths_body.inc"
 }
 
@@ -326,7 +358,7 @@ __global__ void MCP_PATHS_BOUNDS(NB, KT, PPT) mc_paths_dd_kernel(const PathArgsD
 // at the horizons, V_h stored after each; V_T and the fused epilogue as in mc_paths_kernel.
 template <int NB, int KT, int PPT, bool LOGC>
 __global__ void MCP_PATHS_BOUNDS(NB, KT, PPT) mc_paths_hz_kernel(const PathArgsHZ a) {
-  constexpr bool DD = false, HZ = true, NATIVE = false, FOLD = false, BOOT = false, BLDS = false, REB = false, STT = false, CF = false, OV = false;
+  constexpr bool DD = false, HZ = true, NATIVE = false, FOLD = false, BOOT = false, BLDS = false, REB = false, STT = false, CF = false, OV = false, GV = false;
 #include "mcp_paths_body.inc"
 }
 
@@ -334,14 +366,14 @@ __global__ void MCP_PATHS_BOUNDS(NB, KT, PPT) mc_paths_hz_kernel(const PathArgsH
 // block per path-step for the row index, no normals, no Cholesky GEMV.  V_T and the fused epilogue as in mc_paths_kernel.
 template <int NB, int KT, int PPT, bool LOGC, bool BLDS>
 __global__ void MCP_PATHS_BOUNDS(NB, KT, PPT) mc_paths_boot_kernel(const PathArgsBT a) {
-  constexpr bool DD = false, HZ = false, NATIVE = false, FOLD = false, BOOT = true, REB = false, STT = false, CF = false, OV = false;
+  constexpr bool DD = false, HZ = false, NATIVE = false, FOLD = false, BOOT = true, REB = false, STT = false, CF = false, OV = false, GV = false;
 #include "mcp_paths_body.inc"
 }
 
 // The bootstrap kernel with the horizons of SPEC.md 4.3 (the segmented walk of mc_paths_hz_kernel).
 template <int NB, int KT, int PPT, bool LOGC, bool BLDS>
 __global__ void MCP_PATHS_BOUNDS(NB, KT, PPT) mc_paths_boot_hz_kernel(const PathArgsBTHZ a) {
-  constexpr bool DD = false, HZ = true, NATIVE = false, FOLD = false, BOOT = true, REB = false, STT = false, CF = false, OV = false;
+  constexpr bool DD = false, HZ = true, NATIVE = false, FOLD = false, BOOT = true, REB = false, STT = false, CF = false, OV = false, GV = false;
 #include "mcp_paths_body.inc"
 }
 // The rebalancing kernel (SPEC.md 4.5; simple compounding, Gaussian draws or, BOOT, the bootstrap's rows): the walk in segments
@@ -349,7 +381,7 @@ __global__ void MCP_PATHS_BOUNDS(NB, KT, PPT) mc_paths_boot_hz_kernel(const Path
 // kernel serves terminal-only and horizon calls.  V_T and the fused epilogue as in mc_paths_kernel.
 template <int NB, int KT, int PPT, bool BOOT, bool BLDS>
 __global__ void MCP_REB_BOUNDS(NB, KT, PPT) mc_paths_reb_kernel(const PathArgsRB a) {
-  constexpr bool DD = false, HZ = false, NATIVE = false, FOLD = false, LOGC = false, REB = true, STT = false, CF = false, OV = false;
+  constexpr bool DD = false, HZ = false, NATIVE = false, FOLD = false, LOGC = false, REB = true, STT = false, CF = false, OV = false, GV = false;
 #include "mcp_paths_body.inc"
 }
 
@@ -358,17 +390,38 @@ __global__ void MCP_REB_BOUNDS(NB, KT, PPT) mc_paths_reb_kernel(const PathArgsRB
 // there.
 template <int NB, int KT, int PPT>
 __global__ void MCP_PATHS_BOUNDS(NB, KT, PPT) mc_paths_t_kernel(const PathArgsT a) {
-  constexpr bool DD = false, HZ = false, NATIVE = false, FOLD = false, LOGC = false, BOOT = false, BLDS = false, REB = false, STT = true, CF = false, OV = false;
+  constexpr bool DD = false, HZ = false, NATIVE = false, FOLD = false, LOGC = false, BOOT = false, BLDS = false, REB = false, STT = true, CF = false, OV = false, GV = false;
 #include "mcp_paths_body.inc"
 }
 template <int NB, int KT, int PPT>
 __global__ void MCP_PATHS_BOUNDS(NB, KT, PPT) mc_paths_t_dd_kernel(const PathArgsTDD a) {
-  constexpr bool DD = true, HZ = false, NATIVE = false, FOLD = false, LOGC = false, BOOT = false, BLDS = false, REB = false, STT = true, CF = false, OV = false;
+  constexpr bool DD = true, HZ = false, NATIVE = false, FOLD = false, LOGC = false, BOOT = false, BLDS = false, REB = false, STT = true, CF = false, OV = false, GV = false;
 #include "mcp_paths_body.inc"
 }
 template <int NB, int KT, int PPT>
 __global__ void MCP_PATHS_BOUNDS(NB, KT, PPT) mc_paths_t_hz_kernel(const PathArgsTHZ a) {
-  constexpr bool DD = false, HZ = true, NATIVE = false, FOLD = false, LOGC = false, BOOT = false, BLDS = false, REB = false, STT = true, CF = false, OV = false;
+  constexpr bool DD = false, HZ = true, NATIVE = false, FOLD = false, LOGC = false, BOOT = false, BLDS = false, REB = false, STT = true, CF = false, OV = false, GV = false;
+#include "mcp_paths_body.inc"
+}
+
+// The GARCH kernels (SPEC.md 4.9; simple compounding, unfolded recurrence; Gaussian draws, or Student-t draws when the launch
+// carries nu != 0, a wave-uniform branch around the chi blocks): mc_paths_kernel, mc_paths_dd_kernel and mc_paths_hz_kernel with
+// every step's normals scaled by u = sqrt(h) (times the step's s), h the path's variance ratio, updated from the step's shock.
+// V_T, the drawdown, the horizons and the fused epilogue as there.  They keep the plain kernel's launch bounds: no listing shows
+// scratch in a step loop (profiles/garch_isa.txt).
+template <int NB, int KT, int PPT>
+__global__ void MCP_PATHS_BOUNDS(NB, KT, PPT) mc_paths_g_kernel(const PathArgsG a) {
+  constexpr bool DD = false, HZ = false, NATIVE = false, FOLD = false, LOGC = false, BOOT = false, BLDS = false, REB = false, STT = true, CF = false, OV = false, GV = true;
+#include "mcp_paths_body.inc"
+}
+template <int NB, int KT, int PPT>
+__global__ void MCP_PATHS_BOUNDS(NB, KT, PPT) mc_paths_g_dd_kernel(const PathArgsGDD a) {
+  constexpr bool DD = true, HZ = false, NATIVE = false, FOLD = false, LOGC = false, BOOT = false, BLDS = false, REB = false, STT = true, CF = false, OV = false, GV = true;
+#include "mcp_paths_body.inc"
+}
+template <int NB, int KT, int PPT>
+__global__ void MCP_PATHS_BOUNDS(NB, KT, PPT) mc_paths_g_hz_kernel(const PathArgsGHZ a) {
+  constexpr bool DD = false, HZ = true, NATIVE = false, FOLD = false, LOGC = false, BOOT = false, BLDS = false, REB = false, STT = true, CF = false, OV = false, GV = true;
 #include "mcp_paths_body.inc"
 }
 
@@ -381,7 +434,7 @@ __global__ void MCP_PATHS_BOUNDS(NB, KT, PPT) mc_paths_t_hz_kernel(const PathArg
                                                      : ((KT == 1 && PPT == 1) ? MCP_MIN_WAVES_BIG : 1))
 template <int NB, int KT, int PPT, bool BOOT, bool BLDS, bool STT>
 __global__ void MCP_CF_BOUNDS(NB, KT, PPT) mc_paths_cf_kernel(const PathArgsCF a) {
-  constexpr bool DD = false, HZ = true, NATIVE = false, FOLD = false, LOGC = false, REB = false, CF = true, OV = false;
+  constexpr bool DD = false, HZ = true, NATIVE = false, FOLD = false, LOGC = false, REB = false, CF = true, OV = false, GV = false;
 #include "mcp_paths_body.inc"
 }
 
@@ -394,7 +447,7 @@ __global__ void MCP_CF_BOUNDS(NB, KT, PPT) mc_paths_cf_kernel(const PathArgsCF a
                                                      : ((KT == 1 && PPT == 1) ? MCP_MIN_WAVES_BIG : 1))
 template <int NB, int KT, int PPT, bool STT, bool DD>
 __global__ void MCP_OV_BOUNDS(NB, KT, PPT) mc_paths_ov_kernel(const PathArgsOV a) {
-  constexpr bool HZ = true, NATIVE = false, FOLD = false, LOGC = false, BOOT = false, BLDS = false, REB = false, CF = false, OV = true;
+  constexpr bool HZ = true, NATIVE = false, FOLD = false, LOGC = false, BOOT = false, BLDS = false, REB = false, CF = false, OV = true, GV = false;
 #include "mcp_paths_body.inc"
 }
 #undef MCP_OV_BOUNDS

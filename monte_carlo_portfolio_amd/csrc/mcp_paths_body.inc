@@ -3,10 +3,11 @@
 // and mc_paths_boot_hz_kernel (BOOT = HZ = true), the rebalancing kernel mc_paths_reb_kernel (REB = true, BOOT either) and the
 // Student-t kernels mc_paths_t_kernel / mc_paths_t_dd_kernel / mc_paths_t_hz_kernel (STT = true, DD or HZ as their twins);
 // and the cash-flow kernel mc_paths_cf_kernel (CF = HZ = true, BOOT or STT either) and the overlay kernel mc_paths_ov_kernel
-// (OV = HZ = true, STT or DD either); the step itself is mcp_paths_step.inc.  As a shared __device__ function the plain kernel's registers came out allocated differently;
+// (OV = HZ = true, STT or DD either) and the GARCH kernels mc_paths_g_kernel / mc_paths_g_dd_kernel / mc_paths_g_hz_kernel (GV =
+// STT = true, DD or HZ as their twins); the step itself is mcp_paths_step.inc.  As a shared __device__ function the plain kernel's registers came out allocated differently;
 // included, the DD = false kernel compiles to the same instructions as before the drawdown existed.  In scope: the template
-// parameters NB, KT, PPT, NATIVE, FOLD, LOGC, DD, HZ, BOOT, BLDS, REB, STT, CF, OV and the kernel argument `a` (PathArgs, or PathArgsDD /
-// PathArgsHZ / PathArgsBT / PathArgsBTHZ / PathArgsRB / PathArgsT / PathArgsTDD / PathArgsTHZ / PathArgsCF / PathArgsOV which start with one).  Without HZ the walk is the one loop it always was, so the plain and drawdown kernels keep their code.
+// parameters NB, KT, PPT, NATIVE, FOLD, LOGC, DD, HZ, BOOT, BLDS, REB, STT, CF, OV, GV and the kernel argument `a` (PathArgs, or PathArgsDD /
+// PathArgsHZ / PathArgsBT / PathArgsBTHZ / PathArgsRB / PathArgsT / PathArgsTDD / PathArgsTHZ / PathArgsCF / PathArgsOV / PathArgsG / PathArgsGDD / PathArgsGHZ which start with one).  Without HZ the walk is the one loop it always was, so the plain and drawdown kernels keep their code.
   constexpr int N4 = 4 * NB;
   // wave-uniform parameters through the constant address space -> s_load_dword* into SGPRs
   typedef const __attribute__((address_space(4))) float* cfloat_p;
@@ -79,6 +80,7 @@
     uint32_t jrow[PPT];                                   // BOOT: the row index j_t of SPEC.md 2.1
     f32x2 Bs[PPT][N4 / 2];                                // REB: the assets' returns since the last rebalance (SPEC.md 4.5)
     float Ps[PPT][N4];                                    // OV: the assets' price levels P_i (SPEC.md 4.8)
+    float gh[PPT];                                        // GV: the variance ratio h of SPEC.md 4.9
 #pragma unroll
     for (int e = 0; e < PPT; e++) {
       p[e] = tl * tile + (uint64_t)e * PATH_BLOCK + threadIdx.x;
@@ -88,6 +90,7 @@
 #pragma unroll
       for (int k = 0; k < KT; k++) V[e][k] = logc ? 0.0f : a.v0;
       if constexpr (BOOT) jrow[e] = 0u;                   // replaced at t = 0 (a restart)
+      if constexpr (GV) gh[e] = garch_args(a)->h0;        // one scalar load per tile
       if constexpr (REB) {
 #pragma unroll
         for (int m = 0; m < N4 / 2; m++) Bs[e][m] = f32x2{0.0f, 0.0f};

@@ -32,22 +32,25 @@ static void go_plain(bool lg, const PathArgs& a, int grid, hipStream_t stream) {
 }
 
 // Every family on the spec's normals and the unfolded recurrence (or no normals: the bootstrap), KT = 1 or 8, compounding LG
-// (the rebalancing, Student-t, cash-flow and overlay kernels compound simply and take no LG).
+// (the rebalancing, Student-t, GARCH, cash-flow and overlay kernels compound simply and take no LG).
 template <int KT, bool LG>
 static void go(const PathKernel& k, const PathArgs& a, int grid, hipStream_t stream) {
   switch (k.family) {
     case FAM_PLAIN:
-      if (k.stt) MCP_GO((mc_paths_t_kernel<MCP_NB, KT, 1>), PathArgsT);
+      if (k.gv) MCP_GO((mc_paths_g_kernel<MCP_NB, KT, 1>), PathArgsG);
+      else if (k.stt) MCP_GO((mc_paths_t_kernel<MCP_NB, KT, 1>), PathArgsT);
       else if (k.boot && k.blds) MCP_GO((mc_paths_boot_kernel<MCP_NB, KT, 1, LG, true>), PathArgsBT);
       else if (k.boot) MCP_GO((mc_paths_boot_kernel<MCP_NB, KT, 1, LG, false>), PathArgsBT);
       else MCP_GO((mc_paths_kernel<MCP_NB, KT, 1, false, false, LG>), PathArgs);
       break;
     case FAM_DD:
-      if (k.stt) MCP_GO((mc_paths_t_dd_kernel<MCP_NB, KT, 1>), PathArgsTDD);
+      if (k.gv) MCP_GO((mc_paths_g_dd_kernel<MCP_NB, KT, 1>), PathArgsGDD);
+      else if (k.stt) MCP_GO((mc_paths_t_dd_kernel<MCP_NB, KT, 1>), PathArgsTDD);
       else MCP_GO((mc_paths_dd_kernel<MCP_NB, KT, 1, LG>), PathArgsDD);
       break;
     case FAM_HZ:
-      if (k.stt) MCP_GO((mc_paths_t_hz_kernel<MCP_NB, KT, 1>), PathArgsTHZ);
+      if (k.gv) MCP_GO((mc_paths_g_hz_kernel<MCP_NB, KT, 1>), PathArgsGHZ);
+      else if (k.stt) MCP_GO((mc_paths_t_hz_kernel<MCP_NB, KT, 1>), PathArgsTHZ);
       else if (k.boot && k.blds) MCP_GO((mc_paths_boot_hz_kernel<MCP_NB, KT, 1, LG, true>), PathArgsBTHZ);
       else if (k.boot) MCP_GO((mc_paths_boot_hz_kernel<MCP_NB, KT, 1, LG, false>), PathArgsBTHZ);
       else MCP_GO((mc_paths_hz_kernel<MCP_NB, KT, 1, LG>), PathArgsHZ);
@@ -73,7 +76,7 @@ static void go(const PathKernel& k, const PathArgs& a, int grid, hipStream_t str
 }
 
 hipError_t MCP_CAT(launch_paths_nb, MCP_NB)(int variant, const PathKernel& k, const PathArgs& a, int grid, hipStream_t stream) {
-  const bool plain = k.family == FAM_PLAIN && !k.boot && !k.stt;
+  const bool plain = k.family == FAM_PLAIN && !k.boot && !k.stt && !k.gv;
   if (k.family < FAM_PLAIN || k.family > FAM_OV || (!plain && variant != 0 && variant != VAR_KT8)) return hipErrorInvalidValue;
   switch (variant) {
     case 0: k.logc ? go<1, true>(k, a, grid, stream) : go<1, false>(k, a, grid, stream); break;

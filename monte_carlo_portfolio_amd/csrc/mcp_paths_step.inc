@@ -5,7 +5,8 @@
 // chi blocks first (only s stays live while the asset normals are formed), then every asset normal scaled by s as it leaves
 // block_normals (SPEC.md 2.2 / 4.6).  CF: the flow c_s after the update, ruin absorbing (SPEC.md 4.7).  OV: between the row pair's
 // returns and the weight dot, the return of every asset that owns option rows is replaced by its rows' return at the asset's price
-// level (SPEC.md 4.8); whether an asset owns rows is wave-uniform, a scalar branch.  In scope: everything mcp_paths_body.inc declares before its step loops, and t.
+// level (SPEC.md 4.8); whether an asset owns rows is wave-uniform, a scalar branch.  GV: s is replaced by u = s sqrt(h) (nu = 0: u =
+// sqrt(h), the chi blocks skipped by a scalar branch) and h is updated from the scaled normals (SPEC.md 4.9).  In scope: everything mcp_paths_body.inc declares before its step loops, and t.
       float rho[PPT][KT];
       if constexpr (BOOT) {
         // SPEC.md 2.1 / 4.4: one Philox block on counter (t, 1, p_lo, p_hi); j_t = mulhi(x0, R) on a restart (t = 0 or
@@ -59,11 +60,16 @@
       if constexpr (LDS_MU) asm volatile("" : "+v"(par_off));
       const float* s_par = s_par0 + par_off;
       float z[PPT][N4];
-      float st_s[PPT];                                 // STT: the step's scale s of SPEC.md 2.2
+      float st_s[PPT];                                 // STT: the step's scale s of SPEC.md 2.2 (GV: u of SPEC.md 4.9)
       if constexpr (STT) {
         // SPEC.md 2.2: chi = sum_k g_k^2 (fma, k = 4q + m ascending) over nt = ceil(nu/4) blocks on counter (t nt + q, 2, p_lo,
         // p_hi); the surplus words of the last block are masked to +0, which leaves chi unchanged.  nu is wave-uniform.
         const int dof = student_dof(a);
+        if constexpr (GV) {                            // SPEC.md 4.9: nu = 0 is the Gaussian call, u = sigma = fl32(1 sigma)
+#pragma unroll
+          for (int e = 0; e < PPT; e++) st_s[e] = 1.0f;
+        }
+        if (!GV || dof != 0) {                         // wave-uniform
         const int nt = (dof + 3) >> 2;
         float chi[PPT];
 #pragma unroll
@@ -89,6 +95,11 @@
         const float num = (float)(dof - 2);
 #pragma unroll
         for (int e = 0; e < PPT; e++) st_s[e] = sqrtf(num / fmaxf(chi[e], 0x1p-126f));
+        }
+        if constexpr (GV) {                            // u = fl32(s sigma), sigma = sqrt(h): IEEE, correctly rounded
+#pragma unroll
+          for (int e = 0; e < PPT; e++) st_s[e] = st_s[e] * sqrtf(gh[e]);
+        }
       }
 #pragma unroll
       for (int q = 0; q < NB; q++) {
@@ -102,6 +113,23 @@
 #pragma unroll
             for (int m = 0; m < 4; m++) z[e][m * NB + q] = st_s[e] * z[e][m * NB + q];
           }
+        }
+      }
+      if constexpr (GV) {
+        // SPEC.md 4.9: q = sum_j z'_j^2 (fma, j ascending over the N assets; the padding normals j >= N masked to +0, which leaves
+        // q unchanged), h = fminf(fma(b, h, fma(a_N, q, omega)), 2^40).  The constants are wave-uniform scalar loads.
+        const cgarch_p gk = garch_args(a);
+        const int n_live = gk->n_assets;
+        const float g_an = gk->a_n, g_b = gk->b, g_om = gk->omega;
+#pragma unroll
+        for (int e = 0; e < PPT; e++) {
+          float q = 0.0f;
+#pragma unroll
+          for (int j = 0; j < N4; j++) {
+            const float zj = (j < N4 - 3 || j < n_live) ? z[e][j] : 0.0f;     // N > N4 - 4: only the last three can be padding
+            q = fma32(zj, zj, q);
+          }
+          gh[e] = fminf(fma32(g_b, gh[e], fma32(g_an, q, g_om)), 0x1p40f);
         }
       }
       if constexpr (FOLD) {

@@ -71,6 +71,7 @@ struct PathKernel {
   int family;
   bool logc, boot, blds, stt;
   bool dd = false;                      // FAM_OV only: the overlay kernel that also tracks the drawdown
+  bool gv = false;                      // FAM_PLAIN, FAM_DD, FAM_HZ: the GARCH kernels (PathArgsG, PathArgsGDD, PathArgsGHZ; SPEC.md 4.9)
 };
 
 // mcp_paths_inst.hip (one translation unit per NB): returns hipErrorInvalidValue for a kernel that is not instantiated.

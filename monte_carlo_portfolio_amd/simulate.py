@@ -65,8 +65,8 @@ class Context:
 
     def _call(self, prm: _ffi.McpParams, W, seed: int, path_begin: int, n_paths: int, store: bool, mu=None, chol=None, rows=None,
               block: float = 1.0, dof=None, period=None, cost: float = 0.0, drawdown: bool = False, horizons=None, levels=(),
-              flows=None, target=None, overlay=None):
-        """The one library call behind every simulate_* method: an option overlay (overlay: the triple of check_overlay), cash flows (flows, target), Student-t draws (dof), rebalancing
+              flows=None, target=None, overlay=None, garch=None):
+        """The one library call behind every simulate_* method: GARCH volatility (garch: the (alpha, beta, h0) of check_garch), an option overlay (overlay: the triple of check_overlay), cash flows (flows, target), Student-t draws (dof), rebalancing
         (period, cost), bootstrap rows (rows, block) or Gaussian draws (mu, chol), with the drawdown or horizons.  Allocates the
         outputs that were asked for and passes NULL for the rest -> _Outputs, None where not asked for (terminal, qd,
         horizon_terminal: with `store` only; counts, hz_counts: with `flows` only)."""
@@ -90,7 +90,12 @@ class Context:
         hz_in = (H, ptr(steps) if H else None, L, ptr(lv) if L else None)
         hz_out = (ptr(hz_term), ptr(hz_stats), ptr(bands) if L else None)
         bt = _ffi.make_bootstrap(rows, block) if rows is not None else None
-        if overlay is not None:
+        if garch is not None:
+            st = _ffi.McpStudentT(int(dof), 0) if dof is not None else None
+            gv = _ffi.McpGarch(float(garch[0]), float(garch[1]), float(garch[2]), 0)
+            rc = lib.mcp_simulate_garch(self._h, prm_p, ctypes.byref(gv), ctypes.byref(st) if st is not None else None, ptr(mu),
+                                        ptr(chol), ptr(W), *walk, *hz_in, ptr(term), ptr(stats), ptr(raw), ptr(dd_stats), *hz_out)
+        elif overlay is not None:
             st = _ffi.McpStudentT(int(dof), 0) if dof is not None else None
             rc = lib.mcp_simulate_overlay(self._h, prm_p, ctypes.byref(_ffi.make_overlay(*overlay)), ptr(mu), ptr(chol),
                                           ctypes.byref(st) if st is not None else None, ptr(W), *walk, *hz_in, ptr(term), ptr(stats),
@@ -173,6 +178,15 @@ class Context:
         terminal is [K, n_paths], qd the binary32 drawdown q [K, n_paths], horizon_terminal [H, K, n_paths]."""
         return tuple(self._call(prm, W, seed, path_begin, n_paths, store, mu=mu, chol=chol, dof=dof, drawdown=drawdown,
                                 horizons=horizons, levels=levels))[:7]
+
+    def simulate_garch(self, prm: _ffi.McpParams, garch, mu, chol, W, seed: int, path_begin: int, n_paths: int, store: bool,
+                       dof=None, drawdown: bool = False, horizons=None, levels=()):
+        """simulate() / simulate_drawdown() / simulate_horizons() / simulate_student_t() with the GARCH(1,1) variance ratio of
+        SPEC.md 4.9 scaling every step's normals: `garch` is (alpha, beta, h0) (SPEC.md 4.9 / 5.8; include/mcport.h,
+        mcp_simulate_garch; simple compounding only); dof=None: Gaussian draws -> _Outputs; the entries of the blocks not asked
+        for are None."""
+        return self._call(prm, W, seed, path_begin, n_paths, store, mu=mu, chol=chol, dof=dof, drawdown=drawdown, horizons=horizons,
+                          levels=levels, garch=garch)
 
     def simulate_cashflow(self, prm: _ffi.McpParams, flows, W, seed: int, path_begin: int, n_paths: int, store: bool, mu=None,
                           chol=None, rows=None, block: float = 1.0, dof=None, target=None, horizons=None, levels=()):
@@ -314,6 +328,37 @@ def check_dof(dof):
     return int(dof)
 
 
+def check_garch(garch):
+    """SPEC.md 4.9 argument rules -> None (no GARCH) or the floats (alpha, beta, h0), h0 = 1 for a pair; ValueError otherwise (not
+    a sequence of 2 or 3 numbers, a bool or a string among them, a non-finite value, alpha < 0, beta < 0, fl32(alpha) + fl32(beta)
+    >= 1, fl32(h0) <= 0)."""
+    if garch is None:
+        return None
+    msg = f"garch must be (alpha, beta) or (alpha, beta, h0), got {garch!r}"
+    if isinstance(garch, (str, bytes)) or not hasattr(garch, "__len__") or len(garch) not in (2, 3):
+        raise ValueError(msg)
+    vals = []
+    for v in garch:
+        if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, float, np.integer, np.floating)):
+            raise ValueError(msg)
+        if not np.isfinite(v):
+            raise ValueError(f"garch values must be finite, got {garch!r}")
+        vals.append(float(v))
+    if len(vals) == 2:
+        vals.append(1.0)
+    with np.errstate(over="ignore"):
+        a, b, g = (np.float32(v) for v in vals)
+    if not (np.isfinite(a) and np.isfinite(b) and np.isfinite(g)):
+        raise ValueError(f"garch values must be finite in binary32, got {garch!r}")
+    if not (a >= 0 and b >= 0):
+        raise ValueError(f"garch alpha and beta must be >= 0, got {garch!r}")
+    if not float(a) + float(b) < 1.0 or not np.float32(1.0 - float(a) - float(b)) > 0:
+        raise ValueError(f"garch alpha + beta must be < 1 in binary32, got {garch!r}")
+    if not g > 0:
+        raise ValueError(f"garch h0 must be > 0 in binary32, got {garch!r}")
+    return tuple(vals)
+
+
 def check_rebalance(rebalance, rebalance_cost):
     """SPEC.md 4.5 argument rules -> (period, cost): period None (constant weights, no rebalancing), 0 (rebalance="never": bought
     and held) or the int k >= 1 of rebalance=k (traded back to the weights every k steps); cost in [0, 1).  ValueError otherwise."""
@@ -424,7 +469,7 @@ def simulate_paths(mu, cov, weights, n_steps=252, n_paths=10_000, seed=0, v0=1.0
                    rf=0.0, alpha=0.95, devices=None, store=False, path_begin=0, chol=None,
                    native_math=False, as_array=False, fold=False, shard="auto", context=None, drawdown=False,
                    horizons=None, bands=(), rebalance=None, rebalance_cost=0.0, dof=None, cashflow=None, target=None,
-                   overlay=None, spot=None):
+                   overlay=None, spot=None, garch=None):
     """Simulate `n_paths` correlated return paths and reduce them to risk statistics.
 
     mu [N], cov [N,N] are per-step mean and covariance (the reference's `mean_returns`, `cov_matrix`
@@ -482,7 +527,21 @@ def simulate_paths(mu, cov, weights, n_steps=252, n_paths=10_000, seed=0, v0=1.0
     in the reference.  The result has the shape of the same call without it (drawdown, horizons / bands, dof, store and as_array
     all combine; pivots of SPEC.md 5.7); an overlay without rows gives the plain call's values bit for bit.  Not with rebalance,
     cashflow, fold, native_math or compounding="log" (ValueError).
+
+    garch=None (default): every step's covariance is `cov`.  garch=(alpha, beta) or (alpha, beta, h0): volatility clustering, a
+    scalar GARCH(1,1) on the covariance (SPEC.md 4.9): step t draws with the covariance h_t cov, one variance ratio h per path,
+    h_{t+1} = (1 - alpha - beta) + alpha (eps_t' cov^-1 eps_t / N) + beta h_t from h0 (default 1: the long-run level; h0 != 1
+    starts the paths "from today's volatility", E[h_t] = 1 + (alpha + beta)^t (h0 - 1)).  The conditional mean of every step is mu
+    (pivots of SPEC.md 5.8) and the asset normals are the Gaussian call's own; alpha = 0, h0 = 1 is the call without it bit for
+    bit.  fit_garch(returns)[:3] estimates the triple from return rows.  The result has the shape of the same call without it
+    (drawdown, horizons / bands, dof, store and as_array all combine).  Not with rebalance, cashflow, overlay, fold, native_math or
+    compounding="log" (ValueError).
     """
+    gv = check_garch(garch)
+    if gv is not None and (rebalance is not None or cashflow is not None or overlay is not None or fold or native_math
+                           or compounding == "log"):
+        raise ValueError("garch needs simple compounding, the spec's normals, the unfolded recurrence and constant weights: not with "
+                         "rebalance, cashflow, overlay, fold, native_math or compounding='log'")
     ov = check_overlay(overlay, spot, len(np.atleast_1d(np.asarray(mu))))
     if ov is not None and (rebalance is not None or cashflow is not None or fold or native_math or compounding == "log"):
         raise ValueError("overlay needs simple compounding, the spec's normals, the unfolded recurrence and constant weights: not "
@@ -506,7 +565,7 @@ def simulate_paths(mu, cov, weights, n_steps=252, n_paths=10_000, seed=0, v0=1.0
     mu32, L, W = prepare_inputs(mu, cov, weights, chol)
     prm, ctx = _setup(mu32.shape[0], n_steps, W.shape[0], compounding, v0, alpha, rf, native_math, fold, devices, shard, context)
     out = ctx._call(prm, W, int(seed), int(path_begin), int(n_paths), store, mu=mu32, chol=L, dof=dof, period=period, cost=cost,
-                    drawdown=drawdown, horizons=steps, levels=levels, flows=flows, target=target, overlay=ov)
+                    drawdown=drawdown, horizons=steps, levels=levels, flows=flows, target=target, overlay=ov, garch=gv)
     return _result(out, np.asarray(weights).ndim == 1, store, as_array, steps, levels, compounding, flows, target)
 
 
@@ -627,6 +686,10 @@ def simulate_bootstrap(returns, weights, n_steps=252, n_paths=10_000, block=1.0,
         raise ValueError("simulate_bootstrap does not take overlay: the rows are observed returns with no price level to strike an "
                          "option at -- apply the strategy to the returns matrix first (options.calc_options_series per asset, as "
                          "the reference does), or call simulate_paths(overlay=...)")
+    if unsupported.get("garch") is not None:
+        raise ValueError("simulate_bootstrap does not take garch: the rows carry their own dynamics -- a mean block length block > 1 "
+                         "keeps the volatility regimes of the observed rows; GARCH is a parametric model, call "
+                         "simulate_paths(garch=...)")
     if unsupported:
         raise ValueError(f"simulate_bootstrap does not take {sorted(unsupported)} (no normals: no fold / native_math / dof -- "
                          "Student-t draws are a parametric model, call simulate_paths(dof=...); drawdown on bootstrap paths is "
