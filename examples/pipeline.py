@@ -47,6 +47,12 @@ def main(paths, resample_rule="M", user_rf=3.0, investment=10000.0, seed=12345, 
           f"VaR95 {sim['var']:+.4f}  CVaR95 {sim['cvar']:+.4f}  Sharpe {sim['sharpe']:.4f}")
     dd = sim["drawdown"]                  # max drawdown of every path before the horizon (SPEC.md 4.2 / 5.1)
     print(f"  max drawdown: mean {dd['mean']:+.4f}  DaR95 {dd['dar']:+.4f}  CDaR95 {dd['cdar']:+.4f}  worst {dd['worst']:+.4f}")
+    # which holding that risk comes from (SPEC.md 4.10 / 5.9): the same paths walked a second time, every asset's part of the CVaR
+    # and of the volatility -- the risk pie next to the dollar pie of the optimum
+    att = mcp.simulate_paths(mu_step, cov_step, w, n_steps=af, n_paths=n_paths, seed=seed, v0=investment, rf=user_rf / 100,
+                             attribution=True)["attribution"]
+    for name, wi, cs, vs in zip(names, w, att["cvar_share"], att["vol_share"]):
+        print(f"  risk attribution {name}: weight {wi * 100:6.2f} %  CVaR share {cs * 100:6.2f} %  volatility share {vs * 100:6.2f} %")
     fan = mcp.simulate_paths(mu_step, cov_step, w, n_steps=6, n_paths=n_paths, seed=seed, v0=investment, horizons=[1, 3, 6],
                              bands=(2.5, 50.0, 97.5))["horizons"]        # values at intermediate horizons (SPEC.md 4.3 / 5.2)
     for h, b in zip(fan["steps"], fan["bands"]):

@@ -96,6 +96,13 @@ with tab_sweep:                                               # app.py:655-783
     st.write({k: sim[k] for k in ("n", "mean", "std", "sharpe", "var", "cvar", "min", "max")})
     st.write({"max drawdown: mean": sim["drawdown"]["mean"], "DaR": sim["drawdown"]["dar"], "CDaR": sim["drawdown"]["cdar"],
               "worst": sim["drawdown"]["worst"]})
+    # the risk pie next to the dollar pie of the optimum (SPEC.md 4.10 / 5.9): every asset's share of the simulated CVaR and volatility
+    att = mcp.simulate_paths(mu_step, cov_step, w, n_steps=annual_factor, n_paths=n_paths, seed=12345,
+                             v0=state["investment_amount"], rf=user_rf / 100.0, attribution=True)["attribution"]
+    st.subheader("where the risk of the max-Sharpe weights comes from (component CVaR and volatility)")
+    st.write({"risk attribution": {"weight %": dict(zip(names, np.round(np.asarray(w) * 100, 2).tolist())),
+                                   "CVaR share %": dict(zip(names, np.round(att["cvar_share"] * 100, 2).tolist())),
+                                   "volatility share %": dict(zip(names, np.round(att["vol_share"] * 100, 2).tolist()))}})
     # the same weights on paths resampled from the observed rows (stationary bootstrap, SPEC.md 2.1 / 4.4), next to the normal
     # model: hedged (option-overlay) rows keep their floor and cap here
     boot = mcp.simulate_bootstrap(returns_df, w, n_steps=annual_factor, n_paths=n_paths, block=3.0, seed=12345,

@@ -29,7 +29,8 @@ extern "C" {
                                     + mcp_simulate_rebalanced, mcp_rebalance_pivots (additive, detected by symbol);
                                     + mcp_simulate_student_t (additive, detected by symbol);
                                     + mcp_simulate_overlay, mcp_overlay_pivots (additive, detected by symbol);
-                                    + mcp_simulate_garch (additive, detected by symbol) */
+                                    + mcp_simulate_garch (additive, detected by symbol);
+                                    + mcp_simulate_attribution (additive, detected by symbol) */
 #define MCP_MAX_ASSETS 64        /* thread-per-path kernels are instantiated for N4 = 4..64 */
 #define MCP_SELECT_BINS 2048     /* radix-select digit: 11 + 11 + 10 bits */
 #define MCP_MAX_HORIZONS 64      /* mcp_simulate_horizons: horizon steps per call */
@@ -37,6 +38,7 @@ extern "C" {
 #define MCP_MAX_BOOT_ROWS (1 << 20) /* mcp_simulate_bootstrap: observed return rows per call */
 #define MCP_MAX_OVERLAY_ROWS 8   /* mcp_simulate_overlay: option rows per asset */
 #define MCP_MAX_T_DOF 32         /* mcp_simulate_student_t: degrees of freedom in [3, MCP_MAX_T_DOF] */
+#define MCP_MAX_ATTR_PORTFOLIOS 16 /* mcp_simulate_attribution: portfolios per call */
 
 enum {
     MCP_OK = 0,
@@ -318,6 +320,36 @@ int mcp_simulate_garch(mcp_ctx *ctx, const mcp_params *prm, const mcp_garch *g,
                        float *horizon_out,         /* NULL or host [H*K*n_paths], row h*K + k */
                        mcp_stats *hz_stats_out,    /* [H*K], NULL iff n_horizons == 0 */
                        double *bands_out);         /* [H*K*L], NULL iff n_levels == 0 */
+
+/* Per-asset risk attribution (SPEC.md 4.10 / 5.9): one record per (portfolio k, asset i).  A_ki is the money asset i made or lost
+ * for portfolio k along a path, A_ki = sum_t V_{t-1} w_ki r_i (binary32, in the kernel); sum_i A_ki = V_T - v0 up to rounding.  sum,
+ * sum_tail and sum_xc are the binary64 sums over the paths of A_ki, of A_ki over the tail {x <= VaR} and of A_ki (x - pivot); mean, cvar
+ * and vol are the asset's parts of the portfolio's mean, CVaR and standard deviation (Euler: the parts add up to the whole). */
+typedef struct {
+    double mean;            /* sum / (v0 n) */
+    double cvar;            /* sum_tail / (v0 n_tail): component CVaR */
+    double vol;             /* cov(A_ki / v0, x) / std, 0 if std == 0: component volatility */
+    double sum, sum_tail, sum_xc;
+} mcp_attr;
+
+/* mcp_simulate (g and st NULL), mcp_simulate_student_t (st) or mcp_simulate_garch (g, st or NULL) without drawdown or horizons, then
+ * a second walk of the same paths that carries every asset's contribution next to the value (one extra walk per portfolio; nothing
+ * per step is stored).  terminal_out and stats_out are bit for bit those of the call without attribution.  attr_out [K][N] and
+ * attr_counts_out [K][2] = {n, n_tail} as this walk counted them (equal to the statistics' own); contrib_out, when given, receives
+ * the binary32 A_ki as [K][N][n_paths].  Path-sharded contexts run the second walk on every shard; the shards' sums are added in
+ * shard order and the results are run-to-run deterministic.  MCP_E_UNSUPPORTED: log compounding, MCP_FLAG_FOLD, MCP_FLAG_NATIVE_MATH,
+ * MCP_FLAG_SHARD_PORTFOLIOS, K > MCP_MAX_ATTR_PORTFOLIOS.  MCP_E_ARG (before any device is touched): the rules of g and st, NULL
+ * attr_out or attr_counts_out. */
+int mcp_simulate_attribution(mcp_ctx *ctx, const mcp_params *prm,
+                             const mcp_garch *g,                 /* NULL: no GARCH */
+                             const mcp_student_t *st,            /* NULL: Gaussian draws */
+                             const float *mu, const float *chol, const float *W,
+                             uint64_t seed, uint64_t path_begin, uint64_t n_paths,
+                             float *terminal_out,        /* NULL or host [K*n_paths] */
+                             mcp_stats *stats_out,       /* [K] */
+                             float *contrib_out,         /* NULL or host [K*N*n_paths], row k*N + i */
+                             mcp_attr *attr_out,         /* [K*N] */
+                             uint64_t *attr_counts_out); /* [K][2] */
 
 /* Contributions, withdrawals and ruin (SPEC.md 4.7 / 5.6).  flows: the schedule c_1 .. c_T, n_flows == prm->n_steps finite
  * binary32 values in the units of v0 (positive: paid in, negative: taken out), the same for every portfolio; flow c_s arrives

@@ -25,6 +25,7 @@ MCP_MAX_LEVELS = 16
 MCP_MAX_BOOT_ROWS = 1 << 20
 MCP_MAX_T_DOF = 32
 MCP_MAX_OVERLAY_ROWS = 8
+MCP_MAX_ATTR_PORTFOLIOS = 16
 MCP_OVERLAY_LINEAR, MCP_OVERLAY_CALL, MCP_OVERLAY_PUT = 0, 1, 2
 MCP_COMPOUND = {"simple": 0, "log": 1}
 MCP_FLAG_NATIVE_MATH = 1
@@ -99,6 +100,11 @@ STATS_DTYPE = np.dtype([
 ])
 assert STATS_DTYPE.itemsize == ctypes.sizeof(McpStats)
 
+# one mcp_attr: an asset's parts of a portfolio's mean, CVaR and standard deviation, and the sums behind them (SPEC.md 5.9)
+ATTR_DTYPE = np.dtype([("mean", np.float64), ("cvar", np.float64), ("vol", np.float64), ("sum", np.float64), ("sum_tail", np.float64),
+                       ("sum_xc", np.float64)])
+assert ATTR_DTYPE.itemsize == 48
+
 RECORD_DTYPE = np.dtype([("n", np.float64), ("sum", np.float64), ("sumsq", np.float64), ("min", np.float64),
                          ("max", np.float64), ("below", np.float64), ("pivot", np.float64), ("pad", np.float64)])
 # one moment partial of the path kernels' epilogue (csrc/mcp_stats_kernels.h: MomentPartial)
@@ -152,6 +158,8 @@ SIGNATURES = {
                                       _vp, _vp, _vp, _vp, _vp, _vp]),
     "mcp_simulate_garch": (_int, [_vp, _PP, ctypes.POINTER(McpGarch), ctypes.POINTER(McpStudentT), _vp, _vp, _vp, _u64, _u64, _u64, _int,
                                   _vp, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "mcp_simulate_attribution": (_int, [_vp, _PP, ctypes.POINTER(McpGarch), ctypes.POINTER(McpStudentT), _vp, _vp, _vp, _u64, _u64, _u64,
+                                        _vp, _vp, _vp, _vp, _vp]),
     "mcp_simulate_cashflow": (_int, [_vp, _PP, ctypes.POINTER(McpCashflow), _vp, _vp, ctypes.POINTER(McpBootstrap),
                                      ctypes.POINTER(McpStudentT), _vp, _u64, _u64, _u64, _int, _vp, _int, _vp, _vp, _vp, _vp, _vp, _vp,
                                      _vp, _vp]),

@@ -363,6 +363,10 @@ struct Request {
   double* bands_out = nullptr;          // [H*K*L]
   uint64_t* counts_out = nullptr;       // cash flows: [K][2] {n_ruined, n_short} (SPEC.md 5.6)
   uint64_t* hz_counts_out = nullptr;    // [H*K][2]
+  bool attr = false;                    // SPEC.md 4.10 / 5.9: the second walk that attributes the risk to the assets
+  float* contrib_out = nullptr;         // NULL or host [K][N][n]
+  mcp_attr* attr_out = nullptr;         // [K][N]
+  uint64_t* attr_counts_out = nullptr;  // [K][2] {n, n_tail}
 };
 
 Request host_request(Source src, const float* mu, const float* chol, const float* W, float* terminal_out, mcp_stats* stats_out) {
@@ -404,6 +408,11 @@ struct Launch {
   const char* d_overlay = nullptr;      // overlay: [rows][row_begin N4 + 1][spot N4] (overlay_pack)
   int ov_n = 0, ov_n4 = 0;              // overlay: N and N4 of that table
   int n_assets = 0;                     // GARCH: N (set by launch_paths_impl)
+  bool attr = false;                    // the attribution walk (SPEC.md 4.10): FAM_AT instead of the request's own family
+  const double* d_var = nullptr;        // attribution: [K] VaRs
+  double* d_attr_partials = nullptr;    // attribution: [K][path_grid(n_paths)][attr_record_len(N4)]
+  float* d_contrib = nullptr;           // attribution: NULL or [K][N][contrib_stride]
+  uint64_t contrib_stride = 0;
   void* d_partials = nullptr;
   void* d_hist = nullptr;
   hipStream_t stream = nullptr;
@@ -454,6 +463,18 @@ int check_request(const mcp_params* prm, const Request& rq, uint64_t n_paths, co
     if (who) return fail(MCP_E_UNSUPPORTED, "%s (no MCP_FLAG_FOLD / MCP_FLAG_NATIVE_MATH)", who);
     if ((prm->flags & MCP_FLAG_FOLD) && (prm->n_portfolios != 1 || (prm->flags & MCP_FLAG_NATIVE_MATH)))
       return fail(MCP_E_UNSUPPORTED, "MCP_FLAG_FOLD needs one portfolio and the spec's normals");
+  }
+  if (rq.attr) {                                               // SPEC.md 4.10: constant weights, simple compounding, the spec's step
+    if (logc) return fail(MCP_E_UNSUPPORTED, "the attribution compounds simply (no log compounding)");
+    if (prm->flags & (MCP_FLAG_FOLD | MCP_FLAG_NATIVE_MATH | MCP_FLAG_SHARD_PORTFOLIOS))
+      return fail(MCP_E_UNSUPPORTED, "the attribution runs on the spec's normals, the unfolded recurrence and path shards (no MCP_FLAG_FOLD / "
+                                     "MCP_FLAG_NATIVE_MATH / MCP_FLAG_SHARD_PORTFOLIOS)");
+    if (rq.src == SRC_BOOT || rq.rebalanced || rq.cash || rq.overlay)
+      return fail(MCP_E_UNSUPPORTED, "the attribution is not combined with bootstrap rows, rebalancing, cash flows or the overlay");
+    if (rq.dd || rq.hz) return fail(MCP_E_UNSUPPORTED, "the attribution is not combined with the drawdown or horizons");
+    if (prm->n_portfolios > MCP_MAX_ATTR_PORTFOLIOS)
+      return fail(MCP_E_UNSUPPORTED, "the attribution takes at most %d portfolios, got %d", MCP_MAX_ATTR_PORTFOLIOS, prm->n_portfolios);
+    if (!ln && (!rq.attr_out || !rq.attr_counts_out)) return fail(MCP_E_ARG, "attr_out or attr_counts_out is NULL");
   }
   if (rq.dd && rq.hz) return fail(MCP_E_UNSUPPORTED, "horizons and the drawdown are not tracked in one walk");
   if (rq.dd && (rq.src == SRC_BOOT || rq.rebalanced))
@@ -654,6 +675,14 @@ struct Shard {
     DevBuf<unsigned long long> counts;     // [(1 + H) K tile][2] {n_ruined, n_short}: the terminal rows, then the horizon rows
     HostBuf<unsigned long long> h_counts;  // pinned copy of counts
   } cf;
+  struct {                                 // attribution calls (SPEC.md 4.10 / 5.9)
+    DevBuf<double> in;                     // [2][K]: the VaRs, then the pivots
+    HostBuf<double> h_in;                  // pinned staging of `in`
+    DevBuf<double> partials;               // [K][path_grid(paths)][attr_record_len(N4)]: one record per workgroup
+    DevBuf<double> records;                // [K][attr_record_len(N4)]: the workgroups' records summed in block order
+    HostBuf<double> h_records;             // pinned copy of records
+    DevBuf<float> contrib;                 // [K][N][paths] A_ki, when the caller asks for them
+  } at;
 };
 
 int grow_dev(void** p, size_t* cap, size_t need, hipStream_t zero_on = nullptr, bool zero = false) {
@@ -923,6 +952,20 @@ static void garch_block(mcp::StudentArgs& st, mcp::GarchArgs& gv, const Request&
 static void fill(mcp::PathArgsG& x, const Request& rq, const Launch& ln) { garch_block(x.st, x.gv, rq, ln.n_assets); }
 static void fill(mcp::PathArgsGDD& x, const Request& rq, const Launch& ln) { fill((mcp::PathArgsDD&)x, rq, ln); garch_block(x.st, x.gv, rq, ln.n_assets); }
 static void fill(mcp::PathArgsGHZ& x, const Request& rq, const Launch& ln) { fill_hz(x, rq, ln); garch_block(x.st, x.gv, rq, ln.n_assets); }
+// The attribution walk draws as the GARCH kernel does: without GARCH on alpha = beta = 0, h0 = 1, which is the Gaussian or Student-t
+// call bit for bit (SPEC.md 4.9).
+static void fill(mcp::PathArgsAT& x, const Request& rq, const Launch& ln) {
+  static const mcp_garch none = {0.0, 0.0, 1.0, 0};
+  Request rg = rq;
+  if (!rq.garch) rg.gv = &none;
+  garch_block(x.st, x.gv, rg, ln.n_assets);
+  x.at.var = ln.d_var;
+  x.at.partials = ln.d_attr_partials;
+  x.at.contrib = ln.d_contrib;
+  x.at.contrib_stride = ln.contrib_stride;
+  x.at.n_assets = ln.n_assets;
+  x.at.pad = 0;
+}
 static void fill(mcp::PathArgsCF& x, const Request& rq, const Launch& ln) {
   fill_hz(x, rq, ln);
   x.bt = boot_block(rq, ln);
@@ -986,7 +1029,7 @@ static int launch_paths_impl(const mcp_params* prm, const Request& rq, const Lau
   DeviceGuard guard(dev);                 // the stream may belong to another device than the thread's current one
   if (guard.err != hipSuccess) return fail(MCP_E_HIP, "hipSetDevice(%d): %s", dev, hipGetErrorString(guard.err));
   if (int rc = device_tables(dev, ln.stream, &tables)) return rc;
-  const bool sweep = plain && uses_sweep(K);
+  const bool sweep = plain && !ln.attr && uses_sweep(K);
   a.tables = tables;
   a.packed = ln.d_packed;
   a.terminal = ln.d_terminal;
@@ -1029,6 +1072,17 @@ static int launch_paths_impl(const mcp_params* prm, const Request& rq, const Lau
   if (!plain && ln.d_partials && a.slots > (uint64_t)mcp::path_grid(ln.n_paths))
     HIP_TRY(mcp::launch_pass0(*prm, K, ln.d_terminal, ln.stride, 0, nullptr, a.slots, (mcp::MomentPartial*)ln.d_partials,
                               (unsigned long long*)ln.d_hist, ln.stream));
+  if (ln.attr) {                               // SPEC.md 4.10: one portfolio per pass, no terminal store, its own epilogue
+    mcp::PathKernel ka;
+    ka.family = mcp::FAM_AT;
+    ka.logc = ka.boot = ka.blds = false;
+    ka.stt = ka.gv = true;
+    a.partials = nullptr;
+    a.hist = nullptr;
+    Launch la = ln;
+    la.n_assets = prm->n_assets;
+    return launch_passes<mcp::PathArgsAT>(a, rq, la, 0, ka, nb);
+  }
   mcp::PathKernel k;
   k.family = rq.overlay ? mcp::FAM_OV : rq.cash ? mcp::FAM_CF : rq.rebalanced ? mcp::FAM_REB : rq.dd ? mcp::FAM_DD : rq.hz ? mcp::FAM_HZ : mcp::FAM_PLAIN;
   k.logc = prm->compounding == MCP_COMPOUND_LOG;
@@ -1289,6 +1343,12 @@ static void free_shard(Shard& sh) {
   release(sh.overlay);
   release(sh.cf.counts);
   release(sh.cf.h_counts);
+  release(sh.at.in);
+  release(sh.at.h_in);
+  release(sh.at.partials);
+  release(sh.at.records);
+  release(sh.at.h_records);
+  release(sh.at.contrib);
 }
 
 int mcp_ctx_create_multi(const int* devices, int ndev, mcp_ctx** out) {
@@ -1761,6 +1821,70 @@ int tile_portfolios(size_t budget, uint64_t n_paths, int K, size_t bytes_per_pat
   return fit >= 1 ? (int)fit : 1;
 }
 
+// SPEC.md 4.10 / 5.9: the second walk of an attribution call, after the call's statistics are in rq.stats_out.  Every shard walks
+// its path range again, one portfolio per pass, and leaves one record of sums per workgroup; a small kernel adds them in block order,
+// the host adds the shards' records in shard order and divides once.
+int run_attribution(mcp_ctx* c, const mcp_params* prm, const Request& rq, uint64_t seed, uint64_t path_begin, uint64_t n_paths,
+                    const std::vector<Job>& jobs) {
+  const size_t S = c->sh.size();
+  const int N = prm->n_assets, K = prm->n_portfolios, n4 = n4_of(N), RL = mcp::attr_record_len(n4);
+  const size_t plen = mcp_packed_len(N, K);
+  int rc;
+  for (size_t s = 0; s < S; s++) {
+    const Job& j = jobs[s];
+    if (!j.pn) continue;
+    Shard& sh = c->sh[s];
+    HIP_TRY(hipSetDevice(sh.device));
+    const size_t grid = (size_t)mcp::path_grid(j.pn);
+    if ((rc = grow(sh.packed, plen)) || (rc = grow(sh.h_packed, plen)) || (rc = grow(sh.at.in, 2 * (size_t)K)) ||
+        (rc = grow(sh.at.h_in, 2 * (size_t)K)) || (rc = grow(sh.at.partials, (size_t)K * grid * RL)) ||
+        (rc = grow(sh.at.records, (size_t)K * RL)) || (rc = grow(sh.at.h_records, (size_t)K * RL)))
+      return rc;
+    if (rq.contrib_out && (rc = grow(sh.at.contrib, (size_t)K * N * j.pn))) return rc;
+    if ((rc = mcp_pack_params(N, K, rq.mu, rq.chol, rq.W, sh.h_packed.p, plen))) return rc;
+    for (int k = 0; k < K; k++) sh.at.h_in.p[k] = rq.stats_out[k].var;
+    if ((rc = mcp_pivots(prm, rq.mu, rq.chol, rq.W, sh.at.h_in.p + K))) return rc;
+    HIP_TRY(hipMemcpyAsync(sh.packed.p, sh.h_packed.p, plen * sizeof(float), hipMemcpyHostToDevice, sh.stream));
+    HIP_TRY(hipMemcpyAsync(sh.at.in.p, sh.at.h_in.p, 2 * (size_t)K * sizeof(double), hipMemcpyHostToDevice, sh.stream));
+    Launch ln = make_launch(sh.packed.p, sh.at.in.p + K, seed, path_begin + j.p0, j.pn, nullptr, j.pn, nullptr, nullptr, sh.stream);
+    ln.attr = true;
+    ln.d_var = sh.at.in.p;
+    ln.d_attr_partials = sh.at.partials.p;
+    ln.d_contrib = rq.contrib_out ? sh.at.contrib.p : nullptr;
+    ln.contrib_stride = j.pn;
+    if ((rc = launch_paths_impl(prm, rq, ln))) return rc;
+    HIP_TRY(mcp::launch_attr_merge(sh.at.partials.p, K, (int)grid, RL, sh.at.records.p, sh.stream));
+    HIP_TRY(hipMemcpyAsync(sh.at.h_records.p, sh.at.records.p, (size_t)K * RL * sizeof(double), hipMemcpyDeviceToHost, sh.stream));
+    if (rq.contrib_out)                                    // [K N][pn] block -> the [K][N][n_paths] array at column p0
+      HIP_TRY(hipMemcpy2DAsync(rq.contrib_out + j.p0, n_paths * sizeof(float), sh.at.contrib.p, j.pn * sizeof(float), j.pn * sizeof(float),
+                               (size_t)K * N, hipMemcpyDeviceToHost, sh.stream));
+  }
+  for (size_t s = 0; s < S; s++)
+    if (jobs[s].pn) { HIP_TRY(hipSetDevice(c->sh[s].device)); HIP_TRY(hipStreamSynchronize(c->sh[s].stream)); }
+  const double v0d = (double)(float)prm->v0;
+  std::vector<double> rec((size_t)RL);
+  for (int k = 0; k < K; k++) {
+    std::fill(rec.begin(), rec.end(), 0.0);
+    for (size_t s = 0; s < S; s++)                         // shard order
+      if (jobs[s].pn)
+        for (int i = 0; i < RL; i++) rec[i] += c->sh[s].at.h_records.p[(size_t)k * RL + i];
+    const double n = rec[0], n_tail = rec[1], s1 = rec[2], sd = rq.stats_out[k].std;
+    rq.attr_counts_out[2 * k] = (uint64_t)n;
+    rq.attr_counts_out[2 * k + 1] = (uint64_t)n_tail;
+    for (int i = 0; i < N; i++) {
+      mcp_attr& o = rq.attr_out[(size_t)k * N + i];
+      o.sum = rec[mcp::ATTR_HEAD + 3 * i];
+      o.sum_tail = rec[mcp::ATTR_HEAD + 3 * i + 1];
+      o.sum_xc = rec[mcp::ATTR_HEAD + 3 * i + 2];
+      o.mean = n > 0 ? o.sum / (v0d * n) : 0.0;
+      o.cvar = n_tail > 0 ? o.sum_tail / (v0d * n_tail) : 0.0;
+      const double cov = n > 1 ? (o.sum_xc - o.sum * s1 / n) / (v0d * (n - 1.0)) : 0.0;
+      o.vol = sd > 0.0 ? cov / sd : 0.0;
+    }
+  }
+  return MCP_OK;
+}
+
 // A checked request (check_request) on the shards of a context.
 int simulate_impl(mcp_ctx* c, const mcp_params* prm, const Request& rq, uint64_t seed, uint64_t path_begin, uint64_t n_paths) {
   if (!c) return fail(MCP_E_ARG, "ctx is NULL");
@@ -1857,6 +1981,7 @@ int simulate_impl(mcp_ctx* c, const mcp_params* prm, const Request& rq, uint64_t
       for (size_t s = 0; s < S; s++) { jobs[s].k0 = k0; jobs[s].kt = std::min(kt_max, K - k0); }
       rc = run_tile(c, prm, rq, seed, path_begin, n_paths, jobs, S > 1 || c->exchange_always);
     }
+    if (rc == MCP_OK && rq.attr) rc = run_attribution(c, prm, rq, seed, path_begin, n_paths, jobs);
   }
   if (rc != MCP_OK) {
     // Leave no work in flight behind a failed call, and restore the invariant of the read-and-clear protocol: a pass that
@@ -1965,6 +2090,20 @@ int mcp_simulate_garch(mcp_ctx* c, const mcp_params* prm, const mcp_garch* g, co
   rq.mdd_out = mdd_out;
   rq.dd_stats_out = dd_stats_out;
   ask_horizons(rq, n_horizons != 0, n_horizons, horizons, n_levels, levels, horizon_out, hz_stats_out, bands_out);
+  return simulate_checked(c, prm, rq, seed, path_begin, n_paths);
+}
+
+int mcp_simulate_attribution(mcp_ctx* c, const mcp_params* prm, const mcp_garch* g, const mcp_student_t* st, const float* mu,
+                             const float* chol, const float* W, uint64_t seed, uint64_t path_begin, uint64_t n_paths, float* terminal_out,
+                             mcp_stats* stats_out, float* contrib_out, mcp_attr* attr_out, uint64_t* attr_counts_out) {
+  Request rq = host_request(st ? SRC_T : SRC_GAUSS, mu, chol, W, terminal_out, stats_out);
+  rq.st = st;
+  rq.garch = g != nullptr;
+  rq.gv = g;
+  rq.attr = true;
+  rq.contrib_out = contrib_out;
+  rq.attr_out = attr_out;
+  rq.attr_counts_out = attr_counts_out;
   return simulate_checked(c, prm, rq, seed, path_begin, n_paths);
 }
 

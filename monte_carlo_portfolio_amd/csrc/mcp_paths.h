@@ -47,6 +47,10 @@
 #ifndef MCP_MIN_WAVES_OV8
 #define MCP_MIN_WAVES_OV8 4 // the same for 8 portfolios, N <= 16
 #endif
+#ifndef MCP_MIN_WAVES_AT
+#define MCP_MIN_WAVES_AT 5  // the attribution kernel (N <= 16, one portfolio) holds the N4 contributions A on top of the GARCH kernel's state, as
+                            // the rebalancing kernel holds B: at 5 waves it gets 96 VGPRs, no scratch (profiles/attribution_isa.txt)
+#endif
 #ifndef MCP_EXP_VKEYS
 #define MCP_EXP_VKEYS 1
 #endif
@@ -175,6 +179,39 @@ __device__ __forceinline__ cgarch_p garch_args(const PathArgs&) { return nullptr
 __device__ __forceinline__ cgarch_p garch_args(const PathArgsG&) { return kernarg_garch<PathArgsG>(); }
 __device__ __forceinline__ cgarch_p garch_args(const PathArgsGDD&) { return kernarg_garch<PathArgsGDD>(); }
 __device__ __forceinline__ cgarch_p garch_args(const PathArgsGHZ&) { return kernarg_garch<PathArgsGHZ>(); }
+
+// Risk attribution (SPEC.md 4.10 / 5.9): the second walk of one portfolio per pass that carries the assets' contributions A_i.
+// var: the VaR of every portfolio from the call's statistics (the tail is x <= var); partials: one record of ATTR_HEAD + 3 N4
+// binary64 sums per portfolio and workgroup, {n, n_tail, S1, then per asset sum A, sum_tail A, sum A (x - c)}; contrib: the
+// per-path contributions, or NULL.  The pivot c is PathArgs::pivot.
+constexpr int ATTR_HEAD = 3;
+__host__ __device__ constexpr int attr_record_len(int n4) { return ATTR_HEAD + 3 * n4; }
+struct AttrArgs {
+  const double* __restrict__ var;     // [K]
+  double* __restrict__ partials;      // [K][gridDim.x][attr_record_len(N4)]
+  float* __restrict__ contrib;        // NULL or [K][n_assets][contrib_stride]
+  uint64_t contrib_stride;
+  int32_t n_assets;
+  int32_t pad;
+};
+// Arguments of mc_paths_attr_kernel: those of mc_paths_g_kernel (student_dof and garch_args read them at the same offsets) and the
+// attribution block.
+struct PathArgsAT : PathArgsG { AttrArgs at; };
+// The attribution block of an attribution kernel's launch: read after the walk through the kernel-argument pointer (scalar loads;
+// nothing held in SGPRs across the walk: the Cholesky factor lives there).
+typedef const __attribute__((address_space(4))) AttrArgs* cattr_p;
+__device__ __forceinline__ cattr_p attr_kernarg() {
+  typedef const __attribute__((address_space(4))) PathArgsAT* cat_p;
+  cat_p k = (cat_p)__builtin_amdgcn_kernarg_segment_ptr();
+  asm volatile("" : "+s"(k));
+  return &k->at;
+}
+// The per-wave accumulators of the attribution epilogue: PATH_BLOCK / 64 records in LDS (mc_paths_attr_kernel only).
+template <int N4>
+__device__ __forceinline__ double* attr_wave_slots() {
+  __shared__ double s_attr[4 * attr_record_len(N4)];
+  return s_attr;
+}
 
 // Cash flows and ruin (SPEC.md 4.7): the schedule c_1 .. c_T, one binary32 flow per step, the same for every portfolio.
 struct CashArgs {
@@ -333,7 +370,8 @@ constexpr int PATH_BLOCK = 256;
 // (SPEC.md 4.7).  OV: the step carries the price P_i of every asset and replaces r_i by the return r'_i of the asset's option rows before
 // the weight dot (SPEC.md 4.8).  GV: the step's normals are scaled by u = sqrt(h) (STT: times s), h the path's GARCH(1,1) variance
 // ratio, and h is updated from the scaled normals (SPEC.md 4.9); in a GV kernel STT is set and nu = 0 at run time means Gaussian
-// draws.  All fourteen kernels are the body in mcp_paths_body.inc.
+// draws.  AT: the step also carries every asset's contribution A_i = fma(V, fl32(w_i r_i), A_i) and the epilogue reduces them
+// (SPEC.md 4.10 / 5.9).  All fifteen kernels are the body in mcp_paths_body.inc.
 #define MCP_PATHS_BOUNDS(NB, KT, PPT) \
   __launch_bounds__(PATH_BLOCK, (NB <= 4 && KT == 1 && PPT == 1) ? MCP_MIN_WAVES : ((KT == 1 && PPT == 1) ? MCP_MIN_WAVES_BIG : 1))
 #define MCP_REB_BOUNDS(NB, KT, PPT) \
@@ -342,7 +380,7 @@ constexpr int PATH_BLOCK = 256;
 
 template <int NB, int KT, int PPT, bool NATIVE, bool FOLD = false, bool LOGC = false>
 __global__ void MCP_PATHS_BOUNDS(NB, KT, PPT) mc_paths_kernel(const PathArgs a) {
-  constexpr bool DD = false, HZ = false, BOOT = false, BLDS = false, REB = false, STT = false, CF = false, OV = false, GV = false;
+  constexpr bool DD = false, HZ = false, BOOT = false, BLDS = false, REB = false, STT = false, CF = false, OV = false, GV = false, AT = false;
 #include "mcp_paths_body.inc"
 }
 
@@ -350,7 +388,7 @@ __global__ void MCP_PATHS_BOUNDS(NB, KT, PPT) mc_paths_kernel(const PathArgs a) 
 // array: appended to PathArgs itself they would move the hidden kernel arguments (grid size) of every plain kernel.
 template <int NB, int KT, int PPT, bool LOGC>
 __global__ void MCP_PATHS_BOUNDS(NB, KT, PPT) mc_paths_dd_kernel(const PathArgsDD a) {
-  constexpr bool DD = true, HZ = false, NATIVE = false, FOLD = false, BOOT = false, BLDS = false, REB = false, STT = false, CF = false, OV = false, GV = false;
+  constexpr bool DD = true, HZ = false, NATIVE = false, FOLD = false, BOOT = false, BLDS = false, REB = false, STT = false, CF = false, OV = false, GV = false, AT = false;
 #include "mcp_paths_body.inc"
 }
 
@@ -358,7 +396,7 @@ __global__ void MCP_PATHS_BOUNDS(NB, KT, PPT) mc_paths_dd_kernel(const PathArgsD
 // at the horizons, V_h stored after each; V_T and the fused epilogue as in mc_paths_kernel.
 template <int NB, int KT, int PPT, bool LOGC>
 __global__ void MCP_PATHS_BOUNDS(NB, KT, PPT) mc_paths_hz_kernel(const PathArgsHZ a) {
-  constexpr bool DD = false, HZ = true, NATIVE = false, FOLD = false, BOOT = false, BLDS = false, REB = false, STT = false, CF = false, OV = false, GV = false;
+  constexpr bool DD = false, HZ = true, NATIVE = false, FOLD = false, BOOT = false, BLDS = false, REB = false, STT = false, CF = false, OV = false, GV = false, AT = false;
 #include "mcp_paths_body.inc"
 }
 
@@ -366,14 +404,14 @@ __global__ void MCP_PATHS_BOUNDS(NB, KT, PPT) mc_paths_hz_kernel(const PathArgsH
 // block per path-step for the row index, no normals, no Cholesky GEMV.  V_T and the fused epilogue as in mc_paths_kernel.
 template <int NB, int KT, int PPT, bool LOGC, bool BLDS>
 __global__ void MCP_PATHS_BOUNDS(NB, KT, PPT) mc_paths_boot_kernel(const PathArgsBT a) {
-  constexpr bool DD = false, HZ = false, NATIVE = false, FOLD = false, BOOT = true, REB = false, STT = false, CF = false, OV = false, GV = false;
+  constexpr bool DD = false, HZ = false, NATIVE = false, FOLD = false, BOOT = true, REB = false, STT = false, CF = false, OV = false, GV = false, AT = false;
 #include "mcp_paths_body.inc"
 }
 
 // The bootstrap kernel with the horizons of SPEC.md 4.3 (the segmented walk of mc_paths_hz_kernel).
 template <int NB, int KT, int PPT, bool LOGC, bool BLDS>
 __global__ void MCP_PATHS_BOUNDS(NB, KT, PPT) mc_paths_boot_hz_kernel(const PathArgsBTHZ a) {
-  constexpr bool DD = false, HZ = true, NATIVE = false, FOLD = false, BOOT = true, REB = false, STT = false, CF = false, OV = false, GV = false;
+  constexpr bool DD = false, HZ = true, NATIVE = false, FOLD = false, BOOT = true, REB = false, STT = false, CF = false, OV = false, GV = false, AT = false;
 #include "mcp_paths_body.inc"
 }
 // The rebalancing kernel (SPEC.md 4.5; simple compounding, Gaussian draws or, BOOT, the bootstrap's rows): the walk in segments
@@ -381,7 +419,7 @@ __global__ void MCP_PATHS_BOUNDS(NB, KT, PPT) mc_paths_boot_hz_kernel(const Path
 // kernel serves terminal-only and horizon calls.  V_T and the fused epilogue as in mc_paths_kernel.
 template <int NB, int KT, int PPT, bool BOOT, bool BLDS>
 __global__ void MCP_REB_BOUNDS(NB, KT, PPT) mc_paths_reb_kernel(const PathArgsRB a) {
-  constexpr bool DD = false, HZ = false, NATIVE = false, FOLD = false, LOGC = false, REB = true, STT = false, CF = false, OV = false, GV = false;
+  constexpr bool DD = false, HZ = false, NATIVE = false, FOLD = false, LOGC = false, REB = true, STT = false, CF = false, OV = false, GV = false, AT = false;
 #include "mcp_paths_body.inc"
 }
 
@@ -390,17 +428,17 @@ __global__ void MCP_REB_BOUNDS(NB, KT, PPT) mc_paths_reb_kernel(const PathArgsRB
 // there.
 template <int NB, int KT, int PPT>
 __global__ void MCP_PATHS_BOUNDS(NB, KT, PPT) mc_paths_t_kernel(const PathArgsT a) {
-  constexpr bool DD = false, HZ = false, NATIVE = false, FOLD = false, LOGC = false, BOOT = false, BLDS = false, REB = false, STT = true, CF = false, OV = false, GV = false;
+  constexpr bool DD = false, HZ = false, NATIVE = false, FOLD = false, LOGC = false, BOOT = false, BLDS = false, REB = false, STT = true, CF = false, OV = false, GV = false, AT = false;
 #include "mcp_paths_body.inc"
 }
 template <int NB, int KT, int PPT>
 __global__ void MCP_PATHS_BOUNDS(NB, KT, PPT) mc_paths_t_dd_kernel(const PathArgsTDD a) {
-  constexpr bool DD = true, HZ = false, NATIVE = false, FOLD = false, LOGC = false, BOOT = false, BLDS = false, REB = false, STT = true, CF = false, OV = false, GV = false;
+  constexpr bool DD = true, HZ = false, NATIVE = false, FOLD = false, LOGC = false, BOOT = false, BLDS = false, REB = false, STT = true, CF = false, OV = false, GV = false, AT = false;
 #include "mcp_paths_body.inc"
 }
 template <int NB, int KT, int PPT>
 __global__ void MCP_PATHS_BOUNDS(NB, KT, PPT) mc_paths_t_hz_kernel(const PathArgsTHZ a) {
-  constexpr bool DD = false, HZ = true, NATIVE = false, FOLD = false, LOGC = false, BOOT = false, BLDS = false, REB = false, STT = true, CF = false, OV = false, GV = false;
+  constexpr bool DD = false, HZ = true, NATIVE = false, FOLD = false, LOGC = false, BOOT = false, BLDS = false, REB = false, STT = true, CF = false, OV = false, GV = false, AT = false;
 #include "mcp_paths_body.inc"
 }
 
@@ -411,17 +449,17 @@ __global__ void MCP_PATHS_BOUNDS(NB, KT, PPT) mc_paths_t_hz_kernel(const PathArg
 // scratch in a step loop (profiles/garch_isa.txt).
 template <int NB, int KT, int PPT>
 __global__ void MCP_PATHS_BOUNDS(NB, KT, PPT) mc_paths_g_kernel(const PathArgsG a) {
-  constexpr bool DD = false, HZ = false, NATIVE = false, FOLD = false, LOGC = false, BOOT = false, BLDS = false, REB = false, STT = true, CF = false, OV = false, GV = true;
+  constexpr bool DD = false, HZ = false, NATIVE = false, FOLD = false, LOGC = false, BOOT = false, BLDS = false, REB = false, STT = true, CF = false, OV = false, GV = true, AT = false;
 #include "mcp_paths_body.inc"
 }
 template <int NB, int KT, int PPT>
 __global__ void MCP_PATHS_BOUNDS(NB, KT, PPT) mc_paths_g_dd_kernel(const PathArgsGDD a) {
-  constexpr bool DD = true, HZ = false, NATIVE = false, FOLD = false, LOGC = false, BOOT = false, BLDS = false, REB = false, STT = true, CF = false, OV = false, GV = true;
+  constexpr bool DD = true, HZ = false, NATIVE = false, FOLD = false, LOGC = false, BOOT = false, BLDS = false, REB = false, STT = true, CF = false, OV = false, GV = true, AT = false;
 #include "mcp_paths_body.inc"
 }
 template <int NB, int KT, int PPT>
 __global__ void MCP_PATHS_BOUNDS(NB, KT, PPT) mc_paths_g_hz_kernel(const PathArgsGHZ a) {
-  constexpr bool DD = false, HZ = true, NATIVE = false, FOLD = false, LOGC = false, BOOT = false, BLDS = false, REB = false, STT = true, CF = false, OV = false, GV = true;
+  constexpr bool DD = false, HZ = true, NATIVE = false, FOLD = false, LOGC = false, BOOT = false, BLDS = false, REB = false, STT = true, CF = false, OV = false, GV = true, AT = false;
 #include "mcp_paths_body.inc"
 }
 
@@ -434,7 +472,7 @@ __global__ void MCP_PATHS_BOUNDS(NB, KT, PPT) mc_paths_g_hz_kernel(const PathArg
                                                      : ((KT == 1 && PPT == 1) ? MCP_MIN_WAVES_BIG : 1))
 template <int NB, int KT, int PPT, bool BOOT, bool BLDS, bool STT>
 __global__ void MCP_CF_BOUNDS(NB, KT, PPT) mc_paths_cf_kernel(const PathArgsCF a) {
-  constexpr bool DD = false, HZ = true, NATIVE = false, FOLD = false, LOGC = false, REB = false, CF = true, OV = false, GV = false;
+  constexpr bool DD = false, HZ = true, NATIVE = false, FOLD = false, LOGC = false, REB = false, CF = true, OV = false, GV = false, AT = false;
 #include "mcp_paths_body.inc"
 }
 
@@ -447,9 +485,24 @@ __global__ void MCP_CF_BOUNDS(NB, KT, PPT) mc_paths_cf_kernel(const PathArgsCF a
                                                      : ((KT == 1 && PPT == 1) ? MCP_MIN_WAVES_BIG : 1))
 template <int NB, int KT, int PPT, bool STT, bool DD>
 __global__ void MCP_OV_BOUNDS(NB, KT, PPT) mc_paths_ov_kernel(const PathArgsOV a) {
-  constexpr bool HZ = true, NATIVE = false, FOLD = false, LOGC = false, BOOT = false, BLDS = false, REB = false, CF = false, OV = true, GV = false;
+  constexpr bool HZ = true, NATIVE = false, FOLD = false, LOGC = false, BOOT = false, BLDS = false, REB = false, CF = false, OV = true, GV = false, AT = false;
 #include "mcp_paths_body.inc"
 }
+
+// The attribution kernel (SPEC.md 4.10 / 5.9; simple compounding, unfolded recurrence, one portfolio per pass): the walk of
+// mc_paths_g_kernel again -- the same draws and the same V, Gaussian (nu = 0, alpha = beta = 0, h0 = 1), Student-t or GARCH -- with
+// the contribution A_i of every asset carried next to V: per pair of assets one packed multiply (w r) and one packed fma (V
+// broadcast).  No terminal store and no fused statistics epilogue; its own epilogue reduces A, A over the tail x <= var and
+// A (x - c) to one record per workgroup, in a fixed order, and stores A when asked to.
+#define MCP_AT_BOUNDS(NB, KT, PPT) \
+  __launch_bounds__(PATH_BLOCK, (NB <= 4 && KT == 1 && PPT == 1) ? MCP_MIN_WAVES_AT : ((KT == 1 && PPT == 1) ? MCP_MIN_WAVES_BIG : 1))
+template <int NB, int KT, int PPT>
+__global__ void MCP_AT_BOUNDS(NB, KT, PPT) mc_paths_attr_kernel(const PathArgsAT a) {
+  static_assert(KT == 1, "one portfolio per pass");
+  constexpr bool DD = false, HZ = false, NATIVE = false, FOLD = false, LOGC = false, BOOT = false, BLDS = false, REB = false, STT = true, CF = false, OV = false, GV = true, AT = true;
+#include "mcp_paths_body.inc"
+}
+#undef MCP_AT_BOUNDS
 #undef MCP_OV_BOUNDS
 #undef MCP_PATHS_BOUNDS
 #undef MCP_REB_BOUNDS

@@ -6,8 +6,8 @@
 // (OV = HZ = true, STT or DD either) and the GARCH kernels mc_paths_g_kernel / mc_paths_g_dd_kernel / mc_paths_g_hz_kernel (GV =
 // STT = true, DD or HZ as their twins); the step itself is mcp_paths_step.inc.  As a shared __device__ function the plain kernel's registers came out allocated differently;
 // included, the DD = false kernel compiles to the same instructions as before the drawdown existed.  In scope: the template
-// parameters NB, KT, PPT, NATIVE, FOLD, LOGC, DD, HZ, BOOT, BLDS, REB, STT, CF, OV, GV and the kernel argument `a` (PathArgs, or PathArgsDD /
-// PathArgsHZ / PathArgsBT / PathArgsBTHZ / PathArgsRB / PathArgsT / PathArgsTDD / PathArgsTHZ / PathArgsCF / PathArgsOV / PathArgsG / PathArgsGDD / PathArgsGHZ which start with one).  Without HZ the walk is the one loop it always was, so the plain and drawdown kernels keep their code.
+// parameters NB, KT, PPT, NATIVE, FOLD, LOGC, DD, HZ, BOOT, BLDS, REB, STT, CF, OV, GV, AT and the kernel argument `a` (PathArgs, or PathArgsDD /
+// PathArgsHZ / PathArgsBT / PathArgsBTHZ / PathArgsRB / PathArgsT / PathArgsTDD / PathArgsTHZ / PathArgsCF / PathArgsOV / PathArgsG / PathArgsGDD / PathArgsGHZ / PathArgsAT which start with one).  AT (mc_paths_attr_kernel, GV = STT = true): the contributions of SPEC.md 4.10 and their own epilogue; every AT block is an `if constexpr`, so the other kernels keep their code.  Without HZ the walk is the one loop it always was, so the plain and drawdown kernels keep their code.
   constexpr int N4 = 4 * NB;
   // wave-uniform parameters through the constant address space -> s_load_dword* into SGPRs
   typedef const __attribute__((address_space(4))) float* cfloat_p;
@@ -55,6 +55,10 @@
     (&s_ext[0][0][0])[2 * threadIdx.x] = __builtin_inff(); (&s_ext[0][0][0])[2 * threadIdx.x + 1] = -__builtin_inff();
   }
   if (threadIdx.x < PATH_BLOCK / 64) s_cnt[threadIdx.x] = 0ull;
+  if constexpr (AT) {                                      // the per-wave records of the attribution epilogue
+    double* const s_at = attr_wave_slots<N4>();
+    for (int i = threadIdx.x; i < (PATH_BLOCK / 64) * attr_record_len(N4); i += PATH_BLOCK) s_at[i] = 0.0;
+  }
   __syncthreads();
   const IcdfConsts kc = icdf_consts();
   PhiloxKeys ks = philox_keys((uint32_t)a.seed, (uint32_t)(a.seed >> 32));
@@ -81,6 +85,7 @@
     f32x2 Bs[PPT][N4 / 2];                                // REB: the assets' returns since the last rebalance (SPEC.md 4.5)
     float Ps[PPT][N4];                                    // OV: the assets' price levels P_i (SPEC.md 4.8)
     float gh[PPT];                                        // GV: the variance ratio h of SPEC.md 4.9
+    f32x2 At[PPT][N4 / 2];                                // AT: the assets' contributions A_i of SPEC.md 4.10
 #pragma unroll
     for (int e = 0; e < PPT; e++) {
       p[e] = tl * tile + (uint64_t)e * PATH_BLOCK + threadIdx.x;
@@ -94,6 +99,10 @@
       if constexpr (REB) {
 #pragma unroll
         for (int m = 0; m < N4 / 2; m++) Bs[e][m] = f32x2{0.0f, 0.0f};
+      }
+      if constexpr (AT) {
+#pragma unroll
+        for (int m = 0; m < N4 / 2; m++) At[e][m] = f32x2{0.0f, 0.0f};
       }
       if constexpr (DD) {
 #pragma unroll
@@ -230,6 +239,56 @@
       }
     }
 
+    if constexpr (AT) {
+      // ---- attribution epilogue (SPEC.md 5.9): x, the tail flag x <= var (binary64), d = x - c; per asset the wave sums of A, of A
+      // over the tail and of A d, added to this wave's record in LDS by lane 0 (its own slot: no race, fixed order over the tiles)
+      const cattr_p ak = attr_kernarg();
+      asm volatile("" : "+s"(kargs));
+      const double e_c = kargs->pivot[a.k_begin], e_var = ak->var[a.k_begin], e_v0d = kargs->v0d;
+      int tid = threadIdx.x;
+      asm volatile("" : "+v"(tid));                        // nothing derived from it (LDS addresses) is hoisted above the step loop
+      const int lane = tid & 63, wv = tid >> 6;
+      double* const slot = attr_wave_slots<N4>() + wv * attr_record_len(N4);
+      double dv[PPT];
+      bool tail[PPT];
+      double cn = 0.0, ct = 0.0, s1 = 0.0;
+#pragma unroll
+      for (int e = 0; e < PPT; e++) {
+        const double x = terminal_to_x(V[e][0], e_v0d, MCP_COMPOUND_SIMPLE);
+        tail[e] = live[e] && x <= e_var;
+        dv[e] = live[e] ? x - e_c : 0.0;
+        cn += live[e] ? 1.0 : 0.0;                         // counts < 2^53: exact in double
+        ct += tail[e] ? 1.0 : 0.0;
+        s1 += dv[e];
+      }
+      cn = wave_sum(cn); ct = wave_sum(ct); s1 = wave_sum(s1);
+      if (lane == 0) { slot[0] += cn; slot[1] += ct; slot[2] += s1; }
+#pragma unroll
+      for (int i = 0; i < N4; i++) {
+        double sa = 0.0, st = 0.0, sx = 0.0;
+#pragma unroll
+        for (int e = 0; e < PPT; e++) {
+          const double ai = live[e] ? (double)((i & 1) ? At[e][i / 2].y : At[e][i / 2].x) : 0.0;
+          sa += ai;
+          st += tail[e] ? ai : 0.0;
+          sx = __builtin_fma(ai, dv[e], sx);
+        }
+        sa = wave_sum(sa); st = wave_sum(st); sx = wave_sum(sx);
+        if (lane == 0) { slot[ATTR_HEAD + 3 * i] += sa; slot[ATTR_HEAD + 3 * i + 1] += st; slot[ATTR_HEAD + 3 * i + 2] += sx; }
+      }
+      float* const cb = ak->contrib;
+      if (cb != nullptr) {                                 // wave-uniform: A_ki to [k][i][path], coalesced over the paths
+        const int n_live = ak->n_assets;
+        const uint64_t cs = ak->contrib_stride;
+#pragma unroll
+        for (int i = 0; i < N4; i++)
+          if (i < n_live) {
+#pragma unroll
+            for (int e = 0; e < PPT; e++)
+              if (live[e]) cb[((size_t)a.k_begin * n_live + i) * cs + p[e]] = (i & 1) ? At[e][i / 2].y : At[e][i / 2].x;
+          }
+      }
+    } else {
 #pragma unroll
     for (int e = 0; e < PPT; e++) {
       if (live[e]) {
@@ -251,6 +310,7 @@
         }
       }
     }
+    }  // !AT
 
     // ---- fused statistics epilogue: V is still in registers ----
     asm volatile("" : "+s"(kargs));
@@ -320,5 +380,16 @@
       o.vmax = fmaxf(fmaxf(s_ext[0][k][1], s_ext[1][k][1]), fmaxf(s_ext[2][k][1], s_ext[3][k][1]));
       o.n = (s_cnt[0] + s_cnt[1]) + (s_cnt[2] + s_cnt[3]);
       kargs->partials[(size_t)(a.k_begin + k) * kargs->slots + blockIdx.x] = o;
+    }
+  }
+  if constexpr (AT) {
+    // one record per workgroup: entry j is the sum of the four waves' entries j, waves in order (SPEC.md 5.9)
+    __syncthreads();
+    const cattr_p ak = attr_kernarg();
+    const double* const s_at = attr_wave_slots<N4>();
+    constexpr int RL = attr_record_len(N4);
+    if ((int)threadIdx.x < RL) {
+      const int j = threadIdx.x;
+      ak->partials[((size_t)a.k_begin * gridDim.x + blockIdx.x) * RL + j] = (s_at[j] + s_at[RL + j]) + (s_at[2 * RL + j] + s_at[3 * RL + j]);
     }
   }

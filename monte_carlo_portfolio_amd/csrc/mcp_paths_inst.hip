@@ -76,6 +76,11 @@ static void go(const PathKernel& k, const PathArgs& a, int grid, hipStream_t str
 }
 
 hipError_t MCP_CAT(launch_paths_nb, MCP_NB)(int variant, const PathKernel& k, const PathArgs& a, int grid, hipStream_t stream) {
+  if (k.family == FAM_AT) {                                // one portfolio per pass, simple compounding, the GARCH kernel's draws
+    if (variant != 0 || k.logc || k.boot) return hipErrorInvalidValue;
+    MCP_GO((mc_paths_attr_kernel<MCP_NB, 1, 1>), PathArgsAT);
+    return hipGetLastError();
+  }
   const bool plain = k.family == FAM_PLAIN && !k.boot && !k.stt && !k.gv;
   if (k.family < FAM_PLAIN || k.family > FAM_OV || (!plain && variant != 0 && variant != VAR_KT8)) return hipErrorInvalidValue;
   switch (variant) {

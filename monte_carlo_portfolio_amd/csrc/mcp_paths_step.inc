@@ -6,7 +6,9 @@
 // block_normals (SPEC.md 2.2 / 4.6).  CF: the flow c_s after the update, ruin absorbing (SPEC.md 4.7).  OV: between the row pair's
 // returns and the weight dot, the return of every asset that owns option rows is replaced by its rows' return at the asset's price
 // level (SPEC.md 4.8); whether an asset owns rows is wave-uniform, a scalar branch.  GV: s is replaced by u = s sqrt(h) (nu = 0: u =
-// sqrt(h), the chi blocks skipped by a scalar branch) and h is updated from the scaled normals (SPEC.md 4.9).  In scope: everything mcp_paths_body.inc declares before its step loops, and t.
+// sqrt(h), the chi blocks skipped by a scalar branch) and h is updated from the scaled normals (SPEC.md 4.9).  AT: between the row
+// pair's returns and the weight dot, c = fl32(w r) and A = fma(V, c, A) for the pair, one v_pk_mul_f32 and one v_pk_fma_f32, V the
+// value before this step's update (SPEC.md 4.10).  In scope: everything mcp_paths_body.inc declares before its step loops, and t.
       float rho[PPT][KT];
       if constexpr (BOOT) {
         // SPEC.md 2.1 / 4.4: one Philox block on counter (t, 1, p_lo, p_hi); j_t = mulhi(x0, R) on a restart (t = 0 or
@@ -187,6 +189,11 @@
               for (int e = 0; e < PPT; e++) acc[e].y = overlay_return(acc[e].y, Ps[e][2 * m + 1], b1, b2);
             }
           }
+        }
+        if constexpr (AT) {
+          const f32x2 w2 = {Wk[2 * m], Wk[2 * m + 1]};    // KT == 1: the pass's portfolio
+#pragma unroll
+          for (int e = 0; e < PPT; e++) At[e][m] = __builtin_elementwise_fma((f32x2){V[e][0], V[e][0]}, w2 * acc[e], At[e][m]);
         }
 #pragma unroll
         for (int h = 0; h < 2; h++) {

@@ -66,7 +66,8 @@ enum { VAR_KT8 = 1, VAR_NATIVE = 4, VAR_FOLD = 8 };
 //   FAM_OV     PathArgsOV (stt: t draws; dd: the drawdown state; the horizons optional)
 // `blds`: the bootstrap's row table is copied into LDS (it fits boot_fits_lds) instead of being read from global memory.
 // VAR_NATIVE and VAR_FOLD exist for the plain Gaussian kernel only.
-enum PathFamily { FAM_PLAIN, FAM_DD, FAM_HZ, FAM_REB, FAM_CF, FAM_OV };
+//   FAM_AT     PathArgsAT (the attribution walk of SPEC.md 4.10: variant 0 only, one portfolio per pass)
+enum PathFamily { FAM_PLAIN, FAM_DD, FAM_HZ, FAM_REB, FAM_CF, FAM_OV, FAM_AT };
 struct PathKernel {
   int family;
   bool logc, boot, blds, stt;
@@ -114,6 +115,9 @@ hipError_t launch_count_rows(const float* values, uint64_t stride, uint64_t n, i
 // every buffer <- element-wise sum of the `nsrc` buffers (u64 words): the exchange between logical shards of ONE device
 // (or of devices with peer access)
 hipError_t launch_sum_u64(unsigned long long* const* bufs, int nsrc, size_t words, hipStream_t s);
+// out[k][j] = sum over the `blocks` workgroup records of portfolio k of entry j, in block order (SPEC.md 5.9); partials is
+// [K][blocks][len], out [K][len]
+hipError_t launch_attr_merge(const double* partials, int K, int blocks, int len, double* out, hipStream_t s);
 
 hipError_t launch_sweep_hist(int N, int R, int P, const double* returns, const double* mean, const double* cov,
                              const double* W, double rf, uint64_t rank_lo, uint64_t rank_hi, double gamma,

@@ -621,4 +621,20 @@ hipError_t launch_sum_u64(unsigned long long* const* bufs, int nsrc, size_t word
   return hipGetLastError();
 }
 
+// ---- attribution (SPEC.md 5.9): the workgroup records of one portfolio added in block order; grid = K, one thread per entry ----
+__global__ void __launch_bounds__(SB) attr_merge_kernel(const double* __restrict__ partials, int blocks, int len, double* __restrict__ out) {
+  const int j = threadIdx.x;
+  if (j >= len) return;
+  const double* src = partials + (size_t)blockIdx.x * blocks * len;
+  double acc = 0.0;
+  for (int b = 0; b < blocks; b++) acc += src[(size_t)b * len + j];
+  out[(size_t)blockIdx.x * len + j] = acc;
+}
+
+hipError_t launch_attr_merge(const double* partials, int K, int blocks, int len, double* out, hipStream_t s) {
+  if (K < 1 || blocks < 1 || len < 1 || len > SB) return hipErrorInvalidValue;
+  attr_merge_kernel<<<(unsigned)K, SB, 0, s>>>(partials, blocks, len, out);
+  return hipGetLastError();
+}
+
 }  // namespace mcp

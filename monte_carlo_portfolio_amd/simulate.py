@@ -65,11 +65,12 @@ class Context:
 
     def _call(self, prm: _ffi.McpParams, W, seed: int, path_begin: int, n_paths: int, store: bool, mu=None, chol=None, rows=None,
               block: float = 1.0, dof=None, period=None, cost: float = 0.0, drawdown: bool = False, horizons=None, levels=(),
-              flows=None, target=None, overlay=None, garch=None):
+              flows=None, target=None, overlay=None, garch=None, attribution=False):
         """The one library call behind every simulate_* method: GARCH volatility (garch: the (alpha, beta, h0) of check_garch), an option overlay (overlay: the triple of check_overlay), cash flows (flows, target), Student-t draws (dof), rebalancing
         (period, cost), bootstrap rows (rows, block) or Gaussian draws (mu, chol), with the drawdown or horizons.  Allocates the
         outputs that were asked for and passes NULL for the rest -> _Outputs, None where not asked for (terminal, qd,
-        horizon_terminal: with `store` only; counts, hz_counts: with `flows` only)."""
+        horizon_terminal: with `store` only; counts, hz_counts: with `flows` only; attr [K, N] records of ATTR_DTYPE and attr_counts
+        [K, 2] with `attribution` only, contributions [K, N, n_paths] with `store` on top)."""
         K = prm.n_portfolios
         ptr = lambda a: a.ctypes.data_as(ctypes.c_void_p) if a is not None else None   # noqa: E731
         stats = np.zeros(K, _ffi.STATS_DTYPE)
@@ -90,7 +91,21 @@ class Context:
         hz_in = (H, ptr(steps) if H else None, L, ptr(lv) if L else None)
         hz_out = (ptr(hz_term), ptr(hz_stats), ptr(bands) if L else None)
         bt = _ffi.make_bootstrap(rows, block) if rows is not None else None
-        if garch is not None:
+        attr = attr_counts = contrib = None
+        if attribution:
+            # the library states the rules (check_request): everything but plain, Student-t and GARCH draws is MCP_E_UNSUPPORTED
+            if (overlay is not None or flows is not None or period is not None or bt is not None or horizons is not None or drawdown):
+                raise ValueError("attribution is not combined with overlay, cashflow, rebalance, bootstrap rows, horizons or drawdown")
+            N = prm.n_assets
+            attr = np.zeros((K, N), _ffi.ATTR_DTYPE)
+            attr_counts = np.zeros((K, 2), np.uint64)
+            contrib = np.empty((K, N, n_paths), np.float32) if store else None
+            st = _ffi.McpStudentT(int(dof), 0) if dof is not None else None
+            gv = _ffi.McpGarch(float(garch[0]), float(garch[1]), float(garch[2]), 0) if garch is not None else None
+            rc = lib.mcp_simulate_attribution(self._h, prm_p, ctypes.byref(gv) if gv is not None else None,
+                                              ctypes.byref(st) if st is not None else None, ptr(mu), ptr(chol), ptr(W), *walk, ptr(term),
+                                              ptr(stats), ptr(contrib), ptr(attr), ptr(attr_counts))
+        elif garch is not None:
             st = _ffi.McpStudentT(int(dof), 0) if dof is not None else None
             gv = _ffi.McpGarch(float(garch[0]), float(garch[1]), float(garch[2]), 0)
             rc = lib.mcp_simulate_garch(self._h, prm_p, ctypes.byref(gv), ctypes.byref(st) if st is not None else None, ptr(mu),
@@ -125,7 +140,7 @@ class Context:
         else:
             rc = lib.mcp_simulate(self._h, prm_p, mu, chol, W, *walk, ptr(term), ptr(stats))
         _ffi.check(rc)
-        return _Outputs(stats, dd_stats, hz_stats, bands, term, raw, hz_term, counts, hz_counts)
+        return _Outputs(stats, dd_stats, hz_stats, bands, term, raw, hz_term, counts, hz_counts, attr, attr_counts, contrib)
 
     def simulate(self, prm: _ffi.McpParams, mu, chol, W, seed: int, path_begin: int, n_paths: int, store: bool):
         o = self._call(prm, W, seed, path_begin, n_paths, store, mu=mu, chol=chol)
@@ -188,6 +203,15 @@ class Context:
         return self._call(prm, W, seed, path_begin, n_paths, store, mu=mu, chol=chol, dof=dof, drawdown=drawdown, horizons=horizons,
                           levels=levels, garch=garch)
 
+    def simulate_attribution(self, prm: _ffi.McpParams, mu, chol, W, seed: int, path_begin: int, n_paths: int, store: bool, dof=None,
+                             garch=None):
+        """simulate() / simulate_student_t() / simulate_garch() (no drawdown, no horizons) followed by the second walk that
+        attributes every portfolio's mean, CVaR and standard deviation to its assets (SPEC.md 4.10 / 5.9; include/mcport.h,
+        mcp_simulate_attribution; simple compounding, K <= 16, path shards) -> _Outputs: stats and terminal bit for bit those of the
+        call without it, attr [K, N] records of _ffi.ATTR_DTYPE, attr_counts [K, 2] uint64 {n, n_tail} and, with `store`,
+        contributions [K, N, n_paths] binary32."""
+        return self._call(prm, W, seed, path_begin, n_paths, store, mu=mu, chol=chol, dof=dof, garch=garch, attribution=True)
+
     def simulate_cashflow(self, prm: _ffi.McpParams, flows, W, seed: int, path_begin: int, n_paths: int, store: bool, mu=None,
                           chol=None, rows=None, block: float = 1.0, dof=None, target=None, horizons=None, levels=()):
         """simulate() / simulate_horizons() / simulate_bootstrap[_horizons]() / simulate_student_t() with the schedule `flows`
@@ -213,8 +237,10 @@ class Context:
 # What Context._call returns: mcp_stats record arrays (stats [K], dd_stats [K], hz_stats [H, K]), bands [H, K, L] and the stored
 # binary32 arrays (terminal [K, n], qd [K, n], horizon_terminal [H, K, n]); with cash flows the counts {n_ruined, n_short} of
 # SPEC.md 5.6 (counts [K, 2], hz_counts [H, K, 2], uint64).
-_Outputs = collections.namedtuple("_Outputs", "stats dd_stats hz_stats bands terminal qd horizon_terminal counts hz_counts",
-                                  defaults=(None, None))
+# With attribution the records of SPEC.md 5.9 (attr [K, N] of ATTR_DTYPE, attr_counts [K, 2] uint64 {n, n_tail}) and, stored, the
+# binary32 contributions [K, N, n].
+_Outputs = collections.namedtuple("_Outputs", "stats dd_stats hz_stats bands terminal qd horizon_terminal counts hz_counts attr "
+                                  "attr_counts contributions", defaults=(None, None, None, None, None))
 
 
 def check_cashflow(cashflow, target, n_steps):
@@ -465,11 +491,24 @@ def drawdown_to_dict(rec) -> dict:
             "x_lo": float(rec["x_lo"]), "x_hi": float(rec["x_hi"])}
 
 
+def attribution_to_dict(attr, counts, rec) -> dict:
+    """The 'attribution' block of one portfolio (SPEC.md 5.9) from its [N] mcp_attr records, its {n, n_tail} and its mcp_stats
+    record: the parts, their shares (0 where the parts sum to 0) and the residuals statistic - sum of parts."""
+    mean, cvar, vol = (np.array(attr[f], np.float64) for f in ("mean", "cvar", "vol"))
+
+    def share(parts):
+        tot = float(parts.sum())
+        return parts / tot if tot != 0.0 else np.zeros_like(parts)
+    return {"mean": mean, "cvar": cvar, "vol": vol, "cvar_share": share(cvar), "vol_share": share(vol), "n_tail": int(counts[1]),
+            "residual": {"mean": float(rec["mean"]) - float(mean.sum()), "cvar": float(rec["cvar"]) - float(cvar.sum()),
+                         "vol": float(rec["std"]) - float(vol.sum())}}
+
+
 def simulate_paths(mu, cov, weights, n_steps=252, n_paths=10_000, seed=0, v0=1.0, compounding="simple",
                    rf=0.0, alpha=0.95, devices=None, store=False, path_begin=0, chol=None,
                    native_math=False, as_array=False, fold=False, shard="auto", context=None, drawdown=False,
                    horizons=None, bands=(), rebalance=None, rebalance_cost=0.0, dof=None, cashflow=None, target=None,
-                   overlay=None, spot=None, garch=None):
+                   overlay=None, spot=None, garch=None, attribution=False):
     """Simulate `n_paths` correlated return paths and reduce them to risk statistics.
 
     mu [N], cov [N,N] are per-step mean and covariance (the reference's `mean_returns`, `cov_matrix`
@@ -536,7 +575,35 @@ def simulate_paths(mu, cov, weights, n_steps=252, n_paths=10_000, seed=0, v0=1.0
     bit.  fit_garch(returns)[:3] estimates the triple from return rows.  The result has the shape of the same call without it
     (drawdown, horizons / bands, dof, store and as_array all combine).  Not with rebalance, cashflow, overlay, fold, native_math or
     compounding="log" (ValueError).
+
+    attribution=False (default): the statistics say how risky a portfolio is.  attribution=True: also which holding the risk comes
+    from (SPEC.md 4.10 / 5.9).  After the call's statistics are known the same paths are walked a second time, one portfolio per pass,
+    carrying next to the value the money A_i every asset made or lost along the path (sum_i A_i = V_T - v0); nothing per step is
+    stored.  Every dict gains 'attribution' {mean, cvar, vol (float64 [N]: the asset's parts of the portfolio's mean, CVaR and
+    standard deviation, which add up to them -- component CVaR and component volatility), cvar_share, vol_share (the parts over
+    their sum: the risk pie), n_tail, residual {mean, cvar, vol} (the statistic minus the sum of its parts: binary32 rounding of the
+    walk, bounded in SPEC.md 6)} and, with store=True, 'contributions' (float32 [N, n_paths], the A_i of every path).
+    as_array=True appends (attr [K, N] records of _ffi.ATTR_DTYPE, counts [K, 2] uint64 {n, n_tail}) and, with store,
+    contributions [K, N, n_paths].  Combines with dof, garch, store, as_array and devices (path shards), for at most 16 portfolios;
+    the statistics and the stored terminal values are bit for bit those of the call without it.  Costs one more walk per portfolio.
+    Not built: attribution with drawdown, horizons, rebalance, cashflow, overlay, fold, native_math, compounding="log",
+    shard="portfolios" or more than 16 portfolios (ValueError), on bootstrap paths (simulate_bootstrap), in simulate_sweep (call
+    simulate_paths for the optimum), in PathEngine and at the mcp_launch_* level.
     """
+    if not isinstance(attribution, (bool, np.bool_)):
+        raise ValueError(f"attribution must be True or False, got {attribution!r}")
+    if attribution:
+        bad = [name for name, on in (("drawdown", drawdown), ("horizons", horizons is not None), ("rebalance", rebalance is not None),
+                                     ("cashflow", cashflow is not None), ("overlay", overlay is not None), ("fold", fold),
+                                     ("native_math", native_math), ("compounding='log'", compounding == "log"),
+                                     ("shard='portfolios'", shard == "portfolios")) if on]
+        if bad:
+            raise ValueError("attribution needs constant weights, simple compounding, the spec's normals, the unfolded recurrence and "
+                             f"path shards: not with {', '.join(bad)}")
+        k_attr = np.atleast_2d(np.asarray(weights)).shape[0]
+        if k_attr > _ffi.MCP_MAX_ATTR_PORTFOLIOS:
+            raise ValueError(f"attribution takes at most {_ffi.MCP_MAX_ATTR_PORTFOLIOS} portfolios, got {k_attr}: call simulate_paths "
+                             "for the portfolios of interest")
     gv = check_garch(garch)
     if gv is not None and (rebalance is not None or cashflow is not None or overlay is not None or fold or native_math
                            or compounding == "log"):
@@ -563,9 +630,11 @@ def simulate_paths(mu, cov, weights, n_steps=252, n_paths=10_000, seed=0, v0=1.0
         raise ValueError("horizons need the spec's normals and the unfolded recurrence: not with drawdown, fold or native_math")
     steps, levels = _check_walk(n_steps, horizons, bands, period, compounding, shard)
     mu32, L, W = prepare_inputs(mu, cov, weights, chol)
-    prm, ctx = _setup(mu32.shape[0], n_steps, W.shape[0], compounding, v0, alpha, rf, native_math, fold, devices, shard, context)
+    prm, ctx = _setup(mu32.shape[0], n_steps, W.shape[0], compounding, v0, alpha, rf, native_math, fold, devices,
+                      "paths" if attribution else shard, context)
     out = ctx._call(prm, W, int(seed), int(path_begin), int(n_paths), store, mu=mu32, chol=L, dof=dof, period=period, cost=cost,
-                    drawdown=drawdown, horizons=steps, levels=levels, flows=flows, target=target, overlay=ov, garch=gv)
+                    drawdown=drawdown, horizons=steps, levels=levels, flows=flows, target=target, overlay=ov, garch=gv,
+                    attribution=bool(attribution))
     return _result(out, np.asarray(weights).ndim == 1, store, as_array, steps, levels, compounding, flows, target)
 
 
@@ -610,7 +679,8 @@ def _result(out, single, store, as_array, steps, levels, compounding, flows=None
     """What simulate_paths / simulate_bootstrap return for Context._call's outputs `out`: with as_array the record arrays (stats,
     then (hz_stats, bands) or dd_stats, then with `store` terminal and horizon_terminal or max_drawdown); else one dict per
     portfolio (one dict for a single weight vector) with its 'drawdown' / 'horizons' blocks and, with `store`, the stored arrays."""
-    stats, dd_stats, hz_stats, hz_bands, term, qd, hz_term, counts, hz_counts = out
+    stats, dd_stats, hz_stats, hz_bands, term, qd, hz_term, counts, hz_counts = out[:9]
+    attr, attr_counts, contrib = out[9:]
     mdd = mdd_from_raw(qd, compounding) if dd_stats is not None and store else None
     if as_array:                          # [K] structured arrays (fields of mcp_stats), for large sweeps
         cash = () if counts is None else (counts,) if hz_counts is None else (counts, hz_counts)
@@ -620,6 +690,8 @@ def _result(out, single, store, as_array, steps, levels, compounding, flows=None
             return (stats, dd_stats, term, mdd) if store else (stats, dd_stats)
         if cash:
             return ((stats, term) if store else (stats,)) + cash
+        if attr is not None:              # SPEC.md 5.9
+            return ((stats, term) if store else (stats,)) + (attr, attr_counts) + ((contrib,) if store else ())
         return (stats, term) if store else stats
     res = [stats_to_dict(stats[k]) for k in range(stats.shape[0])]
     for k, d in enumerate(res):
@@ -633,8 +705,12 @@ def _result(out, single, store, as_array, steps, levels, compounding, flows=None
                 d["horizons"].update(_cash_block(hz_counts[:, k, :], int(stats[k]["n"]), target))
         if counts is not None:            # SPEC.md 5.6; contributed: the binary64 sum of the binary32 flows
             d["cashflow"] = _cash_block(counts[k], int(stats[k]["n"]), target, float(np.sum(flows.astype(np.float64))))
+        if attr is not None:
+            d["attribution"] = attribution_to_dict(attr[k], attr_counts[k], stats[k])
         if store:
             d["terminal"] = term[k]
+            if contrib is not None:
+                d["contributions"] = contrib[k]
             if dd_stats is not None:
                 d["max_drawdown"] = mdd[k]
             if hz_stats is not None:
@@ -686,6 +762,10 @@ def simulate_bootstrap(returns, weights, n_steps=252, n_paths=10_000, block=1.0,
         raise ValueError("simulate_bootstrap does not take overlay: the rows are observed returns with no price level to strike an "
                          "option at -- apply the strategy to the returns matrix first (options.calc_options_series per asset, as "
                          "the reference does), or call simulate_paths(overlay=...)")
+    if unsupported.get("attribution"):
+        raise ValueError("simulate_bootstrap does not take attribution: the second walk re-draws normals, the bootstrap's rows are not "
+                         "built into it -- call simulate_paths(attribution=True)")
+    unsupported.pop("attribution", None)
     if unsupported.get("garch") is not None:
         raise ValueError("simulate_bootstrap does not take garch: the rows carry their own dynamics -- a mean block length block > 1 "
                          "keeps the volatility regimes of the observed rows; GARCH is a parametric model, call "
@@ -726,6 +806,9 @@ def simulate_sweep(mu, cov, weights=None, n_portfolios=2500, min_weights=None, m
         raise ValueError("simulate_sweep does not take horizons or bands: call simulate_paths for the optimum")
     if kw.get("cashflow") is not None or kw.get("target") is not None:
         raise ValueError("simulate_sweep does not take cashflow or target: call simulate_paths for the optimum")
+    if kw.get("attribution"):
+        raise ValueError("simulate_sweep does not take attribution: call simulate_paths for the optimum")
+    kw.pop("attribution", None)
     drawdown = bool(kw.get("drawdown", False))
     stats = simulate_paths(mu, cov, W, n_steps=n_steps, n_paths=n_paths, seed=seed, rf=rf, alpha=alpha, as_array=True, **kw)
     dd_stats = None
