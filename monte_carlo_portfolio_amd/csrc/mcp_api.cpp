@@ -406,8 +406,6 @@ struct Launch {
   const float* d_rows = nullptr;        // bootstrap: [R][N4], zero-padded
   const float* d_flows = nullptr;       // cash flows: [n_steps]
   const char* d_overlay = nullptr;      // overlay: [rows][row_begin N4 + 1][spot N4] (overlay_pack)
-  int ov_n = 0, ov_n4 = 0;              // overlay: N and N4 of that table
-  int n_assets = 0;                     // GARCH: N (set by launch_paths_impl)
   bool attr = false;                    // the attribution walk (SPEC.md 4.10): FAM_AT instead of the request's own family
   const double* d_var = nullptr;        // attribution: [K] VaRs
   double* d_attr_partials = nullptr;    // attribution: [K][path_grid(n_paths)][attr_record_len(N4)]
@@ -908,7 +906,8 @@ int mcp_bootstrap_pivots(const mcp_params* prm, const mcp_bootstrap* boot, const
 
 }  // extern "C"
 
-// The blocks that the family kernels add to PathArgs (mcp_paths.h), filled from the request and its launch.
+// The blocks that the family kernels add to PathArgs (mcp_paths.h), filled from the request and its launch; a block the request
+// does not carry is empty.
 static void fill_hz(mcp::PathArgsHZ& x, const Request& rq, const Launch& ln) {
   x.hz = rq.hz ? ln.d_hz : nullptr;
   x.hz_stride = rq.hz ? ln.hz_stride : 0;
@@ -926,87 +925,41 @@ static mcp::BootArgs boot_block(const Request& rq, const Launch& ln) {
 }
 static mcp::StudentArgs student_block(const Request& rq) {
   mcp::StudentArgs st;
-  st.dof = rq.st->dof;
+  st.dof = rq.src == SRC_T ? rq.st->dof : 0;                   // 0: Gaussian draws
   st.pad = 0;
   return st;
 }
-static void fill(mcp::PathArgs&, const Request&, const Launch&) {}
-static void fill(mcp::PathArgsDD& x, const Request&, const Launch& ln) { x.mdd = ln.d_mdd; x.mdd_stride = ln.mdd_stride; }
-static void fill(mcp::PathArgsHZ& x, const Request& rq, const Launch& ln) { fill_hz(x, rq, ln); }
-static void fill(mcp::PathArgsBT& x, const Request& rq, const Launch& ln) { x.bt = boot_block(rq, ln); }
-static void fill(mcp::PathArgsBTHZ& x, const Request& rq, const Launch& ln) { fill_hz(x, rq, ln); x.bt = boot_block(rq, ln); }
-static void fill(mcp::PathArgsT& x, const Request& rq, const Launch&) { x.st = student_block(rq); }
-static void fill(mcp::PathArgsTDD& x, const Request& rq, const Launch& ln) { fill((mcp::PathArgsDD&)x, rq, ln); x.st = student_block(rq); }
-static void fill(mcp::PathArgsTHZ& x, const Request& rq, const Launch& ln) { fill_hz(x, rq, ln); x.st = student_block(rq); }
-static void garch_block(mcp::StudentArgs& st, mcp::GarchArgs& gv, const Request& rq, int n_assets) {
-  const GarchConsts c = garch_consts(rq.gv, n_assets);
-  st.dof = rq.src == SRC_T ? rq.st->dof : 0;                   // 0: Gaussian draws
-  st.pad = 0;
+static mcp::GarchArgs garch_block(const mcp_garch* g, int n_assets) {
+  const GarchConsts c = garch_consts(g, n_assets);
+  mcp::GarchArgs gv;
   gv.a_n = c.a_n;
   gv.b = c.b;
   gv.omega = c.omega;
   gv.h0 = c.g;
   gv.n_assets = n_assets;
   gv.pad = 0;
+  return gv;
 }
-static void fill(mcp::PathArgsG& x, const Request& rq, const Launch& ln) { garch_block(x.st, x.gv, rq, ln.n_assets); }
-static void fill(mcp::PathArgsGDD& x, const Request& rq, const Launch& ln) { fill((mcp::PathArgsDD&)x, rq, ln); garch_block(x.st, x.gv, rq, ln.n_assets); }
-static void fill(mcp::PathArgsGHZ& x, const Request& rq, const Launch& ln) { fill_hz(x, rq, ln); garch_block(x.st, x.gv, rq, ln.n_assets); }
-// The attribution walk draws as the GARCH kernel does: without GARCH on alpha = beta = 0, h0 = 1, which is the Gaussian or Student-t
-// call bit for bit (SPEC.md 4.9).
-static void fill(mcp::PathArgsAT& x, const Request& rq, const Launch& ln) {
-  static const mcp_garch none = {0.0, 0.0, 1.0, 0};
-  Request rg = rq;
-  if (!rq.garch) rg.gv = &none;
-  garch_block(x.st, x.gv, rg, ln.n_assets);
-  x.at.var = ln.d_var;
-  x.at.partials = ln.d_attr_partials;
-  x.at.contrib = ln.d_contrib;
-  x.at.contrib_stride = ln.contrib_stride;
-  x.at.n_assets = ln.n_assets;
-  x.at.pad = 0;
-}
-static void fill(mcp::PathArgsCF& x, const Request& rq, const Launch& ln) {
-  fill_hz(x, rq, ln);
-  x.bt = boot_block(rq, ln);
-  x.st.dof = rq.src == SRC_T ? rq.st->dof : 0;
-  x.st.pad = 0;
-  x.cf.flows = ln.d_flows;
-}
-static void fill(mcp::PathArgsOV& x, const Request& rq, const Launch& ln) {
-  fill_hz(x, rq, ln);
-  x.mdd = rq.dd ? ln.d_mdd : nullptr;
-  x.mdd_stride = rq.dd ? ln.mdd_stride : 0;
-  x.st.dof = rq.src == SRC_T ? rq.st->dof : 0;
-  x.st.pad = 0;
+static mcp::OverlayArgs overlay_block(const Request& rq, const Launch& ln, int n_assets) {
+  mcp::OverlayArgs ov;
   const size_t row_bytes = (size_t)rq.ov->n_rows * sizeof(mcp_overlay_row);
-  x.ov.rows = (const mcp_overlay_row*)ln.d_overlay;
-  x.ov.row_begin = (const int32_t*)(ln.d_overlay + row_bytes);
-  x.ov.spot = (const float*)(ln.d_overlay + row_bytes) + ln.ov_n4 + 1;
-  x.ov.mask = 0;
-  for (int i = 0; i < ln.ov_n; i++)                            // the padding assets >= N own no rows
-    if (rq.ov->row_begin[i + 1] > rq.ov->row_begin[i]) x.ov.mask |= (uint64_t)1 << i;
+  ov.rows = (const mcp_overlay_row*)ln.d_overlay;
+  ov.row_begin = (const int32_t*)(ln.d_overlay + row_bytes);
+  ov.spot = (const float*)(ln.d_overlay + row_bytes) + n4_of(n_assets) + 1;
+  ov.mask = 0;
+  for (int i = 0; i < n_assets; i++)                           // the padding assets >= N own no rows
+    if (rq.ov->row_begin[i + 1] > rq.ov->row_begin[i]) ov.mask |= (uint64_t)1 << i;
+  return ov;
 }
-static void fill(mcp::PathArgsRB& x, const Request& rq, const Launch& ln) {
-  fill_hz(x, rq, ln);
-  x.bt = boot_block(rq, ln);
-  x.period = rq.reb->period;
-  x.cost = (float)rq.reb->cost;
-}
-
-// The passes of KT portfolios of kernel `k`, whose argument struct is A: PathArgs `a`, then the blocks of A.
-template <class A>
-static int launch_passes(const mcp::PathArgs& a, const Request& rq, const Launch& ln, int variant, const mcp::PathKernel& k, int nb) {
-  A x;
-  static_cast<mcp::PathArgs&>(x) = a;
-  fill(x, rq, ln);
-  const int kt = (variant & mcp::VAR_KT8) ? KT_WIDE : 1;
-  for (int kb = 0; kb < a.n_portfolios; kb += kt) {
-    x.k_begin = kb;
-    const hipError_t e = k_launch[nb - 1](variant, k, x, mcp::path_grid(ln.n_paths), ln.stream);
-    if (e != hipSuccess) return fail(MCP_E_HIP, "path kernel launch (family %d): %s", k.family, hipGetErrorString(e));
-  }
-  return MCP_OK;
+static mcp::AttrArgs attr_block(const Launch& ln, int n_assets) {
+  mcp::AttrArgs at;
+  at.var = ln.d_var;
+  at.partials = ln.d_attr_partials;
+  at.contrib = ln.d_contrib;
+  at.contrib_stride = ln.contrib_stride;
+  at.n_assets = n_assets;
+  at.pad = 0;
+  return at;
 }
 
 // Enqueues the path kernels of a checked request (check_request).  Plain Gaussian walks with K >= 17 run on the MFMA sweep
@@ -1015,14 +968,11 @@ static int launch_passes(const mcp::PathArgs& a, const Request& rq, const Launch
 // gives (what mcp_launch_scan reads): where that is one slot per 64-path tile (K >= 17), an empty pass 0 first pads every slot,
 // and the path kernel's workgroups overwrite the first path_grid(n) of them.
 static int launch_paths_impl(const mcp_params* prm, const Request& rq, const Launch& ln) {
-  const int nb = (prm->n_assets + 3) / 4;
+  const int N = prm->n_assets, nb = (N + 3) / 4;
   const int K = prm->n_portfolios;
   const bool plain = rq.src == SRC_GAUSS && !rq.dd && !rq.hz && !rq.rebalanced && !rq.cash && !rq.overlay && !rq.garch;
-  int variant = 0;
-  if (prm->flags & MCP_FLAG_FOLD) variant |= mcp::VAR_FOLD;
-  if (K > 1) variant |= mcp::VAR_KT8;
-  if (prm->flags & MCP_FLAG_NATIVE_MATH) variant |= mcp::VAR_NATIVE;
-  mcp::PathArgs a;
+  mcp::PathLaunchArgs s = {};             // every block the request does not carry stays empty
+  mcp::PathArgs& a = s.hz;
   const float4* tables = nullptr;
   int dev = 0;
   if (int rc = stream_device(ln.stream, &dev)) return rc;
@@ -1049,7 +999,7 @@ static int launch_paths_impl(const mcp_params* prm, const Request& rq, const Lau
   a.compounding = prm->compounding;
   a.v0 = (float)prm->v0;
   a.k_count = K;
-  a.fold_offset = (uint32_t)(n4_of(prm->n_assets) + n4_of(prm->n_assets) * (n4_of(prm->n_assets) / 2 + 1) + kpad_of(K) * n4_of(prm->n_assets));
+  a.fold_offset = (uint32_t)(n4_of(N) + n4_of(N) * (n4_of(N) / 2 + 1) + kpad_of(K) * n4_of(N));
   if (sweep) {
     const bool native = (prm->flags & MCP_FLAG_NATIVE_MATH) != 0;
     SweepSeg segs[4];
@@ -1072,47 +1022,41 @@ static int launch_paths_impl(const mcp_params* prm, const Request& rq, const Lau
   if (!plain && ln.d_partials && a.slots > (uint64_t)mcp::path_grid(ln.n_paths))
     HIP_TRY(mcp::launch_pass0(*prm, K, ln.d_terminal, ln.stride, 0, nullptr, a.slots, (mcp::MomentPartial*)ln.d_partials,
                               (unsigned long long*)ln.d_hist, ln.stream));
-  if (ln.attr) {                               // SPEC.md 4.10: one portfolio per pass, no terminal store, its own epilogue
-    mcp::PathKernel ka;
-    ka.family = mcp::FAM_AT;
-    ka.logc = ka.boot = ka.blds = false;
-    ka.stt = ka.gv = true;
-    a.partials = nullptr;
-    a.hist = nullptr;
-    Launch la = ln;
-    la.n_assets = prm->n_assets;
-    return launch_passes<mcp::PathArgsAT>(a, rq, la, 0, ka, nb);
-  }
-  mcp::PathKernel k;
-  k.family = rq.overlay ? mcp::FAM_OV : rq.cash ? mcp::FAM_CF : rq.rebalanced ? mcp::FAM_REB : rq.dd ? mcp::FAM_DD : rq.hz ? mcp::FAM_HZ : mcp::FAM_PLAIN;
+  fill_hz(s.hz, rq, ln);
+  s.mdd = rq.dd ? ln.d_mdd : nullptr;
+  s.mdd_stride = rq.dd ? ln.mdd_stride : 0;
+  s.bt = boot_block(rq, ln);
+  s.st = student_block(rq);
+  if (rq.garch) s.gv = garch_block(rq.gv, N);
+  if (rq.cash) s.cf.flows = ln.d_flows;
+  if (rq.overlay) s.ov = overlay_block(rq, ln, N);
+  if (rq.rebalanced) { s.period = rq.reb->period; s.cost = (float)rq.reb->cost; }
+  mcp::PathKernel k = {};
   k.logc = prm->compounding == MCP_COMPOUND_LOG;
   k.boot = rq.src == SRC_BOOT;
   k.blds = k.boot && mcp::boot_fits_lds((uint64_t)rq.boot->n_rows, nb);
   k.stt = rq.src == SRC_T;
-  k.dd = rq.overlay && rq.dd;
-  k.gv = rq.garch;
-  if (k.gv) {
-    Launch lg = ln;
-    lg.n_assets = prm->n_assets;
-    switch (k.family) {
-      case mcp::FAM_DD: return launch_passes<mcp::PathArgsGDD>(a, rq, lg, variant, k, nb);
-      case mcp::FAM_HZ: return launch_passes<mcp::PathArgsGHZ>(a, rq, lg, variant, k, nb);
-      default: return launch_passes<mcp::PathArgsG>(a, rq, lg, variant, k, nb);
-    }
+  if (ln.attr) {
+    // SPEC.md 4.10: one portfolio per pass, no terminal store, its own epilogue.  The walk draws as the GARCH kernel does: without
+    // GARCH on alpha = beta = 0, h0 = 1, which is the Gaussian or Student-t call bit for bit (SPEC.md 4.9).
+    static const mcp_garch none = {0.0, 0.0, 1.0, 0};
+    k.family = mcp::FAM_AT;
+    k.stt = k.gv = true;
+    a.partials = nullptr;
+    a.hist = nullptr;
+    if (!rq.garch) s.gv = garch_block(&none, N);
+    s.at = attr_block(ln, N);
+  } else {
+    k.family = rq.overlay ? mcp::FAM_OV : rq.cash ? mcp::FAM_CF : rq.rebalanced ? mcp::FAM_REB : rq.dd ? mcp::FAM_DD : rq.hz ? mcp::FAM_HZ : mcp::FAM_PLAIN;
+    k.dd = rq.overlay && rq.dd;
+    k.gv = rq.garch;
+    k.kt8 = K > 1;
+    k.native = (prm->flags & MCP_FLAG_NATIVE_MATH) != 0;
+    k.fold = (prm->flags & MCP_FLAG_FOLD) != 0;
   }
-  switch (k.family) {
-    case mcp::FAM_OV: return launch_passes<mcp::PathArgsOV>(a, rq, ln, variant, k, nb);
-    case mcp::FAM_CF: return launch_passes<mcp::PathArgsCF>(a, rq, ln, variant, k, nb);
-    case mcp::FAM_REB: return launch_passes<mcp::PathArgsRB>(a, rq, ln, variant, k, nb);
-    case mcp::FAM_DD: return k.stt ? launch_passes<mcp::PathArgsTDD>(a, rq, ln, variant, k, nb)
-                                   : launch_passes<mcp::PathArgsDD>(a, rq, ln, variant, k, nb);
-    case mcp::FAM_HZ: return k.stt ? launch_passes<mcp::PathArgsTHZ>(a, rq, ln, variant, k, nb)
-                           : k.boot ? launch_passes<mcp::PathArgsBTHZ>(a, rq, ln, variant, k, nb)
-                                    : launch_passes<mcp::PathArgsHZ>(a, rq, ln, variant, k, nb);
-    default: return k.stt ? launch_passes<mcp::PathArgsT>(a, rq, ln, variant, k, nb)
-                  : k.boot ? launch_passes<mcp::PathArgsBT>(a, rq, ln, variant, k, nb)
-                           : launch_passes<mcp::PathArgs>(a, rq, ln, variant, k, nb);
-  }
+  const hipError_t e = k_launch[nb - 1](k, s, ln.stream);
+  if (e != hipSuccess) return fail(MCP_E_HIP, "path kernel launch (family %d): %s", k.family, hipGetErrorString(e));
+  return MCP_OK;
 }
 
 static Launch make_launch(const float* d_packed, const double* d_pivot, uint64_t seed, uint64_t path_begin, uint64_t n_paths,
@@ -1700,8 +1644,6 @@ int run_tile(mcp_ctx* c, const mcp_params* prm, const Request& rq, uint64_t seed
       ln.d_rows = sh.boot.p;
       ln.d_flows = sh.cf.flows.p;
       ln.d_overlay = sh.overlay.p;
-      ln.ov_n = N;
-      ln.ov_n4 = n4_of(N);
       if ((rc = launch_paths_impl(&tp[s], rq, ln))) return rc;
       if (rq.cash) {                                         // SPEC.md 5.6: the ruined and the short paths of every stored row
         const size_t rows_hz = rq.hz ? (size_t)rq.H * j.kt : 0;

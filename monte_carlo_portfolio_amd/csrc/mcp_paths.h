@@ -17,6 +17,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "../../include/mcport.h"
 #include "mcp_device.h"
 #include "mcp_stats_kernels.h"
@@ -72,6 +74,25 @@ typedef float f32x2 __attribute__((ext_vector_type(2)));
 extern __device__ unsigned long long mcp_diag_stamps[2 * 8192];
 #endif
 
+// The kernel arguments as struct A, through the kernel-argument pointer and the constant address space: what is read through it is
+// wave-uniform (scalar loads) and is loaded where it is used -- the compiler cannot see through the pointer, so nothing is held
+// in SGPRs across the walk (the Cholesky factor lives there).
+template <class A>
+__device__ __forceinline__ const __attribute__((address_space(4))) A* kernarg() {
+  typedef const __attribute__((address_space(4))) A* cst_p;
+  cst_p k = (cst_p)__builtin_amdgcn_kernarg_segment_ptr();
+  asm volatile("" : "+s"(k));
+  return k;
+}
+// has_<m><A>: the argument struct A carries the member (block) m.  The block accessors below and make_args ask it inside a
+// template on A: in a kernel the type of `a` is not dependent, so `if constexpr (BOOT) bt = a.bt;` would still be checked there.
+#define MCP_HAS_MEMBER(m)                                                 \
+  template <class A, class = void> struct has_##m : std::false_type {}; \
+  template <class A> struct has_##m<A, std::void_t<decltype(A::m)>> : std::true_type {};
+MCP_HAS_MEMBER(hz) MCP_HAS_MEMBER(mdd) MCP_HAS_MEMBER(bt) MCP_HAS_MEMBER(st) MCP_HAS_MEMBER(gv) MCP_HAS_MEMBER(cf)
+MCP_HAS_MEMBER(ov) MCP_HAS_MEMBER(at) MCP_HAS_MEMBER(period)
+#undef MCP_HAS_MEMBER
+
 struct PathArgs {
   const float* __restrict__ packed;   // [mu N4][L row pairs N4(N4/2+1)][W Kpad*N4]  (mcp_pack_params)
   float* __restrict__ terminal;       // [K][stride]
@@ -116,9 +137,11 @@ struct BootArgs {
 // Arguments of mc_paths_boot_kernel / mc_paths_boot_hz_kernel: PathArgs (PathArgsHZ) first, as for the drawdown kernel.
 struct PathArgsBT : PathArgs { BootArgs bt; };
 struct PathArgsBTHZ : PathArgsHZ { BootArgs bt; };
-__device__ __forceinline__ BootArgs boot_args(const PathArgs&) { return BootArgs{}; }
-__device__ __forceinline__ BootArgs boot_args(const PathArgsBT& a) { return a.bt; }
-__device__ __forceinline__ BootArgs boot_args(const PathArgsBTHZ& a) { return a.bt; }
+template <class A>
+__device__ __forceinline__ BootArgs boot_args(const A& a) {
+  if constexpr (has_bt<A>::value) return a.bt;
+  else return BootArgs{};
+}
 // Arguments of mc_paths_reb_kernel (SPEC.md 4.5): the horizons of PathArgsHZ (n_horizons = 0: none), the row table of the
 // bootstrap (read only when BOOT) and the rebalancing rule.
 struct PathArgsRB : PathArgsHZ {
@@ -126,7 +149,6 @@ struct PathArgsRB : PathArgsHZ {
   int32_t period;                     // m >= 0: a rebalance after every step s with s mod m == 0 and s < T (0: never)
   float cost;                         // kappa32 = fl32(kappa), in [0, 1)
 };
-__device__ __forceinline__ BootArgs boot_args(const PathArgsRB& a) { return a.bt; }
 // The Student-t draws of SPEC.md 2.2 / 4.6: the degrees of freedom nu in [3, MCP_MAX_T_DOF], wave-uniform.  Appended to the
 // arguments of the plain, drawdown and horizon kernels (mc_paths_t_kernel, mc_paths_t_dd_kernel, mc_paths_t_hz_kernel).
 struct StudentArgs {
@@ -136,19 +158,13 @@ struct StudentArgs {
 struct PathArgsT : PathArgs { StudentArgs st; };
 struct PathArgsTDD : PathArgsDD { StudentArgs st; };
 struct PathArgsTHZ : PathArgsHZ { StudentArgs st; };
-// nu of a t kernel's launch, read through the kernel-argument pointer where it is needed (nothing held in SGPRs across the walk:
-// the Cholesky factor lives there); the argument only selects the kernel's argument type.
+// nu of a launch whose arguments carry the Student-t block, read where it is needed (kernarg); the argument only selects the
+// kernel's argument type.
 template <class A>
-__device__ __forceinline__ int32_t kernarg_dof() {
-  typedef const __attribute__((address_space(4))) A* cst_p;
-  cst_p k = (cst_p)__builtin_amdgcn_kernarg_segment_ptr();
-  asm volatile("" : "+s"(k));
-  return k->st.dof;
+__device__ __forceinline__ int32_t student_dof(const A&) {
+  if constexpr (has_st<A>::value) return kernarg<A>()->st.dof;
+  else return 0;
 }
-__device__ __forceinline__ int32_t student_dof(const PathArgs&) { return 0; }
-__device__ __forceinline__ int32_t student_dof(const PathArgsT&) { return kernarg_dof<PathArgsT>(); }
-__device__ __forceinline__ int32_t student_dof(const PathArgsTDD&) { return kernarg_dof<PathArgsTDD>(); }
-__device__ __forceinline__ int32_t student_dof(const PathArgsTHZ&) { return kernarg_dof<PathArgsTHZ>(); }
 
 // GARCH(1,1) on the covariance (SPEC.md 4.9): the host constants a_N = fl32(a / N), b, omega = fl32(1 - a - b), the start h0 of the
 // per-path variance ratio h, and N (the padding normals j >= N stay out of the step's shock q).  Appended, after the degrees of
@@ -162,23 +178,13 @@ struct GarchArgs {
 struct PathArgsG : PathArgs { StudentArgs st; GarchArgs gv; };
 struct PathArgsGDD : PathArgsDD { StudentArgs st; GarchArgs gv; };
 struct PathArgsGHZ : PathArgsHZ { StudentArgs st; GarchArgs gv; };
-__device__ __forceinline__ int32_t student_dof(const PathArgsG&) { return kernarg_dof<PathArgsG>(); }
-__device__ __forceinline__ int32_t student_dof(const PathArgsGDD&) { return kernarg_dof<PathArgsGDD>(); }
-__device__ __forceinline__ int32_t student_dof(const PathArgsGHZ&) { return kernarg_dof<PathArgsGHZ>(); }
-// The GARCH block of a g kernel's launch: wave-uniform and read-only, read where it is used through the kernel-argument pointer
-// and the constant address space (scalar loads; nothing held in SGPRs across the walk: the Cholesky factor lives there).
+// The GARCH block of a g kernel's launch, read where it is used (kernarg).
 typedef const __attribute__((address_space(4))) GarchArgs* cgarch_p;
 template <class A>
-__device__ __forceinline__ cgarch_p kernarg_garch() {
-  typedef const __attribute__((address_space(4))) A* cg_p;
-  cg_p k = (cg_p)__builtin_amdgcn_kernarg_segment_ptr();
-  asm volatile("" : "+s"(k));
-  return &k->gv;
+__device__ __forceinline__ cgarch_p garch_args(const A&) {
+  if constexpr (has_gv<A>::value) return &kernarg<A>()->gv;
+  else return nullptr;
 }
-__device__ __forceinline__ cgarch_p garch_args(const PathArgs&) { return nullptr; }
-__device__ __forceinline__ cgarch_p garch_args(const PathArgsG&) { return kernarg_garch<PathArgsG>(); }
-__device__ __forceinline__ cgarch_p garch_args(const PathArgsGDD&) { return kernarg_garch<PathArgsGDD>(); }
-__device__ __forceinline__ cgarch_p garch_args(const PathArgsGHZ&) { return kernarg_garch<PathArgsGHZ>(); }
 
 // Risk attribution (SPEC.md 4.10 / 5.9): the second walk of one portfolio per pass that carries the assets' contributions A_i.
 // var: the VaR of every portfolio from the call's statistics (the tail is x <= var); partials: one record of ATTR_HEAD + 3 N4
@@ -197,15 +203,6 @@ struct AttrArgs {
 // Arguments of mc_paths_attr_kernel: those of mc_paths_g_kernel (student_dof and garch_args read them at the same offsets) and the
 // attribution block.
 struct PathArgsAT : PathArgsG { AttrArgs at; };
-// The attribution block of an attribution kernel's launch: read after the walk through the kernel-argument pointer (scalar loads;
-// nothing held in SGPRs across the walk: the Cholesky factor lives there).
-typedef const __attribute__((address_space(4))) AttrArgs* cattr_p;
-__device__ __forceinline__ cattr_p attr_kernarg() {
-  typedef const __attribute__((address_space(4))) PathArgsAT* cat_p;
-  cat_p k = (cat_p)__builtin_amdgcn_kernarg_segment_ptr();
-  asm volatile("" : "+s"(k));
-  return &k->at;
-}
 // The per-wave accumulators of the attribution epilogue: PATH_BLOCK / 64 records in LDS (mc_paths_attr_kernel only).
 template <int N4>
 __device__ __forceinline__ double* attr_wave_slots() {
@@ -224,17 +221,12 @@ struct PathArgsCF : PathArgsHZ {
   StudentArgs st;
   CashArgs cf;
 };
-__device__ __forceinline__ BootArgs boot_args(const PathArgsCF& a) { return a.bt; }
-__device__ __forceinline__ int32_t student_dof(const PathArgsCF&) { return kernarg_dof<PathArgsCF>(); }
-// c_{t+1} of a cash-flow kernel's launch: wave-uniform, read where it is used through the kernel-argument pointer and the constant
-// address space (two scalar loads per step; nothing held in SGPRs across the walk: the Cholesky factor lives there).
-__device__ __forceinline__ float cash_flow(const PathArgs&, int) { return 0.0f; }
-__device__ __forceinline__ float cash_flow(const PathArgsCF&, int t) {
-  typedef const __attribute__((address_space(4))) PathArgsCF* ccf_p;
+// c_{t+1} of a cash-flow kernel's launch, read where it is used (kernarg): two scalar loads per step.
+template <class A>
+__device__ __forceinline__ float cash_flow(const A&, int t) {
   typedef const __attribute__((address_space(4))) float* cflow_p;
-  ccf_p k = (ccf_p)__builtin_amdgcn_kernarg_segment_ptr();
-  asm volatile("" : "+s"(k));
-  return ((cflow_p)k->cf.flows)[t];
+  if constexpr (has_cf<A>::value) return ((cflow_p)kernarg<A>()->cf.flows)[t];
+  else return 0.0f;
 }
 
 // The option overlay of SPEC.md 4.8: per asset a run of rows (kind, strike, premium, qty) that turns the raw return r_i of a step
@@ -254,15 +246,6 @@ struct PathArgsOV : PathArgsHZ {
   StudentArgs st;
   OverlayArgs ov;
 };
-__device__ __forceinline__ int32_t student_dof(const PathArgsOV&) { return kernarg_dof<PathArgsOV>(); }
-// The overlay of an overlay kernel's launch: wave-uniform and read-only, read where it is used through the kernel-argument pointer
-// and the constant address space (scalar loads; nothing held in SGPRs across the walk: the Cholesky factor lives there).
-typedef const __attribute__((address_space(4))) PathArgsOV* cov_p;
-__device__ __forceinline__ cov_p overlay_kernarg() {
-  cov_p k = (cov_p)__builtin_amdgcn_kernarg_segment_ptr();
-  asm volatile("" : "+s"(k));
-  return k;
-}
 // r'_i of SPEC.md 4.8 for an asset that owns the rows [rb, re): price = fma(prev, r, prev); num = fma(q_j, leg_j, num) over the
 // rows in order from +0; r' = prev != 0 ? num / prev : +0 (IEEE division); P_i = price.  The loop over the rows is a run-time loop
 // on wave-uniform bounds; every row is four scalar loads.
@@ -273,7 +256,7 @@ __device__ __forceinline__ float overlay_return(float r, float& P, int rb, int r
   float num = 0.0f;
 #pragma unroll 1
   for (int j = rb; j < re; j++) {
-    const crow_p row = (crow_p)overlay_kernarg()->ov.rows + j;
+    const crow_p row = (crow_p)kernarg<PathArgsOV>()->ov.rows + j;
     const int32_t kind = row->kind;
     const float strike = row->strike, premium = row->premium, qty = row->qty;
     float leg;
@@ -287,6 +270,37 @@ __device__ __forceinline__ float overlay_return(float r, float& P, int rb, int r
   }
   P = price;
   return prev != 0.0f ? num / prev : 0.0f;
+}
+
+// Everything a launch of a path kernel may carry: mcp_api.cpp fills it once per launch, and a block the request does not have
+// stays zero.  make_args builds the argument struct A of one kernel from it by value: PathArgs, then the blocks A has.
+struct PathLaunchArgs {
+  PathArgsHZ hz;                      // PathArgs and the horizons (n_horizons = 0: none)
+  float* mdd;                         // the drawdown output
+  uint64_t mdd_stride;
+  BootArgs bt;
+  StudentArgs st;
+  GarchArgs gv;
+  CashArgs cf;
+  OverlayArgs ov;
+  AttrArgs at;
+  int32_t period;                     // the rebalancing rule of PathArgsRB
+  float cost;
+};
+template <class A>
+inline A make_args(const PathLaunchArgs& s) {
+  A x;
+  if constexpr (has_hz<A>::value) static_cast<PathArgsHZ&>(x) = s.hz;
+  else static_cast<PathArgs&>(x) = s.hz;
+  if constexpr (has_mdd<A>::value) { x.mdd = s.mdd; x.mdd_stride = s.mdd_stride; }
+  if constexpr (has_bt<A>::value) x.bt = s.bt;
+  if constexpr (has_st<A>::value) x.st = s.st;
+  if constexpr (has_gv<A>::value) x.gv = s.gv;
+  if constexpr (has_cf<A>::value) x.cf = s.cf;
+  if constexpr (has_ov<A>::value) x.ov = s.ov;
+  if constexpr (has_at<A>::value) x.at = s.at;
+  if constexpr (has_period<A>::value) { x.period = s.period; x.cost = s.cost; }
+  return x;
 }
 
 // The LDS copy of the row table takes the slot of the inverse-CDF table (ICDF_LDS_ENTRIES float4: the bootstrap needs neither
@@ -371,55 +385,68 @@ constexpr int PATH_BLOCK = 256;
 // the weight dot (SPEC.md 4.8).  GV: the step's normals are scaled by u = sqrt(h) (STT: times s), h the path's GARCH(1,1) variance
 // ratio, and h is updated from the scaled normals (SPEC.md 4.9); in a GV kernel STT is set and nu = 0 at run time means Gaussian
 // draws.  AT: the step also carries every asset's contribution A_i = fma(V, fl32(w_i r_i), A_i) and the epilogue reduces them
-// (SPEC.md 4.10 / 5.9).  All fifteen kernels are the body in mcp_paths_body.inc.
-#define MCP_PATHS_BOUNDS(NB, KT, PPT) \
-  __launch_bounds__(PATH_BLOCK, (NB <= 4 && KT == 1 && PPT == 1) ? MCP_MIN_WAVES : ((KT == 1 && PPT == 1) ? MCP_MIN_WAVES_BIG : 1))
-#define MCP_REB_BOUNDS(NB, KT, PPT) \
-  __launch_bounds__(PATH_BLOCK, (NB <= 4 && PPT == 1) ? (KT == 1 ? MCP_MIN_WAVES_REB : MCP_MIN_WAVES_REB8) \
-                                                     : ((KT == 1 && PPT == 1) ? MCP_MIN_WAVES_BIG : 1))
+// (SPEC.md 4.10 / 5.9).  Every kernel below is the body in mcp_paths_body.inc under its own flags F: it names the flags it sets, the
+// rest are PathFlagsOff's.  F is a local class, which may not have static data members, so it sets its flags as enumerators of an
+// `enum : bool`; they hide the defaults' names and read as the same constant expressions.
+struct PathFlagsOff {
+  static constexpr bool NATIVE = false, FOLD = false, LOGC = false, DD = false, HZ = false, BOOT = false, BLDS = false, REB = false,
+                        STT = false, CF = false, OV = false, GV = false, AT = false;
+};
 
-template <int NB, int KT, int PPT, bool NATIVE, bool FOLD = false, bool LOGC = false>
-__global__ void MCP_PATHS_BOUNDS(NB, KT, PPT) mc_paths_kernel(const PathArgs a) {
-  constexpr bool DD = false, HZ = false, BOOT = false, BLDS = false, REB = false, STT = false, CF = false, OV = false, GV = false, AT = false;
+// __launch_bounds__ 2nd argument of a path kernel: the MCP_MIN_WAVES* above for N <= 16 and one path per lane, by the kind of
+// state the kernel carries; MCP_MIN_WAVES_BIG for 16 < N <= 64 and one portfolio; otherwise unbounded.
+enum BoundsKind { BK_PATHS, BK_REB, BK_CF, BK_OV, BK_AT };
+constexpr int min_waves(BoundsKind kind, int NB, int KT, int PPT) {
+  if (NB <= 4 && PPT == 1 && KT == 1)
+    return kind == BK_REB ? MCP_MIN_WAVES_REB : kind == BK_OV ? MCP_MIN_WAVES_OV : kind == BK_AT ? MCP_MIN_WAVES_AT : MCP_MIN_WAVES;
+  if (NB <= 4 && PPT == 1 && kind != BK_PATHS && kind != BK_AT)
+    return kind == BK_REB ? MCP_MIN_WAVES_REB8 : kind == BK_CF ? MCP_MIN_WAVES_CF8 : MCP_MIN_WAVES_OV8;
+  return (KT == 1 && PPT == 1) ? MCP_MIN_WAVES_BIG : 1;
+}
+#define MCP_BOUNDS(kind) __launch_bounds__(PATH_BLOCK, min_waves(kind, NB, KT, PPT))
+
+template <int NB, int KT, int PPT, bool NATIVE_, bool FOLD_ = false, bool LOGC_ = false>
+__global__ void MCP_BOUNDS(BK_PATHS) mc_paths_kernel(const PathArgs a) {
+  struct F : PathFlagsOff { enum : bool { NATIVE = NATIVE_, FOLD = FOLD_, LOGC = LOGC_ }; };
 #include "mcp_paths_body.inc"
 }
 
 // The drawdown kernel (SPEC.md 4.2; spec normals, unfolded recurrence only).  Its arguments are PathArgs plus the drawdown
 // array: appended to PathArgs itself they would move the hidden kernel arguments (grid size) of every plain kernel.
-template <int NB, int KT, int PPT, bool LOGC>
-__global__ void MCP_PATHS_BOUNDS(NB, KT, PPT) mc_paths_dd_kernel(const PathArgsDD a) {
-  constexpr bool DD = true, HZ = false, NATIVE = false, FOLD = false, BOOT = false, BLDS = false, REB = false, STT = false, CF = false, OV = false, GV = false, AT = false;
+template <int NB, int KT, int PPT, bool LOGC_>
+__global__ void MCP_BOUNDS(BK_PATHS) mc_paths_dd_kernel(const PathArgsDD a) {
+  struct F : PathFlagsOff { enum : bool { DD = true, LOGC = LOGC_ }; };
 #include "mcp_paths_body.inc"
 }
 
 // The horizon kernel (SPEC.md 4.3; spec normals, unfolded recurrence only): the walk of mc_paths_kernel in segments that end
 // at the horizons, V_h stored after each; V_T and the fused epilogue as in mc_paths_kernel.
-template <int NB, int KT, int PPT, bool LOGC>
-__global__ void MCP_PATHS_BOUNDS(NB, KT, PPT) mc_paths_hz_kernel(const PathArgsHZ a) {
-  constexpr bool DD = false, HZ = true, NATIVE = false, FOLD = false, BOOT = false, BLDS = false, REB = false, STT = false, CF = false, OV = false, GV = false, AT = false;
+template <int NB, int KT, int PPT, bool LOGC_>
+__global__ void MCP_BOUNDS(BK_PATHS) mc_paths_hz_kernel(const PathArgsHZ a) {
+  struct F : PathFlagsOff { enum : bool { HZ = true, LOGC = LOGC_ }; };
 #include "mcp_paths_body.inc"
 }
 
 // The bootstrap kernel (SPEC.md 2.1 / 4.4): the walk of mc_paths_kernel on resampled rows of observed returns, one Philox
 // block per path-step for the row index, no normals, no Cholesky GEMV.  V_T and the fused epilogue as in mc_paths_kernel.
-template <int NB, int KT, int PPT, bool LOGC, bool BLDS>
-__global__ void MCP_PATHS_BOUNDS(NB, KT, PPT) mc_paths_boot_kernel(const PathArgsBT a) {
-  constexpr bool DD = false, HZ = false, NATIVE = false, FOLD = false, BOOT = true, REB = false, STT = false, CF = false, OV = false, GV = false, AT = false;
+template <int NB, int KT, int PPT, bool LOGC_, bool BLDS_>
+__global__ void MCP_BOUNDS(BK_PATHS) mc_paths_boot_kernel(const PathArgsBT a) {
+  struct F : PathFlagsOff { enum : bool { BOOT = true, LOGC = LOGC_, BLDS = BLDS_ }; };
 #include "mcp_paths_body.inc"
 }
 
 // The bootstrap kernel with the horizons of SPEC.md 4.3 (the segmented walk of mc_paths_hz_kernel).
-template <int NB, int KT, int PPT, bool LOGC, bool BLDS>
-__global__ void MCP_PATHS_BOUNDS(NB, KT, PPT) mc_paths_boot_hz_kernel(const PathArgsBTHZ a) {
-  constexpr bool DD = false, HZ = true, NATIVE = false, FOLD = false, BOOT = true, REB = false, STT = false, CF = false, OV = false, GV = false, AT = false;
+template <int NB, int KT, int PPT, bool LOGC_, bool BLDS_>
+__global__ void MCP_BOUNDS(BK_PATHS) mc_paths_boot_hz_kernel(const PathArgsBTHZ a) {
+  struct F : PathFlagsOff { enum : bool { HZ = true, BOOT = true, LOGC = LOGC_, BLDS = BLDS_ }; };
 #include "mcp_paths_body.inc"
 }
 // The rebalancing kernel (SPEC.md 4.5; simple compounding, Gaussian draws or, BOOT, the bootstrap's rows): the walk in segments
 // that end at the events -- rebalance dates, horizons, T -- where V^ = V (1 + W.B) is marked.  H = 0 is one segment, so one
 // kernel serves terminal-only and horizon calls.  V_T and the fused epilogue as in mc_paths_kernel.
-template <int NB, int KT, int PPT, bool BOOT, bool BLDS>
-__global__ void MCP_REB_BOUNDS(NB, KT, PPT) mc_paths_reb_kernel(const PathArgsRB a) {
-  constexpr bool DD = false, HZ = false, NATIVE = false, FOLD = false, LOGC = false, REB = true, STT = false, CF = false, OV = false, GV = false, AT = false;
+template <int NB, int KT, int PPT, bool BOOT_, bool BLDS_>
+__global__ void MCP_BOUNDS(BK_REB) mc_paths_reb_kernel(const PathArgsRB a) {
+  struct F : PathFlagsOff { enum : bool { REB = true, BOOT = BOOT_, BLDS = BLDS_ }; };
 #include "mcp_paths_body.inc"
 }
 
@@ -427,18 +454,18 @@ __global__ void MCP_REB_BOUNDS(NB, KT, PPT) mc_paths_reb_kernel(const PathArgsRB
 // mc_paths_hz_kernel with every step's normals scaled by the step's s.  V_T, the drawdown, the horizons and the fused epilogue as
 // there.
 template <int NB, int KT, int PPT>
-__global__ void MCP_PATHS_BOUNDS(NB, KT, PPT) mc_paths_t_kernel(const PathArgsT a) {
-  constexpr bool DD = false, HZ = false, NATIVE = false, FOLD = false, LOGC = false, BOOT = false, BLDS = false, REB = false, STT = true, CF = false, OV = false, GV = false, AT = false;
+__global__ void MCP_BOUNDS(BK_PATHS) mc_paths_t_kernel(const PathArgsT a) {
+  struct F : PathFlagsOff { enum : bool { STT = true }; };
 #include "mcp_paths_body.inc"
 }
 template <int NB, int KT, int PPT>
-__global__ void MCP_PATHS_BOUNDS(NB, KT, PPT) mc_paths_t_dd_kernel(const PathArgsTDD a) {
-  constexpr bool DD = true, HZ = false, NATIVE = false, FOLD = false, LOGC = false, BOOT = false, BLDS = false, REB = false, STT = true, CF = false, OV = false, GV = false, AT = false;
+__global__ void MCP_BOUNDS(BK_PATHS) mc_paths_t_dd_kernel(const PathArgsTDD a) {
+  struct F : PathFlagsOff { enum : bool { DD = true, STT = true }; };
 #include "mcp_paths_body.inc"
 }
 template <int NB, int KT, int PPT>
-__global__ void MCP_PATHS_BOUNDS(NB, KT, PPT) mc_paths_t_hz_kernel(const PathArgsTHZ a) {
-  constexpr bool DD = false, HZ = true, NATIVE = false, FOLD = false, LOGC = false, BOOT = false, BLDS = false, REB = false, STT = true, CF = false, OV = false, GV = false, AT = false;
+__global__ void MCP_BOUNDS(BK_PATHS) mc_paths_t_hz_kernel(const PathArgsTHZ a) {
+  struct F : PathFlagsOff { enum : bool { HZ = true, STT = true }; };
 #include "mcp_paths_body.inc"
 }
 
@@ -448,18 +475,18 @@ __global__ void MCP_PATHS_BOUNDS(NB, KT, PPT) mc_paths_t_hz_kernel(const PathArg
 // V_T, the drawdown, the horizons and the fused epilogue as there.  They keep the plain kernel's launch bounds: no listing shows
 // scratch in a step loop (profiles/garch_isa.txt).
 template <int NB, int KT, int PPT>
-__global__ void MCP_PATHS_BOUNDS(NB, KT, PPT) mc_paths_g_kernel(const PathArgsG a) {
-  constexpr bool DD = false, HZ = false, NATIVE = false, FOLD = false, LOGC = false, BOOT = false, BLDS = false, REB = false, STT = true, CF = false, OV = false, GV = true, AT = false;
+__global__ void MCP_BOUNDS(BK_PATHS) mc_paths_g_kernel(const PathArgsG a) {
+  struct F : PathFlagsOff { enum : bool { STT = true, GV = true }; };
 #include "mcp_paths_body.inc"
 }
 template <int NB, int KT, int PPT>
-__global__ void MCP_PATHS_BOUNDS(NB, KT, PPT) mc_paths_g_dd_kernel(const PathArgsGDD a) {
-  constexpr bool DD = true, HZ = false, NATIVE = false, FOLD = false, LOGC = false, BOOT = false, BLDS = false, REB = false, STT = true, CF = false, OV = false, GV = true, AT = false;
+__global__ void MCP_BOUNDS(BK_PATHS) mc_paths_g_dd_kernel(const PathArgsGDD a) {
+  struct F : PathFlagsOff { enum : bool { DD = true, STT = true, GV = true }; };
 #include "mcp_paths_body.inc"
 }
 template <int NB, int KT, int PPT>
-__global__ void MCP_PATHS_BOUNDS(NB, KT, PPT) mc_paths_g_hz_kernel(const PathArgsGHZ a) {
-  constexpr bool DD = false, HZ = true, NATIVE = false, FOLD = false, LOGC = false, BOOT = false, BLDS = false, REB = false, STT = true, CF = false, OV = false, GV = true, AT = false;
+__global__ void MCP_BOUNDS(BK_PATHS) mc_paths_g_hz_kernel(const PathArgsGHZ a) {
+  struct F : PathFlagsOff { enum : bool { HZ = true, STT = true, GV = true }; };
 #include "mcp_paths_body.inc"
 }
 
@@ -467,12 +494,9 @@ __global__ void MCP_PATHS_BOUNDS(NB, KT, PPT) mc_paths_g_hz_kernel(const PathArg
 // Student-t draws): the segmented walk of mc_paths_hz_kernel with U = fma(V, rho, V) + c_s after every step and V = U while both
 // V and U are positive, +0 from then on.  H = 0 is one segment, so one kernel serves terminal-only and horizon calls.  V_T, the
 // horizons and the fused epilogue as in mc_paths_hz_kernel.
-#define MCP_CF_BOUNDS(NB, KT, PPT) \
-  __launch_bounds__(PATH_BLOCK, (NB <= 4 && PPT == 1) ? (KT == 1 ? MCP_MIN_WAVES : MCP_MIN_WAVES_CF8) \
-                                                     : ((KT == 1 && PPT == 1) ? MCP_MIN_WAVES_BIG : 1))
-template <int NB, int KT, int PPT, bool BOOT, bool BLDS, bool STT>
-__global__ void MCP_CF_BOUNDS(NB, KT, PPT) mc_paths_cf_kernel(const PathArgsCF a) {
-  constexpr bool DD = false, HZ = true, NATIVE = false, FOLD = false, LOGC = false, REB = false, CF = true, OV = false, GV = false, AT = false;
+template <int NB, int KT, int PPT, bool BOOT_, bool BLDS_, bool STT_>
+__global__ void MCP_BOUNDS(BK_CF) mc_paths_cf_kernel(const PathArgsCF a) {
+  struct F : PathFlagsOff { enum : bool { HZ = true, CF = true, BOOT = BOOT_, BLDS = BLDS_, STT = STT_ }; };
 #include "mcp_paths_body.inc"
 }
 
@@ -480,12 +504,9 @@ __global__ void MCP_CF_BOUNDS(NB, KT, PPT) mc_paths_cf_kernel(const PathArgsCF a
 // walk of mc_paths_hz_kernel with every asset's return replaced by its option rows' return at the price level the kernel carries.
 // H = 0 is one segment, so one kernel serves terminal-only and horizon calls; DD adds the drawdown state of mc_paths_dd_kernel.
 // V_T, the horizons, the drawdown and the fused epilogue as in those kernels.
-#define MCP_OV_BOUNDS(NB, KT, PPT) \
-  __launch_bounds__(PATH_BLOCK, (NB <= 4 && PPT == 1) ? (KT == 1 ? MCP_MIN_WAVES_OV : MCP_MIN_WAVES_OV8) \
-                                                     : ((KT == 1 && PPT == 1) ? MCP_MIN_WAVES_BIG : 1))
-template <int NB, int KT, int PPT, bool STT, bool DD>
-__global__ void MCP_OV_BOUNDS(NB, KT, PPT) mc_paths_ov_kernel(const PathArgsOV a) {
-  constexpr bool HZ = true, NATIVE = false, FOLD = false, LOGC = false, BOOT = false, BLDS = false, REB = false, CF = false, OV = true, GV = false, AT = false;
+template <int NB, int KT, int PPT, bool STT_, bool DD_>
+__global__ void MCP_BOUNDS(BK_OV) mc_paths_ov_kernel(const PathArgsOV a) {
+  struct F : PathFlagsOff { enum : bool { HZ = true, OV = true, STT = STT_, DD = DD_ }; };
 #include "mcp_paths_body.inc"
 }
 
@@ -494,18 +515,12 @@ __global__ void MCP_OV_BOUNDS(NB, KT, PPT) mc_paths_ov_kernel(const PathArgsOV a
 // the contribution A_i of every asset carried next to V: per pair of assets one packed multiply (w r) and one packed fma (V
 // broadcast).  No terminal store and no fused statistics epilogue; its own epilogue reduces A, A over the tail x <= var and
 // A (x - c) to one record per workgroup, in a fixed order, and stores A when asked to.
-#define MCP_AT_BOUNDS(NB, KT, PPT) \
-  __launch_bounds__(PATH_BLOCK, (NB <= 4 && KT == 1 && PPT == 1) ? MCP_MIN_WAVES_AT : ((KT == 1 && PPT == 1) ? MCP_MIN_WAVES_BIG : 1))
 template <int NB, int KT, int PPT>
-__global__ void MCP_AT_BOUNDS(NB, KT, PPT) mc_paths_attr_kernel(const PathArgsAT a) {
+__global__ void MCP_BOUNDS(BK_AT) mc_paths_attr_kernel(const PathArgsAT a) {
   static_assert(KT == 1, "one portfolio per pass");
-  constexpr bool DD = false, HZ = false, NATIVE = false, FOLD = false, LOGC = false, BOOT = false, BLDS = false, REB = false, STT = true, CF = false, OV = false, GV = true, AT = true;
+  struct F : PathFlagsOff { enum : bool { STT = true, GV = true, AT = true }; };
 #include "mcp_paths_body.inc"
 }
-#undef MCP_AT_BOUNDS
-#undef MCP_OV_BOUNDS
-#undef MCP_PATHS_BOUNDS
-#undef MCP_REB_BOUNDS
-#undef MCP_CF_BOUNDS
+#undef MCP_BOUNDS
 
 }  // namespace mcp

@@ -1,13 +1,10 @@
-// mcp_paths_body.inc -- the body of the path kernels of mcp_paths.h, included textually by mc_paths_kernel (DD = HZ = false),
-// mc_paths_dd_kernel (DD = true), mc_paths_hz_kernel (HZ = true), the bootstrap kernels mc_paths_boot_kernel (BOOT = true)
-// and mc_paths_boot_hz_kernel (BOOT = HZ = true), the rebalancing kernel mc_paths_reb_kernel (REB = true, BOOT either) and the
-// Student-t kernels mc_paths_t_kernel / mc_paths_t_dd_kernel / mc_paths_t_hz_kernel (STT = true, DD or HZ as their twins);
-// and the cash-flow kernel mc_paths_cf_kernel (CF = HZ = true, BOOT or STT either) and the overlay kernel mc_paths_ov_kernel
-// (OV = HZ = true, STT or DD either) and the GARCH kernels mc_paths_g_kernel / mc_paths_g_dd_kernel / mc_paths_g_hz_kernel (GV =
-// STT = true, DD or HZ as their twins); the step itself is mcp_paths_step.inc.  As a shared __device__ function the plain kernel's registers came out allocated differently;
-// included, the DD = false kernel compiles to the same instructions as before the drawdown existed.  In scope: the template
-// parameters NB, KT, PPT, NATIVE, FOLD, LOGC, DD, HZ, BOOT, BLDS, REB, STT, CF, OV, GV, AT and the kernel argument `a` (PathArgs, or PathArgsDD /
-// PathArgsHZ / PathArgsBT / PathArgsBTHZ / PathArgsRB / PathArgsT / PathArgsTDD / PathArgsTHZ / PathArgsCF / PathArgsOV / PathArgsG / PathArgsGDD / PathArgsGHZ / PathArgsAT which start with one).  AT (mc_paths_attr_kernel, GV = STT = true): the contributions of SPEC.md 4.10 and their own epilogue; every AT block is an `if constexpr`, so the other kernels keep their code.  Without HZ the walk is the one loop it always was, so the plain and drawdown kernels keep their code.
+// mcp_paths_body.inc -- the body of every path kernel of mcp_paths.h (they are listed there, each with the flags it sets); the
+// step itself is mcp_paths_step.inc.  Included textually: as a shared __device__ function the plain kernel's registers came out
+// allocated differently.  Every feature is an `if constexpr` on its flag, so a kernel without it keeps its code; without HZ the
+// walk is the one loop it always was.  In scope: the template parameters NB, KT, PPT, the flags F (PathFlagsOff or a struct
+// derived from it) and the kernel argument `a` (PathArgs or a struct that starts with one).
+  constexpr bool NATIVE = F::NATIVE, FOLD = F::FOLD, LOGC = F::LOGC, DD = F::DD, HZ = F::HZ, BOOT = F::BOOT, BLDS = F::BLDS, REB = F::REB,
+                 STT = F::STT, CF = F::CF, OV = F::OV, GV = F::GV, AT = F::AT;
   constexpr int N4 = 4 * NB;
   // wave-uniform parameters through the constant address space -> s_load_dword* into SGPRs
   typedef const __attribute__((address_space(4))) float* cfloat_p;
@@ -46,7 +43,8 @@
   __shared__ unsigned long long s_cnt[PATH_BLOCK / 64];
   // The epilogue's own arguments (pivot, partials, hist, slots, v0d: 13 dwords) are read from the kernel-argument segment
   // AFTER the step loop, through a pointer the compiler cannot see through: loaded up front they would sit in SGPRs for the
-  // whole walk, and the kernel has none to spare (the Cholesky factor is fed from SGPRs): they spilled into VGPR lanes.
+  // whole walk, and the kernel has none to spare (the Cholesky factor is fed from SGPRs): they spilled into VGPR lanes.  One
+  // pointer, made opaque again in place before each use (not kernarg<PathArgs>() at each use: that moves every kernel's code).
   typedef const __attribute__((address_space(4))) PathArgs* cargs_p;
   cargs_p kargs = (cargs_p)__builtin_amdgcn_kernarg_segment_ptr();
   for (int i = threadIdx.x; i < MCP_SELECT_BINS; i += PATH_BLOCK) s_hist[i] = 0u;
@@ -110,7 +108,7 @@
       }
       if constexpr (OV) {                                 // P_i = fl32(spot_i), scalar loads once per tile
         typedef const __attribute__((address_space(4))) float* cspot_p;
-        const cspot_p sp = (cspot_p)overlay_kernarg()->ov.spot;
+        const cspot_p sp = (cspot_p)kernarg<PathArgsOV>()->ov.spot;
 #pragma unroll
         for (int i = 0; i < N4; i++) Ps[e][i] = sp[i];
       }
@@ -120,21 +118,16 @@
       // SPEC.md 4.5: the walk in segments that end at the events -- the next rebalance date nd, the next horizon, T.  Between
       // events the step updates B only.  At an event: the mark rho^_k = W_k.B (i ascending) and V^_k = fma(V_k, rho^_k, V_k),
       // the horizon store of V^, and at a date the trade (V_k = fma(V_k, rho'_k, V_k), B = +0) or, at T, V = V^.  The period,
-      // cost and horizons are read through the kernel-argument pointer where they are needed, wave-uniform (nothing held in
-      // SGPRs across the walk: the Cholesky factor lives there); every branch below is on wave-uniform values.
-      typedef const __attribute__((address_space(4))) PathArgsRB* crb_p;
-      const crb_p rk = (crb_p)__builtin_amdgcn_kernarg_segment_ptr();
+      // cost and horizons are read where they are needed (kernarg), wave-uniform; every branch below is on wave-uniform values.
       int nd;                                              // the next rebalance date (s mod m == 0, s < T), T if none is left
       {
-        crb_p rs = rk;
-        asm volatile("" : "+s"(rs));
+        const auto rs = kernarg<PathArgsRB>();
         const int per = rs->period;
         nd = (per >= 1 && per < T) ? per : T;
       }
       int t = 0, hi = 0;
       while (t < T) {
-        crb_p rs = rk;
-        asm volatile("" : "+s"(rs));
+        const auto rs = kernarg<PathArgsRB>();
         const int t_hz = hi < rs->n_horizons ? rs->steps[hi] : T;
         const int t_end = min(nd, t_hz);
         for (; t < t_end; t++) {
@@ -155,8 +148,7 @@
             rh[e][k] = acc;
             vh[e][k] = fma32(V[e][k], acc, V[e][k]);
           }
-        crb_p hs = rk;
-        asm volatile("" : "+s"(hs));
+        const auto hs = kernarg<PathArgsRB>();
         if (hi < hs->n_horizons && hs->steps[hi] == t) {   // V_h of SPEC.md 4.3, before any trade of step h (t_hz may be T with no
                                                            // horizon left: the list is read again, nothing is stored then)
           float* const row = hs->hz + (size_t)(hi * a.n_portfolios + a.k_begin) * hs->hz_stride;
@@ -175,8 +167,7 @@
 #pragma unroll
             for (int k = 0; k < KT; k++) V[e][k] = vh[e][k];
         } else if (t == nd) {                              // a rebalance date: the trade back to W
-          crb_p cs = rk;
-          asm volatile("" : "+s"(cs));
+          const auto cs = kernarg<PathArgsRB>();
           const float kap = cs->cost;
           if (kap > 0.0f) {                                // rho' = rho^ - kappa tau, tau = sum_i |W_ki| |B_i - rho^_k|
             asm volatile("" : "+s"(Wk));
@@ -209,8 +200,8 @@
     } else if constexpr (HZ) {
       // SPEC.md 4.3: segment i runs the steps [h_{i-1}, h_i) with the unchanged step body and ends in one coalesced store
       // per live path and portfolio into row i*K + k of the horizon array; the last segment runs on to T.  The horizon
-      // count, the steps and the array are read through the kernel-argument pointer, wave-uniform, where they are needed
-      // (nothing held in SGPRs across the walk: the Cholesky factor lives there).
+      // count, the steps and the array are read where they are needed, wave-uniform: the bounds through the plain kernel-argument
+      // pointer (the compiler may place those loads), the array through kernarg.
       typedef const __attribute__((address_space(4))) PathArgsHZ* chz_p;
       chz_p hk = (chz_p)__builtin_amdgcn_kernarg_segment_ptr();
       const int n_seg = hk->n_horizons + 1;
@@ -221,8 +212,7 @@
 #include "mcp_paths_step.inc"
         }
         if (seg < n_seg - 1) {                             // V_h (simple) / S_h (log) of SPEC.md 4.3
-          chz_p hs = hk;
-          asm volatile("" : "+s"(hs));
+          const auto hs = kernarg<PathArgsHZ>();
           float* const row = hs->hz + (size_t)(seg * a.n_portfolios + a.k_begin) * hs->hz_stride;
 #pragma unroll
           for (int e = 0; e < PPT; e++)
@@ -242,7 +232,7 @@
     if constexpr (AT) {
       // ---- attribution epilogue (SPEC.md 5.9): x, the tail flag x <= var (binary64), d = x - c; per asset the wave sums of A, of A
       // over the tail and of A d, added to this wave's record in LDS by lane 0 (its own slot: no race, fixed order over the tiles)
-      const cattr_p ak = attr_kernarg();
+      const auto ak = &kernarg<PathArgsAT>()->at;
       asm volatile("" : "+s"(kargs));
       const double e_c = kargs->pivot[a.k_begin], e_var = ak->var[a.k_begin], e_v0d = kargs->v0d;
       int tid = threadIdx.x;
@@ -296,14 +286,12 @@
         for (int k = 0; k < KT; k++)
           if (k < kt) a.terminal[(size_t)(a.k_begin + k) * a.stride + p[e]] = V[e][k];
         if constexpr (DD && OV) {                          // the drawdown output of the overlay kernel's arguments
-          const cov_p dk = overlay_kernarg();
+          const auto dk = kernarg<PathArgsOV>();
 #pragma unroll
           for (int k = 0; k < KT; k++)
             if (k < kt) dk->mdd[(size_t)(a.k_begin + k) * dk->mdd_stride + p[e]] = Qk[e][k];
         } else if constexpr (DD) {                         // the drawdown output, read from the kernel arguments here only
-          typedef const __attribute__((address_space(4))) PathArgsDD* cdd_p;
-          cdd_p dk = (cdd_p)__builtin_amdgcn_kernarg_segment_ptr();
-          asm volatile("" : "+s"(dk));
+          const auto dk = kernarg<PathArgsDD>();
 #pragma unroll
           for (int k = 0; k < KT; k++)
             if (k < kt) dk->mdd[(size_t)(a.k_begin + k) * dk->mdd_stride + p[e]] = Qk[e][k];
@@ -385,7 +373,7 @@
   if constexpr (AT) {
     // one record per workgroup: entry j is the sum of the four waves' entries j, waves in order (SPEC.md 5.9)
     __syncthreads();
-    const cattr_p ak = attr_kernarg();
+    const auto ak = &kernarg<PathArgsAT>()->at;
     const double* const s_at = attr_wave_slots<N4>();
     constexpr int RL = attr_record_len(N4);
     if ((int)threadIdx.x < RL) {

@@ -1,5 +1,6 @@
-// mcp_paths_inst.hip -- instantiates mc_paths_kernel for ONE value of NB (= ceil(N/4), -DMCP_NB=n).
-// Built once per NB in 1..16 so the 16 translation units compile in parallel (see Makefile).
+// mcp_paths_inst.hip -- the path kernels of mcp_paths.h for ONE value of NB (= ceil(N/4), -DMCP_NB=n) and their one entry point,
+// launch_paths_nb<n>: the ladder below is the only place that maps a selector (PathKernel) to a kernel, and what it names is
+// what this unit instantiates.  Built once per NB in 1..16 so the 16 translation units compile in parallel (see Makefile).
 #include <cstdlib>
 
 #include "mcp_paths.h"
@@ -22,77 +23,99 @@ static size_t lds_pad() {
   return pad;
 }
 
-#define MCP_GO(kernel, A) kernel<<<grid, PATH_BLOCK, lds_pad(), stream>>>(static_cast<const A&>(a))
-
-// The plain Gaussian kernel with the native-math or folded step (one portfolio, or KT = 8 passes without FOLD).
-template <int KT, bool NATIVE, bool FOLD>
-static void go_plain(bool lg, const PathArgs& a, int grid, hipStream_t stream) {
-  if (lg) MCP_GO((mc_paths_kernel<MCP_NB, KT, 1, NATIVE, FOLD, true>), PathArgs);
-  else MCP_GO((mc_paths_kernel<MCP_NB, KT, 1, NATIVE, FOLD, false>), PathArgs);
+// Every pass of KT portfolios (k_begin = 0, KT, ...) of one kernel.  A, the kernel's own argument struct, is deduced from the
+// kernel and built by value from the blocks of `s` that it has, so the arguments cannot be another kernel's.
+template <int KT, class A>
+static hipError_t run(void (*kernel)(A), const PathLaunchArgs& s, hipStream_t stream) {
+  A x = make_args<A>(s);
+  const int grid = path_grid(x.n_paths);
+  for (x.k_begin = 0; x.k_begin < x.n_portfolios; x.k_begin += KT) {
+    kernel<<<grid, PATH_BLOCK, lds_pad(), stream>>>(x);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+  }
+  return hipSuccess;
 }
+#define MCP_ROW(cond, ...) \
+  if (cond) return run<KT>(__VA_ARGS__, s, stream)
 
-// Every family on the spec's normals and the unfolded recurrence (or no normals: the bootstrap), KT = 1 or 8, compounding LG
-// (the rebalancing, Student-t, GARCH, cash-flow and overlay kernels compound simply and take no LG).
-template <int KT, bool LG>
-static void go(const PathKernel& k, const PathArgs& a, int grid, hipStream_t stream) {
+// The kernels on the spec's normals or the bootstrap's rows and the unfolded recurrence, and the plain Gaussian kernel on native
+// math, in passes of KT = 1 or 8 portfolios.  The predicates name the draw source alone; every row states its compounding, and
+// only the plain, drawdown, horizon and bootstrap kernels compound in logs.
+template <int KT>
+static hipError_t ladder(const PathKernel& k, const PathLaunchArgs& s, hipStream_t stream) {
+  constexpr int NB = MCP_NB;
+  const bool lg = k.logc;
+  const bool gauss = !k.boot && !k.stt && !k.gv;                               // Gaussian draws
+  const bool t = k.stt && !k.gv && !k.boot, g = k.gv && !k.boot;                // Student-t draws; GARCH (nu = 0: Gaussian draws)
+  const bool bl = k.boot && k.blds && !k.stt && !k.gv, bg = k.boot && !k.blds && !k.stt && !k.gv;   // rows from LDS / global memory
+  if (k.native) {
+    MCP_ROW(k.family == FAM_PLAIN && gauss && lg, mc_paths_kernel<NB, KT, 1, true, false, true>);
+    MCP_ROW(k.family == FAM_PLAIN && gauss && !lg, mc_paths_kernel<NB, KT, 1, true, false, false>);
+    return hipErrorInvalidValue;
+  }
   switch (k.family) {
     case FAM_PLAIN:
-      if (k.gv) MCP_GO((mc_paths_g_kernel<MCP_NB, KT, 1>), PathArgsG);
-      else if (k.stt) MCP_GO((mc_paths_t_kernel<MCP_NB, KT, 1>), PathArgsT);
-      else if (k.boot && k.blds) MCP_GO((mc_paths_boot_kernel<MCP_NB, KT, 1, LG, true>), PathArgsBT);
-      else if (k.boot) MCP_GO((mc_paths_boot_kernel<MCP_NB, KT, 1, LG, false>), PathArgsBT);
-      else MCP_GO((mc_paths_kernel<MCP_NB, KT, 1, false, false, LG>), PathArgs);
+      MCP_ROW(gauss && lg, mc_paths_kernel<NB, KT, 1, false, false, true>);
+      MCP_ROW(gauss && !lg, mc_paths_kernel<NB, KT, 1, false, false, false>);
+      MCP_ROW(t && !lg, mc_paths_t_kernel<NB, KT, 1>);
+      MCP_ROW(g && !lg, mc_paths_g_kernel<NB, KT, 1>);
+      MCP_ROW(bl && lg, mc_paths_boot_kernel<NB, KT, 1, true, true>);
+      MCP_ROW(bl && !lg, mc_paths_boot_kernel<NB, KT, 1, false, true>);
+      MCP_ROW(bg && lg, mc_paths_boot_kernel<NB, KT, 1, true, false>);
+      MCP_ROW(bg && !lg, mc_paths_boot_kernel<NB, KT, 1, false, false>);
       break;
     case FAM_DD:
-      if (k.gv) MCP_GO((mc_paths_g_dd_kernel<MCP_NB, KT, 1>), PathArgsGDD);
-      else if (k.stt) MCP_GO((mc_paths_t_dd_kernel<MCP_NB, KT, 1>), PathArgsTDD);
-      else MCP_GO((mc_paths_dd_kernel<MCP_NB, KT, 1, LG>), PathArgsDD);
+      MCP_ROW(gauss && lg, mc_paths_dd_kernel<NB, KT, 1, true>);
+      MCP_ROW(gauss && !lg, mc_paths_dd_kernel<NB, KT, 1, false>);
+      MCP_ROW(t && !lg, mc_paths_t_dd_kernel<NB, KT, 1>);
+      MCP_ROW(g && !lg, mc_paths_g_dd_kernel<NB, KT, 1>);
       break;
     case FAM_HZ:
-      if (k.gv) MCP_GO((mc_paths_g_hz_kernel<MCP_NB, KT, 1>), PathArgsGHZ);
-      else if (k.stt) MCP_GO((mc_paths_t_hz_kernel<MCP_NB, KT, 1>), PathArgsTHZ);
-      else if (k.boot && k.blds) MCP_GO((mc_paths_boot_hz_kernel<MCP_NB, KT, 1, LG, true>), PathArgsBTHZ);
-      else if (k.boot) MCP_GO((mc_paths_boot_hz_kernel<MCP_NB, KT, 1, LG, false>), PathArgsBTHZ);
-      else MCP_GO((mc_paths_hz_kernel<MCP_NB, KT, 1, LG>), PathArgsHZ);
+      MCP_ROW(gauss && lg, mc_paths_hz_kernel<NB, KT, 1, true>);
+      MCP_ROW(gauss && !lg, mc_paths_hz_kernel<NB, KT, 1, false>);
+      MCP_ROW(t && !lg, mc_paths_t_hz_kernel<NB, KT, 1>);
+      MCP_ROW(g && !lg, mc_paths_g_hz_kernel<NB, KT, 1>);
+      MCP_ROW(bl && lg, mc_paths_boot_hz_kernel<NB, KT, 1, true, true>);
+      MCP_ROW(bl && !lg, mc_paths_boot_hz_kernel<NB, KT, 1, false, true>);
+      MCP_ROW(bg && lg, mc_paths_boot_hz_kernel<NB, KT, 1, true, false>);
+      MCP_ROW(bg && !lg, mc_paths_boot_hz_kernel<NB, KT, 1, false, false>);
       break;
     case FAM_REB:
-      if (k.boot && k.blds) MCP_GO((mc_paths_reb_kernel<MCP_NB, KT, 1, true, true>), PathArgsRB);
-      else if (k.boot) MCP_GO((mc_paths_reb_kernel<MCP_NB, KT, 1, true, false>), PathArgsRB);
-      else MCP_GO((mc_paths_reb_kernel<MCP_NB, KT, 1, false, false>), PathArgsRB);
+      MCP_ROW(gauss && !lg, mc_paths_reb_kernel<NB, KT, 1, false, false>);
+      MCP_ROW(bl && !lg, mc_paths_reb_kernel<NB, KT, 1, true, true>);
+      MCP_ROW(bg && !lg, mc_paths_reb_kernel<NB, KT, 1, true, false>);
       break;
     case FAM_CF:
-      if (k.stt) MCP_GO((mc_paths_cf_kernel<MCP_NB, KT, 1, false, false, true>), PathArgsCF);
-      else if (k.boot && k.blds) MCP_GO((mc_paths_cf_kernel<MCP_NB, KT, 1, true, true, false>), PathArgsCF);
-      else if (k.boot) MCP_GO((mc_paths_cf_kernel<MCP_NB, KT, 1, true, false, false>), PathArgsCF);
-      else MCP_GO((mc_paths_cf_kernel<MCP_NB, KT, 1, false, false, false>), PathArgsCF);
+      MCP_ROW(gauss && !lg, mc_paths_cf_kernel<NB, KT, 1, false, false, false>);
+      MCP_ROW(t && !lg, mc_paths_cf_kernel<NB, KT, 1, false, false, true>);
+      MCP_ROW(bl && !lg, mc_paths_cf_kernel<NB, KT, 1, true, true, false>);
+      MCP_ROW(bg && !lg, mc_paths_cf_kernel<NB, KT, 1, true, false, false>);
       break;
     case FAM_OV:
-      if (k.stt && k.dd) MCP_GO((mc_paths_ov_kernel<MCP_NB, KT, 1, true, true>), PathArgsOV);
-      else if (k.stt) MCP_GO((mc_paths_ov_kernel<MCP_NB, KT, 1, true, false>), PathArgsOV);
-      else if (k.dd) MCP_GO((mc_paths_ov_kernel<MCP_NB, KT, 1, false, true>), PathArgsOV);
-      else MCP_GO((mc_paths_ov_kernel<MCP_NB, KT, 1, false, false>), PathArgsOV);
+      MCP_ROW(gauss && !lg && !k.dd, mc_paths_ov_kernel<NB, KT, 1, false, false>);
+      MCP_ROW(gauss && !lg && k.dd, mc_paths_ov_kernel<NB, KT, 1, false, true>);
+      MCP_ROW(t && !lg && !k.dd, mc_paths_ov_kernel<NB, KT, 1, true, false>);
+      MCP_ROW(t && !lg && k.dd, mc_paths_ov_kernel<NB, KT, 1, true, true>);
       break;
   }
+  return hipErrorInvalidValue;
 }
 
-hipError_t MCP_CAT(launch_paths_nb, MCP_NB)(int variant, const PathKernel& k, const PathArgs& a, int grid, hipStream_t stream) {
-  if (k.family == FAM_AT) {                                // one portfolio per pass, simple compounding, the GARCH kernel's draws
-    if (variant != 0 || k.logc || k.boot) return hipErrorInvalidValue;
-    MCP_GO((mc_paths_attr_kernel<MCP_NB, 1, 1>), PathArgsAT);
-    return hipGetLastError();
+hipError_t MCP_CAT(launch_paths_nb, MCP_NB)(const PathKernel& k, const PathLaunchArgs& s, hipStream_t stream) {
+  constexpr int NB = MCP_NB, KT = 1;                       // the folded step and the attribution walk: one portfolio per pass
+  if (k.fold) {                                            // rho = c + v.z: the plain Gaussian walk on the spec's normals
+    const bool ok = k.family == FAM_PLAIN && !k.boot && !k.stt && !k.gv && !k.native && !k.kt8;
+    MCP_ROW(ok && k.logc, mc_paths_kernel<NB, 1, 1, false, true, true>);
+    MCP_ROW(ok && !k.logc, mc_paths_kernel<NB, 1, 1, false, true, false>);
+    return hipErrorInvalidValue;
   }
-  const bool plain = k.family == FAM_PLAIN && !k.boot && !k.stt && !k.gv;
-  if (k.family < FAM_PLAIN || k.family > FAM_OV || (!plain && variant != 0 && variant != VAR_KT8)) return hipErrorInvalidValue;
-  switch (variant) {
-    case 0: k.logc ? go<1, true>(k, a, grid, stream) : go<1, false>(k, a, grid, stream); break;
-    case VAR_KT8: k.logc ? go<8, true>(k, a, grid, stream) : go<8, false>(k, a, grid, stream); break;
-    case VAR_NATIVE: go_plain<1, true, false>(k.logc, a, grid, stream); break;
-    case VAR_FOLD: go_plain<1, false, true>(k.logc, a, grid, stream); break;
-    case VAR_KT8 | VAR_NATIVE: go_plain<8, true, false>(k.logc, a, grid, stream); break;
-    default: return hipErrorInvalidValue;
+  if (k.family == FAM_AT) {                                // simple compounding, the GARCH kernel's draws
+    MCP_ROW(!k.kt8 && !k.native && !k.logc && !k.boot, mc_paths_attr_kernel<NB, 1, 1>);
+    return hipErrorInvalidValue;
   }
-  return hipGetLastError();
+  return k.kt8 ? ladder<8>(k, s, stream) : ladder<1>(k, s, stream);
 }
-#undef MCP_GO
+#undef MCP_ROW
 
 }  // namespace mcp

@@ -174,7 +174,7 @@
           }
         } else {
         if constexpr (OV) {
-          const cov_p ok = overlay_kernarg();
+          const auto ok = kernarg<PathArgsOV>();
           const uint32_t has = (uint32_t)(ok->ov.mask >> (2 * m)) & 3u;     // do the assets 2m, 2m+1 own rows?
           if (has) {
             typedef const __attribute__((address_space(4))) int32_t* cbeg_p;

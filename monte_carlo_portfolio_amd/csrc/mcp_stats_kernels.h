@@ -54,30 +54,22 @@ __host__ __device__ inline int stream_slots(int K) {
 }
 
 struct PathArgs;
+struct PathLaunchArgs;
 
-// variant bits for launch_paths
-enum { VAR_KT8 = 1, VAR_NATIVE = 4, VAR_FOLD = 8 };
-
-// Which path kernel a launch runs (mcp_paths.h): the family, the compounding mode and the draw source.  `args` of launch_paths
-// is the PathArgs base of the kernel's argument struct:
-//   FAM_PLAIN  PathArgs, PathArgsBT (boot), PathArgsT (stt)        FAM_DD   PathArgsDD, PathArgsTDD (stt)
-//   FAM_HZ     PathArgsHZ, PathArgsBTHZ (boot), PathArgsTHZ (stt)  FAM_REB  PathArgsRB (boot: its rows instead of normals)
-//   FAM_CF     PathArgsCF (boot: its rows; stt: t draws; the horizons optional)
-//   FAM_OV     PathArgsOV (stt: t draws; dd: the drawdown state; the horizons optional)
-// `blds`: the bootstrap's row table is copied into LDS (it fits boot_fits_lds) instead of being read from global memory.
-// VAR_NATIVE and VAR_FOLD exist for the plain Gaussian kernel only.
-//   FAM_AT     PathArgsAT (the attribution walk of SPEC.md 4.10: variant 0 only, one portfolio per pass)
+// Which path kernel a launch runs: the family, the compounding mode, the draw source (boot: the bootstrap's rows, blds: its row
+// table copied into LDS, it fits boot_fits_lds; stt: Student-t draws; gv: GARCH), dd (FAM_OV only: the overlay kernel that also
+// tracks the drawdown), kt8 (passes of 8 portfolios instead of 1) and the plain Gaussian kernel's native-math and folded steps.
+// The one ladder of mcp_paths_inst.hip maps it to a kernel and lists which selectors have one.
 enum PathFamily { FAM_PLAIN, FAM_DD, FAM_HZ, FAM_REB, FAM_CF, FAM_OV, FAM_AT };
 struct PathKernel {
   int family;
-  bool logc, boot, blds, stt;
-  bool dd = false;                      // FAM_OV only: the overlay kernel that also tracks the drawdown
-  bool gv = false;                      // FAM_PLAIN, FAM_DD, FAM_HZ: the GARCH kernels (PathArgsG, PathArgsGDD, PathArgsGHZ; SPEC.md 4.9)
+  bool logc, boot, blds, stt, dd, gv, kt8, native, fold;
 };
 
-// mcp_paths_inst.hip (one translation unit per NB): returns hipErrorInvalidValue for a kernel that is not instantiated.
-typedef hipError_t (*launch_paths_fn)(int variant, const PathKernel& k, const PathArgs& args, int grid, hipStream_t stream);
-#define MCP_DECL_NB(n) hipError_t launch_paths_nb##n(int variant, const PathKernel& k, const PathArgs& args, int grid, hipStream_t stream);
+// mcp_paths_inst.hip (one translation unit per NB): every pass of the kernel that `k` selects, on the blocks of `args` that the
+// kernel's own argument struct has; hipErrorInvalidValue for a selector that has no kernel.
+typedef hipError_t (*launch_paths_fn)(const PathKernel& k, const PathLaunchArgs& args, hipStream_t stream);
+#define MCP_DECL_NB(n) hipError_t launch_paths_nb##n(const PathKernel& k, const PathLaunchArgs& args, hipStream_t stream);
 MCP_DECL_NB(1) MCP_DECL_NB(2) MCP_DECL_NB(3) MCP_DECL_NB(4) MCP_DECL_NB(5) MCP_DECL_NB(6) MCP_DECL_NB(7) MCP_DECL_NB(8)
 MCP_DECL_NB(9) MCP_DECL_NB(10) MCP_DECL_NB(11) MCP_DECL_NB(12) MCP_DECL_NB(13) MCP_DECL_NB(14) MCP_DECL_NB(15) MCP_DECL_NB(16)
 #undef MCP_DECL_NB

@@ -113,6 +113,32 @@ def test_horizon_rows_equal_the_n_steps_h_calls_and_the_bands_np_percentile(mode
                 assert _same(bands[i, k, j], np.percentile(x, q), mode), (h, k, q)
 
 
+ONE_PORTFOLIO = [  # call, compounding, R: the one-portfolio (K = 1) kernels that no case above launches
+    ("terminal", "log", 7),
+    ("horizons", "simple", 7), ("horizons", "log", 7),
+    ("horizons", "simple", 1088 // 2 + 1), ("horizons", "log", 1088 // 2 + 1),
+]
+
+
+@pytest.mark.parametrize("call,mode,R", ONE_PORTFOLIO)
+def test_one_portfolio_kernels_equal_the_restatement_on_every_path(call, mode, R, gpu_ctx):
+    """N = 5 is two asset blocks with three padding assets, 300 paths are two workgroups with the second one ragged; at two
+    asset blocks 7 rows sit in LDS and 545 are one more than it holds."""
+    N, T, n, begin, b = 5, 6, 300, 3, 2.5
+    rows, W = _table(R, N, 11), _weights(N, 1, 11)
+    prm = _ffi.make_params(N, T, 1, compounding=mode, v0=2.0)
+    paths = (begin + np.arange(n)).astype(np.uint64)
+    if call == "terminal":
+        _, term = gpu_ctx.simulate_bootstrap(prm, rows, W, b, SEED, begin, n, True)
+        ref = simulate_boot(rows, W, T, SEED, paths, b, mode, v0=2.0)
+    else:
+        hz = [1, 4, 6]
+        _, _, _, term, hzt = gpu_ctx.simulate_bootstrap_horizons(prm, rows, W, b, SEED, begin, n, hz, (50.0,), True)
+        ref = simulate_boot(rows, W, T, SEED, paths, b, mode, v0=2.0, horizons=hz)
+        assert np.array_equal(hzt.view(np.uint32), ref["V_h"].view(np.uint32))
+    assert np.array_equal(term.view(np.uint32), ref["V_T"].view(np.uint32))
+
+
 @pytest.mark.parametrize("mode", ["simple", "log"])
 @pytest.mark.parametrize("N,R", [(16, 250), (16, 300), (5, 64)])
 def test_b_inf_with_T_equal_R_visits_every_row_once(mode, N, R, gpu_ctx):

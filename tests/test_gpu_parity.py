@@ -121,6 +121,30 @@ def test_native_math_is_statistically_equivalent(gpu_ctx):
     assert abs(a["cvar"] - b["cvar"]) < 30 * se
 
 
+@pytest.mark.parametrize("K,comp", [(1, "log"), (9, "simple"), (9, "log")])
+def test_native_math_kernels_of_log_compounding_and_eight_portfolios(gpu_ctx, K, comp):
+    """The native normals have no restatement, so these kernels are tied to the one-portfolio simple-compounding kernel of the test
+    above.  Nine portfolios are two passes of the 8-portfolio kernel, the second with one live portfolio: native math changes the
+    normals only, which the portfolios share, and on the spec's normals both kernels equal the oracle, so every row is bit for bit
+    the one-portfolio call on its weights.  One portfolio in log compounding: another sample of the law of the call on the spec's
+    normals, so the means differ by less than 6 standard errors of a difference (a kernel compounding the other way is off by
+    about 1, hundreds of them).  N = 5 is two asset blocks with three padding assets, 300 paths two workgroups, the second ragged."""
+    N, T, P = 5, 6, 300
+    mu, cov = synthetic.synthetic_market(N)
+    W = synthetic.dirichlet_weights(N, 9)
+    kw = dict(n_steps=T, n_paths=P, seed=SEED, store=True, compounding=comp)
+    if K == 1:
+        a = simulate_paths(mu, cov, W[0], **kw)
+        b = simulate_paths(mu, cov, W[0], native_math=True, **kw)
+        assert b["n"] == P and not np.array_equal(a["terminal"], b["terminal"])
+        assert abs(a["mean"] - b["mean"]) < 6 * np.sqrt(2) * a["std"] / np.sqrt(P)
+        return
+    _, term = simulate_paths(mu, cov, W, native_math=True, as_array=True, **kw)
+    for k in range(K):
+        one = simulate_paths(mu, cov, W[k], native_math=True, **kw)
+        assert np.array_equal(term[k].view(np.uint32), one["terminal"].view(np.uint32)), k
+
+
 def test_config1_scale_properties(gpu_ctx):
     """BASELINE config 1 at full size (16 assets, 1M paths, 252 steps): size-independent properties.
     The first 50k paths are checked bit-exactly against the oracle; the rest through the statistics:

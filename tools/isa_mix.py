@@ -3,7 +3,9 @@
 The step loop is the innermost loop (backward branch) with the most VALU instructions, as in tools/issue_model.py.  The last
 line is a digest of the kernel's whole instruction stream (comments and label numbers dropped): two listings whose digests
 agree hold the same code for that kernel."""
-import collections, hashlib, re, sys
+import collections, os, re, sys
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from isa_digests import digest
 lines = open(sys.argv[1]).read().split("\n")
 pat = sys.argv[2] if len(sys.argv) > 2 else "mc_paths_kernelILi4ELi1ELi1ELb0ELb0E"
 k0 = next(i for i, l in enumerate(lines) if l.startswith("_ZN3mcp") and pat in l.split(":")[0] and ":" in l)
@@ -28,6 +30,4 @@ if div:
     print("  division: " + "; ".join(f"{n} {o}" for o, n in sorted(div.items())))
 meta = [l.strip() for l in lines[k1:k1 + 200] if "NumVgprs" in l or "; Occupancy" in l or "ScratchSize" in l]
 print("  " + " ".join(meta[:4]))
-body = [re.sub(r"\.LBB\d+_\d+", "L", l.split(";")[0].strip()) for l in lines[k0 + 1:k1 + 1]]
-body = [l for l in body if l and not l.startswith(".")]
-print(f"  code digest {hashlib.sha1(chr(10).join(body).encode()).hexdigest()[:16]} ({len(body)} instructions)")
+print("  code digest %s (%d instructions)" % digest(lines[k0 + 1:k1 + 1]))
