@@ -30,7 +30,8 @@ extern "C" {
                                     + mcp_simulate_student_t (additive, detected by symbol);
                                     + mcp_simulate_overlay, mcp_overlay_pivots (additive, detected by symbol);
                                     + mcp_simulate_garch (additive, detected by symbol);
-                                    + mcp_simulate_attribution (additive, detected by symbol) */
+                                    + mcp_simulate_attribution (additive, detected by symbol);
+                                    + mcp_simulate_antithetic (additive, detected by symbol) */
 #define MCP_MAX_ASSETS 64        /* thread-per-path kernels are instantiated for N4 = 4..64 */
 #define MCP_SELECT_BINS 2048     /* radix-select digit: 11 + 11 + 10 bits */
 #define MCP_MAX_HORIZONS 64      /* mcp_simulate_horizons: horizon steps per call */
@@ -320,6 +321,39 @@ int mcp_simulate_garch(mcp_ctx *ctx, const mcp_params *prm, const mcp_garch *g,
                        float *horizon_out,         /* NULL or host [H*K*n_paths], row h*K + k */
                        mcp_stats *hz_stats_out,    /* [H*K], NULL iff n_horizons == 0 */
                        double *bands_out);         /* [H*K*L], NULL iff n_levels == 0 */
+
+/* Antithetic pairs (SPEC.md 2.3 / 5.10): the pair statistics of one portfolio on the terminal x.  cross = sum_j (x_2j - c)(x_2j+1 - c)
+ * with c the pivot of mcp_pivots; with C = cross - S1^2 / (2 n), S1 = (mean - c) n: pair_cov = C / (n_pairs - 1), pair_corr = 2 C / m2
+ * (0 if m2 == 0), mean_se = sqrt(max(m2 + 2 C, 0) / (n (n - 2))) -- the standard error of the mean of the n / 2 independent pair
+ * means -- and mean_se_iid = std / sqrt(n), what n independent paths would have given.  pair_cov and mean_se are 0 when n_pairs < 2. */
+typedef struct {
+    uint64_t n_pairs, reserved;
+    double cross, pair_cov, pair_corr, mean_se, mean_se_iid;
+} mcp_pair;
+
+/* mcp_simulate (g and st NULL), mcp_simulate_student_t (st) or mcp_simulate_garch (g, st or NULL) on antithetic pairs: path_begin and
+ * n_paths even; the global paths 2j and 2j + 1 share every draw of pair j -- the Philox counters carry j -- and path 2j + 1 sees the
+ * asset normals negated (the chi blocks and the GARCH variance are shared).  Member 2j is bit for bit path j of the call without pairs
+ * at (path_begin / 2, n_paths / 2), member 2j + 1 path j of that call with chol negated.  Every statistic is that of the call without
+ * pairs over all n_paths values; pair_out [K] adds the pair statistics.  The horizon inputs, the outputs and their rules are those of
+ * mcp_simulate_garch; log compounding with Gaussian draws only.  MCP_E_ARG (before any device is touched): odd path_begin or n_paths,
+ * NULL pair_out, the rules of g and st.  MCP_E_UNSUPPORTED: MCP_FLAG_FOLD, MCP_FLAG_NATIVE_MATH, MCP_FLAG_SHARD_PORTFOLIOS, log
+ * compounding with g or st.  Path-sharded contexts cut the path range at even ids; the shards' cross sums are added in shard order.
+ * Costs per pair: the draws of one path and the Cholesky product of two.  K >= 17 runs as passes of 8 portfolios. */
+int mcp_simulate_antithetic(mcp_ctx *ctx, const mcp_params *prm,
+                            const mcp_garch *g,                 /* NULL: no GARCH */
+                            const mcp_student_t *st,            /* NULL: Gaussian draws */
+                            const float *mu, const float *chol, const float *W,
+                            uint64_t seed, uint64_t path_begin, uint64_t n_paths,
+                            int n_horizons, const int32_t *horizons, int n_levels, const double *levels,
+                            float *terminal_out,        /* NULL or host [K*n_paths] */
+                            mcp_stats *stats_out,       /* [K] */
+                            float *mdd_out,             /* NULL or host [K*n_paths]; needs dd_stats_out */
+                            mcp_stats *dd_stats_out,    /* [K], or NULL: no drawdown */
+                            float *horizon_out,         /* NULL or host [H*K*n_paths], row h*K + k */
+                            mcp_stats *hz_stats_out,    /* [H*K], NULL iff n_horizons == 0 */
+                            double *bands_out,          /* [H*K*L], NULL iff n_levels == 0 */
+                            mcp_pair *pair_out);        /* [K] */
 
 /* Per-asset risk attribution (SPEC.md 4.10 / 5.9): one record per (portfolio k, asset i).  A_ki is the money asset i made or lost
  * for portfolio k along a path, A_ki = sum_t V_{t-1} w_ki r_i (binary32, in the kernel); sum_i A_ki = V_T - v0 up to rounding.  sum,

@@ -105,6 +105,11 @@ ATTR_DTYPE = np.dtype([("mean", np.float64), ("cvar", np.float64), ("vol", np.fl
                        ("sum_xc", np.float64)])
 assert ATTR_DTYPE.itemsize == 48
 
+# one mcp_pair: the pair statistics of a portfolio's antithetic sample (SPEC.md 5.10)
+PAIR_DTYPE = np.dtype([("n_pairs", np.uint64), ("reserved", np.uint64), ("cross", np.float64), ("pair_cov", np.float64),
+                       ("pair_corr", np.float64), ("mean_se", np.float64), ("mean_se_iid", np.float64)])
+assert PAIR_DTYPE.itemsize == 56
+
 RECORD_DTYPE = np.dtype([("n", np.float64), ("sum", np.float64), ("sumsq", np.float64), ("min", np.float64),
                          ("max", np.float64), ("below", np.float64), ("pivot", np.float64), ("pad", np.float64)])
 # one moment partial of the path kernels' epilogue (csrc/mcp_stats_kernels.h: MomentPartial)
@@ -160,6 +165,8 @@ SIGNATURES = {
                                   _vp, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mcp_simulate_attribution": (_int, [_vp, _PP, ctypes.POINTER(McpGarch), ctypes.POINTER(McpStudentT), _vp, _vp, _vp, _u64, _u64, _u64,
                                         _vp, _vp, _vp, _vp, _vp]),
+    "mcp_simulate_antithetic": (_int, [_vp, _PP, ctypes.POINTER(McpGarch), ctypes.POINTER(McpStudentT), _vp, _vp, _vp, _u64, _u64, _u64,
+                                       _int, _vp, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mcp_simulate_cashflow": (_int, [_vp, _PP, ctypes.POINTER(McpCashflow), _vp, _vp, ctypes.POINTER(McpBootstrap),
                                      ctypes.POINTER(McpStudentT), _vp, _u64, _u64, _u64, _int, _vp, _int, _vp, _vp, _vp, _vp, _vp, _vp,
                                      _vp, _vp]),

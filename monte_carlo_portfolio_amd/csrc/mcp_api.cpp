@@ -367,6 +367,9 @@ struct Request {
   float* contrib_out = nullptr;         // NULL or host [K][N][n]
   mcp_attr* attr_out = nullptr;         // [K][N]
   uint64_t* attr_counts_out = nullptr;  // [K][2] {n, n_tail}
+  bool anti = false;                    // SPEC.md 2.3 / 5.10: antithetic pairs
+  mcp_pair* pair_out = nullptr;         // [K]
+  double* cross_out = nullptr;          // [K] the call's cross sums: every tile adds its shards' in shard order
 };
 
 Request host_request(Source src, const float* mu, const float* chol, const float* W, float* terminal_out, mcp_stats* stats_out) {
@@ -408,6 +411,7 @@ struct Launch {
   const char* d_overlay = nullptr;      // overlay: [rows][row_begin N4 + 1][spot N4] (overlay_pack)
   bool attr = false;                    // the attribution walk (SPEC.md 4.10): FAM_AT instead of the request's own family
   const double* d_var = nullptr;        // attribution: [K] VaRs
+  double* d_cross = nullptr;            // antithetic pairs: [K][path_grid(n_paths / 2)] cross partials
   double* d_attr_partials = nullptr;    // attribution: [K][path_grid(n_paths)][attr_record_len(N4)]
   float* d_contrib = nullptr;           // attribution: NULL or [K][N][contrib_stride]
   uint64_t contrib_stride = 0;
@@ -418,7 +422,7 @@ struct Launch {
 
 // Every rule a request meets: each feature's own arguments, then which features combine (MCP_E_UNSUPPORTED), then the outputs.
 // `ln`: an mcp_launch_paths* call, whose device arrays are checked instead of the host arrays of an mcp_simulate* call.
-int check_request(const mcp_params* prm, const Request& rq, uint64_t n_paths, const Launch* ln = nullptr) {
+int check_request(const mcp_params* prm, const Request& rq, uint64_t n_paths, const Launch* ln = nullptr, uint64_t path_begin = 0) {
   int rc;
   if ((rc = check_params(prm))) return rc;
   if (rq.rebalanced) {
@@ -473,6 +477,17 @@ int check_request(const mcp_params* prm, const Request& rq, uint64_t n_paths, co
     if (prm->n_portfolios > MCP_MAX_ATTR_PORTFOLIOS)
       return fail(MCP_E_UNSUPPORTED, "the attribution takes at most %d portfolios, got %d", MCP_MAX_ATTR_PORTFOLIOS, prm->n_portfolios);
     if (!ln && (!rq.attr_out || !rq.attr_counts_out)) return fail(MCP_E_ARG, "attr_out or attr_counts_out is NULL");
+  }
+  if (rq.anti) {                                               // SPEC.md 2.3: whole pairs of the spec's step on Gaussian, t or GARCH draws
+    if ((path_begin | n_paths) & 1)
+      return fail(MCP_E_ARG, "antithetic pairs: path_begin=%llu and n_paths=%llu must both be even", (unsigned long long)path_begin,
+                  (unsigned long long)n_paths);
+    if (!ln && !rq.pair_out) return fail(MCP_E_ARG, "pair_out is NULL");
+    if (prm->flags & (MCP_FLAG_FOLD | MCP_FLAG_NATIVE_MATH | MCP_FLAG_SHARD_PORTFOLIOS))
+      return fail(MCP_E_UNSUPPORTED, "antithetic pairs run on the spec's normals, the unfolded recurrence and path shards (no MCP_FLAG_FOLD / "
+                                     "MCP_FLAG_NATIVE_MATH / MCP_FLAG_SHARD_PORTFOLIOS)");
+    if (rq.src == SRC_BOOT || rq.rebalanced || rq.cash || rq.overlay || rq.attr)
+      return fail(MCP_E_UNSUPPORTED, "antithetic pairs are not combined with bootstrap rows, rebalancing, cash flows, the overlay or the attribution");
   }
   if (rq.dd && rq.hz) return fail(MCP_E_UNSUPPORTED, "horizons and the drawdown are not tracked in one walk");
   if (rq.dd && (rq.src == SRC_BOOT || rq.rebalanced))
@@ -681,6 +696,11 @@ struct Shard {
     HostBuf<double> h_records;             // pinned copy of records
     DevBuf<float> contrib;                 // [K][N][paths] A_ki, when the caller asks for them
   } at;
+  struct {                                 // antithetic calls (SPEC.md 5.10)
+    DevBuf<double> partials;               // [K tile][path_grid(pairs)] cross partials, one per workgroup
+    DevBuf<double> cross;                  // [K tile] the workgroups' partials summed in block order
+    HostBuf<double> h_cross;               // pinned copy of cross
+  } pr;
 };
 
 int grow_dev(void** p, size_t* cap, size_t need, hipStream_t zero_on = nullptr, bool zero = false) {
@@ -979,7 +999,7 @@ static int launch_paths_impl(const mcp_params* prm, const Request& rq, const Lau
   DeviceGuard guard(dev);                 // the stream may belong to another device than the thread's current one
   if (guard.err != hipSuccess) return fail(MCP_E_HIP, "hipSetDevice(%d): %s", dev, hipGetErrorString(guard.err));
   if (int rc = device_tables(dev, ln.stream, &tables)) return rc;
-  const bool sweep = plain && !ln.attr && uses_sweep(K);
+  const bool sweep = plain && !ln.attr && !rq.anti && uses_sweep(K);
   a.tables = tables;
   a.packed = ln.d_packed;
   a.terminal = ln.d_terminal;
@@ -1000,6 +1020,14 @@ static int launch_paths_impl(const mcp_params* prm, const Request& rq, const Lau
   a.v0 = (float)prm->v0;
   a.k_count = K;
   a.fold_offset = (uint32_t)(n4_of(N) + n4_of(N) * (n4_of(N) / 2 + 1) + kpad_of(K) * n4_of(N));
+  if (rq.anti) {
+    // SPEC.md 2.3: one lane per pair -- the kernel counts pairs and stores the members 2j, 2j + 1 of every row with one 8-byte store
+    if ((ln.path_begin | ln.n_paths | ln.stride | (rq.dd ? ln.mdd_stride : 0) | (rq.hz ? ln.hz_stride : 0)) & 1)
+      return fail(MCP_E_ARG, "antithetic pairs: a launch begins, ends and strides at even path ids");
+    a.path_begin = ln.path_begin / 2;
+    a.n_paths = ln.n_paths / 2;
+    s.pr.cross = ln.d_partials ? ln.d_cross : nullptr;
+  }
   if (sweep) {
     const bool native = (prm->flags & MCP_FLAG_NATIVE_MATH) != 0;
     SweepSeg segs[4];
@@ -1019,7 +1047,7 @@ static int launch_paths_impl(const mcp_params* prm, const Request& rq, const Lau
     }
     return MCP_OK;
   }
-  if (!plain && ln.d_partials && a.slots > (uint64_t)mcp::path_grid(ln.n_paths))
+  if ((!plain || rq.anti) && ln.d_partials && a.slots > (uint64_t)mcp::path_grid(a.n_paths))
     HIP_TRY(mcp::launch_pass0(*prm, K, ln.d_terminal, ln.stride, 0, nullptr, a.slots, (mcp::MomentPartial*)ln.d_partials,
                               (unsigned long long*)ln.d_hist, ln.stream));
   fill_hz(s.hz, rq, ln);
@@ -1053,6 +1081,15 @@ static int launch_paths_impl(const mcp_params* prm, const Request& rq, const Lau
     k.kt8 = K > 1;
     k.native = (prm->flags & MCP_FLAG_NATIVE_MATH) != 0;
     k.fold = (prm->flags & MCP_FLAG_FOLD) != 0;
+    if (rq.anti) {
+      // Student-t and GARCH requests share the GARCH walk, as the attribution does: without GARCH on alpha = beta = 0, h0 = 1
+      static const mcp_garch none = {0.0, 0.0, 1.0, 0};
+      k.anti = true;
+      if (k.stt || k.gv) {
+        k.stt = k.gv = true;
+        if (!rq.garch) s.gv = garch_block(&none, N);
+      }
+    }
   }
   const hipError_t e = k_launch[nb - 1](k, s, ln.stream);
   if (e != hipSuccess) return fail(MCP_E_HIP, "path kernel launch (family %d): %s", k.family, hipGetErrorString(e));
@@ -1293,6 +1330,9 @@ static void free_shard(Shard& sh) {
   release(sh.at.records);
   release(sh.at.h_records);
   release(sh.at.contrib);
+  release(sh.pr.partials);
+  release(sh.pr.cross);
+  release(sh.pr.h_cross);
 }
 
 int mcp_ctx_create_multi(const int* devices, int ndev, mcp_ctx** out) {
@@ -1581,6 +1621,9 @@ int run_tile(mcp_ctx* c, const mcp_params* prm, const Request& rq, uint64_t seed
                   (rc = grow(sh.hz.h_pivot, (size_t)rows)) || (rc = grow_mapped(sh.hz.stats, (size_t)(1 + rq.L) * rows))))
       return rc;
     if (rq.cash && ((rc = grow(sh.cf.counts, 2 * (size_t)(j.kt + rows))) || (rc = grow(sh.cf.h_counts, 2 * (size_t)(j.kt + rows))))) return rc;
+    if (rq.anti && ((rc = grow(sh.pr.partials, (size_t)j.kt * (size_t)mcp::path_grid(pn / 2))) || (rc = grow(sh.pr.cross, (size_t)j.kt)) ||
+                    (rc = grow(sh.pr.h_cross, (size_t)j.kt))))
+      return rc;
   }
   // 1b. parameters up and the path kernels out, device after device with nothing else in between: every GPU should be
   //     simulating as early as possible.  Shards of a path-sharded tile share one packed block and one pivot vector
@@ -1644,7 +1687,12 @@ int run_tile(mcp_ctx* c, const mcp_params* prm, const Request& rq, uint64_t seed
       ln.d_rows = sh.boot.p;
       ln.d_flows = sh.cf.flows.p;
       ln.d_overlay = sh.overlay.p;
+      ln.d_cross = sh.pr.partials.p;
       if ((rc = launch_paths_impl(&tp[s], rq, ln))) return rc;
+      if (rq.anti) {                                         // SPEC.md 5.10: the workgroups' cross partials in block order
+        HIP_TRY(mcp::launch_attr_merge(sh.pr.partials.p, j.kt, mcp::path_grid(j.pn / 2), 1, sh.pr.cross.p, sh.stream));
+        HIP_TRY(hipMemcpyAsync(sh.pr.h_cross.p, sh.pr.cross.p, (size_t)j.kt * sizeof(double), hipMemcpyDeviceToHost, sh.stream));
+      }
       if (rq.cash) {                                         // SPEC.md 5.6: the ruined and the short paths of every stored row
         const size_t rows_hz = rq.hz ? (size_t)rq.H * j.kt : 0;
         const bool tg = rq.cf->has_target != 0;
@@ -1729,6 +1777,11 @@ int run_tile(mcp_ctx* c, const mcp_params* prm, const Request& rq, uint64_t seed
         for (int h = 0; rq.hz && h < rq.H; h++)
           rq.hz_counts_out[2 * ((size_t)h * prm->n_portfolios + j.k0 + k) + i] += hc[2 * ((size_t)j.kt + (size_t)h * j.kt + k) + i];
       }
+  }
+  for (size_t s = 0; rq.anti && s < S; s++) {              // the cross sums of every shard that walked pairs, in shard order
+    const Job& j = jobs[s];
+    if (!j.active || !j.pn) continue;
+    for (int k = 0; k < j.kt; k++) rq.cross_out[j.k0 + k] += c->sh[s].pr.h_cross.p[k];
   }
   for (size_t s = 0; s < S; s++) {
     const Job& j = jobs[s];
@@ -1911,9 +1964,10 @@ int simulate_impl(mcp_ctx* c, const mcp_params* prm, const Request& rq, uint64_t
   } else if (rc == MCP_OK) {
     // the path range is sharded; all shards see the same tile of portfolios
     uint64_t pn_max = 0;
+    const uint64_t unit = rq.anti ? 2 : 1, n_units = n_paths / unit;   // antithetic pairs: the range is cut at even ids (SPEC.md 2.3)
     for (size_t s = 0; s < S; s++) {
-      jobs[s].p0 = n_paths / S * s + std::min<uint64_t>(s, n_paths % S);
-      jobs[s].pn = n_paths / S + (s < n_paths % S ? 1 : 0);
+      jobs[s].p0 = unit * (n_units / S * s + std::min<uint64_t>(s, n_units % S));
+      jobs[s].pn = unit * (n_units / S + (s < n_units % S ? 1 : 0));
       jobs[s].active = true;
       pn_max = std::max(pn_max, jobs[s].pn);
     }
@@ -1946,7 +2000,7 @@ int simulate_impl(mcp_ctx* c, const mcp_params* prm, const Request& rq, uint64_t
 
 // Every public simulate entry point: the request is checked in full before the context is looked at.
 int simulate_checked(mcp_ctx* c, const mcp_params* prm, const Request& rq, uint64_t seed, uint64_t path_begin, uint64_t n_paths) {
-  if (int rc = check_request(prm, rq, n_paths)) return rc;
+  if (int rc = check_request(prm, rq, n_paths, nullptr, path_begin)) return rc;
   return simulate_impl(c, prm, rq, seed, path_begin, n_paths);
 }
 
@@ -2033,6 +2087,45 @@ int mcp_simulate_garch(mcp_ctx* c, const mcp_params* prm, const mcp_garch* g, co
   rq.dd_stats_out = dd_stats_out;
   ask_horizons(rq, n_horizons != 0, n_horizons, horizons, n_levels, levels, horizon_out, hz_stats_out, bands_out);
   return simulate_checked(c, prm, rq, seed, path_begin, n_paths);
+}
+
+// SPEC.md 5.10: the pair record of one portfolio from the call's statistics, its pivot c and cross = sum (x_2j - c)(x_2j+1 - c)
+static void pair_record(const mcp_stats& st, double c, double cross, mcp_pair* out) {
+  const double n = (double)st.n, np = (double)(st.n / 2);
+  const double s1 = (st.mean - c) * n;
+  const double C = n > 0.0 ? cross - s1 * s1 / (2.0 * n) : 0.0;
+  out->n_pairs = st.n / 2;
+  out->reserved = 0;
+  out->cross = cross;
+  out->pair_cov = np >= 2.0 ? C / (np - 1.0) : 0.0;
+  out->pair_corr = st.m2 > 0.0 ? 2.0 * C / st.m2 : 0.0;
+  out->mean_se = np >= 2.0 ? std::sqrt(std::max(st.m2 + 2.0 * C, 0.0) / (n * (n - 2.0))) : 0.0;
+  out->mean_se_iid = n > 0.0 ? st.std / std::sqrt(n) : 0.0;
+}
+
+int mcp_simulate_antithetic(mcp_ctx* c, const mcp_params* prm, const mcp_garch* g, const mcp_student_t* st, const float* mu,
+                            const float* chol, const float* W, uint64_t seed, uint64_t path_begin, uint64_t n_paths, int n_horizons,
+                            const int32_t* horizons, int n_levels, const double* levels, float* terminal_out, mcp_stats* stats_out,
+                            float* mdd_out, mcp_stats* dd_stats_out, float* horizon_out, mcp_stats* hz_stats_out, double* bands_out,
+                            mcp_pair* pair_out) {
+  Request rq = host_request(st ? SRC_T : SRC_GAUSS, mu, chol, W, terminal_out, stats_out);
+  rq.st = st;
+  rq.garch = g != nullptr;
+  rq.gv = g;
+  rq.dd = dd_stats_out != nullptr;
+  rq.mdd_out = mdd_out;
+  rq.dd_stats_out = dd_stats_out;
+  rq.anti = true;
+  rq.pair_out = pair_out;
+  ask_horizons(rq, n_horizons != 0, n_horizons, horizons, n_levels, levels, horizon_out, hz_stats_out, bands_out);
+  if (int rc = check_request(prm, rq, n_paths, nullptr, path_begin)) return rc;
+  const size_t K = (size_t)prm->n_portfolios;
+  std::vector<double> cross(K, 0.0), pivot(K);
+  rq.cross_out = cross.data();
+  if (int rc = simulate_impl(c, prm, rq, seed, path_begin, n_paths)) return rc;
+  if (int rc = mcp_pivots(prm, mu, chol, W, pivot.data())) return rc;
+  for (size_t k = 0; k < K; k++) pair_record(stats_out[k], pivot[k], cross[k], pair_out + k);
+  return MCP_OK;
 }
 
 int mcp_simulate_attribution(mcp_ctx* c, const mcp_params* prm, const mcp_garch* g, const mcp_student_t* st, const float* mu,

@@ -53,6 +53,10 @@
 #define MCP_MIN_WAVES_AT 5  // the attribution kernel (N <= 16, one portfolio) holds the N4 contributions A on top of the GARCH kernel's state, as
                             // the rebalancing kernel holds B: at 5 waves it gets 96 VGPRs, no scratch (profiles/attribution_isa.txt)
 #endif
+#ifndef MCP_MIN_WAVES_ANTI
+#define MCP_MIN_WAVES_ANTI 5 // the antithetic kernels (N <= 16, one portfolio) carry the second member's V, row-pair accumulator and rho (and
+                            // peak and drawdown) next to the first's: see profiles/antithetic_isa.txt
+#endif
 #ifndef MCP_EXP_VKEYS
 #define MCP_EXP_VKEYS 1
 #endif
@@ -90,7 +94,7 @@ __device__ __forceinline__ const __attribute__((address_space(4))) A* kernarg() 
   template <class A, class = void> struct has_##m : std::false_type {}; \
   template <class A> struct has_##m<A, std::void_t<decltype(A::m)>> : std::true_type {};
 MCP_HAS_MEMBER(hz) MCP_HAS_MEMBER(mdd) MCP_HAS_MEMBER(bt) MCP_HAS_MEMBER(st) MCP_HAS_MEMBER(gv) MCP_HAS_MEMBER(cf)
-MCP_HAS_MEMBER(ov) MCP_HAS_MEMBER(at) MCP_HAS_MEMBER(period)
+MCP_HAS_MEMBER(ov) MCP_HAS_MEMBER(at) MCP_HAS_MEMBER(period) MCP_HAS_MEMBER(pr)
 #undef MCP_HAS_MEMBER
 
 struct PathArgs {
@@ -210,6 +214,32 @@ __device__ __forceinline__ double* attr_wave_slots() {
   return s_attr;
 }
 
+// Antithetic pairs (SPEC.md 2.3 / 5.10): a lane walks both members of one pair; in such a launch PathArgs::path_begin and n_paths
+// count PAIRS (the Philox counters carry the pair id), the members 2j and 2j + 1 are adjacent in every output row (strides even,
+// one 8-byte store per lane), and the epilogue leaves sum (x_2j - c)(x_2j+1 - c) per workgroup and portfolio in `cross`.
+struct PairArgs {
+  double* __restrict__ cross;         // [K][gridDim.x], NULL exactly when PathArgs::partials is
+};
+// Arguments of mc_paths_anti_kernel: those of the plain, drawdown or horizon kernel, or of their GARCH twins, and the pair block.
+struct PathArgsA : PathArgs { PairArgs pr; };
+struct PathArgsADD : PathArgsDD { PairArgs pr; };
+struct PathArgsAHZ : PathArgsHZ { PairArgs pr; };
+struct PathArgsGA : PathArgsG { PairArgs pr; };
+struct PathArgsGADD : PathArgsGDD { PairArgs pr; };
+struct PathArgsGAHZ : PathArgsGHZ { PairArgs pr; };
+// The cross-product partials of an antithetic launch, read where they are written (kernarg).
+template <class A>
+__device__ __forceinline__ double* pair_cross(const A&) {
+  if constexpr (has_pr<A>::value) return kernarg<A>()->pr.cross;
+  else return nullptr;
+}
+// The per-wave accumulators of the cross products: PATH_BLOCK / 64 slots per portfolio of the pass in LDS (antithetic kernels only).
+template <int KT>
+__device__ __forceinline__ double* pair_wave_slots() {
+  __shared__ double s_cross[4 * KT];
+  return s_cross;
+}
+
 // Cash flows and ruin (SPEC.md 4.7): the schedule c_1 .. c_T, one binary32 flow per step, the same for every portfolio.
 struct CashArgs {
   const float* __restrict__ flows;    // [n_steps] device copy; flows[t] = c_{t+1} arrives at the end of step t
@@ -286,6 +316,7 @@ struct PathLaunchArgs {
   AttrArgs at;
   int32_t period;                     // the rebalancing rule of PathArgsRB
   float cost;
+  PairArgs pr;
 };
 template <class A>
 inline A make_args(const PathLaunchArgs& s) {
@@ -300,6 +331,7 @@ inline A make_args(const PathLaunchArgs& s) {
   if constexpr (has_ov<A>::value) x.ov = s.ov;
   if constexpr (has_at<A>::value) x.at = s.at;
   if constexpr (has_period<A>::value) { x.period = s.period; x.cost = s.cost; }
+  if constexpr (has_pr<A>::value) x.pr = s.pr;
   return x;
 }
 
@@ -385,18 +417,22 @@ constexpr int PATH_BLOCK = 256;
 // the weight dot (SPEC.md 4.8).  GV: the step's normals are scaled by u = sqrt(h) (STT: times s), h the path's GARCH(1,1) variance
 // ratio, and h is updated from the scaled normals (SPEC.md 4.9); in a GV kernel STT is set and nu = 0 at run time means Gaussian
 // draws.  AT: the step also carries every asset's contribution A_i = fma(V, fl32(w_i r_i), A_i) and the epilogue reduces them
-// (SPEC.md 4.10 / 5.9).  Every kernel below is the body in mcp_paths_body.inc under its own flags F: it names the flags it sets, the
-// rest are PathFlagsOff's.  F is a local class, which may not have static data members, so it sets its flags as enumerators of an
-// `enum : bool`; they hide the defaults' names and read as the same constant expressions.
+// (SPEC.md 4.10 / 5.9).  ANTI: a lane walks the two members of an antithetic pair on one set of draws: everything up to the step's
+// normals z (Philox, the transform, the chi blocks, h) runs once, everything downstream of z -- the row-pair accumulators, rho, V,
+// the peak and drawdown, the stores and the epilogue -- carries a second member that sees -z (SPEC.md 2.3 / 5.10).  Every kernel
+// below is the body in mcp_paths_body.inc under its own flags F: it names the flags it sets, the rest are PathFlagsOff's.  F is a
+// local class, which may not have static data members, so it sets its flags as enumerators of an `enum : bool`; they hide the
+// defaults' names and read as the same constant expressions.
 struct PathFlagsOff {
   static constexpr bool NATIVE = false, FOLD = false, LOGC = false, DD = false, HZ = false, BOOT = false, BLDS = false, REB = false,
-                        STT = false, CF = false, OV = false, GV = false, AT = false;
+                        STT = false, CF = false, OV = false, GV = false, AT = false, ANTI = false;
 };
 
 // __launch_bounds__ 2nd argument of a path kernel: the MCP_MIN_WAVES* above for N <= 16 and one path per lane, by the kind of
 // state the kernel carries; MCP_MIN_WAVES_BIG for 16 < N <= 64 and one portfolio; otherwise unbounded.
-enum BoundsKind { BK_PATHS, BK_REB, BK_CF, BK_OV, BK_AT };
+enum BoundsKind { BK_PATHS, BK_REB, BK_CF, BK_OV, BK_AT, BK_ANTI };
 constexpr int min_waves(BoundsKind kind, int NB, int KT, int PPT) {
+  if (kind == BK_ANTI) return (NB <= 4 && PPT == 1 && KT == 1) ? MCP_MIN_WAVES_ANTI : 1;
   if (NB <= 4 && PPT == 1 && KT == 1)
     return kind == BK_REB ? MCP_MIN_WAVES_REB : kind == BK_OV ? MCP_MIN_WAVES_OV : kind == BK_AT ? MCP_MIN_WAVES_AT : MCP_MIN_WAVES;
   if (NB <= 4 && PPT == 1 && kind != BK_PATHS && kind != BK_AT)
@@ -519,6 +555,21 @@ template <int NB, int KT, int PPT>
 __global__ void MCP_BOUNDS(BK_AT) mc_paths_attr_kernel(const PathArgsAT a) {
   static_assert(KT == 1, "one portfolio per pass");
   struct F : PathFlagsOff { enum : bool { STT = true, GV = true, AT = true }; };
+#include "mcp_paths_body.inc"
+}
+
+// The antithetic kernels (SPEC.md 2.3 / 5.10; spec normals, unfolded recurrence): one lane walks the pair (2j, 2j + 1) -- member 2j
+// is path j of the call without pairs, member 2j + 1 the same walk on -z.  The argument struct A selects the walk: PathArgsA,
+// PathArgsADD, PathArgsAHZ are mc_paths_kernel, mc_paths_dd_kernel and mc_paths_hz_kernel (simple or log compounding), PathArgsGA,
+// PathArgsGADD, PathArgsGAHZ their GARCH twins, which also serve Student-t and GARCH-free requests at run time as
+// mc_paths_attr_kernel does.  V_T, the drawdown, the horizons and the fused epilogue as there, over both members; the epilogue
+// also leaves the pair cross products.
+template <int NB, int KT, int PPT, bool LOGC_, class A>
+__global__ void MCP_BOUNDS(BK_ANTI) mc_paths_anti_kernel(const A a) {
+  static_assert(!(LOGC_ && has_gv<A>::value), "GARCH and Student-t paths compound simply");
+  struct F : PathFlagsOff {
+    enum : bool { ANTI = true, LOGC = LOGC_, DD = has_mdd<A>::value, HZ = has_hz<A>::value, STT = has_gv<A>::value, GV = has_gv<A>::value };
+  };
 #include "mcp_paths_body.inc"
 }
 #undef MCP_BOUNDS

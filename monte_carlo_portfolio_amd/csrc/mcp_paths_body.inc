@@ -4,8 +4,12 @@
 // walk is the one loop it always was.  In scope: the template parameters NB, KT, PPT, the flags F (PathFlagsOff or a struct
 // derived from it) and the kernel argument `a` (PathArgs or a struct that starts with one).
   constexpr bool NATIVE = F::NATIVE, FOLD = F::FOLD, LOGC = F::LOGC, DD = F::DD, HZ = F::HZ, BOOT = F::BOOT, BLDS = F::BLDS, REB = F::REB,
-                 STT = F::STT, CF = F::CF, OV = F::OV, GV = F::GV, AT = F::AT;
+                 STT = F::STT, CF = F::CF, OV = F::OV, GV = F::GV, AT = F::AT, ANTI = F::ANTI;
   constexpr int N4 = 4 * NB;
+  // ANTI (SPEC.md 2.3): a lane's PPT draws feed EM = 2 PPT members -- slot e < PPT walks on z[e], slot PPT + e on -z[e]; p, live and
+  // the counters are per draw (a.path_begin and a.n_paths count pairs), the members 2 p and 2 p + 1 are adjacent in the output rows
+  constexpr int EM = ANTI ? 2 * PPT : PPT;
+  static_assert(!ANTI || !(NATIVE || FOLD || BOOT || REB || CF || OV || AT), "antithetic pairs: the lean Gaussian and GARCH walks only");
   // wave-uniform parameters through the constant address space -> s_load_dword* into SGPRs
   typedef const __attribute__((address_space(4))) float* cfloat_p;
   cfloat_p mu = (cfloat_p)a.packed;
@@ -57,6 +61,9 @@
     double* const s_at = attr_wave_slots<N4>();
     for (int i = threadIdx.x; i < (PATH_BLOCK / 64) * attr_record_len(N4); i += PATH_BLOCK) s_at[i] = 0.0;
   }
+  if constexpr (ANTI) {                                    // the per-wave cross products of the pairs
+    if (threadIdx.x < (PATH_BLOCK / 64) * KT) pair_wave_slots<KT>()[threadIdx.x] = 0.0;
+  }
   __syncthreads();
   const IcdfConsts kc = icdf_consts();
   PhiloxKeys ks = philox_keys((uint32_t)a.seed, (uint32_t)(a.seed >> 32));
@@ -77,8 +84,8 @@
     uint64_t p[PPT];
     bool live[PPT];
     uint32_t plo[PPT], phi[PPT];
-    float V[PPT][KT];
-    float Pk[PPT][KT], Qk[PPT][KT];                       // DD: running peak P and q (simple) / d (log)
+    float V[EM][KT];
+    float Pk[EM][KT], Qk[EM][KT];                         // DD: running peak P and q (simple) / d (log)
     uint32_t jrow[PPT];                                   // BOOT: the row index j_t of SPEC.md 2.1
     f32x2 Bs[PPT][N4 / 2];                                // REB: the assets' returns since the last rebalance (SPEC.md 4.5)
     float Ps[PPT][N4];                                    // OV: the assets' price levels P_i (SPEC.md 4.8)
@@ -111,6 +118,13 @@
         const cspot_p sp = (cspot_p)kernarg<PathArgsOV>()->ov.spot;
 #pragma unroll
         for (int i = 0; i < N4; i++) Ps[e][i] = sp[i];
+      }
+      if constexpr (ANTI) {                               // the second member starts as the first
+#pragma unroll
+        for (int k = 0; k < KT; k++) {
+          V[PPT + e][k] = V[e][k];
+          if constexpr (DD) { Pk[PPT + e][k] = Pk[e][k]; Qk[PPT + e][k] = Qk[e][k]; }
+        }
       }
     }
 
@@ -219,7 +233,10 @@
             if (live[e]) {
 #pragma unroll
               for (int k = 0; k < KT; k++)
-                if (k < kt) row[(size_t)k * hs->hz_stride + p[e]] = V[e][k];
+                if (k < kt) {
+                  if constexpr (ANTI) *(float2*)&row[(size_t)k * hs->hz_stride + 2 * p[e]] = make_float2(V[e][k], V[PPT + e][k]);
+                  else row[(size_t)k * hs->hz_stride + p[e]] = V[e][k];
+                }
             }
         }
       }
@@ -284,7 +301,10 @@
       if (live[e]) {
 #pragma unroll
         for (int k = 0; k < KT; k++)
-          if (k < kt) a.terminal[(size_t)(a.k_begin + k) * a.stride + p[e]] = V[e][k];
+          if (k < kt) {
+            if constexpr (ANTI) *(float2*)&a.terminal[(size_t)(a.k_begin + k) * a.stride + 2 * p[e]] = make_float2(V[e][k], V[PPT + e][k]);
+            else a.terminal[(size_t)(a.k_begin + k) * a.stride + p[e]] = V[e][k];
+          }
         if constexpr (DD && OV) {                          // the drawdown output of the overlay kernel's arguments
           const auto dk = kernarg<PathArgsOV>();
 #pragma unroll
@@ -294,7 +314,10 @@
           const auto dk = kernarg<PathArgsDD>();
 #pragma unroll
           for (int k = 0; k < KT; k++)
-            if (k < kt) dk->mdd[(size_t)(a.k_begin + k) * dk->mdd_stride + p[e]] = Qk[e][k];
+            if (k < kt) {
+              if constexpr (ANTI) *(float2*)&dk->mdd[(size_t)(a.k_begin + k) * dk->mdd_stride + 2 * p[e]] = make_float2(Qk[e][k], Qk[PPT + e][k]);
+              else dk->mdd[(size_t)(a.k_begin + k) * dk->mdd_stride + p[e]] = Qk[e][k];
+            }
         }
       }
     }
@@ -311,31 +334,41 @@
       const int lane = tid & 63, wv = tid >> 6;
       unsigned long long cnt = 0;
 #pragma unroll
-      for (int e = 0; e < PPT; e++) cnt += (unsigned long long)__popcll(__ballot(live[e]));
+      for (int e = 0; e < PPT; e++) cnt += (unsigned long long)((EM / PPT) * __popcll(__ballot(live[e])));
       if (lane == 0) s_cnt[wv] += cnt;
 #pragma unroll 1
       for (int k = 0; k < kt; k++) {
         const double c = e_pivot ? e_pivot[a.k_begin + k] : 0.0;
         double d1 = 0.0, d2 = 0.0;
         float mn = __builtin_inff(), mx = -__builtin_inff();
+        double dm[EM];                                     // ANTI: d of every member, +0 for a dead lane
 #pragma unroll
-        for (int e = 0; e < PPT; e++) {
+        for (int e = 0; e < EM; e++) {
           float v = V[e][0];
 #pragma unroll
           for (int kk = 1; kk < KT; kk++) v = (kk == k) ? V[e][kk] : v;      // register select (k is a run-time index)
-          if (live[e]) {
+          if constexpr (ANTI) dm[e] = 0.0;
+          if (live[e % PPT]) {
             const double d = terminal_to_x(v, e_v0d, logc ? MCP_COMPOUND_LOG : MCP_COMPOUND_SIMPLE) - c;
             d1 += d;
             d2 = __builtin_fma(d, d, d2);
             mn = fminf(mn, v);
             mx = fmaxf(mx, v);
+            if constexpr (ANTI) dm[e] = d;
           }
-          if (e_hist) lds_hist_add(s_hist, float_to_key(v) >> 21, live[e]);
+          if (e_hist) lds_hist_add(s_hist, float_to_key(v) >> 21, live[e % PPT]);
         }
         d1 = wave_sum(d1); d2 = wave_sum(d2); mn = wave_minf(mn); mx = wave_maxf(mx);
         if (lane == 0) {                                   // this wave's own slot: no race, fixed order over the tiles
           s_mom[wv][k][0] += d1; s_mom[wv][k][1] += d2;
           s_ext[wv][k][0] = fminf(s_ext[wv][k][0], mn); s_ext[wv][k][1] = fmaxf(s_ext[wv][k][1], mx);
+        }
+        if constexpr (ANTI) {                              // SPEC.md 5.10: cross = sum (x_2j - c)(x_2j+1 - c), lane -> wave -> slot
+          double cr = 0.0;
+#pragma unroll
+          for (int e = 0; e < PPT; e++) cr = __builtin_fma(dm[e], dm[PPT + e], cr);
+          cr = wave_sum(cr);
+          if (lane == 0) pair_wave_slots<KT>()[wv * KT + k] += cr;
         }
         if (e_hist) {                                      // flush portfolio k's digit-0 counts (read-and-clear)
           __syncthreads();
@@ -368,6 +401,10 @@
       o.vmax = fmaxf(fmaxf(s_ext[0][k][1], s_ext[1][k][1]), fmaxf(s_ext[2][k][1], s_ext[3][k][1]));
       o.n = (s_cnt[0] + s_cnt[1]) + (s_cnt[2] + s_cnt[3]);
       kargs->partials[(size_t)(a.k_begin + k) * kargs->slots + blockIdx.x] = o;
+      if constexpr (ANTI) {                                // one cross partial per workgroup and portfolio, waves in order
+        const double* const s_cr = pair_wave_slots<KT>();
+        pair_cross(a)[(size_t)(a.k_begin + k) * gridDim.x + blockIdx.x] = (s_cr[k] + s_cr[KT + k]) + (s_cr[2 * KT + k] + s_cr[3 * KT + k]);
+      }
     }
   }
   if constexpr (AT) {

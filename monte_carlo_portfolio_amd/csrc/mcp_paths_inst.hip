@@ -49,6 +49,27 @@ static hipError_t ladder(const PathKernel& k, const PathLaunchArgs& s, hipStream
   const bool gauss = !k.boot && !k.stt && !k.gv;                               // Gaussian draws
   const bool t = k.stt && !k.gv && !k.boot, g = k.gv && !k.boot;                // Student-t draws; GARCH (nu = 0: Gaussian draws)
   const bool bl = k.boot && k.blds && !k.stt && !k.gv, bg = k.boot && !k.blds && !k.stt && !k.gv;   // rows from LDS / global memory
+  if (k.anti) {                                           // SPEC.md 2.3: gv names the GARCH walk, which also serves Student-t requests
+    const bool lean = gauss && !k.native, gw = k.stt && k.gv && !k.boot && !k.native && !lg;
+    switch (k.family) {
+      case FAM_PLAIN:
+        MCP_ROW(lean && lg, mc_paths_anti_kernel<NB, KT, 1, true, PathArgsA>);
+        MCP_ROW(lean && !lg, mc_paths_anti_kernel<NB, KT, 1, false, PathArgsA>);
+        MCP_ROW(gw, mc_paths_anti_kernel<NB, KT, 1, false, PathArgsGA>);
+        break;
+      case FAM_DD:
+        MCP_ROW(lean && lg, mc_paths_anti_kernel<NB, KT, 1, true, PathArgsADD>);
+        MCP_ROW(lean && !lg, mc_paths_anti_kernel<NB, KT, 1, false, PathArgsADD>);
+        MCP_ROW(gw, mc_paths_anti_kernel<NB, KT, 1, false, PathArgsGADD>);
+        break;
+      case FAM_HZ:
+        MCP_ROW(lean && lg, mc_paths_anti_kernel<NB, KT, 1, true, PathArgsAHZ>);
+        MCP_ROW(lean && !lg, mc_paths_anti_kernel<NB, KT, 1, false, PathArgsAHZ>);
+        MCP_ROW(gw, mc_paths_anti_kernel<NB, KT, 1, false, PathArgsGAHZ>);
+        break;
+    }
+    return hipErrorInvalidValue;
+  }
   if (k.native) {
     MCP_ROW(k.family == FAM_PLAIN && gauss && lg, mc_paths_kernel<NB, KT, 1, true, false, true>);
     MCP_ROW(k.family == FAM_PLAIN && gauss && !lg, mc_paths_kernel<NB, KT, 1, true, false, false>);
@@ -104,6 +125,7 @@ static hipError_t ladder(const PathKernel& k, const PathLaunchArgs& s, hipStream
 
 hipError_t MCP_CAT(launch_paths_nb, MCP_NB)(const PathKernel& k, const PathLaunchArgs& s, hipStream_t stream) {
   constexpr int NB = MCP_NB, KT = 1;                       // the folded step and the attribution walk: one portfolio per pass
+  if (k.anti && (k.fold || k.family == FAM_AT)) return hipErrorInvalidValue;
   if (k.fold) {                                            // rho = c + v.z: the plain Gaussian walk on the spec's normals
     const bool ok = k.family == FAM_PLAIN && !k.boot && !k.stt && !k.gv && !k.native && !k.kt8;
     MCP_ROW(ok && k.logc, mc_paths_kernel<NB, 1, 1, false, true, true>);

@@ -8,8 +8,11 @@
 // level (SPEC.md 4.8); whether an asset owns rows is wave-uniform, a scalar branch.  GV: s is replaced by u = s sqrt(h) (nu = 0: u =
 // sqrt(h), the chi blocks skipped by a scalar branch) and h is updated from the scaled normals (SPEC.md 4.9).  AT: between the row
 // pair's returns and the weight dot, c = fl32(w r) and A = fma(V, c, A) for the pair, one v_pk_mul_f32 and one v_pk_fma_f32, V the
-// value before this step's update (SPEC.md 4.10).  In scope: everything mcp_paths_body.inc declares before its step loops, and t.
-      float rho[PPT][KT];
+// value before this step's update (SPEC.md 4.10).  ANTI: the step's normals are formed once; the row pair's accumulator, rho and
+// the update of V (DD: of the peak and drawdown) run for EM = 2 PPT members, member PPT + e on -z[e] (SPEC.md 2.3): a second fma
+// chain from the same mu2 -- never a shared L z, mu + L z and mu - L z round differently.  In scope: everything mcp_paths_body.inc
+// declares before its step loops, and t.
+      float rho[EM][KT];
       if constexpr (BOOT) {
         // SPEC.md 2.1 / 4.4: one Philox block on counter (t, 1, p_lo, p_hi); j_t = mulhi(x0, R) on a restart (t = 0 or
         // x1 < thr), else the next row, circularly; rho_k = sum_i w_ki r_i, i ascending over N4 (zero-padded rows)
@@ -147,24 +150,28 @@
       } else {
       // r = mu + L z (row i: acc = mu_i, then j ascending), rho_k = sum_i w_ki r_i (i ascending)
 #pragma unroll
-      for (int e = 0; e < PPT; e++)
+      for (int e = 0; e < EM; e++)
 #pragma unroll
         for (int k = 0; k < KT; k++) rho[e][k] = 0.0f;
       // Rows are processed in pairs (2m, 2m+1): one v_pk_fma_f32 per column does both rows, its L operand
       // an SGPR pair straight from the row-pair-interleaved parameter block, z_j broadcast by op_sel.
 #pragma unroll
       for (int m = 0; m < N4 / 2; m++) {
-        f32x2 acc[PPT];
+        f32x2 acc[EM];
         f32x2 mu2;
         if constexpr (LDS_MU) mu2 = *(const f32x2*)&s_par[2 * m];
         else mu2 = f32x2{mu[2 * m], mu[2 * m + 1]};
 #pragma unroll
-        for (int e = 0; e < PPT; e++) acc[e] = mu2;
+        for (int e = 0; e < EM; e++) acc[e] = mu2;
 #pragma unroll
         for (int j = 0; j <= 2 * m + 1; j++) {
           const f32x2 l2 = {Lp[2 * m * (m + 1) + 2 * j], Lp[2 * m * (m + 1) + 2 * j + 1]};   // (L[2m][j], L[2m+1][j])
 #pragma unroll
           for (int e = 0; e < PPT; e++) acc[e] = __builtin_elementwise_fma(l2, (f32x2){z[e][j], z[e][j]}, acc[e]);
+          if constexpr (ANTI) {                        // fma(L, -z, r): the negation is a source modifier of the packed fma
+#pragma unroll
+            for (int e = 0; e < PPT; e++) acc[PPT + e] = __builtin_elementwise_fma(l2, (f32x2){-z[e][j], -z[e][j]}, acc[PPT + e]);
+          }
         }
         if constexpr (REB) {
 #pragma unroll
@@ -202,7 +209,7 @@
           for (int k = 0; k < KT; k++) {
             const float wki = LDS_W ? s_par[N4 + i] : Wk[k * N4 + i];   // rows >= kt are zero-padded by pack_params
 #pragma unroll
-            for (int e = 0; e < PPT; e++) rho[e][k] = fma32(wki, h ? acc[e].y : acc[e].x, rho[e][k]);
+            for (int e = 0; e < EM; e++) rho[e][k] = fma32(wki, h ? acc[e].y : acc[e].x, rho[e][k]);
           }
         }
         }  // !REB
@@ -221,7 +228,7 @@
           }
       } else if constexpr (!REB) {
 #pragma unroll
-      for (int e = 0; e < PPT; e++)
+      for (int e = 0; e < EM; e++)
 #pragma unroll
         for (int k = 0; k < KT; k++)
           V[e][k] = logc ? (V[e][k] + rho[e][k]) : fma32(V[e][k], rho[e][k], V[e][k]);
@@ -230,7 +237,7 @@
         // SPEC.md 4.2: P = fmax(P, V_t); q = fminf(q, V_t / P) (IEEE division) or d = fminf(d, S_t - P).  fminf is IEEE
         // minNum: the 0/0 of a zero peak is ignored.
 #pragma unroll
-        for (int e = 0; e < PPT; e++)
+        for (int e = 0; e < EM; e++)
 #pragma unroll
           for (int k = 0; k < KT; k++) {
             Pk[e][k] = fmaxf(Pk[e][k], V[e][k]);

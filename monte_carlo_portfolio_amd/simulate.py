@@ -65,12 +65,13 @@ class Context:
 
     def _call(self, prm: _ffi.McpParams, W, seed: int, path_begin: int, n_paths: int, store: bool, mu=None, chol=None, rows=None,
               block: float = 1.0, dof=None, period=None, cost: float = 0.0, drawdown: bool = False, horizons=None, levels=(),
-              flows=None, target=None, overlay=None, garch=None, attribution=False):
+              flows=None, target=None, overlay=None, garch=None, attribution=False, antithetic=False):
         """The one library call behind every simulate_* method: GARCH volatility (garch: the (alpha, beta, h0) of check_garch), an option overlay (overlay: the triple of check_overlay), cash flows (flows, target), Student-t draws (dof), rebalancing
         (period, cost), bootstrap rows (rows, block) or Gaussian draws (mu, chol), with the drawdown or horizons.  Allocates the
         outputs that were asked for and passes NULL for the rest -> _Outputs, None where not asked for (terminal, qd,
         horizon_terminal: with `store` only; counts, hz_counts: with `flows` only; attr [K, N] records of ATTR_DTYPE and attr_counts
-        [K, 2] with `attribution` only, contributions [K, N, n_paths] with `store` on top)."""
+        [K, 2] with `attribution` only, contributions [K, N, n_paths] with `store` on top; pairs [K] records of PAIR_DTYPE with
+        `antithetic` only)."""
         K = prm.n_portfolios
         ptr = lambda a: a.ctypes.data_as(ctypes.c_void_p) if a is not None else None   # noqa: E731
         stats = np.zeros(K, _ffi.STATS_DTYPE)
@@ -91,8 +92,18 @@ class Context:
         hz_in = (H, ptr(steps) if H else None, L, ptr(lv) if L else None)
         hz_out = (ptr(hz_term), ptr(hz_stats), ptr(bands) if L else None)
         bt = _ffi.make_bootstrap(rows, block) if rows is not None else None
-        attr = attr_counts = contrib = None
-        if attribution:
+        attr = attr_counts = contrib = pairs = None
+        if antithetic:
+            # the library states the rules (check_request): everything but plain, Student-t and GARCH draws is MCP_E_UNSUPPORTED
+            if overlay is not None or flows is not None or period is not None or bt is not None or attribution:
+                raise ValueError("antithetic pairs are not combined with overlay, cashflow, rebalance, bootstrap rows or attribution")
+            pairs = np.zeros(K, _ffi.PAIR_DTYPE)
+            st = _ffi.McpStudentT(int(dof), 0) if dof is not None else None
+            gv = _ffi.McpGarch(float(garch[0]), float(garch[1]), float(garch[2]), 0) if garch is not None else None
+            rc = lib.mcp_simulate_antithetic(self._h, prm_p, ctypes.byref(gv) if gv is not None else None,
+                                             ctypes.byref(st) if st is not None else None, ptr(mu), ptr(chol), ptr(W), *walk, *hz_in,
+                                             ptr(term), ptr(stats), ptr(raw), ptr(dd_stats), *hz_out, ptr(pairs))
+        elif attribution:
             # the library states the rules (check_request): everything but plain, Student-t and GARCH draws is MCP_E_UNSUPPORTED
             if (overlay is not None or flows is not None or period is not None or bt is not None or horizons is not None or drawdown):
                 raise ValueError("attribution is not combined with overlay, cashflow, rebalance, bootstrap rows, horizons or drawdown")
@@ -140,7 +151,7 @@ class Context:
         else:
             rc = lib.mcp_simulate(self._h, prm_p, mu, chol, W, *walk, ptr(term), ptr(stats))
         _ffi.check(rc)
-        return _Outputs(stats, dd_stats, hz_stats, bands, term, raw, hz_term, counts, hz_counts, attr, attr_counts, contrib)
+        return _Outputs(stats, dd_stats, hz_stats, bands, term, raw, hz_term, counts, hz_counts, attr, attr_counts, contrib, pairs)
 
     def simulate(self, prm: _ffi.McpParams, mu, chol, W, seed: int, path_begin: int, n_paths: int, store: bool):
         o = self._call(prm, W, seed, path_begin, n_paths, store, mu=mu, chol=chol)
@@ -212,6 +223,15 @@ class Context:
         contributions [K, N, n_paths] binary32."""
         return self._call(prm, W, seed, path_begin, n_paths, store, mu=mu, chol=chol, dof=dof, garch=garch, attribution=True)
 
+    def simulate_antithetic(self, prm: _ffi.McpParams, mu, chol, W, seed: int, path_begin: int, n_paths: int, store: bool, dof=None,
+                            garch=None, drawdown: bool = False, horizons=None, levels=()):
+        """simulate() / simulate_drawdown() / simulate_horizons() / simulate_student_t() / simulate_garch() on antithetic pairs
+        (SPEC.md 2.3 / 5.10; include/mcport.h, mcp_simulate_antithetic; path_begin and n_paths even; log compounding on Gaussian
+        draws only; path shards) -> _Outputs: the paths 2j and 2j + 1 share the draws of path j of the call without pairs, path
+        2j + 1 with the asset normals negated; the statistics are over all n_paths values, pairs [K] records of _ffi.PAIR_DTYPE."""
+        return self._call(prm, W, seed, path_begin, n_paths, store, mu=mu, chol=chol, dof=dof, garch=garch, drawdown=drawdown,
+                          horizons=horizons, levels=levels, antithetic=True)
+
     def simulate_cashflow(self, prm: _ffi.McpParams, flows, W, seed: int, path_begin: int, n_paths: int, store: bool, mu=None,
                           chol=None, rows=None, block: float = 1.0, dof=None, target=None, horizons=None, levels=()):
         """simulate() / simulate_horizons() / simulate_bootstrap[_horizons]() / simulate_student_t() with the schedule `flows`
@@ -238,9 +258,9 @@ class Context:
 # binary32 arrays (terminal [K, n], qd [K, n], horizon_terminal [H, K, n]); with cash flows the counts {n_ruined, n_short} of
 # SPEC.md 5.6 (counts [K, 2], hz_counts [H, K, 2], uint64).
 # With attribution the records of SPEC.md 5.9 (attr [K, N] of ATTR_DTYPE, attr_counts [K, 2] uint64 {n, n_tail}) and, stored, the
-# binary32 contributions [K, N, n].
+# binary32 contributions [K, N, n].  With antithetic pairs the records of SPEC.md 5.10 (pairs [K] of PAIR_DTYPE).
 _Outputs = collections.namedtuple("_Outputs", "stats dd_stats hz_stats bands terminal qd horizon_terminal counts hz_counts attr "
-                                  "attr_counts contributions", defaults=(None, None, None, None, None))
+                                  "attr_counts contributions pairs", defaults=(None, None, None, None, None, None))
 
 
 def check_cashflow(cashflow, target, n_steps):
@@ -504,11 +524,19 @@ def attribution_to_dict(attr, counts, rec) -> dict:
                          "vol": float(rec["std"]) - float(vol.sum())}}
 
 
+def antithetic_to_dict(rec) -> dict:
+    """The 'antithetic' block of one portfolio from its mcp_pair record (SPEC.md 5.10); variance_ratio is the variance of the mean
+    over what independent paths would have given, (mean_se / mean_se_iid)^2, 0 when the denominator is 0."""
+    se, iid = float(rec["mean_se"]), float(rec["mean_se_iid"])
+    return {"n_pairs": int(rec["n_pairs"]), "pair_corr": float(rec["pair_corr"]), "pair_cov": float(rec["pair_cov"]), "mean_se": se,
+            "mean_se_iid": iid, "variance_ratio": (se / iid) ** 2 if iid != 0.0 else 0.0}
+
+
 def simulate_paths(mu, cov, weights, n_steps=252, n_paths=10_000, seed=0, v0=1.0, compounding="simple",
                    rf=0.0, alpha=0.95, devices=None, store=False, path_begin=0, chol=None,
                    native_math=False, as_array=False, fold=False, shard="auto", context=None, drawdown=False,
                    horizons=None, bands=(), rebalance=None, rebalance_cost=0.0, dof=None, cashflow=None, target=None,
-                   overlay=None, spot=None, garch=None, attribution=False):
+                   overlay=None, spot=None, garch=None, attribution=False, antithetic=False):
     """Simulate `n_paths` correlated return paths and reduce them to risk statistics.
 
     mu [N], cov [N,N] are per-step mean and covariance (the reference's `mean_returns`, `cov_matrix`
@@ -589,7 +617,31 @@ def simulate_paths(mu, cov, weights, n_steps=252, n_paths=10_000, seed=0, v0=1.0
     Not built: attribution with drawdown, horizons, rebalance, cashflow, overlay, fold, native_math, compounding="log",
     shard="portfolios" or more than 16 portfolios (ValueError), on bootstrap paths (simulate_bootstrap), in simulate_sweep (call
     simulate_paths for the optimum), in PathEngine and at the mcp_launch_* level.
+
+    antithetic=False (default): independent paths.  antithetic=True: antithetic pairs (SPEC.md 2.3 / 5.10; n_paths and path_begin
+    even).  The paths 2j and 2j + 1 share every draw of path j of the call without it and path 2j + 1 sees the asset normals negated
+    (the Student-t scale and the GARCH variance are shared), so the pair's returns are strongly negatively correlated and the mean
+    -- what Sharpe ranks on -- is far more accurate than n_paths independent paths give; tail statistics gain less.  Every
+    statistic is the usual one over all n_paths values.  Every dict gains 'antithetic' {n_pairs, pair_corr, pair_cov, mean_se (the
+    standard error of the mean, from the n_paths / 2 independent pair means: std / sqrt(n) is wrong for such a sample), mean_se_iid
+    (std / sqrt(n), what independent paths would have given), variance_ratio (their ratio squared)}.  as_array=True appends the [K]
+    record array of _ffi.PAIR_DTYPE last.  A kernel lane walks both members on one set of draws.  Combines with dof, garch,
+    drawdown, horizons / bands, store, as_array, devices (path shards, cut at even path ids) and compounding="log" on Gaussian
+    draws.  Not built: antithetic with rebalance, cashflow, overlay, attribution, fold, native_math or shard="portfolios"
+    (ValueError), on bootstrap paths (observed rows have no sign to flip), in simulate_sweep (call simulate_paths for the
+    optimum), in PathEngine and at the mcp_launch_* level.
     """
+    if not isinstance(antithetic, (bool, np.bool_)):
+        raise ValueError(f"antithetic must be True or False, got {antithetic!r}")
+    if antithetic:
+        bad = [name for name, on in (("rebalance", rebalance is not None), ("cashflow", cashflow is not None),
+                                     ("overlay", overlay is not None), ("attribution", bool(attribution)), ("fold", fold),
+                                     ("native_math", native_math), ("shard='portfolios'", shard == "portfolios")) if on]
+        if bad:
+            raise ValueError("antithetic needs constant weights, the spec's normals, the unfolded recurrence and path shards: not with "
+                             f"{', '.join(bad)}")
+        if int(n_paths) % 2 or int(path_begin) % 2:
+            raise ValueError(f"antithetic pairs need an even n_paths and an even path_begin, got n_paths={n_paths}, path_begin={path_begin}")
     if not isinstance(attribution, (bool, np.bool_)):
         raise ValueError(f"attribution must be True or False, got {attribution!r}")
     if attribution:
@@ -631,10 +683,10 @@ def simulate_paths(mu, cov, weights, n_steps=252, n_paths=10_000, seed=0, v0=1.0
     steps, levels = _check_walk(n_steps, horizons, bands, period, compounding, shard)
     mu32, L, W = prepare_inputs(mu, cov, weights, chol)
     prm, ctx = _setup(mu32.shape[0], n_steps, W.shape[0], compounding, v0, alpha, rf, native_math, fold, devices,
-                      "paths" if attribution else shard, context)
+                      "paths" if attribution or antithetic else shard, context)
     out = ctx._call(prm, W, int(seed), int(path_begin), int(n_paths), store, mu=mu32, chol=L, dof=dof, period=period, cost=cost,
                     drawdown=drawdown, horizons=steps, levels=levels, flows=flows, target=target, overlay=ov, garch=gv,
-                    attribution=bool(attribution))
+                    attribution=bool(attribution), antithetic=bool(antithetic))
     return _result(out, np.asarray(weights).ndim == 1, store, as_array, steps, levels, compounding, flows, target)
 
 
@@ -680,8 +732,11 @@ def _result(out, single, store, as_array, steps, levels, compounding, flows=None
     then (hz_stats, bands) or dd_stats, then with `store` terminal and horizon_terminal or max_drawdown); else one dict per
     portfolio (one dict for a single weight vector) with its 'drawdown' / 'horizons' blocks and, with `store`, the stored arrays."""
     stats, dd_stats, hz_stats, hz_bands, term, qd, hz_term, counts, hz_counts = out[:9]
-    attr, attr_counts, contrib = out[9:]
+    attr, attr_counts, contrib, pairs = out[9:]
     mdd = mdd_from_raw(qd, compounding) if dd_stats is not None and store else None
+    if as_array and pairs is not None:    # SPEC.md 5.10: what the call without pairs returns, then the [K] pair records
+        base = _result(out._replace(pairs=None), single, store, as_array, steps, levels, compounding, flows, target)
+        return (base if isinstance(base, tuple) else (base,)) + (pairs,)
     if as_array:                          # [K] structured arrays (fields of mcp_stats), for large sweeps
         cash = () if counts is None else (counts,) if hz_counts is None else (counts, hz_counts)
         if hz_stats is not None:
@@ -707,6 +762,8 @@ def _result(out, single, store, as_array, steps, levels, compounding, flows=None
             d["cashflow"] = _cash_block(counts[k], int(stats[k]["n"]), target, float(np.sum(flows.astype(np.float64))))
         if attr is not None:
             d["attribution"] = attribution_to_dict(attr[k], attr_counts[k], stats[k])
+        if pairs is not None:
+            d["antithetic"] = antithetic_to_dict(pairs[k])
         if store:
             d["terminal"] = term[k]
             if contrib is not None:
@@ -766,6 +823,10 @@ def simulate_bootstrap(returns, weights, n_steps=252, n_paths=10_000, block=1.0,
         raise ValueError("simulate_bootstrap does not take attribution: the second walk re-draws normals, the bootstrap's rows are not "
                          "built into it -- call simulate_paths(attribution=True)")
     unsupported.pop("attribution", None)
+    if unsupported.get("antithetic"):
+        raise ValueError("simulate_bootstrap does not take antithetic: observed rows have no sign to flip -- antithetic pairs negate "
+                         "the normals of a parametric model, call simulate_paths(antithetic=True)")
+    unsupported.pop("antithetic", None)
     if unsupported.get("garch") is not None:
         raise ValueError("simulate_bootstrap does not take garch: the rows carry their own dynamics -- a mean block length block > 1 "
                          "keeps the volatility regimes of the observed rows; GARCH is a parametric model, call "
@@ -809,6 +870,10 @@ def simulate_sweep(mu, cov, weights=None, n_portfolios=2500, min_weights=None, m
     if kw.get("attribution"):
         raise ValueError("simulate_sweep does not take attribution: call simulate_paths for the optimum")
     kw.pop("attribution", None)
+    if kw.get("antithetic"):
+        raise ValueError("simulate_sweep does not take antithetic: the sweep ranks the portfolios on common random numbers -- call "
+                         "simulate_paths(antithetic=True) for the optimum, whose mean then carries its standard error")
+    kw.pop("antithetic", None)
     drawdown = bool(kw.get("drawdown", False))
     stats = simulate_paths(mu, cov, W, n_steps=n_steps, n_paths=n_paths, seed=seed, rf=rf, alpha=alpha, as_array=True, **kw)
     dd_stats = None
