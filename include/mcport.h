@@ -478,7 +478,12 @@ int mcp_overlay_pivots(const mcp_params *prm, const mcp_overlay *ov, const float
  * vectors at once, binary64 like the reference.  returns: [R*N] row-major (returns_df.values, app.py:667),
  * mean/cov: the annualised mean_returns / cov_matrix of app.py:679-680, W: [P*N] (rows as drawn at
  * app.py:702), rf in the reference's units (user_rf, app.py:711), alpha = cvar_alpha (app.py:684).
- * Outputs are [P] each.  Limits: N <= MCP_MAX_ASSETS, R <= MCP_SWEEP_MAX_ROWS. */
+ * Outputs are [P] each.  Limits: N <= MCP_MAX_ASSETS, R <= MCP_SWEEP_MAX_ROWS.
+ * Every value of returns, W, mean and cov must be finite (the rule of mcp_bootstrap rows): a NaN or an infinity is MCP_E_ARG,
+ * mcp_last_error() naming the array and the first offending index, found by a host scan before anything is copied or
+ * launched -- the kernels order the series with plain compares, under which a NaN would come back as a finite VaR.  Drop such
+ * rows first, as the reference's ingest does.  cvar is the tail mean from an exactly accumulated sum, kept inside
+ * [smallest tail element, var], so cvar <= var always and cvar == var where the tail is one value repeated. */
 #define MCP_SWEEP_MAX_ROWS 4096
 int mcp_sweep_historical(mcp_ctx *ctx, int n_assets, int n_rows, int n_portfolios, const double *returns,
                          const double *mean, const double *cov, const double *W, double rf, double alpha,

@@ -2210,8 +2210,26 @@ int mcp_sweep_historical(mcp_ctx* c, int N, int R, int P, const double* returns,
   if (R < 1 || R > MCP_SWEEP_MAX_ROWS) return fail(MCP_E_ARG, "n_rows=%d outside [1,%d]", R, MCP_SWEEP_MAX_ROWS);
   if (P < 1) return fail(MCP_E_ARG, "n_portfolios=%d < 1", P);
   if (!(alpha > 0.0 && alpha < 1.0)) return fail(MCP_E_ARG, "alpha=%g outside (0,1)", alpha);
-  if (!returns || !mean || !cov || !W || !o_ret || !o_std || !o_sharpe || !o_var || !o_cvar)
-    return fail(MCP_E_ARG, "NULL pointer");
+  const void* const ptrs[9] = {returns, mean, cov, W, o_ret, o_std, o_sharpe, o_var, o_cvar};
+  static const char* const ptr_names[9] = {"returns", "mean", "cov", "W", "port_return", "port_std", "sharpe", "var", "cvar"};
+  for (int i = 0; i < 9; i++)
+    if (!ptrs[i]) return fail(MCP_E_ARG, "%s is NULL", ptr_names[i]);
+  // Finite input only, the rule of bootstrap rows (check_bootstrap): the kernels order the series with plain compares, under
+  // which a NaN has no rank, and would answer with a finite number.  A host scan of (R + 1 + N + P) * N doubles, at most
+  // 4096 * 64 + P * 64 for returns and W, before any copy or launch.
+  const auto first_bad = [](const double* a, size_t n) {
+    size_t i = 0;
+    while (i < n && std::isfinite(a[i])) i++;
+    return i;
+  };
+  const size_t n = (size_t)N;
+  size_t i;
+  if ((i = first_bad(returns, (size_t)R * n)) < (size_t)R * n)
+    return fail(MCP_E_ARG, "returns[%zu] (row %zu, asset %zu) is not finite", i, i / n, i % n);
+  if ((i = first_bad(W, (size_t)P * n)) < (size_t)P * n)
+    return fail(MCP_E_ARG, "W[%zu] (portfolio %zu, asset %zu) is not finite", i, i / n, i % n);
+  if ((i = first_bad(mean, n)) < n) return fail(MCP_E_ARG, "mean[%zu] is not finite", i);
+  if ((i = first_bad(cov, n * n)) < n * n) return fail(MCP_E_ARG, "cov[%zu] (row %zu, column %zu) is not finite", i, i / n, i % n);
   std::lock_guard<std::mutex> lock(c->mu);
   Shard& sh = c->sh[0];
   DeviceGuard guard(sh.device);

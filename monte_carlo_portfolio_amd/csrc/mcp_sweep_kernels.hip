@@ -27,6 +27,37 @@ __device__ __forceinline__ double wsum(double v) {
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
   return v;
 }
+__device__ __forceinline__ double wmin(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = fmin(v, __shfl_xor(v, o, 64));
+  return v;
+}
+// The tail sum as an unevaluated pair s + c: c collects what every addition rounds away (Knuth's TwoSum, exact here because the
+// build neither contracts nor reassociates), so the sum is the exact one rounded once, in whatever order the lanes add.  A plain
+// tree of R / 256 + 8 additions is off by up to that many roundings of the running sum, which a tail of equal or nearly equal
+// values shows in the last digits of the mean.
+struct Sum2 {
+  double s, c;
+};
+__device__ __forceinline__ void add2(Sum2& a, double x) {
+  const double t = a.s + x, bp = t - a.s;
+  a.c += (a.s - (t - bp)) + (x - bp);
+  a.s = t;
+}
+__device__ __forceinline__ Sum2 wsum2(Sum2 a) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const double os = __shfl_xor(a.s, o, 64), oc = __shfl_xor(a.c, o, 64);
+    add2(a, os);
+    a.c += oc;
+  }
+  return a;
+}
+// The tail mean, kept inside its range [smallest tail element, VaR]: even the exact sum, rounded and divided by the count, can leave
+// it by an ulp when the tail is one value repeated (three times 0.1, over 3, is above 0.1), and CVaR <= VaR is what callers rely on.
+__device__ __forceinline__ double tail_mean(Sum2 sum, double cnt, double lo, double v) {
+  return cnt > 0.0 ? fmin(fmax((sum.s + sum.c) / cnt, lo), v) : v;
+}
 
 // grid = P, block = 64, dynamic LDS = (R + N) doubles
 __global__ void __launch_bounds__(64) sweep_hist_kernel(int N, int R, const double* __restrict__ returns,
@@ -80,19 +111,21 @@ __global__ void __launch_bounds__(64) sweep_hist_kernel(int N, int R, const doub
   double v = a + diff * gamma;                    // numpy _lerp
   if (gamma >= 0.5) v = b - diff * (1.0 - gamma);
 
-  double cnt = 0.0, sum = 0.0;
+  double cnt = 0.0, lo = v;
+  Sum2 sum = {0.0, 0.0};
   for (int r = lane; r < R; r += 64) {
     const double x = series[r];
-    if (x <= v) { cnt += 1.0; sum += x; }
+    if (x <= v) { cnt += 1.0; add2(sum, x); lo = fmin(lo, x); }
   }
   cnt = wsum(cnt);
-  sum = wsum(sum);
+  sum = wsum2(sum);
+  lo = wmin(lo);
   if (lane == 0) {
     out_ret[p] = pr;
     out_std[p] = sd;
     out_sharpe[p] = sd > 0.0 ? (pr - rf) / sd : 0.0;
     out_var[p] = v;
-    out_cvar[p] = cnt > 0.0 ? sum / cnt : v;
+    out_cvar[p] = tail_mean(sum, cnt, lo, v);
   }
 }
 
@@ -105,6 +138,15 @@ __device__ __forceinline__ double bsum(double v, double* red /* [4] LDS */) {
   __syncthreads();
   return (red[0] + red[1]) + (red[2] + red[3]);
 }
+__device__ __forceinline__ Sum2 bsum2(Sum2 a, double* red /* [8] LDS */) {
+  a = wsum2(a);
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) { red[threadIdx.x >> 6] = a.s; red[4 + (threadIdx.x >> 6)] = a.c; }
+  __syncthreads();
+  Sum2 r = {red[0], red[4]};
+  for (int i = 1; i < 4; i++) { add2(r, red[i]); r.c += red[4 + i]; }
+  return r;
+}
 
 // grid = P, block = 256, dynamic LDS = (R2 + N) doubles, R2 = R rounded up to a power of two
 __global__ void __launch_bounds__(SORT_BLOCK) sweep_hist_sorted_kernel(int N, int R, int R2, const double* __restrict__ returns,
@@ -114,7 +156,7 @@ __global__ void __launch_bounds__(SORT_BLOCK) sweep_hist_sorted_kernel(int N, in
                                                                        double* __restrict__ out_std, double* __restrict__ out_sharpe,
                                                                        double* __restrict__ out_var, double* __restrict__ out_cvar) {
   extern __shared__ double lds[];
-  __shared__ double red[4];
+  __shared__ double red[8];
   double* series = lds;        // [R2], sorted in place
   double* w = lds + R2;        // [N]
   const int p = blockIdx.x, tid = threadIdx.x;
@@ -162,19 +204,20 @@ __global__ void __launch_bounds__(SORT_BLOCK) sweep_hist_sorted_kernel(int N, in
   double v = a + diff * gamma;                    // numpy _lerp
   if (gamma >= 0.5) v = b - diff * (1.0 - gamma);
 
-  double cnt = 0.0, sum = 0.0;
+  double cnt = 0.0;
+  Sum2 sum = {0.0, 0.0};
   for (int r = tid; r < R; r += SORT_BLOCK) {
     const double x = series[r];
-    if (x <= v) { cnt += 1.0; sum += x; }
+    if (x <= v) { cnt += 1.0; add2(sum, x); }
   }
   cnt = bsum(cnt, red);
-  sum = bsum(sum, red);
+  sum = bsum2(sum, red);
   if (tid == 0) {
     out_ret[p] = pr;
     out_std[p] = sd;
     out_sharpe[p] = sd > 0.0 ? (pr - rf) / sd : 0.0;
     out_var[p] = v;
-    out_cvar[p] = cnt > 0.0 ? sum / cnt : v;
+    out_cvar[p] = tail_mean(sum, cnt, series[0], v);   // sorted: series[0] is the smallest
   }
 }
 

@@ -112,9 +112,31 @@ def sweep_inputs(returns_df, annual_factor):
 
 
 def score_portfolios(R, mean, cov, W, rf, alpha=0.95, device=0):
-    """app.py:708-713 for all rows of W on the GPU -> dict of float64 [P] arrays."""
+    """app.py:708-713 for all rows of W on the GPU -> dict of float64 [P] arrays.
+
+    Every value of R, mean, cov and W must be finite, the rule `simulate_bootstrap` has for historical rows: the kernels order
+    the series with plain compares, under which a NaN has no place, so such input is a ValueError here (and MCP_E_ARG in
+    `mcp_sweep_historical`), not a finite number that looks like a VaR.  The reference's ingest drops such rows."""
     W = np.ascontiguousarray(W, np.float64)
+    if W.ndim != 2:
+        raise ValueError(f"W must be a [P, N] matrix, got shape {W.shape}")
     P, N = W.shape
+    R = np.ascontiguousarray(R, np.float64)
+    mean = np.ascontiguousarray(mean, np.float64)
+    cov = np.ascontiguousarray(cov, np.float64)
+    if R.ndim != 2 or R.shape[1] != N:
+        raise ValueError(f"returns must be an [R, {N}] matrix like the {N} columns of W, got shape {R.shape}")
+    if mean.shape != (N,):
+        raise ValueError(f"mean must have shape ({N},), got {mean.shape}")
+    if cov.shape != (N, N):
+        raise ValueError(f"cov must have shape ({N}, {N}), got {cov.shape}")
+    for name, a, axes in (("returns", R, ("row", "asset")), ("W", W, ("portfolio", "asset")), ("mean", mean, ("asset",)),
+                          ("cov", cov, ("row", "column"))):
+        bad = ~np.isfinite(a)
+        if bad.any():
+            first = np.unravel_index(int(np.argmax(bad)), a.shape)
+            where = ", ".join(f"{ax} {int(i)}" for ax, i in zip(axes, first))
+            raise ValueError(f"NaN or infinite values in {name} (first: {where}); {int(bad.sum())} in all, drop them first")
     outs = [np.empty(P, np.float64) for _ in range(5)]
     if P:
         ctx = default_context(device)

@@ -13,6 +13,7 @@ import numpy as np
 import pandas as pd
 import pytest
 
+import sweep_ref
 from monte_carlo_portfolio_amd import sweep
 
 pytestmark = pytest.mark.gpu
@@ -127,9 +128,7 @@ def test_sweep_on_long_histories(gpu_ctx, R, N, P):
     t0 = time.perf_counter()
     s = sweep.score_portfolios(Rc, mean, cov, W, rf=0.03)
     dt = time.perf_counter() - t0
-    series = np.empty((R, P))
-    for i in range(N):                                           # the kernel's summation order: assets ascending, multiply then add
-        series = (Rc[:, i:i + 1] * W[:, i][None, :]) if i == 0 else series + Rc[:, i:i + 1] * W[:, i][None, :]
+    series = sweep_ref.series(Rc, W)                             # the kernel's summation order: assets ascending, multiply then add
     want = np.percentile(series, (1 - 0.95) * 100, axis=0)
     assert np.array_equal(s["var_95"], want)
     for p in range(0, P, max(1, P // 40)):
