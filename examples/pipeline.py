@@ -90,6 +90,14 @@ def main(paths, resample_rule="M", user_rf=3.0, investment=10000.0, seed=12345, 
     for h, b in zip(gfan["steps"], gfan["bands"]):
         lo, mid, hi = investment * (1.0 + b)
         print(f"  GARCH fan after {h} period(s): 2.5 % {lo:,.2f}  median {mid:,.2f}  97.5 % {hi:,.2f}")
+    # the observed rows themselves at today's volatility (SPEC.md 2.4 / 4.11, filtered historical simulation): the rows divided by
+    # the fitted variance path, resampled, and every draw scaled by the variance ratio the path carries from the same h0
+    frows = mcp.filter_rows(returns_df, gfit[:2])
+    ffan = mcp.simulate_filtered(frows, w, n_steps=6, n_paths=n_paths, seed=seed, v0=investment, horizons=[1, 3, 6],
+                                 levels=(2.5, 50.0, 97.5))["horizons"]
+    for h, b in zip(ffan["steps"], ffan["bands"]):
+        lo, mid, hi = investment * (1.0 + b)
+        print(f"  filtered-rows fan after {h} period(s): 2.5 % {lo:,.2f}  median {mid:,.2f}  97.5 % {hi:,.2f}")
     # a withdrawal plan on the same weights (SPEC.md 4.7 / 5.6): 1.5 % of the capital taken out after every period for 6 years;
     # a path whose value is used up is ruined and stays so -- the share of ruined paths per horizon is the survival curve
     T, take = 6 * af, 0.015 * investment

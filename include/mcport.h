@@ -31,12 +31,13 @@ extern "C" {
                                     + mcp_simulate_overlay, mcp_overlay_pivots (additive, detected by symbol);
                                     + mcp_simulate_garch (additive, detected by symbol);
                                     + mcp_simulate_attribution (additive, detected by symbol);
-                                    + mcp_simulate_antithetic (additive, detected by symbol) */
+                                    + mcp_simulate_antithetic (additive, detected by symbol);
+                                    + mcp_simulate_filtered, mcp_filtered_pivots (additive, detected by symbol) */
 #define MCP_MAX_ASSETS 64        /* thread-per-path kernels are instantiated for N4 = 4..64 */
 #define MCP_SELECT_BINS 2048     /* radix-select digit: 11 + 11 + 10 bits */
 #define MCP_MAX_HORIZONS 64      /* mcp_simulate_horizons: horizon steps per call */
 #define MCP_MAX_LEVELS 16        /* mcp_simulate_horizons: band levels per call */
-#define MCP_MAX_BOOT_ROWS (1 << 20) /* mcp_simulate_bootstrap: observed return rows per call */
+#define MCP_MAX_BOOT_ROWS (1 << 20) /* mcp_simulate_bootstrap, mcp_simulate_filtered: observed return rows per call */
 #define MCP_MAX_OVERLAY_ROWS 8   /* mcp_simulate_overlay: option rows per asset */
 #define MCP_MAX_T_DOF 32         /* mcp_simulate_student_t: degrees of freedom in [3, MCP_MAX_T_DOF] */
 #define MCP_MAX_ATTR_PORTFOLIOS 16 /* mcp_simulate_attribution: portfolios per call */
@@ -321,6 +322,41 @@ int mcp_simulate_garch(mcp_ctx *ctx, const mcp_params *prm, const mcp_garch *g,
                        float *horizon_out,         /* NULL or host [H*K*n_paths], row h*K + k */
                        mcp_stats *hz_stats_out,    /* [H*K], NULL iff n_horizons == 0 */
                        double *bands_out);         /* [H*K*L], NULL iff n_levels == 0 */
+
+/* Filtered historical simulation (Barone-Adesi, Giannopoulos & Vosper 1999; SPEC.md 2.4 / 4.11 / 5.11): the bootstrap on rows that
+ * were de-volatilised with a fitted GARCH(1,1) variance path, every draw re-scaled by the path's own simulated variance ratio.
+ * mu: [N] the level the residuals are added to; resid: [n_rows * N] row-major residual rows E; shock: [n_rows] the rows' shocks
+ * s_j >= 0 (the row's Mahalanobis shock over its fitted variance ratio); all binary32 and finite, 1 <= n_rows <= MCP_MAX_BOOT_ROWS.
+ * mean_block: the mean block length b in [1, +inf] of mcp_bootstrap (b = 1: classical FHS).  reserved must be 0. */
+typedef struct {
+    const float *mu, *resid, *shock;
+    int32_t n_rows;
+    int32_t reserved;
+    double mean_block;
+} mcp_filtered;
+
+/* mcp_simulate_bootstrap[_horizons] on filtered rows (SPEC.md 4.11; simple compounding only): step t of path p draws the row j_t
+ * of SPEC.md 2.1, r_i = fma(sqrt(h), E[j_t, i], mu_i), rho_k = w_k . r, V = fma(V, rho_k, V), and then
+ * h = min(fma(b, h, fma(a, fl32(h s[j_t]), omega)), 2^40) from h = g, with (a, b, g, omega) of the mcp_garch triple as in SPEC.md 4.9.
+ * alpha = 0 and h0 = 1 is mcp_simulate_bootstrap on the rows fl32(E + mu) bit for bit.  n_horizons = 0: no horizons (horizons ignored,
+ * n_levels = 0, horizon_out, hz_stats_out and bands_out NULL); otherwise the horizons, records and bands of mcp_simulate_horizons.
+ * The moments are pivoted at SPEC.md 5.11.  Argument errors (MCP_E_ARG: a NULL struct or member, n_rows out of range, reserved != 0,
+ * mean_block < 1 or NaN, a non-finite entry, a negative shock -- the message names the array and the first offending index -- and the
+ * rules of g) are found before any device is touched; log compounding, MCP_FLAG_FOLD, MCP_FLAG_NATIVE_MATH: MCP_E_UNSUPPORTED.
+ * Costs: the rows and shocks are uploaded once per device and call (4 N4 + 4 B per row); they are read from LDS when
+ * n_rows * ceil(N/4) + ceil(n_rows/4) <= 1088 (N = 16: 256 rows), else from global memory; one square root and N4 + 3 fused
+ * multiply-adds or multiplies per path-step on top of the bootstrap; K >= 17 runs as passes of 8 portfolios. */
+int mcp_simulate_filtered(mcp_ctx *ctx, const mcp_params *prm, const mcp_filtered *filt, const mcp_garch *g, const float *W,
+                          uint64_t seed, uint64_t path_begin, uint64_t n_paths,
+                          int n_horizons, const int32_t *horizons, int n_levels, const double *levels,
+                          float *terminal_out,        /* NULL or host [K*n_paths] */
+                          mcp_stats *stats_out,       /* [K] */
+                          float *horizon_out,         /* NULL or host [H*K*n_paths], row h*K + k */
+                          mcp_stats *hz_stats_out,    /* [H*K], NULL iff n_horizons == 0 */
+                          double *bands_out);         /* [H*K*L], NULL iff n_levels == 0 */
+/* The shift of the moments of filtered paths at prm->n_steps (SPEC.md 5.11; host side, binary64): with e_i the mean of column i of
+ * resid (rows ascending), m_k = sum_i W[k,i] (mu_i + e_i): c_k = expm1(T log1p(m_k)), 0 if m_k <= -1 or where it is not finite. */
+int mcp_filtered_pivots(const mcp_params *prm, const mcp_filtered *filt, const float *W, double *pivots_out /* [K] */);
 
 /* Antithetic pairs (SPEC.md 2.3 / 5.10): the pair statistics of one portfolio on the terminal x.  cross = sum_j (x_2j - c)(x_2j+1 - c)
  * with c the pivot of mcp_pivots; with C = cross - S1^2 / (2 n), S1 = (mean - c) n: pair_cov = C / (n_pairs - 1), pair_corr = 2 C / m2

@@ -73,6 +73,12 @@ class McpStudentT(ctypes.Structure):
     _fields_ = [("dof", ctypes.c_int32), ("reserved", ctypes.c_int32)]
 
 
+class McpFiltered(ctypes.Structure):
+    """mcp_filtered: the filtered residual rows of a filtered-historical-simulation call (SPEC.md 2.4)."""
+    _fields_ = [("mu", ctypes.c_void_p), ("resid", ctypes.c_void_p), ("shock", ctypes.c_void_p), ("n_rows", ctypes.c_int32),
+                ("reserved", ctypes.c_int32), ("mean_block", ctypes.c_double)]
+
+
 class McpGarch(ctypes.Structure):
     """mcp_garch: alpha, beta and the starting variance ratio h0 of the GARCH(1,1) recurrence of SPEC.md 4.9."""
     _fields_ = [("alpha", ctypes.c_double), ("beta", ctypes.c_double), ("h0", ctypes.c_double), ("reserved", ctypes.c_uint64)]
@@ -163,6 +169,9 @@ SIGNATURES = {
                                       _vp, _vp, _vp, _vp, _vp, _vp]),
     "mcp_simulate_garch": (_int, [_vp, _PP, ctypes.POINTER(McpGarch), ctypes.POINTER(McpStudentT), _vp, _vp, _vp, _u64, _u64, _u64, _int,
                                   _vp, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "mcp_simulate_filtered": (_int, [_vp, _PP, ctypes.POINTER(McpFiltered), ctypes.POINTER(McpGarch), _vp, _u64, _u64, _u64, _int, _vp,
+                                     _int, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "mcp_filtered_pivots": (_int, [_PP, ctypes.POINTER(McpFiltered), _f32p, _f64p]),
     "mcp_simulate_attribution": (_int, [_vp, _PP, ctypes.POINTER(McpGarch), ctypes.POINTER(McpStudentT), _vp, _vp, _vp, _u64, _u64, _u64,
                                         _vp, _vp, _vp, _vp, _vp]),
     "mcp_simulate_antithetic": (_int, [_vp, _PP, ctypes.POINTER(McpGarch), ctypes.POINTER(McpStudentT), _vp, _vp, _vp, _u64, _u64, _u64,
@@ -300,6 +309,26 @@ def make_bootstrap(rows: np.ndarray, block: float) -> McpBootstrap:
     if rows.dtype != np.float32 or rows.ndim != 2 or not rows.flags.c_contiguous:
         raise ValueError("bootstrap rows must be a C-contiguous float32 [R, N] array")
     return McpBootstrap(rows.ctypes.data_as(ctypes.c_void_p), int(rows.shape[0]), 0, float(block))
+
+
+def make_filtered(mu: np.ndarray, resid: np.ndarray, shock: np.ndarray, block: float) -> McpFiltered:
+    """mcp_filtered over C-contiguous binary32 arrays mu [N], resid [R, N], shock [R] (the caller keeps them alive for the call)."""
+    for a, nd in ((mu, 1), (resid, 2), (shock, 1)):
+        if a.dtype != np.float32 or a.ndim != nd or not a.flags.c_contiguous:
+            raise ValueError("filtered mu [N], resid [R, N] and shock [R] must be C-contiguous float32 arrays")
+    if resid.shape != (shock.shape[0], mu.shape[0]):
+        raise ValueError(f"filtered resid has shape {resid.shape}, mu and shock want {(shock.shape[0], mu.shape[0])}")
+    return McpFiltered(mu.ctypes.data_as(ctypes.c_void_p), resid.ctypes.data_as(ctypes.c_void_p), shock.ctypes.data_as(ctypes.c_void_p),
+                       int(resid.shape[0]), 0, float(block))
+
+
+def filtered_pivots(prm: McpParams, mu: np.ndarray, resid: np.ndarray, shock: np.ndarray, W: np.ndarray) -> np.ndarray:
+    """[K] shifts of the moments of filtered paths (SPEC.md 5.11; include/mcport.h, mcp_filtered_pivots), pure host arithmetic."""
+    out = np.zeros(W.shape[0], np.float64)
+    mu, resid, shock = (np.ascontiguousarray(a, np.float32) for a in (mu, resid, shock))
+    ft = make_filtered(mu, resid, shock, 1.0)
+    check(lib().mcp_filtered_pivots(ctypes.byref(prm), ctypes.byref(ft), W, out))
+    return out
 
 
 def bootstrap_pivots(prm: McpParams, rows: np.ndarray, W: np.ndarray, block: float = 1.0) -> np.ndarray:

@@ -228,6 +228,48 @@ int check_garch(const mcp_params* prm, const mcp_garch* g) {
   return MCP_OK;
 }
 
+// SPEC.md 2.4: the filtered rows -- mu [N], resid [R][N] and shock [R] finite binary32 values, every shock >= 0, 1..MCP_MAX_BOOT_ROWS
+// rows, 1 <= b <= +inf, reserved == 0
+int check_filtered(const mcp_params* prm, const mcp_filtered* f) {
+  if (!f) return fail(MCP_E_ARG, "filtered is NULL");
+  if (!f->mu) return fail(MCP_E_ARG, "filtered mu is NULL");
+  if (!f->resid) return fail(MCP_E_ARG, "filtered resid is NULL");
+  if (!f->shock) return fail(MCP_E_ARG, "filtered shock is NULL");
+  if (f->n_rows < 1 || f->n_rows > MCP_MAX_BOOT_ROWS) return fail(MCP_E_ARG, "filtered n_rows=%d outside [1,%d]", f->n_rows, MCP_MAX_BOOT_ROWS);
+  if (f->reserved != 0) return fail(MCP_E_ARG, "filtered reserved=%d must be 0", f->reserved);
+  if (!(f->mean_block >= 1.0)) return fail(MCP_E_ARG, "filtered mean_block=%g must be >= 1 (or +inf)", f->mean_block);
+  const size_t N = (size_t)prm->n_assets, R = (size_t)f->n_rows;
+  for (size_t i = 0; i < N; i++)
+    if (!std::isfinite(f->mu[i])) return fail(MCP_E_ARG, "filtered mu, asset %zu is not finite", i);
+  for (size_t i = 0; i < R * N; i++)
+    if (!std::isfinite(f->resid[i])) return fail(MCP_E_ARG, "filtered resid row %zu, asset %zu is not finite", i / N, i % N);
+  for (size_t j = 0; j < R; j++) {
+    if (!std::isfinite(f->shock[j])) return fail(MCP_E_ARG, "filtered shock, row %zu is not finite", j);
+    if (!(f->shock[j] >= 0.0f)) return fail(MCP_E_ARG, "filtered shock, row %zu = %g is negative", j, (double)f->shock[j]);
+  }
+  return MCP_OK;
+}
+
+// SPEC.md 5.11: mu_i + e_i of the pivot of filtered paths, binary64 -- e_i the mean of column i of the residual rows, j ascending
+void filt_means(int N, const mcp_filtered* f, double* out) {
+  for (int i = 0; i < N; i++) {
+    double sum = 0.0;
+    for (int j = 0; j < f->n_rows; j++) sum += (double)f->resid[(size_t)j * N + i];
+    out[i] = (double)f->mu[i] + sum / (double)f->n_rows;
+  }
+}
+
+// SPEC.md 5.11: m_k = sum_i W[k,i] (mu_i + e_i) (i ascending), c_k = expm1(T log1p(m_k)), 0 if m_k <= -1 or not finite
+void filt_pivots(int N, int K, int T, const double* me, const float* W, double* out) {
+  for (int k = 0; k < K; k++) {
+    const float* w = W + (size_t)k * N;
+    double m = 0.0;
+    for (int i = 0; i < N; i++) m += (double)w[i] * me[i];
+    const double c = m > -1.0 ? std::expm1((double)T * std::log1p(m)) : 0.0;
+    out[k] = std::isfinite(c) ? c : 0.0;
+  }
+}
+
 // SPEC.md 4.7: n_flows == n_steps finite flows, has_target 0 / 1 with a finite target, fl32(v0) > 0
 int check_cashflow(const mcp_params* prm, const mcp_cashflow* cf) {
   if (!cf) return fail(MCP_E_ARG, "cashflow is NULL");
@@ -329,8 +371,9 @@ void overlay_pack(int N, const mcp_overlay* ov, char* out) {
   for (int i = 0; i < n4; i++) sp[i] = i < N ? ov->spot[i] : 1.0f;
 }
 
-// The draws of a walk (SPEC.md 2): Gaussian steps mu + L z, rows of the bootstrap, or Student-t steps mu + L s z.
-enum Source { SRC_GAUSS, SRC_BOOT, SRC_T };
+// The draws of a walk (SPEC.md 2): Gaussian steps mu + L z, rows of the bootstrap, Student-t steps mu + L s z, or filtered residual
+// rows scaled by the path's GARCH variance ratio (SPEC.md 2.4).
+enum Source { SRC_GAUSS, SRC_BOOT, SRC_T, SRC_FHS };
 
 // What one call asks of the walk: the draw source, optionally a rebalancing rule, the drawdown or horizons, and the host arrays
 // of an mcp_simulate* call (an mcp_launch_paths* call gives its device arrays in a Launch instead).
@@ -340,6 +383,7 @@ struct Request {
   const float* chol = nullptr;
   const mcp_bootstrap* boot = nullptr;  // SRC_BOOT (SPEC.md 2.1)
   const mcp_student_t* st = nullptr;    // SRC_T (SPEC.md 2.2)
+  const mcp_filtered* filt = nullptr;   // SRC_FHS (SPEC.md 2.4): the rows, with the triple of SPEC.md 4.9 in `gv` (`garch` stays false)
   bool rebalanced = false;              // SPEC.md 4.5: the rule `reb`
   const mcp_rebalance* reb = nullptr;
   bool cash = false;                    // SPEC.md 4.7: the schedule `cf`
@@ -371,6 +415,12 @@ struct Request {
   mcp_pair* pair_out = nullptr;         // [K]
   double* cross_out = nullptr;          // [K] the call's cross sums: every tile adds its shards' in shard order
 };
+
+// The row table of a request that walks rows: the bootstrap's own, or the residual rows of SRC_FHS.
+mcp_bootstrap rows_of(const Request& rq) {
+  if (rq.src == SRC_FHS) return mcp_bootstrap{rq.filt->resid, rq.filt->n_rows, 0, rq.filt->mean_block};
+  return *rq.boot;
+}
 
 Request host_request(Source src, const float* mu, const float* chol, const float* W, float* terminal_out, mcp_stats* stats_out) {
   Request rq;
@@ -441,6 +491,17 @@ int check_request(const mcp_params* prm, const Request& rq, uint64_t n_paths, co
   if (rq.overlay && (rc = check_overlay(prm, rq.ov))) return rc;
   if (rq.garch && (rc = check_garch(prm, rq.gv))) return rc;
   const bool logc = prm->compounding != MCP_COMPOUND_SIMPLE;
+  if (rq.src == SRC_FHS) {                                     // SPEC.md 2.4 / 4.11: the rows, the triple, then what it is not combined with
+    if ((rc = check_filtered(prm, rq.filt))) return rc;
+    if ((rc = check_garch(prm, rq.gv))) return rc;
+    if (logc) return fail(MCP_E_UNSUPPORTED, "filtered paths compound simply (no log compounding)");
+    if (prm->flags & (MCP_FLAG_FOLD | MCP_FLAG_NATIVE_MATH))
+      return fail(MCP_E_UNSUPPORTED, "filtered paths draw no normals (no MCP_FLAG_FOLD / MCP_FLAG_NATIVE_MATH)");
+    if (rq.st || rq.garch || rq.rebalanced || rq.cash || rq.overlay || rq.dd || rq.attr || rq.anti)
+      return fail(MCP_E_UNSUPPORTED, "filtered rows are not combined with Student-t draws, rebalancing, cash flows, the overlay, the drawdown, "
+                                     "the attribution or antithetic pairs");
+    if (ln) return fail(MCP_E_UNSUPPORTED, "filtered rows are not wired into mcp_launch_paths*");
+  }
   if (rq.garch && logc)
     return fail(MCP_E_UNSUPPORTED, "GARCH paths compound simply (log compounding: expm1(S) has no finite mean under GARCH tails)");
   if (rq.garch && (rq.src == SRC_BOOT || rq.rebalanced || rq.cash || rq.overlay))
@@ -495,7 +556,7 @@ int check_request(const mcp_params* prm, const Request& rq, uint64_t n_paths, co
   if (rq.src == SRC_T && rq.rebalanced) return fail(MCP_E_UNSUPPORTED, "Student-t draws are not combined with rebalancing");
   if (rq.cash && (rq.dd || rq.rebalanced))
     return fail(MCP_E_UNSUPPORTED, "cash flows are not combined with the drawdown or with rebalancing");
-  if (rq.src != SRC_BOOT && (uint64_t)prm->n_steps * (uint64_t)((prm->n_assets + 3) / 4) > 0xFFFFFFFFull)
+  if (rq.src != SRC_BOOT && rq.src != SRC_FHS && (uint64_t)prm->n_steps * (uint64_t)((prm->n_assets + 3) / 4) > 0xFFFFFFFFull)
     return fail(MCP_E_UNSUPPORTED, "n_steps * ceil(N/4) exceeds the 32-bit Philox block counter");
   if (!rq.dd && rq.mdd_out) return fail(MCP_E_ARG, "mdd_out needs dd_stats_out");
   if (!rq.hz) {
@@ -508,7 +569,7 @@ int check_request(const mcp_params* prm, const Request& rq, uint64_t n_paths, co
     if ((rq.bands_out == nullptr) != (rq.L == 0)) return fail(MCP_E_ARG, "bands_out must be NULL exactly when n_levels == 0");
   }
   if (!ln) {
-    if ((rq.src != SRC_BOOT && (!rq.mu || !rq.chol)) || !rq.W || !rq.stats_out || (rq.dd && !rq.dd_stats_out))
+    if ((rq.src != SRC_BOOT && rq.src != SRC_FHS && (!rq.mu || !rq.chol)) || !rq.W || !rq.stats_out || (rq.dd && !rq.dd_stats_out))
       return fail(MCP_E_ARG, "NULL pointer");
     if (n_paths < 1) return fail(MCP_E_ARG, "n_paths must be >= 1");
     return MCP_OK;
@@ -936,12 +997,23 @@ static void fill_hz(mcp::PathArgsHZ& x, const Request& rq, const Launch& ln) {
 }
 static mcp::BootArgs boot_block(const Request& rq, const Launch& ln) {
   mcp::BootArgs bt;
-  const bool on = rq.src == SRC_BOOT;
+  const bool on = rq.src == SRC_BOOT || rq.src == SRC_FHS;
   bt.rows = on ? (const float4*)ln.d_rows : nullptr;
-  bt.thr = on ? boot_threshold(rq.boot->mean_block) : 0;
-  bt.n_rows = on ? (uint32_t)rq.boot->n_rows : 0;
+  bt.thr = on ? boot_threshold(rows_of(rq).mean_block) : 0;
+  bt.n_rows = on ? (uint32_t)rows_of(rq).n_rows : 0;
   bt.pad = 0;
   return bt;
+}
+// SPEC.md 4.11: the shocks sit behind the [R][N4] rows of the launch's row buffer; a itself, not a_N
+static mcp::FiltArgs filt_block(const Request& rq, const Launch& ln, int n_assets) {
+  const GarchConsts c = garch_consts(rq.gv, n_assets);
+  mcp::FiltArgs fh;
+  fh.shock = ln.d_rows + (size_t)rq.filt->n_rows * (size_t)n4_of(n_assets);
+  fh.a = c.a;
+  fh.b = c.b;
+  fh.omega = c.omega;
+  fh.h0 = c.g;
+  return fh;
 }
 static mcp::StudentArgs student_block(const Request& rq) {
   mcp::StudentArgs st;
@@ -1059,10 +1131,12 @@ static int launch_paths_impl(const mcp_params* prm, const Request& rq, const Lau
   if (rq.cash) s.cf.flows = ln.d_flows;
   if (rq.overlay) s.ov = overlay_block(rq, ln, N);
   if (rq.rebalanced) { s.period = rq.reb->period; s.cost = (float)rq.reb->cost; }
+  if (rq.src == SRC_FHS) s.fh = filt_block(rq, ln, N);
   mcp::PathKernel k = {};
   k.logc = prm->compounding == MCP_COMPOUND_LOG;
-  k.boot = rq.src == SRC_BOOT;
-  k.blds = k.boot && mcp::boot_fits_lds((uint64_t)rq.boot->n_rows, nb);
+  k.fh = rq.src == SRC_FHS;
+  k.boot = rq.src == SRC_BOOT || k.fh;
+  k.blds = k.fh ? mcp::filt_fits_lds((uint64_t)rq.filt->n_rows, nb) : k.boot && mcp::boot_fits_lds((uint64_t)rq.boot->n_rows, nb);
   k.stt = rq.src == SRC_T;
   if (ln.attr) {
     // SPEC.md 4.10: one portfolio per pass, no terminal store, its own epilogue.  The walk draws as the GARCH kernel does: without
@@ -1579,6 +1653,10 @@ int tile_pivots(const mcp_params& tp, const Request& rq, int T, const float* W, 
     for (int k = 0; k < tp.n_portfolios; k++) out[k] = boot_pivot(tp.compounding, T, bm[k], bs2[k]);
     return MCP_OK;
   }
+  if (rq.src == SRC_FHS) {                                   // SPEC.md 5.11: rmu holds mu_i + e_i
+    filt_pivots(tp.n_assets, tp.n_portfolios, T, rmu, W, out);
+    return MCP_OK;
+  }
   mcp_params p = tp;
   p.n_steps = T;
   return mcp_pivots(&p, rq.mu, rq.chol, W, out);
@@ -1633,12 +1711,14 @@ int run_tile(mcp_ctx* c, const mcp_params* prm, const Request& rq, uint64_t seed
   const double* shared_hz_pivot = nullptr;
   // bootstrap: no drift and no Cholesky factor in the packed block (only W is read), the pivots of SPEC.md 5.3 from the row
   // moments (computed once per tile); rebalancing: the per-asset means of the draws (SPEC.md 5.4), once per tile
-  const bool boot = rq.src == SRC_BOOT;
-  const std::vector<float> zmu(boot ? N : 0, 0.0f), zchol(boot ? (size_t)N * N : 0, 0.0f);
-  const float* mu = boot ? zmu.data() : rq.mu;
-  const float* chol = boot ? zchol.data() : rq.chol;
-  std::vector<double> bm, bs2, rmu(rq.rebalanced ? N : 0), cm;
+  // filtered rows (SPEC.md 4.11): their drift in the packed block, the Cholesky factor zero
+  const bool boot = rq.src == SRC_BOOT, fhs = rq.src == SRC_FHS;
+  const std::vector<float> zmu(boot ? N : 0, 0.0f), zchol(boot || fhs ? (size_t)N * N : 0, 0.0f);
+  const float* mu = boot ? zmu.data() : fhs ? rq.filt->mu : rq.mu;
+  const float* chol = boot || fhs ? zchol.data() : rq.chol;
+  std::vector<double> bm, bs2, rmu(rq.rebalanced || fhs ? N : 0), cm;
   if (rq.rebalanced) reb_means(N, rq.mu, boot ? rq.boot : nullptr, rmu.data());
+  if (fhs) filt_means(N, rq.filt, rmu.data());
   const bool ov_walk = rq.overlay && rq.ov->n_rows > 0;    // no rows: the pivots of the plain call (SPEC.md 5.7)
   for (size_t s = 0; s < S; s++) {
     const Job& j = jobs[s];
@@ -1892,15 +1972,18 @@ int simulate_impl(mcp_ctx* c, const mcp_params* prm, const Request& rq, uint64_t
   int rc = MCP_OK;
   std::vector<Job> jobs(S);
   const bool by_portfolio = S > 1 && (prm->flags & MCP_FLAG_SHARD_PORTFOLIOS);
-  if (rq.src == SRC_BOOT) {
+  if (rq.src == SRC_BOOT || rq.src == SRC_FHS) {
     // SPEC.md 2.1: the rows, zero-padded to N4, into one pinned staging copy and from there once into the boot buffer of every
-    // shard that walks paths in this call (the tiles of the call share it)
+    // shard that walks paths in this call (the tiles of the call share it).  SPEC.md 2.4: the shocks of filtered rows behind them,
+    // zero-padded to a multiple of 4
     const int N = prm->n_assets, n4 = n4_of(N);
-    const size_t R = rq.boot->n_rows, bytes = R * (size_t)n4 * sizeof(float);
+    const mcp_bootstrap tab = rows_of(rq);
+    const size_t R = tab.n_rows, n_shock = rq.src == SRC_FHS ? (R + 3) / 4 * 4 : 0, bytes = (R * (size_t)n4 + n_shock) * sizeof(float);
     rc = grow_host((void**)&c->h_boot, &c->h_boot_cap, bytes);
     if (rc == MCP_OK) {
       memset(c->h_boot, 0, bytes);
-      for (size_t j = 0; j < R; j++) memcpy(c->h_boot + j * n4, rq.boot->rows + j * N, (size_t)N * sizeof(float));
+      for (size_t j = 0; j < R; j++) memcpy(c->h_boot + j * n4, tab.rows + j * N, (size_t)N * sizeof(float));
+      if (n_shock) memcpy(c->h_boot + R * n4, rq.filt->shock, R * sizeof(float));
     }
     for (size_t s = 0; s < S && rc == MCP_OK; s++) {
       const bool works = by_portfolio ? (int64_t)K * (int64_t)(s + 1) / (int64_t)S > (int64_t)K * (int64_t)s / (int64_t)S
@@ -1908,7 +1991,7 @@ int simulate_impl(mcp_ctx* c, const mcp_params* prm, const Request& rq, uint64_t
       if (!works) continue;
       Shard& sh = c->sh[s];
       if (hipSetDevice(sh.device) != hipSuccess) { rc = fail(MCP_E_HIP, "hipSetDevice(%d)", sh.device); break; }
-      if ((rc = grow(sh.boot, R * (size_t)n4))) break;
+      if ((rc = grow(sh.boot, R * (size_t)n4 + n_shock))) break;
       const hipError_t e = hipMemcpyAsync(sh.boot.p, c->h_boot, bytes, hipMemcpyHostToDevice, sh.stream);
       if (e != hipSuccess) rc = fail(MCP_E_HIP, "bootstrap rows upload: %s", hipGetErrorString(e));
     }
@@ -2087,6 +2170,28 @@ int mcp_simulate_garch(mcp_ctx* c, const mcp_params* prm, const mcp_garch* g, co
   rq.dd_stats_out = dd_stats_out;
   ask_horizons(rq, n_horizons != 0, n_horizons, horizons, n_levels, levels, horizon_out, hz_stats_out, bands_out);
   return simulate_checked(c, prm, rq, seed, path_begin, n_paths);
+}
+
+int mcp_simulate_filtered(mcp_ctx* c, const mcp_params* prm, const mcp_filtered* filt, const mcp_garch* g, const float* W, uint64_t seed,
+                          uint64_t path_begin, uint64_t n_paths, int n_horizons, const int32_t* horizons, int n_levels,
+                          const double* levels, float* terminal_out, mcp_stats* stats_out, float* horizon_out, mcp_stats* hz_stats_out,
+                          double* bands_out) {
+  Request rq = host_request(SRC_FHS, nullptr, nullptr, W, terminal_out, stats_out);
+  rq.filt = filt;
+  rq.gv = g;
+  ask_horizons(rq, n_horizons != 0, n_horizons, horizons, n_levels, levels, horizon_out, hz_stats_out, bands_out);
+  return simulate_checked(c, prm, rq, seed, path_begin, n_paths);
+}
+
+int mcp_filtered_pivots(const mcp_params* prm, const mcp_filtered* filt, const float* W, double* out) {
+  if (int rc = check_params(prm)) return rc;
+  if (int rc = check_filtered(prm, filt)) return rc;
+  if (!W || !out) return fail(MCP_E_ARG, "NULL pointer");
+  if (prm->compounding != MCP_COMPOUND_SIMPLE) return fail(MCP_E_UNSUPPORTED, "filtered paths compound simply (no log compounding)");
+  std::vector<double> me((size_t)prm->n_assets);
+  filt_means(prm->n_assets, filt, me.data());
+  filt_pivots(prm->n_assets, prm->n_portfolios, prm->n_steps, me.data(), W, out);
+  return MCP_OK;
 }
 
 // SPEC.md 5.10: the pair record of one portfolio from the call's statistics, its pivot c and cross = sum (x_2j - c)(x_2j+1 - c)

@@ -95,6 +95,7 @@ __device__ __forceinline__ const __attribute__((address_space(4))) A* kernarg() 
   template <class A> struct has_##m<A, std::void_t<decltype(A::m)>> : std::true_type {};
 MCP_HAS_MEMBER(hz) MCP_HAS_MEMBER(mdd) MCP_HAS_MEMBER(bt) MCP_HAS_MEMBER(st) MCP_HAS_MEMBER(gv) MCP_HAS_MEMBER(cf)
 MCP_HAS_MEMBER(ov) MCP_HAS_MEMBER(at) MCP_HAS_MEMBER(period) MCP_HAS_MEMBER(pr)
+MCP_HAS_MEMBER(fh)
 #undef MCP_HAS_MEMBER
 
 struct PathArgs {
@@ -187,6 +188,26 @@ typedef const __attribute__((address_space(4))) GarchArgs* cgarch_p;
 template <class A>
 __device__ __forceinline__ cgarch_p garch_args(const A&) {
   if constexpr (has_gv<A>::value) return &kernarg<A>()->gv;
+  else return nullptr;
+}
+
+// Filtered historical simulation (SPEC.md 2.4 / 4.11): the rows of BootArgs are the filtered residuals E, `shock` holds the rows'
+// shocks s_j ([R] floats behind the rows, padded to a multiple of 4), and a, b, omega, h0 are the binary32 constants of SPEC.md 4.9
+// -- a itself, not a_N: the shock is already per asset.
+struct FiltArgs {
+  const float* __restrict__ shock;    // [4 ceil(R/4)] device copy
+  float a, b, omega, h0;
+};
+// Arguments of mc_paths_fhs_kernel: the horizons of PathArgsHZ (n_horizons = 0: none), the residual rows and the filter block.
+struct PathArgsFH : PathArgsHZ {
+  BootArgs bt;
+  FiltArgs fh;
+};
+// The filter block of an fhs kernel's launch, read where it is used (kernarg).
+typedef const __attribute__((address_space(4))) FiltArgs* cfilt_p;
+template <class A>
+__device__ __forceinline__ cfilt_p filt_args(const A&) {
+  if constexpr (has_fh<A>::value) return &kernarg<A>()->fh;
   else return nullptr;
 }
 
@@ -317,6 +338,7 @@ struct PathLaunchArgs {
   int32_t period;                     // the rebalancing rule of PathArgsRB
   float cost;
   PairArgs pr;
+  FiltArgs fh;
 };
 template <class A>
 inline A make_args(const PathLaunchArgs& s) {
@@ -332,12 +354,17 @@ inline A make_args(const PathLaunchArgs& s) {
   if constexpr (has_at<A>::value) x.at = s.at;
   if constexpr (has_period<A>::value) { x.period = s.period; x.cost = s.cost; }
   if constexpr (has_pr<A>::value) x.pr = s.pr;
+  if constexpr (has_fh<A>::value) x.fh = s.fh;
   return x;
 }
 
 // The LDS copy of the row table takes the slot of the inverse-CDF table (ICDF_LDS_ENTRIES float4: the bootstrap needs neither
 // that table nor the drift copy in its padding): R rows of NB float4 fit when R * NB <= ICDF_LDS_ENTRIES (N = 16: 272 rows).
 __host__ __device__ constexpr bool boot_fits_lds(uint64_t n_rows, int nb) { return n_rows * (uint64_t)nb <= (uint64_t)ICDF_LDS_ENTRIES; }
+// The filtered rows carry their shock table behind them in the same slot, ceil(R/4) float4 more (N = 16: 256 rows).
+__host__ __device__ constexpr bool filt_fits_lds(uint64_t n_rows, int nb) {
+  return n_rows * (uint64_t)nb + (n_rows + 3) / 4 <= (uint64_t)ICDF_LDS_ENTRIES;
+}
 // LDS banking of the gather (ds_read_b128: 16 slots of 16 B, bank slot = float4 index mod 16).  Row j starts at slot
 // (j NB) mod 16, a multiple of G = the largest power of two dividing NB, so a fixed chunk q of random rows would fall on only
 // 16 / G slots.  Chunk q of row j is stored at j NB + (q ^ s(j)), s(j) = (j >> log2(16 / G)) & (G - 1): the bits of j that
@@ -417,7 +444,8 @@ constexpr int PATH_BLOCK = 256;
 // the weight dot (SPEC.md 4.8).  GV: the step's normals are scaled by u = sqrt(h) (STT: times s), h the path's GARCH(1,1) variance
 // ratio, and h is updated from the scaled normals (SPEC.md 4.9); in a GV kernel STT is set and nu = 0 at run time means Gaussian
 // draws.  AT: the step also carries every asset's contribution A_i = fma(V, fl32(w_i r_i), A_i) and the epilogue reduces them
-// (SPEC.md 4.10 / 5.9).  ANTI: a lane walks the two members of an antithetic pair on one set of draws: everything up to the step's
+// (SPEC.md 4.10 / 5.9).  FH (with BOOT): the row is a filtered residual, r_i = fma(sqrt(h), E_ji, mu_i), and h is updated from the
+// row's shock, h = fminf(fma(b, h, fma(a, h s_j, omega)), 2^40) (SPEC.md 2.4 / 4.11).  ANTI: a lane walks the two members of an antithetic pair on one set of draws: everything up to the step's
 // normals z (Philox, the transform, the chi blocks, h) runs once, everything downstream of z -- the row-pair accumulators, rho, V,
 // the peak and drawdown, the stores and the epilogue -- carries a second member that sees -z (SPEC.md 2.3 / 5.10).  Every kernel
 // below is the body in mcp_paths_body.inc under its own flags F: it names the flags it sets, the rest are PathFlagsOff's.  F is a
@@ -425,7 +453,7 @@ constexpr int PATH_BLOCK = 256;
 // defaults' names and read as the same constant expressions.
 struct PathFlagsOff {
   static constexpr bool NATIVE = false, FOLD = false, LOGC = false, DD = false, HZ = false, BOOT = false, BLDS = false, REB = false,
-                        STT = false, CF = false, OV = false, GV = false, AT = false, ANTI = false;
+                        STT = false, CF = false, OV = false, GV = false, AT = false, ANTI = false, FH = false;
 };
 
 // __launch_bounds__ 2nd argument of a path kernel: the MCP_MIN_WAVES* above for N <= 16 and one path per lane, by the kind of
@@ -533,6 +561,15 @@ __global__ void MCP_BOUNDS(BK_PATHS) mc_paths_g_hz_kernel(const PathArgsGHZ a) {
 template <int NB, int KT, int PPT, bool BOOT_, bool BLDS_, bool STT_>
 __global__ void MCP_BOUNDS(BK_CF) mc_paths_cf_kernel(const PathArgsCF a) {
   struct F : PathFlagsOff { enum : bool { HZ = true, CF = true, BOOT = BOOT_, BLDS = BLDS_, STT = STT_ }; };
+#include "mcp_paths_body.inc"
+}
+
+// The filtered-historical-simulation kernel (SPEC.md 2.4 / 4.11; simple compounding): the segmented walk of mc_paths_boot_hz_kernel
+// on the residual rows, every row scaled by sqrt(h) and added to the drift, h updated from the row's shock.  H = 0 is one segment, so
+// one kernel serves terminal-only and horizon calls.  V_T, the horizons and the fused epilogue as in mc_paths_boot_hz_kernel.
+template <int NB, int KT, int PPT, bool BLDS_>
+__global__ void MCP_BOUNDS(BK_PATHS) mc_paths_fhs_kernel(const PathArgsFH a) {
+  struct F : PathFlagsOff { enum : bool { HZ = true, BOOT = true, BLDS = BLDS_, FH = true }; };
 #include "mcp_paths_body.inc"
 }
 

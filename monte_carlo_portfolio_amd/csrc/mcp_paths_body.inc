@@ -4,12 +4,13 @@
 // walk is the one loop it always was.  In scope: the template parameters NB, KT, PPT, the flags F (PathFlagsOff or a struct
 // derived from it) and the kernel argument `a` (PathArgs or a struct that starts with one).
   constexpr bool NATIVE = F::NATIVE, FOLD = F::FOLD, LOGC = F::LOGC, DD = F::DD, HZ = F::HZ, BOOT = F::BOOT, BLDS = F::BLDS, REB = F::REB,
-                 STT = F::STT, CF = F::CF, OV = F::OV, GV = F::GV, AT = F::AT, ANTI = F::ANTI;
+                 STT = F::STT, CF = F::CF, OV = F::OV, GV = F::GV, AT = F::AT, ANTI = F::ANTI, FH = F::FH;
+  static_assert(!FH || (BOOT && HZ && !(LOGC || REB || CF || STT || GV || OV || AT || DD)), "filtered rows: the bootstrap's segmented walk only");
   constexpr int N4 = 4 * NB;
   // ANTI (SPEC.md 2.3): a lane's PPT draws feed EM = 2 PPT members -- slot e < PPT walks on z[e], slot PPT + e on -z[e]; p, live and
   // the counters are per draw (a.path_begin and a.n_paths count pairs), the members 2 p and 2 p + 1 are adjacent in the output rows
   constexpr int EM = ANTI ? 2 * PPT : PPT;
-  static_assert(!ANTI || !(NATIVE || FOLD || BOOT || REB || CF || OV || AT), "antithetic pairs: the lean Gaussian and GARCH walks only");
+  static_assert(!ANTI || !(NATIVE || FOLD || BOOT || REB || CF || OV || AT || FH), "antithetic pairs: the lean Gaussian and GARCH walks only");
   // wave-uniform parameters through the constant address space -> s_load_dword* into SGPRs
   typedef const __attribute__((address_space(4))) float* cfloat_p;
   cfloat_p mu = (cfloat_p)a.packed;
@@ -30,6 +31,12 @@
       const uint32_t j = i / NB, q = i % NB;
       s_tab[j * NB + (q ^ BootSwizzle<NB>::of(j))] = bt.rows[i];
     }
+  }
+  // FH: the rows' shocks (SPEC.md 2.4), [R] floats; BLDS: copied behind the rows, not swizzled (filt_fits_lds)
+  const float* fshock = nullptr;
+  if constexpr (FH) fshock = filt_args(a)->shock;
+  if constexpr (FH && BLDS) {
+    for (uint32_t i = threadIdx.x; i < (bt.n_rows + 3u) / 4u; i += PATH_BLOCK) s_tab[bt.n_rows * (uint32_t)NB + i] = ((const float4*)fshock)[i];
   }
   // The 512 B of padding in front of the table hold the drift (and, for one portfolio, the weights): read from LDS they
   // land in VGPRs without a VALU instruction (a v_mov from an SGPR costs an issue slot, an SGPR operand halves the
@@ -89,7 +96,7 @@
     uint32_t jrow[PPT];                                   // BOOT: the row index j_t of SPEC.md 2.1
     f32x2 Bs[PPT][N4 / 2];                                // REB: the assets' returns since the last rebalance (SPEC.md 4.5)
     float Ps[PPT][N4];                                    // OV: the assets' price levels P_i (SPEC.md 4.8)
-    float gh[PPT];                                        // GV: the variance ratio h of SPEC.md 4.9
+    float gh[PPT];                                        // GV, FH: the variance ratio h of SPEC.md 4.9 / 4.11
     f32x2 At[PPT][N4 / 2];                                // AT: the assets' contributions A_i of SPEC.md 4.10
 #pragma unroll
     for (int e = 0; e < PPT; e++) {
@@ -101,6 +108,7 @@
       for (int k = 0; k < KT; k++) V[e][k] = logc ? 0.0f : a.v0;
       if constexpr (BOOT) jrow[e] = 0u;                   // replaced at t = 0 (a restart)
       if constexpr (GV) gh[e] = garch_args(a)->h0;        // one scalar load per tile
+      if constexpr (FH) gh[e] = filt_args(a)->h0;
       if constexpr (REB) {
 #pragma unroll
         for (int m = 0; m < N4 / 2; m++) Bs[e][m] = f32x2{0.0f, 0.0f};

@@ -48,7 +48,13 @@ static hipError_t ladder(const PathKernel& k, const PathLaunchArgs& s, hipStream
   const bool lg = k.logc;
   const bool gauss = !k.boot && !k.stt && !k.gv;                               // Gaussian draws
   const bool t = k.stt && !k.gv && !k.boot, g = k.gv && !k.boot;                // Student-t draws; GARCH (nu = 0: Gaussian draws)
-  const bool bl = k.boot && k.blds && !k.stt && !k.gv, bg = k.boot && !k.blds && !k.stt && !k.gv;   // rows from LDS / global memory
+  const bool bl = k.boot && k.blds && !k.stt && !k.gv && !k.fh, bg = k.boot && !k.blds && !k.stt && !k.gv && !k.fh;   // rows from LDS / global memory
+  if (k.fh) {                                             // SPEC.md 4.11: filtered rows, with or without horizons (H = 0: one segment)
+    const bool ok = (k.family == FAM_PLAIN || k.family == FAM_HZ) && k.boot && !k.stt && !k.gv && !k.native && !k.anti && !lg;
+    MCP_ROW(ok && k.blds, mc_paths_fhs_kernel<NB, KT, 1, true>);
+    MCP_ROW(ok && !k.blds, mc_paths_fhs_kernel<NB, KT, 1, false>);
+    return hipErrorInvalidValue;
+  }
   if (k.anti) {                                           // SPEC.md 2.3: gv names the GARCH walk, which also serves Student-t requests
     const bool lean = gauss && !k.native, gw = k.stt && k.gv && !k.boot && !k.native && !lg;
     switch (k.family) {
@@ -126,6 +132,7 @@ static hipError_t ladder(const PathKernel& k, const PathLaunchArgs& s, hipStream
 hipError_t MCP_CAT(launch_paths_nb, MCP_NB)(const PathKernel& k, const PathLaunchArgs& s, hipStream_t stream) {
   constexpr int NB = MCP_NB, KT = 1;                       // the folded step and the attribution walk: one portfolio per pass
   if (k.anti && (k.fold || k.family == FAM_AT)) return hipErrorInvalidValue;
+  if (k.fh && (k.fold || k.family == FAM_AT)) return hipErrorInvalidValue;
   if (k.fold) {                                            // rho = c + v.z: the plain Gaussian walk on the spec's normals
     const bool ok = k.family == FAM_PLAIN && !k.boot && !k.stt && !k.gv && !k.native && !k.kt8;
     MCP_ROW(ok && k.logc, mc_paths_kernel<NB, 1, 1, false, true, true>);

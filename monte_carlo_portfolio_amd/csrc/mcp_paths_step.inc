@@ -10,13 +10,16 @@
 // pair's returns and the weight dot, c = fl32(w r) and A = fma(V, c, A) for the pair, one v_pk_mul_f32 and one v_pk_fma_f32, V the
 // value before this step's update (SPEC.md 4.10).  ANTI: the step's normals are formed once; the row pair's accumulator, rho and
 // the update of V (DD: of the peak and drawdown) run for EM = 2 PPT members, member PPT + e on -z[e] (SPEC.md 2.3): a second fma
-// chain from the same mu2 -- never a shared L z, mu + L z and mu - L z round differently.  In scope: everything mcp_paths_body.inc
+// chain from the same mu2 -- never a shared L z, mu + L z and mu - L z round differently.  FH: the gathered row is a residual, r_i = fma(sqrt(h),
+// E_ji, mu_i) with mu from the packed block by scalar loads, and after the update of V h moves on the row's shock (SPEC.md 4.11).  In scope: everything mcp_paths_body.inc
 // declares before its step loops, and t.
       float rho[EM][KT];
+      float fsh[PPT];                                  // FH: the shock s_j of the step's row (SPEC.md 2.4)
       if constexpr (BOOT) {
         // SPEC.md 2.1 / 4.4: one Philox block on counter (t, 1, p_lo, p_hi); j_t = mulhi(x0, R) on a restart (t = 0 or
         // x1 < thr), else the next row, circularly; rho_k = sum_i w_ki r_i, i ascending over N4 (zero-padded rows)
         asm volatile("" : "+s"(Wk));
+        if constexpr (FH) asm volatile("" : "+s"(mu));   // the drift's scalar loads stay inside the step
 #pragma unroll
         for (int e = 0; e < PPT; e++) {
           uint32_t x[4];
@@ -34,6 +37,19 @@
             const float4* src = bt.rows + (size_t)j * NB;
 #pragma unroll
             for (int q = 0; q < NB; q++) r4[q] = src[q];
+          }
+          if constexpr (FH) {
+            // SPEC.md 4.11: sigma = sqrt(h) (IEEE, correctly rounded), r_i = fma(sigma, E_ji, mu_i) over N4 (zero-padded rows and drift)
+            if constexpr (BLDS) fsh[e] = ((const float*)&s_tab[bt.n_rows * (uint32_t)NB])[j];
+            else fsh[e] = fshock[j];
+            const float sg = sqrtf(gh[e]);
+#pragma unroll
+            for (int q = 0; q < NB; q++) {
+              r4[q].x = fma32(sg, r4[q].x, mu[4 * q + 0]);
+              r4[q].y = fma32(sg, r4[q].y, mu[4 * q + 1]);
+              r4[q].z = fma32(sg, r4[q].z, mu[4 * q + 2]);
+              r4[q].w = fma32(sg, r4[q].w, mu[4 * q + 3]);
+            }
           }
           if constexpr (REB) {
 #pragma unroll
@@ -232,6 +248,13 @@
 #pragma unroll
         for (int k = 0; k < KT; k++)
           V[e][k] = logc ? (V[e][k] + rho[e][k]) : fma32(V[e][k], rho[e][k], V[e][k]);
+      }
+      if constexpr (FH) {
+        // SPEC.md 4.11: d = fl32(h s_j), h = fminf(fma(b, h, fma(a, d, omega)), 2^40).  The constants are wave-uniform scalar loads.
+        const cfilt_p fk = filt_args(a);
+        const float f_a = fk->a, f_b = fk->b, f_om = fk->omega;
+#pragma unroll
+        for (int e = 0; e < PPT; e++) gh[e] = fminf(fma32(f_b, gh[e], fma32(f_a, gh[e] * fsh[e], f_om)), 0x1p40f);
       }
       if constexpr (DD) {
         // SPEC.md 4.2: P = fmax(P, V_t); q = fminf(q, V_t / P) (IEEE division) or d = fminf(d, S_t - P).  fminf is IEEE

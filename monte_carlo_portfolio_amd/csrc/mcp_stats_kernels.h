@@ -57,14 +57,15 @@ struct PathArgs;
 struct PathLaunchArgs;
 
 // Which path kernel a launch runs: the family, the compounding mode, the draw source (boot: the bootstrap's rows, blds: its row
-// table copied into LDS, it fits boot_fits_lds; stt: Student-t draws; gv: GARCH), dd (FAM_OV only: the overlay kernel that also
+// table copied into LDS, it fits boot_fits_lds; stt: Student-t draws; gv: GARCH; fh with boot: filtered residual rows, blds by
+// filt_fits_lds), dd (FAM_OV only: the overlay kernel that also
 // tracks the drawdown), kt8 (passes of 8 portfolios instead of 1), the plain Gaussian kernel's native-math and folded steps, and
 // anti (the antithetic kernels of the plain, drawdown and horizon families: Gaussian draws, or stt and gv both set for the GARCH walk).
 // The one ladder of mcp_paths_inst.hip maps it to a kernel and lists which selectors have one.
 enum PathFamily { FAM_PLAIN, FAM_DD, FAM_HZ, FAM_REB, FAM_CF, FAM_OV, FAM_AT };
 struct PathKernel {
   int family;
-  bool logc, boot, blds, stt, dd, gv, kt8, native, fold, anti;
+  bool logc, boot, blds, stt, dd, gv, kt8, native, fold, anti, fh;
 };
 
 // mcp_paths_inst.hip (one translation unit per NB): every pass of the kernel that `k` selects, on the blocks of `args` that the

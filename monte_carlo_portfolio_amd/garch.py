@@ -10,6 +10,11 @@ covariance simulates the covariance the Gaussian call does in the long run: only
 The maximiser is a deterministic two-stage grid on multiples of 0.002 (alpha = i / 500, beta = j / 500, i, j >= 0, i + j <= 499):
 the coarse stage visits the multiples of 0.02 (i, j multiples of 10), the fine stage every grid point within 0.02 of the coarse best
 in both coordinates.  Ties go to the smaller alpha, then the smaller beta.
+
+filter_rows: the rows de-volatilised with that variance path, for filtered historical simulation (SPEC.md 2.4; simulate_filtered).
+With h_1 = 1 and h_{t+1} = (1 - alpha - beta) + alpha d_t + beta h_t, row t becomes the residual e_t = (x_t - m) / sqrt(h_t) and carries
+the shock s_t = d_t / h_t, its own d in units of its fitted variance; h0 = h_{R+1}.  The recurrence takes d_t back as fl64(s_t h_t),
+within an ulp of d_t, so that the shocks it returns reproduce h0 exactly.
 """
 from __future__ import annotations
 
@@ -55,6 +60,50 @@ class _Garch:
 
     def logliks(self, alphas, betas):
         return self.walk(alphas, betas)[0]
+
+
+class FilteredRows(NamedTuple):
+    """filter_rows' result: what simulate_filtered takes.  mu [N], resid [R, N] and shock [R] are float32."""
+    mu: np.ndarray
+    resid: np.ndarray
+    shock: np.ndarray
+    alpha: float
+    beta: float
+    h0: float             # h_{R+1}: the variance ratio of the step after the last row
+
+
+def _filter64(X: np.ndarray, alpha: float, beta: float):
+    """-> (m [N], resid [R, N], shock [R], h [R], h0) in binary64: the recurrence of the module docstring over the rows."""
+    g = _Garch(X)
+    m = X.mean(axis=0)
+    w = 1.0 - alpha - beta
+    h = np.empty(g.R, np.float64)
+    shock = np.empty(g.R, np.float64)
+    ht = 1.0
+    for t in range(g.R):
+        h[t] = ht
+        shock[t] = g.d[t] / ht
+        ht = w + alpha * (shock[t] * ht) + beta * ht
+    return m, (X - m) / np.sqrt(h)[:, None], shock, h, float(ht)
+
+
+def filter_rows(returns, garch=None) -> FilteredRows:
+    """The return rows filtered by the scalar GARCH(1,1) on the covariance (SPEC.md 2.4): the sample mean m, the residual rows
+    (x_t - m) / sqrt(h_t) and the shocks d_t / h_t along the fitted variance path h_t, and h0 = h_{R+1}, today's level.  garch: None
+    fits (alpha, beta) with fit_garch; otherwise (alpha, beta[, h0]) -- an h0 given is ignored, the path decides it.  alpha = beta = 0
+    gives the centred rows and h0 = 1.  returns: as fit_garch.  -> FilteredRows(mu, resid, shock, alpha, beta, h0), the arrays
+    rounded to float32.  ValueError for rows fit_garch refuses, alpha or beta negative or not finite, or alpha + beta >= 1."""
+    X = _rows(returns)
+    if garch is None:
+        alpha, beta = fit_garch(X)[:2]
+    else:
+        if len(garch) < 2:
+            raise ValueError("garch must be (alpha, beta) or (alpha, beta, h0)")
+        alpha, beta = float(garch[0]), float(garch[1])
+    if not (np.isfinite(alpha) and np.isfinite(beta) and alpha >= 0.0 and beta >= 0.0 and alpha + beta < 1.0):
+        raise ValueError(f"garch alpha={alpha} and beta={beta} must be >= 0 with alpha + beta < 1")
+    m, resid, shock, _, h0 = _filter64(X, alpha, beta)
+    return FilteredRows(m.astype(np.float32), resid.astype(np.float32), shock.astype(np.float32), float(alpha), float(beta), h0)
 
 
 def garch_loglik(returns, alpha: float, beta: float) -> float:

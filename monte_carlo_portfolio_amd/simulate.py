@@ -65,7 +65,7 @@ class Context:
 
     def _call(self, prm: _ffi.McpParams, W, seed: int, path_begin: int, n_paths: int, store: bool, mu=None, chol=None, rows=None,
               block: float = 1.0, dof=None, period=None, cost: float = 0.0, drawdown: bool = False, horizons=None, levels=(),
-              flows=None, target=None, overlay=None, garch=None, attribution=False, antithetic=False):
+              flows=None, target=None, overlay=None, garch=None, attribution=False, antithetic=False, filtered=None):
         """The one library call behind every simulate_* method: GARCH volatility (garch: the (alpha, beta, h0) of check_garch), an option overlay (overlay: the triple of check_overlay), cash flows (flows, target), Student-t draws (dof), rebalancing
         (period, cost), bootstrap rows (rows, block) or Gaussian draws (mu, chol), with the drawdown or horizons.  Allocates the
         outputs that were asked for and passes NULL for the rest -> _Outputs, None where not asked for (terminal, qd,
@@ -93,7 +93,16 @@ class Context:
         hz_out = (ptr(hz_term), ptr(hz_stats), ptr(bands) if L else None)
         bt = _ffi.make_bootstrap(rows, block) if rows is not None else None
         attr = attr_counts = contrib = pairs = None
-        if antithetic:
+        if filtered is not None:
+            # SPEC.md 2.4 / 4.11: the library states the rules (check_request); nothing else of this method is passed on
+            if (overlay is not None or flows is not None or period is not None or bt is not None or dof is not None or attribution
+                    or antithetic or drawdown or garch is None):
+                raise ValueError("filtered rows take garch, block and horizons only")
+            ft = _ffi.make_filtered(*filtered, block)
+            gv = _ffi.McpGarch(float(garch[0]), float(garch[1]), float(garch[2]), 0)
+            rc = lib.mcp_simulate_filtered(self._h, prm_p, ctypes.byref(ft), ctypes.byref(gv), ptr(W), *walk, *hz_in, ptr(term), ptr(stats),
+                                           *hz_out)
+        elif antithetic:
             # the library states the rules (check_request): everything but plain, Student-t and GARCH draws is MCP_E_UNSUPPORTED
             if overlay is not None or flows is not None or period is not None or bt is not None or attribution:
                 raise ValueError("antithetic pairs are not combined with overlay, cashflow, rebalance, bootstrap rows or attribution")
@@ -213,6 +222,14 @@ class Context:
         for are None."""
         return self._call(prm, W, seed, path_begin, n_paths, store, mu=mu, chol=chol, dof=dof, drawdown=drawdown, horizons=horizons,
                           levels=levels, garch=garch)
+
+    def simulate_filtered(self, prm: _ffi.McpParams, filtered, garch, W, block: float, seed: int, path_begin: int, n_paths: int,
+                          store: bool, horizons=None, levels=()):
+        """simulate_bootstrap[_horizons]() on filtered rows (SPEC.md 2.4 / 4.11; include/mcport.h, mcp_simulate_filtered; simple
+        compounding only): `filtered` is the binary32 (mu [N], resid [R, N], shock [R]) triple, `garch` (alpha, beta, h0) -> _Outputs;
+        the horizon entries are None without horizons."""
+        return self._call(prm, W, seed, path_begin, n_paths, store, block=block, horizons=horizons, levels=levels, garch=garch,
+                          filtered=filtered)
 
     def simulate_attribution(self, prm: _ffi.McpParams, mu, chol, W, seed: int, path_begin: int, n_paths: int, store: bool, dof=None,
                              garch=None):
@@ -848,6 +865,77 @@ def simulate_bootstrap(returns, weights, n_steps=252, n_paths=10_000, block=1.0,
     out = ctx._call(prm, W, int(seed), int(path_begin), int(n_paths), store, rows=rows, block=b, period=period, cost=cost,
                     horizons=steps, levels=levels, flows=flows, target=target)
     return _result(out, np.asarray(weights).ndim == 1, store, as_array, steps, levels, compounding, flows, target)
+
+
+def filtered_inputs(filtered, weights):
+    """SPEC.md 2.4 argument rules -> (mu [N], resid [R, N], shock [R], W [K, N]), binary32 and C-contiguous; ValueError otherwise.
+    `filtered` is a garch.FilteredRows or a (mu, resid, shock) triple; its values are rounded to binary32 to nearest."""
+    if hasattr(filtered, "resid"):
+        filtered = (filtered.mu, filtered.resid, filtered.shock)
+    if isinstance(filtered, (str, bytes)) or not hasattr(filtered, "__len__") or len(filtered) != 3:
+        raise ValueError("filtered must be a FilteredRows (filter_rows(...)) or a (mu, resid, shock) triple")
+    mu, resid, shock = (np.asarray(a, np.float64) for a in filtered)
+    mu, shock = np.atleast_1d(mu), np.atleast_1d(shock)
+    if resid.ndim == 1:
+        resid = resid[:, None]
+    if resid.ndim != 2 or resid.shape[0] < 1 or mu.ndim != 1 or shock.ndim != 1:
+        raise ValueError(f"filtered wants mu [N], resid [R, N] with R >= 1 and shock [R], got shapes {mu.shape}, {resid.shape}, {shock.shape}")
+    R, N = resid.shape
+    if mu.shape[0] != N or shock.shape[0] != R:
+        raise ValueError(f"filtered resid is [{R}, {N}], mu has {mu.shape[0]} entries and shock {shock.shape[0]}")
+    if R > _ffi.MCP_MAX_BOOT_ROWS:
+        raise ValueError(f"at most {_ffi.MCP_MAX_BOOT_ROWS} residual rows, got {R}")
+    if not 1 <= N <= _ffi.MCP_MAX_ASSETS:
+        raise ValueError(f"n_assets={N} outside [1, {_ffi.MCP_MAX_ASSETS}]")
+    with np.errstate(over="ignore"):
+        mu, resid, shock = (np.ascontiguousarray(a.astype(np.float32)) for a in (mu, resid, shock))
+    for name, a in (("mu", mu), ("resid", resid), ("shock", shock)):
+        if not np.isfinite(a).all():
+            raise ValueError(f"filtered {name} holds NaN or infinite values (first: index {int(np.argmax(~np.isfinite(a).ravel()))})")
+    if (shock < 0).any():
+        raise ValueError(f"filtered shock must be >= 0 (first: row {int(np.argmax(shock < 0))})")
+    W = np.ascontiguousarray(np.atleast_2d(np.asarray(weights, np.float32)))
+    if W.ndim != 2 or W.shape[1] != N:
+        raise ValueError(f"weights have {W.shape[-1]} columns, the residual rows {N}")
+    return mu, resid, shock, W
+
+
+def simulate_filtered(filtered, weights, n_steps=252, n_paths=10_000, garch=None, block=1.0, seed=0, v0=1.0, rf=0.0, alpha=0.95,
+                      horizons=None, levels=(), devices=None, store=False, as_array=False, path_begin=0, shard="auto", context=None,
+                      **unsupported):
+    """Filtered historical simulation (Barone-Adesi, Giannopoulos & Vosper 1999; SPEC.md 2.4 / 4.11): simulate_bootstrap on rows
+    that garch.filter_rows de-volatilised with the fitted GARCH(1,1) variance path, every draw re-scaled by the path's own simulated
+    variance ratio h -- the empirical shocks of the bootstrap (tails, skew, assets that crash together) with the volatility
+    clustering of simulate_paths(garch=...), and a fan that starts from today's variance level.  A step draws a row j as the
+    bootstrap does, r = mu + sqrt(h) resid[j], and h moves on the row's shock.
+
+    filtered: a FilteredRows (filter_rows(returns)) or a (mu [N], resid [R, N], shock [R]) triple, finite, shock >= 0, R <= 2^20;
+    weights [N] or [K, N].  garch: (alpha, beta[, h0]) as simulate_paths takes it; None takes (alpha, beta, h0) from the FilteredRows
+    (a plain triple then needs garch).  alpha = 0 with h0 = 1 is simulate_bootstrap on the rows resid + mu bit for bit.  block: the
+    mean block length of simulate_bootstrap (1: classical FHS).  horizons / levels: simulate_paths' horizons / bands.  Returns what
+    simulate_bootstrap returns for the same arguments (pivots of SPEC.md 5.11).  Simple compounding only: ValueError for
+    compounding="log" and for the simulate_paths keywords that have no meaning here (dof, fold, native_math, drawdown, rebalance,
+    cashflow, overlay, attribution, antithetic)."""
+    comp = unsupported.pop("compounding", "simple")
+    if comp != "simple":
+        raise ValueError(f"simulate_filtered compounds simply: not with compounding={comp!r}")
+    if unsupported:
+        raise ValueError(f"simulate_filtered does not take {sorted(unsupported)}: filtered rows combine with garch, block and horizons "
+                         "only (SPEC.md 4.11)")
+    if garch is None:
+        if not hasattr(filtered, "h0"):
+            raise ValueError("garch=None needs a FilteredRows (filter_rows(...)): a (mu, resid, shock) triple carries no (alpha, beta, h0)")
+        garch = (filtered.alpha, filtered.beta, filtered.h0)
+    gv = check_garch(garch)
+    b = float(block)
+    if not b >= 1.0:
+        raise ValueError(f"block (mean block length) must be >= 1 or inf, got {block!r}")
+    steps, lv = _check_walk(n_steps, horizons, levels, None, "simple", shard)
+    mu, resid, shock, W = filtered_inputs(filtered, weights)
+    prm, ctx = _setup(resid.shape[1], n_steps, W.shape[0], "simple", v0, alpha, rf, False, False, devices, shard, context)
+    out = ctx.simulate_filtered(prm, (mu, resid, shock), gv, W, b, int(seed), int(path_begin), int(n_paths), store, horizons=steps,
+                                levels=lv)
+    return _result(out, np.asarray(weights).ndim == 1, store, as_array, steps, lv, "simple")
 
 
 def simulate_sweep(mu, cov, weights=None, n_portfolios=2500, min_weights=None, max_weights=None, n_steps=252,
