@@ -20,6 +20,10 @@
 #include "mcp_paths.h"
 #include "mcp_stats_kernels.h"
 
+#ifndef MCP_EXP_LEAN        // 1: launches that pass mcp::lean_range run mc_paths_lean_kernel; 0: every launch stays on mc_paths_kernel
+#define MCP_EXP_LEAN 1      // (tools/kernel_lab.py arms `lean` and `nolean`; profiles/lean_probe.json)
+#endif
+
 namespace {
 
 thread_local std::string g_err;
@@ -1155,6 +1159,8 @@ static int launch_paths_impl(const mcp_params* prm, const Request& rq, const Lau
     k.kt8 = K > 1;
     k.native = (prm->flags & MCP_FLAG_NATIVE_MATH) != 0;
     k.fold = (prm->flags & MCP_FLAG_FOLD) != 0;
+    // the plain Gaussian walk of one portfolio whose paths share the high counter word runs the lean step loop (mcp_paths.h, UHI)
+    k.uhi = MCP_EXP_LEAN && plain && !rq.anti && !k.kt8 && !k.native && !k.fold && nb <= mcp::LEAN_MAX_NB && mcp::lean_range(a.path_begin, a.n_paths);
     if (rq.anti) {
       // Student-t and GARCH requests share the GARCH walk, as the attribution does: without GARCH on alpha = beta = 0, h0 = 1
       static const mcp_garch none = {0.0, 0.0, 1.0, 0};

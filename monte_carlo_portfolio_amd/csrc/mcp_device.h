@@ -75,6 +75,54 @@ __device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t
   x[0] = c0; x[1] = c1; x[2] = c2; x[3] = c3;
 }
 
+// Scalar copies of the round keys that meet a wave-uniform operand in philox4x32_10_uhi: from the seed alone, never pinned in
+// VGPRs, so the compiler keeps them and everything folded with them on the SALU.
+struct PhiloxUniformKeys {
+  uint32_t k1_0, k0_1, k1_1, k0_2;
+};
+__device__ __forceinline__ PhiloxUniformKeys philox_uniform_keys(uint32_t k0, uint32_t k1) {
+  PhiloxUniformKeys sk = {k1, k0 + PHILOX_W0, k1 + PHILOX_W1, k0 + 2u * PHILOX_W0};
+  sk.k1_0 = __builtin_amdgcn_readfirstlane(sk.k1_0); sk.k0_1 = __builtin_amdgcn_readfirstlane(sk.k0_1);
+  sk.k1_1 = __builtin_amdgcn_readfirstlane(sk.k1_1); sk.k0_2 = __builtin_amdgcn_readfirstlane(sk.k0_2);
+  return sk;
+}
+
+// philox4x32_10 on the counter (blk, 0, p_lo, p_hi) with blk AND p_hi wave-uniform (SGPRs; every path of the launch shares
+// p_hi).  Round 1's c2 = hi(M0 blk) ^ p_hi ^ k1[0] and c3 = lo(M0 blk) are then scalar, and so is round 2's M1 c2: written out on
+// scalars, with scalar ^ key folded on the SALU so that every vector xor that remains reads one SGPR.  The words are those of
+// philox4x32_10 bit for bit (xor is associative; the products are the same products).  What depends on p_lo and the keys
+// alone -- M1 p_lo, round 1's c0 and round 2's M0 c0 -- is loop-invariant in the walk over t, as in philox4x32_10.
+__device__ __forceinline__ void philox4x32_10_uhi(uint32_t blk, uint32_t p_lo, uint32_t p_hi, const PhiloxKeys& ks,
+                                                  const PhiloxUniformKeys& sk, uint32_t (&x)[4]) {
+  // round 1: c0 = blk, c1 = 0, c2 = p_lo, c3 = p_hi
+  const uint64_t q0 = (uint64_t)PHILOX_M0 * blk;                 // scalar
+  const uint64_t p1 = (uint64_t)PHILOX_M1 * p_lo;
+  const uint32_t a0 = (uint32_t)(p1 >> 32) ^ ks.k0[0];
+  const uint32_t s2 = (uint32_t)(q0 >> 32) ^ p_hi ^ sk.k1_0;     // scalar
+  // round 2: c0 = a0, c1 = lo(p1), c2 = s2, c3 = lo(q0)
+  const uint64_t p0 = (uint64_t)PHILOX_M0 * a0;
+  const uint64_t q1 = (uint64_t)PHILOX_M1 * s2;                  // scalar: s_mul_hi_u32, s_mul_i32
+  uint32_t f0 = (uint32_t)(q1 >> 32) ^ sk.k0_1, f2 = (uint32_t)q0 ^ sk.k1_1, f1 = (uint32_t)q1 ^ sk.k0_2;
+  asm("" : "+s"(f0), "+s"(f2), "+s"(f1));                        // folded on the SALU, not re-associated into the vector xors
+  uint32_t c0 = (uint32_t)p1 ^ f0;
+  uint32_t c2 = (uint32_t)(p0 >> 32) ^ f2;
+  uint32_t c3 = (uint32_t)p0;
+  uint32_t c1 = 0u;
+#pragma unroll
+  for (int r = 2; r < 10; r++) {
+    const uint64_t r0 = (uint64_t)PHILOX_M0 * c0;
+    const uint64_t r1 = (uint64_t)PHILOX_M1 * c2;
+    // round 3: c1 = lo(q1) is scalar and meets k0[2] in f1
+    const uint32_t n0 = r == 2 ? (uint32_t)(r1 >> 32) ^ f1 : xor3((uint32_t)(r1 >> 32), c1, ks.k0[r]);
+    const uint32_t n2 = xor3((uint32_t)(r0 >> 32), c3, ks.k1[r]);
+    c1 = (uint32_t)r1;
+    c3 = (uint32_t)r0;
+    c0 = n0;
+    c2 = n2;
+  }
+  x[0] = c0; x[1] = c1; x[2] = c2; x[3] = c3;
+}
+
 constexpr float NEG_2LN2 = -0x1.62e43p+0f;       // -2 ln 2 (native Box-Muller only)
 
 constexpr int ICDF_ENTRIES = 1056;   // 33 octaves x 32 mantissa bins of float4 {c0,c1,c2,c3}: 16.5 KiB of LDS per workgroup
@@ -92,10 +140,14 @@ constexpr int ICDF_LDS_ENTRIES = ICDF_ENTRIES + ICDF_PAD;
 // rate of a VALU instruction on gfx950 (profiles/r01_valu_rates.txt).
 struct IcdfConsts {
   uint32_t m18, m31;
+  float su, sh;         // the scaling of u: us = fma(v, su, sh)
 };
+// PIN_SCALE: su and sh sit in VGPRs too (otherwise they are literals, and the compiler forms the pair with a v_mov_b64 per step)
+template <bool PIN_SCALE = false>
 __device__ __forceinline__ IcdfConsts icdf_consts() {
-  IcdfConsts c = {0x0003ffffu, 0x7fffffffu};
+  IcdfConsts c = {0x0003ffffu, 0x7fffffffu, 0x1p-125f, 0x1p-126f};
   asm volatile("" : "+v"(c.m18), "+v"(c.m31));
+  if constexpr (PIN_SCALE) asm volatile("" : "+v"(c.su), "+v"(c.sh));
   return c;
 }
 
@@ -111,7 +163,7 @@ __device__ __forceinline__ uint32_t bitselect(uint32_t m, uint32_t a, uint32_t b
 // remaining 18 mantissa bits: one ds_read_b128 from the LDS copy of the table, three fma, no transcendental.
 // `tab` is the PADDED LDS table (entry ICDF_PAD holds T[0]).  10.5 VALU instructions per normal.
 __device__ __forceinline__ float normal_icdf(uint32_t x, const float4* tab, const IcdfConsts& k) {
-  const float us = fma32((float)(x & 0x7fffffffu), 0x1p-125f, 0x1p-126f);          // u * 2^-93: exponent field 1..33
+  const float us = fma32((float)(x & 0x7fffffffu), k.su, k.sh);          // u * 2^-93: exponent field 1..33
   const uint32_t b = __float_as_uint(us);
   const float4 c = *(const float4*)((const char*)tab + ((b >> 14) & 0x0003fff0u));   // tab[b >> 18]
   const float dc = __uint_as_float((b & k.m18) | 0x3f800000u) - 0x1.04p+0f;
@@ -148,7 +200,7 @@ __device__ __forceinline__ void block_normals(const uint32_t (&x)[4], const floa
     float4 c[4];
     float dc[4], a[4];
 #pragma unroll
-    for (int i = 0; i < 4; i++) b[i] = __float_as_uint(fma32((float)(x[i] & 0x7fffffffu), 0x1p-125f, 0x1p-126f));
+    for (int i = 0; i < 4; i++) b[i] = __float_as_uint(fma32((float)(x[i] & 0x7fffffffu), k.su, k.sh));
 #pragma unroll
     for (int i = 0; i < 4; i++) c[i] = *(const float4*)((const char*)tab + ((b[i] >> 14) & 0x0003fff0u));
     __builtin_amdgcn_sched_barrier(0);

@@ -63,8 +63,8 @@
 #ifndef MCP_EXP_BOOT_SWIZZLE  // 1: the bootstrap's LDS row table is XOR-swizzled (BootSwizzle); 0: plain layout (lab builds)
 #define MCP_EXP_BOOT_SWIZZLE 1
 #endif
-#ifndef MCP_EXP_LDSPAR      // 1: drift from LDS (default); 2: drift and (one portfolio) weights from LDS; 0: both from SGPRs
-#define MCP_EXP_LDSPAR 1
+#ifndef MCP_EXP_LDSPAR      // 1: drift from LDS (default); 2: drift and (one portfolio) weights from LDS; 0: both from SGPRs.  2 was priced at
+#define MCP_EXP_LDSPAR 1    // -2 % by the issue model and measured within +-0.5 % of 1 (profiles/r02_lab5.txt): not to be tried again
 #endif
 
 namespace mcp {
@@ -95,7 +95,7 @@ __device__ __forceinline__ const __attribute__((address_space(4))) A* kernarg() 
   template <class A> struct has_##m<A, std::void_t<decltype(A::m)>> : std::true_type {};
 MCP_HAS_MEMBER(hz) MCP_HAS_MEMBER(mdd) MCP_HAS_MEMBER(bt) MCP_HAS_MEMBER(st) MCP_HAS_MEMBER(gv) MCP_HAS_MEMBER(cf)
 MCP_HAS_MEMBER(ov) MCP_HAS_MEMBER(at) MCP_HAS_MEMBER(period) MCP_HAS_MEMBER(pr)
-MCP_HAS_MEMBER(fh)
+MCP_HAS_MEMBER(fh) MCP_HAS_MEMBER(p_hi)
 #undef MCP_HAS_MEMBER
 
 struct PathArgs {
@@ -116,6 +116,19 @@ struct PathArgs {
   float v0;
   uint32_t fold_offset;               // float index of [c, v_0 .. v_{N4-1}] (portfolio 0 folded through L, SPEC.md 4.1)
 };
+
+// Arguments of mc_paths_lean_kernel: PathArgs and the high counter word that every path of the launch shares,
+// p_hi = path_begin >> 32 = (path_begin + n_paths - 1) >> 32 (lean_range in mcp_route.h decides it on the host).
+struct PathArgsLean : PathArgs {
+  uint32_t p_hi;
+  uint32_t pad;
+};
+// p_hi of a lean launch, a kernel argument (an SGPR for the whole walk); the argument also selects the kernel's argument type.
+template <class A>
+__device__ __forceinline__ uint32_t uniform_hi(const A& a) {
+  if constexpr (has_p_hi<A>::value) return a.p_hi;
+  else return 0u;
+}
 
 // Arguments of mc_paths_dd_kernel: PathArgs (at offset 0, where the epilogue reads it through the kernarg pointer) and the
 // per-path drawdown output of SPEC.md 4.2.
@@ -355,6 +368,7 @@ inline A make_args(const PathLaunchArgs& s) {
   if constexpr (has_period<A>::value) { x.period = s.period; x.cost = s.cost; }
   if constexpr (has_pr<A>::value) x.pr = s.pr;
   if constexpr (has_fh<A>::value) x.fh = s.fh;
+  if constexpr (has_p_hi<A>::value) { x.p_hi = (uint32_t)(s.hz.path_begin >> 32); x.pad = 0u; }
   return x;
 }
 
@@ -447,13 +461,16 @@ constexpr int PATH_BLOCK = 256;
 // (SPEC.md 4.10 / 5.9).  FH (with BOOT): the row is a filtered residual, r_i = fma(sqrt(h), E_ji, mu_i), and h is updated from the
 // row's shock, h = fminf(fma(b, h, fma(a, h s_j, omega)), 2^40) (SPEC.md 2.4 / 4.11).  ANTI: a lane walks the two members of an antithetic pair on one set of draws: everything up to the step's
 // normals z (Philox, the transform, the chi blocks, h) runs once, everything downstream of z -- the row-pair accumulators, rho, V,
-// the peak and drawdown, the stores and the epilogue -- carries a second member that sees -z (SPEC.md 2.3 / 5.10).  Every kernel
+// the peak and drawdown, the stores and the epilogue -- carries a second member that sees -z (SPEC.md 2.3 / 5.10).  UHI: the high
+// counter word p_hi is one value for the whole launch, a kernel argument: Philox rounds 1 and 2 run on the SALU where their operands
+// are wave-uniform (philox4x32_10_uhi), the drift's LDS address and the transform's two scaling constants sit in VGPRs across the walk
+// instead of being formed every step; the draws, and every result, are those of the kernel without it.  Every kernel
 // below is the body in mcp_paths_body.inc under its own flags F: it names the flags it sets, the rest are PathFlagsOff's.  F is a
 // local class, which may not have static data members, so it sets its flags as enumerators of an `enum : bool`; they hide the
 // defaults' names and read as the same constant expressions.
 struct PathFlagsOff {
   static constexpr bool NATIVE = false, FOLD = false, LOGC = false, DD = false, HZ = false, BOOT = false, BLDS = false, REB = false,
-                        STT = false, CF = false, OV = false, GV = false, AT = false, ANTI = false, FH = false;
+                        STT = false, CF = false, OV = false, GV = false, AT = false, ANTI = false, FH = false, UHI = false;
 };
 
 // __launch_bounds__ 2nd argument of a path kernel: the MCP_MIN_WAVES* above for N <= 16 and one path per lane, by the kind of
@@ -472,6 +489,16 @@ constexpr int min_waves(BoundsKind kind, int NB, int KT, int PPT) {
 template <int NB, int KT, int PPT, bool NATIVE_, bool FOLD_ = false, bool LOGC_ = false>
 __global__ void MCP_BOUNDS(BK_PATHS) mc_paths_kernel(const PathArgs a) {
   struct F : PathFlagsOff { enum : bool { NATIVE = NATIVE_, FOLD = FOLD_, LOGC = LOGC_ }; };
+#include "mcp_paths_body.inc"
+}
+
+// The lean Gaussian kernel: mc_paths_kernel<NB, 1, 1, false, false, LOGC> for a launch whose paths share the high counter word
+// (UHI above) -- the same walk, terminal values and fused epilogue bit for bit, with the step loop's wave-uniform work taken off
+// the VALU.  A launch whose path range crosses a multiple of 2^32 stays on mc_paths_kernel.
+template <int NB, bool LOGC_>
+__global__ void __launch_bounds__(PATH_BLOCK, min_waves(BK_PATHS, NB, 1, 1)) mc_paths_lean_kernel(const PathArgsLean a) {
+  constexpr int KT = 1, PPT = 1;
+  struct F : PathFlagsOff { enum : bool { LOGC = LOGC_, UHI = true }; };
 #include "mcp_paths_body.inc"
 }
 

@@ -4,7 +4,9 @@
 // walk is the one loop it always was.  In scope: the template parameters NB, KT, PPT, the flags F (PathFlagsOff or a struct
 // derived from it) and the kernel argument `a` (PathArgs or a struct that starts with one).
   constexpr bool NATIVE = F::NATIVE, FOLD = F::FOLD, LOGC = F::LOGC, DD = F::DD, HZ = F::HZ, BOOT = F::BOOT, BLDS = F::BLDS, REB = F::REB,
-                 STT = F::STT, CF = F::CF, OV = F::OV, GV = F::GV, AT = F::AT, ANTI = F::ANTI, FH = F::FH;
+                 STT = F::STT, CF = F::CF, OV = F::OV, GV = F::GV, AT = F::AT, ANTI = F::ANTI, FH = F::FH, UHI = F::UHI;
+  static_assert(!UHI || (KT == 1 && PPT == 1 && !(NATIVE || FOLD || DD || HZ || BOOT || REB || STT || CF || OV || GV || AT || ANTI || FH)),
+                "uniform high counter word: the plain Gaussian walk of one portfolio only");
   static_assert(!FH || (BOOT && HZ && !(LOGC || REB || CF || STT || GV || OV || AT || DD)), "filtered rows: the bootstrap's segmented walk only");
   constexpr int N4 = 4 * NB;
   // ANTI (SPEC.md 2.3): a lane's PPT draws feed EM = 2 PPT members -- slot e < PPT walks on z[e], slot PPT + e on -z[e]; p, live and
@@ -72,13 +74,23 @@
     if (threadIdx.x < (PATH_BLOCK / 64) * KT) pair_wave_slots<KT>()[threadIdx.x] = 0.0;
   }
   __syncthreads();
-  const IcdfConsts kc = icdf_consts();
+  const IcdfConsts kc = icdf_consts<UHI>();
   PhiloxKeys ks = philox_keys((uint32_t)a.seed, (uint32_t)(a.seed >> 32));
 #if MCP_EXP_VKEYS
   // pin the 20 round keys in VGPRs: an SGPR operand halves the issue rate of the xor (profiles/r01_valu_rates.txt)
 #pragma unroll
   for (int r = 0; r < 10; r++) { asm volatile("" : "+v"(ks.k0[r])); asm volatile("" : "+v"(ks.k1[r])); }
 #endif
+  // UHI: the scalar copies of the keys of rounds 1 to 3, the launch's p_hi, and the drift's LDS address in a VGPR of its own
+  typedef const __attribute__((address_space(3))) float* lfloat_p;
+  PhiloxUniformKeys sk{};
+  uint32_t uhi = 0u;
+  lfloat_p par_lds = nullptr;
+  if constexpr (UHI) {
+    sk = philox_uniform_keys((uint32_t)a.seed, (uint32_t)(a.seed >> 32));
+    uhi = uniform_hi(a);
+    par_lds = (lfloat_p)s_par0;
+  }
   const int T = a.n_steps;
   constexpr bool logc = LOGC;
 

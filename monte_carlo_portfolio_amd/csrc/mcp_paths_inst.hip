@@ -139,6 +139,14 @@ hipError_t MCP_CAT(launch_paths_nb, MCP_NB)(const PathKernel& k, const PathLaunc
     MCP_ROW(ok && !k.logc, mc_paths_kernel<NB, 1, 1, false, true, false>);
     return hipErrorInvalidValue;
   }
+  if (k.uhi) {                                             // one p_hi for the whole launch (lean_range): the plain Gaussian walk, lean
+    if constexpr (NB <= LEAN_MAX_NB) {
+      const bool ok = k.family == FAM_PLAIN && !k.boot && !k.stt && !k.gv && !k.native && !k.kt8 && !k.anti && !k.fh;
+      MCP_ROW(ok && k.logc, mc_paths_lean_kernel<NB, true>);
+      MCP_ROW(ok && !k.logc, mc_paths_lean_kernel<NB, false>);
+    }
+    return hipErrorInvalidValue;
+  }
   if (k.family == FAM_AT) {                                // simple compounding, the GARCH kernel's draws
     MCP_ROW(!k.kt8 && !k.native && !k.logc && !k.boot, mc_paths_attr_kernel<NB, 1, 1>);
     return hipErrorInvalidValue;

@@ -12,7 +12,8 @@
 // the update of V (DD: of the peak and drawdown) run for EM = 2 PPT members, member PPT + e on -z[e] (SPEC.md 2.3): a second fma
 // chain from the same mu2 -- never a shared L z, mu + L z and mu - L z round differently.  FH: the gathered row is a residual, r_i = fma(sqrt(h),
 // E_ji, mu_i) with mu from the packed block by scalar loads, and after the update of V h moves on the row's shock (SPEC.md 4.11).  In scope: everything mcp_paths_body.inc
-// declares before its step loops, and t.
+// declares before its step loops, and t.  UHI: the same step with p_hi a scalar (philox4x32_10_uhi), the drift read through the LDS address
+// par_lds instead of the opaque zero offset, and the blocks scheduled one at a time.
       float rho[EM][KT];
       float fsh[PPT];                                  // FH: the shock s_j of the step's row (SPEC.md 2.4)
       if constexpr (BOOT) {
@@ -78,8 +79,12 @@
       // keep the (loop-invariant) parameter loads inside the step: hoisted, they would pin ~170 registers
       asm volatile("" : "+s"(mu), "+s"(Lp), "+s"(Wk));
       uint32_t par_off = 0;                                        // opaque zero: keeps the LDS reads inside the step too
-      if constexpr (LDS_MU) asm volatile("" : "+v"(par_off));
+      if constexpr (LDS_MU && !UHI) asm volatile("" : "+v"(par_off));
       const float* s_par = s_par0 + par_off;
+      if constexpr (UHI) {                                         // the address itself, made opaque in place: no instruction
+        asm volatile("" : "+v"(par_lds));
+        s_par = (const float*)par_lds;
+      }
       float z[PPT][N4];
       float st_s[PPT];                                 // STT: the step's scale s of SPEC.md 2.2 (GV: u of SPEC.md 4.9)
       if constexpr (STT) {
@@ -128,7 +133,13 @@
 #pragma unroll
         for (int e = 0; e < PPT; e++) {
           uint32_t x[4];
-          philox4x32_10(blk, 0u, plo[e], phi[e], ks, x);
+          if constexpr (UHI) {
+            // one block at a time: scheduled across the blocks, the step's temporaries pushed the values the epilogue needs to scratch
+            __builtin_amdgcn_sched_barrier(0);
+            philox4x32_10_uhi(blk, plo[e], uhi, ks, sk, x);
+          } else {
+            philox4x32_10(blk, 0u, plo[e], phi[e], ks, x);
+          }
           block_normals<NATIVE>(x, s_tab, kc, z[e][0 * NB + q], z[e][1 * NB + q], z[e][2 * NB + q], z[e][3 * NB + q]);
           if constexpr (STT) {                         // SPEC.md 4.6: z' = fl32(s z)
 #pragma unroll

@@ -4,6 +4,7 @@
 #include <stdint.h>
 
 #include "../../include/mcport.h"
+#include "mcp_route.h"
 
 namespace mcp {
 
@@ -60,12 +61,16 @@ struct PathLaunchArgs;
 // table copied into LDS, it fits boot_fits_lds; stt: Student-t draws; gv: GARCH; fh with boot: filtered residual rows, blds by
 // filt_fits_lds), dd (FAM_OV only: the overlay kernel that also
 // tracks the drawdown), kt8 (passes of 8 portfolios instead of 1), the plain Gaussian kernel's native-math and folded steps, and
-// anti (the antithetic kernels of the plain, drawdown and horizon families: Gaussian draws, or stt and gv both set for the GARCH walk).
+// anti (the antithetic kernels of the plain, drawdown and horizon families: Gaussian draws, or stt and gv both set for the GARCH walk),
+// and uhi (the plain Gaussian walk of one portfolio on the spec's normals whose launch passes lean_range: mc_paths_lean_kernel,
+// N <= 16 only -- LEAN_MAX_NB: from NB = 5 on the listings show it at more registers than mc_paths_kernel, at NB = 12, 14 and 15
+// at one wave per SIMD fewer, and nothing above NB = 4 has been timed).
 // The one ladder of mcp_paths_inst.hip maps it to a kernel and lists which selectors have one.
+constexpr int LEAN_MAX_NB = 4;
 enum PathFamily { FAM_PLAIN, FAM_DD, FAM_HZ, FAM_REB, FAM_CF, FAM_OV, FAM_AT };
 struct PathKernel {
   int family;
-  bool logc, boot, blds, stt, dd, gv, kt8, native, fold, anti, fh;
+  bool logc, boot, blds, stt, dd, gv, kt8, native, fold, anti, fh, uhi;
 };
 
 // mcp_paths_inst.hip (one translation unit per NB): every pass of the kernel that `k` selects, on the blocks of `args` that the

@@ -3,18 +3,25 @@
 
   python tools/kernel_lab.py build  name1:"-DFLAG=1 ..." name2:"..."     (CPU box: cross-compiles)
   python tools/kernel_lab.py run [--paths P --rounds R --assets N] name1 name2 ...   (GPU box)
+
+A name without flags is one of ARMS below: `lean` routes the plain Gaussian walk to mc_paths_lean_kernel where the launch's
+paths share the high counter word, `nolean` keeps every launch on mc_paths_kernel (the code of the tree before the lean
+kernel), `nolean2` is the same build again for an A/A repeat (profiles/lean_probe.json).
 """
 import ctypes, os, subprocess, sys, statistics
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 LAB = os.path.join(ROOT, "tools", "lab_build")
 CSRC = os.path.join(ROOT, "monte_carlo_portfolio_amd", "csrc")
+ARMS = {"lean": "-DMCP_EXP_LEAN=1", "nolean": "-DMCP_EXP_LEAN=0", "nolean2": "-DMCP_EXP_LEAN=0"}
 
 
 def build(specs):
     os.makedirs(LAB, exist_ok=True)
     for spec in specs:
-        name, _, flags = spec.partition(":")
+        name, colon, flags = spec.partition(":")
+        if not colon:
+            flags = ARMS[name]
         out = os.path.join(LAB, f"libmcport_{name}.so")
         r = subprocess.run(["make", "-C", CSRC, "-j8", f"BUILD=build_{name}", f"OUT={out}", f"EXTRA={flags}"],
                            capture_output=True, text=True)
@@ -68,6 +75,7 @@ def run(names, paths, rounds, assets, steps, native, stats=True, K=1):
         ts = times[n]
         tf = f"  W.r product {2.0 * K * assets * paths * steps / statistics.median(ts) / 1e9:.1f} TFLOP/s" if K > 1 else ""
         print(f"{n:>14}: median {statistics.median(ts):.3f} ms  min {min(ts):.3f} ms  -> {paths / statistics.median(ts) * 1e3:.4e} paths/s{tf}")
+        print(f"{n:>14}  rounds (ms): " + " ".join(f"{t:.4f}" for t in ts))
 
 
 if __name__ == "__main__":
