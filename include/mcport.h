@@ -32,7 +32,8 @@ extern "C" {
                                     + mcp_simulate_garch (additive, detected by symbol);
                                     + mcp_simulate_attribution (additive, detected by symbol);
                                     + mcp_simulate_antithetic (additive, detected by symbol);
-                                    + mcp_simulate_filtered, mcp_filtered_pivots (additive, detected by symbol) */
+                                    + mcp_simulate_filtered, mcp_filtered_pivots (additive, detected by symbol);
+                                    + mcp_simulate_jumps, mcp_jump_consts (additive, detected by symbol) */
 #define MCP_MAX_ASSETS 64        /* thread-per-path kernels are instantiated for N4 = 4..64 */
 #define MCP_SELECT_BINS 2048     /* radix-select digit: 11 + 11 + 10 bits */
 #define MCP_MAX_HORIZONS 64      /* mcp_simulate_horizons: horizon steps per call */
@@ -41,6 +42,7 @@ extern "C" {
 #define MCP_MAX_OVERLAY_ROWS 8   /* mcp_simulate_overlay: option rows per asset */
 #define MCP_MAX_T_DOF 32         /* mcp_simulate_student_t: degrees of freedom in [3, MCP_MAX_T_DOF] */
 #define MCP_MAX_ATTR_PORTFOLIOS 16 /* mcp_simulate_attribution: portfolios per call */
+#define MCP_MAX_JUMPS 8          /* mcp_simulate_jumps: market jumps per path-step (the Poisson count is truncated there) */
 
 enum {
     MCP_OK = 0,
@@ -357,6 +359,46 @@ int mcp_simulate_filtered(mcp_ctx *ctx, const mcp_params *prm, const mcp_filtere
 /* The shift of the moments of filtered paths at prm->n_steps (SPEC.md 5.11; host side, binary64): with e_i the mean of column i of
  * resid (rows ascending), m_k = sum_i W[k,i] (mu_i + e_i): c_k = expm1(T log1p(m_k)), 0 if m_k <= -1 or where it is not finite. */
 int mcp_filtered_pivots(const mcp_params *prm, const mcp_filtered *filt, const float *W, double *pivots_out /* [K] */);
+
+/* Merton jump-diffusion (Merton 1976; SPEC.md 2.5 / 4.12 / 5.12): on top of the Gaussian step every path-step takes a compound-Poisson
+ * market jump J = sum of n normal(mean, std^2) jumps, n ~ Poisson(intensity) truncated at MCP_MAX_JUMPS, that asset i takes part in
+ * through its loading: r_i = mu'_i + b_i J + (L z)_i.  intensity: expected jumps per step, in [0, 1]; mean, std >= 0: of one jump, rounded
+ * to binary32; loading: [N] binary32 (NULL: all ones).  Everything finite, before and after rounding to binary32; reserved must be 0. */
+typedef struct {
+    double intensity, mean, std;
+    const float *loading;
+    int32_t reserved;
+} mcp_jumps;
+
+/* mcp_simulate / mcp_simulate_drawdown / mcp_simulate_horizons with the market jump of SPEC.md 2.5 added to every step (simple
+ * compounding only): one more Philox block per path-step on counter stream 3 gives the count n (uint32 compares of its first word
+ * against the thresholds of mcp_jump_consts) and the size J = fma(fl32(sqrt(n) s32), Z(second word), fl32(n m32)); row i of the
+ * step starts at fma(b_i, J, mu'_i) with mu' the compensated drift of mcp_jump_consts, so the mean of every step stays mu and
+ * the moments are pivoted as mcp_pivots on mu.  chol is the DIFFUSIVE factor: the per-step covariance is L L' + Var(J) b b'.  The
+ * asset normals are those of the call without jumps (common random numbers); intensity = 0, mean = std = 0 or loading = 0 is that
+ * call bit for bit for a drift without zero entries.  The horizon inputs and the outputs are those of mcp_simulate_garch (the
+ * drawdown or the horizons, not both: MCP_E_UNSUPPORTED).  Argument errors (MCP_E_ARG: the rules above, NULL pointers) are found
+ * before any device is touched; log compounding, MCP_FLAG_FOLD, MCP_FLAG_NATIVE_MATH: MCP_E_UNSUPPORTED.  Not built: jumps with
+ * Student-t draws, GARCH, bootstrap or filtered rows, rebalancing, cash flows, the overlay, the attribution or antithetic pairs, and
+ * at the mcp_launch_paths* level.  Costs: one Philox block, one normal, 8 compares and N4/2 packed fused multiply-adds per path-step;
+ * the loadings are uploaded once per device and tile behind the packed parameters; K >= 17 runs as passes of 8 portfolios. */
+int mcp_simulate_jumps(mcp_ctx *ctx, const mcp_params *prm, const mcp_jumps *j,
+                       const float *mu, const float *chol, const float *W,
+                       uint64_t seed, uint64_t path_begin, uint64_t n_paths,
+                       int n_horizons, const int32_t *horizons, int n_levels, const double *levels,
+                       float *terminal_out,        /* NULL or host [K*n_paths] */
+                       mcp_stats *stats_out,       /* [K] */
+                       float *mdd_out,             /* NULL or host [K*n_paths]; needs dd_stats_out */
+                       mcp_stats *dd_stats_out,    /* [K], or NULL: no drawdown */
+                       float *horizon_out,         /* NULL or host [H*K*n_paths], row h*K + k */
+                       mcp_stats *hz_stats_out,    /* [H*K], NULL iff n_horizons == 0 */
+                       double *bands_out);         /* [H*K*L], NULL iff n_levels == 0 */
+/* The host constants of a jump request (SPEC.md 2.5; no device is touched): thr_out[k-1] = floor(2^32 P(Poisson(intensity) >= k)) for
+ * k = 1 .. MCP_MAX_JUMPS (binary64, libm exp), *mean_count_out = sum_k thr_k / 2^32 -- the exact mean of the count the kernel draws
+ * -- and, when drift_out is not NULL, the compensated drift mu'_i = fl32(mu_i - b_i fl32(mean) mean_count) of the [n_assets] drift
+ * mu (mu_i itself where b_i or the product is 0). */
+int mcp_jump_consts(const mcp_jumps *j, int n_assets, const float *mu,
+                    uint32_t *thr_out /* [MCP_MAX_JUMPS] */, double *mean_count_out, float *drift_out /* NULL or [n_assets] */);
 
 /* Antithetic pairs (SPEC.md 2.3 / 5.10): the pair statistics of one portfolio on the terminal x.  cross = sum_j (x_2j - c)(x_2j+1 - c)
  * with c the pivot of mcp_pivots; with C = cross - S1^2 / (2 n), S1 = (mean - c) n: pair_cov = C / (n_pairs - 1), pair_corr = 2 C / m2

@@ -26,6 +26,7 @@ MCP_MAX_BOOT_ROWS = 1 << 20
 MCP_MAX_T_DOF = 32
 MCP_MAX_OVERLAY_ROWS = 8
 MCP_MAX_ATTR_PORTFOLIOS = 16
+MCP_MAX_JUMPS = 8
 MCP_OVERLAY_LINEAR, MCP_OVERLAY_CALL, MCP_OVERLAY_PUT = 0, 1, 2
 MCP_COMPOUND = {"simple": 0, "log": 1}
 MCP_FLAG_NATIVE_MATH = 1
@@ -82,6 +83,12 @@ class McpFiltered(ctypes.Structure):
 class McpGarch(ctypes.Structure):
     """mcp_garch: alpha, beta and the starting variance ratio h0 of the GARCH(1,1) recurrence of SPEC.md 4.9."""
     _fields_ = [("alpha", ctypes.c_double), ("beta", ctypes.c_double), ("h0", ctypes.c_double), ("reserved", ctypes.c_uint64)]
+
+
+class McpJumps(ctypes.Structure):
+    """mcp_jumps: intensity, mean and std of the market jump of SPEC.md 2.5 and the [N] binary32 loadings (NULL: all ones)."""
+    _fields_ = [("intensity", ctypes.c_double), ("mean", ctypes.c_double), ("std", ctypes.c_double), ("loading", ctypes.c_void_p),
+                ("reserved", ctypes.c_int32)]
 
 
 class McpCashflow(ctypes.Structure):
@@ -172,6 +179,9 @@ SIGNATURES = {
     "mcp_simulate_filtered": (_int, [_vp, _PP, ctypes.POINTER(McpFiltered), ctypes.POINTER(McpGarch), _vp, _u64, _u64, _u64, _int, _vp,
                                      _int, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mcp_filtered_pivots": (_int, [_PP, ctypes.POINTER(McpFiltered), _f32p, _f64p]),
+    "mcp_simulate_jumps": (_int, [_vp, _PP, ctypes.POINTER(McpJumps), _vp, _vp, _vp, _u64, _u64, _u64, _int, _vp, _int, _vp, _vp, _vp,
+                                  _vp, _vp, _vp, _vp, _vp]),
+    "mcp_jump_consts": (_int, [ctypes.POINTER(McpJumps), _int, _vp, _vp, ctypes.POINTER(ctypes.c_double), _vp]),
     "mcp_simulate_attribution": (_int, [_vp, _PP, ctypes.POINTER(McpGarch), ctypes.POINTER(McpStudentT), _vp, _vp, _vp, _u64, _u64, _u64,
                                         _vp, _vp, _vp, _vp, _vp]),
     "mcp_simulate_antithetic": (_int, [_vp, _PP, ctypes.POINTER(McpGarch), ctypes.POINTER(McpStudentT), _vp, _vp, _vp, _u64, _u64, _u64,
@@ -329,6 +339,28 @@ def filtered_pivots(prm: McpParams, mu: np.ndarray, resid: np.ndarray, shock: np
     ft = make_filtered(mu, resid, shock, 1.0)
     check(lib().mcp_filtered_pivots(ctypes.byref(prm), ctypes.byref(ft), W, out))
     return out
+
+
+def make_jumps(intensity: float, mean: float, std: float, loading: np.ndarray | None = None) -> McpJumps:
+    """mcp_jumps; `loading` is None (all ones) or a C-contiguous binary32 [N] array (the caller keeps it alive for the call)."""
+    if loading is not None and (loading.dtype != np.float32 or loading.ndim != 1 or not loading.flags.c_contiguous):
+        raise ValueError("jump loadings must be a C-contiguous float32 [N] array")
+    return McpJumps(float(intensity), float(mean), float(std), loading.ctypes.data_as(ctypes.c_void_p) if loading is not None else None, 0)
+
+
+def jump_consts(intensity: float, mean: float, std: float, loading=None, mu=None, n_assets: int | None = None):
+    """(thr uint32 [8], mean_count, drift float32 [N] or None): the host constants of SPEC.md 2.5 (include/mcport.h,
+    mcp_jump_consts), pure host arithmetic.  `mu` [N]: also the compensated drift."""
+    ld = np.ascontiguousarray(loading, np.float32) if loading is not None else None
+    mu32 = np.ascontiguousarray(mu, np.float32) if mu is not None else None
+    n = mu32.size if mu32 is not None else ld.size if ld is not None else int(n_assets or 1)
+    thr = np.zeros(MCP_MAX_JUMPS, np.uint32)
+    mean_count = ctypes.c_double()
+    drift = np.zeros(n, np.float32) if mu32 is not None else None
+    jp = make_jumps(intensity, mean, std, ld)
+    ptr = lambda a: a.ctypes.data_as(_vp) if a is not None else None   # noqa: E731
+    check(lib().mcp_jump_consts(ctypes.byref(jp), n, ptr(mu32), ptr(thr), ctypes.byref(mean_count), ptr(drift)))
+    return thr, mean_count.value, drift
 
 
 def bootstrap_pivots(prm: McpParams, rows: np.ndarray, W: np.ndarray, block: float = 1.0) -> np.ndarray:

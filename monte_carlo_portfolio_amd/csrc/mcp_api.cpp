@@ -232,6 +232,51 @@ int check_garch(const mcp_params* prm, const mcp_garch* g) {
   return MCP_OK;
 }
 
+// SPEC.md 2.5: the host constants of a jump request, binary64 in the spec's order -- thr[k-1] = clamp(floor((1 - cum_k) 2^32), 0,
+// 2^32 - 1) with cum_k the Poisson(lambda) mass below k, E = sum_k thr_k / 2^32 (the exact mean of the truncated count the kernel
+// draws), m = fl32(mean), s = fl32(std)
+struct JumpConsts { uint32_t thr[MCP_MAX_JUMPS]; double mean_count; float m, s; };
+JumpConsts jump_consts(const mcp_jumps* j) {
+  JumpConsts c;
+  double p = std::exp(-j->intensity), cum = 0.0;
+  c.mean_count = 0.0;
+  for (int k = 1; k <= MCP_MAX_JUMPS; k++) {
+    cum = cum + p;
+    double v = std::floor((1.0 - cum) * 4294967296.0);
+    v = v < 0.0 ? 0.0 : v > 4294967295.0 ? 4294967295.0 : v;
+    c.thr[k - 1] = (uint32_t)v;
+    c.mean_count += (double)c.thr[k - 1] / 4294967296.0;
+    p = p * j->intensity / (double)k;
+  }
+  c.m = (float)j->mean;
+  c.s = (float)j->std;
+  return c;
+}
+// SPEC.md 2.5: the compensated drift mu'_i = (d == 0 or b_i == 0) ? mu_i : fl32(mu_i - b_i d), d = (double)m E: E[r] stays mu
+void jump_drift(const mcp_jumps* j, const JumpConsts& c, int N, const float* mu, float* out) {
+  const double d = (double)c.m * c.mean_count;
+  for (int i = 0; i < N; i++) {
+    const float b = j->loading ? j->loading[i] : 1.0f;
+    out[i] = (d == 0.0 || b == 0.0f) ? mu[i] : (float)((double)mu[i] - (double)b * d);
+  }
+}
+
+// SPEC.md 2.5: intensity, mean, std and the loadings finite, before and after rounding to binary32; 0 <= intensity <= 1; std >= 0;
+// reserved == 0
+int check_jumps(int n_assets, const mcp_jumps* j) {
+  if (!j) return fail(MCP_E_ARG, "jumps is NULL");
+  if (j->reserved != 0) return fail(MCP_E_ARG, "jumps reserved=%d must be 0", j->reserved);
+  if (!std::isfinite(j->intensity) || !std::isfinite(j->mean) || !std::isfinite(j->std))
+    return fail(MCP_E_ARG, "jumps intensity=%g, mean=%g, std=%g must be finite", j->intensity, j->mean, j->std);
+  if (!std::isfinite((float)j->intensity) || !std::isfinite((float)j->mean) || !std::isfinite((float)j->std))
+    return fail(MCP_E_ARG, "jumps intensity=%g, mean=%g, std=%g must be finite in binary32", j->intensity, j->mean, j->std);
+  if (!(j->intensity >= 0.0 && j->intensity <= 1.0)) return fail(MCP_E_ARG, "jumps intensity=%g outside [0, 1]", j->intensity);
+  if (!(j->std >= 0.0)) return fail(MCP_E_ARG, "jumps std=%g must be >= 0", j->std);
+  for (int i = 0; j->loading && i < n_assets; i++)
+    if (!std::isfinite(j->loading[i])) return fail(MCP_E_ARG, "jumps loading, asset %d is not finite", i);
+  return MCP_OK;
+}
+
 // SPEC.md 2.4: the filtered rows -- mu [N], resid [R][N] and shock [R] finite binary32 values, every shock >= 0, 1..MCP_MAX_BOOT_ROWS
 // rows, 1 <= b <= +inf, reserved == 0
 int check_filtered(const mcp_params* prm, const mcp_filtered* f) {
@@ -396,6 +441,8 @@ struct Request {
   const mcp_overlay* ov = nullptr;
   bool garch = false;                   // SPEC.md 4.9: the variance recurrence `gv` (SRC_GAUSS or SRC_T)
   const mcp_garch* gv = nullptr;
+  bool jumps = false;                   // SPEC.md 2.5 / 4.12: the market jump `jp` on top of SRC_GAUSS
+  const mcp_jumps* jp = nullptr;
   bool dd = false;                      // SPEC.md 4.2 / 5.1: the drawdown of every path
   bool hz = false;                      // SPEC.md 4.3 / 5.2: the values after H steps, statistics at alpha and at L levels
   int H = 0, L = 0;
@@ -463,6 +510,7 @@ struct Launch {
   const float* d_rows = nullptr;        // bootstrap: [R][N4], zero-padded
   const float* d_flows = nullptr;       // cash flows: [n_steps]
   const char* d_overlay = nullptr;      // overlay: [rows][row_begin N4 + 1][spot N4] (overlay_pack)
+  const float* d_loading = nullptr;     // jumps: [N4] loadings, zero-padded
   bool attr = false;                    // the attribution walk (SPEC.md 4.10): FAM_AT instead of the request's own family
   const double* d_var = nullptr;        // attribution: [K] VaRs
   double* d_cross = nullptr;            // antithetic pairs: [K][path_grid(n_paths / 2)] cross partials
@@ -494,7 +542,16 @@ int check_request(const mcp_params* prm, const Request& rq, uint64_t n_paths, co
   }
   if (rq.overlay && (rc = check_overlay(prm, rq.ov))) return rc;
   if (rq.garch && (rc = check_garch(prm, rq.gv))) return rc;
+  if (rq.jumps && (rc = check_jumps(prm->n_assets, rq.jp))) return rc;
   const bool logc = prm->compounding != MCP_COMPOUND_SIMPLE;
+  if (rq.jumps) {                                              // SPEC.md 4.12: what the jump-diffusion is not combined with
+    if (logc) return fail(MCP_E_UNSUPPORTED, "jump-diffusion paths compound simply (no log compounding)");
+    if (rq.src != SRC_GAUSS || rq.st || rq.garch)
+      return fail(MCP_E_UNSUPPORTED, "jumps are not combined with Student-t draws, GARCH, bootstrap or filtered rows");
+    if (rq.rebalanced || rq.cash || rq.overlay || rq.attr || rq.anti)
+      return fail(MCP_E_UNSUPPORTED, "jumps are not combined with rebalancing, cash flows, the overlay, the attribution or antithetic pairs");
+    if (ln) return fail(MCP_E_UNSUPPORTED, "jumps are not wired into mcp_launch_paths*");
+  }
   if (rq.src == SRC_FHS) {                                     // SPEC.md 2.4 / 4.11: the rows, the triple, then what it is not combined with
     if ((rc = check_filtered(prm, rq.filt))) return rc;
     if ((rc = check_garch(prm, rq.gv))) return rc;
@@ -518,7 +575,8 @@ int check_request(const mcp_params* prm, const Request& rq, uint64_t n_paths, co
   if (rq.src == SRC_T && logc)
     return fail(MCP_E_UNSUPPORTED, "Student-t paths compound simply (log compounding: expm1(S) has no finite mean under t steps)");
   if (prm->flags & (MCP_FLAG_FOLD | MCP_FLAG_NATIVE_MATH)) {   // the fast steps exist for plain Gaussian walks only
-    const char* who = rq.garch             ? "GARCH paths run on the spec's normals and the unfolded recurrence"
+    const char* who = rq.jumps             ? "jump-diffusion paths run on the spec's normals and the unfolded recurrence"
+                      : rq.garch           ? "GARCH paths run on the spec's normals and the unfolded recurrence"
                       : rq.overlay         ? "overlaid paths run on the unfolded recurrence and the spec's normals"
                       : rq.cash            ? "paths with cash flows run on the unfolded recurrence and the spec's normals"
                       : rq.rebalanced      ? "rebalanced paths run on the unfolded recurrence and the spec's normals"
@@ -1036,6 +1094,16 @@ static mcp::GarchArgs garch_block(const mcp_garch* g, int n_assets) {
   gv.pad = 0;
   return gv;
 }
+// SPEC.md 2.5: the thresholds and the binary32 jump law; the loadings sit behind the launch's packed block
+static mcp::JumpArgs jump_block(const Request& rq, const Launch& ln) {
+  const JumpConsts c = jump_consts(rq.jp);
+  mcp::JumpArgs jp;
+  jp.loading = ln.d_loading;
+  for (int k = 0; k < MCP_MAX_JUMPS; k++) jp.thr[k] = c.thr[k];
+  jp.m = c.m;
+  jp.s = c.s;
+  return jp;
+}
 static mcp::OverlayArgs overlay_block(const Request& rq, const Launch& ln, int n_assets) {
   mcp::OverlayArgs ov;
   const size_t row_bytes = (size_t)rq.ov->n_rows * sizeof(mcp_overlay_row);
@@ -1066,7 +1134,7 @@ static mcp::AttrArgs attr_block(const Launch& ln, int n_assets) {
 static int launch_paths_impl(const mcp_params* prm, const Request& rq, const Launch& ln) {
   const int N = prm->n_assets, nb = (N + 3) / 4;
   const int K = prm->n_portfolios;
-  const bool plain = rq.src == SRC_GAUSS && !rq.dd && !rq.hz && !rq.rebalanced && !rq.cash && !rq.overlay && !rq.garch;
+  const bool plain = rq.src == SRC_GAUSS && !rq.dd && !rq.hz && !rq.rebalanced && !rq.cash && !rq.overlay && !rq.garch && !rq.jumps;
   mcp::PathLaunchArgs s = {};             // every block the request does not carry stays empty
   mcp::PathArgs& a = s.hz;
   const float4* tables = nullptr;
@@ -1136,6 +1204,7 @@ static int launch_paths_impl(const mcp_params* prm, const Request& rq, const Lau
   if (rq.overlay) s.ov = overlay_block(rq, ln, N);
   if (rq.rebalanced) { s.period = rq.reb->period; s.cost = (float)rq.reb->cost; }
   if (rq.src == SRC_FHS) s.fh = filt_block(rq, ln, N);
+  if (rq.jumps) s.jp = jump_block(rq, ln);
   mcp::PathKernel k = {};
   k.logc = prm->compounding == MCP_COMPOUND_LOG;
   k.fh = rq.src == SRC_FHS;
@@ -1156,6 +1225,7 @@ static int launch_paths_impl(const mcp_params* prm, const Request& rq, const Lau
     k.family = rq.overlay ? mcp::FAM_OV : rq.cash ? mcp::FAM_CF : rq.rebalanced ? mcp::FAM_REB : rq.dd ? mcp::FAM_DD : rq.hz ? mcp::FAM_HZ : mcp::FAM_PLAIN;
     k.dd = rq.overlay && rq.dd;
     k.gv = rq.garch;
+    k.jp = rq.jumps;
     k.kt8 = K > 1;
     k.native = (prm->flags & MCP_FLAG_NATIVE_MATH) != 0;
     k.fold = (prm->flags & MCP_FLAG_FOLD) != 0;
@@ -1689,7 +1759,7 @@ int run_tile(mcp_ctx* c, const mcp_params* prm, const Request& rq, uint64_t seed
     Shard& sh = c->sh[s];
     HIP_TRY(hipSetDevice(sh.device));
     tp[s].n_portfolios = j.kt;
-    const size_t plen = mcp_packed_len(N, j.kt), pn = j.pn ? j.pn : 1;
+    const size_t plen = mcp_packed_len(N, j.kt) + (rq.jumps ? (size_t)n4_of(N) : 0), pn = j.pn ? j.pn : 1;   // jumps: the loadings behind it
     const int rows = rq.hz ? rq.H * j.kt : j.kt;  // horizon calls: the work buffers also serve the H*kt rows of the horizon selects
     for (int w = 0; w < MCP_WS_COUNT; w++) {      // only the histogram and the select state must start zeroed
       const size_t need = std::max(mcp_ws_bytes(w, j.kt, pn), mcp_ws_bytes(w, rows, pn));
@@ -1720,7 +1790,11 @@ int run_tile(mcp_ctx* c, const mcp_params* prm, const Request& rq, uint64_t seed
   // filtered rows (SPEC.md 4.11): their drift in the packed block, the Cholesky factor zero
   const bool boot = rq.src == SRC_BOOT, fhs = rq.src == SRC_FHS;
   const std::vector<float> zmu(boot ? N : 0, 0.0f), zchol(boot || fhs ? (size_t)N * N : 0, 0.0f);
-  const float* mu = boot ? zmu.data() : fhs ? rq.filt->mu : rq.mu;
+  // jumps (SPEC.md 2.5): the compensated drift in the packed block (the pivots keep the drift itself), the loadings behind the block
+  std::vector<float> jmu(rq.jumps ? N : 0);
+  if (rq.jumps) jump_drift(rq.jp, jump_consts(rq.jp), N, rq.mu, jmu.data());
+  const size_t n_load = rq.jumps ? (size_t)n4_of(N) : 0;
+  const float* mu = boot ? zmu.data() : fhs ? rq.filt->mu : rq.jumps ? jmu.data() : rq.mu;
   const float* chol = boot || fhs ? zchol.data() : rq.chol;
   std::vector<double> bm, bs2, rmu(rq.rebalanced || fhs ? N : 0), cm;
   if (rq.rebalanced) reb_means(N, rq.mu, boot ? rq.boot : nullptr, rmu.data());
@@ -1742,6 +1816,7 @@ int run_tile(mcp_ctx* c, const mcp_params* prm, const Request& rq, uint64_t seed
     } else {
       const float* Wt = rq.W + (size_t)j.k0 * N;
       if ((rc = mcp_pack_params(N, j.kt, mu, chol, Wt, sh.h_packed.p, plen))) return rc;
+      for (size_t i = 0; i < n_load; i++) sh.h_packed.p[plen + i] = (int)i < N ? (rq.jp->loading ? rq.jp->loading[i] : 1.0f) : 0.0f;
       if (boot && !rq.rebalanced) {
         bm.resize((size_t)j.kt);
         bs2.resize((size_t)j.kt);
@@ -1760,7 +1835,7 @@ int run_tile(mcp_ctx* c, const mcp_params* prm, const Request& rq, uint64_t seed
           return rc;
       if (exchange) { shared_packed = sh.h_packed.p; shared_pivot = sh.h_pivot.p; shared_hz_pivot = sh.hz.h_pivot.p; }
     }
-    HIP_TRY(hipMemcpyAsync(sh.packed.p, src, plen * sizeof(float), hipMemcpyHostToDevice, sh.stream));
+    HIP_TRY(hipMemcpyAsync(sh.packed.p, src, (plen + n_load) * sizeof(float), hipMemcpyHostToDevice, sh.stream));
     HIP_TRY(hipMemcpyAsync(sh.ws[MCP_WS_PIVOT], psrc, (size_t)j.kt * sizeof(double), hipMemcpyHostToDevice, sh.stream));
     if (rq.hz) HIP_TRY(hipMemcpyAsync(sh.hz.pivot.p, hpsrc, (size_t)rq.H * j.kt * sizeof(double), hipMemcpyHostToDevice, sh.stream));
     if (j.pn) {
@@ -1773,6 +1848,7 @@ int run_tile(mcp_ctx* c, const mcp_params* prm, const Request& rq, uint64_t seed
       ln.d_rows = sh.boot.p;
       ln.d_flows = sh.cf.flows.p;
       ln.d_overlay = sh.overlay.p;
+      ln.d_loading = sh.packed.p + plen;
       ln.d_cross = sh.pr.partials.p;
       if ((rc = launch_paths_impl(&tp[s], rq, ln))) return rc;
       if (rq.anti) {                                         // SPEC.md 5.10: the workgroups' cross partials in block order
@@ -2176,6 +2252,31 @@ int mcp_simulate_garch(mcp_ctx* c, const mcp_params* prm, const mcp_garch* g, co
   rq.dd_stats_out = dd_stats_out;
   ask_horizons(rq, n_horizons != 0, n_horizons, horizons, n_levels, levels, horizon_out, hz_stats_out, bands_out);
   return simulate_checked(c, prm, rq, seed, path_begin, n_paths);
+}
+
+int mcp_simulate_jumps(mcp_ctx* c, const mcp_params* prm, const mcp_jumps* j, const float* mu, const float* chol, const float* W,
+                       uint64_t seed, uint64_t path_begin, uint64_t n_paths, int n_horizons, const int32_t* horizons, int n_levels,
+                       const double* levels, float* terminal_out, mcp_stats* stats_out, float* mdd_out, mcp_stats* dd_stats_out,
+                       float* horizon_out, mcp_stats* hz_stats_out, double* bands_out) {
+  Request rq = host_request(SRC_GAUSS, mu, chol, W, terminal_out, stats_out);
+  rq.jumps = true;
+  rq.jp = j;
+  rq.dd = dd_stats_out != nullptr;
+  rq.mdd_out = mdd_out;
+  rq.dd_stats_out = dd_stats_out;
+  ask_horizons(rq, n_horizons != 0, n_horizons, horizons, n_levels, levels, horizon_out, hz_stats_out, bands_out);
+  return simulate_checked(c, prm, rq, seed, path_begin, n_paths);
+}
+
+int mcp_jump_consts(const mcp_jumps* j, int n_assets, const float* mu, uint32_t* thr_out, double* mean_count_out, float* drift_out) {
+  if (n_assets < 1 || n_assets > MCP_MAX_ASSETS) return fail(MCP_E_ARG, "n_assets=%d outside [1,%d]", n_assets, MCP_MAX_ASSETS);
+  if (int rc = check_jumps(n_assets, j)) return rc;
+  if (!thr_out || !mean_count_out || (drift_out && !mu)) return fail(MCP_E_ARG, "NULL pointer");
+  const JumpConsts c = jump_consts(j);
+  for (int k = 0; k < MCP_MAX_JUMPS; k++) thr_out[k] = c.thr[k];
+  *mean_count_out = c.mean_count;
+  if (drift_out) jump_drift(j, c, n_assets, mu, drift_out);
+  return MCP_OK;
 }
 
 int mcp_simulate_filtered(mcp_ctx* c, const mcp_params* prm, const mcp_filtered* filt, const mcp_garch* g, const float* W, uint64_t seed,

@@ -95,7 +95,7 @@ __device__ __forceinline__ const __attribute__((address_space(4))) A* kernarg() 
   template <class A> struct has_##m<A, std::void_t<decltype(A::m)>> : std::true_type {};
 MCP_HAS_MEMBER(hz) MCP_HAS_MEMBER(mdd) MCP_HAS_MEMBER(bt) MCP_HAS_MEMBER(st) MCP_HAS_MEMBER(gv) MCP_HAS_MEMBER(cf)
 MCP_HAS_MEMBER(ov) MCP_HAS_MEMBER(at) MCP_HAS_MEMBER(period) MCP_HAS_MEMBER(pr)
-MCP_HAS_MEMBER(fh) MCP_HAS_MEMBER(p_hi)
+MCP_HAS_MEMBER(fh) MCP_HAS_MEMBER(p_hi) MCP_HAS_MEMBER(jp)
 #undef MCP_HAS_MEMBER
 
 struct PathArgs {
@@ -201,6 +201,27 @@ typedef const __attribute__((address_space(4))) GarchArgs* cgarch_p;
 template <class A>
 __device__ __forceinline__ cgarch_p garch_args(const A&) {
   if constexpr (has_gv<A>::value) return &kernarg<A>()->gv;
+  else return nullptr;
+}
+
+// Merton jump-diffusion (SPEC.md 2.5 / 4.12): one market jump J per path and step, drawn from one Philox block on counter stream 3
+// -- the count n = #{k : x0 < thr[k]} (thr[k] = floor(2^32 P(Poisson >= k + 1)), at most MCP_MAX_JUMPS = 8 jumps), the size from
+// Z(x1) -- and added to every asset through its loading: row i starts at fma(b_i, J, mu'_i), mu' the compensated drift the host
+// packs in place of mu.  `loading` is zero-padded to N4.  Appended to the arguments of the plain, drawdown and horizon kernels
+// (mc_paths_j_kernel, mc_paths_j_dd_kernel, mc_paths_j_hz_kernel).
+struct JumpArgs {
+  const float* __restrict__ loading;  // [N4] device copy
+  uint32_t thr[8];
+  float m, s;                         // m32 = fl32(mean), s32 = fl32(std) of one jump
+};
+struct PathArgsJ : PathArgs { JumpArgs jp; };
+struct PathArgsJDD : PathArgsDD { JumpArgs jp; };
+struct PathArgsJHZ : PathArgsHZ { JumpArgs jp; };
+// The jump block of a j kernel's launch, read where it is used (kernarg).
+typedef const __attribute__((address_space(4))) JumpArgs* cjump_p;
+template <class A>
+__device__ __forceinline__ cjump_p jump_args(const A&) {
+  if constexpr (has_jp<A>::value) return &kernarg<A>()->jp;
   else return nullptr;
 }
 
@@ -352,6 +373,7 @@ struct PathLaunchArgs {
   float cost;
   PairArgs pr;
   FiltArgs fh;
+  JumpArgs jp;
 };
 template <class A>
 inline A make_args(const PathLaunchArgs& s) {
@@ -368,6 +390,7 @@ inline A make_args(const PathLaunchArgs& s) {
   if constexpr (has_period<A>::value) { x.period = s.period; x.cost = s.cost; }
   if constexpr (has_pr<A>::value) x.pr = s.pr;
   if constexpr (has_fh<A>::value) x.fh = s.fh;
+  if constexpr (has_jp<A>::value) x.jp = s.jp;
   if constexpr (has_p_hi<A>::value) { x.p_hi = (uint32_t)(s.hz.path_begin >> 32); x.pad = 0u; }
   return x;
 }
@@ -464,13 +487,15 @@ constexpr int PATH_BLOCK = 256;
 // the peak and drawdown, the stores and the epilogue -- carries a second member that sees -z (SPEC.md 2.3 / 5.10).  UHI: the high
 // counter word p_hi is one value for the whole launch, a kernel argument: Philox rounds 1 and 2 run on the SALU where their operands
 // are wave-uniform (philox4x32_10_uhi), the drift's LDS address and the transform's two scaling constants sit in VGPRs across the walk
-// instead of being formed every step; the draws, and every result, are those of the kernel without it.  Every kernel
+// instead of being formed every step; the draws, and every result, are those of the kernel without it.  JP: before the asset normals one
+// more Philox block on counter stream 3 gives the step's market jump J (SPEC.md 2.5), and every row pair's accumulator starts at
+// fma(b, J, mu') instead of mu, one packed fma with the loadings b from the LDS slot behind the drift (SPEC.md 4.12).  Every kernel
 // below is the body in mcp_paths_body.inc under its own flags F: it names the flags it sets, the rest are PathFlagsOff's.  F is a
 // local class, which may not have static data members, so it sets its flags as enumerators of an `enum : bool`; they hide the
 // defaults' names and read as the same constant expressions.
 struct PathFlagsOff {
   static constexpr bool NATIVE = false, FOLD = false, LOGC = false, DD = false, HZ = false, BOOT = false, BLDS = false, REB = false,
-                        STT = false, CF = false, OV = false, GV = false, AT = false, ANTI = false, FH = false, UHI = false;
+                        STT = false, CF = false, OV = false, GV = false, AT = false, ANTI = false, FH = false, UHI = false, JP = false;
 };
 
 // __launch_bounds__ 2nd argument of a path kernel: the MCP_MIN_WAVES* above for N <= 16 and one path per lane, by the kind of
@@ -578,6 +603,26 @@ __global__ void MCP_BOUNDS(BK_PATHS) mc_paths_g_dd_kernel(const PathArgsGDD a) {
 template <int NB, int KT, int PPT>
 __global__ void MCP_BOUNDS(BK_PATHS) mc_paths_g_hz_kernel(const PathArgsGHZ a) {
   struct F : PathFlagsOff { enum : bool { HZ = true, STT = true, GV = true }; };
+#include "mcp_paths_body.inc"
+}
+
+// The jump-diffusion kernels (SPEC.md 2.5 / 4.12; simple compounding, unfolded recurrence, Gaussian draws): mc_paths_kernel,
+// mc_paths_dd_kernel and mc_paths_hz_kernel with the step's market jump added to every asset through its loading.  V_T, the
+// drawdown, the horizons and the fused epilogue as there.  They keep the plain kernel's launch bounds: no listing shows scratch in
+// a step loop (profiles/jump_isa.txt).
+template <int NB, int KT, int PPT>
+__global__ void MCP_BOUNDS(BK_PATHS) mc_paths_j_kernel(const PathArgsJ a) {
+  struct F : PathFlagsOff { enum : bool { JP = true }; };
+#include "mcp_paths_body.inc"
+}
+template <int NB, int KT, int PPT>
+__global__ void MCP_BOUNDS(BK_PATHS) mc_paths_j_dd_kernel(const PathArgsJDD a) {
+  struct F : PathFlagsOff { enum : bool { JP = true, DD = true }; };
+#include "mcp_paths_body.inc"
+}
+template <int NB, int KT, int PPT>
+__global__ void MCP_BOUNDS(BK_PATHS) mc_paths_j_hz_kernel(const PathArgsJHZ a) {
+  struct F : PathFlagsOff { enum : bool { JP = true, HZ = true }; };
 #include "mcp_paths_body.inc"
 }
 

@@ -4,10 +4,12 @@
 // walk is the one loop it always was.  In scope: the template parameters NB, KT, PPT, the flags F (PathFlagsOff or a struct
 // derived from it) and the kernel argument `a` (PathArgs or a struct that starts with one).
   constexpr bool NATIVE = F::NATIVE, FOLD = F::FOLD, LOGC = F::LOGC, DD = F::DD, HZ = F::HZ, BOOT = F::BOOT, BLDS = F::BLDS, REB = F::REB,
-                 STT = F::STT, CF = F::CF, OV = F::OV, GV = F::GV, AT = F::AT, ANTI = F::ANTI, FH = F::FH, UHI = F::UHI;
-  static_assert(!UHI || (KT == 1 && PPT == 1 && !(NATIVE || FOLD || DD || HZ || BOOT || REB || STT || CF || OV || GV || AT || ANTI || FH)),
+                 STT = F::STT, CF = F::CF, OV = F::OV, GV = F::GV, AT = F::AT, ANTI = F::ANTI, FH = F::FH, UHI = F::UHI, JP = F::JP;
+  static_assert(!UHI || (KT == 1 && PPT == 1 && !(NATIVE || FOLD || DD || HZ || BOOT || REB || STT || CF || OV || GV || AT || ANTI || FH || JP)),
                 "uniform high counter word: the plain Gaussian walk of one portfolio only");
   static_assert(!FH || (BOOT && HZ && !(LOGC || REB || CF || STT || GV || OV || AT || DD)), "filtered rows: the bootstrap's segmented walk only");
+  static_assert(!JP || !(NATIVE || FOLD || LOGC || BOOT || REB || STT || CF || OV || GV || AT || ANTI || FH),
+                "jump-diffusion: the Gaussian walk, its drawdown and its horizons, simple compounding only");
   constexpr int N4 = 4 * NB;
   // ANTI (SPEC.md 2.3): a lane's PPT draws feed EM = 2 PPT members -- slot e < PPT walks on z[e], slot PPT + e on -z[e]; p, live and
   // the counters are per draw (a.path_begin and a.n_paths count pairs), the members 2 p and 2 p + 1 are adjacent in the output rows
@@ -48,6 +50,11 @@
   float* const s_par0 = (float*)&s_tab[0];
   if constexpr (LDS_MU) {
     if (threadIdx.x < N4) { s_par0[threadIdx.x] = mu[threadIdx.x]; if (LDS_W) s_par0[N4 + threadIdx.x] = Wk[threadIdx.x]; }
+  }
+  // JP: the loadings b (SPEC.md 4.12) take the N4 floats behind the drift, the slot the weights of LDS_W would take
+  constexpr bool LDS_B = JP && LDS_MU && !LDS_W;
+  if constexpr (LDS_B) {
+    if (threadIdx.x < N4) s_par0[N4 + threadIdx.x] = ((cfloat_p)jump_args(a)->loading)[threadIdx.x];
   }
   // statistics epilogue (N3): per-wave moment accumulators and the digit-0 histogram of one portfolio at a time
   __shared__ uint32_t s_hist[MCP_SELECT_BINS];

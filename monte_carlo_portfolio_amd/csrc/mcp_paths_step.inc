@@ -12,7 +12,8 @@
 // the update of V (DD: of the peak and drawdown) run for EM = 2 PPT members, member PPT + e on -z[e] (SPEC.md 2.3): a second fma
 // chain from the same mu2 -- never a shared L z, mu + L z and mu - L z round differently.  FH: the gathered row is a residual, r_i = fma(sqrt(h),
 // E_ji, mu_i) with mu from the packed block by scalar loads, and after the update of V h moves on the row's shock (SPEC.md 4.11).  In scope: everything mcp_paths_body.inc
-// declares before its step loops, and t.  UHI: the same step with p_hi a scalar (philox4x32_10_uhi), the drift read through the LDS address
+// declares before its step loops, and t.  JP: one more Philox block on counter stream 3 before the asset normals gives
+// the step's market jump J, and the row pair's accumulator starts at fma(b, J, mu) (SPEC.md 2.5 / 4.12).  UHI: the same step with p_hi a scalar (philox4x32_10_uhi), the drift read through the LDS address
 // par_lds instead of the opaque zero offset, and the blocks scheduled one at a time.
       float rho[EM][KT];
       float fsh[PPT];                                  // FH: the shock s_j of the step's row (SPEC.md 2.4)
@@ -84,6 +85,25 @@
       if constexpr (UHI) {                                         // the address itself, made opaque in place: no instruction
         asm volatile("" : "+v"(par_lds));
         s_par = (const float*)par_lds;
+      }
+      float jmp[PPT];                                  // JP: the step's market jump J of SPEC.md 2.5
+      if constexpr (JP) {
+        // SPEC.md 2.5: one Philox block on counter (t, 3, p_lo, p_hi); n = #{k : x0 < thr_k} (uint32 compares against wave-uniform
+        // thresholds, scalar loads), g = Z(x1); J = fma(fl32(sqrt(nf) s32), g, fl32(nf m32)), the square root IEEE, correctly rounded.
+        // Formed before the asset normals: only J stays live while they are.
+        const cjump_p jk = jump_args(a);
+        const float j_m = jk->m, j_s = jk->s;
+#pragma unroll
+        for (int e = 0; e < PPT; e++) {
+          uint32_t x[4];
+          philox4x32_10((uint32_t)t, 3u, plo[e], phi[e], ks, x);
+          uint32_t n = 0u;
+#pragma unroll
+          for (int k = 0; k < 8; k++) n += x[0] < jk->thr[k] ? 1u : 0u;
+          const float nf = (float)n;
+          const float g = normal_icdf(x[1], s_tab, kc);
+          jmp[e] = fma32(sqrtf(nf) * j_s, g, nf * j_m);
+        }
       }
       float z[PPT][N4];
       float st_s[PPT];                                 // STT: the step's scale s of SPEC.md 2.2 (GV: u of SPEC.md 4.9)
@@ -188,8 +208,20 @@
         f32x2 mu2;
         if constexpr (LDS_MU) mu2 = *(const f32x2*)&s_par[2 * m];
         else mu2 = f32x2{mu[2 * m], mu[2 * m + 1]};
+        if constexpr (JP) {                            // SPEC.md 4.12: acc = fma(b_i, J, mu'_i), one packed fma per row pair
+          f32x2 b2;
+          if constexpr (LDS_B) {
+            b2 = *(const f32x2*)&s_par[N4 + 2 * m];
+          } else {
+            const cfloat_p jb = (cfloat_p)jump_args(a)->loading;
+            b2 = f32x2{jb[2 * m], jb[2 * m + 1]};
+          }
+#pragma unroll
+          for (int e = 0; e < EM; e++) acc[e] = __builtin_elementwise_fma(b2, (f32x2){jmp[e % PPT], jmp[e % PPT]}, mu2);
+        } else {
 #pragma unroll
         for (int e = 0; e < EM; e++) acc[e] = mu2;
+        }
 #pragma unroll
         for (int j = 0; j <= 2 * m + 1; j++) {
           const f32x2 l2 = {Lp[2 * m * (m + 1) + 2 * j], Lp[2 * m * (m + 1) + 2 * j + 1]};   // (L[2m][j], L[2m+1][j])

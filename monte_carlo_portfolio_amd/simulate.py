@@ -65,8 +65,8 @@ class Context:
 
     def _call(self, prm: _ffi.McpParams, W, seed: int, path_begin: int, n_paths: int, store: bool, mu=None, chol=None, rows=None,
               block: float = 1.0, dof=None, period=None, cost: float = 0.0, drawdown: bool = False, horizons=None, levels=(),
-              flows=None, target=None, overlay=None, garch=None, attribution=False, antithetic=False, filtered=None):
-        """The one library call behind every simulate_* method: GARCH volatility (garch: the (alpha, beta, h0) of check_garch), an option overlay (overlay: the triple of check_overlay), cash flows (flows, target), Student-t draws (dof), rebalancing
+              flows=None, target=None, overlay=None, garch=None, attribution=False, antithetic=False, filtered=None, jumps=None):
+        """The one library call behind every simulate_* method: market jumps (jumps: the (intensity, mean, std, loading or None) of check_jumps), GARCH volatility (garch: the (alpha, beta, h0) of check_garch), an option overlay (overlay: the triple of check_overlay), cash flows (flows, target), Student-t draws (dof), rebalancing
         (period, cost), bootstrap rows (rows, block) or Gaussian draws (mu, chol), with the drawdown or horizons.  Allocates the
         outputs that were asked for and passes NULL for the rest -> _Outputs, None where not asked for (terminal, qd,
         horizon_terminal: with `store` only; counts, hz_counts: with `flows` only; attr [K, N] records of ATTR_DTYPE and attr_counts
@@ -102,6 +102,15 @@ class Context:
             gv = _ffi.McpGarch(float(garch[0]), float(garch[1]), float(garch[2]), 0)
             rc = lib.mcp_simulate_filtered(self._h, prm_p, ctypes.byref(ft), ctypes.byref(gv), ptr(W), *walk, *hz_in, ptr(term), ptr(stats),
                                            *hz_out)
+        elif jumps is not None:
+            # SPEC.md 2.5 / 4.12: the library states the rules (check_request); Gaussian draws with the drawdown or horizons only
+            if (overlay is not None or flows is not None or period is not None or bt is not None or dof is not None or attribution
+                    or antithetic or garch is not None):
+                raise ValueError("jumps are not combined with overlay, cashflow, rebalance, bootstrap rows, dof, garch, attribution or "
+                                 "antithetic")
+            jp = _ffi.make_jumps(*jumps)
+            rc = lib.mcp_simulate_jumps(self._h, prm_p, ctypes.byref(jp), ptr(mu), ptr(chol), ptr(W), *walk, *hz_in, ptr(term), ptr(stats),
+                                        ptr(raw), ptr(dd_stats), *hz_out)
         elif antithetic:
             # the library states the rules (check_request): everything but plain, Student-t and GARCH draws is MCP_E_UNSUPPORTED
             if overlay is not None or flows is not None or period is not None or bt is not None or attribution:
@@ -222,6 +231,15 @@ class Context:
         for are None."""
         return self._call(prm, W, seed, path_begin, n_paths, store, mu=mu, chol=chol, dof=dof, drawdown=drawdown, horizons=horizons,
                           levels=levels, garch=garch)
+
+    def simulate_jumps(self, prm: _ffi.McpParams, jumps, mu, chol, W, seed: int, path_begin: int, n_paths: int, store: bool,
+                       drawdown: bool = False, horizons=None, levels=()):
+        """simulate() / simulate_drawdown() / simulate_horizons() with the market jump of SPEC.md 2.5 added to every step: `jumps`
+        is the (intensity, mean, std, loading) of check_jumps, loading None (all ones) or binary32 [N]; `chol` is the diffusive
+        factor (SPEC.md 4.12 / 5.12; include/mcport.h, mcp_simulate_jumps; simple compounding only) -> _Outputs; the entries of the
+        blocks not asked for are None."""
+        return self._call(prm, W, seed, path_begin, n_paths, store, mu=mu, chol=chol, drawdown=drawdown, horizons=horizons,
+                          levels=levels, jumps=jumps)
 
     def simulate_filtered(self, prm: _ffi.McpParams, filtered, garch, W, block: float, seed: int, path_begin: int, n_paths: int,
                           store: bool, horizons=None, levels=()):
@@ -422,6 +440,41 @@ def check_garch(garch):
     return tuple(vals)
 
 
+def check_jumps(jumps, n_assets):
+    """SPEC.md 2.5 argument rules -> None (no jumps) or (intensity, mean, std, loading): three floats and None (all ones) or the
+    binary32 [N] loadings; ValueError otherwise (not a sequence of 3 or 4 entries, a bool or a string among the numbers, a value
+    that is not finite before or after rounding to binary32, intensity outside [0, 1], std < 0, loadings of another length)."""
+    if jumps is None:
+        return None
+    msg = f"jumps must be (intensity, mean, std) or (intensity, mean, std, loading), got {jumps!r}"
+    if isinstance(jumps, (str, bytes)) or not hasattr(jumps, "__len__") or len(jumps) not in (3, 4):
+        raise ValueError(msg)
+    vals = []
+    for v in tuple(jumps)[:3]:
+        if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, float, np.integer, np.floating)):
+            raise ValueError(msg)
+        with np.errstate(over="ignore"):
+            if not np.isfinite(v) or not np.isfinite(np.float32(v)):
+                raise ValueError(f"jumps values must be finite, in binary32 too, got {jumps!r}")
+        vals.append(float(v))
+    if not 0.0 <= vals[0] <= 1.0:
+        raise ValueError(f"jumps intensity must be in [0, 1] (expected jumps per step), got {vals[0]!r}")
+    if not vals[2] >= 0.0:
+        raise ValueError(f"jumps std must be >= 0, got {vals[2]!r}")
+    loading = None
+    if len(jumps) == 4 and jumps[3] is not None:
+        try:
+            with np.errstate(over="ignore"):
+                loading = np.ascontiguousarray(np.asarray(jumps[3], np.float64).astype(np.float32)).ravel()
+        except (TypeError, ValueError):
+            raise ValueError(msg) from None
+        if np.asarray(jumps[3]).dtype == np.bool_ or loading.size != int(n_assets):
+            raise ValueError(f"jumps loading must hold one number per asset ({n_assets}), got {jumps[3]!r}")
+        if not (np.all(np.isfinite(np.asarray(jumps[3], np.float64))) and np.all(np.isfinite(loading))):
+            raise ValueError(f"jumps loading must be finite, in binary32 too, got {jumps[3]!r}")
+    return vals[0], vals[1], vals[2], loading
+
+
 def check_rebalance(rebalance, rebalance_cost):
     """SPEC.md 4.5 argument rules -> (period, cost): period None (constant weights, no rebalancing), 0 (rebalance="never": bought
     and held) or the int k >= 1 of rebalance=k (traded back to the weights every k steps); cost in [0, 1).  ValueError otherwise."""
@@ -553,7 +606,7 @@ def simulate_paths(mu, cov, weights, n_steps=252, n_paths=10_000, seed=0, v0=1.0
                    rf=0.0, alpha=0.95, devices=None, store=False, path_begin=0, chol=None,
                    native_math=False, as_array=False, fold=False, shard="auto", context=None, drawdown=False,
                    horizons=None, bands=(), rebalance=None, rebalance_cost=0.0, dof=None, cashflow=None, target=None,
-                   overlay=None, spot=None, garch=None, attribution=False, antithetic=False):
+                   overlay=None, spot=None, garch=None, attribution=False, antithetic=False, jumps=None):
     """Simulate `n_paths` correlated return paths and reduce them to risk statistics.
 
     mu [N], cov [N,N] are per-step mean and covariance (the reference's `mean_returns`, `cov_matrix`
@@ -647,7 +700,32 @@ def simulate_paths(mu, cov, weights, n_steps=252, n_paths=10_000, seed=0, v0=1.0
     draws.  Not built: antithetic with rebalance, cashflow, overlay, attribution, fold, native_math or shard="portfolios"
     (ValueError), on bootstrap paths (observed rows have no sign to flip), in simulate_sweep (call simulate_paths for the
     optimum), in PathEngine and at the mcp_launch_* level.
+
+    jumps=None (default): every step is Gaussian around mu.  jumps=(intensity, mean, std) or (intensity, mean, std, loading): Merton
+    jump-diffusion (SPEC.md 2.5 / 4.12).  Every path-step also takes a market jump J, the sum of n normal(mean, std^2) jumps with n
+    ~ Poisson(intensity) (0 <= intensity <= 1 expected jumps per step, at most 8 in one step), and asset i moves by loading_i J
+    (default: all ones): with a negative mean the assets fall harder than they rise, fall together, and fall within one step --
+    what VaR, CVaR, the drawdown and the lower fan band are most sensitive to.  mu stays the mean of every step (the drift is
+    compensated, pivots of SPEC.md 5.12) and `cov` stays the TOTAL per-step covariance: the diffusion is factored from
+    jumps.diffusion_cov(cov, jumps) = cov - Var(J) b b' (ValueError when that is not positive definite), so the call has the
+    Gaussian call's mean and covariance and differs in skew and tails; an explicit chol= is taken as the diffusive factor
+    untouched.  The asset normals are the Gaussian call's own (common random numbers with the same seed); intensity = 0 is the call
+    without it bit for bit.  fit_jumps(returns) estimates the triple and the loadings from return rows.  The result has the shape of
+    the same call without it (drawdown, horizons / bands, store, as_array, devices and shard all combine); every dict gains 'jumps'
+    {intensity, mean_count (the mean of the count the kernels draw), variance_share (the jump's share of the portfolio's one-step
+    variance)}.  Not built: jumps with dof, garch, rebalance, cashflow, overlay, attribution, antithetic, fold, native_math or
+    compounding="log" (ValueError), on bootstrap or filtered paths (the rows carry their own jumps), in PathEngine and at the
+    mcp_launch_* level; jumps with cashflow -- ruin under crash risk -- is the obvious next step.
     """
+    jv = check_jumps(jumps, len(np.atleast_1d(np.asarray(mu))))
+    if jv is not None:
+        bad = [name for name, on in (("dof", dof is not None), ("garch", garch is not None), ("rebalance", rebalance is not None),
+                                     ("cashflow", cashflow is not None), ("overlay", overlay is not None),
+                                     ("attribution", bool(attribution)), ("antithetic", bool(antithetic)), ("fold", fold),
+                                     ("native_math", native_math), ("compounding='log'", compounding == "log")) if on]
+        if bad:
+            raise ValueError("jumps need Gaussian draws, constant weights, simple compounding, the spec's normals and the unfolded "
+                             f"recurrence: not with {', '.join(bad)}")
     if not isinstance(antithetic, (bool, np.bool_)):
         raise ValueError(f"antithetic must be True or False, got {antithetic!r}")
     if antithetic:
@@ -698,13 +776,34 @@ def simulate_paths(mu, cov, weights, n_steps=252, n_paths=10_000, seed=0, v0=1.0
     if horizons is not None and (drawdown or fold or native_math):
         raise ValueError("horizons need the spec's normals and the unfolded recurrence: not with drawdown, fold or native_math")
     steps, levels = _check_walk(n_steps, horizons, bands, period, compounding, shard)
+    if jv is not None and chol is None:                    # `cov` is the total covariance: the diffusion gets what the jumps leave
+        from .jumps import diffusion_cov
+        cov = diffusion_cov(cov, jv)
     mu32, L, W = prepare_inputs(mu, cov, weights, chol)
     prm, ctx = _setup(mu32.shape[0], n_steps, W.shape[0], compounding, v0, alpha, rf, native_math, fold, devices,
                       "paths" if attribution or antithetic else shard, context)
     out = ctx._call(prm, W, int(seed), int(path_begin), int(n_paths), store, mu=mu32, chol=L, dof=dof, period=period, cost=cost,
                     drawdown=drawdown, horizons=steps, levels=levels, flows=flows, target=target, overlay=ov, garch=gv,
-                    attribution=bool(attribution), antithetic=bool(antithetic))
-    return _result(out, np.asarray(weights).ndim == 1, store, as_array, steps, levels, compounding, flows, target)
+                    attribution=bool(attribution), antithetic=bool(antithetic), jumps=jv)
+    res = _result(out, np.asarray(weights).ndim == 1, store, as_array, steps, levels, compounding, flows, target)
+    if jv is not None and not as_array:
+        for d, blk in zip([res] if isinstance(res, dict) else res, _jump_blocks(jv, L, W)):
+            d["jumps"] = blk
+    return res
+
+
+def _jump_blocks(jv, L, W):
+    """The 'jumps' block of every portfolio: the intensity asked for, the mean of the count the kernels draw and the jump's share
+    Var(J) (w.b)^2 / (w' L L' w + Var(J) (w.b)^2) of the one-step variance (0 where that is 0)."""
+    from .jumps import jump_law
+    law = jump_law(jv)
+    L64, W64 = np.tril(L).astype(np.float64), W.astype(np.float64)
+    b = np.ones(L64.shape[0]) if jv[3] is None else jv[3].astype(np.float64)
+    out = []
+    for w in W64:
+        diff, jump = float(w @ L64 @ L64.T @ w), law.var_jump * float(w @ b) ** 2
+        out.append({"intensity": jv[0], "mean_count": law.mean_count, "variance_share": jump / (diff + jump) if diff + jump > 0 else 0.0})
+    return out
 
 
 def _check_walk(n_steps, horizons, bands, period, compounding, shard):
