@@ -33,7 +33,8 @@ extern "C" {
                                     + mcp_simulate_attribution (additive, detected by symbol);
                                     + mcp_simulate_antithetic (additive, detected by symbol);
                                     + mcp_simulate_filtered, mcp_filtered_pivots (additive, detected by symbol);
-                                    + mcp_simulate_jumps, mcp_jump_consts (additive, detected by symbol) */
+                                    + mcp_simulate_jumps, mcp_jump_consts (additive, detected by symbol);
+                                    + mcp_simulate_regimes, mcp_regime_consts, mcp_regime_pivots (additive, detected by symbol) */
 #define MCP_MAX_ASSETS 64        /* thread-per-path kernels are instantiated for N4 = 4..64 */
 #define MCP_SELECT_BINS 2048     /* radix-select digit: 11 + 11 + 10 bits */
 #define MCP_MAX_HORIZONS 64      /* mcp_simulate_horizons: horizon steps per call */
@@ -399,6 +400,55 @@ int mcp_simulate_jumps(mcp_ctx *ctx, const mcp_params *prm, const mcp_jumps *j,
  * mu (mu_i itself where b_i or the product is 0). */
 int mcp_jump_consts(const mcp_jumps *j, int n_assets, const float *mu,
                     uint32_t *thr_out /* [MCP_MAX_JUMPS] */, double *mean_count_out, float *drift_out /* NULL or [n_assets] */);
+
+/* Two-regime Markov switching (Hamilton 1989; SPEC.md 2.6 / 4.13 / 5.13): every path carries a regime s_t in {0 (calm), 1 (crisis)}
+ * that moves once per step with P(0 -> 1) = p01 and P(1 -> 0) = p10, and step t draws r = mu^(s_t) + L^(s_t) z: the call's mu and
+ * chol are regime 0, mu1 [N] and chol1 [N*N, lower Cholesky factor, row-major] regime 1.  start = P(regime 1 in step 0).  Everything
+ * finite, the three probabilities in [0, 1], no NULL pointer, reserved 0. */
+typedef struct {
+    double p01, p10, start;
+    const float *mu1;
+    const float *chol1;
+    int32_t reserved;
+} mcp_regimes;
+
+/* mcp_simulate / mcp_simulate_drawdown / mcp_simulate_horizons on the two regimes of SPEC.md 2.6 (simple compounding only): one more
+ * Philox block per path-step on counter stream 4 moves the regime -- s_0 = x1 < thr_start (block of t = 0), s_{t+1} = s_t == 0 ?
+ * x0 < thr01 : !(x0 < thr10), uint64 compares against the thresholds of mcp_regime_consts -- and row i of step t is mu^(s)_i then
+ * fma(L^(s)_ij, z_j, acc), j ascending, s = s_t, each regime a whole chain of its own.  All portfolios and assets of a path share the
+ * regime.  The asset normals are those of the call without regimes (common random numbers): mu1 = mu and chol1 = chol, or start = 0
+ * and p01 = 0, is mcp_simulate* on (mu, chol) bit for bit, start = 1 and p10 = 0 that call on (mu1, chol1).  The moments are pivoted
+ * on the exact mean of mcp_regime_pivots, horizon row h on the h-step one.  The horizon inputs and the outputs are those of
+ * mcp_simulate_jumps (the drawdown or the horizons, not both: MCP_E_UNSUPPORTED).  Argument errors (MCP_E_ARG: the rules above,
+ * NULL pointers) are found before any device is touched; log compounding, MCP_FLAG_FOLD, MCP_FLAG_NATIVE_MATH: MCP_E_UNSUPPORTED.  Not
+ * built: regimes with Student-t draws, GARCH, jumps, bootstrap or filtered rows, rebalancing, cash flows, the overlay, the attribution
+ * or antithetic pairs, and at the mcp_launch_paths* level.  Costs: one Philox block and three compares per path-step, and a second
+ * chain of N4 (N4/2 + 1) / 2 packed fused multiply-adds in every wave whose 64 paths are not all in one regime; (mu1, chol1) are
+ * uploaded once per device and tile behind the packed parameters; K >= 17 runs as passes of 8 portfolios. */
+int mcp_simulate_regimes(mcp_ctx *ctx, const mcp_params *prm, const mcp_regimes *r,
+                         const float *mu, const float *chol, const float *W,
+                         uint64_t seed, uint64_t path_begin, uint64_t n_paths,
+                         int n_horizons, const int32_t *horizons, int n_levels, const double *levels,
+                         float *terminal_out,        /* NULL or host [K*n_paths] */
+                         mcp_stats *stats_out,       /* [K] */
+                         float *mdd_out,             /* NULL or host [K*n_paths]; needs dd_stats_out */
+                         mcp_stats *dd_stats_out,    /* [K], or NULL: no drawdown */
+                         float *horizon_out,         /* NULL or host [H*K*n_paths], row h*K + k */
+                         mcp_stats *hz_stats_out,    /* [H*K], NULL iff n_horizons == 0 */
+                         double *bands_out);         /* [H*K*L], NULL iff n_levels == 0 */
+/* The host constants of a regime request (SPEC.md 2.6; no device is touched; mu1 and chol1 are not read): for x = 01, 10, start in
+ * this order thr_out[x] = min(2^32, floor(p_x 2^32)) and p_out[x] = thr_x / 2^32, the probability the kernel really uses (p = 0 and
+ * p = 1 are exact: never and always). */
+int mcp_regime_consts(const mcp_regimes *r, uint64_t *thr_out /* [3] */, double *p_out /* [3] */);
+/* The shifts of the moments of regime paths (SPEC.md 5.13; no device is touched), binary64 from the binary32 inputs: with d_ks = 1 +
+ * sum_i W[k,i] mu^(s)_i (i ascending), pi = (1 - p^start, p^start), P^ the transition matrix on the p^ of mcp_regime_consts and
+ * D_k = diag(d_k0, d_k1): c_k(h) = pi' D_k (P^ D_k)^(h-1) 1 - 1, the exact mean of x after h steps, by the recursion v = pi D_k, then
+ * u = v P^ (u_0 = v_0 (1 - p^01) + v_1 p^10, u_1 = v_0 p^01 + v_1 (1 - p^10)), v = u D_k; c = (v_0 + v_1) - 1; 0 for h = 0 or where it
+ * is not finite.  Where portfolio k walks on one drift m only (m_k0 == m_k1; p^start = 0 and p^01 = 0; p^start = 1 and p^10 = 0) c_k(h)
+ * is mcp_pivots' expm1(h log1p(m)), 0 if m <= -1: the same mean, so that such a call has the Gaussian call's statistics bit for bit.
+ * pivots_out[k] = c_k(n_steps); hz_pivots_out[h*K + k] = c_k(horizons[h]) (NULL iff n_horizons == 0). */
+int mcp_regime_pivots(const mcp_params *prm, const mcp_regimes *r, const float *mu, const float *W,
+                      int n_horizons, const int32_t *horizons, double *pivots_out /* [K] */, double *hz_pivots_out /* NULL or [H*K] */);
 
 /* Antithetic pairs (SPEC.md 2.3 / 5.10): the pair statistics of one portfolio on the terminal x.  cross = sum_j (x_2j - c)(x_2j+1 - c)
  * with c the pivot of mcp_pivots; with C = cross - S1^2 / (2 n), S1 = (mean - c) n: pair_cov = C / (n_pairs - 1), pair_corr = 2 C / m2

@@ -91,6 +91,12 @@ class McpJumps(ctypes.Structure):
                 ("reserved", ctypes.c_int32)]
 
 
+class McpRegimes(ctypes.Structure):
+    """mcp_regimes: the transition and start probabilities of SPEC.md 2.6 and regime 1's binary32 drift [N] and Cholesky factor [N, N]."""
+    _fields_ = [("p01", ctypes.c_double), ("p10", ctypes.c_double), ("start", ctypes.c_double), ("mu1", ctypes.c_void_p),
+                ("chol1", ctypes.c_void_p), ("reserved", ctypes.c_int32)]
+
+
 class McpCashflow(ctypes.Structure):
     """mcp_cashflow: the schedule c_1 .. c_T (binary32, n_flows == n_steps) and the optional target of SPEC.md 4.7 / 5.6."""
     _fields_ = [("flows", ctypes.c_void_p), ("n_flows", ctypes.c_int32), ("has_target", ctypes.c_int32), ("target", ctypes.c_double)]
@@ -182,6 +188,10 @@ SIGNATURES = {
     "mcp_simulate_jumps": (_int, [_vp, _PP, ctypes.POINTER(McpJumps), _vp, _vp, _vp, _u64, _u64, _u64, _int, _vp, _int, _vp, _vp, _vp,
                                   _vp, _vp, _vp, _vp, _vp]),
     "mcp_jump_consts": (_int, [ctypes.POINTER(McpJumps), _int, _vp, _vp, ctypes.POINTER(ctypes.c_double), _vp]),
+    "mcp_simulate_regimes": (_int, [_vp, _PP, ctypes.POINTER(McpRegimes), _vp, _vp, _vp, _u64, _u64, _u64, _int, _vp, _int, _vp, _vp, _vp,
+                                    _vp, _vp, _vp, _vp, _vp]),
+    "mcp_regime_consts": (_int, [ctypes.POINTER(McpRegimes), _vp, _vp]),
+    "mcp_regime_pivots": (_int, [_PP, ctypes.POINTER(McpRegimes), _vp, _vp, _int, _vp, _vp, _vp]),
     "mcp_simulate_attribution": (_int, [_vp, _PP, ctypes.POINTER(McpGarch), ctypes.POINTER(McpStudentT), _vp, _vp, _vp, _u64, _u64, _u64,
                                         _vp, _vp, _vp, _vp, _vp]),
     "mcp_simulate_antithetic": (_int, [_vp, _PP, ctypes.POINTER(McpGarch), ctypes.POINTER(McpStudentT), _vp, _vp, _vp, _u64, _u64, _u64,
@@ -361,6 +371,41 @@ def jump_consts(intensity: float, mean: float, std: float, loading=None, mu=None
     ptr = lambda a: a.ctypes.data_as(_vp) if a is not None else None   # noqa: E731
     check(lib().mcp_jump_consts(ctypes.byref(jp), n, ptr(mu32), ptr(thr), ctypes.byref(mean_count), ptr(drift)))
     return thr, mean_count.value, drift
+
+
+def make_regimes(p01: float, p10: float, start: float, mu1: np.ndarray | None, chol1: np.ndarray | None) -> McpRegimes:
+    """mcp_regimes; `mu1` [N] and `chol1` [N, N] are C-contiguous binary32 arrays (the caller keeps them alive for the call)."""
+    for a, nd in ((mu1, 1), (chol1, 2)):
+        if a is not None and (a.dtype != np.float32 or a.ndim != nd or not a.flags.c_contiguous):
+            raise ValueError("regime mu1 [N] and chol1 [N, N] must be C-contiguous float32 arrays")
+    ptr = lambda a: a.ctypes.data_as(ctypes.c_void_p) if a is not None else None   # noqa: E731
+    return McpRegimes(float(p01), float(p10), float(start), ptr(mu1), ptr(chol1), 0)
+
+
+def regime_consts(p01: float, p10: float, start: float):
+    """(thr uint64 [3], p float64 [3]) for (p01, p10, start): the thresholds of SPEC.md 2.6 and the probabilities the kernel really
+    uses (include/mcport.h, mcp_regime_consts), pure host arithmetic."""
+    thr, p = np.zeros(3, np.uint64), np.zeros(3, np.float64)
+    rs = make_regimes(p01, p10, start, None, None)
+    check(lib().mcp_regime_consts(ctypes.byref(rs), thr.ctypes.data_as(_vp), p.ctypes.data_as(_vp)))
+    return thr, p
+
+
+def regime_pivots(prm: McpParams, regimes, mu: np.ndarray, mu1: np.ndarray, W: np.ndarray, horizons=None):
+    """([K] pivots at n_steps, [H, K] at the horizons or None): the exact means of SPEC.md 5.13 (include/mcport.h, mcp_regime_pivots),
+    pure host arithmetic.  `regimes` is (p01, p10, start)."""
+    mu, mu1 = (np.ascontiguousarray(a, np.float32) for a in (mu, mu1))
+    W = np.ascontiguousarray(W, np.float32)
+    n = mu.size
+    chol1 = np.zeros((n, n), np.float32)                  # not read by the pivots; the rules want a pointer
+    rs = make_regimes(*regimes, mu1, chol1)
+    hz = np.ascontiguousarray(horizons, np.int32) if horizons is not None and len(horizons) else None
+    out = np.zeros(W.shape[0], np.float64)
+    hout = np.zeros((hz.size, W.shape[0]), np.float64) if hz is not None else None
+    ptr = lambda a: a.ctypes.data_as(_vp) if a is not None else None   # noqa: E731
+    check(lib().mcp_regime_pivots(ctypes.byref(prm), ctypes.byref(rs), ptr(mu), ptr(W), 0 if hz is None else hz.size, ptr(hz), ptr(out),
+                                  ptr(hout)))
+    return out, hout
 
 
 def bootstrap_pivots(prm: McpParams, rows: np.ndarray, W: np.ndarray, block: float = 1.0) -> np.ndarray:

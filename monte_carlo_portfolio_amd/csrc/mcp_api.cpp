@@ -91,6 +91,8 @@ int sweep_plan(int K, int nb, SweepSeg* out) {
 }
 
 inline int n4_of(int n) { return 4 * ((n + 3) / 4); }
+// floats of the regime-1 block [mu1 N4][L1 row pairs N4(N4/2+1)] (SPEC.md 4.13)
+inline size_t regime_block_len(int n) { const size_t n4 = (size_t)n4_of(n); return n4 + n4 * (n4 / 2 + 1); }
 // W rows are zero-padded to whole MFMA workgroups for a sweep, to whole KT_WIDE passes otherwise
 inline int kpad_of(int k) { return k >= SWEEP_MIN_K ? K_PAD * ((k + K_PAD - 1) / K_PAD) : KT_WIDE * ((k + KT_WIDE - 1) / KT_WIDE); }
 
@@ -277,6 +279,75 @@ int check_jumps(int n_assets, const mcp_jumps* j) {
   return MCP_OK;
 }
 
+// SPEC.md 2.6: the host constants of a regime request, binary64 -- thr_x = min(2^32, floor(p_x 2^32)) (the product an exact scaling)
+// and the probabilities the kernel really uses, p^_x = thr_x / 2^32, for x = 01, 10, start
+struct RegimeConsts { uint64_t thr01, thr10, thr_start; double p01, p10, start; };
+inline uint64_t regime_thr(double p) {
+  const double v = std::floor(p * 4294967296.0);
+  return v >= 4294967296.0 ? (uint64_t)1 << 32 : (uint64_t)v;
+}
+RegimeConsts regime_consts(const mcp_regimes* r) {
+  RegimeConsts c;
+  c.thr01 = regime_thr(r->p01);
+  c.thr10 = regime_thr(r->p10);
+  c.thr_start = regime_thr(r->start);
+  c.p01 = (double)c.thr01 / 4294967296.0;
+  c.p10 = (double)c.thr10 / 4294967296.0;
+  c.start = (double)c.thr_start / 4294967296.0;
+  return c;
+}
+
+// SPEC.md 2.6: the three probabilities finite and in [0, 1], mu1 [N] and chol1 [N][N] not NULL and finite, reserved == 0
+int check_regimes(int n_assets, const mcp_regimes* r) {
+  if (!r) return fail(MCP_E_ARG, "regimes is NULL");
+  if (r->reserved != 0) return fail(MCP_E_ARG, "regimes reserved=%d must be 0", r->reserved);
+  if (!std::isfinite(r->p01) || !std::isfinite(r->p10) || !std::isfinite(r->start))
+    return fail(MCP_E_ARG, "regimes p01=%g, p10=%g, start=%g must be finite", r->p01, r->p10, r->start);
+  if (!(r->p01 >= 0.0 && r->p01 <= 1.0) || !(r->p10 >= 0.0 && r->p10 <= 1.0) || !(r->start >= 0.0 && r->start <= 1.0))
+    return fail(MCP_E_ARG, "regimes p01=%g, p10=%g, start=%g outside [0, 1]", r->p01, r->p10, r->start);
+  if (!r->mu1 || !r->chol1) return fail(MCP_E_ARG, "regimes mu1 or chol1 is NULL");
+  for (int i = 0; i < n_assets; i++)
+    if (!std::isfinite(r->mu1[i])) return fail(MCP_E_ARG, "regimes mu1, asset %d is not finite", i);
+  for (size_t i = 0; i < (size_t)n_assets * n_assets; i++)
+    if (!std::isfinite(r->chol1[i])) return fail(MCP_E_ARG, "regimes chol1, entry %zu is not finite", i);
+  return MCP_OK;
+}
+
+// SPEC.md 5.13: the exact mean of x after h steps, c_k(h) = pi' D_k (P^ D_k)^(h-1) 1 - 1 with d_ks = 1 + sum_i W[k,i] mu^(s)_i (i
+// ascending, binary64 from the binary32 inputs), as one row-vector recursion over h = 1 .. T: v = pi D, then v = (v P^) D;
+// out_T[k] = c_k(T), out_hz[h*K + k] = c_k(steps[h]); 0 for h = 0 and where c is not finite.  Where the walk of portfolio k has one
+// drift only -- m_k0 == m_k1, or the chain never leaves the regime it starts in (p^start = 0 and p^01 = 0: regime 0; p^start = 1 and
+// p^10 = 0: regime 1) -- c_k(h) is mcp_pivots' own expm1(h log1p(m)) on that drift, the same mean in the Gaussian call's rounding, so
+// that such a call has the Gaussian call's statistics bit for bit.
+void regime_pivots(int N, int K, int T, const float* mu0, const float* mu1, const RegimeConsts& c, const float* W, int H, const int32_t* steps,
+                   double* out_T, double* out_hz) {
+  for (int k = 0; k < K; k++) {
+    const float* w = W + (size_t)k * N;
+    double d0 = 0.0, d1 = 0.0;
+    for (int i = 0; i < N; i++) d0 += (double)w[i] * (double)(mu0[i] + 0.0f);
+    for (int i = 0; i < N; i++) d1 += (double)w[i] * (double)(mu1[i] + 0.0f);
+    const bool only0 = c.thr_start == 0 && c.thr01 == 0, only1 = c.thr_start == ((uint64_t)1 << 32) && c.thr10 == 0;
+    const bool one_drift = d0 == d1 || only0 || only1;
+    const double m = only1 ? d1 : d0;
+    d0 = 1.0 + d0;
+    d1 = 1.0 + d1;
+    double v0 = (1.0 - c.start) * d0, v1 = c.start * d1;
+    int hi = 0;
+    if (out_T) out_T[k] = 0.0;
+    for (int h = 1; h <= T; h++) {
+      if (h > 1) {
+        const double u0 = v0 * (1.0 - c.p01) + v1 * c.p10, u1 = v0 * c.p01 + v1 * (1.0 - c.p10);
+        v0 = u0 * d0;
+        v1 = u1 * d1;
+      }
+      const double ch = one_drift ? (m > -1.0 ? std::expm1((double)h * std::log1p(m)) : 0.0) : (v0 + v1) - 1.0;
+      const double piv = std::isfinite(ch) ? ch : 0.0;
+      if (hi < H && steps[hi] == h) out_hz[(size_t)hi++ * K + k] = piv;
+      if (h == T && out_T) out_T[k] = piv;
+    }
+  }
+}
+
 // SPEC.md 2.4: the filtered rows -- mu [N], resid [R][N] and shock [R] finite binary32 values, every shock >= 0, 1..MCP_MAX_BOOT_ROWS
 // rows, 1 <= b <= +inf, reserved == 0
 int check_filtered(const mcp_params* prm, const mcp_filtered* f) {
@@ -443,6 +514,8 @@ struct Request {
   const mcp_garch* gv = nullptr;
   bool jumps = false;                   // SPEC.md 2.5 / 4.12: the market jump `jp` on top of SRC_GAUSS
   const mcp_jumps* jp = nullptr;
+  bool regimes = false;                 // SPEC.md 2.6 / 4.13: two regimes `rs`, regime 0 on (mu, chol), on top of SRC_GAUSS
+  const mcp_regimes* rs = nullptr;
   bool dd = false;                      // SPEC.md 4.2 / 5.1: the drawdown of every path
   bool hz = false;                      // SPEC.md 4.3 / 5.2: the values after H steps, statistics at alpha and at L levels
   int H = 0, L = 0;
@@ -511,6 +584,7 @@ struct Launch {
   const float* d_flows = nullptr;       // cash flows: [n_steps]
   const char* d_overlay = nullptr;      // overlay: [rows][row_begin N4 + 1][spot N4] (overlay_pack)
   const float* d_loading = nullptr;     // jumps: [N4] loadings, zero-padded
+  const float* d_block1 = nullptr;      // regimes: [mu1 N4][L1 row pairs], the layout of mcp_pack_params
   bool attr = false;                    // the attribution walk (SPEC.md 4.10): FAM_AT instead of the request's own family
   const double* d_var = nullptr;        // attribution: [K] VaRs
   double* d_cross = nullptr;            // antithetic pairs: [K][path_grid(n_paths / 2)] cross partials
@@ -552,6 +626,19 @@ int check_request(const mcp_params* prm, const Request& rq, uint64_t n_paths, co
       return fail(MCP_E_UNSUPPORTED, "jumps are not combined with rebalancing, cash flows, the overlay, the attribution or antithetic pairs");
     if (ln) return fail(MCP_E_UNSUPPORTED, "jumps are not wired into mcp_launch_paths*");
   }
+  if (rq.regimes) {                                            // SPEC.md 2.6 / 4.13: the rules, then what the regimes are not combined with
+    if ((rc = check_regimes(prm->n_assets, rq.rs))) return rc;
+    for (int i = 0; rq.mu && i < prm->n_assets; i++)
+      if (!std::isfinite(rq.mu[i])) return fail(MCP_E_ARG, "regimes: mu, asset %d is not finite", i);
+    for (size_t i = 0; rq.chol && i < (size_t)prm->n_assets * prm->n_assets; i++)
+      if (!std::isfinite(rq.chol[i])) return fail(MCP_E_ARG, "regimes: chol, entry %zu is not finite", i);
+    if (logc) return fail(MCP_E_UNSUPPORTED, "regime-switching paths compound simply (no log compounding)");
+    if (rq.src != SRC_GAUSS || rq.st || rq.garch || rq.jumps)
+      return fail(MCP_E_UNSUPPORTED, "regimes are not combined with Student-t draws, GARCH, jumps, bootstrap or filtered rows");
+    if (rq.rebalanced || rq.cash || rq.overlay || rq.attr || rq.anti)
+      return fail(MCP_E_UNSUPPORTED, "regimes are not combined with rebalancing, cash flows, the overlay, the attribution or antithetic pairs");
+    if (ln) return fail(MCP_E_UNSUPPORTED, "regimes are not wired into mcp_launch_paths*");
+  }
   if (rq.src == SRC_FHS) {                                     // SPEC.md 2.4 / 4.11: the rows, the triple, then what it is not combined with
     if ((rc = check_filtered(prm, rq.filt))) return rc;
     if ((rc = check_garch(prm, rq.gv))) return rc;
@@ -575,7 +662,8 @@ int check_request(const mcp_params* prm, const Request& rq, uint64_t n_paths, co
   if (rq.src == SRC_T && logc)
     return fail(MCP_E_UNSUPPORTED, "Student-t paths compound simply (log compounding: expm1(S) has no finite mean under t steps)");
   if (prm->flags & (MCP_FLAG_FOLD | MCP_FLAG_NATIVE_MATH)) {   // the fast steps exist for plain Gaussian walks only
-    const char* who = rq.jumps             ? "jump-diffusion paths run on the spec's normals and the unfolded recurrence"
+    const char* who = rq.regimes           ? "regime-switching paths run on the spec's normals and the unfolded recurrence"
+                      : rq.jumps           ? "jump-diffusion paths run on the spec's normals and the unfolded recurrence"
                       : rq.garch           ? "GARCH paths run on the spec's normals and the unfolded recurrence"
                       : rq.overlay         ? "overlaid paths run on the unfolded recurrence and the spec's normals"
                       : rq.cash            ? "paths with cash flows run on the unfolded recurrence and the spec's normals"
@@ -1104,6 +1192,16 @@ static mcp::JumpArgs jump_block(const Request& rq, const Launch& ln) {
   jp.s = c.s;
   return jp;
 }
+// SPEC.md 2.6: the thresholds; the regime-1 block sits behind the launch's packed block
+static mcp::RegimeArgs regime_block(const Request& rq, const Launch& ln) {
+  const RegimeConsts c = regime_consts(rq.rs);
+  mcp::RegimeArgs rs;
+  rs.block1 = ln.d_block1;
+  rs.thr01 = c.thr01;
+  rs.thr10 = c.thr10;
+  rs.thr_start = c.thr_start;
+  return rs;
+}
 static mcp::OverlayArgs overlay_block(const Request& rq, const Launch& ln, int n_assets) {
   mcp::OverlayArgs ov;
   const size_t row_bytes = (size_t)rq.ov->n_rows * sizeof(mcp_overlay_row);
@@ -1134,7 +1232,7 @@ static mcp::AttrArgs attr_block(const Launch& ln, int n_assets) {
 static int launch_paths_impl(const mcp_params* prm, const Request& rq, const Launch& ln) {
   const int N = prm->n_assets, nb = (N + 3) / 4;
   const int K = prm->n_portfolios;
-  const bool plain = rq.src == SRC_GAUSS && !rq.dd && !rq.hz && !rq.rebalanced && !rq.cash && !rq.overlay && !rq.garch && !rq.jumps;
+  const bool plain = rq.src == SRC_GAUSS && !rq.dd && !rq.hz && !rq.rebalanced && !rq.cash && !rq.overlay && !rq.garch && !rq.jumps && !rq.regimes;
   mcp::PathLaunchArgs s = {};             // every block the request does not carry stays empty
   mcp::PathArgs& a = s.hz;
   const float4* tables = nullptr;
@@ -1205,6 +1303,7 @@ static int launch_paths_impl(const mcp_params* prm, const Request& rq, const Lau
   if (rq.rebalanced) { s.period = rq.reb->period; s.cost = (float)rq.reb->cost; }
   if (rq.src == SRC_FHS) s.fh = filt_block(rq, ln, N);
   if (rq.jumps) s.jp = jump_block(rq, ln);
+  if (rq.regimes) s.rs = regime_block(rq, ln);
   mcp::PathKernel k = {};
   k.logc = prm->compounding == MCP_COMPOUND_LOG;
   k.fh = rq.src == SRC_FHS;
@@ -1226,6 +1325,7 @@ static int launch_paths_impl(const mcp_params* prm, const Request& rq, const Lau
     k.dd = rq.overlay && rq.dd;
     k.gv = rq.garch;
     k.jp = rq.jumps;
+    k.rs = rq.regimes;
     k.kt8 = K > 1;
     k.native = (prm->flags & MCP_FLAG_NATIVE_MATH) != 0;
     k.fold = (prm->flags & MCP_FLAG_FOLD) != 0;
@@ -1759,7 +1859,8 @@ int run_tile(mcp_ctx* c, const mcp_params* prm, const Request& rq, uint64_t seed
     Shard& sh = c->sh[s];
     HIP_TRY(hipSetDevice(sh.device));
     tp[s].n_portfolios = j.kt;
-    const size_t plen = mcp_packed_len(N, j.kt) + (rq.jumps ? (size_t)n4_of(N) : 0), pn = j.pn ? j.pn : 1;   // jumps: the loadings behind it
+    // jumps: the loadings behind the packed block; regimes: [mu1][L1 row pairs] there
+    const size_t plen = mcp_packed_len(N, j.kt) + (rq.jumps ? (size_t)n4_of(N) : 0) + (rq.regimes ? regime_block_len(N) : 0), pn = j.pn ? j.pn : 1;
     const int rows = rq.hz ? rq.H * j.kt : j.kt;  // horizon calls: the work buffers also serve the H*kt rows of the horizon selects
     for (int w = 0; w < MCP_WS_COUNT; w++) {      // only the histogram and the select state must start zeroed
       const size_t need = std::max(mcp_ws_bytes(w, j.kt, pn), mcp_ws_bytes(w, rows, pn));
@@ -1793,7 +1894,13 @@ int run_tile(mcp_ctx* c, const mcp_params* prm, const Request& rq, uint64_t seed
   // jumps (SPEC.md 2.5): the compensated drift in the packed block (the pivots keep the drift itself), the loadings behind the block
   std::vector<float> jmu(rq.jumps ? N : 0);
   if (rq.jumps) jump_drift(rq.jp, jump_consts(rq.jp), N, rq.mu, jmu.data());
-  const size_t n_load = rq.jumps ? (size_t)n4_of(N) : 0;
+  // regimes (SPEC.md 2.6): (mu1, chol1) packed as (mu, chol) are, the head of that block behind the packed block
+  const size_t n_load = rq.jumps ? (size_t)n4_of(N) : rq.regimes ? regime_block_len(N) : 0;
+  std::vector<float> blk1;
+  if (rq.regimes) {
+    blk1.resize(mcp_packed_len(N, 1));
+    if ((rc = mcp_pack_params(N, 1, rq.rs->mu1, rq.rs->chol1, rq.W, blk1.data(), blk1.size()))) return rc;
+  }
   const float* mu = boot ? zmu.data() : fhs ? rq.filt->mu : rq.jumps ? jmu.data() : rq.mu;
   const float* chol = boot || fhs ? zchol.data() : rq.chol;
   std::vector<double> bm, bs2, rmu(rq.rebalanced || fhs ? N : 0), cm;
@@ -1816,7 +1923,8 @@ int run_tile(mcp_ctx* c, const mcp_params* prm, const Request& rq, uint64_t seed
     } else {
       const float* Wt = rq.W + (size_t)j.k0 * N;
       if ((rc = mcp_pack_params(N, j.kt, mu, chol, Wt, sh.h_packed.p, plen))) return rc;
-      for (size_t i = 0; i < n_load; i++) sh.h_packed.p[plen + i] = (int)i < N ? (rq.jp->loading ? rq.jp->loading[i] : 1.0f) : 0.0f;
+      for (size_t i = 0; rq.jumps && i < n_load; i++) sh.h_packed.p[plen + i] = (int)i < N ? (rq.jp->loading ? rq.jp->loading[i] : 1.0f) : 0.0f;
+      for (size_t i = 0; rq.regimes && i < n_load; i++) sh.h_packed.p[plen + i] = blk1[i];
       if (boot && !rq.rebalanced) {
         bm.resize((size_t)j.kt);
         bs2.resize((size_t)j.kt);
@@ -1829,8 +1937,11 @@ int run_tile(mcp_ctx* c, const mcp_params* prm, const Request& rq, uint64_t seed
                     sh.hz.h_pivot.p);
       } else if (ov_walk) {                                  // SPEC.md 5.7: one walk gives T and every horizon
         overlay_pivots(N, j.kt, prm->n_steps, rq.ov, rq.mu, Wt, rq.hz ? rq.H : 0, rq.steps, sh.h_pivot.p, sh.hz.h_pivot.p);
+      } else if (rq.regimes) {                               // SPEC.md 5.13: one recursion gives T and every horizon
+        regime_pivots(N, j.kt, prm->n_steps, rq.mu, rq.rs->mu1, regime_consts(rq.rs), Wt, rq.hz ? rq.H : 0, rq.steps, sh.h_pivot.p,
+                      sh.hz.h_pivot.p);
       } else if ((rc = tile_pivots(tp[s], rq, prm->n_steps, Wt, rmu.data(), bm.data(), bs2.data(), sh.h_pivot.p))) return rc;
-      for (int h = 0; rq.hz && !rq.cash && !ov_walk && h < rq.H; h++)                // SPEC.md 5.2 / 5.3: row h*kt + k is pivoted with n_steps = h
+      for (int h = 0; rq.hz && !rq.cash && !ov_walk && !rq.regimes && h < rq.H; h++)                // SPEC.md 5.2 / 5.3: row h*kt + k is pivoted with n_steps = h
         if ((rc = tile_pivots(tp[s], rq, rq.steps[h], Wt, rmu.data(), bm.data(), bs2.data(), sh.hz.h_pivot.p + (size_t)h * j.kt)))
           return rc;
       if (exchange) { shared_packed = sh.h_packed.p; shared_pivot = sh.h_pivot.p; shared_hz_pivot = sh.hz.h_pivot.p; }
@@ -1849,6 +1960,7 @@ int run_tile(mcp_ctx* c, const mcp_params* prm, const Request& rq, uint64_t seed
       ln.d_flows = sh.cf.flows.p;
       ln.d_overlay = sh.overlay.p;
       ln.d_loading = sh.packed.p + plen;
+      ln.d_block1 = sh.packed.p + plen;
       ln.d_cross = sh.pr.partials.p;
       if ((rc = launch_paths_impl(&tp[s], rq, ln))) return rc;
       if (rq.anti) {                                         // SPEC.md 5.10: the workgroups' cross partials in block order
@@ -2266,6 +2378,50 @@ int mcp_simulate_jumps(mcp_ctx* c, const mcp_params* prm, const mcp_jumps* j, co
   rq.dd_stats_out = dd_stats_out;
   ask_horizons(rq, n_horizons != 0, n_horizons, horizons, n_levels, levels, horizon_out, hz_stats_out, bands_out);
   return simulate_checked(c, prm, rq, seed, path_begin, n_paths);
+}
+
+int mcp_simulate_regimes(mcp_ctx* c, const mcp_params* prm, const mcp_regimes* r, const float* mu, const float* chol, const float* W,
+                         uint64_t seed, uint64_t path_begin, uint64_t n_paths, int n_horizons, const int32_t* horizons, int n_levels,
+                         const double* levels, float* terminal_out, mcp_stats* stats_out, float* mdd_out, mcp_stats* dd_stats_out,
+                         float* horizon_out, mcp_stats* hz_stats_out, double* bands_out) {
+  Request rq = host_request(SRC_GAUSS, mu, chol, W, terminal_out, stats_out);
+  rq.regimes = true;
+  rq.rs = r;
+  rq.dd = dd_stats_out != nullptr;
+  rq.mdd_out = mdd_out;
+  rq.dd_stats_out = dd_stats_out;
+  ask_horizons(rq, n_horizons != 0, n_horizons, horizons, n_levels, levels, horizon_out, hz_stats_out, bands_out);
+  return simulate_checked(c, prm, rq, seed, path_begin, n_paths);
+}
+
+int mcp_regime_consts(const mcp_regimes* r, uint64_t* thr_out, double* p_out) {
+  if (!r) return fail(MCP_E_ARG, "regimes is NULL");
+  if (r->reserved != 0) return fail(MCP_E_ARG, "regimes reserved=%d must be 0", r->reserved);
+  if (!std::isfinite(r->p01) || !std::isfinite(r->p10) || !std::isfinite(r->start))
+    return fail(MCP_E_ARG, "regimes p01=%g, p10=%g, start=%g must be finite", r->p01, r->p10, r->start);
+  if (!(r->p01 >= 0.0 && r->p01 <= 1.0) || !(r->p10 >= 0.0 && r->p10 <= 1.0) || !(r->start >= 0.0 && r->start <= 1.0))
+    return fail(MCP_E_ARG, "regimes p01=%g, p10=%g, start=%g outside [0, 1]", r->p01, r->p10, r->start);
+  if (!thr_out || !p_out) return fail(MCP_E_ARG, "NULL pointer");
+  const RegimeConsts c = regime_consts(r);
+  thr_out[0] = c.thr01; thr_out[1] = c.thr10; thr_out[2] = c.thr_start;
+  p_out[0] = c.p01; p_out[1] = c.p10; p_out[2] = c.start;
+  return MCP_OK;
+}
+
+int mcp_regime_pivots(const mcp_params* prm, const mcp_regimes* r, const float* mu, const float* W, int n_horizons,
+                      const int32_t* horizons, double* pivots_out, double* hz_pivots_out) {
+  if (int rc = check_params(prm)) return rc;
+  if (int rc = check_regimes(prm->n_assets, r)) return rc;
+  if (!mu || !W || !pivots_out) return fail(MCP_E_ARG, "NULL pointer");
+  for (int i = 0; i < prm->n_assets; i++)
+    if (!std::isfinite(mu[i])) return fail(MCP_E_ARG, "regimes: mu, asset %d is not finite", i);
+  if (prm->compounding != MCP_COMPOUND_SIMPLE) return fail(MCP_E_UNSUPPORTED, "regime-switching paths compound simply (no log compounding)");
+  if (n_horizons != 0) {
+    if (int rc = check_horizons(prm->n_steps, n_horizons, horizons)) return rc;
+    if (!hz_pivots_out) return fail(MCP_E_ARG, "hz_pivots_out is NULL");
+  }
+  regime_pivots(prm->n_assets, prm->n_portfolios, prm->n_steps, mu, r->mu1, regime_consts(r), W, n_horizons, horizons, pivots_out, hz_pivots_out);
+  return MCP_OK;
 }
 
 int mcp_jump_consts(const mcp_jumps* j, int n_assets, const float* mu, uint32_t* thr_out, double* mean_count_out, float* drift_out) {

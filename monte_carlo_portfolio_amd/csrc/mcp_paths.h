@@ -95,7 +95,7 @@ __device__ __forceinline__ const __attribute__((address_space(4))) A* kernarg() 
   template <class A> struct has_##m<A, std::void_t<decltype(A::m)>> : std::true_type {};
 MCP_HAS_MEMBER(hz) MCP_HAS_MEMBER(mdd) MCP_HAS_MEMBER(bt) MCP_HAS_MEMBER(st) MCP_HAS_MEMBER(gv) MCP_HAS_MEMBER(cf)
 MCP_HAS_MEMBER(ov) MCP_HAS_MEMBER(at) MCP_HAS_MEMBER(period) MCP_HAS_MEMBER(pr)
-MCP_HAS_MEMBER(fh) MCP_HAS_MEMBER(p_hi) MCP_HAS_MEMBER(jp)
+MCP_HAS_MEMBER(fh) MCP_HAS_MEMBER(p_hi) MCP_HAS_MEMBER(jp) MCP_HAS_MEMBER(rs)
 #undef MCP_HAS_MEMBER
 
 struct PathArgs {
@@ -222,6 +222,26 @@ typedef const __attribute__((address_space(4))) JumpArgs* cjump_p;
 template <class A>
 __device__ __forceinline__ cjump_p jump_args(const A&) {
   if constexpr (has_jp<A>::value) return &kernarg<A>()->jp;
+  else return nullptr;
+}
+
+// Two-regime Markov switching (SPEC.md 2.6 / 4.13): every path carries a regime s_t in {0, 1}, moved once per step by one Philox
+// block on counter stream 4 -- s_0 = x1 < thr_start (the block of t = 0), s_{t+1} = s_t == 0 ? x0 < thr01 : !(x0 < thr10), uint64
+// compares against thresholds in [0, 2^32] -- and step t walks on (mu, L) of regime s_t: the packed block's for regime 0, `block1`
+// ([mu1 N4][L1 row pairs N4(N4/2+1)], the layout of mcp_pack_params, behind the launch's packed block) for regime 1.  Appended to
+// the arguments of the plain, drawdown and horizon kernels (mc_paths_r_kernel, mc_paths_r_dd_kernel, mc_paths_r_hz_kernel).
+struct RegimeArgs {
+  const float* __restrict__ block1;   // [N4 + N4(N4/2+1)] device copy
+  uint64_t thr01, thr10, thr_start;
+};
+struct PathArgsR : PathArgs { RegimeArgs rs; };
+struct PathArgsRDD : PathArgsDD { RegimeArgs rs; };
+struct PathArgsRHZ : PathArgsHZ { RegimeArgs rs; };
+// The regime block of an r kernel's launch, read where it is used (kernarg).
+typedef const __attribute__((address_space(4))) RegimeArgs* cregime_p;
+template <class A>
+__device__ __forceinline__ cregime_p regime_args(const A&) {
+  if constexpr (has_rs<A>::value) return &kernarg<A>()->rs;
   else return nullptr;
 }
 
@@ -374,6 +394,7 @@ struct PathLaunchArgs {
   PairArgs pr;
   FiltArgs fh;
   JumpArgs jp;
+  RegimeArgs rs;
 };
 template <class A>
 inline A make_args(const PathLaunchArgs& s) {
@@ -391,6 +412,7 @@ inline A make_args(const PathLaunchArgs& s) {
   if constexpr (has_pr<A>::value) x.pr = s.pr;
   if constexpr (has_fh<A>::value) x.fh = s.fh;
   if constexpr (has_jp<A>::value) x.jp = s.jp;
+  if constexpr (has_rs<A>::value) x.rs = s.rs;
   if constexpr (has_p_hi<A>::value) { x.p_hi = (uint32_t)(s.hz.path_begin >> 32); x.pad = 0u; }
   return x;
 }
@@ -489,13 +511,16 @@ constexpr int PATH_BLOCK = 256;
 // are wave-uniform (philox4x32_10_uhi), the drift's LDS address and the transform's two scaling constants sit in VGPRs across the walk
 // instead of being formed every step; the draws, and every result, are those of the kernel without it.  JP: before the asset normals one
 // more Philox block on counter stream 3 gives the step's market jump J (SPEC.md 2.5), and every row pair's accumulator starts at
-// fma(b, J, mu') instead of mu, one packed fma with the loadings b from the LDS slot behind the drift (SPEC.md 4.12).  Every kernel
+// fma(b, J, mu') instead of mu, one packed fma with the loadings b from the LDS slot behind the drift (SPEC.md 4.12).  RS: before the
+// asset normals one more Philox block on counter stream 4 moves the path's regime (SPEC.md 2.6), and every row pair's chain runs once per
+// regime under that regime's lanes -- a divergent if / else, skipped where the wave has no lane in the regime -- with that regime's
+// drift and Cholesky factor, the factor still a scalar operand (SPEC.md 4.13).  Every kernel
 // below is the body in mcp_paths_body.inc under its own flags F: it names the flags it sets, the rest are PathFlagsOff's.  F is a
 // local class, which may not have static data members, so it sets its flags as enumerators of an `enum : bool`; they hide the
 // defaults' names and read as the same constant expressions.
 struct PathFlagsOff {
   static constexpr bool NATIVE = false, FOLD = false, LOGC = false, DD = false, HZ = false, BOOT = false, BLDS = false, REB = false,
-                        STT = false, CF = false, OV = false, GV = false, AT = false, ANTI = false, FH = false, UHI = false, JP = false;
+                        STT = false, CF = false, OV = false, GV = false, AT = false, ANTI = false, FH = false, UHI = false, JP = false, RS = false;
 };
 
 // __launch_bounds__ 2nd argument of a path kernel: the MCP_MIN_WAVES* above for N <= 16 and one path per lane, by the kind of
@@ -623,6 +648,26 @@ __global__ void MCP_BOUNDS(BK_PATHS) mc_paths_j_dd_kernel(const PathArgsJDD a) {
 template <int NB, int KT, int PPT>
 __global__ void MCP_BOUNDS(BK_PATHS) mc_paths_j_hz_kernel(const PathArgsJHZ a) {
   struct F : PathFlagsOff { enum : bool { JP = true, HZ = true }; };
+#include "mcp_paths_body.inc"
+}
+
+// The regime-switching kernels (SPEC.md 2.6 / 4.13; simple compounding, unfolded recurrence, Gaussian draws): mc_paths_kernel,
+// mc_paths_dd_kernel and mc_paths_hz_kernel with one regime in {0, 1} per path, step t on the drift and factor of the path's regime.
+// V_T, the drawdown, the horizons and the fused epilogue as there.  They keep the plain kernel's launch bounds
+// (profiles/regime_isa.txt).
+template <int NB, int KT, int PPT>
+__global__ void MCP_BOUNDS(BK_PATHS) mc_paths_r_kernel(const PathArgsR a) {
+  struct F : PathFlagsOff { enum : bool { RS = true }; };
+#include "mcp_paths_body.inc"
+}
+template <int NB, int KT, int PPT>
+__global__ void MCP_BOUNDS(BK_PATHS) mc_paths_r_dd_kernel(const PathArgsRDD a) {
+  struct F : PathFlagsOff { enum : bool { RS = true, DD = true }; };
+#include "mcp_paths_body.inc"
+}
+template <int NB, int KT, int PPT>
+__global__ void MCP_BOUNDS(BK_PATHS) mc_paths_r_hz_kernel(const PathArgsRHZ a) {
+  struct F : PathFlagsOff { enum : bool { RS = true, HZ = true }; };
 #include "mcp_paths_body.inc"
 }
 

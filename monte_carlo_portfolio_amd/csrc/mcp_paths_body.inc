@@ -4,12 +4,14 @@
 // walk is the one loop it always was.  In scope: the template parameters NB, KT, PPT, the flags F (PathFlagsOff or a struct
 // derived from it) and the kernel argument `a` (PathArgs or a struct that starts with one).
   constexpr bool NATIVE = F::NATIVE, FOLD = F::FOLD, LOGC = F::LOGC, DD = F::DD, HZ = F::HZ, BOOT = F::BOOT, BLDS = F::BLDS, REB = F::REB,
-                 STT = F::STT, CF = F::CF, OV = F::OV, GV = F::GV, AT = F::AT, ANTI = F::ANTI, FH = F::FH, UHI = F::UHI, JP = F::JP;
-  static_assert(!UHI || (KT == 1 && PPT == 1 && !(NATIVE || FOLD || DD || HZ || BOOT || REB || STT || CF || OV || GV || AT || ANTI || FH || JP)),
+                 STT = F::STT, CF = F::CF, OV = F::OV, GV = F::GV, AT = F::AT, ANTI = F::ANTI, FH = F::FH, UHI = F::UHI, JP = F::JP, RS = F::RS;
+  static_assert(!UHI || (KT == 1 && PPT == 1 && !(NATIVE || FOLD || DD || HZ || BOOT || REB || STT || CF || OV || GV || AT || ANTI || FH || JP || RS)),
                 "uniform high counter word: the plain Gaussian walk of one portfolio only");
   static_assert(!FH || (BOOT && HZ && !(LOGC || REB || CF || STT || GV || OV || AT || DD)), "filtered rows: the bootstrap's segmented walk only");
   static_assert(!JP || !(NATIVE || FOLD || LOGC || BOOT || REB || STT || CF || OV || GV || AT || ANTI || FH),
                 "jump-diffusion: the Gaussian walk, its drawdown and its horizons, simple compounding only");
+  static_assert(!RS || !(NATIVE || FOLD || LOGC || BOOT || REB || STT || CF || OV || GV || AT || ANTI || FH || JP),
+                "regime switching: the Gaussian walk, its drawdown and its horizons, simple compounding only");
   constexpr int N4 = 4 * NB;
   // ANTI (SPEC.md 2.3): a lane's PPT draws feed EM = 2 PPT members -- slot e < PPT walks on z[e], slot PPT + e on -z[e]; p, live and
   // the counters are per draw (a.path_begin and a.n_paths count pairs), the members 2 p and 2 p + 1 are adjacent in the output rows
@@ -55,6 +57,17 @@
   constexpr bool LDS_B = JP && LDS_MU && !LDS_W;
   if constexpr (LDS_B) {
     if (threadIdx.x < N4) s_par0[N4 + threadIdx.x] = ((cfloat_p)jump_args(a)->loading)[threadIdx.x];
+  }
+  // RS: the drift of regime 1 (SPEC.md 4.13) takes the same N4 floats behind the drift; the factor of regime 1 follows it in the
+  // regime block and is fed as the packed block's own, by scalar loads inside the step (no SGPR is held across steps for it)
+  constexpr bool LDS_R = RS && LDS_MU && !LDS_W;
+  cfloat_p mu1 = nullptr, L1p = nullptr;
+  if constexpr (RS) {
+    mu1 = (cfloat_p)regime_args(a)->block1;
+    L1p = mu1 + N4;
+  }
+  if constexpr (LDS_R) {
+    if (threadIdx.x < N4) s_par0[N4 + threadIdx.x] = mu1[threadIdx.x];
   }
   // statistics epilogue (N3): per-wave moment accumulators and the digit-0 histogram of one portfolio at a time
   __shared__ uint32_t s_hist[MCP_SELECT_BINS];
@@ -117,6 +130,7 @@
     float Ps[PPT][N4];                                    // OV: the assets' price levels P_i (SPEC.md 4.8)
     float gh[PPT];                                        // GV, FH: the variance ratio h of SPEC.md 4.9 / 4.11
     f32x2 At[PPT][N4 / 2];                                // AT: the assets' contributions A_i of SPEC.md 4.10
+    uint32_t rg[PPT];                                     // RS: the regime of the next step (SPEC.md 2.6); s_0 is drawn in step 0
 #pragma unroll
     for (int e = 0; e < PPT; e++) {
       p[e] = tl * tile + (uint64_t)e * PATH_BLOCK + threadIdx.x;
@@ -128,6 +142,7 @@
       if constexpr (BOOT) jrow[e] = 0u;                   // replaced at t = 0 (a restart)
       if constexpr (GV) gh[e] = garch_args(a)->h0;        // one scalar load per tile
       if constexpr (FH) gh[e] = filt_args(a)->h0;
+      if constexpr (RS) rg[e] = 0u;                       // replaced at t = 0
       if constexpr (REB) {
 #pragma unroll
         for (int m = 0; m < N4 / 2; m++) Bs[e][m] = f32x2{0.0f, 0.0f};

@@ -46,18 +46,19 @@ template <int KT>
 static hipError_t ladder(const PathKernel& k, const PathLaunchArgs& s, hipStream_t stream) {
   constexpr int NB = MCP_NB;
   const bool lg = k.logc;
-  const bool gauss = !k.boot && !k.stt && !k.gv && !k.jp;                      // Gaussian draws
-  const bool j = k.jp && !k.boot && !k.stt && !k.gv;                           // Gaussian draws and the market jump (SPEC.md 2.5)
+  const bool gauss = !k.boot && !k.stt && !k.gv && !k.jp && !k.rs;             // Gaussian draws
+  const bool j = k.jp && !k.rs && !k.boot && !k.stt && !k.gv;                  // Gaussian draws and the market jump (SPEC.md 2.5)
+  const bool r = k.rs && !k.jp && !k.boot && !k.stt && !k.gv;                  // Gaussian draws on the regime's drift and factor (SPEC.md 2.6)
   const bool t = k.stt && !k.gv && !k.boot, g = k.gv && !k.boot;                // Student-t draws; GARCH (nu = 0: Gaussian draws)
   const bool bl = k.boot && k.blds && !k.stt && !k.gv && !k.fh, bg = k.boot && !k.blds && !k.stt && !k.gv && !k.fh;   // rows from LDS / global memory
   if (k.fh) {                                             // SPEC.md 4.11: filtered rows, with or without horizons (H = 0: one segment)
-    const bool ok = (k.family == FAM_PLAIN || k.family == FAM_HZ) && k.boot && !k.stt && !k.gv && !k.jp && !k.native && !k.anti && !lg;
+    const bool ok = (k.family == FAM_PLAIN || k.family == FAM_HZ) && k.boot && !k.stt && !k.gv && !k.jp && !k.rs && !k.native && !k.anti && !lg;
     MCP_ROW(ok && k.blds, mc_paths_fhs_kernel<NB, KT, 1, true>);
     MCP_ROW(ok && !k.blds, mc_paths_fhs_kernel<NB, KT, 1, false>);
     return hipErrorInvalidValue;
   }
   if (k.anti) {                                           // SPEC.md 2.3: gv names the GARCH walk, which also serves Student-t requests
-    const bool lean = gauss && !k.native, gw = k.stt && k.gv && !k.jp && !k.boot && !k.native && !lg;
+    const bool lean = gauss && !k.native, gw = k.stt && k.gv && !k.jp && !k.rs && !k.boot && !k.native && !lg;
     switch (k.family) {
       case FAM_PLAIN:
         MCP_ROW(lean && lg, mc_paths_anti_kernel<NB, KT, 1, true, PathArgsA>);
@@ -89,6 +90,7 @@ static hipError_t ladder(const PathKernel& k, const PathLaunchArgs& s, hipStream
       MCP_ROW(t && !lg, mc_paths_t_kernel<NB, KT, 1>);
       MCP_ROW(g && !lg, mc_paths_g_kernel<NB, KT, 1>);
       MCP_ROW(j && !lg, mc_paths_j_kernel<NB, KT, 1>);
+      MCP_ROW(r && !lg, mc_paths_r_kernel<NB, KT, 1>);
       MCP_ROW(bl && lg, mc_paths_boot_kernel<NB, KT, 1, true, true>);
       MCP_ROW(bl && !lg, mc_paths_boot_kernel<NB, KT, 1, false, true>);
       MCP_ROW(bg && lg, mc_paths_boot_kernel<NB, KT, 1, true, false>);
@@ -100,6 +102,7 @@ static hipError_t ladder(const PathKernel& k, const PathLaunchArgs& s, hipStream
       MCP_ROW(t && !lg, mc_paths_t_dd_kernel<NB, KT, 1>);
       MCP_ROW(g && !lg, mc_paths_g_dd_kernel<NB, KT, 1>);
       MCP_ROW(j && !lg, mc_paths_j_dd_kernel<NB, KT, 1>);
+      MCP_ROW(r && !lg, mc_paths_r_dd_kernel<NB, KT, 1>);
       break;
     case FAM_HZ:
       MCP_ROW(gauss && lg, mc_paths_hz_kernel<NB, KT, 1, true>);
@@ -107,6 +110,7 @@ static hipError_t ladder(const PathKernel& k, const PathLaunchArgs& s, hipStream
       MCP_ROW(t && !lg, mc_paths_t_hz_kernel<NB, KT, 1>);
       MCP_ROW(g && !lg, mc_paths_g_hz_kernel<NB, KT, 1>);
       MCP_ROW(j && !lg, mc_paths_j_hz_kernel<NB, KT, 1>);
+      MCP_ROW(r && !lg, mc_paths_r_hz_kernel<NB, KT, 1>);
       MCP_ROW(bl && lg, mc_paths_boot_hz_kernel<NB, KT, 1, true, true>);
       MCP_ROW(bl && !lg, mc_paths_boot_hz_kernel<NB, KT, 1, false, true>);
       MCP_ROW(bg && lg, mc_paths_boot_hz_kernel<NB, KT, 1, true, false>);
@@ -138,6 +142,7 @@ hipError_t MCP_CAT(launch_paths_nb, MCP_NB)(const PathKernel& k, const PathLaunc
   if (k.anti && (k.fold || k.family == FAM_AT)) return hipErrorInvalidValue;
   if (k.fh && (k.fold || k.family == FAM_AT)) return hipErrorInvalidValue;
   if (k.jp && (k.fold || k.uhi || k.native || k.anti || k.fh || k.family == FAM_AT)) return hipErrorInvalidValue;
+  if (k.rs && (k.fold || k.uhi || k.native || k.anti || k.fh || k.family == FAM_AT)) return hipErrorInvalidValue;
   if (k.fold) {                                            // rho = c + v.z: the plain Gaussian walk on the spec's normals
     const bool ok = k.family == FAM_PLAIN && !k.boot && !k.stt && !k.gv && !k.native && !k.kt8;
     MCP_ROW(ok && k.logc, mc_paths_kernel<NB, 1, 1, false, true, true>);

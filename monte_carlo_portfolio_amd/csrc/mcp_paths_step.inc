@@ -13,7 +13,9 @@
 // chain from the same mu2 -- never a shared L z, mu + L z and mu - L z round differently.  FH: the gathered row is a residual, r_i = fma(sqrt(h),
 // E_ji, mu_i) with mu from the packed block by scalar loads, and after the update of V h moves on the row's shock (SPEC.md 4.11).  In scope: everything mcp_paths_body.inc
 // declares before its step loops, and t.  JP: one more Philox block on counter stream 3 before the asset normals gives
-// the step's market jump J, and the row pair's accumulator starts at fma(b, J, mu) (SPEC.md 2.5 / 4.12).  UHI: the same step with p_hi a scalar (philox4x32_10_uhi), the drift read through the LDS address
+// the step's market jump J, and the row pair's accumulator starts at fma(b, J, mu) (SPEC.md 2.5 / 4.12).  RS: one more Philox block on
+// counter stream 4 before the asset normals gives the step's regime s_t and the next step's; the row pair's chain runs on (mu, L) where the
+// wave has a lane in regime 0 and then, under `if (s_t)`, on (mu1, L1) -- each a whole chain of its own, nothing shared (SPEC.md 2.6 / 4.13).  UHI: the same step with p_hi a scalar (philox4x32_10_uhi), the drift read through the LDS address
 // par_lds instead of the opaque zero offset, and the blocks scheduled one at a time.
       float rho[EM][KT];
       float fsh[PPT];                                  // FH: the shock s_j of the step's row (SPEC.md 2.4)
@@ -103,6 +105,24 @@
           const float nf = (float)n;
           const float g = normal_icdf(x[1], s_tab, kc);
           jmp[e] = fma32(sqrtf(nf) * j_s, g, nf * j_m);
+        }
+      }
+      bool rcur[PPT], rany0[PPT];                      // RS: is the step's regime s_t of SPEC.md 2.6 regime 1?  has the wave a lane in regime 0?
+      if constexpr (RS) {
+        // SPEC.md 2.6: one Philox block on counter (t, 4, p_lo, p_hi); s_0 = x1 < thr_start at t = 0, then s_{t+1} from x0 and the row
+        // s_t of the transition matrix (uint64 compares against wave-uniform thresholds in [0, 2^32], scalar loads).  Formed before
+        // the asset normals: only s_t and s_{t+1} stay live while they are.
+        asm volatile("" : "+s"(mu1), "+s"(L1p));
+        const cregime_p rk = regime_args(a);
+        const uint64_t r01 = rk->thr01, r10 = rk->thr10, r_start = rk->thr_start;
+#pragma unroll
+        for (int e = 0; e < PPT; e++) {
+          uint32_t x[4];
+          philox4x32_10((uint32_t)t, 4u, plo[e], phi[e], ks, x);
+          const uint32_t cur = t == 0 ? ((uint64_t)x[1] < r_start ? 1u : 0u) : rg[e];
+          rg[e] = cur == 0u ? ((uint64_t)x[0] < r01 ? 1u : 0u) : ((uint64_t)x[0] < r10 ? 0u : 1u);
+          rcur[e] = cur != 0u;
+          rany0[e] = __ballot(cur == 0u) != 0ull;
         }
       }
       float z[PPT][N4];
@@ -205,6 +225,35 @@
 #pragma unroll
       for (int m = 0; m < N4 / 2; m++) {
         f32x2 acc[EM];
+        if constexpr (RS) {
+          // SPEC.md 4.13: row i is acc = mu^(s)_i, then fma(L^(s)_ij, z_j, acc), j ascending, s = s_t.  Two whole chains, each fed
+          // as the plain kernel's (the factor an SGPR pair): regime 0's where the wave has a lane in regime 0 (a scalar branch; it
+          // runs on every lane, those of regime 1 drop it), then regime 1's under the mask of its lanes, from mu1 -- never from the
+          // other chain's sums -- skipped where no lane is in regime 1.  So a wave in one regime pays one chain.
+#pragma unroll
+          for (int e = 0; e < PPT; e++) {
+            f32x2 c;
+            if constexpr (LDS_MU) c = *(const f32x2*)&s_par[2 * m];
+            else c = f32x2{mu[2 * m], mu[2 * m + 1]};
+            if (rany0[e]) {
+#pragma unroll
+              for (int j = 0; j <= 2 * m + 1; j++) {
+                const f32x2 l2 = {Lp[2 * m * (m + 1) + 2 * j], Lp[2 * m * (m + 1) + 2 * j + 1]};
+                c = __builtin_elementwise_fma(l2, (f32x2){z[e][j], z[e][j]}, c);
+              }
+            }
+            if (rcur[e]) {
+              if constexpr (LDS_R) c = *(const f32x2*)&s_par[N4 + 2 * m];
+              else c = f32x2{mu1[2 * m], mu1[2 * m + 1]};
+#pragma unroll
+              for (int j = 0; j <= 2 * m + 1; j++) {
+                const f32x2 l2 = {L1p[2 * m * (m + 1) + 2 * j], L1p[2 * m * (m + 1) + 2 * j + 1]};
+                c = __builtin_elementwise_fma(l2, (f32x2){z[e][j], z[e][j]}, c);
+              }
+            }
+            acc[e] = c;
+          }
+        } else {
         f32x2 mu2;
         if constexpr (LDS_MU) mu2 = *(const f32x2*)&s_par[2 * m];
         else mu2 = f32x2{mu[2 * m], mu[2 * m + 1]};
@@ -232,6 +281,7 @@
             for (int e = 0; e < PPT; e++) acc[PPT + e] = __builtin_elementwise_fma(l2, (f32x2){-z[e][j], -z[e][j]}, acc[PPT + e]);
           }
         }
+        }  // !RS
         if constexpr (REB) {
 #pragma unroll
           for (int e = 0; e < PPT; e++) {

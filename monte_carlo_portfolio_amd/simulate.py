@@ -65,8 +65,8 @@ class Context:
 
     def _call(self, prm: _ffi.McpParams, W, seed: int, path_begin: int, n_paths: int, store: bool, mu=None, chol=None, rows=None,
               block: float = 1.0, dof=None, period=None, cost: float = 0.0, drawdown: bool = False, horizons=None, levels=(),
-              flows=None, target=None, overlay=None, garch=None, attribution=False, antithetic=False, filtered=None, jumps=None):
-        """The one library call behind every simulate_* method: market jumps (jumps: the (intensity, mean, std, loading or None) of check_jumps), GARCH volatility (garch: the (alpha, beta, h0) of check_garch), an option overlay (overlay: the triple of check_overlay), cash flows (flows, target), Student-t draws (dof), rebalancing
+              flows=None, target=None, overlay=None, garch=None, attribution=False, antithetic=False, filtered=None, jumps=None, regimes=None):
+        """The one library call behind every simulate_* method: two regimes (regimes: the (p01, p10, start, mu1, chol1) of check_regimes), market jumps (jumps: the (intensity, mean, std, loading or None) of check_jumps), GARCH volatility (garch: the (alpha, beta, h0) of check_garch), an option overlay (overlay: the triple of check_overlay), cash flows (flows, target), Student-t draws (dof), rebalancing
         (period, cost), bootstrap rows (rows, block) or Gaussian draws (mu, chol), with the drawdown or horizons.  Allocates the
         outputs that were asked for and passes NULL for the rest -> _Outputs, None where not asked for (terminal, qd,
         horizon_terminal: with `store` only; counts, hz_counts: with `flows` only; attr [K, N] records of ATTR_DTYPE and attr_counts
@@ -102,6 +102,15 @@ class Context:
             gv = _ffi.McpGarch(float(garch[0]), float(garch[1]), float(garch[2]), 0)
             rc = lib.mcp_simulate_filtered(self._h, prm_p, ctypes.byref(ft), ctypes.byref(gv), ptr(W), *walk, *hz_in, ptr(term), ptr(stats),
                                            *hz_out)
+        elif regimes is not None:
+            # SPEC.md 2.6 / 4.13: the library states the rules (check_request); Gaussian draws with the drawdown or horizons only
+            if (overlay is not None or flows is not None or period is not None or bt is not None or dof is not None or attribution
+                    or antithetic or garch is not None or jumps is not None):
+                raise ValueError("regimes are not combined with overlay, cashflow, rebalance, bootstrap rows, dof, garch, jumps, "
+                                 "attribution or antithetic")
+            rs = _ffi.make_regimes(*regimes)
+            rc = lib.mcp_simulate_regimes(self._h, prm_p, ctypes.byref(rs), ptr(mu), ptr(chol), ptr(W), *walk, *hz_in, ptr(term),
+                                          ptr(stats), ptr(raw), ptr(dd_stats), *hz_out)
         elif jumps is not None:
             # SPEC.md 2.5 / 4.12: the library states the rules (check_request); Gaussian draws with the drawdown or horizons only
             if (overlay is not None or flows is not None or period is not None or bt is not None or dof is not None or attribution
@@ -240,6 +249,15 @@ class Context:
         blocks not asked for are None."""
         return self._call(prm, W, seed, path_begin, n_paths, store, mu=mu, chol=chol, drawdown=drawdown, horizons=horizons,
                           levels=levels, jumps=jumps)
+
+    def simulate_regimes(self, prm: _ffi.McpParams, regimes, mu, chol, W, seed: int, path_begin: int, n_paths: int, store: bool,
+                         drawdown: bool = False, horizons=None, levels=()):
+        """simulate() / simulate_drawdown() / simulate_horizons() on the two regimes of SPEC.md 2.6: `regimes` is (p01, p10, start, mu1,
+        chol1) with mu1 binary32 [N] and chol1 binary32 [N, N], the drift and lower Cholesky factor of regime 1; `mu` and `chol` are
+        regime 0 (SPEC.md 4.13 / 5.13; include/mcport.h, mcp_simulate_regimes; simple compounding only) -> _Outputs; the entries of
+        the blocks not asked for are None."""
+        return self._call(prm, W, seed, path_begin, n_paths, store, mu=mu, chol=chol, drawdown=drawdown, horizons=horizons,
+                          levels=levels, regimes=regimes)
 
     def simulate_filtered(self, prm: _ffi.McpParams, filtered, garch, W, block: float, seed: int, path_begin: int, n_paths: int,
                           store: bool, horizons=None, levels=()):
@@ -475,6 +493,45 @@ def check_jumps(jumps, n_assets):
     return vals[0], vals[1], vals[2], loading
 
 
+def check_regimes(regimes, n_assets, factor=False):
+    """SPEC.md 2.6 argument rules -> None (no regimes) or (p01, p10, start, mu1 float32 [N], L1 float32 [N, N]).  `regimes` is (p01,
+    p10, mu1, cov1) or (p01, p10, mu1, cov1, start); factor=True (the call passed chol=): the fourth entry is regime 1's lower
+    Cholesky factor chol1, taken untouched, instead of its covariance.  start=None or absent: the stationary p01 / (p01 + p10), 0 if
+    both are 0.  ValueError otherwise (not a sequence of 4 or 5 entries, a bool or a string among the probabilities, a probability
+    that is not finite or outside [0, 1], mu1 or cov1 of another shape or not finite, in binary32 too, cov1 not positive definite)."""
+    if regimes is None:
+        return None
+    def msg():                                               # formatted on failure only: the tuple holds arrays
+        return f"regimes must be (p01, p10, mu1, cov1) or (p01, p10, mu1, cov1, start), got {regimes!r}"
+    if isinstance(regimes, (str, bytes)) or not hasattr(regimes, "__len__") or len(regimes) not in (4, 5):
+        raise ValueError(msg())
+    n = int(n_assets)
+    probs = [regimes[0], regimes[1]] + ([regimes[4]] if len(regimes) == 5 and regimes[4] is not None else [])
+    vals = []
+    for v in probs:
+        if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, float, np.integer, np.floating)):
+            raise ValueError(msg())
+        if not np.isfinite(v) or not 0.0 <= float(v) <= 1.0:
+            raise ValueError(f"regimes p01, p10 and start must be probabilities in [0, 1], got {v!r}")
+        vals.append(float(v))
+    p01, p10 = vals[0], vals[1]
+    start = vals[2] if len(vals) == 3 else (p01 / (p01 + p10) if p01 + p10 > 0 else 0.0)
+    try:
+        with np.errstate(over="ignore"):
+            mu64, c64 = np.asarray(regimes[2], np.float64), np.asarray(regimes[3], np.float64)
+            mu1 = np.ascontiguousarray(np.atleast_1d(mu64).astype(np.float32)).ravel()
+            c32 = np.atleast_2d(c64).astype(np.float32)
+    except (TypeError, ValueError):
+        raise ValueError(msg()) from None
+    if mu1.size != n or c32.shape != (n, n):
+        raise ValueError(f"regimes mu1 must hold {n} numbers and {'chol1' if factor else 'cov1'} be [{n}, {n}], got shapes "
+                         f"{np.shape(regimes[2])} and {np.shape(regimes[3])}")
+    if not (np.all(np.isfinite(mu64)) and np.all(np.isfinite(c64)) and np.all(np.isfinite(mu1)) and np.all(np.isfinite(c32))):
+        raise ValueError("regimes mu1 and cov1 must be finite, in binary32 too")
+    L1 = np.ascontiguousarray(np.tril(c32), np.float32) if factor else cholesky_factor(np.atleast_2d(c64))
+    return p01, p10, start, mu1, L1
+
+
 def check_rebalance(rebalance, rebalance_cost):
     """SPEC.md 4.5 argument rules -> (period, cost): period None (constant weights, no rebalancing), 0 (rebalance="never": bought
     and held) or the int k >= 1 of rebalance=k (traded back to the weights every k steps); cost in [0, 1).  ValueError otherwise."""
@@ -606,7 +663,7 @@ def simulate_paths(mu, cov, weights, n_steps=252, n_paths=10_000, seed=0, v0=1.0
                    rf=0.0, alpha=0.95, devices=None, store=False, path_begin=0, chol=None,
                    native_math=False, as_array=False, fold=False, shard="auto", context=None, drawdown=False,
                    horizons=None, bands=(), rebalance=None, rebalance_cost=0.0, dof=None, cashflow=None, target=None,
-                   overlay=None, spot=None, garch=None, attribution=False, antithetic=False, jumps=None):
+                   overlay=None, spot=None, garch=None, attribution=False, antithetic=False, jumps=None, regimes=None):
     """Simulate `n_paths` correlated return paths and reduce them to risk statistics.
 
     mu [N], cov [N,N] are per-step mean and covariance (the reference's `mean_returns`, `cov_matrix`
@@ -716,7 +773,38 @@ def simulate_paths(mu, cov, weights, n_steps=252, n_paths=10_000, seed=0, v0=1.0
     variance)}.  Not built: jumps with dof, garch, rebalance, cashflow, overlay, attribution, antithetic, fold, native_math or
     compounding="log" (ValueError), on bootstrap or filtered paths (the rows carry their own jumps), in PathEngine and at the
     mcp_launch_* level; jumps with cashflow -- ruin under crash risk -- is the obvious next step.
+
+    regimes=None (default): one mean and one covariance for the whole walk.  regimes=(p01, p10, mu1, cov1) or (p01, p10, mu1, cov1,
+    start): two-regime Markov switching (Hamilton 1989; SPEC.md 2.6 / 4.13).  Every path carries a regime, 0 (calm) or 1 (crisis),
+    that moves once per step with P(0 -> 1) = p01 and P(1 -> 0) = p10; a step in regime 0 draws r = mu + L z, a step in regime 1
+    r = mu1 + L1 z: `mu` and `cov` are regime 0, mu1 [N] and cov1 [N, N] regime 1 (factored in float64 like cov; ValueError when it
+    is not positive definite) -- a crisis that lasts 1 / p10 steps on average, in which means, volatilities and correlations all
+    change.  start = P(regime 1 in the first step), default the stationary p01 / (p01 + p10) (0 if both are 0).  With an explicit
+    chol= the fourth entry is read the same way: regimes=(p01, p10, mu1, chol1[, start]), chol1 the lower Cholesky factor of regime 1,
+    taken untouched as chol is.  All portfolios and assets of a path share its regime.  The asset normals are the Gaussian call's own
+    (common random numbers with the same seed); identical regimes, or start = 0 with p01 = 0, are the Gaussian call bit for bit.
+    regimes.fit_regimes(returns) estimates everything from return rows, its `start` from the last row ("today's regime").  The
+    result has the shape of the same call without it (drawdown, horizons / bands, store, as_array, devices and shard all combine); every
+    dict gains 'regimes' {p01, p10, start: as the kernels use them (multiples of 2^-32), stationary: the long-run probability of
+    regime 1, mean_duration: (1 / p01, 1 / p10) expected steps in regime 0 and 1 (inf where the probability is 0) and, with
+    horizons, occupancy: per horizon h the expected share of the first h steps walked in regime 1}.  Not built: regimes with dof,
+    garch, jumps, rebalance, cashflow, overlay, attribution, antithetic, fold, native_math or compounding="log" (ValueError), on
+    bootstrap or filtered paths, in PathEngine and at the mcp_launch_* level.
     """
+    rv = check_regimes(regimes, len(np.atleast_1d(np.asarray(mu))), factor=chol is not None)
+    if rv is not None:
+        bad = [name for name, on in (("dof", dof is not None), ("garch", garch is not None), ("jumps", jumps is not None),
+                                     ("rebalance", rebalance is not None), ("cashflow", cashflow is not None),
+                                     ("overlay", overlay is not None), ("attribution", bool(attribution)),
+                                     ("antithetic", bool(antithetic)), ("fold", fold), ("native_math", native_math),
+                                     ("compounding='log'", compounding == "log")) if on]
+        if bad:
+            raise ValueError("regimes need Gaussian draws, constant weights, simple compounding, the spec's normals and the unfolded "
+                             f"recurrence: not with {', '.join(bad)}")
+        with np.errstate(over="ignore"):
+            if not (np.all(np.isfinite(np.asarray(mu, np.float64))) and np.all(np.isfinite(np.asarray(mu, np.float64).astype(np.float32)))
+                    and np.all(np.isfinite(np.asarray(cov if chol is None else chol, np.float64)))):
+                raise ValueError("regimes need finite mu and cov")
     jv = check_jumps(jumps, len(np.atleast_1d(np.asarray(mu))))
     if jv is not None:
         bad = [name for name, on in (("dof", dof is not None), ("garch", garch is not None), ("rebalance", rebalance is not None),
@@ -784,12 +872,29 @@ def simulate_paths(mu, cov, weights, n_steps=252, n_paths=10_000, seed=0, v0=1.0
                       "paths" if attribution or antithetic else shard, context)
     out = ctx._call(prm, W, int(seed), int(path_begin), int(n_paths), store, mu=mu32, chol=L, dof=dof, period=period, cost=cost,
                     drawdown=drawdown, horizons=steps, levels=levels, flows=flows, target=target, overlay=ov, garch=gv,
-                    attribution=bool(attribution), antithetic=bool(antithetic), jumps=jv)
+                    attribution=bool(attribution), antithetic=bool(antithetic), jumps=jv, regimes=rv)
     res = _result(out, np.asarray(weights).ndim == 1, store, as_array, steps, levels, compounding, flows, target)
     if jv is not None and not as_array:
         for d, blk in zip([res] if isinstance(res, dict) else res, _jump_blocks(jv, L, W)):
             d["jumps"] = blk
+    if rv is not None and not as_array:
+        blk = _regime_block(rv, steps)
+        for d in [res] if isinstance(res, dict) else res:
+            d["regimes"] = dict(blk)
     return res
+
+
+def _regime_block(rv, steps):
+    """The 'regimes' block of a result dict: the probabilities the kernels use (SPEC.md 2.6), the long-run probability of regime 1,
+    the expected steps in each regime and, with horizons, the expected share of the first h steps walked in regime 1."""
+    from .regimes import occupancy_path, stationary, used_probabilities
+    p01, p10, start = used_probabilities(rv[0], rv[1], rv[2])
+    blk = {"p01": p01, "p10": p10, "start": start, "stationary": stationary(p01, p10),
+           "mean_duration": (1.0 / p01 if p01 > 0 else float("inf"), 1.0 / p10 if p10 > 0 else float("inf"))}
+    if steps is not None:
+        cum = np.cumsum(occupancy_path(p01, p10, start, int(steps[-1])))
+        blk["occupancy"] = np.array([cum[h - 1] / h for h in steps.astype(np.int64)], np.float64)
+    return blk
 
 
 def _jump_blocks(jv, L, W):
