@@ -13,6 +13,8 @@
 
 namespace mcp {
 
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+
 constexpr uint32_t PHILOX_M0 = 0xD2511F53u;
 constexpr uint32_t PHILOX_M1 = 0xCD9E8D57u;
 constexpr uint32_t PHILOX_W0 = 0x9E3779B9u;
@@ -26,6 +28,9 @@ constexpr uint32_t PHILOX_W1 = 0xBB67AE85u;
 #endif
 #ifndef MCP_EXP_NORMALS4
 #define MCP_EXP_NORMALS4 1
+#endif
+#ifndef MCP_EXP_ICDF_CENTRED  // 1: the lean kernel runs normal_icdf_centred on a binade-scaled LDS table; 0: normal_icdf (lab builds)
+#define MCP_EXP_ICDF_CENTRED 1
 #endif
 
 // a ^ b ^ c in one VALU instruction (v_bitop3_b32, truth table 0x96).
@@ -142,13 +147,27 @@ struct IcdfConsts {
   uint32_t m18, m31;
   float su, sh;         // the scaling of u: us = fma(v, su, sh)
 };
-// PIN_SCALE: su and sh sit in VGPRs too (otherwise they are literals, and the compiler forms the pair with a v_mov_b64 per step)
-template <bool PIN_SCALE = false>
-__device__ __forceinline__ IcdfConsts icdf_consts() {
-  IcdfConsts c = {0x0003ffffu, 0x7fffffffu, 0x1p-125f, 0x1p-126f};
-  asm volatile("" : "+v"(c.m18), "+v"(c.m31));
-  if constexpr (PIN_SCALE) asm volatile("" : "+v"(c.su), "+v"(c.sh));
-  return c;
+// The constants of normal_icdf_centred: the scaling is y = fma(v, 4, 2), and the bin centre 2^17 of the low 18 mantissa bits sits
+// in a VGPR next to m18.  A type of its own: as one more member of IcdfConsts it moved two instructions of two antithetic kernels.
+struct IcdfCentredConsts : IcdfConsts {
+  uint32_t ctr;
+};
+// PIN_SCALE: su and sh sit in VGPRs too (otherwise they are literals, and the compiler forms the pair with a v_mov_b64 per step).
+// CENTRED: IcdfCentredConsts, everything pinned.
+template <bool PIN_SCALE = false, bool CENTRED = false>
+__device__ __forceinline__ auto icdf_consts() {
+  if constexpr (CENTRED) {
+    IcdfCentredConsts c = {{0x0003ffffu, 0x7fffffffu, 0x1p+2f, 0x1p+1f}, 0x00020000u};
+    asm volatile("" : "+v"(c.m18), "+v"(c.m31));
+    asm volatile("" : "+v"(c.su), "+v"(c.sh));
+    asm volatile("" : "+v"(c.ctr));
+    return c;
+  } else {
+    IcdfConsts c = {0x0003ffffu, 0x7fffffffu, 0x1p-125f, 0x1p-126f};
+    asm volatile("" : "+v"(c.m18), "+v"(c.m31));
+    if constexpr (PIN_SCALE) asm volatile("" : "+v"(c.su), "+v"(c.sh));
+    return c;
+  }
 }
 
 // (a & m) | (b & ~m) in one v_bfi_b32
@@ -173,6 +192,34 @@ __device__ __forceinline__ float normal_icdf(uint32_t x, const float4* tab, cons
   return __uint_as_float(bitselect(k.m31, __float_as_uint(a), x));                  // |a| with the sign of bit 31
 }
 
+// The same transform on ten VALU instructions, bit for bit.  y = fma(v, 4, 2) = u 2^34 has u's significand
+// and the binary32 exponent field 128..160, so table entry i = 32 (E - 1) + (top 5 mantissa bits) has the unbiased exponent
+// E = 1 + i / 32 in [1, 33].  yc is y with its low 18 mantissa bits replaced by the bin centre 2^17: d = y - yc is exact (one
+// binade) and equals dc 2^E, dc the delta of normal_icdf.  `tab` holds entry i SCALED by its binade, {c0, c1 2^-E, c2 2^-2E,
+// c3 2^-3E} (icdf_scaled_entry): a power-of-two scaling commutes with the rounding of an fma while nothing is subnormal or
+// overflows, so the Horner chain on d walks through 2^-2E a, 2^-E a, a with a the chain of normal_icdf
+// (tests/test_icdf_centred_cpu.py checks every entry and every delta).  The table's byte offset is one instruction: bits 14..29
+// of yc are 16 i + 8 (the centre's set bit 17 lands on bit 3; the exponent's always-set top bit is masked off), and the
+// constant part, ICDF_PAD entries less 8 bytes, folds into the ds_read_b128's immediate offset.
+__device__ __forceinline__ uint32_t icdf_centred_offset(uint32_t yc) {
+  return (yc >> 14) & 0xffffu;                           // v_bfe_u32; written on the high word in 16 bits it compiles to two
+}
+constexpr int ICDF_CENTRED_BIAS = ICDF_PAD * 16 - 8;   // byte offset of T[0] in the padded table, less the centre's 8
+__device__ __forceinline__ float4 icdf_scaled_entry(float4 c, int i) {
+  const int e = 1 + i / 32;
+  return make_float4(c.x, __builtin_ldexpf(c.y, -e), __builtin_ldexpf(c.z, -2 * e), __builtin_ldexpf(c.w, -3 * e));
+}
+__device__ __forceinline__ float normal_icdf_centred(uint32_t x, const float4* tab, const IcdfCentredConsts& k) {
+  const float y = fma32((float)(x & 0x7fffffffu), k.su, k.sh);           // u * 2^34: exponent field 128..160
+  const uint32_t yc = bitselect(k.m18, k.ctr, __float_as_uint(y));
+  const float4 c = *(const float4*)((const char*)tab + ICDF_CENTRED_BIAS + icdf_centred_offset(yc));
+  const float d = y - __uint_as_float(yc);
+  float a = fma32(c.w, d, c.z);
+  a = fma32(a, d, c.y);
+  a = fma32(a, d, c.x);
+  return __uint_as_float(bitselect(k.m31, __float_as_uint(a), x));
+}
+
 // MCP_FLAG_NATIVE_MATH: Box-Muller on the hardware approximations (v_log_f32, v_sqrt_f32, v_sin_f32, v_cos_f32) of
 // word pairs.  Statistically equivalent N(0,1) draws from the same Philox stream, but NOT the spec's normals: results
 // are comparable to the oracle only in distribution (tests check moments and Monte-Carlo-level agreement).
@@ -185,13 +232,41 @@ __device__ __forceinline__ void box_muller_native(uint32_t xa, uint32_t xb, floa
   z_cos = s * __builtin_amdgcn_cosf(turns);
 }
 
-// The four normals of one Philox block.
-template <bool NATIVE>
-__device__ __forceinline__ void block_normals(const uint32_t (&x)[4], const float4* tab, const IcdfConsts& k, float& z0, float& z1,
+// The four normals of one Philox block.  CENTRED: by normal_icdf_centred, `tab` the binade-scaled table and k IcdfCentredConsts.
+template <bool NATIVE, bool CENTRED = false, class K = IcdfConsts>
+__device__ __forceinline__ void block_normals(const uint32_t (&x)[4], const float4* tab, const K& k, float& z0, float& z1,
                                               float& z2, float& z3) {
   if constexpr (NATIVE) {
     box_muller_native(x[0], x[1], z0, z1);
     box_muller_native(x[2], x[3], z2, z3);
+  } else if constexpr (CENTRED) {
+    // as below: the four table reads issued together, ahead of everything that depends on them, the four chains interleaved
+    uint32_t yc[4];
+    float4 c[4];
+    float y[4], d[4], a[4];
+#pragma unroll
+    for (int i = 0; i < 4; i += 2) {                       // the scaling as one v_pk_fma_f32 per pair, as the compiler forms it below
+      const f32x2 v2 = {(float)(x[i] & 0x7fffffffu), (float)(x[i + 1] & 0x7fffffffu)};
+      const f32x2 y2 = __builtin_elementwise_fma(v2, (f32x2){k.su, k.su}, (f32x2){k.sh, k.sh});
+      y[i] = y2.x; y[i + 1] = y2.y;
+    }
+#pragma unroll
+    for (int i = 0; i < 4; i++) yc[i] = bitselect(k.m18, k.ctr, __float_as_uint(y[i]));
+#pragma unroll
+    for (int i = 0; i < 4; i++) c[i] = *(const float4*)((const char*)tab + ICDF_CENTRED_BIAS + icdf_centred_offset(yc[i]));
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int i = 0; i < 4; i++) d[i] = y[i] - __uint_as_float(yc[i]);
+#pragma unroll
+    for (int i = 0; i < 4; i++) a[i] = fma32(c[i].w, d[i], c[i].z);
+#pragma unroll
+    for (int i = 0; i < 4; i++) a[i] = fma32(a[i], d[i], c[i].y);
+#pragma unroll
+    for (int i = 0; i < 4; i++) a[i] = fma32(a[i], d[i], c[i].x);
+    z0 = __uint_as_float(bitselect(k.m31, __float_as_uint(a[0]), x[0]));
+    z1 = __uint_as_float(bitselect(k.m31, __float_as_uint(a[1]), x[1]));
+    z2 = __uint_as_float(bitselect(k.m31, __float_as_uint(a[2]), x[2]));
+    z3 = __uint_as_float(bitselect(k.m31, __float_as_uint(a[3]), x[3]));
   } else {
 #if MCP_EXP_NORMALS4
     // the same four transforms with the four table reads issued together, ahead of everything that depends on them

@@ -69,8 +69,6 @@
 
 namespace mcp {
 
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-
 #ifdef MCP_DIAG_CLOCK
 // Diagnostic build only (tools/clock_probe.py; MI355X_MICROARCH.md, DVFS give-back item 6): every workgroup of mc_paths_kernel
 // stamps s_memtime (shader cycles) and s_memrealtime (100 MHz) around its step loops into a buffer of its own that nothing

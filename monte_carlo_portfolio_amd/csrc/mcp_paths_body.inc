@@ -24,8 +24,13 @@
   cfloat_p Wk = mu + N4 + N4 * (N4 / 2 + 1) + (size_t)a.k_begin * N4;
   const int kt = min(KT, a.n_portfolios - a.k_begin);   // live portfolios in this pass (uniform)
   // inverse-CDF table: 16.5 KiB of LDS per block, filled once from the device-resident copy
+  // CEN: the lean kernel's copy is scaled by each entry's binade as it is filled, for normal_icdf_centred (exact; once per workgroup,
+  // nothing of it lives in the step loop)
+  constexpr bool CEN = UHI && MCP_EXP_ICDF_CENTRED != 0;
   __shared__ float4 s_tab[ICDF_LDS_ENTRIES];
-  if constexpr (!NATIVE && !BOOT) {
+  if constexpr (CEN) {
+    for (int i = threadIdx.x; i < ICDF_ENTRIES; i += PATH_BLOCK) s_tab[ICDF_PAD + i] = icdf_scaled_entry(a.tables[i], i);
+  } else if constexpr (!NATIVE && !BOOT) {
     for (int i = threadIdx.x; i < ICDF_ENTRIES; i += PATH_BLOCK) s_tab[ICDF_PAD + i] = a.tables[i];
   }
   // BOOT: the observed rows (SPEC.md 2.1); BLDS: copied into the table's slot, chunk q of row j at j NB + (q ^ s(j))
@@ -94,7 +99,7 @@
     if (threadIdx.x < (PATH_BLOCK / 64) * KT) pair_wave_slots<KT>()[threadIdx.x] = 0.0;
   }
   __syncthreads();
-  const IcdfConsts kc = icdf_consts<UHI>();
+  const auto kc = icdf_consts<UHI, CEN>();
   PhiloxKeys ks = philox_keys((uint32_t)a.seed, (uint32_t)(a.seed >> 32));
 #if MCP_EXP_VKEYS
   // pin the 20 round keys in VGPRs: an SGPR operand halves the issue rate of the xor (profiles/r01_valu_rates.txt)

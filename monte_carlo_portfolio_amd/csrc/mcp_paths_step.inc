@@ -180,7 +180,7 @@
           } else {
             philox4x32_10(blk, 0u, plo[e], phi[e], ks, x);
           }
-          block_normals<NATIVE>(x, s_tab, kc, z[e][0 * NB + q], z[e][1 * NB + q], z[e][2 * NB + q], z[e][3 * NB + q]);
+          block_normals<NATIVE, CEN>(x, s_tab, kc, z[e][0 * NB + q], z[e][1 * NB + q], z[e][2 * NB + q], z[e][3 * NB + q]);
           if constexpr (STT) {                         // SPEC.md 4.6: z' = fl32(s z)
 #pragma unroll
             for (int m = 0; m < 4; m++) z[e][m * NB + q] = st_s[e] * z[e][m * NB + q];

@@ -13,7 +13,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 LAB = os.path.join(ROOT, "tools", "lab_build")
 CSRC = os.path.join(ROOT, "monte_carlo_portfolio_amd", "csrc")
-ARMS = {"lean": "-DMCP_EXP_LEAN=1", "nolean": "-DMCP_EXP_LEAN=0", "nolean2": "-DMCP_EXP_LEAN=0"}
+ARMS = {"lean": "-DMCP_EXP_LEAN=1", "nolean": "-DMCP_EXP_LEAN=0", "nolean2": "-DMCP_EXP_LEAN=0",
+        "centred": "-DMCP_EXP_ICDF_CENTRED=1", "base": "-DMCP_EXP_ICDF_CENTRED=0", "base2": "-DMCP_EXP_ICDF_CENTRED=0"}
 
 
 def build(specs):
@@ -43,7 +44,9 @@ def run(names, paths, rounds, assets, steps, native, stats=True, K=1):
     hist = torch.zeros(base.mcp_ws_bytes(_ffi.WS_HIST, K, paths) // 8, dtype=torch.int64, device="cuda")
     libs = {}
     for n in names:
-        path = _ffi.LIB_PATH if n == "base" else os.path.join(LAB, f"libmcport_{n}.so")
+        path = os.path.join(LAB, f"libmcport_{n}.so")
+        if n == "base" and not os.path.exists(path):
+            path = _ffi.LIB_PATH
         Lb = ctypes.CDLL(path)
         Lb.mcp_launch_paths.restype = ctypes.c_int
         Lb.mcp_launch_paths.argtypes = _ffi.SIGNATURES["mcp_launch_paths"][1]

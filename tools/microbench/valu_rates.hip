@@ -28,7 +28,7 @@ __global__ void __launch_bounds__(256) bench(float* out, unsigned long long* cyc
     v[i] = seedf + 0.001f * (threadIdx.x + i); u[i] = seedu * (threadIdx.x + 7 * i + 1);
     w[i] = u[i]; p[i] = f32x2{v[i], v[i] + 1.f}; acc[i] = f32x4{v[i], 0.f, 1.f, 2.f};
   }
-  float ca = seedf * 0.5f, cb = 0.25f; unsigned cu = seedu | 1u;
+  float ca = seedf * 0.5f, cb = 0.25f; unsigned cu = seedu | 1u, cw = (seedu >> 29) | 2u;
   __shared__ f32x4 ldsbuf[64]; if (threadIdx.x < 64) ldsbuf[threadIdx.x] = f32x4{seedf, ca, cb, 1.f}; __syncthreads();
   unsigned ldsaddr = (unsigned)(size_t)(&ldsbuf[0]) + (blockIdx.x & 1) * 16; f32x2 spv = {seedf, seedf}; unsigned long long sp; __builtin_memcpy(&sp, &spv, 8); sp = __builtin_amdgcn_readfirstlane((unsigned)sp) | ((unsigned long long)__builtin_amdgcn_readfirstlane((unsigned)(sp >> 32)) << 32);
   unsigned long long t0 = __builtin_amdgcn_s_memtime();
@@ -182,6 +182,38 @@ __global__ void __launch_bounds__(256) bench(float* out, unsigned long long* cyc
 #define OP(i) asm volatile("v_cmp_lt_f32_e64 s[20:21], %1, %2\n v_cndmask_b32_e64 %0, %0, %3, s[20:21]" : "+v"(u[i]) : "v"(ca), "v"(v[i]), "v"(cu) : "s20", "s21");
       REP8(OP) REP8(OP)
 #undef OP
+    } else if constexpr (KIND == 34) {   // v_lshrrev_b32 (VOP2, inline shift count)
+#define OP(i) asm volatile("v_lshrrev_b32_e32 %0, 14, %0" : "+v"(u[i]));
+      REP32(OP)
+#undef OP
+    } else if constexpr (KIND == 35) {   // v_bfe_u32, offset and width inline constants
+#define OP(i) asm volatile("v_bfe_u32 %0, %0, 14, 16" : "+v"(u[i]));
+      REP32(OP)
+#undef OP
+    } else if constexpr (KIND == 36) {   // v_bfe_u32, offset and width in VGPRs
+#define OP(i) asm volatile("v_bfe_u32 %0, %0, %1, %2" : "+v"(u[i]) : "v"(cu), "v"(cw));
+      REP32(OP)
+#undef OP
+    } else if constexpr (KIND == 37) {   // v_lshlrev_b16 on the high word of its source (SDWA word select)
+#define OP(i) asm volatile("v_lshlrev_b16_sdwa %0, %1, %0 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:WORD_1" : "+v"(u[i]) : "v"(cw));
+      REP32(OP)
+#undef OP
+    } else if constexpr (KIND == 38) {   // v_bfi_b32, all VGPR
+#define OP(i) asm volatile("v_bfi_b32 %0, %1, %2, %0" : "+v"(u[i]) : "v"(cu), "v"(cw));
+      REP32(OP)
+#undef OP
+    } else if constexpr (KIND == 39) {   // v_and_or_b32, all VGPR
+#define OP(i) asm volatile("v_and_or_b32 %0, %0, %1, %2" : "+v"(u[i]) : "v"(cu), "v"(cw));
+      REP32(OP)
+#undef OP
+    } else if constexpr (KIND == 40) {   // v_sub_f32, all VGPR
+#define OP(i) asm volatile("v_sub_f32_e32 %0, %0, %1" : "+v"(v[i]) : "v"(ca));
+      REP32(OP)
+#undef OP
+    } else if constexpr (KIND == 41) {   // v_lshrrev_b32 writing the low word only (SDWA destination select): shift and 16-bit mask in one
+#define OP(i) asm volatile("v_lshrrev_b32_sdwa %0, %1, %0 dst_sel:WORD_0 dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:DWORD" : "+v"(u[i]) : "v"(cw));
+      REP32(OP)
+#undef OP
     }
   }
   unsigned long long t1 = __builtin_amdgcn_s_memtime();
@@ -256,5 +288,13 @@ int main() {
   run<31>("v_pk_mul_f32", 32, d_out, d_cyc, num_cu);
   run<32>("v_bfe_i32", 32, d_out, d_cyc, num_cu);
   run<33>("v_cmp_e64+v_cndmask_e64 (16 pairs)", 32, d_out, d_cyc, num_cu);
+  run<34>("v_lshrrev_b32_e32 inline", 32, d_out, d_cyc, num_cu);
+  run<35>("v_bfe_u32 inline", 32, d_out, d_cyc, num_cu);
+  run<36>("v_bfe_u32 vgpr", 32, d_out, d_cyc, num_cu);
+  run<37>("v_lshlrev_b16_sdwa src WORD_1", 32, d_out, d_cyc, num_cu);
+  run<38>("v_bfi_b32 vgpr", 32, d_out, d_cyc, num_cu);
+  run<39>("v_and_or_b32 vgpr", 32, d_out, d_cyc, num_cu);
+  run<40>("v_sub_f32_e32 vgpr", 32, d_out, d_cyc, num_cu);
+  run<41>("v_lshrrev_b32_sdwa dst WORD_0", 32, d_out, d_cyc, num_cu);
   return 0;
 }
