@@ -34,7 +34,8 @@ extern "C" {
                                     + mcp_simulate_antithetic (additive, detected by symbol);
                                     + mcp_simulate_filtered, mcp_filtered_pivots (additive, detected by symbol);
                                     + mcp_simulate_jumps, mcp_jump_consts (additive, detected by symbol);
-                                    + mcp_simulate_regimes, mcp_regime_consts, mcp_regime_pivots (additive, detected by symbol) */
+                                    + mcp_simulate_regimes, mcp_regime_consts, mcp_regime_pivots (additive, detected by symbol);
+                                    + mcp_simulate_glide, mcp_glide_pivots (additive, detected by symbol) */
 #define MCP_MAX_ASSETS 64        /* thread-per-path kernels are instantiated for N4 = 4..64 */
 #define MCP_SELECT_BINS 2048     /* radix-select digit: 11 + 11 + 10 bits */
 #define MCP_MAX_HORIZONS 64      /* mcp_simulate_horizons: horizon steps per call */
@@ -44,6 +45,7 @@ extern "C" {
 #define MCP_MAX_T_DOF 32         /* mcp_simulate_student_t: degrees of freedom in [3, MCP_MAX_T_DOF] */
 #define MCP_MAX_ATTR_PORTFOLIOS 16 /* mcp_simulate_attribution: portfolios per call */
 #define MCP_MAX_JUMPS 8          /* mcp_simulate_jumps: market jumps per path-step (the Poisson count is truncated there) */
+#define MCP_MAX_GLIDE 64         /* mcp_simulate_glide: breaks (changes of the target weights) per call */
 
 enum {
     MCP_OK = 0,
@@ -554,6 +556,48 @@ int mcp_simulate_cashflow(mcp_ctx *ctx, const mcp_params *prm, const mcp_cashflo
  * exact mean of x while no path is ruined. */
 int mcp_cashflow_pivots(const mcp_params *prm, const mcp_cashflow *cf, const float *mu, const mcp_bootstrap *boot,
                         const float *W, double *pivots_out /* [K] */);
+
+/* Glide paths: scheduled target weights (SPEC.md 4.14 / 5.14).  breaks: n_breaks strictly increasing steps in [1, n_steps - 1];
+ * targets: n_breaks blocks of [K][N] finite binary32 weights.  Step s = 1 .. n_steps of portfolio k walks on block g = #{j : breaks[j]
+ * < s}, block 0 being the call's W: W is held through step breaks[0], targets block 0 through step breaks[1], and so on.  The
+ * portfolio stands at its current target at the start of every step; the trade at a break is free.  reserved must be 0. */
+typedef struct {
+    const int32_t *breaks;    /* [n_breaks], strictly increasing, in [1, n_steps - 1]; NULL when n_breaks == 0 */
+    const float *targets;     /* [n_breaks][K][N] row-major, finite; NULL when n_breaks == 0 */
+    int32_t n_breaks;         /* 0 .. MCP_MAX_GLIDE */
+    int32_t reserved;         /* 0 */
+} mcp_glide;
+
+/* mcp_simulate_cashflow on the weights of a glide path: the draws, the recurrence U = fma(V, rho, V) + c_s with absorbing ruin, the
+ * horizons, records, bands and counts are that call's, only the weights of the dot rho_k = sum_i w_ki r_i change at the breaks.  cf
+ * NULL: the all-zero schedule without a target (V stays absorbed at +0 once it is not positive).  n_breaks = 0, or every target block
+ * equal to W, is mcp_simulate_cashflow bit for bit.  The moments are pivoted at SPEC.md 5.14 (mcp_glide_pivots).  Argument errors
+ * (MCP_E_ARG: a NULL struct, n_breaks outside [0, MCP_MAX_GLIDE], NULL breaks or targets with n_breaks > 0, a break outside
+ * [1, n_steps - 1] or not above the one before, a target that is not finite, reserved != 0, and every rule of mcp_simulate_cashflow)
+ * are found before any device is touched; log compounding, MCP_FLAG_FOLD, MCP_FLAG_NATIVE_MATH: MCP_E_UNSUPPORTED.  Not built:
+ * a glide path with the drawdown, rebalancing, the overlay, GARCH, jumps, regimes, filtered rows, the attribution, antithetic pairs,
+ * or at the mcp_launch_* level.  K >= 17 runs as passes of 8 portfolios. */
+int mcp_simulate_glide(mcp_ctx *ctx, const mcp_params *prm, const mcp_glide *gl,
+                       const mcp_cashflow *cf,                /* NULL: all-zero schedule, no target              */
+                       const float *mu, const float *chol,   /* Gaussian or Student-t draws ...                */
+                       const mcp_bootstrap *boot,             /* ... or bootstrap rows: exactly one             */
+                       const mcp_student_t *st,               /* NULL: Gaussian; needs mu and chol              */
+                       const float *W, uint64_t seed, uint64_t path_begin, uint64_t n_paths,
+                       int n_horizons, const int32_t *horizons, int n_levels, const double *levels,
+                       float *terminal_out,        /* NULL or host [K*n_paths] */
+                       mcp_stats *stats_out,       /* [K] */
+                       uint64_t *counts_out,       /* [K][2] {n_ruined, n_short} */
+                       float *horizon_out,         /* NULL or host [H*K*n_paths], row h*K + k */
+                       mcp_stats *hz_stats_out,    /* [H*K], NULL iff n_horizons == 0 */
+                       double *bands_out,          /* [H*K*L], NULL iff n_levels == 0 */
+                       uint64_t *hz_counts_out);   /* [H*K][2], NULL iff n_horizons == 0 */
+/* The shifts of the moments of a glide path (SPEC.md 5.14; host side, binary64 from the binary32 inputs): with m_kg the per-step
+ * mean of mcp_cashflow_pivots on the weights of block g, A_0 = fl32(v0), A_s = A_{s-1} (1 + m_kg(s)) + c_s (a sum, a product, a
+ * sum): max(A, 0) / fl32(v0) - 1, 0 where it is not finite, after step n_steps into pivots_out[k] and after the steps of the
+ * n_horizons horizons into hz_pivots_out[h*K + k] (n_horizons = 0: horizons and hz_pivots_out ignored).  cf NULL: c_s = 0. */
+int mcp_glide_pivots(const mcp_params *prm, const mcp_glide *gl, const mcp_cashflow *cf, const float *mu,
+                     const mcp_bootstrap *boot, const float *W, int n_horizons, const int32_t *horizons,
+                     double *pivots_out /* [K] */, double *hz_pivots_out /* NULL or [H*K] */);
 
 /* Option and hedging overlays (SPEC.md 4.8 / 5.7).  Asset i owns the rows [row_begin[i], row_begin[i+1]) of `rows`, applied in that
  * order; kind LINEAR: leg = price - prev, CALL: leg = max(price - strike, 0) - premium, PUT: leg = max(strike - price, 0) -

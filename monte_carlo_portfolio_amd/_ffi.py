@@ -27,6 +27,7 @@ MCP_MAX_T_DOF = 32
 MCP_MAX_OVERLAY_ROWS = 8
 MCP_MAX_ATTR_PORTFOLIOS = 16
 MCP_MAX_JUMPS = 8
+MCP_MAX_GLIDE = 64
 MCP_OVERLAY_LINEAR, MCP_OVERLAY_CALL, MCP_OVERLAY_PUT = 0, 1, 2
 MCP_COMPOUND = {"simple": 0, "log": 1}
 MCP_FLAG_NATIVE_MATH = 1
@@ -100,6 +101,11 @@ class McpRegimes(ctypes.Structure):
 class McpCashflow(ctypes.Structure):
     """mcp_cashflow: the schedule c_1 .. c_T (binary32, n_flows == n_steps) and the optional target of SPEC.md 4.7 / 5.6."""
     _fields_ = [("flows", ctypes.c_void_p), ("n_flows", ctypes.c_int32), ("has_target", ctypes.c_int32), ("target", ctypes.c_double)]
+
+
+class McpGlide(ctypes.Structure):
+    """mcp_glide: the breaks (int32 [G]) and target weight blocks (binary32 [G, K, N]) of the glide path of SPEC.md 4.14."""
+    _fields_ = [("breaks", ctypes.c_void_p), ("targets", ctypes.c_void_p), ("n_breaks", ctypes.c_int32), ("reserved", ctypes.c_int32)]
 
 
 class McpOverlay(ctypes.Structure):
@@ -200,6 +206,11 @@ SIGNATURES = {
                                      ctypes.POINTER(McpStudentT), _vp, _u64, _u64, _u64, _int, _vp, _int, _vp, _vp, _vp, _vp, _vp, _vp,
                                      _vp, _vp]),
     "mcp_cashflow_pivots": (_int, [_PP, ctypes.POINTER(McpCashflow), _vp, ctypes.POINTER(McpBootstrap), _f32p, _f64p]),
+    "mcp_simulate_glide": (_int, [_vp, _PP, ctypes.POINTER(McpGlide), ctypes.POINTER(McpCashflow), _vp, _vp, ctypes.POINTER(McpBootstrap),
+                                  ctypes.POINTER(McpStudentT), _vp, _u64, _u64, _u64, _int, _vp, _int, _vp, _vp, _vp, _vp, _vp, _vp,
+                                  _vp, _vp]),
+    "mcp_glide_pivots": (_int, [_PP, ctypes.POINTER(McpGlide), ctypes.POINTER(McpCashflow), _vp, ctypes.POINTER(McpBootstrap), _vp, _int,
+                                _vp, _vp, _vp]),
     "mcp_simulate_overlay": (_int, [_vp, _PP, ctypes.POINTER(McpOverlay), _vp, _vp, ctypes.POINTER(McpStudentT), _vp, _u64, _u64, _u64,
                                     _int, _vp, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mcp_overlay_pivots": (_int, [_PP, ctypes.POINTER(McpOverlay), _f32p, _f32p, _f64p]),
@@ -450,6 +461,39 @@ def cashflow_pivots(prm: McpParams, flows: np.ndarray, W: np.ndarray, mu: np.nda
     check(lib().mcp_cashflow_pivots(ctypes.byref(prm), ctypes.byref(cf), mu_p.ctypes.data_as(_vp) if mu_p is not None else None,
                                     ctypes.byref(bt) if bt is not None else None, W, out))
     return out
+
+
+def make_glide(breaks: np.ndarray, targets: np.ndarray) -> McpGlide:
+    """mcp_glide over C-contiguous arrays, breaks int32 [G] and targets binary32 [G, K, N] (the caller keeps them alive for the call)."""
+    if breaks.dtype != np.int32 or breaks.ndim != 1 or not breaks.flags.c_contiguous:
+        raise ValueError("glide breaks must be a C-contiguous int32 [G] array")
+    if targets.dtype != np.float32 or targets.ndim != 3 or targets.shape[0] != breaks.size or not targets.flags.c_contiguous:
+        raise ValueError("glide targets must be a C-contiguous float32 [G, K, N] array")
+    G = int(breaks.size)
+    return McpGlide(breaks.ctypes.data_as(ctypes.c_void_p) if G else None, targets.ctypes.data_as(ctypes.c_void_p) if G else None, G, 0)
+
+
+def glide_pivots(prm: McpParams, breaks, targets, W: np.ndarray, flows=None, mu: np.ndarray | None = None,
+                 rows: np.ndarray | None = None, horizons=None):
+    """([K] pivots at n_steps, [H, K] at the horizons or None): the shifts of the moments of a glide path (SPEC.md 5.14;
+    include/mcport.h, mcp_glide_pivots), pure host arithmetic.  breaks [G], targets [G, K, N]; flows None: no cash flows; pass the
+    drift `mu` (Gaussian and Student-t draws) or the binary32 [R, N] `rows` (bootstrap draws)."""
+    W = np.ascontiguousarray(W, np.float32)
+    breaks = np.ascontiguousarray(breaks, np.int32).ravel()
+    targets = np.ascontiguousarray(targets, np.float32).reshape(breaks.size, W.shape[0], W.shape[1])
+    gl = make_glide(breaks, targets)
+    fl = np.ascontiguousarray(flows, np.float32) if flows is not None else None
+    cf = make_cashflow(fl) if fl is not None else None
+    mu_p = np.ascontiguousarray(mu, np.float32) if mu is not None else None
+    bt = make_bootstrap(np.ascontiguousarray(rows, np.float32), 1.0) if rows is not None else None
+    hz = np.ascontiguousarray(horizons, np.int32) if horizons is not None and len(horizons) else None
+    out = np.zeros(W.shape[0], np.float64)
+    hout = np.zeros((hz.size, W.shape[0]), np.float64) if hz is not None else None
+    ptr = lambda a: a.ctypes.data_as(_vp) if a is not None else None   # noqa: E731
+    check(lib().mcp_glide_pivots(ctypes.byref(prm), ctypes.byref(gl), ctypes.byref(cf) if cf is not None else None, ptr(mu_p),
+                                 ctypes.byref(bt) if bt is not None else None, ptr(W), 0 if hz is None else hz.size, ptr(hz), ptr(out),
+                                 ptr(hout)))
+    return out, hout
 
 
 def make_overlay(rows: np.ndarray, row_begin: np.ndarray, spot: np.ndarray) -> McpOverlay:

@@ -403,6 +403,38 @@ int check_cashflow(const mcp_params* prm, const mcp_cashflow* cf) {
   return MCP_OK;
 }
 
+// SPEC.md 4.14: 0..MCP_MAX_GLIDE strictly increasing breaks in [1, n_steps - 1], n_breaks blocks of [K][N] finite targets, reserved == 0
+int check_glide(const mcp_params* prm, const mcp_glide* gl) {
+  if (!gl) return fail(MCP_E_ARG, "glide is NULL");
+  if (gl->reserved != 0) return fail(MCP_E_ARG, "glide reserved=%d must be 0", gl->reserved);
+  if (gl->n_breaks < 0 || gl->n_breaks > MCP_MAX_GLIDE) return fail(MCP_E_ARG, "n_breaks=%d outside [0,%d]", gl->n_breaks, MCP_MAX_GLIDE);
+  if (gl->n_breaks > 0 && (!gl->breaks || !gl->targets)) return fail(MCP_E_ARG, "glide breaks or targets is NULL");
+  for (int g = 0; g < gl->n_breaks; g++) {
+    if (gl->breaks[g] < 1 || gl->breaks[g] > prm->n_steps - 1)
+      return fail(MCP_E_ARG, "glide break %d = %d outside [1, n_steps - 1 = %d]", g, gl->breaks[g], prm->n_steps - 1);
+    if (g && gl->breaks[g] <= gl->breaks[g - 1])
+      return fail(MCP_E_ARG, "glide breaks must be strictly increasing (%d after %d)", gl->breaks[g], gl->breaks[g - 1]);
+  }
+  const size_t KN = (size_t)prm->n_portfolios * (size_t)prm->n_assets;
+  for (size_t i = 0; i < (size_t)gl->n_breaks * KN; i++)
+    if (!std::isfinite(gl->targets[i]))
+      return fail(MCP_E_ARG, "glide target %zu, portfolio %zu, asset %zu is not finite", i / KN + 1, i % KN / (size_t)prm->n_assets,
+                  i % (size_t)prm->n_assets);
+  return MCP_OK;
+}
+
+// SPEC.md 4.14: the device copy of the target blocks of the portfolios [k0, k0 + kt) -- per block glide_rows(kt) rows of N4 floats, the
+// packed weights' layout with the rows padded to whole passes of 8 (the glide kernels run no MFMA sweep)
+inline size_t glide_rows(int kt) { return (size_t)KT_WIDE * (size_t)((kt + KT_WIDE - 1) / KT_WIDE); }
+inline size_t glide_len(int N, int kt, const mcp_glide* gl) { return (size_t)gl->n_breaks * glide_rows(kt) * (size_t)n4_of(N); }
+void glide_pack(int N, int K, int k0, int kt, const mcp_glide* gl, float* out) {
+  const size_t n4 = (size_t)n4_of(N), blk = glide_rows(kt) * n4;
+  std::fill(out, out + (size_t)gl->n_breaks * blk, 0.0f);
+  for (int g = 0; g < gl->n_breaks; g++)
+    for (int k = 0; k < kt; k++)
+      memcpy(out + (size_t)g * blk + (size_t)k * n4, gl->targets + ((size_t)g * K + (size_t)(k0 + k)) * N, (size_t)N * sizeof(float));
+}
+
 // SPEC.md 4.8: row_begin ascending from 0 to n_rows, at most MCP_MAX_OVERLAY_ROWS rows per asset, kinds 0..2, finite numbers, a
 // positive spot on every asset that owns rows, reserved == 0
 int check_overlay(const mcp_params* prm, const mcp_overlay* ov) {
@@ -508,6 +540,8 @@ struct Request {
   const mcp_rebalance* reb = nullptr;
   bool cash = false;                    // SPEC.md 4.7: the schedule `cf`
   const mcp_cashflow* cf = nullptr;
+  bool glide = false;                   // SPEC.md 4.14: the weight schedule `gl`, always with `cf` (mcp_simulate_glide)
+  const mcp_glide* gl = nullptr;
   bool overlay = false;                 // SPEC.md 4.8: the option rows `ov`
   const mcp_overlay* ov = nullptr;
   bool garch = false;                   // SPEC.md 4.9: the variance recurrence `gv` (SRC_GAUSS or SRC_T)
@@ -582,6 +616,7 @@ struct Launch {
   uint64_t hz_stride = 0;
   const float* d_rows = nullptr;        // bootstrap: [R][N4], zero-padded
   const float* d_flows = nullptr;       // cash flows: [n_steps]
+  const float* d_targets = nullptr;     // glide path: [n_breaks][glide_rows(K)][N4] target blocks (glide_pack)
   const char* d_overlay = nullptr;      // overlay: [rows][row_begin N4 + 1][spot N4] (overlay_pack)
   const float* d_loading = nullptr;     // jumps: [N4] loadings, zero-padded
   const float* d_block1 = nullptr;      // regimes: [mu1 N4][L1 row pairs], the layout of mcp_pack_params
@@ -613,6 +648,16 @@ int check_request(const mcp_params* prm, const Request& rq, uint64_t n_paths, co
       return fail(MCP_E_ARG, "exactly one draw source: mu and chol (with or without student_t), or boot");
     if (!rq.counts_out) return fail(MCP_E_ARG, "counts_out is NULL");
     if ((rq.hz_counts_out == nullptr) != !rq.hz) return fail(MCP_E_ARG, "hz_counts_out must be NULL exactly when n_horizons == 0");
+  }
+  if (rq.glide) {                                              // SPEC.md 4.14: the rules, then what a glide path is not combined with
+    if ((rc = check_glide(prm, rq.gl))) return rc;
+    if (prm->compounding != MCP_COMPOUND_SIMPLE) return fail(MCP_E_UNSUPPORTED, "glide paths compound simply (no log compounding)");
+    if (prm->flags & (MCP_FLAG_FOLD | MCP_FLAG_NATIVE_MATH))
+      return fail(MCP_E_UNSUPPORTED, "glide paths run on the unfolded recurrence and the spec's normals (no MCP_FLAG_FOLD / MCP_FLAG_NATIVE_MATH)");
+    if (!rq.cash || rq.src == SRC_FHS || rq.rebalanced || rq.overlay || rq.garch || rq.jumps || rq.regimes || rq.dd || rq.attr || rq.anti)
+      return fail(MCP_E_UNSUPPORTED, "a glide path is not combined with the drawdown, rebalancing, the overlay, GARCH, jumps, regimes, "
+                                     "filtered rows, the attribution or antithetic pairs");
+    if (ln) return fail(MCP_E_UNSUPPORTED, "glide paths are not wired into mcp_launch_paths*");
   }
   if (rq.overlay && (rc = check_overlay(prm, rq.ov))) return rc;
   if (rq.garch && (rc = check_garch(prm, rq.gv))) return rc;
@@ -814,6 +859,35 @@ void cash_pivots(int K, int T, const double* m, const float* flows, double v0, i
     }
     out_T[k] = pivot(A);
   }
+}
+
+// SPEC.md 5.14: cash_pivots with the per-step mean of the step's segment.  m[g*K + k]: the mean of portfolio k on the weights of
+// block g = 0 .. G (block 0: the call's W); step s walks on block #{j : breaks[j] < s}.  flows NULL: c_s = +0.  G = 0, or equal
+// means in every block, is cash_pivots operation for operation.
+void glide_pivots(int K, int T, int G, const int32_t* breaks, const double* m, const float* flows, double v0, int H, const int32_t* steps,
+                  double* out_T, double* out_hz) {
+  const auto pivot = [v0](double A) {
+    const double c = (A > 0.0 ? A : 0.0) / v0 - 1.0;
+    return std::isfinite(A) && std::isfinite(c) ? c : 0.0;
+  };
+  for (int k = 0; k < K; k++) {
+    double A = v0;
+    int hi = 0, gi = 0;
+    double g = 1.0 + m[k];
+    for (int s = 1; s <= T; s++) {
+      A = A * g;
+      A = A + (flows ? (double)flows[s - 1] : 0.0);
+      if (hi < H && steps[hi] == s) out_hz[(size_t)(hi++) * K + k] = pivot(A);
+      if (gi < G && breaks[gi] == s) g = 1.0 + m[(size_t)(++gi) * K + k];
+    }
+    out_T[k] = pivot(A);
+  }
+}
+// The means m[g*kt + k] of glide_pivots for the portfolios [k0, k0 + kt) of a call with K portfolios (cash_means per block)
+void glide_means(int N, int K, int k0, int kt, const float* mu, const mcp_bootstrap* boot, const float* W, const mcp_glide* gl, double* out) {
+  cash_means(N, kt, mu, boot, W + (size_t)k0 * N, out);
+  for (int g = 0; g < gl->n_breaks; g++)
+    cash_means(N, kt, mu, boot, gl->targets + ((size_t)g * K + (size_t)k0) * N, out + (size_t)(g + 1) * kt);
 }
 
 // Inverse-CDF coefficient table (SPEC.md section 3; DATA of the spec, generated by tools/fit_icdf_table.py): one
@@ -1202,6 +1276,15 @@ static mcp::RegimeArgs regime_block(const Request& rq, const Launch& ln) {
   rs.thr_start = c.thr_start;
   return rs;
 }
+// SPEC.md 4.14: the breaks; the target blocks sit behind the launch's packed block
+static mcp::GlideArgs glide_block(const Request& rq, const Launch& ln, int n_assets, int n_portfolios) {
+  mcp::GlideArgs gp;
+  gp.targets = ln.d_targets;
+  gp.stride = (uint32_t)(glide_rows(n_portfolios) * (size_t)n4_of(n_assets));
+  gp.n_breaks = rq.gl->n_breaks;
+  for (int g = 0; g < MCP_MAX_GLIDE; g++) gp.breaks[g] = g < gp.n_breaks ? rq.gl->breaks[g] : 0;
+  return gp;
+}
 static mcp::OverlayArgs overlay_block(const Request& rq, const Launch& ln, int n_assets) {
   mcp::OverlayArgs ov;
   const size_t row_bytes = (size_t)rq.ov->n_rows * sizeof(mcp_overlay_row);
@@ -1299,6 +1382,7 @@ static int launch_paths_impl(const mcp_params* prm, const Request& rq, const Lau
   s.st = student_block(rq);
   if (rq.garch) s.gv = garch_block(rq.gv, N);
   if (rq.cash) s.cf.flows = ln.d_flows;
+  if (rq.glide) s.gp = glide_block(rq, ln, N, K);
   if (rq.overlay) s.ov = overlay_block(rq, ln, N);
   if (rq.rebalanced) { s.period = rq.reb->period; s.cost = (float)rq.reb->cost; }
   if (rq.src == SRC_FHS) s.fh = filt_block(rq, ln, N);
@@ -1326,6 +1410,7 @@ static int launch_paths_impl(const mcp_params* prm, const Request& rq, const Lau
     k.gv = rq.garch;
     k.jp = rq.jumps;
     k.rs = rq.regimes;
+    k.gp = rq.glide;
     k.kt8 = K > 1;
     k.native = (prm->flags & MCP_FLAG_NATIVE_MATH) != 0;
     k.fold = (prm->flags & MCP_FLAG_FOLD) != 0;
@@ -1860,7 +1945,9 @@ int run_tile(mcp_ctx* c, const mcp_params* prm, const Request& rq, uint64_t seed
     HIP_TRY(hipSetDevice(sh.device));
     tp[s].n_portfolios = j.kt;
     // jumps: the loadings behind the packed block; regimes: [mu1][L1 row pairs] there
-    const size_t plen = mcp_packed_len(N, j.kt) + (rq.jumps ? (size_t)n4_of(N) : 0) + (rq.regimes ? regime_block_len(N) : 0), pn = j.pn ? j.pn : 1;
+    // glide path: the target blocks of the tile's portfolios there
+    const size_t plen = mcp_packed_len(N, j.kt) + (rq.jumps ? (size_t)n4_of(N) : 0) + (rq.regimes ? regime_block_len(N) : 0) +
+                        (rq.glide ? glide_len(N, j.kt, rq.gl) : 0), pn = j.pn ? j.pn : 1;
     const int rows = rq.hz ? rq.H * j.kt : j.kt;  // horizon calls: the work buffers also serve the H*kt rows of the horizon selects
     for (int w = 0; w < MCP_WS_COUNT; w++) {      // only the histogram and the select state must start zeroed
       const size_t need = std::max(mcp_ws_bytes(w, j.kt, pn), mcp_ws_bytes(w, rows, pn));
@@ -1913,6 +2000,7 @@ int run_tile(mcp_ctx* c, const mcp_params* prm, const Request& rq, uint64_t seed
     Shard& sh = c->sh[s];
     HIP_TRY(hipSetDevice(sh.device));
     const size_t plen = mcp_packed_len(N, j.kt);
+    const size_t n_tail = rq.glide ? glide_len(N, j.kt, rq.gl) : n_load;   // what follows the packed block: loadings, regime 1 or targets
     const float* src = sh.h_packed.p;
     const double* psrc = sh.h_pivot.p;
     const double* hpsrc = sh.hz.h_pivot.p;
@@ -1930,7 +2018,13 @@ int run_tile(mcp_ctx* c, const mcp_params* prm, const Request& rq, uint64_t seed
         bs2.resize((size_t)j.kt);
         boot_moments(N, rq.boot, Wt, j.kt, bm.data(), bs2.data());
       }
-      if (rq.cash) {                                         // SPEC.md 5.6: one Horner walk gives T and every horizon
+      if (rq.glide) {                                        // SPEC.md 4.14 / 5.14: the tile's target blocks; one walk gives every pivot
+        glide_pack(N, prm->n_portfolios, j.k0, j.kt, rq.gl, sh.h_packed.p + plen);
+        cm.resize((size_t)(rq.gl->n_breaks + 1) * j.kt);
+        glide_means(N, prm->n_portfolios, j.k0, j.kt, rq.mu, boot ? rq.boot : nullptr, rq.W, rq.gl, cm.data());
+        glide_pivots(j.kt, prm->n_steps, rq.gl->n_breaks, rq.gl->breaks, cm.data(), rq.cf->flows, (double)(float)prm->v0, rq.hz ? rq.H : 0,
+                     rq.steps, sh.h_pivot.p, sh.hz.h_pivot.p);
+      } else if (rq.cash) {                                  // SPEC.md 5.6: one Horner walk gives T and every horizon
         cm.resize((size_t)j.kt);
         cash_means(N, j.kt, rq.mu, boot ? rq.boot : nullptr, Wt, cm.data());
         cash_pivots(j.kt, prm->n_steps, cm.data(), rq.cf->flows, (double)(float)prm->v0, rq.hz ? rq.H : 0, rq.steps, sh.h_pivot.p,
@@ -1946,7 +2040,7 @@ int run_tile(mcp_ctx* c, const mcp_params* prm, const Request& rq, uint64_t seed
           return rc;
       if (exchange) { shared_packed = sh.h_packed.p; shared_pivot = sh.h_pivot.p; shared_hz_pivot = sh.hz.h_pivot.p; }
     }
-    HIP_TRY(hipMemcpyAsync(sh.packed.p, src, (plen + n_load) * sizeof(float), hipMemcpyHostToDevice, sh.stream));
+    HIP_TRY(hipMemcpyAsync(sh.packed.p, src, (plen + n_tail) * sizeof(float), hipMemcpyHostToDevice, sh.stream));
     HIP_TRY(hipMemcpyAsync(sh.ws[MCP_WS_PIVOT], psrc, (size_t)j.kt * sizeof(double), hipMemcpyHostToDevice, sh.stream));
     if (rq.hz) HIP_TRY(hipMemcpyAsync(sh.hz.pivot.p, hpsrc, (size_t)rq.H * j.kt * sizeof(double), hipMemcpyHostToDevice, sh.stream));
     if (j.pn) {
@@ -1961,6 +2055,7 @@ int run_tile(mcp_ctx* c, const mcp_params* prm, const Request& rq, uint64_t seed
       ln.d_overlay = sh.overlay.p;
       ln.d_loading = sh.packed.p + plen;
       ln.d_block1 = sh.packed.p + plen;
+      ln.d_targets = sh.packed.p + plen;
       ln.d_cross = sh.pr.partials.p;
       if ((rc = launch_paths_impl(&tp[s], rq, ln))) return rc;
       if (rq.anti) {                                         // SPEC.md 5.10: the workgroups' cross partials in block order
@@ -2539,6 +2634,52 @@ int mcp_cashflow_pivots(const mcp_params* prm, const mcp_cashflow* cf, const flo
   std::vector<double> m((size_t)prm->n_portfolios);
   cash_means(prm->n_assets, prm->n_portfolios, mu, boot, W, m.data());
   cash_pivots(prm->n_portfolios, prm->n_steps, m.data(), cf->flows, (double)(float)prm->v0, 0, nullptr, out, nullptr);
+  return MCP_OK;
+}
+
+int mcp_simulate_glide(mcp_ctx* c, const mcp_params* prm, const mcp_glide* gl, const mcp_cashflow* cf, const float* mu, const float* chol,
+                       const mcp_bootstrap* boot, const mcp_student_t* st, const float* W, uint64_t seed, uint64_t path_begin,
+                       uint64_t n_paths, int n_horizons, const int32_t* horizons, int n_levels, const double* levels, float* terminal_out,
+                       mcp_stats* stats_out, uint64_t* counts_out, float* horizon_out, mcp_stats* hz_stats_out, double* bands_out,
+                       uint64_t* hz_counts_out) {
+  if (boot && st) return fail(MCP_E_ARG, "exactly one draw source: mu and chol (with or without student_t), or boot");
+  // cf NULL: the all-zero schedule without a target, so that one request and one kernel serve both
+  const std::vector<float> zeros(!cf && prm && prm->n_steps > 0 ? (size_t)prm->n_steps : 0, 0.0f);
+  const mcp_cashflow none = {zeros.data(), prm ? prm->n_steps : 0, 0, 0.0};
+  Request rq = host_request(boot ? SRC_BOOT : st ? SRC_T : SRC_GAUSS, mu, chol, W, terminal_out, stats_out);
+  rq.boot = boot;
+  rq.st = st;
+  rq.cash = true;
+  rq.cf = cf ? cf : &none;
+  rq.glide = true;
+  rq.gl = gl;
+  rq.counts_out = counts_out;
+  rq.hz_counts_out = hz_counts_out;
+  ask_horizons(rq, n_horizons != 0, n_horizons, horizons, n_levels, levels, horizon_out, hz_stats_out, bands_out);
+  return simulate_checked(c, prm, rq, seed, path_begin, n_paths);
+}
+
+int mcp_glide_pivots(const mcp_params* prm, const mcp_glide* gl, const mcp_cashflow* cf, const float* mu, const mcp_bootstrap* boot,
+                     const float* W, int n_horizons, const int32_t* horizons, double* pivots_out, double* hz_pivots_out) {
+  if (int rc = check_params(prm)) return rc;
+  if (cf)
+    if (int rc = check_cashflow(prm, cf)) return rc;
+  if (!((float)prm->v0 > 0.0f)) return fail(MCP_E_ARG, "v0=%g rounds to zero in binary32", prm->v0);
+  if (int rc = check_glide(prm, gl)) return rc;
+  if ((mu == nullptr) == (boot == nullptr)) return fail(MCP_E_ARG, "exactly one of mu and boot");
+  if (boot)
+    if (int rc = check_boot(prm, boot)) return rc;
+  if (!W || !pivots_out) return fail(MCP_E_ARG, "NULL pointer");
+  if (n_horizons != 0) {
+    if (int rc = check_horizons(prm->n_steps, n_horizons, horizons)) return rc;
+    if (!hz_pivots_out) return fail(MCP_E_ARG, "hz_pivots_out is NULL");
+  }
+  if (prm->compounding != MCP_COMPOUND_SIMPLE) return fail(MCP_E_UNSUPPORTED, "glide paths compound simply (no log compounding)");
+  const int K = prm->n_portfolios;
+  std::vector<double> m((size_t)(gl->n_breaks + 1) * K);
+  glide_means(prm->n_assets, K, 0, K, mu, boot, W, gl, m.data());
+  glide_pivots(K, prm->n_steps, gl->n_breaks, gl->breaks, m.data(), cf ? cf->flows : nullptr, (double)(float)prm->v0, n_horizons, horizons,
+               pivots_out, hz_pivots_out);
   return MCP_OK;
 }
 

@@ -93,7 +93,7 @@ __device__ __forceinline__ const __attribute__((address_space(4))) A* kernarg() 
   template <class A> struct has_##m<A, std::void_t<decltype(A::m)>> : std::true_type {};
 MCP_HAS_MEMBER(hz) MCP_HAS_MEMBER(mdd) MCP_HAS_MEMBER(bt) MCP_HAS_MEMBER(st) MCP_HAS_MEMBER(gv) MCP_HAS_MEMBER(cf)
 MCP_HAS_MEMBER(ov) MCP_HAS_MEMBER(at) MCP_HAS_MEMBER(period) MCP_HAS_MEMBER(pr)
-MCP_HAS_MEMBER(fh) MCP_HAS_MEMBER(p_hi) MCP_HAS_MEMBER(jp) MCP_HAS_MEMBER(rs)
+MCP_HAS_MEMBER(fh) MCP_HAS_MEMBER(p_hi) MCP_HAS_MEMBER(jp) MCP_HAS_MEMBER(rs) MCP_HAS_MEMBER(gp)
 #undef MCP_HAS_MEMBER
 
 struct PathArgs {
@@ -332,6 +332,18 @@ __device__ __forceinline__ float cash_flow(const A&, int t) {
   else return 0.0f;
 }
 
+// The glide path of SPEC.md 4.14: the weights of the walk change at the breaks b_1 < .. < b_G (steps in [1, n_steps - 1]).  Step s
+// walks on block g = #{j : b_j < s}: block 0 is the packed weights of the launch, block g >= 1 is `targets + (g - 1) stride`, in the
+// packed weights' own layout -- rows of N4 floats, the columns i >= N and the rows up to the end of the last pass of 8 zero.
+struct GlideArgs {
+  const float* __restrict__ targets;  // [n_breaks][stride] device copy
+  uint32_t stride;                    // floats between consecutive target blocks (padded rows x N4)
+  int32_t n_breaks;                   // G in [0, MCP_MAX_GLIDE]
+  int32_t breaks[MCP_MAX_GLIDE];      // strictly increasing, in [1, n_steps - 1]
+};
+// Arguments of mc_paths_glide_kernel: those of mc_paths_cf_kernel and the glide block, read where it is needed (kernarg).
+struct PathArgsGP : PathArgsCF { GlideArgs gp; };
+
 // The option overlay of SPEC.md 4.8: per asset a run of rows (kind, strike, premium, qty) that turns the raw return r_i of a step
 // into the strategy's return r'_i at the asset's price level P_i.  rows, row_begin [N4 + 1] (assets >= N own no rows) and spot [N4]
 // are device copies; bit i of `mask` is set when asset i owns rows.
@@ -393,6 +405,7 @@ struct PathLaunchArgs {
   FiltArgs fh;
   JumpArgs jp;
   RegimeArgs rs;
+  GlideArgs gp;
 };
 template <class A>
 inline A make_args(const PathLaunchArgs& s) {
@@ -411,6 +424,7 @@ inline A make_args(const PathLaunchArgs& s) {
   if constexpr (has_fh<A>::value) x.fh = s.fh;
   if constexpr (has_jp<A>::value) x.jp = s.jp;
   if constexpr (has_rs<A>::value) x.rs = s.rs;
+  if constexpr (has_gp<A>::value) x.gp = s.gp;
   if constexpr (has_p_hi<A>::value) { x.p_hi = (uint32_t)(s.hz.path_begin >> 32); x.pad = 0u; }
   return x;
 }
@@ -512,13 +526,16 @@ constexpr int PATH_BLOCK = 256;
 // fma(b, J, mu') instead of mu, one packed fma with the loadings b from the LDS slot behind the drift (SPEC.md 4.12).  RS: before the
 // asset normals one more Philox block on counter stream 4 moves the path's regime (SPEC.md 2.6), and every row pair's chain runs once per
 // regime under that regime's lanes -- a divergent if / else, skipped where the wave has no lane in the regime -- with that regime's
-// drift and Cholesky factor, the factor still a scalar operand (SPEC.md 4.13).  Every kernel
+// drift and Cholesky factor, the factor still a scalar operand (SPEC.md 4.13).  GP (with CF and HZ): the
+// walk's weight pointer moves to the next target block at the breaks of the glide path, wave-uniform events merged with the horizons
+// as the rebalancing walk merges its dates; the step itself is the cash-flow kernel's (SPEC.md 4.14).  Every kernel
 // below is the body in mcp_paths_body.inc under its own flags F: it names the flags it sets, the rest are PathFlagsOff's.  F is a
 // local class, which may not have static data members, so it sets its flags as enumerators of an `enum : bool`; they hide the
 // defaults' names and read as the same constant expressions.
 struct PathFlagsOff {
   static constexpr bool NATIVE = false, FOLD = false, LOGC = false, DD = false, HZ = false, BOOT = false, BLDS = false, REB = false,
-                        STT = false, CF = false, OV = false, GV = false, AT = false, ANTI = false, FH = false, UHI = false, JP = false, RS = false;
+                        STT = false, CF = false, OV = false, GV = false, AT = false, ANTI = false, FH = false, UHI = false, JP = false, RS = false,
+                        GP = false;
 };
 
 // __launch_bounds__ 2nd argument of a path kernel: the MCP_MIN_WAVES* above for N <= 16 and one path per lane, by the kind of
@@ -676,6 +693,16 @@ __global__ void MCP_BOUNDS(BK_PATHS) mc_paths_r_hz_kernel(const PathArgsRHZ a) {
 template <int NB, int KT, int PPT, bool BOOT_, bool BLDS_, bool STT_>
 __global__ void MCP_BOUNDS(BK_CF) mc_paths_cf_kernel(const PathArgsCF a) {
   struct F : PathFlagsOff { enum : bool { HZ = true, CF = true, BOOT = BOOT_, BLDS = BLDS_, STT = STT_ }; };
+#include "mcp_paths_body.inc"
+}
+
+// The glide-path kernel (SPEC.md 4.14): mc_paths_cf_kernel with the weights of the dot taken from the target block of the step's
+// segment.  The segmented walk ends a segment at the next horizon, the next break or T; at a break the scalar weight pointer moves
+// on, at a horizon V is stored, both when they share a step.  G = 0 is the cash-flow kernel's walk.  It keeps that kernel's launch
+// bounds: the step loop is its twin's and no listing shows scratch in it (profiles/glide_isa.txt).
+template <int NB, int KT, int PPT, bool BOOT_, bool BLDS_, bool STT_>
+__global__ void MCP_BOUNDS(BK_CF) mc_paths_glide_kernel(const PathArgsGP a) {
+  struct F : PathFlagsOff { enum : bool { HZ = true, CF = true, GP = true, BOOT = BOOT_, BLDS = BLDS_, STT = STT_ }; };
 #include "mcp_paths_body.inc"
 }
 

@@ -4,7 +4,8 @@
 // walk is the one loop it always was.  In scope: the template parameters NB, KT, PPT, the flags F (PathFlagsOff or a struct
 // derived from it) and the kernel argument `a` (PathArgs or a struct that starts with one).
   constexpr bool NATIVE = F::NATIVE, FOLD = F::FOLD, LOGC = F::LOGC, DD = F::DD, HZ = F::HZ, BOOT = F::BOOT, BLDS = F::BLDS, REB = F::REB,
-                 STT = F::STT, CF = F::CF, OV = F::OV, GV = F::GV, AT = F::AT, ANTI = F::ANTI, FH = F::FH, UHI = F::UHI, JP = F::JP, RS = F::RS;
+                 STT = F::STT, CF = F::CF, OV = F::OV, GV = F::GV, AT = F::AT, ANTI = F::ANTI, FH = F::FH, UHI = F::UHI, JP = F::JP, RS = F::RS,
+                 GP = F::GP;
   static_assert(!UHI || (KT == 1 && PPT == 1 && !(NATIVE || FOLD || DD || HZ || BOOT || REB || STT || CF || OV || GV || AT || ANTI || FH || JP || RS)),
                 "uniform high counter word: the plain Gaussian walk of one portfolio only");
   static_assert(!FH || (BOOT && HZ && !(LOGC || REB || CF || STT || GV || OV || AT || DD)), "filtered rows: the bootstrap's segmented walk only");
@@ -12,6 +13,8 @@
                 "jump-diffusion: the Gaussian walk, its drawdown and its horizons, simple compounding only");
   static_assert(!RS || !(NATIVE || FOLD || LOGC || BOOT || REB || STT || CF || OV || GV || AT || ANTI || FH || JP),
                 "regime switching: the Gaussian walk, its drawdown and its horizons, simple compounding only");
+  static_assert(!GP || (CF && HZ && !(NATIVE || FOLD || LOGC || DD || REB || OV || GV || AT || ANTI || FH || UHI || JP || RS)),
+                "glide path: the cash-flow kernel's segmented walk only");
   constexpr int N4 = 4 * NB;
   // ANTI (SPEC.md 2.3): a lane's PPT draws feed EM = 2 PPT members -- slot e < PPT walks on z[e], slot PPT + e on -z[e]; p, live and
   // the counters are per draw (a.path_begin and a.n_paths count pairs), the members 2 p and 2 p + 1 are adjacent in the output rows
@@ -256,6 +259,40 @@
             for (int m = 0; m < N4 / 2; m++) Bs[e][m] = f32x2{0.0f, 0.0f};
           const int per = cs->period;
           nd = per < T - t ? t + per : T;
+        }
+      }
+    } else if constexpr (GP) {
+      // SPEC.md 4.14: the walk in segments that end at the events -- the next horizon, the next break, T -- with the unchanged step
+      // body.  At a horizon V_h is stored as below; at a break b_g the weight pointer moves to target block g for this pass, so step
+      // b_g + 1 is the first on the new weights; both happen when they share a step.  Every tile starts on the packed weights again.
+      // The horizons, the breaks and the targets are read where they are needed (kernarg), wave-uniform; every branch below is on
+      // wave-uniform values.
+      Wk = mu + N4 + N4 * (N4 / 2 + 1) + (size_t)a.k_begin * N4;
+      int t = 0, hi = 0, gi = 0;
+      while (t < T) {
+        const auto gs = kernarg<PathArgsGP>();
+        const int t_hz = hi < gs->n_horizons ? gs->steps[hi] : T;
+        const int t_br = gi < gs->gp.n_breaks ? gs->gp.breaks[gi] : T;
+        const int t_end = min(min(t_hz, t_br), T);
+        for (; t < t_end; t++) {
+#include "mcp_paths_step.inc"
+        }
+        const auto hs = kernarg<PathArgsGP>();
+        if (hi < hs->n_horizons && hs->steps[hi] <= t) {   // V_h of SPEC.md 4.3, after the flow c_h (the host checked the lists: the
+                                                           // step is t; `<=` so that every pass of the loop consumes an event or steps)
+          float* const row = hs->hz + (size_t)(hi * a.n_portfolios + a.k_begin) * hs->hz_stride;
+#pragma unroll
+          for (int e = 0; e < PPT; e++)
+            if (live[e]) {
+#pragma unroll
+              for (int k = 0; k < KT; k++)
+                if (k < kt) row[(size_t)k * hs->hz_stride + p[e]] = V[e][k];
+            }
+          hi++;
+        }
+        if (gi < hs->gp.n_breaks && hs->gp.breaks[gi] <= t) {
+          Wk = (cfloat_p)hs->gp.targets + (size_t)gi * hs->gp.stride + (size_t)a.k_begin * N4;
+          gi++;
         }
       }
     } else if constexpr (HZ) {

@@ -66,13 +66,14 @@ struct PathLaunchArgs;
 // N <= 16 only -- LEAN_MAX_NB: from NB = 5 on the listings show it at more registers than mc_paths_kernel, at NB = 12, 14 and 15
 // at one wave per SIMD fewer, and nothing above NB = 4 has been timed), and jp (the jump-diffusion kernels of the plain, drawdown
 // and horizon families: Gaussian draws plus the market jump of SPEC.md 2.5, simple compounding), and rs (the regime-switching kernels
-// of the same three families: Gaussian draws on the drift and factor of the path's regime, SPEC.md 2.6, simple compounding).
+// of the same three families: Gaussian draws on the drift and factor of the path's regime, SPEC.md 2.6, simple compounding), and
+// gp (FAM_CF only: the glide-path kernel, the cash-flow walk on scheduled target weights, SPEC.md 4.14).
 // The one ladder of mcp_paths_inst.hip maps it to a kernel and lists which selectors have one.
 constexpr int LEAN_MAX_NB = 4;
 enum PathFamily { FAM_PLAIN, FAM_DD, FAM_HZ, FAM_REB, FAM_CF, FAM_OV, FAM_AT };
 struct PathKernel {
   int family;
-  bool logc, boot, blds, stt, dd, gv, kt8, native, fold, anti, fh, uhi, jp, rs;
+  bool logc, boot, blds, stt, dd, gv, kt8, native, fold, anti, fh, uhi, jp, rs, gp;
 };
 
 // mcp_paths_inst.hip (one translation unit per NB): every pass of the kernel that `k` selects, on the blocks of `args` that the

@@ -65,7 +65,8 @@ class Context:
 
     def _call(self, prm: _ffi.McpParams, W, seed: int, path_begin: int, n_paths: int, store: bool, mu=None, chol=None, rows=None,
               block: float = 1.0, dof=None, period=None, cost: float = 0.0, drawdown: bool = False, horizons=None, levels=(),
-              flows=None, target=None, overlay=None, garch=None, attribution=False, antithetic=False, filtered=None, jumps=None, regimes=None):
+              flows=None, target=None, overlay=None, garch=None, attribution=False, antithetic=False, filtered=None, jumps=None, regimes=None,
+              glide=None):
         """The one library call behind every simulate_* method: two regimes (regimes: the (p01, p10, start, mu1, chol1) of check_regimes), market jumps (jumps: the (intensity, mean, std, loading or None) of check_jumps), GARCH volatility (garch: the (alpha, beta, h0) of check_garch), an option overlay (overlay: the triple of check_overlay), cash flows (flows, target), Student-t draws (dof), rebalancing
         (period, cost), bootstrap rows (rows, block) or Gaussian draws (mu, chol), with the drawdown or horizons.  Allocates the
         outputs that were asked for and passes NULL for the rest -> _Outputs, None where not asked for (terminal, qd,
@@ -93,7 +94,22 @@ class Context:
         hz_out = (ptr(hz_term), ptr(hz_stats), ptr(bands) if L else None)
         bt = _ffi.make_bootstrap(rows, block) if rows is not None else None
         attr = attr_counts = contrib = pairs = None
-        if filtered is not None:
+        if glide is not None:
+            # SPEC.md 4.14: glide is the (breaks int32 [G], targets binary32 [G, K, N]) of check_glide; the cash-flow call on scheduled
+            # weights (flows None: the all-zero schedule).  The library states the rules (check_request)
+            if (filtered is not None or regimes is not None or jumps is not None or antithetic or attribution or garch is not None
+                    or overlay is not None or period is not None or drawdown):
+                raise ValueError("glide is not combined with drawdown, rebalance, overlay, garch, attribution, antithetic, jumps, regimes "
+                                 "or filtered rows")
+            counts = np.zeros((K, 2), np.uint64)
+            hz_counts = np.zeros((H, K, 2), np.uint64) if horizons is not None else None
+            st = _ffi.McpStudentT(int(dof), 0) if dof is not None else None
+            gl = _ffi.make_glide(*glide)
+            cf = _ffi.make_cashflow(flows, target) if flows is not None else None
+            rc = lib.mcp_simulate_glide(self._h, prm_p, ctypes.byref(gl), ctypes.byref(cf) if cf is not None else None, ptr(mu), ptr(chol),
+                                        ctypes.byref(bt) if bt is not None else None, ctypes.byref(st) if st is not None else None,
+                                        ptr(W), *walk, *hz_in, ptr(term), ptr(stats), ptr(counts), *hz_out, ptr(hz_counts))
+        elif filtered is not None:
             # SPEC.md 2.4 / 4.11: the library states the rules (check_request); nothing else of this method is passed on
             if (overlay is not None or flows is not None or period is not None or bt is not None or dof is not None or attribution
                     or antithetic or drawdown or garch is None):
@@ -296,6 +312,15 @@ class Context:
         return self._call(prm, W, seed, path_begin, n_paths, store, mu=mu, chol=chol, rows=rows, block=block, dof=dof,
                           horizons=horizons, levels=levels, flows=np.ascontiguousarray(flows, np.float32), target=target)
 
+    def simulate_glide(self, prm: _ffi.McpParams, glide, W, seed: int, path_begin: int, n_paths: int, store: bool, flows=None, mu=None,
+                       chol=None, rows=None, block: float = 1.0, dof=None, target=None, horizons=None, levels=()):
+        """simulate_cashflow() on the scheduled target weights of a glide path (SPEC.md 4.14 / 5.14; include/mcport.h,
+        mcp_simulate_glide; simple compounding only): `glide` is (breaks int32 [G], targets binary32 [G, K, N]); step s walks on
+        target block #{j : breaks[j] < s}, block 0 being `W`.  flows None: the all-zero schedule.  Draws and -> _Outputs as
+        simulate_cashflow."""
+        return self._call(prm, W, seed, path_begin, n_paths, store, mu=mu, chol=chol, rows=rows, block=block, dof=dof,
+                          horizons=horizons, levels=levels, flows=None if flows is None else np.ascontiguousarray(flows, np.float32),
+                          target=target, glide=(np.ascontiguousarray(glide[0], np.int32), np.ascontiguousarray(glide[1], np.float32)))
 
     def simulate_overlay(self, prm: _ffi.McpParams, overlay, mu, chol, W, seed: int, path_begin: int, n_paths: int, store: bool,
                          dof=None, drawdown: bool = False, horizons=None, levels=()):
@@ -345,6 +370,52 @@ def check_cashflow(cashflow, target, n_steps):
     if not np.all(np.isfinite(flows)):
         raise ValueError("cashflow entries must be finite (in binary32)")
     return flows, target
+
+
+def check_glide(glide, weights, n_steps):
+    """SPEC.md 4.14 argument rules -> None (no glide path) or (breaks int32 [G], targets binary32 [G, K, N], C-contiguous).  `glide`
+    is (breaks, targets): breaks, at most 64 strictly increasing whole steps in [1, n_steps - 1]; targets, the weights held AFTER
+    each break, [G, N] for a weight vector and [K, G, N] for K portfolios.  ValueError for anything else: not a pair, bools, breaks
+    out of range or order, a shape that does not match the weights, an entry that is not finite (also after rounding to
+    binary32)."""
+    if glide is None:
+        return None
+    if isinstance(glide, (str, bytes)) or not hasattr(glide, "__len__") or len(glide) != 2:
+        raise ValueError("glide must be a (breaks, targets) pair (glide.glide_path(...) builds one)")
+    raw = np.atleast_1d(np.asarray(glide[0], object)).ravel().tolist()
+    if any(isinstance(b, (bool, np.bool_)) or not isinstance(b, (int, np.integer)) for b in raw):
+        raise ValueError("glide breaks must be whole step numbers (no bools, no floats)")
+    G = len(raw)
+    if G > _ffi.MCP_MAX_GLIDE:
+        raise ValueError(f"glide takes at most {_ffi.MCP_MAX_GLIDE} breaks, got {G}")
+    if any(not 1 <= int(b) <= int(n_steps) - 1 for b in raw):
+        raise ValueError(f"glide breaks must lie in [1, n_steps - 1 = {int(n_steps) - 1}], got {[int(b) for b in raw]}")
+    if any(int(b) <= int(a) for a, b in zip(raw, raw[1:])):
+        raise ValueError(f"glide breaks must be strictly increasing, got {[int(b) for b in raw]}")
+    w = np.asarray(weights)
+    if w.ndim not in (1, 2):
+        raise ValueError(f"glide needs weights [N] or [K, N], got shape {w.shape}")
+    N = w.shape[-1]
+    try:
+        t64 = np.asarray(glide[1], np.float64)
+    except (TypeError, ValueError):
+        raise ValueError("glide targets must be numbers") from None
+    want = (G, N) if w.ndim == 1 else (w.shape[0], G, N)
+    if G == 0 and t64.size == 0:
+        t64 = np.zeros(want, np.float64)
+    if t64.shape != want:
+        raise ValueError(f"glide targets must have shape {want} ([G, N] for a weight vector, [K, G, N] for K portfolios), got {t64.shape}")
+    with np.errstate(over="ignore"):
+        t32 = t64.astype(np.float32)
+    if not np.all(np.isfinite(t32)):
+        raise ValueError("glide targets must be finite (in binary32)")
+    targets = np.ascontiguousarray(t32[:, None, :] if w.ndim == 1 else np.transpose(t32, (1, 0, 2)))
+    return np.ascontiguousarray([int(b) for b in raw], np.int32).reshape(G), targets
+
+
+def _glide_blocks(gl, W):
+    """The 'glide' block of every portfolio: the breaks and the binary32 weights [G + 1, N] as used, segment 0 the call's weights."""
+    return [{"breaks": gl[0].astype(np.int64), "weights": np.concatenate([W[k][None, :], gl[1][:, k, :]], axis=0)} for k in range(W.shape[0])]
 
 
 def check_overlay(overlay, spot, n_assets):
@@ -663,7 +734,7 @@ def simulate_paths(mu, cov, weights, n_steps=252, n_paths=10_000, seed=0, v0=1.0
                    rf=0.0, alpha=0.95, devices=None, store=False, path_begin=0, chol=None,
                    native_math=False, as_array=False, fold=False, shard="auto", context=None, drawdown=False,
                    horizons=None, bands=(), rebalance=None, rebalance_cost=0.0, dof=None, cashflow=None, target=None,
-                   overlay=None, spot=None, garch=None, attribution=False, antithetic=False, jumps=None, regimes=None):
+                   overlay=None, spot=None, garch=None, attribution=False, antithetic=False, jumps=None, regimes=None, glide=None):
     """Simulate `n_paths` correlated return paths and reduce them to risk statistics.
 
     mu [N], cov [N,N] are per-step mean and covariance (the reference's `mean_returns`, `cov_matrix`
@@ -790,7 +861,32 @@ def simulate_paths(mu, cov, weights, n_steps=252, n_paths=10_000, seed=0, v0=1.0
     horizons, occupancy: per horizon h the expected share of the first h steps walked in regime 1}.  Not built: regimes with dof,
     garch, jumps, rebalance, cashflow, overlay, attribution, antithetic, fold, native_math or compounding="log" (ValueError), on
     bootstrap or filtered paths, in PathEngine and at the mcp_launch_* level.
+
+    glide=None (default): the weights are held from the first step to the last.  glide=(breaks, targets): a glide path, target
+    weights on a calendar (SPEC.md 4.14 / 5.14) -- target-date funds, "100 minus age", de-risking before the goal.  breaks: at most
+    64 strictly increasing steps in [1, n_steps - 1]; targets: the weights held after each break, [G, N] for a weight vector and
+    [K, G, N] for K portfolios (glide.glide_path(start, end, n_steps, every) builds a linear one).  `weights` is held through step
+    breaks[0], targets[0] through step breaks[1], and so on; the portfolio stands at its current target at the start of every step,
+    and the trade at a break is free (holdings that drift between breaks are rebalance's subject, not built together).  The walk is
+    the cashflow walk -- the same draws, flows and absorbing ruin -- so glide with cashflow=None is the call with cashflow=0 and the
+    result has that call's shape, 'cashflow' block and as_array tuple included; every dict gains 'glide' {breaks, weights (float32
+    [G + 1, N] as used, segment 0 = weights)}.  Targets equal to the weights give the cashflow call bit for bit.
+    glide.glide_law(mu, cov, weights, glide, n_steps) is the exact mean and variance for Gaussian draws without flows.  Combines
+    with cashflow / target, dof, horizons / bands, store, as_array, devices and bootstrap rows (simulate_bootstrap).  Not built:
+    glide with drawdown, rebalance, overlay, garch, attribution, antithetic, jumps, regimes, fold, native_math or
+    compounding="log" (ValueError), on filtered rows, in simulate_sweep, in PathEngine and at the mcp_launch_* level.
     """
+    gl = check_glide(glide, weights, n_steps)
+    if gl is not None:
+        bad = [name for name, on in (("drawdown", bool(drawdown)), ("rebalance", rebalance is not None), ("overlay", overlay is not None),
+                                     ("garch", garch is not None), ("attribution", bool(attribution)), ("antithetic", bool(antithetic)),
+                                     ("jumps", jumps is not None), ("regimes", regimes is not None), ("fold", fold),
+                                     ("native_math", native_math), ("compounding='log'", compounding == "log")) if on]
+        if bad:
+            raise ValueError("glide needs the cashflow walk -- simple compounding, the spec's normals and the unfolded recurrence: not "
+                             f"with {', '.join(bad)}")
+        if cashflow is None:
+            cashflow = 0.0
     rv = check_regimes(regimes, len(np.atleast_1d(np.asarray(mu))), factor=chol is not None)
     if rv is not None:
         bad = [name for name, on in (("dof", dof is not None), ("garch", garch is not None), ("jumps", jumps is not None),
@@ -872,8 +968,11 @@ def simulate_paths(mu, cov, weights, n_steps=252, n_paths=10_000, seed=0, v0=1.0
                       "paths" if attribution or antithetic else shard, context)
     out = ctx._call(prm, W, int(seed), int(path_begin), int(n_paths), store, mu=mu32, chol=L, dof=dof, period=period, cost=cost,
                     drawdown=drawdown, horizons=steps, levels=levels, flows=flows, target=target, overlay=ov, garch=gv,
-                    attribution=bool(attribution), antithetic=bool(antithetic), jumps=jv, regimes=rv)
+                    attribution=bool(attribution), antithetic=bool(antithetic), jumps=jv, regimes=rv, glide=gl)
     res = _result(out, np.asarray(weights).ndim == 1, store, as_array, steps, levels, compounding, flows, target)
+    if gl is not None and not as_array:
+        for d, blk in zip([res] if isinstance(res, dict) else res, _glide_blocks(gl, W)):
+            d["glide"] = blk
     if jv is not None and not as_array:
         for d, blk in zip([res] if isinstance(res, dict) else res, _jump_blocks(jv, L, W)):
             d["jumps"] = blk
@@ -1022,7 +1121,7 @@ def bootstrap_inputs(returns, weights):
 
 def simulate_bootstrap(returns, weights, n_steps=252, n_paths=10_000, block=1.0, seed=0, v0=1.0, compounding="simple",
                        rf=0.0, alpha=0.95, devices=None, store=False, path_begin=0, as_array=False, shard="auto", context=None,
-                       horizons=None, bands=(), rebalance=None, rebalance_cost=0.0, cashflow=None, target=None, **unsupported):
+                       horizons=None, bands=(), rebalance=None, rebalance_cost=0.0, cashflow=None, target=None, glide=None, **unsupported):
     """simulate_paths on paths resampled from the observed return rows instead of a normal model: the stationary block
     bootstrap of Politis & Romano (SPEC.md 2.1 / 4.4).  Every step of a path uses one whole row of `returns` (all assets of one
     date together), so fat tails, skew, the co-movement within a row and -- with a mean block length `block` > 1 -- short-range
@@ -1034,7 +1133,8 @@ def simulate_bootstrap(returns, weights, n_steps=252, n_paths=10_000, block=1.0,
     SPEC.md 5.3).  ValueError for NaN rows, a width that does not match the weights, block < 1, or the simulate_paths keywords
     that have no meaning here (fold, native_math, drawdown, chol).  rebalance / rebalance_cost as in simulate_paths (SPEC.md 4.5,
     pivots of SPEC.md 5.4; not with compounding="log").  cashflow / target as in simulate_paths (SPEC.md 4.7, pivots of SPEC.md
-    5.6; not with rebalance or compounding="log").
+    5.6; not with rebalance or compounding="log").  glide as in simulate_paths (SPEC.md 4.14, pivots of SPEC.md 5.14 on the row
+    means; not with rebalance or compounding="log").
     """
     if unsupported.get("overlay") is not None or unsupported.get("spot") is not None:
         raise ValueError("simulate_bootstrap does not take overlay: the rows are observed returns with no price level to strike an "
@@ -1056,6 +1156,12 @@ def simulate_bootstrap(returns, weights, n_steps=252, n_paths=10_000, block=1.0,
         raise ValueError(f"simulate_bootstrap does not take {sorted(unsupported)} (no normals: no fold / native_math / dof -- "
                          "Student-t draws are a parametric model, call simulate_paths(dof=...); drawdown on bootstrap paths is "
                          "not supported)")
+    gl = check_glide(glide, weights, n_steps)
+    if gl is not None:
+        if rebalance is not None or compounding == "log":
+            raise ValueError("glide needs the cashflow walk and simple compounding: not with rebalance or compounding='log'")
+        if cashflow is None:
+            cashflow = 0.0
     flows, target = check_cashflow(cashflow, target, n_steps)
     if flows is not None and (rebalance is not None or compounding == "log"):
         raise ValueError("cashflow needs simple compounding and constant weights: not with rebalance or compounding='log'")
@@ -1067,8 +1173,12 @@ def simulate_bootstrap(returns, weights, n_steps=252, n_paths=10_000, block=1.0,
     rows, W = bootstrap_inputs(returns, weights)
     prm, ctx = _setup(rows.shape[1], n_steps, W.shape[0], compounding, v0, alpha, rf, False, False, devices, shard, context)
     out = ctx._call(prm, W, int(seed), int(path_begin), int(n_paths), store, rows=rows, block=b, period=period, cost=cost,
-                    horizons=steps, levels=levels, flows=flows, target=target)
-    return _result(out, np.asarray(weights).ndim == 1, store, as_array, steps, levels, compounding, flows, target)
+                    horizons=steps, levels=levels, flows=flows, target=target, glide=gl)
+    res = _result(out, np.asarray(weights).ndim == 1, store, as_array, steps, levels, compounding, flows, target)
+    if gl is not None and not as_array:
+        for d, blk in zip([res] if isinstance(res, dict) else res, _glide_blocks(gl, W)):
+            d["glide"] = blk
+    return res
 
 
 def filtered_inputs(filtered, weights):
@@ -1159,6 +1269,8 @@ def simulate_sweep(mu, cov, weights=None, n_portfolios=2500, min_weights=None, m
         raise ValueError("simulate_sweep does not take horizons or bands: call simulate_paths for the optimum")
     if kw.get("cashflow") is not None or kw.get("target") is not None:
         raise ValueError("simulate_sweep does not take cashflow or target: call simulate_paths for the optimum")
+    if kw.get("glide") is not None:
+        raise ValueError("simulate_sweep does not take glide: call simulate_paths for the optimum")
     if kw.get("attribution"):
         raise ValueError("simulate_sweep does not take attribution: call simulate_paths for the optimum")
     kw.pop("attribution", None)
