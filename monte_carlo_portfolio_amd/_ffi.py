@@ -163,7 +163,6 @@ SIGNATURES = {
     "mcp_ctx_exchange_note": (ctypes.c_char_p, [_vp]),
     "mcp_ctx_set_terminal_budget": (_int, [_vp, ctypes.c_size_t]),
     "mcp_ctx_destroy": (None, [_vp]),
-    "mcp_simulate": (_int, [_vp, _PP, _f32p, _f32p, _f32p, _u64, _u64, _u64, _vp, _vp]),
     "mcp_sweep_historical": (_int, [_vp, _int, _int, _int, _f64p, _f64p, _f64p, _f64p, ctypes.c_double, ctypes.c_double,
                                     _f64p, _f64p, _f64p, _f64p, _f64p]),
     "mcp_ws_bytes": (ctypes.c_size_t, [_int, _int, _u64]),
@@ -172,47 +171,17 @@ SIGNATURES = {
     "mcp_packed_len": (ctypes.c_size_t, [_int, _int]),
     "mcp_pack_params": (_int, [_int, _int, _f32p, _f32p, _f32p, _f32p, ctypes.c_size_t]),
     "mcp_launch_paths": (_int, [_PP, _vp, _vp, _u64, _u64, _u64, _vp, _u64, _vp, _vp, _vp]),
-    "mcp_simulate_drawdown": (_int, [_vp, _PP, _f32p, _f32p, _f32p, _u64, _u64, _u64, _vp, _vp, _vp, _vp]),
     "mcp_launch_paths_drawdown": (_int, [_PP, _vp, _vp, _u64, _u64, _u64, _vp, _u64, _vp, _u64, _vp, _vp, _vp]),
-    "mcp_simulate_horizons": (_int, [_vp, _PP, _f32p, _f32p, _f32p, _u64, _u64, _u64, _int, _vp, _int, _vp, _vp, _vp, _vp, _vp,
-                                     _vp]),
     "mcp_launch_paths_horizons": (_int, [_PP, _vp, _vp, _u64, _u64, _u64, _vp, _u64, _int, _vp, _vp, _u64, _vp, _vp, _vp]),
-    "mcp_simulate_bootstrap": (_int, [_vp, _PP, ctypes.POINTER(McpBootstrap), _f32p, _u64, _u64, _u64, _vp, _vp]),
-    "mcp_simulate_bootstrap_horizons": (_int, [_vp, _PP, ctypes.POINTER(McpBootstrap), _f32p, _u64, _u64, _u64, _int, _vp, _int, _vp,
-                                               _vp, _vp, _vp, _vp, _vp]),
     "mcp_bootstrap_pivots": (_int, [_PP, ctypes.POINTER(McpBootstrap), _f32p, _f64p]),
-    "mcp_simulate_rebalanced": (_int, [_vp, _PP, ctypes.POINTER(McpRebalance), _vp, _vp, ctypes.POINTER(McpBootstrap), _f32p, _u64, _u64,
-                                       _u64, _int, _vp, _int, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mcp_rebalance_pivots": (_int, [_PP, ctypes.POINTER(McpRebalance), _vp, ctypes.POINTER(McpBootstrap), _f32p, _f64p]),
-    "mcp_simulate_student_t": (_int, [_vp, _PP, ctypes.POINTER(McpStudentT), _vp, _vp, _vp, _u64, _u64, _u64, _int, _vp, _int, _vp, _vp,
-                                      _vp, _vp, _vp, _vp, _vp, _vp]),
-    "mcp_simulate_garch": (_int, [_vp, _PP, ctypes.POINTER(McpGarch), ctypes.POINTER(McpStudentT), _vp, _vp, _vp, _u64, _u64, _u64, _int,
-                                  _vp, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "mcp_simulate_filtered": (_int, [_vp, _PP, ctypes.POINTER(McpFiltered), ctypes.POINTER(McpGarch), _vp, _u64, _u64, _u64, _int, _vp,
-                                     _int, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mcp_filtered_pivots": (_int, [_PP, ctypes.POINTER(McpFiltered), _f32p, _f64p]),
-    "mcp_simulate_jumps": (_int, [_vp, _PP, ctypes.POINTER(McpJumps), _vp, _vp, _vp, _u64, _u64, _u64, _int, _vp, _int, _vp, _vp, _vp,
-                                  _vp, _vp, _vp, _vp, _vp]),
     "mcp_jump_consts": (_int, [ctypes.POINTER(McpJumps), _int, _vp, _vp, ctypes.POINTER(ctypes.c_double), _vp]),
-    "mcp_simulate_regimes": (_int, [_vp, _PP, ctypes.POINTER(McpRegimes), _vp, _vp, _vp, _u64, _u64, _u64, _int, _vp, _int, _vp, _vp, _vp,
-                                    _vp, _vp, _vp, _vp, _vp]),
     "mcp_regime_consts": (_int, [ctypes.POINTER(McpRegimes), _vp, _vp]),
     "mcp_regime_pivots": (_int, [_PP, ctypes.POINTER(McpRegimes), _vp, _vp, _int, _vp, _vp, _vp]),
-    "mcp_simulate_attribution": (_int, [_vp, _PP, ctypes.POINTER(McpGarch), ctypes.POINTER(McpStudentT), _vp, _vp, _vp, _u64, _u64, _u64,
-                                        _vp, _vp, _vp, _vp, _vp]),
-    "mcp_simulate_antithetic": (_int, [_vp, _PP, ctypes.POINTER(McpGarch), ctypes.POINTER(McpStudentT), _vp, _vp, _vp, _u64, _u64, _u64,
-                                       _int, _vp, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "mcp_simulate_cashflow": (_int, [_vp, _PP, ctypes.POINTER(McpCashflow), _vp, _vp, ctypes.POINTER(McpBootstrap),
-                                     ctypes.POINTER(McpStudentT), _vp, _u64, _u64, _u64, _int, _vp, _int, _vp, _vp, _vp, _vp, _vp, _vp,
-                                     _vp, _vp]),
     "mcp_cashflow_pivots": (_int, [_PP, ctypes.POINTER(McpCashflow), _vp, ctypes.POINTER(McpBootstrap), _f32p, _f64p]),
-    "mcp_simulate_glide": (_int, [_vp, _PP, ctypes.POINTER(McpGlide), ctypes.POINTER(McpCashflow), _vp, _vp, ctypes.POINTER(McpBootstrap),
-                                  ctypes.POINTER(McpStudentT), _vp, _u64, _u64, _u64, _int, _vp, _int, _vp, _vp, _vp, _vp, _vp, _vp,
-                                  _vp, _vp]),
     "mcp_glide_pivots": (_int, [_PP, ctypes.POINTER(McpGlide), ctypes.POINTER(McpCashflow), _vp, ctypes.POINTER(McpBootstrap), _vp, _int,
                                 _vp, _vp, _vp]),
-    "mcp_simulate_overlay": (_int, [_vp, _PP, ctypes.POINTER(McpOverlay), _vp, _vp, ctypes.POINTER(McpStudentT), _vp, _u64, _u64, _u64,
-                                    _int, _vp, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mcp_overlay_pivots": (_int, [_PP, ctypes.POINTER(McpOverlay), _f32p, _f32p, _f64p]),
     "mcp_percentile_rank_q": (_int, [_u64, ctypes.c_double, ctypes.POINTER(_u64), ctypes.POINTER(_u64),
                                      ctypes.POINTER(ctypes.c_double)]),
@@ -232,6 +201,46 @@ SIGNATURES = {
     "mcp_key_to_float": (ctypes.c_float, [ctypes.c_uint32]),
     "mcp_terminal_to_x": (ctypes.c_double, [_PP, ctypes.c_float]),
 }
+
+# The argument groups of the host entry points mcp_simulate*: the types each one stands for.  mu, chol and W have a second
+# flavour, written `mu*`: an ndpointer, which takes the array itself.
+ARG_GROUPS = {
+    "ctx": [_vp], "prm": [_PP],
+    "gl": [ctypes.POINTER(McpGlide)], "cf": [ctypes.POINTER(McpCashflow)], "rb": [ctypes.POINTER(McpRebalance)],
+    "st": [ctypes.POINTER(McpStudentT)], "gv": [ctypes.POINTER(McpGarch)], "jp": [ctypes.POINTER(McpJumps)],
+    "rs": [ctypes.POINTER(McpRegimes)], "ft": [ctypes.POINTER(McpFiltered)], "ov": [ctypes.POINTER(McpOverlay)],
+    "bt": [ctypes.POINTER(McpBootstrap)],
+    "mu": [_vp], "chol": [_vp], "W": [_vp], "mu*": [_f32p], "chol*": [_f32p], "W*": [_f32p],
+    "walk": [_u64, _u64, _u64],                           # seed, path_begin, n_paths
+    "hz_in": [_int, _vp, _int, _vp],                      # n_horizons, horizons, n_levels, levels
+    "out": [_vp, _vp],                                    # terminal_out, stats_out
+    "dd": [_vp, _vp],                                     # mdd_out, dd_stats_out
+    "hz_out": [_vp, _vp, _vp],                            # horizon_out, hz_stats_out, bands_out
+    "counts": [_vp], "hz_counts": [_vp], "pairs": [_vp], "contrib": [_vp], "attr": [_vp], "attr_counts": [_vp],
+}
+
+# every mcp_simulate* entry point of include/mcport.h: its argument groups, in the header's order.  The one statement of that
+# order on the Python side: SIGNATURES and Context._call (simulate.py) both follow it.
+SIMULATE_ENTRIES = {
+    "mcp_simulate": "ctx prm mu* chol* W* walk out",
+    "mcp_simulate_drawdown": "ctx prm mu* chol* W* walk out dd",
+    "mcp_simulate_horizons": "ctx prm mu* chol* W* walk hz_in out hz_out",
+    "mcp_simulate_bootstrap": "ctx prm bt W* walk out",
+    "mcp_simulate_bootstrap_horizons": "ctx prm bt W* walk hz_in out hz_out",
+    "mcp_simulate_rebalanced": "ctx prm rb mu chol bt W* walk hz_in out hz_out",
+    "mcp_simulate_student_t": "ctx prm st mu chol W walk hz_in out dd hz_out",
+    "mcp_simulate_garch": "ctx prm gv st mu chol W walk hz_in out dd hz_out",
+    "mcp_simulate_filtered": "ctx prm ft gv W walk hz_in out hz_out",
+    "mcp_simulate_jumps": "ctx prm jp mu chol W walk hz_in out dd hz_out",
+    "mcp_simulate_regimes": "ctx prm rs mu chol W walk hz_in out dd hz_out",
+    "mcp_simulate_attribution": "ctx prm gv st mu chol W walk out contrib attr attr_counts",
+    "mcp_simulate_antithetic": "ctx prm gv st mu chol W walk hz_in out dd hz_out pairs",
+    "mcp_simulate_cashflow": "ctx prm cf mu chol bt st W walk hz_in out counts hz_out hz_counts",
+    "mcp_simulate_glide": "ctx prm gl cf mu chol bt st W walk hz_in out counts hz_out hz_counts",
+    "mcp_simulate_overlay": "ctx prm ov mu chol st W walk hz_in out dd hz_out",
+}
+SIMULATE_ENTRIES = {name: tuple(groups.split()) for name, groups in SIMULATE_ENTRIES.items()}
+SIGNATURES.update((name, (_int, [t for g in groups for t in ARG_GROUPS[g]])) for name, groups in SIMULATE_ENTRIES.items())
 
 _LIB = None
 
@@ -310,6 +319,16 @@ def check(rc: int) -> int:
     return rc
 
 
+def ptr(a):
+    """The void * of an array's data; None (NULL) for None."""
+    return a.ctypes.data_as(_vp) if a is not None else None
+
+
+def ref(x):
+    """A ctypes struct by reference; None (NULL) for None."""
+    return ctypes.byref(x) if x is not None else None
+
+
 def make_params(n_assets, n_steps, n_portfolios, compounding="simple", v0=1.0, alpha=0.95, rf=0.0,
                 native_math=False, fold=False, shard_portfolios=False) -> McpParams:
     if compounding not in MCP_COMPOUND:
@@ -366,7 +385,7 @@ def make_jumps(intensity: float, mean: float, std: float, loading: np.ndarray | 
     """mcp_jumps; `loading` is None (all ones) or a C-contiguous binary32 [N] array (the caller keeps it alive for the call)."""
     if loading is not None and (loading.dtype != np.float32 or loading.ndim != 1 or not loading.flags.c_contiguous):
         raise ValueError("jump loadings must be a C-contiguous float32 [N] array")
-    return McpJumps(float(intensity), float(mean), float(std), loading.ctypes.data_as(ctypes.c_void_p) if loading is not None else None, 0)
+    return McpJumps(float(intensity), float(mean), float(std), ptr(loading), 0)
 
 
 def jump_consts(intensity: float, mean: float, std: float, loading=None, mu=None, n_assets: int | None = None):
@@ -379,7 +398,6 @@ def jump_consts(intensity: float, mean: float, std: float, loading=None, mu=None
     mean_count = ctypes.c_double()
     drift = np.zeros(n, np.float32) if mu32 is not None else None
     jp = make_jumps(intensity, mean, std, ld)
-    ptr = lambda a: a.ctypes.data_as(_vp) if a is not None else None   # noqa: E731
     check(lib().mcp_jump_consts(ctypes.byref(jp), n, ptr(mu32), ptr(thr), ctypes.byref(mean_count), ptr(drift)))
     return thr, mean_count.value, drift
 
@@ -389,7 +407,6 @@ def make_regimes(p01: float, p10: float, start: float, mu1: np.ndarray | None, c
     for a, nd in ((mu1, 1), (chol1, 2)):
         if a is not None and (a.dtype != np.float32 or a.ndim != nd or not a.flags.c_contiguous):
             raise ValueError("regime mu1 [N] and chol1 [N, N] must be C-contiguous float32 arrays")
-    ptr = lambda a: a.ctypes.data_as(ctypes.c_void_p) if a is not None else None   # noqa: E731
     return McpRegimes(float(p01), float(p10), float(start), ptr(mu1), ptr(chol1), 0)
 
 
@@ -398,7 +415,7 @@ def regime_consts(p01: float, p10: float, start: float):
     uses (include/mcport.h, mcp_regime_consts), pure host arithmetic."""
     thr, p = np.zeros(3, np.uint64), np.zeros(3, np.float64)
     rs = make_regimes(p01, p10, start, None, None)
-    check(lib().mcp_regime_consts(ctypes.byref(rs), thr.ctypes.data_as(_vp), p.ctypes.data_as(_vp)))
+    check(lib().mcp_regime_consts(ctypes.byref(rs), ptr(thr), ptr(p)))
     return thr, p
 
 
@@ -413,7 +430,6 @@ def regime_pivots(prm: McpParams, regimes, mu: np.ndarray, mu1: np.ndarray, W: n
     hz = np.ascontiguousarray(horizons, np.int32) if horizons is not None and len(horizons) else None
     out = np.zeros(W.shape[0], np.float64)
     hout = np.zeros((hz.size, W.shape[0]), np.float64) if hz is not None else None
-    ptr = lambda a: a.ctypes.data_as(_vp) if a is not None else None   # noqa: E731
     check(lib().mcp_regime_pivots(ctypes.byref(prm), ctypes.byref(rs), ptr(mu), ptr(W), 0 if hz is None else hz.size, ptr(hz), ptr(out),
                                   ptr(hout)))
     return out, hout
@@ -436,8 +452,7 @@ def rebalance_pivots(prm: McpParams, period: int, W: np.ndarray, mu: np.ndarray 
     rb = McpRebalance(int(period), 0, float(cost))
     mu_p = np.ascontiguousarray(mu, np.float32) if mu is not None else None
     bt = make_bootstrap(np.ascontiguousarray(rows, np.float32), 1.0) if rows is not None else None
-    check(lib().mcp_rebalance_pivots(ctypes.byref(prm), ctypes.byref(rb), mu_p.ctypes.data_as(_vp) if mu_p is not None else None,
-                                     ctypes.byref(bt) if bt is not None else None, W, out))
+    check(lib().mcp_rebalance_pivots(ctypes.byref(prm), ctypes.byref(rb), ptr(mu_p), ref(bt), W, out))
     return out
 
 
@@ -458,8 +473,7 @@ def cashflow_pivots(prm: McpParams, flows: np.ndarray, W: np.ndarray, mu: np.nda
     cf = make_cashflow(flows)
     mu_p = np.ascontiguousarray(mu, np.float32) if mu is not None else None
     bt = make_bootstrap(np.ascontiguousarray(rows, np.float32), 1.0) if rows is not None else None
-    check(lib().mcp_cashflow_pivots(ctypes.byref(prm), ctypes.byref(cf), mu_p.ctypes.data_as(_vp) if mu_p is not None else None,
-                                    ctypes.byref(bt) if bt is not None else None, W, out))
+    check(lib().mcp_cashflow_pivots(ctypes.byref(prm), ctypes.byref(cf), ptr(mu_p), ref(bt), W, out))
     return out
 
 
@@ -489,10 +503,8 @@ def glide_pivots(prm: McpParams, breaks, targets, W: np.ndarray, flows=None, mu:
     hz = np.ascontiguousarray(horizons, np.int32) if horizons is not None and len(horizons) else None
     out = np.zeros(W.shape[0], np.float64)
     hout = np.zeros((hz.size, W.shape[0]), np.float64) if hz is not None else None
-    ptr = lambda a: a.ctypes.data_as(_vp) if a is not None else None   # noqa: E731
-    check(lib().mcp_glide_pivots(ctypes.byref(prm), ctypes.byref(gl), ctypes.byref(cf) if cf is not None else None, ptr(mu_p),
-                                 ctypes.byref(bt) if bt is not None else None, ptr(W), 0 if hz is None else hz.size, ptr(hz), ptr(out),
-                                 ptr(hout)))
+    check(lib().mcp_glide_pivots(ctypes.byref(prm), ctypes.byref(gl), ref(cf), ptr(mu_p), ref(bt), ptr(W),
+                                 0 if hz is None else hz.size, ptr(hz), ptr(out), ptr(hout)))
     return out, hout
 
 

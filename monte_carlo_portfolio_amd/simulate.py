@@ -21,6 +21,38 @@ _CTX_LOCK = threading.Lock()
 _CTX: dict[tuple, "Context"] = {}
 
 
+# Which mcp_simulate* entry point a call of Context._call takes: the first row whose keywords are all given.  Last in a row, the
+# sentence that refuses a keyword the entry point has no argument group for (None: a plain one naming the entry point and the
+# keyword).  A new feature adds its row here, its groups to _ffi.SIMULATE_ENTRIES and its keyword to _KEYWORD_GROUP.
+_ENTRY_CHOICE = (
+    (("glide",), "mcp_simulate_glide", "glide is not combined with drawdown, rebalance, overlay, garch, attribution, antithetic, jumps, "
+                                       "regimes or filtered rows"),
+    (("filtered",), "mcp_simulate_filtered", "filtered rows take garch, block and horizons only"),
+    (("regimes",), "mcp_simulate_regimes", "regimes are not combined with overlay, cashflow, rebalance, bootstrap rows, dof, garch, jumps, "
+                                           "attribution or antithetic"),
+    (("jumps",), "mcp_simulate_jumps", "jumps are not combined with overlay, cashflow, rebalance, bootstrap rows, dof, garch, attribution "
+                                       "or antithetic"),
+    (("antithetic",), "mcp_simulate_antithetic", "antithetic pairs are not combined with overlay, cashflow, rebalance, bootstrap rows or "
+                                                 "attribution"),
+    (("attribution",), "mcp_simulate_attribution", "attribution is not combined with overlay, cashflow, rebalance, bootstrap rows, "
+                                                   "horizons or drawdown"),
+    (("garch",), "mcp_simulate_garch", None),
+    (("overlay",), "mcp_simulate_overlay", None),
+    (("flows",), "mcp_simulate_cashflow", None),
+    (("dof",), "mcp_simulate_student_t", None),
+    (("period",), "mcp_simulate_rebalanced", None),
+    (("rows", "horizons"), "mcp_simulate_bootstrap_horizons", None),
+    (("rows",), "mcp_simulate_bootstrap", None),
+    (("horizons",), "mcp_simulate_horizons", None),
+    (("drawdown",), "mcp_simulate_drawdown", None),
+    ((), "mcp_simulate", None),
+)
+# the argument group of _ffi.SIMULATE_ENTRIES that carries each feature keyword of Context._call
+_KEYWORD_GROUP = {"rows": "bt", "dof": "st", "period": "rb", "drawdown": "dd", "horizons": "hz_in", "flows": "cf", "overlay": "ov",
+                  "garch": "gv", "attribution": "attr", "antithetic": "pairs", "filtered": "ft", "jumps": "jp", "regimes": "rs",
+                  "glide": "gl"}
+
+
 class Context:
     """Owns one mcp_ctx: device buffers + one stream per device.  `device` is a device index or a sequence of them
     (one context over several GPUs, exchanging through RCCL inside the library; a device listed
@@ -73,11 +105,25 @@ class Context:
         horizon_terminal: with `store` only; counts, hz_counts: with `flows` only; attr [K, N] records of ATTR_DTYPE and attr_counts
         [K, 2] with `attribution` only, contributions [K, N, n_paths] with `store` on top; pairs [K] records of PAIR_DTYPE with
         `antithetic` only)."""
-        K = prm.n_portfolios
-        ptr = lambda a: a.ctypes.data_as(ctypes.c_void_p) if a is not None else None   # noqa: E731
+        K, N = prm.n_portfolios, prm.n_assets
+        bt = _ffi.make_bootstrap(rows, block) if rows is not None else None
+        given = [kw for kw, on in (("rows", rows is not None), ("dof", dof is not None), ("period", period is not None),
+                                   ("drawdown", drawdown), ("horizons", horizons is not None), ("flows", flows is not None),
+                                   ("overlay", overlay is not None), ("garch", garch is not None), ("attribution", attribution),
+                                   ("antithetic", antithetic), ("filtered", filtered is not None), ("jumps", jumps is not None),
+                                   ("regimes", regimes is not None), ("glide", glide is not None)) if on]
+        has = set(given).issuperset
+        entry, refusal = next((e, r) for needs, e, r in _ENTRY_CHOICE if has(needs))
+        groups = _ffi.SIMULATE_ENTRIES[entry]
+        # the library states the rules (check_request); a keyword the entry point has no argument for is refused here, not dropped
+        for kw in given:
+            if _KEYWORD_GROUP[kw] not in groups:
+                raise ValueError(refusal or f"{entry} has no argument for {kw}")
+        if filtered is not None and garch is None:             # SPEC.md 4.11: the one keyword an entry point cannot do without
+            raise ValueError(refusal)
         stats = np.zeros(K, _ffi.STATS_DTYPE)
         term = np.empty((K, n_paths), np.float32) if store else None
-        dd_stats = raw = hz_stats = bands = hz_term = steps = lv = counts = hz_counts = None
+        dd_stats = raw = hz_stats = bands = hz_term = steps = lv = None
         H = L = 0
         if drawdown:
             dd_stats = np.zeros(K, _ffi.STATS_DTYPE)
@@ -89,110 +135,31 @@ class Context:
             hz_stats = np.zeros((H, K), _ffi.STATS_DTYPE)
             bands = np.zeros((H, K, L), np.float64)
             hz_term = np.empty((H, K, n_paths), np.float32) if store else None
-        lib, prm_p, walk = _ffi.lib(), ctypes.byref(prm), (seed, path_begin, n_paths)
-        hz_in = (H, ptr(steps) if H else None, L, ptr(lv) if L else None)
-        hz_out = (ptr(hz_term), ptr(hz_stats), ptr(bands) if L else None)
-        bt = _ffi.make_bootstrap(rows, block) if rows is not None else None
-        attr = attr_counts = contrib = pairs = None
-        if glide is not None:
-            # SPEC.md 4.14: glide is the (breaks int32 [G], targets binary32 [G, K, N]) of check_glide; the cash-flow call on scheduled
-            # weights (flows None: the all-zero schedule).  The library states the rules (check_request)
-            if (filtered is not None or regimes is not None or jumps is not None or antithetic or attribution or garch is not None
-                    or overlay is not None or period is not None or drawdown):
-                raise ValueError("glide is not combined with drawdown, rebalance, overlay, garch, attribution, antithetic, jumps, regimes "
-                                 "or filtered rows")
-            counts = np.zeros((K, 2), np.uint64)
-            hz_counts = np.zeros((H, K, 2), np.uint64) if horizons is not None else None
-            st = _ffi.McpStudentT(int(dof), 0) if dof is not None else None
-            gl = _ffi.make_glide(*glide)
-            cf = _ffi.make_cashflow(flows, target) if flows is not None else None
-            rc = lib.mcp_simulate_glide(self._h, prm_p, ctypes.byref(gl), ctypes.byref(cf) if cf is not None else None, ptr(mu), ptr(chol),
-                                        ctypes.byref(bt) if bt is not None else None, ctypes.byref(st) if st is not None else None,
-                                        ptr(W), *walk, *hz_in, ptr(term), ptr(stats), ptr(counts), *hz_out, ptr(hz_counts))
-        elif filtered is not None:
-            # SPEC.md 2.4 / 4.11: the library states the rules (check_request); nothing else of this method is passed on
-            if (overlay is not None or flows is not None or period is not None or bt is not None or dof is not None or attribution
-                    or antithetic or drawdown or garch is None):
-                raise ValueError("filtered rows take garch, block and horizons only")
-            ft = _ffi.make_filtered(*filtered, block)
-            gv = _ffi.McpGarch(float(garch[0]), float(garch[1]), float(garch[2]), 0)
-            rc = lib.mcp_simulate_filtered(self._h, prm_p, ctypes.byref(ft), ctypes.byref(gv), ptr(W), *walk, *hz_in, ptr(term), ptr(stats),
-                                           *hz_out)
-        elif regimes is not None:
-            # SPEC.md 2.6 / 4.13: the library states the rules (check_request); Gaussian draws with the drawdown or horizons only
-            if (overlay is not None or flows is not None or period is not None or bt is not None or dof is not None or attribution
-                    or antithetic or garch is not None or jumps is not None):
-                raise ValueError("regimes are not combined with overlay, cashflow, rebalance, bootstrap rows, dof, garch, jumps, "
-                                 "attribution or antithetic")
-            rs = _ffi.make_regimes(*regimes)
-            rc = lib.mcp_simulate_regimes(self._h, prm_p, ctypes.byref(rs), ptr(mu), ptr(chol), ptr(W), *walk, *hz_in, ptr(term),
-                                          ptr(stats), ptr(raw), ptr(dd_stats), *hz_out)
-        elif jumps is not None:
-            # SPEC.md 2.5 / 4.12: the library states the rules (check_request); Gaussian draws with the drawdown or horizons only
-            if (overlay is not None or flows is not None or period is not None or bt is not None or dof is not None or attribution
-                    or antithetic or garch is not None):
-                raise ValueError("jumps are not combined with overlay, cashflow, rebalance, bootstrap rows, dof, garch, attribution or "
-                                 "antithetic")
-            jp = _ffi.make_jumps(*jumps)
-            rc = lib.mcp_simulate_jumps(self._h, prm_p, ctypes.byref(jp), ptr(mu), ptr(chol), ptr(W), *walk, *hz_in, ptr(term), ptr(stats),
-                                        ptr(raw), ptr(dd_stats), *hz_out)
-        elif antithetic:
-            # the library states the rules (check_request): everything but plain, Student-t and GARCH draws is MCP_E_UNSUPPORTED
-            if overlay is not None or flows is not None or period is not None or bt is not None or attribution:
-                raise ValueError("antithetic pairs are not combined with overlay, cashflow, rebalance, bootstrap rows or attribution")
-            pairs = np.zeros(K, _ffi.PAIR_DTYPE)
-            st = _ffi.McpStudentT(int(dof), 0) if dof is not None else None
-            gv = _ffi.McpGarch(float(garch[0]), float(garch[1]), float(garch[2]), 0) if garch is not None else None
-            rc = lib.mcp_simulate_antithetic(self._h, prm_p, ctypes.byref(gv) if gv is not None else None,
-                                             ctypes.byref(st) if st is not None else None, ptr(mu), ptr(chol), ptr(W), *walk, *hz_in,
-                                             ptr(term), ptr(stats), ptr(raw), ptr(dd_stats), *hz_out, ptr(pairs))
-        elif attribution:
-            # the library states the rules (check_request): everything but plain, Student-t and GARCH draws is MCP_E_UNSUPPORTED
-            if (overlay is not None or flows is not None or period is not None or bt is not None or horizons is not None or drawdown):
-                raise ValueError("attribution is not combined with overlay, cashflow, rebalance, bootstrap rows, horizons or drawdown")
-            N = prm.n_assets
-            attr = np.zeros((K, N), _ffi.ATTR_DTYPE)
-            attr_counts = np.zeros((K, 2), np.uint64)
-            contrib = np.empty((K, N, n_paths), np.float32) if store else None
-            st = _ffi.McpStudentT(int(dof), 0) if dof is not None else None
-            gv = _ffi.McpGarch(float(garch[0]), float(garch[1]), float(garch[2]), 0) if garch is not None else None
-            rc = lib.mcp_simulate_attribution(self._h, prm_p, ctypes.byref(gv) if gv is not None else None,
-                                              ctypes.byref(st) if st is not None else None, ptr(mu), ptr(chol), ptr(W), *walk, ptr(term),
-                                              ptr(stats), ptr(contrib), ptr(attr), ptr(attr_counts))
-        elif garch is not None:
-            st = _ffi.McpStudentT(int(dof), 0) if dof is not None else None
-            gv = _ffi.McpGarch(float(garch[0]), float(garch[1]), float(garch[2]), 0)
-            rc = lib.mcp_simulate_garch(self._h, prm_p, ctypes.byref(gv), ctypes.byref(st) if st is not None else None, ptr(mu),
-                                        ptr(chol), ptr(W), *walk, *hz_in, ptr(term), ptr(stats), ptr(raw), ptr(dd_stats), *hz_out)
-        elif overlay is not None:
-            st = _ffi.McpStudentT(int(dof), 0) if dof is not None else None
-            rc = lib.mcp_simulate_overlay(self._h, prm_p, ctypes.byref(_ffi.make_overlay(*overlay)), ptr(mu), ptr(chol),
-                                          ctypes.byref(st) if st is not None else None, ptr(W), *walk, *hz_in, ptr(term), ptr(stats),
-                                          ptr(raw), ptr(dd_stats), *hz_out)
-        elif flows is not None:
-            counts = np.zeros((K, 2), np.uint64)
-            hz_counts = np.zeros((H, K, 2), np.uint64) if horizons is not None else None
-            st = _ffi.McpStudentT(int(dof), 0) if dof is not None else None
-            rc = lib.mcp_simulate_cashflow(self._h, prm_p, ctypes.byref(_ffi.make_cashflow(flows, target)), ptr(mu), ptr(chol),
-                                           ctypes.byref(bt) if bt is not None else None, ctypes.byref(st) if st is not None else None,
-                                           ptr(W), *walk, *hz_in, ptr(term), ptr(stats), ptr(counts), *hz_out, ptr(hz_counts))
-        elif dof is not None:
-            rc = lib.mcp_simulate_student_t(self._h, prm_p, ctypes.byref(_ffi.McpStudentT(int(dof), 0)), ptr(mu), ptr(chol), ptr(W), *walk,
-                                            *hz_in, ptr(term), ptr(stats), ptr(raw), ptr(dd_stats), *hz_out)
-        elif period is not None:
-            rc = lib.mcp_simulate_rebalanced(self._h, prm_p, ctypes.byref(_ffi.McpRebalance(int(period), 0, float(cost))), ptr(mu),
-                                             ptr(chol), ctypes.byref(bt) if bt is not None else None, W, *walk, *hz_in, ptr(term),
-                                             ptr(stats), *hz_out)
-        elif bt is not None and horizons is not None:
-            rc = lib.mcp_simulate_bootstrap_horizons(self._h, prm_p, ctypes.byref(bt), W, *walk, *hz_in, ptr(term), ptr(stats), *hz_out)
-        elif bt is not None:
-            rc = lib.mcp_simulate_bootstrap(self._h, prm_p, ctypes.byref(bt), W, *walk, ptr(term), ptr(stats))
-        elif horizons is not None:
-            rc = lib.mcp_simulate_horizons(self._h, prm_p, mu, chol, W, *walk, *hz_in, ptr(term), ptr(stats), *hz_out)
-        elif drawdown:
-            rc = lib.mcp_simulate_drawdown(self._h, prm_p, mu, chol, W, *walk, ptr(term), ptr(stats), ptr(raw), ptr(dd_stats))
-        else:
-            rc = lib.mcp_simulate(self._h, prm_p, mu, chol, W, *walk, ptr(term), ptr(stats))
+        counts = np.zeros((K, 2), np.uint64) if "counts" in groups else None
+        hz_counts = np.zeros((H, K, 2), np.uint64) if "hz_counts" in groups and horizons is not None else None
+        pairs = np.zeros(K, _ffi.PAIR_DTYPE) if "pairs" in groups else None
+        attr = np.zeros((K, N), _ffi.ATTR_DTYPE) if "attr" in groups else None
+        attr_counts = np.zeros((K, 2), np.uint64) if "attr_counts" in groups else None
+        contrib = np.empty((K, N, n_paths), np.float32) if "contrib" in groups and store else None
+        vals = {"ctx": (self._h,), "prm": (prm,), "mu": (mu,), "chol": (chol,), "W": (W,), "walk": (seed, path_begin, n_paths),
+                "hz_in": (H, steps if H else None, L, lv if L else None), "out": (term, stats), "dd": (raw, dd_stats),
+                "hz_out": (hz_term, hz_stats, bands if L else None), "counts": (counts,), "hz_counts": (hz_counts,), "pairs": (pairs,),
+                "contrib": (contrib,), "attr": (attr,), "attr_counts": (attr_counts,), "bt": (bt,),
+                "gl": (_ffi.make_glide(*glide) if glide is not None else None,),               # flows None: the all-zero schedule
+                "cf": (_ffi.make_cashflow(flows, target) if flows is not None else None,),
+                "rb": (_ffi.McpRebalance(int(period), 0, float(cost)) if period is not None else None,),
+                "st": (_ffi.McpStudentT(int(dof), 0) if dof is not None else None,),
+                "gv": (_ffi.McpGarch(float(garch[0]), float(garch[1]), float(garch[2]), 0) if garch is not None else None,),
+                "jp": (_ffi.make_jumps(*jumps) if jumps is not None else None,),
+                "rs": (_ffi.make_regimes(*regimes) if regimes is not None else None,),
+                "ft": (_ffi.make_filtered(*filtered, block) if filtered is not None else None,),
+                "ov": (_ffi.make_overlay(*overlay) if overlay is not None else None,)}
+
+        def arg(group, v):               # a struct by reference and an array by its address; the ndpointer flavour takes the array
+            if isinstance(v, np.ndarray):
+                return v if group.endswith("*") else _ffi.ptr(v)
+            return ctypes.byref(v) if isinstance(v, ctypes.Structure) else v
+        rc = getattr(_ffi.lib(), entry)(*(arg(g, v) for g in groups for v in vals[g.rstrip("*")]))
         _ffi.check(rc)
         return _Outputs(stats, dd_stats, hz_stats, bands, term, raw, hz_term, counts, hz_counts, attr, attr_counts, contrib, pairs)
 
@@ -730,6 +697,61 @@ def antithetic_to_dict(rec) -> dict:
             "mean_se_iid": iid, "variance_ratio": (se / iid) ** 2 if iid != 0.0 else 0.0}
 
 
+# Which features of simulate_paths combine: per feature, what it needs (the head of the refusal), the names it is not combined
+# with, and whether the refusal lists the offending names only (True) or all of them as one fixed sentence (False).  A name is a
+# keyword -- given when it is not None, or true for a flag -- or keyword='value'.  The rows stand in the order the rules are
+# checked, so the same rule wins when two apply.  The C side states the same rules for the library (check_request).
+_FLAGS = ("drawdown", "attribution", "antithetic", "fold", "native_math")
+_PATHS_COMBINE = {
+    "glide": ("glide needs the cashflow walk -- simple compounding, the spec's normals and the unfolded recurrence",
+              ("drawdown", "rebalance", "overlay", "garch", "attribution", "antithetic", "jumps", "regimes", "fold", "native_math",
+               "compounding='log'"), True),
+    "regimes": ("regimes need Gaussian draws, constant weights, simple compounding, the spec's normals and the unfolded recurrence",
+                ("dof", "garch", "jumps", "rebalance", "cashflow", "overlay", "attribution", "antithetic", "fold", "native_math",
+                 "compounding='log'"), True),
+    "jumps": ("jumps need Gaussian draws, constant weights, simple compounding, the spec's normals and the unfolded recurrence",
+              ("dof", "garch", "rebalance", "cashflow", "overlay", "attribution", "antithetic", "fold", "native_math",
+               "compounding='log'"), True),
+    "antithetic": ("antithetic needs constant weights, the spec's normals, the unfolded recurrence and path shards",
+                   ("rebalance", "cashflow", "overlay", "attribution", "fold", "native_math", "shard='portfolios'"), True),
+    "attribution": ("attribution needs constant weights, simple compounding, the spec's normals, the unfolded recurrence and path shards",
+                    ("drawdown", "horizons", "rebalance", "cashflow", "overlay", "fold", "native_math", "compounding='log'",
+                     "shard='portfolios'"), True),
+    "garch": ("garch needs simple compounding, the spec's normals, the unfolded recurrence and constant weights",
+              ("rebalance", "cashflow", "overlay", "fold", "native_math", "compounding='log'"), False),
+    "overlay": ("overlay needs simple compounding, the spec's normals, the unfolded recurrence and constant weights",
+                ("rebalance", "cashflow", "fold", "native_math", "compounding='log'"), False),
+    "cashflow": ("cashflow needs simple compounding, the spec's normals, the unfolded recurrence and constant weights",
+                 ("drawdown", "rebalance", "fold", "native_math", "compounding='log'"), False),
+    "dof": ("dof needs simple compounding, the spec's normals, the unfolded recurrence and constant weights",
+            ("fold", "native_math", "rebalance", "compounding='log'"), False),
+    "rebalance": ("rebalance needs the spec's normals and the unfolded recurrence", ("drawdown", "fold", "native_math"), False),
+    "drawdown": ("drawdown=True needs the spec's normals and the unfolded recurrence", ("fold", "native_math"), False),
+    "horizons": ("horizons need the spec's normals and the unfolded recurrence", ("drawdown", "fold", "native_math"), False),
+}
+# simulate_bootstrap: the same two features on observed rows
+_BOOTSTRAP_COMBINE = {
+    "glide": ("glide needs the cashflow walk and simple compounding", ("rebalance", "compounding='log'"), False),
+    "cashflow": ("cashflow needs simple compounding and constant weights", ("rebalance", "compounding='log'"), False),
+}
+
+
+def _given(name, kw):
+    """Whether the call's keywords `kw` hold `name` (a row of _PATHS_COMBINE explains the names)."""
+    if "=" in name:
+        key, value = name.split("=")
+        return kw[key] == value.strip("'")
+    return bool(kw[name]) if name in _FLAGS else kw[name] is not None
+
+
+def _check_combines(table, feature, kw):
+    """ValueError if `feature` is given together with a name its row of `table` excludes."""
+    head, names, listed = table[feature]
+    bad = [name for name in names if _given(name, kw)] if _given(feature, kw) else []
+    if bad:
+        raise ValueError(f"{head}: not with " + (", ".join(bad) if listed else ", ".join(names[:-1]) + " or " + names[-1]))
+
+
 def simulate_paths(mu, cov, weights, n_steps=252, n_paths=10_000, seed=0, v0=1.0, compounding="simple",
                    rf=0.0, alpha=0.95, devices=None, store=False, path_begin=0, chol=None,
                    native_math=False, as_array=False, fold=False, shard="auto", context=None, drawdown=False,
@@ -876,89 +898,46 @@ def simulate_paths(mu, cov, weights, n_steps=252, n_paths=10_000, seed=0, v0=1.0
     glide with drawdown, rebalance, overlay, garch, attribution, antithetic, jumps, regimes, fold, native_math or
     compounding="log" (ValueError), on filtered rows, in simulate_sweep, in PathEngine and at the mcp_launch_* level.
     """
+    kw = dict(glide=glide, regimes=regimes, jumps=jumps, antithetic=antithetic, attribution=attribution, garch=garch, overlay=overlay,
+              cashflow=cashflow, dof=dof, rebalance=rebalance, drawdown=drawdown, horizons=horizons, fold=fold, native_math=native_math,
+              compounding=compounding, shard=shard)
     gl = check_glide(glide, weights, n_steps)
-    if gl is not None:
-        bad = [name for name, on in (("drawdown", bool(drawdown)), ("rebalance", rebalance is not None), ("overlay", overlay is not None),
-                                     ("garch", garch is not None), ("attribution", bool(attribution)), ("antithetic", bool(antithetic)),
-                                     ("jumps", jumps is not None), ("regimes", regimes is not None), ("fold", fold),
-                                     ("native_math", native_math), ("compounding='log'", compounding == "log")) if on]
-        if bad:
-            raise ValueError("glide needs the cashflow walk -- simple compounding, the spec's normals and the unfolded recurrence: not "
-                             f"with {', '.join(bad)}")
-        if cashflow is None:
-            cashflow = 0.0
+    _check_combines(_PATHS_COMBINE, "glide", kw)
+    if gl is not None and cashflow is None:
+        kw["cashflow"] = cashflow = 0.0
     rv = check_regimes(regimes, len(np.atleast_1d(np.asarray(mu))), factor=chol is not None)
+    _check_combines(_PATHS_COMBINE, "regimes", kw)
     if rv is not None:
-        bad = [name for name, on in (("dof", dof is not None), ("garch", garch is not None), ("jumps", jumps is not None),
-                                     ("rebalance", rebalance is not None), ("cashflow", cashflow is not None),
-                                     ("overlay", overlay is not None), ("attribution", bool(attribution)),
-                                     ("antithetic", bool(antithetic)), ("fold", fold), ("native_math", native_math),
-                                     ("compounding='log'", compounding == "log")) if on]
-        if bad:
-            raise ValueError("regimes need Gaussian draws, constant weights, simple compounding, the spec's normals and the unfolded "
-                             f"recurrence: not with {', '.join(bad)}")
         with np.errstate(over="ignore"):
             if not (np.all(np.isfinite(np.asarray(mu, np.float64))) and np.all(np.isfinite(np.asarray(mu, np.float64).astype(np.float32)))
                     and np.all(np.isfinite(np.asarray(cov if chol is None else chol, np.float64)))):
                 raise ValueError("regimes need finite mu and cov")
     jv = check_jumps(jumps, len(np.atleast_1d(np.asarray(mu))))
-    if jv is not None:
-        bad = [name for name, on in (("dof", dof is not None), ("garch", garch is not None), ("rebalance", rebalance is not None),
-                                     ("cashflow", cashflow is not None), ("overlay", overlay is not None),
-                                     ("attribution", bool(attribution)), ("antithetic", bool(antithetic)), ("fold", fold),
-                                     ("native_math", native_math), ("compounding='log'", compounding == "log")) if on]
-        if bad:
-            raise ValueError("jumps need Gaussian draws, constant weights, simple compounding, the spec's normals and the unfolded "
-                             f"recurrence: not with {', '.join(bad)}")
+    _check_combines(_PATHS_COMBINE, "jumps", kw)
     if not isinstance(antithetic, (bool, np.bool_)):
         raise ValueError(f"antithetic must be True or False, got {antithetic!r}")
-    if antithetic:
-        bad = [name for name, on in (("rebalance", rebalance is not None), ("cashflow", cashflow is not None),
-                                     ("overlay", overlay is not None), ("attribution", bool(attribution)), ("fold", fold),
-                                     ("native_math", native_math), ("shard='portfolios'", shard == "portfolios")) if on]
-        if bad:
-            raise ValueError("antithetic needs constant weights, the spec's normals, the unfolded recurrence and path shards: not with "
-                             f"{', '.join(bad)}")
-        if int(n_paths) % 2 or int(path_begin) % 2:
-            raise ValueError(f"antithetic pairs need an even n_paths and an even path_begin, got n_paths={n_paths}, path_begin={path_begin}")
+    _check_combines(_PATHS_COMBINE, "antithetic", kw)
+    if antithetic and (int(n_paths) % 2 or int(path_begin) % 2):
+        raise ValueError(f"antithetic pairs need an even n_paths and an even path_begin, got n_paths={n_paths}, path_begin={path_begin}")
     if not isinstance(attribution, (bool, np.bool_)):
         raise ValueError(f"attribution must be True or False, got {attribution!r}")
+    _check_combines(_PATHS_COMBINE, "attribution", kw)
     if attribution:
-        bad = [name for name, on in (("drawdown", drawdown), ("horizons", horizons is not None), ("rebalance", rebalance is not None),
-                                     ("cashflow", cashflow is not None), ("overlay", overlay is not None), ("fold", fold),
-                                     ("native_math", native_math), ("compounding='log'", compounding == "log"),
-                                     ("shard='portfolios'", shard == "portfolios")) if on]
-        if bad:
-            raise ValueError("attribution needs constant weights, simple compounding, the spec's normals, the unfolded recurrence and "
-                             f"path shards: not with {', '.join(bad)}")
         k_attr = np.atleast_2d(np.asarray(weights)).shape[0]
         if k_attr > _ffi.MCP_MAX_ATTR_PORTFOLIOS:
             raise ValueError(f"attribution takes at most {_ffi.MCP_MAX_ATTR_PORTFOLIOS} portfolios, got {k_attr}: call simulate_paths "
                              "for the portfolios of interest")
     gv = check_garch(garch)
-    if gv is not None and (rebalance is not None or cashflow is not None or overlay is not None or fold or native_math
-                           or compounding == "log"):
-        raise ValueError("garch needs simple compounding, the spec's normals, the unfolded recurrence and constant weights: not with "
-                         "rebalance, cashflow, overlay, fold, native_math or compounding='log'")
+    _check_combines(_PATHS_COMBINE, "garch", kw)
     ov = check_overlay(overlay, spot, len(np.atleast_1d(np.asarray(mu))))
-    if ov is not None and (rebalance is not None or cashflow is not None or fold or native_math or compounding == "log"):
-        raise ValueError("overlay needs simple compounding, the spec's normals, the unfolded recurrence and constant weights: not "
-                         "with rebalance, cashflow, fold, native_math or compounding='log'")
+    _check_combines(_PATHS_COMBINE, "overlay", kw)
     flows, target = check_cashflow(cashflow, target, n_steps)
-    if flows is not None and (drawdown or rebalance is not None or fold or native_math or compounding == "log"):
-        raise ValueError("cashflow needs simple compounding, the spec's normals, the unfolded recurrence and constant weights: not "
-                         "with drawdown, rebalance, fold, native_math or compounding='log'")
+    _check_combines(_PATHS_COMBINE, "cashflow", kw)
     dof = check_dof(dof)
-    if dof is not None and (fold or native_math or compounding == "log" or rebalance is not None):
-        raise ValueError("dof needs simple compounding, the spec's normals, the unfolded recurrence and constant weights: not with "
-                         "fold, native_math, rebalance or compounding='log'")
+    _check_combines(_PATHS_COMBINE, "dof", kw)
     period, cost = check_rebalance(rebalance, rebalance_cost)
-    if period is not None and (drawdown or fold or native_math):
-        raise ValueError("rebalance needs the spec's normals and the unfolded recurrence: not with drawdown, fold or native_math")
-    if drawdown and (fold or native_math):
-        raise ValueError("drawdown=True needs the spec's normals and the unfolded recurrence: not with fold or native_math")
-    if horizons is not None and (drawdown or fold or native_math):
-        raise ValueError("horizons need the spec's normals and the unfolded recurrence: not with drawdown, fold or native_math")
+    for feature in ("rebalance", "drawdown", "horizons"):
+        _check_combines(_PATHS_COMBINE, feature, kw)
     steps, levels = _check_walk(n_steps, horizons, bands, period, compounding, shard)
     if jv is not None and chol is None:                    # `cov` is the total covariance: the diffusion gets what the jumps leave
         from .jumps import diffusion_cov
@@ -1156,15 +1135,13 @@ def simulate_bootstrap(returns, weights, n_steps=252, n_paths=10_000, block=1.0,
         raise ValueError(f"simulate_bootstrap does not take {sorted(unsupported)} (no normals: no fold / native_math / dof -- "
                          "Student-t draws are a parametric model, call simulate_paths(dof=...); drawdown on bootstrap paths is "
                          "not supported)")
+    kw = dict(glide=glide, cashflow=cashflow, rebalance=rebalance, compounding=compounding)
     gl = check_glide(glide, weights, n_steps)
-    if gl is not None:
-        if rebalance is not None or compounding == "log":
-            raise ValueError("glide needs the cashflow walk and simple compounding: not with rebalance or compounding='log'")
-        if cashflow is None:
-            cashflow = 0.0
+    _check_combines(_BOOTSTRAP_COMBINE, "glide", kw)
+    if gl is not None and cashflow is None:
+        kw["cashflow"] = cashflow = 0.0
     flows, target = check_cashflow(cashflow, target, n_steps)
-    if flows is not None and (rebalance is not None or compounding == "log"):
-        raise ValueError("cashflow needs simple compounding and constant weights: not with rebalance or compounding='log'")
+    _check_combines(_BOOTSTRAP_COMBINE, "cashflow", kw)
     period, cost = check_rebalance(rebalance, rebalance_cost)
     b = float(block)
     if not b >= 1.0:

@@ -22,6 +22,23 @@ def test_header_and_binding_agree():
     assert declared_symbols() == sorted(_ffi.SIGNATURES)
 
 
+def test_header_and_binding_agree_on_argument_counts():
+    """Every prototype of include/mcport.h has as many parameters as its row of _ffi.SIGNATURES has argtypes, and every row has the
+    argument types it had before the mcp_simulate* rows were derived from _ffi.SIMULATE_ENTRIES (tests/golden/front_end_cases.json,
+    block "argtypes": the parent commit's, by name)."""
+    import json
+    text = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "mcport.h")).read(), flags=re.S)
+    protos = dict(re.findall(r"\b(mcp_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", text))
+    assert sorted(protos) == sorted(_ffi.SIGNATURES) and len(protos) == 59
+    for name, params in protos.items():
+        n = 0 if params.strip() in ("", "void") else len(params.split(","))
+        assert n == len(_ffi.SIGNATURES[name][1]), name
+    want = json.load(open(os.path.join(ROOT, "tests", "golden", "front_end_cases.json")))["argtypes"]
+    got = {name: [t.__name__ for t in args] for name, (_, args) in _ffi.SIGNATURES.items()}
+    assert got == want
+    assert sorted(_ffi.SIMULATE_ENTRIES) == sorted(n for n in protos if n.startswith("mcp_simulate")) and len(_ffi.SIMULATE_ENTRIES) == 16
+
+
 def test_library_exports_every_declared_symbol(mcp_lib):
     raw = ctypes.CDLL(_ffi.LIB_PATH)
     for name in declared_symbols():
