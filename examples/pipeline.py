@@ -161,6 +161,26 @@ def main(paths, resample_rule="M", user_rf=3.0, investment=10000.0, seed=12345, 
     print(f"  optimum without regimes: VaR = {sim['var']:+.4f}  CVaR = {sim['cvar']:+.4f}  mean max drawdown = {sim['drawdown']['mean']:+.4f}")
     print(f"  optimum with regimes:    VaR = {rsim['var']:+.4f}  CVaR = {rsim['cvar']:+.4f}  mean max drawdown = "
           f"{rsim['drawdown']['mean']:+.4f}  (long-run share of crisis steps {rsim['regimes']['stationary'] * 100:.1f} %)")
+    # downside protection three ways on the same weights and model (SPEC.md 4.15 / 5.15): left alone, the protective put above (static,
+    # paid for up front), and an 80 % floor held dynamically at a multiplier of 4 (CPPI: four times the cushion above the floor in the
+    # portfolio, the rest riskless).  The gap probability is the share of paths that end below 80 % of the capital: the dynamic floor
+    # holds while every step stays above -1 / m, so under small Gaussian steps it is 0; steps as large as these rows', and crash
+    # jumps, gap through it -- the number to read next to the put's premium
+    floor_T = np.float32(0.8 * investment)
+    for draws, dkw in (("Gaussian draws", {}), ("fitted jumps", {"jumps": tuple(jfit[:4])})):
+        for label, kw in (("unprotected", {}), ("protective put", {"overlay": {0: put}, "spot": spots}),
+                          ("80 % floor at m = 4", {"protect": (0.8, 4.0)})):
+            if "overlay" in kw and dkw:
+                print(f"protection on {draws} ( {label} ): not built (the overlay is not combined with jumps)")
+                continue
+            args = dict(n_steps=af, n_paths=n_paths, seed=seed, v0=investment, drawdown=True, store=True, **kw, **dkw)
+            try:
+                o = mcp.simulate_paths(raw.mean().values, raw.cov().values, w, **args)
+            except ValueError:            # the fitted jumps carry more variance than the covariance leaves: keep the diffusion whole
+                o = mcp.simulate_paths(raw.mean().values, raw.cov().values, w, chol=np.linalg.cholesky(raw.cov().values), **args)
+            gap = o["protect"]["gap_probability"] if "protect" in o else float(np.mean(o["terminal"] < floor_T))
+            print(f"protection on {draws} ( {label} ): VaR95 {o['var']:+.4f}  CVaR95 {o['cvar']:+.4f}  mean max drawdown "
+                  f"{o['drawdown']['mean']:+.4f}  gap probability {gap:.4f}")
     return res, sim
 
 

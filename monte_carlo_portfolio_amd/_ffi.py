@@ -108,6 +108,13 @@ class McpGlide(ctypes.Structure):
     _fields_ = [("breaks", ctypes.c_void_p), ("targets", ctypes.c_void_p), ("n_breaks", ctypes.c_int32), ("reserved", ctypes.c_int32)]
 
 
+class McpProtect(ctypes.Structure):
+    """mcp_protect (include/mcport_protect.h): the floor schedule (binary32 [n_steps + 1]), multiplier, cap, rate and ratchet of
+    SPEC.md 4.15 and the optional target (NULL or one binary64 value)."""
+    _fields_ = [("floor", ctypes.c_void_p), ("multiplier", ctypes.c_double), ("cap", ctypes.c_double), ("rate", ctypes.c_double),
+                ("ratchet", ctypes.c_double), ("target", ctypes.c_void_p), ("reserved", ctypes.c_int32)]
+
+
 class McpOverlay(ctypes.Structure):
     """mcp_overlay: the option rows of SPEC.md 4.8 -- rows [n_rows] of OVERLAY_ROW_DTYPE, row_begin int32 [N + 1], spot binary32 [N]."""
     _fields_ = [("rows", ctypes.c_void_p), ("row_begin", ctypes.c_void_p), ("spot", ctypes.c_void_p), ("n_rows", ctypes.c_int32),
@@ -209,7 +216,7 @@ ARG_GROUPS = {
     "gl": [ctypes.POINTER(McpGlide)], "cf": [ctypes.POINTER(McpCashflow)], "rb": [ctypes.POINTER(McpRebalance)],
     "st": [ctypes.POINTER(McpStudentT)], "gv": [ctypes.POINTER(McpGarch)], "jp": [ctypes.POINTER(McpJumps)],
     "rs": [ctypes.POINTER(McpRegimes)], "ft": [ctypes.POINTER(McpFiltered)], "ov": [ctypes.POINTER(McpOverlay)],
-    "bt": [ctypes.POINTER(McpBootstrap)],
+    "bt": [ctypes.POINTER(McpBootstrap)], "pt": [ctypes.POINTER(McpProtect)],
     "mu": [_vp], "chol": [_vp], "W": [_vp], "mu*": [_f32p], "chol*": [_f32p], "W*": [_f32p],
     "walk": [_u64, _u64, _u64],                           # seed, path_begin, n_paths
     "hz_in": [_int, _vp, _int, _vp],                      # n_horizons, horizons, n_levels, levels
@@ -241,6 +248,18 @@ SIMULATE_ENTRIES = {
 }
 SIMULATE_ENTRIES = {name: tuple(groups.split()) for name, groups in SIMULATE_ENTRIES.items()}
 SIGNATURES.update((name, (_int, [t for g in groups for t in ARG_GROUPS[g]])) for name, groups in SIMULATE_ENTRIES.items())
+
+# The entry points of the extension headers (include/mcport_protect.h), bound after SIGNATURES: SIGNATURES and SIMULATE_ENTRIES are
+# include/mcport.h's alone.  EXTENSION_ENTRIES: the mcp_simulate* among them by argument groups, as SIMULATE_ENTRIES.
+EXTENSION_ENTRIES = {
+    "mcp_simulate_protected": "ctx prm pt gv st jp mu chol W walk hz_in out dd counts hz_out hz_counts",
+}
+EXTENSION_ENTRIES = {name: tuple(groups.split()) for name, groups in EXTENSION_ENTRIES.items()}
+EXTENSION_SIGNATURES = {
+    "mcp_protect_pivots": (_int, [_PP, ctypes.POINTER(McpProtect), _vp, _vp, _int, _vp, _vp, _vp]),
+    "mcp_protect_floor": (_int, [ctypes.c_double, ctypes.c_double, _int, _vp]),
+}
+EXTENSION_SIGNATURES.update((name, (_int, [t for g in groups for t in ARG_GROUPS[g]])) for name, groups in EXTENSION_ENTRIES.items())
 
 _LIB = None
 
@@ -304,6 +323,10 @@ def lib() -> ctypes.CDLL:
         L = ctypes.CDLL(LIB_PATH)
         for name, (res, args) in SIGNATURES.items():
             fn = getattr(L, name)          # AttributeError if the ABI lost a symbol
+            fn.restype = res
+            fn.argtypes = args
+        for name, (res, args) in EXTENSION_SIGNATURES.items():
+            fn = getattr(L, name)          # additive entry points, detected by symbol: a library without them is too old
             fn.restype = res
             fn.argtypes = args
         got = L.mcp_abi_version()
@@ -505,6 +528,37 @@ def glide_pivots(prm: McpParams, breaks, targets, W: np.ndarray, flows=None, mu:
     hout = np.zeros((hz.size, W.shape[0]), np.float64) if hz is not None else None
     check(lib().mcp_glide_pivots(ctypes.byref(prm), ctypes.byref(gl), ref(cf), ptr(mu_p), ref(bt), ptr(W),
                                  0 if hz is None else hz.size, ptr(hz), ptr(out), ptr(hout)))
+    return out, hout
+
+
+def make_protect(floor: np.ndarray, multiplier: float, rate: float = 0.0, cap: float = 1.0, ratchet: float = 0.0, target=None) -> McpProtect:
+    """mcp_protect over a C-contiguous binary32 [n_steps + 1] floor schedule (the caller keeps it alive for the call); the target,
+    when given, lives in a one-element array kept on the struct."""
+    if floor.dtype != np.float32 or floor.ndim != 1 or not floor.flags.c_contiguous:
+        raise ValueError("the protect floor must be a C-contiguous float32 [n_steps + 1] array")
+    tg = np.array([float(target)], np.float64) if target is not None else None
+    pt = McpProtect(ptr(floor), float(multiplier), float(cap), float(rate), float(ratchet), ptr(tg), 0)
+    pt._keep = (floor, tg)
+    return pt
+
+
+def protect_floor(floor0: float, rate: float, n_steps: int) -> np.ndarray:
+    """binary32 [n_steps + 1]: S_0 = fl32(floor0), S_{t+1} = fma(S_t, fl32(rate), S_t) (include/mcport_protect.h, mcp_protect_floor)."""
+    out = np.zeros(int(n_steps) + 1 if int(n_steps) >= 0 else 0, np.float32)
+    check(lib().mcp_protect_floor(float(floor0), float(rate), int(n_steps), ptr(out)))
+    return out
+
+
+def protect_pivots(prm: McpParams, protect: McpProtect, mu: np.ndarray, W: np.ndarray, horizons=None):
+    """([K] pivots at n_steps, [H, K] at the horizons or None): the shifts of the moments of protected paths (SPEC.md 5.15;
+    include/mcport_protect.h, mcp_protect_pivots), pure host arithmetic."""
+    W = np.ascontiguousarray(W, np.float32)
+    mu32 = np.ascontiguousarray(mu, np.float32)
+    hz = np.ascontiguousarray(horizons, np.int32) if horizons is not None and len(horizons) else None
+    out = np.zeros(W.shape[0], np.float64)
+    hout = np.zeros((hz.size, W.shape[0]), np.float64) if hz is not None else None
+    check(lib().mcp_protect_pivots(ctypes.byref(prm), ctypes.byref(protect), ptr(mu32), ptr(W), 0 if hz is None else hz.size, ptr(hz),
+                                   ptr(out), ptr(hout)))
     return out, hout
 
 

@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "../../include/mcport.h"
+#include "../../include/mcport_protect.h"
 #include "mcp_device.h"
 #include "mcp_paths.h"
 #include "mcp_stats_kernels.h"
@@ -435,6 +436,49 @@ void glide_pack(int N, int K, int k0, int kt, const mcp_glide* gl, float* out) {
       memcpy(out + (size_t)g * blk + (size_t)k * n4, gl->targets + ((size_t)g * K + (size_t)(k0 + k)) * N, (size_t)N * sizeof(float));
 }
 
+// SPEC.md 4.15: the binary32 constants of a protection request
+struct ProtectConsts { float m, b, rf, theta; };
+ProtectConsts protect_consts(const mcp_protect* pt) {
+  return ProtectConsts{(float)pt->multiplier, (float)pt->cap, (float)pt->rate, (float)pt->ratchet};
+}
+// SPEC.md 4.15: a finite floor >= +0 at every step 0 .. n_steps; multiplier >= 0, cap > 0, rate > -1, ratchet in [0, 1), each finite
+// before and after rounding to binary32 and inside its range after it; a finite target; reserved == 0
+int check_protect(const mcp_params* prm, const mcp_protect* pt) {
+  if (!pt) return fail(MCP_E_ARG, "protect is NULL");
+  if (pt->reserved != 0) return fail(MCP_E_ARG, "protect reserved=%d must be 0", pt->reserved);
+  if (!pt->floor) return fail(MCP_E_ARG, "protect floor is NULL");
+  const double v[4] = {pt->multiplier, pt->cap, pt->rate, pt->ratchet};
+  for (int i = 0; i < 4; i++)
+    if (!std::isfinite(v[i]) || !std::isfinite((float)v[i]))
+      return fail(MCP_E_ARG, "protect multiplier=%g, cap=%g, rate=%g, ratchet=%g must be finite, also in binary32", v[0], v[1], v[2], v[3]);
+  const ProtectConsts c = protect_consts(pt);
+  if (!(pt->multiplier >= 0.0)) return fail(MCP_E_ARG, "protect multiplier=%g must be >= 0", pt->multiplier);
+  if (!(pt->cap > 0.0) || !(c.b > 0.0f)) return fail(MCP_E_ARG, "protect cap=%g must be > 0 in binary32", pt->cap);
+  if (!(pt->rate > -1.0) || !(c.rf > -1.0f)) return fail(MCP_E_ARG, "protect rate=%g must be > -1 in binary32", pt->rate);
+  if (!(pt->ratchet >= 0.0 && pt->ratchet < 1.0) || !(c.theta < 1.0f))
+    return fail(MCP_E_ARG, "protect ratchet=%g outside [0, 1) in binary32", pt->ratchet);
+  if (pt->target && (!std::isfinite(*pt->target) || !std::isfinite((float)*pt->target)))
+    return fail(MCP_E_ARG, "protect target=%g must be finite, also in binary32", *pt->target);
+  for (int t = 0; t <= prm->n_steps; t++)
+    if (!std::isfinite(pt->floor[t]) || !(pt->floor[t] >= 0.0f))
+      return fail(MCP_E_ARG, "protect floor, step %d = %g must be finite and >= 0", t, (double)pt->floor[t]);
+  if (!((float)prm->v0 > 0.0f)) return fail(MCP_E_ARG, "v0=%g rounds to zero in binary32", prm->v0);
+  return MCP_OK;
+}
+// What follows the packed block (and the jump loadings) of a protected launch: the schedule S_0 .. S_T, then per stored row -- the kt
+// terminal rows, then the H*kt horizon rows -- the two thresholds {S_h, target or -inf} of the counts (SPEC.md 5.15)
+inline size_t protect_len(int T, int kt, int H) { return (size_t)T + 1 + 2 * (size_t)kt * (size_t)(1 + H); }
+void protect_pack(int T, int kt, int H, const int32_t* steps, const mcp_protect* pt, float* out) {
+  memcpy(out, pt->floor, ((size_t)T + 1) * sizeof(float));
+  float* thr = out + T + 1;
+  const float tg = pt->target ? (float)*pt->target : -HUGE_VALF;
+  for (int h = -1; h < H; h++)
+    for (int k = 0; k < kt; k++) {
+      *thr++ = pt->floor[h < 0 ? T : steps[h]];
+      *thr++ = tg;
+    }
+}
+
 // SPEC.md 4.8: row_begin ascending from 0 to n_rows, at most MCP_MAX_OVERLAY_ROWS rows per asset, kinds 0..2, finite numbers, a
 // positive spot on every asset that owns rows, reserved == 0
 int check_overlay(const mcp_params* prm, const mcp_overlay* ov) {
@@ -542,6 +586,8 @@ struct Request {
   const mcp_cashflow* cf = nullptr;
   bool glide = false;                   // SPEC.md 4.14: the weight schedule `gl`, always with `cf` (mcp_simulate_glide)
   const mcp_glide* gl = nullptr;
+  bool protect = false;                 // SPEC.md 4.15: the floor rule `pi` (mcp_simulate_protected)
+  const mcp_protect* pi = nullptr;
   bool overlay = false;                 // SPEC.md 4.8: the option rows `ov`
   const mcp_overlay* ov = nullptr;
   bool garch = false;                   // SPEC.md 4.9: the variance recurrence `gv` (SRC_GAUSS or SRC_T)
@@ -563,7 +609,7 @@ struct Request {
   float* hz_out = nullptr;              // [H*K*n], row h*K + k
   mcp_stats* hz_stats_out = nullptr;    // [H*K]
   double* bands_out = nullptr;          // [H*K*L]
-  uint64_t* counts_out = nullptr;       // cash flows: [K][2] {n_ruined, n_short} (SPEC.md 5.6)
+  uint64_t* counts_out = nullptr;       // cash flows: [K][2] {n_ruined, n_short} (SPEC.md 5.6); protection: {n_gap, n_short} (5.15)
   uint64_t* hz_counts_out = nullptr;    // [H*K][2]
   bool attr = false;                    // SPEC.md 4.10 / 5.9: the second walk that attributes the risk to the assets
   float* contrib_out = nullptr;         // NULL or host [K][N][n]
@@ -616,6 +662,7 @@ struct Launch {
   uint64_t hz_stride = 0;
   const float* d_rows = nullptr;        // bootstrap: [R][N4], zero-padded
   const float* d_flows = nullptr;       // cash flows: [n_steps]
+  const float* d_floor = nullptr;       // protection: [n_steps + 1] the floor schedule
   const float* d_targets = nullptr;     // glide path: [n_breaks][glide_rows(K)][N4] target blocks (glide_pack)
   const char* d_overlay = nullptr;      // overlay: [rows][row_begin N4 + 1][spot N4] (overlay_pack)
   const float* d_loading = nullptr;     // jumps: [N4] loadings, zero-padded
@@ -658,6 +705,21 @@ int check_request(const mcp_params* prm, const Request& rq, uint64_t n_paths, co
       return fail(MCP_E_UNSUPPORTED, "a glide path is not combined with the drawdown, rebalancing, the overlay, GARCH, jumps, regimes, "
                                      "filtered rows, the attribution or antithetic pairs");
     if (ln) return fail(MCP_E_UNSUPPORTED, "glide paths are not wired into mcp_launch_paths*");
+  }
+  if (rq.protect) {                                            // SPEC.md 4.15: the rules, then what the protection is not combined with
+    if ((rc = check_protect(prm, rq.pi))) return rc;
+    if (!rq.counts_out) return fail(MCP_E_ARG, "counts_out is NULL");
+    if ((rq.hz_counts_out == nullptr) != !rq.hz) return fail(MCP_E_ARG, "hz_counts_out must be NULL exactly when n_horizons == 0");
+    if (rq.src == SRC_T && (rc = check_student_t(prm, rq.st))) return rc;
+    if (rq.garch && (rc = check_garch(prm, rq.gv))) return rc;
+    if (rq.jumps && (rc = check_jumps(prm->n_assets, rq.jp))) return rc;
+    if (prm->compounding != MCP_COMPOUND_SIMPLE) return fail(MCP_E_UNSUPPORTED, "protected paths compound simply (no log compounding)");
+    if (prm->flags & (MCP_FLAG_FOLD | MCP_FLAG_NATIVE_MATH))
+      return fail(MCP_E_UNSUPPORTED, "protected paths run on the unfolded recurrence and the spec's normals (no MCP_FLAG_FOLD / MCP_FLAG_NATIVE_MATH)");
+    if (rq.src == SRC_BOOT || rq.src == SRC_FHS || rq.regimes || rq.rebalanced || rq.cash || rq.glide || rq.overlay || rq.attr || rq.anti)
+      return fail(MCP_E_UNSUPPORTED, "floor protection is not combined with bootstrap or filtered rows, regimes, rebalancing, cash flows, "
+                                     "glide paths, the overlay, the attribution or antithetic pairs");
+    if (ln) return fail(MCP_E_UNSUPPORTED, "floor protection is not wired into mcp_launch_paths*");
   }
   if (rq.overlay && (rc = check_overlay(prm, rq.ov))) return rc;
   if (rq.garch && (rc = check_garch(prm, rq.gv))) return rc;
@@ -1285,6 +1347,17 @@ static mcp::GlideArgs glide_block(const Request& rq, const Launch& ln, int n_ass
   for (int g = 0; g < MCP_MAX_GLIDE; g++) gp.breaks[g] = g < gp.n_breaks ? rq.gl->breaks[g] : 0;
   return gp;
 }
+// SPEC.md 4.15: the binary32 constants; the schedule sits behind the launch's packed block
+static mcp::ProtectArgs protect_block(const Request& rq, const Launch& ln) {
+  const ProtectConsts c = protect_consts(rq.pi);
+  mcp::ProtectArgs pi;
+  pi.floor = ln.d_floor;
+  pi.m = c.m;
+  pi.b = c.b;
+  pi.rf = c.rf;
+  pi.theta = c.theta;
+  return pi;
+}
 static mcp::OverlayArgs overlay_block(const Request& rq, const Launch& ln, int n_assets) {
   mcp::OverlayArgs ov;
   const size_t row_bytes = (size_t)rq.ov->n_rows * sizeof(mcp_overlay_row);
@@ -1315,7 +1388,8 @@ static mcp::AttrArgs attr_block(const Launch& ln, int n_assets) {
 static int launch_paths_impl(const mcp_params* prm, const Request& rq, const Launch& ln) {
   const int N = prm->n_assets, nb = (N + 3) / 4;
   const int K = prm->n_portfolios;
-  const bool plain = rq.src == SRC_GAUSS && !rq.dd && !rq.hz && !rq.rebalanced && !rq.cash && !rq.overlay && !rq.garch && !rq.jumps && !rq.regimes;
+  const bool plain = rq.src == SRC_GAUSS && !rq.dd && !rq.hz && !rq.rebalanced && !rq.cash && !rq.overlay && !rq.garch && !rq.jumps && !rq.regimes &&
+                     !rq.protect;
   mcp::PathLaunchArgs s = {};             // every block the request does not carry stays empty
   mcp::PathArgs& a = s.hz;
   const float4* tables = nullptr;
@@ -1388,6 +1462,7 @@ static int launch_paths_impl(const mcp_params* prm, const Request& rq, const Lau
   if (rq.src == SRC_FHS) s.fh = filt_block(rq, ln, N);
   if (rq.jumps) s.jp = jump_block(rq, ln);
   if (rq.regimes) s.rs = regime_block(rq, ln);
+  if (rq.protect) s.pi = protect_block(rq, ln);
   mcp::PathKernel k = {};
   k.logc = prm->compounding == MCP_COMPOUND_LOG;
   k.fh = rq.src == SRC_FHS;
@@ -1411,6 +1486,17 @@ static int launch_paths_impl(const mcp_params* prm, const Request& rq, const Lau
     k.jp = rq.jumps;
     k.rs = rq.regimes;
     k.gp = rq.glide;
+    if (rq.protect) {
+      // SPEC.md 4.15: one segmented kernel serves terminal-only and horizon calls.  Gaussian, Student-t and GARCH requests share the
+      // GARCH walk, as the attribution does: without GARCH on alpha = beta = 0, h0 = 1
+      static const mcp_garch none = {0.0, 0.0, 1.0, 0};
+      k.pi = true;
+      k.family = rq.dd ? mcp::FAM_DD : mcp::FAM_HZ;
+      if (!rq.jumps) {
+        k.stt = k.gv = true;
+        if (!rq.garch) s.gv = garch_block(&none, N);
+      }
+    }
     k.kt8 = K > 1;
     k.native = (prm->flags & MCP_FLAG_NATIVE_MATH) != 0;
     k.fold = (prm->flags & MCP_FLAG_FOLD) != 0;
@@ -1902,6 +1988,30 @@ int run_select(mcp_ctx* c, const std::vector<mcp_params>& tp, const std::vector<
   return MCP_OK;
 }
 
+// SPEC.md 5.15: c_k(h) = (S_h + (v0 - S_0) g_k^h) / v0 - 1, g_k = 1 + rf + m (mu_k - rf), mu_k = sum_i W_ki mu_i (i ascending), binary64
+// from the binary32 inputs; where g_k <= 0 or the result is not finite, the pivot of the plain call at h steps (mcp_pivots).  K
+// portfolios W[0, K); h = T into out_T[k], the H horizons into out_hz[h*K + k].
+void protect_pivots(const mcp_params& prm, const mcp_protect* pt, const float* mu, const float* W, int K, int H, const int32_t* steps,
+                    double* out_T, double* out_hz) {
+  const ProtectConsts pc = protect_consts(pt);
+  const double v0 = (double)(float)prm.v0, rf = (double)pc.rf, m = (double)pc.m, s0 = (double)pt->floor[0];
+  const int N = prm.n_assets;
+  for (int k = 0; k < K; k++) {
+    double mk = 0.0;
+    for (int i = 0; i < N; i++) mk += (double)W[(size_t)k * N + i] * (double)mu[i];
+    const double g = 1.0 + rf + m * (mk - rf);
+    for (int h = -1; h < H; h++) {
+      const int st = h < 0 ? prm.n_steps : steps[h];
+      double c = (((double)pt->floor[st] + (v0 - s0) * std::pow(g, (double)st)) / v0) - 1.0;
+      if (!(g > 0.0) || !std::isfinite(c)) {
+        c = mk > -1.0 ? std::expm1((double)st * std::log1p(mk)) : 0.0;
+        if (!std::isfinite(c)) c = 0.0;
+      }
+      (h < 0 ? out_T[k] : out_hz[(size_t)h * K + k]) = c;
+    }
+  }
+}
+
 // The [kt] pivots of the portfolios W[0, kt) of a tile (tp.n_portfolios = kt) at T steps (SPEC.md 5): of rebalanced paths from
 // the draws' per-asset means rmu (5.4), of bootstrap paths from the row moments bm, bs2 (5.3), else mcp_pivots.
 int tile_pivots(const mcp_params& tp, const Request& rq, int T, const float* W, const double* rmu, const double* bm, const double* bs2,
@@ -1947,7 +2057,8 @@ int run_tile(mcp_ctx* c, const mcp_params* prm, const Request& rq, uint64_t seed
     // jumps: the loadings behind the packed block; regimes: [mu1][L1 row pairs] there
     // glide path: the target blocks of the tile's portfolios there
     const size_t plen = mcp_packed_len(N, j.kt) + (rq.jumps ? (size_t)n4_of(N) : 0) + (rq.regimes ? regime_block_len(N) : 0) +
-                        (rq.glide ? glide_len(N, j.kt, rq.gl) : 0), pn = j.pn ? j.pn : 1;
+                        (rq.glide ? glide_len(N, j.kt, rq.gl) : 0) + (rq.protect ? protect_len(prm->n_steps, j.kt, rq.hz ? rq.H : 0) : 0),
+                 pn = j.pn ? j.pn : 1;   // protection: the floor schedule and the counts' thresholds there (protect_pack)
     const int rows = rq.hz ? rq.H * j.kt : j.kt;  // horizon calls: the work buffers also serve the H*kt rows of the horizon selects
     for (int w = 0; w < MCP_WS_COUNT; w++) {      // only the histogram and the select state must start zeroed
       const size_t need = std::max(mcp_ws_bytes(w, j.kt, pn), mcp_ws_bytes(w, rows, pn));
@@ -1962,7 +2073,7 @@ int run_tile(mcp_ctx* c, const mcp_params* prm, const Request& rq, uint64_t seed
     if (rq.hz && ((rc = grow(sh.hz.values, (size_t)rows * pn)) || (rc = grow(sh.hz.pivot, (size_t)rows)) ||
                   (rc = grow(sh.hz.h_pivot, (size_t)rows)) || (rc = grow_mapped(sh.hz.stats, (size_t)(1 + rq.L) * rows))))
       return rc;
-    if (rq.cash && ((rc = grow(sh.cf.counts, 2 * (size_t)(j.kt + rows))) || (rc = grow(sh.cf.h_counts, 2 * (size_t)(j.kt + rows))))) return rc;
+    if ((rq.cash || rq.protect) && ((rc = grow(sh.cf.counts, 2 * (size_t)(j.kt + rows))) || (rc = grow(sh.cf.h_counts, 2 * (size_t)(j.kt + rows))))) return rc;
     if (rq.anti && ((rc = grow(sh.pr.partials, (size_t)j.kt * (size_t)mcp::path_grid(pn / 2))) || (rc = grow(sh.pr.cross, (size_t)j.kt)) ||
                     (rc = grow(sh.pr.h_cross, (size_t)j.kt))))
       return rc;
@@ -2000,7 +2111,8 @@ int run_tile(mcp_ctx* c, const mcp_params* prm, const Request& rq, uint64_t seed
     Shard& sh = c->sh[s];
     HIP_TRY(hipSetDevice(sh.device));
     const size_t plen = mcp_packed_len(N, j.kt);
-    const size_t n_tail = rq.glide ? glide_len(N, j.kt, rq.gl) : n_load;   // what follows the packed block: loadings, regime 1 or targets
+    const size_t n_prot = rq.protect ? protect_len(prm->n_steps, j.kt, rq.hz ? rq.H : 0) : 0;
+    const size_t n_tail = rq.glide ? glide_len(N, j.kt, rq.gl) : n_load + n_prot;   // what follows the packed block: loadings, regime 1 or targets; then the floor
     const float* src = sh.h_packed.p;
     const double* psrc = sh.h_pivot.p;
     const double* hpsrc = sh.hz.h_pivot.p;
@@ -2018,7 +2130,10 @@ int run_tile(mcp_ctx* c, const mcp_params* prm, const Request& rq, uint64_t seed
         bs2.resize((size_t)j.kt);
         boot_moments(N, rq.boot, Wt, j.kt, bm.data(), bs2.data());
       }
-      if (rq.glide) {                                        // SPEC.md 4.14 / 5.14: the tile's target blocks; one walk gives every pivot
+      if (rq.protect) {                                      // SPEC.md 4.15 / 5.15: the schedule and thresholds; every pivot in closed form
+        protect_pack(prm->n_steps, j.kt, rq.hz ? rq.H : 0, rq.steps, rq.pi, sh.h_packed.p + plen + n_load);
+        protect_pivots(*prm, rq.pi, rq.mu, Wt, j.kt, rq.hz ? rq.H : 0, rq.steps, sh.h_pivot.p, sh.hz.h_pivot.p);
+      } else if (rq.glide) {                                 // SPEC.md 4.14 / 5.14: the tile's target blocks; one walk gives every pivot
         glide_pack(N, prm->n_portfolios, j.k0, j.kt, rq.gl, sh.h_packed.p + plen);
         cm.resize((size_t)(rq.gl->n_breaks + 1) * j.kt);
         glide_means(N, prm->n_portfolios, j.k0, j.kt, rq.mu, boot ? rq.boot : nullptr, rq.W, rq.gl, cm.data());
@@ -2035,7 +2150,7 @@ int run_tile(mcp_ctx* c, const mcp_params* prm, const Request& rq, uint64_t seed
         regime_pivots(N, j.kt, prm->n_steps, rq.mu, rq.rs->mu1, regime_consts(rq.rs), Wt, rq.hz ? rq.H : 0, rq.steps, sh.h_pivot.p,
                       sh.hz.h_pivot.p);
       } else if ((rc = tile_pivots(tp[s], rq, prm->n_steps, Wt, rmu.data(), bm.data(), bs2.data(), sh.h_pivot.p))) return rc;
-      for (int h = 0; rq.hz && !rq.cash && !ov_walk && !rq.regimes && h < rq.H; h++)                // SPEC.md 5.2 / 5.3: row h*kt + k is pivoted with n_steps = h
+      for (int h = 0; rq.hz && !rq.cash && !ov_walk && !rq.regimes && !rq.protect && h < rq.H; h++)                // SPEC.md 5.2 / 5.3: row h*kt + k is pivoted with n_steps = h
         if ((rc = tile_pivots(tp[s], rq, rq.steps[h], Wt, rmu.data(), bm.data(), bs2.data(), sh.hz.h_pivot.p + (size_t)h * j.kt)))
           return rc;
       if (exchange) { shared_packed = sh.h_packed.p; shared_pivot = sh.h_pivot.p; shared_hz_pivot = sh.hz.h_pivot.p; }
@@ -2056,6 +2171,7 @@ int run_tile(mcp_ctx* c, const mcp_params* prm, const Request& rq, uint64_t seed
       ln.d_loading = sh.packed.p + plen;
       ln.d_block1 = sh.packed.p + plen;
       ln.d_targets = sh.packed.p + plen;
+      ln.d_floor = sh.packed.p + plen + n_load;
       ln.d_cross = sh.pr.partials.p;
       if ((rc = launch_paths_impl(&tp[s], rq, ln))) return rc;
       if (rq.anti) {                                         // SPEC.md 5.10: the workgroups' cross partials in block order
@@ -2070,6 +2186,15 @@ int run_tile(mcp_ctx* c, const mcp_params* prm, const Request& rq, uint64_t seed
         HIP_TRY(mcp::launch_count_rows(sh.terminal.p, j.pn, j.pn, j.kt, tg, g32, sh.cf.counts.p, sh.stream));
         if (rows_hz)
           HIP_TRY(mcp::launch_count_rows(sh.hz.values.p, j.pn, j.pn, (int)rows_hz, tg, g32, sh.cf.counts.p + 2 * (size_t)j.kt, sh.stream));
+      }
+      if (rq.protect) {                                      // SPEC.md 5.15: the paths below the floor and below the target, every stored row
+        const size_t rows_hz = rq.hz ? (size_t)rq.H * j.kt : 0;
+        const float* thr = ln.d_floor + prm->n_steps + 1;
+        HIP_TRY(mcp::launch_zero(sh.cf.counts.p, 2 * ((size_t)j.kt + rows_hz) * sizeof(unsigned long long), sh.stream));
+        HIP_TRY(mcp::launch_count_below(sh.terminal.p, j.pn, j.pn, j.kt, thr, sh.cf.counts.p, sh.stream));
+        if (rows_hz)
+          HIP_TRY(mcp::launch_count_below(sh.hz.values.p, j.pn, j.pn, (int)rows_hz, thr + 2 * (size_t)j.kt, sh.cf.counts.p + 2 * (size_t)j.kt,
+                                          sh.stream));
       }
     } else {
       // a shard without paths (fewer paths than shards): empty moment partials, nothing in the histogram
@@ -2130,13 +2255,13 @@ int run_tile(mcp_ctx* c, const mcp_params* prm, const Request& rq, uint64_t seed
     if (rq.hz && rq.hz_out)
       for (int h = 0; h < rq.H; h++)
         HIP_TRY(copy_out(rq.hz_out + (size_t)h * prm->n_portfolios * n_total, sh.hz.values.p + (size_t)h * j.kt * j.pn));
-    if (rq.cash)
+    if (rq.cash || rq.protect)
       HIP_TRY(hipMemcpyAsync(sh.cf.h_counts.p, sh.cf.counts.p, 2 * (size_t)((rq.hz ? 1 + rq.H : 1) * j.kt) * sizeof(unsigned long long),
                              hipMemcpyDeviceToHost, sh.stream));
   }
   for (size_t s = 0; s < S; s++)
     if (jobs[s].active) { HIP_TRY(hipSetDevice(c->sh[s].device)); HIP_TRY(hipStreamSynchronize(c->sh[s].stream)); }
-  for (size_t s = 0; rq.cash && s < S; s++) {              // the counts of every shard that walked paths add up (zeroed per call)
+  for (size_t s = 0; (rq.cash || rq.protect) && s < S; s++) {   // the counts of every shard that walked paths add up (zeroed per call)
     const Job& j = jobs[s];
     if (!j.active || !j.pn) continue;
     const unsigned long long* hc = c->sh[s].cf.h_counts.p;
@@ -2300,6 +2425,10 @@ int simulate_impl(mcp_ctx* c, const mcp_params* prm, const Request& rq, uint64_t
       const hipError_t e = hipMemcpyAsync(sh.cf.flows.p, c->h_flows, bytes, hipMemcpyHostToDevice, sh.stream);
       if (e != hipSuccess) rc = fail(MCP_E_HIP, "cash-flow schedule upload: %s", hipGetErrorString(e));
     }
+  }
+  if (rc == MCP_OK && rq.protect) {                          // SPEC.md 5.15: the counts of the call start at zero, every tile and shard adds its own
+    memset(rq.counts_out, 0, 2 * (size_t)K * sizeof(uint64_t));
+    if (rq.hz) memset(rq.hz_counts_out, 0, 2 * (size_t)rq.H * K * sizeof(uint64_t));
   }
   if (rc == MCP_OK && rq.overlay) {
     // SPEC.md 4.8: the table into one pinned staging copy and from there once into the overlay buffer of every shard (the tiles
@@ -2680,6 +2809,58 @@ int mcp_glide_pivots(const mcp_params* prm, const mcp_glide* gl, const mcp_cashf
   glide_means(prm->n_assets, K, 0, K, mu, boot, W, gl, m.data());
   glide_pivots(K, prm->n_steps, gl->n_breaks, gl->breaks, m.data(), cf ? cf->flows : nullptr, (double)(float)prm->v0, n_horizons, horizons,
                pivots_out, hz_pivots_out);
+  return MCP_OK;
+}
+
+int mcp_simulate_protected(mcp_ctx* c, const mcp_params* prm, const mcp_protect* pt, const mcp_garch* gv, const mcp_student_t* st,
+                           const mcp_jumps* jp, const float* mu, const float* chol, const float* W, uint64_t seed, uint64_t path_begin,
+                           uint64_t n_paths, int n_horizons, const int32_t* horizons, int n_levels, const double* levels, float* terminal_out,
+                           mcp_stats* stats_out, float* mdd_out, mcp_stats* dd_stats_out, uint64_t* counts_out, float* horizon_out,
+                           mcp_stats* hz_stats_out, double* bands_out, uint64_t* hz_counts_out) {
+  Request rq = host_request(st ? SRC_T : SRC_GAUSS, mu, chol, W, terminal_out, stats_out);
+  rq.st = st;
+  rq.garch = gv != nullptr;
+  rq.gv = gv;
+  rq.jumps = jp != nullptr;
+  rq.jp = jp;
+  rq.protect = true;
+  rq.pi = pt;
+  rq.dd = dd_stats_out != nullptr;
+  rq.mdd_out = mdd_out;
+  rq.dd_stats_out = dd_stats_out;
+  rq.counts_out = counts_out;
+  rq.hz_counts_out = hz_counts_out;
+  ask_horizons(rq, n_horizons != 0, n_horizons, horizons, n_levels, levels, horizon_out, hz_stats_out, bands_out);
+  return simulate_checked(c, prm, rq, seed, path_begin, n_paths);
+}
+
+int mcp_protect_pivots(const mcp_params* prm, const mcp_protect* pt, const float* mu, const float* W, int n_horizons,
+                       const int32_t* horizons, double* pivots_out, double* hz_pivots_out) {
+  if (int rc = check_params(prm)) return rc;
+  if (int rc = check_protect(prm, pt)) return rc;
+  if (!mu || !W || !pivots_out) return fail(MCP_E_ARG, "NULL pointer");
+  if (prm->compounding != MCP_COMPOUND_SIMPLE) return fail(MCP_E_UNSUPPORTED, "protected paths compound simply (no log compounding)");
+  if (n_horizons != 0) {
+    if (int rc = check_horizons(prm->n_steps, n_horizons, horizons)) return rc;
+    if (!hz_pivots_out) return fail(MCP_E_ARG, "hz_pivots_out is NULL");
+  }
+  protect_pivots(*prm, pt, mu, W, prm->n_portfolios, n_horizons, horizons, pivots_out, hz_pivots_out);
+  return MCP_OK;
+}
+
+int mcp_protect_floor(double floor0, double rate, int n_steps, float* out) {
+  if (!std::isfinite(floor0) || !std::isfinite(rate) || !std::isfinite((float)floor0) || !std::isfinite((float)rate))
+    return fail(MCP_E_ARG, "floor0=%g and rate=%g must be finite, also in binary32", floor0, rate);
+  if (!(floor0 >= 0.0)) return fail(MCP_E_ARG, "floor0=%g must be >= 0", floor0);
+  if (!(rate > -1.0) || !((float)rate > -1.0f)) return fail(MCP_E_ARG, "rate=%g must be > -1 in binary32", rate);
+  if (n_steps < 1) return fail(MCP_E_ARG, "n_steps=%d must be >= 1", n_steps);
+  if (!out) return fail(MCP_E_ARG, "out is NULL");
+  const float r = (float)rate;
+  out[0] = (float)floor0;
+  for (int t = 0; t < n_steps; t++) {
+    out[t + 1] = std::fmaf(out[t], r, out[t]);
+    if (!std::isfinite(out[t + 1])) return fail(MCP_E_ARG, "the floor schedule overflows binary32 at step %d", t + 1);
+  }
   return MCP_OK;
 }
 

@@ -53,6 +53,11 @@
 #define MCP_MIN_WAVES_AT 5  // the attribution kernel (N <= 16, one portfolio) holds the N4 contributions A on top of the GARCH kernel's state, as
                             // the rebalancing kernel holds B: at 5 waves it gets 96 VGPRs, no scratch (profiles/attribution_isa.txt)
 #endif
+#ifndef MCP_MIN_WAVES_PI
+#define MCP_MIN_WAVES_PI 5  // the floor-protection kernel on the jump walk (N <= 16, one portfolio) carries the peak M on top of the jump kernel's
+                            // state: at 6 waves (80 VGPRs) the N = 16 kernels reloaded one spilled pair inside the step loop; at 5 none does.  On
+                            // the GARCH walk it fits in 80 and keeps MCP_MIN_WAVES (profiles/protect_isa.txt)
+#endif
 #ifndef MCP_MIN_WAVES_ANTI
 #define MCP_MIN_WAVES_ANTI 5 // the antithetic kernels (N <= 16, one portfolio) carry the second member's V, row-pair accumulator and rho (and
                             // peak and drawdown) next to the first's: see profiles/antithetic_isa.txt
@@ -94,6 +99,7 @@ __device__ __forceinline__ const __attribute__((address_space(4))) A* kernarg() 
 MCP_HAS_MEMBER(hz) MCP_HAS_MEMBER(mdd) MCP_HAS_MEMBER(bt) MCP_HAS_MEMBER(st) MCP_HAS_MEMBER(gv) MCP_HAS_MEMBER(cf)
 MCP_HAS_MEMBER(ov) MCP_HAS_MEMBER(at) MCP_HAS_MEMBER(period) MCP_HAS_MEMBER(pr)
 MCP_HAS_MEMBER(fh) MCP_HAS_MEMBER(p_hi) MCP_HAS_MEMBER(jp) MCP_HAS_MEMBER(rs) MCP_HAS_MEMBER(gp)
+MCP_HAS_MEMBER(pi)
 #undef MCP_HAS_MEMBER
 
 struct PathArgs {
@@ -344,6 +350,31 @@ struct GlideArgs {
 // Arguments of mc_paths_glide_kernel: those of mc_paths_cf_kernel and the glide block, read where it is needed (kernarg).
 struct PathArgsGP : PathArgsCF { GlideArgs gp; };
 
+// Floor protection (SPEC.md 4.15): CPPI with an exposure cap and a drawdown ratchet.  Per path and portfolio the walk carries V and the
+// peak M (both from v0); step t holds E = fmaxf(fminf(fl32(m (V - F)), fl32(b V)), +0) in the risky portfolio, F = fmaxf(S_t,
+// fl32(theta M)), and V - E at the riskless rate: V' = fma(E, rho, fma(V - E, rf, V)).  `floor` is the schedule S_0 .. S_T behind the
+// launch's packed block; S_t is wave-uniform and read inside the step, as the cash flow is.
+struct ProtectArgs {
+  const float* __restrict__ floor;    // [n_steps + 1] device copy
+  float m, b, rf, theta;              // binary32: multiplier >= 0, cap > 0, riskless rate > -1, ratchet in [0, 1)
+};
+// Arguments of mc_paths_pi_kernel: the horizons of PathArgsHZ (n_horizons = 0: none), the drawdown output (written only when DD),
+// then the draws' block -- nu and the GARCH constants (the GARCH walk, which also serves Gaussian and Student-t requests), or the
+// jump block -- and the protection rule.
+struct PathArgsPI : PathArgsHZ {
+  float* __restrict__ mdd;
+  uint64_t mdd_stride;
+};
+struct PathArgsPG : PathArgsPI { StudentArgs st; GarchArgs gv; ProtectArgs pi; };
+struct PathArgsPJ : PathArgsPI { JumpArgs jp; ProtectArgs pi; };
+// The protection block of a pi kernel's launch, read where it is used (kernarg).
+typedef const __attribute__((address_space(4))) ProtectArgs* cprotect_p;
+template <class A>
+__device__ __forceinline__ cprotect_p protect_args(const A&) {
+  if constexpr (has_pi<A>::value) return &kernarg<A>()->pi;
+  else return nullptr;
+}
+
 // The option overlay of SPEC.md 4.8: per asset a run of rows (kind, strike, premium, qty) that turns the raw return r_i of a step
 // into the strategy's return r'_i at the asset's price level P_i.  rows, row_begin [N4 + 1] (assets >= N own no rows) and spot [N4]
 // are device copies; bit i of `mask` is set when asset i owns rows.
@@ -406,6 +437,7 @@ struct PathLaunchArgs {
   JumpArgs jp;
   RegimeArgs rs;
   GlideArgs gp;
+  ProtectArgs pi;
 };
 template <class A>
 inline A make_args(const PathLaunchArgs& s) {
@@ -425,6 +457,7 @@ inline A make_args(const PathLaunchArgs& s) {
   if constexpr (has_jp<A>::value) x.jp = s.jp;
   if constexpr (has_rs<A>::value) x.rs = s.rs;
   if constexpr (has_gp<A>::value) x.gp = s.gp;
+  if constexpr (has_pi<A>::value) x.pi = s.pi;
   if constexpr (has_p_hi<A>::value) { x.p_hi = (uint32_t)(s.hz.path_begin >> 32); x.pad = 0u; }
   return x;
 }
@@ -528,24 +561,27 @@ constexpr int PATH_BLOCK = 256;
 // regime under that regime's lanes -- a divergent if / else, skipped where the wave has no lane in the regime -- with that regime's
 // drift and Cholesky factor, the factor still a scalar operand (SPEC.md 4.13).  GP (with CF and HZ): the
 // walk's weight pointer moves to the next target block at the breaks of the glide path, wave-uniform events merged with the horizons
-// as the rebalancing walk merges its dates; the step itself is the cash-flow kernel's (SPEC.md 4.14).  Every kernel
+// as the rebalancing walk merges its dates; the step itself is the cash-flow kernel's (SPEC.md 4.14).  PI (with HZ): the walk also
+// carries the peak M of V, and the update of V holds only the exposure E of the floor rule in the risky portfolio, the rest at the
+// riskless rate (SPEC.md 4.15).  Every kernel
 // below is the body in mcp_paths_body.inc under its own flags F: it names the flags it sets, the rest are PathFlagsOff's.  F is a
 // local class, which may not have static data members, so it sets its flags as enumerators of an `enum : bool`; they hide the
 // defaults' names and read as the same constant expressions.
 struct PathFlagsOff {
   static constexpr bool NATIVE = false, FOLD = false, LOGC = false, DD = false, HZ = false, BOOT = false, BLDS = false, REB = false,
                         STT = false, CF = false, OV = false, GV = false, AT = false, ANTI = false, FH = false, UHI = false, JP = false, RS = false,
-                        GP = false;
+                        GP = false, PI = false;
 };
 
 // __launch_bounds__ 2nd argument of a path kernel: the MCP_MIN_WAVES* above for N <= 16 and one path per lane, by the kind of
 // state the kernel carries; MCP_MIN_WAVES_BIG for 16 < N <= 64 and one portfolio; otherwise unbounded.
-enum BoundsKind { BK_PATHS, BK_REB, BK_CF, BK_OV, BK_AT, BK_ANTI };
+enum BoundsKind { BK_PATHS, BK_REB, BK_CF, BK_OV, BK_AT, BK_ANTI, BK_PI };
 constexpr int min_waves(BoundsKind kind, int NB, int KT, int PPT) {
   if (kind == BK_ANTI) return (NB <= 4 && PPT == 1 && KT == 1) ? MCP_MIN_WAVES_ANTI : 1;
   if (NB <= 4 && PPT == 1 && KT == 1)
-    return kind == BK_REB ? MCP_MIN_WAVES_REB : kind == BK_OV ? MCP_MIN_WAVES_OV : kind == BK_AT ? MCP_MIN_WAVES_AT : MCP_MIN_WAVES;
-  if (NB <= 4 && PPT == 1 && kind != BK_PATHS && kind != BK_AT)
+    return kind == BK_REB ? MCP_MIN_WAVES_REB : kind == BK_OV ? MCP_MIN_WAVES_OV : kind == BK_AT ? MCP_MIN_WAVES_AT
+           : kind == BK_PI ? MCP_MIN_WAVES_PI : MCP_MIN_WAVES;
+  if (NB <= 4 && PPT == 1 && kind != BK_PATHS && kind != BK_AT && kind != BK_PI)
     return kind == BK_REB ? MCP_MIN_WAVES_REB8 : kind == BK_CF ? MCP_MIN_WAVES_CF8 : MCP_MIN_WAVES_OV8;
   return (KT == 1 && PPT == 1) ? MCP_MIN_WAVES_BIG : 1;
 }
@@ -703,6 +739,18 @@ __global__ void MCP_BOUNDS(BK_CF) mc_paths_cf_kernel(const PathArgsCF a) {
 template <int NB, int KT, int PPT, bool BOOT_, bool BLDS_, bool STT_>
 __global__ void MCP_BOUNDS(BK_CF) mc_paths_glide_kernel(const PathArgsGP a) {
   struct F : PathFlagsOff { enum : bool { HZ = true, CF = true, GP = true, BOOT = BOOT_, BLDS = BLDS_, STT = STT_ }; };
+#include "mcp_paths_body.inc"
+}
+
+// The floor-protection kernel (SPEC.md 4.15; simple compounding, unfolded recurrence): the segmented walk of mc_paths_hz_kernel with
+// the CPPI / ratchet rule in the update of V.  H = 0 is one segment, so one kernel serves terminal-only and horizon calls; DD adds
+// the drawdown state of mc_paths_dd_kernel, which sees the protected V.  JP_ = false: the GARCH walk, which serves Gaussian (nu = 0,
+// alpha = beta = 0, h0 = 1) and Student-t requests at run time as mc_paths_attr_kernel does; JP_ = true: the jump walk.  V_T, the
+// horizons, the drawdown and the fused epilogue as in those kernels.  On the GARCH walk it keeps the plain kernel's launch bounds, on
+// the jump walk it takes MCP_MIN_WAVES_PI: so no listing shows scratch in a step loop (profiles/protect_isa.txt).
+template <int NB, int KT, int PPT, bool JP_, bool DD_>
+__global__ void MCP_BOUNDS(JP_ ? BK_PI : BK_PATHS) mc_paths_pi_kernel(const std::conditional_t<JP_, PathArgsPJ, PathArgsPG> a) {
+  struct F : PathFlagsOff { enum : bool { HZ = true, PI = true, DD = DD_, STT = !JP_, GV = !JP_, JP = JP_ }; };
 #include "mcp_paths_body.inc"
 }
 

@@ -5,21 +5,23 @@
 // derived from it) and the kernel argument `a` (PathArgs or a struct that starts with one).
   constexpr bool NATIVE = F::NATIVE, FOLD = F::FOLD, LOGC = F::LOGC, DD = F::DD, HZ = F::HZ, BOOT = F::BOOT, BLDS = F::BLDS, REB = F::REB,
                  STT = F::STT, CF = F::CF, OV = F::OV, GV = F::GV, AT = F::AT, ANTI = F::ANTI, FH = F::FH, UHI = F::UHI, JP = F::JP, RS = F::RS,
-                 GP = F::GP;
-  static_assert(!UHI || (KT == 1 && PPT == 1 && !(NATIVE || FOLD || DD || HZ || BOOT || REB || STT || CF || OV || GV || AT || ANTI || FH || JP || RS)),
+                 GP = F::GP, PI = F::PI;
+  static_assert(!UHI || (KT == 1 && PPT == 1 && !(NATIVE || FOLD || DD || HZ || BOOT || REB || STT || CF || OV || GV || AT || ANTI || FH || JP || RS || PI)),
                 "uniform high counter word: the plain Gaussian walk of one portfolio only");
-  static_assert(!FH || (BOOT && HZ && !(LOGC || REB || CF || STT || GV || OV || AT || DD)), "filtered rows: the bootstrap's segmented walk only");
+  static_assert(!FH || (BOOT && HZ && !(LOGC || REB || CF || STT || GV || OV || AT || DD || PI)), "filtered rows: the bootstrap's segmented walk only");
   static_assert(!JP || !(NATIVE || FOLD || LOGC || BOOT || REB || STT || CF || OV || GV || AT || ANTI || FH),
                 "jump-diffusion: the Gaussian walk, its drawdown and its horizons, simple compounding only");
-  static_assert(!RS || !(NATIVE || FOLD || LOGC || BOOT || REB || STT || CF || OV || GV || AT || ANTI || FH || JP),
+  static_assert(!RS || !(NATIVE || FOLD || LOGC || BOOT || REB || STT || CF || OV || GV || AT || ANTI || FH || JP || PI),
                 "regime switching: the Gaussian walk, its drawdown and its horizons, simple compounding only");
-  static_assert(!GP || (CF && HZ && !(NATIVE || FOLD || LOGC || DD || REB || OV || GV || AT || ANTI || FH || UHI || JP || RS)),
+  static_assert(!GP || (CF && HZ && !(NATIVE || FOLD || LOGC || DD || REB || OV || GV || AT || ANTI || FH || UHI || JP || RS || PI)),
                 "glide path: the cash-flow kernel's segmented walk only");
+  static_assert(!PI || (HZ && (JP || (STT && GV)) && !(NATIVE || FOLD || LOGC || BOOT || REB || CF || OV || AT || ANTI || FH || UHI || RS || GP)),
+                "floor protection: the segmented GARCH or jump walk, simple compounding only");
   constexpr int N4 = 4 * NB;
   // ANTI (SPEC.md 2.3): a lane's PPT draws feed EM = 2 PPT members -- slot e < PPT walks on z[e], slot PPT + e on -z[e]; p, live and
   // the counters are per draw (a.path_begin and a.n_paths count pairs), the members 2 p and 2 p + 1 are adjacent in the output rows
   constexpr int EM = ANTI ? 2 * PPT : PPT;
-  static_assert(!ANTI || !(NATIVE || FOLD || BOOT || REB || CF || OV || AT || FH), "antithetic pairs: the lean Gaussian and GARCH walks only");
+  static_assert(!ANTI || !(NATIVE || FOLD || BOOT || REB || CF || OV || AT || FH || PI), "antithetic pairs: the lean Gaussian and GARCH walks only");
   // wave-uniform parameters through the constant address space -> s_load_dword* into SGPRs
   typedef const __attribute__((address_space(4))) float* cfloat_p;
   cfloat_p mu = (cfloat_p)a.packed;
@@ -139,6 +141,7 @@
     float gh[PPT];                                        // GV, FH: the variance ratio h of SPEC.md 4.9 / 4.11
     f32x2 At[PPT][N4 / 2];                                // AT: the assets' contributions A_i of SPEC.md 4.10
     uint32_t rg[PPT];                                     // RS: the regime of the next step (SPEC.md 2.6); s_0 is drawn in step 0
+    float Mk[EM][KT];                                     // PI: the running peak M of SPEC.md 4.15, V_0 included
 #pragma unroll
     for (int e = 0; e < PPT; e++) {
       p[e] = tl * tile + (uint64_t)e * PATH_BLOCK + threadIdx.x;
@@ -147,6 +150,10 @@
       plo[e] = (uint32_t)g; phi[e] = (uint32_t)(g >> 32);
 #pragma unroll
       for (int k = 0; k < KT; k++) V[e][k] = logc ? 0.0f : a.v0;
+      if constexpr (PI) {
+#pragma unroll
+        for (int k = 0; k < KT; k++) Mk[e][k] = a.v0;
+      }
       if constexpr (BOOT) jrow[e] = 0u;                   // replaced at t = 0 (a restart)
       if constexpr (GV) gh[e] = garch_args(a)->h0;        // one scalar load per tile
       if constexpr (FH) gh[e] = filt_args(a)->h0;
@@ -391,6 +398,11 @@
           }
         if constexpr (DD && OV) {                          // the drawdown output of the overlay kernel's arguments
           const auto dk = kernarg<PathArgsOV>();
+#pragma unroll
+          for (int k = 0; k < KT; k++)
+            if (k < kt) dk->mdd[(size_t)(a.k_begin + k) * dk->mdd_stride + p[e]] = Qk[e][k];
+        } else if constexpr (DD && PI) {                   // the drawdown output of the protection kernel's arguments
+          const auto dk = kernarg<PathArgsPI>();
 #pragma unroll
           for (int k = 0; k < KT; k++)
             if (k < kt) dk->mdd[(size_t)(a.k_begin + k) * dk->mdd_stride + p[e]] = Qk[e][k];

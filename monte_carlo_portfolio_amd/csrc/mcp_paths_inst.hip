@@ -57,6 +57,15 @@ static hipError_t ladder(const PathKernel& k, const PathLaunchArgs& s, hipStream
     MCP_ROW(ok && !k.blds, mc_paths_fhs_kernel<NB, KT, 1, false>);
     return hipErrorInvalidValue;
   }
+  if (k.pi) {                                             // SPEC.md 4.15: the GARCH walk (also Gaussian and Student-t requests) or the jump walk
+    const bool ok = (k.family == FAM_DD || k.family == FAM_HZ) && !k.boot && !k.rs && !k.native && !k.anti && !lg;
+    const bool gw = ok && k.stt && k.gv && !k.jp, jw = ok && k.jp && !k.stt && !k.gv, dd = k.family == FAM_DD;
+    MCP_ROW(gw && !dd, mc_paths_pi_kernel<NB, KT, 1, false, false>);
+    MCP_ROW(gw && dd, mc_paths_pi_kernel<NB, KT, 1, false, true>);
+    MCP_ROW(jw && !dd, mc_paths_pi_kernel<NB, KT, 1, true, false>);
+    MCP_ROW(jw && dd, mc_paths_pi_kernel<NB, KT, 1, true, true>);
+    return hipErrorInvalidValue;
+  }
   if (k.anti) {                                           // SPEC.md 2.3: gv names the GARCH walk, which also serves Student-t requests
     const bool lean = gauss && !k.native, gw = k.stt && k.gv && !k.jp && !k.rs && !k.boot && !k.native && !lg;
     switch (k.family) {
@@ -148,6 +157,7 @@ hipError_t MCP_CAT(launch_paths_nb, MCP_NB)(const PathKernel& k, const PathLaunc
   if (k.jp && (k.fold || k.uhi || k.native || k.anti || k.fh || k.family == FAM_AT)) return hipErrorInvalidValue;
   if (k.rs && (k.fold || k.uhi || k.native || k.anti || k.fh || k.family == FAM_AT)) return hipErrorInvalidValue;
   if (k.gp && (k.family != FAM_CF || k.fold || k.uhi || k.native || k.anti || k.fh || k.jp || k.rs || k.gv)) return hipErrorInvalidValue;
+  if (k.pi && (k.fold || k.uhi || k.native || k.anti || k.fh || k.rs || k.gp || k.family == FAM_AT)) return hipErrorInvalidValue;
   if (k.fold) {                                            // rho = c + v.z: the plain Gaussian walk on the spec's normals
     const bool ok = k.family == FAM_PLAIN && !k.boot && !k.stt && !k.gv && !k.native && !k.kt8;
     MCP_ROW(ok && k.logc, mc_paths_kernel<NB, 1, 1, false, true, true>);

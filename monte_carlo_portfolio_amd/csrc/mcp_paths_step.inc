@@ -16,7 +16,8 @@
 // the step's market jump J, and the row pair's accumulator starts at fma(b, J, mu) (SPEC.md 2.5 / 4.12).  RS: one more Philox block on
 // counter stream 4 before the asset normals gives the step's regime s_t and the next step's; the row pair's chain runs on (mu, L) where the
 // wave has a lane in regime 0 and then, under `if (s_t)`, on (mu1, L1) -- each a whole chain of its own, nothing shared (SPEC.md 2.6 / 4.13).  UHI: the same step with p_hi a scalar (philox4x32_10_uhi), the drift read through the LDS address
-// par_lds instead of the opaque zero offset, and the blocks scheduled one at a time.
+// par_lds instead of the opaque zero offset, and the blocks scheduled one at a time.  PI: the update of V is the floor rule of SPEC.md
+// 4.15 on the step's rho, then the peak M.
       float rho[EM][KT];
       float fsh[PPT];                                  // FH: the shock s_j of the step's row (SPEC.md 2.4)
       if constexpr (BOOT) {
@@ -334,6 +335,25 @@
           for (int k = 0; k < KT; k++) {
             const float u = fma32(V[e][k], rho[e][k], V[e][k]) + cs;
             V[e][k] = (V[e][k] > 0.0f && u > 0.0f) ? u : 0.0f;
+          }
+      } else if constexpr (PI) {
+        // SPEC.md 4.15: F = fmaxf(S_t, fl32(theta M)), C = V - F, E = fmaxf(fminf(fl32(m C), fl32(b V)), +0), u = fma(V - E, rf, V),
+        // V = fma(E, rho, u), M = fmaxf(M, V); fminf / fmaxf are IEEE minNum / maxNum.  S_t and the constants are wave-uniform
+        // scalar loads inside the step.
+        typedef const __attribute__((address_space(4))) float* cfloor_p;
+        __builtin_amdgcn_sched_barrier(0);             // the rule's scalar loads stay behind the weight dot: issued earlier they are
+                                                       // live across the step's SGPR peak and the compiler parks scalars in VGPR lanes
+        const cprotect_p pk = protect_args(a);
+        const float p_s = ((cfloor_p)pk->floor)[t], p_m = pk->m, p_b = pk->b, p_rf = pk->rf, p_th = pk->theta;
+#pragma unroll
+        for (int e = 0; e < PPT; e++)
+#pragma unroll
+          for (int k = 0; k < KT; k++) {
+            const float fl = fmaxf(p_s, p_th * Mk[e][k]);
+            const float ex = fmaxf(fminf(p_m * (V[e][k] - fl), p_b * V[e][k]), 0.0f);
+            const float u = fma32(V[e][k] - ex, p_rf, V[e][k]);
+            V[e][k] = fma32(ex, rho[e][k], u);
+            Mk[e][k] = fmaxf(Mk[e][k], V[e][k]);
           }
       } else if constexpr (!REB) {
 #pragma unroll

@@ -67,13 +67,14 @@ struct PathLaunchArgs;
 // at one wave per SIMD fewer, and nothing above NB = 4 has been timed), and jp (the jump-diffusion kernels of the plain, drawdown
 // and horizon families: Gaussian draws plus the market jump of SPEC.md 2.5, simple compounding), and rs (the regime-switching kernels
 // of the same three families: Gaussian draws on the drift and factor of the path's regime, SPEC.md 2.6, simple compounding), and
-// gp (FAM_CF only: the glide-path kernel, the cash-flow walk on scheduled target weights, SPEC.md 4.14).
+// gp (FAM_CF only: the glide-path kernel, the cash-flow walk on scheduled target weights, SPEC.md 4.14), and pi (the floor-protection
+// kernel of SPEC.md 4.15: FAM_DD with the drawdown, else FAM_HZ, H = 0 included; stt and gv both set for the GARCH walk, or jp).
 // The one ladder of mcp_paths_inst.hip maps it to a kernel and lists which selectors have one.
 constexpr int LEAN_MAX_NB = 4;
 enum PathFamily { FAM_PLAIN, FAM_DD, FAM_HZ, FAM_REB, FAM_CF, FAM_OV, FAM_AT };
 struct PathKernel {
   int family;
-  bool logc, boot, blds, stt, dd, gv, kt8, native, fold, anti, fh, uhi, jp, rs, gp;
+  bool logc, boot, blds, stt, dd, gv, kt8, native, fold, anti, fh, uhi, jp, rs, gp, pi;
 };
 
 // mcp_paths_inst.hip (one translation unit per NB): every pass of the kernel that `k` selects, on the blocks of `args` that the
@@ -114,6 +115,10 @@ hipError_t launch_zero(void* p, size_t bytes, hipStream_t s);
 // binary32 array (SPEC.md 5.6); `counts` is [rows][2] and zeroed by the caller
 hipError_t launch_count_rows(const float* values, uint64_t stride, uint64_t n, int rows, bool has_target, float target,
                              unsigned long long* counts, hipStream_t s);
+// counts[r] += {#(v < thr[r][0]), #(v < thr[r][1])} over the n live values of each of the `rows` rows of a [rows][stride] binary32
+// array (SPEC.md 5.15); `thr` is a device [rows][2] array (-inf: nothing is below), `counts` is [rows][2] and zeroed by the caller
+hipError_t launch_count_below(const float* values, uint64_t stride, uint64_t n, int rows, const float* thr, unsigned long long* counts,
+                              hipStream_t s);
 // every buffer <- element-wise sum of the `nsrc` buffers (u64 words): the exchange between logical shards of ONE device
 // (or of devices with peer access)
 hipError_t launch_sum_u64(unsigned long long* const* bufs, int nsrc, size_t words, hipStream_t s);

@@ -609,6 +609,44 @@ hipError_t launch_count_rows(const float* values, uint64_t stride, uint64_t n, i
   return hipGetLastError();
 }
 
+// SPEC.md 5.15: the paths below each of a row's two thresholds -- count_rows_kernel with two compares against per-row values.
+__global__ void __launch_bounds__(SB) count_below_kernel(const float* __restrict__ values, uint64_t stride, uint64_t n,
+                                                         const float* __restrict__ thr, unsigned long long* __restrict__ counts) {
+  __shared__ unsigned long long s_n[2];
+  if (threadIdx.x < 2) s_n[threadIdx.x] = 0ull;
+  __syncthreads();
+  const float* __restrict__ row = values + (size_t)blockIdx.y * stride;
+  const float ta = thr[2 * (size_t)blockIdx.y], tb = thr[2 * (size_t)blockIdx.y + 1];
+  unsigned long long na = 0, nb = 0;
+  for (uint64_t base = (uint64_t)blockIdx.x * SB; base < n; base += (uint64_t)gridDim.x * SB) {   // block-uniform trip count
+    const uint64_t i = base + threadIdx.x;
+    const bool live = i < n;
+    const float v = live ? row[i] : 0.0f;
+    na += (unsigned long long)__popcll(__ballot(live && v < ta));
+    nb += (unsigned long long)__popcll(__ballot(live && v < tb));
+  }
+  if ((threadIdx.x & 63) == 0) {
+    if (na) atomicAdd(&s_n[0], na);
+    if (nb) atomicAdd(&s_n[1], nb);
+  }
+  __syncthreads();
+  if (threadIdx.x < 2 && s_n[threadIdx.x]) atomicAdd(&counts[2 * (size_t)blockIdx.y + threadIdx.x], s_n[threadIdx.x]);
+}
+
+hipError_t launch_count_below(const float* values, uint64_t stride, uint64_t n, int rows, const float* thr, unsigned long long* counts,
+                              hipStream_t s) {
+  if (rows < 1) return hipErrorInvalidValue;
+  uint64_t g = (n + SB - 1) / SB;
+  if (g < 1) g = 1;
+  if (g > 256) g = 256;
+  for (int r0 = 0; r0 < rows; r0 += 65535) {             // gridDim.y holds at most 65535 rows
+    const int nr = rows - r0 < 65535 ? rows - r0 : 65535;
+    count_below_kernel<<<dim3((unsigned)g, (unsigned)nr), SB, 0, s>>>(values + (size_t)r0 * stride, stride, n, thr + 2 * (size_t)r0,
+                                                                     counts + 2 * (size_t)r0);
+  }
+  return hipGetLastError();
+}
+
 hipError_t launch_sum_u64(unsigned long long* const* bufs, int nsrc, size_t words, hipStream_t s) {
   if (nsrc < 1 || nsrc > 8) return hipErrorInvalidValue;
   PtrList l;

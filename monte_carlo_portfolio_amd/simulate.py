@@ -25,6 +25,8 @@ _CTX: dict[tuple, "Context"] = {}
 # sentence that refuses a keyword the entry point has no argument group for (None: a plain one naming the entry point and the
 # keyword).  A new feature adds its row here, its groups to _ffi.SIMULATE_ENTRIES and its keyword to _KEYWORD_GROUP.
 _ENTRY_CHOICE = (
+    (("protect",), "mcp_simulate_protected", "protect is not combined with overlay, cashflow, rebalance, bootstrap or filtered rows, regimes, "
+                                             "glide, attribution or antithetic"),
     (("glide",), "mcp_simulate_glide", "glide is not combined with drawdown, rebalance, overlay, garch, attribution, antithetic, jumps, "
                                        "regimes or filtered rows"),
     (("filtered",), "mcp_simulate_filtered", "filtered rows take garch, block and horizons only"),
@@ -50,7 +52,7 @@ _ENTRY_CHOICE = (
 # the argument group of _ffi.SIMULATE_ENTRIES that carries each feature keyword of Context._call
 _KEYWORD_GROUP = {"rows": "bt", "dof": "st", "period": "rb", "drawdown": "dd", "horizons": "hz_in", "flows": "cf", "overlay": "ov",
                   "garch": "gv", "attribution": "attr", "antithetic": "pairs", "filtered": "ft", "jumps": "jp", "regimes": "rs",
-                  "glide": "gl"}
+                  "glide": "gl", "protect": "pt"}
 
 
 class Context:
@@ -98,8 +100,8 @@ class Context:
     def _call(self, prm: _ffi.McpParams, W, seed: int, path_begin: int, n_paths: int, store: bool, mu=None, chol=None, rows=None,
               block: float = 1.0, dof=None, period=None, cost: float = 0.0, drawdown: bool = False, horizons=None, levels=(),
               flows=None, target=None, overlay=None, garch=None, attribution=False, antithetic=False, filtered=None, jumps=None, regimes=None,
-              glide=None):
-        """The one library call behind every simulate_* method: two regimes (regimes: the (p01, p10, start, mu1, chol1) of check_regimes), market jumps (jumps: the (intensity, mean, std, loading or None) of check_jumps), GARCH volatility (garch: the (alpha, beta, h0) of check_garch), an option overlay (overlay: the triple of check_overlay), cash flows (flows, target), Student-t draws (dof), rebalancing
+              glide=None, protect=None):
+        """The one library call behind every simulate_* method: floor protection (protect: the (floor, multiplier, rate, cap, ratchet) of check_protect; `target` is then its second count), two regimes (regimes: the (p01, p10, start, mu1, chol1) of check_regimes), market jumps (jumps: the (intensity, mean, std, loading or None) of check_jumps), GARCH volatility (garch: the (alpha, beta, h0) of check_garch), an option overlay (overlay: the triple of check_overlay), cash flows (flows, target), Student-t draws (dof), rebalancing
         (period, cost), bootstrap rows (rows, block) or Gaussian draws (mu, chol), with the drawdown or horizons.  Allocates the
         outputs that were asked for and passes NULL for the rest -> _Outputs, None where not asked for (terminal, qd,
         horizon_terminal: with `store` only; counts, hz_counts: with `flows` only; attr [K, N] records of ATTR_DTYPE and attr_counts
@@ -111,10 +113,11 @@ class Context:
                                    ("drawdown", drawdown), ("horizons", horizons is not None), ("flows", flows is not None),
                                    ("overlay", overlay is not None), ("garch", garch is not None), ("attribution", attribution),
                                    ("antithetic", antithetic), ("filtered", filtered is not None), ("jumps", jumps is not None),
-                                   ("regimes", regimes is not None), ("glide", glide is not None)) if on]
+                                   ("regimes", regimes is not None), ("glide", glide is not None),
+                                   ("protect", protect is not None)) if on]
         has = set(given).issuperset
         entry, refusal = next((e, r) for needs, e, r in _ENTRY_CHOICE if has(needs))
-        groups = _ffi.SIMULATE_ENTRIES[entry]
+        groups = _ffi.SIMULATE_ENTRIES[entry] if entry in _ffi.SIMULATE_ENTRIES else _ffi.EXTENSION_ENTRIES[entry]
         # the library states the rules (check_request); a keyword the entry point has no argument for is refused here, not dropped
         for kw in given:
             if _KEYWORD_GROUP[kw] not in groups:
@@ -145,6 +148,7 @@ class Context:
                 "hz_in": (H, steps if H else None, L, lv if L else None), "out": (term, stats), "dd": (raw, dd_stats),
                 "hz_out": (hz_term, hz_stats, bands if L else None), "counts": (counts,), "hz_counts": (hz_counts,), "pairs": (pairs,),
                 "contrib": (contrib,), "attr": (attr,), "attr_counts": (attr_counts,), "bt": (bt,),
+                "pt": (_ffi.make_protect(*protect, target=target) if protect is not None else None,),
                 "gl": (_ffi.make_glide(*glide) if glide is not None else None,),               # flows None: the all-zero schedule
                 "cf": (_ffi.make_cashflow(flows, target) if flows is not None else None,),
                 "rb": (_ffi.McpRebalance(int(period), 0, float(cost)) if period is not None else None,),
@@ -289,6 +293,17 @@ class Context:
                           horizons=horizons, levels=levels, flows=None if flows is None else np.ascontiguousarray(flows, np.float32),
                           target=target, glide=(np.ascontiguousarray(glide[0], np.int32), np.ascontiguousarray(glide[1], np.float32)))
 
+    def simulate_protected(self, prm: _ffi.McpParams, protect, mu, chol, W, seed: int, path_begin: int, n_paths: int, store: bool,
+                           dof=None, garch=None, jumps=None, target=None, drawdown: bool = False, horizons=None, levels=()):
+        """simulate() / simulate_student_t() / simulate_garch() / simulate_jumps(), with their drawdown or horizons, under the floor
+        rule of SPEC.md 4.15 (CPPI with an exposure cap and a drawdown ratchet; include/mcport_protect.h, mcp_simulate_protected;
+        simple compounding only): `protect` is (floor binary32 [n_steps + 1], multiplier, rate, cap, ratchet) -> _Outputs with counts
+        [K, 2] uint64 {n_gap: V_T below the floor, n_short: V_T below `target`, 0 without one} and hz_counts [H, K, 2]; the entries of
+        the blocks not asked for are None."""
+        floor = np.ascontiguousarray(protect[0], np.float32)
+        return self._call(prm, W, seed, path_begin, n_paths, store, mu=mu, chol=chol, dof=dof, garch=garch, jumps=jumps, target=target,
+                          drawdown=drawdown, horizons=horizons, levels=levels, protect=(floor,) + tuple(float(v) for v in protect[1:5]))
+
     def simulate_overlay(self, prm: _ffi.McpParams, overlay, mu, chol, W, seed: int, path_begin: int, n_paths: int, store: bool,
                          dof=None, drawdown: bool = False, horizons=None, levels=()):
         """simulate() / simulate_drawdown() / simulate_horizons() / simulate_student_t() with the option rows `overlay` (the (rows,
@@ -383,6 +398,76 @@ def check_glide(glide, weights, n_steps):
 def _glide_blocks(gl, W):
     """The 'glide' block of every portfolio: the breaks and the binary32 weights [G + 1, N] as used, segment 0 the call's weights."""
     return [{"breaks": gl[0].astype(np.int64), "weights": np.concatenate([W[k][None, :], gl[1][:, k, :]], axis=0)} for k in range(W.shape[0])]
+
+
+def check_protect(protect, n_steps, v0=1.0):
+    """SPEC.md 4.15 argument rules -> None (no protection) or (floor binary32 [n_steps + 1], multiplier, rate, cap, ratchet).
+    `protect` is (floor, multiplier[, rate[, cap[, ratchet]]]), rate 0, cap 1 and ratchet 0 by default.  floor: a number, the floor
+    as a fraction of v0 that grows at `rate` per step (protect.floor_schedule), or an explicit sequence of n_steps + 1 floors in the
+    units of v0.  ValueError for anything else: not a sequence of 2 to 5 entries, a bool or a string among the numbers, a value that is
+    not finite before or after rounding to binary32, a negative floor, multiplier < 0, cap <= 0, rate <= -1, ratchet outside
+    [0, 1), a floor sequence of another length."""
+    if protect is None:
+        return None
+    msg = f"protect must be (floor, multiplier[, rate[, cap[, ratchet]]]), got {protect!r}"
+    if isinstance(protect, (str, bytes)) or not hasattr(protect, "__len__") or not 2 <= len(protect) <= 5:
+        raise ValueError(msg)
+
+    def number(v):
+        return isinstance(v, (int, float, np.integer, np.floating)) and not isinstance(v, (bool, np.bool_))
+
+    def finite32(v):
+        with np.errstate(over="ignore"):
+            return bool(np.isfinite(v)) and bool(np.isfinite(np.float32(v)))
+    vals = list(protect[1:]) + [0.0, 1.0, 0.0][len(protect) - 2:]
+    if any(not number(v) for v in vals):
+        raise ValueError(msg)
+    m, rate, cap, ratchet = (float(v) for v in vals)
+    if not all(finite32(v) for v in (m, rate, cap, ratchet)):
+        raise ValueError(f"protect values must be finite, in binary32 too, got {protect!r}")
+    if m < 0.0:
+        raise ValueError(f"protect multiplier must be >= 0, got {m!r}")
+    if not (cap > 0.0 and np.float32(cap) > 0.0):
+        raise ValueError(f"protect cap must be > 0, got {cap!r}")
+    if not (rate > -1.0 and np.float32(rate) > np.float32(-1.0)):
+        raise ValueError(f"protect rate must be > -1, got {rate!r}")
+    if not (0.0 <= ratchet < 1.0 and np.float32(ratchet) < np.float32(1.0)):
+        raise ValueError(f"protect ratchet must be in [0, 1), got {ratchet!r}")
+    fl = protect[0]
+    if number(fl):
+        if not finite32(float(fl) * float(v0)) or float(fl) < 0.0:
+            raise ValueError(f"the protect floor must be a finite fraction of v0 >= 0, got {fl!r}")
+        from .protect import floor_schedule
+        floor = floor_schedule(float(fl), rate, n_steps, v0)
+    else:
+        if isinstance(fl, (str, bytes, bool, np.bool_)) or any(not number(v) for v in np.asarray(fl, object).ravel().tolist()):
+            raise ValueError(msg)
+        f64 = np.asarray(fl, np.float64).ravel()
+        if f64.size != int(n_steps) + 1:
+            raise ValueError(f"a protect floor sequence must hold n_steps + 1 = {int(n_steps) + 1} numbers, got {f64.size}")
+        with np.errstate(over="ignore"):
+            floor = np.ascontiguousarray(f64.astype(np.float32))
+    if not np.all(np.isfinite(floor)) or np.any(floor < 0):
+        raise ValueError("the protect floors must be finite (in binary32) and >= 0")
+    return floor, m, rate, cap, ratchet
+
+
+def _protect_blocks(pv, counts, hz_counts, n, target):
+    """The 'protect' block of every portfolio: the schedule and the binary32 parameters as used, the paths that end below the floor
+    (n_gap, gap_probability), below the target (n_short, shortfall_probability; 0 without one) and, with horizons, the same per
+    horizon against S_h."""
+    floor, m, rate, cap, ratchet = pv
+    out = []
+    for k in range(counts.shape[0]):
+        blk = {"floor": floor.copy(), "multiplier": float(np.float32(m)), "cap": float(np.float32(cap)), "rate": float(np.float32(rate)),
+               "ratchet": float(np.float32(ratchet)), "target": target, "n_gap": int(counts[k, 0]), "gap_probability": float(counts[k, 0]) / n,
+               "n_short": int(counts[k, 1]), "shortfall_probability": float(counts[k, 1]) / n}
+        if hz_counts is not None:
+            c = hz_counts[:, k, :]
+            blk["horizons"] = {"n_gap": c[:, 0].astype(np.int64), "gap_probability": c[:, 0].astype(np.float64) / n,
+                               "n_short": c[:, 1].astype(np.int64), "shortfall_probability": c[:, 1].astype(np.float64) / n}
+        out.append(blk)
+    return out
 
 
 def check_overlay(overlay, spot, n_assets):
@@ -703,6 +788,9 @@ def antithetic_to_dict(rec) -> dict:
 # checked, so the same rule wins when two apply.  The C side states the same rules for the library (check_request).
 _FLAGS = ("drawdown", "attribution", "antithetic", "fold", "native_math")
 _PATHS_COMBINE = {
+    "protect": ("protect needs constant weights, simple compounding, the spec's normals and the unfolded recurrence",
+                ("rebalance", "cashflow", "overlay", "regimes", "glide", "attribution", "antithetic", "fold", "native_math",
+                 "compounding='log'"), True),
     "glide": ("glide needs the cashflow walk -- simple compounding, the spec's normals and the unfolded recurrence",
               ("drawdown", "rebalance", "overlay", "garch", "attribution", "antithetic", "jumps", "regimes", "fold", "native_math",
                "compounding='log'"), True),
@@ -756,7 +844,8 @@ def simulate_paths(mu, cov, weights, n_steps=252, n_paths=10_000, seed=0, v0=1.0
                    rf=0.0, alpha=0.95, devices=None, store=False, path_begin=0, chol=None,
                    native_math=False, as_array=False, fold=False, shard="auto", context=None, drawdown=False,
                    horizons=None, bands=(), rebalance=None, rebalance_cost=0.0, dof=None, cashflow=None, target=None,
-                   overlay=None, spot=None, garch=None, attribution=False, antithetic=False, jumps=None, regimes=None, glide=None):
+                   overlay=None, spot=None, garch=None, attribution=False, antithetic=False, jumps=None, regimes=None, glide=None,
+                   protect=None):
     """Simulate `n_paths` correlated return paths and reduce them to risk statistics.
 
     mu [N], cov [N,N] are per-step mean and covariance (the reference's `mean_returns`, `cov_matrix`
@@ -897,10 +986,32 @@ def simulate_paths(mu, cov, weights, n_steps=252, n_paths=10_000, seed=0, v0=1.0
     with cashflow / target, dof, horizons / bands, store, as_array, devices and bootstrap rows (simulate_bootstrap).  Not built:
     glide with drawdown, rebalance, overlay, garch, attribution, antithetic, jumps, regimes, fold, native_math or
     compounding="log" (ValueError), on filtered rows, in simulate_sweep, in PathEngine and at the mcp_launch_* level.
+
+    protect=None (default): the whole value rides the weights.  protect=(floor, multiplier[, rate[, cap[, ratchet]]]): floor
+    protection inside the walk (SPEC.md 4.15 / 5.15) -- CPPI: before every step, multiplier times the cushion V - F above the floor
+    F is held in the portfolio `weights`, at most cap times V (default 1: no leverage), never less than 0, and the rest earns the
+    riskless `rate` per step (default 0).  floor: a fraction of v0 that grows at `rate` (0.8: never lose more than 20 %), or an
+    explicit sequence of n_steps + 1 floors.  ratchet (default 0) in [0, 1): the floor is also at least ratchet times the running
+    peak of V -- TIPP, drawdown control.  The allocation reacts to the path, the draws are the call's own; floor 0, ratchet 0, cap 1
+    and multiplier >= 1 is the call without it bit for bit.  Under small Gaussian steps the floor holds; under jumps or dof it can be
+    gapped through, and every dict gains 'protect' {floor (float32 [n_steps + 1] as used), multiplier, cap, rate, ratchet, target,
+    n_gap, gap_probability (paths that end below the floor), n_short, shortfall_probability (below `target`; 0 without one) and,
+    with horizons, 'horizons' {the same four, [H], against the floor of that step}}.  as_array=True appends counts [K, 2] uint64
+    {n_gap, n_short} (and hz_counts [H, K, 2] with horizons).  protect.protect_law(mu, cov, weights, n_steps, protect) is the exact
+    mean and variance on Gaussian draws while neither the cap, a gap nor the ratchet acts.  Combines with dof, garch, jumps,
+    drawdown or horizons / bands, store, target, as_array and devices.  Not built: protect with rebalance, cashflow, overlay,
+    regimes, glide, attribution, antithetic, fold, native_math or compounding="log" (ValueError), on bootstrap or filtered rows, in
+    simulate_sweep, in PathEngine and at the mcp_launch_* level.
     """
-    kw = dict(glide=glide, regimes=regimes, jumps=jumps, antithetic=antithetic, attribution=attribution, garch=garch, overlay=overlay,
+    kw = dict(protect=protect, glide=glide, regimes=regimes, jumps=jumps, antithetic=antithetic, attribution=attribution, garch=garch, overlay=overlay,
               cashflow=cashflow, dof=dof, rebalance=rebalance, drawdown=drawdown, horizons=horizons, fold=fold, native_math=native_math,
               compounding=compounding, shard=shard)
+    pv = check_protect(protect, n_steps, v0)
+    _check_combines(_PATHS_COMBINE, "protect", kw)
+    goal = None
+    if pv is not None and target is not None:              # the target of a protected call is the second count's, not a cash-flow goal
+        goal = check_cashflow(0.0, target, n_steps)[1]
+        target = None
     gl = check_glide(glide, weights, n_steps)
     _check_combines(_PATHS_COMBINE, "glide", kw)
     if gl is not None and cashflow is None:
@@ -946,9 +1057,18 @@ def simulate_paths(mu, cov, weights, n_steps=252, n_paths=10_000, seed=0, v0=1.0
     prm, ctx = _setup(mu32.shape[0], n_steps, W.shape[0], compounding, v0, alpha, rf, native_math, fold, devices,
                       "paths" if attribution or antithetic else shard, context)
     out = ctx._call(prm, W, int(seed), int(path_begin), int(n_paths), store, mu=mu32, chol=L, dof=dof, period=period, cost=cost,
-                    drawdown=drawdown, horizons=steps, levels=levels, flows=flows, target=target, overlay=ov, garch=gv,
-                    attribution=bool(attribution), antithetic=bool(antithetic), jumps=jv, regimes=rv, glide=gl)
-    res = _result(out, np.asarray(weights).ndim == 1, store, as_array, steps, levels, compounding, flows, target)
+                    drawdown=drawdown, horizons=steps, levels=levels, flows=flows, target=target if pv is None else goal, overlay=ov,
+                    garch=gv, attribution=bool(attribution), antithetic=bool(antithetic), jumps=jv, regimes=rv, glide=gl, protect=pv)
+    if pv is not None:                                     # the counts are the 'protect' block's, not a 'cashflow' block's
+        res = _result(out._replace(counts=None, hz_counts=None), np.asarray(weights).ndim == 1, store, as_array, steps, levels, compounding)
+        if as_array:
+            res = (res if isinstance(res, tuple) else (res,)) + ((out.counts,) if out.hz_counts is None else (out.counts, out.hz_counts))
+        else:
+            for d, blk in zip([res] if isinstance(res, dict) else res,
+                              _protect_blocks(pv, out.counts, out.hz_counts, int(out.stats[0]["n"]), goal)):
+                d["protect"] = blk
+    else:
+        res = _result(out, np.asarray(weights).ndim == 1, store, as_array, steps, levels, compounding, flows, target)
     if gl is not None and not as_array:
         for d, blk in zip([res] if isinstance(res, dict) else res, _glide_blocks(gl, W)):
             d["glide"] = blk
@@ -1248,6 +1368,8 @@ def simulate_sweep(mu, cov, weights=None, n_portfolios=2500, min_weights=None, m
         raise ValueError("simulate_sweep does not take cashflow or target: call simulate_paths for the optimum")
     if kw.get("glide") is not None:
         raise ValueError("simulate_sweep does not take glide: call simulate_paths for the optimum")
+    if kw.get("protect") is not None:
+        raise ValueError("simulate_sweep does not take protect: call simulate_paths for the optimum")
     if kw.get("attribution"):
         raise ValueError("simulate_sweep does not take attribution: call simulate_paths for the optimum")
     kw.pop("attribution", None)
