@@ -1,0 +1,142 @@
+// host_selftest.cpp -- drives mcp_host.cpp on heap buffers of exactly the documented lengths, for `make host-selftest`: built
+// with a plain C++ compiler under AddressSanitizer + UBSan, so an overrun of a packer or a pivot rule is a sanitizer report.  It
+// asserts return codes and finiteness only; the values are pinned bit for bit by the CPU tests against their NumPy restatements.
+#include <cmath>
+#include <cstdio>
+#include <cstdlib>
+#include <vector>
+
+#include "mcp_host.h"
+
+using namespace mcph;
+
+#define EXPECT(cond)                                                                                           \
+  do {                                                                                                         \
+    if (!(cond)) {                                                                                             \
+      fprintf(stderr, "host_selftest:%d: %s  [%s; last error: %s]\n", __LINE__, #cond, g_case, mcp_last_error()); \
+      exit(1);                                                                                                 \
+    }                                                                                                          \
+  } while (0)
+
+static char g_case[96] = "";
+template <class T> static bool finite(const std::vector<T>& v) {
+  for (const T& x : v)
+    if (!std::isfinite(x)) return false;
+  return true;
+}
+
+enum Feature { PLAIN, BOOT, FILTERED, JUMPS, REGIMES, GLIDE_CF, GLIDE, PROTECT, CASH, OVERLAY, N_FEATURES };
+static const char* const k_names[N_FEATURES] = {"plain", "bootstrap", "filtered", "jumps", "regimes", "glide+flows", "glide",
+                                                "protect", "cash", "overlay"};
+
+static void run_shape(int N, int K, int T, int H) {
+  const int R = 6, G = 2;
+  const int32_t steps_v[2] = {1, T}, breaks_v[G] = {3, 7};
+  const std::vector<int32_t> steps(steps_v, steps_v + H), breaks(breaks_v, breaks_v + G);
+  std::vector<float> mu(N), mu1(N), chol((size_t)N * N, 0.0f), chol1((size_t)N * N, 0.0f), W((size_t)K * N), rows((size_t)R * N), shock(R),
+      loading(N), targets((size_t)G * K * N), flows(T, -0.01f), zero_flows(T, 0.0f), floor_s(T + 1), spot(N, 100.0f);
+  for (int i = 0; i < N; i++) {
+    mu[i] = 0.001f * (float)(i + 1) / (float)N;
+    mu1[i] = -2.0f * mu[i];
+    loading[i] = 0.5f + 0.5f * (float)(i & 1);
+    for (int j = 0; j <= i; j++) chol[(size_t)i * N + j] = i == j ? 0.01f : 0.001f;
+    for (int j = 0; j <= i; j++) chol1[(size_t)i * N + j] = 3.0f * chol[(size_t)i * N + j];
+  }
+  for (size_t i = 0; i < W.size(); i++) W[i] = (1.0f + 0.1f * (float)(i % 3)) / (float)N;
+  for (size_t i = 0; i < targets.size(); i++) targets[i] = (1.0f + 0.1f * (float)(i % 5)) / (float)N;
+  for (size_t i = 0; i < rows.size(); i++) rows[i] = 0.002f * (float)((int)(i % 7) - 3);
+  for (int j = 0; j < R; j++) shock[j] = 0.5f + 0.25f * (float)j;
+  EXPECT(mcp_protect_floor(0.8, 0.001, T, floor_s.data()) == MCP_OK && finite(floor_s));
+  std::vector<int32_t> row_begin(N + 1, 1);
+  row_begin[0] = 0;
+  const std::vector<mcp_overlay_row> ov_rows(1, mcp_overlay_row{MCP_OVERLAY_PUT, 95.0f, 1.0f, 0.01f});
+
+  mcp_params prm = {N, T, K, MCP_COMPOUND_SIMPLE, 0, 0, 1.0, 0.95, 0.0};
+  const mcp_bootstrap boot = {rows.data(), R, 0, 3.0};
+  const mcp_filtered filt = {mu.data(), rows.data(), shock.data(), R, 0, 2.0};
+  const mcp_garch gv = {0.05, 0.9, 1.0, 0};
+  const mcp_jumps jp = {0.1, -0.05, 0.02, (N & 1) ? loading.data() : nullptr, 0};
+  const mcp_regimes rs = {0.05, 0.2, 0.1, mu1.data(), chol1.data(), 0};
+  const mcp_glide gl = {breaks.data(), targets.data(), G, 0};
+  const mcp_cashflow cf = {flows.data(), T, 1, 1.0}, no_cf = {zero_flows.data(), T, 0, 0.0};
+  const mcp_protect pt = {floor_s.data(), 3.0, 1.0, 0.001, 0.1, nullptr, 0};
+  const mcp_overlay ov = {ov_rows.data(), row_begin.data(), spot.data(), 1, 0};
+  const mcp_rebalance reb = {5, 0, 0.001};
+  const int32_t* hs = H ? steps.data() : nullptr;
+
+  // every pure entry point, outputs of exactly the documented length
+  snprintf(g_case, sizeof g_case, "entry points, N=%d K=%d T=%d H=%d", N, K, T, H);
+  std::vector<double> pv(K), hz((size_t)H * K), p3(3), mean_count(1);
+  std::vector<float> packed(mcp_packed_len(N, K)), drift(N);
+  std::vector<uint64_t> thr3(3), rank(2);
+  std::vector<uint32_t> jthr(MCP_MAX_JUMPS);
+  double* hzp = H ? hz.data() : nullptr;
+  EXPECT(mcp_abi_version() == MCP_ABI_VERSION && !packed.empty());
+  EXPECT(mcp_pack_params(N, K, mu.data(), chol.data(), W.data(), packed.data(), packed.size()) == MCP_OK && finite(packed));
+  EXPECT(mcp_pivots(&prm, mu.data(), chol.data(), W.data(), pv.data()) == MCP_OK && finite(pv));
+  EXPECT(mcp_rebalance_pivots(&prm, &reb, mu.data(), nullptr, W.data(), pv.data()) == MCP_OK && finite(pv));
+  EXPECT(mcp_rebalance_pivots(&prm, &reb, nullptr, &boot, W.data(), pv.data()) == MCP_OK && finite(pv));
+  EXPECT(mcp_bootstrap_pivots(&prm, &boot, W.data(), pv.data()) == MCP_OK && finite(pv));
+  EXPECT(mcp_filtered_pivots(&prm, &filt, W.data(), pv.data()) == MCP_OK && finite(pv));
+  EXPECT(mcp_cashflow_pivots(&prm, &cf, mu.data(), nullptr, W.data(), pv.data()) == MCP_OK && finite(pv));
+  EXPECT(mcp_overlay_pivots(&prm, &ov, mu.data(), W.data(), pv.data()) == MCP_OK && finite(pv));
+  EXPECT(mcp_regime_pivots(&prm, &rs, mu.data(), W.data(), H, hs, pv.data(), hzp) == MCP_OK && finite(pv) && finite(hz));
+  EXPECT(mcp_glide_pivots(&prm, &gl, &cf, mu.data(), nullptr, W.data(), H, hs, pv.data(), hzp) == MCP_OK && finite(pv) && finite(hz));
+  EXPECT(mcp_protect_pivots(&prm, &pt, mu.data(), W.data(), H, hs, pv.data(), hzp) == MCP_OK && finite(pv) && finite(hz));
+  EXPECT(mcp_regime_consts(&rs, thr3.data(), p3.data()) == MCP_OK && finite(p3));
+  EXPECT(mcp_jump_consts(&jp, N, mu.data(), jthr.data(), mean_count.data(), drift.data()) == MCP_OK && finite(mean_count) && finite(drift));
+  EXPECT(mcp_percentile_rank(1000, 0.95, &rank[0], &rank[1], p3.data()) == MCP_OK && rank[1] == rank[0] + 1 && finite(p3));
+  EXPECT(mcp_percentile_rank_q(1000, 2.5, &rank[0], &rank[1], p3.data()) == MCP_OK && rank[1] == rank[0] + 1 && finite(p3));
+
+  // every feature: the request's rules, then the block and the pivots of every tile on exactly sized buffers
+  std::vector<mcp_stats> stats(K), hz_stats((size_t)H * K);
+  std::vector<uint64_t> counts(2 * (size_t)K), hz_counts(2 * (size_t)H * K);
+  for (int f = 0; f < N_FEATURES; f++) {
+    snprintf(g_case, sizeof g_case, "%s, N=%d K=%d T=%d H=%d", k_names[f], N, K, T, H);
+    const Source src = f == BOOT ? SRC_BOOT : f == FILTERED ? SRC_FHS : SRC_GAUSS;
+    const bool rows_only = src != SRC_GAUSS;
+    Request rq = host_request(src, rows_only ? nullptr : mu.data(), rows_only ? nullptr : chol.data(), W.data(), nullptr, stats.data());
+    ask_horizons(rq, H != 0, H, hs, 0, nullptr, nullptr, H ? hz_stats.data() : nullptr, nullptr);
+    if (f == BOOT) rq.boot = &boot;
+    if (f == FILTERED) { rq.filt = &filt; rq.gv = &gv; }
+    if (f == JUMPS) { rq.jumps = true; rq.jp = &jp; }
+    if (f == REGIMES) { rq.regimes = true; rq.rs = &rs; }
+    if (f == GLIDE || f == GLIDE_CF) { rq.glide = true; rq.gl = &gl; }
+    if (f == GLIDE || f == GLIDE_CF || f == CASH) { rq.cash = true; rq.cf = f == GLIDE ? &no_cf : &cf; }
+    if (f == PROTECT) { rq.protect = true; rq.pi = &pt; }
+    if (f == OVERLAY) { rq.overlay = true; rq.ov = &ov; }
+    if (rq.cash || rq.protect) { rq.counts_out = counts.data(); rq.hz_counts_out = H ? hz_counts.data() : nullptr; }
+    EXPECT(check_request(&prm, rq, 4) == MCP_OK);
+    TileInputs in;
+    EXPECT(tile_inputs(&prm, rq, &in) == MCP_OK);
+    const int tiles[3][2] = {{0, K}, {0, K < 8 ? K : 8}, {8, K - 8}};     // the whole call; K = 9 also as tiles of 8 and 1
+    for (int t = 0; t < (K == 9 ? 3 : 1); t++) {
+      const int k0 = tiles[t][0], kt = tiles[t][1];
+      const TileLayout lay = tile_layout(&prm, rq, kt);
+      EXPECT(lay.base == mcp_packed_len(N, kt) && lay.base <= lay.load && lay.load <= lay.floor && lay.floor <= lay.total);
+      std::vector<float> block(lay.total);
+      std::vector<double> piv(kt), piv_hz((size_t)H * kt);
+      EXPECT(pack_tile(&prm, rq, in, k0, kt, block.data()) == MCP_OK);
+      block.resize(lay.floor + (rq.protect ? (size_t)T + 1 : 0));         // the thresholds behind the schedule may be -inf (no target)
+      EXPECT(finite(block));
+      EXPECT(request_pivots(&prm, rq, in, k0, kt, piv.data(), H ? piv_hz.data() : nullptr) == MCP_OK && finite(piv) && finite(piv_hz));
+    }
+    // one invalid request per feature and its documented code
+    mcp_params bad = prm;
+    mcp_bootstrap bad_boot = boot;
+    if (f == PLAIN) bad.flags = MCP_FLAG_FOLD | MCP_FLAG_NATIVE_MATH;      // the folded step needs the spec's normals
+    else if (f == BOOT) { bad_boot.mean_block = 0.5; rq.boot = &bad_boot; }  // the bootstrap compounds either way; b < 1 does not
+    else bad.compounding = MCP_COMPOUND_LOG;                              // every other feature compounds simply
+    EXPECT(check_request(&bad, rq, 4) == (f == BOOT ? MCP_E_ARG : MCP_E_UNSUPPORTED) && mcp_last_error()[0] != '\0');
+  }
+}
+
+int main() {
+  const int Ns[3] = {1, 5, MCP_MAX_ASSETS}, Ks[4] = {1, 8, 9, 17}, Hs[2] = {0, 2};
+  int n = 0;
+  for (int N : Ns)
+    for (int K : Ks)
+      for (int H : Hs) { run_shape(N, K, 12, H); n++; }
+  printf("host_selftest ok: %d shapes x %d requests\n", n, (int)N_FEATURES);
+  return 0;
+}

@@ -1,0 +1,204 @@
+// mcp_host.h -- the host code of libmcport.so that touches no device (mcp_host.cpp): every argument rule, every feature's host
+// constants, every closed-form pivot, the packers and the layout of a tile's parameter block.  Internal, not installed.  It
+// includes no device header, so that mcp_host.cpp also builds with a plain C++ compiler (make host-selftest).
+#pragma once
+#include <stddef.h>
+#include <stdint.h>
+
+#include <vector>
+
+#include "../../include/mcport.h"
+#include "../../include/mcport_protect.h"
+
+namespace mcp {
+constexpr int SWEEP_MIN_K = 17;      // from this many portfolios on the MFMA sweep kernels run
+}
+
+namespace mcph {
+
+using mcp::SWEEP_MIN_K;
+constexpr int KT_WIDE = 8;           // portfolios per pass of the KT=8 kernel
+constexpr int K_PAD = 512;           // W rows are zero-padded to a multiple of this (MFMA sweep tile: 32*MT)
+
+// Records the thread's last error (mcp_last_error) and returns `code`.
+int fail(int code, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
+
+inline int n4_of(int n) { return 4 * ((n + 3) / 4); }
+// floats of the regime-1 block [mu1 N4][L1 row pairs N4(N4/2+1)] (SPEC.md 4.13)
+inline size_t regime_block_len(int n) { const size_t n4 = (size_t)n4_of(n); return n4 + n4 * (n4 / 2 + 1); }
+// W rows are zero-padded to whole MFMA workgroups for a sweep, to whole KT_WIDE passes otherwise
+inline int kpad_of(int k) { return k >= SWEEP_MIN_K ? K_PAD * ((k + K_PAD - 1) / K_PAD) : KT_WIDE * ((k + KT_WIDE - 1) / KT_WIDE); }
+
+// The draws of a walk (SPEC.md 2): Gaussian steps mu + L z, rows of the bootstrap, Student-t steps mu + L s z, or filtered residual
+// rows scaled by the path's GARCH variance ratio (SPEC.md 2.4).
+enum Source { SRC_GAUSS, SRC_BOOT, SRC_T, SRC_FHS };
+
+// What one call asks of the walk: the draw source, optionally a rebalancing rule, the drawdown or horizons, and the host arrays
+// of an mcp_simulate* call (an mcp_launch_paths* call gives its device arrays in a Launch instead).
+struct Request {
+  Source src = SRC_GAUSS;
+  const float* mu = nullptr;            // SRC_GAUSS, SRC_T: the drift and the Cholesky factor
+  const float* chol = nullptr;
+  const mcp_bootstrap* boot = nullptr;  // SRC_BOOT (SPEC.md 2.1)
+  const mcp_student_t* st = nullptr;    // SRC_T (SPEC.md 2.2)
+  const mcp_filtered* filt = nullptr;   // SRC_FHS (SPEC.md 2.4): the rows, with the triple of SPEC.md 4.9 in `gv` (`garch` stays false)
+  bool rebalanced = false;              // SPEC.md 4.5: the rule `reb`
+  const mcp_rebalance* reb = nullptr;
+  bool cash = false;                    // SPEC.md 4.7: the schedule `cf`
+  const mcp_cashflow* cf = nullptr;
+  bool glide = false;                   // SPEC.md 4.14: the weight schedule `gl`, always with `cf` (mcp_simulate_glide)
+  const mcp_glide* gl = nullptr;
+  bool protect = false;                 // SPEC.md 4.15: the floor rule `pi` (mcp_simulate_protected)
+  const mcp_protect* pi = nullptr;
+  bool overlay = false;                 // SPEC.md 4.8: the option rows `ov`
+  const mcp_overlay* ov = nullptr;
+  bool garch = false;                   // SPEC.md 4.9: the variance recurrence `gv` (SRC_GAUSS or SRC_T)
+  const mcp_garch* gv = nullptr;
+  bool jumps = false;                   // SPEC.md 2.5 / 4.12: the market jump `jp` on top of SRC_GAUSS
+  const mcp_jumps* jp = nullptr;
+  bool regimes = false;                 // SPEC.md 2.6 / 4.13: two regimes `rs`, regime 0 on (mu, chol), on top of SRC_GAUSS
+  const mcp_regimes* rs = nullptr;
+  bool dd = false;                      // SPEC.md 4.2 / 5.1: the drawdown of every path
+  bool hz = false;                      // SPEC.md 4.3 / 5.2: the values after H steps, statistics at alpha and at L levels
+  int H = 0, L = 0;
+  const int32_t* steps = nullptr;
+  const double* levels = nullptr;
+  const float* W = nullptr;             // [K][N]
+  float* terminal_out = nullptr;        // outputs; the optional ones NULL when not asked for
+  mcp_stats* stats_out = nullptr;
+  float* mdd_out = nullptr;
+  mcp_stats* dd_stats_out = nullptr;
+  float* hz_out = nullptr;              // [H*K*n], row h*K + k
+  mcp_stats* hz_stats_out = nullptr;    // [H*K]
+  double* bands_out = nullptr;          // [H*K*L]
+  uint64_t* counts_out = nullptr;       // cash flows: [K][2] {n_ruined, n_short} (SPEC.md 5.6); protection: {n_gap, n_short} (5.15)
+  uint64_t* hz_counts_out = nullptr;    // [H*K][2]
+  bool attr = false;                    // SPEC.md 4.10 / 5.9: the second walk that attributes the risk to the assets
+  float* contrib_out = nullptr;         // NULL or host [K][N][n]
+  mcp_attr* attr_out = nullptr;         // [K][N]
+  uint64_t* attr_counts_out = nullptr;  // [K][2] {n, n_tail}
+  bool anti = false;                    // SPEC.md 2.3 / 5.10: antithetic pairs
+  mcp_pair* pair_out = nullptr;         // [K]
+  double* cross_out = nullptr;          // [K] the call's cross sums: every tile adds its shards' in shard order
+};
+
+// The row table of a request that walks rows: the bootstrap's own, or the residual rows of SRC_FHS.
+mcp_bootstrap rows_of(const Request& rq);
+Request host_request(Source src, const float* mu, const float* chol, const float* W, float* terminal_out, mcp_stats* stats_out);
+void ask_horizons(Request& rq, bool on, int H, const int32_t* steps, int L, const double* levels, float* out, mcp_stats* stats,
+                  double* bands);
+// The drawdown is asked for by its statistics: dd_stats_out != NULL
+void ask_drawdown(Request& rq, float* mdd_out, mcp_stats* dd_stats_out);
+
+// One launch of the path kernels for a request: the device arrays of an mcp_launch_paths* call or of one shard's part of a tile.
+struct Launch {
+  const float* d_packed = nullptr;
+  const double* d_pivot = nullptr;
+  uint64_t seed = 0, path_begin = 0, n_paths = 0;
+  float* d_terminal = nullptr;
+  uint64_t stride = 0;
+  float* d_mdd = nullptr;               // drawdown: [K][mdd_stride]
+  uint64_t mdd_stride = 0;
+  float* d_hz = nullptr;                // horizons: [H][K][hz_stride]
+  uint64_t hz_stride = 0;
+  const float* d_rows = nullptr;        // bootstrap: [R][N4], zero-padded
+  const float* d_flows = nullptr;       // cash flows: [n_steps]
+  const float* d_floor = nullptr;       // protection: [n_steps + 1] the floor schedule
+  const float* d_targets = nullptr;     // glide path: [n_breaks][glide_rows(K)][N4] target blocks (glide_pack)
+  const char* d_overlay = nullptr;      // overlay: [rows][row_begin N4 + 1][spot N4] (overlay_pack)
+  const float* d_loading = nullptr;     // jumps: [N4] loadings, zero-padded
+  const float* d_block1 = nullptr;      // regimes: [mu1 N4][L1 row pairs], the layout of mcp_pack_params
+  bool attr = false;                    // the attribution walk (SPEC.md 4.10): FAM_AT instead of the request's own family
+  const double* d_var = nullptr;        // attribution: [K] VaRs
+  double* d_cross = nullptr;            // antithetic pairs: [K][path_grid(n_paths / 2)] cross partials
+  double* d_attr_partials = nullptr;    // attribution: [K][path_grid(n_paths)][attr_record_len(N4)]
+  float* d_contrib = nullptr;           // attribution: NULL or [K][N][contrib_stride]
+  uint64_t contrib_stride = 0;
+  void* d_partials = nullptr;
+  void* d_hist = nullptr;
+  void* stream = nullptr;               // the device side casts it to its stream type
+};
+
+// ---- each feature's argument rules (SPEC.md sections as in mcp_host.cpp) ----
+int check_params(const mcp_params* p);
+int check_horizons(int n_steps, int H, const int32_t* steps);
+int check_levels(int L, const double* levels);
+int check_boot(const mcp_params* prm, const mcp_bootstrap* boot);
+int check_reb(const mcp_rebalance* reb);
+int check_student_t(const mcp_params* prm, const mcp_student_t* st);
+int check_garch(const mcp_params* prm, const mcp_garch* g);
+int check_jumps(int n_assets, const mcp_jumps* j);
+int check_regimes(int n_assets, const mcp_regimes* r);
+int check_filtered(const mcp_params* prm, const mcp_filtered* f);
+int check_cashflow(const mcp_params* prm, const mcp_cashflow* cf);
+int check_glide(const mcp_params* prm, const mcp_glide* gl);
+int check_protect(const mcp_params* prm, const mcp_protect* pt);
+int check_overlay(const mcp_params* prm, const mcp_overlay* ov);
+// Every rule a request meets: each feature's own arguments, then which features combine (MCP_E_UNSUPPORTED), then the outputs.
+// `ln`: an mcp_launch_paths* call, whose device arrays are checked instead of the host arrays of an mcp_simulate* call.
+int check_request(const mcp_params* prm, const Request& rq, uint64_t n_paths, const Launch* ln = nullptr, uint64_t path_begin = 0);
+
+// ---- each feature's host constants ----
+uint64_t boot_threshold(double b);
+void boot_moments(int N, const mcp_bootstrap* boot, const float* W, int K, double* m_out, double* s2_out);
+double boot_pivot(int compounding, int T, double m, double s2);
+struct GarchConsts { float a, b, g, omega, a_n; };
+GarchConsts garch_consts(const mcp_garch* g, int N);
+struct JumpConsts { uint32_t thr[MCP_MAX_JUMPS]; double mean_count; float m, s; };
+JumpConsts jump_consts(const mcp_jumps* j);
+void jump_drift(const mcp_jumps* j, const JumpConsts& c, int N, const float* mu, float* out);
+struct RegimeConsts { uint64_t thr01, thr10, thr_start; double p01, p10, start; };
+RegimeConsts regime_consts(const mcp_regimes* r);
+struct ProtectConsts { float m, b, rf, theta; };
+ProtectConsts protect_consts(const mcp_protect* pt);
+
+// ---- the closed-form pivots and their means ----
+void regime_pivots(int N, int K, int T, const float* mu0, const float* mu1, const RegimeConsts& c, const float* W, int H, const int32_t* steps,
+                   double* out_T, double* out_hz);
+void filt_means(int N, const mcp_filtered* f, double* out);
+void filt_pivots(int N, int K, int T, const double* me, const float* W, double* out);
+void overlay_pivots(int N, int K, int T, const mcp_overlay* ov, const float* mu, const float* W, int H, const int32_t* steps,
+                    double* out_T, double* out_hz);
+void reb_means(int N, const float* mu, const mcp_bootstrap* boot, double* out);
+void reb_pivots(int N, int K, int T, int m, const double* mu, const float* W, double* out);
+void cash_means(int N, int K, const float* mu, const mcp_bootstrap* boot, const float* W, double* out);
+void cash_pivots(int K, int T, const double* m, const float* flows, double v0, int H, const int32_t* steps, double* out_T, double* out_hz);
+void glide_means(int N, int K, int k0, int kt, const float* mu, const mcp_bootstrap* boot, const float* W, const mcp_glide* gl, double* out);
+void glide_pivots(int K, int T, int G, const int32_t* breaks, const double* m, const float* flows, double v0, int H, const int32_t* steps,
+                  double* out_T, double* out_hz);
+void protect_pivots(const mcp_params& prm, const mcp_protect* pt, const float* mu, const float* W, int K, int H, const int32_t* steps,
+                    double* out_T, double* out_hz);
+
+// ---- the packers of what a launch reads besides the packed block of mcp_pack_params ----
+size_t glide_rows(int kt);
+size_t glide_len(int N, int kt, const mcp_glide* gl);
+void glide_pack(int N, int K, int k0, int kt, const mcp_glide* gl, float* out);
+size_t protect_len(int T, int kt, int H);
+void protect_pack(int T, int kt, int H, const int32_t* steps, const mcp_protect* pt, float* out);
+size_t overlay_bytes(int N, int n_rows);
+void overlay_pack(int N, const mcp_overlay* ov, char* out);
+
+// ---- one tile of a checked request: the portfolios [k0, k0 + kt) of the call's W ----
+// Float offsets into the parameter block of a tile.  This is the only place that knows what follows the packed block.
+struct TileLayout {
+  size_t base;     // mcp_packed_len(N, kt): the end of the packed block
+  size_t load;     // where the jump loadings, the regime-1 block or the glide targets begin
+  size_t floor;    // where the protection schedule and the counts' thresholds begin (protect_pack)
+  size_t total;    // floats of the whole block
+};
+TileLayout tile_layout(const mcp_params* prm, const Request& rq, int kt);
+
+// What pack_tile and request_pivots need of the request that no tile changes; filled once per call by tile_inputs.
+struct TileInputs {
+  std::vector<float> zmu, zchol;   // bootstrap: no drift and no Cholesky factor in the packed block; filtered rows: no factor
+  std::vector<float> jmu;          // jumps: the compensated drift (SPEC.md 2.5)
+  std::vector<float> blk1;         // regimes: (mu1, chol1) packed as (mu, chol) are (SPEC.md 2.6)
+  std::vector<double> rmu;         // rebalancing: the draws' per-asset means (SPEC.md 5.4); filtered rows: mu_i + e_i (5.11)
+};
+int tile_inputs(const mcp_params* prm, const Request& rq, TileInputs* in);
+// The host block of one tile, out[tile_layout(prm, rq, kt).total]
+int pack_tile(const mcp_params* prm, const Request& rq, const TileInputs& in, int k0, int kt, float* out);
+// The tile's pivots at n_steps into out_T[kt] and at the request's horizons into out_hz[H*kt] (row h*kt + k; NULL without horizons)
+int request_pivots(const mcp_params* prm, const Request& rq, const TileInputs& in, int k0, int kt, double* out_T, double* out_hz);
+
+}  // namespace mcph

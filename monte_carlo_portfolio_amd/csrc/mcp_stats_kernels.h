@@ -4,6 +4,7 @@
 #include <stdint.h>
 
 #include "../../include/mcport.h"
+#include "mcp_host.h"
 #include "mcp_route.h"
 
 namespace mcp {
@@ -32,7 +33,6 @@ struct MomentPartial {
 static_assert(sizeof(MomentPartial) == 32, "MomentPartial is 32 bytes");
 
 constexpr int PATH_GRID_CAP = 8192;      // path-kernel blocks (K <= 16); tiles beyond are grid-strided
-constexpr int SWEEP_MIN_K = 17;          // from this many portfolios on the MFMA sweep kernels run
 constexpr int SWEEP_TILE_PATHS = 64;     // the sweep kernels contribute one MomentPartial per portfolio and 64-path wave tile
 
 // blocks of the one-lane-per-path kernels for n paths
