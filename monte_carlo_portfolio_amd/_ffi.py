@@ -115,6 +115,14 @@ class McpProtect(ctypes.Structure):
                 ("ratchet", ctypes.c_double), ("target", ctypes.c_void_p), ("reserved", ctypes.c_int32)]
 
 
+class McpSpending(ctypes.Structure):
+    """mcp_spending (include/mcport_spend.h): the rate, the largest cut and raise per review, the inflation per review, the optional
+    first withdrawal and target, and the review period of the spending rule of SPEC.md 4.16."""
+    _fields_ = [("rate", ctypes.c_double), ("down", ctypes.c_double), ("up", ctypes.c_double), ("inflation", ctypes.c_double),
+                ("first", ctypes.c_double), ("target", ctypes.c_double), ("every", ctypes.c_int32), ("has_first", ctypes.c_int32),
+                ("has_target", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
 class McpOverlay(ctypes.Structure):
     """mcp_overlay: the option rows of SPEC.md 4.8 -- rows [n_rows] of OVERLAY_ROW_DTYPE, row_begin int32 [N + 1], spot binary32 [N]."""
     _fields_ = [("rows", ctypes.c_void_p), ("row_begin", ctypes.c_void_p), ("spot", ctypes.c_void_p), ("n_rows", ctypes.c_int32),
@@ -217,6 +225,7 @@ ARG_GROUPS = {
     "st": [ctypes.POINTER(McpStudentT)], "gv": [ctypes.POINTER(McpGarch)], "jp": [ctypes.POINTER(McpJumps)],
     "rs": [ctypes.POINTER(McpRegimes)], "ft": [ctypes.POINTER(McpFiltered)], "ov": [ctypes.POINTER(McpOverlay)],
     "bt": [ctypes.POINTER(McpBootstrap)], "pt": [ctypes.POINTER(McpProtect)],
+    "sp": [ctypes.POINTER(McpSpending)], "wd": [_vp, _vp],     # withdrawn_out, wd_stats_out
     "mu": [_vp], "chol": [_vp], "W": [_vp], "mu*": [_f32p], "chol*": [_f32p], "W*": [_f32p],
     "walk": [_u64, _u64, _u64],                           # seed, path_begin, n_paths
     "hz_in": [_int, _vp, _int, _vp],                      # n_horizons, horizons, n_levels, levels
@@ -260,6 +269,18 @@ EXTENSION_SIGNATURES = {
     "mcp_protect_floor": (_int, [ctypes.c_double, ctypes.c_double, _int, _vp]),
 }
 EXTENSION_SIGNATURES.update((name, (_int, [t for g in groups for t in ARG_GROUPS[g]])) for name, groups in EXTENSION_ENTRIES.items())
+
+# The same pair of tables for include/mcport_spend.h: every extension header has its own, so that each header's test pins exactly
+# the symbols that header declares.
+SPEND_ENTRIES = {
+    "mcp_simulate_spending": "ctx prm sp mu chol bt st W walk hz_in out counts hz_out hz_counts wd",
+}
+SPEND_ENTRIES = {name: tuple(groups.split()) for name, groups in SPEND_ENTRIES.items()}
+SPEND_SIGNATURES = {
+    "mcp_spending_pivots": (_int, [_PP, ctypes.POINTER(McpSpending), _vp, ctypes.POINTER(McpBootstrap), _vp, _int, _vp, _vp, _vp, _vp]),
+    "mcp_spending_consts": (_int, [ctypes.POINTER(McpSpending), ctypes.c_double, _vp]),
+}
+SPEND_SIGNATURES.update((name, (_int, [t for g in groups for t in ARG_GROUPS[g]])) for name, groups in SPEND_ENTRIES.items())
 
 _LIB = None
 
@@ -325,7 +346,7 @@ def lib() -> ctypes.CDLL:
             fn = getattr(L, name)          # AttributeError if the ABI lost a symbol
             fn.restype = res
             fn.argtypes = args
-        for name, (res, args) in EXTENSION_SIGNATURES.items():
+        for name, (res, args) in list(EXTENSION_SIGNATURES.items()) + list(SPEND_SIGNATURES.items()):
             fn = getattr(L, name)          # additive entry points, detected by symbol: a library without them is too old
             fn.restype = res
             fn.argtypes = args
@@ -560,6 +581,38 @@ def protect_pivots(prm: McpParams, protect: McpProtect, mu: np.ndarray, W: np.nd
     check(lib().mcp_protect_pivots(ctypes.byref(prm), ctypes.byref(protect), ptr(mu32), ptr(W), 0 if hz is None else hz.size, ptr(hz),
                                    ptr(out), ptr(hout)))
     return out, hout
+
+
+def make_spending(rate: float, every: int, down: float, up: float, inflation: float = 0.0, first=None, target=None) -> McpSpending:
+    """mcp_spending of the spending rule of SPEC.md 4.16 (include/mcport_spend.h); first None: w0 = fl32(p32 fl32(v0)); target None:
+    no second count."""
+    return McpSpending(float(rate), float(down), float(up), float(inflation), 0.0 if first is None else float(first),
+                       0.0 if target is None else float(target), int(every), int(first is not None), int(target is not None), 0)
+
+
+def spending_consts(spending: McpSpending, v0: float) -> np.ndarray:
+    """binary32 [5] {p32, g32, lo32, hi32, w0}: the constants of the rule as the walk uses them (include/mcport_spend.h,
+    mcp_spending_consts), pure host arithmetic."""
+    out = np.zeros(5, np.float32)
+    check(lib().mcp_spending_consts(ctypes.byref(spending), float(v0), ptr(out)))
+    return out
+
+
+def spending_pivots(prm: McpParams, spending: McpSpending, W: np.ndarray, mu: np.ndarray | None = None, rows: np.ndarray | None = None,
+                    horizons=None):
+    """([K] pivots of V at n_steps, [H, K] at the horizons or None, [K] pivots of the total paid out): the spending rule on the mean
+    path (SPEC.md 5.16; include/mcport_spend.h, mcp_spending_pivots), pure host arithmetic.  Pass the drift `mu` (Gaussian and
+    Student-t draws) or the binary32 [R, N] `rows` (bootstrap draws)."""
+    W = np.ascontiguousarray(W, np.float32)
+    mu_p = np.ascontiguousarray(mu, np.float32) if mu is not None else None
+    bt = make_bootstrap(np.ascontiguousarray(rows, np.float32), 1.0) if rows is not None else None
+    hz = np.ascontiguousarray(horizons, np.int32) if horizons is not None and len(horizons) else None
+    out = np.zeros(W.shape[0], np.float64)
+    wout = np.zeros(W.shape[0], np.float64)
+    hout = np.zeros((hz.size, W.shape[0]), np.float64) if hz is not None else None
+    check(lib().mcp_spending_pivots(ctypes.byref(prm), ctypes.byref(spending), ptr(mu_p), ref(bt), ptr(W), 0 if hz is None else hz.size,
+                                    ptr(hz), ptr(out), ptr(hout), ptr(wout)))
+    return out, hout, wout
 
 
 def make_overlay(rows: np.ndarray, row_begin: np.ndarray, spot: np.ndarray) -> McpOverlay:

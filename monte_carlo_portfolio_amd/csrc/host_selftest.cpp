@@ -25,9 +25,9 @@ template <class T> static bool finite(const std::vector<T>& v) {
   return true;
 }
 
-enum Feature { PLAIN, BOOT, FILTERED, JUMPS, REGIMES, GLIDE_CF, GLIDE, PROTECT, CASH, OVERLAY, N_FEATURES };
+enum Feature { PLAIN, BOOT, FILTERED, JUMPS, REGIMES, GLIDE_CF, GLIDE, PROTECT, CASH, OVERLAY, SPEND, SPEND_BOOT, N_FEATURES };
 static const char* const k_names[N_FEATURES] = {"plain", "bootstrap", "filtered", "jumps", "regimes", "glide+flows", "glide",
-                                                "protect", "cash", "overlay"};
+                                                "protect", "cash", "overlay", "spend", "spend+bootstrap"};
 
 static void run_shape(int N, int K, int T, int H) {
   const int R = 6, G = 2;
@@ -62,6 +62,7 @@ static void run_shape(int N, int K, int T, int H) {
   const mcp_protect pt = {floor_s.data(), 3.0, 1.0, 0.001, 0.1, nullptr, 0};
   const mcp_overlay ov = {ov_rows.data(), row_begin.data(), spot.data(), 1, 0};
   const mcp_rebalance reb = {5, 0, 0.001};
+  const mcp_spending sp = {0.01, 0.1, HUGE_VAL, 0.02, 0.015, 0.9, 5, 1, 1, 0};
   const int32_t* hs = H ? steps.data() : nullptr;
 
   // every pure entry point, outputs of exactly the documented length
@@ -83,6 +84,11 @@ static void run_shape(int N, int K, int T, int H) {
   EXPECT(mcp_regime_pivots(&prm, &rs, mu.data(), W.data(), H, hs, pv.data(), hzp) == MCP_OK && finite(pv) && finite(hz));
   EXPECT(mcp_glide_pivots(&prm, &gl, &cf, mu.data(), nullptr, W.data(), H, hs, pv.data(), hzp) == MCP_OK && finite(pv) && finite(hz));
   EXPECT(mcp_protect_pivots(&prm, &pt, mu.data(), W.data(), H, hs, pv.data(), hzp) == MCP_OK && finite(pv) && finite(hz));
+  std::vector<double> wdp(K);
+  std::vector<float> c5(5);
+  EXPECT(mcp_spending_pivots(&prm, &sp, mu.data(), nullptr, W.data(), H, hs, pv.data(), hzp, wdp.data()) == MCP_OK && finite(pv) && finite(hz) && finite(wdp));
+  EXPECT(mcp_spending_pivots(&prm, &sp, nullptr, &boot, W.data(), H, hs, pv.data(), hzp, wdp.data()) == MCP_OK && finite(pv) && finite(hz) && finite(wdp));
+  EXPECT(mcp_spending_consts(&sp, prm.v0, c5.data()) == MCP_OK && std::isinf(c5[3]) && c5[4] == 0.015f);
   EXPECT(mcp_regime_consts(&rs, thr3.data(), p3.data()) == MCP_OK && finite(p3));
   EXPECT(mcp_jump_consts(&jp, N, mu.data(), jthr.data(), mean_count.data(), drift.data()) == MCP_OK && finite(mean_count) && finite(drift));
   EXPECT(mcp_percentile_rank(1000, 0.95, &rank[0], &rank[1], p3.data()) == MCP_OK && rank[1] == rank[0] + 1 && finite(p3));
@@ -93,17 +99,18 @@ static void run_shape(int N, int K, int T, int H) {
   std::vector<uint64_t> counts(2 * (size_t)K), hz_counts(2 * (size_t)H * K);
   for (int f = 0; f < N_FEATURES; f++) {
     snprintf(g_case, sizeof g_case, "%s, N=%d K=%d T=%d H=%d", k_names[f], N, K, T, H);
-    const Source src = f == BOOT ? SRC_BOOT : f == FILTERED ? SRC_FHS : SRC_GAUSS;
+    const Source src = f == BOOT || f == SPEND_BOOT ? SRC_BOOT : f == FILTERED ? SRC_FHS : SRC_GAUSS;
     const bool rows_only = src != SRC_GAUSS;
     Request rq = host_request(src, rows_only ? nullptr : mu.data(), rows_only ? nullptr : chol.data(), W.data(), nullptr, stats.data());
     ask_horizons(rq, H != 0, H, hs, 0, nullptr, nullptr, H ? hz_stats.data() : nullptr, nullptr);
-    if (f == BOOT) rq.boot = &boot;
+    if (f == BOOT || f == SPEND_BOOT) rq.boot = &boot;
     if (f == FILTERED) { rq.filt = &filt; rq.gv = &gv; }
     if (f == JUMPS) { rq.jumps = true; rq.jp = &jp; }
     if (f == REGIMES) { rq.regimes = true; rq.rs = &rs; }
     if (f == GLIDE || f == GLIDE_CF) { rq.glide = true; rq.gl = &gl; }
     if (f == GLIDE || f == GLIDE_CF || f == CASH) { rq.cash = true; rq.cf = f == GLIDE ? &no_cf : &cf; }
     if (f == PROTECT) { rq.protect = true; rq.pi = &pt; }
+    if (f == SPEND || f == SPEND_BOOT) { rq.cash = rq.spend = true; rq.cf = &no_cf; rq.sp = &sp; rq.wd_stats_out = stats.data(); }
     if (f == OVERLAY) { rq.overlay = true; rq.ov = &ov; }
     if (rq.cash || rq.protect) { rq.counts_out = counts.data(); rq.hz_counts_out = H ? hz_counts.data() : nullptr; }
     EXPECT(check_request(&prm, rq, 4) == MCP_OK);
@@ -120,6 +127,10 @@ static void run_shape(int N, int K, int T, int H) {
       block.resize(lay.floor + (rq.protect ? (size_t)T + 1 : 0));         // the thresholds behind the schedule may be -inf (no target)
       EXPECT(finite(block));
       EXPECT(request_pivots(&prm, rq, in, k0, kt, piv.data(), H ? piv_hz.data() : nullptr) == MCP_OK && finite(piv) && finite(piv_hz));
+      if (rq.spend) {
+        request_wd_pivots(&prm, rq, k0, kt, piv.data());
+        EXPECT(finite(piv));
+      }
     }
     // one invalid request per feature and its documented code
     mcp_params bad = prm;

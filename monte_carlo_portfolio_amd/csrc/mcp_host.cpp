@@ -385,6 +385,35 @@ int check_protect(const mcp_params* prm, const mcp_protect* pt) {
   if (!((float)prm->v0 > 0.0f)) return fail(MCP_E_ARG, "v0=%g rounds to zero in binary32", prm->v0);
   return MCP_OK;
 }
+// SPEC.md 4.16: the binary32 constants of a spending request; w0 without `first` is fl32(p32 fl32(v0)), the product in binary64 (exact)
+SpendConsts spend_consts(const mcp_spending* sp, double v0) {
+  const float p = (float)sp->rate;
+  return SpendConsts{p, (float)(1.0 + sp->inflation), (float)(1.0 - sp->down), (float)(1.0 + sp->up),
+                     sp->has_first ? (float)sp->first : (float)((double)p * (double)(float)v0)};
+}
+// SPEC.md 4.16: rate finite >= 0, every >= 0, down in [0, 1], up in [0, +inf] (+inf allowed), inflation finite > -1, first finite >= 0,
+// a finite target, each rule before and after rounding to binary32; flags 0 / 1, reserved == 0, fl32(v0) > 0
+int check_spending(double v0, const mcp_spending* sp) {
+  if (!sp) return fail(MCP_E_ARG, "spending is NULL");
+  if (sp->reserved != 0) return fail(MCP_E_ARG, "spending reserved=%d must be 0", sp->reserved);
+  if (sp->has_first != 0 && sp->has_first != 1) return fail(MCP_E_ARG, "has_first=%d must be 0 or 1", sp->has_first);
+  if (sp->has_target != 0 && sp->has_target != 1) return fail(MCP_E_ARG, "has_target=%d must be 0 or 1", sp->has_target);
+  if (sp->every < 0) return fail(MCP_E_ARG, "spending every=%d must be >= 0", sp->every);
+  if (!((float)v0 > 0.0f) || !std::isfinite((float)v0)) return fail(MCP_E_ARG, "v0=%g must be positive and finite in binary32", v0);
+  const SpendConsts c = spend_consts(sp, v0);
+  if (!std::isfinite(sp->rate) || !(sp->rate >= 0.0) || !std::isfinite(c.p)) return fail(MCP_E_ARG, "spending rate=%g must be finite and >= 0, also in binary32", sp->rate);
+  if (!(sp->down >= 0.0 && sp->down <= 1.0) || !(c.lo >= 0.0f && c.lo <= 1.0f)) return fail(MCP_E_ARG, "spending down=%g outside [0, 1]", sp->down);
+  if (!(sp->up >= 0.0) || !(c.hi >= 1.0f)) return fail(MCP_E_ARG, "spending up=%g must be >= 0 (+inf allowed)", sp->up);
+  if (!std::isfinite(sp->inflation) || !(sp->inflation > -1.0) || !((float)sp->inflation > -1.0f) || !(c.g > 0.0f) || !std::isfinite(c.g))
+    return fail(MCP_E_ARG, "spending inflation=%g must be finite and > -1, also in binary32", sp->inflation);
+  if (sp->has_first && (!std::isfinite(sp->first) || !(sp->first >= 0.0) || !std::isfinite(c.w0)))
+    return fail(MCP_E_ARG, "spending first=%g must be finite and >= 0, also in binary32", sp->first);
+  if (!std::isfinite(c.w0)) return fail(MCP_E_ARG, "spending rate=%g times v0=%g overflows binary32", sp->rate, v0);
+  if (sp->has_target && (!std::isfinite(sp->target) || !std::isfinite((float)sp->target)))
+    return fail(MCP_E_ARG, "spending target=%g must be finite, also in binary32", sp->target);
+  return MCP_OK;
+}
+
 // What follows the packed block (and the jump loadings) of a protected launch: the schedule S_0 .. S_T, then per stored row -- the kt
 // terminal rows, then the H*kt horizon rows -- the two thresholds {S_h, target or -inf} of the counts (SPEC.md 5.15)
 size_t protect_len(int T, int kt, int H) { return (size_t)T + 1 + 2 * (size_t)kt * (size_t)(1 + H); }
@@ -551,6 +580,18 @@ int check_request(const mcp_params* prm, const Request& rq, uint64_t n_paths, co
       return fail(MCP_E_UNSUPPORTED, "a glide path is not combined with the drawdown, rebalancing, the overlay, GARCH, jumps, regimes, "
                                      "filtered rows, the attribution or antithetic pairs");
     if (ln) return fail(MCP_E_UNSUPPORTED, "glide paths are not wired into mcp_launch_paths*");
+  }
+  if (rq.spend) {                                              // SPEC.md 4.16: the rules, then what a spending rule is not combined with
+    if ((rc = check_spending(prm->v0, rq.sp))) return rc;
+    if (!ln && !rq.wd_stats_out) return fail(MCP_E_ARG, "wd_stats_out is NULL");
+    if (prm->compounding != MCP_COMPOUND_SIMPLE) return fail(MCP_E_UNSUPPORTED, "paths with a spending rule compound simply (no log compounding)");
+    if (prm->flags & (MCP_FLAG_FOLD | MCP_FLAG_NATIVE_MATH))
+      return fail(MCP_E_UNSUPPORTED, "paths with a spending rule run on the unfolded recurrence and the spec's normals (no MCP_FLAG_FOLD / MCP_FLAG_NATIVE_MATH)");
+    if (!rq.cash || rq.glide || rq.protect || rq.src == SRC_FHS || rq.rebalanced || rq.overlay || rq.garch || rq.jumps || rq.regimes || rq.dd ||
+        rq.attr || rq.anti)
+      return fail(MCP_E_UNSUPPORTED, "a spending rule is not combined with a cash-flow schedule, a glide path, floor protection, the drawdown, "
+                                     "rebalancing, the overlay, GARCH, jumps, regimes, filtered rows, the attribution or antithetic pairs");
+    if (ln) return fail(MCP_E_UNSUPPORTED, "spending rules are not wired into mcp_launch_paths*");
   }
   if (rq.protect) {                                            // SPEC.md 4.15: the rules, then what the protection is not combined with
     if ((rc = check_protect(prm, rq.pi))) return rc;
@@ -769,6 +810,39 @@ void cash_pivots(int K, int T, const double* m, const float* flows, double v0, i
   }
 }
 
+// SPEC.md 5.16: the spending rule on the mean path -- cash_pivots with the flow -wbar, wbar reviewed as the walk reviews w, on the
+// doubles of the binary32 constants; out_wd[k] is the pivot of the total paid out (NULL: not asked for).  every = 0, or g = lo = hi = 1,
+// is cash_pivots on c_s = -w0 operation for operation.
+void spend_pivots(int K, int T, const double* m, const SpendConsts& c, int every, double v0, int H, const int32_t* steps, double* out_T,
+                  double* out_hz, double* out_wd) {
+  const auto pivot = [v0](double A) {
+    const double x = (A > 0.0 ? A : 0.0) / v0 - 1.0;
+    return std::isfinite(A) && std::isfinite(x) ? x : 0.0;
+  };
+  const double p = (double)c.p, gi = (double)c.g, lo = (double)c.lo, hi = (double)c.hi;
+  for (int k = 0; k < K; k++) {
+    const double g = 1.0 + m[k];
+    double A = v0, w = (double)c.w0, Y = 0.0;
+    int h = 0, nr = every >= 1 ? every : 0;
+    for (int s = 1; s <= T; s++) {
+      A = A * g;
+      A = A + (-w);
+      Y = Y + w;
+      if (h < H && steps[h] == s) out_hz[(size_t)(h++) * K + k] = pivot(A);
+      if (nr && s == nr) {
+        const double wp = w * gi;
+        w = std::fmin(std::fmax(p * (A > 0.0 ? A : 0.0), wp * lo), wp * hi);
+        nr += every;
+      }
+    }
+    if (out_T) out_T[k] = pivot(A);
+    if (out_wd) {
+      const double x = Y / v0 - 1.0;
+      out_wd[k] = std::isfinite(x) ? x : 0.0;
+    }
+  }
+}
+
 // SPEC.md 5.14: cash_pivots with the per-step mean of the step's segment.  m[g*K + k]: the mean of portfolio k on the weights of
 // block g = 0 .. G (block 0: the call's W); step s walks on block #{j : breaks[j] < s}.  flows NULL: c_s = +0.  G = 0, or equal
 // means in every block, is cash_pivots operation for operation.
@@ -877,6 +951,10 @@ int request_pivots(const mcp_params* prm, const Request& rq, const TileInputs& i
   const double v0 = (double)(float)prm->v0;
   if (rq.protect) {                                            // SPEC.md 5.15: every pivot in closed form
     protect_pivots(*prm, rq.pi, rq.mu, Wt, kt, H, rq.steps, out_T, out_hz);
+  } else if (rq.spend) {                                       // SPEC.md 5.16: the rule on the mean path gives T and every horizon
+    std::vector<double> cm((size_t)kt);
+    cash_means(N, kt, rq.mu, boot, Wt, cm.data());
+    spend_pivots(kt, T, cm.data(), spend_consts(rq.sp, prm->v0), rq.sp->every, v0, H, rq.steps, out_T, out_hz, nullptr);
   } else if (rq.glide) {                                       // SPEC.md 5.14: one walk gives T and every horizon
     std::vector<double> cm((size_t)(rq.gl->n_breaks + 1) * kt);
     glide_means(N, prm->n_portfolios, k0, kt, rq.mu, boot, rq.W, rq.gl, cm.data());
@@ -914,6 +992,12 @@ int request_pivots(const mcp_params* prm, const Request& rq, const TileInputs& i
     }
   }
   return MCP_OK;
+}
+
+void request_wd_pivots(const mcp_params* prm, const Request& rq, int k0, int kt, double* out_wd) {
+  std::vector<double> cm((size_t)kt);
+  cash_means(prm->n_assets, kt, rq.mu, rq.src == SRC_BOOT ? rq.boot : nullptr, rq.W + (size_t)k0 * prm->n_assets, cm.data());
+  spend_pivots(kt, prm->n_steps, cm.data(), spend_consts(rq.sp, prm->v0), rq.sp->every, (double)(float)prm->v0, 0, nullptr, nullptr, nullptr, out_wd);
 }
 
 }  // namespace mcph
@@ -1163,6 +1247,34 @@ int mcp_protect_floor(double floor0, double rate, int n_steps, float* out) {
     out[t + 1] = std::fmaf(out[t], r, out[t]);
     if (!std::isfinite(out[t + 1])) return fail(MCP_E_ARG, "the floor schedule overflows binary32 at step %d", t + 1);
   }
+  return MCP_OK;
+}
+
+int mcp_spending_pivots(const mcp_params* prm, const mcp_spending* sp, const float* mu, const mcp_bootstrap* boot, const float* W,
+                        int n_horizons, const int32_t* horizons, double* pivots_out, double* hz_pivots_out, double* wd_pivots_out) {
+  if (int rc = check_params(prm)) return rc;
+  if (int rc = check_spending(prm->v0, sp)) return rc;
+  if ((mu == nullptr) == (boot == nullptr)) return fail(MCP_E_ARG, "exactly one of mu and boot");
+  if (boot)
+    if (int rc = check_boot(prm, boot)) return rc;
+  if (!W || !pivots_out || !wd_pivots_out) return fail(MCP_E_ARG, "NULL pointer");
+  if (n_horizons != 0) {
+    if (int rc = check_horizons(prm->n_steps, n_horizons, horizons)) return rc;
+    if (!hz_pivots_out) return fail(MCP_E_ARG, "hz_pivots_out is NULL");
+  }
+  if (prm->compounding != MCP_COMPOUND_SIMPLE) return fail(MCP_E_UNSUPPORTED, "paths with a spending rule compound simply (no log compounding)");
+  std::vector<double> m((size_t)prm->n_portfolios);
+  cash_means(prm->n_assets, prm->n_portfolios, mu, boot, W, m.data());
+  spend_pivots(prm->n_portfolios, prm->n_steps, m.data(), spend_consts(sp, prm->v0), sp->every, (double)(float)prm->v0, n_horizons, horizons,
+               pivots_out, hz_pivots_out, wd_pivots_out);
+  return MCP_OK;
+}
+
+int mcp_spending_consts(const mcp_spending* sp, double v0, float* out) {
+  if (int rc = check_spending(v0, sp)) return rc;
+  if (!out) return fail(MCP_E_ARG, "out is NULL");
+  const SpendConsts c = spend_consts(sp, v0);
+  out[0] = c.p; out[1] = c.g; out[2] = c.lo; out[3] = c.hi; out[4] = c.w0;
   return MCP_OK;
 }
 

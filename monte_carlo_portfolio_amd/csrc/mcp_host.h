@@ -9,6 +9,7 @@
 
 #include "../../include/mcport.h"
 #include "../../include/mcport_protect.h"
+#include "../../include/mcport_spend.h"
 
 namespace mcp {
 constexpr int SWEEP_MIN_K = 17;      // from this many portfolios on the MFMA sweep kernels run
@@ -50,6 +51,8 @@ struct Request {
   const mcp_glide* gl = nullptr;
   bool protect = false;                 // SPEC.md 4.15: the floor rule `pi` (mcp_simulate_protected)
   const mcp_protect* pi = nullptr;
+  bool spend = false;                   // SPEC.md 4.16: the spending rule `sp`, always with `cash` on an all-zero `cf` that carries the
+  const mcp_spending* sp = nullptr;     // rule's target (mcp_simulate_spending)
   bool overlay = false;                 // SPEC.md 4.8: the option rows `ov`
   const mcp_overlay* ov = nullptr;
   bool garch = false;                   // SPEC.md 4.9: the variance recurrence `gv` (SRC_GAUSS or SRC_T)
@@ -73,6 +76,8 @@ struct Request {
   double* bands_out = nullptr;          // [H*K*L]
   uint64_t* counts_out = nullptr;       // cash flows: [K][2] {n_ruined, n_short} (SPEC.md 5.6); protection: {n_gap, n_short} (5.15)
   uint64_t* hz_counts_out = nullptr;    // [H*K][2]
+  float* wd_out = nullptr;              // spending rule: NULL or host [K*n] Y_T (SPEC.md 4.16)
+  mcp_stats* wd_stats_out = nullptr;    // [K]
   bool attr = false;                    // SPEC.md 4.10 / 5.9: the second walk that attributes the risk to the assets
   float* contrib_out = nullptr;         // NULL or host [K][N][n]
   mcp_attr* attr_out = nullptr;         // [K][N]
@@ -99,6 +104,8 @@ struct Launch {
   uint64_t stride = 0;
   float* d_mdd = nullptr;               // drawdown: [K][mdd_stride]
   uint64_t mdd_stride = 0;
+  float* d_wd = nullptr;                // spending rule: [K][wd_stride] Y_T
+  uint64_t wd_stride = 0;
   float* d_hz = nullptr;                // horizons: [H][K][hz_stride]
   uint64_t hz_stride = 0;
   const float* d_rows = nullptr;        // bootstrap: [R][N4], zero-padded
@@ -133,6 +140,7 @@ int check_filtered(const mcp_params* prm, const mcp_filtered* f);
 int check_cashflow(const mcp_params* prm, const mcp_cashflow* cf);
 int check_glide(const mcp_params* prm, const mcp_glide* gl);
 int check_protect(const mcp_params* prm, const mcp_protect* pt);
+int check_spending(double v0, const mcp_spending* sp);
 int check_overlay(const mcp_params* prm, const mcp_overlay* ov);
 // Every rule a request meets: each feature's own arguments, then which features combine (MCP_E_UNSUPPORTED), then the outputs.
 // `ln`: an mcp_launch_paths* call, whose device arrays are checked instead of the host arrays of an mcp_simulate* call.
@@ -151,6 +159,8 @@ struct RegimeConsts { uint64_t thr01, thr10, thr_start; double p01, p10, start; 
 RegimeConsts regime_consts(const mcp_regimes* r);
 struct ProtectConsts { float m, b, rf, theta; };
 ProtectConsts protect_consts(const mcp_protect* pt);
+struct SpendConsts { float p, g, lo, hi, w0; };
+SpendConsts spend_consts(const mcp_spending* sp, double v0);
 
 // ---- the closed-form pivots and their means ----
 void regime_pivots(int N, int K, int T, const float* mu0, const float* mu1, const RegimeConsts& c, const float* W, int H, const int32_t* steps,
@@ -168,6 +178,8 @@ void glide_pivots(int K, int T, int G, const int32_t* breaks, const double* m, c
                   double* out_T, double* out_hz);
 void protect_pivots(const mcp_params& prm, const mcp_protect* pt, const float* mu, const float* W, int K, int H, const int32_t* steps,
                     double* out_T, double* out_hz);
+void spend_pivots(int K, int T, const double* m, const SpendConsts& c, int every, double v0, int H, const int32_t* steps, double* out_T,
+                  double* out_hz, double* out_wd);
 
 // ---- the packers of what a launch reads besides the packed block of mcp_pack_params ----
 size_t glide_rows(int kt);
@@ -200,5 +212,7 @@ int tile_inputs(const mcp_params* prm, const Request& rq, TileInputs* in);
 int pack_tile(const mcp_params* prm, const Request& rq, const TileInputs& in, int k0, int kt, float* out);
 // The tile's pivots at n_steps into out_T[kt] and at the request's horizons into out_hz[H*kt] (row h*kt + k; NULL without horizons)
 int request_pivots(const mcp_params* prm, const Request& rq, const TileInputs& in, int k0, int kt, double* out_T, double* out_hz);
+// SPEC.md 5.16: the tile's pivots of the total paid out into out_wd[kt] (a spending request only)
+void request_wd_pivots(const mcp_params* prm, const Request& rq, int k0, int kt, double* out_wd);
 
 }  // namespace mcph

@@ -58,6 +58,15 @@
                             // state: at 6 waves (80 VGPRs) the N = 16 kernels reloaded one spilled pair inside the step loop; at 5 none does.  On
                             // the GARCH walk it fits in 80 and keeps MCP_MIN_WAVES (profiles/protect_isa.txt)
 #endif
+#ifndef MCP_MIN_WAVES_SP
+#define MCP_MIN_WAVES_SP 6  // the spending kernel (N <= 16, one portfolio) carries the withdrawal w and the payout Y on top of the cash-flow
+                            // kernel's state: unbounded it took 83 VGPRs (5 waves); at 6, the most the 25 KiB of LDS admit, it gets 80 and no listing shows
+                            // scratch in the loop over t (profiles/spend_isa.txt)
+#endif
+#ifndef MCP_MIN_WAVES_SP8
+#define MCP_MIN_WAVES_SP8 4 // the same for 8 portfolios, N <= 16, 16 registers on top of the cash-flow kernel's: unbounded it took 110-115
+                            // VGPRs (4 waves); at 5 (96) the Student-t kernel reloads spilled registers inside the loop over t, at 4 nothing spills
+#endif
 #ifndef MCP_MIN_WAVES_ANTI
 #define MCP_MIN_WAVES_ANTI 5 // the antithetic kernels (N <= 16, one portfolio) carry the second member's V, row-pair accumulator and rho (and
                             // peak and drawdown) next to the first's: see profiles/antithetic_isa.txt
@@ -99,7 +108,7 @@ __device__ __forceinline__ const __attribute__((address_space(4))) A* kernarg() 
 MCP_HAS_MEMBER(hz) MCP_HAS_MEMBER(mdd) MCP_HAS_MEMBER(bt) MCP_HAS_MEMBER(st) MCP_HAS_MEMBER(gv) MCP_HAS_MEMBER(cf)
 MCP_HAS_MEMBER(ov) MCP_HAS_MEMBER(at) MCP_HAS_MEMBER(period) MCP_HAS_MEMBER(pr)
 MCP_HAS_MEMBER(fh) MCP_HAS_MEMBER(p_hi) MCP_HAS_MEMBER(jp) MCP_HAS_MEMBER(rs) MCP_HAS_MEMBER(gp)
-MCP_HAS_MEMBER(pi)
+MCP_HAS_MEMBER(pi) MCP_HAS_MEMBER(sp)
 #undef MCP_HAS_MEMBER
 
 struct PathArgs {
@@ -350,6 +359,26 @@ struct GlideArgs {
 // Arguments of mc_paths_glide_kernel: those of mc_paths_cf_kernel and the glide block, read where it is needed (kernarg).
 struct PathArgsGP : PathArgsCF { GlideArgs gp; };
 
+// The spending rule of SPEC.md 4.16: per path and portfolio the walk carries the per-step withdrawal w (from w0) and the total paid out
+// Y (from +0) next to V.  Every step pays w out of U0 = fma(V, rho, V), the step of ruin what is left; after every `every`-th step the
+// review moves w to p32 V, held between lo32 and hi32 times the inflated w.  The constants are wave-uniform and read inside the
+// review, w0 once per tile, the output where it is written.
+struct SpendArgs {
+  float p32, g32, lo32, hi32, w0;     // binary32: rate, 1 + inflation, 1 - down, 1 + up (may be +inf), the first withdrawal
+  int32_t every;                      // review after the steps s with s mod every == 0; 0: never
+  float* __restrict__ wd;             // [K][wd_stride] Y_T
+  uint64_t wd_stride;
+};
+// Arguments of mc_paths_spend_kernel: those of mc_paths_cf_kernel (the schedule is not read) and the spending block.
+struct PathArgsSP : PathArgsCF { SpendArgs sp; };
+// The spending block of a spend kernel's launch, read where it is used (kernarg).
+typedef const __attribute__((address_space(4))) SpendArgs* cspend_p;
+template <class A>
+__device__ __forceinline__ cspend_p spend_args(const A&) {
+  if constexpr (has_sp<A>::value) return &kernarg<A>()->sp;
+  else return nullptr;
+}
+
 // Floor protection (SPEC.md 4.15): CPPI with an exposure cap and a drawdown ratchet.  Per path and portfolio the walk carries V and the
 // peak M (both from v0); step t holds E = fmaxf(fminf(fl32(m (V - F)), fl32(b V)), +0) in the risky portfolio, F = fmaxf(S_t,
 // fl32(theta M)), and V - E at the riskless rate: V' = fma(E, rho, fma(V - E, rf, V)).  `floor` is the schedule S_0 .. S_T behind the
@@ -438,6 +467,7 @@ struct PathLaunchArgs {
   RegimeArgs rs;
   GlideArgs gp;
   ProtectArgs pi;
+  SpendArgs sp;
 };
 template <class A>
 inline A make_args(const PathLaunchArgs& s) {
@@ -458,6 +488,7 @@ inline A make_args(const PathLaunchArgs& s) {
   if constexpr (has_rs<A>::value) x.rs = s.rs;
   if constexpr (has_gp<A>::value) x.gp = s.gp;
   if constexpr (has_pi<A>::value) x.pi = s.pi;
+  if constexpr (has_sp<A>::value) x.sp = s.sp;
   if constexpr (has_p_hi<A>::value) { x.p_hi = (uint32_t)(s.hz.path_begin >> 32); x.pad = 0u; }
   return x;
 }
@@ -563,20 +594,23 @@ constexpr int PATH_BLOCK = 256;
 // walk's weight pointer moves to the next target block at the breaks of the glide path, wave-uniform events merged with the horizons
 // as the rebalancing walk merges its dates; the step itself is the cash-flow kernel's (SPEC.md 4.14).  PI (with HZ): the walk also
 // carries the peak M of V, and the update of V holds only the exposure E of the floor rule in the risky portfolio, the rest at the
-// riskless rate (SPEC.md 4.15).  Every kernel
+// riskless rate (SPEC.md 4.15).  SP (with CF and HZ): the flow of the step is the path's own withdrawal w instead of the schedule's c_s,
+// the walk also carries w and the total paid out Y, and the reviews of w are wave-uniform events merged with the horizons as the glide
+// walk merges its breaks (SPEC.md 4.16).  Every kernel
 // below is the body in mcp_paths_body.inc under its own flags F: it names the flags it sets, the rest are PathFlagsOff's.  F is a
 // local class, which may not have static data members, so it sets its flags as enumerators of an `enum : bool`; they hide the
 // defaults' names and read as the same constant expressions.
 struct PathFlagsOff {
   static constexpr bool NATIVE = false, FOLD = false, LOGC = false, DD = false, HZ = false, BOOT = false, BLDS = false, REB = false,
                         STT = false, CF = false, OV = false, GV = false, AT = false, ANTI = false, FH = false, UHI = false, JP = false, RS = false,
-                        GP = false, PI = false;
+                        GP = false, PI = false, SP = false;
 };
 
 // __launch_bounds__ 2nd argument of a path kernel: the MCP_MIN_WAVES* above for N <= 16 and one path per lane, by the kind of
 // state the kernel carries; MCP_MIN_WAVES_BIG for 16 < N <= 64 and one portfolio; otherwise unbounded.
-enum BoundsKind { BK_PATHS, BK_REB, BK_CF, BK_OV, BK_AT, BK_ANTI, BK_PI };
+enum BoundsKind { BK_PATHS, BK_REB, BK_CF, BK_OV, BK_AT, BK_ANTI, BK_PI, BK_SP };
 constexpr int min_waves(BoundsKind kind, int NB, int KT, int PPT) {
+  if (kind == BK_SP) return (NB <= 4 && PPT == 1) ? (KT == 1 ? MCP_MIN_WAVES_SP : MCP_MIN_WAVES_SP8) : (KT == 1 && PPT == 1) ? MCP_MIN_WAVES_BIG : 1;
   if (kind == BK_ANTI) return (NB <= 4 && PPT == 1 && KT == 1) ? MCP_MIN_WAVES_ANTI : 1;
   if (NB <= 4 && PPT == 1 && KT == 1)
     return kind == BK_REB ? MCP_MIN_WAVES_REB : kind == BK_OV ? MCP_MIN_WAVES_OV : kind == BK_AT ? MCP_MIN_WAVES_AT
@@ -739,6 +773,17 @@ __global__ void MCP_BOUNDS(BK_CF) mc_paths_cf_kernel(const PathArgsCF a) {
 template <int NB, int KT, int PPT, bool BOOT_, bool BLDS_, bool STT_>
 __global__ void MCP_BOUNDS(BK_CF) mc_paths_glide_kernel(const PathArgsGP a) {
   struct F : PathFlagsOff { enum : bool { HZ = true, CF = true, GP = true, BOOT = BOOT_, BLDS = BLDS_, STT = STT_ }; };
+#include "mcp_paths_body.inc"
+}
+
+// The spending kernel (SPEC.md 4.16): mc_paths_cf_kernel with the path's own withdrawal in place of the schedule.  The segmented walk
+// ends a segment at the next horizon, the next review or T; at a horizon V is stored, at a review w moves, the store first when they
+// share a step.  every = 0 is the cash-flow kernel's walk on c_s = -w0.  V_T keeps the fused epilogue; Y_T is stored next to it and
+// reduced by the non-fused passes.  Launch bounds of its own: the kernel carries 2 KT registers more than its twin
+// (profiles/spend_isa.txt).
+template <int NB, int KT, int PPT, bool BOOT_, bool BLDS_, bool STT_>
+__global__ void MCP_BOUNDS(BK_SP) mc_paths_spend_kernel(const PathArgsSP a) {
+  struct F : PathFlagsOff { enum : bool { HZ = true, CF = true, SP = true, BOOT = BOOT_, BLDS = BLDS_, STT = STT_ }; };
 #include "mcp_paths_body.inc"
 }
 

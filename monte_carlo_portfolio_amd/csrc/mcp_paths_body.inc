@@ -5,7 +5,7 @@
 // derived from it) and the kernel argument `a` (PathArgs or a struct that starts with one).
   constexpr bool NATIVE = F::NATIVE, FOLD = F::FOLD, LOGC = F::LOGC, DD = F::DD, HZ = F::HZ, BOOT = F::BOOT, BLDS = F::BLDS, REB = F::REB,
                  STT = F::STT, CF = F::CF, OV = F::OV, GV = F::GV, AT = F::AT, ANTI = F::ANTI, FH = F::FH, UHI = F::UHI, JP = F::JP, RS = F::RS,
-                 GP = F::GP, PI = F::PI;
+                 GP = F::GP, PI = F::PI, SP = F::SP;
   static_assert(!UHI || (KT == 1 && PPT == 1 && !(NATIVE || FOLD || DD || HZ || BOOT || REB || STT || CF || OV || GV || AT || ANTI || FH || JP || RS || PI)),
                 "uniform high counter word: the plain Gaussian walk of one portfolio only");
   static_assert(!FH || (BOOT && HZ && !(LOGC || REB || CF || STT || GV || OV || AT || DD || PI)), "filtered rows: the bootstrap's segmented walk only");
@@ -17,6 +17,8 @@
                 "glide path: the cash-flow kernel's segmented walk only");
   static_assert(!PI || (HZ && (JP || (STT && GV)) && !(NATIVE || FOLD || LOGC || BOOT || REB || CF || OV || AT || ANTI || FH || UHI || RS || GP)),
                 "floor protection: the segmented GARCH or jump walk, simple compounding only");
+  static_assert(!SP || (CF && HZ && !(NATIVE || FOLD || LOGC || DD || REB || OV || GV || AT || ANTI || FH || UHI || JP || RS || GP || PI)),
+                "spending rule: the cash-flow kernel's segmented walk only");
   constexpr int N4 = 4 * NB;
   // ANTI (SPEC.md 2.3): a lane's PPT draws feed EM = 2 PPT members -- slot e < PPT walks on z[e], slot PPT + e on -z[e]; p, live and
   // the counters are per draw (a.path_begin and a.n_paths count pairs), the members 2 p and 2 p + 1 are adjacent in the output rows
@@ -142,6 +144,7 @@
     f32x2 At[PPT][N4 / 2];                                // AT: the assets' contributions A_i of SPEC.md 4.10
     uint32_t rg[PPT];                                     // RS: the regime of the next step (SPEC.md 2.6); s_0 is drawn in step 0
     float Mk[EM][KT];                                     // PI: the running peak M of SPEC.md 4.15, V_0 included
+    float Wd[PPT][KT], Yk[PPT][KT];                       // SP: the per-step withdrawal w and the total paid out Y of SPEC.md 4.16
 #pragma unroll
     for (int e = 0; e < PPT; e++) {
       p[e] = tl * tile + (uint64_t)e * PATH_BLOCK + threadIdx.x;
@@ -153,6 +156,11 @@
       if constexpr (PI) {
 #pragma unroll
         for (int k = 0; k < KT; k++) Mk[e][k] = a.v0;
+      }
+      if constexpr (SP) {
+        const float w0 = spend_args(a)->w0;               // one scalar load per tile
+#pragma unroll
+        for (int k = 0; k < KT; k++) { Wd[e][k] = w0; Yk[e][k] = 0.0f; }
       }
       if constexpr (BOOT) jrow[e] = 0u;                   // replaced at t = 0 (a restart)
       if constexpr (GV) gh[e] = garch_args(a)->h0;        // one scalar load per tile
@@ -302,6 +310,52 @@
           gi++;
         }
       }
+    } else if constexpr (SP) {
+      // SPEC.md 4.16: the walk in segments that end at the events -- the next horizon, the next review nr, T -- with the step body
+      // unchanged between them.  At a horizon V_h is stored as below; at a review (s mod every == 0, s < T: the review at T moves no
+      // output) w' = fl32(w g32) and w = fminf(fmaxf(fl32(p32 V), fl32(w' lo32)), fl32(w' hi32)), on every lane -- a ruined path's w
+      // is never paid; the store first when they share a step.  The period, the four constants and the horizons are read where they
+      // are needed (kernarg), wave-uniform; every branch below is on wave-uniform values, and the next review is an addition.
+      int nr;                                              // the next review (s mod every == 0, s < T), T if none is left
+      {
+        const int per = spend_args(a)->every;
+        nr = (per >= 1 && per < T) ? per : T;
+      }
+      int t = 0, hi = 0;
+      while (t < T) {
+        const auto gs = kernarg<PathArgsSP>();
+        const int t_hz = hi < gs->n_horizons ? gs->steps[hi] : T;
+        const int t_end = min(min(t_hz, nr), T);
+        for (; t < t_end; t++) {
+#include "mcp_paths_step.inc"
+        }
+        const auto hs = kernarg<PathArgsSP>();
+        if (hi < hs->n_horizons && hs->steps[hi] <= t) {   // V_h of SPEC.md 4.3, after the withdrawal of step h (the host checked the
+                                                           // list: the step is t; `<=` so that every pass consumes an event or steps)
+          float* const row = hs->hz + (size_t)(hi * a.n_portfolios + a.k_begin) * hs->hz_stride;
+#pragma unroll
+          for (int e = 0; e < PPT; e++)
+            if (live[e]) {
+#pragma unroll
+              for (int k = 0; k < KT; k++)
+                if (k < kt) row[(size_t)k * hs->hz_stride + p[e]] = V[e][k];
+            }
+          hi++;
+        }
+        if (t == nr && t < T) {                            // a review, after the store
+          const cspend_p sk = spend_args(a);
+          const float s_p = sk->p32, s_g = sk->g32, s_lo = sk->lo32, s_hi = sk->hi32;
+#pragma unroll
+          for (int e = 0; e < PPT; e++)
+#pragma unroll
+            for (int k = 0; k < KT; k++) {
+              const float wp = Wd[e][k] * s_g;
+              Wd[e][k] = fminf(fmaxf(s_p * V[e][k], wp * s_lo), wp * s_hi);
+            }
+          const int per = sk->every;
+          nr = per < T - t ? t + per : T;
+        }
+      }
     } else if constexpr (HZ) {
       // SPEC.md 4.3: segment i runs the steps [h_{i-1}, h_i) with the unchanged step body and ends in one coalesced store
       // per live path and portfolio into row i*K + k of the horizon array; the last segment runs on to T.  The horizon
@@ -406,6 +460,11 @@
 #pragma unroll
           for (int k = 0; k < KT; k++)
             if (k < kt) dk->mdd[(size_t)(a.k_begin + k) * dk->mdd_stride + p[e]] = Qk[e][k];
+        } else if constexpr (SP) {                         // Y_T of SPEC.md 4.16, next to V_T
+          const cspend_p sk = spend_args(a);
+#pragma unroll
+          for (int k = 0; k < KT; k++)
+            if (k < kt) sk->wd[(size_t)(a.k_begin + k) * sk->wd_stride + p[e]] = Yk[e][k];
         } else if constexpr (DD) {                         // the drawdown output, read from the kernel arguments here only
           const auto dk = kernarg<PathArgsDD>();
 #pragma unroll

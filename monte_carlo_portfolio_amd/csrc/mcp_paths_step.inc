@@ -17,7 +17,8 @@
 // counter stream 4 before the asset normals gives the step's regime s_t and the next step's; the row pair's chain runs on (mu, L) where the
 // wave has a lane in regime 0 and then, under `if (s_t)`, on (mu1, L1) -- each a whole chain of its own, nothing shared (SPEC.md 2.6 / 4.13).  UHI: the same step with p_hi a scalar (philox4x32_10_uhi), the drift read through the LDS address
 // par_lds instead of the opaque zero offset, and the blocks scheduled one at a time.  PI: the update of V is the floor rule of SPEC.md
-// 4.15 on the step's rho, then the peak M.
+// 4.15 on the step's rho, then the peak M.  SP (with CF): the flow is the path's own -w, and the step adds what it pays out to Y
+// (SPEC.md 4.16); the reviews of w are events of the walk, not of the step.
       float rho[EM][KT];
       float fsh[PPT];                                  // FH: the shock s_j of the step's row (SPEC.md 2.4)
       if constexpr (BOOT) {
@@ -326,7 +327,23 @@
       }
       }  // !FOLD
       }  // !BOOT
-      if constexpr (CF) {
+      if constexpr (SP) {
+        // SPEC.md 4.16: U0 = fma(V, rho, V), U = U0 - w, live = V > 0 and U > 0; the step pays w, the step of ruin what is left of a
+        // positive U0, every later step +0; V = live ? U : +0 -- a NaN U0 is ruin and pays +0.  No schedule is read.  V is +0 or
+        // positive and w >= +0, always: at V = +0, U0 is +0 or NaN and U is not positive, so `U > 0` alone is `live`, and where the
+        // path is not live fmaxf(U0, +0) is the payment in every case (IEEE maxNum: +0 for a NaN; a -0 adds nothing to Y >= +0).
+        // One compare per value instead of three: the masks of eight portfolios would not fit the SGPRs beside the Cholesky factor.
+#pragma unroll
+        for (int e = 0; e < PPT; e++)
+#pragma unroll
+          for (int k = 0; k < KT; k++) {
+            const float u0 = fma32(V[e][k], rho[e][k], V[e][k]);
+            const float u = u0 - Wd[e][k];
+            const bool lv = u > 0.0f;
+            Yk[e][k] = Yk[e][k] + (lv ? Wd[e][k] : fmaxf(u0, 0.0f));
+            V[e][k] = lv ? u : 0.0f;
+          }
+      } else if constexpr (CF) {
         // SPEC.md 4.7: U = fma(V, rho, V), U = U + c_s (two roundings), V = (V > 0 and U > 0) ? U : +0 -- a NaN U is ruin too
         const float cs = cash_flow(a, t);
 #pragma unroll

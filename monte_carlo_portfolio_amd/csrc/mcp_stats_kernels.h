@@ -68,13 +68,14 @@ struct PathLaunchArgs;
 // and horizon families: Gaussian draws plus the market jump of SPEC.md 2.5, simple compounding), and rs (the regime-switching kernels
 // of the same three families: Gaussian draws on the drift and factor of the path's regime, SPEC.md 2.6, simple compounding), and
 // gp (FAM_CF only: the glide-path kernel, the cash-flow walk on scheduled target weights, SPEC.md 4.14), and pi (the floor-protection
-// kernel of SPEC.md 4.15: FAM_DD with the drawdown, else FAM_HZ, H = 0 included; stt and gv both set for the GARCH walk, or jp).
+// kernel of SPEC.md 4.15: FAM_DD with the drawdown, else FAM_HZ, H = 0 included; stt and gv both set for the GARCH walk, or jp), and
+// sp (FAM_CF only: the spending kernel, the cash-flow walk on the path's own withdrawal, SPEC.md 4.16).
 // The one ladder of mcp_paths_inst.hip maps it to a kernel and lists which selectors have one.
 constexpr int LEAN_MAX_NB = 4;
 enum PathFamily { FAM_PLAIN, FAM_DD, FAM_HZ, FAM_REB, FAM_CF, FAM_OV, FAM_AT };
 struct PathKernel {
   int family;
-  bool logc, boot, blds, stt, dd, gv, kt8, native, fold, anti, fh, uhi, jp, rs, gp, pi;
+  bool logc, boot, blds, stt, dd, gv, kt8, native, fold, anti, fh, uhi, jp, rs, gp, pi, sp;
 };
 
 // mcp_paths_inst.hip (one translation unit per NB): every pass of the kernel that `k` selects, on the blocks of `args` that the

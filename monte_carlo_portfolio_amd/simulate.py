@@ -25,6 +25,8 @@ _CTX: dict[tuple, "Context"] = {}
 # sentence that refuses a keyword the entry point has no argument group for (None: a plain one naming the entry point and the
 # keyword).  A new feature adds its row here, its groups to _ffi.SIMULATE_ENTRIES and its keyword to _KEYWORD_GROUP.
 _ENTRY_CHOICE = (
+    (("spending",), "mcp_simulate_spending", "spending is not combined with cashflow, glide, protect, drawdown, rebalance, overlay, garch, "
+                                             "jumps, regimes, filtered rows, attribution or antithetic"),
     (("protect",), "mcp_simulate_protected", "protect is not combined with overlay, cashflow, rebalance, bootstrap or filtered rows, regimes, "
                                              "glide, attribution or antithetic"),
     (("glide",), "mcp_simulate_glide", "glide is not combined with drawdown, rebalance, overlay, garch, attribution, antithetic, jumps, "
@@ -52,7 +54,7 @@ _ENTRY_CHOICE = (
 # the argument group of _ffi.SIMULATE_ENTRIES that carries each feature keyword of Context._call
 _KEYWORD_GROUP = {"rows": "bt", "dof": "st", "period": "rb", "drawdown": "dd", "horizons": "hz_in", "flows": "cf", "overlay": "ov",
                   "garch": "gv", "attribution": "attr", "antithetic": "pairs", "filtered": "ft", "jumps": "jp", "regimes": "rs",
-                  "glide": "gl", "protect": "pt"}
+                  "glide": "gl", "protect": "pt", "spending": "sp"}
 
 
 class Context:
@@ -100,8 +102,8 @@ class Context:
     def _call(self, prm: _ffi.McpParams, W, seed: int, path_begin: int, n_paths: int, store: bool, mu=None, chol=None, rows=None,
               block: float = 1.0, dof=None, period=None, cost: float = 0.0, drawdown: bool = False, horizons=None, levels=(),
               flows=None, target=None, overlay=None, garch=None, attribution=False, antithetic=False, filtered=None, jumps=None, regimes=None,
-              glide=None, protect=None):
-        """The one library call behind every simulate_* method: floor protection (protect: the (floor, multiplier, rate, cap, ratchet) of check_protect; `target` is then its second count), two regimes (regimes: the (p01, p10, start, mu1, chol1) of check_regimes), market jumps (jumps: the (intensity, mean, std, loading or None) of check_jumps), GARCH volatility (garch: the (alpha, beta, h0) of check_garch), an option overlay (overlay: the triple of check_overlay), cash flows (flows, target), Student-t draws (dof), rebalancing
+              glide=None, protect=None, spending=None):
+        """The one library call behind every simulate_* method: a spending rule (spending: the (rate, every, down, up, inflation, first or None) of check_spending; `target` is then its second count), floor protection (protect: the (floor, multiplier, rate, cap, ratchet) of check_protect; `target` is then its second count), two regimes (regimes: the (p01, p10, start, mu1, chol1) of check_regimes), market jumps (jumps: the (intensity, mean, std, loading or None) of check_jumps), GARCH volatility (garch: the (alpha, beta, h0) of check_garch), an option overlay (overlay: the triple of check_overlay), cash flows (flows, target), Student-t draws (dof), rebalancing
         (period, cost), bootstrap rows (rows, block) or Gaussian draws (mu, chol), with the drawdown or horizons.  Allocates the
         outputs that were asked for and passes NULL for the rest -> _Outputs, None where not asked for (terminal, qd,
         horizon_terminal: with `store` only; counts, hz_counts: with `flows` only; attr [K, N] records of ATTR_DTYPE and attr_counts
@@ -114,10 +116,10 @@ class Context:
                                    ("overlay", overlay is not None), ("garch", garch is not None), ("attribution", attribution),
                                    ("antithetic", antithetic), ("filtered", filtered is not None), ("jumps", jumps is not None),
                                    ("regimes", regimes is not None), ("glide", glide is not None),
-                                   ("protect", protect is not None)) if on]
+                                   ("protect", protect is not None), ("spending", spending is not None)) if on]
         has = set(given).issuperset
         entry, refusal = next((e, r) for needs, e, r in _ENTRY_CHOICE if has(needs))
-        groups = _ffi.SIMULATE_ENTRIES[entry] if entry in _ffi.SIMULATE_ENTRIES else _ffi.EXTENSION_ENTRIES[entry]
+        groups = next(t[entry] for t in (_ffi.SIMULATE_ENTRIES, _ffi.EXTENSION_ENTRIES, _ffi.SPEND_ENTRIES) if entry in t)
         # the library states the rules (check_request); a keyword the entry point has no argument for is refused here, not dropped
         for kw in given:
             if _KEYWORD_GROUP[kw] not in groups:
@@ -144,11 +146,14 @@ class Context:
         attr = np.zeros((K, N), _ffi.ATTR_DTYPE) if "attr" in groups else None
         attr_counts = np.zeros((K, 2), np.uint64) if "attr_counts" in groups else None
         contrib = np.empty((K, N, n_paths), np.float32) if "contrib" in groups and store else None
+        wd_stats = np.zeros(K, _ffi.STATS_DTYPE) if "wd" in groups else None
+        withdrawn = np.empty((K, n_paths), np.float32) if "wd" in groups and store else None
         vals = {"ctx": (self._h,), "prm": (prm,), "mu": (mu,), "chol": (chol,), "W": (W,), "walk": (seed, path_begin, n_paths),
                 "hz_in": (H, steps if H else None, L, lv if L else None), "out": (term, stats), "dd": (raw, dd_stats),
                 "hz_out": (hz_term, hz_stats, bands if L else None), "counts": (counts,), "hz_counts": (hz_counts,), "pairs": (pairs,),
                 "contrib": (contrib,), "attr": (attr,), "attr_counts": (attr_counts,), "bt": (bt,),
                 "pt": (_ffi.make_protect(*protect, target=target) if protect is not None else None,),
+                "sp": (_ffi.make_spending(*spending, target=target) if spending is not None else None,), "wd": (withdrawn, wd_stats),
                 "gl": (_ffi.make_glide(*glide) if glide is not None else None,),               # flows None: the all-zero schedule
                 "cf": (_ffi.make_cashflow(flows, target) if flows is not None else None,),
                 "rb": (_ffi.McpRebalance(int(period), 0, float(cost)) if period is not None else None,),
@@ -165,7 +170,8 @@ class Context:
             return ctypes.byref(v) if isinstance(v, ctypes.Structure) else v
         rc = getattr(_ffi.lib(), entry)(*(arg(g, v) for g in groups for v in vals[g.rstrip("*")]))
         _ffi.check(rc)
-        return _Outputs(stats, dd_stats, hz_stats, bands, term, raw, hz_term, counts, hz_counts, attr, attr_counts, contrib, pairs)
+        return _Outputs(stats, dd_stats, hz_stats, bands, term, raw, hz_term, counts, hz_counts, attr, attr_counts, contrib, pairs,
+                        wd_stats, withdrawn)
 
     def simulate(self, prm: _ffi.McpParams, mu, chol, W, seed: int, path_begin: int, n_paths: int, store: bool):
         o = self._call(prm, W, seed, path_begin, n_paths, store, mu=mu, chol=chol)
@@ -304,6 +310,16 @@ class Context:
         return self._call(prm, W, seed, path_begin, n_paths, store, mu=mu, chol=chol, dof=dof, garch=garch, jumps=jumps, target=target,
                           drawdown=drawdown, horizons=horizons, levels=levels, protect=(floor,) + tuple(float(v) for v in protect[1:5]))
 
+    def simulate_spending(self, prm: _ffi.McpParams, spending, W, seed: int, path_begin: int, n_paths: int, store: bool, mu=None,
+                          chol=None, rows=None, block: float = 1.0, dof=None, target=None, horizons=None, levels=()):
+        """simulate_cashflow() with a withdrawal that depends on the path in place of the schedule (SPEC.md 4.16 / 5.16;
+        include/mcport_spend.h, mcp_simulate_spending; simple compounding only): `spending` is (rate, every, down, up[, inflation[,
+        first]]), first None: rate times v0.  Draws as simulate_cashflow -> _Outputs with counts [K, 2] uint64 {n_ruined, n_short},
+        hz_counts [H, K, 2], wd_stats [K] (the record of the total paid out Y_T) and, with `store`, withdrawn [K, n_paths] binary32."""
+        sp = tuple(spending) + (0.0, None)[len(tuple(spending)) - 4:]
+        return self._call(prm, W, seed, path_begin, n_paths, store, mu=mu, chol=chol, rows=rows, block=block, dof=dof, target=target,
+                          horizons=horizons, levels=levels, spending=sp)
+
     def simulate_overlay(self, prm: _ffi.McpParams, overlay, mu, chol, W, seed: int, path_begin: int, n_paths: int, store: bool,
                          dof=None, drawdown: bool = False, horizons=None, levels=()):
         """simulate() / simulate_drawdown() / simulate_horizons() / simulate_student_t() with the option rows `overlay` (the (rows,
@@ -318,9 +334,10 @@ class Context:
 # binary32 arrays (terminal [K, n], qd [K, n], horizon_terminal [H, K, n]); with cash flows the counts {n_ruined, n_short} of
 # SPEC.md 5.6 (counts [K, 2], hz_counts [H, K, 2], uint64).
 # With attribution the records of SPEC.md 5.9 (attr [K, N] of ATTR_DTYPE, attr_counts [K, 2] uint64 {n, n_tail}) and, stored, the
-# binary32 contributions [K, N, n].  With antithetic pairs the records of SPEC.md 5.10 (pairs [K] of PAIR_DTYPE).
+# binary32 contributions [K, N, n].  With antithetic pairs the records of SPEC.md 5.10 (pairs [K] of PAIR_DTYPE).  With a spending rule
+# the record of the total paid out (wd_stats [K]) and, stored, the binary32 withdrawn [K, n] (SPEC.md 5.16).
 _Outputs = collections.namedtuple("_Outputs", "stats dd_stats hz_stats bands terminal qd horizon_terminal counts hz_counts attr "
-                                  "attr_counts contributions pairs", defaults=(None, None, None, None, None, None))
+                                  "attr_counts contributions pairs wd_stats withdrawn", defaults=(None,) * 8)
 
 
 def check_cashflow(cashflow, target, n_steps):
@@ -468,6 +485,84 @@ def _protect_blocks(pv, counts, hz_counts, n, target):
                                "n_short": c[:, 1].astype(np.int64), "shortfall_probability": c[:, 1].astype(np.float64) / n}
         out.append(blk)
     return out
+
+
+def check_spending(spending, v0=1.0):
+    """SPEC.md 4.16 argument rules -> None (no spending rule) or (rate, every, down, up, inflation, first or None).  `spending` is
+    (rate, every, down, up[, inflation[, first]]), inflation 0 and first None (rate times v0) by default (spending.spending_rule
+    builds the three named policies).  rate: the fraction of the current value aimed at per step, finite, >= 0; every: review every
+    that many whole steps, >= 0, 0 never; down in [0, 1] and up in [0, inf], inf allowed: the largest cut and raise per review;
+    inflation: finite, > -1, applied per review; first: the first withdrawal in currency, finite, >= 0.  ValueError for anything
+    else: not such a tuple, bools, a value outside its range before or after rounding to binary32, v0 that is not positive in
+    binary32."""
+    if spending is None:
+        return None
+    msg = f"spending must be (rate, every, down, up[, inflation[, first]]), got {spending!r}"
+    if isinstance(spending, (str, bytes)) or not hasattr(spending, "__len__") or not 4 <= len(spending) <= 6:
+        raise ValueError(msg)
+    vals = list(spending) + [0.0, None][len(spending) - 4:]
+    rate, every, down, up, inflation, first = vals
+    if isinstance(every, (bool, np.bool_)) or not isinstance(every, (int, np.integer)):
+        raise ValueError(f"spending every must be a whole number of steps (no bools, no floats), got {every!r}")
+    if not 0 <= int(every) <= 2 ** 31 - 1:
+        raise ValueError(f"spending every must be >= 0, got {every!r}")
+    nums = [rate, down, up, inflation] + ([first] if first is not None else [])
+    if any(isinstance(v, (bool, np.bool_)) for v in nums):
+        raise ValueError(msg)
+    try:
+        rate, down, up, inflation = (float(v) for v in nums[:4])
+        first = None if first is None else float(first)
+    except (TypeError, ValueError):
+        raise ValueError(msg) from None
+    with np.errstate(over="ignore", invalid="ignore"):
+        f32 = lambda v: float(np.float32(v))   # noqa: E731
+        if not (np.isfinite(rate) and rate >= 0.0 and np.isfinite(f32(rate))):
+            raise ValueError(f"spending rate must be finite and >= 0, in binary32 too, got {rate!r}")
+        if not (0.0 <= down <= 1.0):
+            raise ValueError(f"spending down must be in [0, 1], got {down!r}")
+        if not up >= 0.0:
+            raise ValueError(f"spending up must be >= 0 (inf allowed), got {up!r}")
+        if not (np.isfinite(inflation) and inflation > -1.0 and f32(inflation) > -1.0 and f32(1.0 + inflation) > 0.0 and np.isfinite(f32(1.0 + inflation))):
+            raise ValueError(f"spending inflation must be finite and > -1, in binary32 too, got {inflation!r}")
+        if first is not None and not (np.isfinite(first) and first >= 0.0 and np.isfinite(f32(first))):
+            raise ValueError(f"spending first must be finite and >= 0, in binary32 too, got {first!r}")
+        v32 = f32(v0)
+        if not (v32 > 0.0 and np.isfinite(v32)):
+            raise ValueError(f"spending needs a v0 that is positive and finite in binary32, got {v0!r}")
+        if first is None and not np.isfinite(f32(f32(rate) * v32)):
+            raise ValueError(f"spending rate {rate!r} times v0 {v0!r} overflows binary32")
+    return rate, int(every), down, up, inflation, first
+
+
+def _spending_blocks(sv, v0, out, n, target):
+    """The 'spending' block of every portfolio: the binary32 constants as used, the ruined and the short paths (with horizons, per
+    horizon too) and 'withdrawn', the record of x_Y = Y_T / fl32(v0) - 1 with its mean / var / cvar also as multiples of v0."""
+    p32, g32, lo32, hi32, w0 = (float(c) for c in _ffi.spending_consts(_ffi.make_spending(*sv), v0))
+    blocks = []
+    for k in range(out.counts.shape[0]):
+        blk = {"rate": p32, "every": sv[1], "growth": g32, "lo": lo32, "hi": hi32, "first": w0, "target": target}
+        blk.update(_cash_block(out.counts[k], n, target))
+        if out.hz_counts is not None:
+            blk["horizons"] = _cash_block(out.hz_counts[:, k, :], n, target)
+        wd = stats_to_dict(out.wd_stats[k])
+        wd.update({f + "_v0": wd[f] + 1.0 for f in ("mean", "var", "cvar")})
+        blk["withdrawn"] = wd
+        blocks.append(blk)
+    return blocks
+
+
+def _spending_result(out, sv, v0, single, store, as_array, steps, levels, compounding, target):
+    """What simulate_paths / simulate_bootstrap return for a spending call: with as_array the tuple of the call without the rule, then
+    counts[, hz_counts], wd_stats[, withdrawn]; else the dicts of _result with the 'spending' block and, with `store`, 'withdrawn'."""
+    res = _result(out._replace(counts=None, hz_counts=None), single, store, as_array, steps, levels, compounding)
+    if as_array:
+        return ((res if isinstance(res, tuple) else (res,)) + ((out.counts,) if out.hz_counts is None else (out.counts, out.hz_counts))
+                + ((out.wd_stats, out.withdrawn) if store else (out.wd_stats,)))
+    for k, (d, blk) in enumerate(zip([res] if isinstance(res, dict) else res, _spending_blocks(sv, v0, out, int(out.stats[0]["n"]), target))):
+        d["spending"] = blk
+        if store:
+            d["withdrawn"] = out.withdrawn[k]
+    return res
 
 
 def check_overlay(overlay, spot, n_assets):
@@ -788,6 +883,10 @@ def antithetic_to_dict(rec) -> dict:
 # checked, so the same rule wins when two apply.  The C side states the same rules for the library (check_request).
 _FLAGS = ("drawdown", "attribution", "antithetic", "fold", "native_math")
 _PATHS_COMBINE = {
+    "spending": ("spending needs the cashflow walk without a schedule -- constant weights, simple compounding, the spec's normals and the "
+                 "unfolded recurrence",
+                 ("cashflow", "glide", "protect", "drawdown", "rebalance", "overlay", "garch", "jumps", "regimes", "attribution", "antithetic",
+                  "fold", "native_math", "compounding='log'"), True),
     "protect": ("protect needs constant weights, simple compounding, the spec's normals and the unfolded recurrence",
                 ("rebalance", "cashflow", "overlay", "regimes", "glide", "attribution", "antithetic", "fold", "native_math",
                  "compounding='log'"), True),
@@ -819,6 +918,8 @@ _PATHS_COMBINE = {
 }
 # simulate_bootstrap: the same two features on observed rows
 _BOOTSTRAP_COMBINE = {
+    "spending": ("spending needs the cashflow walk without a schedule, constant weights and simple compounding",
+                 ("cashflow", "glide", "rebalance", "compounding='log'"), True),
     "glide": ("glide needs the cashflow walk and simple compounding", ("rebalance", "compounding='log'"), False),
     "cashflow": ("cashflow needs simple compounding and constant weights", ("rebalance", "compounding='log'"), False),
 }
@@ -845,7 +946,7 @@ def simulate_paths(mu, cov, weights, n_steps=252, n_paths=10_000, seed=0, v0=1.0
                    native_math=False, as_array=False, fold=False, shard="auto", context=None, drawdown=False,
                    horizons=None, bands=(), rebalance=None, rebalance_cost=0.0, dof=None, cashflow=None, target=None,
                    overlay=None, spot=None, garch=None, attribution=False, antithetic=False, jumps=None, regimes=None, glide=None,
-                   protect=None):
+                   protect=None, spending=None):
     """Simulate `n_paths` correlated return paths and reduce them to risk statistics.
 
     mu [N], cov [N,N] are per-step mean and covariance (the reference's `mean_returns`, `cov_matrix`
@@ -1002,13 +1103,34 @@ def simulate_paths(mu, cov, weights, n_steps=252, n_paths=10_000, seed=0, v0=1.0
     drawdown or horizons / bands, store, target, as_array and devices.  Not built: protect with rebalance, cashflow, overlay,
     regimes, glide, attribution, antithetic, fold, native_math or compounding="log" (ValueError), on bootstrap or filtered rows, in
     simulate_sweep, in PathEngine and at the mcp_launch_* level.
+
+    spending=None (default): the only withdrawals are cashflow's, fixed before the first draw.  spending=(rate, every, down, up[,
+    inflation[, first]]): a withdrawal that reacts to the path (SPEC.md 4.16 / 5.16).  Every step pays out the current amount w, from
+    `first` (default rate times v0); every `every` steps w is inflated by `inflation` and then moved to rate times the current
+    value, but cut by at most the share `down` and raised by at most the share `up` (inf: no ceiling).  every=0 or down=up=0 is the
+    constant inflation-adjusted amount ("4 % rule"), every=1, down=1, up=inf the fixed percentage of the value, anything between a
+    floor-and-ceiling rule (spending.spending_rule names the three).  Ruin is absorbing as in cashflow; the step of ruin pays out
+    what is left.  `target` is then the rule's second count.  The result has the shape of the call without it plus 'spending'
+    {rate, every, growth, lo, hi, first (binary32 as used), target, n_ruined, ruin_probability[, n_short, shortfall_probability],
+    horizons {the same per horizon}, withdrawn {the mcp_stats fields of x_Y = Y_T / v0 - 1 at alpha, and mean_v0 / var_v0 / cvar_v0 =
+    x + 1, the payout as a multiple of v0}} and, with store=True, 'withdrawn' float32 [n_paths], the total paid out per path;
+    as_array appends counts[, hz_counts], wd_stats[, withdrawn].  With every=0 the values are those of cashflow=-first bit for bit.
+    spending.spending_law is the exact law of the pure percentage rule.  Combines with dof, horizons / bands, target, store, as_array,
+    devices and bootstrap rows (simulate_bootstrap).  Not built: spending with cashflow, glide, protect, drawdown, rebalance, overlay,
+    garch, jumps, regimes, attribution, antithetic, fold, native_math or compounding="log" (ValueError), on filtered rows, in
+    simulate_sweep, in PathEngine and at the mcp_launch_* level.
     """
-    kw = dict(protect=protect, glide=glide, regimes=regimes, jumps=jumps, antithetic=antithetic, attribution=attribution, garch=garch, overlay=overlay,
+    kw = dict(spending=spending, protect=protect, glide=glide, regimes=regimes, jumps=jumps, antithetic=antithetic, attribution=attribution, garch=garch, overlay=overlay,
               cashflow=cashflow, dof=dof, rebalance=rebalance, drawdown=drawdown, horizons=horizons, fold=fold, native_math=native_math,
               compounding=compounding, shard=shard)
+    sv = check_spending(spending, v0)
+    _check_combines(_PATHS_COMBINE, "spending", kw)
     pv = check_protect(protect, n_steps, v0)
     _check_combines(_PATHS_COMBINE, "protect", kw)
     goal = None
+    if sv is not None and target is not None:              # the target of a spending call is the rule's second count
+        goal = check_cashflow(0.0, target, n_steps)[1]
+        target = None
     if pv is not None and target is not None:              # the target of a protected call is the second count's, not a cash-flow goal
         goal = check_cashflow(0.0, target, n_steps)[1]
         target = None
@@ -1057,9 +1179,12 @@ def simulate_paths(mu, cov, weights, n_steps=252, n_paths=10_000, seed=0, v0=1.0
     prm, ctx = _setup(mu32.shape[0], n_steps, W.shape[0], compounding, v0, alpha, rf, native_math, fold, devices,
                       "paths" if attribution or antithetic else shard, context)
     out = ctx._call(prm, W, int(seed), int(path_begin), int(n_paths), store, mu=mu32, chol=L, dof=dof, period=period, cost=cost,
-                    drawdown=drawdown, horizons=steps, levels=levels, flows=flows, target=target if pv is None else goal, overlay=ov,
-                    garch=gv, attribution=bool(attribution), antithetic=bool(antithetic), jumps=jv, regimes=rv, glide=gl, protect=pv)
-    if pv is not None:                                     # the counts are the 'protect' block's, not a 'cashflow' block's
+                    drawdown=drawdown, horizons=steps, levels=levels, flows=flows, target=target if pv is None and sv is None else goal,
+                    overlay=ov, garch=gv, attribution=bool(attribution), antithetic=bool(antithetic), jumps=jv, regimes=rv, glide=gl, protect=pv,
+                    spending=sv)
+    if sv is not None:                                     # the counts are the 'spending' block's, not a 'cashflow' block's
+        res = _spending_result(out, sv, v0, np.asarray(weights).ndim == 1, store, as_array, steps, levels, compounding, goal)
+    elif pv is not None:                                     # the counts are the 'protect' block's, not a 'cashflow' block's
         res = _result(out._replace(counts=None, hz_counts=None), np.asarray(weights).ndim == 1, store, as_array, steps, levels, compounding)
         if as_array:
             res = (res if isinstance(res, tuple) else (res,)) + ((out.counts,) if out.hz_counts is None else (out.counts, out.hz_counts))
@@ -1151,7 +1276,7 @@ def _result(out, single, store, as_array, steps, levels, compounding, flows=None
     then (hz_stats, bands) or dd_stats, then with `store` terminal and horizon_terminal or max_drawdown); else one dict per
     portfolio (one dict for a single weight vector) with its 'drawdown' / 'horizons' blocks and, with `store`, the stored arrays."""
     stats, dd_stats, hz_stats, hz_bands, term, qd, hz_term, counts, hz_counts = out[:9]
-    attr, attr_counts, contrib, pairs = out[9:]
+    attr, attr_counts, contrib, pairs = out[9:13]
     mdd = mdd_from_raw(qd, compounding) if dd_stats is not None and store else None
     if as_array and pairs is not None:    # SPEC.md 5.10: what the call without pairs returns, then the [K] pair records
         base = _result(out._replace(pairs=None), single, store, as_array, steps, levels, compounding, flows, target)
@@ -1220,7 +1345,8 @@ def bootstrap_inputs(returns, weights):
 
 def simulate_bootstrap(returns, weights, n_steps=252, n_paths=10_000, block=1.0, seed=0, v0=1.0, compounding="simple",
                        rf=0.0, alpha=0.95, devices=None, store=False, path_begin=0, as_array=False, shard="auto", context=None,
-                       horizons=None, bands=(), rebalance=None, rebalance_cost=0.0, cashflow=None, target=None, glide=None, **unsupported):
+                       horizons=None, bands=(), rebalance=None, rebalance_cost=0.0, cashflow=None, target=None, glide=None, spending=None,
+                       **unsupported):
     """simulate_paths on paths resampled from the observed return rows instead of a normal model: the stationary block
     bootstrap of Politis & Romano (SPEC.md 2.1 / 4.4).  Every step of a path uses one whole row of `returns` (all assets of one
     date together), so fat tails, skew, the co-movement within a row and -- with a mean block length `block` > 1 -- short-range
@@ -1233,7 +1359,8 @@ def simulate_bootstrap(returns, weights, n_steps=252, n_paths=10_000, block=1.0,
     that have no meaning here (fold, native_math, drawdown, chol).  rebalance / rebalance_cost as in simulate_paths (SPEC.md 4.5,
     pivots of SPEC.md 5.4; not with compounding="log").  cashflow / target as in simulate_paths (SPEC.md 4.7, pivots of SPEC.md
     5.6; not with rebalance or compounding="log").  glide as in simulate_paths (SPEC.md 4.14, pivots of SPEC.md 5.14 on the row
-    means; not with rebalance or compounding="log").
+    means; not with rebalance or compounding="log").  spending as in simulate_paths (SPEC.md 4.16, pivots of SPEC.md 5.16 on the
+    row means; not with cashflow, glide, rebalance or compounding="log").
     """
     if unsupported.get("overlay") is not None or unsupported.get("spot") is not None:
         raise ValueError("simulate_bootstrap does not take overlay: the rows are observed returns with no price level to strike an "
@@ -1255,7 +1382,13 @@ def simulate_bootstrap(returns, weights, n_steps=252, n_paths=10_000, block=1.0,
         raise ValueError(f"simulate_bootstrap does not take {sorted(unsupported)} (no normals: no fold / native_math / dof -- "
                          "Student-t draws are a parametric model, call simulate_paths(dof=...); drawdown on bootstrap paths is "
                          "not supported)")
-    kw = dict(glide=glide, cashflow=cashflow, rebalance=rebalance, compounding=compounding)
+    kw = dict(spending=spending, glide=glide, cashflow=cashflow, rebalance=rebalance, compounding=compounding)
+    sv = check_spending(spending, v0)
+    _check_combines(_BOOTSTRAP_COMBINE, "spending", kw)
+    goal = None
+    if sv is not None and target is not None:
+        goal = check_cashflow(0.0, target, n_steps)[1]
+        target = None
     gl = check_glide(glide, weights, n_steps)
     _check_combines(_BOOTSTRAP_COMBINE, "glide", kw)
     if gl is not None and cashflow is None:
@@ -1270,7 +1403,9 @@ def simulate_bootstrap(returns, weights, n_steps=252, n_paths=10_000, block=1.0,
     rows, W = bootstrap_inputs(returns, weights)
     prm, ctx = _setup(rows.shape[1], n_steps, W.shape[0], compounding, v0, alpha, rf, False, False, devices, shard, context)
     out = ctx._call(prm, W, int(seed), int(path_begin), int(n_paths), store, rows=rows, block=b, period=period, cost=cost,
-                    horizons=steps, levels=levels, flows=flows, target=target, glide=gl)
+                    horizons=steps, levels=levels, flows=flows, target=target if sv is None else goal, glide=gl, spending=sv)
+    if sv is not None:
+        return _spending_result(out, sv, v0, np.asarray(weights).ndim == 1, store, as_array, steps, levels, compounding, goal)
     res = _result(out, np.asarray(weights).ndim == 1, store, as_array, steps, levels, compounding, flows, target)
     if gl is not None and not as_array:
         for d, blk in zip([res] if isinstance(res, dict) else res, _glide_blocks(gl, W)):
@@ -1370,6 +1505,8 @@ def simulate_sweep(mu, cov, weights=None, n_portfolios=2500, min_weights=None, m
         raise ValueError("simulate_sweep does not take glide: call simulate_paths for the optimum")
     if kw.get("protect") is not None:
         raise ValueError("simulate_sweep does not take protect: call simulate_paths for the optimum")
+    if kw.get("spending") is not None:
+        raise ValueError("simulate_sweep does not take spending: call simulate_paths for the optimum")
     if kw.get("attribution"):
         raise ValueError("simulate_sweep does not take attribution: call simulate_paths for the optimum")
     kw.pop("attribution", None)
