@@ -142,6 +142,15 @@ def main(paths, resample_rule="M", user_rf=3.0, investment=10000.0, seed=12345, 
     (pd_, d5, d50), (pf, f5, f50) = payout["dynamic"], payout["fixed"]
     print(f"  floor-and-ceiling spending (reviewed yearly, cut <= 2.5 %, raise <= 5 %): ruin probability {pd_:.4f} against {pf:.4f} fixed  "
           f"5 % / median payout {d5:,.2f} / {d50:,.2f} against {f5:,.2f} / {f50:,.2f}")
+    # how long the money lasts (SPEC.md 4.17 / 5.17): the periods a path ended with money left, as the lifetime that 95 % of the paths
+    # reach and the median one; a path that is not ruined inside the plan counts its whole length
+    life = {label: mcp.simulate_paths(mu_step, cov_step, w, n_steps=T, n_paths=n_paths, seed=seed, v0=investment, lifetime=True,
+                                      lifetime_levels=(5, 50), **how)["lifetime"]
+            for label, how in (("fixed", dict(cashflow=-take)),
+                               ("dynamic", dict(spending=mcp.spending_rule("floor_ceiling", 0.015, every=af, down=0.025, up=0.05, first=take))))}
+    print(f"  lifetime of the plan, 5 % / median of {T} periods: fixed {life['fixed']['quantiles'][5.0]} / {life['fixed']['quantiles'][50.0]}  "
+          f"floor-and-ceiling {life['dynamic']['quantiles'][5.0]} / {life['dynamic']['quantiles'][50.0]}  "
+          f"(ruined inside the plan: {life['fixed']['n_ruined']} and {life['dynamic']['n_ruined']} of {n_paths} paths)")
     # the same weights with the first asset held through a protective put, on simulated paths (SPEC.md 4.8 / 5.7): the put is
     # applied inside the path kernel at the price level of every path, so the floor shows in the tail and in the drawdown, and
     # the premium (2 % of the price here, in price units) in the mean.  The model is the UNHEDGED returns' mean and covariance.

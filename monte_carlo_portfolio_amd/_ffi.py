@@ -226,6 +226,7 @@ ARG_GROUPS = {
     "rs": [ctypes.POINTER(McpRegimes)], "ft": [ctypes.POINTER(McpFiltered)], "ov": [ctypes.POINTER(McpOverlay)],
     "bt": [ctypes.POINTER(McpBootstrap)], "pt": [ctypes.POINTER(McpProtect)],
     "sp": [ctypes.POINTER(McpSpending)], "wd": [_vp, _vp],     # withdrawn_out, wd_stats_out
+    "life": [_vp, _vp, _vp, _int, _vp, _vp],              # life_out, life_hist_out, life_sum_out, n_life_levels, life_levels, life_q_out
     "mu": [_vp], "chol": [_vp], "W": [_vp], "mu*": [_f32p], "chol*": [_f32p], "W*": [_f32p],
     "walk": [_u64, _u64, _u64],                           # seed, path_begin, n_paths
     "hz_in": [_int, _vp, _int, _vp],                      # n_horizons, horizons, n_levels, levels
@@ -281,6 +282,17 @@ SPEND_SIGNATURES = {
     "mcp_spending_consts": (_int, [ctypes.POINTER(McpSpending), ctypes.c_double, _vp]),
 }
 SPEND_SIGNATURES.update((name, (_int, [t for g in groups for t in ARG_GROUPS[g]])) for name, groups in SPEND_ENTRIES.items())
+
+# And for include/mcport_life.h (SPEC.md 4.17 / 5.17).
+MCP_MAX_LIFE_STEPS = 1 << 20
+LIFE_ENTRIES = {
+    "mcp_simulate_lifetime": "ctx prm cf gl sp mu chol bt st W walk hz_in out counts hz_out hz_counts wd life",
+}
+LIFE_ENTRIES = {name: tuple(groups.split()) for name, groups in LIFE_ENTRIES.items()}
+LIFE_SIGNATURES = {
+    "mcp_lifetime_summary": (_int, [_vp, _int, _int, _vp, _vp, _vp]),
+}
+LIFE_SIGNATURES.update((name, (_int, [t for g in groups for t in ARG_GROUPS[g]])) for name, groups in LIFE_ENTRIES.items())
 
 _LIB = None
 
@@ -346,7 +358,7 @@ def lib() -> ctypes.CDLL:
             fn = getattr(L, name)          # AttributeError if the ABI lost a symbol
             fn.restype = res
             fn.argtypes = args
-        for name, (res, args) in list(EXTENSION_SIGNATURES.items()) + list(SPEND_SIGNATURES.items()):
+        for name, (res, args) in list(EXTENSION_SIGNATURES.items()) + list(SPEND_SIGNATURES.items()) + list(LIFE_SIGNATURES.items()):
             fn = getattr(L, name)          # additive entry points, detected by symbol: a library without them is too old
             fn.restype = res
             fn.argtypes = args
@@ -613,6 +625,17 @@ def spending_pivots(prm: McpParams, spending: McpSpending, W: np.ndarray, mu: np
     check(lib().mcp_spending_pivots(ctypes.byref(prm), ctypes.byref(spending), ptr(mu_p), ref(bt), ptr(W), 0 if hz is None else hz.size,
                                     ptr(hz), ptr(out), ptr(hout), ptr(wout)))
     return out, hout, wout
+
+
+def lifetime_summary(hist, levels=()):
+    """(life_sum, uint32 [L] order statistics at the ranks `lo` of mcp_percentile_rank_q) of one lifetime histogram hist[0 .. T]
+    (SPEC.md 5.17; include/mcport_life.h, mcp_lifetime_summary), pure host arithmetic."""
+    h = np.ascontiguousarray(hist, np.uint64).ravel()
+    lv = np.ascontiguousarray(levels, np.float64).ravel()
+    total = np.zeros(1, np.uint64)
+    q = np.zeros(lv.size, np.uint32)
+    check(lib().mcp_lifetime_summary(ptr(h), h.size - 1, lv.size, ptr(lv) if lv.size else None, ptr(total), ptr(q) if lv.size else None))
+    return int(total[0]), q
 
 
 def make_overlay(rows: np.ndarray, row_begin: np.ndarray, spot: np.ndarray) -> McpOverlay:

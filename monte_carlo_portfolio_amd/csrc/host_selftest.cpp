@@ -89,6 +89,15 @@ static void run_shape(int N, int K, int T, int H) {
   EXPECT(mcp_spending_pivots(&prm, &sp, mu.data(), nullptr, W.data(), H, hs, pv.data(), hzp, wdp.data()) == MCP_OK && finite(pv) && finite(hz) && finite(wdp));
   EXPECT(mcp_spending_pivots(&prm, &sp, nullptr, &boot, W.data(), H, hs, pv.data(), hzp, wdp.data()) == MCP_OK && finite(pv) && finite(hz) && finite(wdp));
   EXPECT(mcp_spending_consts(&sp, prm.v0, c5.data()) == MCP_OK && std::isinf(c5[3]) && c5[4] == 0.015f);
+  {                                       // SPEC.md 5.17 on an exactly sized histogram: T + 1 bins, one level per quartile
+    std::vector<uint64_t> lh((size_t)T + 1, 1);
+    std::vector<double> lq = {0.0, 25.0, 50.0, 100.0};
+    std::vector<uint32_t> got(lq.size());
+    uint64_t total = 0;
+    EXPECT(mcp_lifetime_summary(lh.data(), T, (int)lq.size(), lq.data(), &total, got.data()) == MCP_OK && total == (uint64_t)T * (T + 1) / 2 &&
+           got[0] == 0 && got[1] == (uint32_t)(T / 4) && got[2] == (uint32_t)(T / 2) && got[3] == (uint32_t)T);
+    EXPECT(mcp_lifetime_summary(lh.data(), T, 0, nullptr, &total, nullptr) == MCP_OK);
+  }
   EXPECT(mcp_regime_consts(&rs, thr3.data(), p3.data()) == MCP_OK && finite(p3));
   EXPECT(mcp_jump_consts(&jp, N, mu.data(), jthr.data(), mean_count.data(), drift.data()) == MCP_OK && finite(mean_count) && finite(drift));
   EXPECT(mcp_percentile_rank(1000, 0.95, &rank[0], &rank[1], p3.data()) == MCP_OK && rank[1] == rank[0] + 1 && finite(p3));
@@ -114,6 +123,15 @@ static void run_shape(int N, int K, int T, int H) {
     if (f == OVERLAY) { rq.overlay = true; rq.ov = &ov; }
     if (rq.cash || rq.protect) { rq.counts_out = counts.data(); rq.hz_counts_out = H ? hz_counts.data() : nullptr; }
     EXPECT(check_request(&prm, rq, 4) == MCP_OK);
+    {                                     // SPEC.md 4.17: the lifetime is taken by the walks with ruin and refused by every other
+      std::vector<uint64_t> lh((size_t)K * (T + 1));
+      Request lr = rq;
+      lr.life = true;
+      lr.life_hist_out = lh.data();
+      EXPECT(check_request(&prm, lr, 4) == (rq.cash ? MCP_OK : MCP_E_UNSUPPORTED));
+      lr.life_hist_out = nullptr;
+      EXPECT(check_request(&prm, lr, 4) == (rq.cash ? MCP_E_ARG : MCP_E_UNSUPPORTED));
+    }
     TileInputs in;
     EXPECT(tile_inputs(&prm, rq, &in) == MCP_OK);
     const int tiles[3][2] = {{0, K}, {0, K < 8 ? K : 8}, {8, K - 8}};     // the whole call; K = 9 also as tiles of 8 and 1

@@ -593,6 +593,12 @@ int check_request(const mcp_params* prm, const Request& rq, uint64_t n_paths, co
                                      "rebalancing, the overlay, GARCH, jumps, regimes, filtered rows, the attribution or antithetic pairs");
     if (ln) return fail(MCP_E_UNSUPPORTED, "spending rules are not wired into mcp_launch_paths*");
   }
+  if (rq.life) {                                               // SPEC.md 4.17: a counter on the walks with absorbing ruin
+    if (!rq.cash) return fail(MCP_E_UNSUPPORTED, "the lifetime needs a walk with ruin: a cash-flow schedule, with or without a glide path, or a spending rule");
+    if (prm->n_steps > MCP_MAX_LIFE_STEPS) return fail(MCP_E_UNSUPPORTED, "lifetime: n_steps=%d above MCP_MAX_LIFE_STEPS=%d", prm->n_steps, MCP_MAX_LIFE_STEPS);
+    if (ln) return fail(MCP_E_UNSUPPORTED, "the lifetime is not wired into mcp_launch_paths*");
+    if (!rq.life_hist_out) return fail(MCP_E_ARG, "life_hist_out is NULL");
+  }
   if (rq.protect) {                                            // SPEC.md 4.15: the rules, then what the protection is not combined with
     if ((rc = check_protect(prm, rq.pi))) return rc;
     if (!rq.counts_out) return fail(MCP_E_ARG, "counts_out is NULL");
@@ -1000,9 +1006,44 @@ void request_wd_pivots(const mcp_params* prm, const Request& rq, int k0, int kt,
   spend_pivots(kt, prm->n_steps, cm.data(), spend_consts(rq.sp, prm->v0), rq.sp->every, (double)(float)prm->v0, 0, nullptr, nullptr, nullptr, out_wd);
 }
 
+// SPEC.md 5.17: one pass over the cumulated histogram.  n = sum hist; level q's value is the smallest s with cum(s) > lo
+int life_summary(const uint64_t* hist, int T, int n_levels, const double* levels, uint64_t* sum_out, uint32_t* q_out) {
+  uint64_t n = 0, sum = 0;
+  for (int s = 0; s <= T; s++) { n += hist[s]; sum += (uint64_t)s * hist[s]; }
+  if (sum_out) *sum_out = sum;
+  for (int l = 0; l < n_levels; l++) {
+    if (n == 0) { q_out[l] = 0u; continue; }
+    uint64_t lo, hi, cum = 0;
+    double gamma;
+    if (int rc = mcp_percentile_rank_q(n, levels[l], &lo, &hi, &gamma)) return rc;
+    int s = 0;
+    for (; s < T; s++) {
+      cum += hist[s];
+      if (cum > lo) break;
+    }
+    q_out[l] = (uint32_t)s;
+  }
+  return MCP_OK;
+}
+
 }  // namespace mcph
 
 using namespace mcph;
+
+int mcp_lifetime_summary(const uint64_t* hist, int n_steps, int n_levels, const double* levels, uint64_t* sum_out, uint32_t* q_out) {
+  if (!hist || !sum_out) return fail(MCP_E_ARG, "NULL pointer");
+  if (n_steps < 0 || n_steps > MCP_MAX_LIFE_STEPS) return fail(MCP_E_ARG, "n_steps=%d outside [0,%d]", n_steps, MCP_MAX_LIFE_STEPS);
+  if (int rc = check_levels(n_levels, levels)) return rc;
+  if ((q_out == nullptr) != (n_levels == 0)) return fail(MCP_E_ARG, "q_out must be NULL exactly when n_levels == 0");
+  uint64_t n = 0;
+  for (int s = 0; s <= n_steps; s++) {
+    if (hist[s] > UINT64_MAX - n) return fail(MCP_E_ARG, "the histogram's total overflows 64 bits");
+    n += hist[s];
+  }
+  if (n_levels && n == 0) return fail(MCP_E_ARG, "an empty histogram has no quantile");
+  if (n > UINT64_MAX / (uint64_t)(n_steps > 0 ? n_steps : 1)) return fail(MCP_E_ARG, "life_sum overflows 64 bits");
+  return life_summary(hist, n_steps, n_levels, levels, sum_out, q_out);
+}
 
 extern "C" {
 

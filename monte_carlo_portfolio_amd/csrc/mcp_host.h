@@ -10,6 +10,7 @@
 #include "../../include/mcport.h"
 #include "../../include/mcport_protect.h"
 #include "../../include/mcport_spend.h"
+#include "../../include/mcport_life.h"
 
 namespace mcp {
 constexpr int SWEEP_MIN_K = 17;      // from this many portfolios on the MFMA sweep kernels run
@@ -53,6 +54,7 @@ struct Request {
   const mcp_protect* pi = nullptr;
   bool spend = false;                   // SPEC.md 4.16: the spending rule `sp`, always with `cash` on an all-zero `cf` that carries the
   const mcp_spending* sp = nullptr;     // rule's target (mcp_simulate_spending)
+  bool life = false;                    // SPEC.md 4.17: the lifetime l of every path, always with `cash` (mcp_simulate_lifetime)
   bool overlay = false;                 // SPEC.md 4.8: the option rows `ov`
   const mcp_overlay* ov = nullptr;
   bool garch = false;                   // SPEC.md 4.9: the variance recurrence `gv` (SRC_GAUSS or SRC_T)
@@ -78,6 +80,8 @@ struct Request {
   uint64_t* hz_counts_out = nullptr;    // [H*K][2]
   float* wd_out = nullptr;              // spending rule: NULL or host [K*n] Y_T (SPEC.md 4.16)
   mcp_stats* wd_stats_out = nullptr;    // [K]
+  uint32_t* life_out = nullptr;         // lifetime: NULL or host [K*n] l (SPEC.md 4.17)
+  uint64_t* life_hist_out = nullptr;    // [K][n_steps + 1] (SPEC.md 5.17)
   bool attr = false;                    // SPEC.md 4.10 / 5.9: the second walk that attributes the risk to the assets
   float* contrib_out = nullptr;         // NULL or host [K][N][n]
   mcp_attr* attr_out = nullptr;         // [K][N]
@@ -106,6 +110,8 @@ struct Launch {
   uint64_t mdd_stride = 0;
   float* d_wd = nullptr;                // spending rule: [K][wd_stride] Y_T
   uint64_t wd_stride = 0;
+  uint32_t* d_life = nullptr;           // lifetime: [K][life_stride] l
+  uint64_t life_stride = 0;
   float* d_hz = nullptr;                // horizons: [H][K][hz_stride]
   uint64_t hz_stride = 0;
   const float* d_rows = nullptr;        // bootstrap: [R][N4], zero-padded
@@ -180,6 +186,9 @@ void protect_pivots(const mcp_params& prm, const mcp_protect* pt, const float* m
                     double* out_T, double* out_hz);
 void spend_pivots(int K, int T, const double* m, const SpendConsts& c, int every, double v0, int H, const int32_t* steps, double* out_T,
                   double* out_hz, double* out_wd);
+
+// SPEC.md 5.17: life_sum and the order statistics at the levels' ranks `lo` (mcp_percentile_rank_q) of one histogram hist[0 .. T]
+int life_summary(const uint64_t* hist, int T, int n_levels, const double* levels, uint64_t* sum_out, uint32_t* q_out);
 
 // ---- the packers of what a launch reads besides the packed block of mcp_pack_params ----
 size_t glide_rows(int kt);

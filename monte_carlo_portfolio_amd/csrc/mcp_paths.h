@@ -108,7 +108,7 @@ __device__ __forceinline__ const __attribute__((address_space(4))) A* kernarg() 
 MCP_HAS_MEMBER(hz) MCP_HAS_MEMBER(mdd) MCP_HAS_MEMBER(bt) MCP_HAS_MEMBER(st) MCP_HAS_MEMBER(gv) MCP_HAS_MEMBER(cf)
 MCP_HAS_MEMBER(ov) MCP_HAS_MEMBER(at) MCP_HAS_MEMBER(period) MCP_HAS_MEMBER(pr)
 MCP_HAS_MEMBER(fh) MCP_HAS_MEMBER(p_hi) MCP_HAS_MEMBER(jp) MCP_HAS_MEMBER(rs) MCP_HAS_MEMBER(gp)
-MCP_HAS_MEMBER(pi) MCP_HAS_MEMBER(sp)
+MCP_HAS_MEMBER(pi) MCP_HAS_MEMBER(sp) MCP_HAS_MEMBER(lf)
 #undef MCP_HAS_MEMBER
 
 struct PathArgs {
@@ -379,6 +379,22 @@ __device__ __forceinline__ cspend_p spend_args(const A&) {
   else return nullptr;
 }
 
+// The lifetime of SPEC.md 4.17: per path and portfolio the walks with absorbing ruin may carry the number of steps l that stored a
+// positive V, a uint32 from 0, and store it next to V_T.  The output is read from the kernel arguments where it is written.
+struct LifeArgs {
+  uint32_t* __restrict__ life;        // [K][life_stride] l
+  uint64_t life_stride;
+};
+// Arguments of the lifetime twins: those of mc_paths_glide_kernel and mc_paths_spend_kernel, and the lifetime block behind them.
+struct PathArgsGPL : PathArgsGP { LifeArgs lf; };
+struct PathArgsSPL : PathArgsSP { LifeArgs lf; };
+typedef const __attribute__((address_space(4))) LifeArgs* clife_p;
+template <class A>
+__device__ __forceinline__ clife_p life_args(const A&) {
+  if constexpr (has_lf<A>::value) return &kernarg<A>()->lf;
+  else return nullptr;
+}
+
 // Floor protection (SPEC.md 4.15): CPPI with an exposure cap and a drawdown ratchet.  Per path and portfolio the walk carries V and the
 // peak M (both from v0); step t holds E = fmaxf(fminf(fl32(m (V - F)), fl32(b V)), +0) in the risky portfolio, F = fmaxf(S_t,
 // fl32(theta M)), and V - E at the riskless rate: V' = fma(E, rho, fma(V - E, rf, V)).  `floor` is the schedule S_0 .. S_T behind the
@@ -468,6 +484,7 @@ struct PathLaunchArgs {
   GlideArgs gp;
   ProtectArgs pi;
   SpendArgs sp;
+  LifeArgs lf;
 };
 template <class A>
 inline A make_args(const PathLaunchArgs& s) {
@@ -489,6 +506,7 @@ inline A make_args(const PathLaunchArgs& s) {
   if constexpr (has_gp<A>::value) x.gp = s.gp;
   if constexpr (has_pi<A>::value) x.pi = s.pi;
   if constexpr (has_sp<A>::value) x.sp = s.sp;
+  if constexpr (has_lf<A>::value) x.lf = s.lf;
   if constexpr (has_p_hi<A>::value) { x.p_hi = (uint32_t)(s.hz.path_begin >> 32); x.pad = 0u; }
   return x;
 }
@@ -596,14 +614,15 @@ constexpr int PATH_BLOCK = 256;
 // carries the peak M of V, and the update of V holds only the exposure E of the floor rule in the risky portfolio, the rest at the
 // riskless rate (SPEC.md 4.15).  SP (with CF and HZ): the flow of the step is the path's own withdrawal w instead of the schedule's c_s,
 // the walk also carries w and the total paid out Y, and the reviews of w are wave-uniform events merged with the horizons as the glide
-// walk merges its breaks (SPEC.md 4.16).  Every kernel
+// walk merges its breaks (SPEC.md 4.16).  LT (with CF): the step also counts, on the mask it already forms, the steps that stored a
+// positive V -- the lifetime l of SPEC.md 4.17 -- and l is stored next to V_T.  Every kernel
 // below is the body in mcp_paths_body.inc under its own flags F: it names the flags it sets, the rest are PathFlagsOff's.  F is a
 // local class, which may not have static data members, so it sets its flags as enumerators of an `enum : bool`; they hide the
 // defaults' names and read as the same constant expressions.
 struct PathFlagsOff {
   static constexpr bool NATIVE = false, FOLD = false, LOGC = false, DD = false, HZ = false, BOOT = false, BLDS = false, REB = false,
                         STT = false, CF = false, OV = false, GV = false, AT = false, ANTI = false, FH = false, UHI = false, JP = false, RS = false,
-                        GP = false, PI = false, SP = false;
+                        GP = false, PI = false, SP = false, LT = false;
 };
 
 // __launch_bounds__ 2nd argument of a path kernel: the MCP_MIN_WAVES* above for N <= 16 and one path per lane, by the kind of
@@ -784,6 +803,22 @@ __global__ void MCP_BOUNDS(BK_CF) mc_paths_glide_kernel(const PathArgsGP a) {
 template <int NB, int KT, int PPT, bool BOOT_, bool BLDS_, bool STT_>
 __global__ void MCP_BOUNDS(BK_SP) mc_paths_spend_kernel(const PathArgsSP a) {
   struct F : PathFlagsOff { enum : bool { HZ = true, CF = true, SP = true, BOOT = BOOT_, BLDS = BLDS_, STT = STT_ }; };
+#include "mcp_paths_body.inc"
+}
+
+// The lifetime twins (SPEC.md 4.17): mc_paths_glide_kernel and mc_paths_spend_kernel with the counter l carried next to V and stored
+// next to V_T; everything else those kernels compute is theirs bit for bit.  G = 0 on the glide twin is the cash-flow walk, so a plain
+// cash-flow request with a lifetime runs there and has no third set of instances.  Both keep their originals' launch bounds: the KT
+// counters fit -- the 8-portfolio glide twin at N <= 16 takes the 96 VGPRs of its 5 waves where the original takes 93; unbounded it took
+// 103 (4 waves) and 76 more VALU per step -- and no listing shows scratch in a loop over t (profiles/lifetime_isa.txt).
+template <int NB, int KT, int PPT, bool BOOT_, bool BLDS_, bool STT_>
+__global__ void MCP_BOUNDS(BK_CF) mc_paths_glide_life_kernel(const PathArgsGPL a) {
+  struct F : PathFlagsOff { enum : bool { HZ = true, CF = true, GP = true, LT = true, BOOT = BOOT_, BLDS = BLDS_, STT = STT_ }; };
+#include "mcp_paths_body.inc"
+}
+template <int NB, int KT, int PPT, bool BOOT_, bool BLDS_, bool STT_>
+__global__ void MCP_BOUNDS(BK_SP) mc_paths_spend_life_kernel(const PathArgsSPL a) {
+  struct F : PathFlagsOff { enum : bool { HZ = true, CF = true, SP = true, LT = true, BOOT = BOOT_, BLDS = BLDS_, STT = STT_ }; };
 #include "mcp_paths_body.inc"
 }
 

@@ -5,7 +5,7 @@
 // derived from it) and the kernel argument `a` (PathArgs or a struct that starts with one).
   constexpr bool NATIVE = F::NATIVE, FOLD = F::FOLD, LOGC = F::LOGC, DD = F::DD, HZ = F::HZ, BOOT = F::BOOT, BLDS = F::BLDS, REB = F::REB,
                  STT = F::STT, CF = F::CF, OV = F::OV, GV = F::GV, AT = F::AT, ANTI = F::ANTI, FH = F::FH, UHI = F::UHI, JP = F::JP, RS = F::RS,
-                 GP = F::GP, PI = F::PI, SP = F::SP;
+                 GP = F::GP, PI = F::PI, SP = F::SP, LT = F::LT;
   static_assert(!UHI || (KT == 1 && PPT == 1 && !(NATIVE || FOLD || DD || HZ || BOOT || REB || STT || CF || OV || GV || AT || ANTI || FH || JP || RS || PI)),
                 "uniform high counter word: the plain Gaussian walk of one portfolio only");
   static_assert(!FH || (BOOT && HZ && !(LOGC || REB || CF || STT || GV || OV || AT || DD || PI)), "filtered rows: the bootstrap's segmented walk only");
@@ -19,6 +19,7 @@
                 "floor protection: the segmented GARCH or jump walk, simple compounding only");
   static_assert(!SP || (CF && HZ && !(NATIVE || FOLD || LOGC || DD || REB || OV || GV || AT || ANTI || FH || UHI || JP || RS || GP || PI)),
                 "spending rule: the cash-flow kernel's segmented walk only");
+  static_assert(!LT || (CF && (GP || SP)), "lifetime: the glide and spending kernels' walks only");
   constexpr int N4 = 4 * NB;
   // ANTI (SPEC.md 2.3): a lane's PPT draws feed EM = 2 PPT members -- slot e < PPT walks on z[e], slot PPT + e on -z[e]; p, live and
   // the counters are per draw (a.path_begin and a.n_paths count pairs), the members 2 p and 2 p + 1 are adjacent in the output rows
@@ -145,6 +146,7 @@
     uint32_t rg[PPT];                                     // RS: the regime of the next step (SPEC.md 2.6); s_0 is drawn in step 0
     float Mk[EM][KT];                                     // PI: the running peak M of SPEC.md 4.15, V_0 included
     float Wd[PPT][KT], Yk[PPT][KT];                       // SP: the per-step withdrawal w and the total paid out Y of SPEC.md 4.16
+    uint32_t Lk[PPT][KT];                                 // LT: the steps that stored a positive V, the lifetime l of SPEC.md 4.17
 #pragma unroll
     for (int e = 0; e < PPT; e++) {
       p[e] = tl * tile + (uint64_t)e * PATH_BLOCK + threadIdx.x;
@@ -161,6 +163,10 @@
         const float w0 = spend_args(a)->w0;               // one scalar load per tile
 #pragma unroll
         for (int k = 0; k < KT; k++) { Wd[e][k] = w0; Yk[e][k] = 0.0f; }
+      }
+      if constexpr (LT) {
+#pragma unroll
+        for (int k = 0; k < KT; k++) Lk[e][k] = 0u;
       }
       if constexpr (BOOT) jrow[e] = 0u;                   // replaced at t = 0 (a restart)
       if constexpr (GV) gh[e] = garch_args(a)->h0;        // one scalar load per tile
@@ -473,6 +479,12 @@
               if constexpr (ANTI) *(float2*)&dk->mdd[(size_t)(a.k_begin + k) * dk->mdd_stride + 2 * p[e]] = make_float2(Qk[e][k], Qk[PPT + e][k]);
               else dk->mdd[(size_t)(a.k_begin + k) * dk->mdd_stride + p[e]] = Qk[e][k];
             }
+        }
+        if constexpr (LT) {                                // l of SPEC.md 4.17, next to V_T
+          const clife_p lk = life_args(a);
+#pragma unroll
+          for (int k = 0; k < KT; k++)
+            if (k < kt) lk->life[(size_t)(a.k_begin + k) * lk->life_stride + p[e]] = Lk[e][k];
         }
       }
     }

@@ -131,18 +131,26 @@ static hipError_t ladder(const PathKernel& k, const PathLaunchArgs& s, hipStream
       MCP_ROW(bg && !lg, mc_paths_reb_kernel<NB, KT, 1, true, false>);
       break;
     case FAM_CF:
-      MCP_ROW(gauss && !lg && !k.gp && !k.sp, mc_paths_cf_kernel<NB, KT, 1, false, false, false>);
-      MCP_ROW(t && !lg && !k.gp && !k.sp, mc_paths_cf_kernel<NB, KT, 1, false, false, true>);
-      MCP_ROW(bl && !lg && !k.gp && !k.sp, mc_paths_cf_kernel<NB, KT, 1, true, true, false>);
-      MCP_ROW(bg && !lg && !k.gp && !k.sp, mc_paths_cf_kernel<NB, KT, 1, true, false, false>);
-      MCP_ROW(gauss && !lg && k.sp, mc_paths_spend_kernel<NB, KT, 1, false, false, false>);   // SPEC.md 4.16: the path's own withdrawal
-      MCP_ROW(t && !lg && k.sp, mc_paths_spend_kernel<NB, KT, 1, false, false, true>);
-      MCP_ROW(bl && !lg && k.sp, mc_paths_spend_kernel<NB, KT, 1, true, true, false>);
-      MCP_ROW(bg && !lg && k.sp, mc_paths_spend_kernel<NB, KT, 1, true, false, false>);
-      MCP_ROW(gauss && !lg && k.gp, mc_paths_glide_kernel<NB, KT, 1, false, false, false>);   // SPEC.md 4.14: the weights on a schedule
-      MCP_ROW(t && !lg && k.gp, mc_paths_glide_kernel<NB, KT, 1, false, false, true>);
-      MCP_ROW(bl && !lg && k.gp, mc_paths_glide_kernel<NB, KT, 1, true, true, false>);
-      MCP_ROW(bg && !lg && k.gp, mc_paths_glide_kernel<NB, KT, 1, true, false, false>);
+      MCP_ROW(gauss && !lg && !k.gp && !k.sp && !k.lt, mc_paths_cf_kernel<NB, KT, 1, false, false, false>);
+      MCP_ROW(t && !lg && !k.gp && !k.sp && !k.lt, mc_paths_cf_kernel<NB, KT, 1, false, false, true>);
+      MCP_ROW(bl && !lg && !k.gp && !k.sp && !k.lt, mc_paths_cf_kernel<NB, KT, 1, true, true, false>);
+      MCP_ROW(bg && !lg && !k.gp && !k.sp && !k.lt, mc_paths_cf_kernel<NB, KT, 1, true, false, false>);
+      MCP_ROW(gauss && !lg && k.sp && !k.lt, mc_paths_spend_kernel<NB, KT, 1, false, false, false>);   // SPEC.md 4.16: the path's own withdrawal
+      MCP_ROW(t && !lg && k.sp && !k.lt, mc_paths_spend_kernel<NB, KT, 1, false, false, true>);
+      MCP_ROW(bl && !lg && k.sp && !k.lt, mc_paths_spend_kernel<NB, KT, 1, true, true, false>);
+      MCP_ROW(bg && !lg && k.sp && !k.lt, mc_paths_spend_kernel<NB, KT, 1, true, false, false>);
+      MCP_ROW(gauss && !lg && k.gp && !k.lt, mc_paths_glide_kernel<NB, KT, 1, false, false, false>);   // SPEC.md 4.14: the weights on a schedule
+      MCP_ROW(t && !lg && k.gp && !k.lt, mc_paths_glide_kernel<NB, KT, 1, false, false, true>);
+      MCP_ROW(bl && !lg && k.gp && !k.lt, mc_paths_glide_kernel<NB, KT, 1, true, true, false>);
+      MCP_ROW(bg && !lg && k.gp && !k.lt, mc_paths_glide_kernel<NB, KT, 1, true, false, false>);
+      MCP_ROW(gauss && !lg && k.sp && k.lt, mc_paths_spend_life_kernel<NB, KT, 1, false, false, false>);   // SPEC.md 4.17: the lifetime twins
+      MCP_ROW(t && !lg && k.sp && k.lt, mc_paths_spend_life_kernel<NB, KT, 1, false, false, true>);
+      MCP_ROW(bl && !lg && k.sp && k.lt, mc_paths_spend_life_kernel<NB, KT, 1, true, true, false>);
+      MCP_ROW(bg && !lg && k.sp && k.lt, mc_paths_spend_life_kernel<NB, KT, 1, true, false, false>);
+      MCP_ROW(gauss && !lg && k.gp && k.lt, mc_paths_glide_life_kernel<NB, KT, 1, false, false, false>);   // G = 0: the cash-flow walk
+      MCP_ROW(t && !lg && k.gp && k.lt, mc_paths_glide_life_kernel<NB, KT, 1, false, false, true>);
+      MCP_ROW(bl && !lg && k.gp && k.lt, mc_paths_glide_life_kernel<NB, KT, 1, true, true, false>);
+      MCP_ROW(bg && !lg && k.gp && k.lt, mc_paths_glide_life_kernel<NB, KT, 1, true, false, false>);
       break;
     case FAM_OV:
       MCP_ROW(gauss && !lg && !k.dd, mc_paths_ov_kernel<NB, KT, 1, false, false>);
@@ -163,6 +171,7 @@ hipError_t MCP_CAT(launch_paths_nb, MCP_NB)(const PathKernel& k, const PathLaunc
   if (k.gp && (k.family != FAM_CF || k.fold || k.uhi || k.native || k.anti || k.fh || k.jp || k.rs || k.gv)) return hipErrorInvalidValue;
   if (k.pi && (k.fold || k.uhi || k.native || k.anti || k.fh || k.rs || k.gp || k.family == FAM_AT)) return hipErrorInvalidValue;
   if (k.sp && (k.family != FAM_CF || k.fold || k.uhi || k.native || k.anti || k.fh || k.jp || k.rs || k.gv || k.gp || k.pi)) return hipErrorInvalidValue;
+  if (k.lt && (k.family != FAM_CF || k.gp == k.sp || k.fold || k.uhi || k.native || k.anti || k.fh || k.jp || k.rs || k.gv || k.pi)) return hipErrorInvalidValue;
   if (k.fold) {                                            // rho = c + v.z: the plain Gaussian walk on the spec's normals
     const bool ok = k.family == FAM_PLAIN && !k.boot && !k.stt && !k.gv && !k.native && !k.kt8;
     MCP_ROW(ok && k.logc, mc_paths_kernel<NB, 1, 1, false, true, true>);

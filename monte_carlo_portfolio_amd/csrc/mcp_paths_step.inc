@@ -18,7 +18,8 @@
 // wave has a lane in regime 0 and then, under `if (s_t)`, on (mu1, L1) -- each a whole chain of its own, nothing shared (SPEC.md 2.6 / 4.13).  UHI: the same step with p_hi a scalar (philox4x32_10_uhi), the drift read through the LDS address
 // par_lds instead of the opaque zero offset, and the blocks scheduled one at a time.  PI: the update of V is the floor rule of SPEC.md
 // 4.15 on the step's rho, then the peak M.  SP (with CF): the flow is the path's own -w, and the step adds what it pays out to Y
-// (SPEC.md 4.16); the reviews of w are events of the walk, not of the step.
+// (SPEC.md 4.16); the reviews of w are events of the walk, not of the step.  LT (with CF): the mask that selects the step's V also
+// adds one to the lifetime l (SPEC.md 4.17).
       float rho[EM][KT];
       float fsh[PPT];                                  // FH: the shock s_j of the step's row (SPEC.md 2.4)
       if constexpr (BOOT) {
@@ -342,6 +343,7 @@
             const bool lv = u > 0.0f;
             Yk[e][k] = Yk[e][k] + (lv ? Wd[e][k] : fmaxf(u0, 0.0f));
             V[e][k] = lv ? u : 0.0f;
+            if constexpr (LT) Lk[e][k] += lv ? 1u : 0u;    // SPEC.md 4.17: the stored V is positive exactly where the path is live
           }
       } else if constexpr (CF) {
         // SPEC.md 4.7: U = fma(V, rho, V), U = U + c_s (two roundings), V = (V > 0 and U > 0) ? U : +0 -- a NaN U is ruin too
@@ -351,7 +353,9 @@
 #pragma unroll
           for (int k = 0; k < KT; k++) {
             const float u = fma32(V[e][k], rho[e][k], V[e][k]) + cs;
-            V[e][k] = (V[e][k] > 0.0f && u > 0.0f) ? u : 0.0f;
+            const bool lv = V[e][k] > 0.0f && u > 0.0f;
+            V[e][k] = lv ? u : 0.0f;
+            if constexpr (LT) Lk[e][k] += lv ? 1u : 0u;    // SPEC.md 4.17, on the mask of the select
           }
       } else if constexpr (PI) {
         // SPEC.md 4.15: F = fmaxf(S_t, fl32(theta M)), C = V - F, E = fmaxf(fminf(fl32(m C), fl32(b V)), +0), u = fma(V - E, rf, V),

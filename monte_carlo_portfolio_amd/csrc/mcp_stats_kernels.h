@@ -69,13 +69,14 @@ struct PathLaunchArgs;
 // of the same three families: Gaussian draws on the drift and factor of the path's regime, SPEC.md 2.6, simple compounding), and
 // gp (FAM_CF only: the glide-path kernel, the cash-flow walk on scheduled target weights, SPEC.md 4.14), and pi (the floor-protection
 // kernel of SPEC.md 4.15: FAM_DD with the drawdown, else FAM_HZ, H = 0 included; stt and gv both set for the GARCH walk, or jp), and
-// sp (FAM_CF only: the spending kernel, the cash-flow walk on the path's own withdrawal, SPEC.md 4.16).
+// sp (FAM_CF only: the spending kernel, the cash-flow walk on the path's own withdrawal, SPEC.md 4.16), and lt (with exactly one of
+// gp and sp: that kernel's lifetime twin, SPEC.md 4.17; a plain cash-flow request asks for the glide twin with no break).
 // The one ladder of mcp_paths_inst.hip maps it to a kernel and lists which selectors have one.
 constexpr int LEAN_MAX_NB = 4;
 enum PathFamily { FAM_PLAIN, FAM_DD, FAM_HZ, FAM_REB, FAM_CF, FAM_OV, FAM_AT };
 struct PathKernel {
   int family;
-  bool logc, boot, blds, stt, dd, gv, kt8, native, fold, anti, fh, uhi, jp, rs, gp, pi, sp;
+  bool logc, boot, blds, stt, dd, gv, kt8, native, fold, anti, fh, uhi, jp, rs, gp, pi, sp, lt;
 };
 
 // mcp_paths_inst.hip (one translation unit per NB): every pass of the kernel that `k` selects, on the blocks of `args` that the
@@ -120,6 +121,10 @@ hipError_t launch_count_rows(const float* values, uint64_t stride, uint64_t n, i
 // array (SPEC.md 5.15); `thr` is a device [rows][2] array (-inf: nothing is below), `counts` is [rows][2] and zeroed by the caller
 hipError_t launch_count_below(const float* values, uint64_t stride, uint64_t n, int rows, const float* thr, unsigned long long* counts,
                               hipStream_t s);
+// hist[r][l] += 1 over the n live values l of each of the `rows` rows of a [rows][stride] uint32 array (SPEC.md 5.17); every value
+// is < bins, `hist` is [rows][bins] and zeroed by the caller
+hipError_t launch_life_hist(const uint32_t* life, uint64_t stride, uint64_t n, int rows, uint32_t bins, unsigned long long* hist,
+                            hipStream_t s);
 // every buffer <- element-wise sum of the `nsrc` buffers (u64 words): the exchange between logical shards of ONE device
 // (or of devices with peer access)
 hipError_t launch_sum_u64(unsigned long long* const* bufs, int nsrc, size_t words, hipStream_t s);

@@ -647,6 +647,66 @@ hipError_t launch_count_below(const float* values, uint64_t stride, uint64_t n, 
   return hipGetLastError();
 }
 
+// SPEC.md 5.17: the histogram of the lifetimes l of every row.  Most paths survive and land on the one bin l = T, and 64 lanes on
+// one word serialise: the adds are aggregated per wave by ballot, as lds_hist_add does (which is the LDS side here); u64_hist_add is
+// the same pattern on 64-bit global counters.  Every lane of the wave must call it (ballots inside).
+__device__ __forceinline__ void u64_hist_add(unsigned long long* h, uint32_t bin, bool active) {
+  unsigned long long todo = __ballot(active);
+  const int lane = threadIdx.x & 63;
+#pragma unroll 1
+  for (int it = 0; it < 4 && todo; it++) {
+    const int leader = __ffsll((long long)todo) - 1;
+    const uint32_t b0 = (uint32_t)__builtin_amdgcn_readlane((int)bin, leader);
+    const bool same = active && bin == b0;
+    const unsigned long long m = __ballot(same);
+    if (lane == leader) atomicAdd(&h[b0], (unsigned long long)__popcll(m));
+    todo &= ~m;
+    active = active && !same;
+  }
+  if (active) atomicAdd(&h[bin], 1ull);
+}
+
+// One workgroup column per row (blockIdx.y).  LDS_: bins <= LIFE_LDS_BINS, a workgroup-private histogram of 32 KiB of u32 (a
+// workgroup reads fewer than 2^32 values), whose non-zero bins are flushed with one 64-bit global atomic each; otherwise straight
+// onto the global counters.  A value >= bins (none, by SPEC.md 4.17) is not counted: no counter outside the row is touched.
+constexpr uint32_t LIFE_LDS_BINS = 8192;
+template <bool LDS_>
+__global__ void __launch_bounds__(SB) life_hist_kernel(const uint32_t* __restrict__ life, uint64_t stride, uint64_t n, uint32_t bins,
+                                                       unsigned long long* __restrict__ hist) {
+  __shared__ uint32_t s_h[LDS_ ? LIFE_LDS_BINS : 1];
+  if constexpr (LDS_) {
+    for (uint32_t i = threadIdx.x; i < bins; i += SB) s_h[i] = 0u;
+    __syncthreads();
+  }
+  const uint32_t* __restrict__ row = life + (size_t)blockIdx.y * stride;
+  unsigned long long* __restrict__ out = hist + (size_t)blockIdx.y * bins;
+  for (uint64_t base = (uint64_t)blockIdx.x * SB; base < n; base += (uint64_t)gridDim.x * SB) {   // block-uniform trip count
+    const uint64_t i = base + threadIdx.x;
+    const uint32_t l = i < n ? row[i] : 0u;
+    const bool live = i < n && l < bins;
+    if constexpr (LDS_) lds_hist_add(s_h, l, live);
+    else u64_hist_add(out, l, live);
+  }
+  if constexpr (LDS_) {
+    __syncthreads();
+    for (uint32_t i = threadIdx.x; i < bins; i += SB) {
+      const uint32_t h = s_h[i];
+      if (h) atomicAdd(&out[i], (unsigned long long)h);
+    }
+  }
+}
+
+hipError_t launch_life_hist(const uint32_t* life, uint64_t stride, uint64_t n, int rows, uint32_t bins, unsigned long long* hist,
+                            hipStream_t s) {
+  if (rows < 1 || rows > 65535 || bins < 1) return hipErrorInvalidValue;
+  uint64_t g = (n + SB - 1) / SB;
+  if (g < 1) g = 1;
+  if (g > 256) g = 256;
+  if (bins <= LIFE_LDS_BINS) life_hist_kernel<true><<<dim3((unsigned)g, (unsigned)rows), SB, 0, s>>>(life, stride, n, bins, hist);
+  else life_hist_kernel<false><<<dim3((unsigned)g, (unsigned)rows), SB, 0, s>>>(life, stride, n, bins, hist);
+  return hipGetLastError();
+}
+
 hipError_t launch_sum_u64(unsigned long long* const* bufs, int nsrc, size_t words, hipStream_t s) {
   if (nsrc < 1 || nsrc > 8) return hipErrorInvalidValue;
   PtrList l;

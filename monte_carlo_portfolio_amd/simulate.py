@@ -51,10 +51,14 @@ _ENTRY_CHOICE = (
     (("drawdown",), "mcp_simulate_drawdown", None),
     ((), "mcp_simulate", None),
 )
+# The lifetime (SPEC.md 4.17) is an opt-in on three of those calls, not a feature of its own: with it the call takes this entry point,
+# whatever the table above would choose, and a keyword that entry point has no argument group for is refused with this sentence.
+_LIFE_CHOICE = ("mcp_simulate_lifetime", "lifetime is not combined with protect, drawdown, rebalance, overlay, garch, jumps, regimes, "
+                                         "filtered rows, attribution or antithetic")
 # the argument group of _ffi.SIMULATE_ENTRIES that carries each feature keyword of Context._call
 _KEYWORD_GROUP = {"rows": "bt", "dof": "st", "period": "rb", "drawdown": "dd", "horizons": "hz_in", "flows": "cf", "overlay": "ov",
                   "garch": "gv", "attribution": "attr", "antithetic": "pairs", "filtered": "ft", "jumps": "jp", "regimes": "rs",
-                  "glide": "gl", "protect": "pt", "spending": "sp"}
+                  "glide": "gl", "protect": "pt", "spending": "sp", "lifetime": "life"}
 
 
 class Context:
@@ -102,8 +106,8 @@ class Context:
     def _call(self, prm: _ffi.McpParams, W, seed: int, path_begin: int, n_paths: int, store: bool, mu=None, chol=None, rows=None,
               block: float = 1.0, dof=None, period=None, cost: float = 0.0, drawdown: bool = False, horizons=None, levels=(),
               flows=None, target=None, overlay=None, garch=None, attribution=False, antithetic=False, filtered=None, jumps=None, regimes=None,
-              glide=None, protect=None, spending=None):
-        """The one library call behind every simulate_* method: a spending rule (spending: the (rate, every, down, up, inflation, first or None) of check_spending; `target` is then its second count), floor protection (protect: the (floor, multiplier, rate, cap, ratchet) of check_protect; `target` is then its second count), two regimes (regimes: the (p01, p10, start, mu1, chol1) of check_regimes), market jumps (jumps: the (intensity, mean, std, loading or None) of check_jumps), GARCH volatility (garch: the (alpha, beta, h0) of check_garch), an option overlay (overlay: the triple of check_overlay), cash flows (flows, target), Student-t draws (dof), rebalancing
+              glide=None, protect=None, spending=None, lifetime=None):
+        """The one library call behind every simulate_* method: the lifetime (lifetime: the levels in percent of its order statistics, SPEC.md 4.17 / 5.17; needs flows or spending), a spending rule (spending: the (rate, every, down, up, inflation, first or None) of check_spending; `target` is then its second count), floor protection (protect: the (floor, multiplier, rate, cap, ratchet) of check_protect; `target` is then its second count), two regimes (regimes: the (p01, p10, start, mu1, chol1) of check_regimes), market jumps (jumps: the (intensity, mean, std, loading or None) of check_jumps), GARCH volatility (garch: the (alpha, beta, h0) of check_garch), an option overlay (overlay: the triple of check_overlay), cash flows (flows, target), Student-t draws (dof), rebalancing
         (period, cost), bootstrap rows (rows, block) or Gaussian draws (mu, chol), with the drawdown or horizons.  Allocates the
         outputs that were asked for and passes NULL for the rest -> _Outputs, None where not asked for (terminal, qd,
         horizon_terminal: with `store` only; counts, hz_counts: with `flows` only; attr [K, N] records of ATTR_DTYPE and attr_counts
@@ -116,10 +120,11 @@ class Context:
                                    ("overlay", overlay is not None), ("garch", garch is not None), ("attribution", attribution),
                                    ("antithetic", antithetic), ("filtered", filtered is not None), ("jumps", jumps is not None),
                                    ("regimes", regimes is not None), ("glide", glide is not None),
-                                   ("protect", protect is not None), ("spending", spending is not None)) if on]
+                                   ("protect", protect is not None), ("spending", spending is not None),
+                                   ("lifetime", lifetime is not None)) if on]
         has = set(given).issuperset
-        entry, refusal = next((e, r) for needs, e, r in _ENTRY_CHOICE if has(needs))
-        groups = next(t[entry] for t in (_ffi.SIMULATE_ENTRIES, _ffi.EXTENSION_ENTRIES, _ffi.SPEND_ENTRIES) if entry in t)
+        entry, refusal = _LIFE_CHOICE if lifetime is not None else next((e, r) for needs, e, r in _ENTRY_CHOICE if has(needs))
+        groups = next(t[entry] for t in (_ffi.SIMULATE_ENTRIES, _ffi.EXTENSION_ENTRIES, _ffi.SPEND_ENTRIES, _ffi.LIFE_ENTRIES) if entry in t)
         # the library states the rules (check_request); a keyword the entry point has no argument for is refused here, not dropped
         for kw in given:
             if _KEYWORD_GROUP[kw] not in groups:
@@ -146,14 +151,24 @@ class Context:
         attr = np.zeros((K, N), _ffi.ATTR_DTYPE) if "attr" in groups else None
         attr_counts = np.zeros((K, 2), np.uint64) if "attr_counts" in groups else None
         contrib = np.empty((K, N, n_paths), np.float32) if "contrib" in groups and store else None
-        wd_stats = np.zeros(K, _ffi.STATS_DTYPE) if "wd" in groups else None
-        withdrawn = np.empty((K, n_paths), np.float32) if "wd" in groups and store else None
+        has_wd = "wd" in groups and spending is not None       # the lifetime's entry point takes them with a spending rule only
+        wd_stats = np.zeros(K, _ffi.STATS_DTYPE) if has_wd else None
+        withdrawn = np.empty((K, n_paths), np.float32) if has_wd and store else None
+        life = life_hist = life_sum = life_q = life_lv = None
+        if lifetime is not None:
+            life_lv = np.ascontiguousarray(lifetime, np.float64).ravel()
+            life = np.empty((K, n_paths), np.uint32) if store else None
+            life_hist = np.zeros((K, prm.n_steps + 1), np.uint64)
+            life_sum = np.zeros(K, np.uint64)
+            life_q = np.zeros((K, life_lv.size), np.uint32)
         vals = {"ctx": (self._h,), "prm": (prm,), "mu": (mu,), "chol": (chol,), "W": (W,), "walk": (seed, path_begin, n_paths),
                 "hz_in": (H, steps if H else None, L, lv if L else None), "out": (term, stats), "dd": (raw, dd_stats),
                 "hz_out": (hz_term, hz_stats, bands if L else None), "counts": (counts,), "hz_counts": (hz_counts,), "pairs": (pairs,),
                 "contrib": (contrib,), "attr": (attr,), "attr_counts": (attr_counts,), "bt": (bt,),
                 "pt": (_ffi.make_protect(*protect, target=target) if protect is not None else None,),
                 "sp": (_ffi.make_spending(*spending, target=target) if spending is not None else None,), "wd": (withdrawn, wd_stats),
+                "life": (life, life_hist, life_sum, 0 if life_lv is None else life_lv.size, life_lv if life_lv is not None and life_lv.size else None,
+                         life_q if life_lv is not None and life_lv.size else None),
                 "gl": (_ffi.make_glide(*glide) if glide is not None else None,),               # flows None: the all-zero schedule
                 "cf": (_ffi.make_cashflow(flows, target) if flows is not None else None,),
                 "rb": (_ffi.McpRebalance(int(period), 0, float(cost)) if period is not None else None,),
@@ -171,7 +186,22 @@ class Context:
         rc = getattr(_ffi.lib(), entry)(*(arg(g, v) for g in groups for v in vals[g.rstrip("*")]))
         _ffi.check(rc)
         return _Outputs(stats, dd_stats, hz_stats, bands, term, raw, hz_term, counts, hz_counts, attr, attr_counts, contrib, pairs,
-                        wd_stats, withdrawn)
+                        wd_stats, withdrawn, life_hist, life_sum, life_q, life)
+
+    def simulate_lifetime(self, prm: _ffi.McpParams, W, seed: int, path_begin: int, n_paths: int, store: bool, levels=(5.0, 25.0, 50.0),
+                          flows=None, glide=None, spending=None, mu=None, chol=None, rows=None, block: float = 1.0, dof=None, target=None,
+                          horizons=None, bands=()):
+        """simulate_cashflow() (flows), simulate_glide() (flows and glide) or simulate_spending() (spending) with the lifetime of every
+        path switched on (SPEC.md 4.17 / 5.17; include/mcport_life.h, mcp_simulate_lifetime): exactly one of flows and spending.
+        `levels`: the percentages of the lifetime's order statistics; `bands`: the levels of the horizons' bands.  -> _Outputs of that
+        call with life_hist [K, n_steps + 1] uint64, life_sum [K] uint64, life_q [K, len(levels)] uint32 and, with `store`, life
+        [K, n_paths] uint32."""
+        sp = None if spending is None else tuple(spending) + (0.0, None)[len(tuple(spending)) - 4:]
+        return self._call(prm, W, seed, path_begin, n_paths, store, mu=mu, chol=chol, rows=rows, block=block, dof=dof, target=target,
+                          horizons=horizons, levels=bands, flows=None if flows is None else np.ascontiguousarray(flows, np.float32),
+                          glide=None if glide is None else (np.ascontiguousarray(glide[0], np.int32), np.ascontiguousarray(glide[1], np.float32)),
+                          spending=sp,
+                          lifetime=np.asarray(levels, np.float64).ravel())
 
     def simulate(self, prm: _ffi.McpParams, mu, chol, W, seed: int, path_begin: int, n_paths: int, store: bool):
         o = self._call(prm, W, seed, path_begin, n_paths, store, mu=mu, chol=chol)
@@ -337,7 +367,7 @@ class Context:
 # binary32 contributions [K, N, n].  With antithetic pairs the records of SPEC.md 5.10 (pairs [K] of PAIR_DTYPE).  With a spending rule
 # the record of the total paid out (wd_stats [K]) and, stored, the binary32 withdrawn [K, n] (SPEC.md 5.16).
 _Outputs = collections.namedtuple("_Outputs", "stats dd_stats hz_stats bands terminal qd horizon_terminal counts hz_counts attr "
-                                  "attr_counts contributions pairs wd_stats withdrawn", defaults=(None,) * 8)
+                                  "attr_counts contributions pairs wd_stats withdrawn life_hist life_sum life_q life", defaults=(None,) * 12)
 
 
 def check_cashflow(cashflow, target, n_steps):
@@ -946,7 +976,7 @@ def simulate_paths(mu, cov, weights, n_steps=252, n_paths=10_000, seed=0, v0=1.0
                    native_math=False, as_array=False, fold=False, shard="auto", context=None, drawdown=False,
                    horizons=None, bands=(), rebalance=None, rebalance_cost=0.0, dof=None, cashflow=None, target=None,
                    overlay=None, spot=None, garch=None, attribution=False, antithetic=False, jumps=None, regimes=None, glide=None,
-                   protect=None, spending=None):
+                   protect=None, spending=None, lifetime=False, lifetime_levels=(5, 25, 50)):
     """Simulate `n_paths` correlated return paths and reduce them to risk statistics.
 
     mu [N], cov [N,N] are per-step mean and covariance (the reference's `mean_returns`, `cov_matrix`
@@ -1119,7 +1149,22 @@ def simulate_paths(mu, cov, weights, n_steps=252, n_paths=10_000, seed=0, v0=1.0
     devices and bootstrap rows (simulate_bootstrap).  Not built: spending with cashflow, glide, protect, drawdown, rebalance, overlay,
     garch, jumps, regimes, attribution, antithetic, fold, native_math or compounding="log" (ValueError), on filtered rows, in
     simulate_sweep, in PathEngine and at the mcp_launch_* level.
+
+    lifetime=False (default): ruin is a count at the end and at the horizons.  lifetime=True, with cashflow (with or without glide) or
+    spending: how long the money lasts (SPEC.md 4.17 / 5.17).  The walk counts per path the steps l that ended with money left: l ==
+    n_steps is a path not ruined inside the horizon, l < n_steps one ruined in step l + 1.  Everything else the call returns is that
+    of the call without it, bit for bit.  Every dict gains 'lifetime' {histogram uint64 [n_steps + 1] (#{l == s}), survival float64
+    [n_steps + 1] (the share of paths with l >= s; 1 - survival[h] is the ruin probability at h), mean (the restricted mean lifetime
+    in steps), quantiles {level: steps} for lifetime_levels in percent (np.percentile(l, q, method="lower"): 5 -> the lifetime that
+    95 % of the paths exceed or meet), n_ruined and, with store=True, steps uint32 [n_paths]}; as_array appends life_hist, life_sum,
+    life_q[, life].  All integers are exact and independent of devices and tiles.  Not built: lifetime without cashflow or spending
+    (a walk without ruin; glide alone included), with protect, drawdown, rebalance, overlay, garch, jumps, regimes, attribution or
+    antithetic (ValueError), on filtered rows, in simulate_sweep, in PathEngine and at the mcp_launch_* level.
     """
+    from .lifetime import check_lifetime
+    lt = check_lifetime(lifetime, lifetime_levels, n_steps)
+    if lt is not None and cashflow is None and spending is None:
+        raise ValueError("lifetime needs a walk with ruin: cashflow (with or without glide) or spending")
     kw = dict(spending=spending, protect=protect, glide=glide, regimes=regimes, jumps=jumps, antithetic=antithetic, attribution=attribution, garch=garch, overlay=overlay,
               cashflow=cashflow, dof=dof, rebalance=rebalance, drawdown=drawdown, horizons=horizons, fold=fold, native_math=native_math,
               compounding=compounding, shard=shard)
@@ -1181,7 +1226,7 @@ def simulate_paths(mu, cov, weights, n_steps=252, n_paths=10_000, seed=0, v0=1.0
     out = ctx._call(prm, W, int(seed), int(path_begin), int(n_paths), store, mu=mu32, chol=L, dof=dof, period=period, cost=cost,
                     drawdown=drawdown, horizons=steps, levels=levels, flows=flows, target=target if pv is None and sv is None else goal,
                     overlay=ov, garch=gv, attribution=bool(attribution), antithetic=bool(antithetic), jumps=jv, regimes=rv, glide=gl, protect=pv,
-                    spending=sv)
+                    spending=sv, **({} if lt is None else {"lifetime": lt}))
     if sv is not None:                                     # the counts are the 'spending' block's, not a 'cashflow' block's
         res = _spending_result(out, sv, v0, np.asarray(weights).ndim == 1, store, as_array, steps, levels, compounding, goal)
     elif pv is not None:                                     # the counts are the 'protect' block's, not a 'cashflow' block's
@@ -1204,6 +1249,17 @@ def simulate_paths(mu, cov, weights, n_steps=252, n_paths=10_000, seed=0, v0=1.0
         blk = _regime_block(rv, steps)
         for d in [res] if isinstance(res, dict) else res:
             d["regimes"] = dict(blk)
+    return res if lt is None else _with_lifetime(res, out, lt, store, as_array)
+
+
+def _with_lifetime(res, out, levels, store, as_array):
+    """The result of a call with its lifetime outputs (SPEC.md 5.17): as_array appends life_hist, life_sum, life_q[, life]; else
+    every dict gains the 'lifetime' block."""
+    from .lifetime import lifetime_blocks
+    if as_array:
+        return (res if isinstance(res, tuple) else (res,)) + (out.life_hist, out.life_sum, out.life_q) + ((out.life,) if store else ())
+    for d, blk in zip([res] if isinstance(res, dict) else res, lifetime_blocks(out, levels, store, int(out.stats[0]["n"]))):
+        d["lifetime"] = blk
     return res
 
 
@@ -1346,7 +1402,7 @@ def bootstrap_inputs(returns, weights):
 def simulate_bootstrap(returns, weights, n_steps=252, n_paths=10_000, block=1.0, seed=0, v0=1.0, compounding="simple",
                        rf=0.0, alpha=0.95, devices=None, store=False, path_begin=0, as_array=False, shard="auto", context=None,
                        horizons=None, bands=(), rebalance=None, rebalance_cost=0.0, cashflow=None, target=None, glide=None, spending=None,
-                       **unsupported):
+                       lifetime=False, lifetime_levels=(5, 25, 50), **unsupported):
     """simulate_paths on paths resampled from the observed return rows instead of a normal model: the stationary block
     bootstrap of Politis & Romano (SPEC.md 2.1 / 4.4).  Every step of a path uses one whole row of `returns` (all assets of one
     date together), so fat tails, skew, the co-movement within a row and -- with a mean block length `block` > 1 -- short-range
@@ -1360,8 +1416,13 @@ def simulate_bootstrap(returns, weights, n_steps=252, n_paths=10_000, block=1.0,
     pivots of SPEC.md 5.4; not with compounding="log").  cashflow / target as in simulate_paths (SPEC.md 4.7, pivots of SPEC.md
     5.6; not with rebalance or compounding="log").  glide as in simulate_paths (SPEC.md 4.14, pivots of SPEC.md 5.14 on the row
     means; not with rebalance or compounding="log").  spending as in simulate_paths (SPEC.md 4.16, pivots of SPEC.md 5.16 on the
-    row means; not with cashflow, glide, rebalance or compounding="log").
+    row means; not with cashflow, glide, rebalance or compounding="log").  lifetime / lifetime_levels as in simulate_paths (SPEC.md
+    4.17 / 5.17; with cashflow, with or without glide, or spending).
     """
+    from .lifetime import check_lifetime
+    lt = check_lifetime(lifetime, lifetime_levels, n_steps)
+    if lt is not None and cashflow is None and spending is None:
+        raise ValueError("lifetime needs a walk with ruin: cashflow (with or without glide) or spending")
     if unsupported.get("overlay") is not None or unsupported.get("spot") is not None:
         raise ValueError("simulate_bootstrap does not take overlay: the rows are observed returns with no price level to strike an "
                          "option at -- apply the strategy to the returns matrix first (options.calc_options_series per asset, as "
@@ -1403,14 +1464,16 @@ def simulate_bootstrap(returns, weights, n_steps=252, n_paths=10_000, block=1.0,
     rows, W = bootstrap_inputs(returns, weights)
     prm, ctx = _setup(rows.shape[1], n_steps, W.shape[0], compounding, v0, alpha, rf, False, False, devices, shard, context)
     out = ctx._call(prm, W, int(seed), int(path_begin), int(n_paths), store, rows=rows, block=b, period=period, cost=cost,
-                    horizons=steps, levels=levels, flows=flows, target=target if sv is None else goal, glide=gl, spending=sv)
+                    horizons=steps, levels=levels, flows=flows, target=target if sv is None else goal, glide=gl, spending=sv,
+                    **({} if lt is None else {"lifetime": lt}))
     if sv is not None:
-        return _spending_result(out, sv, v0, np.asarray(weights).ndim == 1, store, as_array, steps, levels, compounding, goal)
+        res = _spending_result(out, sv, v0, np.asarray(weights).ndim == 1, store, as_array, steps, levels, compounding, goal)
+        return res if lt is None else _with_lifetime(res, out, lt, store, as_array)
     res = _result(out, np.asarray(weights).ndim == 1, store, as_array, steps, levels, compounding, flows, target)
     if gl is not None and not as_array:
         for d, blk in zip([res] if isinstance(res, dict) else res, _glide_blocks(gl, W)):
             d["glide"] = blk
-    return res
+    return res if lt is None else _with_lifetime(res, out, lt, store, as_array)
 
 
 def filtered_inputs(filtered, weights):
