@@ -151,6 +151,17 @@ def main(paths, resample_rule="M", user_rf=3.0, investment=10000.0, seed=12345, 
     print(f"  lifetime of the plan, 5 % / median of {T} periods: fixed {life['fixed']['quantiles'][5.0]} / {life['fixed']['quantiles'][50.0]}  "
           f"floor-and-ceiling {life['dynamic']['quantiles'][5.0]} / {life['dynamic']['quantiles'][50.0]}  "
           f"(ruined inside the plan: {life['fixed']['n_ruined']} and {life['dynamic']['n_ruined']} of {n_paths} paths)")
+    # how to rebalance (SPEC.md 4.18 / 5.18): the optimum held over the same 6 years without withdrawals, traded back to its weights
+    # every quarter, or looked at every period and traded only when an asset has left its 5/25 band (5 points, or a quarter of its
+    # target), at 0.2 % of what is traded either way
+    quarter = max(1, af // 4)
+    kw = dict(n_steps=T, n_paths=n_paths, seed=seed, v0=investment, rf=user_rf / 100, rebalance_cost=0.002, store=True)
+    cal = mcp.simulate_paths(mu_step, cov_step, w, rebalance=quarter, tolerance=0.0, **kw)
+    band = mcp.simulate_paths(mu_step, cov_step, w, rebalance=1, tolerance=mcp.tolerance_bands(w, absolute=0.05, relative=0.25), **kw)
+    for label, o in (("quarterly calendar", cal), ("5/25 bands", band)):
+        tb = o["tolerance"]
+        print(f"  rebalancing by {label}: mean trades {tb['trades']['mean']:.2f} of {tb['n_reviews']} reviews  median turnover "
+              f"{np.percentile(tb['turnover']['paths'].astype(np.float64), 50.0):.4f}  VaR = {o['var']:+.4f}  CVaR = {o['cvar']:+.4f}")
     # the same weights with the first asset held through a protective put, on simulated paths (SPEC.md 4.8 / 5.7): the put is
     # applied inside the path kernel at the price level of every path, so the floor shows in the tail and in the drawdown, and
     # the premium (2 % of the price here, in price units) in the mean.  The model is the UNHEDGED returns' mean and covariance.

@@ -70,6 +70,12 @@ class McpRebalance(ctypes.Structure):
     _fields_ = [("period", ctypes.c_int32), ("reserved", ctypes.c_int32), ("cost", ctypes.c_double)]
 
 
+class McpBand(ctypes.Structure):
+    """mcp_band: the tolerance bands of SPEC.md 4.18 (every: the review period, 0 never; cost: proportional, in [0, 1); tol: float32
+    [K][N], every entry >= 0 or +inf for an asset that is not watched)."""
+    _fields_ = [("every", ctypes.c_int32), ("reserved", ctypes.c_int32), ("cost", ctypes.c_double), ("tol", ctypes.c_void_p)]
+
+
 class McpStudentT(ctypes.Structure):
     """mcp_student_t: the degrees of freedom nu in [3, MCP_MAX_T_DOF] of Student-t draws (SPEC.md 2.2)."""
     _fields_ = [("dof", ctypes.c_int32), ("reserved", ctypes.c_int32)]
@@ -227,6 +233,9 @@ ARG_GROUPS = {
     "bt": [ctypes.POINTER(McpBootstrap)], "pt": [ctypes.POINTER(McpProtect)],
     "sp": [ctypes.POINTER(McpSpending)], "wd": [_vp, _vp],     # withdrawn_out, wd_stats_out
     "life": [_vp, _vp, _vp, _int, _vp, _vp],              # life_out, life_hist_out, life_sum_out, n_life_levels, life_levels, life_q_out
+    "tb": [ctypes.POINTER(McpBand)],
+    # trades_out, trade_hist_out, trade_sum_out, n_trade_levels, trade_levels, trade_q_out, turnover_out, turnover_stats_out
+    "trades": [_vp, _vp, _vp, _int, _vp, _vp, _vp, _vp],
     "mu": [_vp], "chol": [_vp], "W": [_vp], "mu*": [_f32p], "chol*": [_f32p], "W*": [_f32p],
     "walk": [_u64, _u64, _u64],                           # seed, path_begin, n_paths
     "hz_in": [_int, _vp, _int, _vp],                      # n_horizons, horizons, n_levels, levels
@@ -294,6 +303,16 @@ LIFE_SIGNATURES = {
 }
 LIFE_SIGNATURES.update((name, (_int, [t for g in groups for t in ARG_GROUPS[g]])) for name, groups in LIFE_ENTRIES.items())
 
+# And for include/mcport_band.h (SPEC.md 4.18 / 5.18).
+BAND_ENTRIES = {
+    "mcp_simulate_banded": "ctx prm tb mu chol bt W* walk hz_in out hz_out trades",
+}
+BAND_ENTRIES = {name: tuple(groups.split()) for name, groups in BAND_ENTRIES.items()}
+BAND_SIGNATURES = {
+    "mcp_band_reviews": (_int, [_PP, ctypes.POINTER(McpBand)]),
+}
+BAND_SIGNATURES.update((name, (_int, [t for g in groups for t in ARG_GROUPS[g]])) for name, groups in BAND_ENTRIES.items())
+
 _LIB = None
 
 
@@ -358,7 +377,8 @@ def lib() -> ctypes.CDLL:
             fn = getattr(L, name)          # AttributeError if the ABI lost a symbol
             fn.restype = res
             fn.argtypes = args
-        for name, (res, args) in list(EXTENSION_SIGNATURES.items()) + list(SPEND_SIGNATURES.items()) + list(LIFE_SIGNATURES.items()):
+        for name, (res, args) in list(EXTENSION_SIGNATURES.items()) + list(SPEND_SIGNATURES.items()) + list(LIFE_SIGNATURES.items()) + \
+                list(BAND_SIGNATURES.items()):
             fn = getattr(L, name)          # additive entry points, detected by symbol: a library without them is too old
             fn.restype = res
             fn.argtypes = args
@@ -636,6 +656,17 @@ def lifetime_summary(hist, levels=()):
     q = np.zeros(lv.size, np.uint32)
     check(lib().mcp_lifetime_summary(ptr(h), h.size - 1, lv.size, ptr(lv) if lv.size else None, ptr(total), ptr(q) if lv.size else None))
     return int(total[0]), q
+
+
+def make_band(every: int, cost: float, tol: np.ndarray) -> McpBand:
+    """mcp_band over the C-contiguous float32 [K, N] table `tol` (the caller keeps it alive for the call)."""
+    return McpBand(int(every), 0, float(cost), ptr(tol))
+
+
+def band_reviews(n_steps: int, every: int) -> int:
+    """n_reviews of SPEC.md 4.18 (include/mcport_band.h, mcp_band_reviews), pure host arithmetic."""
+    n = lib().mcp_band_reviews(ctypes.byref(McpParams(n_steps=int(n_steps))), ctypes.byref(McpBand(int(every), 0, 0.0, None)))
+    return check(n)
 
 
 def make_overlay(rows: np.ndarray, row_begin: np.ndarray, spot: np.ndarray) -> McpOverlay:

@@ -25,9 +25,9 @@ template <class T> static bool finite(const std::vector<T>& v) {
   return true;
 }
 
-enum Feature { PLAIN, BOOT, FILTERED, JUMPS, REGIMES, GLIDE_CF, GLIDE, PROTECT, CASH, OVERLAY, SPEND, SPEND_BOOT, N_FEATURES };
+enum Feature { PLAIN, BOOT, FILTERED, JUMPS, REGIMES, GLIDE_CF, GLIDE, PROTECT, CASH, OVERLAY, SPEND, SPEND_BOOT, BAND, BAND_BOOT, N_FEATURES };
 static const char* const k_names[N_FEATURES] = {"plain", "bootstrap", "filtered", "jumps", "regimes", "glide+flows", "glide",
-                                                "protect", "cash", "overlay", "spend", "spend+bootstrap"};
+                                                "protect", "cash", "overlay", "spend", "spend+bootstrap", "band", "band+bootstrap"};
 
 static void run_shape(int N, int K, int T, int H) {
   const int R = 6, G = 2;
@@ -62,6 +62,10 @@ static void run_shape(int N, int K, int T, int H) {
   const mcp_protect pt = {floor_s.data(), 3.0, 1.0, 0.001, 0.1, nullptr, 0};
   const mcp_overlay ov = {ov_rows.data(), row_begin.data(), spot.data(), 1, 0};
   const mcp_rebalance reb = {5, 0, 0.001};
+  std::vector<float> tol((size_t)K * N, 0.05f);          // SPEC.md 4.18: bands, the last asset of every portfolio not watched
+  for (int k = 0; k < K; k++) tol[(size_t)k * N + N - 1] = HUGE_VALF;
+  const mcp_band bd = {5, 0, 0.001, tol.data()};
+  const mcp_rebalance bd_reb = {bd.every, 0, bd.cost};
   const mcp_spending sp = {0.01, 0.1, HUGE_VAL, 0.02, 0.015, 0.9, 5, 1, 1, 0};
   const int32_t* hs = H ? steps.data() : nullptr;
 
@@ -98,6 +102,7 @@ static void run_shape(int N, int K, int T, int H) {
            got[0] == 0 && got[1] == (uint32_t)(T / 4) && got[2] == (uint32_t)(T / 2) && got[3] == (uint32_t)T);
     EXPECT(mcp_lifetime_summary(lh.data(), T, 0, nullptr, &total, nullptr) == MCP_OK);
   }
+  EXPECT(mcp_band_reviews(&prm, &bd) == (T - 1) / 5 && mcp_band_reviews(&prm, nullptr) == -1);
   EXPECT(mcp_regime_consts(&rs, thr3.data(), p3.data()) == MCP_OK && finite(p3));
   EXPECT(mcp_jump_consts(&jp, N, mu.data(), jthr.data(), mean_count.data(), drift.data()) == MCP_OK && finite(mean_count) && finite(drift));
   EXPECT(mcp_percentile_rank(1000, 0.95, &rank[0], &rank[1], p3.data()) == MCP_OK && rank[1] == rank[0] + 1 && finite(p3));
@@ -108,11 +113,16 @@ static void run_shape(int N, int K, int T, int H) {
   std::vector<uint64_t> counts(2 * (size_t)K), hz_counts(2 * (size_t)H * K);
   for (int f = 0; f < N_FEATURES; f++) {
     snprintf(g_case, sizeof g_case, "%s, N=%d K=%d T=%d H=%d", k_names[f], N, K, T, H);
-    const Source src = f == BOOT || f == SPEND_BOOT ? SRC_BOOT : f == FILTERED ? SRC_FHS : SRC_GAUSS;
+    const Source src = f == BOOT || f == SPEND_BOOT || f == BAND_BOOT ? SRC_BOOT : f == FILTERED ? SRC_FHS : SRC_GAUSS;
     const bool rows_only = src != SRC_GAUSS;
     Request rq = host_request(src, rows_only ? nullptr : mu.data(), rows_only ? nullptr : chol.data(), W.data(), nullptr, stats.data());
     ask_horizons(rq, H != 0, H, hs, 0, nullptr, nullptr, H ? hz_stats.data() : nullptr, nullptr);
-    if (f == BOOT || f == SPEND_BOOT) rq.boot = &boot;
+    if (f == BOOT || f == SPEND_BOOT || f == BAND_BOOT) rq.boot = &boot;
+    std::vector<uint64_t> trade_hist((size_t)K * ((size_t)(T - 1) / 5 + 1));
+    if (f == BAND || f == BAND_BOOT) {
+      rq.rebalanced = rq.band = true; rq.reb = &bd_reb; rq.bd = &bd;
+      rq.trade_hist_out = trade_hist.data(); rq.turnover_stats_out = stats.data();
+    }
     if (f == FILTERED) { rq.filt = &filt; rq.gv = &gv; }
     if (f == JUMPS) { rq.jumps = true; rq.jp = &jp; }
     if (f == REGIMES) { rq.regimes = true; rq.rs = &rs; }
@@ -132,6 +142,18 @@ static void run_shape(int N, int K, int T, int H) {
       lr.life_hist_out = nullptr;
       EXPECT(check_request(&prm, lr, 4) == (rq.cash ? MCP_E_ARG : MCP_E_UNSUPPORTED));
     }
+    if (rq.band) {                        // SPEC.md 4.18: a negative entry, a missing histogram, and the size of the histogram
+      Request br = rq;
+      std::vector<float> neg(tol);
+      neg.back() = -0.01f;
+      const mcp_band bad_bd = {5, 0, 0.001, neg.data()};
+      br.bd = &bad_bd;
+      EXPECT(check_request(&prm, br, 4) == MCP_E_ARG);
+      br = rq;
+      br.trade_hist_out = nullptr;
+      EXPECT(check_request(&prm, br, 4) == MCP_E_ARG);
+      EXPECT(count_bins(&prm, rq) * (size_t)K == trade_hist.size());
+    }
     TileInputs in;
     EXPECT(tile_inputs(&prm, rq, &in) == MCP_OK);
     const int tiles[3][2] = {{0, K}, {0, K < 8 ? K : 8}, {8, K - 8}};     // the whole call; K = 9 also as tiles of 8 and 1
@@ -143,6 +165,15 @@ static void run_shape(int N, int K, int T, int H) {
       std::vector<double> piv(kt), piv_hz((size_t)H * kt);
       EXPECT(pack_tile(&prm, rq, in, k0, kt, block.data()) == MCP_OK);
       block.resize(lay.floor + (rq.protect ? (size_t)T + 1 : 0));         // the thresholds behind the schedule may be -inf (no target)
+      if (rq.band) {                                                      // the table is finite (+0 where not watched); behind it the mask words
+        EXPECT(lay.floor - lay.load == band_len(N, kt));
+        const uint32_t* words = (const uint32_t*)(block.data() + lay.load + (size_t)kt * (4 * ((N + 3) / 4)));
+        for (int k = 0; k < kt; k++) {
+          const uint64_t watch = (uint64_t)words[2 * k] | (uint64_t)words[2 * k + 1] << 32;
+          EXPECT(watch == (N == 1 ? 0 : (N - 1 == 64 ? ~0ull : (1ull << (N - 1)) - 1)));
+        }
+        block.resize(lay.load + (size_t)kt * (4 * ((N + 3) / 4)));
+      }
       EXPECT(finite(block));
       EXPECT(request_pivots(&prm, rq, in, k0, kt, piv.data(), H ? piv_hz.data() : nullptr) == MCP_OK && finite(piv) && finite(piv_hz));
       if (rq.spend) {

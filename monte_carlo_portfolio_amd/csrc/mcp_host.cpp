@@ -505,6 +505,43 @@ void overlay_pivots(int N, int K, int T, const mcp_overlay* ov, const float* mu,
   for (int k = 0; k < K; k++) out_T[k] = pivot(A[(size_t)k]);
 }
 
+// SPEC.md 4.18: the rule's arguments.  tol is [K][N]: every entry >= 0 (finite or +inf); a NaN fails the compare too
+int check_band(const mcp_params* prm, const mcp_band* bd) {
+  if (!bd) return fail(MCP_E_ARG, "band is NULL");
+  if (bd->every < 0) return fail(MCP_E_ARG, "band every=%d < 0", bd->every);
+  if (bd->reserved != 0) return fail(MCP_E_ARG, "band reserved=%d must be 0", bd->reserved);
+  if (!(bd->cost >= 0.0 && bd->cost < 1.0)) return fail(MCP_E_ARG, "band cost=%g outside [0, 1)", bd->cost);
+  if (!bd->tol) return fail(MCP_E_ARG, "band tol is NULL");
+  const size_t n = (size_t)prm->n_portfolios * (size_t)prm->n_assets;
+  for (size_t i = 0; i < n; i++)
+    if (!(bd->tol[i] >= 0.0f))
+      return fail(MCP_E_ARG, "band tol[%zu]=%g (portfolio %zu, asset %zu) must be >= 0 or +inf", i, (double)bd->tol[i], i / (size_t)prm->n_assets,
+                  i % (size_t)prm->n_assets);
+  return MCP_OK;
+}
+int band_reviews(int T, int e) { return (e >= 1 && e < T) ? (T - 1) / e : 0; }
+size_t count_bins(const mcp_params* prm, const Request& rq) {
+  return (size_t)(rq.band ? band_reviews(prm->n_steps, rq.bd->every) : prm->n_steps) + 1;
+}
+// SPEC.md 4.18: the device copy of the tolerances of the portfolios [k0, k0 + kt) -- [kt][N4] floats, an entry of an unwatched asset
+// (+inf, or padding) stored as +0, then per portfolio the two 32-bit words (low, high) of the mask of the watched assets
+size_t band_len(int N, int kt) { return (size_t)kt * ((size_t)n4_of(N) + 2); }
+void band_pack(int N, int k0, int kt, const mcp_band* bd, float* out) {
+  const size_t n4 = (size_t)n4_of(N);
+  uint32_t* words = (uint32_t*)(out + (size_t)kt * n4);
+  for (int k = 0; k < kt; k++) {
+    uint64_t watch = 0;
+    for (size_t i = 0; i < n4; i++) {
+      const float t = i < (size_t)N ? bd->tol[(size_t)(k0 + k) * N + i] : __builtin_inff();
+      const bool on = t < __builtin_inff();
+      out[(size_t)k * n4 + i] = on ? t : 0.0f;
+      if (on) watch |= (uint64_t)1 << i;
+    }
+    words[2 * k] = (uint32_t)watch;
+    words[2 * k + 1] = (uint32_t)(watch >> 32);
+  }
+}
+
 // SPEC.md 4.8: the device copy of an overlay -- [rows n_rows][row_begin N4 + 1][spot N4]; the assets >= N own no rows
 size_t overlay_bytes(int N, int n_rows) { return (size_t)n_rows * sizeof(mcp_overlay_row) + (size_t)(2 * n4_of(N) + 1) * 4; }
 void overlay_pack(int N, const mcp_overlay* ov, char* out) {
@@ -558,6 +595,20 @@ void ask_drawdown(Request& rq, float* mdd_out, mcp_stats* dd_stats_out) {
 int check_request(const mcp_params* prm, const Request& rq, uint64_t n_paths, const Launch* ln, uint64_t path_begin) {
   int rc;
   if ((rc = check_params(prm))) return rc;
+  if (rq.band) {                                               // SPEC.md 4.18: the rules, then what the bands are not combined with
+    if ((rc = check_band(prm, rq.bd))) return rc;
+    if (!rq.trade_hist_out || !rq.turnover_stats_out) return fail(MCP_E_ARG, "trade_hist_out or turnover_stats_out is NULL");
+    if (prm->compounding != MCP_COMPOUND_SIMPLE) return fail(MCP_E_UNSUPPORTED, "banded paths compound simply (no log compounding)");
+    if (prm->flags & (MCP_FLAG_FOLD | MCP_FLAG_NATIVE_MATH))
+      return fail(MCP_E_UNSUPPORTED, "banded paths run on the unfolded recurrence and the spec's normals (no MCP_FLAG_FOLD / MCP_FLAG_NATIVE_MATH)");
+    if (band_reviews(prm->n_steps, rq.bd->every) > MCP_MAX_LIFE_STEPS)
+      return fail(MCP_E_UNSUPPORTED, "bands: %d reviews above MCP_MAX_LIFE_STEPS=%d", band_reviews(prm->n_steps, rq.bd->every), MCP_MAX_LIFE_STEPS);
+    if (!rq.rebalanced || rq.src == SRC_T || rq.src == SRC_FHS || rq.cash || rq.glide || rq.protect || rq.spend || rq.life || rq.overlay ||
+        rq.garch || rq.jumps || rq.regimes || rq.dd || rq.attr || rq.anti)
+      return fail(MCP_E_UNSUPPORTED, "tolerance bands are not combined with Student-t draws, filtered rows, cash flows, glide paths, floor protection, "
+                                     "spending rules, the drawdown, the overlay, GARCH, jumps, regimes, the attribution or antithetic pairs");
+    if (ln) return fail(MCP_E_UNSUPPORTED, "tolerance bands are not wired into mcp_launch_paths*");
+  }
   if (rq.rebalanced) {
     if ((rc = check_reb(rq.reb))) return rc;
     if (rq.src == SRC_BOOT ? rq.mu || rq.chol : !rq.mu || !rq.chol) return fail(MCP_E_ARG, "exactly one draw source: mu and chol, or boot");
@@ -903,13 +954,14 @@ void protect_pivots(const mcp_params& prm, const mcp_protect* pt, const float* m
 }
 
 // What follows the packed block of a tile of kt portfolios.  Jumps: the [N4] loadings; regimes: [mu1][L1 row pairs]; glide path: the
-// target blocks of the tile's portfolios (check_request lets at most one of the three through).  Protection: behind them the floor
+// target blocks of the tile's portfolios; bands: the tolerance table and the masks (check_request lets at most one of the four through).  Protection: behind them the floor
 // schedule and the counts' thresholds (protect_pack).
 TileLayout tile_layout(const mcp_params* prm, const Request& rq, int kt) {
   const int N = prm->n_assets;
   TileLayout t;
   t.base = t.load = mcp_packed_len(N, kt);
-  t.floor = t.load + (rq.jumps ? (size_t)n4_of(N) : rq.regimes ? regime_block_len(N) : rq.glide ? glide_len(N, kt, rq.gl) : 0);
+  t.floor = t.load + (rq.jumps ? (size_t)n4_of(N) : rq.regimes ? regime_block_len(N) : rq.glide ? glide_len(N, kt, rq.gl)
+                       : rq.band ? band_len(N, kt) : 0);
   t.total = t.floor + (rq.protect ? protect_len(prm->n_steps, kt, rq.hz ? rq.H : 0) : 0);
   return t;
 }
@@ -945,6 +997,7 @@ int pack_tile(const mcp_params* prm, const Request& rq, const TileInputs& in, in
   for (int i = 0; rq.jumps && i < n4_of(N); i++) load[i] = i < N ? (rq.jp->loading ? rq.jp->loading[i] : 1.0f) : 0.0f;
   if (rq.regimes) std::copy(in.blk1.begin(), in.blk1.begin() + (ptrdiff_t)regime_block_len(N), load);
   if (rq.glide) glide_pack(N, prm->n_portfolios, k0, kt, rq.gl, load);
+  if (rq.band) band_pack(N, k0, kt, rq.bd, load);
   if (rq.protect) protect_pack(prm->n_steps, kt, H, rq.steps, rq.pi, out + lay.floor);
   return MCP_OK;
 }
@@ -1043,6 +1096,12 @@ int mcp_lifetime_summary(const uint64_t* hist, int n_steps, int n_levels, const 
   if (n_levels && n == 0) return fail(MCP_E_ARG, "an empty histogram has no quantile");
   if (n > UINT64_MAX / (uint64_t)(n_steps > 0 ? n_steps : 1)) return fail(MCP_E_ARG, "life_sum overflows 64 bits");
   return life_summary(hist, n_steps, n_levels, levels, sum_out, q_out);
+}
+
+int mcp_band_reviews(const mcp_params* prm, const mcp_band* bd) {
+  if (!prm || !bd) { (void)fail(MCP_E_ARG, "NULL pointer"); return -1; }
+  if (prm->n_steps < 0 || bd->every < 0) { (void)fail(MCP_E_ARG, "n_steps=%d or every=%d < 0", prm->n_steps, bd->every); return -1; }
+  return band_reviews(prm->n_steps, bd->every);
 }
 
 extern "C" {

@@ -11,6 +11,7 @@
 #include "../../include/mcport_protect.h"
 #include "../../include/mcport_spend.h"
 #include "../../include/mcport_life.h"
+#include "../../include/mcport_band.h"
 
 namespace mcp {
 constexpr int SWEEP_MIN_K = 17;      // from this many portfolios on the MFMA sweep kernels run
@@ -55,6 +56,8 @@ struct Request {
   bool spend = false;                   // SPEC.md 4.16: the spending rule `sp`, always with `cash` on an all-zero `cf` that carries the
   const mcp_spending* sp = nullptr;     // rule's target (mcp_simulate_spending)
   bool life = false;                    // SPEC.md 4.17: the lifetime l of every path, always with `cash` (mcp_simulate_lifetime)
+  bool band = false;                    // SPEC.md 4.18: the tolerance bands `bd`, always with `rebalanced` on a rule `reb` of the same
+  const mcp_band* bd = nullptr;         // period and cost (mcp_simulate_banded)
   bool overlay = false;                 // SPEC.md 4.8: the option rows `ov`
   const mcp_overlay* ov = nullptr;
   bool garch = false;                   // SPEC.md 4.9: the variance recurrence `gv` (SRC_GAUSS or SRC_T)
@@ -82,6 +85,10 @@ struct Request {
   mcp_stats* wd_stats_out = nullptr;    // [K]
   uint32_t* life_out = nullptr;         // lifetime: NULL or host [K*n] l (SPEC.md 4.17)
   uint64_t* life_hist_out = nullptr;    // [K][n_steps + 1] (SPEC.md 5.17)
+  uint32_t* trades_out = nullptr;       // bands: NULL or host [K*n] c (SPEC.md 4.18)
+  uint64_t* trade_hist_out = nullptr;   // [K][n_reviews + 1] (SPEC.md 5.18)
+  float* turnover_out = nullptr;        // NULL or host [K*n] Y
+  mcp_stats* turnover_stats_out = nullptr;   // [K]
   bool attr = false;                    // SPEC.md 4.10 / 5.9: the second walk that attributes the risk to the assets
   float* contrib_out = nullptr;         // NULL or host [K][N][n]
   mcp_attr* attr_out = nullptr;         // [K][N]
@@ -117,6 +124,7 @@ struct Launch {
   const float* d_rows = nullptr;        // bootstrap: [R][N4], zero-padded
   const float* d_flows = nullptr;       // cash flows: [n_steps]
   const float* d_floor = nullptr;       // protection: [n_steps + 1] the floor schedule
+  const float* d_band = nullptr;        // bands: [K][N4] tolerances, then [K][2] mask words (band_pack); c goes to d_life, Y to d_wd
   const float* d_targets = nullptr;     // glide path: [n_breaks][glide_rows(K)][N4] target blocks (glide_pack)
   const char* d_overlay = nullptr;      // overlay: [rows][row_begin N4 + 1][spot N4] (overlay_pack)
   const float* d_loading = nullptr;     // jumps: [N4] loadings, zero-padded
@@ -148,6 +156,7 @@ int check_glide(const mcp_params* prm, const mcp_glide* gl);
 int check_protect(const mcp_params* prm, const mcp_protect* pt);
 int check_spending(double v0, const mcp_spending* sp);
 int check_overlay(const mcp_params* prm, const mcp_overlay* ov);
+int check_band(const mcp_params* prm, const mcp_band* bd);
 // Every rule a request meets: each feature's own arguments, then which features combine (MCP_E_UNSUPPORTED), then the outputs.
 // `ln`: an mcp_launch_paths* call, whose device arrays are checked instead of the host arrays of an mcp_simulate* call.
 int check_request(const mcp_params* prm, const Request& rq, uint64_t n_paths, const Launch* ln = nullptr, uint64_t path_begin = 0);
@@ -190,10 +199,17 @@ void spend_pivots(int K, int T, const double* m, const SpendConsts& c, int every
 // SPEC.md 5.17: life_sum and the order statistics at the levels' ranks `lo` (mcp_percentile_rank_q) of one histogram hist[0 .. T]
 int life_summary(const uint64_t* hist, int T, int n_levels, const double* levels, uint64_t* sum_out, uint32_t* q_out);
 
+// SPEC.md 4.18: the reviews of a walk of T steps reviewed every e steps, floor((T - 1) / e) for 1 <= e < T, else 0
+int band_reviews(int T, int e);
+// The bins of the exact histogram of a request's integer record: the lifetime's n_steps + 1 (SPEC.md 5.17), the bands' n_reviews + 1 (5.18)
+size_t count_bins(const mcp_params* prm, const Request& rq);
+
 // ---- the packers of what a launch reads besides the packed block of mcp_pack_params ----
 size_t glide_rows(int kt);
 size_t glide_len(int N, int kt, const mcp_glide* gl);
 void glide_pack(int N, int K, int k0, int kt, const mcp_glide* gl, float* out);
+size_t band_len(int N, int kt);
+void band_pack(int N, int k0, int kt, const mcp_band* bd, float* out);
 size_t protect_len(int T, int kt, int H);
 void protect_pack(int T, int kt, int H, const int32_t* steps, const mcp_protect* pt, float* out);
 size_t overlay_bytes(int N, int n_rows);
@@ -203,7 +219,7 @@ void overlay_pack(int N, const mcp_overlay* ov, char* out);
 // Float offsets into the parameter block of a tile.  This is the only place that knows what follows the packed block.
 struct TileLayout {
   size_t base;     // mcp_packed_len(N, kt): the end of the packed block
-  size_t load;     // where the jump loadings, the regime-1 block or the glide targets begin
+  size_t load;     // where the jump loadings, the regime-1 block, the glide targets or the tolerance table begin
   size_t floor;    // where the protection schedule and the counts' thresholds begin (protect_pack)
   size_t total;    // floats of the whole block
 };

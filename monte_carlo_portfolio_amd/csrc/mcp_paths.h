@@ -108,7 +108,7 @@ __device__ __forceinline__ const __attribute__((address_space(4))) A* kernarg() 
 MCP_HAS_MEMBER(hz) MCP_HAS_MEMBER(mdd) MCP_HAS_MEMBER(bt) MCP_HAS_MEMBER(st) MCP_HAS_MEMBER(gv) MCP_HAS_MEMBER(cf)
 MCP_HAS_MEMBER(ov) MCP_HAS_MEMBER(at) MCP_HAS_MEMBER(period) MCP_HAS_MEMBER(pr)
 MCP_HAS_MEMBER(fh) MCP_HAS_MEMBER(p_hi) MCP_HAS_MEMBER(jp) MCP_HAS_MEMBER(rs) MCP_HAS_MEMBER(gp)
-MCP_HAS_MEMBER(pi) MCP_HAS_MEMBER(sp) MCP_HAS_MEMBER(lf)
+MCP_HAS_MEMBER(pi) MCP_HAS_MEMBER(sp) MCP_HAS_MEMBER(lf) MCP_HAS_MEMBER(tb)
 #undef MCP_HAS_MEMBER
 
 struct PathArgs {
@@ -395,6 +395,27 @@ __device__ __forceinline__ clife_p life_args(const A&) {
   else return nullptr;
 }
 
+// Tolerance bands (SPEC.md 4.18): the rebalancing walk reviews every `period` steps and trades a path back to W only when a watched
+// asset of that path has drifted out of its band.  `tol` is the table of the pass's portfolios in the packed weights' layout ([K][N4],
+// behind the launch's packed block; an unwatched entry is +0), `watch` the 64-bit masks of the watched assets as [K][2] words (low,
+// high).  Both, and the outputs, are read from the kernel arguments where they are used, as scalar loads.
+struct BandArgs {
+  const float* __restrict__ tol;      // [K][N4]
+  const uint32_t* __restrict__ watch; // [K][2]: bit i of the mask is set iff i < N and tol[k][i] < +inf
+  uint32_t* __restrict__ trades;      // [K][trades_stride] c
+  uint64_t trades_stride;
+  float* __restrict__ turnover;       // [K][turnover_stride] Y
+  uint64_t turnover_stride;
+};
+// Arguments of mc_paths_band_kernel: those of mc_paths_reb_kernel (period: the review period) and the band block behind them.
+struct PathArgsTB : PathArgsRB { BandArgs tb; };
+typedef const __attribute__((address_space(4))) BandArgs* cband_p;
+template <class A>
+__device__ __forceinline__ cband_p band_args(const A&) {
+  if constexpr (has_tb<A>::value) return &kernarg<A>()->tb;
+  else return nullptr;
+}
+
 // Floor protection (SPEC.md 4.15): CPPI with an exposure cap and a drawdown ratchet.  Per path and portfolio the walk carries V and the
 // peak M (both from v0); step t holds E = fmaxf(fminf(fl32(m (V - F)), fl32(b V)), +0) in the risky portfolio, F = fmaxf(S_t,
 // fl32(theta M)), and V - E at the riskless rate: V' = fma(E, rho, fma(V - E, rf, V)).  `floor` is the schedule S_0 .. S_T behind the
@@ -485,6 +506,7 @@ struct PathLaunchArgs {
   ProtectArgs pi;
   SpendArgs sp;
   LifeArgs lf;
+  BandArgs tb;
 };
 template <class A>
 inline A make_args(const PathLaunchArgs& s) {
@@ -507,6 +529,7 @@ inline A make_args(const PathLaunchArgs& s) {
   if constexpr (has_pi<A>::value) x.pi = s.pi;
   if constexpr (has_sp<A>::value) x.sp = s.sp;
   if constexpr (has_lf<A>::value) x.lf = s.lf;
+  if constexpr (has_tb<A>::value) x.tb = s.tb;
   if constexpr (has_p_hi<A>::value) { x.p_hi = (uint32_t)(s.hz.path_begin >> 32); x.pad = 0u; }
   return x;
 }
@@ -615,14 +638,16 @@ constexpr int PATH_BLOCK = 256;
 // riskless rate (SPEC.md 4.15).  SP (with CF and HZ): the flow of the step is the path's own withdrawal w instead of the schedule's c_s,
 // the walk also carries w and the total paid out Y, and the reviews of w are wave-uniform events merged with the horizons as the glide
 // walk merges its breaks (SPEC.md 4.16).  LT (with CF): the step also counts, on the mask it already forms, the steps that stored a
-// positive V -- the lifetime l of SPEC.md 4.17 -- and l is stored next to V_T.  Every kernel
+// positive V -- the lifetime l of SPEC.md 4.17 -- and l is stored next to V_T.  TB (with REB, one portfolio): a rebalance date is a
+// review, at which only the lanes with a watched asset out of its band trade; the walk also carries the trade count c and the turnover
+// Y and stores them next to V_T (SPEC.md 4.18).  Every kernel
 // below is the body in mcp_paths_body.inc under its own flags F: it names the flags it sets, the rest are PathFlagsOff's.  F is a
 // local class, which may not have static data members, so it sets its flags as enumerators of an `enum : bool`; they hide the
 // defaults' names and read as the same constant expressions.
 struct PathFlagsOff {
   static constexpr bool NATIVE = false, FOLD = false, LOGC = false, DD = false, HZ = false, BOOT = false, BLDS = false, REB = false,
                         STT = false, CF = false, OV = false, GV = false, AT = false, ANTI = false, FH = false, UHI = false, JP = false, RS = false,
-                        GP = false, PI = false, SP = false, LT = false;
+                        GP = false, PI = false, SP = false, LT = false, TB = false;
 };
 
 // __launch_bounds__ 2nd argument of a path kernel: the MCP_MIN_WAVES* above for N <= 16 and one path per lane, by the kind of
@@ -692,6 +717,17 @@ __global__ void MCP_BOUNDS(BK_PATHS) mc_paths_boot_hz_kernel(const PathArgsBTHZ 
 template <int NB, int KT, int PPT, bool BOOT_, bool BLDS_>
 __global__ void MCP_BOUNDS(BK_REB) mc_paths_reb_kernel(const PathArgsRB a) {
   struct F : PathFlagsOff { enum : bool { REB = true, BOOT = BOOT_, BLDS = BLDS_ }; };
+#include "mcp_paths_body.inc"
+}
+
+// The tolerance-band kernel (SPEC.md 4.18): mc_paths_reb_kernel's walk with the trade of a date decided per path.  The returns B since
+// a path's last trade belong to one portfolio -- under section 4.5 every portfolio of a pass trades on the same dates and shares them,
+// under bands each trades on its own -- so there is no 8-portfolio instance: K portfolios run as K passes of this kernel, K walks of
+// the draws.  It keeps the rebalancing kernel's launch bounds: c, Y and the hit mask fit the 96 VGPRs of 5 waves, and no listing
+// shows scratch in a loop over t (profiles/band_isa.txt).
+template <int NB, int KT, int PPT, bool BOOT_, bool BLDS_>
+__global__ void MCP_BOUNDS(BK_REB) mc_paths_band_kernel(const PathArgsTB a) {
+  struct F : PathFlagsOff { enum : bool { REB = true, TB = true, BOOT = BOOT_, BLDS = BLDS_ }; };
 #include "mcp_paths_body.inc"
 }
 

@@ -5,7 +5,7 @@
 // derived from it) and the kernel argument `a` (PathArgs or a struct that starts with one).
   constexpr bool NATIVE = F::NATIVE, FOLD = F::FOLD, LOGC = F::LOGC, DD = F::DD, HZ = F::HZ, BOOT = F::BOOT, BLDS = F::BLDS, REB = F::REB,
                  STT = F::STT, CF = F::CF, OV = F::OV, GV = F::GV, AT = F::AT, ANTI = F::ANTI, FH = F::FH, UHI = F::UHI, JP = F::JP, RS = F::RS,
-                 GP = F::GP, PI = F::PI, SP = F::SP, LT = F::LT;
+                 GP = F::GP, PI = F::PI, SP = F::SP, LT = F::LT, TB = F::TB;
   static_assert(!UHI || (KT == 1 && PPT == 1 && !(NATIVE || FOLD || DD || HZ || BOOT || REB || STT || CF || OV || GV || AT || ANTI || FH || JP || RS || PI)),
                 "uniform high counter word: the plain Gaussian walk of one portfolio only");
   static_assert(!FH || (BOOT && HZ && !(LOGC || REB || CF || STT || GV || OV || AT || DD || PI)), "filtered rows: the bootstrap's segmented walk only");
@@ -20,6 +20,7 @@
   static_assert(!SP || (CF && HZ && !(NATIVE || FOLD || LOGC || DD || REB || OV || GV || AT || ANTI || FH || UHI || JP || RS || GP || PI)),
                 "spending rule: the cash-flow kernel's segmented walk only");
   static_assert(!LT || (CF && (GP || SP)), "lifetime: the glide and spending kernels' walks only");
+  static_assert(!TB || (REB && KT == 1), "tolerance bands: the rebalancing kernel's walk, one portfolio per pass");
   constexpr int N4 = 4 * NB;
   // ANTI (SPEC.md 2.3): a lane's PPT draws feed EM = 2 PPT members -- slot e < PPT walks on z[e], slot PPT + e on -z[e]; p, live and
   // the counters are per draw (a.path_begin and a.n_paths count pairs), the members 2 p and 2 p + 1 are adjacent in the output rows
@@ -147,6 +148,8 @@
     float Mk[EM][KT];                                     // PI: the running peak M of SPEC.md 4.15, V_0 included
     float Wd[PPT][KT], Yk[PPT][KT];                       // SP: the per-step withdrawal w and the total paid out Y of SPEC.md 4.16
     uint32_t Lk[PPT][KT];                                 // LT: the steps that stored a positive V, the lifetime l of SPEC.md 4.17
+    uint32_t Tc[PPT];                                     // TB: the trade count c of SPEC.md 4.18
+    float Ty[PPT];                                        // TB: the turnover Y of SPEC.md 4.18
 #pragma unroll
     for (int e = 0; e < PPT; e++) {
       p[e] = tl * tile + (uint64_t)e * PATH_BLOCK + threadIdx.x;
@@ -176,6 +179,7 @@
 #pragma unroll
         for (int m = 0; m < N4 / 2; m++) Bs[e][m] = f32x2{0.0f, 0.0f};
       }
+      if constexpr (TB) { Tc[e] = 0u; Ty[e] = 0.0f; }     // per tile, as B is: a second grid-stride tile starts from zero
       if constexpr (AT) {
 #pragma unroll
         for (int m = 0; m < N4 / 2; m++) At[e][m] = f32x2{0.0f, 0.0f};
@@ -251,6 +255,62 @@
           for (int e = 0; e < PPT; e++)
 #pragma unroll
             for (int k = 0; k < KT; k++) V[e][k] = vh[e][k];
+        } else if constexpr (TB) {
+          if (t == nd) {
+            // SPEC.md 4.18: a review.  A lane trades when a watched asset is out of its band: |W_i| |B_i - rho^| >= tol_i (1 + rho^),
+            // an IEEE compare (false on a NaN).  The mask bit and the tolerance are scalar loads, the test of the bit is wave-uniform, and an
+            // unwatched asset forms no compare.  The trade is section 4.5's on the lanes that hit, by selects; a wave without a hit skips it.
+            const cband_p bk = band_args(a);
+            typedef const __attribute__((address_space(4))) uint32_t* cword_p;
+            const cword_p wm = (cword_p)bk->watch + 2 * a.k_begin;
+            const uint32_t w_lo = wm[0], w_hi = wm[1];
+            cfloat_p tl = (cfloat_p)bk->tol + (size_t)a.k_begin * N4;
+            bool hit[PPT];
+#pragma unroll
+            for (int e = 0; e < PPT; e++) hit[e] = false;
+            asm volatile("" : "+s"(Wk));
+#pragma unroll
+            for (int i = 0; i < N4; i++) {
+              if (((i < 32 ? w_lo : w_hi) >> (i & 31)) & 1u) {
+                const float aw = fabsf(Wk[i]), tol = tl[i];
+#pragma unroll
+                for (int e = 0; e < PPT; e++) {
+                  const float d = fabsf(((i & 1) ? Bs[e][i / 2].y : Bs[e][i / 2].x) - rh[e][0]);
+                  const float x = aw * d;
+                  const float g = fma32(tol, rh[e][0], tol);
+                  hit[e] = hit[e] || x >= g;
+                }
+              }
+            }
+            unsigned long long any = 0ull;
+#pragma unroll
+            for (int e = 0; e < PPT; e++) any |= __ballot(hit[e]);
+            if (any != 0ull) {                               // wave-uniform
+              const float kap = kernarg<PathArgsTB>()->cost;
+              asm volatile("" : "+s"(Wk));
+#pragma unroll
+              for (int e = 0; e < PPT; e++) {
+                float tau = 0.0f;
+#pragma unroll
+                for (int m = 0; m < N4 / 2; m++) {
+                  tau = fma32(fabsf(Wk[2 * m]), fabsf(Bs[e][m].x - rh[e][0]), tau);
+                  tau = fma32(fabsf(Wk[2 * m + 1]), fabsf(Bs[e][m].y - rh[e][0]), tau);
+                }
+                const float rp = kap > 0.0f ? fma32(-kap, tau, rh[e][0]) : rh[e][0];
+                const float vt = fma32(V[e][0], rp, V[e][0]);
+                V[e][0] = hit[e] ? vt : V[e][0];
+#pragma unroll
+                for (int m = 0; m < N4 / 2; m++) {
+                  Bs[e][m].x = hit[e] ? 0.0f : Bs[e][m].x;
+                  Bs[e][m].y = hit[e] ? 0.0f : Bs[e][m].y;
+                }
+                Tc[e] += hit[e] ? 1u : 0u;
+                Ty[e] = hit[e] ? Ty[e] + tau : Ty[e];
+              }
+            }
+            const int per = kernarg<PathArgsTB>()->period;
+            nd = per < T - t ? t + per : T;
+          }
         } else if (t == nd) {                              // a rebalance date: the trade back to W
           const auto cs = kernarg<PathArgsRB>();
           const float kap = cs->cost;
@@ -479,6 +539,11 @@
               if constexpr (ANTI) *(float2*)&dk->mdd[(size_t)(a.k_begin + k) * dk->mdd_stride + 2 * p[e]] = make_float2(Qk[e][k], Qk[PPT + e][k]);
               else dk->mdd[(size_t)(a.k_begin + k) * dk->mdd_stride + p[e]] = Qk[e][k];
             }
+        }
+        if constexpr (TB) {                                // c and Y of SPEC.md 4.18, next to V_T
+          const cband_p bk = band_args(a);
+          bk->trades[(size_t)a.k_begin * bk->trades_stride + p[e]] = Tc[e];
+          bk->turnover[(size_t)a.k_begin * bk->turnover_stride + p[e]] = Ty[e];
         }
         if constexpr (LT) {                                // l of SPEC.md 4.17, next to V_T
           const clife_p lk = life_args(a);

@@ -126,9 +126,14 @@ static hipError_t ladder(const PathKernel& k, const PathLaunchArgs& s, hipStream
       MCP_ROW(bg && !lg, mc_paths_boot_hz_kernel<NB, KT, 1, false, false>);
       break;
     case FAM_REB:
-      MCP_ROW(gauss && !lg, mc_paths_reb_kernel<NB, KT, 1, false, false>);
-      MCP_ROW(bl && !lg, mc_paths_reb_kernel<NB, KT, 1, true, true>);
-      MCP_ROW(bg && !lg, mc_paths_reb_kernel<NB, KT, 1, true, false>);
+      MCP_ROW(gauss && !lg && !k.tb, mc_paths_reb_kernel<NB, KT, 1, false, false>);
+      MCP_ROW(bl && !lg && !k.tb, mc_paths_reb_kernel<NB, KT, 1, true, true>);
+      MCP_ROW(bg && !lg && !k.tb, mc_paths_reb_kernel<NB, KT, 1, true, false>);
+      if constexpr (KT == 1) {                             // SPEC.md 4.18: tolerance bands, every K as passes of one portfolio
+        MCP_ROW(gauss && !lg && k.tb, mc_paths_band_kernel<NB, 1, 1, false, false>);
+        MCP_ROW(bl && !lg && k.tb, mc_paths_band_kernel<NB, 1, 1, true, true>);
+        MCP_ROW(bg && !lg && k.tb, mc_paths_band_kernel<NB, 1, 1, true, false>);
+      }
       break;
     case FAM_CF:
       MCP_ROW(gauss && !lg && !k.gp && !k.sp && !k.lt, mc_paths_cf_kernel<NB, KT, 1, false, false, false>);
@@ -172,6 +177,8 @@ hipError_t MCP_CAT(launch_paths_nb, MCP_NB)(const PathKernel& k, const PathLaunc
   if (k.pi && (k.fold || k.uhi || k.native || k.anti || k.fh || k.rs || k.gp || k.family == FAM_AT)) return hipErrorInvalidValue;
   if (k.sp && (k.family != FAM_CF || k.fold || k.uhi || k.native || k.anti || k.fh || k.jp || k.rs || k.gv || k.gp || k.pi)) return hipErrorInvalidValue;
   if (k.lt && (k.family != FAM_CF || k.gp == k.sp || k.fold || k.uhi || k.native || k.anti || k.fh || k.jp || k.rs || k.gv || k.pi)) return hipErrorInvalidValue;
+  if (k.tb && (k.family != FAM_REB || k.kt8 || k.fold || k.uhi || k.native || k.anti || k.fh || k.jp || k.rs || k.gv || k.stt || k.gp || k.pi || k.sp || k.lt))
+    return hipErrorInvalidValue;
   if (k.fold) {                                            // rho = c + v.z: the plain Gaussian walk on the spec's normals
     const bool ok = k.family == FAM_PLAIN && !k.boot && !k.stt && !k.gv && !k.native && !k.kt8;
     MCP_ROW(ok && k.logc, mc_paths_kernel<NB, 1, 1, false, true, true>);

@@ -70,13 +70,14 @@ struct PathLaunchArgs;
 // gp (FAM_CF only: the glide-path kernel, the cash-flow walk on scheduled target weights, SPEC.md 4.14), and pi (the floor-protection
 // kernel of SPEC.md 4.15: FAM_DD with the drawdown, else FAM_HZ, H = 0 included; stt and gv both set for the GARCH walk, or jp), and
 // sp (FAM_CF only: the spending kernel, the cash-flow walk on the path's own withdrawal, SPEC.md 4.16), and lt (with exactly one of
-// gp and sp: that kernel's lifetime twin, SPEC.md 4.17; a plain cash-flow request asks for the glide twin with no break).
+// gp and sp: that kernel's lifetime twin, SPEC.md 4.17; a plain cash-flow request asks for the glide twin with no break), and tb
+// (FAM_REB only, never kt8: the tolerance-band kernel of SPEC.md 4.18, K portfolios as K passes of one).
 // The one ladder of mcp_paths_inst.hip maps it to a kernel and lists which selectors have one.
 constexpr int LEAN_MAX_NB = 4;
 enum PathFamily { FAM_PLAIN, FAM_DD, FAM_HZ, FAM_REB, FAM_CF, FAM_OV, FAM_AT };
 struct PathKernel {
   int family;
-  bool logc, boot, blds, stt, dd, gv, kt8, native, fold, anti, fh, uhi, jp, rs, gp, pi, sp, lt;
+  bool logc, boot, blds, stt, dd, gv, kt8, native, fold, anti, fh, uhi, jp, rs, gp, pi, sp, lt, tb;
 };
 
 // mcp_paths_inst.hip (one translation unit per NB): every pass of the kernel that `k` selects, on the blocks of `args` that the

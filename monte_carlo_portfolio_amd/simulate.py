@@ -55,10 +55,15 @@ _ENTRY_CHOICE = (
 # whatever the table above would choose, and a keyword that entry point has no argument group for is refused with this sentence.
 _LIFE_CHOICE = ("mcp_simulate_lifetime", "lifetime is not combined with protect, drawdown, rebalance, overlay, garch, jumps, regimes, "
                                          "filtered rows, attribution or antithetic")
+# Tolerance bands (SPEC.md 4.18) take the rebalancing rule's place: with `tolerance` the call takes this entry point, whatever the table
+# above would choose, and a keyword that entry point has no argument group for is refused with this sentence.  (It is not the first
+# row of _ENTRY_CHOICE: tests/test_spend_cpu.py pins that row.)
+_BAND_CHOICE = ("mcp_simulate_banded", "tolerance is not combined with drawdown, cashflow, glide, protect, spending, overlay, dof, garch, "
+                                       "jumps, regimes, filtered rows, attribution or antithetic")
 # the argument group of _ffi.SIMULATE_ENTRIES that carries each feature keyword of Context._call
 _KEYWORD_GROUP = {"rows": "bt", "dof": "st", "period": "rb", "drawdown": "dd", "horizons": "hz_in", "flows": "cf", "overlay": "ov",
                   "garch": "gv", "attribution": "attr", "antithetic": "pairs", "filtered": "ft", "jumps": "jp", "regimes": "rs",
-                  "glide": "gl", "protect": "pt", "spending": "sp", "lifetime": "life"}
+                  "glide": "gl", "protect": "pt", "spending": "sp", "lifetime": "life", "tolerance": "tb"}
 
 
 class Context:
@@ -106,8 +111,8 @@ class Context:
     def _call(self, prm: _ffi.McpParams, W, seed: int, path_begin: int, n_paths: int, store: bool, mu=None, chol=None, rows=None,
               block: float = 1.0, dof=None, period=None, cost: float = 0.0, drawdown: bool = False, horizons=None, levels=(),
               flows=None, target=None, overlay=None, garch=None, attribution=False, antithetic=False, filtered=None, jumps=None, regimes=None,
-              glide=None, protect=None, spending=None, lifetime=None):
-        """The one library call behind every simulate_* method: the lifetime (lifetime: the levels in percent of its order statistics, SPEC.md 4.17 / 5.17; needs flows or spending), a spending rule (spending: the (rate, every, down, up, inflation, first or None) of check_spending; `target` is then its second count), floor protection (protect: the (floor, multiplier, rate, cap, ratchet) of check_protect; `target` is then its second count), two regimes (regimes: the (p01, p10, start, mu1, chol1) of check_regimes), market jumps (jumps: the (intensity, mean, std, loading or None) of check_jumps), GARCH volatility (garch: the (alpha, beta, h0) of check_garch), an option overlay (overlay: the triple of check_overlay), cash flows (flows, target), Student-t draws (dof), rebalancing
+              glide=None, protect=None, spending=None, lifetime=None, tolerance=None):
+        """The one library call behind every simulate_* method: tolerance bands (tolerance: (every, cost, tol float32 [K, N], levels in percent of the trade counts' order statistics), SPEC.md 4.18 / 5.18; the rule carries its own period and cost, so not with `period`), the lifetime (lifetime: the levels in percent of its order statistics, SPEC.md 4.17 / 5.17; needs flows or spending), a spending rule (spending: the (rate, every, down, up, inflation, first or None) of check_spending; `target` is then its second count), floor protection (protect: the (floor, multiplier, rate, cap, ratchet) of check_protect; `target` is then its second count), two regimes (regimes: the (p01, p10, start, mu1, chol1) of check_regimes), market jumps (jumps: the (intensity, mean, std, loading or None) of check_jumps), GARCH volatility (garch: the (alpha, beta, h0) of check_garch), an option overlay (overlay: the triple of check_overlay), cash flows (flows, target), Student-t draws (dof), rebalancing
         (period, cost), bootstrap rows (rows, block) or Gaussian draws (mu, chol), with the drawdown or horizons.  Allocates the
         outputs that were asked for and passes NULL for the rest -> _Outputs, None where not asked for (terminal, qd,
         horizon_terminal: with `store` only; counts, hz_counts: with `flows` only; attr [K, N] records of ATTR_DTYPE and attr_counts
@@ -121,10 +126,11 @@ class Context:
                                    ("antithetic", antithetic), ("filtered", filtered is not None), ("jumps", jumps is not None),
                                    ("regimes", regimes is not None), ("glide", glide is not None),
                                    ("protect", protect is not None), ("spending", spending is not None),
-                                   ("lifetime", lifetime is not None)) if on]
+                                   ("lifetime", lifetime is not None), ("tolerance", tolerance is not None)) if on]
         has = set(given).issuperset
-        entry, refusal = _LIFE_CHOICE if lifetime is not None else next((e, r) for needs, e, r in _ENTRY_CHOICE if has(needs))
-        groups = next(t[entry] for t in (_ffi.SIMULATE_ENTRIES, _ffi.EXTENSION_ENTRIES, _ffi.SPEND_ENTRIES, _ffi.LIFE_ENTRIES) if entry in t)
+        entry, refusal = _BAND_CHOICE if tolerance is not None else _LIFE_CHOICE if lifetime is not None else next((e, r) for needs, e, r in _ENTRY_CHOICE if has(needs))
+        groups = next(t[entry] for t in (_ffi.SIMULATE_ENTRIES, _ffi.EXTENSION_ENTRIES, _ffi.SPEND_ENTRIES, _ffi.LIFE_ENTRIES,
+                                            _ffi.BAND_ENTRIES) if entry in t)
         # the library states the rules (check_request); a keyword the entry point has no argument for is refused here, not dropped
         for kw in given:
             if _KEYWORD_GROUP[kw] not in groups:
@@ -161,6 +167,17 @@ class Context:
             life_hist = np.zeros((K, prm.n_steps + 1), np.uint64)
             life_sum = np.zeros(K, np.uint64)
             life_q = np.zeros((K, life_lv.size), np.uint32)
+        trades = trade_hist = trade_sum = trade_q = trade_lv = turnover = turnover_stats = tol = None
+        if tolerance is not None:
+            from .tolerance import n_reviews
+            tol = np.ascontiguousarray(tolerance[2], np.float32)
+            trade_lv = np.ascontiguousarray(tolerance[3], np.float64).ravel()
+            trades = np.empty((K, n_paths), np.uint32) if store else None
+            turnover = np.empty((K, n_paths), np.float32) if store else None
+            trade_hist = np.zeros((K, n_reviews(prm.n_steps, tolerance[0]) + 1), np.uint64)
+            trade_sum = np.zeros(K, np.uint64)
+            trade_q = np.zeros((K, trade_lv.size), np.uint32)
+            turnover_stats = np.zeros(K, _ffi.STATS_DTYPE)
         vals = {"ctx": (self._h,), "prm": (prm,), "mu": (mu,), "chol": (chol,), "W": (W,), "walk": (seed, path_begin, n_paths),
                 "hz_in": (H, steps if H else None, L, lv if L else None), "out": (term, stats), "dd": (raw, dd_stats),
                 "hz_out": (hz_term, hz_stats, bands if L else None), "counts": (counts,), "hz_counts": (hz_counts,), "pairs": (pairs,),
@@ -169,6 +186,10 @@ class Context:
                 "sp": (_ffi.make_spending(*spending, target=target) if spending is not None else None,), "wd": (withdrawn, wd_stats),
                 "life": (life, life_hist, life_sum, 0 if life_lv is None else life_lv.size, life_lv if life_lv is not None and life_lv.size else None,
                          life_q if life_lv is not None and life_lv.size else None),
+                "tb": (_ffi.make_band(tolerance[0], tolerance[1], tol) if tolerance is not None else None,),
+                "trades": (trades, trade_hist, trade_sum, 0 if trade_lv is None else trade_lv.size,
+                           trade_lv if trade_lv is not None and trade_lv.size else None, trade_q if trade_lv is not None and trade_lv.size else None,
+                           turnover, turnover_stats),
                 "gl": (_ffi.make_glide(*glide) if glide is not None else None,),               # flows None: the all-zero schedule
                 "cf": (_ffi.make_cashflow(flows, target) if flows is not None else None,),
                 "rb": (_ffi.McpRebalance(int(period), 0, float(cost)) if period is not None else None,),
@@ -186,7 +207,18 @@ class Context:
         rc = getattr(_ffi.lib(), entry)(*(arg(g, v) for g in groups for v in vals[g.rstrip("*")]))
         _ffi.check(rc)
         return _Outputs(stats, dd_stats, hz_stats, bands, term, raw, hz_term, counts, hz_counts, attr, attr_counts, contrib, pairs,
-                        wd_stats, withdrawn, life_hist, life_sum, life_q, life)
+                        wd_stats, withdrawn, life_hist, life_sum, life_q, life, trade_hist, trade_sum, trade_q, trades, turnover_stats, turnover)
+
+    def simulate_banded(self, prm: _ffi.McpParams, every: int, cost: float, tol, W, seed: int, path_begin: int, n_paths: int, store: bool,
+                        levels=(5.0, 50.0, 95.0), mu=None, chol=None, rows=None, block: float = 1.0, horizons=None, bands=()):
+        """simulate_rebalanced() with the trade of every review decided per path by the tolerance table `tol` [K, N] (SPEC.md 4.18 / 5.18;
+        include/mcport_band.h, mcp_simulate_banded): `every` is the review period (0: never), `cost` the proportional cost.  `levels`:
+        the percentages of the trade counts' order statistics; `bands`: the levels of the horizons' bands.  -> _Outputs of
+        simulate_rebalanced with trade_hist [K, n_reviews + 1] uint64, trade_sum [K] uint64, trade_q [K, len(levels)] uint32,
+        turnover_stats [K] mcp_stats records over Y - 1 and, with `store`, trades [K, n_paths] uint32 and turnover [K, n_paths]
+        binary32."""
+        return self._call(prm, W, seed, path_begin, n_paths, store, mu=mu, chol=chol, rows=rows, block=block, horizons=horizons, levels=bands,
+                          tolerance=(int(every), float(cost), np.ascontiguousarray(tol, np.float32), np.asarray(levels, np.float64).ravel()))
 
     def simulate_lifetime(self, prm: _ffi.McpParams, W, seed: int, path_begin: int, n_paths: int, store: bool, levels=(5.0, 25.0, 50.0),
                           flows=None, glide=None, spending=None, mu=None, chol=None, rows=None, block: float = 1.0, dof=None, target=None,
@@ -367,7 +399,8 @@ class Context:
 # binary32 contributions [K, N, n].  With antithetic pairs the records of SPEC.md 5.10 (pairs [K] of PAIR_DTYPE).  With a spending rule
 # the record of the total paid out (wd_stats [K]) and, stored, the binary32 withdrawn [K, n] (SPEC.md 5.16).
 _Outputs = collections.namedtuple("_Outputs", "stats dd_stats hz_stats bands terminal qd horizon_terminal counts hz_counts attr "
-                                  "attr_counts contributions pairs wd_stats withdrawn life_hist life_sum life_q life", defaults=(None,) * 12)
+                                  "attr_counts contributions pairs wd_stats withdrawn life_hist life_sum life_q life trade_hist trade_sum trade_q trades "
+                                  "turnover_stats turnover", defaults=(None,) * 18)
 
 
 def check_cashflow(cashflow, target, n_steps):
@@ -913,6 +946,9 @@ def antithetic_to_dict(rec) -> dict:
 # checked, so the same rule wins when two apply.  The C side states the same rules for the library (check_request).
 _FLAGS = ("drawdown", "attribution", "antithetic", "fold", "native_math")
 _PATHS_COMBINE = {
+    "tolerance": ("tolerance needs the rebalancing walk -- Gaussian draws, simple compounding, the spec's normals and the unfolded recurrence",
+                  ("drawdown", "cashflow", "glide", "protect", "spending", "overlay", "dof", "garch", "jumps", "regimes", "attribution",
+                   "antithetic", "fold", "native_math", "compounding='log'"), True),
     "spending": ("spending needs the cashflow walk without a schedule -- constant weights, simple compounding, the spec's normals and the "
                  "unfolded recurrence",
                  ("cashflow", "glide", "protect", "drawdown", "rebalance", "overlay", "garch", "jumps", "regimes", "attribution", "antithetic",
@@ -948,6 +984,8 @@ _PATHS_COMBINE = {
 }
 # simulate_bootstrap: the same two features on observed rows
 _BOOTSTRAP_COMBINE = {
+    "tolerance": ("tolerance needs the rebalancing walk and simple compounding",
+                  ("cashflow", "glide", "spending", "compounding='log'"), True),
     "spending": ("spending needs the cashflow walk without a schedule, constant weights and simple compounding",
                  ("cashflow", "glide", "rebalance", "compounding='log'"), True),
     "glide": ("glide needs the cashflow walk and simple compounding", ("rebalance", "compounding='log'"), False),
@@ -976,7 +1014,7 @@ def simulate_paths(mu, cov, weights, n_steps=252, n_paths=10_000, seed=0, v0=1.0
                    native_math=False, as_array=False, fold=False, shard="auto", context=None, drawdown=False,
                    horizons=None, bands=(), rebalance=None, rebalance_cost=0.0, dof=None, cashflow=None, target=None,
                    overlay=None, spot=None, garch=None, attribution=False, antithetic=False, jumps=None, regimes=None, glide=None,
-                   protect=None, spending=None, lifetime=False, lifetime_levels=(5, 25, 50)):
+                   protect=None, spending=None, lifetime=False, lifetime_levels=(5, 25, 50), tolerance=None, tolerance_levels=(5, 50, 95)):
     """Simulate `n_paths` correlated return paths and reduce them to risk statistics.
 
     mu [N], cov [N,N] are per-step mean and covariance (the reference's `mean_returns`, `cov_matrix`
@@ -1160,11 +1198,39 @@ def simulate_paths(mu, cov, weights, n_steps=252, n_paths=10_000, seed=0, v0=1.0
     life_q[, life].  All integers are exact and independent of devices and tiles.  Not built: lifetime without cashflow or spending
     (a walk without ruin; glide alone included), with protect, drawdown, rebalance, overlay, garch, jumps, regimes, attribution or
     antithetic (ValueError), on filtered rows, in simulate_sweep, in PathEngine and at the mcp_launch_* level.
+
+    tolerance=None (default): `rebalance` trades on the calendar.  tolerance=a number, [N], [K, N] or tolerance_bands(...): tolerance-band
+    rebalancing (SPEC.md 4.18 / 5.18).  `rebalance` becomes the review period (None: every step; "never": no review): at a review a
+    path is traded back to `weights`, at rebalance_cost, only when an asset's weight is off its target by its tolerance or more (inf: the
+    asset is not watched); a path inside its bands changes nothing.  tolerance=0 is rebalance=k bit for bit, tolerance=inf is
+    rebalance="never".  Every dict gains 'tolerance' {every, n_reviews, table float64 [N], trades {hist uint64 [n_reviews + 1] (#{c ==
+    s}), mean, q {level: trades} for tolerance_levels in percent (np.percentile(c, q, method="lower")) and, with store=True, paths uint32
+    [n_paths]}, turnover {mean, std, var, cvar, min, max, n_tail, x_lo, x_hi of the total two-sided fraction of value traded per path
+    and, with store=True, paths float32 [n_paths]}}; as_array appends trade_hist, trade_sum, trade_q, turnover_stats (over Y - 1)[,
+    trades, turnover].  The counts are exact and independent of devices and tiles.  Every portfolio is a walk of its own: K portfolios
+    cost K walks.  Combines with horizons / bands, store, as_array, devices, path_begin and bootstrap rows (simulate_bootstrap).  Not
+    built: tolerance with drawdown, cashflow, glide, protect, spending, overlay, dof, garch, jumps, regimes, attribution, antithetic, fold,
+    native_math or compounding="log" (ValueError), on filtered rows, in simulate_sweep, in PathEngine and at the mcp_launch_* level.
     """
     from .lifetime import check_lifetime
     lt = check_lifetime(lifetime, lifetime_levels, n_steps)
     if lt is not None and cashflow is None and spending is None:
         raise ValueError("lifetime needs a walk with ruin: cashflow (with or without glide) or spending")
+    if tolerance is not None:
+        kw = dict(tolerance=tolerance, spending=spending, protect=protect, glide=glide, regimes=regimes, jumps=jumps, antithetic=antithetic,
+                  attribution=attribution, garch=garch, overlay=overlay, cashflow=cashflow, dof=dof, drawdown=drawdown, fold=fold,
+                  native_math=native_math, compounding=compounding)
+        _check_combines(_PATHS_COMBINE, "tolerance", kw)
+        period, cost = check_rebalance(1 if rebalance is None else rebalance, rebalance_cost)
+        steps, levels = _check_walk(n_steps, horizons, bands, period, compounding, shard)
+        mu32, L, W = prepare_inputs(mu, cov, weights, chol)
+        from .tolerance import check_tolerance
+        tol, tlv = check_tolerance(tolerance, tolerance_levels, W.shape, n_steps, period)
+        prm, ctx = _setup(mu32.shape[0], n_steps, W.shape[0], compounding, v0, alpha, rf, False, False, devices, shard, context)
+        out = ctx._call(prm, W, int(seed), int(path_begin), int(n_paths), store, mu=mu32, chol=L, horizons=steps, levels=levels,
+                        tolerance=(period, cost, tol, tlv))
+        return _with_tolerance(_result(out, np.asarray(weights).ndim == 1, store, as_array, steps, levels, compounding), out, tol, period,
+                               tlv, store, as_array)
     kw = dict(spending=spending, protect=protect, glide=glide, regimes=regimes, jumps=jumps, antithetic=antithetic, attribution=attribution, garch=garch, overlay=overlay,
               cashflow=cashflow, dof=dof, rebalance=rebalance, drawdown=drawdown, horizons=horizons, fold=fold, native_math=native_math,
               compounding=compounding, shard=shard)
@@ -1250,6 +1316,18 @@ def simulate_paths(mu, cov, weights, n_steps=252, n_paths=10_000, seed=0, v0=1.0
         for d in [res] if isinstance(res, dict) else res:
             d["regimes"] = dict(blk)
     return res if lt is None else _with_lifetime(res, out, lt, store, as_array)
+
+
+def _with_tolerance(res, out, tol, every, levels, store, as_array):
+    """The result of a call with its band outputs (SPEC.md 5.18): as_array appends trade_hist, trade_sum, trade_q, turnover_stats[,
+    trades, turnover]; else every dict gains the 'tolerance' block."""
+    from .tolerance import tolerance_blocks
+    if as_array:
+        return ((res if isinstance(res, tuple) else (res,)) + (out.trade_hist, out.trade_sum, out.trade_q, out.turnover_stats)
+                + ((out.trades, out.turnover) if store else ()))
+    for d, blk in zip([res] if isinstance(res, dict) else res, tolerance_blocks(out, tol, every, levels, store, int(out.stats[0]["n"]))):
+        d["tolerance"] = blk
+    return res
 
 
 def _with_lifetime(res, out, levels, store, as_array):
@@ -1402,7 +1480,7 @@ def bootstrap_inputs(returns, weights):
 def simulate_bootstrap(returns, weights, n_steps=252, n_paths=10_000, block=1.0, seed=0, v0=1.0, compounding="simple",
                        rf=0.0, alpha=0.95, devices=None, store=False, path_begin=0, as_array=False, shard="auto", context=None,
                        horizons=None, bands=(), rebalance=None, rebalance_cost=0.0, cashflow=None, target=None, glide=None, spending=None,
-                       lifetime=False, lifetime_levels=(5, 25, 50), **unsupported):
+                       lifetime=False, lifetime_levels=(5, 25, 50), tolerance=None, tolerance_levels=(5, 50, 95), **unsupported):
     """simulate_paths on paths resampled from the observed return rows instead of a normal model: the stationary block
     bootstrap of Politis & Romano (SPEC.md 2.1 / 4.4).  Every step of a path uses one whole row of `returns` (all assets of one
     date together), so fat tails, skew, the co-movement within a row and -- with a mean block length `block` > 1 -- short-range
@@ -1417,7 +1495,8 @@ def simulate_bootstrap(returns, weights, n_steps=252, n_paths=10_000, block=1.0,
     5.6; not with rebalance or compounding="log").  glide as in simulate_paths (SPEC.md 4.14, pivots of SPEC.md 5.14 on the row
     means; not with rebalance or compounding="log").  spending as in simulate_paths (SPEC.md 4.16, pivots of SPEC.md 5.16 on the
     row means; not with cashflow, glide, rebalance or compounding="log").  lifetime / lifetime_levels as in simulate_paths (SPEC.md
-    4.17 / 5.17; with cashflow, with or without glide, or spending).
+    4.17 / 5.17; with cashflow, with or without glide, or spending).  tolerance / tolerance_levels as in simulate_paths (SPEC.md 4.18 /
+    5.18, pivots of SPEC.md 5.4; not with cashflow, glide, spending or compounding="log").
     """
     from .lifetime import check_lifetime
     lt = check_lifetime(lifetime, lifetime_levels, n_steps)
@@ -1443,6 +1522,22 @@ def simulate_bootstrap(returns, weights, n_steps=252, n_paths=10_000, block=1.0,
         raise ValueError(f"simulate_bootstrap does not take {sorted(unsupported)} (no normals: no fold / native_math / dof -- "
                          "Student-t draws are a parametric model, call simulate_paths(dof=...); drawdown on bootstrap paths is "
                          "not supported)")
+    if tolerance is not None:
+        kw = dict(tolerance=tolerance, spending=spending, glide=glide, cashflow=cashflow, compounding=compounding)
+        _check_combines(_BOOTSTRAP_COMBINE, "tolerance", kw)
+        period, cost = check_rebalance(1 if rebalance is None else rebalance, rebalance_cost)
+        b = float(block)
+        if not b >= 1.0:
+            raise ValueError(f"block (mean block length) must be >= 1 or inf, got {block!r}")
+        steps, levels = _check_walk(n_steps, horizons, bands, period, compounding, shard)
+        rows, W = bootstrap_inputs(returns, weights)
+        from .tolerance import check_tolerance
+        tol, tlv = check_tolerance(tolerance, tolerance_levels, W.shape, n_steps, period)
+        prm, ctx = _setup(rows.shape[1], n_steps, W.shape[0], compounding, v0, alpha, rf, False, False, devices, shard, context)
+        out = ctx._call(prm, W, int(seed), int(path_begin), int(n_paths), store, rows=rows, block=b, horizons=steps, levels=levels,
+                        tolerance=(period, cost, tol, tlv))
+        return _with_tolerance(_result(out, np.asarray(weights).ndim == 1, store, as_array, steps, levels, compounding), out, tol, period,
+                               tlv, store, as_array)
     kw = dict(spending=spending, glide=glide, cashflow=cashflow, rebalance=rebalance, compounding=compounding)
     sv = check_spending(spending, v0)
     _check_combines(_BOOTSTRAP_COMBINE, "spending", kw)
@@ -1570,6 +1665,8 @@ def simulate_sweep(mu, cov, weights=None, n_portfolios=2500, min_weights=None, m
         raise ValueError("simulate_sweep does not take protect: call simulate_paths for the optimum")
     if kw.get("spending") is not None:
         raise ValueError("simulate_sweep does not take spending: call simulate_paths for the optimum")
+    if kw.get("tolerance") is not None:
+        raise ValueError("simulate_sweep does not take tolerance: call simulate_paths for the optimum")
     if kw.get("attribution"):
         raise ValueError("simulate_sweep does not take attribution: call simulate_paths for the optimum")
     kw.pop("attribution", None)
