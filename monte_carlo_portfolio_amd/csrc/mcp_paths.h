@@ -80,6 +80,12 @@
 #ifndef MCP_EXP_LDSPAR      // 1: drift from LDS (default); 2: drift and (one portfolio) weights from LDS; 0: both from SGPRs.  2 was priced at
 #define MCP_EXP_LDSPAR 1    // -2 % by the issue model and measured within +-0.5 % of 1 (profiles/r02_lab5.txt): not to be tried again
 #endif
+#ifndef MCP_EXP_GEMV2       // the lean kernel's factor: 1: row pairs (m, m + 1) in flight together, two accumulators interleaved column by
+#define MCP_EXP_GEMV2 1     // column, every row's own chain kept (bit-identical); 0: one row pair after another (tools/kernel_lab.py arm `feed_base`)
+#endif
+#ifndef MCP_EXP_PRIO        // the lean kernel's wave priority: 1: raised over the factor and the weight dot of every step (s_setprio, two per
+#define MCP_EXP_PRIO 1      // step); 0: never changed (tools/kernel_lab.py arm `gemv2`).  Raised over Philox and the normals instead it cost 4 %,
+#endif                      // and factor loads issued a Philox block ahead gained nothing (profiles/gemv_feed_probe.json): not to be tried again
 
 namespace mcp {
 

@@ -16,7 +16,8 @@
 // the step's market jump J, and the row pair's accumulator starts at fma(b, J, mu) (SPEC.md 2.5 / 4.12).  RS: one more Philox block on
 // counter stream 4 before the asset normals gives the step's regime s_t and the next step's; the row pair's chain runs on (mu, L) where the
 // wave has a lane in regime 0 and then, under `if (s_t)`, on (mu1, L1) -- each a whole chain of its own, nothing shared (SPEC.md 2.6 / 4.13).  UHI: the same step with p_hi a scalar (philox4x32_10_uhi), the drift read through the LDS address
-// par_lds instead of the opaque zero offset, and the blocks scheduled one at a time.  PI: the update of V is the floor rule of SPEC.md
+// par_lds instead of the opaque zero offset, the blocks scheduled one at a time, the factor's row pairs two at a time and the wave's
+// priority raised over the factor (MCP_EXP_GEMV2, MCP_EXP_PRIO).  PI: the update of V is the floor rule of SPEC.md
 // 4.15 on the step's rho, then the peak M.  SP (with CF): the flow is the path's own -w, and the step adds what it pays out to Y
 // (SPEC.md 4.16); the reviews of w are events of the walk, not of the step.  LT (with CF): the mask that selects the step's V also
 // adds one to the lifetime l (SPEC.md 4.17).
@@ -223,8 +224,51 @@
       for (int e = 0; e < EM; e++)
 #pragma unroll
         for (int k = 0; k < KT; k++) rho[e][k] = 0.0f;
+      if constexpr (UHI && MCP_EXP_PRIO != 0) {
+        // The lean kernel: the wave's priority is raised over the factor and the weight dot and dropped again behind the update of V
+        // (two s_setprio per step), a hint to the instruction arbiter that changes no result: measured, not modelled
+        // (profiles/gemv_feed_probe.json).  Nothing is scheduled across the boundary.
+        __builtin_amdgcn_sched_barrier(0);
+        __builtin_amdgcn_s_setprio(1);
+        __builtin_amdgcn_sched_barrier(0);
+      }
       // Rows are processed in pairs (2m, 2m+1): one v_pk_fma_f32 per column does both rows, its L operand
       // an SGPR pair straight from the row-pair-interleaved parameter block, z_j broadcast by op_sel.
+      if constexpr (UHI && MCP_EXP_GEMV2 != 0) {
+        // The lean kernel: row pairs (m, m + 1) in flight together, m even (N4 / 2 = 2 NB is even), their two accumulators interleaved
+        // column by column, so a packed fma is never followed by the one that reads its sum; row pair m + 1's two more columns finish
+        // around row pair m's weights.  Every row keeps its own chain (mu_i, then j ascending) and rho its order (i ascending): the
+        // same bits as the loop below.
+#pragma unroll
+        for (int m = 0; m < N4 / 2; m += 2) {
+          f32x2 c0, c1;
+          if constexpr (LDS_MU) { c0 = *(const f32x2*)&s_par[2 * m]; c1 = *(const f32x2*)&s_par[2 * m + 2]; }
+          else { c0 = f32x2{mu[2 * m], mu[2 * m + 1]}; c1 = f32x2{mu[2 * m + 2], mu[2 * m + 3]}; }
+          const int o0 = 2 * m * (m + 1), o1 = 2 * (m + 1) * (m + 2);       // the row pairs' offsets in the factor block
+#pragma unroll
+          for (int j = 0; j <= 2 * m + 1; j++) {
+            const f32x2 l0 = {Lp[o0 + 2 * j], Lp[o0 + 2 * j + 1]}, l1 = {Lp[o1 + 2 * j], Lp[o1 + 2 * j + 1]};
+            c0 = __builtin_elementwise_fma(l0, (f32x2){z[0][j], z[0][j]}, c0);
+            c1 = __builtin_elementwise_fma(l1, (f32x2){z[0][j], z[0][j]}, c1);
+          }
+          const float w0 = LDS_W ? s_par[N4 + 2 * m] : Wk[2 * m], w1 = LDS_W ? s_par[N4 + 2 * m + 1] : Wk[2 * m + 1];
+          const float w2 = LDS_W ? s_par[N4 + 2 * m + 2] : Wk[2 * m + 2], w3 = LDS_W ? s_par[N4 + 2 * m + 3] : Wk[2 * m + 3];
+          {
+            const int j = 2 * m + 2;
+            const f32x2 l1 = {Lp[o1 + 2 * j], Lp[o1 + 2 * j + 1]};
+            c1 = __builtin_elementwise_fma(l1, (f32x2){z[0][j], z[0][j]}, c1);
+          }
+          rho[0][0] = fma32(w0, c0.x, rho[0][0]);
+          rho[0][0] = fma32(w1, c0.y, rho[0][0]);
+          {
+            const int j = 2 * m + 3;
+            const f32x2 l1 = {Lp[o1 + 2 * j], Lp[o1 + 2 * j + 1]};
+            c1 = __builtin_elementwise_fma(l1, (f32x2){z[0][j], z[0][j]}, c1);
+          }
+          rho[0][0] = fma32(w2, c1.x, rho[0][0]);
+          rho[0][0] = fma32(w3, c1.y, rho[0][0]);
+        }
+      } else {
 #pragma unroll
       for (int m = 0; m < N4 / 2; m++) {
         f32x2 acc[EM];
@@ -326,6 +370,7 @@
         }
         }  // !REB
       }
+      }  // !(UHI && GEMV2)
       }  // !FOLD
       }  // !BOOT
       if constexpr (SP) {
@@ -383,6 +428,7 @@
         for (int k = 0; k < KT; k++)
           V[e][k] = logc ? (V[e][k] + rho[e][k]) : fma32(V[e][k], rho[e][k], V[e][k]);
       }
+      if constexpr (UHI && MCP_EXP_PRIO != 0) __builtin_amdgcn_s_setprio(0);   // the step's other phase boundary
       if constexpr (FH) {
         // SPEC.md 4.11: d = fl32(h s_j), h = fminf(fma(b, h, fma(a, d, omega)), 2^40).  The constants are wave-uniform scalar loads.
         const cfilt_p fk = filt_args(a);

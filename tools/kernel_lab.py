@@ -6,15 +6,20 @@
 
 A name without flags is one of ARMS below: `lean` routes the plain Gaussian walk to mc_paths_lean_kernel where the launch's
 paths share the high counter word, `nolean` keeps every launch on mc_paths_kernel (the code of the tree before the lean
-kernel), `nolean2` is the same build again for an A/A repeat (profiles/lean_probe.json).
+kernel), `nolean2` is the same build again for an A/A repeat (profiles/lean_probe.json).  `feed_base` / `feed_base2` are the lean step
+loop with its factor one row pair after another and no priority change (the A/A pair), `gemv2` two row pairs in flight, `prio_only`
+the wave priority raised over the factor alone, `prio_gemv` both, the product build (profiles/gemv_feed_probe.json).
 """
 import ctypes, os, subprocess, sys, statistics
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 LAB = os.path.join(ROOT, "tools", "lab_build")
 CSRC = os.path.join(ROOT, "monte_carlo_portfolio_amd", "csrc")
+FEED0 = "-DMCP_EXP_GEMV2=0 -DMCP_EXP_PRIO=0"    # the lean step loop of the tree before profiles/gemv_feed_probe.json
 ARMS = {"lean": "-DMCP_EXP_LEAN=1", "nolean": "-DMCP_EXP_LEAN=0", "nolean2": "-DMCP_EXP_LEAN=0",
-        "centred": "-DMCP_EXP_ICDF_CENTRED=1", "base": "-DMCP_EXP_ICDF_CENTRED=0", "base2": "-DMCP_EXP_ICDF_CENTRED=0"}
+        "centred": "-DMCP_EXP_ICDF_CENTRED=1", "base": "-DMCP_EXP_ICDF_CENTRED=0", "base2": "-DMCP_EXP_ICDF_CENTRED=0",
+        "feed_base": FEED0, "feed_base2": FEED0, "gemv2": "-DMCP_EXP_GEMV2=1 -DMCP_EXP_PRIO=0", "prio_only": "-DMCP_EXP_GEMV2=0 -DMCP_EXP_PRIO=1",
+        "prio_gemv": "-DMCP_EXP_GEMV2=1 -DMCP_EXP_PRIO=1"}
 
 
 def build(specs):
