@@ -1,6 +1,7 @@
 // host_selftest.cpp -- drives mcp_host.cpp on heap buffers of exactly the documented lengths, for `make host-selftest`: built
 // with a plain C++ compiler under AddressSanitizer + UBSan, so an overrun of a packer or a pivot rule is a sanitizer report.  It
 // asserts return codes and finiteness only; the values are pinned bit for bit by the CPU tests against their NumPy restatements.
+// The plan of a call (second_of, counted_of, tile_bytes_per_path, plan_tiles) has no other CPU test: it is asserted in full here.
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -132,12 +133,36 @@ static void run_shape(int N, int K, int T, int H) {
     if (f == SPEND || f == SPEND_BOOT) { rq.cash = rq.spend = true; rq.cf = &no_cf; rq.sp = &sp; rq.wd_stats_out = stats.data(); }
     if (f == OVERLAY) { rq.overlay = true; rq.ov = &ov; }
     if (rq.cash || rq.protect) { rq.counts_out = counts.data(); rq.hz_counts_out = H ? hz_counts.data() : nullptr; }
+    std::vector<float> second((size_t)K * 4);                // [K][4 paths] the optional per-path outputs
+    std::vector<uint32_t> record((size_t)K * 4);
+    std::vector<mcp_stats> second_stats(K);
+    if (rq.band) { rq.turnover_out = second.data(); rq.turnover_stats_out = second_stats.data(); rq.trades_out = record.data(); }
+    if (rq.spend) { rq.wd_out = second.data(); rq.wd_stats_out = second_stats.data(); }
     EXPECT(check_request(&prm, rq, 4) == MCP_OK);
+    {                                     // the one second array and the one integer record of the request, on the request's own outputs
+      const Second sec = second_of(rq);
+      const Counted cnt = counted_of(&prm, rq);
+      EXPECT(sec.on == (rq.band || rq.spend) && cnt.on == rq.band && cnt.bins == count_bins(&prm, rq));
+      EXPECT(sec.out == (sec.on ? second.data() : nullptr) && sec.stats_out == (sec.on ? second_stats.data() : nullptr));
+      EXPECT(cnt.out == (cnt.on ? record.data() : nullptr) && cnt.hist_out == (cnt.on ? trade_hist.data() : nullptr));
+      if (rq.band) EXPECT(sec.unit_v0 && !sec.pivoted);   // SPEC.md 5.18: x = Y - 1, no pivot
+      if (rq.spend) EXPECT(!sec.unit_v0 && sec.pivoted);  // SPEC.md 5.16: x = Y / fl32(v0) - 1, the pivots of request_wd_pivots
+      Request dr = rq;                                    // SPEC.md 5.1: the drawdown, where the request may carry it
+      ask_drawdown(dr, second.data(), second_stats.data());
+      if (check_request(&prm, dr, 4) == MCP_OK) {
+        const Second dd = second_of(dr);
+        EXPECT(dd.on && dd.unit_v0 && !dd.pivoted && dd.out == second.data() && dd.stats_out == second_stats.data());
+      }
+    }
     {                                     // SPEC.md 4.17: the lifetime is taken by the walks with ruin and refused by every other
       std::vector<uint64_t> lh((size_t)K * (T + 1));
       Request lr = rq;
       lr.life = true;
       lr.life_hist_out = lh.data();
+      lr.life_out = record.data();
+      const Counted cnt = counted_of(&prm, lr);
+      if (rq.cash) EXPECT(cnt.on && cnt.bins == (size_t)T + 1 && cnt.bins == count_bins(&prm, lr) && cnt.out == record.data() && cnt.hist_out == lh.data());
+      lr.life_out = nullptr;
       EXPECT(check_request(&prm, lr, 4) == (rq.cash ? MCP_OK : MCP_E_UNSUPPORTED));
       lr.life_hist_out = nullptr;
       EXPECT(check_request(&prm, lr, 4) == (rq.cash ? MCP_E_ARG : MCP_E_UNSUPPORTED));
@@ -191,12 +216,123 @@ static void run_shape(int N, int K, int T, int H) {
   }
 }
 
+// The plan of one call (plan_tiles) against what it promises: every (portfolio, path) cell once, the shape of either sharding, the
+// budget, whole K_PAD tiles, and which shards walk paths.
+static void check_plan(size_t S, int K, uint64_t n, bool by_portfolio, uint64_t unit, size_t budget, size_t bytes) {
+  snprintf(g_case, sizeof g_case, "plan S=%zu K=%d n=%llu %s unit=%llu budget=%zu", S, K, (unsigned long long)n,
+           by_portfolio ? "portfolios" : "paths", (unsigned long long)unit, budget);
+  const TilePlan plan = plan_tiles(S, K, n, by_portfolio, unit, budget, bytes);
+  EXPECT(plan.S == S && plan.tiles() >= 1 && plan.jobs.size() == plan.tiles() * S);
+  std::vector<unsigned char> seen((size_t)K * n, 0);
+  std::vector<int> next(S);                                  // portfolio shards: where shard s goes on
+  for (size_t s = 0; s < S; s++) next[s] = (int)((int64_t)K * (int64_t)s / (int64_t)S);
+  for (size_t t = 0; t < plan.tiles(); t++) {
+    const Job* jobs = plan.tile(t);
+    bool any = false;
+    for (size_t s = 0; s < S; s++) {
+      const Job& j = jobs[s];
+      const int slice_end = (int)((int64_t)K * (int64_t)(s + 1) / (int64_t)S);
+      if (by_portfolio) {
+        EXPECT(j.active == (next[s] < slice_end));           // active until its slice is done, never on an empty slice
+        if (!j.active) continue;
+        EXPECT(j.k0 == next[s] && j.kt >= 1 && j.k0 + j.kt <= slice_end && j.p0 == 0 && j.pn == n);
+        const uint64_t fit = budget / (bytes * n);
+        if (j.kt < slice_end - next[s] && fit >= (uint64_t)K_PAD) EXPECT(j.kt % K_PAD == 0);
+        next[s] += j.kt;
+      } else {
+        EXPECT(j.active && j.k0 == jobs[0].k0 && j.kt == jobs[0].kt && j.kt >= 1 && j.k0 + j.kt <= K);
+        EXPECT(j.p0 == (s ? jobs[s - 1].p0 + jobs[s - 1].pn : 0) && j.p0 % unit == 0 && j.pn % unit == 0);
+        if (s) EXPECT(j.pn <= jobs[s - 1].pn);               // the remainder goes to the first shards: pn = 0 only at the end
+        if (s + 1 == S) EXPECT(j.p0 + j.pn == n);
+        EXPECT(j.k0 == (t ? plan.tile(t - 1)[s].k0 + plan.tile(t - 1)[s].kt : 0));
+        const uint64_t fit = budget / (bytes * (jobs[0].pn ? jobs[0].pn : 1));   // shard 0 holds the largest range
+        if (j.kt < K && j.k0 + j.kt < K && fit >= (uint64_t)K_PAD) EXPECT(j.kt % K_PAD == 0);
+      }
+      any = true;
+      if (j.kt > 1) EXPECT((uint64_t)j.kt * j.pn * bytes <= budget);
+      for (int k = j.k0; k < j.k0 + j.kt; k++)
+        for (uint64_t p = j.p0; p < j.p0 + j.pn; p++) seen[(size_t)k * n + p]++;
+    }
+    EXPECT(any);                                             // no tile without work
+    if (!by_portfolio && t + 1 == plan.tiles()) EXPECT(jobs[0].k0 + jobs[0].kt == K);
+  }
+  for (unsigned char c : seen) EXPECT(c == 1);
+  for (size_t s = 0; s < S && unit == 1; s++) {              // the shards that take the row table of a bootstrap call (never antithetic)
+    const bool walks = by_portfolio ? (int64_t)K * (int64_t)(s + 1) / (int64_t)S > (int64_t)K * (int64_t)s / (int64_t)S
+                                    : n / S + (s < n % S ? 1 : 0) > 0;
+    EXPECT(plan.walks(s) == walks);
+  }
+}
+
+static void run_plans() {
+  const size_t Ss[4] = {1, 2, 3, 8}, bytes = sizeof(float);
+  const int Ks[5] = {1, 3, 17, 600, 1700};
+  const uint64_t ns[4] = {1, 2, 5, 4098};
+  for (size_t S : Ss)
+    for (int K : Ks)
+      for (uint64_t n : ns)
+        for (int mode = 0; mode < 3; mode++) {               // path shards, path shards of antithetic pairs, portfolio shards
+          const bool by_portfolio = mode == 2;
+          const uint64_t unit = mode == 1 ? 2 : 1;
+          if (unit == 2 && (n & 1)) continue;
+          const uint64_t units = n / unit, pn_max = by_portfolio ? n : unit * (units / S + (units % S ? 1 : 0));
+          const size_t per = bytes * (size_t)(pn_max ? pn_max : 1);
+          for (size_t fit : {(size_t)K, (size_t)1100, (size_t)3, (size_t)1})   // tiles of K, of 1024 (K = 1700), of 3 and of 1 portfolio
+            check_plan(S, K, n, by_portfolio, unit, fit * per, bytes);
+        }
+  // tests/test_gpu_round2.py::test_terminal_budget_tiles_the_portfolios, one shard: room for 600 portfolios of 8192 paths
+  snprintf(g_case, sizeof g_case, "pinned plan, 1700 portfolios");
+  {
+    const TilePlan plan = plan_tiles(1, 1700, 8192, false, 1, (size_t)600 * 8192 * 4, 4);
+    const int want[4][2] = {{0, 512}, {512, 512}, {1024, 512}, {1536, 164}};
+    EXPECT(plan.tiles() == 4);
+    for (size_t t = 0; t < 4; t++) {
+      const Job& j = plan.tile(t)[0];
+      EXPECT(j.active && j.k0 == want[t][0] && j.kt == want[t][1] && j.p0 == 0 && j.pn == 8192);
+    }
+  }
+  // tests/test_gpu_band.py::test_property_d_shards_and_tiles, one shard: 5 banded portfolios with two horizons, two per tile
+  snprintf(g_case, sizeof g_case, "pinned plan, banded call");
+  {
+    const int32_t steps[2] = {10, 30};
+    const uint64_t n = 30001;
+    Request rq;
+    rq.rebalanced = rq.band = true;
+    ask_horizons(rq, true, 2, steps, 0, nullptr, nullptr, nullptr, nullptr);
+    const TilePlan plan = plan_tiles(1, 5, n, false, 1, 2 * n * (4 * (1 + 2) + 12), tile_bytes_per_path(rq));
+    const int want[3][2] = {{0, 2}, {2, 2}, {4, 1}};
+    EXPECT(plan.tiles() == 3);
+    for (size_t t = 0; t < 3; t++) {
+      const Job& j = plan.tile(t)[0];
+      EXPECT(j.active && j.k0 == want[t][0] && j.kt == want[t][1] && j.p0 == 0 && j.pn == n);
+    }
+  }
+  // what the budget counts per path and portfolio
+  snprintf(g_case, sizeof g_case, "tile_bytes_per_path");
+  const int32_t steps[2] = {1, 2};
+  for (int H : {0, 2}) {
+    Request rq;
+    ask_horizons(rq, H != 0, H, steps, 0, nullptr, nullptr, nullptr, nullptr);
+    const size_t hz = 4 * (size_t)H;
+    Request dd = rq, spend = rq, life = rq, spend_life = rq, band = rq;
+    dd.dd = true;
+    spend.cash = spend.spend = true;
+    life.cash = life.life = true;
+    spend_life.cash = spend_life.spend = spend_life.life = true;
+    band.rebalanced = band.band = true;
+    EXPECT(tile_bytes_per_path(rq) == 4 + hz && tile_bytes_per_path(spend) == 8 + hz && tile_bytes_per_path(life) == 8 + hz);
+    EXPECT(tile_bytes_per_path(spend_life) == 12 + hz && tile_bytes_per_path(band) == 16 + hz);
+    if (!H) EXPECT(tile_bytes_per_path(dd) == 8);            // the drawdown and horizons are never asked together
+  }
+}
+
 int main() {
   const int Ns[3] = {1, 5, MCP_MAX_ASSETS}, Ks[4] = {1, 8, 9, 17}, Hs[2] = {0, 2};
   int n = 0;
   for (int N : Ns)
     for (int K : Ks)
       for (int H : Hs) { run_shape(N, K, 12, H); n++; }
-  printf("host_selftest ok: %d shapes x %d requests\n", n, (int)N_FEATURES);
+  run_plans();
+  printf("host_selftest ok: %d shapes x %d requests, the plans\n", n, (int)N_FEATURES);
   return 0;
 }

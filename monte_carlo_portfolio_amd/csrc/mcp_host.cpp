@@ -1059,6 +1059,78 @@ void request_wd_pivots(const mcp_params* prm, const Request& rq, int k0, int kt,
   spend_pivots(kt, prm->n_steps, cm.data(), spend_consts(rq.sp, prm->v0), rq.sp->every, (double)(float)prm->v0, 0, nullptr, nullptr, nullptr, out_wd);
 }
 
+Second second_of(const Request& rq) {
+  if (rq.dd) return {true, true, false, rq.mdd_out, rq.dd_stats_out};
+  if (rq.band) return {true, true, false, rq.turnover_out, rq.turnover_stats_out};
+  if (rq.spend) return {true, false, true, rq.wd_out, rq.wd_stats_out};
+  return {false, false, false, nullptr, nullptr};
+}
+
+Counted counted_of(const mcp_params* prm, const Request& rq) {
+  if (rq.band) return {true, count_bins(prm, rq), rq.trades_out, rq.trade_hist_out};
+  return {rq.life, count_bins(prm, rq), rq.life ? rq.life_out : nullptr, rq.life ? rq.life_hist_out : nullptr};
+}
+
+// A banded call is budgeted at 4 bytes more per path than its arrays hold (V_T, the horizon rows, Y and c): the figure it was
+// introduced with, which decides the tile sizes of every banded call under a small budget.
+constexpr size_t BAND_BUDGET_SLACK = sizeof(float);
+size_t tile_bytes_per_path(const Request& rq) {
+  return (1 + (rq.hz ? (size_t)rq.H : 0)) * sizeof(float) + (second_of(rq).on ? sizeof(float) : 0) +
+         (rq.life || rq.band ? sizeof(uint32_t) : 0) + (rq.band ? BAND_BUDGET_SLACK : 0);
+}
+
+int tile_portfolios(size_t budget, uint64_t n_paths, int K, size_t bytes_per_path) {
+  const uint64_t fit = budget / (bytes_per_path * (n_paths ? n_paths : 1));
+  if (fit >= (uint64_t)K) return K;
+  if (fit >= (uint64_t)K_PAD) return (int)(fit / K_PAD) * K_PAD;
+  return fit >= 1 ? (int)fit : 1;
+}
+
+bool TilePlan::walks(size_t s) const {
+  for (size_t t = 0; t < tiles(); t++)
+    if (tile(t)[s].active && tile(t)[s].pn) return true;
+  return false;
+}
+
+TilePlan plan_tiles(size_t S, int K, uint64_t n_paths, bool by_portfolio, uint64_t unit, size_t budget, size_t bytes_per_path) {
+  TilePlan plan;
+  plan.S = S;
+  std::vector<Job> jobs(S);
+  if (by_portfolio) {
+    const auto kb = [&](size_t s) { return (int)((int64_t)K * (int64_t)s / (int64_t)S); };
+    std::vector<int> done(S, 0);
+    for (bool more = true; more;) {
+      more = false;
+      for (size_t s = 0; s < S; s++) {
+        const int left = kb(s + 1) - kb(s) - done[s];
+        jobs[s] = Job();
+        if (left <= 0) continue;
+        const int kt = std::min(left, tile_portfolios(budget, n_paths, left, bytes_per_path));
+        jobs[s].k0 = kb(s) + done[s]; jobs[s].kt = kt; jobs[s].p0 = 0; jobs[s].pn = n_paths; jobs[s].active = true;
+        done[s] += kt;
+        more = true;
+      }
+      if (more) plan.jobs.insert(plan.jobs.end(), jobs.begin(), jobs.end());
+    }
+    return plan;
+  }
+  uint64_t pn_max = 0;
+  const uint64_t n_units = n_paths / unit;
+  for (size_t s = 0; s < S; s++) {
+    jobs[s].p0 = unit * (n_units / S * s + std::min<uint64_t>(s, n_units % S));
+    jobs[s].pn = unit * (n_units / S + (s < n_units % S ? 1 : 0));
+    jobs[s].active = true;
+    pn_max = std::max(pn_max, jobs[s].pn);
+  }
+  const int kt_max = tile_portfolios(budget, pn_max, K, bytes_per_path);
+  plan.jobs.reserve(S * (size_t)((K + kt_max - 1) / kt_max));
+  for (int k0 = 0; k0 < K; k0 += kt_max) {
+    for (size_t s = 0; s < S; s++) { jobs[s].k0 = k0; jobs[s].kt = std::min(kt_max, K - k0); }
+    plan.jobs.insert(plan.jobs.end(), jobs.begin(), jobs.end());
+  }
+  return plan;
+}
+
 // SPEC.md 5.17: one pass over the cumulated histogram.  n = sum hist; level q's value is the smallest s with cum(s) > lo
 int life_summary(const uint64_t* hist, int T, int n_levels, const double* levels, uint64_t* sum_out, uint32_t* q_out) {
   uint64_t n = 0, sum = 0;

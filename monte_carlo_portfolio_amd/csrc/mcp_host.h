@@ -1,5 +1,5 @@
 // mcp_host.h -- the host code of libmcport.so that touches no device (mcp_host.cpp): every argument rule, every feature's host
-// constants, every closed-form pivot, the packers and the layout of a tile's parameter block.  Internal, not installed.  It
+// constants, every closed-form pivot, the packers, the layout of a tile's parameter block and the plan of a call.  Internal, not installed.  It
 // includes no device header, so that mcp_host.cpp also builds with a plain C++ compiler (make host-selftest).
 #pragma once
 #include <stddef.h>
@@ -239,5 +239,51 @@ int pack_tile(const mcp_params* prm, const Request& rq, const TileInputs& in, in
 int request_pivots(const mcp_params* prm, const Request& rq, const TileInputs& in, int k0, int kt, double* out_T, double* out_hz);
 // SPEC.md 5.16: the tile's pivots of the total paid out into out_wd[kt] (a spending request only)
 void request_wd_pivots(const mcp_params* prm, const Request& rq, int k0, int kt, double* out_wd);
+
+// ---- what a request leaves per path besides V_T and the horizon rows ----
+// The one second float array: the drawdown q / d (SPEC.md 5.1), the turnover Y of the bands (5.18) or the total paid out Y_T of a
+// spending rule (5.16); check_request lets at most one of the three through.  It is reduced as the terminal values are, at rf = 0.
+struct Second {
+  bool on;                // the request has one
+  bool unit_v0;           // its select runs at v0 = 1: x = q - 1, expm1(d) or Y - 1; the total paid out keeps v0: x = Y / fl32(v0) - 1
+  bool pivoted;           // its select takes the pivots of request_wd_pivots (spending only); the other two take none
+  float* out;             // the caller's [K*n] array, or NULL
+  mcp_stats* stats_out;   // the caller's [K] records
+};
+Second second_of(const Request& rq);
+// The one integer record: the lifetime l (SPEC.md 4.17 / 5.17) or the bands' trade count c (4.18 / 5.18), with its exact histogram.
+struct Counted {
+  bool on;
+  size_t bins;            // count_bins
+  uint32_t* out;          // the caller's [K*n] array, or NULL
+  uint64_t* hist_out;     // the caller's [K][bins] histogram
+};
+Counted counted_of(const mcp_params* prm, const Request& rq);
+
+// ---- the plan of a call: which shard does what in which tile ----
+// Bytes per path and portfolio that the tile budget counts: 4 of V_T, 4 per horizon row, 4 of the second array, 4 of the integer record
+size_t tile_bytes_per_path(const Request& rq);
+// Portfolios per tile so that kt * n_paths * bytes_per_path fits the budget: whole 512-portfolio workgroups of the MFMA sweep kernel
+// when K is tiled at all.
+int tile_portfolios(size_t budget, uint64_t n_paths, int K, size_t bytes_per_path);
+// What one shard does in one tile of portfolios.
+struct Job {
+  int k0 = 0, kt = 0;            // portfolios [k0, k0+kt) of the caller's W
+  uint64_t p0 = 0, pn = 0;       // paths [p0, p0+pn) relative to path_begin
+  bool active = false;
+};
+struct TilePlan {
+  size_t S = 0;                  // shards
+  std::vector<Job> jobs;         // [tiles][S], in the order the tiles run
+  size_t tiles() const { return jobs.size() / S; }
+  const Job* tile(size_t t) const { return jobs.data() + t * S; }
+  bool walks(size_t s) const;    // does shard s walk paths in this call?
+};
+// The tiles of a call of K portfolios and n_paths paths on S shards under `budget` bytes per device.  Portfolio shards: shard s takes
+// the slice [K*s/S, K*(s+1)/S) of W and walks all paths; the slices are tiled independently, round after round until every shard is
+// done, a finished shard inactive.  Path shards: all shards see the same tile of portfolios and shard s walks its part of the path
+// range, cut at multiples of `unit` (2 for antithetic pairs, SPEC.md 2.3); with fewer units than shards the last ones are active on
+// no paths.
+TilePlan plan_tiles(size_t S, int K, uint64_t n_paths, bool by_portfolio, uint64_t unit, size_t budget, size_t bytes_per_path);
 
 }  // namespace mcph
