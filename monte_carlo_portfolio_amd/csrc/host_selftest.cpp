@@ -2,9 +2,14 @@
 // with a plain C++ compiler under AddressSanitizer + UBSan, so an overrun of a packer or a pivot rule is a sanitizer report.  It
 // asserts return codes and finiteness only; the values are pinned bit for bit by the CPU tests against their NumPy restatements.
 // The plan of a call (second_of, counted_of, tile_bytes_per_path, plan_tiles) has no other CPU test: it is asserted in full here.
+// So is the routing: every combination of features goes through check_request, route_kernel and the rows of mcp_paths_ladder.inc,
+// the text the device build compiles (run_routes).
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
+#include <set>
+#include <utility>
 #include <vector>
 
 #include "mcp_host.h"
@@ -26,49 +31,110 @@ template <class T> static bool finite(const std::vector<T>& v) {
   return true;
 }
 
+// Minimal valid arguments of every feature for N assets, K portfolios, T steps and row tables of R rows, with the outputs a request
+// must carry, and the request of one combination of features over them.
+enum Bit { B_DD = 1, B_HZ = 2, B_REB = 4, B_BAND = 8, B_CASH = 16, B_GLIDE = 32, B_SPEND = 64, B_LIFE = 128, B_PROTECT = 256, B_OVERLAY = 512,
+           B_GARCH = 1024, B_JUMPS = 2048, B_REGIMES = 4096, B_ANTI = 8192, B_ATTR = 16384, N_BITS = 15 };
+struct Payloads {
+  static constexpr int G = 2, H = 2;
+  const int N, K, T, R;
+  const int32_t steps[H], breaks[G] = {3, 7};
+  std::vector<float> mu, mu1, chol, chol1, W, rows, shock, loading, targets, flows, zero_flows, floor_s, spot, tol;
+  std::vector<int32_t> row_begin;
+  const std::vector<mcp_overlay_row> ov_rows;
+  mcp_bootstrap boot;
+  mcp_filtered filt;
+  const mcp_student_t st = {5, 0};
+  const mcp_garch gv = {0.05, 0.9, 1.0, 0};
+  mcp_jumps jp;
+  mcp_regimes rs;
+  mcp_glide gl;
+  mcp_cashflow cf, no_cf;
+  mcp_protect pt;
+  mcp_overlay ov;
+  const mcp_rebalance reb = {5, 0, 0.001};
+  mcp_band bd;
+  mcp_rebalance bd_reb;
+  const mcp_spending sp = {0.01, 0.1, HUGE_VAL, 0.02, 0.015, 0.9, 5, 1, 1, 0};
+  std::vector<mcp_stats> stats, hz_stats, second_stats;
+  std::vector<uint64_t> counts, hz_counts, trade_hist, life_hist, attr_counts;
+  std::vector<mcp_attr> attr;
+  std::vector<mcp_pair> pair;
+
+  Payloads(int N_, int K_, int T_, int R_)
+      : N(N_), K(K_), T(T_), R(R_), steps{1, T_}, mu(N), mu1(N), chol((size_t)N * N, 0.0f), chol1((size_t)N * N, 0.0f), W((size_t)K * N),
+        rows((size_t)R * N), shock(R), loading(N), targets((size_t)G * K * N), flows(T, -0.01f), zero_flows(T, 0.0f), floor_s(T + 1),
+        spot(N, 100.0f), tol((size_t)K * N, 0.05f), row_begin(N + 1, 1), ov_rows(1, mcp_overlay_row{MCP_OVERLAY_PUT, 95.0f, 1.0f, 0.01f}),
+        stats(K), hz_stats((size_t)H * K), second_stats(K), counts(2 * (size_t)K), hz_counts(2 * (size_t)H * K),
+        trade_hist((size_t)K * ((size_t)(T - 1) / 5 + 1)), life_hist((size_t)K * ((size_t)T + 1)), attr_counts(2 * (size_t)K),
+        attr((size_t)K * N), pair(K) {
+    for (int i = 0; i < N; i++) {
+      mu[i] = 0.001f * (float)(i + 1) / (float)N;
+      mu1[i] = -2.0f * mu[i];
+      loading[i] = 0.5f + 0.5f * (float)(i & 1);
+      for (int j = 0; j <= i; j++) chol[(size_t)i * N + j] = i == j ? 0.01f : 0.001f;
+      for (int j = 0; j <= i; j++) chol1[(size_t)i * N + j] = 3.0f * chol[(size_t)i * N + j];
+    }
+    for (size_t i = 0; i < W.size(); i++) W[i] = (1.0f + 0.1f * (float)(i % 3)) / (float)N;
+    for (size_t i = 0; i < targets.size(); i++) targets[i] = (1.0f + 0.1f * (float)(i % 5)) / (float)N;
+    for (size_t i = 0; i < rows.size(); i++) rows[i] = 0.002f * (float)((int)(i % 7) - 3);
+    for (int j = 0; j < R; j++) shock[j] = 0.5f + 0.25f * (float)(j % 6);
+    EXPECT(mcp_protect_floor(0.8, 0.001, T, floor_s.data()) == MCP_OK && finite(floor_s));
+    row_begin[0] = 0;
+    for (int k = 0; k < K; k++) tol[(size_t)k * N + N - 1] = HUGE_VALF;     // SPEC.md 4.18: the last asset of every portfolio not watched
+    boot = {rows.data(), R, 0, 3.0};
+    filt = {mu.data(), rows.data(), shock.data(), R, 0, 2.0};
+    jp = {0.1, -0.05, 0.02, (N & 1) ? loading.data() : nullptr, 0};
+    rs = {0.05, 0.2, 0.1, mu1.data(), chol1.data(), 0};
+    gl = {breaks, targets.data(), G, 0};
+    cf = {flows.data(), T, 1, 1.0};
+    no_cf = {zero_flows.data(), T, 0, 0.0};
+    pt = {floor_s.data(), 3.0, 1.0, 0.001, 0.1, nullptr, 0};
+    ov = {ov_rows.data(), row_begin.data(), spot.data(), 1, 0};
+    bd = {5, 0, 0.001, tol.data()};
+    bd_reb = {bd.every, 0, bd.cost};
+  }
+  Payloads(const Payloads&) = delete;
+
+  // The request of an mcp_simulate* call with the draw source `src` and the features `bits`, every output it must carry on this
+  // object's buffers and none of the optional ones.  A spending rule comes on the all-zero schedule, as mcp_simulate_spending asks it.
+  Request request(Source src, int bits) {
+    const bool rows_only = src == SRC_BOOT || src == SRC_FHS;
+    Request rq = host_request(src, rows_only ? nullptr : mu.data(), rows_only ? nullptr : chol.data(), W.data(), nullptr, stats.data());
+    if (src == SRC_BOOT) rq.boot = &boot;
+    if (src == SRC_T) rq.st = &st;
+    if (src == SRC_FHS) { rq.filt = &filt; rq.gv = &gv; }
+    if (bits & B_DD) ask_drawdown(rq, nullptr, second_stats.data());
+    if (bits & B_HZ) ask_horizons(rq, true, H, steps, 0, nullptr, nullptr, hz_stats.data(), nullptr);
+    if (bits & B_REB) { rq.rebalanced = true; rq.reb = (bits & B_BAND) ? &bd_reb : &reb; }
+    if (bits & B_BAND) { rq.band = true; rq.bd = &bd; rq.trade_hist_out = trade_hist.data(); rq.turnover_stats_out = second_stats.data(); }
+    if (bits & B_CASH) { rq.cash = true; rq.cf = (bits & B_SPEND) ? &no_cf : &cf; }
+    if (bits & B_GLIDE) { rq.glide = true; rq.gl = &gl; }
+    if (bits & B_SPEND) { rq.spend = true; rq.sp = &sp; rq.wd_stats_out = second_stats.data(); }
+    if (bits & B_LIFE) { rq.life = true; rq.life_hist_out = life_hist.data(); }
+    if (bits & B_PROTECT) { rq.protect = true; rq.pi = &pt; }
+    if (bits & B_OVERLAY) { rq.overlay = true; rq.ov = &ov; }
+    if (bits & B_GARCH) { rq.garch = true; rq.gv = &gv; }
+    if (bits & B_JUMPS) { rq.jumps = true; rq.jp = &jp; }
+    if (bits & B_REGIMES) { rq.regimes = true; rq.rs = &rs; }
+    if (bits & B_ANTI) { rq.anti = true; rq.pair_out = pair.data(); }
+    if (bits & B_ATTR) { rq.attr = true; rq.attr_out = attr.data(); rq.attr_counts_out = attr_counts.data(); }
+    if (rq.cash || rq.protect) { rq.counts_out = counts.data(); rq.hz_counts_out = rq.hz ? hz_counts.data() : nullptr; }
+    return rq;
+  }
+};
+
 enum Feature { PLAIN, BOOT, FILTERED, JUMPS, REGIMES, GLIDE_CF, GLIDE, PROTECT, CASH, OVERLAY, SPEND, SPEND_BOOT, BAND, BAND_BOOT, N_FEATURES };
-static const char* const k_names[N_FEATURES] = {"plain", "bootstrap", "filtered", "jumps", "regimes", "glide+flows", "glide",
-                                                "protect", "cash", "overlay", "spend", "spend+bootstrap", "band", "band+bootstrap"};
+static const struct { const char* name; Source src; int bits; } k_features[N_FEATURES] = {
+    {"plain", SRC_GAUSS, 0}, {"bootstrap", SRC_BOOT, 0}, {"filtered", SRC_FHS, 0}, {"jumps", SRC_GAUSS, B_JUMPS}, {"regimes", SRC_GAUSS, B_REGIMES},
+    {"glide+flows", SRC_GAUSS, B_CASH | B_GLIDE}, {"glide", SRC_GAUSS, B_CASH | B_GLIDE}, {"protect", SRC_GAUSS, B_PROTECT},
+    {"cash", SRC_GAUSS, B_CASH}, {"overlay", SRC_GAUSS, B_OVERLAY}, {"spend", SRC_GAUSS, B_CASH | B_SPEND},
+    {"spend+bootstrap", SRC_BOOT, B_CASH | B_SPEND}, {"band", SRC_GAUSS, B_REB | B_BAND}, {"band+bootstrap", SRC_BOOT, B_REB | B_BAND}};
 
 static void run_shape(int N, int K, int T, int H) {
-  const int R = 6, G = 2;
-  const int32_t steps_v[2] = {1, T}, breaks_v[G] = {3, 7};
-  const std::vector<int32_t> steps(steps_v, steps_v + H), breaks(breaks_v, breaks_v + G);
-  std::vector<float> mu(N), mu1(N), chol((size_t)N * N, 0.0f), chol1((size_t)N * N, 0.0f), W((size_t)K * N), rows((size_t)R * N), shock(R),
-      loading(N), targets((size_t)G * K * N), flows(T, -0.01f), zero_flows(T, 0.0f), floor_s(T + 1), spot(N, 100.0f);
-  for (int i = 0; i < N; i++) {
-    mu[i] = 0.001f * (float)(i + 1) / (float)N;
-    mu1[i] = -2.0f * mu[i];
-    loading[i] = 0.5f + 0.5f * (float)(i & 1);
-    for (int j = 0; j <= i; j++) chol[(size_t)i * N + j] = i == j ? 0.01f : 0.001f;
-    for (int j = 0; j <= i; j++) chol1[(size_t)i * N + j] = 3.0f * chol[(size_t)i * N + j];
-  }
-  for (size_t i = 0; i < W.size(); i++) W[i] = (1.0f + 0.1f * (float)(i % 3)) / (float)N;
-  for (size_t i = 0; i < targets.size(); i++) targets[i] = (1.0f + 0.1f * (float)(i % 5)) / (float)N;
-  for (size_t i = 0; i < rows.size(); i++) rows[i] = 0.002f * (float)((int)(i % 7) - 3);
-  for (int j = 0; j < R; j++) shock[j] = 0.5f + 0.25f * (float)j;
-  EXPECT(mcp_protect_floor(0.8, 0.001, T, floor_s.data()) == MCP_OK && finite(floor_s));
-  std::vector<int32_t> row_begin(N + 1, 1);
-  row_begin[0] = 0;
-  const std::vector<mcp_overlay_row> ov_rows(1, mcp_overlay_row{MCP_OVERLAY_PUT, 95.0f, 1.0f, 0.01f});
-
+  Payloads p(N, K, T, 6);
   mcp_params prm = {N, T, K, MCP_COMPOUND_SIMPLE, 0, 0, 1.0, 0.95, 0.0};
-  const mcp_bootstrap boot = {rows.data(), R, 0, 3.0};
-  const mcp_filtered filt = {mu.data(), rows.data(), shock.data(), R, 0, 2.0};
-  const mcp_garch gv = {0.05, 0.9, 1.0, 0};
-  const mcp_jumps jp = {0.1, -0.05, 0.02, (N & 1) ? loading.data() : nullptr, 0};
-  const mcp_regimes rs = {0.05, 0.2, 0.1, mu1.data(), chol1.data(), 0};
-  const mcp_glide gl = {breaks.data(), targets.data(), G, 0};
-  const mcp_cashflow cf = {flows.data(), T, 1, 1.0}, no_cf = {zero_flows.data(), T, 0, 0.0};
-  const mcp_protect pt = {floor_s.data(), 3.0, 1.0, 0.001, 0.1, nullptr, 0};
-  const mcp_overlay ov = {ov_rows.data(), row_begin.data(), spot.data(), 1, 0};
-  const mcp_rebalance reb = {5, 0, 0.001};
-  std::vector<float> tol((size_t)K * N, 0.05f);          // SPEC.md 4.18: bands, the last asset of every portfolio not watched
-  for (int k = 0; k < K; k++) tol[(size_t)k * N + N - 1] = HUGE_VALF;
-  const mcp_band bd = {5, 0, 0.001, tol.data()};
-  const mcp_rebalance bd_reb = {bd.every, 0, bd.cost};
-  const mcp_spending sp = {0.01, 0.1, HUGE_VAL, 0.02, 0.015, 0.9, 5, 1, 1, 0};
-  const int32_t* hs = H ? steps.data() : nullptr;
+  const int32_t* hs = H ? p.steps : nullptr;
 
   // every pure entry point, outputs of exactly the documented length
   snprintf(g_case, sizeof g_case, "entry points, N=%d K=%d T=%d H=%d", N, K, T, H);
@@ -78,22 +144,22 @@ static void run_shape(int N, int K, int T, int H) {
   std::vector<uint32_t> jthr(MCP_MAX_JUMPS);
   double* hzp = H ? hz.data() : nullptr;
   EXPECT(mcp_abi_version() == MCP_ABI_VERSION && !packed.empty());
-  EXPECT(mcp_pack_params(N, K, mu.data(), chol.data(), W.data(), packed.data(), packed.size()) == MCP_OK && finite(packed));
-  EXPECT(mcp_pivots(&prm, mu.data(), chol.data(), W.data(), pv.data()) == MCP_OK && finite(pv));
-  EXPECT(mcp_rebalance_pivots(&prm, &reb, mu.data(), nullptr, W.data(), pv.data()) == MCP_OK && finite(pv));
-  EXPECT(mcp_rebalance_pivots(&prm, &reb, nullptr, &boot, W.data(), pv.data()) == MCP_OK && finite(pv));
-  EXPECT(mcp_bootstrap_pivots(&prm, &boot, W.data(), pv.data()) == MCP_OK && finite(pv));
-  EXPECT(mcp_filtered_pivots(&prm, &filt, W.data(), pv.data()) == MCP_OK && finite(pv));
-  EXPECT(mcp_cashflow_pivots(&prm, &cf, mu.data(), nullptr, W.data(), pv.data()) == MCP_OK && finite(pv));
-  EXPECT(mcp_overlay_pivots(&prm, &ov, mu.data(), W.data(), pv.data()) == MCP_OK && finite(pv));
-  EXPECT(mcp_regime_pivots(&prm, &rs, mu.data(), W.data(), H, hs, pv.data(), hzp) == MCP_OK && finite(pv) && finite(hz));
-  EXPECT(mcp_glide_pivots(&prm, &gl, &cf, mu.data(), nullptr, W.data(), H, hs, pv.data(), hzp) == MCP_OK && finite(pv) && finite(hz));
-  EXPECT(mcp_protect_pivots(&prm, &pt, mu.data(), W.data(), H, hs, pv.data(), hzp) == MCP_OK && finite(pv) && finite(hz));
+  EXPECT(mcp_pack_params(N, K, p.mu.data(), p.chol.data(), p.W.data(), packed.data(), packed.size()) == MCP_OK && finite(packed));
+  EXPECT(mcp_pivots(&prm, p.mu.data(), p.chol.data(), p.W.data(), pv.data()) == MCP_OK && finite(pv));
+  EXPECT(mcp_rebalance_pivots(&prm, &p.reb, p.mu.data(), nullptr, p.W.data(), pv.data()) == MCP_OK && finite(pv));
+  EXPECT(mcp_rebalance_pivots(&prm, &p.reb, nullptr, &p.boot, p.W.data(), pv.data()) == MCP_OK && finite(pv));
+  EXPECT(mcp_bootstrap_pivots(&prm, &p.boot, p.W.data(), pv.data()) == MCP_OK && finite(pv));
+  EXPECT(mcp_filtered_pivots(&prm, &p.filt, p.W.data(), pv.data()) == MCP_OK && finite(pv));
+  EXPECT(mcp_cashflow_pivots(&prm, &p.cf, p.mu.data(), nullptr, p.W.data(), pv.data()) == MCP_OK && finite(pv));
+  EXPECT(mcp_overlay_pivots(&prm, &p.ov, p.mu.data(), p.W.data(), pv.data()) == MCP_OK && finite(pv));
+  EXPECT(mcp_regime_pivots(&prm, &p.rs, p.mu.data(), p.W.data(), H, hs, pv.data(), hzp) == MCP_OK && finite(pv) && finite(hz));
+  EXPECT(mcp_glide_pivots(&prm, &p.gl, &p.cf, p.mu.data(), nullptr, p.W.data(), H, hs, pv.data(), hzp) == MCP_OK && finite(pv) && finite(hz));
+  EXPECT(mcp_protect_pivots(&prm, &p.pt, p.mu.data(), p.W.data(), H, hs, pv.data(), hzp) == MCP_OK && finite(pv) && finite(hz));
   std::vector<double> wdp(K);
   std::vector<float> c5(5);
-  EXPECT(mcp_spending_pivots(&prm, &sp, mu.data(), nullptr, W.data(), H, hs, pv.data(), hzp, wdp.data()) == MCP_OK && finite(pv) && finite(hz) && finite(wdp));
-  EXPECT(mcp_spending_pivots(&prm, &sp, nullptr, &boot, W.data(), H, hs, pv.data(), hzp, wdp.data()) == MCP_OK && finite(pv) && finite(hz) && finite(wdp));
-  EXPECT(mcp_spending_consts(&sp, prm.v0, c5.data()) == MCP_OK && std::isinf(c5[3]) && c5[4] == 0.015f);
+  EXPECT(mcp_spending_pivots(&prm, &p.sp, p.mu.data(), nullptr, p.W.data(), H, hs, pv.data(), hzp, wdp.data()) == MCP_OK && finite(pv) && finite(hz) && finite(wdp));
+  EXPECT(mcp_spending_pivots(&prm, &p.sp, nullptr, &p.boot, p.W.data(), H, hs, pv.data(), hzp, wdp.data()) == MCP_OK && finite(pv) && finite(hz) && finite(wdp));
+  EXPECT(mcp_spending_consts(&p.sp, prm.v0, c5.data()) == MCP_OK && std::isinf(c5[3]) && c5[4] == 0.015f);
   {                                       // SPEC.md 5.17 on an exactly sized histogram: T + 1 bins, one level per quartile
     std::vector<uint64_t> lh((size_t)T + 1, 1);
     std::vector<double> lq = {0.0, 25.0, 50.0, 100.0};
@@ -103,36 +169,17 @@ static void run_shape(int N, int K, int T, int H) {
            got[0] == 0 && got[1] == (uint32_t)(T / 4) && got[2] == (uint32_t)(T / 2) && got[3] == (uint32_t)T);
     EXPECT(mcp_lifetime_summary(lh.data(), T, 0, nullptr, &total, nullptr) == MCP_OK);
   }
-  EXPECT(mcp_band_reviews(&prm, &bd) == (T - 1) / 5 && mcp_band_reviews(&prm, nullptr) == -1);
-  EXPECT(mcp_regime_consts(&rs, thr3.data(), p3.data()) == MCP_OK && finite(p3));
-  EXPECT(mcp_jump_consts(&jp, N, mu.data(), jthr.data(), mean_count.data(), drift.data()) == MCP_OK && finite(mean_count) && finite(drift));
+  EXPECT(mcp_band_reviews(&prm, &p.bd) == (T - 1) / 5 && mcp_band_reviews(&prm, nullptr) == -1);
+  EXPECT(mcp_regime_consts(&p.rs, thr3.data(), p3.data()) == MCP_OK && finite(p3));
+  EXPECT(mcp_jump_consts(&p.jp, N, p.mu.data(), jthr.data(), mean_count.data(), drift.data()) == MCP_OK && finite(mean_count) && finite(drift));
   EXPECT(mcp_percentile_rank(1000, 0.95, &rank[0], &rank[1], p3.data()) == MCP_OK && rank[1] == rank[0] + 1 && finite(p3));
   EXPECT(mcp_percentile_rank_q(1000, 2.5, &rank[0], &rank[1], p3.data()) == MCP_OK && rank[1] == rank[0] + 1 && finite(p3));
 
   // every feature: the request's rules, then the block and the pivots of every tile on exactly sized buffers
-  std::vector<mcp_stats> stats(K), hz_stats((size_t)H * K);
-  std::vector<uint64_t> counts(2 * (size_t)K), hz_counts(2 * (size_t)H * K);
   for (int f = 0; f < N_FEATURES; f++) {
-    snprintf(g_case, sizeof g_case, "%s, N=%d K=%d T=%d H=%d", k_names[f], N, K, T, H);
-    const Source src = f == BOOT || f == SPEND_BOOT || f == BAND_BOOT ? SRC_BOOT : f == FILTERED ? SRC_FHS : SRC_GAUSS;
-    const bool rows_only = src != SRC_GAUSS;
-    Request rq = host_request(src, rows_only ? nullptr : mu.data(), rows_only ? nullptr : chol.data(), W.data(), nullptr, stats.data());
-    ask_horizons(rq, H != 0, H, hs, 0, nullptr, nullptr, H ? hz_stats.data() : nullptr, nullptr);
-    if (f == BOOT || f == SPEND_BOOT || f == BAND_BOOT) rq.boot = &boot;
-    std::vector<uint64_t> trade_hist((size_t)K * ((size_t)(T - 1) / 5 + 1));
-    if (f == BAND || f == BAND_BOOT) {
-      rq.rebalanced = rq.band = true; rq.reb = &bd_reb; rq.bd = &bd;
-      rq.trade_hist_out = trade_hist.data(); rq.turnover_stats_out = stats.data();
-    }
-    if (f == FILTERED) { rq.filt = &filt; rq.gv = &gv; }
-    if (f == JUMPS) { rq.jumps = true; rq.jp = &jp; }
-    if (f == REGIMES) { rq.regimes = true; rq.rs = &rs; }
-    if (f == GLIDE || f == GLIDE_CF) { rq.glide = true; rq.gl = &gl; }
-    if (f == GLIDE || f == GLIDE_CF || f == CASH) { rq.cash = true; rq.cf = f == GLIDE ? &no_cf : &cf; }
-    if (f == PROTECT) { rq.protect = true; rq.pi = &pt; }
-    if (f == SPEND || f == SPEND_BOOT) { rq.cash = rq.spend = true; rq.cf = &no_cf; rq.sp = &sp; rq.wd_stats_out = stats.data(); }
-    if (f == OVERLAY) { rq.overlay = true; rq.ov = &ov; }
-    if (rq.cash || rq.protect) { rq.counts_out = counts.data(); rq.hz_counts_out = H ? hz_counts.data() : nullptr; }
+    snprintf(g_case, sizeof g_case, "%s, N=%d K=%d T=%d H=%d", k_features[f].name, N, K, T, H);
+    Request rq = p.request(k_features[f].src, k_features[f].bits | (H ? B_HZ : 0));
+    if (f == GLIDE) rq.cf = &p.no_cf;
     std::vector<float> second((size_t)K * 4);                // [K][4 paths] the optional per-path outputs
     std::vector<uint32_t> record((size_t)K * 4);
     std::vector<mcp_stats> second_stats(K);
@@ -144,7 +191,7 @@ static void run_shape(int N, int K, int T, int H) {
       const Counted cnt = counted_of(&prm, rq);
       EXPECT(sec.on == (rq.band || rq.spend) && cnt.on == rq.band && cnt.bins == count_bins(&prm, rq));
       EXPECT(sec.out == (sec.on ? second.data() : nullptr) && sec.stats_out == (sec.on ? second_stats.data() : nullptr));
-      EXPECT(cnt.out == (cnt.on ? record.data() : nullptr) && cnt.hist_out == (cnt.on ? trade_hist.data() : nullptr));
+      EXPECT(cnt.out == (cnt.on ? record.data() : nullptr) && cnt.hist_out == (cnt.on ? p.trade_hist.data() : nullptr));
       if (rq.band) EXPECT(sec.unit_v0 && !sec.pivoted);   // SPEC.md 5.18: x = Y - 1, no pivot
       if (rq.spend) EXPECT(!sec.unit_v0 && sec.pivoted);  // SPEC.md 5.16: x = Y / fl32(v0) - 1, the pivots of request_wd_pivots
       Request dr = rq;                                    // SPEC.md 5.1: the drawdown, where the request may carry it
@@ -169,7 +216,7 @@ static void run_shape(int N, int K, int T, int H) {
     }
     if (rq.band) {                        // SPEC.md 4.18: a negative entry, a missing histogram, and the size of the histogram
       Request br = rq;
-      std::vector<float> neg(tol);
+      std::vector<float> neg(p.tol);
       neg.back() = -0.01f;
       const mcp_band bad_bd = {5, 0, 0.001, neg.data()};
       br.bd = &bad_bd;
@@ -177,7 +224,7 @@ static void run_shape(int N, int K, int T, int H) {
       br = rq;
       br.trade_hist_out = nullptr;
       EXPECT(check_request(&prm, br, 4) == MCP_E_ARG);
-      EXPECT(count_bins(&prm, rq) * (size_t)K == trade_hist.size());
+      EXPECT(count_bins(&prm, rq) * (size_t)K == p.trade_hist.size());
     }
     TileInputs in;
     EXPECT(tile_inputs(&prm, rq, &in) == MCP_OK);
@@ -208,7 +255,7 @@ static void run_shape(int N, int K, int T, int H) {
     }
     // one invalid request per feature and its documented code
     mcp_params bad = prm;
-    mcp_bootstrap bad_boot = boot;
+    mcp_bootstrap bad_boot = p.boot;
     if (f == PLAIN) bad.flags = MCP_FLAG_FOLD | MCP_FLAG_NATIVE_MATH;      // the folded step needs the spec's normals
     else if (f == BOOT) { bad_boot.mean_block = 0.5; rq.boot = &bad_boot; }  // the bootstrap compounds either way; b < 1 does not
     else bad.compounding = MCP_COMPOUND_LOG;                              // every other feature compounds simply
@@ -326,6 +373,175 @@ static void run_plans() {
   }
 }
 
+// ---- the routing: check_request -> route_kernel -> the rows of mcp_paths_ladder.inc ----
+// Every combination of draw source, features, compounding, flags, view (mcp_simulate* or mcp_launch_paths*) and path range (one that
+// passes lean_range, one that crosses 2^32; even, so that pairs stay legal) goes to visit(prm, rq, ln or NULL, path_begin, n_paths) on
+// minimal valid arguments, for NB = 1, 4, 5, 16 (the smallest N of each) and K = 1, 2, and for K = 20 at NB = 1: K meets the limits
+// of the folded step and the attribution and sets the pass width, none of which looks at N.  `visit` says whether check_request
+// accepts; a request on rows that it accepts on a table that fits LDS (8 rows) comes again on the first table that does not --
+// check_request scans the table, and sees its size in check_boot's and check_filtered's own rules only.
+template <class Visit>
+static void for_each_request(Visit&& visit) {
+  static float d_array[1];                                   // an mcp_launch_paths* call's device arrays are only tested against NULL
+  const int T = 12, shapes[9][2] = {{1, 1}, {1, 2}, {1, 20}, {4, 1}, {4, 2}, {5, 1}, {5, 2}, {16, 1}, {16, 2}};   // (NB, K)
+  const uint64_t ranges[2][2] = {{0, 66}, {(1ull << 32) - 64, 66}};
+  for (const auto& shape : shapes) {
+    const int nb = shape[0], N = 4 * nb - 3, K = shape[1];
+    int r_boot = 8, r_filt = 8;
+    while (mcp::boot_fits_lds((uint64_t)r_boot, nb)) r_boot++;
+    while (mcp::filt_fits_lds((uint64_t)r_filt, nb)) r_filt++;
+    Payloads fits(N, K, T, 8), big_boot(N, K, T, r_boot), big_filt(N, K, T, r_filt);
+    for (int src = SRC_GAUSS; src <= SRC_FHS; src++)
+      for (int bits = 0; bits < 1 << N_BITS; bits++) {
+        const Request rq = fits.request((Source)src, bits);
+        for (int compounding : {MCP_COMPOUND_SIMPLE, MCP_COMPOUND_LOG})
+          for (int flags : {0, (int)MCP_FLAG_NATIVE_MATH, (int)MCP_FLAG_FOLD, MCP_FLAG_NATIVE_MATH | MCP_FLAG_FOLD}) {
+            const mcp_params prm = {N, T, K, compounding, flags, 0, 1.0, 0.95, 0.0};
+            for (const auto& range : ranges) {
+              Launch ln;
+              ln.d_packed = ln.d_terminal = d_array;
+              ln.path_begin = range[0];
+              ln.n_paths = ln.stride = ln.mdd_stride = ln.hz_stride = range[1];
+              if (rq.dd) ln.d_mdd = d_array;
+              if (rq.hz) ln.d_hz = d_array;
+              for (const Launch* view : {(const Launch*)nullptr, (const Launch*)&ln})
+                if (visit(prm, rq, view, range[0], range[1]) && (src == SRC_BOOT || src == SRC_FHS)) {
+                  snprintf(g_case, sizeof g_case, "the table that does not fit LDS: nb=%d K=%d src=%d bits=0x%x", nb, K, src, bits);
+                  EXPECT(visit(prm, (src == SRC_BOOT ? big_boot : big_filt).request((Source)src, bits), view, range[0], range[1]));
+                }
+            }
+          }
+      }
+  }
+}
+
+// The rows of mcp_paths_ladder.inc that exist at (NB, KT), the text the device build compiles, with the kernel's name for the launch
+struct Row { int family; uint32_t mask; const char* kernel; };
+template <int NB, int KT>
+static std::vector<Row> ladder_rows() {
+  using namespace mcp;
+  std::vector<Row> rows;
+#define MCP_ROW_IF(cond, family, mask, ...) \
+  if constexpr (cond) rows.push_back(Row{family, mask, #__VA_ARGS__});
+#include "mcp_paths_ladder.inc"
+#undef MCP_ROW_IF
+  return rows;
+}
+static const std::vector<Row>& rows_at(int nb, bool kt8) {
+  static const std::vector<Row> at[4][2] = {{ladder_rows<1, 1>(), ladder_rows<1, 8>()}, {ladder_rows<4, 1>(), ladder_rows<4, 8>()},
+                                            {ladder_rows<5, 1>(), ladder_rows<5, 8>()}, {ladder_rows<16, 1>(), ladder_rows<16, 8>()}};
+  return at[nb == 1 ? 0 : nb == 4 ? 1 : nb == 5 ? 2 : 3][kt8];
+}
+// The row that `k` selects at `nb`, as launch_paths_nb<nb> finds it; *n_out: how many rows it equals
+static const Row* select_row(int nb, const mcp::PathKernel& k, int* n_out = nullptr) {
+  const Row* hit = nullptr;
+  int n = 0;
+  for (const Row& r : rows_at(nb, (k.flags & mcp::PK_KT8) != 0))
+    if (mcp::selects(k, r.family, r.mask)) { if (!hit) hit = &r; n++; }
+  if (n_out) *n_out = n;
+  return hit;
+}
+
+static long run_routes() {
+  using namespace mcp;
+  // (d) the table: 78 rows for NB <= LEAN_MAX_NB (the two lean kernels), 76 above; at KT = 8 without the folded step, the lean kernels,
+  // the bands and the attribution
+  for (int nb : {1, 4, 5, 16}) {
+    snprintf(g_case, sizeof g_case, "row counts, nb=%d", nb);
+    EXPECT(rows_at(nb, false).size() == (nb <= LEAN_MAX_NB ? 78u : 76u) && rows_at(nb, true).size() == 70u);
+  }
+  // (a) every accepted request has exactly one row; (b) its selector is canonical: with any one flag set or cleared it is another
+  // kernel's or nobody's -- under equality that is (a) again, asserted all the same, once per selector and nb; (c) every row is
+  // reached, at KT = 1 and where it exists at KT = 8
+  std::set<std::pair<int, uint32_t>> reached[2];             // (family, mask) by kt8
+  std::set<std::pair<int, std::pair<int, uint32_t>>> canonical;
+  long n_requests = 0, n_accepted = 0;
+  for_each_request([&](const mcp_params& prm, const Request& rq, const Launch* ln, uint64_t path_begin, uint64_t n_paths) {
+    n_requests++;
+    if (check_request(&prm, rq, n_paths, ln, path_begin) != MCP_OK) return false;
+    n_accepted++;
+    const int nb = (prm.n_assets + 3) / 4;
+    for (int attr_walk = 0; attr_walk <= (rq.attr ? 1 : 0); attr_walk++) {
+      const PathKernel k = route_kernel(&prm, rq, attr_walk != 0, path_begin, n_paths);
+      if (!canonical.insert({nb, {k.family, k.flags}}).second) continue;
+      snprintf(g_case, sizeof g_case, "route nb=%d K=%d src=%d family=%d flags=0x%x", nb, prm.n_portfolios, (int)rq.src, k.family, k.flags);
+      int n = 0;
+      const Row* row = select_row(nb, k, &n);
+      EXPECT(n == 1);
+      for (int b = 0; b < N_PATH_FLAGS; b++) {
+        const PathKernel other = {k.family, k.flags ^ (1u << b)};
+        EXPECT(select_row(nb, other) != row);               // PK_KT8: the row of the table at the other KT, another kernel
+      }
+      reached[(k.flags & PK_KT8) != 0].insert({row->family, row->mask});
+    }
+    return true;
+  });
+  for (int kt8 = 0; kt8 < 2; kt8++)
+    for (const Row& r : rows_at(1, kt8 != 0)) {
+      snprintf(g_case, sizeof g_case, "no accepted request reaches %s (family %d, mask 0x%x) at KT = %d", r.kernel, r.family, r.mask, kt8 ? 8 : 1);
+      EXPECT(reached[kt8].count({r.family, r.mask}) == 1);
+    }
+  snprintf(g_case, sizeof g_case, "accepted requests");
+  EXPECT(n_accepted > 0 && n_accepted < n_requests);
+  return n_requests;
+}
+
+// (e) the kernel of the named requests, literally: what runs what.  NB and KT stand for ceil(N / 4) and for 8 (K >= 2) or 1.
+static void run_named_routes() {
+  const uint64_t far = (1ull << 32) - 64;
+  const struct { const char* what; Source src; int bits, compounding, flags, K, N; uint64_t path_begin; bool attr_walk; const char* kernel; } named[] = {
+      {"plain, one portfolio", SRC_GAUSS, 0, MCP_COMPOUND_SIMPLE, 0, 1, 16, 0, false, "mc_paths_lean_kernel<NB, false>"},
+      {"plain, log", SRC_GAUSS, 0, MCP_COMPOUND_LOG, 0, 1, 16, 0, false, "mc_paths_lean_kernel<NB, true>"},
+      {"plain, N > 16", SRC_GAUSS, 0, MCP_COMPOUND_SIMPLE, 0, 1, 17, 0, false, "mc_paths_kernel<NB, KT, 1, false, false, false>"},
+      {"plain, across 2^32", SRC_GAUSS, 0, MCP_COMPOUND_SIMPLE, 0, 1, 16, far, false, "mc_paths_kernel<NB, KT, 1, false, false, false>"},
+      {"plain, K = 2", SRC_GAUSS, 0, MCP_COMPOUND_LOG, 0, 2, 16, 0, false, "mc_paths_kernel<NB, KT, 1, false, false, true>"},
+      {"plain, native math", SRC_GAUSS, 0, MCP_COMPOUND_SIMPLE, MCP_FLAG_NATIVE_MATH, 2, 16, 0, false, "mc_paths_kernel<NB, KT, 1, true, false, false>"},
+      {"plain, folded", SRC_GAUSS, 0, MCP_COMPOUND_LOG, MCP_FLAG_FOLD, 1, 16, 0, false, "mc_paths_kernel<NB, 1, 1, false, true, true>"},
+      {"drawdown", SRC_GAUSS, B_DD, MCP_COMPOUND_LOG, 0, 1, 16, 0, false, "mc_paths_dd_kernel<NB, KT, 1, true>"},
+      {"horizons", SRC_GAUSS, B_HZ, MCP_COMPOUND_SIMPLE, 0, 1, 16, 0, false, "mc_paths_hz_kernel<NB, KT, 1, false>"},
+      {"bootstrap", SRC_BOOT, 0, MCP_COMPOUND_LOG, 0, 1, 16, 0, false, "mc_paths_boot_kernel<NB, KT, 1, true, true>"},
+      {"bootstrap, horizons", SRC_BOOT, B_HZ, MCP_COMPOUND_SIMPLE, 0, 1, 16, 0, false, "mc_paths_boot_hz_kernel<NB, KT, 1, false, true>"},
+      {"filtered", SRC_FHS, 0, MCP_COMPOUND_SIMPLE, 0, 1, 16, 0, false, "mc_paths_fhs_kernel<NB, KT, 1, true>"},
+      {"filtered, horizons", SRC_FHS, B_HZ, MCP_COMPOUND_SIMPLE, 0, 2, 16, 0, false, "mc_paths_fhs_kernel<NB, KT, 1, true>"},
+      {"Student-t", SRC_T, 0, MCP_COMPOUND_SIMPLE, 0, 1, 16, 0, false, "mc_paths_t_kernel<NB, KT, 1>"},
+      {"Student-t, drawdown", SRC_T, B_DD, MCP_COMPOUND_SIMPLE, 0, 1, 16, 0, false, "mc_paths_t_dd_kernel<NB, KT, 1>"},
+      {"GARCH", SRC_GAUSS, B_GARCH, MCP_COMPOUND_SIMPLE, 0, 1, 16, 0, false, "mc_paths_g_kernel<NB, KT, 1>"},
+      {"GARCH, Student-t, horizons", SRC_T, B_GARCH | B_HZ, MCP_COMPOUND_SIMPLE, 0, 1, 16, 0, false, "mc_paths_g_hz_kernel<NB, KT, 1>"},
+      {"jumps", SRC_GAUSS, B_JUMPS, MCP_COMPOUND_SIMPLE, 0, 1, 16, 0, false, "mc_paths_j_kernel<NB, KT, 1>"},
+      {"regimes, drawdown", SRC_GAUSS, B_REGIMES | B_DD, MCP_COMPOUND_SIMPLE, 0, 1, 16, 0, false, "mc_paths_r_dd_kernel<NB, KT, 1>"},
+      {"antithetic", SRC_GAUSS, B_ANTI, MCP_COMPOUND_LOG, 0, 1, 16, 0, false, "mc_paths_anti_kernel<NB, KT, 1, true, PathArgsA>"},
+      {"antithetic, Student-t, drawdown", SRC_T, B_ANTI | B_DD, MCP_COMPOUND_SIMPLE, 0, 1, 16, 0, false, "mc_paths_anti_kernel<NB, KT, 1, false, PathArgsGADD>"},
+      {"attribution, first walk", SRC_GAUSS, B_ATTR, MCP_COMPOUND_SIMPLE, 0, 1, 17, 0, false, "mc_paths_kernel<NB, KT, 1, false, false, false>"},
+      {"attribution, second walk", SRC_GAUSS, B_ATTR, MCP_COMPOUND_SIMPLE, 0, 2, 16, 0, true, "mc_paths_attr_kernel<NB, 1, 1>"},
+      {"rebalanced", SRC_GAUSS, B_REB, MCP_COMPOUND_SIMPLE, 0, 1, 16, 0, false, "mc_paths_reb_kernel<NB, KT, 1, false, false>"},
+      {"band", SRC_GAUSS, B_REB | B_BAND, MCP_COMPOUND_SIMPLE, 0, 2, 16, 0, false, "mc_paths_band_kernel<NB, 1, 1, false, false>"},
+      {"band, bootstrap", SRC_BOOT, B_REB | B_BAND, MCP_COMPOUND_SIMPLE, 0, 1, 16, 0, false, "mc_paths_band_kernel<NB, 1, 1, true, true>"},
+      {"cash", SRC_GAUSS, B_CASH, MCP_COMPOUND_SIMPLE, 0, 1, 16, 0, false, "mc_paths_cf_kernel<NB, KT, 1, false, false, false>"},
+      {"cash, Student-t", SRC_T, B_CASH, MCP_COMPOUND_SIMPLE, 0, 1, 16, 0, false, "mc_paths_cf_kernel<NB, KT, 1, false, false, true>"},
+      {"cash, lifetime", SRC_GAUSS, B_CASH | B_LIFE, MCP_COMPOUND_SIMPLE, 0, 1, 16, 0, false, "mc_paths_glide_life_kernel<NB, KT, 1, false, false, false>"},
+      {"glide", SRC_GAUSS, B_CASH | B_GLIDE, MCP_COMPOUND_SIMPLE, 0, 1, 16, 0, false, "mc_paths_glide_kernel<NB, KT, 1, false, false, false>"},
+      {"glide, lifetime", SRC_GAUSS, B_CASH | B_GLIDE | B_LIFE, MCP_COMPOUND_SIMPLE, 0, 1, 16, 0, false, "mc_paths_glide_life_kernel<NB, KT, 1, false, false, false>"},
+      {"spend", SRC_GAUSS, B_CASH | B_SPEND, MCP_COMPOUND_SIMPLE, 0, 1, 16, 0, false, "mc_paths_spend_kernel<NB, KT, 1, false, false, false>"},
+      {"spend, bootstrap", SRC_BOOT, B_CASH | B_SPEND, MCP_COMPOUND_SIMPLE, 0, 1, 16, 0, false, "mc_paths_spend_kernel<NB, KT, 1, true, true, false>"},
+      {"spend, lifetime", SRC_GAUSS, B_CASH | B_SPEND | B_LIFE, MCP_COMPOUND_SIMPLE, 0, 1, 16, 0, false, "mc_paths_spend_life_kernel<NB, KT, 1, false, false, false>"},
+      {"overlay", SRC_GAUSS, B_OVERLAY, MCP_COMPOUND_SIMPLE, 0, 1, 16, 0, false, "mc_paths_ov_kernel<NB, KT, 1, false, false>"},
+      {"overlay, Student-t, drawdown", SRC_T, B_OVERLAY | B_DD, MCP_COMPOUND_SIMPLE, 0, 1, 16, 0, false, "mc_paths_ov_kernel<NB, KT, 1, true, true>"},
+      {"protect", SRC_GAUSS, B_PROTECT, MCP_COMPOUND_SIMPLE, 0, 1, 16, 0, false, "mc_paths_pi_kernel<NB, KT, 1, false, false>"},
+      {"protect, GARCH, drawdown", SRC_GAUSS, B_PROTECT | B_GARCH | B_DD, MCP_COMPOUND_SIMPLE, 0, 1, 16, 0, false, "mc_paths_pi_kernel<NB, KT, 1, false, true>"},
+      {"protect, jumps, horizons", SRC_GAUSS, B_PROTECT | B_JUMPS | B_HZ, MCP_COMPOUND_SIMPLE, 0, 1, 16, 0, false, "mc_paths_pi_kernel<NB, KT, 1, true, false>"},
+  };
+  for (const auto& c : named) {
+    snprintf(g_case, sizeof g_case, "named route: %s", c.what);
+    Payloads p(c.N, c.K, 12, 8);
+    const mcp_params prm = {c.N, 12, c.K, c.compounding, c.flags, 0, 1.0, 0.95, 0.0};
+    const Request rq = p.request(c.src, c.bits);
+    EXPECT(check_request(&prm, rq, 66, nullptr, c.path_begin) == MCP_OK);
+    const mcp::PathKernel k = route_kernel(&prm, rq, c.attr_walk, c.path_begin, 66);
+    const Row* row = select_row(c.N == 16 ? 4 : 5, k);
+    EXPECT(row && strcmp(row->kernel, c.kernel) == 0 && ((k.flags & mcp::PK_KT8) != 0) == (c.K > 1 && !(c.bits & B_BAND) && !c.attr_walk));
+  }
+}
+
 int main() {
   const int Ns[3] = {1, 5, MCP_MAX_ASSETS}, Ks[4] = {1, 8, 9, 17}, Hs[2] = {0, 2};
   int n = 0;
@@ -333,6 +549,8 @@ int main() {
     for (int K : Ks)
       for (int H : Hs) { run_shape(N, K, 12, H); n++; }
   run_plans();
-  printf("host_selftest ok: %d shapes x %d requests, the plans\n", n, (int)N_FEATURES);
+  run_named_routes();
+  const long n_routed = run_routes();
+  printf("host_selftest ok: %d shapes x %d requests, the plans, the routes of %ld requests\n", n, (int)N_FEATURES, n_routed);
   return 0;
 }

@@ -11,6 +11,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "mcp_route.h"   // ICDF_ENTRIES, ICDF_PAD, ICDF_LDS_ENTRIES: the sizes of the table that the host's routing needs too
+
 namespace mcp {
 
 typedef float f32x2 __attribute__((ext_vector_type(2)));
@@ -130,16 +132,9 @@ __device__ __forceinline__ void philox4x32_10_uhi(uint32_t blk, uint32_t p_lo, u
 
 constexpr float NEG_2LN2 = -0x1.62e43p+0f;       // -2 ln 2 (native Box-Muller only)
 
-constexpr int ICDF_ENTRIES = 1056;   // 33 octaves x 32 mantissa bins of float4 {c0,c1,c2,c3}: 16.5 KiB of LDS per workgroup
 constexpr uint32_t ICDF_E_LO = 94;   // u in [2^-33, 1/2]: binary32 exponents 94..126
 
 __device__ __forceinline__ float fma32(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
-
-// The LDS copy of the table carries ICDF_PAD unused entries in front: u is formed with its exponent pre-scaled by 2^-93
-// (binary32 exponent field 1..33 instead of 94..126; same significand, so the same table entry and the same delta), and
-// then bits(u) >> 18 indexes the padded table directly -- the spec's subtraction of (94 << 23) costs no instruction.
-constexpr int ICDF_PAD = 32;
-constexpr int ICDF_LDS_ENTRIES = ICDF_ENTRIES + ICDF_PAD;
 
 // Constants of the transform that must sit in VGPRs: an SGPR (or, in VOP3, any non-inline) operand halves the issue
 // rate of a VALU instruction on gfx950 (profiles/r01_valu_rates.txt).

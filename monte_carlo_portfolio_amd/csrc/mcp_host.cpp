@@ -1,6 +1,7 @@
 // mcp_host.cpp -- the host code of libmcport.so that touches no device (mcp_host.h): argument checking, every feature's host
-// constants and closed-form pivots, parameter packing, the layout of a tile's parameter block, and the entry points of
-// include/mcport.h that need nothing else.  No device header: make host-selftest builds this file with a plain C++ compiler.
+// constants and closed-form pivots, parameter packing, the layout of a tile's parameter block, the choice of the path kernel
+// (route_kernel), and the entry points of include/mcport.h that need nothing else.  No device header: make host-selftest builds
+// this file with a plain C++ compiler.
 #include "mcp_host.h"
 
 #include <algorithm>
@@ -785,6 +786,60 @@ int check_request(const mcp_params* prm, const Request& rq, uint64_t n_paths, co
   for (int i = 0; i < 3; i++)
     if (need[i] < n_paths) return fail(MCP_E_ARG, "%s %llu < n_paths %llu", name[i], (unsigned long long)need[i], (unsigned long long)n_paths);
   return MCP_OK;
+}
+
+#ifndef MCP_EXP_LEAN        // 1: launches that pass mcp::lean_range run mc_paths_lean_kernel; 0: every launch stays on mc_paths_kernel
+#define MCP_EXP_LEAN 1      // (tools/kernel_lab.py arms `lean` and `nolean`; profiles/lean_probe.json)
+#endif
+
+// Which kernel walks the paths of a checked request (mcp_route.h; the rows are mcp_paths_ladder.inc).  Every other request than a
+// plain Gaussian walk of K >= 17 portfolios, which goes to the MFMA sweep kernels before this is asked (mcp_api.cpp), runs its
+// family's kernel, K >= 2 as passes of the 8-portfolio kernel.
+mcp::PathKernel route_kernel(const mcp_params* prm, const Request& rq, bool attr_walk, uint64_t path_begin, uint64_t n_paths) {
+  using namespace mcp;
+  const int nb = (prm->n_assets + 3) / 4;
+  // Gaussian, Student-t and GARCH requests of a family with one walk run the GARCH walk on Student-t draws: without GARCH on
+  // alpha = beta = 0, h0 = 1, which is the Gaussian or Student-t call bit for bit (SPEC.md 4.9)
+  const auto share_garch_walk = [](uint32_t flags) { return (flags & ~(uint32_t)PK_STT) | PK_GV; };
+  PathKernel k = {FAM_PLAIN, 0};
+  if (prm->compounding == MCP_COMPOUND_LOG) k.flags |= PK_LOGC;
+  if (rq.src == SRC_BOOT) k.flags |= PK_BOOT;
+  if (rq.src == SRC_FHS) k.flags |= PK_BOOT | PK_FH;
+  if (rq.src == SRC_FHS ? filt_fits_lds((uint64_t)rq.filt->n_rows, nb) : rq.src == SRC_BOOT && boot_fits_lds((uint64_t)rq.boot->n_rows, nb))
+    k.flags |= PK_BLDS;
+  if (rq.src == SRC_T) k.flags |= PK_STT;
+  if (attr_walk) {                        // SPEC.md 4.10: one portfolio per pass.  The walk draws as the GARCH kernel does
+    k.family = FAM_AT;
+    k.flags = share_garch_walk(k.flags);
+    return k;
+  }
+  k.family = rq.overlay ? FAM_OV : rq.cash ? FAM_CF : rq.rebalanced ? FAM_REB : rq.dd ? FAM_DD : rq.hz ? FAM_HZ : FAM_PLAIN;
+  if (rq.src == SRC_FHS) k.family = FAM_HZ;            // SPEC.md 4.11: one segmented kernel serves terminal-only and horizon calls
+  if (rq.overlay && rq.dd) k.flags |= PK_DD;
+  if (rq.garch) k.flags = share_garch_walk(k.flags);   // the GARCH kernels draw Student-t, nu = 0 for Gaussian draws
+  if (rq.jumps) k.flags |= PK_JP;
+  if (rq.regimes) k.flags |= PK_RS;
+  if (rq.glide) k.flags |= PK_GP;
+  if (rq.spend) k.flags |= PK_SP;
+  if (rq.life) k.flags |= PK_LT;
+  if (rq.life && !rq.spend) k.flags |= PK_GP;          // SPEC.md 4.17: a plain cash-flow request runs the glide twin on G = 0 (no targets)
+  if (rq.protect) {                       // SPEC.md 4.15: one segmented kernel serves terminal-only and horizon calls, on the GARCH or the jump walk
+    k.family = rq.dd ? FAM_DD : FAM_HZ;
+    k.flags |= PK_PI;
+    if (!rq.jumps) k.flags = share_garch_walk(k.flags);
+  }
+  if (rq.band) k.flags |= PK_TB;          // SPEC.md 4.18: B is per portfolio, so every portfolio of a banded call is a pass of its own
+  if (prm->n_portfolios > 1 && !rq.band) k.flags |= PK_KT8;
+  if (prm->flags & MCP_FLAG_NATIVE_MATH) k.flags |= PK_NATIVE;
+  if (prm->flags & MCP_FLAG_FOLD) k.flags |= PK_FOLD;
+  if (rq.anti) {                          // SPEC.md 2.3: Student-t and GARCH requests share the GARCH walk, as the attribution does
+    k.flags |= PK_ANTI;
+    if (k.flags & (PK_STT | PK_GV)) k.flags = share_garch_walk(k.flags);
+  }
+  // the plain Gaussian walk of one portfolio whose paths share the high counter word runs the lean step loop (mcp_paths.h, UHI)
+  if (MCP_EXP_LEAN && k.family == FAM_PLAIN && (k.flags & ~(uint32_t)PK_LOGC) == 0 && nb <= LEAN_MAX_NB && lean_range(path_begin, n_paths))
+    k.flags |= PK_UHI;
+  return k;
 }
 
 // SPEC.md 5.4: mu_i of the pivot of rebalanced paths, binary64 -- the drift (Gaussian) or the mean of column i of the rows

@@ -1,6 +1,7 @@
 // mcp_host.h -- the host code of libmcport.so that touches no device (mcp_host.cpp): every argument rule, every feature's host
-// constants, every closed-form pivot, the packers, the layout of a tile's parameter block and the plan of a call.  Internal, not installed.  It
-// includes no device header, so that mcp_host.cpp also builds with a plain C++ compiler (make host-selftest).
+// constants, every closed-form pivot, the packers, the layout of a tile's parameter block, the plan of a call and the choice of the
+// path kernel.  Internal, not installed.  It includes no device header, so that mcp_host.cpp also builds with a plain C++ compiler
+// (make host-selftest).
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -12,6 +13,7 @@
 #include "../../include/mcport_spend.h"
 #include "../../include/mcport_life.h"
 #include "../../include/mcport_band.h"
+#include "mcp_route.h"
 
 namespace mcp {
 constexpr int SWEEP_MIN_K = 17;      // from this many portfolios on the MFMA sweep kernels run
@@ -160,6 +162,10 @@ int check_band(const mcp_params* prm, const mcp_band* bd);
 // Every rule a request meets: each feature's own arguments, then which features combine (MCP_E_UNSUPPORTED), then the outputs.
 // `ln`: an mcp_launch_paths* call, whose device arrays are checked instead of the host arrays of an mcp_simulate* call.
 int check_request(const mcp_params* prm, const Request& rq, uint64_t n_paths, const Launch* ln = nullptr, uint64_t path_begin = 0);
+// The path kernel of one launch of a checked request on the paths [path_begin, path_begin + n_paths): its selector, with no flag
+// set that the kernel does not consume, so that it equals one row of mcp_paths_ladder.inc (host_selftest.cpp proves both for every
+// request check_request accepts).  `attr_walk`: the second walk of an attribution call (Launch::attr) instead of the request's own.
+mcp::PathKernel route_kernel(const mcp_params* prm, const Request& rq, bool attr_walk, uint64_t path_begin, uint64_t n_paths);
 
 // ---- each feature's host constants ----
 uint64_t boot_threshold(double b);

@@ -540,13 +540,7 @@ inline A make_args(const PathLaunchArgs& s) {
   return x;
 }
 
-// The LDS copy of the row table takes the slot of the inverse-CDF table (ICDF_LDS_ENTRIES float4: the bootstrap needs neither
-// that table nor the drift copy in its padding): R rows of NB float4 fit when R * NB <= ICDF_LDS_ENTRIES (N = 16: 272 rows).
-__host__ __device__ constexpr bool boot_fits_lds(uint64_t n_rows, int nb) { return n_rows * (uint64_t)nb <= (uint64_t)ICDF_LDS_ENTRIES; }
-// The filtered rows carry their shock table behind them in the same slot, ceil(R/4) float4 more (N = 16: 256 rows).
-__host__ __device__ constexpr bool filt_fits_lds(uint64_t n_rows, int nb) {
-  return n_rows * (uint64_t)nb + (n_rows + 3) / 4 <= (uint64_t)ICDF_LDS_ENTRIES;
-}
+// (boot_fits_lds / filt_fits_lds, mcp_route.h: when the row table takes the LDS slot of the inverse-CDF table)
 // LDS banking of the gather (ds_read_b128: 16 slots of 16 B, bank slot = float4 index mod 16).  Row j starts at slot
 // (j NB) mod 16, a multiple of G = the largest power of two dividing NB, so a fixed chunk q of random rows would fall on only
 // 16 / G slots.  Chunk q of row j is stored at j NB + (q ^ s(j)), s(j) = (j >> log2(16 / G)) & (G - 1): the bits of j that

@@ -57,31 +57,8 @@ __host__ __device__ inline int stream_slots(int K) {
 struct PathArgs;
 struct PathLaunchArgs;
 
-// Which path kernel a launch runs: the family, the compounding mode, the draw source (boot: the bootstrap's rows, blds: its row
-// table copied into LDS, it fits boot_fits_lds; stt: Student-t draws; gv: GARCH; fh with boot: filtered residual rows, blds by
-// filt_fits_lds), dd (FAM_OV only: the overlay kernel that also
-// tracks the drawdown), kt8 (passes of 8 portfolios instead of 1), the plain Gaussian kernel's native-math and folded steps, and
-// anti (the antithetic kernels of the plain, drawdown and horizon families: Gaussian draws, or stt and gv both set for the GARCH walk),
-// and uhi (the plain Gaussian walk of one portfolio on the spec's normals whose launch passes lean_range: mc_paths_lean_kernel,
-// N <= 16 only -- LEAN_MAX_NB: from NB = 5 on the listings show it at more registers than mc_paths_kernel, at NB = 12, 14 and 15
-// at one wave per SIMD fewer, and nothing above NB = 4 has been timed), and jp (the jump-diffusion kernels of the plain, drawdown
-// and horizon families: Gaussian draws plus the market jump of SPEC.md 2.5, simple compounding), and rs (the regime-switching kernels
-// of the same three families: Gaussian draws on the drift and factor of the path's regime, SPEC.md 2.6, simple compounding), and
-// gp (FAM_CF only: the glide-path kernel, the cash-flow walk on scheduled target weights, SPEC.md 4.14), and pi (the floor-protection
-// kernel of SPEC.md 4.15: FAM_DD with the drawdown, else FAM_HZ, H = 0 included; stt and gv both set for the GARCH walk, or jp), and
-// sp (FAM_CF only: the spending kernel, the cash-flow walk on the path's own withdrawal, SPEC.md 4.16), and lt (with exactly one of
-// gp and sp: that kernel's lifetime twin, SPEC.md 4.17; a plain cash-flow request asks for the glide twin with no break), and tb
-// (FAM_REB only, never kt8: the tolerance-band kernel of SPEC.md 4.18, K portfolios as K passes of one).
-// The one ladder of mcp_paths_inst.hip maps it to a kernel and lists which selectors have one.
-constexpr int LEAN_MAX_NB = 4;
-enum PathFamily { FAM_PLAIN, FAM_DD, FAM_HZ, FAM_REB, FAM_CF, FAM_OV, FAM_AT };
-struct PathKernel {
-  int family;
-  bool logc, boot, blds, stt, dd, gv, kt8, native, fold, anti, fh, uhi, jp, rs, gp, pi, sp, lt, tb;
-};
-
-// mcp_paths_inst.hip (one translation unit per NB): every pass of the kernel that `k` selects, on the blocks of `args` that the
-// kernel's own argument struct has; hipErrorInvalidValue for a selector that has no kernel.
+// mcp_paths_inst.hip (one translation unit per NB): every pass of the kernel that `k` (mcp_route.h) selects, on the blocks of `args`
+// that the kernel's own argument struct has; hipErrorInvalidValue for a selector without a row in mcp_paths_ladder.inc.
 typedef hipError_t (*launch_paths_fn)(const PathKernel& k, const PathLaunchArgs& args, hipStream_t stream);
 #define MCP_DECL_NB(n) hipError_t launch_paths_nb##n(const PathKernel& k, const PathLaunchArgs& args, hipStream_t stream);
 MCP_DECL_NB(1) MCP_DECL_NB(2) MCP_DECL_NB(3) MCP_DECL_NB(4) MCP_DECL_NB(5) MCP_DECL_NB(6) MCP_DECL_NB(7) MCP_DECL_NB(8)

@@ -1,7 +1,8 @@
 """csrc/mcp_host.cpp -- every argument rule, host constant, pivot, packer and the tile layout -- needs no device header, so
 `make host-selftest` builds it with the plain C++ compiler that ships beside hipcc, under AddressSanitizer + UBSan, together with
 csrc/host_selftest.cpp, and runs that program: every pure entry point and, per feature, check_request, tile_layout + pack_tile
-and request_pivots on heap buffers of exactly the documented lengths.  The build itself proves the unit is free of the device
+and request_pivots on heap buffers of exactly the documented lengths, then the routing of every combination of features:
+check_request, route_kernel and the rows of csrc/mcp_paths_ladder.inc, the text the device build includes.  The build itself proves the unit is free of the device
 runtime; an overrun is a sanitizer report and a non-zero exit.  No GPU, nothing loaded into this process."""
 import os
 import subprocess
