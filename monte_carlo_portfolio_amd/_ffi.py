@@ -121,6 +121,13 @@ class McpProtect(ctypes.Structure):
                 ("ratchet", ctypes.c_double), ("target", ctypes.c_void_p), ("reserved", ctypes.c_int32)]
 
 
+class McpVolTarget(ctypes.Structure):
+    """mcp_vol_target (include/mcport_voltarget.h): target, decay, cap, rate and spread of SPEC.md 4.19, the optional initial variance
+    estimates (NULL or binary64 [K]) and the optional target value of the second count (NULL or one binary64 value)."""
+    _fields_ = [("target", ctypes.c_double), ("decay", ctypes.c_double), ("cap", ctypes.c_double), ("rate", ctypes.c_double),
+                ("spread", ctypes.c_double), ("s0", ctypes.c_void_p), ("target_value", ctypes.c_void_p), ("reserved", ctypes.c_int32)]
+
+
 class McpSpending(ctypes.Structure):
     """mcp_spending (include/mcport_spend.h): the rate, the largest cut and raise per review, the inflation per review, the optional
     first withdrawal and target, and the review period of the spending rule of SPEC.md 4.16."""
@@ -234,6 +241,7 @@ ARG_GROUPS = {
     "sp": [ctypes.POINTER(McpSpending)], "wd": [_vp, _vp],     # withdrawn_out, wd_stats_out
     "life": [_vp, _vp, _vp, _int, _vp, _vp],              # life_out, life_hist_out, life_sum_out, n_life_levels, life_levels, life_q_out
     "tb": [ctypes.POINTER(McpBand)],
+    "vt": [ctypes.POINTER(McpVolTarget)], "exposure": [_vp, _vp],     # exposure_out, exposure_stats_out
     # trades_out, trade_hist_out, trade_sum_out, n_trade_levels, trade_levels, trade_q_out, turnover_out, turnover_stats_out
     "trades": [_vp, _vp, _vp, _int, _vp, _vp, _vp, _vp],
     "mu": [_vp], "chol": [_vp], "W": [_vp], "mu*": [_f32p], "chol*": [_f32p], "W*": [_f32p],
@@ -313,6 +321,17 @@ BAND_SIGNATURES = {
 }
 BAND_SIGNATURES.update((name, (_int, [t for g in groups for t in ARG_GROUPS[g]])) for name, groups in BAND_ENTRIES.items())
 
+# And for include/mcport_voltarget.h (SPEC.md 4.19 / 5.19).
+VOLTARGET_ENTRIES = {
+    "mcp_simulate_vol_target": "ctx prm vt gv st jp mu chol W walk hz_in out dd exposure counts hz_out hz_counts",
+}
+VOLTARGET_ENTRIES = {name: tuple(groups.split()) for name, groups in VOLTARGET_ENTRIES.items()}
+VOLTARGET_SIGNATURES = {
+    "mcp_vol_target_pivots": (_int, [_PP, ctypes.POINTER(McpVolTarget), _vp, _vp, _vp, _int, _vp, _vp, _vp]),
+    "mcp_vol_target_consts": (_int, [_PP, ctypes.POINTER(McpVolTarget), _vp, _vp, _vp]),
+}
+VOLTARGET_SIGNATURES.update((name, (_int, [t for g in groups for t in ARG_GROUPS[g]])) for name, groups in VOLTARGET_ENTRIES.items())
+
 _LIB = None
 
 
@@ -378,7 +397,7 @@ def lib() -> ctypes.CDLL:
             fn.restype = res
             fn.argtypes = args
         for name, (res, args) in list(EXTENSION_SIGNATURES.items()) + list(SPEND_SIGNATURES.items()) + list(LIFE_SIGNATURES.items()) + \
-                list(BAND_SIGNATURES.items()):
+                list(BAND_SIGNATURES.items()) + list(VOLTARGET_SIGNATURES.items()):
             fn = getattr(L, name)          # additive entry points, detected by symbol: a library without them is too old
             fn.restype = res
             fn.argtypes = args
@@ -667,6 +686,41 @@ def band_reviews(n_steps: int, every: int) -> int:
     """n_reviews of SPEC.md 4.18 (include/mcport_band.h, mcp_band_reviews), pure host arithmetic."""
     n = lib().mcp_band_reviews(ctypes.byref(McpParams(n_steps=int(n_steps))), ctypes.byref(McpBand(int(every), 0, 0.0, None)))
     return check(n)
+
+
+def make_vol_target(target: float, decay: float, cap: float = 1.0, rate: float = 0.0, spread: float = 0.0, s0=None,
+                    target_value=None) -> McpVolTarget:
+    """mcp_vol_target of the rule of SPEC.md 4.19 (include/mcport_voltarget.h); s0 None: the default of the Gaussian part; the arrays
+    behind the two pointers are kept on the struct."""
+    s0a = np.ascontiguousarray(s0, np.float64).ravel() if s0 is not None else None
+    tg = np.array([float(target_value)], np.float64) if target_value is not None else None
+    vt = McpVolTarget(float(target), float(decay), float(cap), float(rate), float(spread), ptr(s0a), ptr(tg), 0)
+    vt._keep = (s0a, tg)
+    return vt
+
+
+def vol_target_consts(prm: McpParams, vol_target: McpVolTarget, chol: np.ndarray | None, W: np.ndarray | None):
+    """(binary32 [6] {tgt, lam, oml, b, rf, sp}, binary32 [K] s0): the constants of the rule as the walk uses them
+    (include/mcport_voltarget.h, mcp_vol_target_consts), pure host arithmetic."""
+    chol32 = np.ascontiguousarray(chol, np.float32) if chol is not None else None
+    W32 = np.ascontiguousarray(W, np.float32) if W is not None else None
+    out = np.zeros(6 + max(int(prm.n_portfolios), 0), np.float32)
+    check(lib().mcp_vol_target_consts(ctypes.byref(prm), ref(vol_target), ptr(chol32), ptr(W32), ptr(out)))
+    return out[:6].copy(), out[6:].copy()
+
+
+def vol_target_pivots(prm: McpParams, vol_target: McpVolTarget, mu: np.ndarray, chol: np.ndarray, W: np.ndarray, horizons=None):
+    """([K] pivots at n_steps, [H, K] at the horizons or None): the shifts of the moments of volatility-targeted paths (SPEC.md 5.19;
+    include/mcport_voltarget.h, mcp_vol_target_pivots), pure host arithmetic."""
+    W = np.ascontiguousarray(W, np.float32)
+    mu32 = np.ascontiguousarray(mu, np.float32)
+    chol32 = np.ascontiguousarray(chol, np.float32)
+    hz = np.ascontiguousarray(horizons, np.int32) if horizons is not None and len(horizons) else None
+    out = np.zeros(W.shape[0], np.float64)
+    hout = np.zeros((hz.size, W.shape[0]), np.float64) if hz is not None else None
+    check(lib().mcp_vol_target_pivots(ctypes.byref(prm), ref(vol_target), ptr(mu32), ptr(chol32), ptr(W), 0 if hz is None else hz.size,
+                                      ptr(hz), ptr(out), ptr(hout)))
+    return out, hout
 
 
 def make_overlay(rows: np.ndarray, row_begin: np.ndarray, spot: np.ndarray) -> McpOverlay:

@@ -34,7 +34,7 @@ template <class T> static bool finite(const std::vector<T>& v) {
 // Minimal valid arguments of every feature for N assets, K portfolios, T steps and row tables of R rows, with the outputs a request
 // must carry, and the request of one combination of features over them.
 enum Bit { B_DD = 1, B_HZ = 2, B_REB = 4, B_BAND = 8, B_CASH = 16, B_GLIDE = 32, B_SPEND = 64, B_LIFE = 128, B_PROTECT = 256, B_OVERLAY = 512,
-           B_GARCH = 1024, B_JUMPS = 2048, B_REGIMES = 4096, B_ANTI = 8192, B_ATTR = 16384, N_BITS = 15 };
+           B_GARCH = 1024, B_JUMPS = 2048, B_REGIMES = 4096, B_ANTI = 8192, B_ATTR = 16384, B_VT = 32768, N_BITS = 16 };
 struct Payloads {
   static constexpr int G = 2, H = 2;
   const int N, K, T, R;
@@ -51,6 +51,7 @@ struct Payloads {
   mcp_glide gl;
   mcp_cashflow cf, no_cf;
   mcp_protect pt;
+  const mcp_vol_target vt = {0.01, 0.94, 1.5, 0.001, 0.0005, nullptr, nullptr, 0};
   mcp_overlay ov;
   const mcp_rebalance reb = {5, 0, 0.001};
   mcp_band bd;
@@ -113,23 +114,25 @@ struct Payloads {
     if (bits & B_SPEND) { rq.spend = true; rq.sp = &sp; rq.wd_stats_out = second_stats.data(); }
     if (bits & B_LIFE) { rq.life = true; rq.life_hist_out = life_hist.data(); }
     if (bits & B_PROTECT) { rq.protect = true; rq.pi = &pt; }
+    if (bits & B_VT) { rq.vol_target = true; rq.vt = &vt; rq.exposure_stats_out = (bits & B_DD) ? nullptr : second_stats.data(); }
     if (bits & B_OVERLAY) { rq.overlay = true; rq.ov = &ov; }
     if (bits & B_GARCH) { rq.garch = true; rq.gv = &gv; }
     if (bits & B_JUMPS) { rq.jumps = true; rq.jp = &jp; }
     if (bits & B_REGIMES) { rq.regimes = true; rq.rs = &rs; }
     if (bits & B_ANTI) { rq.anti = true; rq.pair_out = pair.data(); }
     if (bits & B_ATTR) { rq.attr = true; rq.attr_out = attr.data(); rq.attr_counts_out = attr_counts.data(); }
-    if (rq.cash || rq.protect) { rq.counts_out = counts.data(); rq.hz_counts_out = rq.hz ? hz_counts.data() : nullptr; }
+    if (rq.cash || rq.protect || rq.vol_target) { rq.counts_out = counts.data(); rq.hz_counts_out = rq.hz ? hz_counts.data() : nullptr; }
     return rq;
   }
 };
 
-enum Feature { PLAIN, BOOT, FILTERED, JUMPS, REGIMES, GLIDE_CF, GLIDE, PROTECT, CASH, OVERLAY, SPEND, SPEND_BOOT, BAND, BAND_BOOT, N_FEATURES };
+enum Feature { PLAIN, BOOT, FILTERED, JUMPS, REGIMES, GLIDE_CF, GLIDE, PROTECT, CASH, OVERLAY, SPEND, SPEND_BOOT, BAND, BAND_BOOT, VOL_TARGET, N_FEATURES };
 static const struct { const char* name; Source src; int bits; } k_features[N_FEATURES] = {
     {"plain", SRC_GAUSS, 0}, {"bootstrap", SRC_BOOT, 0}, {"filtered", SRC_FHS, 0}, {"jumps", SRC_GAUSS, B_JUMPS}, {"regimes", SRC_GAUSS, B_REGIMES},
     {"glide+flows", SRC_GAUSS, B_CASH | B_GLIDE}, {"glide", SRC_GAUSS, B_CASH | B_GLIDE}, {"protect", SRC_GAUSS, B_PROTECT},
     {"cash", SRC_GAUSS, B_CASH}, {"overlay", SRC_GAUSS, B_OVERLAY}, {"spend", SRC_GAUSS, B_CASH | B_SPEND},
-    {"spend+bootstrap", SRC_BOOT, B_CASH | B_SPEND}, {"band", SRC_GAUSS, B_REB | B_BAND}, {"band+bootstrap", SRC_BOOT, B_REB | B_BAND}};
+    {"spend+bootstrap", SRC_BOOT, B_CASH | B_SPEND}, {"band", SRC_GAUSS, B_REB | B_BAND}, {"band+bootstrap", SRC_BOOT, B_REB | B_BAND},
+    {"vol_target", SRC_GAUSS, B_VT}};
 
 static void run_shape(int N, int K, int T, int H) {
   Payloads p(N, K, T, 6);
@@ -155,6 +158,13 @@ static void run_shape(int N, int K, int T, int H) {
   EXPECT(mcp_regime_pivots(&prm, &p.rs, p.mu.data(), p.W.data(), H, hs, pv.data(), hzp) == MCP_OK && finite(pv) && finite(hz));
   EXPECT(mcp_glide_pivots(&prm, &p.gl, &p.cf, p.mu.data(), nullptr, p.W.data(), H, hs, pv.data(), hzp) == MCP_OK && finite(pv) && finite(hz));
   EXPECT(mcp_protect_pivots(&prm, &p.pt, p.mu.data(), p.W.data(), H, hs, pv.data(), hzp) == MCP_OK && finite(pv) && finite(hz));
+  {                                       // SPEC.md 4.19 / 5.19: the pivots, and the six constants with s0_k behind them
+    std::vector<float> vc(6 + (size_t)K);
+    EXPECT(mcp_vol_target_pivots(&prm, &p.vt, p.mu.data(), p.chol.data(), p.W.data(), H, hs, pv.data(), hzp) == MCP_OK && finite(pv) && finite(hz));
+    EXPECT(mcp_vol_target_consts(&prm, &p.vt, p.chol.data(), p.W.data(), vc.data()) == MCP_OK && finite(vc) && vc[0] == 0.01f && vc[1] == 0.94f &&
+           vc[2] == (float)(1.0 - (double)0.94f) && vc[3] == 1.5f && vc[6] > 0.0f);
+    EXPECT(mcp_vol_target_consts(&prm, &p.vt, nullptr, p.W.data(), vc.data()) == MCP_E_ARG);   // the default s0 needs the factor
+  }
   std::vector<double> wdp(K);
   std::vector<float> c5(5);
   EXPECT(mcp_spending_pivots(&prm, &p.sp, p.mu.data(), nullptr, p.W.data(), H, hs, pv.data(), hzp, wdp.data()) == MCP_OK && finite(pv) && finite(hz) && finite(wdp));
@@ -185,15 +195,17 @@ static void run_shape(int N, int K, int T, int H) {
     std::vector<mcp_stats> second_stats(K);
     if (rq.band) { rq.turnover_out = second.data(); rq.turnover_stats_out = second_stats.data(); rq.trades_out = record.data(); }
     if (rq.spend) { rq.wd_out = second.data(); rq.wd_stats_out = second_stats.data(); }
+    if (rq.vol_target) { rq.exposure_out = second.data(); rq.exposure_stats_out = second_stats.data(); }
     EXPECT(check_request(&prm, rq, 4) == MCP_OK);
     {                                     // the one second array and the one integer record of the request, on the request's own outputs
       const Second sec = second_of(rq);
       const Counted cnt = counted_of(&prm, rq);
-      EXPECT(sec.on == (rq.band || rq.spend) && cnt.on == rq.band && cnt.bins == count_bins(&prm, rq));
+      EXPECT(sec.on == (rq.band || rq.spend || rq.vol_target) && cnt.on == rq.band && cnt.bins == count_bins(&prm, rq));
       EXPECT(sec.out == (sec.on ? second.data() : nullptr) && sec.stats_out == (sec.on ? second_stats.data() : nullptr));
       EXPECT(cnt.out == (cnt.on ? record.data() : nullptr) && cnt.hist_out == (cnt.on ? p.trade_hist.data() : nullptr));
       if (rq.band) EXPECT(sec.unit_v0 && !sec.pivoted);   // SPEC.md 5.18: x = Y - 1, no pivot
       if (rq.spend) EXPECT(!sec.unit_v0 && sec.pivoted);  // SPEC.md 5.16: x = Y / fl32(v0) - 1, the pivots of request_wd_pivots
+      if (rq.vol_target) EXPECT(sec.unit_v0 && !sec.pivoted);   // SPEC.md 5.19: x = Y - 1, no pivot
       Request dr = rq;                                    // SPEC.md 5.1: the drawdown, where the request may carry it
       ask_drawdown(dr, second.data(), second_stats.data());
       if (check_request(&prm, dr, 4) == MCP_OK) {
@@ -213,6 +225,33 @@ static void run_shape(int N, int K, int T, int H) {
       EXPECT(check_request(&prm, lr, 4) == (rq.cash ? MCP_OK : MCP_E_UNSUPPORTED));
       lr.life_hist_out = nullptr;
       EXPECT(check_request(&prm, lr, 4) == (rq.cash ? MCP_E_ARG : MCP_E_UNSUPPORTED));
+    }
+    if (rq.vol_target) {                  // SPEC.md 4.19 / 5.19: one second array; a bad constant; s0 behind the block, padded with ones
+      Request vr = rq;
+      ask_drawdown(vr, nullptr, p.second_stats.data());
+      EXPECT(check_request(&prm, vr, 4) == MCP_E_UNSUPPORTED);             // the exposure record together with the drawdown
+      vr.exposure_out = nullptr;
+      vr.exposure_stats_out = nullptr;
+      EXPECT(check_request(&prm, vr, 4) == (H ? MCP_E_UNSUPPORTED : MCP_OK) && second_of(vr).stats_out == p.second_stats.data());
+      vr = rq;
+      vr.exposure_stats_out = nullptr;
+      EXPECT(check_request(&prm, vr, 4) == MCP_E_ARG);
+      std::vector<double> s0(K, 1e-4);
+      mcp_vol_target bad_vt = p.vt;
+      bad_vt.s0 = s0.data();
+      vr = rq;
+      vr.vt = &bad_vt;
+      EXPECT(check_request(&prm, vr, 4) == MCP_OK);
+      s0.back() = 0.0;
+      EXPECT(check_request(&prm, vr, 4) == MCP_E_ARG);
+      bad_vt = p.vt;
+      bad_vt.decay = 1.0000001;
+      EXPECT(check_request(&prm, vr, 4) == MCP_E_ARG);
+      bad_vt = p.vt;
+      bad_vt.spread = -1e-9;
+      EXPECT(check_request(&prm, vr, 4) == MCP_E_ARG);
+      const TileLayout lay = tile_layout(&prm, rq, K);
+      EXPECT(lay.total - lay.floor == 8 * (((size_t)K + 7) / 8));
     }
     if (rq.band) {                        // SPEC.md 4.18: a negative entry, a missing histogram, and the size of the histogram
       Request br = rq;
@@ -444,11 +483,11 @@ static const Row* select_row(int nb, const mcp::PathKernel& k, int* n_out = null
 
 static long run_routes() {
   using namespace mcp;
-  // (d) the table: 78 rows for NB <= LEAN_MAX_NB (the two lean kernels), 76 above; at KT = 8 without the folded step, the lean kernels,
+  // (d) the table: 82 rows for NB <= LEAN_MAX_NB (the two lean kernels), 80 above; at KT = 8 without the folded step, the lean kernels,
   // the bands and the attribution
   for (int nb : {1, 4, 5, 16}) {
     snprintf(g_case, sizeof g_case, "row counts, nb=%d", nb);
-    EXPECT(rows_at(nb, false).size() == (nb <= LEAN_MAX_NB ? 78u : 76u) && rows_at(nb, true).size() == 70u);
+    EXPECT(rows_at(nb, false).size() == (nb <= LEAN_MAX_NB ? 82u : 80u) && rows_at(nb, true).size() == 74u);
   }
   // (a) every accepted request has exactly one row; (b) its selector is canonical: with any one flag set or cleared it is another
   // kernel's or nobody's -- under equality that is (a) again, asserted all the same, once per selector and nb; (c) every row is
@@ -529,6 +568,9 @@ static void run_named_routes() {
       {"protect", SRC_GAUSS, B_PROTECT, MCP_COMPOUND_SIMPLE, 0, 1, 16, 0, false, "mc_paths_pi_kernel<NB, KT, 1, false, false>"},
       {"protect, GARCH, drawdown", SRC_GAUSS, B_PROTECT | B_GARCH | B_DD, MCP_COMPOUND_SIMPLE, 0, 1, 16, 0, false, "mc_paths_pi_kernel<NB, KT, 1, false, true>"},
       {"protect, jumps, horizons", SRC_GAUSS, B_PROTECT | B_JUMPS | B_HZ, MCP_COMPOUND_SIMPLE, 0, 1, 16, 0, false, "mc_paths_pi_kernel<NB, KT, 1, true, false>"},
+      {"vol target", SRC_GAUSS, B_VT, MCP_COMPOUND_SIMPLE, 0, 1, 16, 0, false, "mc_paths_vt_kernel<NB, KT, 1, false, false>"},
+      {"vol target, Student-t, GARCH, drawdown", SRC_T, B_VT | B_GARCH | B_DD, MCP_COMPOUND_SIMPLE, 0, 2, 16, 0, false, "mc_paths_vt_kernel<NB, KT, 1, false, true>"},
+      {"vol target, jumps, horizons", SRC_GAUSS, B_VT | B_JUMPS | B_HZ, MCP_COMPOUND_SIMPLE, 0, 1, 16, 0, false, "mc_paths_vt_kernel<NB, KT, 1, true, false>"},
   };
   for (const auto& c : named) {
     snprintf(g_case, sizeof g_case, "named route: %s", c.what);

@@ -386,6 +386,51 @@ int check_protect(const mcp_params* prm, const mcp_protect* pt) {
   if (!((float)prm->v0 > 0.0f)) return fail(MCP_E_ARG, "v0=%g rounds to zero in binary32", prm->v0);
   return MCP_OK;
 }
+// SPEC.md 4.19: the binary32 constants of a volatility-targeting request; oml = fl32(1 - (double)lam)
+VolTargetConsts vol_target_consts(const mcp_vol_target* vt) {
+  const float lam = (float)vt->decay;
+  return VolTargetConsts{(float)vt->target, lam, (float)(1.0 - (double)lam), (float)vt->cap, (float)vt->rate, (float)vt->spread};
+}
+// SPEC.md 4.19: the caller's s0_k, or fl32(sum_j (sum_i W[k,i] L[i,j])^2) in binary64 from the binary32 inputs, i and j ascending over
+// the lower triangle the walk reads, rounded once
+float vol_target_s0(int N, const mcp_vol_target* vt, const float* chol, const float* W, int k) {
+  if (vt->s0) return (float)vt->s0[k];
+  double q = 0.0;
+  for (int j = 0; j < N; j++) {
+    double v = 0.0;
+    for (int i = j; i < N; i++) v += (double)W[(size_t)k * N + i] * (double)chol[(size_t)i * N + j];
+    q += v * v;
+  }
+  return (float)q;
+}
+// SPEC.md 4.19: target > 0, decay in [0, 1], cap > 0, rate > -1, spread >= 0, each finite before and after rounding to binary32 and
+// inside its range after it; s0 finite and > 0 in binary32, given or formed; a finite target_value; reserved == 0; fl32(v0) > 0
+int check_vol_target(const mcp_params* prm, const mcp_vol_target* vt, const float* chol, const float* W) {
+  if (!vt) return fail(MCP_E_ARG, "vol_target is NULL");
+  if (vt->reserved != 0) return fail(MCP_E_ARG, "vol_target reserved=%d must be 0", vt->reserved);
+  const double v[5] = {vt->target, vt->decay, vt->cap, vt->rate, vt->spread};
+  for (int i = 0; i < 5; i++)
+    if (!std::isfinite(v[i]) || !std::isfinite((float)v[i]))
+      return fail(MCP_E_ARG, "vol_target target=%g, decay=%g, cap=%g, rate=%g, spread=%g must be finite, also in binary32", v[0], v[1], v[2], v[3],
+                  v[4]);
+  const VolTargetConsts c = vol_target_consts(vt);
+  if (!(vt->target > 0.0) || !(c.tgt > 0.0f)) return fail(MCP_E_ARG, "vol_target target=%g must be > 0 in binary32", vt->target);
+  if (!(vt->decay >= 0.0 && vt->decay <= 1.0) || !(c.lam >= 0.0f && c.lam <= 1.0f))
+    return fail(MCP_E_ARG, "vol_target decay=%g outside [0, 1]", vt->decay);
+  if (!(vt->cap > 0.0) || !(c.b > 0.0f)) return fail(MCP_E_ARG, "vol_target cap=%g must be > 0 in binary32", vt->cap);
+  if (!(vt->rate > -1.0) || !(c.rf > -1.0f)) return fail(MCP_E_ARG, "vol_target rate=%g must be > -1 in binary32", vt->rate);
+  if (!(vt->spread >= 0.0)) return fail(MCP_E_ARG, "vol_target spread=%g must be >= 0", vt->spread);
+  if (vt->target_value && (!std::isfinite(*vt->target_value) || !std::isfinite((float)*vt->target_value)))
+    return fail(MCP_E_ARG, "vol_target target_value=%g must be finite, also in binary32", *vt->target_value);
+  if (!((float)prm->v0 > 0.0f)) return fail(MCP_E_ARG, "v0=%g rounds to zero in binary32", prm->v0);
+  if (!vt->s0 && (!chol || !W)) return fail(MCP_E_ARG, "NULL pointer");
+  for (int k = 0; k < prm->n_portfolios; k++) {
+    const float s0 = vol_target_s0(prm->n_assets, vt, chol, W, k);
+    if ((vt->s0 && !(std::isfinite(vt->s0[k]) && vt->s0[k] > 0.0)) || !std::isfinite(s0) || !(s0 > 0.0f))
+      return fail(MCP_E_ARG, "vol_target s0, portfolio %d = %g must be finite and > 0 in binary32", k, vt->s0 ? vt->s0[k] : (double)s0);
+  }
+  return MCP_OK;
+}
 // SPEC.md 4.16: the binary32 constants of a spending request; w0 without `first` is fl32(p32 fl32(v0)), the product in binary64 (exact)
 SpendConsts spend_consts(const mcp_spending* sp, double v0) {
   const float p = (float)sp->rate;
@@ -666,6 +711,27 @@ int check_request(const mcp_params* prm, const Request& rq, uint64_t n_paths, co
                                      "glide paths, the overlay, the attribution or antithetic pairs");
     if (ln) return fail(MCP_E_UNSUPPORTED, "floor protection is not wired into mcp_launch_paths*");
   }
+  if (rq.vol_target) {                                         // SPEC.md 4.19: the rules, then what the volatility target is not combined with
+    if ((rc = check_vol_target(prm, rq.vt, rq.chol, rq.W))) return rc;
+    if (!rq.counts_out) return fail(MCP_E_ARG, "counts_out is NULL");
+    if ((rq.hz_counts_out == nullptr) != !rq.hz) return fail(MCP_E_ARG, "hz_counts_out must be NULL exactly when n_horizons == 0");
+    if (!rq.exposure_stats_out && rq.exposure_out) return fail(MCP_E_ARG, "exposure_out needs exposure_stats_out");
+    if (!rq.exposure_stats_out && !rq.dd) return fail(MCP_E_ARG, "exposure_stats_out is NULL (it may be only where dd_stats_out is not)");
+    if (rq.src == SRC_T && (rc = check_student_t(prm, rq.st))) return rc;
+    if (rq.garch && (rc = check_garch(prm, rq.gv))) return rc;
+    if (rq.jumps && (rc = check_jumps(prm->n_assets, rq.jp))) return rc;
+    if (prm->compounding != MCP_COMPOUND_SIMPLE) return fail(MCP_E_UNSUPPORTED, "volatility-targeted paths compound simply (no log compounding)");
+    if (prm->flags & (MCP_FLAG_FOLD | MCP_FLAG_NATIVE_MATH))
+      return fail(MCP_E_UNSUPPORTED, "volatility-targeted paths run on the unfolded recurrence and the spec's normals (no MCP_FLAG_FOLD / MCP_FLAG_NATIVE_MATH)");
+    if (rq.exposure_stats_out && rq.dd)
+      return fail(MCP_E_UNSUPPORTED, "a call leaves one second array: the exposure record is not combined with the drawdown");
+    if (rq.src == SRC_BOOT || rq.src == SRC_FHS || rq.regimes || rq.rebalanced || rq.cash || rq.glide || rq.protect || rq.spend || rq.life ||
+        rq.band || rq.overlay || rq.attr || rq.anti)
+      return fail(MCP_E_UNSUPPORTED, "a volatility target is not combined with bootstrap or filtered rows, regimes, rebalancing, cash flows, "
+                                     "glide paths, floor protection, spending rules, tolerance bands, the overlay, the attribution or "
+                                     "antithetic pairs");
+    if (ln) return fail(MCP_E_UNSUPPORTED, "volatility targeting is not wired into mcp_launch_paths*");
+  }
   if (rq.overlay && (rc = check_overlay(prm, rq.ov))) return rc;
   if (rq.garch && (rc = check_garch(prm, rq.gv))) return rc;
   if (rq.jumps && (rc = check_jumps(prm->n_assets, rq.jp))) return rc;
@@ -826,6 +892,11 @@ mcp::PathKernel route_kernel(const mcp_params* prm, const Request& rq, bool attr
   if (rq.protect) {                       // SPEC.md 4.15: one segmented kernel serves terminal-only and horizon calls, on the GARCH or the jump walk
     k.family = rq.dd ? FAM_DD : FAM_HZ;
     k.flags |= PK_PI;
+    if (!rq.jumps) k.flags = share_garch_walk(k.flags);
+  }
+  if (rq.vol_target) {                    // SPEC.md 4.19: the protection's two walks and families, with the targeting rule
+    k.family = rq.dd ? FAM_DD : FAM_HZ;
+    k.flags |= PK_VT;
     if (!rq.jumps) k.flags = share_garch_walk(k.flags);
   }
   if (rq.band) k.flags |= PK_TB;          // SPEC.md 4.18: B is per portfolio, so every portfolio of a banded call is a pass of its own
@@ -1008,16 +1079,43 @@ void protect_pivots(const mcp_params& prm, const mcp_protect* pt, const float* m
   }
 }
 
+// SPEC.md 5.19: c_k(h) = g_k^h - 1, g_k = 1 + rf + e_k (mu_k - rf) - sp max(e_k - 1, 0), e_k = min(tgt / sqrt(s0_k), b), mu_k = sum_i W_ki mu_i
+// (i ascending), binary64 from the binary32 constants; where g_k <= 0 or the result is not finite, the pivot of the plain call at h
+// steps (mcp_pivots).  The portfolios [k0, k0 + K) of the call's W; h = T into out_T[k], the H horizons into out_hz[h*K + k].
+void vol_target_pivots(const mcp_params& prm, const mcp_vol_target* vt, const float* mu, const float* chol, const float* W, int k0, int K,
+                       int H, const int32_t* steps, double* out_T, double* out_hz) {
+  const VolTargetConsts vc = vol_target_consts(vt);
+  const double rf = (double)vc.rf, sp = (double)vc.sp;
+  const int N = prm.n_assets;
+  for (int k = 0; k < K; k++) {
+    double mk = 0.0;
+    for (int i = 0; i < N; i++) mk += (double)W[(size_t)(k0 + k) * N + i] * (double)mu[i];
+    const double e = std::fmin((double)vc.tgt / std::sqrt((double)vol_target_s0(N, vt, chol, W, k0 + k)), (double)vc.b);
+    const double g = 1.0 + rf + e * (mk - rf) - sp * std::fmax(e - 1.0, 0.0);
+    for (int h = -1; h < H; h++) {
+      const int st = h < 0 ? prm.n_steps : steps[h];
+      double c = std::pow(g, (double)st) - 1.0;
+      if (!(g > 0.0) || !std::isfinite(c)) {
+        c = mk > -1.0 ? std::expm1((double)st * std::log1p(mk)) : 0.0;
+        if (!std::isfinite(c)) c = 0.0;
+      }
+      (h < 0 ? out_T[k] : out_hz[(size_t)h * K + k]) = c;
+    }
+  }
+}
+
 // What follows the packed block of a tile of kt portfolios.  Jumps: the [N4] loadings; regimes: [mu1][L1 row pairs]; glide path: the
 // target blocks of the tile's portfolios; bands: the tolerance table and the masks (check_request lets at most one of the four through).  Protection: behind them the floor
-// schedule and the counts' thresholds (protect_pack).
+// schedule and the counts' thresholds (protect_pack), or, volatility target, s0 of the tile's portfolios padded with ones to whole
+// passes of 8.
 TileLayout tile_layout(const mcp_params* prm, const Request& rq, int kt) {
   const int N = prm->n_assets;
   TileLayout t;
   t.base = t.load = mcp_packed_len(N, kt);
   t.floor = t.load + (rq.jumps ? (size_t)n4_of(N) : rq.regimes ? regime_block_len(N) : rq.glide ? glide_len(N, kt, rq.gl)
                        : rq.band ? band_len(N, kt) : 0);
-  t.total = t.floor + (rq.protect ? protect_len(prm->n_steps, kt, rq.hz ? rq.H : 0) : 0);
+  t.total = t.floor + (rq.protect ? protect_len(prm->n_steps, kt, rq.hz ? rq.H : 0)
+                       : rq.vol_target ? (size_t)KT_WIDE * (size_t)((kt + KT_WIDE - 1) / KT_WIDE) : 0);
   return t;
 }
 
@@ -1054,6 +1152,8 @@ int pack_tile(const mcp_params* prm, const Request& rq, const TileInputs& in, in
   if (rq.glide) glide_pack(N, prm->n_portfolios, k0, kt, rq.gl, load);
   if (rq.band) band_pack(N, k0, kt, rq.bd, load);
   if (rq.protect) protect_pack(prm->n_steps, kt, H, rq.steps, rq.pi, out + lay.floor);
+  for (size_t k = 0; rq.vol_target && k < lay.total - lay.floor; k++)
+    out[lay.floor + k] = k < (size_t)kt ? vol_target_s0(N, rq.vt, rq.chol, rq.W, k0 + (int)k) : 1.0f;
   return MCP_OK;
 }
 
@@ -1063,7 +1163,9 @@ int request_pivots(const mcp_params* prm, const Request& rq, const TileInputs& i
   const float* Wt = rq.W + (size_t)k0 * N;
   const mcp_bootstrap* boot = rq.src == SRC_BOOT ? rq.boot : nullptr;
   const double v0 = (double)(float)prm->v0;
-  if (rq.protect) {                                            // SPEC.md 5.15: every pivot in closed form
+  if (rq.vol_target) {                                         // SPEC.md 5.19: every pivot in closed form
+    vol_target_pivots(*prm, rq.vt, rq.mu, rq.chol, rq.W, k0, kt, H, rq.steps, out_T, out_hz);
+  } else if (rq.protect) {                                     // SPEC.md 5.15: every pivot in closed form
     protect_pivots(*prm, rq.pi, rq.mu, Wt, kt, H, rq.steps, out_T, out_hz);
   } else if (rq.spend) {                                       // SPEC.md 5.16: the rule on the mean path gives T and every horizon
     std::vector<double> cm((size_t)kt);
@@ -1118,6 +1220,7 @@ Second second_of(const Request& rq) {
   if (rq.dd) return {true, true, false, rq.mdd_out, rq.dd_stats_out};
   if (rq.band) return {true, true, false, rq.turnover_out, rq.turnover_stats_out};
   if (rq.spend) return {true, false, true, rq.wd_out, rq.wd_stats_out};
+  if (rq.vol_target) return {true, true, false, rq.exposure_out, rq.exposure_stats_out};   // SPEC.md 5.19: x = Y - 1, without the drawdown only
   return {false, false, false, nullptr, nullptr};
 }
 
@@ -1458,6 +1561,30 @@ int mcp_protect_pivots(const mcp_params* prm, const mcp_protect* pt, const float
     if (!hz_pivots_out) return fail(MCP_E_ARG, "hz_pivots_out is NULL");
   }
   protect_pivots(*prm, pt, mu, W, prm->n_portfolios, n_horizons, horizons, pivots_out, hz_pivots_out);
+  return MCP_OK;
+}
+
+int mcp_vol_target_pivots(const mcp_params* prm, const mcp_vol_target* vt, const float* mu, const float* chol, const float* W, int n_horizons,
+                          const int32_t* horizons, double* pivots_out, double* hz_pivots_out) {
+  if (int rc = check_params(prm)) return rc;
+  if (!mu || !chol || !W || !pivots_out) return fail(MCP_E_ARG, "NULL pointer");
+  if (int rc = check_vol_target(prm, vt, chol, W)) return rc;
+  if (prm->compounding != MCP_COMPOUND_SIMPLE) return fail(MCP_E_UNSUPPORTED, "volatility-targeted paths compound simply (no log compounding)");
+  if (n_horizons != 0) {
+    if (int rc = check_horizons(prm->n_steps, n_horizons, horizons)) return rc;
+    if (!hz_pivots_out) return fail(MCP_E_ARG, "hz_pivots_out is NULL");
+  }
+  vol_target_pivots(*prm, vt, mu, chol, W, 0, prm->n_portfolios, n_horizons, horizons, pivots_out, hz_pivots_out);
+  return MCP_OK;
+}
+
+int mcp_vol_target_consts(const mcp_params* prm, const mcp_vol_target* vt, const float* chol, const float* W, float* out) {
+  if (int rc = check_params(prm)) return rc;
+  if (int rc = check_vol_target(prm, vt, chol, W)) return rc;
+  if (!out) return fail(MCP_E_ARG, "out is NULL");
+  const VolTargetConsts c = vol_target_consts(vt);
+  out[0] = c.tgt; out[1] = c.lam; out[2] = c.oml; out[3] = c.b; out[4] = c.rf; out[5] = c.sp;
+  for (int k = 0; k < prm->n_portfolios; k++) out[6 + k] = vol_target_s0(prm->n_assets, vt, chol, W, k);
   return MCP_OK;
 }
 

@@ -13,6 +13,7 @@
 #include "../../include/mcport_spend.h"
 #include "../../include/mcport_life.h"
 #include "../../include/mcport_band.h"
+#include "../../include/mcport_voltarget.h"
 #include "mcp_route.h"
 
 namespace mcp {
@@ -60,6 +61,8 @@ struct Request {
   bool life = false;                    // SPEC.md 4.17: the lifetime l of every path, always with `cash` (mcp_simulate_lifetime)
   bool band = false;                    // SPEC.md 4.18: the tolerance bands `bd`, always with `rebalanced` on a rule `reb` of the same
   const mcp_band* bd = nullptr;         // period and cost (mcp_simulate_banded)
+  bool vol_target = false;              // SPEC.md 4.19: the targeting rule `vt` (mcp_simulate_vol_target)
+  const mcp_vol_target* vt = nullptr;
   bool overlay = false;                 // SPEC.md 4.8: the option rows `ov`
   const mcp_overlay* ov = nullptr;
   bool garch = false;                   // SPEC.md 4.9: the variance recurrence `gv` (SRC_GAUSS or SRC_T)
@@ -81,10 +84,12 @@ struct Request {
   float* hz_out = nullptr;              // [H*K*n], row h*K + k
   mcp_stats* hz_stats_out = nullptr;    // [H*K]
   double* bands_out = nullptr;          // [H*K*L]
-  uint64_t* counts_out = nullptr;       // cash flows: [K][2] {n_ruined, n_short} (SPEC.md 5.6); protection: {n_gap, n_short} (5.15)
+  uint64_t* counts_out = nullptr;       // cash flows, volatility target: [K][2] {n_ruined, n_short} (SPEC.md 5.6 / 5.19); protection: {n_gap, n_short} (5.15)
   uint64_t* hz_counts_out = nullptr;    // [H*K][2]
   float* wd_out = nullptr;              // spending rule: NULL or host [K*n] Y_T (SPEC.md 4.16)
   mcp_stats* wd_stats_out = nullptr;    // [K]
+  float* exposure_out = nullptr;        // volatility target without the drawdown: NULL or host [K*n] Y_T (SPEC.md 4.19)
+  mcp_stats* exposure_stats_out = nullptr;   // [K]
   uint32_t* life_out = nullptr;         // lifetime: NULL or host [K*n] l (SPEC.md 4.17)
   uint64_t* life_hist_out = nullptr;    // [K][n_steps + 1] (SPEC.md 5.17)
   uint32_t* trades_out = nullptr;       // bands: NULL or host [K*n] c (SPEC.md 4.18)
@@ -117,7 +122,7 @@ struct Launch {
   uint64_t stride = 0;
   float* d_mdd = nullptr;               // drawdown: [K][mdd_stride]
   uint64_t mdd_stride = 0;
-  float* d_wd = nullptr;                // spending rule: [K][wd_stride] Y_T
+  float* d_wd = nullptr;                // spending rule: [K][wd_stride] Y_T; volatility target: the summed exposure Y_T
   uint64_t wd_stride = 0;
   uint32_t* d_life = nullptr;           // lifetime: [K][life_stride] l
   uint64_t life_stride = 0;
@@ -126,6 +131,7 @@ struct Launch {
   const float* d_rows = nullptr;        // bootstrap: [R][N4], zero-padded
   const float* d_flows = nullptr;       // cash flows: [n_steps]
   const float* d_floor = nullptr;       // protection: [n_steps + 1] the floor schedule
+  const float* d_s0 = nullptr;          // volatility target: [8 ceil(K/8)] the initial variance estimates
   const float* d_band = nullptr;        // bands: [K][N4] tolerances, then [K][2] mask words (band_pack); c goes to d_life, Y to d_wd
   const float* d_targets = nullptr;     // glide path: [n_breaks][glide_rows(K)][N4] target blocks (glide_pack)
   const char* d_overlay = nullptr;      // overlay: [rows][row_begin N4 + 1][spot N4] (overlay_pack)
@@ -159,6 +165,8 @@ int check_protect(const mcp_params* prm, const mcp_protect* pt);
 int check_spending(double v0, const mcp_spending* sp);
 int check_overlay(const mcp_params* prm, const mcp_overlay* ov);
 int check_band(const mcp_params* prm, const mcp_band* bd);
+// `chol`, `W`: what the default s0_k is formed from (read only when vt->s0 is NULL)
+int check_vol_target(const mcp_params* prm, const mcp_vol_target* vt, const float* chol, const float* W);
 // Every rule a request meets: each feature's own arguments, then which features combine (MCP_E_UNSUPPORTED), then the outputs.
 // `ln`: an mcp_launch_paths* call, whose device arrays are checked instead of the host arrays of an mcp_simulate* call.
 int check_request(const mcp_params* prm, const Request& rq, uint64_t n_paths, const Launch* ln = nullptr, uint64_t path_begin = 0);
@@ -181,6 +189,10 @@ RegimeConsts regime_consts(const mcp_regimes* r);
 struct ProtectConsts { float m, b, rf, theta; };
 ProtectConsts protect_consts(const mcp_protect* pt);
 struct SpendConsts { float p, g, lo, hi, w0; };
+struct VolTargetConsts { float tgt, lam, oml, b, rf, sp; };
+VolTargetConsts vol_target_consts(const mcp_vol_target* vt);
+// SPEC.md 4.19: s0_k of portfolio k of W -- the caller's, or fl32(sum_j (sum_i W[k,i] L[i,j])^2)
+float vol_target_s0(int N, const mcp_vol_target* vt, const float* chol, const float* W, int k);
 SpendConsts spend_consts(const mcp_spending* sp, double v0);
 
 // ---- the closed-form pivots and their means ----
@@ -199,6 +211,8 @@ void glide_pivots(int K, int T, int G, const int32_t* breaks, const double* m, c
                   double* out_T, double* out_hz);
 void protect_pivots(const mcp_params& prm, const mcp_protect* pt, const float* mu, const float* W, int K, int H, const int32_t* steps,
                     double* out_T, double* out_hz);
+void vol_target_pivots(const mcp_params& prm, const mcp_vol_target* vt, const float* mu, const float* chol, const float* W, int k0, int K,
+                       int H, const int32_t* steps, double* out_T, double* out_hz);
 void spend_pivots(int K, int T, const double* m, const SpendConsts& c, int every, double v0, int H, const int32_t* steps, double* out_T,
                   double* out_hz, double* out_wd);
 
@@ -226,7 +240,7 @@ void overlay_pack(int N, const mcp_overlay* ov, char* out);
 struct TileLayout {
   size_t base;     // mcp_packed_len(N, kt): the end of the packed block
   size_t load;     // where the jump loadings, the regime-1 block, the glide targets or the tolerance table begin
-  size_t floor;    // where the protection schedule and the counts' thresholds begin (protect_pack)
+  size_t floor;    // where the protection schedule and the counts' thresholds begin (protect_pack), or the volatility target's s0
   size_t total;    // floats of the whole block
 };
 TileLayout tile_layout(const mcp_params* prm, const Request& rq, int kt);
@@ -247,11 +261,12 @@ int request_pivots(const mcp_params* prm, const Request& rq, const TileInputs& i
 void request_wd_pivots(const mcp_params* prm, const Request& rq, int k0, int kt, double* out_wd);
 
 // ---- what a request leaves per path besides V_T and the horizon rows ----
-// The one second float array: the drawdown q / d (SPEC.md 5.1), the turnover Y of the bands (5.18) or the total paid out Y_T of a
-// spending rule (5.16); check_request lets at most one of the three through.  It is reduced as the terminal values are, at rf = 0.
+// The one second float array: the drawdown q / d (SPEC.md 5.1), the turnover Y of the bands (5.18), the total paid out Y_T of a
+// spending rule (5.16) or, in a call without the drawdown, the summed exposure Y_T of a volatility target (5.19); check_request lets
+// at most one of them through.  It is reduced as the terminal values are, at rf = 0.
 struct Second {
   bool on;                // the request has one
-  bool unit_v0;           // its select runs at v0 = 1: x = q - 1, expm1(d) or Y - 1; the total paid out keeps v0: x = Y / fl32(v0) - 1
+  bool unit_v0;           // its select runs at v0 = 1: x = q - 1, expm1(d) or Y - 1 (turnover, summed exposure); the total paid out keeps v0: x = Y / fl32(v0) - 1
   bool pivoted;           // its select takes the pivots of request_wd_pivots (spending only); the other two take none
   float* out;             // the caller's [K*n] array, or NULL
   mcp_stats* stats_out;   // the caller's [K] records

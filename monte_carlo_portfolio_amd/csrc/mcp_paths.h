@@ -114,7 +114,7 @@ __device__ __forceinline__ const __attribute__((address_space(4))) A* kernarg() 
 MCP_HAS_MEMBER(hz) MCP_HAS_MEMBER(mdd) MCP_HAS_MEMBER(bt) MCP_HAS_MEMBER(st) MCP_HAS_MEMBER(gv) MCP_HAS_MEMBER(cf)
 MCP_HAS_MEMBER(ov) MCP_HAS_MEMBER(at) MCP_HAS_MEMBER(period) MCP_HAS_MEMBER(pr)
 MCP_HAS_MEMBER(fh) MCP_HAS_MEMBER(p_hi) MCP_HAS_MEMBER(jp) MCP_HAS_MEMBER(rs) MCP_HAS_MEMBER(gp)
-MCP_HAS_MEMBER(pi) MCP_HAS_MEMBER(sp) MCP_HAS_MEMBER(lf) MCP_HAS_MEMBER(tb)
+MCP_HAS_MEMBER(pi) MCP_HAS_MEMBER(sp) MCP_HAS_MEMBER(lf) MCP_HAS_MEMBER(tb) MCP_HAS_MEMBER(vt)
 #undef MCP_HAS_MEMBER
 
 struct PathArgs {
@@ -447,6 +447,28 @@ __device__ __forceinline__ cprotect_p protect_args(const A&) {
   else return nullptr;
 }
 
+// Volatility targeting (SPEC.md 4.19): per path and portfolio the walk carries V, the EWMA variance estimate s (from s0_k) and, without the
+// drawdown, the summed exposure Y (from +0); step t holds E = fl32(e V), e = fminf(tgt / sqrtf(s), b), in the risky portfolio, V - E at the
+// rate rf, pays sp on what it borrows, and ruin is absorbing as in SPEC.md 4.7.  `s0` sits behind the launch's packed block, one value per
+// portfolio, padded to whole passes of 8.  The constants are wave-uniform and read inside the step, s0 once per tile, the output where it
+// is written.
+struct VolTargetArgs {
+  float tgt, lam, oml, b, rf, sp;     // binary32: target, decay, fl32(1 - lam), cap > 0, rate > -1, spread >= 0
+  const float* __restrict__ s0;       // [Kpad] device copy
+  float* __restrict__ exposure;       // [K][exposure_stride] Y_T (written only without DD)
+  uint64_t exposure_stride;
+};
+// Arguments of mc_paths_vt_kernel: those of mc_paths_pi_kernel with the targeting rule in place of the protection rule.
+struct PathArgsVG : PathArgsPI { StudentArgs st; GarchArgs gv; VolTargetArgs vt; };
+struct PathArgsVJ : PathArgsPI { JumpArgs jp; VolTargetArgs vt; };
+// The targeting block of a vt kernel's launch, read where it is used (kernarg).
+typedef const __attribute__((address_space(4))) VolTargetArgs* cvoltarget_p;
+template <class A>
+__device__ __forceinline__ cvoltarget_p vol_target_args(const A&) {
+  if constexpr (has_vt<A>::value) return &kernarg<A>()->vt;
+  else return nullptr;
+}
+
 // The option overlay of SPEC.md 4.8: per asset a run of rows (kind, strike, premium, qty) that turns the raw return r_i of a step
 // into the strategy's return r'_i at the asset's price level P_i.  rows, row_begin [N4 + 1] (assets >= N own no rows) and spot [N4]
 // are device copies; bit i of `mask` is set when asset i owns rows.
@@ -513,6 +535,7 @@ struct PathLaunchArgs {
   SpendArgs sp;
   LifeArgs lf;
   BandArgs tb;
+  VolTargetArgs vt;
 };
 template <class A>
 inline A make_args(const PathLaunchArgs& s) {
@@ -536,6 +559,7 @@ inline A make_args(const PathLaunchArgs& s) {
   if constexpr (has_sp<A>::value) x.sp = s.sp;
   if constexpr (has_lf<A>::value) x.lf = s.lf;
   if constexpr (has_tb<A>::value) x.tb = s.tb;
+  if constexpr (has_vt<A>::value) x.vt = s.vt;
   if constexpr (has_p_hi<A>::value) { x.p_hi = (uint32_t)(s.hz.path_begin >> 32); x.pad = 0u; }
   return x;
 }
@@ -640,14 +664,16 @@ constexpr int PATH_BLOCK = 256;
 // walk merges its breaks (SPEC.md 4.16).  LT (with CF): the step also counts, on the mask it already forms, the steps that stored a
 // positive V -- the lifetime l of SPEC.md 4.17 -- and l is stored next to V_T.  TB (with REB, one portfolio): a rebalance date is a
 // review, at which only the lanes with a watched asset out of its band trade; the walk also carries the trade count c and the turnover
-// Y and stores them next to V_T (SPEC.md 4.18).  Every kernel
+// Y and stores them next to V_T (SPEC.md 4.18).  VT (with HZ): the walk also carries the variance estimate s and, without DD, the summed
+// exposure Y; the update of V holds the exposure e = fminf(tgt / sqrtf(s), b) in the risky portfolio, the rest at the riskless rate, what
+// is borrowed at the spread on top, ruin absorbing; s then moves on the step's rho (SPEC.md 4.19).  Every kernel
 // below is the body in mcp_paths_body.inc under its own flags F: it names the flags it sets, the rest are PathFlagsOff's.  F is a
 // local class, which may not have static data members, so it sets its flags as enumerators of an `enum : bool`; they hide the
 // defaults' names and read as the same constant expressions.
 struct PathFlagsOff {
   static constexpr bool NATIVE = false, FOLD = false, LOGC = false, DD = false, HZ = false, BOOT = false, BLDS = false, REB = false,
                         STT = false, CF = false, OV = false, GV = false, AT = false, ANTI = false, FH = false, UHI = false, JP = false, RS = false,
-                        GP = false, PI = false, SP = false, LT = false, TB = false;
+                        GP = false, PI = false, SP = false, LT = false, TB = false, VT = false;
 };
 
 // __launch_bounds__ 2nd argument of a path kernel: the MCP_MIN_WAVES* above for N <= 16 and one path per lane, by the kind of
@@ -867,6 +893,17 @@ __global__ void MCP_BOUNDS(BK_SP) mc_paths_spend_life_kernel(const PathArgsSPL a
 template <int NB, int KT, int PPT, bool JP_, bool DD_>
 __global__ void MCP_BOUNDS(JP_ ? BK_PI : BK_PATHS) mc_paths_pi_kernel(const std::conditional_t<JP_, PathArgsPJ, PathArgsPG> a) {
   struct F : PathFlagsOff { enum : bool { HZ = true, PI = true, DD = DD_, STT = !JP_, GV = !JP_, JP = JP_ }; };
+#include "mcp_paths_body.inc"
+}
+
+// The volatility-targeting kernel (SPEC.md 4.19; simple compounding, unfolded recurrence): mc_paths_pi_kernel's walks -- the segmented
+// GARCH walk (JP_ = false: Gaussian, Student-t and GARCH requests) or jump walk (JP_ = true), H = 0 one segment, DD the drawdown state,
+// which sees the targeted V -- with the targeting rule in the update of V.  Per portfolio of the pass one IEEE square root and one IEEE
+// division per step.  V_T, the horizons, the drawdown and the fused epilogue as in those kernels; without DD the summed exposure Y is
+// stored next to V_T and reduced by the non-fused passes.  It takes the protection kernel's launch bounds (profiles/voltarget_isa.txt).
+template <int NB, int KT, int PPT, bool JP_, bool DD_>
+__global__ void MCP_BOUNDS(JP_ ? BK_PI : BK_PATHS) mc_paths_vt_kernel(const std::conditional_t<JP_, PathArgsVJ, PathArgsVG> a) {
+  struct F : PathFlagsOff { enum : bool { HZ = true, VT = true, DD = DD_, STT = !JP_, GV = !JP_, JP = JP_ }; };
 #include "mcp_paths_body.inc"
 }
 

@@ -5,7 +5,7 @@
 // derived from it) and the kernel argument `a` (PathArgs or a struct that starts with one).
   constexpr bool NATIVE = F::NATIVE, FOLD = F::FOLD, LOGC = F::LOGC, DD = F::DD, HZ = F::HZ, BOOT = F::BOOT, BLDS = F::BLDS, REB = F::REB,
                  STT = F::STT, CF = F::CF, OV = F::OV, GV = F::GV, AT = F::AT, ANTI = F::ANTI, FH = F::FH, UHI = F::UHI, JP = F::JP, RS = F::RS,
-                 GP = F::GP, PI = F::PI, SP = F::SP, LT = F::LT, TB = F::TB;
+                 GP = F::GP, PI = F::PI, SP = F::SP, LT = F::LT, TB = F::TB, VT = F::VT;
   static_assert(!UHI || (KT == 1 && PPT == 1 && !(NATIVE || FOLD || DD || HZ || BOOT || REB || STT || CF || OV || GV || AT || ANTI || FH || JP || RS || PI)),
                 "uniform high counter word: the plain Gaussian walk of one portfolio only");
   static_assert(!FH || (BOOT && HZ && !(LOGC || REB || CF || STT || GV || OV || AT || DD || PI)), "filtered rows: the bootstrap's segmented walk only");
@@ -21,6 +21,8 @@
                 "spending rule: the cash-flow kernel's segmented walk only");
   static_assert(!LT || (CF && (GP || SP)), "lifetime: the glide and spending kernels' walks only");
   static_assert(!TB || (REB && KT == 1), "tolerance bands: the rebalancing kernel's walk, one portfolio per pass");
+  static_assert(!VT || (HZ && (JP || (STT && GV)) && !(NATIVE || FOLD || LOGC || BOOT || REB || CF || OV || AT || ANTI || FH || UHI || RS || GP || PI || SP || LT || TB)),
+                "volatility targeting: the segmented GARCH or jump walk, simple compounding only");
   constexpr int N4 = 4 * NB;
   // ANTI (SPEC.md 2.3): a lane's PPT draws feed EM = 2 PPT members -- slot e < PPT walks on z[e], slot PPT + e on -z[e]; p, live and
   // the counters are per draw (a.path_begin and a.n_paths count pairs), the members 2 p and 2 p + 1 are adjacent in the output rows
@@ -150,6 +152,7 @@
     uint32_t Lk[PPT][KT];                                 // LT: the steps that stored a positive V, the lifetime l of SPEC.md 4.17
     uint32_t Tc[PPT];                                     // TB: the trade count c of SPEC.md 4.18
     float Ty[PPT];                                        // TB: the turnover Y of SPEC.md 4.18
+    float Sg[PPT][KT];                                    // VT: the variance estimate s of SPEC.md 4.19; the summed exposure is Yk (!DD only)
 #pragma unroll
     for (int e = 0; e < PPT; e++) {
       p[e] = tl * tile + (uint64_t)e * PATH_BLOCK + threadIdx.x;
@@ -170,6 +173,14 @@
       if constexpr (LT) {
 #pragma unroll
         for (int k = 0; k < KT; k++) Lk[e][k] = 0u;
+      }
+      if constexpr (VT) {                                 // s0_k of the pass's portfolios, scalar loads once per tile
+        const cfloat_p s0 = (cfloat_p)vol_target_args(a)->s0 + a.k_begin;
+#pragma unroll
+        for (int k = 0; k < KT; k++) {
+          Sg[e][k] = s0[k];
+          if constexpr (!DD) Yk[e][k] = 0.0f;
+        }
       }
       if constexpr (BOOT) jrow[e] = 0u;                   // replaced at t = 0 (a restart)
       if constexpr (GV) gh[e] = garch_args(a)->h0;        // one scalar load per tile
@@ -526,6 +537,16 @@
 #pragma unroll
           for (int k = 0; k < KT; k++)
             if (k < kt) dk->mdd[(size_t)(a.k_begin + k) * dk->mdd_stride + p[e]] = Qk[e][k];
+        } else if constexpr (DD && VT) {                   // the drawdown output of the targeting kernel's arguments
+          const auto dk = kernarg<PathArgsPI>();
+#pragma unroll
+          for (int k = 0; k < KT; k++)
+            if (k < kt) dk->mdd[(size_t)(a.k_begin + k) * dk->mdd_stride + p[e]] = Qk[e][k];
+        } else if constexpr (VT) {                         // Y_T of SPEC.md 4.19, next to V_T
+          const cvoltarget_p vk = vol_target_args(a);
+#pragma unroll
+          for (int k = 0; k < KT; k++)
+            if (k < kt) vk->exposure[(size_t)(a.k_begin + k) * vk->exposure_stride + p[e]] = Yk[e][k];
         } else if constexpr (SP) {                         // Y_T of SPEC.md 4.16, next to V_T
           const cspend_p sk = spend_args(a);
 #pragma unroll

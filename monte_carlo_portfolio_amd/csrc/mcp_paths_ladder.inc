@@ -39,9 +39,11 @@ MCP_ROW(FAM_DD, PK_ANTI | PK_LOGC, mc_paths_anti_kernel<NB, KT, 1, true, PathArg
 MCP_ROW(FAM_DD, PK_ANTI | PK_GV, mc_paths_anti_kernel<NB, KT, 1, false, PathArgsGADD>)
 MCP_ROW(FAM_DD, PK_PI | PK_GV, mc_paths_pi_kernel<NB, KT, 1, false, true>)
 MCP_ROW(FAM_DD, PK_PI | PK_JP, mc_paths_pi_kernel<NB, KT, 1, true, true>)
+MCP_ROW(FAM_DD, PK_VT | PK_GV, mc_paths_vt_kernel<NB, KT, 1, false, true>)
+MCP_ROW(FAM_DD, PK_VT | PK_JP, mc_paths_vt_kernel<NB, KT, 1, true, true>)
 
-// The walk in segments between horizons.  The filtered rows and the protection without a drawdown run here with or without
-// horizons (H = 0: one segment).
+// The walk in segments between horizons.  The filtered rows, and the protection and the volatility target without a drawdown, run
+// here with or without horizons (H = 0: one segment).
 MCP_ROW(FAM_HZ, 0, mc_paths_hz_kernel<NB, KT, 1, false>)
 MCP_ROW(FAM_HZ, PK_LOGC, mc_paths_hz_kernel<NB, KT, 1, true>)
 MCP_ROW(FAM_HZ, PK_STT, mc_paths_t_hz_kernel<NB, KT, 1>)
@@ -59,6 +61,8 @@ MCP_ROW(FAM_HZ, PK_ANTI | PK_LOGC, mc_paths_anti_kernel<NB, KT, 1, true, PathArg
 MCP_ROW(FAM_HZ, PK_ANTI | PK_GV, mc_paths_anti_kernel<NB, KT, 1, false, PathArgsGAHZ>)
 MCP_ROW(FAM_HZ, PK_PI | PK_GV, mc_paths_pi_kernel<NB, KT, 1, false, false>)
 MCP_ROW(FAM_HZ, PK_PI | PK_JP, mc_paths_pi_kernel<NB, KT, 1, true, false>)
+MCP_ROW(FAM_HZ, PK_VT | PK_GV, mc_paths_vt_kernel<NB, KT, 1, false, false>)
+MCP_ROW(FAM_HZ, PK_VT | PK_JP, mc_paths_vt_kernel<NB, KT, 1, true, false>)
 
 // Rebalancing on a period; within tolerance bands (SPEC.md 4.18) every portfolio is a pass of its own
 MCP_ROW(FAM_REB, 0, mc_paths_reb_kernel<NB, KT, 1, false, false>)

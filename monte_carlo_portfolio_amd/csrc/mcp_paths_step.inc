@@ -20,7 +20,8 @@
 // priority raised over the factor (MCP_EXP_GEMV2, MCP_EXP_PRIO).  PI: the update of V is the floor rule of SPEC.md
 // 4.15 on the step's rho, then the peak M.  SP (with CF): the flow is the path's own -w, and the step adds what it pays out to Y
 // (SPEC.md 4.16); the reviews of w are events of the walk, not of the step.  LT (with CF): the mask that selects the step's V also
-// adds one to the lifetime l (SPEC.md 4.17).
+// adds one to the lifetime l (SPEC.md 4.17).  VT: the update of V is the targeting rule of SPEC.md 4.19 on the step's rho, then the
+// variance estimate s moves on rho.
       float rho[EM][KT];
       float fsh[PPT];                                  // FH: the shock s_j of the step's row (SPEC.md 2.4)
       if constexpr (BOOT) {
@@ -420,6 +421,28 @@
             const float u = fma32(V[e][k] - ex, p_rf, V[e][k]);
             V[e][k] = fma32(ex, rho[e][k], u);
             Mk[e][k] = fmaxf(Mk[e][k], V[e][k]);
+          }
+      } else if constexpr (VT) {
+        // SPEC.md 4.19: e = fminf(tgt / sqrtf(s), b), E = fl32(e V), u = fma(V - E, rf, V), U = fma(E, rho, u), D = fmaxf(E - V, +0),
+        // U = fma(D, -sp, U), V = (V > 0 and U > 0) ? U : +0, Y = Y + e, s = fminf(fma(oml, fl32(rho rho), fl32(lam s)), 2^40).  The
+        // square root and the division are IEEE, correctly rounded, one of each per path and portfolio; fminf / fmaxf are IEEE
+        // minNum / maxNum (a NaN estimate becomes 2^40).  The constants are wave-uniform scalar loads inside the step.
+        __builtin_amdgcn_sched_barrier(0);             // as the PI arm: the rule's scalar loads stay behind the weight dot
+        const cvoltarget_p vk = vol_target_args(a);
+        const float v_tgt = vk->tgt, v_lam = vk->lam, v_oml = vk->oml, v_b = vk->b, v_rf = vk->rf, v_sp = vk->sp;
+#pragma unroll
+        for (int e = 0; e < PPT; e++)
+#pragma unroll
+          for (int k = 0; k < KT; k++) {
+            const float ee = fminf(v_tgt / sqrtf(Sg[e][k]), v_b);
+            const float ex = ee * V[e][k];
+            const float u = fma32(V[e][k] - ex, v_rf, V[e][k]);
+            float uu = fma32(ex, rho[e][k], u);
+            const float bor = fmaxf(ex - V[e][k], 0.0f);
+            uu = fma32(bor, -v_sp, uu);
+            V[e][k] = (V[e][k] > 0.0f && uu > 0.0f) ? uu : 0.0f;
+            if constexpr (!DD) Yk[e][k] = Yk[e][k] + ee;
+            Sg[e][k] = fminf(fma32(v_oml, rho[e][k] * rho[e][k], v_lam * Sg[e][k]), 0x1p40f);
           }
       } else if constexpr (!REB) {
 #pragma unroll

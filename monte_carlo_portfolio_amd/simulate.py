@@ -60,10 +60,15 @@ _LIFE_CHOICE = ("mcp_simulate_lifetime", "lifetime is not combined with protect,
 # row of _ENTRY_CHOICE: tests/test_spend_cpu.py pins that row.)
 _BAND_CHOICE = ("mcp_simulate_banded", "tolerance is not combined with drawdown, cashflow, glide, protect, spending, overlay, dof, garch, "
                                        "jumps, regimes, filtered rows, attribution or antithetic")
+# Volatility targeting (SPEC.md 4.19) is a rule in the update of V on the Gaussian, Student-t, GARCH and jump walks: with `vol_target` the
+# call takes this entry point, whatever the table above would choose, and a keyword that entry point has no argument group for is
+# refused with this sentence.
+_VOLTARGET_CHOICE = ("mcp_simulate_vol_target", "vol_target is not combined with overlay, cashflow, rebalance, bootstrap or filtered rows, "
+                                                "regimes, glide, protect, spending, lifetime, tolerance, attribution or antithetic")
 # the argument group of _ffi.SIMULATE_ENTRIES that carries each feature keyword of Context._call
 _KEYWORD_GROUP = {"rows": "bt", "dof": "st", "period": "rb", "drawdown": "dd", "horizons": "hz_in", "flows": "cf", "overlay": "ov",
                   "garch": "gv", "attribution": "attr", "antithetic": "pairs", "filtered": "ft", "jumps": "jp", "regimes": "rs",
-                  "glide": "gl", "protect": "pt", "spending": "sp", "lifetime": "life", "tolerance": "tb"}
+                  "glide": "gl", "protect": "pt", "spending": "sp", "lifetime": "life", "tolerance": "tb", "vol_target": "vt"}
 
 
 class Context:
@@ -111,8 +116,8 @@ class Context:
     def _call(self, prm: _ffi.McpParams, W, seed: int, path_begin: int, n_paths: int, store: bool, mu=None, chol=None, rows=None,
               block: float = 1.0, dof=None, period=None, cost: float = 0.0, drawdown: bool = False, horizons=None, levels=(),
               flows=None, target=None, overlay=None, garch=None, attribution=False, antithetic=False, filtered=None, jumps=None, regimes=None,
-              glide=None, protect=None, spending=None, lifetime=None, tolerance=None):
-        """The one library call behind every simulate_* method: tolerance bands (tolerance: (every, cost, tol float32 [K, N], levels in percent of the trade counts' order statistics), SPEC.md 4.18 / 5.18; the rule carries its own period and cost, so not with `period`), the lifetime (lifetime: the levels in percent of its order statistics, SPEC.md 4.17 / 5.17; needs flows or spending), a spending rule (spending: the (rate, every, down, up, inflation, first or None) of check_spending; `target` is then its second count), floor protection (protect: the (floor, multiplier, rate, cap, ratchet) of check_protect; `target` is then its second count), two regimes (regimes: the (p01, p10, start, mu1, chol1) of check_regimes), market jumps (jumps: the (intensity, mean, std, loading or None) of check_jumps), GARCH volatility (garch: the (alpha, beta, h0) of check_garch), an option overlay (overlay: the triple of check_overlay), cash flows (flows, target), Student-t draws (dof), rebalancing
+              glide=None, protect=None, spending=None, lifetime=None, tolerance=None, vol_target=None):
+        """The one library call behind every simulate_* method: a volatility target (vol_target: the (target, decay, cap, rate, spread, s0 or None) of voltarget.check_vol_target, SPEC.md 4.19 / 5.19; `target` is then its second count, and without `drawdown` the call leaves the exposure record), tolerance bands (tolerance: (every, cost, tol float32 [K, N], levels in percent of the trade counts' order statistics), SPEC.md 4.18 / 5.18; the rule carries its own period and cost, so not with `period`), the lifetime (lifetime: the levels in percent of its order statistics, SPEC.md 4.17 / 5.17; needs flows or spending), a spending rule (spending: the (rate, every, down, up, inflation, first or None) of check_spending; `target` is then its second count), floor protection (protect: the (floor, multiplier, rate, cap, ratchet) of check_protect; `target` is then its second count), two regimes (regimes: the (p01, p10, start, mu1, chol1) of check_regimes), market jumps (jumps: the (intensity, mean, std, loading or None) of check_jumps), GARCH volatility (garch: the (alpha, beta, h0) of check_garch), an option overlay (overlay: the triple of check_overlay), cash flows (flows, target), Student-t draws (dof), rebalancing
         (period, cost), bootstrap rows (rows, block) or Gaussian draws (mu, chol), with the drawdown or horizons.  Allocates the
         outputs that were asked for and passes NULL for the rest -> _Outputs, None where not asked for (terminal, qd,
         horizon_terminal: with `store` only; counts, hz_counts: with `flows` only; attr [K, N] records of ATTR_DTYPE and attr_counts
@@ -126,11 +131,12 @@ class Context:
                                    ("antithetic", antithetic), ("filtered", filtered is not None), ("jumps", jumps is not None),
                                    ("regimes", regimes is not None), ("glide", glide is not None),
                                    ("protect", protect is not None), ("spending", spending is not None),
-                                   ("lifetime", lifetime is not None), ("tolerance", tolerance is not None)) if on]
+                                   ("lifetime", lifetime is not None), ("tolerance", tolerance is not None),
+                                   ("vol_target", vol_target is not None)) if on]
         has = set(given).issuperset
-        entry, refusal = _BAND_CHOICE if tolerance is not None else _LIFE_CHOICE if lifetime is not None else next((e, r) for needs, e, r in _ENTRY_CHOICE if has(needs))
+        entry, refusal = _BAND_CHOICE if tolerance is not None else _LIFE_CHOICE if lifetime is not None else _VOLTARGET_CHOICE if vol_target is not None else next((e, r) for needs, e, r in _ENTRY_CHOICE if has(needs))
         groups = next(t[entry] for t in (_ffi.SIMULATE_ENTRIES, _ffi.EXTENSION_ENTRIES, _ffi.SPEND_ENTRIES, _ffi.LIFE_ENTRIES,
-                                            _ffi.BAND_ENTRIES) if entry in t)
+                                            _ffi.BAND_ENTRIES, _ffi.VOLTARGET_ENTRIES) if entry in t)
         # the library states the rules (check_request); a keyword the entry point has no argument for is refused here, not dropped
         for kw in given:
             if _KEYWORD_GROUP[kw] not in groups:
@@ -167,6 +173,9 @@ class Context:
             life_hist = np.zeros((K, prm.n_steps + 1), np.uint64)
             life_sum = np.zeros(K, np.uint64)
             life_q = np.zeros((K, life_lv.size), np.uint32)
+        has_exposure = "exposure" in groups and not drawdown  # SPEC.md 5.19: one second array, the drawdown's when it is asked for
+        exposure_stats = np.zeros(K, _ffi.STATS_DTYPE) if has_exposure else None
+        exposure = np.empty((K, n_paths), np.float32) if has_exposure and store else None
         trades = trade_hist = trade_sum = trade_q = trade_lv = turnover = turnover_stats = tol = None
         if tolerance is not None:
             from .tolerance import n_reviews
@@ -187,6 +196,8 @@ class Context:
                 "life": (life, life_hist, life_sum, 0 if life_lv is None else life_lv.size, life_lv if life_lv is not None and life_lv.size else None,
                          life_q if life_lv is not None and life_lv.size else None),
                 "tb": (_ffi.make_band(tolerance[0], tolerance[1], tol) if tolerance is not None else None,),
+                "vt": (_ffi.make_vol_target(*vol_target, target_value=target) if vol_target is not None else None,),
+                "exposure": (exposure, exposure_stats),
                 "trades": (trades, trade_hist, trade_sum, 0 if trade_lv is None else trade_lv.size,
                            trade_lv if trade_lv is not None and trade_lv.size else None, trade_q if trade_lv is not None and trade_lv.size else None,
                            turnover, turnover_stats),
@@ -207,7 +218,8 @@ class Context:
         rc = getattr(_ffi.lib(), entry)(*(arg(g, v) for g in groups for v in vals[g.rstrip("*")]))
         _ffi.check(rc)
         return _Outputs(stats, dd_stats, hz_stats, bands, term, raw, hz_term, counts, hz_counts, attr, attr_counts, contrib, pairs,
-                        wd_stats, withdrawn, life_hist, life_sum, life_q, life, trade_hist, trade_sum, trade_q, trades, turnover_stats, turnover)
+                        wd_stats, withdrawn, life_hist, life_sum, life_q, life, trade_hist, trade_sum, trade_q, trades, turnover_stats, turnover,
+                        exposure_stats, exposure)
 
     def simulate_banded(self, prm: _ffi.McpParams, every: int, cost: float, tol, W, seed: int, path_begin: int, n_paths: int, store: bool,
                         levels=(5.0, 50.0, 95.0), mu=None, chol=None, rows=None, block: float = 1.0, horizons=None, bands=()):
@@ -372,6 +384,17 @@ class Context:
         return self._call(prm, W, seed, path_begin, n_paths, store, mu=mu, chol=chol, dof=dof, garch=garch, jumps=jumps, target=target,
                           drawdown=drawdown, horizons=horizons, levels=levels, protect=(floor,) + tuple(float(v) for v in protect[1:5]))
 
+    def simulate_vol_target(self, prm: _ffi.McpParams, vol_target, mu, chol, W, seed: int, path_begin: int, n_paths: int, store: bool,
+                            dof=None, garch=None, jumps=None, target=None, drawdown: bool = False, horizons=None, levels=()):
+        """simulate() / simulate_student_t() / simulate_garch() / simulate_jumps(), with their drawdown or horizons, under the
+        volatility target of SPEC.md 4.19 (include/mcport_voltarget.h, mcp_simulate_vol_target; simple compounding only): `vol_target`
+        is (target, decay, cap, rate, spread, s0 float64 [K] or None) -> _Outputs with counts [K, 2] uint64 {n_ruined, n_short: V_T
+        below `target`, 0 without one}, hz_counts [H, K, 2] and, without `drawdown`, exposure_stats [K] (the record of the summed
+        exposure Y_T - 1) and, with `store`, exposure [K, n_paths] binary32."""
+        vt = tuple(vol_target) + (1.0, 0.0, 0.0, None)[len(tuple(vol_target)) - 2:]
+        return self._call(prm, W, seed, path_begin, n_paths, store, mu=mu, chol=chol, dof=dof, garch=garch, jumps=jumps, target=target,
+                          drawdown=drawdown, horizons=horizons, levels=levels, vol_target=vt)
+
     def simulate_spending(self, prm: _ffi.McpParams, spending, W, seed: int, path_begin: int, n_paths: int, store: bool, mu=None,
                           chol=None, rows=None, block: float = 1.0, dof=None, target=None, horizons=None, levels=()):
         """simulate_cashflow() with a withdrawal that depends on the path in place of the schedule (SPEC.md 4.16 / 5.16;
@@ -397,10 +420,11 @@ class Context:
 # SPEC.md 5.6 (counts [K, 2], hz_counts [H, K, 2], uint64).
 # With attribution the records of SPEC.md 5.9 (attr [K, N] of ATTR_DTYPE, attr_counts [K, 2] uint64 {n, n_tail}) and, stored, the
 # binary32 contributions [K, N, n].  With antithetic pairs the records of SPEC.md 5.10 (pairs [K] of PAIR_DTYPE).  With a spending rule
-# the record of the total paid out (wd_stats [K]) and, stored, the binary32 withdrawn [K, n] (SPEC.md 5.16).
+# the record of the total paid out (wd_stats [K]) and, stored, the binary32 withdrawn [K, n] (SPEC.md 5.16).  With a volatility target
+# and no drawdown the record of the summed exposure (exposure_stats [K], over Y - 1) and, stored, the binary32 exposure [K, n] (5.19).
 _Outputs = collections.namedtuple("_Outputs", "stats dd_stats hz_stats bands terminal qd horizon_terminal counts hz_counts attr "
                                   "attr_counts contributions pairs wd_stats withdrawn life_hist life_sum life_q life trade_hist trade_sum trade_q trades "
-                                  "turnover_stats turnover", defaults=(None,) * 18)
+                                  "turnover_stats turnover exposure_stats exposure", defaults=(None,) * 20)
 
 
 def check_cashflow(cashflow, target, n_steps):
@@ -944,8 +968,11 @@ def antithetic_to_dict(rec) -> dict:
 # with, and whether the refusal lists the offending names only (True) or all of them as one fixed sentence (False).  A name is a
 # keyword -- given when it is not None, or true for a flag -- or keyword='value'.  The rows stand in the order the rules are
 # checked, so the same rule wins when two apply.  The C side states the same rules for the library (check_request).
-_FLAGS = ("drawdown", "attribution", "antithetic", "fold", "native_math")
+_FLAGS = ("drawdown", "attribution", "antithetic", "fold", "native_math", "lifetime")
 _PATHS_COMBINE = {
+    "vol_target": ("vol_target needs constant weights, simple compounding, the spec's normals and the unfolded recurrence",
+                   ("tolerance", "spending", "protect", "glide", "regimes", "rebalance", "cashflow", "overlay", "attribution", "antithetic",
+                    "lifetime", "fold", "native_math", "compounding='log'"), True),
     "tolerance": ("tolerance needs the rebalancing walk -- Gaussian draws, simple compounding, the spec's normals and the unfolded recurrence",
                   ("drawdown", "cashflow", "glide", "protect", "spending", "overlay", "dof", "garch", "jumps", "regimes", "attribution",
                    "antithetic", "fold", "native_math", "compounding='log'"), True),
@@ -1014,7 +1041,8 @@ def simulate_paths(mu, cov, weights, n_steps=252, n_paths=10_000, seed=0, v0=1.0
                    native_math=False, as_array=False, fold=False, shard="auto", context=None, drawdown=False,
                    horizons=None, bands=(), rebalance=None, rebalance_cost=0.0, dof=None, cashflow=None, target=None,
                    overlay=None, spot=None, garch=None, attribution=False, antithetic=False, jumps=None, regimes=None, glide=None,
-                   protect=None, spending=None, lifetime=False, lifetime_levels=(5, 25, 50), tolerance=None, tolerance_levels=(5, 50, 95)):
+                   protect=None, spending=None, lifetime=False, lifetime_levels=(5, 25, 50), tolerance=None, tolerance_levels=(5, 50, 95),
+                   vol_target=None):
     """Simulate `n_paths` correlated return paths and reduce them to risk statistics.
 
     mu [N], cov [N,N] are per-step mean and covariance (the reference's `mean_returns`, `cov_matrix`
@@ -1211,7 +1239,28 @@ def simulate_paths(mu, cov, weights, n_steps=252, n_paths=10_000, seed=0, v0=1.0
     cost K walks.  Combines with horizons / bands, store, as_array, devices, path_begin and bootstrap rows (simulate_bootstrap).  Not
     built: tolerance with drawdown, cashflow, glide, protect, spending, overlay, dof, garch, jumps, regimes, attribution, antithetic, fold,
     native_math or compounding="log" (ValueError), on filtered rows, in simulate_sweep, in PathEngine and at the mcp_launch_* level.
+
+    vol_target=None (default): the whole value rides the weights.  vol_target=(target, decay[, cap[, rate[, spread[, s0]]]]): volatility
+    targeting inside the walk (SPEC.md 4.19 / 5.19) -- before every step the exposure to the weights is e = min(target / sqrt(s), cap),
+    s an exponentially weighted average of the path's own squared portfolio returns (decay = voltarget.ewma_decay(halflife); it starts
+    at s0, by default the variance w' cov w of the Gaussian part); the rest of the value earns `rate` per step, what is borrowed above
+    the value (cap > 1) pays rate + spread, and a path that loses everything is ruined for good.  The draws, the drawdown and the
+    horizons are those of the same call without it, on the targeted value.  With cap=1 and a target that always binds the cap the
+    stored values are the plain call's bit for bit.  Every dict gains 'vol_target' {target, decay, one_minus_decay, cap, rate, spread
+    (binary32, as used), s0, exposure0 (the first step's exposure), target_value, n_ruined, ruin_probability, n_short,
+    shortfall_probability (below `target`; 0 without one), with horizons the same per horizon and, without drawdown, exposure {mean,
+    std, quantile (at level 1 - alpha), level, min, max of the per-path average exposure and, with store=True, paths float32
+    [n_paths]: the per-path SUM of the exposures}}; as_array appends counts[, hz_counts] and, without drawdown, exposure_stats (over
+    Y - 1)[, exposure].  voltarget.vol_target_law is the exact law of a constant exposure.  Combines with dof, garch, jumps (alone),
+    drawdown or horizons / bands, target, store, as_array, devices and shard="portfolios".  Not built: vol_target with tolerance,
+    spending, protect, glide, regimes, rebalance, cashflow, overlay, attribution, antithetic, lifetime, fold, native_math or
+    compounding="log" (ValueError), on bootstrap or filtered rows, in simulate_sweep, in PathEngine and at the mcp_launch_* level.
     """
+    if vol_target is not None:
+        return _simulate_vol_target(mu, cov, weights, n_steps, n_paths, seed, v0, compounding, rf, alpha, devices, store, path_begin, chol,
+                                    native_math, as_array, fold, shard, context, drawdown, horizons, bands, rebalance, rebalance_cost, dof,
+                                    cashflow, target, overlay, spot, garch, attribution, antithetic, jumps, regimes, glide, protect, spending,
+                                    lifetime, tolerance, vol_target)
     from .lifetime import check_lifetime
     lt = check_lifetime(lifetime, lifetime_levels, n_steps)
     if lt is not None and cashflow is None and spending is None:
@@ -1316,6 +1365,51 @@ def simulate_paths(mu, cov, weights, n_steps=252, n_paths=10_000, seed=0, v0=1.0
         for d in [res] if isinstance(res, dict) else res:
             d["regimes"] = dict(blk)
     return res if lt is None else _with_lifetime(res, out, lt, store, as_array)
+
+
+def _simulate_vol_target(mu, cov, weights, n_steps, n_paths, seed, v0, compounding, rf, alpha, devices, store, path_begin, chol, native_math,
+                         as_array, fold, shard, context, drawdown, horizons, bands, rebalance, rebalance_cost, dof, cashflow, target, overlay,
+                         spot, garch, attribution, antithetic, jumps, regimes, glide, protect, spending, lifetime, tolerance, vol_target):
+    """simulate_paths with a volatility target (SPEC.md 4.19 / 5.19): the rules of what it combines with, then the draws' own rules
+    in simulate_paths' order, the call and the 'vol_target' block."""
+    from .voltarget import check_vol_target, vol_target_blocks
+    if not isinstance(lifetime, (bool, np.bool_)):
+        raise ValueError(f"lifetime must be True or False, got {lifetime!r}")
+    kw = dict(vol_target=vol_target, tolerance=tolerance, spending=spending, protect=protect, glide=glide, regimes=regimes, jumps=jumps,
+              antithetic=antithetic, attribution=attribution, garch=garch, overlay=overlay, cashflow=cashflow, dof=dof, rebalance=rebalance,
+              drawdown=drawdown, horizons=horizons, lifetime=lifetime, fold=fold, native_math=native_math, compounding=compounding,
+              shard=shard)
+    vt = check_vol_target(vol_target, np.atleast_2d(np.asarray(weights)).shape[0])
+    _check_combines(_PATHS_COMBINE, "vol_target", kw)
+    if spot is not None:
+        raise ValueError("spot belongs to overlay: vol_target takes none")
+    goal = check_cashflow(0.0, target, n_steps)[1] if target is not None else None   # the target of a targeted call is the second count's
+    jv = check_jumps(jumps, len(np.atleast_1d(np.asarray(mu))))
+    _check_combines(_PATHS_COMBINE, "jumps", kw)
+    gv = check_garch(garch)
+    dof = check_dof(dof)
+    for feature in ("drawdown", "horizons"):
+        _check_combines(_PATHS_COMBINE, feature, kw)
+    steps, levels = _check_walk(n_steps, horizons, bands, None, compounding, shard)
+    if jv is not None and chol is None:                    # `cov` is the total covariance: the diffusion gets what the jumps leave
+        from .jumps import diffusion_cov
+        cov = diffusion_cov(cov, jv)
+    mu32, L, W = prepare_inputs(mu, cov, weights, chol)
+    prm, ctx = _setup(mu32.shape[0], n_steps, W.shape[0], compounding, v0, alpha, rf, False, False, devices, shard, context)
+    vts = _ffi.make_vol_target(*vt)
+    consts, s0 = _ffi.vol_target_consts(prm, vts, L, W)    # the library's rules, s0's among them, before anything is launched
+    out = ctx._call(prm, W, int(seed), int(path_begin), int(n_paths), store, mu=mu32, chol=L, dof=dof, drawdown=bool(drawdown), horizons=steps,
+                    levels=levels, target=goal, garch=gv, jumps=jv, vol_target=vt)
+    res = _result(out._replace(counts=None, hz_counts=None), np.asarray(weights).ndim == 1, store, as_array, steps, levels, compounding)
+    if as_array:
+        return ((res if isinstance(res, tuple) else (res,)) + ((out.counts,) if out.hz_counts is None else (out.counts, out.hz_counts))
+                + (() if out.exposure_stats is None else (out.exposure_stats, out.exposure) if store else (out.exposure_stats,)))
+    for d, blk in zip([res] if isinstance(res, dict) else res, vol_target_blocks(consts, s0, out, n_steps, alpha, goal, store)):
+        d["vol_target"] = blk
+    if jv is not None:
+        for d, blk in zip([res] if isinstance(res, dict) else res, _jump_blocks(jv, L, W)):
+            d["jumps"] = blk
+    return res
 
 
 def _with_tolerance(res, out, tol, every, levels, store, as_array):
@@ -1667,6 +1761,8 @@ def simulate_sweep(mu, cov, weights=None, n_portfolios=2500, min_weights=None, m
         raise ValueError("simulate_sweep does not take spending: call simulate_paths for the optimum")
     if kw.get("tolerance") is not None:
         raise ValueError("simulate_sweep does not take tolerance: call simulate_paths for the optimum")
+    if kw.get("vol_target") is not None:
+        raise ValueError("simulate_sweep does not take vol_target: call simulate_paths for the optimum")
     if kw.get("attribution"):
         raise ValueError("simulate_sweep does not take attribution: call simulate_paths for the optimum")
     kw.pop("attribution", None)
