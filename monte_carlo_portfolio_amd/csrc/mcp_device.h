@@ -217,7 +217,8 @@ __device__ __forceinline__ float normal_icdf_centred(uint32_t x, const float4* t
 
 // MCP_FLAG_NATIVE_MATH: Box-Muller on the hardware approximations (v_log_f32, v_sqrt_f32, v_sin_f32, v_cos_f32) of
 // word pairs.  Statistically equivalent N(0,1) draws from the same Philox stream, but NOT the spec's normals: results
-// are comparable to the oracle only in distribution (tests check moments and Monte-Carlo-level agreement).
+// are comparable to the oracle only in distribution.  Every draw is held to the float64 evaluation of this formula on the same
+// words, |z - z_ref| <= 2^-20 max(1, R) (tests/native_ref.py, tests/test_gpu_native.py; SPEC.md section 3).
 __device__ __forceinline__ void box_muller_native(uint32_t xa, uint32_t xb, float& z_sin, float& z_cos) {
   const float u = fma32((float)xa, 0x1p-32f, 0x1p-32f);
   const float t = __builtin_amdgcn_logf(u) * NEG_2LN2;
