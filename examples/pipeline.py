@@ -75,6 +75,11 @@ def main(paths, resample_rule="M", user_rf=3.0, investment=10000.0, seed=12345, 
     print(f"Student-t (nu = {nu}, fitted to the {len(returns_df)} observed rows), same weights: mean {tsim['mean']:+.4f}  "
           f"std {tsim['std']:.4f}  VaR95 {tsim['var']:+.4f}  CVaR95 {tsim['cvar']:+.4f}  Sharpe {tsim['sharpe']:.4f}  "
           f"DaR95 {tsim['drawdown']['dar']:+.4f}")
+    # how long the optimum stays below its high-water mark on those paths (SPEC.md 4.20 / 5.20): exact integers off two histograms
+    uw = mcp.simulate_paths(mu_step, cov_step, w, n_steps=af, n_paths=n_paths, seed=seed, v0=investment, rf=user_rf / 100, dof=nu,
+                            drawdown=True, underwater=True, underwater_levels=(50, 95))["underwater"]
+    print(f"  time under water: longest spell median {uw['longest']['levels'][50.0]} / 95 % {uw['longest']['levels'][95.0]} of {af} "
+          f"period(s), P(under water at the end) = {uw['p_under_water_at_end']:.4f}")
     tfan = mcp.simulate_paths(mu_step, cov_step, w, n_steps=6, n_paths=n_paths, seed=seed, v0=investment, dof=nu, horizons=[1, 3, 6],
                               bands=(2.5, 50.0, 97.5))["horizons"]
     for h, b in zip(tfan["steps"], tfan["bands"]):

@@ -242,6 +242,8 @@ ARG_GROUPS = {
     "life": [_vp, _vp, _vp, _int, _vp, _vp],              # life_out, life_hist_out, life_sum_out, n_life_levels, life_levels, life_q_out
     "tb": [ctypes.POINTER(McpBand)],
     "vt": [ctypes.POINTER(McpVolTarget)], "exposure": [_vp, _vp],     # exposure_out, exposure_stats_out
+    # longest_out, current_out, longest_hist_out, current_hist_out, sums_out, n_uw_levels, uw_levels, q_out
+    "uw": [_vp, _vp, _vp, _vp, _vp, _int, _vp, _vp],
     # trades_out, trade_hist_out, trade_sum_out, n_trade_levels, trade_levels, trade_q_out, turnover_out, turnover_stats_out
     "trades": [_vp, _vp, _vp, _int, _vp, _vp, _vp, _vp],
     "mu": [_vp], "chol": [_vp], "W": [_vp], "mu*": [_f32p], "chol*": [_f32p], "W*": [_f32p],
@@ -332,6 +334,14 @@ VOLTARGET_SIGNATURES = {
 }
 VOLTARGET_SIGNATURES.update((name, (_int, [t for g in groups for t in ARG_GROUPS[g]])) for name, groups in VOLTARGET_ENTRIES.items())
 
+# And for include/mcport_underwater.h (SPEC.md 4.20 / 5.20).
+UNDERWATER_ENTRIES = {
+    "mcp_simulate_underwater": "ctx prm gv st jp mu chol W walk out dd uw",
+}
+UNDERWATER_ENTRIES = {name: tuple(groups.split()) for name, groups in UNDERWATER_ENTRIES.items()}
+UNDERWATER_SIGNATURES = {}
+UNDERWATER_SIGNATURES.update((name, (_int, [t for g in groups for t in ARG_GROUPS[g]])) for name, groups in UNDERWATER_ENTRIES.items())
+
 _LIB = None
 
 
@@ -397,7 +407,7 @@ def lib() -> ctypes.CDLL:
             fn.restype = res
             fn.argtypes = args
         for name, (res, args) in list(EXTENSION_SIGNATURES.items()) + list(SPEND_SIGNATURES.items()) + list(LIFE_SIGNATURES.items()) + \
-                list(BAND_SIGNATURES.items()) + list(VOLTARGET_SIGNATURES.items()):
+                list(BAND_SIGNATURES.items()) + list(VOLTARGET_SIGNATURES.items()) + list(UNDERWATER_SIGNATURES.items()):
             fn = getattr(L, name)          # additive entry points, detected by symbol: a library without them is too old
             fn.restype = res
             fn.argtypes = args

@@ -34,7 +34,7 @@ template <class T> static bool finite(const std::vector<T>& v) {
 // Minimal valid arguments of every feature for N assets, K portfolios, T steps and row tables of R rows, with the outputs a request
 // must carry, and the request of one combination of features over them.
 enum Bit { B_DD = 1, B_HZ = 2, B_REB = 4, B_BAND = 8, B_CASH = 16, B_GLIDE = 32, B_SPEND = 64, B_LIFE = 128, B_PROTECT = 256, B_OVERLAY = 512,
-           B_GARCH = 1024, B_JUMPS = 2048, B_REGIMES = 4096, B_ANTI = 8192, B_ATTR = 16384, B_VT = 32768, N_BITS = 16 };
+           B_GARCH = 1024, B_JUMPS = 2048, B_REGIMES = 4096, B_ANTI = 8192, B_ATTR = 16384, B_VT = 32768, B_UW = 65536, N_BITS = 17 };
 struct Payloads {
   static constexpr int G = 2, H = 2;
   const int N, K, T, R;
@@ -58,7 +58,7 @@ struct Payloads {
   mcp_rebalance bd_reb;
   const mcp_spending sp = {0.01, 0.1, HUGE_VAL, 0.02, 0.015, 0.9, 5, 1, 1, 0};
   std::vector<mcp_stats> stats, hz_stats, second_stats;
-  std::vector<uint64_t> counts, hz_counts, trade_hist, life_hist, attr_counts;
+  std::vector<uint64_t> counts, hz_counts, trade_hist, life_hist, uw_longest_hist, uw_current_hist, attr_counts;
   std::vector<mcp_attr> attr;
   std::vector<mcp_pair> pair;
 
@@ -67,7 +67,8 @@ struct Payloads {
         rows((size_t)R * N), shock(R), loading(N), targets((size_t)G * K * N), flows(T, -0.01f), zero_flows(T, 0.0f), floor_s(T + 1),
         spot(N, 100.0f), tol((size_t)K * N, 0.05f), row_begin(N + 1, 1), ov_rows(1, mcp_overlay_row{MCP_OVERLAY_PUT, 95.0f, 1.0f, 0.01f}),
         stats(K), hz_stats((size_t)H * K), second_stats(K), counts(2 * (size_t)K), hz_counts(2 * (size_t)H * K),
-        trade_hist((size_t)K * ((size_t)(T - 1) / 5 + 1)), life_hist((size_t)K * ((size_t)T + 1)), attr_counts(2 * (size_t)K),
+        trade_hist((size_t)K * ((size_t)(T - 1) / 5 + 1)), life_hist((size_t)K * ((size_t)T + 1)), uw_longest_hist((size_t)K * ((size_t)T + 1)),
+        uw_current_hist((size_t)K * ((size_t)T + 1)), attr_counts(2 * (size_t)K),
         attr((size_t)K * N), pair(K) {
     for (int i = 0; i < N; i++) {
       mu[i] = 0.001f * (float)(i + 1) / (float)N;
@@ -115,6 +116,7 @@ struct Payloads {
     if (bits & B_LIFE) { rq.life = true; rq.life_hist_out = life_hist.data(); }
     if (bits & B_PROTECT) { rq.protect = true; rq.pi = &pt; }
     if (bits & B_VT) { rq.vol_target = true; rq.vt = &vt; rq.exposure_stats_out = (bits & B_DD) ? nullptr : second_stats.data(); }
+    if (bits & B_UW) { rq.underwater = true; rq.uw_longest_hist_out = uw_longest_hist.data(); rq.uw_current_hist_out = uw_current_hist.data(); }
     if (bits & B_OVERLAY) { rq.overlay = true; rq.ov = &ov; }
     if (bits & B_GARCH) { rq.garch = true; rq.gv = &gv; }
     if (bits & B_JUMPS) { rq.jumps = true; rq.jp = &jp; }
@@ -126,13 +128,14 @@ struct Payloads {
   }
 };
 
-enum Feature { PLAIN, BOOT, FILTERED, JUMPS, REGIMES, GLIDE_CF, GLIDE, PROTECT, CASH, OVERLAY, SPEND, SPEND_BOOT, BAND, BAND_BOOT, VOL_TARGET, N_FEATURES };
+enum Feature { PLAIN, BOOT, FILTERED, JUMPS, REGIMES, GLIDE_CF, GLIDE, PROTECT, CASH, OVERLAY, SPEND, SPEND_BOOT, BAND, BAND_BOOT, VOL_TARGET, UNDERWATER,
+               N_FEATURES };
 static const struct { const char* name; Source src; int bits; } k_features[N_FEATURES] = {
     {"plain", SRC_GAUSS, 0}, {"bootstrap", SRC_BOOT, 0}, {"filtered", SRC_FHS, 0}, {"jumps", SRC_GAUSS, B_JUMPS}, {"regimes", SRC_GAUSS, B_REGIMES},
     {"glide+flows", SRC_GAUSS, B_CASH | B_GLIDE}, {"glide", SRC_GAUSS, B_CASH | B_GLIDE}, {"protect", SRC_GAUSS, B_PROTECT},
     {"cash", SRC_GAUSS, B_CASH}, {"overlay", SRC_GAUSS, B_OVERLAY}, {"spend", SRC_GAUSS, B_CASH | B_SPEND},
     {"spend+bootstrap", SRC_BOOT, B_CASH | B_SPEND}, {"band", SRC_GAUSS, B_REB | B_BAND}, {"band+bootstrap", SRC_BOOT, B_REB | B_BAND},
-    {"vol_target", SRC_GAUSS, B_VT}};
+    {"vol_target", SRC_GAUSS, B_VT}, {"underwater", SRC_GAUSS, B_DD | B_UW}};
 
 static void run_shape(int N, int K, int T, int H) {
   Payloads p(N, K, T, 6);
@@ -191,18 +194,31 @@ static void run_shape(int N, int K, int T, int H) {
     Request rq = p.request(k_features[f].src, k_features[f].bits | (H ? B_HZ : 0));
     if (f == GLIDE) rq.cf = &p.no_cf;
     std::vector<float> second((size_t)K * 4);                // [K][4 paths] the optional per-path outputs
-    std::vector<uint32_t> record((size_t)K * 4);
+    std::vector<uint32_t> record((size_t)K * 4), record2((size_t)K * 4);
     std::vector<mcp_stats> second_stats(K);
+    if (f == UNDERWATER && H) {           // SPEC.md 4.20: the drawdown walk stores no horizons, with or without the counters
+      EXPECT(check_request(&prm, rq, 4) == MCP_E_UNSUPPORTED);
+      continue;
+    }
+    if (rq.underwater) {
+      ask_drawdown(rq, second.data(), second_stats.data());
+      rq.uw_longest_out = record.data();
+      rq.uw_current_out = record2.data();
+    }
     if (rq.band) { rq.turnover_out = second.data(); rq.turnover_stats_out = second_stats.data(); rq.trades_out = record.data(); }
     if (rq.spend) { rq.wd_out = second.data(); rq.wd_stats_out = second_stats.data(); }
     if (rq.vol_target) { rq.exposure_out = second.data(); rq.exposure_stats_out = second_stats.data(); }
     EXPECT(check_request(&prm, rq, 4) == MCP_OK);
-    {                                     // the one second array and the one integer record of the request, on the request's own outputs
+    {                                     // the one second array and the integer records of the request, on the request's own outputs
       const Second sec = second_of(rq);
       const Counted cnt = counted_of(&prm, rq);
-      EXPECT(sec.on == (rq.band || rq.spend || rq.vol_target) && cnt.on == rq.band && cnt.bins == count_bins(&prm, rq));
+      EXPECT(sec.on == (rq.band || rq.spend || rq.vol_target || rq.underwater) && cnt.on == (rq.band || rq.underwater) && cnt.bins == count_bins(&prm, rq));
       EXPECT(sec.out == (sec.on ? second.data() : nullptr) && sec.stats_out == (sec.on ? second_stats.data() : nullptr));
-      EXPECT(cnt.out == (cnt.on ? record.data() : nullptr) && cnt.hist_out == (cnt.on ? p.trade_hist.data() : nullptr));
+      EXPECT(cnt.out == (cnt.on ? record.data() : nullptr) &&
+             cnt.hist_out == (rq.band ? p.trade_hist.data() : rq.underwater ? p.uw_longest_hist.data() : nullptr));
+      EXPECT(cnt.records == (rq.underwater ? 2 : cnt.on ? 1 : 0) && cnt.out2 == (rq.underwater ? record2.data() : nullptr) &&
+             cnt.hist_out2 == (rq.underwater ? p.uw_current_hist.data() : nullptr));
+      if (rq.underwater) EXPECT(cnt.bins == (size_t)T + 1 && sec.unit_v0 && !sec.pivoted);   // SPEC.md 5.20: the lifetime's bins; 5.1's record
       if (rq.band) EXPECT(sec.unit_v0 && !sec.pivoted);   // SPEC.md 5.18: x = Y - 1, no pivot
       if (rq.spend) EXPECT(!sec.unit_v0 && sec.pivoted);  // SPEC.md 5.16: x = Y / fl32(v0) - 1, the pivots of request_wd_pivots
       if (rq.vol_target) EXPECT(sec.unit_v0 && !sec.pivoted);   // SPEC.md 5.19: x = Y - 1, no pivot
@@ -253,6 +269,35 @@ static void run_shape(int N, int K, int T, int H) {
       const TileLayout lay = tile_layout(&prm, rq, K);
       EXPECT(lay.total - lay.floor == 8 * (((size_t)K + 7) / 8));
     }
+    if (rq.underwater) {                  // SPEC.md 4.20: a missing histogram; no drawdown; what the counters are not combined with; the step limit
+      Request ur = rq;
+      ur.uw_current_hist_out = nullptr;
+      EXPECT(check_request(&prm, ur, 4) == MCP_E_ARG);
+      ur = rq;
+      ask_drawdown(ur, nullptr, nullptr);
+      EXPECT(check_request(&prm, ur, 4) == MCP_E_ARG);
+      ur = rq;
+      ur.regimes = true;
+      ur.rs = &p.rs;
+      EXPECT(check_request(&prm, ur, 4) == MCP_E_UNSUPPORTED);
+      ur = rq;
+      ur.anti = true;
+      ur.pair_out = p.pair.data();
+      EXPECT(check_request(&prm, ur, 4) == MCP_E_UNSUPPORTED);
+      mcp_params big = prm;
+      big.n_steps = MCP_MAX_LIFE_STEPS + 1;
+      EXPECT(check_request(&big, rq, 4) == MCP_E_UNSUPPORTED);
+      mcp_params lg = prm;
+      lg.compounding = MCP_COMPOUND_LOG;  // Gaussian draws compound either way; the GARCH, Student-t and jump walks simply
+      EXPECT(check_request(&lg, rq, 4) == MCP_OK);
+      ur = rq;
+      ur.garch = true;
+      ur.gv = &p.gv;
+      EXPECT(check_request(&prm, ur, 4) == MCP_OK && check_request(&lg, ur, 4) == MCP_E_UNSUPPORTED);
+      ur.jumps = true;
+      ur.jp = &p.jp;
+      EXPECT(check_request(&prm, ur, 4) == MCP_E_UNSUPPORTED);
+    }
     if (rq.band) {                        // SPEC.md 4.18: a negative entry, a missing histogram, and the size of the histogram
       Request br = rq;
       std::vector<float> neg(p.tol);
@@ -297,6 +342,7 @@ static void run_shape(int N, int K, int T, int H) {
     mcp_bootstrap bad_boot = p.boot;
     if (f == PLAIN) bad.flags = MCP_FLAG_FOLD | MCP_FLAG_NATIVE_MATH;      // the folded step needs the spec's normals
     else if (f == BOOT) { bad_boot.mean_block = 0.5; rq.boot = &bad_boot; }  // the bootstrap compounds either way; b < 1 does not
+    else if (f == UNDERWATER) bad.flags = MCP_FLAG_NATIVE_MATH;          // the drawdown walk runs on the spec's normals
     else bad.compounding = MCP_COMPOUND_LOG;                              // every other feature compounds simply
     EXPECT(check_request(&bad, rq, 4) == (f == BOOT ? MCP_E_ARG : MCP_E_UNSUPPORTED) && mcp_last_error()[0] != '\0');
   }
@@ -400,15 +446,16 @@ static void run_plans() {
     Request rq;
     ask_horizons(rq, H != 0, H, steps, 0, nullptr, nullptr, nullptr, nullptr);
     const size_t hz = 4 * (size_t)H;
-    Request dd = rq, spend = rq, life = rq, spend_life = rq, band = rq;
+    Request dd = rq, spend = rq, life = rq, spend_life = rq, band = rq, uw = rq;
     dd.dd = true;
+    uw.dd = uw.underwater = true;
     spend.cash = spend.spend = true;
     life.cash = life.life = true;
     spend_life.cash = spend_life.spend = spend_life.life = true;
     band.rebalanced = band.band = true;
     EXPECT(tile_bytes_per_path(rq) == 4 + hz && tile_bytes_per_path(spend) == 8 + hz && tile_bytes_per_path(life) == 8 + hz);
     EXPECT(tile_bytes_per_path(spend_life) == 12 + hz && tile_bytes_per_path(band) == 16 + hz);
-    if (!H) EXPECT(tile_bytes_per_path(dd) == 8);            // the drawdown and horizons are never asked together
+    if (!H) EXPECT(tile_bytes_per_path(dd) == 8 && tile_bytes_per_path(uw) == 16);   // the drawdown and horizons are never asked together
   }
 }
 
@@ -483,11 +530,11 @@ static const Row* select_row(int nb, const mcp::PathKernel& k, int* n_out = null
 
 static long run_routes() {
   using namespace mcp;
-  // (d) the table: 82 rows for NB <= LEAN_MAX_NB (the two lean kernels), 80 above; at KT = 8 without the folded step, the lean kernels,
+  // (d) the table: 86 rows for NB <= LEAN_MAX_NB (the two lean kernels), 84 above; at KT = 8 without the folded step, the lean kernels,
   // the bands and the attribution
   for (int nb : {1, 4, 5, 16}) {
     snprintf(g_case, sizeof g_case, "row counts, nb=%d", nb);
-    EXPECT(rows_at(nb, false).size() == (nb <= LEAN_MAX_NB ? 82u : 80u) && rows_at(nb, true).size() == 74u);
+    EXPECT(rows_at(nb, false).size() == (nb <= LEAN_MAX_NB ? 86u : 84u) && rows_at(nb, true).size() == 78u);
   }
   // (a) every accepted request has exactly one row; (b) its selector is canonical: with any one flag set or cleared it is another
   // kernel's or nobody's -- under equality that is (a) again, asserted all the same, once per selector and nb; (c) every row is
@@ -571,6 +618,11 @@ static void run_named_routes() {
       {"vol target", SRC_GAUSS, B_VT, MCP_COMPOUND_SIMPLE, 0, 1, 16, 0, false, "mc_paths_vt_kernel<NB, KT, 1, false, false>"},
       {"vol target, Student-t, GARCH, drawdown", SRC_T, B_VT | B_GARCH | B_DD, MCP_COMPOUND_SIMPLE, 0, 2, 16, 0, false, "mc_paths_vt_kernel<NB, KT, 1, false, true>"},
       {"vol target, jumps, horizons", SRC_GAUSS, B_VT | B_JUMPS | B_HZ, MCP_COMPOUND_SIMPLE, 0, 1, 16, 0, false, "mc_paths_vt_kernel<NB, KT, 1, true, false>"},
+      {"under water", SRC_GAUSS, B_DD | B_UW, MCP_COMPOUND_SIMPLE, 0, 1, 16, 0, false, "mc_paths_uw_kernel<NB, KT, 1, false>"},
+      {"under water, log", SRC_GAUSS, B_DD | B_UW, MCP_COMPOUND_LOG, 0, 2, 17, 0, false, "mc_paths_uw_kernel<NB, KT, 1, true>"},
+      {"under water, Student-t", SRC_T, B_DD | B_UW, MCP_COMPOUND_SIMPLE, 0, 1, 16, 0, false, "mc_paths_g_uw_kernel<NB, KT, 1>"},
+      {"under water, GARCH", SRC_GAUSS, B_DD | B_UW | B_GARCH, MCP_COMPOUND_SIMPLE, 0, 2, 16, 0, false, "mc_paths_g_uw_kernel<NB, KT, 1>"},
+      {"under water, jumps", SRC_GAUSS, B_DD | B_UW | B_JUMPS, MCP_COMPOUND_SIMPLE, 0, 1, 16, 0, false, "mc_paths_j_uw_kernel<NB, KT, 1>"},
   };
   for (const auto& c : named) {
     snprintf(g_case, sizeof g_case, "named route: %s", c.what);

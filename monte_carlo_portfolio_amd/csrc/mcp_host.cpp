@@ -732,6 +732,23 @@ int check_request(const mcp_params* prm, const Request& rq, uint64_t n_paths, co
                                      "antithetic pairs");
     if (ln) return fail(MCP_E_UNSUPPORTED, "volatility targeting is not wired into mcp_launch_paths*");
   }
+  if (rq.underwater) {                                         // SPEC.md 4.20: two counters on the drawdown walk
+    if (!rq.dd) return fail(MCP_E_ARG, "the time under water needs the drawdown walk: dd_stats_out is NULL");
+    if (!rq.uw_longest_hist_out || !rq.uw_current_hist_out) return fail(MCP_E_ARG, "longest_hist_out or current_hist_out is NULL");
+    if (rq.src == SRC_T && (rc = check_student_t(prm, rq.st))) return rc;
+    if (rq.garch && (rc = check_garch(prm, rq.gv))) return rc;
+    if (rq.jumps && (rc = check_jumps(prm->n_assets, rq.jp))) return rc;
+    if (prm->n_steps > MCP_MAX_LIFE_STEPS)
+      return fail(MCP_E_UNSUPPORTED, "time under water: n_steps=%d above MCP_MAX_LIFE_STEPS=%d", prm->n_steps, MCP_MAX_LIFE_STEPS);
+    if (prm->flags & (MCP_FLAG_FOLD | MCP_FLAG_NATIVE_MATH))
+      return fail(MCP_E_UNSUPPORTED, "the time under water runs on the unfolded recurrence and the spec's normals (no MCP_FLAG_FOLD / MCP_FLAG_NATIVE_MATH)");
+    if (rq.src == SRC_BOOT || rq.src == SRC_FHS || rq.regimes || rq.rebalanced || rq.cash || rq.glide || rq.protect || rq.spend || rq.life ||
+        rq.band || rq.vol_target || rq.overlay || rq.attr || rq.anti || rq.hz)
+      return fail(MCP_E_UNSUPPORTED, "the time under water is not combined with bootstrap or filtered rows, regimes, rebalancing, cash flows, "
+                                     "glide paths, floor protection, spending rules, tolerance bands, volatility targeting, the overlay, the "
+                                     "attribution, antithetic pairs or horizons");
+    if (ln) return fail(MCP_E_UNSUPPORTED, "the time under water is not wired into mcp_launch_paths*");
+  }
   if (rq.overlay && (rc = check_overlay(prm, rq.ov))) return rc;
   if (rq.garch && (rc = check_garch(prm, rq.gv))) return rc;
   if (rq.jumps && (rc = check_jumps(prm->n_assets, rq.jp))) return rc;
@@ -898,6 +915,10 @@ mcp::PathKernel route_kernel(const mcp_params* prm, const Request& rq, bool attr
     k.family = rq.dd ? FAM_DD : FAM_HZ;
     k.flags |= PK_VT;
     if (!rq.jumps) k.flags = share_garch_walk(k.flags);
+  }
+  if (rq.underwater) {                    // SPEC.md 4.20: the twins of the Gaussian, the GARCH and the jump drawdown kernels; a Student-t
+    k.flags |= PK_UW;                     // request shares the GARCH walk
+    if (k.flags & PK_STT) k.flags = share_garch_walk(k.flags);
   }
   if (rq.band) k.flags |= PK_TB;          // SPEC.md 4.18: B is per portfolio, so every portfolio of a banded call is a pass of its own
   if (prm->n_portfolios > 1 && !rq.band) k.flags |= PK_KT8;
@@ -1225,8 +1246,10 @@ Second second_of(const Request& rq) {
 }
 
 Counted counted_of(const mcp_params* prm, const Request& rq) {
-  if (rq.band) return {true, count_bins(prm, rq), rq.trades_out, rq.trade_hist_out};
-  return {rq.life, count_bins(prm, rq), rq.life ? rq.life_out : nullptr, rq.life ? rq.life_hist_out : nullptr};
+  if (rq.band) return {true, count_bins(prm, rq), rq.trades_out, rq.trade_hist_out, 1, nullptr, nullptr};
+  if (rq.underwater)                                           // SPEC.md 5.20: m, then c_T
+    return {true, count_bins(prm, rq), rq.uw_longest_out, rq.uw_longest_hist_out, 2, rq.uw_current_out, rq.uw_current_hist_out};
+  return {rq.life, count_bins(prm, rq), rq.life ? rq.life_out : nullptr, rq.life ? rq.life_hist_out : nullptr, rq.life ? 1 : 0, nullptr, nullptr};
 }
 
 // A banded call is budgeted at 4 bytes more per path than its arrays hold (V_T, the horizon rows, Y and c): the figure it was
@@ -1234,7 +1257,7 @@ Counted counted_of(const mcp_params* prm, const Request& rq) {
 constexpr size_t BAND_BUDGET_SLACK = sizeof(float);
 size_t tile_bytes_per_path(const Request& rq) {
   return (1 + (rq.hz ? (size_t)rq.H : 0)) * sizeof(float) + (second_of(rq).on ? sizeof(float) : 0) +
-         (rq.life || rq.band ? sizeof(uint32_t) : 0) + (rq.band ? BAND_BUDGET_SLACK : 0);
+         (rq.life || rq.band ? sizeof(uint32_t) : 0) + (rq.band ? BAND_BUDGET_SLACK : 0) + (rq.underwater ? 2 * sizeof(uint32_t) : 0);
 }
 
 int tile_portfolios(size_t budget, uint64_t n_paths, int K, size_t bytes_per_path) {

@@ -14,6 +14,7 @@
 #include "../../include/mcport_life.h"
 #include "../../include/mcport_band.h"
 #include "../../include/mcport_voltarget.h"
+#include "../../include/mcport_underwater.h"
 #include "mcp_route.h"
 
 namespace mcp {
@@ -72,6 +73,8 @@ struct Request {
   bool regimes = false;                 // SPEC.md 2.6 / 4.13: two regimes `rs`, regime 0 on (mu, chol), on top of SRC_GAUSS
   const mcp_regimes* rs = nullptr;
   bool dd = false;                      // SPEC.md 4.2 / 5.1: the drawdown of every path
+  bool underwater = false;              // SPEC.md 4.20 / 5.20: the longest and the current spell under water, always with `dd`
+                                        // (mcp_simulate_underwater)
   bool hz = false;                      // SPEC.md 4.3 / 5.2: the values after H steps, statistics at alpha and at L levels
   int H = 0, L = 0;
   const int32_t* steps = nullptr;
@@ -94,6 +97,10 @@ struct Request {
   uint64_t* life_hist_out = nullptr;    // [K][n_steps + 1] (SPEC.md 5.17)
   uint32_t* trades_out = nullptr;       // bands: NULL or host [K*n] c (SPEC.md 4.18)
   uint64_t* trade_hist_out = nullptr;   // [K][n_reviews + 1] (SPEC.md 5.18)
+  uint32_t* uw_longest_out = nullptr;   // time under water: NULL or host [K*n] m (SPEC.md 4.20)
+  uint32_t* uw_current_out = nullptr;   // NULL or host [K*n] c_T
+  uint64_t* uw_longest_hist_out = nullptr;   // [K][n_steps + 1] (SPEC.md 5.20)
+  uint64_t* uw_current_hist_out = nullptr;   // [K][n_steps + 1]
   float* turnover_out = nullptr;        // NULL or host [K*n] Y
   mcp_stats* turnover_stats_out = nullptr;   // [K]
   bool attr = false;                    // SPEC.md 4.10 / 5.9: the second walk that attributes the risk to the assets
@@ -124,8 +131,9 @@ struct Launch {
   uint64_t mdd_stride = 0;
   float* d_wd = nullptr;                // spending rule: [K][wd_stride] Y_T; volatility target: the summed exposure Y_T
   uint64_t wd_stride = 0;
-  uint32_t* d_life = nullptr;           // lifetime: [K][life_stride] l
+  uint32_t* d_life = nullptr;           // lifetime: [K][life_stride] l; time under water: the longest spell m
   uint64_t life_stride = 0;
+  uint32_t* d_life2 = nullptr;          // time under water: [K][life_stride] the current spell c_T
   float* d_hz = nullptr;                // horizons: [H][K][hz_stride]
   uint64_t hz_stride = 0;
   const float* d_rows = nullptr;        // bootstrap: [R][N4], zero-padded
@@ -221,7 +229,8 @@ int life_summary(const uint64_t* hist, int T, int n_levels, const double* levels
 
 // SPEC.md 4.18: the reviews of a walk of T steps reviewed every e steps, floor((T - 1) / e) for 1 <= e < T, else 0
 int band_reviews(int T, int e);
-// The bins of the exact histogram of a request's integer record: the lifetime's n_steps + 1 (SPEC.md 5.17), the bands' n_reviews + 1 (5.18)
+// The bins of the exact histogram of a request's integer records: the lifetime's and the time under water's n_steps + 1 (SPEC.md 5.17 /
+// 5.20), the bands' n_reviews + 1 (5.18)
 size_t count_bins(const mcp_params* prm, const Request& rq);
 
 // ---- the packers of what a launch reads besides the packed block of mcp_pack_params ----
@@ -272,17 +281,22 @@ struct Second {
   mcp_stats* stats_out;   // the caller's [K] records
 };
 Second second_of(const Request& rq);
-// The one integer record: the lifetime l (SPEC.md 4.17 / 5.17) or the bands' trade count c (4.18 / 5.18), with its exact histogram.
+// The integer records: the lifetime l (SPEC.md 4.17 / 5.17), the bands' trade count c (4.18 / 5.18), or the two counters of the time
+// under water, m then c_T (4.20 / 5.20), each with its exact histogram.  A shard holds record r of a tile of kt portfolios as the rows
+// [r kt, (r + 1) kt) of one array, and its histograms likewise.
 struct Counted {
   bool on;
   size_t bins;            // count_bins
   uint32_t* out;          // the caller's [K*n] array, or NULL
   uint64_t* hist_out;     // the caller's [K][bins] histogram
+  int records;            // 1, or 2 for the time under water (0 when off)
+  uint32_t* out2;         // the second record's, as `out` and `hist_out`
+  uint64_t* hist_out2;
 };
 Counted counted_of(const mcp_params* prm, const Request& rq);
 
 // ---- the plan of a call: which shard does what in which tile ----
-// Bytes per path and portfolio that the tile budget counts: 4 of V_T, 4 per horizon row, 4 of the second array, 4 of the integer record
+// Bytes per path and portfolio that the tile budget counts: 4 of V_T, 4 per horizon row, 4 of the second array, 4 per integer record
 size_t tile_bytes_per_path(const Request& rq);
 // Portfolios per tile so that kt * n_paths * bytes_per_path fits the budget: whole 512-portfolio workgroups of the MFMA sweep kernel
 // when K is tiled at all.

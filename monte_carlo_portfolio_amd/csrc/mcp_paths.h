@@ -71,6 +71,11 @@
 #define MCP_MIN_WAVES_ANTI 5 // the antithetic kernels (N <= 16, one portfolio) carry the second member's V, row-pair accumulator and rho (and
                             // peak and drawdown) next to the first's: see profiles/antithetic_isa.txt
 #endif
+#ifndef MCP_MIN_WAVES_UW8
+#define MCP_MIN_WAVES_UW8 4 // the under-water twins for 8 portfolios, N <= 16, simple compounding, 16 counters on top of the drawdown kernel's
+                            // state: unbounded the Gaussian twin took 129 VGPRs at N = 16 and the jump twin 134 (3 waves) where their parents
+                            // run 4; at 4 they get 128 and no listing shows scratch in a loop over t (profiles/underwater_isa.txt)
+#endif
 #ifndef MCP_EXP_VKEYS
 #define MCP_EXP_VKEYS 1
 #endif
@@ -114,7 +119,7 @@ __device__ __forceinline__ const __attribute__((address_space(4))) A* kernarg() 
 MCP_HAS_MEMBER(hz) MCP_HAS_MEMBER(mdd) MCP_HAS_MEMBER(bt) MCP_HAS_MEMBER(st) MCP_HAS_MEMBER(gv) MCP_HAS_MEMBER(cf)
 MCP_HAS_MEMBER(ov) MCP_HAS_MEMBER(at) MCP_HAS_MEMBER(period) MCP_HAS_MEMBER(pr)
 MCP_HAS_MEMBER(fh) MCP_HAS_MEMBER(p_hi) MCP_HAS_MEMBER(jp) MCP_HAS_MEMBER(rs) MCP_HAS_MEMBER(gp)
-MCP_HAS_MEMBER(pi) MCP_HAS_MEMBER(sp) MCP_HAS_MEMBER(lf) MCP_HAS_MEMBER(tb) MCP_HAS_MEMBER(vt)
+MCP_HAS_MEMBER(pi) MCP_HAS_MEMBER(sp) MCP_HAS_MEMBER(lf) MCP_HAS_MEMBER(tb) MCP_HAS_MEMBER(vt) MCP_HAS_MEMBER(uw)
 #undef MCP_HAS_MEMBER
 
 struct PathArgs {
@@ -469,6 +474,26 @@ __device__ __forceinline__ cvoltarget_p vol_target_args(const A&) {
   else return nullptr;
 }
 
+// The time under water of SPEC.md 4.20: per path and portfolio the drawdown walk may carry two uint32 counters from 0 -- the current
+// spell c, the steps since the value last stood at its running peak, and the longest spell m -- and store both next to V_T and q.  The
+// outputs are read from the kernel arguments where they are written.
+struct UnderwaterArgs {
+  uint32_t* __restrict__ longest;     // [K][uw_stride] m
+  uint32_t* __restrict__ current;     // [K][uw_stride] c_T
+  uint64_t uw_stride;
+};
+// Arguments of the under-water twins: those of mc_paths_dd_kernel, mc_paths_g_dd_kernel and mc_paths_j_dd_kernel, and the counters'
+// block behind them.
+struct PathArgsUW : PathArgsDD { UnderwaterArgs uw; };
+struct PathArgsGUW : PathArgsGDD { UnderwaterArgs uw; };
+struct PathArgsJUW : PathArgsJDD { UnderwaterArgs uw; };
+typedef const __attribute__((address_space(4))) UnderwaterArgs* cunderwater_p;
+template <class A>
+__device__ __forceinline__ cunderwater_p underwater_args(const A&) {
+  if constexpr (has_uw<A>::value) return &kernarg<A>()->uw;
+  else return nullptr;
+}
+
 // The option overlay of SPEC.md 4.8: per asset a run of rows (kind, strike, premium, qty) that turns the raw return r_i of a step
 // into the strategy's return r'_i at the asset's price level P_i.  rows, row_begin [N4 + 1] (assets >= N own no rows) and spot [N4]
 // are device copies; bit i of `mask` is set when asset i owns rows.
@@ -536,6 +561,7 @@ struct PathLaunchArgs {
   LifeArgs lf;
   BandArgs tb;
   VolTargetArgs vt;
+  UnderwaterArgs uw;
 };
 template <class A>
 inline A make_args(const PathLaunchArgs& s) {
@@ -560,6 +586,7 @@ inline A make_args(const PathLaunchArgs& s) {
   if constexpr (has_lf<A>::value) x.lf = s.lf;
   if constexpr (has_tb<A>::value) x.tb = s.tb;
   if constexpr (has_vt<A>::value) x.vt = s.vt;
+  if constexpr (has_uw<A>::value) x.uw = s.uw;
   if constexpr (has_p_hi<A>::value) { x.p_hi = (uint32_t)(s.hz.path_begin >> 32); x.pad = 0u; }
   return x;
 }
@@ -666,20 +693,28 @@ constexpr int PATH_BLOCK = 256;
 // review, at which only the lanes with a watched asset out of its band trade; the walk also carries the trade count c and the turnover
 // Y and stores them next to V_T (SPEC.md 4.18).  VT (with HZ): the walk also carries the variance estimate s and, without DD, the summed
 // exposure Y; the update of V holds the exposure e = fminf(tgt / sqrtf(s), b) in the risky portfolio, the rest at the riskless rate, what
-// is borrowed at the spread on top, ruin absorbing; s then moves on the step's rho (SPEC.md 4.19).  Every kernel
+// is borrowed at the spread on top, ruin absorbing; s then moves on the step's rho (SPEC.md 4.19).  UW (with DD): behind the update of the
+// peak the step also counts the current spell below it and keeps the longest, one compare against the peak just written, one add, one
+// select and one integer max per path and portfolio; both counters are stored next to V_T (SPEC.md 4.20).  Every kernel
 // below is the body in mcp_paths_body.inc under its own flags F: it names the flags it sets, the rest are PathFlagsOff's.  F is a
 // local class, which may not have static data members, so it sets its flags as enumerators of an `enum : bool`; they hide the
 // defaults' names and read as the same constant expressions.
 struct PathFlagsOff {
   static constexpr bool NATIVE = false, FOLD = false, LOGC = false, DD = false, HZ = false, BOOT = false, BLDS = false, REB = false,
                         STT = false, CF = false, OV = false, GV = false, AT = false, ANTI = false, FH = false, UHI = false, JP = false, RS = false,
-                        GP = false, PI = false, SP = false, LT = false, TB = false, VT = false;
+                        GP = false, PI = false, SP = false, LT = false, TB = false, VT = false, UW = false;
 };
 
 // __launch_bounds__ 2nd argument of a path kernel: the MCP_MIN_WAVES* above for N <= 16 and one path per lane, by the kind of
 // state the kernel carries; MCP_MIN_WAVES_BIG for 16 < N <= 64 and one portfolio; otherwise unbounded.
-enum BoundsKind { BK_PATHS, BK_REB, BK_CF, BK_OV, BK_AT, BK_ANTI, BK_PI, BK_SP };
+enum BoundsKind { BK_PATHS, BK_REB, BK_CF, BK_OV, BK_AT, BK_ANTI, BK_PI, BK_SP, BK_UW, BK_UWJ };
 constexpr int min_waves(BoundsKind kind, int NB, int KT, int PPT) {
+  if (kind == BK_UW || kind == BK_UWJ) {      // the under-water twins (simple compounding); BK_UWJ: on the jump walk, which from N = 5 on
+                                              // takes the protection kernel's 5 waves (at 6 the N = 16 kernel had scratch in its step loop)
+    if (NB <= 4 && PPT == 1 && KT == 1) return (kind == BK_UWJ && NB >= 2) ? MCP_MIN_WAVES_PI : MCP_MIN_WAVES;
+    if (NB <= 4 && PPT == 1) return MCP_MIN_WAVES_UW8;
+    return (KT == 1 && PPT == 1) ? MCP_MIN_WAVES_BIG : 1;
+  }
   if (kind == BK_SP) return (NB <= 4 && PPT == 1) ? (KT == 1 ? MCP_MIN_WAVES_SP : MCP_MIN_WAVES_SP8) : (KT == 1 && PPT == 1) ? MCP_MIN_WAVES_BIG : 1;
   if (kind == BK_ANTI) return (NB <= 4 && PPT == 1 && KT == 1) ? MCP_MIN_WAVES_ANTI : 1;
   if (NB <= 4 && PPT == 1 && KT == 1)
@@ -904,6 +939,29 @@ __global__ void MCP_BOUNDS(JP_ ? BK_PI : BK_PATHS) mc_paths_pi_kernel(const std:
 template <int NB, int KT, int PPT, bool JP_, bool DD_>
 __global__ void MCP_BOUNDS(JP_ ? BK_PI : BK_PATHS) mc_paths_vt_kernel(const std::conditional_t<JP_, PathArgsVJ, PathArgsVG> a) {
   struct F : PathFlagsOff { enum : bool { HZ = true, VT = true, DD = DD_, STT = !JP_, GV = !JP_, JP = JP_ }; };
+#include "mcp_paths_body.inc"
+}
+
+// The under-water twins (SPEC.md 4.20): mc_paths_dd_kernel (simple or log compounding), mc_paths_g_dd_kernel (the GARCH walk, which
+// also serves Student-t requests: alpha = beta = 0, h0 = 1) and mc_paths_j_dd_kernel with the two counters c and m carried next to the
+// peak and stored next to V_T and q; everything else those kernels compute is theirs bit for bit.  Launch bounds: their originals',
+// but for N <= 16 the jump twin of one portfolio takes 5 waves from N = 5 on (one fewer than mc_paths_j_dd_kernel: at 6 its step loop
+// at N = 16 held a scratch access) and the 8-portfolio twins under simple compounding are held at their parents' 4 (MCP_MIN_WAVES_UW8).
+// What the 2 KT counters cost in registers and occupancy is listed in profiles/underwater_isa.txt; no listing shows scratch in a
+// step loop.
+template <int NB, int KT, int PPT, bool LOGC_>
+__global__ void MCP_BOUNDS(LOGC_ ? BK_PATHS : BK_UW) mc_paths_uw_kernel(const PathArgsUW a) {
+  struct F : PathFlagsOff { enum : bool { DD = true, UW = true, LOGC = LOGC_ }; };
+#include "mcp_paths_body.inc"
+}
+template <int NB, int KT, int PPT>
+__global__ void MCP_BOUNDS(BK_UW) mc_paths_g_uw_kernel(const PathArgsGUW a) {
+  struct F : PathFlagsOff { enum : bool { DD = true, UW = true, STT = true, GV = true }; };
+#include "mcp_paths_body.inc"
+}
+template <int NB, int KT, int PPT>
+__global__ void MCP_BOUNDS(BK_UWJ) mc_paths_j_uw_kernel(const PathArgsJUW a) {
+  struct F : PathFlagsOff { enum : bool { DD = true, UW = true, JP = true }; };
 #include "mcp_paths_body.inc"
 }
 

@@ -5,7 +5,7 @@
 // derived from it) and the kernel argument `a` (PathArgs or a struct that starts with one).
   constexpr bool NATIVE = F::NATIVE, FOLD = F::FOLD, LOGC = F::LOGC, DD = F::DD, HZ = F::HZ, BOOT = F::BOOT, BLDS = F::BLDS, REB = F::REB,
                  STT = F::STT, CF = F::CF, OV = F::OV, GV = F::GV, AT = F::AT, ANTI = F::ANTI, FH = F::FH, UHI = F::UHI, JP = F::JP, RS = F::RS,
-                 GP = F::GP, PI = F::PI, SP = F::SP, LT = F::LT, TB = F::TB, VT = F::VT;
+                 GP = F::GP, PI = F::PI, SP = F::SP, LT = F::LT, TB = F::TB, VT = F::VT, UW = F::UW;
   static_assert(!UHI || (KT == 1 && PPT == 1 && !(NATIVE || FOLD || DD || HZ || BOOT || REB || STT || CF || OV || GV || AT || ANTI || FH || JP || RS || PI)),
                 "uniform high counter word: the plain Gaussian walk of one portfolio only");
   static_assert(!FH || (BOOT && HZ && !(LOGC || REB || CF || STT || GV || OV || AT || DD || PI)), "filtered rows: the bootstrap's segmented walk only");
@@ -23,6 +23,8 @@
   static_assert(!TB || (REB && KT == 1), "tolerance bands: the rebalancing kernel's walk, one portfolio per pass");
   static_assert(!VT || (HZ && (JP || (STT && GV)) && !(NATIVE || FOLD || LOGC || BOOT || REB || CF || OV || AT || ANTI || FH || UHI || RS || GP || PI || SP || LT || TB)),
                 "volatility targeting: the segmented GARCH or jump walk, simple compounding only");
+  static_assert(!UW || (DD && !(NATIVE || FOLD || HZ || BOOT || REB || CF || OV || AT || ANTI || FH || UHI || RS || GP || PI || SP || LT || TB || VT)),
+                "time under water: the drawdown walk on Gaussian draws, the GARCH walk or the jump walk only");
   constexpr int N4 = 4 * NB;
   // ANTI (SPEC.md 2.3): a lane's PPT draws feed EM = 2 PPT members -- slot e < PPT walks on z[e], slot PPT + e on -z[e]; p, live and
   // the counters are per draw (a.path_begin and a.n_paths count pairs), the members 2 p and 2 p + 1 are adjacent in the output rows
@@ -153,6 +155,7 @@
     uint32_t Tc[PPT];                                     // TB: the trade count c of SPEC.md 4.18
     float Ty[PPT];                                        // TB: the turnover Y of SPEC.md 4.18
     float Sg[PPT][KT];                                    // VT: the variance estimate s of SPEC.md 4.19; the summed exposure is Yk (!DD only)
+    uint32_t Uc[PPT][KT], Um[PPT][KT];                    // UW: the current and the longest spell under water, c and m of SPEC.md 4.20
 #pragma unroll
     for (int e = 0; e < PPT; e++) {
       p[e] = tl * tile + (uint64_t)e * PATH_BLOCK + threadIdx.x;
@@ -198,6 +201,10 @@
       if constexpr (DD) {
 #pragma unroll
         for (int k = 0; k < KT; k++) { Pk[e][k] = -__builtin_inff(); Qk[e][k] = logc ? 0.0f : 1.0f; }
+      }
+      if constexpr (UW) {
+#pragma unroll
+        for (int k = 0; k < KT; k++) { Uc[e][k] = 0u; Um[e][k] = 0u; }
       }
       if constexpr (OV) {                                 // P_i = fl32(spot_i), scalar loads once per tile
         typedef const __attribute__((address_space(4))) float* cspot_p;
@@ -565,6 +572,15 @@
           const cband_p bk = band_args(a);
           bk->trades[(size_t)a.k_begin * bk->trades_stride + p[e]] = Tc[e];
           bk->turnover[(size_t)a.k_begin * bk->turnover_stride + p[e]] = Ty[e];
+        }
+        if constexpr (UW) {                                // m and c_T of SPEC.md 4.20, next to V_T
+          const cunderwater_p uk = underwater_args(a);
+#pragma unroll
+          for (int k = 0; k < KT; k++)
+            if (k < kt) {
+              uk->longest[(size_t)(a.k_begin + k) * uk->uw_stride + p[e]] = Um[e][k];
+              uk->current[(size_t)(a.k_begin + k) * uk->uw_stride + p[e]] = Uc[e][k];
+            }
         }
         if constexpr (LT) {                                // l of SPEC.md 4.17, next to V_T
           const clife_p lk = life_args(a);

@@ -41,6 +41,12 @@ MCP_ROW(FAM_DD, PK_PI | PK_GV, mc_paths_pi_kernel<NB, KT, 1, false, true>)
 MCP_ROW(FAM_DD, PK_PI | PK_JP, mc_paths_pi_kernel<NB, KT, 1, true, true>)
 MCP_ROW(FAM_DD, PK_VT | PK_GV, mc_paths_vt_kernel<NB, KT, 1, false, true>)
 MCP_ROW(FAM_DD, PK_VT | PK_JP, mc_paths_vt_kernel<NB, KT, 1, true, true>)
+// ... and the time under water (SPEC.md 4.20): the twins of the first two, of the GARCH walk (which also serves Student-t requests) and
+// of the jump walk
+MCP_ROW(FAM_DD, PK_UW, mc_paths_uw_kernel<NB, KT, 1, false>)
+MCP_ROW(FAM_DD, PK_UW | PK_LOGC, mc_paths_uw_kernel<NB, KT, 1, true>)
+MCP_ROW(FAM_DD, PK_UW | PK_GV, mc_paths_g_uw_kernel<NB, KT, 1>)
+MCP_ROW(FAM_DD, PK_UW | PK_JP, mc_paths_j_uw_kernel<NB, KT, 1>)
 
 // The walk in segments between horizons.  The filtered rows, and the protection and the volatility target without a drawdown, run
 // here with or without horizons (H = 0: one segment).

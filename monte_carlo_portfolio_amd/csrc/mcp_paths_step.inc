@@ -468,5 +468,10 @@
           for (int k = 0; k < KT; k++) {
             Pk[e][k] = fmaxf(Pk[e][k], V[e][k]);
             Qk[e][k] = fminf(Qk[e][k], logc ? V[e][k] - Pk[e][k] : V[e][k] / Pk[e][k]);
+            if constexpr (UW) {
+              // SPEC.md 4.20: w = X_t < P against the peak just written (false on a NaN), c = w ? c + 1 : 0, m = max(m, c)
+              Uc[e][k] = V[e][k] < Pk[e][k] ? Uc[e][k] + 1u : 0u;
+              Um[e][k] = max(Um[e][k], Uc[e][k]);
+            }
           }
       }

@@ -56,9 +56,11 @@ enum PathFlag : uint32_t {
   PK_SP = 1u << 16,      // FAM_CF only: the spending kernel, the cash-flow walk on the path's own withdrawal (SPEC.md 4.16)
   PK_LT = 1u << 17,      // with exactly one of PK_GP and PK_SP: that kernel's lifetime twin (SPEC.md 4.17)
   PK_TB = 1u << 18,      // FAM_REB only, never PK_KT8: the tolerance-band kernel (SPEC.md 4.18), K portfolios as K passes of one
-  PK_VT = 1u << 19       // the volatility-targeting kernel (SPEC.md 4.19): FAM_DD with the drawdown, else FAM_HZ (H = 0 included); PK_GV or PK_JP
+  PK_VT = 1u << 19,      // the volatility-targeting kernel (SPEC.md 4.19): FAM_DD with the drawdown, else FAM_HZ (H = 0 included); PK_GV or PK_JP
+  PK_UW = 1u << 20       // FAM_DD only: the drawdown kernel's twin that also counts the time under water (SPEC.md 4.20); alone, or with one
+                         // of PK_LOGC, PK_GV and PK_JP
 };
-constexpr int N_PATH_FLAGS = 20;
+constexpr int N_PATH_FLAGS = 21;
 struct PathKernel {
   int family;            // PathFamily
   uint32_t flags;        // PathFlag bits

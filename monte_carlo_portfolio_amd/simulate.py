@@ -65,10 +65,16 @@ _BAND_CHOICE = ("mcp_simulate_banded", "tolerance is not combined with drawdown,
 # refused with this sentence.
 _VOLTARGET_CHOICE = ("mcp_simulate_vol_target", "vol_target is not combined with overlay, cashflow, rebalance, bootstrap or filtered rows, "
                                                 "regimes, glide, protect, spending, lifetime, tolerance, attribution or antithetic")
+# The time under water (SPEC.md 4.20) is an opt-in on the drawdown walk of the Gaussian, Student-t, GARCH and jump calls, not a feature of
+# its own: with `underwater` the call takes this entry point, whatever the table above would choose, and a keyword that entry point
+# has no argument group for is refused with this sentence.
+_UNDERWATER_CHOICE = ("mcp_simulate_underwater", "underwater is not combined with horizons, overlay, cashflow, rebalance, bootstrap or "
+                                                 "filtered rows, regimes, glide, protect, spending, lifetime, tolerance, vol_target, "
+                                                 "attribution or antithetic")
 # the argument group of _ffi.SIMULATE_ENTRIES that carries each feature keyword of Context._call
 _KEYWORD_GROUP = {"rows": "bt", "dof": "st", "period": "rb", "drawdown": "dd", "horizons": "hz_in", "flows": "cf", "overlay": "ov",
                   "garch": "gv", "attribution": "attr", "antithetic": "pairs", "filtered": "ft", "jumps": "jp", "regimes": "rs",
-                  "glide": "gl", "protect": "pt", "spending": "sp", "lifetime": "life", "tolerance": "tb", "vol_target": "vt"}
+                  "glide": "gl", "protect": "pt", "spending": "sp", "lifetime": "life", "tolerance": "tb", "vol_target": "vt", "underwater": "uw"}
 
 
 class Context:
@@ -116,8 +122,8 @@ class Context:
     def _call(self, prm: _ffi.McpParams, W, seed: int, path_begin: int, n_paths: int, store: bool, mu=None, chol=None, rows=None,
               block: float = 1.0, dof=None, period=None, cost: float = 0.0, drawdown: bool = False, horizons=None, levels=(),
               flows=None, target=None, overlay=None, garch=None, attribution=False, antithetic=False, filtered=None, jumps=None, regimes=None,
-              glide=None, protect=None, spending=None, lifetime=None, tolerance=None, vol_target=None):
-        """The one library call behind every simulate_* method: a volatility target (vol_target: the (target, decay, cap, rate, spread, s0 or None) of voltarget.check_vol_target, SPEC.md 4.19 / 5.19; `target` is then its second count, and without `drawdown` the call leaves the exposure record), tolerance bands (tolerance: (every, cost, tol float32 [K, N], levels in percent of the trade counts' order statistics), SPEC.md 4.18 / 5.18; the rule carries its own period and cost, so not with `period`), the lifetime (lifetime: the levels in percent of its order statistics, SPEC.md 4.17 / 5.17; needs flows or spending), a spending rule (spending: the (rate, every, down, up, inflation, first or None) of check_spending; `target` is then its second count), floor protection (protect: the (floor, multiplier, rate, cap, ratchet) of check_protect; `target` is then its second count), two regimes (regimes: the (p01, p10, start, mu1, chol1) of check_regimes), market jumps (jumps: the (intensity, mean, std, loading or None) of check_jumps), GARCH volatility (garch: the (alpha, beta, h0) of check_garch), an option overlay (overlay: the triple of check_overlay), cash flows (flows, target), Student-t draws (dof), rebalancing
+              glide=None, protect=None, spending=None, lifetime=None, tolerance=None, vol_target=None, underwater=None):
+        """The one library call behind every simulate_* method: the time under water (underwater: the levels in percent of the two counters' order statistics, SPEC.md 4.20 / 5.20; needs `drawdown`), a volatility target (vol_target: the (target, decay, cap, rate, spread, s0 or None) of voltarget.check_vol_target, SPEC.md 4.19 / 5.19; `target` is then its second count, and without `drawdown` the call leaves the exposure record), tolerance bands (tolerance: (every, cost, tol float32 [K, N], levels in percent of the trade counts' order statistics), SPEC.md 4.18 / 5.18; the rule carries its own period and cost, so not with `period`), the lifetime (lifetime: the levels in percent of its order statistics, SPEC.md 4.17 / 5.17; needs flows or spending), a spending rule (spending: the (rate, every, down, up, inflation, first or None) of check_spending; `target` is then its second count), floor protection (protect: the (floor, multiplier, rate, cap, ratchet) of check_protect; `target` is then its second count), two regimes (regimes: the (p01, p10, start, mu1, chol1) of check_regimes), market jumps (jumps: the (intensity, mean, std, loading or None) of check_jumps), GARCH volatility (garch: the (alpha, beta, h0) of check_garch), an option overlay (overlay: the triple of check_overlay), cash flows (flows, target), Student-t draws (dof), rebalancing
         (period, cost), bootstrap rows (rows, block) or Gaussian draws (mu, chol), with the drawdown or horizons.  Allocates the
         outputs that were asked for and passes NULL for the rest -> _Outputs, None where not asked for (terminal, qd,
         horizon_terminal: with `store` only; counts, hz_counts: with `flows` only; attr [K, N] records of ATTR_DTYPE and attr_counts
@@ -132,15 +138,17 @@ class Context:
                                    ("regimes", regimes is not None), ("glide", glide is not None),
                                    ("protect", protect is not None), ("spending", spending is not None),
                                    ("lifetime", lifetime is not None), ("tolerance", tolerance is not None),
-                                   ("vol_target", vol_target is not None)) if on]
+                                   ("vol_target", vol_target is not None), ("underwater", underwater is not None)) if on]
         has = set(given).issuperset
-        entry, refusal = _BAND_CHOICE if tolerance is not None else _LIFE_CHOICE if lifetime is not None else _VOLTARGET_CHOICE if vol_target is not None else next((e, r) for needs, e, r in _ENTRY_CHOICE if has(needs))
+        entry, refusal = _UNDERWATER_CHOICE if underwater is not None else _BAND_CHOICE if tolerance is not None else _LIFE_CHOICE if lifetime is not None else _VOLTARGET_CHOICE if vol_target is not None else next((e, r) for needs, e, r in _ENTRY_CHOICE if has(needs))
         groups = next(t[entry] for t in (_ffi.SIMULATE_ENTRIES, _ffi.EXTENSION_ENTRIES, _ffi.SPEND_ENTRIES, _ffi.LIFE_ENTRIES,
-                                            _ffi.BAND_ENTRIES, _ffi.VOLTARGET_ENTRIES) if entry in t)
+                                            _ffi.BAND_ENTRIES, _ffi.VOLTARGET_ENTRIES, _ffi.UNDERWATER_ENTRIES) if entry in t)
         # the library states the rules (check_request); a keyword the entry point has no argument for is refused here, not dropped
         for kw in given:
             if _KEYWORD_GROUP[kw] not in groups:
                 raise ValueError(refusal or f"{entry} has no argument for {kw}")
+        if underwater is not None and not drawdown:            # SPEC.md 4.20: the counters ride the drawdown walk
+            raise ValueError("underwater needs drawdown")
         if filtered is not None and garch is None:             # SPEC.md 4.11: the one keyword an entry point cannot do without
             raise ValueError(refusal)
         stats = np.zeros(K, _ffi.STATS_DTYPE)
@@ -173,6 +181,15 @@ class Context:
             life_hist = np.zeros((K, prm.n_steps + 1), np.uint64)
             life_sum = np.zeros(K, np.uint64)
             life_q = np.zeros((K, life_lv.size), np.uint32)
+        uw_longest = uw_current = uw_longest_hist = uw_current_hist = uw_sums = uw_q = uw_lv = None
+        if underwater is not None:
+            uw_lv = np.ascontiguousarray(underwater, np.float64).ravel()
+            uw_longest = np.empty((K, n_paths), np.uint32) if store else None
+            uw_current = np.empty((K, n_paths), np.uint32) if store else None
+            uw_longest_hist = np.zeros((K, prm.n_steps + 1), np.uint64)
+            uw_current_hist = np.zeros((K, prm.n_steps + 1), np.uint64)
+            uw_sums = np.zeros((K, 2), np.uint64)
+            uw_q = np.zeros((K, 2, uw_lv.size), np.uint32)
         has_exposure = "exposure" in groups and not drawdown  # SPEC.md 5.19: one second array, the drawdown's when it is asked for
         exposure_stats = np.zeros(K, _ffi.STATS_DTYPE) if has_exposure else None
         exposure = np.empty((K, n_paths), np.float32) if has_exposure and store else None
@@ -198,6 +215,8 @@ class Context:
                 "tb": (_ffi.make_band(tolerance[0], tolerance[1], tol) if tolerance is not None else None,),
                 "vt": (_ffi.make_vol_target(*vol_target, target_value=target) if vol_target is not None else None,),
                 "exposure": (exposure, exposure_stats),
+                "uw": (uw_longest, uw_current, uw_longest_hist, uw_current_hist, uw_sums, 0 if uw_lv is None else uw_lv.size,
+                       uw_lv if uw_lv is not None and uw_lv.size else None, uw_q if uw_lv is not None and uw_lv.size else None),
                 "trades": (trades, trade_hist, trade_sum, 0 if trade_lv is None else trade_lv.size,
                            trade_lv if trade_lv is not None and trade_lv.size else None, trade_q if trade_lv is not None and trade_lv.size else None,
                            turnover, turnover_stats),
@@ -219,7 +238,17 @@ class Context:
         _ffi.check(rc)
         return _Outputs(stats, dd_stats, hz_stats, bands, term, raw, hz_term, counts, hz_counts, attr, attr_counts, contrib, pairs,
                         wd_stats, withdrawn, life_hist, life_sum, life_q, life, trade_hist, trade_sum, trade_q, trades, turnover_stats, turnover,
-                        exposure_stats, exposure)
+                        exposure_stats, exposure, uw_longest_hist, uw_current_hist, uw_sums, uw_q, uw_longest, uw_current)
+
+    def simulate_underwater(self, prm: _ffi.McpParams, mu, chol, W, seed: int, path_begin: int, n_paths: int, store: bool,
+                            levels=(50.0, 95.0), dof=None, garch=None, jumps=None):
+        """simulate_drawdown() / simulate_student_t() / simulate_garch() / simulate_jumps() with the drawdown and the time under water of
+        every path switched on (SPEC.md 4.20 / 5.20; include/mcport_underwater.h, mcp_simulate_underwater).  `levels`: the percentages
+        of the two counters' order statistics.  -> _Outputs of that call with uw_longest_hist and uw_current_hist [K, n_steps + 1]
+        uint64, uw_sums [K, 2] uint64 {sum of m, sum of c_T}, uw_q [K, 2, len(levels)] uint32 and, with `store`, uw_longest and
+        uw_current [K, n_paths] uint32."""
+        return self._call(prm, W, seed, path_begin, n_paths, store, mu=mu, chol=chol, dof=dof, garch=garch, jumps=jumps, drawdown=True,
+                          underwater=np.asarray(levels, np.float64).ravel())
 
     def simulate_banded(self, prm: _ffi.McpParams, every: int, cost: float, tol, W, seed: int, path_begin: int, n_paths: int, store: bool,
                         levels=(5.0, 50.0, 95.0), mu=None, chol=None, rows=None, block: float = 1.0, horizons=None, bands=()):
@@ -424,7 +453,8 @@ class Context:
 # and no drawdown the record of the summed exposure (exposure_stats [K], over Y - 1) and, stored, the binary32 exposure [K, n] (5.19).
 _Outputs = collections.namedtuple("_Outputs", "stats dd_stats hz_stats bands terminal qd horizon_terminal counts hz_counts attr "
                                   "attr_counts contributions pairs wd_stats withdrawn life_hist life_sum life_q life trade_hist trade_sum trade_q trades "
-                                  "turnover_stats turnover exposure_stats exposure", defaults=(None,) * 20)
+                                  "turnover_stats turnover exposure_stats exposure uw_longest_hist uw_current_hist uw_sums uw_q uw_longest uw_current",
+                                  defaults=(None,) * 26)
 
 
 def check_cashflow(cashflow, target, n_steps):
@@ -968,8 +998,12 @@ def antithetic_to_dict(rec) -> dict:
 # with, and whether the refusal lists the offending names only (True) or all of them as one fixed sentence (False).  A name is a
 # keyword -- given when it is not None, or true for a flag -- or keyword='value'.  The rows stand in the order the rules are
 # checked, so the same rule wins when two apply.  The C side states the same rules for the library (check_request).
-_FLAGS = ("drawdown", "attribution", "antithetic", "fold", "native_math", "lifetime")
+_FLAGS = ("drawdown", "attribution", "antithetic", "fold", "native_math", "lifetime", "underwater")
 _PATHS_COMBINE = {
+    "underwater": ("underwater=True needs the drawdown walk on Gaussian, Student-t, GARCH or jump draws, the spec's normals and the unfolded "
+                   "recurrence",
+                   ("vol_target", "tolerance", "spending", "protect", "glide", "regimes", "rebalance", "cashflow", "overlay", "attribution",
+                    "antithetic", "lifetime", "horizons", "fold", "native_math"), True),
     "vol_target": ("vol_target needs constant weights, simple compounding, the spec's normals and the unfolded recurrence",
                    ("tolerance", "spending", "protect", "glide", "regimes", "rebalance", "cashflow", "overlay", "attribution", "antithetic",
                     "lifetime", "fold", "native_math", "compounding='log'"), True),
@@ -1042,7 +1076,7 @@ def simulate_paths(mu, cov, weights, n_steps=252, n_paths=10_000, seed=0, v0=1.0
                    horizons=None, bands=(), rebalance=None, rebalance_cost=0.0, dof=None, cashflow=None, target=None,
                    overlay=None, spot=None, garch=None, attribution=False, antithetic=False, jumps=None, regimes=None, glide=None,
                    protect=None, spending=None, lifetime=False, lifetime_levels=(5, 25, 50), tolerance=None, tolerance_levels=(5, 50, 95),
-                   vol_target=None):
+                   vol_target=None, underwater=False, underwater_levels=(50, 95)):
     """Simulate `n_paths` correlated return paths and reduce them to risk statistics.
 
     mu [N], cov [N,N] are per-step mean and covariance (the reference's `mean_returns`, `cov_matrix`
@@ -1255,7 +1289,26 @@ def simulate_paths(mu, cov, weights, n_steps=252, n_paths=10_000, seed=0, v0=1.0
     drawdown or horizons / bands, target, store, as_array, devices and shard="portfolios".  Not built: vol_target with tolerance,
     spending, protect, glide, regimes, rebalance, cashflow, overlay, attribution, antithetic, lifetime, fold, native_math or
     compounding="log" (ValueError), on bootstrap or filtered rows, in simulate_sweep, in PathEngine and at the mcp_launch_* level.
+
+    underwater=False (default): the drawdown says how deep a path falls, not for how long.  underwater=True, with drawdown=True: the time
+    under water (SPEC.md 4.20 / 5.20) -- per path the longest run m of consecutive steps strictly below the running peak and the steps
+    c_T since the last peak at the horizon (0: the path ends at its high-water mark), two uint32 counters on the drawdown walk; every
+    other output is that of the call without it, bit for bit.  Every dict gains 'underwater' {longest and current, each {hist uint64
+    [n_steps + 1] (#{. == s}), mean (steps), levels {level: steps} for underwater_levels in percent (np.percentile(., q,
+    method="lower")), with store steps uint32 [n_paths]}, p_under_water_at_end (1 - hist_c[0] / n)}; as_array appends longest_hist,
+    current_hist, sums [K, 2], q [K, 2, L][, longest, current].  All integers are exact and independent of devices and tiles.
+    underwater.spell_law gives the two distribution-free probabilities of a symmetric walk.  Combines with dof, garch, jumps (alone),
+    compounding="log" (Gaussian draws), store, as_array, devices and shard="portfolios".  Not built: underwater without drawdown, with
+    vol_target, tolerance, spending, protect, glide, regimes, rebalance, cashflow, overlay, attribution, antithetic, lifetime, horizons,
+    fold or native_math (ValueError), on bootstrap or filtered rows, in simulate_sweep, in PathEngine and at the mcp_launch_* level.
     """
+    if not isinstance(underwater, (bool, np.bool_)):
+        raise ValueError(f"underwater must be True or False, got {underwater!r}")
+    if underwater:
+        return _simulate_underwater(mu, cov, weights, n_steps, n_paths, seed, v0, compounding, rf, alpha, devices, store, path_begin, chol,
+                                    native_math, as_array, fold, shard, context, drawdown, horizons, bands, rebalance, rebalance_cost, dof,
+                                    cashflow, target, overlay, spot, garch, attribution, antithetic, jumps, regimes, glide, protect, spending,
+                                    lifetime, tolerance, vol_target, underwater_levels)
     if vol_target is not None:
         return _simulate_vol_target(mu, cov, weights, n_steps, n_paths, seed, v0, compounding, rf, alpha, devices, store, path_begin, chol,
                                     native_math, as_array, fold, shard, context, drawdown, horizons, bands, rebalance, rebalance_cost, dof,
@@ -1406,6 +1459,53 @@ def _simulate_vol_target(mu, cov, weights, n_steps, n_paths, seed, v0, compoundi
                 + (() if out.exposure_stats is None else (out.exposure_stats, out.exposure) if store else (out.exposure_stats,)))
     for d, blk in zip([res] if isinstance(res, dict) else res, vol_target_blocks(consts, s0, out, n_steps, alpha, goal, store)):
         d["vol_target"] = blk
+    if jv is not None:
+        for d, blk in zip([res] if isinstance(res, dict) else res, _jump_blocks(jv, L, W)):
+            d["jumps"] = blk
+    return res
+
+
+def _simulate_underwater(mu, cov, weights, n_steps, n_paths, seed, v0, compounding, rf, alpha, devices, store, path_begin, chol, native_math,
+                         as_array, fold, shard, context, drawdown, horizons, bands, rebalance, rebalance_cost, dof, cashflow, target, overlay,
+                         spot, garch, attribution, antithetic, jumps, regimes, glide, protect, spending, lifetime, tolerance, vol_target,
+                         underwater_levels):
+    """simulate_paths with the time under water (SPEC.md 4.20 / 5.20): the rules of what it combines with, then the draws' own rules in
+    simulate_paths' order, the call and the 'underwater' block."""
+    from .underwater import check_underwater, underwater_blocks
+    if not isinstance(lifetime, (bool, np.bool_)):
+        raise ValueError(f"lifetime must be True or False, got {lifetime!r}")
+    if not drawdown:
+        raise ValueError("underwater=True needs drawdown=True: the spells are counted against the running peak of the drawdown walk")
+    kw = dict(underwater=True, vol_target=vol_target, tolerance=tolerance, spending=spending, protect=protect, glide=glide, regimes=regimes,
+              jumps=jumps, antithetic=antithetic, attribution=attribution, garch=garch, overlay=overlay, cashflow=cashflow, dof=dof,
+              rebalance=rebalance, drawdown=drawdown, horizons=horizons, lifetime=lifetime, fold=fold, native_math=native_math,
+              compounding=compounding, shard=shard)
+    lv = check_underwater(underwater_levels, n_steps)
+    _check_combines(_PATHS_COMBINE, "underwater", kw)
+    if spot is not None:
+        raise ValueError("spot belongs to overlay: underwater takes none")
+    if target is not None:
+        raise ValueError("target belongs to cashflow, protect, spending or vol_target: underwater takes none")
+    jv = check_jumps(jumps, len(np.atleast_1d(np.asarray(mu))))
+    _check_combines(_PATHS_COMBINE, "jumps", kw)
+    gv = check_garch(garch)
+    _check_combines(_PATHS_COMBINE, "garch", kw)
+    dof = check_dof(dof)
+    _check_combines(_PATHS_COMBINE, "dof", kw)
+    _check_walk(n_steps, None, bands, None, compounding, shard)
+    if jv is not None and chol is None:                    # `cov` is the total covariance: the diffusion gets what the jumps leave
+        from .jumps import diffusion_cov
+        cov = diffusion_cov(cov, jv)
+    mu32, L, W = prepare_inputs(mu, cov, weights, chol)
+    prm, ctx = _setup(mu32.shape[0], n_steps, W.shape[0], compounding, v0, alpha, rf, False, False, devices, shard, context)
+    out = ctx._call(prm, W, int(seed), int(path_begin), int(n_paths), store, mu=mu32, chol=L, dof=dof, drawdown=True, garch=gv, jumps=jv,
+                    underwater=lv)
+    res = _result(out, np.asarray(weights).ndim == 1, store, as_array, None, (), compounding)
+    if as_array:
+        return ((res if isinstance(res, tuple) else (res,)) + (out.uw_longest_hist, out.uw_current_hist, out.uw_sums, out.uw_q)
+                + ((out.uw_longest, out.uw_current) if store else ()))
+    for d, blk in zip([res] if isinstance(res, dict) else res, underwater_blocks(out, lv, store, int(out.stats[0]["n"]))):
+        d["underwater"] = blk
     if jv is not None:
         for d, blk in zip([res] if isinstance(res, dict) else res, _jump_blocks(jv, L, W)):
             d["jumps"] = blk
@@ -1763,6 +1863,8 @@ def simulate_sweep(mu, cov, weights=None, n_portfolios=2500, min_weights=None, m
         raise ValueError("simulate_sweep does not take tolerance: call simulate_paths for the optimum")
     if kw.get("vol_target") is not None:
         raise ValueError("simulate_sweep does not take vol_target: call simulate_paths for the optimum")
+    if kw.get("underwater"):
+        raise ValueError("simulate_sweep does not take underwater: call simulate_paths for the optimum")
     if kw.get("attribution"):
         raise ValueError("simulate_sweep does not take attribution: call simulate_paths for the optimum")
     kw.pop("attribution", None)
