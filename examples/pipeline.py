@@ -58,6 +58,12 @@ def main(paths, resample_rule="M", user_rf=3.0, investment=10000.0, seed=12345, 
     for h, b in zip(fan["steps"], fan["bands"]):
         lo, mid, hi = investment * (1.0 + b)
         print(f"  forecast fan after {h} period(s): 2.5 % {lo:,.2f}  median {mid:,.2f}  97.5 % {hi:,.2f}")
+    # the same fan with the estimation risk of the mean inside it (SPEC.md 2.7 / 4.21): one drift per path, drawn from drift_cov(rows)
+    ufan = mcp.simulate_paths(mu_step, cov_step, w, n_steps=6, n_paths=n_paths, seed=seed, v0=investment, horizons=[1, 3, 6],
+                              bands=(2.5, 50.0, 97.5), drift_uncertainty=mcp.drift_cov(returns_df))["horizons"]
+    for h, b in zip(ufan["steps"], ufan["bands"]):
+        lo, mid, hi = investment * (1.0 + b)
+        print(f"  fan with drift uncertainty after {h} period(s): 2.5 % {lo:,.2f}  median {mid:,.2f}  97.5 % {hi:,.2f}")
     # the same weights on paths resampled from the observed rows (stationary bootstrap, SPEC.md 2.1 / 4.4): the option
     # overlay's kinks and the fat tails stay in the paths instead of being reduced to mean / cov
     boot = mcp.simulate_bootstrap(returns_df, w, n_steps=af, n_paths=n_paths, block=3.0, seed=seed, v0=investment, rf=user_rf / 100,
@@ -138,6 +144,12 @@ def main(paths, resample_rule="M", user_rf=3.0, investment=10000.0, seed=12345, 
           f"{cash['ruin_probability']:.4f}  below the initial capital {cash['shortfall_probability']:.4f}")
     for h, p, b in zip(plan["horizons"]["steps"], plan["horizons"]["ruin_probability"], plan["horizons"]["bands"]):
         print(f"  ruined after {h} periods: {p:.4f}  median value {investment * (1.0 + b[0]):,.2f}")
+    # the same plan when the drift is not taken as known (SPEC.md 2.7 / 4.21): mu_step is a mean over len(returns_df) rows, so every
+    # path draws its own drift from the standard error of that mean and walks on it -- the variance this adds grows like T^2
+    unsure = mcp.simulate_paths(mu_step, cov_step, w, n_steps=T, n_paths=n_paths, seed=seed, v0=investment, cashflow=-take, target=investment,
+                                drift_uncertainty=mcp.drift_cov(returns_df))
+    print(f"  with drift uncertainty (the mean of {len(returns_df)} rows, drift std {unsure['drift_uncertainty']['drift_std']:.5f} per period): "
+          f"ruin probability {unsure['cashflow']['ruin_probability']:.4f} against {cash['ruin_probability']:.4f} with the drift known")
     # the same plan on a glide path (SPEC.md 4.14 / 5.14): the weights move once a year, in equal steps, from the optimum to the
     # minimum-variance portfolio of the same sweep -- de-risking while the capital is drawn down
     mc = res["Monte Carlo"]

@@ -128,6 +128,12 @@ class McpVolTarget(ctypes.Structure):
                 ("spread", ctypes.c_double), ("s0", ctypes.c_void_p), ("target_value", ctypes.c_void_p), ("reserved", ctypes.c_int32)]
 
 
+class McpDriftUncertainty(ctypes.Structure):
+    """mcp_drift_uncertainty (include/mcport_uncertain.h): the lower-triangular factor M of the covariance of the drift (binary32
+    [N, N]) of SPEC.md 2.7 / 4.21."""
+    _fields_ = [("factor", ctypes.c_void_p), ("reserved", ctypes.c_int32)]
+
+
 class McpSpending(ctypes.Structure):
     """mcp_spending (include/mcport_spend.h): the rate, the largest cut and raise per review, the inflation per review, the optional
     first withdrawal and target, and the review period of the spending rule of SPEC.md 4.16."""
@@ -242,6 +248,7 @@ ARG_GROUPS = {
     "life": [_vp, _vp, _vp, _int, _vp, _vp],              # life_out, life_hist_out, life_sum_out, n_life_levels, life_levels, life_q_out
     "tb": [ctypes.POINTER(McpBand)],
     "vt": [ctypes.POINTER(McpVolTarget)], "exposure": [_vp, _vp],     # exposure_out, exposure_stats_out
+    "du": [ctypes.POINTER(McpDriftUncertainty)],
     # longest_out, current_out, longest_hist_out, current_hist_out, sums_out, n_uw_levels, uw_levels, q_out
     "uw": [_vp, _vp, _vp, _vp, _vp, _int, _vp, _vp],
     # trades_out, trade_hist_out, trade_sum_out, n_trade_levels, trade_levels, trade_q_out, turnover_out, turnover_stats_out
@@ -342,6 +349,14 @@ UNDERWATER_ENTRIES = {name: tuple(groups.split()) for name, groups in UNDERWATER
 UNDERWATER_SIGNATURES = {}
 UNDERWATER_SIGNATURES.update((name, (_int, [t for g in groups for t in ARG_GROUPS[g]])) for name, groups in UNDERWATER_ENTRIES.items())
 
+# And for include/mcport_uncertain.h (SPEC.md 2.7 / 4.21 / 5.21).
+UNCERTAIN_ENTRIES = {
+    "mcp_simulate_uncertain": "ctx prm du cf mu chol W walk hz_in out dd counts hz_out hz_counts",
+}
+UNCERTAIN_ENTRIES = {name: tuple(groups.split()) for name, groups in UNCERTAIN_ENTRIES.items()}
+UNCERTAIN_SIGNATURES = {}
+UNCERTAIN_SIGNATURES.update((name, (_int, [t for g in groups for t in ARG_GROUPS[g]])) for name, groups in UNCERTAIN_ENTRIES.items())
+
 _LIB = None
 
 
@@ -407,7 +422,8 @@ def lib() -> ctypes.CDLL:
             fn.restype = res
             fn.argtypes = args
         for name, (res, args) in list(EXTENSION_SIGNATURES.items()) + list(SPEND_SIGNATURES.items()) + list(LIFE_SIGNATURES.items()) + \
-                list(BAND_SIGNATURES.items()) + list(VOLTARGET_SIGNATURES.items()) + list(UNDERWATER_SIGNATURES.items()):
+                list(BAND_SIGNATURES.items()) + list(VOLTARGET_SIGNATURES.items()) + list(UNDERWATER_SIGNATURES.items()) + \
+                list(UNCERTAIN_SIGNATURES.items()):
             fn = getattr(L, name)          # additive entry points, detected by symbol: a library without them is too old
             fn.restype = res
             fn.argtypes = args
@@ -696,6 +712,15 @@ def band_reviews(n_steps: int, every: int) -> int:
     """n_reviews of SPEC.md 4.18 (include/mcport_band.h, mcp_band_reviews), pure host arithmetic."""
     n = lib().mcp_band_reviews(ctypes.byref(McpParams(n_steps=int(n_steps))), ctypes.byref(McpBand(int(every), 0, 0.0, None)))
     return check(n)
+
+
+def make_drift_uncertainty(factor: np.ndarray) -> McpDriftUncertainty:
+    """mcp_drift_uncertainty over the binary32 factor M [N, N] of SPEC.md 4.21 (include/mcport_uncertain.h); the array is kept on the
+    struct."""
+    m = np.ascontiguousarray(factor, np.float32)
+    du = McpDriftUncertainty(m.ctypes.data, 0)
+    du._keep = m
+    return du
 
 
 def make_vol_target(target: float, decay: float, cap: float = 1.0, rate: float = 0.0, spread: float = 0.0, s0=None,

@@ -35,11 +35,12 @@ template <class T> static bool finite(const std::vector<T>& v) {
 // must carry, and the request of one combination of features over them.
 enum Bit { B_DD = 1, B_HZ = 2, B_REB = 4, B_BAND = 8, B_CASH = 16, B_GLIDE = 32, B_SPEND = 64, B_LIFE = 128, B_PROTECT = 256, B_OVERLAY = 512,
            B_GARCH = 1024, B_JUMPS = 2048, B_REGIMES = 4096, B_ANTI = 8192, B_ATTR = 16384, B_VT = 32768, B_UW = 65536, N_BITS = 17 };
+enum { B_PU = 1 << N_BITS, N_BITS_PU = N_BITS + 1 };     // SPEC.md 4.21: the per-path drift, the bit behind them (131072; 18 bits in all)
 struct Payloads {
   static constexpr int G = 2, H = 2;
   const int N, K, T, R;
   const int32_t steps[H], breaks[G] = {3, 7};
-  std::vector<float> mu, mu1, chol, chol1, W, rows, shock, loading, targets, flows, zero_flows, floor_s, spot, tol;
+  std::vector<float> mu, mu1, chol, chol1, W, rows, shock, loading, targets, flows, zero_flows, floor_s, spot, tol, drift_m;
   std::vector<int32_t> row_begin;
   const std::vector<mcp_overlay_row> ov_rows;
   mcp_bootstrap boot;
@@ -57,6 +58,7 @@ struct Payloads {
   mcp_band bd;
   mcp_rebalance bd_reb;
   const mcp_spending sp = {0.01, 0.1, HUGE_VAL, 0.02, 0.015, 0.9, 5, 1, 1, 0};
+  mcp_drift_uncertainty du;
   std::vector<mcp_stats> stats, hz_stats, second_stats;
   std::vector<uint64_t> counts, hz_counts, trade_hist, life_hist, uw_longest_hist, uw_current_hist, attr_counts;
   std::vector<mcp_attr> attr;
@@ -65,7 +67,7 @@ struct Payloads {
   Payloads(int N_, int K_, int T_, int R_)
       : N(N_), K(K_), T(T_), R(R_), steps{1, T_}, mu(N), mu1(N), chol((size_t)N * N, 0.0f), chol1((size_t)N * N, 0.0f), W((size_t)K * N),
         rows((size_t)R * N), shock(R), loading(N), targets((size_t)G * K * N), flows(T, -0.01f), zero_flows(T, 0.0f), floor_s(T + 1),
-        spot(N, 100.0f), tol((size_t)K * N, 0.05f), row_begin(N + 1, 1), ov_rows(1, mcp_overlay_row{MCP_OVERLAY_PUT, 95.0f, 1.0f, 0.01f}),
+        spot(N, 100.0f), tol((size_t)K * N, 0.05f), drift_m((size_t)N * N, 0.0f), row_begin(N + 1, 1), ov_rows(1, mcp_overlay_row{MCP_OVERLAY_PUT, 95.0f, 1.0f, 0.01f}),
         stats(K), hz_stats((size_t)H * K), second_stats(K), counts(2 * (size_t)K), hz_counts(2 * (size_t)H * K),
         trade_hist((size_t)K * ((size_t)(T - 1) / 5 + 1)), life_hist((size_t)K * ((size_t)T + 1)), uw_longest_hist((size_t)K * ((size_t)T + 1)),
         uw_current_hist((size_t)K * ((size_t)T + 1)), attr_counts(2 * (size_t)K),
@@ -76,6 +78,7 @@ struct Payloads {
       loading[i] = 0.5f + 0.5f * (float)(i & 1);
       for (int j = 0; j <= i; j++) chol[(size_t)i * N + j] = i == j ? 0.01f : 0.001f;
       for (int j = 0; j <= i; j++) chol1[(size_t)i * N + j] = 3.0f * chol[(size_t)i * N + j];
+      for (int j = 0; j <= i; j++) drift_m[(size_t)i * N + j] = i == j ? 0.002f : -0.0005f;
     }
     for (size_t i = 0; i < W.size(); i++) W[i] = (1.0f + 0.1f * (float)(i % 3)) / (float)N;
     for (size_t i = 0; i < targets.size(); i++) targets[i] = (1.0f + 0.1f * (float)(i % 5)) / (float)N;
@@ -95,6 +98,7 @@ struct Payloads {
     ov = {ov_rows.data(), row_begin.data(), spot.data(), 1, 0};
     bd = {5, 0, 0.001, tol.data()};
     bd_reb = {bd.every, 0, bd.cost};
+    du = {drift_m.data(), 0};
   }
   Payloads(const Payloads&) = delete;
 
@@ -117,6 +121,7 @@ struct Payloads {
     if (bits & B_PROTECT) { rq.protect = true; rq.pi = &pt; }
     if (bits & B_VT) { rq.vol_target = true; rq.vt = &vt; rq.exposure_stats_out = (bits & B_DD) ? nullptr : second_stats.data(); }
     if (bits & B_UW) { rq.underwater = true; rq.uw_longest_hist_out = uw_longest_hist.data(); rq.uw_current_hist_out = uw_current_hist.data(); }
+    if (bits & B_PU) { rq.uncertain = true; rq.du = &du; }
     if (bits & B_OVERLAY) { rq.overlay = true; rq.ov = &ov; }
     if (bits & B_GARCH) { rq.garch = true; rq.gv = &gv; }
     if (bits & B_JUMPS) { rq.jumps = true; rq.jp = &jp; }
@@ -129,13 +134,14 @@ struct Payloads {
 };
 
 enum Feature { PLAIN, BOOT, FILTERED, JUMPS, REGIMES, GLIDE_CF, GLIDE, PROTECT, CASH, OVERLAY, SPEND, SPEND_BOOT, BAND, BAND_BOOT, VOL_TARGET, UNDERWATER,
-               N_FEATURES };
+               UNCERTAIN, UNCERTAIN_CASH, N_FEATURES };
 static const struct { const char* name; Source src; int bits; } k_features[N_FEATURES] = {
     {"plain", SRC_GAUSS, 0}, {"bootstrap", SRC_BOOT, 0}, {"filtered", SRC_FHS, 0}, {"jumps", SRC_GAUSS, B_JUMPS}, {"regimes", SRC_GAUSS, B_REGIMES},
     {"glide+flows", SRC_GAUSS, B_CASH | B_GLIDE}, {"glide", SRC_GAUSS, B_CASH | B_GLIDE}, {"protect", SRC_GAUSS, B_PROTECT},
     {"cash", SRC_GAUSS, B_CASH}, {"overlay", SRC_GAUSS, B_OVERLAY}, {"spend", SRC_GAUSS, B_CASH | B_SPEND},
     {"spend+bootstrap", SRC_BOOT, B_CASH | B_SPEND}, {"band", SRC_GAUSS, B_REB | B_BAND}, {"band+bootstrap", SRC_BOOT, B_REB | B_BAND},
-    {"vol_target", SRC_GAUSS, B_VT}, {"underwater", SRC_GAUSS, B_DD | B_UW}};
+    {"vol_target", SRC_GAUSS, B_VT}, {"underwater", SRC_GAUSS, B_DD | B_UW},
+    {"uncertain", SRC_GAUSS, B_PU}, {"uncertain+flows", SRC_GAUSS, B_PU | B_CASH}};
 
 static void run_shape(int N, int K, int T, int H) {
   Payloads p(N, K, T, 6);
@@ -238,7 +244,7 @@ static void run_shape(int N, int K, int T, int H) {
       const Counted cnt = counted_of(&prm, lr);
       if (rq.cash) EXPECT(cnt.on && cnt.bins == (size_t)T + 1 && cnt.bins == count_bins(&prm, lr) && cnt.out == record.data() && cnt.hist_out == lh.data());
       lr.life_out = nullptr;
-      EXPECT(check_request(&prm, lr, 4) == (rq.cash ? MCP_OK : MCP_E_UNSUPPORTED));
+      EXPECT(check_request(&prm, lr, 4) == (rq.cash && !rq.uncertain ? MCP_OK : MCP_E_UNSUPPORTED));   // SPEC.md 4.21: not with the per-path drift
       lr.life_hist_out = nullptr;
       EXPECT(check_request(&prm, lr, 4) == (rq.cash ? MCP_E_ARG : MCP_E_UNSUPPORTED));
     }
@@ -298,6 +304,50 @@ static void run_shape(int N, int K, int T, int H) {
       ur.jp = &p.jp;
       EXPECT(check_request(&prm, ur, 4) == MCP_E_UNSUPPORTED);
     }
+    if (rq.uncertain) {                   // SPEC.md 4.21: the struct's rules, the refusals, M behind the block, never the lean step loop
+      Request ur = rq;
+      ur.du = nullptr;
+      EXPECT(check_request(&prm, ur, 4) == MCP_E_ARG);
+      mcp_drift_uncertainty bad_du = p.du;
+      ur.du = &bad_du;
+      bad_du.factor = nullptr;
+      EXPECT(check_request(&prm, ur, 4) == MCP_E_ARG);
+      bad_du = p.du;
+      bad_du.reserved = 1;
+      EXPECT(check_request(&prm, ur, 4) == MCP_E_ARG);
+      std::vector<float> inf_m(p.drift_m);
+      inf_m.back() = HUGE_VALF;
+      bad_du = {inf_m.data(), 0};
+      EXPECT(check_request(&prm, ur, 4) == MCP_E_ARG);
+      inf_m.back() = NAN;
+      EXPECT(check_request(&prm, ur, 4) == MCP_E_ARG);
+      std::vector<float> zero_m(p.drift_m.size(), 0.0f);
+      bad_du = {zero_m.data(), 0};
+      EXPECT(check_request(&prm, ur, 4) == MCP_OK);        // all-zero is allowed
+      mcp_params lg = prm;
+      lg.compounding = MCP_COMPOUND_LOG;
+      EXPECT(check_request(&lg, rq, 4) == (rq.cash ? MCP_E_UNSUPPORTED : MCP_OK));
+      mcp_params fold = prm;
+      fold.flags = MCP_FLAG_FOLD;
+      EXPECT(check_request(&fold, rq, 4) == MCP_E_UNSUPPORTED);
+      ur = rq;
+      ask_drawdown(ur, nullptr, p.second_stats.data());
+      EXPECT(check_request(&prm, ur, 4) == (H || rq.cash ? MCP_E_UNSUPPORTED : MCP_OK));
+      ur = rq;
+      ur.garch = true;
+      ur.gv = &p.gv;
+      EXPECT(check_request(&prm, ur, 4) == MCP_E_UNSUPPORTED);
+      ur = rq;
+      ur.src = SRC_T;
+      ur.st = &p.st;
+      EXPECT(check_request(&prm, ur, 4) == MCP_E_UNSUPPORTED);
+      const TileLayout lay = tile_layout(&prm, rq, K);
+      EXPECT(lay.floor - lay.load == drift_len(N) && lay.total == lay.floor);
+      for (uint64_t begin : {(uint64_t)0, ((uint64_t)1 << 32) - 2}) {
+        const mcp::PathKernel k = route_kernel(&prm, rq, false, begin, 4);
+        EXPECT((k.flags & mcp::PK_PU) && !(k.flags & mcp::PK_UHI));
+      }
+    }
     if (rq.band) {                        // SPEC.md 4.18: a negative entry, a missing histogram, and the size of the histogram
       Request br = rq;
       std::vector<float> neg(p.tol);
@@ -343,6 +393,7 @@ static void run_shape(int N, int K, int T, int H) {
     if (f == PLAIN) bad.flags = MCP_FLAG_FOLD | MCP_FLAG_NATIVE_MATH;      // the folded step needs the spec's normals
     else if (f == BOOT) { bad_boot.mean_block = 0.5; rq.boot = &bad_boot; }  // the bootstrap compounds either way; b < 1 does not
     else if (f == UNDERWATER) bad.flags = MCP_FLAG_NATIVE_MATH;          // the drawdown walk runs on the spec's normals
+    else if (f == UNCERTAIN) bad.flags = MCP_FLAG_NATIVE_MATH;           // the per-path drift compounds either way, on the spec's normals only
     else bad.compounding = MCP_COMPOUND_LOG;                              // every other feature compounds simply
     EXPECT(check_request(&bad, rq, 4) == (f == BOOT ? MCP_E_ARG : MCP_E_UNSUPPORTED) && mcp_last_error()[0] != '\0');
   }
@@ -478,7 +529,11 @@ static void for_each_request(Visit&& visit) {
     while (mcp::filt_fits_lds((uint64_t)r_filt, nb)) r_filt++;
     Payloads fits(N, K, T, 8), big_boot(N, K, T, r_boot), big_filt(N, K, T, r_filt);
     for (int src = SRC_GAUSS; src <= SRC_FHS; src++)
-      for (int bits = 0; bits < 1 << N_BITS; bits++) {
+      for (int bits = 0; bits < 1 << N_BITS_PU; bits++) {
+        // SPEC.md 4.21: the per-path drift comes with every set of up to three other features -- what it combines with (the drawdown,
+        // horizons, cash flows) has no larger set, and every other feature is refused alone and in every pair and triple; the larger
+        // sets would double the run for refusals that the rule's one sentence already states
+        if ((bits & B_PU) && __builtin_popcount((unsigned)(bits & ~B_PU)) > 3) continue;
         const Request rq = fits.request((Source)src, bits);
         for (int compounding : {MCP_COMPOUND_SIMPLE, MCP_COMPOUND_LOG})
           for (int flags : {0, (int)MCP_FLAG_NATIVE_MATH, (int)MCP_FLAG_FOLD, MCP_FLAG_NATIVE_MATH | MCP_FLAG_FOLD}) {
@@ -530,11 +585,11 @@ static const Row* select_row(int nb, const mcp::PathKernel& k, int* n_out = null
 
 static long run_routes() {
   using namespace mcp;
-  // (d) the table: 86 rows for NB <= LEAN_MAX_NB (the two lean kernels), 84 above; at KT = 8 without the folded step, the lean kernels,
+  // (d) the table: 93 rows for NB <= LEAN_MAX_NB (the two lean kernels), 91 above; at KT = 8 without the folded step, the lean kernels,
   // the bands and the attribution
   for (int nb : {1, 4, 5, 16}) {
     snprintf(g_case, sizeof g_case, "row counts, nb=%d", nb);
-    EXPECT(rows_at(nb, false).size() == (nb <= LEAN_MAX_NB ? 86u : 84u) && rows_at(nb, true).size() == 78u);
+    EXPECT(rows_at(nb, false).size() == (nb <= LEAN_MAX_NB ? 93u : 91u) && rows_at(nb, true).size() == 85u);
   }
   // (a) every accepted request has exactly one row; (b) its selector is canonical: with any one flag set or cleared it is another
   // kernel's or nobody's -- under equality that is (a) again, asserted all the same, once per selector and nb; (c) every row is
@@ -554,7 +609,7 @@ static long run_routes() {
       int n = 0;
       const Row* row = select_row(nb, k, &n);
       EXPECT(n == 1);
-      for (int b = 0; b < N_PATH_FLAGS; b++) {
+      for (int b = 0; b < N_PATH_FLAGS_PU; b++) {
         const PathKernel other = {k.family, k.flags ^ (1u << b)};
         EXPECT(select_row(nb, other) != row);               // PK_KT8: the row of the table at the other KT, another kernel
       }
@@ -623,6 +678,13 @@ static void run_named_routes() {
       {"under water, Student-t", SRC_T, B_DD | B_UW, MCP_COMPOUND_SIMPLE, 0, 1, 16, 0, false, "mc_paths_g_uw_kernel<NB, KT, 1>"},
       {"under water, GARCH", SRC_GAUSS, B_DD | B_UW | B_GARCH, MCP_COMPOUND_SIMPLE, 0, 2, 16, 0, false, "mc_paths_g_uw_kernel<NB, KT, 1>"},
       {"under water, jumps", SRC_GAUSS, B_DD | B_UW | B_JUMPS, MCP_COMPOUND_SIMPLE, 0, 1, 16, 0, false, "mc_paths_j_uw_kernel<NB, KT, 1>"},
+      {"uncertain: never the lean kernel", SRC_GAUSS, B_PU, MCP_COMPOUND_SIMPLE, 0, 1, 16, 0, false, "mc_paths_pu_kernel<NB, KT, 1, false>"},
+      {"uncertain, log, K = 2", SRC_GAUSS, B_PU, MCP_COMPOUND_LOG, 0, 2, 17, 0, false, "mc_paths_pu_kernel<NB, KT, 1, true>"},
+      {"uncertain, drawdown", SRC_GAUSS, B_PU | B_DD, MCP_COMPOUND_SIMPLE, 0, 1, 16, 0, false, "mc_paths_pu_dd_kernel<NB, KT, 1, false>"},
+      {"uncertain, drawdown, log", SRC_GAUSS, B_PU | B_DD, MCP_COMPOUND_LOG, 0, 1, 16, far, false, "mc_paths_pu_dd_kernel<NB, KT, 1, true>"},
+      {"uncertain, horizons", SRC_GAUSS, B_PU | B_HZ, MCP_COMPOUND_SIMPLE, 0, 2, 16, 0, false, "mc_paths_pu_hz_kernel<NB, KT, 1, false>"},
+      {"uncertain, horizons, log", SRC_GAUSS, B_PU | B_HZ, MCP_COMPOUND_LOG, 0, 1, 16, 0, false, "mc_paths_pu_hz_kernel<NB, KT, 1, true>"},
+      {"uncertain, cash, horizons", SRC_GAUSS, B_PU | B_CASH | B_HZ, MCP_COMPOUND_SIMPLE, 0, 1, 16, 0, false, "mc_paths_pu_cf_kernel<NB, KT, 1>"},
   };
   for (const auto& c : named) {
     snprintf(g_case, sizeof g_case, "named route: %s", c.what);

@@ -431,6 +431,24 @@ int check_vol_target(const mcp_params* prm, const mcp_vol_target* vt, const floa
   }
   return MCP_OK;
 }
+// SPEC.md 4.21: the struct, reserved == 0, and every entry of M finite (binary32 already: before and after rounding are one test)
+int check_drift_uncertainty(int n_assets, const mcp_drift_uncertainty* du) {
+  if (!du) return fail(MCP_E_ARG, "drift_uncertainty is NULL");
+  if (!du->factor) return fail(MCP_E_ARG, "drift_uncertainty factor is NULL");
+  if (du->reserved != 0) return fail(MCP_E_ARG, "drift_uncertainty reserved=%d must be 0", du->reserved);
+  for (size_t i = 0; i < (size_t)n_assets * (size_t)n_assets; i++)
+    if (!std::isfinite(du->factor[i]))
+      return fail(MCP_E_ARG, "drift_uncertainty factor, entry (%zu, %zu) is not finite", i / (size_t)n_assets, i % (size_t)n_assets);
+  return MCP_OK;
+}
+size_t drift_len(int N) { const size_t n4 = (size_t)n4_of(N); return n4 * (n4 / 2 + 1); }
+// M's lower triangle as mcp_pack_params lays out the Cholesky factor: pair m = rows (2m, 2m+1) at offset 2m(m+1), columns j = 0 ..
+// 2m+1 interleaved as (M[2m][j], M[2m+1][j]); the padding and M[2m][2m+1] are +0; -0 -> +0
+void drift_pack(int N, const mcp_drift_uncertainty* du, float* out) {
+  std::fill(out, out + drift_len(N), 0.0f);
+  for (int i = 0; i < N; i++)
+    for (int j = 0; j <= i; j++) out[2 * (i / 2) * (i / 2 + 1) + 2 * j + (i & 1)] = du->factor[(size_t)i * N + j] + 0.0f;
+}
 // SPEC.md 4.16: the binary32 constants of a spending request; w0 without `first` is fl32(p32 fl32(v0)), the product in binary64 (exact)
 SpendConsts spend_consts(const mcp_spending* sp, double v0) {
   const float p = (float)sp->rate;
@@ -749,6 +767,17 @@ int check_request(const mcp_params* prm, const Request& rq, uint64_t n_paths, co
                                      "attribution, antithetic pairs or horizons");
     if (ln) return fail(MCP_E_UNSUPPORTED, "the time under water is not wired into mcp_launch_paths*");
   }
+  if (rq.uncertain) {                                          // SPEC.md 4.21: the factor, then what the per-path drift is not combined with
+    if ((rc = check_drift_uncertainty(prm->n_assets, rq.du))) return rc;
+    if (prm->flags & (MCP_FLAG_FOLD | MCP_FLAG_NATIVE_MATH))
+      return fail(MCP_E_UNSUPPORTED, "paths with drift uncertainty run on the unfolded recurrence and the spec's normals (no MCP_FLAG_FOLD / MCP_FLAG_NATIVE_MATH)");
+    if (rq.src != SRC_GAUSS || rq.st || rq.garch || rq.jumps || rq.regimes || rq.rebalanced || rq.band || rq.glide || rq.spend || rq.life ||
+        rq.protect || rq.vol_target || rq.overlay || rq.attr || rq.anti || rq.underwater)
+      return fail(MCP_E_UNSUPPORTED, "drift uncertainty is not combined with Student-t draws, GARCH, jumps, regimes, bootstrap or filtered rows, "
+                                     "rebalancing, tolerance bands, glide paths, spending rules, the lifetime, floor protection, volatility "
+                                     "targeting, the overlay, the attribution, antithetic pairs or the time under water");
+    if (ln) return fail(MCP_E_UNSUPPORTED, "drift uncertainty is not wired into mcp_launch_paths*");
+  }
   if (rq.overlay && (rc = check_overlay(prm, rq.ov))) return rc;
   if (rq.garch && (rc = check_garch(prm, rq.gv))) return rc;
   if (rq.jumps && (rc = check_jumps(prm->n_assets, rq.jp))) return rc;
@@ -920,6 +949,7 @@ mcp::PathKernel route_kernel(const mcp_params* prm, const Request& rq, bool attr
     k.flags |= PK_UW;                     // request shares the GARCH walk
     if (k.flags & PK_STT) k.flags = share_garch_walk(k.flags);
   }
+  if (rq.uncertain) k.flags |= PK_PU;     // SPEC.md 4.21: the request's own family; the flag also keeps the launch off the lean step loop below
   if (rq.band) k.flags |= PK_TB;          // SPEC.md 4.18: B is per portfolio, so every portfolio of a banded call is a pass of its own
   if (prm->n_portfolios > 1 && !rq.band) k.flags |= PK_KT8;
   if (prm->flags & MCP_FLAG_NATIVE_MATH) k.flags |= PK_NATIVE;
@@ -1126,7 +1156,8 @@ void vol_target_pivots(const mcp_params& prm, const mcp_vol_target* vt, const fl
 }
 
 // What follows the packed block of a tile of kt portfolios.  Jumps: the [N4] loadings; regimes: [mu1][L1 row pairs]; glide path: the
-// target blocks of the tile's portfolios; bands: the tolerance table and the masks (check_request lets at most one of the four through).  Protection: behind them the floor
+// target blocks of the tile's portfolios; bands: the tolerance table and the masks; drift uncertainty: M in the factor's row-pair layout
+// (check_request lets at most one of the five through).  Protection: behind them the floor
 // schedule and the counts' thresholds (protect_pack), or, volatility target, s0 of the tile's portfolios padded with ones to whole
 // passes of 8.
 TileLayout tile_layout(const mcp_params* prm, const Request& rq, int kt) {
@@ -1134,7 +1165,7 @@ TileLayout tile_layout(const mcp_params* prm, const Request& rq, int kt) {
   TileLayout t;
   t.base = t.load = mcp_packed_len(N, kt);
   t.floor = t.load + (rq.jumps ? (size_t)n4_of(N) : rq.regimes ? regime_block_len(N) : rq.glide ? glide_len(N, kt, rq.gl)
-                       : rq.band ? band_len(N, kt) : 0);
+                       : rq.band ? band_len(N, kt) : rq.uncertain ? drift_len(N) : 0);
   t.total = t.floor + (rq.protect ? protect_len(prm->n_steps, kt, rq.hz ? rq.H : 0)
                        : rq.vol_target ? (size_t)KT_WIDE * (size_t)((kt + KT_WIDE - 1) / KT_WIDE) : 0);
   return t;
@@ -1172,6 +1203,7 @@ int pack_tile(const mcp_params* prm, const Request& rq, const TileInputs& in, in
   if (rq.regimes) std::copy(in.blk1.begin(), in.blk1.begin() + (ptrdiff_t)regime_block_len(N), load);
   if (rq.glide) glide_pack(N, prm->n_portfolios, k0, kt, rq.gl, load);
   if (rq.band) band_pack(N, k0, kt, rq.bd, load);
+  if (rq.uncertain) drift_pack(N, rq.du, load);
   if (rq.protect) protect_pack(prm->n_steps, kt, H, rq.steps, rq.pi, out + lay.floor);
   for (size_t k = 0; rq.vol_target && k < lay.total - lay.floor; k++)
     out[lay.floor + k] = k < (size_t)kt ? vol_target_s0(N, rq.vt, rq.chol, rq.W, k0 + (int)k) : 1.0f;

@@ -15,6 +15,7 @@
 #include "../../include/mcport_band.h"
 #include "../../include/mcport_voltarget.h"
 #include "../../include/mcport_underwater.h"
+#include "../../include/mcport_uncertain.h"
 #include "mcp_route.h"
 
 namespace mcp {
@@ -75,7 +76,9 @@ struct Request {
   bool dd = false;                      // SPEC.md 4.2 / 5.1: the drawdown of every path
   bool underwater = false;              // SPEC.md 4.20 / 5.20: the longest and the current spell under water, always with `dd`
                                         // (mcp_simulate_underwater)
-  bool hz = false;                      // SPEC.md 4.3 / 5.2: the values after H steps, statistics at alpha and at L levels
+  bool uncertain = false;               // SPEC.md 2.7 / 4.21: the drift of every path drawn once, m = mu + M g, on top of SRC_GAUSS
+  const mcp_drift_uncertainty* du = nullptr;   // (mcp_simulate_uncertain)
+  bool hz = false;                     // SPEC.md 4.3 / 5.2: the values after H steps, statistics at alpha and at L levels
   int H = 0, L = 0;
   const int32_t* steps = nullptr;
   const double* levels = nullptr;
@@ -145,7 +148,8 @@ struct Launch {
   const char* d_overlay = nullptr;      // overlay: [rows][row_begin N4 + 1][spot N4] (overlay_pack)
   const float* d_loading = nullptr;     // jumps: [N4] loadings, zero-padded
   const float* d_block1 = nullptr;      // regimes: [mu1 N4][L1 row pairs], the layout of mcp_pack_params
-  bool attr = false;                    // the attribution walk (SPEC.md 4.10): FAM_AT instead of the request's own family
+  const float* d_drift = nullptr;       // drift uncertainty: [N4 (N4/2 + 1)] M in the factor's row-pair layout (drift_pack)
+  bool attr = false;                   // the attribution walk (SPEC.md 4.10): FAM_AT instead of the request's own family
   const double* d_var = nullptr;        // attribution: [K] VaRs
   double* d_cross = nullptr;            // antithetic pairs: [K][path_grid(n_paths / 2)] cross partials
   double* d_attr_partials = nullptr;    // attribution: [K][path_grid(n_paths)][attr_record_len(N4)]
@@ -175,6 +179,7 @@ int check_overlay(const mcp_params* prm, const mcp_overlay* ov);
 int check_band(const mcp_params* prm, const mcp_band* bd);
 // `chol`, `W`: what the default s0_k is formed from (read only when vt->s0 is NULL)
 int check_vol_target(const mcp_params* prm, const mcp_vol_target* vt, const float* chol, const float* W);
+int check_drift_uncertainty(int n_assets, const mcp_drift_uncertainty* du);
 // Every rule a request meets: each feature's own arguments, then which features combine (MCP_E_UNSUPPORTED), then the outputs.
 // `ln`: an mcp_launch_paths* call, whose device arrays are checked instead of the host arrays of an mcp_simulate* call.
 int check_request(const mcp_params* prm, const Request& rq, uint64_t n_paths, const Launch* ln = nullptr, uint64_t path_begin = 0);
@@ -241,6 +246,9 @@ size_t band_len(int N, int kt);
 void band_pack(int N, int k0, int kt, const mcp_band* bd, float* out);
 size_t protect_len(int T, int kt, int H);
 void protect_pack(int T, int kt, int H, const int32_t* steps, const mcp_protect* pt, float* out);
+// SPEC.md 4.21: M's lower triangle in the row-pair layout of the Cholesky factor (mcp_pack_params), every entry through + 0.0f
+size_t drift_len(int N);
+void drift_pack(int N, const mcp_drift_uncertainty* du, float* out);
 size_t overlay_bytes(int N, int n_rows);
 void overlay_pack(int N, const mcp_overlay* ov, char* out);
 
@@ -248,7 +256,7 @@ void overlay_pack(int N, const mcp_overlay* ov, char* out);
 // Float offsets into the parameter block of a tile.  This is the only place that knows what follows the packed block.
 struct TileLayout {
   size_t base;     // mcp_packed_len(N, kt): the end of the packed block
-  size_t load;     // where the jump loadings, the regime-1 block, the glide targets or the tolerance table begin
+  size_t load;     // where the jump loadings, the regime-1 block, the glide targets, the tolerance table or the drift factor M begin
   size_t floor;    // where the protection schedule and the counts' thresholds begin (protect_pack), or the volatility target's s0
   size_t total;    // floats of the whole block
 };

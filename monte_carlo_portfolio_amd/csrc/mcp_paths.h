@@ -71,6 +71,12 @@
 #define MCP_MIN_WAVES_ANTI 5 // the antithetic kernels (N <= 16, one portfolio) carry the second member's V, row-pair accumulator and rho (and
                             // peak and drawdown) next to the first's: see profiles/antithetic_isa.txt
 #endif
+#ifndef MCP_MIN_WAVES_PU
+#define MCP_MIN_WAVES_PU 5  // the drift-uncertainty kernels (N <= 16, one portfolio) hold the path's own drift, N4 registers, on top of their
+#endif                      // twins' state, as the rebalancing kernel holds B: 5 waves (<= 96 VGPRs), no scratch in a walk (profiles/uncertain_isa.txt)
+#ifndef MCP_MIN_WAVES_PU8
+#define MCP_MIN_WAVES_PU8 4 // the same for 8 portfolios, N <= 16: 4 waves (<= 128 VGPRs), no scratch in a walk
+#endif
 #ifndef MCP_MIN_WAVES_UW8
 #define MCP_MIN_WAVES_UW8 4 // the under-water twins for 8 portfolios, N <= 16, simple compounding, 16 counters on top of the drawdown kernel's
                             // state: unbounded the Gaussian twin took 129 VGPRs at N = 16 and the jump twin 134 (3 waves) where their parents
@@ -119,7 +125,7 @@ __device__ __forceinline__ const __attribute__((address_space(4))) A* kernarg() 
 MCP_HAS_MEMBER(hz) MCP_HAS_MEMBER(mdd) MCP_HAS_MEMBER(bt) MCP_HAS_MEMBER(st) MCP_HAS_MEMBER(gv) MCP_HAS_MEMBER(cf)
 MCP_HAS_MEMBER(ov) MCP_HAS_MEMBER(at) MCP_HAS_MEMBER(period) MCP_HAS_MEMBER(pr)
 MCP_HAS_MEMBER(fh) MCP_HAS_MEMBER(p_hi) MCP_HAS_MEMBER(jp) MCP_HAS_MEMBER(rs) MCP_HAS_MEMBER(gp)
-MCP_HAS_MEMBER(pi) MCP_HAS_MEMBER(sp) MCP_HAS_MEMBER(lf) MCP_HAS_MEMBER(tb) MCP_HAS_MEMBER(vt) MCP_HAS_MEMBER(uw)
+MCP_HAS_MEMBER(pi) MCP_HAS_MEMBER(sp) MCP_HAS_MEMBER(lf) MCP_HAS_MEMBER(tb) MCP_HAS_MEMBER(vt) MCP_HAS_MEMBER(uw) MCP_HAS_MEMBER(pu)
 #undef MCP_HAS_MEMBER
 
 struct PathArgs {
@@ -494,6 +500,25 @@ __device__ __forceinline__ cunderwater_p underwater_args(const A&) {
   else return nullptr;
 }
 
+// Drift uncertainty (SPEC.md 2.7 / 4.21): every path draws its own drift once, before step 0 -- nb Philox blocks on counter stream 5
+// give g, and m_i = mu_i, then m_i = fma(M[i,j], g_j, m_i) for j = 0 .. i -- and every step of the path starts row i of its chain at
+// m_i.  `factor` is M in the row-pair layout of the Cholesky factor (mcp_pack_params), behind the launch's packed block; it is read
+// through the kernel arguments where it is used, by scalar loads, once per tile, and nothing of it is held across the walk.
+struct DriftArgs {
+  const float* __restrict__ factor;   // [N4 (N4/2 + 1)] device copy
+};
+// Arguments of the mc_paths_pu_* kernels: those of the plain, drawdown, horizon and cash-flow kernels and the drift block behind them.
+struct PathArgsPU : PathArgs { DriftArgs pu; };
+struct PathArgsPUDD : PathArgsDD { DriftArgs pu; };
+struct PathArgsPUHZ : PathArgsHZ { DriftArgs pu; };
+struct PathArgsPUCF : PathArgsCF { DriftArgs pu; };
+template <class A>
+__device__ __forceinline__ const __attribute__((address_space(4))) float* drift_factor(const A&) {
+  typedef const __attribute__((address_space(4))) float* cfactor_p;
+  if constexpr (has_pu<A>::value) return (cfactor_p)kernarg<A>()->pu.factor;
+  else return nullptr;
+}
+
 // The option overlay of SPEC.md 4.8: per asset a run of rows (kind, strike, premium, qty) that turns the raw return r_i of a step
 // into the strategy's return r'_i at the asset's price level P_i.  rows, row_begin [N4 + 1] (assets >= N own no rows) and spot [N4]
 // are device copies; bit i of `mask` is set when asset i owns rows.
@@ -562,6 +587,7 @@ struct PathLaunchArgs {
   BandArgs tb;
   VolTargetArgs vt;
   UnderwaterArgs uw;
+  DriftArgs pu;
 };
 template <class A>
 inline A make_args(const PathLaunchArgs& s) {
@@ -587,6 +613,7 @@ inline A make_args(const PathLaunchArgs& s) {
   if constexpr (has_tb<A>::value) x.tb = s.tb;
   if constexpr (has_vt<A>::value) x.vt = s.vt;
   if constexpr (has_uw<A>::value) x.uw = s.uw;
+  if constexpr (has_pu<A>::value) x.pu = s.pu;
   if constexpr (has_p_hi<A>::value) { x.p_hi = (uint32_t)(s.hz.path_begin >> 32); x.pad = 0u; }
   return x;
 }
@@ -695,20 +722,24 @@ constexpr int PATH_BLOCK = 256;
 // exposure Y; the update of V holds the exposure e = fminf(tgt / sqrtf(s), b) in the risky portfolio, the rest at the riskless rate, what
 // is borrowed at the spread on top, ruin absorbing; s then moves on the step's rho (SPEC.md 4.19).  UW (with DD): behind the update of the
 // peak the step also counts the current spell below it and keeps the longest, one compare against the peak just written, one add, one
-// select and one integer max per path and portfolio; both counters are stored next to V_T (SPEC.md 4.20).  Every kernel
+// select and one integer max per path and portfolio; both counters are stored next to V_T (SPEC.md 4.20).  PU: before step 0 every path
+// draws its own drift m = mu + M g from nb Philox blocks on counter stream 5 and holds it in N4 registers across the walk; every step's
+// row pair starts from the path's m pair instead of the launch's drift, and nothing else in the step changes (SPEC.md 2.7 / 4.21).  Every kernel
 // below is the body in mcp_paths_body.inc under its own flags F: it names the flags it sets, the rest are PathFlagsOff's.  F is a
 // local class, which may not have static data members, so it sets its flags as enumerators of an `enum : bool`; they hide the
 // defaults' names and read as the same constant expressions.
 struct PathFlagsOff {
   static constexpr bool NATIVE = false, FOLD = false, LOGC = false, DD = false, HZ = false, BOOT = false, BLDS = false, REB = false,
                         STT = false, CF = false, OV = false, GV = false, AT = false, ANTI = false, FH = false, UHI = false, JP = false, RS = false,
-                        GP = false, PI = false, SP = false, LT = false, TB = false, VT = false, UW = false;
+                        GP = false, PI = false, SP = false, LT = false, TB = false, VT = false, UW = false, PU = false;
 };
 
 // __launch_bounds__ 2nd argument of a path kernel: the MCP_MIN_WAVES* above for N <= 16 and one path per lane, by the kind of
 // state the kernel carries; MCP_MIN_WAVES_BIG for 16 < N <= 64 and one portfolio; otherwise unbounded.
-enum BoundsKind { BK_PATHS, BK_REB, BK_CF, BK_OV, BK_AT, BK_ANTI, BK_PI, BK_SP, BK_UW, BK_UWJ };
+enum BoundsKind { BK_PATHS, BK_REB, BK_CF, BK_OV, BK_AT, BK_ANTI, BK_PI, BK_SP, BK_UW, BK_UWJ, BK_PU };
 constexpr int min_waves(BoundsKind kind, int NB, int KT, int PPT) {
+  if (kind == BK_PU)                          // the kernels that hold the path's own drift, N4 registers on top of their twins'
+    return (NB <= 4 && PPT == 1) ? (KT == 1 ? MCP_MIN_WAVES_PU : MCP_MIN_WAVES_PU8) : (KT == 1 && PPT == 1) ? MCP_MIN_WAVES_BIG : 1;
   if (kind == BK_UW || kind == BK_UWJ) {      // the under-water twins (simple compounding); BK_UWJ: on the jump walk, which from N = 5 on
                                               // takes the protection kernel's 5 waves (at 6 the N = 16 kernel had scratch in its step loop)
     if (NB <= 4 && PPT == 1 && KT == 1) return (kind == BK_UWJ && NB >= 2) ? MCP_MIN_WAVES_PI : MCP_MIN_WAVES;
@@ -962,6 +993,33 @@ __global__ void MCP_BOUNDS(BK_UW) mc_paths_g_uw_kernel(const PathArgsGUW a) {
 template <int NB, int KT, int PPT>
 __global__ void MCP_BOUNDS(BK_UWJ) mc_paths_j_uw_kernel(const PathArgsJUW a) {
   struct F : PathFlagsOff { enum : bool { DD = true, UW = true, JP = true }; };
+#include "mcp_paths_body.inc"
+}
+
+// The drift-uncertainty kernels (SPEC.md 2.7 / 4.21; spec normals, unfolded recurrence, Gaussian draws): mc_paths_kernel,
+// mc_paths_dd_kernel and mc_paths_hz_kernel (simple or log compounding) and mc_paths_cf_kernel on Gaussian draws, each with the drift
+// of every path drawn once inside the tile loop and held in N4 registers: the step's row pairs start from it, so the drift is not
+// read from LDS.  V_T, the drawdown, the horizons, ruin and the fused epilogue as in those kernels; with M = 0 their stored values bit
+// for bit.  Launch bounds of their own (MCP_MIN_WAVES_PU, MCP_MIN_WAVES_PU8): no listing shows scratch in a loop over t
+// (profiles/uncertain_isa.txt).
+template <int NB, int KT, int PPT, bool LOGC_>
+__global__ void MCP_BOUNDS(BK_PU) mc_paths_pu_kernel(const PathArgsPU a) {
+  struct F : PathFlagsOff { enum : bool { PU = true, LOGC = LOGC_ }; };
+#include "mcp_paths_body.inc"
+}
+template <int NB, int KT, int PPT, bool LOGC_>
+__global__ void MCP_BOUNDS(BK_PU) mc_paths_pu_dd_kernel(const PathArgsPUDD a) {
+  struct F : PathFlagsOff { enum : bool { PU = true, DD = true, LOGC = LOGC_ }; };
+#include "mcp_paths_body.inc"
+}
+template <int NB, int KT, int PPT, bool LOGC_>
+__global__ void MCP_BOUNDS(BK_PU) mc_paths_pu_hz_kernel(const PathArgsPUHZ a) {
+  struct F : PathFlagsOff { enum : bool { PU = true, HZ = true, LOGC = LOGC_ }; };
+#include "mcp_paths_body.inc"
+}
+template <int NB, int KT, int PPT>
+__global__ void MCP_BOUNDS(BK_PU) mc_paths_pu_cf_kernel(const PathArgsPUCF a) {
+  struct F : PathFlagsOff { enum : bool { PU = true, HZ = true, CF = true }; };
 #include "mcp_paths_body.inc"
 }
 

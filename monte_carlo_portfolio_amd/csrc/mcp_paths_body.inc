@@ -5,7 +5,7 @@
 // derived from it) and the kernel argument `a` (PathArgs or a struct that starts with one).
   constexpr bool NATIVE = F::NATIVE, FOLD = F::FOLD, LOGC = F::LOGC, DD = F::DD, HZ = F::HZ, BOOT = F::BOOT, BLDS = F::BLDS, REB = F::REB,
                  STT = F::STT, CF = F::CF, OV = F::OV, GV = F::GV, AT = F::AT, ANTI = F::ANTI, FH = F::FH, UHI = F::UHI, JP = F::JP, RS = F::RS,
-                 GP = F::GP, PI = F::PI, SP = F::SP, LT = F::LT, TB = F::TB, VT = F::VT, UW = F::UW;
+                 GP = F::GP, PI = F::PI, SP = F::SP, LT = F::LT, TB = F::TB, VT = F::VT, UW = F::UW, PU = F::PU;
   static_assert(!UHI || (KT == 1 && PPT == 1 && !(NATIVE || FOLD || DD || HZ || BOOT || REB || STT || CF || OV || GV || AT || ANTI || FH || JP || RS || PI)),
                 "uniform high counter word: the plain Gaussian walk of one portfolio only");
   static_assert(!FH || (BOOT && HZ && !(LOGC || REB || CF || STT || GV || OV || AT || DD || PI)), "filtered rows: the bootstrap's segmented walk only");
@@ -25,6 +25,8 @@
                 "volatility targeting: the segmented GARCH or jump walk, simple compounding only");
   static_assert(!UW || (DD && !(NATIVE || FOLD || HZ || BOOT || REB || CF || OV || AT || ANTI || FH || UHI || RS || GP || PI || SP || LT || TB || VT)),
                 "time under water: the drawdown walk on Gaussian draws, the GARCH walk or the jump walk only");
+  static_assert(!PU || !(NATIVE || FOLD || UHI || BOOT || REB || STT || GV || OV || AT || ANTI || FH || JP || RS || GP || PI || SP || LT || TB || VT || UW),
+                "drift uncertainty: the Gaussian walk, its drawdown, its horizons and its cash flows on the spec's normals only");
   constexpr int N4 = 4 * NB;
   // ANTI (SPEC.md 2.3): a lane's PPT draws feed EM = 2 PPT members -- slot e < PPT walks on z[e], slot PPT + e on -z[e]; p, live and
   // the counters are per draw (a.path_begin and a.n_paths count pairs), the members 2 p and 2 p + 1 are adjacent in the output rows
@@ -156,6 +158,7 @@
     float Ty[PPT];                                        // TB: the turnover Y of SPEC.md 4.18
     float Sg[PPT][KT];                                    // VT: the variance estimate s of SPEC.md 4.19; the summed exposure is Yk (!DD only)
     uint32_t Uc[PPT][KT], Um[PPT][KT];                    // UW: the current and the longest spell under water, c and m of SPEC.md 4.20
+    f32x2 Dm[PPT][N4 / 2];                                // PU: the path's own drift m of SPEC.md 4.21, in the step's row pairs
 #pragma unroll
     for (int e = 0; e < PPT; e++) {
       p[e] = tl * tile + (uint64_t)e * PATH_BLOCK + threadIdx.x;
@@ -183,6 +186,29 @@
         for (int k = 0; k < KT; k++) {
           Sg[e][k] = s0[k];
           if constexpr (!DD) Yk[e][k] = 0.0f;
+        }
+      }
+      if constexpr (PU) {
+        // SPEC.md 2.7 / 4.21: nb Philox blocks on counter (q, 5, p_lo, p_hi) give g, normal m of block q for asset m nb + q; then
+        // m_i = mu_i and m_i = fma(M[i,j], g_j, m_i), j ascending -- the step's chain on M, row pairs by packed fma, the factor and the
+        // drift scalar loads.  Per tile, so a second grid-stride tile draws its own; g and M die here, only m lives across the walk.
+        const cfloat_p Mp = drift_factor(a);
+        float g[N4];
+#pragma unroll
+        for (int q = 0; q < NB; q++) {
+          uint32_t x[4];
+          philox4x32_10((uint32_t)q, 5u, plo[e], phi[e], ks, x);
+          block_normals<false>(x, s_tab, kc, g[0 * NB + q], g[1 * NB + q], g[2 * NB + q], g[3 * NB + q]);
+        }
+#pragma unroll
+        for (int m = 0; m < N4 / 2; m++) {
+          f32x2 c = f32x2{mu[2 * m], mu[2 * m + 1]};
+#pragma unroll
+          for (int j = 0; j <= 2 * m + 1; j++) {
+            const f32x2 l2 = {Mp[2 * m * (m + 1) + 2 * j], Mp[2 * m * (m + 1) + 2 * j + 1]};   // (M[2m][j], M[2m+1][j])
+            c = __builtin_elementwise_fma(l2, (f32x2){g[j], g[j]}, c);
+          }
+          Dm[e][m] = c;
         }
       }
       if constexpr (BOOT) jrow[e] = 0u;                   // replaced at t = 0 (a restart)

@@ -26,6 +26,9 @@ MCP_ROW(FAM_PLAIN, PK_BOOT | PK_BLDS | PK_LOGC, mc_paths_boot_kernel<NB, KT, 1, 
 MCP_ROW(FAM_PLAIN, PK_ANTI, mc_paths_anti_kernel<NB, KT, 1, false, PathArgsA>)
 MCP_ROW(FAM_PLAIN, PK_ANTI | PK_LOGC, mc_paths_anti_kernel<NB, KT, 1, true, PathArgsA>)
 MCP_ROW(FAM_PLAIN, PK_ANTI | PK_GV, mc_paths_anti_kernel<NB, KT, 1, false, PathArgsGA>)
+// ... and on a drift drawn once per path (SPEC.md 2.7 / 4.21): the spec's normals and the unfolded recurrence, never the lean step loop
+MCP_ROW(FAM_PLAIN, PK_PU, mc_paths_pu_kernel<NB, KT, 1, false>)
+MCP_ROW(FAM_PLAIN, PK_PU | PK_LOGC, mc_paths_pu_kernel<NB, KT, 1, true>)
 
 // The walk that tracks the drawdown
 MCP_ROW(FAM_DD, 0, mc_paths_dd_kernel<NB, KT, 1, false>)
@@ -47,6 +50,9 @@ MCP_ROW(FAM_DD, PK_UW, mc_paths_uw_kernel<NB, KT, 1, false>)
 MCP_ROW(FAM_DD, PK_UW | PK_LOGC, mc_paths_uw_kernel<NB, KT, 1, true>)
 MCP_ROW(FAM_DD, PK_UW | PK_GV, mc_paths_g_uw_kernel<NB, KT, 1>)
 MCP_ROW(FAM_DD, PK_UW | PK_JP, mc_paths_j_uw_kernel<NB, KT, 1>)
+// ... and the Gaussian drawdown walk on a drift drawn once per path (SPEC.md 4.21)
+MCP_ROW(FAM_DD, PK_PU, mc_paths_pu_dd_kernel<NB, KT, 1, false>)
+MCP_ROW(FAM_DD, PK_PU | PK_LOGC, mc_paths_pu_dd_kernel<NB, KT, 1, true>)
 
 // The walk in segments between horizons.  The filtered rows, and the protection and the volatility target without a drawdown, run
 // here with or without horizons (H = 0: one segment).
@@ -69,6 +75,8 @@ MCP_ROW(FAM_HZ, PK_PI | PK_GV, mc_paths_pi_kernel<NB, KT, 1, false, false>)
 MCP_ROW(FAM_HZ, PK_PI | PK_JP, mc_paths_pi_kernel<NB, KT, 1, true, false>)
 MCP_ROW(FAM_HZ, PK_VT | PK_GV, mc_paths_vt_kernel<NB, KT, 1, false, false>)
 MCP_ROW(FAM_HZ, PK_VT | PK_JP, mc_paths_vt_kernel<NB, KT, 1, true, false>)
+MCP_ROW(FAM_HZ, PK_PU, mc_paths_pu_hz_kernel<NB, KT, 1, false>)
+MCP_ROW(FAM_HZ, PK_PU | PK_LOGC, mc_paths_pu_hz_kernel<NB, KT, 1, true>)
 
 // Rebalancing on a period; within tolerance bands (SPEC.md 4.18) every portfolio is a pass of its own
 MCP_ROW(FAM_REB, 0, mc_paths_reb_kernel<NB, KT, 1, false, false>)
@@ -100,6 +108,8 @@ MCP_ROW(FAM_CF, PK_GP | PK_LT, mc_paths_glide_life_kernel<NB, KT, 1, false, fals
 MCP_ROW(FAM_CF, PK_GP | PK_LT | PK_STT, mc_paths_glide_life_kernel<NB, KT, 1, false, false, true>)
 MCP_ROW(FAM_CF, PK_GP | PK_LT | PK_BOOT, mc_paths_glide_life_kernel<NB, KT, 1, true, false, false>)
 MCP_ROW(FAM_CF, PK_GP | PK_LT | PK_BOOT | PK_BLDS, mc_paths_glide_life_kernel<NB, KT, 1, true, true, false>)
+// ... and the Gaussian cash-flow walk on a drift drawn once per path (SPEC.md 4.21)
+MCP_ROW(FAM_CF, PK_PU, mc_paths_pu_cf_kernel<NB, KT, 1>)
 
 // The option overlay, with or without the drawdown
 MCP_ROW(FAM_OV, 0, mc_paths_ov_kernel<NB, KT, 1, false, false>)

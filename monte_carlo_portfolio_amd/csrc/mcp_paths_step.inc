@@ -21,7 +21,8 @@
 // 4.15 on the step's rho, then the peak M.  SP (with CF): the flow is the path's own -w, and the step adds what it pays out to Y
 // (SPEC.md 4.16); the reviews of w are events of the walk, not of the step.  LT (with CF): the mask that selects the step's V also
 // adds one to the lifetime l (SPEC.md 4.17).  VT: the update of V is the targeting rule of SPEC.md 4.19 on the step's rho, then the
-// variance estimate s moves on rho.
+// variance estimate s moves on rho.  PU: the row pair's accumulator starts at the path's own drift pair m (SPEC.md 4.21), held in
+// registers since before step 0, instead of the launch's mu; the drift is then not read from LDS.
       float rho[EM][KT];
       float fsh[PPT];                                  // FH: the shock s_j of the step's row (SPEC.md 2.4)
       if constexpr (BOOT) {
@@ -303,9 +304,13 @@
           }
         } else {
         f32x2 mu2;
-        if constexpr (LDS_MU) mu2 = *(const f32x2*)&s_par[2 * m];
+        if constexpr (PU) mu2 = f32x2{0.0f, 0.0f};     // never read: the row pair starts from the path's own drift
+        else if constexpr (LDS_MU) mu2 = *(const f32x2*)&s_par[2 * m];
         else mu2 = f32x2{mu[2 * m], mu[2 * m + 1]};
-        if constexpr (JP) {                            // SPEC.md 4.12: acc = fma(b_i, J, mu'_i), one packed fma per row pair
+        if constexpr (PU) {                            // SPEC.md 4.21: acc = m, the pair the path drew before step 0
+#pragma unroll
+          for (int e = 0; e < PPT; e++) acc[e] = Dm[e][m];
+        } else if constexpr (JP) {                            // SPEC.md 4.12: acc = fma(b_i, J, mu'_i), one packed fma per row pair
           f32x2 b2;
           if constexpr (LDS_B) {
             b2 = *(const f32x2*)&s_par[N4 + 2 * m];

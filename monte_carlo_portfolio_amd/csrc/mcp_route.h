@@ -57,10 +57,13 @@ enum PathFlag : uint32_t {
   PK_LT = 1u << 17,      // with exactly one of PK_GP and PK_SP: that kernel's lifetime twin (SPEC.md 4.17)
   PK_TB = 1u << 18,      // FAM_REB only, never PK_KT8: the tolerance-band kernel (SPEC.md 4.18), K portfolios as K passes of one
   PK_VT = 1u << 19,      // the volatility-targeting kernel (SPEC.md 4.19): FAM_DD with the drawdown, else FAM_HZ (H = 0 included); PK_GV or PK_JP
-  PK_UW = 1u << 20       // FAM_DD only: the drawdown kernel's twin that also counts the time under water (SPEC.md 4.20); alone, or with one
+  PK_UW = 1u << 20,      // FAM_DD only: the drawdown kernel's twin that also counts the time under water (SPEC.md 4.20); alone, or with one
                          // of PK_LOGC, PK_GV and PK_JP
+  PK_PU = 1u << 21       // the Gaussian walk on a drift drawn once per path (SPEC.md 2.7 / 4.21): FAM_PLAIN, FAM_DD and FAM_HZ alone or with
+                         // PK_LOGC, FAM_CF alone; never PK_UHI
 };
-constexpr int N_PATH_FLAGS = 21;
+constexpr int N_PATH_FLAGS = 21;                      // the bits PK_LOGC .. PK_UW
+constexpr int N_PATH_FLAGS_PU = N_PATH_FLAGS + 1;     // ... and PK_PU behind them: the 22 bits a selector may carry
 struct PathKernel {
   int family;            // PathFamily
   uint32_t flags;        // PathFlag bits

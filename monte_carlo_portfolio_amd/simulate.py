@@ -71,10 +71,17 @@ _VOLTARGET_CHOICE = ("mcp_simulate_vol_target", "vol_target is not combined with
 _UNDERWATER_CHOICE = ("mcp_simulate_underwater", "underwater is not combined with horizons, overlay, cashflow, rebalance, bootstrap or "
                                                  "filtered rows, regimes, glide, protect, spending, lifetime, tolerance, vol_target, "
                                                  "attribution or antithetic")
+# Drift uncertainty (SPEC.md 2.7 / 4.21) is a per-path drift on the Gaussian walk, its drawdown, its horizons and its cash flows: with
+# `drift_uncertainty` the call takes this entry point, whatever the table above would choose, and a keyword that entry point has no
+# argument group for is refused with this sentence.
+_UNCERTAIN_CHOICE = ("mcp_simulate_uncertain", "drift_uncertainty is not combined with dof, garch, jumps, regimes, overlay, rebalance, "
+                                               "bootstrap or filtered rows, glide, protect, spending, lifetime, tolerance, vol_target, "
+                                               "underwater, attribution or antithetic")
 # the argument group of _ffi.SIMULATE_ENTRIES that carries each feature keyword of Context._call
 _KEYWORD_GROUP = {"rows": "bt", "dof": "st", "period": "rb", "drawdown": "dd", "horizons": "hz_in", "flows": "cf", "overlay": "ov",
                   "garch": "gv", "attribution": "attr", "antithetic": "pairs", "filtered": "ft", "jumps": "jp", "regimes": "rs",
-                  "glide": "gl", "protect": "pt", "spending": "sp", "lifetime": "life", "tolerance": "tb", "vol_target": "vt", "underwater": "uw"}
+                  "glide": "gl", "protect": "pt", "spending": "sp", "lifetime": "life", "tolerance": "tb", "vol_target": "vt", "underwater": "uw",
+                  "drift_uncertainty": "du"}
 
 
 class Context:
@@ -122,8 +129,9 @@ class Context:
     def _call(self, prm: _ffi.McpParams, W, seed: int, path_begin: int, n_paths: int, store: bool, mu=None, chol=None, rows=None,
               block: float = 1.0, dof=None, period=None, cost: float = 0.0, drawdown: bool = False, horizons=None, levels=(),
               flows=None, target=None, overlay=None, garch=None, attribution=False, antithetic=False, filtered=None, jumps=None, regimes=None,
-              glide=None, protect=None, spending=None, lifetime=None, tolerance=None, vol_target=None, underwater=None):
-        """The one library call behind every simulate_* method: the time under water (underwater: the levels in percent of the two counters' order statistics, SPEC.md 4.20 / 5.20; needs `drawdown`), a volatility target (vol_target: the (target, decay, cap, rate, spread, s0 or None) of voltarget.check_vol_target, SPEC.md 4.19 / 5.19; `target` is then its second count, and without `drawdown` the call leaves the exposure record), tolerance bands (tolerance: (every, cost, tol float32 [K, N], levels in percent of the trade counts' order statistics), SPEC.md 4.18 / 5.18; the rule carries its own period and cost, so not with `period`), the lifetime (lifetime: the levels in percent of its order statistics, SPEC.md 4.17 / 5.17; needs flows or spending), a spending rule (spending: the (rate, every, down, up, inflation, first or None) of check_spending; `target` is then its second count), floor protection (protect: the (floor, multiplier, rate, cap, ratchet) of check_protect; `target` is then its second count), two regimes (regimes: the (p01, p10, start, mu1, chol1) of check_regimes), market jumps (jumps: the (intensity, mean, std, loading or None) of check_jumps), GARCH volatility (garch: the (alpha, beta, h0) of check_garch), an option overlay (overlay: the triple of check_overlay), cash flows (flows, target), Student-t draws (dof), rebalancing
+              glide=None, protect=None, spending=None, lifetime=None, tolerance=None, vol_target=None, underwater=None,
+              drift_uncertainty=None):
+        """The one library call behind every simulate_* method: drift uncertainty (drift_uncertainty: the binary32 factor M [N, N] of uncertainty.drift_factor, SPEC.md 2.7 / 4.21; on Gaussian draws with the drawdown, horizons or flows), the time under water (underwater: the levels in percent of the two counters' order statistics, SPEC.md 4.20 / 5.20; needs `drawdown`), a volatility target (vol_target: the (target, decay, cap, rate, spread, s0 or None) of voltarget.check_vol_target, SPEC.md 4.19 / 5.19; `target` is then its second count, and without `drawdown` the call leaves the exposure record), tolerance bands (tolerance: (every, cost, tol float32 [K, N], levels in percent of the trade counts' order statistics), SPEC.md 4.18 / 5.18; the rule carries its own period and cost, so not with `period`), the lifetime (lifetime: the levels in percent of its order statistics, SPEC.md 4.17 / 5.17; needs flows or spending), a spending rule (spending: the (rate, every, down, up, inflation, first or None) of check_spending; `target` is then its second count), floor protection (protect: the (floor, multiplier, rate, cap, ratchet) of check_protect; `target` is then its second count), two regimes (regimes: the (p01, p10, start, mu1, chol1) of check_regimes), market jumps (jumps: the (intensity, mean, std, loading or None) of check_jumps), GARCH volatility (garch: the (alpha, beta, h0) of check_garch), an option overlay (overlay: the triple of check_overlay), cash flows (flows, target), Student-t draws (dof), rebalancing
         (period, cost), bootstrap rows (rows, block) or Gaussian draws (mu, chol), with the drawdown or horizons.  Allocates the
         outputs that were asked for and passes NULL for the rest -> _Outputs, None where not asked for (terminal, qd,
         horizon_terminal: with `store` only; counts, hz_counts: with `flows` only; attr [K, N] records of ATTR_DTYPE and attr_counts
@@ -138,11 +146,13 @@ class Context:
                                    ("regimes", regimes is not None), ("glide", glide is not None),
                                    ("protect", protect is not None), ("spending", spending is not None),
                                    ("lifetime", lifetime is not None), ("tolerance", tolerance is not None),
-                                   ("vol_target", vol_target is not None), ("underwater", underwater is not None)) if on]
+                                   ("vol_target", vol_target is not None), ("underwater", underwater is not None),
+                                   ("drift_uncertainty", drift_uncertainty is not None)) if on]
         has = set(given).issuperset
-        entry, refusal = _UNDERWATER_CHOICE if underwater is not None else _BAND_CHOICE if tolerance is not None else _LIFE_CHOICE if lifetime is not None else _VOLTARGET_CHOICE if vol_target is not None else next((e, r) for needs, e, r in _ENTRY_CHOICE if has(needs))
+        entry, refusal = _UNCERTAIN_CHOICE if drift_uncertainty is not None else _UNDERWATER_CHOICE if underwater is not None else _BAND_CHOICE if tolerance is not None else _LIFE_CHOICE if lifetime is not None else _VOLTARGET_CHOICE if vol_target is not None else next((e, r) for needs, e, r in _ENTRY_CHOICE if has(needs))
         groups = next(t[entry] for t in (_ffi.SIMULATE_ENTRIES, _ffi.EXTENSION_ENTRIES, _ffi.SPEND_ENTRIES, _ffi.LIFE_ENTRIES,
-                                            _ffi.BAND_ENTRIES, _ffi.VOLTARGET_ENTRIES, _ffi.UNDERWATER_ENTRIES) if entry in t)
+                                            _ffi.BAND_ENTRIES, _ffi.VOLTARGET_ENTRIES, _ffi.UNDERWATER_ENTRIES, _ffi.UNCERTAIN_ENTRIES)
+                      if entry in t)
         # the library states the rules (check_request); a keyword the entry point has no argument for is refused here, not dropped
         for kw in given:
             if _KEYWORD_GROUP[kw] not in groups:
@@ -165,8 +175,9 @@ class Context:
             hz_stats = np.zeros((H, K), _ffi.STATS_DTYPE)
             bands = np.zeros((H, K, L), np.float64)
             hz_term = np.empty((H, K, n_paths), np.float32) if store else None
-        counts = np.zeros((K, 2), np.uint64) if "counts" in groups else None
-        hz_counts = np.zeros((H, K, 2), np.uint64) if "hz_counts" in groups and horizons is not None else None
+        has_counts = "counts" in groups and not (drift_uncertainty is not None and flows is None)   # SPEC.md 4.21: the counts are the flows'
+        counts = np.zeros((K, 2), np.uint64) if has_counts else None
+        hz_counts = np.zeros((H, K, 2), np.uint64) if has_counts and "hz_counts" in groups and horizons is not None else None
         pairs = np.zeros(K, _ffi.PAIR_DTYPE) if "pairs" in groups else None
         attr = np.zeros((K, N), _ffi.ATTR_DTYPE) if "attr" in groups else None
         attr_counts = np.zeros((K, 2), np.uint64) if "attr_counts" in groups else None
@@ -215,6 +226,7 @@ class Context:
                 "tb": (_ffi.make_band(tolerance[0], tolerance[1], tol) if tolerance is not None else None,),
                 "vt": (_ffi.make_vol_target(*vol_target, target_value=target) if vol_target is not None else None,),
                 "exposure": (exposure, exposure_stats),
+                "du": (_ffi.make_drift_uncertainty(drift_uncertainty) if drift_uncertainty is not None else None,),
                 "uw": (uw_longest, uw_current, uw_longest_hist, uw_current_hist, uw_sums, 0 if uw_lv is None else uw_lv.size,
                        uw_lv if uw_lv is not None and uw_lv.size else None, uw_q if uw_lv is not None and uw_lv.size else None),
                 "trades": (trades, trade_hist, trade_sum, 0 if trade_lv is None else trade_lv.size,
@@ -239,6 +251,15 @@ class Context:
         return _Outputs(stats, dd_stats, hz_stats, bands, term, raw, hz_term, counts, hz_counts, attr, attr_counts, contrib, pairs,
                         wd_stats, withdrawn, life_hist, life_sum, life_q, life, trade_hist, trade_sum, trade_q, trades, turnover_stats, turnover,
                         exposure_stats, exposure, uw_longest_hist, uw_current_hist, uw_sums, uw_q, uw_longest, uw_current)
+
+    def simulate_uncertain(self, prm: _ffi.McpParams, factor, mu, chol, W, seed: int, path_begin: int, n_paths: int, store: bool,
+                           drawdown: bool = False, horizons=None, levels=(), flows=None, target=None):
+        """simulate() / simulate_drawdown() / simulate_horizons() / simulate_cashflow() on Gaussian draws with the drift of every path
+        drawn once, m = mu + M g (SPEC.md 2.7 / 4.21; include/mcport_uncertain.h, mcp_simulate_uncertain): `factor` is the binary32
+        lower-triangular M [N, N] (uncertainty.drift_factor) -> _Outputs as those calls leave them; counts and hz_counts with `flows`
+        only."""
+        return self._call(prm, W, seed, path_begin, n_paths, store, mu=mu, chol=chol, drawdown=drawdown, horizons=horizons, levels=levels,
+                          flows=flows, target=target, drift_uncertainty=np.ascontiguousarray(factor, np.float32))
 
     def simulate_underwater(self, prm: _ffi.McpParams, mu, chol, W, seed: int, path_begin: int, n_paths: int, store: bool,
                             levels=(50.0, 95.0), dof=None, garch=None, jumps=None):
@@ -1000,6 +1021,9 @@ def antithetic_to_dict(rec) -> dict:
 # checked, so the same rule wins when two apply.  The C side states the same rules for the library (check_request).
 _FLAGS = ("drawdown", "attribution", "antithetic", "fold", "native_math", "lifetime", "underwater")
 _PATHS_COMBINE = {
+    "drift_uncertainty": ("drift_uncertainty needs Gaussian draws, constant weights, the spec's normals and the unfolded recurrence",
+                          ("underwater", "vol_target", "tolerance", "spending", "protect", "glide", "regimes", "jumps", "garch", "dof",
+                           "rebalance", "overlay", "attribution", "antithetic", "lifetime", "fold", "native_math"), True),
     "underwater": ("underwater=True needs the drawdown walk on Gaussian, Student-t, GARCH or jump draws, the spec's normals and the unfolded "
                    "recurrence",
                    ("vol_target", "tolerance", "spending", "protect", "glide", "regimes", "rebalance", "cashflow", "overlay", "attribution",
@@ -1076,7 +1100,7 @@ def simulate_paths(mu, cov, weights, n_steps=252, n_paths=10_000, seed=0, v0=1.0
                    horizons=None, bands=(), rebalance=None, rebalance_cost=0.0, dof=None, cashflow=None, target=None,
                    overlay=None, spot=None, garch=None, attribution=False, antithetic=False, jumps=None, regimes=None, glide=None,
                    protect=None, spending=None, lifetime=False, lifetime_levels=(5, 25, 50), tolerance=None, tolerance_levels=(5, 50, 95),
-                   vol_target=None, underwater=False, underwater_levels=(50, 95)):
+                   vol_target=None, underwater=False, underwater_levels=(50, 95), drift_uncertainty=None):
     """Simulate `n_paths` correlated return paths and reduce them to risk statistics.
 
     mu [N], cov [N,N] are per-step mean and covariance (the reference's `mean_returns`, `cov_matrix`
@@ -1301,7 +1325,27 @@ def simulate_paths(mu, cov, weights, n_steps=252, n_paths=10_000, seed=0, v0=1.0
     compounding="log" (Gaussian draws), store, as_array, devices and shard="portfolios".  Not built: underwater without drawdown, with
     vol_target, tolerance, spending, protect, glide, regimes, rebalance, cashflow, overlay, attribution, antithetic, lifetime, horizons,
     fold or native_math (ValueError), on bootstrap or filtered rows, in simulate_sweep, in PathEngine and at the mcp_launch_* level.
+
+    drift_uncertainty=None (default): every path walks on `mu` as if it were known.  drift_uncertainty=n_obs | cov_of_drift |
+    ("factor", M): estimation risk inside the walk (SPEC.md 2.7 / 4.21 / 5.21) -- `mu` is a sample mean, so every path draws its own
+    drift once, m = mu + M g with g ~ N(0, I), and compounds on it at every step.  A positive number n_obs takes M = chol(cov) /
+    sqrt(n_obs), the standard error of a mean over n_obs observed steps; an [N, N] matrix is the covariance of the drift itself
+    (uncertainty.drift_cov(returns)), factored here; ("factor", M) is a lower-triangular factor used as given, zeros allowed.  The
+    draws of the steps are those of the same call without it (common random numbers), and with M = 0 every stored value is that
+    call's, bit for bit.  The fan of `horizons` and the ruin probability of `cashflow` widen: the variance of the log value gains
+    h^2 b_k on top of h a_k.  Every dict gains 'drift_uncertainty' {drift_std (sqrt(b_k), the standard deviation of the portfolio's
+    drift), log_variance_share (T b_k / (a_k + T b_k)) and, with horizons, horizon_log_variance_share}; as_array returns what the
+    call without it returns.  uncertainty.drift_law gives the exact laws.  Combines with drawdown, horizons / bands,
+    compounding="log", cashflow and target, store, as_array, devices and shard="portfolios".  Not built: drift_uncertainty with
+    underwater, vol_target, tolerance, spending, protect, glide, regimes, jumps, garch, dof, rebalance, overlay, attribution,
+    antithetic, lifetime, fold or native_math (ValueError), on bootstrap or filtered rows, in simulate_sweep, in PathEngine and at
+    the mcp_launch_* level.
     """
+    if drift_uncertainty is not None:
+        return _simulate_uncertain(mu, cov, weights, n_steps, n_paths, seed, v0, compounding, rf, alpha, devices, store, path_begin, chol,
+                                   native_math, as_array, fold, shard, context, drawdown, horizons, bands, rebalance, rebalance_cost, dof,
+                                   cashflow, target, overlay, spot, garch, attribution, antithetic, jumps, regimes, glide, protect, spending,
+                                   lifetime, tolerance, vol_target, underwater, drift_uncertainty)
     if not isinstance(underwater, (bool, np.bool_)):
         raise ValueError(f"underwater must be True or False, got {underwater!r}")
     if underwater:
@@ -1462,6 +1506,42 @@ def _simulate_vol_target(mu, cov, weights, n_steps, n_paths, seed, v0, compoundi
     if jv is not None:
         for d, blk in zip([res] if isinstance(res, dict) else res, _jump_blocks(jv, L, W)):
             d["jumps"] = blk
+    return res
+
+
+def _simulate_uncertain(mu, cov, weights, n_steps, n_paths, seed, v0, compounding, rf, alpha, devices, store, path_begin, chol, native_math,
+                        as_array, fold, shard, context, drawdown, horizons, bands, rebalance, rebalance_cost, dof, cashflow, target, overlay,
+                        spot, garch, attribution, antithetic, jumps, regimes, glide, protect, spending, lifetime, tolerance, vol_target,
+                        underwater, drift_uncertainty):
+    """simulate_paths with drift uncertainty (SPEC.md 2.7 / 4.21 / 5.21): the rules of what it combines with, then the underlying
+    call's own rules in simulate_paths' order, the call and the 'drift_uncertainty' block."""
+    from .uncertainty import check_drift_uncertainty, uncertainty_blocks
+    for name, flag in (("lifetime", lifetime), ("underwater", underwater), ("attribution", attribution), ("antithetic", antithetic)):
+        if not isinstance(flag, (bool, np.bool_)):
+            raise ValueError(f"{name} must be True or False, got {flag!r}")
+    kw = dict(drift_uncertainty=drift_uncertainty, underwater=underwater, vol_target=vol_target, tolerance=tolerance, spending=spending,
+              protect=protect, glide=glide, regimes=regimes, jumps=jumps, antithetic=antithetic, attribution=attribution, garch=garch,
+              overlay=overlay, cashflow=cashflow, dof=dof, rebalance=rebalance, drawdown=drawdown, horizons=horizons, lifetime=lifetime,
+              fold=fold, native_math=native_math, compounding=compounding, shard=shard)
+    _check_combines(_PATHS_COMBINE, "drift_uncertainty", kw)
+    if spot is not None:
+        raise ValueError("spot belongs to overlay: drift_uncertainty takes none")
+    M = check_drift_uncertainty(drift_uncertainty, cov, chol)
+    flows, target = check_cashflow(cashflow, target, n_steps)
+    for feature in ("cashflow", "drawdown", "horizons"):
+        _check_combines(_PATHS_COMBINE, feature, kw)
+    steps, levels = _check_walk(n_steps, horizons, bands, None, compounding, shard)
+    mu32, L, W = prepare_inputs(mu, cov, weights, chol)
+    if M.shape != L.shape:
+        raise ValueError(f"drift_uncertainty: the factor is {M.shape}, the market has {L.shape[0]} assets")
+    prm, ctx = _setup(mu32.shape[0], n_steps, W.shape[0], compounding, v0, alpha, rf, False, False, devices, shard, context)
+    out = ctx._call(prm, W, int(seed), int(path_begin), int(n_paths), store, mu=mu32, chol=L, drawdown=bool(drawdown), horizons=steps,
+                    levels=levels, flows=flows, target=target, drift_uncertainty=M)
+    res = _result(out, np.asarray(weights).ndim == 1, store, as_array, steps, levels, compounding, flows, target)
+    if as_array:
+        return res
+    for d, blk in zip([res] if isinstance(res, dict) else res, uncertainty_blocks(L, M, W, n_steps, steps)):
+        d["drift_uncertainty"] = blk
     return res
 
 
@@ -1865,6 +1945,8 @@ def simulate_sweep(mu, cov, weights=None, n_portfolios=2500, min_weights=None, m
         raise ValueError("simulate_sweep does not take vol_target: call simulate_paths for the optimum")
     if kw.get("underwater"):
         raise ValueError("simulate_sweep does not take underwater: call simulate_paths for the optimum")
+    if kw.get("drift_uncertainty") is not None:
+        raise ValueError("simulate_sweep does not take drift_uncertainty: call simulate_paths for the optimum")
     if kw.get("attribution"):
         raise ValueError("simulate_sweep does not take attribution: call simulate_paths for the optimum")
     kw.pop("attribution", None)
