@@ -42,9 +42,15 @@ def main(paths, resample_rule="M", user_rf=3.0, investment=10000.0, seed=12345, 
     w = res["Monte Carlo"]["weights"]
     mu_step, cov_step = returns_df.mean().values, returns_df.cov().values  # per period, before annualising
     sim = mcp.simulate_paths(mu_step, cov_step, w, n_steps=af, n_paths=n_paths, seed=seed, v0=investment, rf=user_rf / 100,
-                             drawdown=True)
+                             drawdown=True, downside=0.0)
     print(f"max-Sharpe weights on {n_paths:,} simulated {af}-period paths: mean {sim['mean']:+.4f}  std {sim['std']:.4f}  "
           f"VaR95 {sim['var']:+.4f}  CVaR95 {sim['cvar']:+.4f}  Sharpe {sim['sharpe']:.4f}")
+
+    def shape(label, o):                  # downside and shape of x at the threshold 0 (SPEC.md 5.22): what fat tails and jumps move
+        d = o["downside"]
+        print(f"  {label}: Sortino {d['sortino']:.4f}  P(loss) {d['p_below']:.4f}  skewness {d['skewness']:+.4f}  "
+              f"excess kurtosis {d['excess_kurtosis']:+.4f}")
+    shape("Gaussian draws", sim)
     dd = sim["drawdown"]                  # max drawdown of every path before the horizon (SPEC.md 4.2 / 5.1)
     print(f"  max drawdown: mean {dd['mean']:+.4f}  DaR95 {dd['dar']:+.4f}  CDaR95 {dd['cdar']:+.4f}  worst {dd['worst']:+.4f}")
     # which holding that risk comes from (SPEC.md 4.10 / 5.9): the same paths walked a second time, every asset's part of the CVaR
@@ -77,10 +83,11 @@ def main(paths, resample_rule="M", user_rf=3.0, investment=10000.0, seed=12345, 
     # mixing variable per path and period shared by all assets, nu fitted to the observed rows (32: no evidence of fat tails)
     nu = mcp.fit_student_t_dof(returns_df)
     tsim = mcp.simulate_paths(mu_step, cov_step, w, n_steps=af, n_paths=n_paths, seed=seed, v0=investment, rf=user_rf / 100,
-                              dof=nu, drawdown=True)
+                              dof=nu, drawdown=True, downside=0.0)
     print(f"Student-t (nu = {nu}, fitted to the {len(returns_df)} observed rows), same weights: mean {tsim['mean']:+.4f}  "
           f"std {tsim['std']:.4f}  VaR95 {tsim['var']:+.4f}  CVaR95 {tsim['cvar']:+.4f}  Sharpe {tsim['sharpe']:.4f}  "
           f"DaR95 {tsim['drawdown']['dar']:+.4f}")
+    shape(f"Student-t draws (6 / (nu - 4) = {6 / (nu - 4):.2f} per step)" if nu > 4 else "Student-t draws", tsim)
     # how long the optimum stays below its high-water mark on those paths (SPEC.md 4.20 / 5.20): exact integers off two histograms
     uw = mcp.simulate_paths(mu_step, cov_step, w, n_steps=af, n_paths=n_paths, seed=seed, v0=investment, rf=user_rf / 100, dof=nu,
                             drawdown=True, underwater=True, underwater_levels=(50, 95))["underwater"]
@@ -126,7 +133,7 @@ def main(paths, resample_rule="M", user_rf=3.0, investment=10000.0, seed=12345, 
     jfit = mcp.fit_jumps(returns_df)
     print(f"jump-diffusion fit: intensity = {jfit.intensity:.4f}  mean = {jfit.mean:+.4f}  std = {jfit.std:.4f}  "
           f"({jfit.n_jump_rows} of {len(returns_df)} rows)  loadings {np.round(jfit.loading, 2)}")
-    kw = dict(n_steps=af, n_paths=n_paths, seed=seed, v0=investment, rf=user_rf / 100, drawdown=True, jumps=tuple(jfit[:4]))
+    kw = dict(n_steps=af, n_paths=n_paths, seed=seed, v0=investment, rf=user_rf / 100, drawdown=True, jumps=tuple(jfit[:4]), downside=0.0)
     try:
         jsim = mcp.simulate_paths(mu_step, cov_step, w, **kw)
     except ValueError:                    # the fitted jumps carry more variance than the rows' covariance leaves: keep the diffusion whole
@@ -134,6 +141,7 @@ def main(paths, resample_rule="M", user_rf=3.0, investment=10000.0, seed=12345, 
     print(f"  optimum without jumps: VaR = {sim['var']:+.4f}  CVaR = {sim['cvar']:+.4f}  mean max drawdown = {sim['drawdown']['mean']:+.4f}")
     print(f"  optimum with jumps:    VaR = {jsim['var']:+.4f}  CVaR = {jsim['cvar']:+.4f}  mean max drawdown = "
           f"{jsim['drawdown']['mean']:+.4f}  (jump share of the variance {jsim['jumps']['variance_share'] * 100:.1f} %)")
+    shape("with jumps", jsim)
     # a withdrawal plan on the same weights (SPEC.md 4.7 / 5.6): 1.5 % of the capital taken out after every period for 6 years;
     # a path whose value is used up is ruined and stays so -- the share of ruined paths per horizon is the survival curve
     T, take = 6 * af, 0.015 * investment

@@ -357,6 +357,28 @@ UNCERTAIN_ENTRIES = {name: tuple(groups.split()) for name, groups in UNCERTAIN_E
 UNCERTAIN_SIGNATURES = {}
 UNCERTAIN_SIGNATURES.update((name, (_int, [t for g in groups for t in ARG_GROUPS[g]])) for name, groups in UNCERTAIN_ENTRIES.items())
 
+# And for include/mcport_downside.h (SPEC.md 5.22): no mcp_simulate* among them -- the request arms a context and rides the next call.
+class McpDownside(ctypes.Structure):
+    """mcp_downside (include/mcport_downside.h): the threshold tau of SPEC.md 5.22, or use_rf != 0 for the call's rf."""
+    _fields_ = [("tau", ctypes.c_double), ("use_rf", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
+# one mcp_downside_sums: the raw record of a row; one mcp_downside_stats: the finished record
+DOWNSIDE_SUMS_DTYPE = np.dtype([("n", np.uint64), ("n_below", np.uint64), ("n_above", np.uint64), ("s1", np.float64), ("s2", np.float64),
+                                ("s3", np.float64), ("s4", np.float64), ("b1", np.float64), ("b2", np.float64), ("l1", np.float64),
+                                ("l2", np.float64), ("u1", np.float64)])
+DOWNSIDE_STATS_DTYPE = np.dtype([(f, np.float64) for f in ("mean", "skewness", "excess_kurtosis", "downside_std", "sortino",
+                                                           "downside_deviation", "sortino_target", "p_below", "mean_shortfall", "omega", "pivot")])
+assert DOWNSIDE_SUMS_DTYPE.itemsize == 96 and DOWNSIDE_STATS_DTYPE.itemsize == 88
+DOWNSIDE_SIGNATURES = {
+    "mcp_downside_grid": (_u64, [_u64]),
+    "mcp_downside_ws_bytes": (ctypes.c_size_t, [_int, _u64]),
+    "mcp_downside_trip_n": (_u64, []),
+    "mcp_launch_downside": (_int, [_PP, _vp, _u64, _u64, _int, _vp, ctypes.c_double, _vp, _vp, _vp]),
+    "mcp_downside_finish": (_int, [_vp, ctypes.c_double, ctypes.c_double, _vp]),
+    "mcp_ctx_request_downside": (_int, [_vp, ctypes.POINTER(McpDownside), _vp, _vp, _vp]),
+}
+
 _LIB = None
 
 
@@ -423,7 +445,7 @@ def lib() -> ctypes.CDLL:
             fn.argtypes = args
         for name, (res, args) in list(EXTENSION_SIGNATURES.items()) + list(SPEND_SIGNATURES.items()) + list(LIFE_SIGNATURES.items()) + \
                 list(BAND_SIGNATURES.items()) + list(VOLTARGET_SIGNATURES.items()) + list(UNDERWATER_SIGNATURES.items()) + \
-                list(UNCERTAIN_SIGNATURES.items()):
+                list(UNCERTAIN_SIGNATURES.items()) + list(DOWNSIDE_SIGNATURES.items()):
             fn = getattr(L, name)          # additive entry points, detected by symbol: a library without them is too old
             fn.restype = res
             fn.argtypes = args
@@ -721,6 +743,15 @@ def make_drift_uncertainty(factor: np.ndarray) -> McpDriftUncertainty:
     du = McpDriftUncertainty(m.ctypes.data, 0)
     du._keep = m
     return du
+
+
+def downside_finish(sums, tau: float, pivot: float):
+    """One finished record (a DOWNSIDE_STATS_DTYPE scalar) of one raw record `sums` (a DOWNSIDE_SUMS_DTYPE scalar or 0-d array):
+    SPEC.md 5.22 (include/mcport_downside.h, mcp_downside_finish), pure host arithmetic."""
+    s = np.array(sums, DOWNSIDE_SUMS_DTYPE).reshape(1)
+    out = np.zeros(1, DOWNSIDE_STATS_DTYPE)
+    check(lib().mcp_downside_finish(ptr(s), float(tau), float(pivot), ptr(out)))
+    return out[0]
 
 
 def make_vol_target(target: float, decay: float, cap: float = 1.0, rate: float = 0.0, spread: float = 0.0, s0=None,

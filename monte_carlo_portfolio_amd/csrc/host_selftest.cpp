@@ -698,7 +698,68 @@ static void run_named_routes() {
   }
 }
 
+// SPEC.md 5.22: mcp_downside_finish on hand-made records -- the three cases of downside_std, the empty sets, a constant sample -- the
+// request's rules, and the arm / disarm rule: armed, a failing call (which takes the request), then a plain call finds nothing.
+static void run_downside() {
+  snprintf(g_case, sizeof g_case, "downside finish");
+  mcp_downside_stats o;
+  // x = {-2, -1, 1, 4} about c = 0 at tau = 0: d = e
+  const mcp_downside_sums four = {4, 2, 2, 2.0, 22.0, 56.0, 274.0, -3.0, 5.0, -3.0, 5.0, 5.0};
+  EXPECT(mcp_downside_finish(&four, 0.0, 0.0, &o) == MCP_OK);
+  EXPECT(o.mean == 0.5 && o.p_below == 0.5 && o.mean_shortfall == -1.5 && o.omega == 5.0 / 3.0);
+  EXPECT(o.downside_std == std::sqrt(0.5) && o.sortino == 0.5 / std::sqrt(0.5) && o.downside_deviation == std::sqrt(1.25));
+  EXPECT(o.sortino_target == 0.5 / std::sqrt(1.25) && std::isfinite(o.skewness) && std::isfinite(o.excess_kurtosis));
+  EXPECT(mcp_downside_finish(&four, 0.0, 10.0, &o) == MCP_OK && o.mean == 10.5);     // the pivot moves the mean alone
+  const mcp_downside_sums one_below = {2, 1, 1, 0.0, 2.0, 0.0, 2.0, -1.0, 1.0, -1.0, 1.0, 1.0};   // x = {-1, 1}
+  EXPECT(mcp_downside_finish(&one_below, 0.0, 0.0, &o) == MCP_OK && std::isnan(o.downside_std) && std::isnan(o.sortino) && o.omega == 1.0);
+  EXPECT(o.skewness == 0.0 && o.excess_kurtosis == -2.0);
+  const mcp_downside_sums none_below = {2, 0, 2, 3.0, 5.0, 9.0, 17.0, 0.0, 0.0, 0.0, 0.0, 3.0};  // x = {1, 2}
+  EXPECT(mcp_downside_finish(&none_below, 0.0, 0.0, &o) == MCP_OK && o.downside_std == 1e-4 && o.sortino == 1.5 / 1e-4);
+  EXPECT(o.omega == HUGE_VAL && o.mean_shortfall == 0.0 && o.sortino_target == 0.0 && o.p_below == 0.0 && o.downside_deviation == 0.0);
+  const mcp_downside_sums constant = {3, 0, 0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};     // x = tau = c three times: neither set
+  EXPECT(mcp_downside_finish(&constant, 0.25, 0.25, &o) == MCP_OK && o.skewness == 0.0 && o.excess_kurtosis == 0.0 && o.mean == 0.25);
+  EXPECT(o.sortino == 0.0 && o.omega == HUGE_VAL && o.p_below == 0.0);
+  const mcp_downside_sums empty = {};
+  EXPECT(mcp_downside_finish(&empty, 0.0, 0.5, &o) == MCP_OK && o.mean == 0.5 && o.p_below == 0.0 && o.downside_deviation == 0.0);
+  EXPECT(mcp_downside_finish(nullptr, 0.0, 0.0, &o) == MCP_E_ARG && mcp_downside_finish(&four, 0.0, 0.0, nullptr) == MCP_E_ARG);
+
+  snprintf(g_case, sizeof g_case, "downside request");
+  mcp_downside req = {0.01, 0, 0};
+  EXPECT(check_downside(&req, &o) == MCP_OK);
+  EXPECT(check_downside(nullptr, &o) == MCP_E_ARG && check_downside(&req, nullptr) == MCP_E_ARG);
+  req.reserved = 1;
+  EXPECT(check_downside(&req, &o) == MCP_E_ARG);
+  req.reserved = 0;
+  for (double bad : {(double)NAN, (double)INFINITY, -(double)INFINITY}) {
+    req.tau = bad;
+    EXPECT(check_downside(&req, &o) == MCP_E_ARG);
+  }
+  req.tau = 0.01;
+  req.use_rf = 1;
+
+  snprintf(g_case, sizeof g_case, "downside arm / disarm");
+  DownsideArm arm;
+  mcp_downside_sums sums;
+  mcp_downside_stats hz;
+  EXPECT(!arm.on && !arm.take().on);
+  arm.arm(req, &sums, &o, &hz);
+  EXPECT(arm.on && arm.use_rf && arm.tau == 0.01 && arm.sums_out == &sums && arm.stats_out == &o && arm.hz_stats_out == &hz);
+  const DownsideArm failing = arm.take();                  // the call that takes it may fail: the request is spent either way
+  EXPECT(failing.on && failing.stats_out == &o && !arm.on && !arm.stats_out && !arm.sums_out && !arm.hz_stats_out);
+  const DownsideArm plain = arm.take();                    // the plain call after it: nothing to write to
+  EXPECT(!plain.on && !plain.stats_out && !plain.sums_out && !plain.hz_stats_out);
+  req.use_rf = 0;
+  arm.arm(req, nullptr, &o, nullptr);
+  arm.arm(req, &sums, &o, nullptr);                        // a second request replaces the first
+  EXPECT(arm.take().sums_out == &sums && !arm.on);
+
+  mcp_downside_sums a = four;
+  downside_add(a, one_below);
+  EXPECT(a.n == 6 && a.n_below == 3 && a.n_above == 3 && a.s2 == 24.0 && a.b1 == -4.0 && a.l2 == 6.0 && a.u1 == 6.0 && a.s4 == 276.0);
+}
+
 int main() {
+  run_downside();
   const int Ns[3] = {1, 5, MCP_MAX_ASSETS}, Ks[4] = {1, 8, 9, 17}, Hs[2] = {0, 2};
   int n = 0;
   for (int N : Ns)

@@ -1364,9 +1364,76 @@ int life_summary(const uint64_t* hist, int T, int n_levels, const double* levels
   return MCP_OK;
 }
 
+// SPEC.md 5.22: the request's own rules, the context aside
+int check_downside(const mcp_downside* req, const mcp_downside_stats* stats_out) {
+  if (!req) return fail(MCP_E_ARG, "downside request is NULL");
+  if (!stats_out) return fail(MCP_E_ARG, "downside stats_out is NULL");
+  if (!std::isfinite(req->tau)) return fail(MCP_E_ARG, "downside tau=%g is not finite", req->tau);
+  if (req->reserved != 0) return fail(MCP_E_ARG, "downside reserved=%d must be 0", req->reserved);
+  return MCP_OK;
+}
+
+void DownsideArm::arm(const mcp_downside& req, mcp_downside_sums* sums, mcp_downside_stats* stats, mcp_downside_stats* hz_stats) {
+  on = true;
+  tau = req.tau;
+  use_rf = req.use_rf != 0;
+  sums_out = sums;
+  stats_out = stats;
+  hz_stats_out = hz_stats;
+}
+
+DownsideArm DownsideArm::take() {
+  const DownsideArm t = *this;
+  *this = DownsideArm();
+  return t;
+}
+
+void downside_add(mcp_downside_sums& a, const mcp_downside_sums& b) {
+  a.n += b.n; a.n_below += b.n_below; a.n_above += b.n_above;
+  a.s1 += b.s1; a.s2 += b.s2; a.s3 += b.s3; a.s4 += b.s4;
+  a.b1 += b.b1; a.b2 += b.b2; a.l1 += b.l1; a.l2 += b.l2; a.u1 += b.u1;
+}
+
 }  // namespace mcph
 
 using namespace mcph;
+
+// SPEC.md 5.22: every operation below is one binary64 operation in the order written (-ffp-contract=off); downside.finish repeats it
+int mcp_downside_finish(const mcp_downside_sums* s, double tau, double pivot, mcp_downside_stats* out) {
+  if (!s || !out) return fail(MCP_E_ARG, "NULL pointer");
+  const double n = (double)s->n, nb = (double)s->n_below;
+  const double dl = s->n ? s->s1 / n : 0.0;
+  mcp_downside_stats o;
+  o.mean = pivot + dl;
+  const double dl2 = dl * dl;
+  const double m2 = s->s2 - s->s1 * dl;
+  const double m3 = (s->s3 - (3.0 * dl) * s->s2) + ((2.0 * n) * dl) * dl2;
+  const double m4 = ((s->s4 - (4.0 * dl) * s->s3) + (6.0 * dl2) * s->s2) - ((3.0 * n) * dl2) * dl2;
+  if (m2 > 0.0) {
+    const double v = m2 / n;
+    o.skewness = (m3 / n) / (v * std::sqrt(v));
+    o.excess_kurtosis = (n * m4) / (m2 * m2) - 3.0;
+  } else {
+    o.skewness = 0.0;
+    o.excess_kurtosis = 0.0;
+  }
+  if (s->n_below >= 2) {
+    const double q = s->b2 - (s->b1 * s->b1) / nb;
+    o.downside_std = std::sqrt((q > 0.0 ? q : 0.0) / (nb - 1.0));
+  } else {
+    o.downside_std = s->n_below == 1 ? std::nan("") : 1e-4;
+  }
+  const double ex = o.mean - tau;
+  o.sortino = ex / o.downside_std;
+  o.downside_deviation = s->n ? std::sqrt(s->l2 / n) : 0.0;
+  o.sortino_target = o.downside_deviation > 0.0 ? ex / o.downside_deviation : 0.0;
+  o.p_below = s->n ? nb / n : 0.0;
+  o.mean_shortfall = s->n_below ? s->l1 / nb : 0.0;
+  o.omega = s->l1 == 0.0 ? HUGE_VAL : s->u1 / (-s->l1);
+  o.pivot = pivot;
+  *out = o;
+  return MCP_OK;
+}
 
 int mcp_lifetime_summary(const uint64_t* hist, int n_steps, int n_levels, const double* levels, uint64_t* sum_out, uint32_t* q_out) {
   if (!hist || !sum_out) return fail(MCP_E_ARG, "NULL pointer");

@@ -16,6 +16,7 @@
 #include "../../include/mcport_voltarget.h"
 #include "../../include/mcport_underwater.h"
 #include "../../include/mcport_uncertain.h"
+#include "../../include/mcport_downside.h"
 #include "mcp_route.h"
 
 namespace mcp {
@@ -113,6 +114,13 @@ struct Request {
   bool anti = false;                    // SPEC.md 2.3 / 5.10: antithetic pairs
   mcp_pair* pair_out = nullptr;         // [K]
   double* cross_out = nullptr;          // [K] the call's cross sums: every tile adds its shards' in shard order
+  bool downside = false;                // SPEC.md 5.22: the context was armed (mcp_ctx_request_downside); set by the call that takes the request
+  bool ds_hz = false;                   // the request also covers the horizon rows
+  double ds_tau = 0.0;                  // the threshold, prm->rf when the request says so
+  mcp_downside_sums* ds_sums = nullptr;      // [K] the call's raw records: every tile adds its shards' in shard order
+  mcp_downside_sums* ds_hz_sums = nullptr;   // [H*K], row h*K + k
+  double* ds_pivot = nullptr;           // [K] the pivots the records are about, as the tiles computed them
+  double* ds_hz_pivot = nullptr;        // [H*K]
 };
 
 // The row table of a request that walks rows: the bootstrap's own, or the residual rows of SRC_FHS.
@@ -180,6 +188,7 @@ int check_band(const mcp_params* prm, const mcp_band* bd);
 // `chol`, `W`: what the default s0_k is formed from (read only when vt->s0 is NULL)
 int check_vol_target(const mcp_params* prm, const mcp_vol_target* vt, const float* chol, const float* W);
 int check_drift_uncertainty(int n_assets, const mcp_drift_uncertainty* du);
+int check_downside(const mcp_downside* req, const mcp_downside_stats* stats_out);
 // Every rule a request meets: each feature's own arguments, then which features combine (MCP_E_UNSUPPORTED), then the outputs.
 // `ln`: an mcp_launch_paths* call, whose device arrays are checked instead of the host arrays of an mcp_simulate* call.
 int check_request(const mcp_params* prm, const Request& rq, uint64_t n_paths, const Launch* ln = nullptr, uint64_t path_begin = 0);
@@ -302,6 +311,22 @@ struct Counted {
   uint64_t* hist_out2;
 };
 Counted counted_of(const mcp_params* prm, const Request& rq);
+
+// ---- downside and shape statistics (SPEC.md 5.22) ----
+// What mcp_ctx_request_downside leaves on a context.  The next call that walks paths takes it, and taking disarms: whatever becomes of
+// that call, the one after it finds nothing and writes nothing.
+struct DownsideArm {
+  bool on = false;
+  double tau = 0.0;
+  bool use_rf = false;
+  mcp_downside_sums* sums_out = nullptr;
+  mcp_downside_stats* stats_out = nullptr;
+  mcp_downside_stats* hz_stats_out = nullptr;
+  void arm(const mcp_downside& req, mcp_downside_sums* sums, mcp_downside_stats* stats, mcp_downside_stats* hz_stats);
+  DownsideArm take();
+};
+// a += b, field by field: how the records of shards add up, in shard order
+void downside_add(mcp_downside_sums& a, const mcp_downside_sums& b);
 
 // ---- the plan of a call: which shard does what in which tile ----
 // Bytes per path and portfolio that the tile budget counts: 4 of V_T, 4 per horizon row, 4 of the second array, 4 per integer record

@@ -4,6 +4,7 @@
 #include <stdint.h>
 
 #include "../../include/mcport.h"
+#include "../../include/mcport_downside.h"
 #include "mcp_host.h"
 #include "mcp_route.h"
 
@@ -109,6 +110,19 @@ hipError_t launch_sum_u64(unsigned long long* const* bufs, int nsrc, size_t word
 // out[k][j] = sum over the `blocks` workgroup records of portfolio k of entry j, in block order (SPEC.md 5.9); partials is
 // [K][blocks][len], out [K][len]
 hipError_t launch_attr_merge(const double* partials, int K, int blocks, int len, double* out, hipStream_t s);
+
+// ---- downside and shape statistics (SPEC.md 5.22) ----
+constexpr int DOWNSIDE_GRID_CAP = 512;   // workgroups per row; a row of more than 4 * 256 * 512 values is grid-strided
+constexpr int DOWNSIDE_BLOCK_VALUES = 1024;   // one 16-byte load per lane of a 256-thread workgroup
+// workgroups per row of the downside pass over n values: a function of n alone (include/mcport_downside.h, mcp_downside_grid)
+__host__ __device__ inline int downside_grid(uint64_t n) {
+  const uint64_t g = (n + DOWNSIDE_BLOCK_VALUES - 1) / DOWNSIDE_BLOCK_VALUES;
+  return (int)(g < 1 ? 1 : (g < (uint64_t)DOWNSIDE_GRID_CAP ? g : (uint64_t)DOWNSIDE_GRID_CAP));
+}
+// sums[r] = the raw record of row r of the [rows][stride] binary32 array `values` over its n live values, about pivot[r] (NULL: 0)
+// and tau: one mcp_downside_sums per row and workgroup into `partials` ([rows][downside_grid(n)]), then added in block order
+hipError_t launch_downside(const mcp_params& prm, const float* values, uint64_t stride, uint64_t n, int rows, const double* pivot,
+                           double tau, mcp_downside_sums* partials, mcp_downside_sums* sums, hipStream_t s);
 
 hipError_t launch_sweep_hist(int N, int R, int P, const double* returns, const double* mean, const double* cov,
                              const double* W, double rf, uint64_t rank_lo, uint64_t rank_hi, double gamma,

@@ -735,4 +735,116 @@ hipError_t launch_attr_merge(const double* partials, int K, int blocks, int len,
   return hipGetLastError();
 }
 
+// ---- downside and shape statistics (SPEC.md 5.22) --------------------------------------------------------------------------------
+// One streaming pass over the [rows][stride] values beside pass0: x as terminal_to_x forms it (one IEEE division per element, or
+// expm1), d = x - c and e = x - tau, and per lane the nine sums and three counts of mcp_downside_sums; every product is rounded once
+// (-ffp-contract=off) and a summand outside its set enters as + 0.0.  blockIdx.y is the row, blockIdx.x the workgroup of the row: wave
+// sums by shuffle, the four waves in LDS, then field j of the workgroup's record by thread j.  The record is twelve 8-byte words, the
+// counts first.  4 B of traffic against one fp64 division and some twenty fp64 operations per element.
+constexpr int DS_WORDS = 12;
+static_assert(sizeof(mcp_downside_sums) == DS_WORDS * 8, "mcp_downside_sums is twelve 8-byte words");
+
+template <bool LOGC>
+__global__ void __launch_bounds__(SB) downside_kernel(double v0d, const float* __restrict__ values, uint64_t stride, uint64_t n,
+                                                      const double* __restrict__ pivot, double tau,
+                                                      mcp_downside_sums* __restrict__ partials) {
+  __shared__ double red[4][DS_WORDS];
+  const int G = gridDim.x, b = blockIdx.x;
+  const size_t r = blockIdx.y;
+  const float* __restrict__ src = values + r * stride;
+  const double c = pivot ? pivot[r] : 0.0;
+  double s1 = 0.0, s2 = 0.0, s3 = 0.0, s4 = 0.0, b1 = 0.0, b2 = 0.0, l1 = 0.0, l2 = 0.0, u1 = 0.0;
+  unsigned long long m = 0, nb = 0, na = 0;
+
+  auto one = [&](float v) {
+    const double x = terminal_to_x(v, v0d, LOGC ? MCP_COMPOUND_LOG : MCP_COMPOUND_SIMPLE);
+    const double d = x - c, e = x - tau;
+    const double d2 = d * d, e2 = e * e;
+    const bool lo = e < 0.0, hi = e > 0.0;
+    m += 1; nb += lo ? 1 : 0; na += hi ? 1 : 0;
+    s1 += d; s2 += d2; s3 += d2 * d; s4 += d2 * d2;
+    b1 += lo ? d : 0.0; b2 += lo ? d2 : 0.0;
+    l1 += lo ? e : 0.0; l2 += lo ? e2 : 0.0;
+    u1 += hi ? e : 0.0;
+  };
+
+  // rows start at arbitrary element offsets: scalar head up to 16-byte alignment, float4 body, scalar tail (as hist_kernel)
+  const uint64_t head = n ? (uint64_t)((4 - (((uintptr_t)src >> 2) & 3)) & 3) : 0;
+  const uint64_t hd = head < n ? head : n;
+  const uint64_t nvec = (n - hd) / 4;
+  const float4* __restrict__ vsrc = (const float4*)(src + hd);
+  const uint64_t vstep = (uint64_t)G * SB;
+  uint64_t j = (uint64_t)b * SB + threadIdx.x;
+  for (; j + vstep < nvec; j += 2 * vstep) {              // two 16-byte loads in flight per lane
+    const float4 q0 = vsrc[j], q1 = vsrc[j + vstep];
+    one(q0.x); one(q0.y); one(q0.z); one(q0.w);
+    one(q1.x); one(q1.y); one(q1.z); one(q1.w);
+  }
+  for (; j < nvec; j += vstep) {
+    const float4 q0 = vsrc[j];
+    one(q0.x); one(q0.y); one(q0.z); one(q0.w);
+  }
+  if (b == 0) {                                           // head and tail scalars: at most 6 elements of the row
+    if (threadIdx.x < hd) one(src[threadIdx.x]);
+    const uint64_t t0 = hd + 4 * nvec;
+    if (t0 + threadIdx.x < n) one(src[t0 + threadIdx.x]);
+  }
+
+  const double w[DS_WORDS] = {wave_sum((double)m), wave_sum((double)nb), wave_sum((double)na),   // < 2^53: exact
+                              wave_sum(s1), wave_sum(s2), wave_sum(s3), wave_sum(s4), wave_sum(b1), wave_sum(b2),
+                              wave_sum(l1), wave_sum(l2), wave_sum(u1)};
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  if (lane == 0) {
+#pragma unroll
+    for (int i = 0; i < DS_WORDS; i++) red[wv][i] = w[i];
+  }
+  __syncthreads();
+  if (threadIdx.x < DS_WORDS) {
+    const int i = threadIdx.x;
+    const double t = (red[0][i] + red[1][i]) + (red[2][i] + red[3][i]);
+    unsigned long long* out = (unsigned long long*)(partials + (r * (size_t)G + b));
+    out[i] = i < 3 ? (unsigned long long)t : (unsigned long long)__double_as_longlong(t);
+  }
+}
+
+// the workgroups' records of one row in a fixed order: grid = rows, one wave; lane l adds records l, l + 64, ... in increasing block
+// order (at most DOWNSIDE_GRID_CAP / 64 = 8 of them, neighbouring lanes on neighbouring records), then the wave's butterfly.  (One
+// thread per word walking all 512 records is a chain of 512 dependent loads: the launch took 150 us over 10^6 values that way.)
+__global__ void __launch_bounds__(64) downside_merge_kernel(const mcp_downside_sums* __restrict__ partials, int G,
+                                                            mcp_downside_sums* __restrict__ sums) {
+  const mcp_downside_sums* __restrict__ src = partials + (size_t)blockIdx.x * G;
+  mcp_downside_sums a = {};
+  for (int b = threadIdx.x; b < G; b += 64) {
+    const mcp_downside_sums p = src[b];
+    a.n += p.n; a.n_below += p.n_below; a.n_above += p.n_above;
+    a.s1 += p.s1; a.s2 += p.s2; a.s3 += p.s3; a.s4 += p.s4;
+    a.b1 += p.b1; a.b2 += p.b2; a.l1 += p.l1; a.l2 += p.l2; a.u1 += p.u1;
+  }
+  mcp_downside_sums o;
+  o.n = (unsigned long long)wave_sum((double)a.n);                 // < 2^53: exact
+  o.n_below = (unsigned long long)wave_sum((double)a.n_below);
+  o.n_above = (unsigned long long)wave_sum((double)a.n_above);
+  o.s1 = wave_sum(a.s1); o.s2 = wave_sum(a.s2); o.s3 = wave_sum(a.s3); o.s4 = wave_sum(a.s4);
+  o.b1 = wave_sum(a.b1); o.b2 = wave_sum(a.b2); o.l1 = wave_sum(a.l1); o.l2 = wave_sum(a.l2); o.u1 = wave_sum(a.u1);
+  if (threadIdx.x == 0) sums[blockIdx.x] = o;
+}
+
+hipError_t launch_downside(const mcp_params& prm, const float* values, uint64_t stride, uint64_t n, int rows, const double* pivot,
+                           double tau, mcp_downside_sums* partials, mcp_downside_sums* sums, hipStream_t s) {
+  if (rows < 1) return hipErrorInvalidValue;
+  const int G = downside_grid(n);
+  const double v0d = (double)(float)prm.v0;
+  for (int r0 = 0; r0 < rows; r0 += 65535) {             // gridDim.y holds at most 65535 rows
+    const int nr = rows - r0 < 65535 ? rows - r0 : 65535;
+    const dim3 grid((unsigned)G, (unsigned)nr);
+    const float* v = values + (size_t)r0 * stride;
+    const double* p = pivot ? pivot + r0 : nullptr;
+    mcp_downside_sums* out = partials + (size_t)r0 * G;
+    if (prm.compounding == MCP_COMPOUND_LOG) downside_kernel<true><<<grid, SB, 0, s>>>(v0d, v, stride, n, p, tau, out);
+    else downside_kernel<false><<<grid, SB, 0, s>>>(v0d, v, stride, n, p, tau, out);
+  }
+  downside_merge_kernel<<<(unsigned)rows, 64, 0, s>>>(partials, G, sums);
+  return hipGetLastError();
+}
+
 }  // namespace mcp

@@ -81,7 +81,9 @@ _UNCERTAIN_CHOICE = ("mcp_simulate_uncertain", "drift_uncertainty is not combine
 _KEYWORD_GROUP = {"rows": "bt", "dof": "st", "period": "rb", "drawdown": "dd", "horizons": "hz_in", "flows": "cf", "overlay": "ov",
                   "garch": "gv", "attribution": "attr", "antithetic": "pairs", "filtered": "ft", "jumps": "jp", "regimes": "rs",
                   "glide": "gl", "protect": "pt", "spending": "sp", "lifetime": "life", "tolerance": "tb", "vol_target": "vt", "underwater": "uw",
-                  "drift_uncertainty": "du"}
+                  "drift_uncertainty": "du",
+                  # SPEC.md 5.22: no argument of an entry point -- the request arms the context, which every entry point takes
+                  "downside": "ctx"}
 
 
 class Context:
@@ -130,8 +132,8 @@ class Context:
               block: float = 1.0, dof=None, period=None, cost: float = 0.0, drawdown: bool = False, horizons=None, levels=(),
               flows=None, target=None, overlay=None, garch=None, attribution=False, antithetic=False, filtered=None, jumps=None, regimes=None,
               glide=None, protect=None, spending=None, lifetime=None, tolerance=None, vol_target=None, underwater=None,
-              drift_uncertainty=None):
-        """The one library call behind every simulate_* method: drift uncertainty (drift_uncertainty: the binary32 factor M [N, N] of uncertainty.drift_factor, SPEC.md 2.7 / 4.21; on Gaussian draws with the drawdown, horizons or flows), the time under water (underwater: the levels in percent of the two counters' order statistics, SPEC.md 4.20 / 5.20; needs `drawdown`), a volatility target (vol_target: the (target, decay, cap, rate, spread, s0 or None) of voltarget.check_vol_target, SPEC.md 4.19 / 5.19; `target` is then its second count, and without `drawdown` the call leaves the exposure record), tolerance bands (tolerance: (every, cost, tol float32 [K, N], levels in percent of the trade counts' order statistics), SPEC.md 4.18 / 5.18; the rule carries its own period and cost, so not with `period`), the lifetime (lifetime: the levels in percent of its order statistics, SPEC.md 4.17 / 5.17; needs flows or spending), a spending rule (spending: the (rate, every, down, up, inflation, first or None) of check_spending; `target` is then its second count), floor protection (protect: the (floor, multiplier, rate, cap, ratchet) of check_protect; `target` is then its second count), two regimes (regimes: the (p01, p10, start, mu1, chol1) of check_regimes), market jumps (jumps: the (intensity, mean, std, loading or None) of check_jumps), GARCH volatility (garch: the (alpha, beta, h0) of check_garch), an option overlay (overlay: the triple of check_overlay), cash flows (flows, target), Student-t draws (dof), rebalancing
+              drift_uncertainty=None, downside=None):
+        """The one library call behind every simulate_* method: downside and shape statistics (downside: True for the threshold rf or the threshold tau, SPEC.md 5.22; the request arms the context and rides whatever call this is, so it combines with every keyword below), drift uncertainty (drift_uncertainty: the binary32 factor M [N, N] of uncertainty.drift_factor, SPEC.md 2.7 / 4.21; on Gaussian draws with the drawdown, horizons or flows), the time under water (underwater: the levels in percent of the two counters' order statistics, SPEC.md 4.20 / 5.20; needs `drawdown`), a volatility target (vol_target: the (target, decay, cap, rate, spread, s0 or None) of voltarget.check_vol_target, SPEC.md 4.19 / 5.19; `target` is then its second count, and without `drawdown` the call leaves the exposure record), tolerance bands (tolerance: (every, cost, tol float32 [K, N], levels in percent of the trade counts' order statistics), SPEC.md 4.18 / 5.18; the rule carries its own period and cost, so not with `period`), the lifetime (lifetime: the levels in percent of its order statistics, SPEC.md 4.17 / 5.17; needs flows or spending), a spending rule (spending: the (rate, every, down, up, inflation, first or None) of check_spending; `target` is then its second count), floor protection (protect: the (floor, multiplier, rate, cap, ratchet) of check_protect; `target` is then its second count), two regimes (regimes: the (p01, p10, start, mu1, chol1) of check_regimes), market jumps (jumps: the (intensity, mean, std, loading or None) of check_jumps), GARCH volatility (garch: the (alpha, beta, h0) of check_garch), an option overlay (overlay: the triple of check_overlay), cash flows (flows, target), Student-t draws (dof), rebalancing
         (period, cost), bootstrap rows (rows, block) or Gaussian draws (mu, chol), with the drawdown or horizons.  Allocates the
         outputs that were asked for and passes NULL for the rest -> _Outputs, None where not asked for (terminal, qd,
         horizon_terminal: with `store` only; counts, hz_counts: with `flows` only; attr [K, N] records of ATTR_DTYPE and attr_counts
@@ -147,7 +149,7 @@ class Context:
                                    ("protect", protect is not None), ("spending", spending is not None),
                                    ("lifetime", lifetime is not None), ("tolerance", tolerance is not None),
                                    ("vol_target", vol_target is not None), ("underwater", underwater is not None),
-                                   ("drift_uncertainty", drift_uncertainty is not None)) if on]
+                                   ("drift_uncertainty", drift_uncertainty is not None), ("downside", downside is not None)) if on]
         has = set(given).issuperset
         entry, refusal = _UNCERTAIN_CHOICE if drift_uncertainty is not None else _UNDERWATER_CHOICE if underwater is not None else _BAND_CHOICE if tolerance is not None else _LIFE_CHOICE if lifetime is not None else _VOLTARGET_CHOICE if vol_target is not None else next((e, r) for needs, e, r in _ENTRY_CHOICE if has(needs))
         groups = next(t[entry] for t in (_ffi.SIMULATE_ENTRIES, _ffi.EXTENSION_ENTRIES, _ffi.SPEND_ENTRIES, _ffi.LIFE_ENTRIES,
@@ -246,11 +248,28 @@ class Context:
             if isinstance(v, np.ndarray):
                 return v if group.endswith("*") else _ffi.ptr(v)
             return ctypes.byref(v) if isinstance(v, ctypes.Structure) else v
-        rc = getattr(_ffi.lib(), entry)(*(arg(g, v) for g in groups for v in vals[g.rstrip("*")]))
+        ds_stats = ds_sums = ds_hz_stats = ds_tau = None
+        if downside is not None:                               # SPEC.md 5.22: arm the context; the call below takes the request
+            ds_tau = float(prm.rf) if downside is True else float(downside)
+            ds_stats, ds_sums = np.zeros(K, _ffi.DOWNSIDE_STATS_DTYPE), np.zeros(K, _ffi.DOWNSIDE_SUMS_DTYPE)
+            ds_hz_stats = np.zeros((H, K), _ffi.DOWNSIDE_STATS_DTYPE) if H else None
+            _ffi.check(_ffi.lib().mcp_ctx_request_downside(self._h, ctypes.byref(_ffi.McpDownside(ds_tau, int(downside is True), 0)),
+                                                           _ffi.ptr(ds_sums), _ffi.ptr(ds_stats), _ffi.ptr(ds_hz_stats)))
+        try:
+            rc = getattr(_ffi.lib(), entry)(*(arg(g, v) for g in groups for v in vals[g.rstrip("*")]))
+        except BaseException:
+            if downside is not None:                           # the call never reached the library: withdraw the request
+                _ffi.lib().mcp_ctx_request_downside(self._h, None, None, None, None)
+            raise
+        if rc < 0 and downside is not None:                    # a call refused before its rules were looked at leaves the request in place
+            why = _ffi.lib().mcp_last_error()
+            _ffi.lib().mcp_ctx_request_downside(self._h, None, None, None, None)
+            raise _ffi.McpError(f"libmcport error {rc}: {why.decode('utf-8', 'replace')}")
         _ffi.check(rc)
         return _Outputs(stats, dd_stats, hz_stats, bands, term, raw, hz_term, counts, hz_counts, attr, attr_counts, contrib, pairs,
                         wd_stats, withdrawn, life_hist, life_sum, life_q, life, trade_hist, trade_sum, trade_q, trades, turnover_stats, turnover,
-                        exposure_stats, exposure, uw_longest_hist, uw_current_hist, uw_sums, uw_q, uw_longest, uw_current)
+                        exposure_stats, exposure, uw_longest_hist, uw_current_hist, uw_sums, uw_q, uw_longest, uw_current,
+                        ds_stats, ds_sums, ds_hz_stats, ds_tau)
 
     def simulate_uncertain(self, prm: _ffi.McpParams, factor, mu, chol, W, seed: int, path_begin: int, n_paths: int, store: bool,
                            drawdown: bool = False, horizons=None, levels=(), flows=None, target=None):
@@ -377,12 +396,12 @@ class Context:
                           levels=levels, regimes=regimes)
 
     def simulate_filtered(self, prm: _ffi.McpParams, filtered, garch, W, block: float, seed: int, path_begin: int, n_paths: int,
-                          store: bool, horizons=None, levels=()):
+                          store: bool, horizons=None, levels=(), downside=None):
         """simulate_bootstrap[_horizons]() on filtered rows (SPEC.md 2.4 / 4.11; include/mcport.h, mcp_simulate_filtered; simple
         compounding only): `filtered` is the binary32 (mu [N], resid [R, N], shock [R]) triple, `garch` (alpha, beta, h0) -> _Outputs;
         the horizon entries are None without horizons."""
         return self._call(prm, W, seed, path_begin, n_paths, store, block=block, horizons=horizons, levels=levels, garch=garch,
-                          filtered=filtered)
+                          filtered=filtered, downside=downside)
 
     def simulate_attribution(self, prm: _ffi.McpParams, mu, chol, W, seed: int, path_begin: int, n_paths: int, store: bool, dof=None,
                              garch=None):
@@ -472,10 +491,13 @@ class Context:
 # binary32 contributions [K, N, n].  With antithetic pairs the records of SPEC.md 5.10 (pairs [K] of PAIR_DTYPE).  With a spending rule
 # the record of the total paid out (wd_stats [K]) and, stored, the binary32 withdrawn [K, n] (SPEC.md 5.16).  With a volatility target
 # and no drawdown the record of the summed exposure (exposure_stats [K], over Y - 1) and, stored, the binary32 exposure [K, n] (5.19).
+# With a downside request the records of SPEC.md 5.22 (downside_stats [K] of DOWNSIDE_STATS_DTYPE, downside_sums [K] of
+# DOWNSIDE_SUMS_DTYPE, downside_hz_stats [H, K] with horizons) and the threshold they are about (downside_tau).
 _Outputs = collections.namedtuple("_Outputs", "stats dd_stats hz_stats bands terminal qd horizon_terminal counts hz_counts attr "
                                   "attr_counts contributions pairs wd_stats withdrawn life_hist life_sum life_q life trade_hist trade_sum trade_q trades "
-                                  "turnover_stats turnover exposure_stats exposure uw_longest_hist uw_current_hist uw_sums uw_q uw_longest uw_current",
-                                  defaults=(None,) * 26)
+                                  "turnover_stats turnover exposure_stats exposure uw_longest_hist uw_current_hist uw_sums uw_q uw_longest uw_current "
+                                  "downside_stats downside_sums downside_hz_stats downside_tau",
+                                  defaults=(None,) * 30)
 
 
 def check_cashflow(cashflow, target, n_steps):
@@ -1021,6 +1043,8 @@ def antithetic_to_dict(rec) -> dict:
 # checked, so the same rule wins when two apply.  The C side states the same rules for the library (check_request).
 _FLAGS = ("drawdown", "attribution", "antithetic", "fold", "native_math", "lifetime", "underwater")
 _PATHS_COMBINE = {
+    # SPEC.md 5.22: a reduction of what the call stores anyway, so no name is excluded
+    "downside": ("downside reads the values of whatever walk the call runs", (), True),
     "drift_uncertainty": ("drift_uncertainty needs Gaussian draws, constant weights, the spec's normals and the unfolded recurrence",
                           ("underwater", "vol_target", "tolerance", "spending", "protect", "glide", "regimes", "jumps", "garch", "dof",
                            "rebalance", "overlay", "attribution", "antithetic", "lifetime", "fold", "native_math"), True),
@@ -1100,7 +1124,7 @@ def simulate_paths(mu, cov, weights, n_steps=252, n_paths=10_000, seed=0, v0=1.0
                    horizons=None, bands=(), rebalance=None, rebalance_cost=0.0, dof=None, cashflow=None, target=None,
                    overlay=None, spot=None, garch=None, attribution=False, antithetic=False, jumps=None, regimes=None, glide=None,
                    protect=None, spending=None, lifetime=False, lifetime_levels=(5, 25, 50), tolerance=None, tolerance_levels=(5, 50, 95),
-                   vol_target=None, underwater=False, underwater_levels=(50, 95), drift_uncertainty=None):
+                   vol_target=None, underwater=False, underwater_levels=(50, 95), drift_uncertainty=None, downside=None):
     """Simulate `n_paths` correlated return paths and reduce them to risk statistics.
 
     mu [N], cov [N,N] are per-step mean and covariance (the reference's `mean_returns`, `cov_matrix`
@@ -1340,24 +1364,41 @@ def simulate_paths(mu, cov, weights, n_steps=252, n_paths=10_000, seed=0, v0=1.0
     underwater, vol_target, tolerance, spending, protect, glide, regimes, jumps, garch, dof, rebalance, overlay, attribution,
     antithetic, lifetime, fold or native_math (ValueError), on bootstrap or filtered rows, in simulate_sweep, in PathEngine and at
     the mcp_launch_* level.
+
+    downside=None (default): the statistics above say how wide the distribution is and how bad its tail, not how it is shaped.
+    downside=True | tau: one more streaming reduction over the values the call keeps on the device anyway (SPEC.md 5.22), whatever
+    walk produced them and with or without `store`.  tau is the threshold in units of x, True takes rf (the reference subtracts
+    risk_free before it looks at the sign, app.py:238-243).  Every dict gains 'downside' {sortino (the reference's ratio: (mean -
+    tau) / downside_std, not annualised), downside_std (np.std(ddof=1) of the excess returns below zero; 1e-4 when there are none,
+    NaN for one), downside_deviation (the target semideviation sqrt(mean min(x - tau, 0)^2)), sortino_target (on that deviation),
+    p_below (the probability of x < tau: of a loss at tau = 0), mean_shortfall (mean of x - tau over those paths), omega (gains over
+    losses about tau), skewness, excess_kurtosis (population forms, scipy.stats' defaults), mean, threshold, sums (the raw record)}
+    and, with horizons, 'horizons': a list of the same dicts per horizon, so that p_below runs along the fan.  Every other entry of
+    the result is the call's without the keyword, bit for bit.  downside.normal_law gives the exact figures of a normal x.  Combines
+    with every other keyword, devices and shard="portfolios".  Not with as_array (the records live in the dicts; ValueError), in
+    simulate_sweep, in PathEngine; mcp_launch_downside is the enqueue-only form.
     """
+    from .downside import check_downside
+    ds = check_downside(downside)
+    if ds is not None and as_array:
+        raise ValueError("downside fills the 'downside' block of the result dicts: not with as_array")
     if drift_uncertainty is not None:
         return _simulate_uncertain(mu, cov, weights, n_steps, n_paths, seed, v0, compounding, rf, alpha, devices, store, path_begin, chol,
                                    native_math, as_array, fold, shard, context, drawdown, horizons, bands, rebalance, rebalance_cost, dof,
                                    cashflow, target, overlay, spot, garch, attribution, antithetic, jumps, regimes, glide, protect, spending,
-                                   lifetime, tolerance, vol_target, underwater, drift_uncertainty)
+                                   lifetime, tolerance, vol_target, underwater, drift_uncertainty, ds)
     if not isinstance(underwater, (bool, np.bool_)):
         raise ValueError(f"underwater must be True or False, got {underwater!r}")
     if underwater:
         return _simulate_underwater(mu, cov, weights, n_steps, n_paths, seed, v0, compounding, rf, alpha, devices, store, path_begin, chol,
                                     native_math, as_array, fold, shard, context, drawdown, horizons, bands, rebalance, rebalance_cost, dof,
                                     cashflow, target, overlay, spot, garch, attribution, antithetic, jumps, regimes, glide, protect, spending,
-                                    lifetime, tolerance, vol_target, underwater_levels)
+                                    lifetime, tolerance, vol_target, underwater_levels, ds)
     if vol_target is not None:
         return _simulate_vol_target(mu, cov, weights, n_steps, n_paths, seed, v0, compounding, rf, alpha, devices, store, path_begin, chol,
                                     native_math, as_array, fold, shard, context, drawdown, horizons, bands, rebalance, rebalance_cost, dof,
                                     cashflow, target, overlay, spot, garch, attribution, antithetic, jumps, regimes, glide, protect, spending,
-                                    lifetime, tolerance, vol_target)
+                                    lifetime, tolerance, vol_target, ds)
     from .lifetime import check_lifetime
     lt = check_lifetime(lifetime, lifetime_levels, n_steps)
     if lt is not None and cashflow is None and spending is None:
@@ -1374,7 +1415,7 @@ def simulate_paths(mu, cov, weights, n_steps=252, n_paths=10_000, seed=0, v0=1.0
         tol, tlv = check_tolerance(tolerance, tolerance_levels, W.shape, n_steps, period)
         prm, ctx = _setup(mu32.shape[0], n_steps, W.shape[0], compounding, v0, alpha, rf, False, False, devices, shard, context)
         out = ctx._call(prm, W, int(seed), int(path_begin), int(n_paths), store, mu=mu32, chol=L, horizons=steps, levels=levels,
-                        tolerance=(period, cost, tol, tlv))
+                        tolerance=(period, cost, tol, tlv), downside=ds)
         return _with_tolerance(_result(out, np.asarray(weights).ndim == 1, store, as_array, steps, levels, compounding), out, tol, period,
                                tlv, store, as_array)
     kw = dict(spending=spending, protect=protect, glide=glide, regimes=regimes, jumps=jumps, antithetic=antithetic, attribution=attribution, garch=garch, overlay=overlay,
@@ -1438,7 +1479,7 @@ def simulate_paths(mu, cov, weights, n_steps=252, n_paths=10_000, seed=0, v0=1.0
     out = ctx._call(prm, W, int(seed), int(path_begin), int(n_paths), store, mu=mu32, chol=L, dof=dof, period=period, cost=cost,
                     drawdown=drawdown, horizons=steps, levels=levels, flows=flows, target=target if pv is None and sv is None else goal,
                     overlay=ov, garch=gv, attribution=bool(attribution), antithetic=bool(antithetic), jumps=jv, regimes=rv, glide=gl, protect=pv,
-                    spending=sv, **({} if lt is None else {"lifetime": lt}))
+                    spending=sv, downside=ds, **({} if lt is None else {"lifetime": lt}))
     if sv is not None:                                     # the counts are the 'spending' block's, not a 'cashflow' block's
         res = _spending_result(out, sv, v0, np.asarray(weights).ndim == 1, store, as_array, steps, levels, compounding, goal)
     elif pv is not None:                                     # the counts are the 'protect' block's, not a 'cashflow' block's
@@ -1466,7 +1507,7 @@ def simulate_paths(mu, cov, weights, n_steps=252, n_paths=10_000, seed=0, v0=1.0
 
 def _simulate_vol_target(mu, cov, weights, n_steps, n_paths, seed, v0, compounding, rf, alpha, devices, store, path_begin, chol, native_math,
                          as_array, fold, shard, context, drawdown, horizons, bands, rebalance, rebalance_cost, dof, cashflow, target, overlay,
-                         spot, garch, attribution, antithetic, jumps, regimes, glide, protect, spending, lifetime, tolerance, vol_target):
+                         spot, garch, attribution, antithetic, jumps, regimes, glide, protect, spending, lifetime, tolerance, vol_target, downside=None):
     """simulate_paths with a volatility target (SPEC.md 4.19 / 5.19): the rules of what it combines with, then the draws' own rules
     in simulate_paths' order, the call and the 'vol_target' block."""
     from .voltarget import check_vol_target, vol_target_blocks
@@ -1496,7 +1537,7 @@ def _simulate_vol_target(mu, cov, weights, n_steps, n_paths, seed, v0, compoundi
     vts = _ffi.make_vol_target(*vt)
     consts, s0 = _ffi.vol_target_consts(prm, vts, L, W)    # the library's rules, s0's among them, before anything is launched
     out = ctx._call(prm, W, int(seed), int(path_begin), int(n_paths), store, mu=mu32, chol=L, dof=dof, drawdown=bool(drawdown), horizons=steps,
-                    levels=levels, target=goal, garch=gv, jumps=jv, vol_target=vt)
+                    levels=levels, target=goal, garch=gv, jumps=jv, vol_target=vt, downside=downside)
     res = _result(out._replace(counts=None, hz_counts=None), np.asarray(weights).ndim == 1, store, as_array, steps, levels, compounding)
     if as_array:
         return ((res if isinstance(res, tuple) else (res,)) + ((out.counts,) if out.hz_counts is None else (out.counts, out.hz_counts))
@@ -1512,7 +1553,7 @@ def _simulate_vol_target(mu, cov, weights, n_steps, n_paths, seed, v0, compoundi
 def _simulate_uncertain(mu, cov, weights, n_steps, n_paths, seed, v0, compounding, rf, alpha, devices, store, path_begin, chol, native_math,
                         as_array, fold, shard, context, drawdown, horizons, bands, rebalance, rebalance_cost, dof, cashflow, target, overlay,
                         spot, garch, attribution, antithetic, jumps, regimes, glide, protect, spending, lifetime, tolerance, vol_target,
-                        underwater, drift_uncertainty):
+                        underwater, drift_uncertainty, downside=None):
     """simulate_paths with drift uncertainty (SPEC.md 2.7 / 4.21 / 5.21): the rules of what it combines with, then the underlying
     call's own rules in simulate_paths' order, the call and the 'drift_uncertainty' block."""
     from .uncertainty import check_drift_uncertainty, uncertainty_blocks
@@ -1536,7 +1577,7 @@ def _simulate_uncertain(mu, cov, weights, n_steps, n_paths, seed, v0, compoundin
         raise ValueError(f"drift_uncertainty: the factor is {M.shape}, the market has {L.shape[0]} assets")
     prm, ctx = _setup(mu32.shape[0], n_steps, W.shape[0], compounding, v0, alpha, rf, False, False, devices, shard, context)
     out = ctx._call(prm, W, int(seed), int(path_begin), int(n_paths), store, mu=mu32, chol=L, drawdown=bool(drawdown), horizons=steps,
-                    levels=levels, flows=flows, target=target, drift_uncertainty=M)
+                    levels=levels, flows=flows, target=target, drift_uncertainty=M, downside=downside)
     res = _result(out, np.asarray(weights).ndim == 1, store, as_array, steps, levels, compounding, flows, target)
     if as_array:
         return res
@@ -1548,7 +1589,7 @@ def _simulate_uncertain(mu, cov, weights, n_steps, n_paths, seed, v0, compoundin
 def _simulate_underwater(mu, cov, weights, n_steps, n_paths, seed, v0, compounding, rf, alpha, devices, store, path_begin, chol, native_math,
                          as_array, fold, shard, context, drawdown, horizons, bands, rebalance, rebalance_cost, dof, cashflow, target, overlay,
                          spot, garch, attribution, antithetic, jumps, regimes, glide, protect, spending, lifetime, tolerance, vol_target,
-                         underwater_levels):
+                         underwater_levels, downside=None):
     """simulate_paths with the time under water (SPEC.md 4.20 / 5.20): the rules of what it combines with, then the draws' own rules in
     simulate_paths' order, the call and the 'underwater' block."""
     from .underwater import check_underwater, underwater_blocks
@@ -1579,7 +1620,7 @@ def _simulate_underwater(mu, cov, weights, n_steps, n_paths, seed, v0, compoundi
     mu32, L, W = prepare_inputs(mu, cov, weights, chol)
     prm, ctx = _setup(mu32.shape[0], n_steps, W.shape[0], compounding, v0, alpha, rf, False, False, devices, shard, context)
     out = ctx._call(prm, W, int(seed), int(path_begin), int(n_paths), store, mu=mu32, chol=L, dof=dof, drawdown=True, garch=gv, jumps=jv,
-                    underwater=lv)
+                    underwater=lv, downside=downside)
     res = _result(out, np.asarray(weights).ndim == 1, store, as_array, None, (), compounding)
     if as_array:
         return ((res if isinstance(res, tuple) else (res,)) + (out.uw_longest_hist, out.uw_current_hist, out.uw_sums, out.uw_q)
@@ -1701,6 +1742,10 @@ def _result(out, single, store, as_array, steps, levels, compounding, flows=None
             return ((stats, term) if store else (stats,)) + (attr, attr_counts) + ((contrib,) if store else ())
         return (stats, term) if store else stats
     res = [stats_to_dict(stats[k]) for k in range(stats.shape[0])]
+    if out.downside_stats is not None:   # SPEC.md 5.22
+        from .downside import downside_blocks
+        for d, blk in zip(res, downside_blocks(out.downside_stats, out.downside_sums, out.downside_tau, out.downside_hz_stats)):
+            d["downside"] = blk
     for k, d in enumerate(res):
         if dd_stats is not None:
             d["drawdown"] = drawdown_to_dict(dd_stats[k])
@@ -1754,7 +1799,8 @@ def bootstrap_inputs(returns, weights):
 def simulate_bootstrap(returns, weights, n_steps=252, n_paths=10_000, block=1.0, seed=0, v0=1.0, compounding="simple",
                        rf=0.0, alpha=0.95, devices=None, store=False, path_begin=0, as_array=False, shard="auto", context=None,
                        horizons=None, bands=(), rebalance=None, rebalance_cost=0.0, cashflow=None, target=None, glide=None, spending=None,
-                       lifetime=False, lifetime_levels=(5, 25, 50), tolerance=None, tolerance_levels=(5, 50, 95), **unsupported):
+                       lifetime=False, lifetime_levels=(5, 25, 50), tolerance=None, tolerance_levels=(5, 50, 95), downside=None,
+                       **unsupported):
     """simulate_paths on paths resampled from the observed return rows instead of a normal model: the stationary block
     bootstrap of Politis & Romano (SPEC.md 2.1 / 4.4).  Every step of a path uses one whole row of `returns` (all assets of one
     date together), so fat tails, skew, the co-movement within a row and -- with a mean block length `block` > 1 -- short-range
@@ -1770,8 +1816,13 @@ def simulate_bootstrap(returns, weights, n_steps=252, n_paths=10_000, block=1.0,
     means; not with rebalance or compounding="log").  spending as in simulate_paths (SPEC.md 4.16, pivots of SPEC.md 5.16 on the
     row means; not with cashflow, glide, rebalance or compounding="log").  lifetime / lifetime_levels as in simulate_paths (SPEC.md
     4.17 / 5.17; with cashflow, with or without glide, or spending).  tolerance / tolerance_levels as in simulate_paths (SPEC.md 4.18 /
-    5.18, pivots of SPEC.md 5.4; not with cashflow, glide, spending or compounding="log").
+    5.18, pivots of SPEC.md 5.4; not with cashflow, glide, spending or compounding="log").  downside as in simulate_paths (SPEC.md
+    5.22; with every keyword here, not with as_array).
     """
+    from .downside import check_downside
+    ds = check_downside(downside)
+    if ds is not None and as_array:
+        raise ValueError("downside fills the 'downside' block of the result dicts: not with as_array")
     from .lifetime import check_lifetime
     lt = check_lifetime(lifetime, lifetime_levels, n_steps)
     if lt is not None and cashflow is None and spending is None:
@@ -1809,7 +1860,7 @@ def simulate_bootstrap(returns, weights, n_steps=252, n_paths=10_000, block=1.0,
         tol, tlv = check_tolerance(tolerance, tolerance_levels, W.shape, n_steps, period)
         prm, ctx = _setup(rows.shape[1], n_steps, W.shape[0], compounding, v0, alpha, rf, False, False, devices, shard, context)
         out = ctx._call(prm, W, int(seed), int(path_begin), int(n_paths), store, rows=rows, block=b, horizons=steps, levels=levels,
-                        tolerance=(period, cost, tol, tlv))
+                        tolerance=(period, cost, tol, tlv), downside=ds)
         return _with_tolerance(_result(out, np.asarray(weights).ndim == 1, store, as_array, steps, levels, compounding), out, tol, period,
                                tlv, store, as_array)
     kw = dict(spending=spending, glide=glide, cashflow=cashflow, rebalance=rebalance, compounding=compounding)
@@ -1833,7 +1884,7 @@ def simulate_bootstrap(returns, weights, n_steps=252, n_paths=10_000, block=1.0,
     rows, W = bootstrap_inputs(returns, weights)
     prm, ctx = _setup(rows.shape[1], n_steps, W.shape[0], compounding, v0, alpha, rf, False, False, devices, shard, context)
     out = ctx._call(prm, W, int(seed), int(path_begin), int(n_paths), store, rows=rows, block=b, period=period, cost=cost,
-                    horizons=steps, levels=levels, flows=flows, target=target if sv is None else goal, glide=gl, spending=sv,
+                    horizons=steps, levels=levels, flows=flows, target=target if sv is None else goal, glide=gl, spending=sv, downside=ds,
                     **({} if lt is None else {"lifetime": lt}))
     if sv is not None:
         res = _spending_result(out, sv, v0, np.asarray(weights).ndim == 1, store, as_array, steps, levels, compounding, goal)
@@ -1880,7 +1931,7 @@ def filtered_inputs(filtered, weights):
 
 def simulate_filtered(filtered, weights, n_steps=252, n_paths=10_000, garch=None, block=1.0, seed=0, v0=1.0, rf=0.0, alpha=0.95,
                       horizons=None, levels=(), devices=None, store=False, as_array=False, path_begin=0, shard="auto", context=None,
-                      **unsupported):
+                      downside=None, **unsupported):
     """Filtered historical simulation (Barone-Adesi, Giannopoulos & Vosper 1999; SPEC.md 2.4 / 4.11): simulate_bootstrap on rows
     that garch.filter_rows de-volatilised with the fitted GARCH(1,1) variance path, every draw re-scaled by the path's own simulated
     variance ratio h -- the empirical shocks of the bootstrap (tails, skew, assets that crash together) with the volatility
@@ -1893,7 +1944,11 @@ def simulate_filtered(filtered, weights, n_steps=252, n_paths=10_000, garch=None
     mean block length of simulate_bootstrap (1: classical FHS).  horizons / levels: simulate_paths' horizons / bands.  Returns what
     simulate_bootstrap returns for the same arguments (pivots of SPEC.md 5.11).  Simple compounding only: ValueError for
     compounding="log" and for the simulate_paths keywords that have no meaning here (dof, fold, native_math, drawdown, rebalance,
-    cashflow, overlay, attribution, antithetic)."""
+    cashflow, overlay, attribution, antithetic).  downside as in simulate_paths (SPEC.md 5.22; not with as_array)."""
+    from .downside import check_downside
+    ds = check_downside(downside)
+    if ds is not None and as_array:
+        raise ValueError("downside fills the 'downside' block of the result dicts: not with as_array")
     comp = unsupported.pop("compounding", "simple")
     if comp != "simple":
         raise ValueError(f"simulate_filtered compounds simply: not with compounding={comp!r}")
@@ -1912,7 +1967,7 @@ def simulate_filtered(filtered, weights, n_steps=252, n_paths=10_000, garch=None
     mu, resid, shock, W = filtered_inputs(filtered, weights)
     prm, ctx = _setup(resid.shape[1], n_steps, W.shape[0], "simple", v0, alpha, rf, False, False, devices, shard, context)
     out = ctx.simulate_filtered(prm, (mu, resid, shock), gv, W, b, int(seed), int(path_begin), int(n_paths), store, horizons=steps,
-                                levels=lv)
+                                levels=lv, downside=ds)
     return _result(out, np.asarray(weights).ndim == 1, store, as_array, steps, lv, "simple")
 
 
@@ -1947,6 +2002,8 @@ def simulate_sweep(mu, cov, weights=None, n_portfolios=2500, min_weights=None, m
         raise ValueError("simulate_sweep does not take underwater: call simulate_paths for the optimum")
     if kw.get("drift_uncertainty") is not None:
         raise ValueError("simulate_sweep does not take drift_uncertainty: call simulate_paths for the optimum")
+    if kw.get("downside") is not None:
+        raise ValueError("simulate_sweep does not take downside: the sweep returns record arrays -- call simulate_paths for the optimum")
     if kw.get("attribution"):
         raise ValueError("simulate_sweep does not take attribution: call simulate_paths for the optimum")
     kw.pop("attribution", None)
