@@ -719,7 +719,9 @@ int mcp_launch_paths_drawdown(const mcp_params *prm, const float *d_packed, cons
 /* mcp_launch_paths that also stores the values after the steps horizons[0..n_horizons) (host array, SPEC.md 4.3) into
  * d_horizon ([n_horizons][K][horizon_stride] floats, row h*K + k; horizon_stride >= n_paths).  Kernels and moment partials
  * as in mcp_launch_paths_drawdown.  To reduce one horizon row set: mcp_launch_pass0 over d_horizon with n_portfolios =
- * H*K and the [H*K] pivots of mcp_pivots at n_steps = h, then the usual scan / hist / final steps.
+ * H*K and the [H*K] pivots of mcp_pivots at n_steps = h, then the usual scan / hist / final steps.  Work buffers that serve
+ * both this and the launch's own K rows take the LARGER of mcp_ws_bytes(w, K, n) and mcp_ws_bytes(w, H*K, n), buffer by
+ * buffer: MCP_WS_BELOW does not grow with the rows (K = 9 needs 16,380 doubles, H*K = 27 only 16,362).
  * MCP_FLAG_FOLD / MCP_FLAG_NATIVE_MATH: MCP_E_UNSUPPORTED. */
 int mcp_launch_paths_horizons(const mcp_params *prm, const float *d_packed, const double *d_pivot, uint64_t seed,
                               uint64_t path_begin, uint64_t n_paths, float *d_terminal, uint64_t terminal_stride,
