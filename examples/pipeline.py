@@ -51,6 +51,12 @@ def main(paths, resample_rule="M", user_rf=3.0, investment=10000.0, seed=12345, 
         print(f"  {label}: Sortino {d['sortino']:.4f}  P(loss) {d['p_below']:.4f}  skewness {d['skewness']:+.4f}  "
               f"excess kurtosis {d['excess_kurtosis']:+.4f}")
     shape("Gaussian draws", sim)
+    # the optimum against equal weights on the same paths (SPEC.md 5.23): row 0 against row 1, the benchmark
+    pair = mcp.simulate_paths(mu_step, cov_step, np.stack([w, np.full(len(w), 1.0 / len(w))]), n_steps=af, n_paths=n_paths, seed=seed,
+                              v0=investment, rf=user_rf / 100, benchmark=1)
+    rel = pair[0]["relative"]
+    print(f"  against equal weights: tracking error {rel['tracking_error']:.4f}  IR {rel['information_ratio']:+.4f}  "
+          f"P(behind) {rel['p_under']:.4f}  relative CVaR95 {rel['active']['cvar']:+.4f}  down capture {rel['down_capture']:.4f}")
     dd = sim["drawdown"]                  # max drawdown of every path before the horizon (SPEC.md 4.2 / 5.1)
     print(f"  max drawdown: mean {dd['mean']:+.4f}  DaR95 {dd['dar']:+.4f}  CDaR95 {dd['cdar']:+.4f}  worst {dd['worst']:+.4f}")
     # which holding that risk comes from (SPEC.md 4.10 / 5.9): the same paths walked a second time, every asset's part of the CVaR

@@ -379,6 +379,29 @@ DOWNSIDE_SIGNATURES = {
     "mcp_ctx_request_downside": (_int, [_vp, ctypes.POINTER(McpDownside), _vp, _vp, _vp]),
 }
 
+# And for include/mcport_relative.h (SPEC.md 5.23): as the downside request, it arms a context and rides the next call.
+class McpRelative(ctypes.Structure):
+    """mcp_relative (include/mcport_relative.h): the benchmark's row of the call's W (SPEC.md 5.23)."""
+    _fields_ = [("bench", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
+# one mcp_relative_sums: the raw record of a row against its benchmark; one mcp_relative_stats: the finished record
+RELATIVE_SUMS_DTYPE = np.dtype([(f, np.uint64) for f in ("n", "n_under", "n_over", "n_up", "n_down")] +
+                               [(f, np.float64) for f in ("e1", "e2", "k1", "b1", "k2", "b2", "kb", "u1", "u2", "up_k", "up_b", "down_k",
+                                                          "down_b")])
+RELATIVE_STATS_DTYPE = np.dtype([(f, np.float64) for f in ("active_mean", "tracking_error", "information_ratio", "p_under", "p_over",
+                                                           "mean_underperformance", "relative_downside_deviation", "beta", "alpha",
+                                                           "correlation", "up_capture", "down_capture", "pivot", "bench_pivot")])
+assert RELATIVE_SUMS_DTYPE.itemsize == 144 and RELATIVE_STATS_DTYPE.itemsize == 112
+RELATIVE_SIGNATURES = {
+    "mcp_relative_grid": (_u64, [_u64]),
+    "mcp_relative_ws_bytes": (ctypes.c_size_t, [_int, _u64]),
+    "mcp_relative_trip_n": (_u64, []),
+    "mcp_launch_relative": (_int, [_PP, _vp, _u64, _u64, _int, _int, _int, _vp, _vp, _vp, _vp, _vp]),
+    "mcp_relative_finish": (_int, [_vp, ctypes.c_double, ctypes.c_double, _vp]),
+    "mcp_ctx_request_relative": (_int, [_vp, ctypes.POINTER(McpRelative), _vp, _vp, _vp, _vp, _vp]),
+}
+
 _LIB = None
 
 
@@ -445,7 +468,7 @@ def lib() -> ctypes.CDLL:
             fn.argtypes = args
         for name, (res, args) in list(EXTENSION_SIGNATURES.items()) + list(SPEND_SIGNATURES.items()) + list(LIFE_SIGNATURES.items()) + \
                 list(BAND_SIGNATURES.items()) + list(VOLTARGET_SIGNATURES.items()) + list(UNDERWATER_SIGNATURES.items()) + \
-                list(UNCERTAIN_SIGNATURES.items()) + list(DOWNSIDE_SIGNATURES.items()):
+                list(UNCERTAIN_SIGNATURES.items()) + list(DOWNSIDE_SIGNATURES.items()) + list(RELATIVE_SIGNATURES.items()):
             fn = getattr(L, name)          # additive entry points, detected by symbol: a library without them is too old
             fn.restype = res
             fn.argtypes = args
@@ -751,6 +774,15 @@ def downside_finish(sums, tau: float, pivot: float):
     s = np.array(sums, DOWNSIDE_SUMS_DTYPE).reshape(1)
     out = np.zeros(1, DOWNSIDE_STATS_DTYPE)
     check(lib().mcp_downside_finish(ptr(s), float(tau), float(pivot), ptr(out)))
+    return out[0]
+
+
+def relative_finish(sums, pivot: float, bench_pivot: float):
+    """One finished record (a RELATIVE_STATS_DTYPE scalar) of one raw record `sums` (a RELATIVE_SUMS_DTYPE scalar or 0-d array) about
+    the row's and the benchmark's pivots: SPEC.md 5.23 (include/mcport_relative.h, mcp_relative_finish), pure host arithmetic."""
+    s = np.array(sums, RELATIVE_SUMS_DTYPE).reshape(1)
+    out = np.zeros(1, RELATIVE_STATS_DTYPE)
+    check(lib().mcp_relative_finish(ptr(s), float(pivot), float(bench_pivot), ptr(out)))
     return out[0]
 
 

@@ -1289,7 +1289,8 @@ Counted counted_of(const mcp_params* prm, const Request& rq) {
 constexpr size_t BAND_BUDGET_SLACK = sizeof(float);
 size_t tile_bytes_per_path(const Request& rq) {
   return (1 + (rq.hz ? (size_t)rq.H : 0)) * sizeof(float) + (second_of(rq).on ? sizeof(float) : 0) +
-         (rq.life || rq.band ? sizeof(uint32_t) : 0) + (rq.band ? BAND_BUDGET_SLACK : 0) + (rq.underwater ? 2 * sizeof(uint32_t) : 0);
+         (rq.life || rq.band ? sizeof(uint32_t) : 0) + (rq.band ? BAND_BUDGET_SLACK : 0) + (rq.underwater ? 2 * sizeof(uint32_t) : 0) +
+         (rq.relative ? sizeof(float) : 0);
 }
 
 int tile_portfolios(size_t budget, uint64_t n_paths, int K, size_t bytes_per_path) {
@@ -1394,9 +1395,81 @@ void downside_add(mcp_downside_sums& a, const mcp_downside_sums& b) {
   a.b1 += b.b1; a.b2 += b.b2; a.l1 += b.l1; a.l2 += b.l2; a.u1 += b.u1;
 }
 
+// SPEC.md 5.23: the request's own rules, the context and the call aside
+int check_relative(const mcp_relative* req, const mcp_relative_stats* stats_out) {
+  if (!req) return fail(MCP_E_ARG, "relative request is NULL");
+  if (!stats_out) return fail(MCP_E_ARG, "relative stats_out is NULL");
+  if (req->bench < 0) return fail(MCP_E_ARG, "relative bench=%d is negative", req->bench);
+  if (req->reserved != 0) return fail(MCP_E_ARG, "relative reserved=%d must be 0", req->reserved);
+  return MCP_OK;
+}
+
+void RelativeArm::arm(const mcp_relative& req, mcp_relative_sums* sums, mcp_relative_stats* stats, mcp_stats* active_stats, float* active,
+                      mcp_relative_stats* hz_stats) {
+  on = true;
+  bench = req.bench;
+  sums_out = sums;
+  stats_out = stats;
+  active_stats_out = active_stats;
+  active_out = active;
+  hz_stats_out = hz_stats;
+}
+
+RelativeArm RelativeArm::take() {
+  const RelativeArm t = *this;
+  *this = RelativeArm();
+  return t;
+}
+
+void relative_add(mcp_relative_sums& a, const mcp_relative_sums& b) {
+  a.n += b.n; a.n_under += b.n_under; a.n_over += b.n_over; a.n_up += b.n_up; a.n_down += b.n_down;
+  a.e1 += b.e1; a.e2 += b.e2; a.k1 += b.k1; a.b1 += b.b1; a.k2 += b.k2; a.b2 += b.b2; a.kb += b.kb;
+  a.u1 += b.u1; a.u2 += b.u2; a.up_k += b.up_k; a.up_b += b.up_b; a.down_k += b.down_k; a.down_b += b.down_b;
+}
+
+int check_relative_plan(const TilePlan& plan, int K, bool by_portfolio) {
+  if (by_portfolio && plan.S > 1)
+    return fail(MCP_E_ARG, "a relative request needs the benchmark's row on every shard: shard by paths, not by portfolios");
+  for (const Job& j : plan.jobs)
+    if (j.active && (j.k0 != 0 || j.kt != K))
+      return fail(MCP_E_ARG, "a relative request needs all %d portfolios in one tile, the terminal budget holds %d: raise the budget or "
+                  "shard by paths", K, j.kt);
+  return MCP_OK;
+}
+
 }  // namespace mcph
 
 using namespace mcph;
+
+// SPEC.md 5.23: every operation below is one binary64 operation in the order written (-ffp-contract=off); relative.finish repeats it
+int mcp_relative_finish(const mcp_relative_sums* s, double pivot, double bench_pivot, mcp_relative_stats* out) {
+  if (!s || !out) return fail(MCP_E_ARG, "NULL pointer");
+  const double n = (double)s->n, nu = (double)s->n_under, no = (double)s->n_over;
+  mcp_relative_stats o;
+  const double el = s->n ? s->e1 / n : 0.0;
+  o.active_mean = (pivot - bench_pivot) + el;
+  const double q = s->e2 - s->e1 * el;
+  o.tracking_error = s->n >= 2 ? std::sqrt((q > 0.0 ? q : 0.0) / (n - 1.0)) : 0.0;
+  o.information_ratio = o.tracking_error > 0.0 ? o.active_mean / o.tracking_error : 0.0;
+  o.p_under = s->n ? nu / n : 0.0;
+  o.p_over = s->n ? no / n : 0.0;
+  o.mean_underperformance = s->n_under ? s->u1 / nu : 0.0;
+  o.relative_downside_deviation = s->n ? std::sqrt(s->u2 / n) : 0.0;
+  const double kl = s->n ? s->k1 / n : 0.0, bl = s->n ? s->b1 / n : 0.0;
+  const double vk = s->k2 - s->k1 * kl, vb = s->b2 - s->b1 * bl, ckb = s->kb - s->k1 * bl;
+  o.beta = vb > 0.0 ? ckb / vb : 0.0;
+  const double mk = pivot + kl, mb = bench_pivot + bl;
+  o.alpha = mk - o.beta * mb;
+  const double vv = vk > 0.0 && vb > 0.0 ? vk * vb : 0.0;
+  const double rho = vv > 0.0 ? ckb / std::sqrt(vv) : 0.0;
+  o.correlation = rho > 1.0 ? 1.0 : (rho < -1.0 ? -1.0 : rho);
+  o.up_capture = s->n_up && s->up_b != 0.0 ? s->up_k / s->up_b : 0.0;
+  o.down_capture = s->n_down && s->down_b != 0.0 ? s->down_k / s->down_b : 0.0;
+  o.pivot = pivot;
+  o.bench_pivot = bench_pivot;
+  *out = o;
+  return MCP_OK;
+}
 
 // SPEC.md 5.22: every operation below is one binary64 operation in the order written (-ffp-contract=off); downside.finish repeats it
 int mcp_downside_finish(const mcp_downside_sums* s, double tau, double pivot, mcp_downside_stats* out) {

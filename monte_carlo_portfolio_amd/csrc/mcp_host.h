@@ -17,6 +17,7 @@
 #include "../../include/mcport_underwater.h"
 #include "../../include/mcport_uncertain.h"
 #include "../../include/mcport_downside.h"
+#include "../../include/mcport_relative.h"
 #include "mcp_route.h"
 
 namespace mcp {
@@ -121,6 +122,15 @@ struct Request {
   mcp_downside_sums* ds_hz_sums = nullptr;   // [H*K], row h*K + k
   double* ds_pivot = nullptr;           // [K] the pivots the records are about, as the tiles computed them
   double* ds_hz_pivot = nullptr;        // [H*K]
+  bool relative = false;                // SPEC.md 5.23: the context was armed (mcp_ctx_request_relative); set by the call that takes the request
+  bool rl_hz = false;                   // the request also covers the horizon rows
+  int rl_bench = 0;                     // the benchmark's row of W
+  mcp_relative_sums* rl_sums = nullptr;      // [K] the call's raw records: the tile's shards' added in shard order
+  mcp_relative_sums* rl_hz_sums = nullptr;   // [H*K], row h*K + k
+  double* rl_pivot = nullptr;           // [K] the pivots the records are about, as the tile computed them
+  double* rl_hz_pivot = nullptr;        // [H*K]
+  float* rl_active_out = nullptr;       // NULL or host [K*n] Y = fl32(1 + a)
+  mcp_stats* rl_active_stats_out = nullptr;  // NULL or [K] the records of Y
 };
 
 // The row table of a request that walks rows: the bootstrap's own, or the residual rows of SRC_FHS.
@@ -189,6 +199,7 @@ int check_band(const mcp_params* prm, const mcp_band* bd);
 int check_vol_target(const mcp_params* prm, const mcp_vol_target* vt, const float* chol, const float* W);
 int check_drift_uncertainty(int n_assets, const mcp_drift_uncertainty* du);
 int check_downside(const mcp_downside* req, const mcp_downside_stats* stats_out);
+int check_relative(const mcp_relative* req, const mcp_relative_stats* stats_out);
 // Every rule a request meets: each feature's own arguments, then which features combine (MCP_E_UNSUPPORTED), then the outputs.
 // `ln`: an mcp_launch_paths* call, whose device arrays are checked instead of the host arrays of an mcp_simulate* call.
 int check_request(const mcp_params* prm, const Request& rq, uint64_t n_paths, const Launch* ln = nullptr, uint64_t path_begin = 0);
@@ -328,8 +339,27 @@ struct DownsideArm {
 // a += b, field by field: how the records of shards add up, in shard order
 void downside_add(mcp_downside_sums& a, const mcp_downside_sums& b);
 
+// ---- benchmark-relative statistics (SPEC.md 5.23) ----
+// What mcp_ctx_request_relative leaves on a context, with DownsideArm's contract: the next call that walks paths takes it, and taking
+// disarms.  Both requests may be armed at once; the same call serves both.
+struct RelativeArm {
+  bool on = false;
+  int bench = 0;
+  mcp_relative_sums* sums_out = nullptr;
+  mcp_relative_stats* stats_out = nullptr;
+  mcp_stats* active_stats_out = nullptr;
+  float* active_out = nullptr;
+  mcp_relative_stats* hz_stats_out = nullptr;
+  void arm(const mcp_relative& req, mcp_relative_sums* sums, mcp_relative_stats* stats, mcp_stats* active_stats, float* active,
+           mcp_relative_stats* hz_stats);
+  RelativeArm take();
+};
+// a += b, field by field: how the records of shards add up, in shard order
+void relative_add(mcp_relative_sums& a, const mcp_relative_sums& b);
+
 // ---- the plan of a call: which shard does what in which tile ----
-// Bytes per path and portfolio that the tile budget counts: 4 of V_T, 4 per horizon row, 4 of the second array, 4 per integer record
+// Bytes per path and portfolio that the tile budget counts: 4 of V_T, 4 per horizon row, 4 of the second array, 4 per integer record,
+// 4 of the active returns Y of a relative request
 size_t tile_bytes_per_path(const Request& rq);
 // Portfolios per tile so that kt * n_paths * bytes_per_path fits the budget: whole 512-portfolio workgroups of the MFMA sweep kernel
 // when K is tiled at all.
@@ -353,5 +383,8 @@ struct TilePlan {
 // range, cut at multiples of `unit` (2 for antithetic pairs, SPEC.md 2.3); with fewer units than shards the last ones are active on
 // no paths.
 TilePlan plan_tiles(size_t S, int K, uint64_t n_paths, bool by_portfolio, uint64_t unit, size_t budget, size_t bytes_per_path);
+// SPEC.md 5.23: a relative request needs row `bench` beside every row, so the plan must hold all K portfolios in one tile on every
+// shard -- MCP_E_ARG for portfolio shards on several shards and for a budget that cuts K
+int check_relative_plan(const TilePlan& plan, int K, bool by_portfolio);
 
 }  // namespace mcph

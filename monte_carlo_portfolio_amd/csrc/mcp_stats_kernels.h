@@ -5,6 +5,7 @@
 
 #include "../../include/mcport.h"
 #include "../../include/mcport_downside.h"
+#include "../../include/mcport_relative.h"
 #include "mcp_host.h"
 #include "mcp_route.h"
 
@@ -123,6 +124,15 @@ __host__ __device__ inline int downside_grid(uint64_t n) {
 // and tau: one mcp_downside_sums per row and workgroup into `partials` ([rows][downside_grid(n)]), then added in block order
 hipError_t launch_downside(const mcp_params& prm, const float* values, uint64_t stride, uint64_t n, int rows, const double* pivot,
                            double tau, mcp_downside_sums* partials, mcp_downside_sums* sums, hipStream_t s);
+
+// ---- benchmark-relative statistics (SPEC.md 5.23) ----
+// the grid of the downside pass: the same function of n (include/mcport_relative.h, mcp_relative_grid)
+__host__ __device__ inline int relative_grid(uint64_t n) { return downside_grid(n); }
+// sums[r] = the raw record of row r of `values` ([rows][stride], n live values) against row (r / group) group + bench, about the
+// rows' pivots (NULL: 0): one mcp_relative_sums per row and workgroup into `partials` ([rows][relative_grid(n)]), then added in block
+// order; active (NULL: nothing is written) [rows][stride] takes Y = fl32(1 + a)
+hipError_t launch_relative(const mcp_params& prm, const float* values, uint64_t stride, uint64_t n, int rows, int group, int bench,
+                           const double* pivot, mcp_relative_sums* partials, mcp_relative_sums* sums, float* active, hipStream_t s);
 
 hipError_t launch_sweep_hist(int N, int R, int P, const double* returns, const double* mean, const double* cov,
                              const double* W, double rf, uint64_t rank_lo, uint64_t rank_hi, double gamma,

@@ -847,4 +847,137 @@ hipError_t launch_downside(const mcp_params& prm, const float* values, uint64_t 
   return hipGetLastError();
 }
 
+// ---- benchmark-relative statistics (SPEC.md 5.23) --------------------------------------------------------------------------------
+// The two-row sibling of downside_kernel: row r of the [rows][stride] values against row rb = (r / group) group + bench, element by
+// element.  x of both as terminal_to_x forms it, d_k = x_k - c_k, d_b = x_b - c_b, e = d_k - d_b, a = x_k - x_b, and per lane the
+// thirteen sums and five counts of mcp_relative_sums; every product is rounded once (-ffp-contract=off) and a summand outside its set
+// enters as + 0.0.  Y = fl32(1 + a) goes to `active` when it is given.  Grid, workgroup reduction and record layout are
+// downside_kernel's: blockIdx.y the row, blockIdx.x the workgroup of the row, the counts first.
+// The two rows lie (r - rb) stride elements apart, so with stride % 4 != 0 they differ in alignment modulo 16 bytes.  The head / float4
+// body / tail split is made on row r; the benchmark's four values of a body slot and Y's four are moved as one 16-byte access when
+// their own address is 16-byte aligned there (a workgroup-uniform test), else as four 4-byte ones, which are right at any 4-byte
+// alignment: neighbouring lanes still cover whole cache lines between them.
+constexpr int RL_COUNTS = 5, RL_WORDS = 18;
+static_assert(sizeof(mcp_relative_sums) == RL_WORDS * 8, "mcp_relative_sums is eighteen 8-byte words");
+
+template <bool LOGC>
+__global__ void __launch_bounds__(SB) relative_kernel(double v0d, const float* __restrict__ values, uint64_t stride, uint64_t n, int row0,
+                                                      int group, int bench, const double* __restrict__ pivot,
+                                                      mcp_relative_sums* __restrict__ partials, float* __restrict__ active) {
+  __shared__ double red[4][RL_WORDS];
+  const int G = gridDim.x, b = blockIdx.x;
+  const size_t r = (size_t)row0 + blockIdx.y;
+  const size_t rb = r / (size_t)group * (size_t)group + (size_t)bench;
+  const float* __restrict__ src = values + r * stride;
+  const float* __restrict__ bsrc = values + rb * stride;
+  float* __restrict__ dst = active ? active + r * stride : nullptr;
+  const double ck = pivot ? pivot[r] : 0.0, cb = pivot ? pivot[rb] : 0.0;
+  double e1 = 0.0, e2 = 0.0, k1 = 0.0, b1 = 0.0, k2 = 0.0, b2 = 0.0, kb = 0.0, u1 = 0.0, u2 = 0.0;
+  double upk = 0.0, upb = 0.0, dnk = 0.0, dnb = 0.0;
+  unsigned long long m = 0, nu = 0, no = 0, nup = 0, ndn = 0;
+
+  auto one = [&](float vk, float vb) -> float {
+    const double xk = terminal_to_x(vk, v0d, LOGC ? MCP_COMPOUND_LOG : MCP_COMPOUND_SIMPLE);
+    const double xb = terminal_to_x(vb, v0d, LOGC ? MCP_COMPOUND_LOG : MCP_COMPOUND_SIMPLE);
+    const double dk = xk - ck, db = xb - cb;
+    const double e = dk - db, a = xk - xb;
+    const bool under = a < 0.0, over = a > 0.0, up = xb > 0.0, down = xb < 0.0;
+    m += 1; nu += under ? 1 : 0; no += over ? 1 : 0; nup += up ? 1 : 0; ndn += down ? 1 : 0;
+    e1 += e; e2 += e * e;
+    k1 += dk; b1 += db; k2 += dk * dk; b2 += db * db; kb += dk * db;
+    u1 += under ? a : 0.0; u2 += under ? a * a : 0.0;
+    upk += up ? xk : 0.0; upb += up ? xb : 0.0;
+    dnk += down ? xk : 0.0; dnb += down ? xb : 0.0;
+    return (float)(1.0 + a);
+  };
+
+  const uint64_t head = n ? (uint64_t)((4 - (((uintptr_t)src >> 2) & 3)) & 3) : 0;
+  const uint64_t hd = head < n ? head : n;
+  const uint64_t nvec = (n - hd) / 4;
+  const float4* __restrict__ vsrc = (const float4*)(src + hd);
+  const bool bvec = (((uintptr_t)(bsrc + hd)) & 15) == 0;          // the benchmark's slots are 16-byte aligned where row r's are
+  const bool yvec = dst && (((uintptr_t)(dst + hd)) & 15) == 0;
+  const uint64_t vstep = (uint64_t)G * SB;
+  for (uint64_t j = (uint64_t)b * SB + threadIdx.x; j < nvec; j += vstep) {
+    const float4 q = vsrc[j];
+    const float* bp = bsrc + hd + 4 * j;
+    float4 p;
+    if (bvec) p = *(const float4*)bp;
+    else { p.x = bp[0]; p.y = bp[1]; p.z = bp[2]; p.w = bp[3]; }
+    float4 y;
+    y.x = one(q.x, p.x); y.y = one(q.y, p.y); y.z = one(q.z, p.z); y.w = one(q.w, p.w);
+    if (dst) {
+      float* yp = dst + hd + 4 * j;
+      if (yvec) *(float4*)yp = y;
+      else { yp[0] = y.x; yp[1] = y.y; yp[2] = y.z; yp[3] = y.w; }
+    }
+  }
+  if (b == 0) {                                           // head and tail scalars: at most 6 elements of the row
+    if (threadIdx.x < hd) {
+      const float y = one(src[threadIdx.x], bsrc[threadIdx.x]);
+      if (dst) dst[threadIdx.x] = y;
+    }
+    const uint64_t t0 = hd + 4 * nvec + threadIdx.x;
+    if (t0 < n) {
+      const float y = one(src[t0], bsrc[t0]);
+      if (dst) dst[t0] = y;
+    }
+  }
+
+  const double w[RL_WORDS] = {wave_sum((double)m), wave_sum((double)nu), wave_sum((double)no), wave_sum((double)nup),   // < 2^53: exact
+                              wave_sum((double)ndn), wave_sum(e1), wave_sum(e2), wave_sum(k1), wave_sum(b1), wave_sum(k2), wave_sum(b2),
+                              wave_sum(kb), wave_sum(u1), wave_sum(u2), wave_sum(upk), wave_sum(upb), wave_sum(dnk), wave_sum(dnb)};
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  if (lane == 0) {
+#pragma unroll
+    for (int i = 0; i < RL_WORDS; i++) red[wv][i] = w[i];
+  }
+  __syncthreads();
+  if (threadIdx.x < RL_WORDS) {
+    const int i = threadIdx.x;
+    const double t = (red[0][i] + red[1][i]) + (red[2][i] + red[3][i]);
+    unsigned long long* out = (unsigned long long*)(partials + (r * (size_t)G + b));
+    out[i] = i < RL_COUNTS ? (unsigned long long)t : (unsigned long long)__double_as_longlong(t);
+  }
+}
+
+// the workgroups' records of one row in downside_merge_kernel's fixed order: grid = rows, one wave; lane l adds records l, l + 64, ...
+// in increasing block order, then the wave's butterfly; word i of the result by lane i
+__global__ void __launch_bounds__(64) relative_merge_kernel(const mcp_relative_sums* __restrict__ partials, int G,
+                                                            mcp_relative_sums* __restrict__ sums) {
+  const unsigned long long* __restrict__ src = (const unsigned long long*)(partials + (size_t)blockIdx.x * G);
+  unsigned long long cnt[RL_COUNTS] = {};
+  double a[RL_WORDS - RL_COUNTS] = {};
+  for (int g = threadIdx.x; g < G; g += 64) {
+    const unsigned long long* p = src + (size_t)g * RL_WORDS;
+#pragma unroll
+    for (int i = 0; i < RL_COUNTS; i++) cnt[i] += p[i];
+#pragma unroll
+    for (int i = RL_COUNTS; i < RL_WORDS; i++) a[i - RL_COUNTS] += __longlong_as_double((long long)p[i]);
+  }
+  unsigned long long* out = (unsigned long long*)(sums + blockIdx.x);
+#pragma unroll
+  for (int i = 0; i < RL_WORDS; i++) {
+    const double t = wave_sum(i < RL_COUNTS ? (double)cnt[i] : a[i - RL_COUNTS]);   // the counts: < 2^53, exact
+    if (threadIdx.x == 0) out[i] = i < RL_COUNTS ? (unsigned long long)t : (unsigned long long)__double_as_longlong(t);
+  }
+}
+
+hipError_t launch_relative(const mcp_params& prm, const float* values, uint64_t stride, uint64_t n, int rows, int group, int bench,
+                           const double* pivot, mcp_relative_sums* partials, mcp_relative_sums* sums, float* active, hipStream_t s) {
+  if (rows < 1 || group < 1 || rows % group != 0 || bench < 0 || bench >= group) return hipErrorInvalidValue;
+  const int G = relative_grid(n);
+  const double v0d = (double)(float)prm.v0;
+  for (int r0 = 0; r0 < rows; r0 += 65535) {             // gridDim.y holds at most 65535 rows; the kernel indexes from row 0
+    const int nr = rows - r0 < 65535 ? rows - r0 : 65535;
+    const dim3 grid((unsigned)G, (unsigned)nr);
+    if (prm.compounding == MCP_COMPOUND_LOG)
+      relative_kernel<true><<<grid, SB, 0, s>>>(v0d, values, stride, n, r0, group, bench, pivot, partials, active);
+    else
+      relative_kernel<false><<<grid, SB, 0, s>>>(v0d, values, stride, n, r0, group, bench, pivot, partials, active);
+  }
+  relative_merge_kernel<<<(unsigned)rows, 64, 0, s>>>(partials, G, sums);
+  return hipGetLastError();
+}
+
 }  // namespace mcp

@@ -132,8 +132,8 @@ class Context:
               block: float = 1.0, dof=None, period=None, cost: float = 0.0, drawdown: bool = False, horizons=None, levels=(),
               flows=None, target=None, overlay=None, garch=None, attribution=False, antithetic=False, filtered=None, jumps=None, regimes=None,
               glide=None, protect=None, spending=None, lifetime=None, tolerance=None, vol_target=None, underwater=None,
-              drift_uncertainty=None, downside=None):
-        """The one library call behind every simulate_* method: downside and shape statistics (downside: True for the threshold rf or the threshold tau, SPEC.md 5.22; the request arms the context and rides whatever call this is, so it combines with every keyword below), drift uncertainty (drift_uncertainty: the binary32 factor M [N, N] of uncertainty.drift_factor, SPEC.md 2.7 / 4.21; on Gaussian draws with the drawdown, horizons or flows), the time under water (underwater: the levels in percent of the two counters' order statistics, SPEC.md 4.20 / 5.20; needs `drawdown`), a volatility target (vol_target: the (target, decay, cap, rate, spread, s0 or None) of voltarget.check_vol_target, SPEC.md 4.19 / 5.19; `target` is then its second count, and without `drawdown` the call leaves the exposure record), tolerance bands (tolerance: (every, cost, tol float32 [K, N], levels in percent of the trade counts' order statistics), SPEC.md 4.18 / 5.18; the rule carries its own period and cost, so not with `period`), the lifetime (lifetime: the levels in percent of its order statistics, SPEC.md 4.17 / 5.17; needs flows or spending), a spending rule (spending: the (rate, every, down, up, inflation, first or None) of check_spending; `target` is then its second count), floor protection (protect: the (floor, multiplier, rate, cap, ratchet) of check_protect; `target` is then its second count), two regimes (regimes: the (p01, p10, start, mu1, chol1) of check_regimes), market jumps (jumps: the (intensity, mean, std, loading or None) of check_jumps), GARCH volatility (garch: the (alpha, beta, h0) of check_garch), an option overlay (overlay: the triple of check_overlay), cash flows (flows, target), Student-t draws (dof), rebalancing
+              drift_uncertainty=None, downside=None, benchmark=None):
+        """The one library call behind every simulate_* method: benchmark-relative statistics (benchmark: the row of W every portfolio is compared with, SPEC.md 5.23; a request on the context as downside is, with every keyword below), downside and shape statistics (downside: True for the threshold rf or the threshold tau, SPEC.md 5.22; the request arms the context and rides whatever call this is, so it combines with every keyword below), drift uncertainty (drift_uncertainty: the binary32 factor M [N, N] of uncertainty.drift_factor, SPEC.md 2.7 / 4.21; on Gaussian draws with the drawdown, horizons or flows), the time under water (underwater: the levels in percent of the two counters' order statistics, SPEC.md 4.20 / 5.20; needs `drawdown`), a volatility target (vol_target: the (target, decay, cap, rate, spread, s0 or None) of voltarget.check_vol_target, SPEC.md 4.19 / 5.19; `target` is then its second count, and without `drawdown` the call leaves the exposure record), tolerance bands (tolerance: (every, cost, tol float32 [K, N], levels in percent of the trade counts' order statistics), SPEC.md 4.18 / 5.18; the rule carries its own period and cost, so not with `period`), the lifetime (lifetime: the levels in percent of its order statistics, SPEC.md 4.17 / 5.17; needs flows or spending), a spending rule (spending: the (rate, every, down, up, inflation, first or None) of check_spending; `target` is then its second count), floor protection (protect: the (floor, multiplier, rate, cap, ratchet) of check_protect; `target` is then its second count), two regimes (regimes: the (p01, p10, start, mu1, chol1) of check_regimes), market jumps (jumps: the (intensity, mean, std, loading or None) of check_jumps), GARCH volatility (garch: the (alpha, beta, h0) of check_garch), an option overlay (overlay: the triple of check_overlay), cash flows (flows, target), Student-t draws (dof), rebalancing
         (period, cost), bootstrap rows (rows, block) or Gaussian draws (mu, chol), with the drawdown or horizons.  Allocates the
         outputs that were asked for and passes NULL for the rest -> _Outputs, None where not asked for (terminal, qd,
         horizon_terminal: with `store` only; counts, hz_counts: with `flows` only; attr [K, N] records of ATTR_DTYPE and attr_counts
@@ -255,21 +255,40 @@ class Context:
             ds_hz_stats = np.zeros((H, K), _ffi.DOWNSIDE_STATS_DTYPE) if H else None
             _ffi.check(_ffi.lib().mcp_ctx_request_downside(self._h, ctypes.byref(_ffi.McpDownside(ds_tau, int(downside is True), 0)),
                                                            _ffi.ptr(ds_sums), _ffi.ptr(ds_stats), _ffi.ptr(ds_hz_stats)))
+        rl_stats = rl_sums = rl_hz_stats = rl_active_stats = rl_active = None
+        if benchmark is not None:                              # SPEC.md 5.23: likewise
+            rl_stats, rl_sums = np.zeros(K, _ffi.RELATIVE_STATS_DTYPE), np.zeros(K, _ffi.RELATIVE_SUMS_DTYPE)
+            rl_active_stats = np.zeros(K, _ffi.STATS_DTYPE)
+            rl_active = np.empty((K, n_paths), np.float32) if store else None
+            rl_hz_stats = np.zeros((H, K), _ffi.RELATIVE_STATS_DTYPE) if H else None
+            rc = _ffi.lib().mcp_ctx_request_relative(self._h, ctypes.byref(_ffi.McpRelative(int(benchmark), 0)), _ffi.ptr(rl_sums),
+                                                     _ffi.ptr(rl_stats), _ffi.ptr(rl_active_stats), _ffi.ptr(rl_active), _ffi.ptr(rl_hz_stats))
+            if rc < 0 and downside is not None:                # the downside request is already in place: it goes with this one
+                why = _ffi.lib().mcp_last_error()
+                _ffi.lib().mcp_ctx_request_downside(self._h, None, None, None, None)
+                raise _ffi.McpError(f"libmcport error {rc}: {why.decode('utf-8', 'replace')}")
+            _ffi.check(rc)
+
+        def withdraw():
+            if downside is not None:
+                _ffi.lib().mcp_ctx_request_downside(self._h, None, None, None, None)
+            if benchmark is not None:
+                _ffi.lib().mcp_ctx_request_relative(self._h, None, None, None, None, None, None)
         try:
             rc = getattr(_ffi.lib(), entry)(*(arg(g, v) for g in groups for v in vals[g.rstrip("*")]))
         except BaseException:
-            if downside is not None:                           # the call never reached the library: withdraw the request
-                _ffi.lib().mcp_ctx_request_downside(self._h, None, None, None, None)
+            withdraw()                                         # the call never reached the library: withdraw the requests
             raise
-        if rc < 0 and downside is not None:                    # a call refused before its rules were looked at leaves the request in place
+        if rc < 0 and (downside is not None or benchmark is not None):   # a call refused before its rules were looked at leaves the requests in place
             why = _ffi.lib().mcp_last_error()
-            _ffi.lib().mcp_ctx_request_downside(self._h, None, None, None, None)
+            withdraw()
             raise _ffi.McpError(f"libmcport error {rc}: {why.decode('utf-8', 'replace')}")
         _ffi.check(rc)
         return _Outputs(stats, dd_stats, hz_stats, bands, term, raw, hz_term, counts, hz_counts, attr, attr_counts, contrib, pairs,
                         wd_stats, withdrawn, life_hist, life_sum, life_q, life, trade_hist, trade_sum, trade_q, trades, turnover_stats, turnover,
                         exposure_stats, exposure, uw_longest_hist, uw_current_hist, uw_sums, uw_q, uw_longest, uw_current,
-                        ds_stats, ds_sums, ds_hz_stats, ds_tau)
+                        ds_stats, ds_sums, ds_hz_stats, ds_tau, rl_stats, rl_sums, rl_hz_stats, rl_active_stats, rl_active,
+                        None if benchmark is None else int(benchmark))
 
     def simulate_uncertain(self, prm: _ffi.McpParams, factor, mu, chol, W, seed: int, path_begin: int, n_paths: int, store: bool,
                            drawdown: bool = False, horizons=None, levels=(), flows=None, target=None):
@@ -396,12 +415,12 @@ class Context:
                           levels=levels, regimes=regimes)
 
     def simulate_filtered(self, prm: _ffi.McpParams, filtered, garch, W, block: float, seed: int, path_begin: int, n_paths: int,
-                          store: bool, horizons=None, levels=(), downside=None):
+                          store: bool, horizons=None, levels=(), downside=None, benchmark=None):
         """simulate_bootstrap[_horizons]() on filtered rows (SPEC.md 2.4 / 4.11; include/mcport.h, mcp_simulate_filtered; simple
         compounding only): `filtered` is the binary32 (mu [N], resid [R, N], shock [R]) triple, `garch` (alpha, beta, h0) -> _Outputs;
         the horizon entries are None without horizons."""
         return self._call(prm, W, seed, path_begin, n_paths, store, block=block, horizons=horizons, levels=levels, garch=garch,
-                          filtered=filtered, downside=downside)
+                          filtered=filtered, downside=downside, benchmark=benchmark)
 
     def simulate_attribution(self, prm: _ffi.McpParams, mu, chol, W, seed: int, path_begin: int, n_paths: int, store: bool, dof=None,
                              garch=None):
@@ -492,12 +511,16 @@ class Context:
 # the record of the total paid out (wd_stats [K]) and, stored, the binary32 withdrawn [K, n] (SPEC.md 5.16).  With a volatility target
 # and no drawdown the record of the summed exposure (exposure_stats [K], over Y - 1) and, stored, the binary32 exposure [K, n] (5.19).
 # With a downside request the records of SPEC.md 5.22 (downside_stats [K] of DOWNSIDE_STATS_DTYPE, downside_sums [K] of
-# DOWNSIDE_SUMS_DTYPE, downside_hz_stats [H, K] with horizons) and the threshold they are about (downside_tau).
+# DOWNSIDE_SUMS_DTYPE, downside_hz_stats [H, K] with horizons) and the threshold they are about (downside_tau).  With a relative
+# request the records of SPEC.md 5.23 (relative_stats [K] of RELATIVE_STATS_DTYPE, relative_sums [K] of RELATIVE_SUMS_DTYPE,
+# relative_hz_stats [H, K] with horizons, relative_active_stats [K] of STATS_DTYPE over Y - 1 and, stored, the binary32 relative_active
+# [K, n] Y) and the row they are against (relative_bench).
 _Outputs = collections.namedtuple("_Outputs", "stats dd_stats hz_stats bands terminal qd horizon_terminal counts hz_counts attr "
                                   "attr_counts contributions pairs wd_stats withdrawn life_hist life_sum life_q life trade_hist trade_sum trade_q trades "
                                   "turnover_stats turnover exposure_stats exposure uw_longest_hist uw_current_hist uw_sums uw_q uw_longest uw_current "
-                                  "downside_stats downside_sums downside_hz_stats downside_tau",
-                                  defaults=(None,) * 30)
+                                  "downside_stats downside_sums downside_hz_stats downside_tau "
+                                  "relative_stats relative_sums relative_hz_stats relative_active_stats relative_active relative_bench",
+                                  defaults=(None,) * 36)
 
 
 def check_cashflow(cashflow, target, n_steps):
@@ -1045,6 +1068,8 @@ _FLAGS = ("drawdown", "attribution", "antithetic", "fold", "native_math", "lifet
 _PATHS_COMBINE = {
     # SPEC.md 5.22: a reduction of what the call stores anyway, so no name is excluded
     "downside": ("downside reads the values of whatever walk the call runs", (), True),
+    # SPEC.md 5.23: likewise, but every row needs the benchmark's beside it -- nothing is excluded but what splits the portfolios
+    "benchmark": ("benchmark needs every portfolio and the benchmark's on the same shard", ("shard='portfolios'",), True),
     "drift_uncertainty": ("drift_uncertainty needs Gaussian draws, constant weights, the spec's normals and the unfolded recurrence",
                           ("underwater", "vol_target", "tolerance", "spending", "protect", "glide", "regimes", "jumps", "garch", "dof",
                            "rebalance", "overlay", "attribution", "antithetic", "lifetime", "fold", "native_math"), True),
@@ -1102,6 +1127,17 @@ _BOOTSTRAP_COMBINE = {
 }
 
 
+def _check_benchmark(benchmark, weights, as_array, shard):
+    """The `benchmark` keyword of simulate_paths, simulate_bootstrap and simulate_filtered -> None or the row (relative.check_benchmark),
+    with the two refusals that need no device (SPEC.md 5.23)."""
+    from .relative import check_benchmark
+    bm = check_benchmark(benchmark, 1 if np.ndim(weights) < 2 else np.shape(weights)[0])
+    if bm is not None and as_array:
+        raise ValueError("benchmark fills the 'relative' block of the result dicts: not with as_array")
+    _check_combines(_PATHS_COMBINE, "benchmark", dict(benchmark=bm, shard=shard))
+    return bm
+
+
 def _given(name, kw):
     """Whether the call's keywords `kw` hold `name` (a row of _PATHS_COMBINE explains the names)."""
     if "=" in name:
@@ -1124,7 +1160,7 @@ def simulate_paths(mu, cov, weights, n_steps=252, n_paths=10_000, seed=0, v0=1.0
                    horizons=None, bands=(), rebalance=None, rebalance_cost=0.0, dof=None, cashflow=None, target=None,
                    overlay=None, spot=None, garch=None, attribution=False, antithetic=False, jumps=None, regimes=None, glide=None,
                    protect=None, spending=None, lifetime=False, lifetime_levels=(5, 25, 50), tolerance=None, tolerance_levels=(5, 50, 95),
-                   vol_target=None, underwater=False, underwater_levels=(50, 95), drift_uncertainty=None, downside=None):
+                   vol_target=None, underwater=False, underwater_levels=(50, 95), drift_uncertainty=None, downside=None, benchmark=None):
     """Simulate `n_paths` correlated return paths and reduce them to risk statistics.
 
     mu [N], cov [N,N] are per-step mean and covariance (the reference's `mean_returns`, `cov_matrix`
@@ -1377,28 +1413,45 @@ def simulate_paths(mu, cov, weights, n_steps=252, n_paths=10_000, seed=0, v0=1.0
     the result is the call's without the keyword, bit for bit.  downside.normal_law gives the exact figures of a normal x.  Combines
     with every other keyword, devices and shard="portfolios".  Not with as_array (the records live in the dicts; ValueError), in
     simulate_sweep, in PathEngine; mcp_launch_downside is the enqueue-only form.
+
+    benchmark=None (default): every statistic above describes one portfolio alone.  benchmark=b, an integer row of `weights`: every
+    portfolio against that row on the same paths (SPEC.md 5.23) -- one more streaming reduction over the values the call keeps on
+    the device, two rows at a time, whatever walk produced them.  With a = x_k - x_b the active return of a path, every dict gains
+    'relative' {active_mean, tracking_error (np.std(a, ddof=1)), information_ratio (their quotient, not annualised), p_under and
+    p_over (the probability of ending behind / ahead; ties in neither), mean_underperformance (mean of a over the paths behind),
+    relative_downside_deviation (sqrt(mean min(a, 0)^2)), beta, alpha (mean_k - beta mean_b), correlation, up_capture and
+    down_capture (sum of x_k over sum of x_b on the paths where the benchmark gains / loses), pivot, bench_pivot, benchmark, sums (the
+    raw record), active {mean, std, var, cvar, n_tail, worst, best}: the statistics of the stored binary32 Y = 1 + a over Y - 1 at the
+    call's alpha, so var / cvar are the relative VaR / CVaR; with store=True also 'y', the [n_paths] row of Y} and, with horizons,
+    'horizons': the finished fields per horizon against the benchmark's row of that horizon.  A quotient whose denominator is 0 is 0;
+    the benchmark's own row has tracking_error 0, beta 1, captures 1.  Every other entry of the result is the call's without the
+    keyword, bit for bit.  relative.relative_law gives the exact figures of a one-step Gaussian pair.  Combines with every other
+    keyword, `downside` included, and with devices; all portfolios must fit one tile: not with shard="portfolios" (ValueError), not
+    under a terminal budget that cuts K (McpError).  ValueError for a bool, a float, a row outside `weights` and with as_array.  Not in
+    simulate_sweep or PathEngine; mcp_launch_relative is the enqueue-only form.
     """
     from .downside import check_downside
     ds = check_downside(downside)
     if ds is not None and as_array:
         raise ValueError("downside fills the 'downside' block of the result dicts: not with as_array")
+    bm = _check_benchmark(benchmark, weights, as_array, shard)
     if drift_uncertainty is not None:
         return _simulate_uncertain(mu, cov, weights, n_steps, n_paths, seed, v0, compounding, rf, alpha, devices, store, path_begin, chol,
                                    native_math, as_array, fold, shard, context, drawdown, horizons, bands, rebalance, rebalance_cost, dof,
                                    cashflow, target, overlay, spot, garch, attribution, antithetic, jumps, regimes, glide, protect, spending,
-                                   lifetime, tolerance, vol_target, underwater, drift_uncertainty, ds)
+                                   lifetime, tolerance, vol_target, underwater, drift_uncertainty, ds, bm)
     if not isinstance(underwater, (bool, np.bool_)):
         raise ValueError(f"underwater must be True or False, got {underwater!r}")
     if underwater:
         return _simulate_underwater(mu, cov, weights, n_steps, n_paths, seed, v0, compounding, rf, alpha, devices, store, path_begin, chol,
                                     native_math, as_array, fold, shard, context, drawdown, horizons, bands, rebalance, rebalance_cost, dof,
                                     cashflow, target, overlay, spot, garch, attribution, antithetic, jumps, regimes, glide, protect, spending,
-                                    lifetime, tolerance, vol_target, underwater_levels, ds)
+                                    lifetime, tolerance, vol_target, underwater_levels, ds, bm)
     if vol_target is not None:
         return _simulate_vol_target(mu, cov, weights, n_steps, n_paths, seed, v0, compounding, rf, alpha, devices, store, path_begin, chol,
                                     native_math, as_array, fold, shard, context, drawdown, horizons, bands, rebalance, rebalance_cost, dof,
                                     cashflow, target, overlay, spot, garch, attribution, antithetic, jumps, regimes, glide, protect, spending,
-                                    lifetime, tolerance, vol_target, ds)
+                                    lifetime, tolerance, vol_target, ds, bm)
     from .lifetime import check_lifetime
     lt = check_lifetime(lifetime, lifetime_levels, n_steps)
     if lt is not None and cashflow is None and spending is None:
@@ -1415,7 +1468,7 @@ def simulate_paths(mu, cov, weights, n_steps=252, n_paths=10_000, seed=0, v0=1.0
         tol, tlv = check_tolerance(tolerance, tolerance_levels, W.shape, n_steps, period)
         prm, ctx = _setup(mu32.shape[0], n_steps, W.shape[0], compounding, v0, alpha, rf, False, False, devices, shard, context)
         out = ctx._call(prm, W, int(seed), int(path_begin), int(n_paths), store, mu=mu32, chol=L, horizons=steps, levels=levels,
-                        tolerance=(period, cost, tol, tlv), downside=ds)
+                        tolerance=(period, cost, tol, tlv), downside=ds, benchmark=bm)
         return _with_tolerance(_result(out, np.asarray(weights).ndim == 1, store, as_array, steps, levels, compounding), out, tol, period,
                                tlv, store, as_array)
     kw = dict(spending=spending, protect=protect, glide=glide, regimes=regimes, jumps=jumps, antithetic=antithetic, attribution=attribution, garch=garch, overlay=overlay,
@@ -1479,7 +1532,7 @@ def simulate_paths(mu, cov, weights, n_steps=252, n_paths=10_000, seed=0, v0=1.0
     out = ctx._call(prm, W, int(seed), int(path_begin), int(n_paths), store, mu=mu32, chol=L, dof=dof, period=period, cost=cost,
                     drawdown=drawdown, horizons=steps, levels=levels, flows=flows, target=target if pv is None and sv is None else goal,
                     overlay=ov, garch=gv, attribution=bool(attribution), antithetic=bool(antithetic), jumps=jv, regimes=rv, glide=gl, protect=pv,
-                    spending=sv, downside=ds, **({} if lt is None else {"lifetime": lt}))
+                    spending=sv, downside=ds, benchmark=bm, **({} if lt is None else {"lifetime": lt}))
     if sv is not None:                                     # the counts are the 'spending' block's, not a 'cashflow' block's
         res = _spending_result(out, sv, v0, np.asarray(weights).ndim == 1, store, as_array, steps, levels, compounding, goal)
     elif pv is not None:                                     # the counts are the 'protect' block's, not a 'cashflow' block's
@@ -1507,7 +1560,7 @@ def simulate_paths(mu, cov, weights, n_steps=252, n_paths=10_000, seed=0, v0=1.0
 
 def _simulate_vol_target(mu, cov, weights, n_steps, n_paths, seed, v0, compounding, rf, alpha, devices, store, path_begin, chol, native_math,
                          as_array, fold, shard, context, drawdown, horizons, bands, rebalance, rebalance_cost, dof, cashflow, target, overlay,
-                         spot, garch, attribution, antithetic, jumps, regimes, glide, protect, spending, lifetime, tolerance, vol_target, downside=None):
+                         spot, garch, attribution, antithetic, jumps, regimes, glide, protect, spending, lifetime, tolerance, vol_target, downside=None, benchmark=None):
     """simulate_paths with a volatility target (SPEC.md 4.19 / 5.19): the rules of what it combines with, then the draws' own rules
     in simulate_paths' order, the call and the 'vol_target' block."""
     from .voltarget import check_vol_target, vol_target_blocks
@@ -1537,7 +1590,7 @@ def _simulate_vol_target(mu, cov, weights, n_steps, n_paths, seed, v0, compoundi
     vts = _ffi.make_vol_target(*vt)
     consts, s0 = _ffi.vol_target_consts(prm, vts, L, W)    # the library's rules, s0's among them, before anything is launched
     out = ctx._call(prm, W, int(seed), int(path_begin), int(n_paths), store, mu=mu32, chol=L, dof=dof, drawdown=bool(drawdown), horizons=steps,
-                    levels=levels, target=goal, garch=gv, jumps=jv, vol_target=vt, downside=downside)
+                    levels=levels, target=goal, garch=gv, jumps=jv, vol_target=vt, downside=downside, benchmark=benchmark)
     res = _result(out._replace(counts=None, hz_counts=None), np.asarray(weights).ndim == 1, store, as_array, steps, levels, compounding)
     if as_array:
         return ((res if isinstance(res, tuple) else (res,)) + ((out.counts,) if out.hz_counts is None else (out.counts, out.hz_counts))
@@ -1553,7 +1606,7 @@ def _simulate_vol_target(mu, cov, weights, n_steps, n_paths, seed, v0, compoundi
 def _simulate_uncertain(mu, cov, weights, n_steps, n_paths, seed, v0, compounding, rf, alpha, devices, store, path_begin, chol, native_math,
                         as_array, fold, shard, context, drawdown, horizons, bands, rebalance, rebalance_cost, dof, cashflow, target, overlay,
                         spot, garch, attribution, antithetic, jumps, regimes, glide, protect, spending, lifetime, tolerance, vol_target,
-                        underwater, drift_uncertainty, downside=None):
+                        underwater, drift_uncertainty, downside=None, benchmark=None):
     """simulate_paths with drift uncertainty (SPEC.md 2.7 / 4.21 / 5.21): the rules of what it combines with, then the underlying
     call's own rules in simulate_paths' order, the call and the 'drift_uncertainty' block."""
     from .uncertainty import check_drift_uncertainty, uncertainty_blocks
@@ -1577,7 +1630,7 @@ def _simulate_uncertain(mu, cov, weights, n_steps, n_paths, seed, v0, compoundin
         raise ValueError(f"drift_uncertainty: the factor is {M.shape}, the market has {L.shape[0]} assets")
     prm, ctx = _setup(mu32.shape[0], n_steps, W.shape[0], compounding, v0, alpha, rf, False, False, devices, shard, context)
     out = ctx._call(prm, W, int(seed), int(path_begin), int(n_paths), store, mu=mu32, chol=L, drawdown=bool(drawdown), horizons=steps,
-                    levels=levels, flows=flows, target=target, drift_uncertainty=M, downside=downside)
+                    levels=levels, flows=flows, target=target, drift_uncertainty=M, downside=downside, benchmark=benchmark)
     res = _result(out, np.asarray(weights).ndim == 1, store, as_array, steps, levels, compounding, flows, target)
     if as_array:
         return res
@@ -1589,7 +1642,7 @@ def _simulate_uncertain(mu, cov, weights, n_steps, n_paths, seed, v0, compoundin
 def _simulate_underwater(mu, cov, weights, n_steps, n_paths, seed, v0, compounding, rf, alpha, devices, store, path_begin, chol, native_math,
                          as_array, fold, shard, context, drawdown, horizons, bands, rebalance, rebalance_cost, dof, cashflow, target, overlay,
                          spot, garch, attribution, antithetic, jumps, regimes, glide, protect, spending, lifetime, tolerance, vol_target,
-                         underwater_levels, downside=None):
+                         underwater_levels, downside=None, benchmark=None):
     """simulate_paths with the time under water (SPEC.md 4.20 / 5.20): the rules of what it combines with, then the draws' own rules in
     simulate_paths' order, the call and the 'underwater' block."""
     from .underwater import check_underwater, underwater_blocks
@@ -1620,7 +1673,7 @@ def _simulate_underwater(mu, cov, weights, n_steps, n_paths, seed, v0, compoundi
     mu32, L, W = prepare_inputs(mu, cov, weights, chol)
     prm, ctx = _setup(mu32.shape[0], n_steps, W.shape[0], compounding, v0, alpha, rf, False, False, devices, shard, context)
     out = ctx._call(prm, W, int(seed), int(path_begin), int(n_paths), store, mu=mu32, chol=L, dof=dof, drawdown=True, garch=gv, jumps=jv,
-                    underwater=lv, downside=downside)
+                    underwater=lv, downside=downside, benchmark=benchmark)
     res = _result(out, np.asarray(weights).ndim == 1, store, as_array, None, (), compounding)
     if as_array:
         return ((res if isinstance(res, tuple) else (res,)) + (out.uw_longest_hist, out.uw_current_hist, out.uw_sums, out.uw_q)
@@ -1746,6 +1799,11 @@ def _result(out, single, store, as_array, steps, levels, compounding, flows=None
         from .downside import downside_blocks
         for d, blk in zip(res, downside_blocks(out.downside_stats, out.downside_sums, out.downside_tau, out.downside_hz_stats)):
             d["downside"] = blk
+    if out.relative_stats is not None:   # SPEC.md 5.23
+        from .relative import relative_blocks
+        for d, blk in zip(res, relative_blocks(out.relative_stats, out.relative_sums, out.relative_bench, out.relative_active_stats,
+                                               out.relative_hz_stats, out.relative_active if store else None)):
+            d["relative"] = blk
     for k, d in enumerate(res):
         if dd_stats is not None:
             d["drawdown"] = drawdown_to_dict(dd_stats[k])
@@ -1800,7 +1858,7 @@ def simulate_bootstrap(returns, weights, n_steps=252, n_paths=10_000, block=1.0,
                        rf=0.0, alpha=0.95, devices=None, store=False, path_begin=0, as_array=False, shard="auto", context=None,
                        horizons=None, bands=(), rebalance=None, rebalance_cost=0.0, cashflow=None, target=None, glide=None, spending=None,
                        lifetime=False, lifetime_levels=(5, 25, 50), tolerance=None, tolerance_levels=(5, 50, 95), downside=None,
-                       **unsupported):
+                       benchmark=None, **unsupported):
     """simulate_paths on paths resampled from the observed return rows instead of a normal model: the stationary block
     bootstrap of Politis & Romano (SPEC.md 2.1 / 4.4).  Every step of a path uses one whole row of `returns` (all assets of one
     date together), so fat tails, skew, the co-movement within a row and -- with a mean block length `block` > 1 -- short-range
@@ -1823,6 +1881,7 @@ def simulate_bootstrap(returns, weights, n_steps=252, n_paths=10_000, block=1.0,
     ds = check_downside(downside)
     if ds is not None and as_array:
         raise ValueError("downside fills the 'downside' block of the result dicts: not with as_array")
+    bm = _check_benchmark(benchmark, weights, as_array, shard)
     from .lifetime import check_lifetime
     lt = check_lifetime(lifetime, lifetime_levels, n_steps)
     if lt is not None and cashflow is None and spending is None:
@@ -1860,7 +1919,7 @@ def simulate_bootstrap(returns, weights, n_steps=252, n_paths=10_000, block=1.0,
         tol, tlv = check_tolerance(tolerance, tolerance_levels, W.shape, n_steps, period)
         prm, ctx = _setup(rows.shape[1], n_steps, W.shape[0], compounding, v0, alpha, rf, False, False, devices, shard, context)
         out = ctx._call(prm, W, int(seed), int(path_begin), int(n_paths), store, rows=rows, block=b, horizons=steps, levels=levels,
-                        tolerance=(period, cost, tol, tlv), downside=ds)
+                        tolerance=(period, cost, tol, tlv), downside=ds, benchmark=bm)
         return _with_tolerance(_result(out, np.asarray(weights).ndim == 1, store, as_array, steps, levels, compounding), out, tol, period,
                                tlv, store, as_array)
     kw = dict(spending=spending, glide=glide, cashflow=cashflow, rebalance=rebalance, compounding=compounding)
@@ -1884,7 +1943,7 @@ def simulate_bootstrap(returns, weights, n_steps=252, n_paths=10_000, block=1.0,
     rows, W = bootstrap_inputs(returns, weights)
     prm, ctx = _setup(rows.shape[1], n_steps, W.shape[0], compounding, v0, alpha, rf, False, False, devices, shard, context)
     out = ctx._call(prm, W, int(seed), int(path_begin), int(n_paths), store, rows=rows, block=b, period=period, cost=cost,
-                    horizons=steps, levels=levels, flows=flows, target=target if sv is None else goal, glide=gl, spending=sv, downside=ds,
+                    horizons=steps, levels=levels, flows=flows, target=target if sv is None else goal, glide=gl, spending=sv, downside=ds, benchmark=bm,
                     **({} if lt is None else {"lifetime": lt}))
     if sv is not None:
         res = _spending_result(out, sv, v0, np.asarray(weights).ndim == 1, store, as_array, steps, levels, compounding, goal)
@@ -1931,7 +1990,7 @@ def filtered_inputs(filtered, weights):
 
 def simulate_filtered(filtered, weights, n_steps=252, n_paths=10_000, garch=None, block=1.0, seed=0, v0=1.0, rf=0.0, alpha=0.95,
                       horizons=None, levels=(), devices=None, store=False, as_array=False, path_begin=0, shard="auto", context=None,
-                      downside=None, **unsupported):
+                      downside=None, benchmark=None, **unsupported):
     """Filtered historical simulation (Barone-Adesi, Giannopoulos & Vosper 1999; SPEC.md 2.4 / 4.11): simulate_bootstrap on rows
     that garch.filter_rows de-volatilised with the fitted GARCH(1,1) variance path, every draw re-scaled by the path's own simulated
     variance ratio h -- the empirical shocks of the bootstrap (tails, skew, assets that crash together) with the volatility
@@ -1949,6 +2008,7 @@ def simulate_filtered(filtered, weights, n_steps=252, n_paths=10_000, garch=None
     ds = check_downside(downside)
     if ds is not None and as_array:
         raise ValueError("downside fills the 'downside' block of the result dicts: not with as_array")
+    bm = _check_benchmark(benchmark, weights, as_array, shard)
     comp = unsupported.pop("compounding", "simple")
     if comp != "simple":
         raise ValueError(f"simulate_filtered compounds simply: not with compounding={comp!r}")
@@ -1967,7 +2027,7 @@ def simulate_filtered(filtered, weights, n_steps=252, n_paths=10_000, garch=None
     mu, resid, shock, W = filtered_inputs(filtered, weights)
     prm, ctx = _setup(resid.shape[1], n_steps, W.shape[0], "simple", v0, alpha, rf, False, False, devices, shard, context)
     out = ctx.simulate_filtered(prm, (mu, resid, shock), gv, W, b, int(seed), int(path_begin), int(n_paths), store, horizons=steps,
-                                levels=lv, downside=ds)
+                                levels=lv, downside=ds, benchmark=bm)
     return _result(out, np.asarray(weights).ndim == 1, store, as_array, steps, lv, "simple")
 
 
@@ -2002,6 +2062,8 @@ def simulate_sweep(mu, cov, weights=None, n_portfolios=2500, min_weights=None, m
         raise ValueError("simulate_sweep does not take underwater: call simulate_paths for the optimum")
     if kw.get("drift_uncertainty") is not None:
         raise ValueError("simulate_sweep does not take drift_uncertainty: call simulate_paths for the optimum")
+    if kw.get("benchmark") is not None:
+        raise ValueError("simulate_sweep does not take benchmark: the sweep returns record arrays -- call simulate_paths for the optimum")
     if kw.get("downside") is not None:
         raise ValueError("simulate_sweep does not take downside: the sweep returns record arrays -- call simulate_paths for the optimum")
     if kw.get("attribution"):
