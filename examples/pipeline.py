@@ -6,7 +6,7 @@
 Mirrors app.py's order of operations with the package's drop-in functions: read_csv_file (app.py:89) ->
 align / resample (app.py:466-482) -> per-asset statistics table (app.py:484-495) -> option overlay and payoff
 curve of one asset (app.py:499-653) -> returns matrix (app.py:658-667) -> the five-method random-weight sweep on
-historical rows (app.py:682-783, GPU) -> the optimum re-scored on one million SIMULATED one-year paths (GPU).
+historical rows (app.py:682-783, GPU) and its best-Sortino / shallowest-drawdown / best-Calmar weights -> the optimum re-scored on one million SIMULATED one-year paths (GPU).
 """
 import os
 import sys
@@ -16,7 +16,7 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import monte_carlo_portfolio_amd as mcp                                   # noqa: E402
-from monte_carlo_portfolio_amd import ingest, options                     # noqa: E402
+from monte_carlo_portfolio_amd import ingest, options, sweep              # noqa: E402
 
 
 def main(paths, resample_rule="M", user_rf=3.0, investment=10000.0, seed=12345, n_paths=1_000_000):
@@ -38,6 +38,12 @@ def main(paths, resample_rule="M", user_rf=3.0, investment=10000.0, seed=12345, 
     for m, r in res.items():
         print(f"{m:12s} opt_idx {r['opt_idx']:5d}  risk {r['all_risks'][r['opt_idx']] * 100:8.3f} %  "
               f"return {r['all_returns'][r['opt_idx']] * 100:8.3f} %  dollars {np.round(r['dollar_vals'], 2)}")
+    # three more criteria over the weights the "Monte Carlo" method drew (SPEC.md 5.24): the reference's own series statistics of
+    # returns_df @ w for every row -- best Sortino, shallowest historical drawdown, best Calmar -- beside the five optima above
+    for m in sweep.EXTRA_METHODS:
+        risks, rets, W, scores, opt = sweep.run_sweep(returns_df, m, user_rf=user_rf, annual_factor=af, seed=seed, risk_free=user_rf / 100)
+        print(f"{m:12s} opt_idx {opt:5d}  risk {risks[opt] * 100:8.3f} %  return {rets[opt] * 100:8.3f} %  "
+              f"dollars {np.round(sweep.allocation(W[opt], investment), 2)}  score {scores[opt]:+.4f}")
 
     w = res["Monte Carlo"]["weights"]
     mu_step, cov_step = returns_df.mean().values, returns_df.cov().values  # per period, before annualising

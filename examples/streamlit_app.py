@@ -88,6 +88,21 @@ with tab_sweep:                                               # app.py:655-783
         st.scatter_chart({"risk %": r["all_risks"] * 100, "return %": r["all_returns"] * 100})
         st.write({"optimum": i, "risk %": float(r["all_risks"][i] * 100), "return %": float(r["all_returns"][i] * 100),
                   "allocation": dict(zip(names, np.round(r["dollar_vals"], 2).tolist()))})
+    # three more criteria over the weights the "Monte Carlo" method drew (SPEC.md 5.24): the reference's own series statistics of
+    # returns_df @ w for every row of the sweep, and for the chosen optimum the dates of its deepest historical drawdown
+    criterion = st.selectbox("historical criterion over the Monte Carlo sweep's weights", list(sweep.EXTRA_METHODS), 0)
+    mc = results["Monte Carlo"]
+    perf = sweep.score_performance(returns_df.to_numpy(dtype=np.float64), mc["all_weights"], risk_free=user_rf / 100.0,
+                                   ann_factor=annual_factor)
+    key = {"Sortino": "sortino_ratio", "Max Drawdown": "max_drawdown", "Calmar": "calmar"}[criterion]
+    j = sweep.select_optimum(criterion, perf[key])
+    peak, trough = int(perf["peak_row"][j]), int(perf["trough_row"][j])
+    st.subheader(f"best {criterion} of the sweep (historical rows)")
+    st.write({"criterion": criterion, "best": j, "score": float(perf[key][j]), "Sortino": float(perf["sortino_ratio"][j]),
+              "max drawdown %": float(perf["max_drawdown"][j] * 100), "Calmar": float(perf["calmar"][j]),
+              "drawdown peak": str(returns_df.index[peak]) if peak >= 0 else None,
+              "drawdown trough": str(returns_df.index[trough]) if trough >= 0 else None,
+              "allocation": dict(zip(names, np.round(sweep.allocation(mc["all_weights"][j], state["investment_amount"]), 2).tolist()))})
     w = results["Monte Carlo"]["weights"]
     mu_step, cov_step = returns_df.mean().values, returns_df.cov().values          # per period (app.py:679-680 before annualising)
     sim = mcp.simulate_paths(mu_step, cov_step, w, n_steps=annual_factor, n_paths=n_paths, seed=12345,

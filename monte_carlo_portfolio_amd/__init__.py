@@ -26,10 +26,10 @@ from .garch import FilteredRows, GarchFit, filter_rows, fit_garch  # noqa: F401
 from .jumps import JumpFit, diffusion_cov, fit_jumps, jump_law  # noqa: F401
 from .regimes import RegimeFit, fit_regimes, regime_law  # noqa: F401
 from .student_t import fit_student_t_dof  # noqa: F401
-from .sweep import allocation, efficient_frontier, run_all_methods, run_sweep  # noqa: F401
+from .sweep import EXTRA_METHODS, allocation, efficient_frontier, performance_finish, run_all_methods, run_sweep, score_performance  # noqa: F401
 
 __all__ = [
-    "McpError", "build", "lib", "Context", "simulate_paths", "simulate_bootstrap", "simulate_filtered", "simulate_sweep", "fit_student_t_dof", "fit_garch", "GarchFit", "filter_rows", "FilteredRows", "fit_jumps", "JumpFit", "jump_law", "diffusion_cov", "fit_regimes", "RegimeFit", "regime_law", "glide_path", "glide_law", "floor_schedule", "protect_law", "spending_rule", "spending_law", "survival_curve", "lifetime_law", "tolerance_bands", "band_law", "ewma_decay", "vol_target_law", "spell_law", "drift_cov", "drift_factor", "drift_law", "check_drift_uncertainty", "check_downside", "normal_law", "check_benchmark", "relative_law", "run_sweep", "run_all_methods", "efficient_frontier",
+    "McpError", "build", "lib", "Context", "simulate_paths", "simulate_bootstrap", "simulate_filtered", "simulate_sweep", "fit_student_t_dof", "fit_garch", "GarchFit", "filter_rows", "FilteredRows", "fit_jumps", "JumpFit", "jump_law", "diffusion_cov", "fit_regimes", "RegimeFit", "regime_law", "glide_path", "glide_law", "floor_schedule", "protect_law", "spending_rule", "spending_law", "survival_curve", "lifetime_law", "tolerance_bands", "band_law", "ewma_decay", "vol_target_law", "spell_law", "drift_cov", "drift_factor", "drift_law", "check_drift_uncertainty", "check_downside", "normal_law", "check_benchmark", "relative_law", "run_sweep", "run_all_methods", "efficient_frontier", "score_performance", "performance_finish", "EXTRA_METHODS",
     "allocation", "ingest_np", "read_csv_file", "align_prices", "load_prices", "returns_matrix", "calc_asset_stats", "stats_table",
     "sharpe_ratio", "sortino_ratio", "annual_volatility", "annual_return", "max_drawdown", "var", "cvar",
     "calc_option_return", "calc_options_series", "calculate_payoff", "calculate_breakeven",

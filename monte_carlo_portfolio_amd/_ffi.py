@@ -402,6 +402,19 @@ RELATIVE_SIGNATURES = {
     "mcp_ctx_request_relative": (_int, [_vp, ctypes.POINTER(McpRelative), _vp, _vp, _vp, _vp, _vp]),
 }
 
+# And for include/mcport_sweep_perf.h (SPEC.md 5.24): the series statistics of the historical sweep's portfolios.
+# one mcp_sweep_perf_sums: the raw record of a portfolio; one mcp_sweep_perf_stats: the finished record
+SWEEP_PERF_SUMS_DTYPE = np.dtype([(f, np.int32) for f in ("n", "n_neg", "peak_row", "trough_row")] +
+                                 [(f, np.float64) for f in ("S", "S_neg", "M2", "M2_neg", "prod", "mdd")])
+SWEEP_PERF_STATS_DTYPE = np.dtype([(f, np.float64) for f in ("sharpe_ratio", "sortino_ratio", "annual_volatility", "annual_return",
+                                                             "max_drawdown", "calmar")] +
+                                  [(f, np.int32) for f in ("peak_row", "trough_row")])
+assert SWEEP_PERF_SUMS_DTYPE.itemsize == 64 and SWEEP_PERF_STATS_DTYPE.itemsize == 56
+SWEEP_PERF_SIGNATURES = {
+    "mcp_sweep_historical_perf": (_int, [_vp, _int, _int, _int, _vp, _vp, ctypes.c_double, ctypes.c_double, _vp, _vp]),
+    "mcp_sweep_perf_finish": (_int, [_vp, ctypes.c_double, _vp]),
+}
+
 _LIB = None
 
 
@@ -468,7 +481,8 @@ def lib() -> ctypes.CDLL:
             fn.argtypes = args
         for name, (res, args) in list(EXTENSION_SIGNATURES.items()) + list(SPEND_SIGNATURES.items()) + list(LIFE_SIGNATURES.items()) + \
                 list(BAND_SIGNATURES.items()) + list(VOLTARGET_SIGNATURES.items()) + list(UNDERWATER_SIGNATURES.items()) + \
-                list(UNCERTAIN_SIGNATURES.items()) + list(DOWNSIDE_SIGNATURES.items()) + list(RELATIVE_SIGNATURES.items()):
+                list(UNCERTAIN_SIGNATURES.items()) + list(DOWNSIDE_SIGNATURES.items()) + list(RELATIVE_SIGNATURES.items()) + \
+                list(SWEEP_PERF_SIGNATURES.items()):
             fn = getattr(L, name)          # additive entry points, detected by symbol: a library without them is too old
             fn.restype = res
             fn.argtypes = args

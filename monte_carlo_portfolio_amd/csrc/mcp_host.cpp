@@ -1437,9 +1437,56 @@ int check_relative_plan(const TilePlan& plan, int K, bool by_portfolio) {
   return MCP_OK;
 }
 
+int check_sweep_perf(int N, int R, int P, const double* returns, const double* W, double risk_free, double ann_factor,
+                     const mcp_sweep_perf_stats* stats_out) {
+  if (N < 1 || N > MCP_MAX_ASSETS) return fail(MCP_E_ARG, "n_assets=%d outside [1,%d]", N, MCP_MAX_ASSETS);
+  if (R < 2 || R > MCP_SWEEP_MAX_ROWS) return fail(MCP_E_ARG, "n_rows=%d outside [2,%d]", R, MCP_SWEEP_MAX_ROWS);
+  if (P < 0) return fail(MCP_E_ARG, "n_portfolios=%d < 0", P);
+  if (!(ann_factor > 0.0) || !std::isfinite(ann_factor)) return fail(MCP_E_ARG, "ann_factor=%g is not finite and > 0", ann_factor);
+  if (!std::isfinite(risk_free)) return fail(MCP_E_ARG, "risk_free=%g is not finite", risk_free);
+  if (!returns) return fail(MCP_E_ARG, "returns is NULL");
+  if (P == 0) return MCP_OK;
+  if (!W) return fail(MCP_E_ARG, "W is NULL");
+  if (!stats_out) return fail(MCP_E_ARG, "stats_out is NULL");
+  const auto first_bad = [](const double* a, size_t n) {
+    size_t i = 0;
+    while (i < n && std::isfinite(a[i])) i++;
+    return i;
+  };
+  const size_t n = (size_t)N;
+  size_t i;
+  if ((i = first_bad(returns, (size_t)R * n)) < (size_t)R * n)
+    return fail(MCP_E_ARG, "returns[%zu] (row %zu, asset %zu) is not finite", i, i / n, i % n);
+  if ((i = first_bad(W, (size_t)P * n)) < (size_t)P * n)
+    return fail(MCP_E_ARG, "W[%zu] (portfolio %zu, asset %zu) is not finite", i, i / n, i % n);
+  return MCP_OK;
+}
+
 }  // namespace mcph
 
 using namespace mcph;
+
+// SPEC.md 5.24: every operation below is one binary64 operation in the reference's order (-ffp-contract=off); sweep.performance_finish
+// repeats it.  n_neg == 1 divides 0 by 0 and a zero downside_std divides by IEEE rules, both as the reference does.
+int mcp_sweep_perf_finish(const mcp_sweep_perf_sums* s, double ann_factor, mcp_sweep_perf_stats* out) {
+  if (!s || !out) return fail(MCP_E_ARG, "NULL pointer");
+  if (!(ann_factor > 0.0) || !std::isfinite(ann_factor)) return fail(MCP_E_ARG, "ann_factor=%g is not finite and > 0", ann_factor);
+  const double n = (double)s->n, nn = (double)s->n_neg, root = std::sqrt(ann_factor);
+  mcp_sweep_perf_stats o;
+  const double mean_excess = s->S / n;
+  const double sd = std::sqrt(s->M2 / (n - 1.0));
+  o.sharpe_ratio = sd == 0.0 ? 0.0 : mean_excess / sd * root;
+  const double downside_std = s->n_neg == 0 ? 1e-4 : std::sqrt(s->M2_neg / (nn - 1.0));
+  o.sortino_ratio = mean_excess / downside_std * root;
+  o.annual_volatility = sd * root;
+  o.annual_return = std::pow(s->prod, ann_factor / n) - 1.0;
+  o.max_drawdown = s->mdd;
+  o.calmar = s->mdd == 0.0 ? 0.0 : o.annual_return / std::fabs(s->mdd);
+  o.peak_row = s->peak_row;
+  o.trough_row = s->trough_row;
+  *out = o;
+  return MCP_OK;
+}
 
 // SPEC.md 5.23: every operation below is one binary64 operation in the order written (-ffp-contract=off); relative.finish repeats it
 int mcp_relative_finish(const mcp_relative_sums* s, double pivot, double bench_pivot, mcp_relative_stats* out) {

@@ -18,6 +18,7 @@
 #include "../../include/mcport_uncertain.h"
 #include "../../include/mcport_downside.h"
 #include "../../include/mcport_relative.h"
+#include "../../include/mcport_sweep_perf.h"
 #include "mcp_route.h"
 
 namespace mcp {
@@ -200,6 +201,9 @@ int check_vol_target(const mcp_params* prm, const mcp_vol_target* vt, const floa
 int check_drift_uncertainty(int n_assets, const mcp_drift_uncertainty* du);
 int check_downside(const mcp_downside* req, const mcp_downside_stats* stats_out);
 int check_relative(const mcp_relative* req, const mcp_relative_stats* stats_out);
+// SPEC.md 5.24: every rule of mcp_sweep_historical_perf but the context's, the finiteness scan of mcp_sweep_historical included
+int check_sweep_perf(int N, int R, int P, const double* returns, const double* W, double risk_free, double ann_factor,
+                     const mcp_sweep_perf_stats* stats_out);
 // Every rule a request meets: each feature's own arguments, then which features combine (MCP_E_UNSUPPORTED), then the outputs.
 // `ln`: an mcp_launch_paths* call, whose device arrays are checked instead of the host arrays of an mcp_simulate* call.
 int check_request(const mcp_params* prm, const Request& rq, uint64_t n_paths, const Launch* ln = nullptr, uint64_t path_begin = 0);

@@ -6,6 +6,7 @@
 #include "../../include/mcport.h"
 #include "../../include/mcport_downside.h"
 #include "../../include/mcport_relative.h"
+#include "../../include/mcport_sweep_perf.h"
 #include "mcp_host.h"
 #include "mcp_route.h"
 
@@ -137,5 +138,8 @@ hipError_t launch_relative(const mcp_params& prm, const float* values, uint64_t 
 hipError_t launch_sweep_hist(int N, int R, int P, const double* returns, const double* mean, const double* cov,
                              const double* W, double rf, uint64_t rank_lo, uint64_t rank_hi, double gamma,
                              double* out5, hipStream_t s);
+// out[p] = the raw record of SPEC.md 5.24 of row p of W over `returns`, rf_step = risk_free / ann_factor; R >= 1, P >= 1
+hipError_t launch_sweep_perf(int N, int R, int P, const double* returns, const double* W, double rf_step,
+                             mcp_sweep_perf_sums* out, hipStream_t s);
 
 }  // namespace mcp

@@ -238,4 +238,97 @@ hipError_t launch_sweep_hist(int N, int R, int P, const double* returns, const d
   return hipGetLastError();
 }
 
+// ---- series statistics of every portfolio (SPEC.md 5.24, include/mcport_sweep_perf.h) ----------------------------------------
+// The order of the sums is the definition (rows ascending, one binary64 operation at a time), so the parallelism is across
+// portfolios: one lane per portfolio, 64 portfolios per wave, every lane walking the rows itself.  A row of `returns` is the same
+// for the whole wave (a uniform address: scalar loads); a lane's weights sit in LDS transposed, wt[i * 64 + lane], so lane l reads
+// bank pair l -- no conflict, no register array, no scratch.  The series is formed twice with the same expression, hence the same
+// bits: pass 1 takes the sums and the wealth recurrence, pass 2 the squared deviations about the means of pass 1 (two passes, as
+// np.std takes them).
+constexpr int PERF_LANES = 64;
+__device__ __forceinline__ double perf_x(const double* __restrict__ row, const double* __restrict__ wt, int N) {
+  double x = 0.0;
+  for (int i = 0; i < N; i++) x += row[i] * wt[i * PERF_LANES];
+  return x;
+}
+
+// grid = ceil(P / 64), block = 64, dynamic LDS = N * 64 doubles (<= 32 KiB)
+__global__ void __launch_bounds__(PERF_LANES) sweep_perf_kernel(int N, int R, int P, const double* __restrict__ returns,
+                                                                const double* __restrict__ W, double rf_step,
+                                                                mcp_sweep_perf_sums* __restrict__ out) {
+  extern __shared__ double lds[];
+  const int lane = threadIdx.x;
+  const int p0 = blockIdx.x * PERF_LANES;
+  const int live = min(PERF_LANES, P - p0);          // portfolios of this wave: the ragged last wave has fewer than 64
+  // the wave's weight rows are one contiguous block of `live` * N doubles: coalesced reads, transposed on the way into LDS;
+  // the columns of absent portfolios are 0.0, so their lanes walk finite numbers and write nothing
+  for (int t = lane; t < PERF_LANES * N; t += PERF_LANES) {
+    const int q = t / N, i = t - q * N;
+    lds[i * PERF_LANES + q] = q < live ? W[(size_t)p0 * N + t] : 0.0;
+  }
+  __syncthreads();
+  const double* wt = lds + lane;
+
+  // pass 1: S, n_neg, S_neg, and the wealth recurrence of max_drawdown
+  double S = 0.0, S_neg = 0.0;
+  int n_neg = 0;
+  double c, peak, mdd;
+  int peak_cur = 0, peak_row = 0, trough_row = 0;
+  bool dd_nan;
+  {
+    const double x = perf_x(returns, wt, N);
+    const double e = x - rf_step;
+    S += e;
+    if (e < 0.0) { n_neg++; S_neg += e; }
+    c = 1.0 + x;
+    peak = c;
+    mdd = (c - peak) / peak;
+    dd_nan = mdd != mdd;
+  }
+  for (int r = 1; r < R; r++) {
+    const double x = perf_x(returns + (size_t)r * N, wt, N);
+    const double e = x - rf_step;
+    S += e;
+    if (e < 0.0) { n_neg++; S_neg += e; }
+    c = c * (1.0 + x);
+    if (c > peak) { peak = c; peak_cur = r; }
+    const double dd = (c - peak) / peak;
+    dd_nan |= dd != dd;
+    if (dd < mdd) { mdd = dd; trough_row = r; peak_row = peak_cur; }
+  }
+
+  // pass 2: squared deviations about the means of pass 1
+  const double mean = S / (double)R, mean_neg = S_neg / (double)n_neg;
+  double M2 = 0.0, M2_neg = 0.0;
+  for (int r = 0; r < R; r++) {
+    const double e = perf_x(returns + (size_t)r * N, wt, N) - rf_step;
+    const double d = e - mean;
+    M2 += d * d;
+    if (e < 0.0) { const double dn = e - mean_neg; M2_neg += dn * dn; }
+  }
+
+  if (lane < live) {
+    mcp_sweep_perf_sums o;
+    o.n = R;
+    o.n_neg = n_neg;
+    o.peak_row = dd_nan ? -1 : peak_row;
+    o.trough_row = dd_nan ? -1 : trough_row;
+    o.S = S;
+    o.S_neg = S_neg;
+    o.M2 = M2;
+    o.M2_neg = M2_neg;
+    o.prod = c;
+    o.mdd = dd_nan ? __builtin_nan("") : mdd;
+    out[p0 + lane] = o;
+  }
+}
+
+hipError_t launch_sweep_perf(int N, int R, int P, const double* returns, const double* W, double rf_step,
+                             mcp_sweep_perf_sums* out, hipStream_t s) {
+  const int grid = (P + PERF_LANES - 1) / PERF_LANES;
+  const size_t lds = (size_t)N * PERF_LANES * sizeof(double);        // <= 64 * 64 * 8 = 32,768 B
+  sweep_perf_kernel<<<grid, PERF_LANES, lds, s>>>(N, R, P, returns, W, rf_step, out);
+  return hipGetLastError();
+}
+
 }  // namespace mcp

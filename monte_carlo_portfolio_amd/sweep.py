@@ -12,6 +12,10 @@ Reference lines restated here (script code of tab 2, app.py:655-764; function tw
 Quirks kept on purpose: Q2 `user_rf` is subtracted as given (default 3.0,
 "percent"); Q7 the four random methods share one RNG stream in the order Monte Carlo, VaR, CVaR, MPT;
 Q8 skipped portfolios shorten the arrays; Q9 `efficient_frontier` keeps the last rejected draw.
+
+Beyond the reference's loop (SPEC.md 5.24): its own series statistics -- sharpe_ratio, sortino_ratio, annual_volatility,
+annual_return, max_drawdown (app.py:231-256), which it applies per asset only -- for every weight row of a sweep
+(`score_performance`, HIP kernel `sweep_perf_kernel`), and the three criteria they give: EXTRA_METHODS.
 """
 from __future__ import annotations
 
@@ -24,6 +28,10 @@ from .simulate import default_context
 
 METHODS = ("Monte Carlo", "VaR", "CVaR", "MPT", "Equal Weight")          # app.py:671-677, dict order
 _METRIC = {"Monte Carlo": "sharpe", "VaR": "var_95", "CVaR": "cvar_95", "MPT": "sharpe", "Equal Weight": "sharpe"}
+EXTRA_METHODS = ("Sortino", "Max Drawdown", "Calmar")                    # SPEC.md 5.24: not in the reference's loop, not in METHODS
+_EXTRA_METRIC = {"Sortino": "sortino_ratio", "Max Drawdown": "max_drawdown", "Calmar": "calmar"}
+PERFORMANCE_KEYS = ("sharpe_ratio", "sortino_ratio", "annual_volatility", "annual_return", "max_drawdown", "calmar", "peak_row",
+                    "trough_row")
 
 
 def draw_weights(n_assets, n_portfolios=2500, min_weights=None, max_weights=None):
@@ -130,13 +138,8 @@ def score_portfolios(R, mean, cov, W, rf, alpha=0.95, device=0):
         raise ValueError(f"mean must have shape ({N},), got {mean.shape}")
     if cov.shape != (N, N):
         raise ValueError(f"cov must have shape ({N}, {N}), got {cov.shape}")
-    for name, a, axes in (("returns", R, ("row", "asset")), ("W", W, ("portfolio", "asset")), ("mean", mean, ("asset",)),
-                          ("cov", cov, ("row", "column"))):
-        bad = ~np.isfinite(a)
-        if bad.any():
-            first = np.unravel_index(int(np.argmax(bad)), a.shape)
-            where = ", ".join(f"{ax} {int(i)}" for ax, i in zip(axes, first))
-            raise ValueError(f"NaN or infinite values in {name} (first: {where}); {int(bad.sum())} in all, drop them first")
+    _check_sweep_arrays((("returns", R, ("row", "asset")), ("W", W, ("portfolio", "asset")), ("mean", mean, ("asset",)),
+                         ("cov", cov, ("row", "column"))))
     outs = [np.empty(P, np.float64) for _ in range(5)]
     if P:
         ctx = default_context(device)
@@ -144,22 +147,98 @@ def score_portfolios(R, mean, cov, W, rf, alpha=0.95, device=0):
     return dict(zip(("port_return", "port_std", "sharpe", "var_95", "cvar_95"), outs))
 
 
+def _check_sweep_arrays(arrays):
+    """The finiteness rule of the sweep's arrays, worded once: (name, array, axis names) each."""
+    for name, a, axes in arrays:
+        bad = ~np.isfinite(a)
+        if bad.any():
+            first = np.unravel_index(int(np.argmax(bad)), a.shape)
+            where = ", ".join(f"{ax} {int(i)}" for ax, i in zip(axes, first))
+            raise ValueError(f"NaN or infinite values in {name} (first: {where}); {int(bad.sum())} in all, drop them first")
+
+
+def performance_finish(sums, ann_factor):
+    """mcp_sweep_perf_finish (SPEC.md 5.24) restated in NumPy binary64, in the reference's order of operations, for an array of raw
+    records (`_ffi.SWEEP_PERF_SUMS_DTYPE`) -> dict of [P] arrays keyed PERFORMANCE_KEYS.  Every figure but the two that pass through
+    pow equals the library's bit for bit."""
+    sums = np.atleast_1d(np.asarray(sums, _ffi.SWEEP_PERF_SUMS_DTYPE))
+    ann = np.float64(ann_factor)
+    if not (np.isfinite(ann) and ann > 0):
+        raise ValueError(f"ann_factor={ann_factor!r} is not finite and > 0")
+    n, nn, root = sums["n"].astype(np.float64), sums["n_neg"].astype(np.float64), np.sqrt(ann)
+    with np.errstate(all="ignore"):
+        mean_excess = sums["S"] / n
+        std = np.sqrt(sums["M2"] / (n - 1.0))
+        sharpe = np.where(std == 0.0, 0.0, mean_excess / std * root)                               # app.py:235-236
+        downside_std = np.where(sums["n_neg"] == 0, 1e-4, np.sqrt(sums["M2_neg"] / (nn - 1.0)))    # app.py:242
+        sortino = mean_excess / downside_std * root
+        annual_return = np.power(sums["prod"], ann / n) - 1.0                                      # app.py:249
+        mdd = sums["mdd"].copy()
+        calmar = np.where(mdd == 0.0, 0.0, annual_return / np.abs(mdd))
+    return {"sharpe_ratio": sharpe, "sortino_ratio": sortino, "annual_volatility": std * root, "annual_return": annual_return,
+            "max_drawdown": mdd, "calmar": calmar, "peak_row": sums["peak_row"].copy(), "trough_row": sums["trough_row"].copy()}
+
+
+def score_performance(R, W, risk_free=0.0, ann_factor=12, device=0, raw=False):
+    """The reference's series statistics (app.py:231-256) of `R @ w` for all rows w of W on the GPU (SPEC.md 5.24) -> dict of
+    float64 [P] arrays sharpe_ratio, sortino_ratio, annual_volatility, annual_return, max_drawdown, calmar and int arrays peak_row,
+    trough_row (the rows of the deepest drawdown's peak and trough; -1 where the drawdown is NaN).  `risk_free` and `ann_factor`
+    mean what they mean in `metrics.sortino_ratio`.  raw=True adds the fields of the raw record (n, n_neg, S, S_neg, M2, M2_neg,
+    prod, mdd).  R and W must be finite, as for `score_portfolios`."""
+    W = np.ascontiguousarray(W, np.float64)
+    if W.ndim != 2:
+        raise ValueError(f"W must be a [P, N] matrix, got shape {W.shape}")
+    P, N = W.shape
+    R = np.ascontiguousarray(R, np.float64)
+    if R.ndim != 2 or R.shape[1] != N:
+        raise ValueError(f"returns must be an [R, {N}] matrix like the {N} columns of W, got shape {R.shape}")
+    if R.shape[0] < 2:
+        raise ValueError(f"returns must have at least 2 rows for a sample deviation, got {R.shape[0]}")
+    if not (np.isfinite(ann_factor) and ann_factor > 0):
+        raise ValueError(f"ann_factor={ann_factor!r} is not finite and > 0")
+    if not np.isfinite(risk_free):
+        raise ValueError(f"risk_free={risk_free!r} is not finite")
+    _check_sweep_arrays((("returns", R, ("row", "asset")), ("W", W, ("portfolio", "asset"))))
+    sums = np.zeros(P, _ffi.SWEEP_PERF_SUMS_DTYPE)
+    stats = np.zeros(P, _ffi.SWEEP_PERF_STATS_DTYPE)
+    if P:
+        ctx = default_context(device)
+        _ffi.check(_ffi.lib().mcp_sweep_historical_perf(ctx._h, N, R.shape[0], P, _ffi.ptr(R), _ffi.ptr(W), float(risk_free),
+                                                        float(ann_factor), _ffi.ptr(sums), _ffi.ptr(stats)))
+    out = {k: np.ascontiguousarray(stats[k]) for k in PERFORMANCE_KEYS}
+    if raw:
+        out.update((k, np.ascontiguousarray(sums[k])) for k in ("n", "n_neg", "S", "S_neg", "M2", "M2_neg", "prod", "mdd"))
+    return out
+
+
 def select_optimum(method, metrics):
-    """`opt_crit` of app.py:672-676 applied as at app.py:747 (the VaR/CVaR arrays hold -var, -cvar)."""
+    """`opt_crit` of app.py:672-676 applied as at app.py:747 (the VaR/CVaR arrays hold -var, -cvar).  The EXTRA_METHODS take the
+    largest finite score (for a drawdown the one closest to 0), the first index on a tie; a NaN or infinite score -- one negative
+    return, a lost first row -- is no candidate."""
     if method == "Equal Weight":
         return 0
     if len(metrics) == 0:
         raise ValueError("no portfolio satisfied the weight constraints (the reference raises here too, Q8)")
+    if method in EXTRA_METHODS:
+        m = np.asarray(metrics, np.float64)
+        ok = np.isfinite(m)
+        if not ok.any():
+            raise ValueError(f"no portfolio has a finite {_EXTRA_METRIC[method]}")
+        return int(np.argmax(np.where(ok, m, -np.inf)))
     return int(np.argmax(metrics)) if _METRIC[method] == "sharpe" else int(np.argmin(metrics))
 
 
 def run_sweep(returns_df, method="Monte Carlo", n_portfolios=2500, min_weights=None, max_weights=None,
-              user_rf=3.0, annual_factor=12, seed=None, alpha=0.95, device=0):
+              user_rf=3.0, annual_factor=12, seed=None, alpha=0.95, device=0, risk_free=0.0):
     """One method of the loop at app.py:682-722 -> (all_risks, all_returns, all_weights, all_metrics, opt_idx).
 
     `seed` (if given) seeds NumPy's global legacy RNG first; pass None to continue the current stream,
-    which is how the reference's four random methods follow each other (Q7)."""
-    if method not in METHODS:
+    which is how the reference's four random methods follow each other (Q7).
+
+    The EXTRA_METHODS draw their weights exactly as "Monte Carlo" does and return the same tuple: risks and returns from
+    `score_portfolios`, all_metrics the criterion of `score_performance` at `risk_free` (in `sortino_ratio`'s units, annual; only
+    these methods read it -- `user_rf` keeps its meaning for the analytic Sharpe)."""
+    if method not in METHODS and method not in EXTRA_METHODS:
         raise ValueError(f"unknown method {method!r}")
     R, mean, cov = sweep_inputs(returns_df, annual_factor)
     N = R.shape[1]
@@ -173,6 +252,9 @@ def run_sweep(returns_df, method="Monte Carlo", n_portfolios=2500, min_weights=N
     else:
         W = draw_weights(N, n_portfolios, min_weights, max_weights)
     s = score_portfolios(R, mean, cov, W, user_rf, alpha, device)
+    if method in EXTRA_METHODS:
+        metric = score_performance(R, W, risk_free, annual_factor, device)[_EXTRA_METRIC[method]]
+        return s["port_std"], s["port_return"], W, metric, select_optimum(method, metric)
     metric = {"sharpe": s["sharpe"], "var_95": -s["var_95"], "cvar_95": -s["cvar_95"]}[_METRIC[method]]   # app.py:717
     if method == "Equal Weight" and len(metric) == 0:
         raise IndexError("equal weights violate the constraints (the reference fails at app.py:749, Q8)")
