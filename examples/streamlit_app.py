@@ -103,6 +103,18 @@ with tab_sweep:                                               # app.py:655-783
               "drawdown peak": str(returns_df.index[peak]) if peak >= 0 else None,
               "drawdown trough": str(returns_df.index[trough]) if trough >= 0 else None,
               "allocation": dict(zip(names, np.round(sweep.allocation(mc["all_weights"][j], state["investment_amount"]), 2).tolist()))})
+    # how far the Monte Carlo optimum can be trusted (SPEC.md 5.25): the same weights scored on resamples of the rows
+    block = max(1.0, float(st.number_input("mean block length of the resampled sweep (1 = i.i.d. rows)", value=1.0)))
+    rs = sweep.score_resampled(returns_df.to_numpy(dtype=np.float64), mc["all_weights"], user_rf, annual_factor, n_replicates=1000,
+                               block=block, seed=12345)
+    summ = sweep.resample_summary(rs, mc["all_weights"], point=mc["opt_idx"])
+    won, i = summ["Monte Carlo"], mc["opt_idx"]
+    st.subheader("resampled sweep: 1,000 bootstrap replicates of the historical rows")
+    st.write({"optimum's win share %": won["point_win_share"] * 100, "in the top 5 % of, %": won["point_top5_share"] * 100,
+              "portfolios that win at least once": int((won["wins"] > 0).sum()),
+              "95 % interval of its Sharpe": [float(v) for v in summ["sharpe"]["interval"][:, i]],
+              "resampled weights": dict(zip(names, np.round(won["resampled_weights"], 4).tolist())),
+              "its own weights": dict(zip(names, np.round(mc["weights"], 4).tolist()))})
     w = results["Monte Carlo"]["weights"]
     mu_step, cov_step = returns_df.mean().values, returns_df.cov().values          # per period (app.py:679-680 before annualising)
     sim = mcp.simulate_paths(mu_step, cov_step, w, n_steps=annual_factor, n_paths=n_paths, seed=12345,

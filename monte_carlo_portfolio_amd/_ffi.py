@@ -415,6 +415,15 @@ SWEEP_PERF_SIGNATURES = {
     "mcp_sweep_perf_finish": (_int, [_vp, ctypes.c_double, _vp]),
 }
 
+# And for include/mcport_sweep_boot.h (SPEC.md 5.25): the resampled historical sweep.
+MCP_SWEEP_MAX_ROWS = 4096                 # mcport.h
+MCP_SWEEP_MAX_REPLICATES = 4096
+SWEEP_BOOT_SIGNATURES = {
+    "mcp_sweep_resampled": (_int, [_vp, _int, _int, _int, _vp, _vp, ctypes.c_double, ctypes.c_double, ctypes.c_double, _u64, _u64,
+                                   _int, ctypes.c_double, _vp, _vp, _vp]),
+    "mcp_sweep_boot_counts": (_int, [_u64, _u64, _int, _int, ctypes.c_double, _vp]),
+}
+
 _LIB = None
 
 
@@ -482,7 +491,7 @@ def lib() -> ctypes.CDLL:
         for name, (res, args) in list(EXTENSION_SIGNATURES.items()) + list(SPEND_SIGNATURES.items()) + list(LIFE_SIGNATURES.items()) + \
                 list(BAND_SIGNATURES.items()) + list(VOLTARGET_SIGNATURES.items()) + list(UNDERWATER_SIGNATURES.items()) + \
                 list(UNCERTAIN_SIGNATURES.items()) + list(DOWNSIDE_SIGNATURES.items()) + list(RELATIVE_SIGNATURES.items()) + \
-                list(SWEEP_PERF_SIGNATURES.items()):
+                list(SWEEP_PERF_SIGNATURES.items()) + list(SWEEP_BOOT_SIGNATURES.items()):
             fn = getattr(L, name)          # additive entry points, detected by symbol: a library without them is too old
             fn.restype = res
             fn.argtypes = args

@@ -1462,9 +1462,90 @@ int check_sweep_perf(int N, int R, int P, const double* returns, const double* W
   return MCP_OK;
 }
 
+// SPEC.md 5.25: the replicate range and the block of a resampled sweep
+int check_boot_replicates(uint64_t replicate_begin, int B, int R, double block) {
+  if (R < 2 || R > MCP_SWEEP_MAX_ROWS) return fail(MCP_E_ARG, "n_rows=%d outside [2,%d]", R, MCP_SWEEP_MAX_ROWS);
+  if (B < 0 || B > MCP_SWEEP_MAX_REPLICATES) return fail(MCP_E_ARG, "n_replicates=%d outside [0,%d]", B, MCP_SWEEP_MAX_REPLICATES);
+  if (!(block >= 1.0)) return fail(MCP_E_ARG, "block=%g must be >= 1 (or +inf)", block);
+  if (replicate_begin + (uint64_t)B < replicate_begin)
+    return fail(MCP_E_ARG, "replicate_begin=%llu + n_replicates=%d wraps", (unsigned long long)replicate_begin, B);
+  return MCP_OK;
+}
+
+int check_sweep_boot(int N, int R, int P, const double* returns, const double* W, double rf, double ann_factor, double alpha,
+                     uint64_t replicate_begin, int B, double block, const double* scores_out, const int32_t* opt_out) {
+  if (N < 1 || N > MCP_MAX_ASSETS) return fail(MCP_E_ARG, "n_assets=%d outside [1,%d]", N, MCP_MAX_ASSETS);
+  if (R < 2 || R > MCP_SWEEP_MAX_ROWS) return fail(MCP_E_ARG, "n_rows=%d outside [2,%d]", R, MCP_SWEEP_MAX_ROWS);
+  if (P < 0) return fail(MCP_E_ARG, "n_portfolios=%d < 0", P);
+  if (int rc = check_boot_replicates(replicate_begin, B, R, block)) return rc;
+  if ((uint64_t)P * (uint64_t)B > ((uint64_t)1 << 27))
+    return fail(MCP_E_ARG, "n_portfolios=%d * n_replicates=%d exceeds 2^27 scores per figure", P, B);
+  if (!(ann_factor > 0.0) || !std::isfinite(ann_factor)) return fail(MCP_E_ARG, "ann_factor=%g is not finite and > 0", ann_factor);
+  if (!std::isfinite(rf)) return fail(MCP_E_ARG, "rf=%g is not finite", rf);
+  if (!(alpha > 0.0 && alpha < 1.0)) return fail(MCP_E_ARG, "alpha=%g outside (0,1)", alpha);
+  if (!returns) return fail(MCP_E_ARG, "returns is NULL");
+  if (P == 0 || B == 0) return MCP_OK;
+  if (!W) return fail(MCP_E_ARG, "W is NULL");
+  if (!scores_out) return fail(MCP_E_ARG, "scores_out is NULL");
+  if (!opt_out) return fail(MCP_E_ARG, "opt_out is NULL");
+  const auto first_bad = [](const double* a, size_t n) {
+    size_t i = 0;
+    while (i < n && std::isfinite(a[i])) i++;
+    return i;
+  };
+  const size_t n = (size_t)N;
+  size_t i;
+  if ((i = first_bad(returns, (size_t)R * n)) < (size_t)R * n)
+    return fail(MCP_E_ARG, "returns[%zu] (row %zu, asset %zu) is not finite", i, i / n, i % n);
+  if ((i = first_bad(W, (size_t)P * n)) < (size_t)P * n)
+    return fail(MCP_E_ARG, "W[%zu] (portfolio %zu, asset %zu) is not finite", i, i / n, i % n);
+  return MCP_OK;
+}
+
+namespace {
+// Philox4x32-10 (SPEC.md 2), the words x0 and x1 of the block on counter (c0, c1, c2, c3) under key (k0, k1)
+inline void philox_x01(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1, uint32_t* x0, uint32_t* x1) {
+  for (int r = 0; r < 10; r++) {
+    const uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;
+    const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1;
+    c1 = (uint32_t)p1;
+    c3 = (uint32_t)p0;
+    c0 = n0;
+    c2 = n2;
+    k0 += 0x9E3779B9u;
+    k1 += 0xBB67AE85u;
+  }
+  *x0 = c0;
+  *x1 = c1;
+}
+}  // namespace
+
 }  // namespace mcph
 
 using namespace mcph;
+
+// SPEC.md 5.25: the rows of replicate g are those of path g of SPEC.md 2.1 with T = R steps on R rows; only their counts leave
+int mcp_sweep_boot_counts(uint64_t seed, uint64_t replicate_begin, int B, int R, double block, uint16_t* counts_out) {
+  if (int rc = check_boot_replicates(replicate_begin, B, R, block)) return rc;
+  if (B == 0) return MCP_OK;
+  if (!counts_out) return fail(MCP_E_ARG, "counts_out is NULL");
+  const uint64_t thr = boot_threshold(block);
+  const uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
+  for (int q = 0; q < B; q++) {
+    const uint64_t g = replicate_begin + (uint64_t)q;
+    uint16_t* c = counts_out + (size_t)q * (size_t)R;
+    for (int r = 0; r < R; r++) c[r] = 0;
+    uint32_t j = 0;
+    for (int t = 0; t < R; t++) {
+      uint32_t x0, x1;
+      philox_x01((uint32_t)t, 1u, (uint32_t)g, (uint32_t)(g >> 32), k0, k1, &x0, &x1);
+      const uint32_t start = (uint32_t)(((uint64_t)x0 * (uint64_t)R) >> 32), next = j + 1u;
+      j = (t == 0 || (uint64_t)x1 < thr) ? start : (next == (uint32_t)R ? 0u : next);
+      c[j] = (uint16_t)(c[j] + 1);
+    }
+  }
+  return MCP_OK;
+}
 
 // SPEC.md 5.24: every operation below is one binary64 operation in the reference's order (-ffp-contract=off); sweep.performance_finish
 // repeats it.  n_neg == 1 divides 0 by 0 and a zero downside_std divides by IEEE rules, both as the reference does.

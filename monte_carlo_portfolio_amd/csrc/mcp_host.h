@@ -19,6 +19,7 @@
 #include "../../include/mcport_downside.h"
 #include "../../include/mcport_relative.h"
 #include "../../include/mcport_sweep_perf.h"
+#include "../../include/mcport_sweep_boot.h"
 #include "mcp_route.h"
 
 namespace mcp {
@@ -204,6 +205,10 @@ int check_relative(const mcp_relative* req, const mcp_relative_stats* stats_out)
 // SPEC.md 5.24: every rule of mcp_sweep_historical_perf but the context's, the finiteness scan of mcp_sweep_historical included
 int check_sweep_perf(int N, int R, int P, const double* returns, const double* W, double risk_free, double ann_factor,
                      const mcp_sweep_perf_stats* stats_out);
+// SPEC.md 5.25: every rule of mcp_sweep_resampled but the context's (the scan above included), and those of mcp_sweep_boot_counts
+int check_sweep_boot(int N, int R, int P, const double* returns, const double* W, double rf, double ann_factor, double alpha,
+                     uint64_t replicate_begin, int B, double block, const double* scores_out, const int32_t* opt_out);
+int check_boot_replicates(uint64_t replicate_begin, int B, int R, double block);
 // Every rule a request meets: each feature's own arguments, then which features combine (MCP_E_UNSUPPORTED), then the outputs.
 // `ln`: an mcp_launch_paths* call, whose device arrays are checked instead of the host arrays of an mcp_simulate* call.
 int check_request(const mcp_params* prm, const Request& rq, uint64_t n_paths, const Launch* ln = nullptr, uint64_t path_begin = 0);

@@ -142,4 +142,12 @@ hipError_t launch_sweep_hist(int N, int R, int P, const double* returns, const d
 hipError_t launch_sweep_perf(int N, int R, int P, const double* returns, const double* W, double rf_step,
                              mcp_sweep_perf_sums* out, hipStream_t s);
 
+// mcp_sweep_boot.hip (SPEC.md 5.25).  counts [R][B]: the row counts of the replicates [begin, begin + B), thr = boot_threshold(block);
+// counts_t: NULL, or [B][R] takes the same counts transposed.  R >= 2, B >= 1
+hipError_t launch_boot_counts(int R, int B, uint64_t seed, uint64_t begin, uint64_t thr, uint16_t* counts, uint16_t* counts_t,
+                              hipStream_t s);
+// scores [5][P][B] and opt [3][B] of the P rows of W on the B resamples of `counts`; the ranks are mcp_percentile_rank(R, alpha)'s
+hipError_t launch_boot_score(int N, int R, int P, int B, const double* returns, const double* W, const uint16_t* counts, double rf,
+                             double ann, uint64_t rank_lo, uint64_t rank_hi, double gamma, double* scores, int32_t* opt, hipStream_t s);
+
 }  // namespace mcp

@@ -211,6 +211,128 @@ def score_performance(R, W, risk_free=0.0, ann_factor=12, device=0, raw=False):
     return out
 
 
+RESAMPLED_KEYS = ("port_return", "port_std", "sharpe", "var_95", "cvar_95")      # the order of scores_out (SPEC.md 5.25)
+RESAMPLED_CRITERIA = {"Monte Carlo": "sharpe", "VaR": "var_95", "CVaR": "cvar_95"}  # the order of opt_out; the largest score wins
+
+
+def _check_resample(n_rows, n_replicates, block, replicate_begin):
+    if n_rows < 2:
+        raise ValueError(f"returns must have at least 2 rows for a sample deviation, got {n_rows}")
+    if n_rows > _ffi.MCP_SWEEP_MAX_ROWS:
+        raise ValueError(f"returns has {n_rows} rows, the resampled sweep takes at most {_ffi.MCP_SWEEP_MAX_ROWS}")
+    if not 0 <= n_replicates <= _ffi.MCP_SWEEP_MAX_REPLICATES:
+        raise ValueError(f"n_replicates={n_replicates!r} outside [0, {_ffi.MCP_SWEEP_MAX_REPLICATES}]")
+    if not block >= 1:
+        raise ValueError(f"block={block!r} must be >= 1 (or inf)")
+    if not 0 <= replicate_begin <= 2 ** 64 - 1 - n_replicates:
+        raise ValueError(f"replicate_begin={replicate_begin!r} + n_replicates={n_replicates} leaves [0, 2^64)")
+
+
+def resample_counts(n_rows, n_replicates=1000, block=1.0, seed=0, replicate_begin=0):
+    """The row counts [B, R] (uint16) of the replicates of `score_resampled`, on the host (`mcp_sweep_boot_counts`, no device):
+    `np.repeat(np.arange(R), counts[b])` is replicate b's resample, up to the order of its rows."""
+    n_rows, n_replicates, replicate_begin = int(n_rows), int(n_replicates), int(replicate_begin)
+    _check_resample(n_rows, n_replicates, block, replicate_begin)
+    out = np.zeros((n_replicates, n_rows), np.uint16)
+    _ffi.check(_ffi.lib().mcp_sweep_boot_counts(int(seed) & (2 ** 64 - 1), replicate_begin, n_replicates, n_rows, float(block),
+                                                _ffi.ptr(out)))
+    return out
+
+
+def score_resampled(R, W, rf, annual_factor=12, alpha=0.95, n_replicates=1000, block=1.0, seed=0, replicate_begin=0, device=0,
+                    counts=False):
+    """All rows of W scored on `n_replicates` stationary-block-bootstrap resamples of the rows of R, on the GPU (SPEC.md 5.25) -> dict
+    of float64 [P, B] arrays port_return, port_std, sharpe, var_95, cvar_95 (all five from the resampled series `R[j] @ w`: mean and
+    sample deviation times `annual_factor`, NumPy's percentile, the tail mean) and `opt`: {"Monte Carlo", "VaR", "CVaR"} -> int32 [B],
+    the first portfolio with the largest sharpe / var_95 / cvar_95 of each replicate.  Replicate `replicate_begin + b` resamples the
+    rows that path `replicate_begin + b` of `simulate_bootstrap(seed=, block=)` walks over R steps; `block` is the mean block length
+    (1: the i.i.d. bootstrap, inf: one circular block).  counts=True adds `counts` [B, R], how often each row was drawn.  R and W must
+    be finite, as for `score_portfolios`."""
+    W = np.ascontiguousarray(W, np.float64)
+    if W.ndim != 2:
+        raise ValueError(f"W must be a [P, N] matrix, got shape {W.shape}")
+    P, N = W.shape
+    R = np.ascontiguousarray(R, np.float64)
+    if R.ndim != 2 or R.shape[1] != N:
+        raise ValueError(f"returns must be an [R, {N}] matrix like the {N} columns of W, got shape {R.shape}")
+    B, begin = int(n_replicates), int(replicate_begin)
+    _check_resample(R.shape[0], B, block, begin)
+    if not (np.isfinite(annual_factor) and annual_factor > 0):
+        raise ValueError(f"annual_factor={annual_factor!r} is not finite and > 0")
+    if not np.isfinite(rf):
+        raise ValueError(f"rf={rf!r} is not finite")
+    if not 0.0 < alpha < 1.0:
+        raise ValueError(f"alpha={alpha!r} outside (0, 1)")
+    if P * B > 2 ** 27:
+        raise ValueError(f"{P} portfolios x {B} replicates exceed 2^27 scores per figure: score the replicates in ranges")
+    _check_sweep_arrays((("returns", R, ("row", "asset")), ("W", W, ("portfolio", "asset"))))
+    scores = np.zeros((5, P, B), np.float64)
+    opt = np.zeros((3, B), np.int32)
+    cnt = np.zeros((B, R.shape[0]), np.uint16) if counts else None
+    if P and B:
+        ctx = default_context(device)
+        _ffi.check(_ffi.lib().mcp_sweep_resampled(ctx._h, N, R.shape[0], P, _ffi.ptr(R), _ffi.ptr(W), float(rf), float(annual_factor),
+                                                  float(alpha), int(seed) & (2 ** 64 - 1), begin, B, float(block), _ffi.ptr(scores),
+                                                  _ffi.ptr(opt), _ffi.ptr(cnt)))
+    elif counts and B:
+        cnt = resample_counts(R.shape[0], B, block, seed, begin)
+    out = {k: scores[i] for i, k in enumerate(RESAMPLED_KEYS)}
+    out["opt"] = {m: opt[i] for i, m in enumerate(RESAMPLED_CRITERIA)}
+    if counts:
+        out["counts"] = cnt
+    return out
+
+
+def resample_summary(scores, W, point=None, levels=(2.5, 97.5)):
+    """What the replicates of `score_resampled` say, in host NumPy.  Per figure of RESAMPLED_KEYS a dict of `mean` [P] (over the
+    replicates), `se` [P] (the bootstrap standard error, ddof = 1; NaN for fewer than 2 replicates) and `interval` [len(levels), P]
+    (the percentile interval at `levels`); per criterion of `scores["opt"]` a dict of `wins` [P] (replicates won, summing to B),
+    `win_share` [P] and `resampled_weights` [N] = the mean over the replicates of W[opt] (Michaud's resampled portfolio).  `point`:
+    the index of a full-sample optimum, or a dict criterion -> index; adds `point`, `point_win_share` and `point_top5_share` -- the
+    share of replicates in which fewer than ceil(P / 20) portfolios score above it -- to the criteria it names."""
+    W = np.asarray(W, np.float64)
+    P = W.shape[0]
+    out = {}
+    for k in RESAMPLED_KEYS:
+        x = np.asarray(scores[k], np.float64)
+        if x.ndim != 2 or x.shape[0] != P:
+            raise ValueError(f"scores[{k!r}] must be a [{P}, B] matrix like the {P} rows of W, got shape {x.shape}")
+        B = x.shape[1]
+        if B < 1:
+            raise ValueError("a summary needs at least one replicate")
+        se = x.std(axis=1, ddof=1) if B > 1 else np.full(P, np.nan)
+        out[k] = {"mean": x.mean(axis=1), "se": se, "interval": np.percentile(x, list(levels), axis=1)}
+    points = point if isinstance(point, dict) else {m: point for m in scores["opt"]}
+    for m, opt in scores["opt"].items():
+        opt = np.asarray(opt)
+        wins = np.bincount(opt, minlength=P).astype(np.int64)
+        o = {"wins": wins, "win_share": wins / len(opt), "resampled_weights": W[opt].mean(axis=0)}
+        at = points.get(m)
+        if at is not None:
+            x = np.asarray(scores[RESAMPLED_CRITERIA[m]], np.float64)
+            above = (x > x[int(at)][None, :]).sum(axis=0)
+            o.update(point=int(at), point_win_share=float(o["win_share"][int(at)]),
+                     point_top5_share=float((above < max(1, -(-P // 20))).mean()))
+        out[m] = o
+    return out
+
+
+def run_resampled_sweep(returns_df, method="Monte Carlo", n_portfolios=2500, min_weights=None, max_weights=None, user_rf=3.0,
+                        annual_factor=12, seed=None, alpha=0.95, device=0, n_replicates=1000, block=1.0, resample_seed=0):
+    """`run_sweep` for one of "Monte Carlo" | "VaR" | "CVaR" | "MPT", and how far its optimum can be trusted: the tuple of `run_sweep`
+    plus `resample_summary` of `score_resampled` on the same weights, with the sweep's optimum as the summary's `point` under the
+    method's own criterion (MPT: the Sharpe ratio).  The weights are drawn by `run_sweep` itself and the resampling draws nothing from
+    NumPy, so the global stream is left where `run_sweep` leaves it; the replicates are keyed by `resample_seed` alone."""
+    if method not in ("Monte Carlo", "VaR", "CVaR", "MPT"):
+        raise ValueError(f"unknown method {method!r} for a resampled sweep")
+    risks, rets, W, metric, opt = run_sweep(returns_df, method, n_portfolios, min_weights, max_weights, user_rf, annual_factor, seed,
+                                            alpha, device)
+    R = sweep_inputs(returns_df, annual_factor)[0]
+    scores = score_resampled(R, W, user_rf, annual_factor, alpha, n_replicates, block, resample_seed, 0, device)
+    criterion = "Monte Carlo" if method == "MPT" else method
+    return risks, rets, W, metric, opt, resample_summary(scores, W, point={criterion: opt})
+
+
 def select_optimum(method, metrics):
     """`opt_crit` of app.py:672-676 applied as at app.py:747 (the VaR/CVaR arrays hold -var, -cvar).  The EXTRA_METHODS take the
     largest finite score (for a drawdown the one closest to 0), the first index on a tie; a NaN or infinite score -- one negative
