@@ -754,7 +754,7 @@ static void run_downside() {
   EXPECT(arm.take().sums_out == &sums && !arm.on);
 
   mcp_downside_sums a = four;
-  downside_add(a, one_below);
+  rowsum_add(a, one_below);
   EXPECT(a.n == 6 && a.n_below == 3 && a.n_above == 3 && a.s2 == 24.0 && a.b1 == -4.0 && a.l2 == 6.0 && a.u1 == 6.0 && a.s4 == 276.0);
 }
 

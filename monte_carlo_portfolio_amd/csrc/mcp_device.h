@@ -11,6 +11,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "mcp_reduce.h"  // wave_sum, wave_min, ..., block_sum
 #include "mcp_route.h"   // ICDF_ENTRIES, ICDF_PAD, ICDF_LDS_ENTRIES: the sizes of the table that the host's routing needs too
 
 namespace mcp {

@@ -1290,7 +1290,7 @@ constexpr size_t BAND_BUDGET_SLACK = sizeof(float);
 size_t tile_bytes_per_path(const Request& rq) {
   return (1 + (rq.hz ? (size_t)rq.H : 0)) * sizeof(float) + (second_of(rq).on ? sizeof(float) : 0) +
          (rq.life || rq.band ? sizeof(uint32_t) : 0) + (rq.band ? BAND_BUDGET_SLACK : 0) + (rq.underwater ? 2 * sizeof(uint32_t) : 0) +
-         (rq.relative ? sizeof(float) : 0);
+         (rq.rl.on ? sizeof(float) : 0);
 }
 
 int tile_portfolios(size_t budget, uint64_t n_paths, int K, size_t bytes_per_path) {
@@ -1389,12 +1389,6 @@ DownsideArm DownsideArm::take() {
   return t;
 }
 
-void downside_add(mcp_downside_sums& a, const mcp_downside_sums& b) {
-  a.n += b.n; a.n_below += b.n_below; a.n_above += b.n_above;
-  a.s1 += b.s1; a.s2 += b.s2; a.s3 += b.s3; a.s4 += b.s4;
-  a.b1 += b.b1; a.b2 += b.b2; a.l1 += b.l1; a.l2 += b.l2; a.u1 += b.u1;
-}
-
 // SPEC.md 5.23: the request's own rules, the context and the call aside
 int check_relative(const mcp_relative* req, const mcp_relative_stats* stats_out) {
   if (!req) return fail(MCP_E_ARG, "relative request is NULL");
@@ -1419,12 +1413,6 @@ RelativeArm RelativeArm::take() {
   const RelativeArm t = *this;
   *this = RelativeArm();
   return t;
-}
-
-void relative_add(mcp_relative_sums& a, const mcp_relative_sums& b) {
-  a.n += b.n; a.n_under += b.n_under; a.n_over += b.n_over; a.n_up += b.n_up; a.n_down += b.n_down;
-  a.e1 += b.e1; a.e2 += b.e2; a.k1 += b.k1; a.b1 += b.b1; a.k2 += b.k2; a.b2 += b.b2; a.kb += b.kb;
-  a.u1 += b.u1; a.u2 += b.u2; a.up_k += b.up_k; a.up_b += b.up_b; a.down_k += b.down_k; a.down_b += b.down_b;
 }
 
 int check_relative_plan(const TilePlan& plan, int K, bool by_portfolio) {

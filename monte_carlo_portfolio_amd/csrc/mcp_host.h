@@ -5,6 +5,7 @@
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
+#include <string.h>
 
 #include <vector>
 
@@ -24,6 +25,14 @@
 
 namespace mcp {
 constexpr int SWEEP_MIN_K = 17;      // from this many portfolios on the MFMA sweep kernels run
+
+// The raw record of a row-sum pass (SPEC.md 5.22, 5.23), declared once for the kernels and the host: WORDS 8-byte words, the COUNTS
+// leading ones unsigned integers, the rest binary64 sums.
+template <class T> struct RowSumLayout;
+template <> struct RowSumLayout<mcp_downside_sums> { static constexpr int WORDS = 12, COUNTS = 3; };
+template <> struct RowSumLayout<mcp_relative_sums> { static constexpr int WORDS = 18, COUNTS = 5; };
+static_assert(sizeof(mcp_downside_sums) == 12 * 8, "mcp_downside_sums is twelve 8-byte words");
+static_assert(sizeof(mcp_relative_sums) == 18 * 8, "mcp_relative_sums is eighteen 8-byte words");
 }
 
 namespace mcph {
@@ -40,6 +49,17 @@ inline int n4_of(int n) { return 4 * ((n + 3) / 4); }
 inline size_t regime_block_len(int n) { const size_t n4 = (size_t)n4_of(n); return n4 + n4 * (n4 / 2 + 1); }
 // W rows are zero-padded to whole MFMA workgroups for a sweep, to whole KT_WIDE passes otherwise
 inline int kpad_of(int k) { return k >= SWEEP_MIN_K ? K_PAD * ((k + K_PAD - 1) / K_PAD) : KT_WIDE * ((k + KT_WIDE - 1) / KT_WIDE); }
+
+// A row-sum request riding a call (SPEC.md 5.22, 5.23): where the call's raw records of T gather, and the pivots they are about
+template <class T>
+struct RowSumRequest {
+  bool on = false;                      // the context was armed; set by the call that takes the request
+  bool hz = false;                      // the request also covers the horizon rows
+  T* sums = nullptr;                    // [K] the call's raw records: every tile adds its shards' in shard order
+  T* hz_sums = nullptr;                 // [H*K], row h*K + k
+  double* pivot = nullptr;              // [K] the pivots the records are about, as the tiles computed them
+  double* hz_pivot = nullptr;           // [H*K]
+};
 
 // The draws of a walk (SPEC.md 2): Gaussian steps mu + L z, rows of the bootstrap, Student-t steps mu + L s z, or filtered residual
 // rows scaled by the path's GARCH variance ratio (SPEC.md 2.4).
@@ -117,20 +137,10 @@ struct Request {
   bool anti = false;                    // SPEC.md 2.3 / 5.10: antithetic pairs
   mcp_pair* pair_out = nullptr;         // [K]
   double* cross_out = nullptr;          // [K] the call's cross sums: every tile adds its shards' in shard order
-  bool downside = false;                // SPEC.md 5.22: the context was armed (mcp_ctx_request_downside); set by the call that takes the request
-  bool ds_hz = false;                   // the request also covers the horizon rows
+  RowSumRequest<mcp_downside_sums> ds;  // SPEC.md 5.22: mcp_ctx_request_downside
   double ds_tau = 0.0;                  // the threshold, prm->rf when the request says so
-  mcp_downside_sums* ds_sums = nullptr;      // [K] the call's raw records: every tile adds its shards' in shard order
-  mcp_downside_sums* ds_hz_sums = nullptr;   // [H*K], row h*K + k
-  double* ds_pivot = nullptr;           // [K] the pivots the records are about, as the tiles computed them
-  double* ds_hz_pivot = nullptr;        // [H*K]
-  bool relative = false;                // SPEC.md 5.23: the context was armed (mcp_ctx_request_relative); set by the call that takes the request
-  bool rl_hz = false;                   // the request also covers the horizon rows
+  RowSumRequest<mcp_relative_sums> rl;  // SPEC.md 5.23: mcp_ctx_request_relative
   int rl_bench = 0;                     // the benchmark's row of W
-  mcp_relative_sums* rl_sums = nullptr;      // [K] the call's raw records: the tile's shards' added in shard order
-  mcp_relative_sums* rl_hz_sums = nullptr;   // [H*K], row h*K + k
-  double* rl_pivot = nullptr;           // [K] the pivots the records are about, as the tile computed them
-  double* rl_hz_pivot = nullptr;        // [H*K]
   float* rl_active_out = nullptr;       // NULL or host [K*n] Y = fl32(1 + a)
   mcp_stats* rl_active_stats_out = nullptr;  // NULL or [K] the records of Y
 };
@@ -345,12 +355,23 @@ struct DownsideArm {
   void arm(const mcp_downside& req, mcp_downside_sums* sums, mcp_downside_stats* stats, mcp_downside_stats* hz_stats);
   DownsideArm take();
 };
-// a += b, field by field: how the records of shards add up, in shard order
-void downside_add(mcp_downside_sums& a, const mcp_downside_sums& b);
+// a += b, word by word over the record's layout, the counts as integers and the sums as doubles: how the records of shards add up,
+// in shard order
+template <class T>
+inline void rowsum_add(T& a, const T& b) {
+  using L = mcp::RowSumLayout<T>;
+  uint64_t n[L::COUNTS], m[L::COUNTS];
+  double x[L::WORDS - L::COUNTS], y[L::WORDS - L::COUNTS];
+  memcpy(n, &a, sizeof n); memcpy(m, &b, sizeof m);
+  memcpy(x, (const char*)&a + sizeof n, sizeof x); memcpy(y, (const char*)&b + sizeof m, sizeof y);
+  for (int i = 0; i < L::COUNTS; i++) n[i] += m[i];
+  for (int i = 0; i < L::WORDS - L::COUNTS; i++) x[i] += y[i];
+  memcpy(&a, n, sizeof n); memcpy((char*)&a + sizeof n, x, sizeof x);
+}
 
 // ---- benchmark-relative statistics (SPEC.md 5.23) ----
-// What mcp_ctx_request_relative leaves on a context, with DownsideArm's contract: the next call that walks paths takes it, and taking
-// disarms.  Both requests may be armed at once; the same call serves both.
+// What mcp_ctx_request_relative leaves on a context: the next call that walks paths takes it, and taking disarms.  Both requests may
+// be armed at once; the same call serves both.
 struct RelativeArm {
   bool on = false;
   int bench = 0;
@@ -363,8 +384,6 @@ struct RelativeArm {
            mcp_relative_stats* hz_stats);
   RelativeArm take();
 };
-// a += b, field by field: how the records of shards add up, in shard order
-void relative_add(mcp_relative_sums& a, const mcp_relative_sums& b);
 
 // ---- the plan of a call: which shard does what in which tile ----
 // Bytes per path and portfolio that the tile budget counts: 4 of V_T, 4 per horizon row, 4 of the second array, 4 per integer record,

@@ -94,6 +94,8 @@ hipError_t launch_final(const mcp_params& prm, int K, uint64_t n, double gamma, 
 hipError_t launch_stats(const mcp_params& prm, int K, int world, const mcp_record* gathered, const Quantile* quant,
                         mcp_stats* out, hipStream_t s);
 hipError_t launch_zero(void* p, size_t bytes, hipStream_t s);
+// The launchers below that take `rows` rows put one workgroup column per row and cut the rows into slices of at most 65,535, what
+// gridDim.y holds: any rows >= 1 is served.  The two counts are one kernel over a predicate pair.
 // counts[r] += {#(v == 0), target ? #(v < *target) : 0} over the n live values of each of the `rows` rows of a [rows][stride]
 // binary32 array (SPEC.md 5.6); `counts` is [rows][2] and zeroed by the caller
 hipError_t launch_count_rows(const float* values, uint64_t stride, uint64_t n, int rows, bool has_target, float target,
@@ -113,7 +115,9 @@ hipError_t launch_sum_u64(unsigned long long* const* bufs, int nsrc, size_t word
 // [K][blocks][len], out [K][len]
 hipError_t launch_attr_merge(const double* partials, int K, int blocks, int len, double* out, hipStream_t s);
 
-// ---- downside and shape statistics (SPEC.md 5.22) ----
+// ---- the row-sum passes: downside and shape statistics (SPEC.md 5.22), benchmark-relative statistics (SPEC.md 5.23) ----
+// One kernel per record type over a shared row walker and workgroup record, one merge kernel for both, on the record layout that
+// RowSumLayout (mcp_host.h) declares.
 constexpr int DOWNSIDE_GRID_CAP = 512;   // workgroups per row; a row of more than 4 * 256 * 512 values is grid-strided
 constexpr int DOWNSIDE_BLOCK_VALUES = 1024;   // one 16-byte load per lane of a 256-thread workgroup
 // workgroups per row of the downside pass over n values: a function of n alone (include/mcport_downside.h, mcp_downside_grid)
@@ -126,7 +130,6 @@ __host__ __device__ inline int downside_grid(uint64_t n) {
 hipError_t launch_downside(const mcp_params& prm, const float* values, uint64_t stride, uint64_t n, int rows, const double* pivot,
                            double tau, mcp_downside_sums* partials, mcp_downside_sums* sums, hipStream_t s);
 
-// ---- benchmark-relative statistics (SPEC.md 5.23) ----
 // the grid of the downside pass: the same function of n (include/mcport_relative.h, mcp_relative_grid)
 __host__ __device__ inline int relative_grid(uint64_t n) { return downside_grid(n); }
 // sums[r] = the raw record of row r of `values` ([rows][stride], n live values) against row (r / group) group + bench, about the

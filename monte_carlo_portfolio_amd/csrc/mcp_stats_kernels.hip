@@ -60,6 +60,53 @@ static int stream_grid(uint64_t n, int K) {
   return (int)(g > cap ? cap : g);
 }
 
+// ---- the vector row walker ---------------------------------------------------------------------------------------------------------
+// Workgroup b of the G that share the n values at `src` (any 4-byte alignment: rows start wherever the caller's stride puts them):
+// a scalar head up to 16-byte alignment, a float4 body, a scalar tail.  The body is grid-strided with DEPTH 16-byte loads in flight per
+// lane: quad(i, q) takes the four values at src[i .. i + 3].  Head and tail, at most 6 elements of the row, go to workgroup 0:
+// single(i) takes src[i].  A lane meets its elements in this order -- ascending body slots, then head, then tail -- and that order is
+// the order of the caller's sums.  Lanes make different numbers of trips: nothing inside the callbacks may need a whole wave.
+struct RowSplit {
+  uint64_t hd, nvec;                  // elements of the head; 16-byte slots of the body, slot j at src[hd + 4 j]
+  const float4* __restrict__ vsrc;    // the body
+  uint64_t j0, vstep;                 // this lane's first slot and the stride of the row's G workgroups
+  int b;
+  __device__ __forceinline__ RowSplit(const float* __restrict__ src, uint64_t n, int G, int b_) : b(b_) {
+    const uint64_t head = n ? (uint64_t)((4 - (((uintptr_t)src >> 2) & 3)) & 3) : 0;
+    hd = head < n ? head : n;
+    nvec = (n - hd) / 4;
+    vsrc = (const float4*)(src + hd);
+    vstep = (uint64_t)G * SB;
+    j0 = (uint64_t)b * SB + threadIdx.x;
+  }
+  template <int DEPTH, class Quad>
+  __device__ __forceinline__ void body(Quad&& quad) const {
+    static_assert(DEPTH == 1 || DEPTH == 2, "one or two loads in flight");
+    uint64_t j = j0;
+    if constexpr (DEPTH == 2) {
+      for (; j + vstep < nvec; j += 2 * vstep) {
+        const float4 q0 = vsrc[j], q1 = vsrc[j + vstep];
+        quad(hd + 4 * j, q0);
+        quad(hd + 4 * (j + vstep), q1);
+      }
+    }
+    for (; j < nvec; j += vstep) quad(hd + 4 * j, vsrc[j]);
+  }
+  template <class Single>
+  __device__ __forceinline__ void edges(uint64_t n, Single&& single) const {
+    if (b != 0) return;
+    if (threadIdx.x < hd) single((uint64_t)threadIdx.x);
+    const uint64_t t = hd + 4 * nvec + threadIdx.x;
+    if (t < n) single(t);
+  }
+};
+template <int DEPTH, class Quad, class Single>
+__device__ __forceinline__ void row_walk(const float* __restrict__ src, uint64_t n, int G, int b, Quad&& quad, Single&& single) {
+  const RowSplit w(src, n, G, b);
+  w.body<DEPTH>(quad);
+  w.edges(n, single);
+}
+
 // "below" contribution of one terminal value (see the header comment)
 template <bool LOGC>
 __device__ __forceinline__ double below_term(float v, double v0d) {
@@ -182,7 +229,7 @@ __global__ void __launch_bounds__(SB) hist_kernel(const mcp_params prm, const fl
     }
   };
 
-  // rows start at arbitrary element offsets (stride is the caller's): scalar head up to 16-byte alignment, float4 body, scalar tail
+  // row_walk<2>, written out: this kernel is on the benchmark's path, and as a callback its instruction order moves
   const uint64_t head = n ? (uint64_t)((4 - (((uintptr_t)src >> 2) & 3)) & 3) : 0;
   const uint64_t hd = head < n ? head : n;
   const uint64_t nvec = (n - hd) / 4;
@@ -244,15 +291,6 @@ __device__ __forceinline__ unsigned long long block_exclusive_scan(unsigned long
   unsigned long long base = 0;
   for (int w = 0; w < wv; w++) base += wtot[w];
   return base + inc - v;
-}
-
-// fixed-order sum of one double per thread over the block -> every thread
-__device__ __forceinline__ double block_sum(double v, double* scratch /* [4] LDS */) {
-  v = wave_sum(v);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) scratch[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return (scratch[0] + scratch[1]) + (scratch[2] + scratch[3]);
 }
 
 // One descent step for target w of portfolio k: c[] = this thread's PER consecutive bins.  The thread owning the rank
@@ -570,81 +608,83 @@ hipError_t launch_zero(void* p, size_t bytes, hipStream_t s) {
   return hipGetLastError();
 }
 
-// SPEC.md 5.6: the ruined (V == +0) and the short (V < g32) paths of every row.  One workgroup column per row (blockIdx.y); a
-// wave counts its 64 values by ballot and population count in wave-uniform registers; the four waves meet in LDS and the
-// workgroup adds once per counter (every adder of a row lands on one address: the fewer the better).
-__global__ void __launch_bounds__(SB) count_rows_kernel(const float* __restrict__ values, uint64_t stride, uint64_t n, int has_target,
-                                                        float target, unsigned long long* __restrict__ counts) {
+// gridDim.y holds at most 65535 rows: launch(row0, nr) for the slices [row0, row0 + nr) of `rows` rows; the kernels index from row 0
+template <class Launch>
+static void for_row_slices(int rows, Launch&& launch) {
+  for (int r0 = 0; r0 < rows; r0 += 65535) launch(r0, rows - r0 < 65535 ? rows - r0 : 65535);
+}
+
+// workgroups per row of the kernels that walk a row 256 values at a time with a block-uniform trip count
+static unsigned row_blocks(uint64_t n) {
+  const uint64_t g = (n + SB - 1) / SB;
+  return (unsigned)(g < 1 ? 1 : (g > 256 ? 256 : g));
+}
+
+// The two counts of a row.  A predicate pair says what it counts: row(r) fetches what the pair needs of row r, a(v) and b(v) are the
+// two tests, `absent` is the value a lane beyond the row carries (no test looks at it: the lane is not live).
+struct RuinedShort {   // SPEC.md 5.6: the ruined (V == +0) and the short (V < g32) paths
+  int has_target;
+  float target;
+  static constexpr float absent = 1.0f;
+  __device__ void row(size_t) {}
+  __device__ bool a(float v) const { return v == 0.0f; }
+  __device__ bool b(float v) const { return has_target && v < target; }
+};
+struct BelowPair {     // SPEC.md 5.15: the paths below each of the row's two thresholds
+  const float* thr;    // [rows][2]
+  float ta, tb;
+  static constexpr float absent = 0.0f;
+  __device__ void row(size_t r) { ta = thr[2 * r]; tb = thr[2 * r + 1]; }
+  __device__ bool a(float v) const { return v < ta; }
+  __device__ bool b(float v) const { return v < tb; }
+};
+
+// One workgroup column per row (blockIdx.y); a wave counts its 64 values by ballot and population count in wave-uniform registers; the
+// four waves meet in LDS and the workgroup adds once per counter (every adder of a row lands on one address: the fewer the better).
+// The ballots need whole waves, hence the block-uniform trip count and not row_walk.
+template <class Pair>
+__global__ void __launch_bounds__(SB) count_kernel(const float* __restrict__ values, uint64_t stride, uint64_t n, int row0, Pair p,
+                                                   unsigned long long* __restrict__ counts) {
   __shared__ unsigned long long s_n[2];
   if (threadIdx.x < 2) s_n[threadIdx.x] = 0ull;
   __syncthreads();
-  const float* __restrict__ row = values + (size_t)blockIdx.y * stride;
-  unsigned long long nr = 0, ns = 0;
-  for (uint64_t base = (uint64_t)blockIdx.x * SB; base < n; base += (uint64_t)gridDim.x * SB) {   // block-uniform trip count
-    const uint64_t i = base + threadIdx.x;
-    const bool live = i < n;
-    const float v = live ? row[i] : 1.0f;
-    nr += (unsigned long long)__popcll(__ballot(live && v == 0.0f));
-    ns += (unsigned long long)__popcll(__ballot(live && has_target && v < target));
-  }
-  if ((threadIdx.x & 63) == 0) {
-    if (nr) atomicAdd(&s_n[0], nr);
-    if (ns) atomicAdd(&s_n[1], ns);
-  }
-  __syncthreads();
-  if (threadIdx.x < 2 && s_n[threadIdx.x]) atomicAdd(&counts[2 * (size_t)blockIdx.y + threadIdx.x], s_n[threadIdx.x]);
-}
-
-hipError_t launch_count_rows(const float* values, uint64_t stride, uint64_t n, int rows, bool has_target, float target,
-                             unsigned long long* counts, hipStream_t s) {
-  if (rows < 1) return hipErrorInvalidValue;
-  uint64_t g = (n + SB - 1) / SB;
-  if (g < 1) g = 1;
-  if (g > 256) g = 256;
-  for (int r0 = 0; r0 < rows; r0 += 65535) {             // gridDim.y holds at most 65535 rows
-    const int nr = rows - r0 < 65535 ? rows - r0 : 65535;
-    count_rows_kernel<<<dim3((unsigned)g, (unsigned)nr), SB, 0, s>>>(values + (size_t)r0 * stride, stride, n, has_target ? 1 : 0, target,
-                                                                    counts + 2 * (size_t)r0);
-  }
-  return hipGetLastError();
-}
-
-// SPEC.md 5.15: the paths below each of a row's two thresholds -- count_rows_kernel with two compares against per-row values.
-__global__ void __launch_bounds__(SB) count_below_kernel(const float* __restrict__ values, uint64_t stride, uint64_t n,
-                                                         const float* __restrict__ thr, unsigned long long* __restrict__ counts) {
-  __shared__ unsigned long long s_n[2];
-  if (threadIdx.x < 2) s_n[threadIdx.x] = 0ull;
-  __syncthreads();
-  const float* __restrict__ row = values + (size_t)blockIdx.y * stride;
-  const float ta = thr[2 * (size_t)blockIdx.y], tb = thr[2 * (size_t)blockIdx.y + 1];
+  const size_t r = (size_t)row0 + blockIdx.y;
+  const float* __restrict__ row = values + r * stride;
+  p.row(r);
   unsigned long long na = 0, nb = 0;
   for (uint64_t base = (uint64_t)blockIdx.x * SB; base < n; base += (uint64_t)gridDim.x * SB) {   // block-uniform trip count
     const uint64_t i = base + threadIdx.x;
     const bool live = i < n;
-    const float v = live ? row[i] : 0.0f;
-    na += (unsigned long long)__popcll(__ballot(live && v < ta));
-    nb += (unsigned long long)__popcll(__ballot(live && v < tb));
+    const float v = live ? row[i] : Pair::absent;
+    na += (unsigned long long)__popcll(__ballot(live && p.a(v)));
+    nb += (unsigned long long)__popcll(__ballot(live && p.b(v)));
   }
   if ((threadIdx.x & 63) == 0) {
     if (na) atomicAdd(&s_n[0], na);
     if (nb) atomicAdd(&s_n[1], nb);
   }
   __syncthreads();
-  if (threadIdx.x < 2 && s_n[threadIdx.x]) atomicAdd(&counts[2 * (size_t)blockIdx.y + threadIdx.x], s_n[threadIdx.x]);
+  if (threadIdx.x < 2 && s_n[threadIdx.x]) atomicAdd(&counts[2 * r + threadIdx.x], s_n[threadIdx.x]);
+}
+
+template <class Pair>
+static hipError_t launch_count(const float* values, uint64_t stride, uint64_t n, int rows, const Pair& p, unsigned long long* counts,
+                               hipStream_t s) {
+  if (rows < 1) return hipErrorInvalidValue;
+  for_row_slices(rows, [&](int r0, int nr) {
+    count_kernel<Pair><<<dim3(row_blocks(n), (unsigned)nr), SB, 0, s>>>(values, stride, n, r0, p, counts);
+  });
+  return hipGetLastError();
+}
+
+hipError_t launch_count_rows(const float* values, uint64_t stride, uint64_t n, int rows, bool has_target, float target,
+                             unsigned long long* counts, hipStream_t s) {
+  return launch_count(values, stride, n, rows, RuinedShort{has_target ? 1 : 0, target}, counts, s);
 }
 
 hipError_t launch_count_below(const float* values, uint64_t stride, uint64_t n, int rows, const float* thr, unsigned long long* counts,
                               hipStream_t s) {
-  if (rows < 1) return hipErrorInvalidValue;
-  uint64_t g = (n + SB - 1) / SB;
-  if (g < 1) g = 1;
-  if (g > 256) g = 256;
-  for (int r0 = 0; r0 < rows; r0 += 65535) {             // gridDim.y holds at most 65535 rows
-    const int nr = rows - r0 < 65535 ? rows - r0 : 65535;
-    count_below_kernel<<<dim3((unsigned)g, (unsigned)nr), SB, 0, s>>>(values + (size_t)r0 * stride, stride, n, thr + 2 * (size_t)r0,
-                                                                     counts + 2 * (size_t)r0);
-  }
-  return hipGetLastError();
+  return launch_count(values, stride, n, rows, BelowPair{thr, 0.0f, 0.0f}, counts, s);
 }
 
 // SPEC.md 5.17: the histogram of the lifetimes l of every row.  Most paths survive and land on the one bin l = T, and 64 lanes on
@@ -698,12 +738,14 @@ __global__ void __launch_bounds__(SB) life_hist_kernel(const uint32_t* __restric
 
 hipError_t launch_life_hist(const uint32_t* life, uint64_t stride, uint64_t n, int rows, uint32_t bins, unsigned long long* hist,
                             hipStream_t s) {
-  if (rows < 1 || rows > 65535 || bins < 1) return hipErrorInvalidValue;
-  uint64_t g = (n + SB - 1) / SB;
-  if (g < 1) g = 1;
-  if (g > 256) g = 256;
-  if (bins <= LIFE_LDS_BINS) life_hist_kernel<true><<<dim3((unsigned)g, (unsigned)rows), SB, 0, s>>>(life, stride, n, bins, hist);
-  else life_hist_kernel<false><<<dim3((unsigned)g, (unsigned)rows), SB, 0, s>>>(life, stride, n, bins, hist);
+  if (rows < 1 || bins < 1) return hipErrorInvalidValue;
+  for_row_slices(rows, [&](int r0, int nr) {               // the kernel's rows are blockIdx.y alone: a slice starts at its own row 0
+    const dim3 grid(row_blocks(n), (unsigned)nr);
+    const uint32_t* l = life + (size_t)r0 * stride;
+    unsigned long long* h = hist + (size_t)r0 * bins;
+    if (bins <= LIFE_LDS_BINS) life_hist_kernel<true><<<grid, SB, 0, s>>>(l, stride, n, bins, h);
+    else life_hist_kernel<false><<<grid, SB, 0, s>>>(l, stride, n, bins, h);
+  });
   return hipGetLastError();
 }
 
@@ -735,22 +777,91 @@ hipError_t launch_attr_merge(const double* partials, int K, int blocks, int len,
   return hipGetLastError();
 }
 
-// ---- downside and shape statistics (SPEC.md 5.22) --------------------------------------------------------------------------------
-// One streaming pass over the [rows][stride] values beside pass0: x as terminal_to_x forms it (one IEEE division per element, or
-// expm1), d = x - c and e = x - tau, and per lane the nine sums and three counts of mcp_downside_sums; every product is rounded once
-// (-ffp-contract=off) and a summand outside its set enters as + 0.0.  blockIdx.y is the row, blockIdx.x the workgroup of the row: wave
-// sums by shuffle, the four waves in LDS, then field j of the workgroup's record by thread j.  The record is twelve 8-byte words, the
-// counts first.  4 B of traffic against one fp64 division and some twenty fp64 operations per element.
-constexpr int DS_WORDS = 12;
-static_assert(sizeof(mcp_downside_sums) == DS_WORDS * 8, "mcp_downside_sums is twelve 8-byte words");
+// ---- the row-sum passes: downside and shape statistics (SPEC.md 5.22), benchmark-relative statistics (SPEC.md 5.23) -----------------
+// One streaming pass over the [rows][stride] values beside pass0.  blockIdx.y is the row (from row0: for_row_slices), blockIdx.x the
+// workgroup of the row; row_walk hands every lane its values, the lane keeps the sums and counts of its record (RowSumLayout,
+// mcp_host.h: 8-byte words, the counts first), block_record adds the workgroup's lanes into one record of `partials`
+// ([rows][downside_grid(n)]) and rowsum_merge_kernel adds a row's records in block order.  Every product is rounded once
+// (-ffp-contract=off) and a summand outside its set enters as + 0.0.
 
+// The workgroup's record from one value per lane and word: wave sums by shuffle, the four waves in LDS, then word i by thread i -- the
+// COUNTS leading words as integers (below 2^53: exact in a double), the rest as the bits of the double.
+template <int WORDS, int COUNTS>
+__device__ __forceinline__ void block_record(const double (&mine)[WORDS], unsigned long long* __restrict__ out) {
+  __shared__ double red[4][WORDS];
+  double w[WORDS];
+#pragma unroll
+  for (int i = 0; i < WORDS; i++) w[i] = wave_sum(mine[i]);
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  if (lane == 0) {
+#pragma unroll
+    for (int i = 0; i < WORDS; i++) red[wv][i] = w[i];
+  }
+  __syncthreads();
+  if (threadIdx.x < WORDS) {
+    const int i = threadIdx.x;
+    const double t = (red[0][i] + red[1][i]) + (red[2][i] + red[3][i]);
+    out[i] = i < COUNTS ? (unsigned long long)t : (unsigned long long)__double_as_longlong(t);
+  }
+}
+
+// The workgroups' records of one row in a fixed order: grid = rows, one wave; lane l adds records l, l + 64, ... in increasing block
+// order (at most DOWNSIDE_GRID_CAP / 64 = 8 of them, neighbouring lanes on neighbouring records), then the wave's butterfly; lane 0
+// writes the words.  (One thread per word walking all 512 records is a chain of 512 dependent loads: the launch took 150 us over 10^6
+// values that way.)
+template <int WORDS, int COUNTS>
+__global__ void __launch_bounds__(64) rowsum_merge_kernel(const unsigned long long* __restrict__ partials, int G,
+                                                          unsigned long long* __restrict__ sums) {
+  const unsigned long long* __restrict__ src = partials + (size_t)blockIdx.x * G * WORDS;
+  unsigned long long cnt[COUNTS] = {};
+  double a[WORDS - COUNTS] = {};
+  for (int g = threadIdx.x; g < G; g += 64) {
+    const unsigned long long* p = src + (size_t)g * WORDS;
+#pragma unroll
+    for (int i = 0; i < COUNTS; i++) cnt[i] += p[i];
+#pragma unroll
+    for (int i = COUNTS; i < WORDS; i++) a[i - COUNTS] += __longlong_as_double((long long)p[i]);
+  }
+  // Lane 0 stores the words in bursts of six behind their sums.  A store behind every wave_sum stretches this one-wave, latency-bound
+  // kernel (1.4 us per launch at twelve words); all eighteen sums ahead of one burst cost 18 more VGPRs and two waves of occupancy.
+  unsigned long long* out = sums + (size_t)blockIdx.x * WORDS;
+  constexpr int BURST = 6;
+  static_assert(WORDS % BURST == 0, "whole bursts");
+#pragma unroll
+  for (int i0 = 0; i0 < WORDS; i0 += BURST) {
+    unsigned long long o[BURST];
+#pragma unroll
+    for (int i = i0; i < i0 + BURST; i++) {
+      const double t = wave_sum(i < COUNTS ? (double)cnt[i] : a[i - COUNTS]);   // the counts: < 2^53, exact
+      o[i - i0] = i < COUNTS ? (unsigned long long)t : (unsigned long long)__double_as_longlong(t);
+    }
+    if (threadIdx.x == 0) {
+#pragma unroll
+      for (int i = 0; i < BURST; i++) out[i0 + i] = o[i];
+    }
+  }
+}
+
+// pass(grid, row0) launches the row-sum kernel of T on every slice of the rows; then the merge
+template <class T, class Pass>
+static hipError_t launch_rowsum(uint64_t n, int rows, const T* partials, T* sums, hipStream_t s, Pass&& pass) {
+  using L = RowSumLayout<T>;
+  const int G = downside_grid(n);
+  for_row_slices(rows, [&](int r0, int nr) { pass(dim3((unsigned)G, (unsigned)nr), r0); });
+  rowsum_merge_kernel<L::WORDS, L::COUNTS><<<(unsigned)rows, 64, 0, s>>>((const unsigned long long*)partials, G, (unsigned long long*)sums);
+  return hipGetLastError();
+}
+
+// SPEC.md 5.22: x as terminal_to_x forms it (one IEEE division per element, or expm1), d = x - c and e = x - tau, and per lane the
+// three counts and nine sums of mcp_downside_sums.  Two loads in flight: 4 B of traffic against one fp64 division and some twenty fp64
+// operations per element.
 template <bool LOGC>
-__global__ void __launch_bounds__(SB) downside_kernel(double v0d, const float* __restrict__ values, uint64_t stride, uint64_t n,
+__global__ void __launch_bounds__(SB) downside_kernel(double v0d, const float* __restrict__ values, uint64_t stride, uint64_t n, int row0,
                                                       const double* __restrict__ pivot, double tau,
                                                       mcp_downside_sums* __restrict__ partials) {
-  __shared__ double red[4][DS_WORDS];
+  using L = RowSumLayout<mcp_downside_sums>;
   const int G = gridDim.x, b = blockIdx.x;
-  const size_t r = blockIdx.y;
+  const size_t r = (size_t)row0 + blockIdx.y;
   const float* __restrict__ src = values + r * stride;
   const double c = pivot ? pivot[r] : 0.0;
   double s1 = 0.0, s2 = 0.0, s3 = 0.0, s4 = 0.0, b1 = 0.0, b2 = 0.0, l1 = 0.0, l2 = 0.0, u1 = 0.0;
@@ -767,104 +878,36 @@ __global__ void __launch_bounds__(SB) downside_kernel(double v0d, const float* _
     l1 += lo ? e : 0.0; l2 += lo ? e2 : 0.0;
     u1 += hi ? e : 0.0;
   };
+  row_walk<2>(src, n, G, b, [&](uint64_t, float4 q) { one(q.x); one(q.y); one(q.z); one(q.w); }, [&](uint64_t i) { one(src[i]); });
 
-  // rows start at arbitrary element offsets: scalar head up to 16-byte alignment, float4 body, scalar tail (as hist_kernel)
-  const uint64_t head = n ? (uint64_t)((4 - (((uintptr_t)src >> 2) & 3)) & 3) : 0;
-  const uint64_t hd = head < n ? head : n;
-  const uint64_t nvec = (n - hd) / 4;
-  const float4* __restrict__ vsrc = (const float4*)(src + hd);
-  const uint64_t vstep = (uint64_t)G * SB;
-  uint64_t j = (uint64_t)b * SB + threadIdx.x;
-  for (; j + vstep < nvec; j += 2 * vstep) {              // two 16-byte loads in flight per lane
-    const float4 q0 = vsrc[j], q1 = vsrc[j + vstep];
-    one(q0.x); one(q0.y); one(q0.z); one(q0.w);
-    one(q1.x); one(q1.y); one(q1.z); one(q1.w);
-  }
-  for (; j < nvec; j += vstep) {
-    const float4 q0 = vsrc[j];
-    one(q0.x); one(q0.y); one(q0.z); one(q0.w);
-  }
-  if (b == 0) {                                           // head and tail scalars: at most 6 elements of the row
-    if (threadIdx.x < hd) one(src[threadIdx.x]);
-    const uint64_t t0 = hd + 4 * nvec;
-    if (t0 + threadIdx.x < n) one(src[t0 + threadIdx.x]);
-  }
-
-  const double w[DS_WORDS] = {wave_sum((double)m), wave_sum((double)nb), wave_sum((double)na),   // < 2^53: exact
-                              wave_sum(s1), wave_sum(s2), wave_sum(s3), wave_sum(s4), wave_sum(b1), wave_sum(b2),
-                              wave_sum(l1), wave_sum(l2), wave_sum(u1)};
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  if (lane == 0) {
-#pragma unroll
-    for (int i = 0; i < DS_WORDS; i++) red[wv][i] = w[i];
-  }
-  __syncthreads();
-  if (threadIdx.x < DS_WORDS) {
-    const int i = threadIdx.x;
-    const double t = (red[0][i] + red[1][i]) + (red[2][i] + red[3][i]);
-    unsigned long long* out = (unsigned long long*)(partials + (r * (size_t)G + b));
-    out[i] = i < 3 ? (unsigned long long)t : (unsigned long long)__double_as_longlong(t);
-  }
-}
-
-// the workgroups' records of one row in a fixed order: grid = rows, one wave; lane l adds records l, l + 64, ... in increasing block
-// order (at most DOWNSIDE_GRID_CAP / 64 = 8 of them, neighbouring lanes on neighbouring records), then the wave's butterfly.  (One
-// thread per word walking all 512 records is a chain of 512 dependent loads: the launch took 150 us over 10^6 values that way.)
-__global__ void __launch_bounds__(64) downside_merge_kernel(const mcp_downside_sums* __restrict__ partials, int G,
-                                                            mcp_downside_sums* __restrict__ sums) {
-  const mcp_downside_sums* __restrict__ src = partials + (size_t)blockIdx.x * G;
-  mcp_downside_sums a = {};
-  for (int b = threadIdx.x; b < G; b += 64) {
-    const mcp_downside_sums p = src[b];
-    a.n += p.n; a.n_below += p.n_below; a.n_above += p.n_above;
-    a.s1 += p.s1; a.s2 += p.s2; a.s3 += p.s3; a.s4 += p.s4;
-    a.b1 += p.b1; a.b2 += p.b2; a.l1 += p.l1; a.l2 += p.l2; a.u1 += p.u1;
-  }
-  mcp_downside_sums o;
-  o.n = (unsigned long long)wave_sum((double)a.n);                 // < 2^53: exact
-  o.n_below = (unsigned long long)wave_sum((double)a.n_below);
-  o.n_above = (unsigned long long)wave_sum((double)a.n_above);
-  o.s1 = wave_sum(a.s1); o.s2 = wave_sum(a.s2); o.s3 = wave_sum(a.s3); o.s4 = wave_sum(a.s4);
-  o.b1 = wave_sum(a.b1); o.b2 = wave_sum(a.b2); o.l1 = wave_sum(a.l1); o.l2 = wave_sum(a.l2); o.u1 = wave_sum(a.u1);
-  if (threadIdx.x == 0) sums[blockIdx.x] = o;
+  const double mine[L::WORDS] = {(double)m, (double)nb, (double)na, s1, s2, s3, s4, b1, b2, l1, l2, u1};
+  block_record<L::WORDS, L::COUNTS>(mine, (unsigned long long*)(partials + (r * (size_t)G + b)));
 }
 
 hipError_t launch_downside(const mcp_params& prm, const float* values, uint64_t stride, uint64_t n, int rows, const double* pivot,
                            double tau, mcp_downside_sums* partials, mcp_downside_sums* sums, hipStream_t s) {
   if (rows < 1) return hipErrorInvalidValue;
-  const int G = downside_grid(n);
   const double v0d = (double)(float)prm.v0;
-  for (int r0 = 0; r0 < rows; r0 += 65535) {             // gridDim.y holds at most 65535 rows
-    const int nr = rows - r0 < 65535 ? rows - r0 : 65535;
-    const dim3 grid((unsigned)G, (unsigned)nr);
-    const float* v = values + (size_t)r0 * stride;
-    const double* p = pivot ? pivot + r0 : nullptr;
-    mcp_downside_sums* out = partials + (size_t)r0 * G;
-    if (prm.compounding == MCP_COMPOUND_LOG) downside_kernel<true><<<grid, SB, 0, s>>>(v0d, v, stride, n, p, tau, out);
-    else downside_kernel<false><<<grid, SB, 0, s>>>(v0d, v, stride, n, p, tau, out);
-  }
-  downside_merge_kernel<<<(unsigned)rows, 64, 0, s>>>(partials, G, sums);
-  return hipGetLastError();
+  return launch_rowsum(n, rows, partials, sums, s, [&](dim3 grid, int r0) {
+    if (prm.compounding == MCP_COMPOUND_LOG) downside_kernel<true><<<grid, SB, 0, s>>>(v0d, values, stride, n, r0, pivot, tau, partials);
+    else downside_kernel<false><<<grid, SB, 0, s>>>(v0d, values, stride, n, r0, pivot, tau, partials);
+  });
 }
 
-// ---- benchmark-relative statistics (SPEC.md 5.23) --------------------------------------------------------------------------------
-// The two-row sibling of downside_kernel: row r of the [rows][stride] values against row rb = (r / group) group + bench, element by
-// element.  x of both as terminal_to_x forms it, d_k = x_k - c_k, d_b = x_b - c_b, e = d_k - d_b, a = x_k - x_b, and per lane the
-// thirteen sums and five counts of mcp_relative_sums; every product is rounded once (-ffp-contract=off) and a summand outside its set
-// enters as + 0.0.  Y = fl32(1 + a) goes to `active` when it is given.  Grid, workgroup reduction and record layout are
-// downside_kernel's: blockIdx.y the row, blockIdx.x the workgroup of the row, the counts first.
-// The two rows lie (r - rb) stride elements apart, so with stride % 4 != 0 they differ in alignment modulo 16 bytes.  The head / float4
-// body / tail split is made on row r; the benchmark's four values of a body slot and Y's four are moved as one 16-byte access when
-// their own address is 16-byte aligned there (a workgroup-uniform test), else as four 4-byte ones, which are right at any 4-byte
-// alignment: neighbouring lanes still cover whole cache lines between them.
-constexpr int RL_COUNTS = 5, RL_WORDS = 18;
-static_assert(sizeof(mcp_relative_sums) == RL_WORDS * 8, "mcp_relative_sums is eighteen 8-byte words");
-
+// SPEC.md 5.23: row r against row rb = (r / group) group + bench, element by element.  x of both as terminal_to_x forms it,
+// d_k = x_k - c_k, d_b = x_b - c_b, e = d_k - d_b, a = x_k - x_b, and per lane the five counts and thirteen sums of mcp_relative_sums.
+// Y = fl32(1 + a) goes to `active` when it is given.  One load in flight.
+// The two rows lie (r - rb) stride elements apart, so with stride % 4 != 0 they differ in alignment modulo 16 bytes.  The split is made
+// on row r; the benchmark's four values of a body slot and Y's four are moved as one 16-byte access when their own address is 16-byte
+// aligned there (a workgroup-uniform test), else as four 4-byte ones, which are right at any 4-byte alignment: neighbouring lanes
+// still cover whole cache lines between them.
+// The body loop is RowSplit::body<1> written out, on the split's own fields: with the body handed over as a callback the log
+// instantiation takes 112 VGPRs instead of 94 and loses a wave of occupancy.  Head and tail go through edges().
 template <bool LOGC>
 __global__ void __launch_bounds__(SB) relative_kernel(double v0d, const float* __restrict__ values, uint64_t stride, uint64_t n, int row0,
                                                       int group, int bench, const double* __restrict__ pivot,
                                                       mcp_relative_sums* __restrict__ partials, float* __restrict__ active) {
-  __shared__ double red[4][RL_WORDS];
+  using L = RowSumLayout<mcp_relative_sums>;
   const int G = gridDim.x, b = blockIdx.x;
   const size_t r = (size_t)row0 + blockIdx.y;
   const size_t rb = r / (size_t)group * (size_t)group + (size_t)bench;
@@ -890,94 +933,43 @@ __global__ void __launch_bounds__(SB) relative_kernel(double v0d, const float* _
     dnk += down ? xk : 0.0; dnb += down ? xb : 0.0;
     return (float)(1.0 + a);
   };
-
-  const uint64_t head = n ? (uint64_t)((4 - (((uintptr_t)src >> 2) & 3)) & 3) : 0;
-  const uint64_t hd = head < n ? head : n;
-  const uint64_t nvec = (n - hd) / 4;
-  const float4* __restrict__ vsrc = (const float4*)(src + hd);
-  const bool bvec = (((uintptr_t)(bsrc + hd)) & 15) == 0;          // the benchmark's slots are 16-byte aligned where row r's are
-  const bool yvec = dst && (((uintptr_t)(dst + hd)) & 15) == 0;
-  const uint64_t vstep = (uint64_t)G * SB;
-  for (uint64_t j = (uint64_t)b * SB + threadIdx.x; j < nvec; j += vstep) {
-    const float4 q = vsrc[j];
-    const float* bp = bsrc + hd + 4 * j;
+  const RowSplit w(src, n, G, b);
+  const bool bvec = (((uintptr_t)(bsrc + w.hd)) & 15) == 0;        // the benchmark's slots are 16-byte aligned where row r's are
+  const bool yvec = dst && (((uintptr_t)(dst + w.hd)) & 15) == 0;
+  for (uint64_t j = w.j0; j < w.nvec; j += w.vstep) {
+    const float4 q = w.vsrc[j];
+    const float* bp = bsrc + w.hd + 4 * j;
     float4 p;
     if (bvec) p = *(const float4*)bp;
     else { p.x = bp[0]; p.y = bp[1]; p.z = bp[2]; p.w = bp[3]; }
     float4 y;
     y.x = one(q.x, p.x); y.y = one(q.y, p.y); y.z = one(q.z, p.z); y.w = one(q.w, p.w);
     if (dst) {
-      float* yp = dst + hd + 4 * j;
+      float* yp = dst + w.hd + 4 * j;
       if (yvec) *(float4*)yp = y;
       else { yp[0] = y.x; yp[1] = y.y; yp[2] = y.z; yp[3] = y.w; }
     }
   }
-  if (b == 0) {                                           // head and tail scalars: at most 6 elements of the row
-    if (threadIdx.x < hd) {
-      const float y = one(src[threadIdx.x], bsrc[threadIdx.x]);
-      if (dst) dst[threadIdx.x] = y;
-    }
-    const uint64_t t0 = hd + 4 * nvec + threadIdx.x;
-    if (t0 < n) {
-      const float y = one(src[t0], bsrc[t0]);
-      if (dst) dst[t0] = y;
-    }
-  }
+  w.edges(n, [&](uint64_t i) {
+    const float y = one(src[i], bsrc[i]);
+    if (dst) dst[i] = y;
+  });
 
-  const double w[RL_WORDS] = {wave_sum((double)m), wave_sum((double)nu), wave_sum((double)no), wave_sum((double)nup),   // < 2^53: exact
-                              wave_sum((double)ndn), wave_sum(e1), wave_sum(e2), wave_sum(k1), wave_sum(b1), wave_sum(k2), wave_sum(b2),
-                              wave_sum(kb), wave_sum(u1), wave_sum(u2), wave_sum(upk), wave_sum(upb), wave_sum(dnk), wave_sum(dnb)};
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  if (lane == 0) {
-#pragma unroll
-    for (int i = 0; i < RL_WORDS; i++) red[wv][i] = w[i];
-  }
-  __syncthreads();
-  if (threadIdx.x < RL_WORDS) {
-    const int i = threadIdx.x;
-    const double t = (red[0][i] + red[1][i]) + (red[2][i] + red[3][i]);
-    unsigned long long* out = (unsigned long long*)(partials + (r * (size_t)G + b));
-    out[i] = i < RL_COUNTS ? (unsigned long long)t : (unsigned long long)__double_as_longlong(t);
-  }
-}
-
-// the workgroups' records of one row in downside_merge_kernel's fixed order: grid = rows, one wave; lane l adds records l, l + 64, ...
-// in increasing block order, then the wave's butterfly; word i of the result by lane i
-__global__ void __launch_bounds__(64) relative_merge_kernel(const mcp_relative_sums* __restrict__ partials, int G,
-                                                            mcp_relative_sums* __restrict__ sums) {
-  const unsigned long long* __restrict__ src = (const unsigned long long*)(partials + (size_t)blockIdx.x * G);
-  unsigned long long cnt[RL_COUNTS] = {};
-  double a[RL_WORDS - RL_COUNTS] = {};
-  for (int g = threadIdx.x; g < G; g += 64) {
-    const unsigned long long* p = src + (size_t)g * RL_WORDS;
-#pragma unroll
-    for (int i = 0; i < RL_COUNTS; i++) cnt[i] += p[i];
-#pragma unroll
-    for (int i = RL_COUNTS; i < RL_WORDS; i++) a[i - RL_COUNTS] += __longlong_as_double((long long)p[i]);
-  }
-  unsigned long long* out = (unsigned long long*)(sums + blockIdx.x);
-#pragma unroll
-  for (int i = 0; i < RL_WORDS; i++) {
-    const double t = wave_sum(i < RL_COUNTS ? (double)cnt[i] : a[i - RL_COUNTS]);   // the counts: < 2^53, exact
-    if (threadIdx.x == 0) out[i] = i < RL_COUNTS ? (unsigned long long)t : (unsigned long long)__double_as_longlong(t);
-  }
+  const double mine[L::WORDS] = {(double)m, (double)nu, (double)no, (double)nup, (double)ndn, e1, e2, k1, b1, k2, b2, kb, u1, u2,
+                                 upk, upb, dnk, dnb};
+  block_record<L::WORDS, L::COUNTS>(mine, (unsigned long long*)(partials + (r * (size_t)G + b)));
 }
 
 hipError_t launch_relative(const mcp_params& prm, const float* values, uint64_t stride, uint64_t n, int rows, int group, int bench,
                            const double* pivot, mcp_relative_sums* partials, mcp_relative_sums* sums, float* active, hipStream_t s) {
   if (rows < 1 || group < 1 || rows % group != 0 || bench < 0 || bench >= group) return hipErrorInvalidValue;
-  const int G = relative_grid(n);
   const double v0d = (double)(float)prm.v0;
-  for (int r0 = 0; r0 < rows; r0 += 65535) {             // gridDim.y holds at most 65535 rows; the kernel indexes from row 0
-    const int nr = rows - r0 < 65535 ? rows - r0 : 65535;
-    const dim3 grid((unsigned)G, (unsigned)nr);
+  return launch_rowsum(n, rows, partials, sums, s, [&](dim3 grid, int r0) {
     if (prm.compounding == MCP_COMPOUND_LOG)
       relative_kernel<true><<<grid, SB, 0, s>>>(v0d, values, stride, n, r0, group, bench, pivot, partials, active);
     else
       relative_kernel<false><<<grid, SB, 0, s>>>(v0d, values, stride, n, r0, group, bench, pivot, partials, active);
-  }
-  relative_merge_kernel<<<(unsigned)rows, 64, 0, s>>>(partials, G, sums);
-  return hipGetLastError();
+  });
 }
 
 }  // namespace mcp

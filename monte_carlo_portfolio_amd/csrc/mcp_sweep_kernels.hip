@@ -18,20 +18,11 @@
 #include <stdint.h>
 
 #include "../../include/mcport.h"
+#include "mcp_reduce.h"
 #include "mcp_stats_kernels.h"
 
 namespace mcp {
 
-__device__ __forceinline__ double wsum(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-__device__ __forceinline__ double wmin(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmin(v, __shfl_xor(v, o, 64));
-  return v;
-}
 // The tail sum as an unevaluated pair s + c: c collects what every addition rounds away (Knuth's TwoSum, exact here because the
 // build neither contracts nor reassociates), so the sum is the exact one rounded once, in whatever order the lanes add.  A plain
 // tree of R / 256 + 8 additions is off by up to that many roundings of the running sum, which a tail of equal or nearly equal
@@ -81,8 +72,8 @@ __global__ void __launch_bounds__(64) sweep_hist_kernel(int N, int R, const doub
     for (int j = 0; j < N; j++) cw += cov[(size_t)i * N + j] * w[j];
     pv += w[i] * cw;
   }
-  pr = wsum(pr);
-  pv = wsum(pv);
+  pr = wave_sum(pr);
+  pv = wave_sum(pv);
   const double sd = sqrt(pv);
 
   // historical portfolio return series
@@ -106,7 +97,7 @@ __global__ void __launch_bounds__(64) sweep_hist_kernel(int N, int R, const doub
     if (rk == rank_hi) b_part = x;
   }
   // exactly one lane holds each; all others contribute +0.0 (x + 0.0 == x, also for -0.0 + 0.0 -> +0.0: harmless)
-  const double a = wsum(a_part), b = wsum(b_part);
+  const double a = wave_sum(a_part), b = wave_sum(b_part);
   const double diff = b - a;
   double v = a + diff * gamma;                    // numpy _lerp
   if (gamma >= 0.5) v = b - diff * (1.0 - gamma);
@@ -117,9 +108,9 @@ __global__ void __launch_bounds__(64) sweep_hist_kernel(int N, int R, const doub
     const double x = series[r];
     if (x <= v) { cnt += 1.0; add2(sum, x); lo = fmin(lo, x); }
   }
-  cnt = wsum(cnt);
+  cnt = wave_sum(cnt);
   sum = wsum2(sum);
-  lo = wmin(lo);
+  lo = wave_min(lo);
   if (lane == 0) {
     out_ret[p] = pr;
     out_std[p] = sd;
@@ -131,13 +122,6 @@ __global__ void __launch_bounds__(64) sweep_hist_kernel(int N, int R, const doub
 
 // ---- R > 256: sort instead of counting ranks ---------------------------------------------------------------------------
 constexpr int SORT_BLOCK = 256;
-__device__ __forceinline__ double bsum(double v, double* red /* [4] LDS */) {
-  v = wsum(v);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return (red[0] + red[1]) + (red[2] + red[3]);
-}
 __device__ __forceinline__ Sum2 bsum2(Sum2 a, double* red /* [8] LDS */) {
   a = wsum2(a);
   __syncthreads();
@@ -171,8 +155,8 @@ __global__ void __launch_bounds__(SORT_BLOCK) sweep_hist_sorted_kernel(int N, in
     for (int j = 0; j < N; j++) cw += cov[(size_t)i * N + j] * w[j];
     pv += w[i] * cw;
   }
-  pr = bsum(pr, red);
-  pv = bsum(pv, red);
+  pr = block_sum(pr, red);
+  pv = block_sum(pv, red);
   const double sd = sqrt(pv);
 
   // historical portfolio return series (app.py:710), padded with +inf up to the power of two
@@ -210,7 +194,7 @@ __global__ void __launch_bounds__(SORT_BLOCK) sweep_hist_sorted_kernel(int N, in
     const double x = series[r];
     if (x <= v) { cnt += 1.0; add2(sum, x); }
   }
-  cnt = bsum(cnt, red);
+  cnt = block_sum(cnt, red);
   sum = bsum2(sum, red);
   if (tid == 0) {
     out_ret[p] = pr;

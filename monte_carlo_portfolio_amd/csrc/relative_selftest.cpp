@@ -64,7 +64,7 @@ static void run_finish() {
   EXPECT(mcp_relative_finish(nullptr, 0.0, 0.0, &o) == MCP_E_ARG && mcp_relative_finish(&four, 0.0, 0.0, nullptr) == MCP_E_ARG);
 
   mcp_relative_sums a = four;
-  relative_add(a, one);
+  rowsum_add(a, one);
   EXPECT(a.n == 5 && a.n_under == 1 && a.n_over == 3 && a.n_up == 2 && a.n_down == 3 && a.e1 == 1.125 && a.e2 == 0.578125);
   EXPECT(a.k1 == 1.25 && a.b1 == 0.125 && a.k2 == 0.9375 && a.b2 == 0.953125 && a.kb == 0.65625 && a.u1 == -0.125 && a.u2 == 0.015625);
   EXPECT(a.up_k == 1.25 && a.up_b == 1.0 && a.down_k == 0.0 && a.down_b == -0.875);
@@ -118,16 +118,16 @@ static void run_plan() {
   Request rq;
   const size_t base = tile_bytes_per_path(rq);
   EXPECT(base == 4);
-  rq.relative = true;
+  rq.rl.on = true;
   EXPECT(tile_bytes_per_path(rq) == base + 4);
   rq.hz = true;
   rq.H = 2;
   EXPECT(tile_bytes_per_path(rq) == 16);                   // V_T, two horizon rows, Y: no Y at the horizons
   rq.dd = true;
   EXPECT(tile_bytes_per_path(rq) == 20);                   // the second array and Y are two arrays
-  rq.relative = false;
+  rq.rl.on = false;
   EXPECT(tile_bytes_per_path(rq) == 16);
-  rq.downside = true;                                      // the downside request stores nothing per path
+  rq.ds.on = true;                                      // the downside request stores nothing per path
   EXPECT(tile_bytes_per_path(rq) == 16);
 
   snprintf(g_case, sizeof g_case, "relative one-tile rule");

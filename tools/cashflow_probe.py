@@ -28,6 +28,8 @@ import numpy as np  # noqa: E402
 
 from monte_carlo_portfolio_amd import simulate_bootstrap, simulate_paths, synthetic  # noqa: E402
 
+COUNT_ROWS = "count_kernel<mcp::RuinedShort>"      # launch_count_rows' kernel as the trace names it
+
 N, T, P = 16, 252, 1_000_000
 HZ = dict(horizons=[21, 63, 126, 252], bands=(5.0, 50.0, 95.0))
 FLOW = 0.001                       # a contribution: no path is ruined, the statistics passes see what the twin's see
@@ -114,8 +116,8 @@ def summarize(d, rounds, warm, calls_json):
         part = lambda sub: [sum(ms(r) for r in c[1:] if sub in r["Kernel_Name"]) for c in mine]   # noqa: E731
         k[name] = {"kernel": mine[0][0]["Kernel_Name"].split("(")[0], "median_ms": med(t), "min_ms": min(t), "max_ms": max(t),
                    "hist_kernel_ms": med(part("hist_kernel")), "hist_kernel_dispatches": sum("hist_kernel" in r["Kernel_Name"] for r in mine[0]),
-                   "count_rows_kernel_ms": med(part("count_rows_kernel")),
-                   "count_rows_kernel_dispatches": sum("count_rows_kernel" in r["Kernel_Name"] for r in mine[0]),
+                   "count_rows_kernel_ms": med(part(COUNT_ROWS)),
+                   "count_rows_kernel_dispatches": sum(COUNT_ROWS in r["Kernel_Name"] for r in mine[0]),
                    "all_dispatches_ms": med([sum(ms(r) for r in c) for c in mine])}
     res = {
         "what": "Cash flows and ruin (SPEC.md 4.7 / 5.6) at configs[1]'s shape (N = 16, T = 252, 10^6 paths, horizons 21 / 63 / 126 / 252), "
@@ -123,7 +125,7 @@ def summarize(d, rounds, warm, calls_json):
                 "(nu = 5) draws with 0.001 paid in per step (no ruin) against the twin without cash flows (mc_paths_hz_kernel, "
                 "mc_paths_boot_hz_kernel, mc_paths_t_hz_kernel), from one rocprofv3 --kernel-trace --stats process; every configuration "
                 f"warmed up ({warm} calls), then {rounds} rounds that each run every configuration once (twins and variants alternate); "
-                "medians over the rounds and ratios of the medians; *_again is the A/A pair.  hist_kernel_ms / count_rows_kernel_ms: the "
+                "medians over the rounds and ratios of the medians; *_again is the A/A pair.  hist_kernel_ms / count_rows_kernel_ms (count_kernel<RuinedShort>, the kernel behind launch_count_rows): the "
                 "dispatches of those kernels summed per call.  ties_ruin / ties_zero: synthetic_market(3), equal weights, T = 60, "
                 "horizons 12 .. 60, 10^6 paths, 0.0165 taken out per step (about 45 % of the paths end at +0) against an all-zero "
                 "schedule.  Whole-call wall-clock medians from two more processes without the profiler (the same command twice: the "

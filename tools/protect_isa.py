@@ -4,8 +4,8 @@ translation unit; mcp_paths_inst.hip at -DMCP_NB=1, 4, 13 and 16), the parent tr
 Section 1 is tools/isa_digests.py's comparison per unit; section 2 lists mc_paths_pi_kernel at those NB, KT = 1 and 8 and its four
 variants (GARCH or jump walk, with or without the drawdown) next to the twin without protection -- mc_paths_g_hz_kernel,
 mc_paths_g_dd_kernel, mc_paths_j_hz_kernel, mc_paths_j_dd_kernel of the same NB and KT: the compiler's figures, the scratch_
-instructions of the kernel and of its walk, and the step loop's instruction mix; section 3 is count_below_kernel next to
-count_rows_kernel."""
+instructions of the kernel and of its walk, and the step loop's instruction mix; section 3 is count_kernel<BelowPair> next to
+count_kernel<RuinedShort>."""
 import os
 import sys
 import textwrap
@@ -22,7 +22,7 @@ HEADER = [
     "1. tools/isa_digests.py BEFORE AFTER per unit: the kernel symbols of the parent's listing, of this tree's, and how many of the "
     "parent's this tree keeps in all five figures (code digest, NumVgprs, ScratchSize, Occupancy, LDS).  The symbols this tree adds "
     "are the 8 mc_paths_pi_kernel instantiations per path unit (GARCH or jump walk, with or without the drawdown, KT = 1 and 8) and "
-    "count_below_kernel in mcp_stats_kernels.hip.",
+    "count_kernel<BelowPair> in mcp_stats_kernels.hip.",
     "2. mc_paths_pi_kernel<NB, KT, 1, JP, DD> (g: the GARCH walk, which also serves Gaussian and Student-t requests; j: the jump walk; "
     "dd: with the drawdown state): SGPRs, VGPRs, the private segment the compiler reserves (ScratchSize: on this compiler also the home "
     "of SGPRs parked in VGPR lanes, so it is not a count of accesses), occupancy as the compiler reports it, the scratch_ instructions "
@@ -40,7 +40,7 @@ HEADER = [
     "(about 130 v_readlane / v_writelane per step at NB = 4).  At NB <= 4, KT = 1 the jump-walk kernels take MCP_MIN_WAVES_PI = 5 "
     "(87 to 95 VGPRs, occupancy 5 where the twin has 6): at 6 waves they reloaded one spilled pair inside the step loop.  No kernel "
     "has a scratch_ instruction in its step loop or walk.",
-    "3. count_below_kernel next to count_rows_kernel (mcp_stats_kernels.hip): the same ballot-and-popcount loop with two compares "
+    "3. count_kernel<BelowPair> next to count_kernel<RuinedShort> (mcp_stats_kernels.hip): the same ballot-and-popcount loop with two compares "
     "against the row's own thresholds.",
 ]
 VARIANTS = (("g", 0, 0, "mc_paths_g_hz_kernel", "PathArgsGHZ"), ("g dd", 0, 1, "mc_paths_g_dd_kernel", "PathArgsGDD"),
@@ -83,7 +83,7 @@ def main(before, after):
     ks = kernels(path)
     out.append("## count kernels: symbol | digest (instructions) NumVgprs ScratchSize Occupancy LDS")
     for s in sorted(ks):
-        if "count_below_kernel" in s or "count_rows_kernel" in s:
+        if "count_kernel" in s:                               # count_kernel<RuinedShort>, count_kernel<BelowPair>
             d = ks[s]
             out.append(f"{s} | {d[0]} ({d[1]}) {d[2]} {d[3]} {d[4]} {d[5]}")
     print("\n".join(out))
